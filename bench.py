@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the oscillator-bank + mixer hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,21 +18,24 @@ the envelope's sustain spans the whole run (no silent voices).  With N > 1 the v
 across ranks and the float64 partial buses are summed to rank 0 by RCCL: `--scaling weak` (default)
 N x 1024 voices (configs[3] at N = 8), `--scaling strong` 8192 voices whatever N.
 
-Timing: W untimed warm-up steps, then PASSES of exactly K steps, each pass bracketed by barrier +
-device synchronisation on both sides and clocked on every rank (maximum over ranks).  Passes repeat
-(consecutive blocks of the same stream) until the timed passes add up to >= --min-seconds (5.5 s): one
-pass of the driver's K = 20 lasts under a millisecond, less than the GPU's clock governor needs to
-leave its idle state (the first ~50 ms of a run are up to 25 % slower), so a single pass measures the
-governor, not the kernel.  `value` / `ms_per_step` are those of the MEDIAN pass (`passes` lists count,
-median, min, first); a step stays one block.
+Timing: W untimed warm-up steps, then ONE pass of exactly K timed steps, bracketed by barrier + device
+synchronisation on both sides and clocked on every rank (maximum over ranks); `ms_per_step` = that pass / K.
+The GPU's clock governor needs ~50 ms of load to leave its idle state (the first blocks of a run are up to
+25 % slower), so the warm-up goes on -- the first timed blocks rendered into a buffer of its own, the timed
+steps unmoved -- until it has lasted 0.2 s (WARM_SECONDS).  `--min-seconds S` (> 0) repeats passes of K steps (consecutive
+blocks of the same stream) until they add up to >= S seconds, and `value` / `ms_per_step` are then those
+of the MEDIAN pass (`passes` lists count, median, min, first); a step stays one block.
 
 value = voice-samples mixed per second over all ranks / 1e6 ("Msamples/s"), inputs (the voice table)
-resident in HBM before the timed region.  The same run also times the other BASELINE configs
-(`configs`), the reference-shaped two-step path (voices materialised as float32 PCM in HBM, then the
-HBM-bound mixer kernel), the PCM rows (resample = configs[4], integer mixer chain, audioop.add ...) and
-the CPU oracle (pure-Python generators; its C restatement on one core and on all host cores) on a bounded sample -- reported
-beside, never as `value`.  Also beside: `staggered_notes` (a table of 22 528 notes that do not move in lock-step, one-second blocks
-and 4096-frame chunks), `config4` at N = 1 (the 8192-voice table; one rank's share through the RCCL ring) and `verified` (the last
+resident in HBM before the timed region.  A plain run does that and nothing else: set-up, warm-up, the
+timed steps, `--dump-outputs DIR` (the float32 stereo bus of the last timed step as DIR/stereo_bus.npy)
+and the line.  `--full` also times, after the headline, the other BASELINE configs (`configs`), the
+reference-shaped two-step path (voices materialised as float32 PCM in HBM, then the HBM-bound mixer
+kernel), the PCM rows (resample = configs[4], integer mixer chain, audioop.add ...) and the CPU oracle
+(pure-Python generators; its C restatement on one core and on all host cores) on a bounded sample -- reported
+beside, never as `value`.  Also beside under `--full`: `staggered_notes` (a table of 22 528 notes that do not move in lock-step,
+one-second blocks and 4096-frame chunks), `config4` at N = 1 (the 8192-voice table; one rank's share through the RCCL ring),
+the int16 stream, runs of blocks, the lone call, the job from frame 0, the per-rank exchange figures and `verified` (the last
 timed block against a fresh single render, bit for bit).
 """
 from __future__ import annotations
@@ -822,6 +825,21 @@ def config_rows(N, prof=None, only=None, K=20):
 
 
 COMPACT_LIMIT = 4096           # bytes of the ONE line on stdout (the driver's parser gave up on a 22.8 KB line)
+DUMP_LIMIT = 64 << 20          # bytes written by --dump-outputs at most
+WARM_SECONDS = 0.2             # the least warm-up of the headline, whatever --warmup says (the clocks need ~0.05 s of load)
+SIDE_STEPS = 100               # --full: the side rows use min(--steps, this) where they loop or run blocks (--steps only sizes the headline beyond it)
+
+
+def dump_outputs(directory, name: str, a) -> None:
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as DIR/<name>.npy.  Past DUMP_LIMIT, a fixed
+    seeded sample of its rows (the same rows in every run of the same arguments, so that two builds compare output for output)."""
+    import numpy as np
+    if a.nbytes > DUMP_LIMIT:
+        keep = DUMP_LIMIT // (a.nbytes // len(a))
+        a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / (name + ".npy"), a)
 
 
 def write_detail(out: dict, path=None):
@@ -953,10 +971,15 @@ def main() -> int:
     ap.add_argument("--frames", type=int, default=SR, help="frames per step (block size)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: 1024 voices per GPU; strong: 8192 voices in total (BASELINE configs[3]) whatever --gpus")
-    ap.add_argument("--min-seconds", type=float, default=5.5,
-                    help="passes of K steps repeat until they add up to this much timed work (5.5 s: longer than the 5 s at which the driver samples amd-smi, "
-                         "so that its independent busy / power signal sees the timed region -- VERDICT r03; the clock governor needs 0.05 s)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="0 (default): one pass of exactly K timed steps; > 0: passes of K steps repeat until they add up to this much timed work "
+                         "(at least three passes; value / ms_per_step are the median pass's)")
     ap.add_argument("--max-passes", type=int, default=40000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every side measurement: the other configs, the two-step and int16 routes, the PCM rows, "
+                         "runs of blocks, the lone call, the job from frame 0, the per-rank exchange, the CPU baselines and the `verified` self-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the float32 stereo bus of the last timed step (rank 0) to DIR/stereo_bus.npy")
     ap.add_argument("--cpu-frames", type=int, default=12288, help="frames of the CPU baseline sample (0 = skip)")
     ap.add_argument("--no-cpu-all-cores", action="store_true")
     ap.add_argument("--no-pcm-rows", action="store_true", help="skip the resample / integer-mix rows")
@@ -970,10 +993,15 @@ def main() -> int:
     ap.add_argument("--reduce-batch", type=int, default=8, help="blocks per RCCL reduce when --gpus > 1 (also the length of a run of pipelined renders)")
     args = ap.parse_args()
 
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     dry = os.environ.get("SYNTHHIP_BENCH_DRY_RUN") == "1"
     if dry:
+        if args.dump_outputs:
+            ap.error("--dump-outputs needs the GPU (a dry run renders nothing)")
         args.no_two_step = args.no_configs = args.no_pcm_rows = True
         args.cpu_frames = 0
+    full = args.full
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: this process becomes one (the ranks are copies of this command with the launcher's environment)
         if not dry:
@@ -1018,6 +1046,7 @@ def main() -> int:
         return 3
 
     K, Wm, F = args.steps, args.warmup, args.frames
+    Ks = min(K, SIDE_STEPS)         # the side rows' loop length and run of blocks: a run of Ks blocks holds a ring of Ks x 8 F bytes in HBM
     if args.only_config == "staggered":
         print(json.dumps({"only_config": "staggered", "library": N.lib().sh_version().decode(), "configs": {"staggered_notes": staggered_row(N, F)}}), flush=True)
         return 0
@@ -1032,7 +1061,7 @@ def main() -> int:
                           "configs": {"job_from_frame_0": job_row(N, local, F, Wm, committed_profile(), with_run=False)}}), flush=True)
         return 0
     if args.only_config:
-        rows = config_rows(N, committed_profile(), only=args.only_config, K=K)
+        rows = config_rows(N, committed_profile(), only=args.only_config, K=Ks)
         print(json.dumps({"only_config": args.only_config, "library": N.lib().sh_version().decode(), "configs": rows}), flush=True)
         return 0
     total_voices = STRONG_VOICES if args.scaling == "strong" else VOICES_PER_GPU * world
@@ -1053,6 +1082,16 @@ def main() -> int:
         bank.render_device(F, s * F)
     bank.flush()
     barrier()
+    # the clock governor leaves its idle state only after ~50 ms of load: each rank's GPU goes on rendering the first timed blocks into a
+    # buffer of its own (no collective; the timed steps and their results do not move) until WARM_SECONDS of warm-up have passed
+    if not dry:
+        warm = N.DeviceBuffer(F * 8)
+        t_warm = time.perf_counter() + WARM_SECONDS
+        while time.perf_counter() < t_warm:
+            for s in range(8):
+                bank.local.render_device(F, (Wm + s) * F, bus_f32=warm)
+            N.sync()
+        warm.free()
     passes = []               # (wall s, HIP-event ms) of each pass of K steps, max over ranks
     step0, timed = Wm, 0.0
     host_enqueue = 0.0
@@ -1061,7 +1100,7 @@ def main() -> int:
         t0 = time.perf_counter()
         N.timer_start()
         for s in range(K):
-            bank.render_device(F, (step0 + s) * F)
+            last_bus = bank.render_device(F, (step0 + s) * F)
         bank.flush()
         host_enqueue = time.perf_counter() - t0      # host time to enqueue all K steps (launches are asynchronous)
         ev_ms = N.timer_stop()                       # HIP events on the library stream (also synchronises it)
@@ -1071,12 +1110,17 @@ def main() -> int:
         passes.append((wall, ev_ms))
         step0 += K
         timed += wall
-        if (timed >= args.min_seconds and len(passes) >= 3) or len(passes) >= args.max_passes:
+        if args.min_seconds <= 0 or (timed >= args.min_seconds and len(passes) >= 3) or len(passes) >= args.max_passes:
             break
+    # the caller's result of the last timed step: the float32 stereo bus of that block (on rank 0, the root of the reduce; final after
+    # the barrier's synchronisation of the render and communication streams)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        dump_outputs(args.dump_outputs, "stereo_bus", last_bus.download(np.float32, F * 2).reshape(F, 2))
     # self-check: the last block of the last timed pass (left in the bank's bus buffer by the pipelined run) against a fresh
     # single render of the same block (records by a prepare kernel, fold by k_bus_combine: none of the run's machinery)
     verified = None
-    if world == 1 and not dry:
+    if full and world == 1 and not dry:
         import numpy as np
         last = (step0 - 1) * F
         got = bank._bus32[0].download(np.float32, F * 2)
@@ -1193,14 +1237,14 @@ def main() -> int:
     }
 
     # ---- multi-GPU: what each rank spends on rendering and what the exchange adds ----
-    if world > 1 and not dry:
+    if full and world > 1 and not dry:
         ring = [N.DeviceBuffer(F * 16) for _ in range(4)]
         pos = [step0]
 
         def local_step():
             bank.local.render_device(F, pos[0] * F, bus_f32=None, bus_f64=ring[pos[0] & 3])
             pos[0] += 1
-        render_ms = steady(N, local_step, min_seconds=0.1, reps=K)
+        render_ms = steady(N, local_step, min_seconds=0.1, reps=Ks)
         nval = bank.batch * F * 2
         msg = N.DeviceBuffer(nval * 8)
         msg.zero()
@@ -1223,14 +1267,14 @@ def main() -> int:
         msg.free()
 
     # ---- the same stream of blocks delivered as int16 PCM (what a player consumes): quantised by the fold itself ----
-    if world == 1:
+    if full and world == 1:
         ring = [N.DeviceBuffer(F * 4) for _ in range(4)]
         pos = [step0]
 
         def pcm_step():
             bank.local.render_pcm_device(F, pos[0] * F, pcm=ring[pos[0] & 3])
             pos[0] += 1
-        pcm_ms = steady(N, pcm_step, min_seconds=0.1, reps=K)
+        pcm_ms = steady(N, pcm_step, min_seconds=0.1, reps=Ks)
         out["int16_stream"] = {"ms_per_step": pcm_ms, "value": local_voices * F / (pcm_ms / 1e3) / 1e6, "unit": "Msamples/s",
                                "note": "sh_bank_render_pcm into a ring of 4 buffers: saturated int16 stereo straight from the "
                                        "partial-bus fold, launches pipelined like the headline's"}
@@ -1239,29 +1283,29 @@ def main() -> int:
 
     # ---- BASELINE's job taken literally: 10 s from frame 0 in blocks of F -- block 0 is the notes' attack, decay and a dozen
     # binades of the phase sum (a segmented launch); the passes above measure the steady state
-    if world == 1 and not dry:
+    if full and world == 1 and not dry:
         out["job_from_frame_0"] = job_row(N, bank.local, F, step0, prof)
         out["job_from_frame_0"]["x_steady"] = out["job_from_frame_0"]["ms"] / 10.0 / out["ms_per_step"]
 
     # ---- the same stream asked for K blocks per call (sh_bank_render_run into a ring of K windows of one allocation: one crossing
     # of the ABI and one launch per K blocks): what a latency-bound caller gains, and what the host then spends per block ----
-    if world == 1 and not dry and not args.no_runs:
-        cont = bank.local.make_ring(F, K)
+    if full and world == 1 and not dry and not args.no_runs:
+        cont = bank.local.make_ring(F, Ks)
         rpos = [step0]
 
         def run_k():
-            bank.local.render_run(F, K, rpos[0] * F, ring=cont)
-            rpos[0] += K
+            bank.local.render_run(F, Ks, rpos[0] * F, ring=cont)
+            rpos[0] += Ks
         for _ in range(2):
             run_k()
         sp_run = {}
-        run_ms = steady(N, run_k, min_seconds=0.3, reps=4, spread=sp_run) / K
+        run_ms = steady(N, run_k, min_seconds=0.3, reps=4, spread=sp_run) / Ks
         t0 = time.perf_counter()
         for _ in range(50):
             run_k()
-        run_host = (time.perf_counter() - t0) / (50 * K)
+        run_host = (time.perf_counter() - t0) / (50 * Ks)
         N.sync()
-        out["run_of_blocks"] = {"blocks_per_call": K, "ms_per_step": run_ms, "min_ms_per_step": sp_run["min_ms"] / K, "max_ms_per_step": sp_run["max_ms"] / K,
+        out["run_of_blocks"] = {"blocks_per_call": Ks, "ms_per_step": run_ms, "min_ms_per_step": sp_run["min_ms"] / Ks, "max_ms_per_step": sp_run["max_ms"] / Ks,
                                 "value": local_voices * F / (run_ms / 1e3) / 1e6, "unit": "Msamples/s",
                                 "host_enqueue_ms_per_step": run_host * 1e3, "x_headline": run_ms / (wall * 1e3 / K),
                                 "note": "K blocks per call (VoiceBank.render_run): a launch of K x %d frames renders them -- fewer voice groups per "
@@ -1270,9 +1314,9 @@ def main() -> int:
 
     # ---- a render call that stands alone (a caller that does not stream: VERDICT r05 item 3): the device synchronised in front of it, a few
     # pipelined renders before that so that the clocks are what a busy caller sees; HIP events around the one call ----
-    if world == 1 and not dry and not args.no_runs:
+    if full and world == 1 and not dry and not args.no_runs:
         ring = [N.DeviceBuffer(F * 8) for _ in range(4)]
-        lpos = [step0 + 7 * K]
+        lpos = [step0 + 7 * Ks]
         got = []
         for _ in range(30):
             for _ in range(3):
@@ -1292,12 +1336,12 @@ def main() -> int:
 
     # ---- notes that do not move in lock-step: 1024 players re-triggering SURVEY 8(d)'s literal note (0.76 s of sound) every second,
     # onsets spread uniformly over the second; one-second blocks 1 .. 20 of the piece ----
-    if world == 1 and not args.no_configs:
+    if full and world == 1 and not args.no_configs:
         out["staggered_notes"] = staggered_row(N, F, prof)
         out["staggered_notes"]["x_headline"] = out["staggered_notes"]["ms_per_step"] / out["ms_per_step"]     # (same run, same box, same protocol)
 
     # ---- two-step path on rank 0's shard: materialise (generate) + HBM-bound mix ----
-    if not args.no_two_step:
+    if full and not args.no_two_step:
         nv = bank.local.nvoices
         F2 = F * 10 if nv * F * 10 * 4 <= (8 << 30) else F     # 10 s blocks: 1.97 GB of voices, far past the 256 MB L3
         vbuf = N.DeviceBuffer(nv * F2 * 4)
@@ -1422,15 +1466,15 @@ def main() -> int:
             b_.free()
 
     # ---- the other BASELINE configs (rank 0, N = 1) ----
-    if rank == 0 and world == 1 and not args.no_configs:
-        out["configs"] = config_rows(N, prof, K=K)
+    if full and rank == 0 and world == 1 and not args.no_configs:
+        out["configs"] = config_rows(N, prof, K=Ks)
 
     # ---- the integer / float PCM rows (rank 0): Sample.resample (configs[4]) and the mixer chain ----
-    if rank == 0 and not args.no_pcm_rows:
+    if full and rank == 0 and not args.no_pcm_rows:
         out["pcm_rows"] = pcm_rows(N)
 
     # ---- CPU baseline (rank 0, N = 1 only) ----
-    if rank == 0 and world == 1 and args.cpu_frames > 0:
+    if full and rank == 0 and world == 1 and args.cpu_frames > 0:
         out["cpu_baseline"] = cpu_baseline(args.cpu_frames, all_cores=not args.no_cpu_all_cores)
         out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
     if out["rccl"]["version"] is None and not dry:

@@ -268,3 +268,17 @@ def test_rendezvous_never_unpickles_and_drops_strangers():
     big = {"x": "y" * (dist.Rendezvous.MAX_MESSAGE + 1)}
     with pytest.raises(ValueError):
         dist.Rendezvous._send_obj(None, big)
+
+
+def test_a_plain_dry_run_times_one_pass_of_exactly_k_steps(tmp_path):
+    """Without --min-seconds the headline is ONE pass of exactly --steps steps, so that a caller can size --steps from ms_per_step;
+    --dump-outputs needs the GPU and is refused by a dry run."""
+    detail = tmp_path / "detail.json"
+    p = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "13", "--warmup", "1", "--detail", str(detail)], {"SYNTHHIP_BENCH_DRY_RUN": "1"})
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = _line(p)
+    assert d["steps"] == 13 and d["passes"]["count"] == 1
+    full = json.loads(detail.read_text())
+    assert full["passes"]["steps_per_pass"] == 13 and full["passes"]["median_ms_per_step"] == pytest.approx(full["ms_per_step"])
+    p = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(tmp_path / "out")], {"SYNTHHIP_BENCH_DRY_RUN": "1"})
+    assert p.returncode == 2 and "--dump-outputs needs the GPU" in p.stderr and not (tmp_path / "out").exists()

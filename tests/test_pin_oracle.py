@@ -10,18 +10,46 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 
 
+def _stand_in_reference(tmp_path):
+    """A reference tree whose synthplayer package is the oracle under upstream's module names: pinning it must find no difference."""
+    pkg = tmp_path / "stand_in" / "synthplayer"
+    pkg.mkdir(parents=True)
+    (pkg / "__init__.py").write_text("")
+    (pkg / "oscillators.py").write_text("from oracle.synth_oracle import *  # noqa: F401,F403\n")
+    (pkg / "params.py").write_text("from oracle.synth_oracle import norm_samplerate, norm_nchannels, norm_samplewidth, norm_osc_blocksize  # noqa: F401\n")
+    (pkg / "sample.py").write_text(
+        "from oracle.sample_oracle import RefSample\n"
+        "from oracle.synth_oracle import quantise\n\n\n"
+        "class _Frames(list):\n"
+        "    def get_frame_array(self):\n"
+        "        return self\n\n\n"
+        "class Sample(RefSample):\n"
+        "    @classmethod\n"
+        "    def from_raw_frames(cls, frames, samplewidth, samplerate, numchannels):\n"
+        "        return cls(frames, samplewidth, samplerate, numchannels)\n\n"
+        "    @classmethod\n"
+        "    def from_osc_block(cls, block, samplerate, samplewidth=2):\n"
+        "        return _Frames(quantise(block, samplewidth))\n")
+    return pkg.parent
+
+
 def test_pin_oracle_outcome(tmp_path):
-    out = tmp_path / "pin.json"
-    p = subprocess.run([sys.executable, str(ROOT / "tools" / "pin_oracle.py"), "--quick", "--json", str(out)],
-                       capture_output=True, text=True, timeout=900)
-    outcome = json.loads(out.read_text())
-    print("pin_oracle: rc %d, status %r, reference %r" % (p.returncode, outcome["status"], outcome["reference"]))
-    assert p.returncode in (0, 3), p.stdout[-3000:] + p.stderr[-2000:]
-    if p.returncode == 3:
-        assert outcome["status"] == "reference absent" and outcome["reference"] is None
-        assert "UNPINNED" in p.stdout
-    else:
-        assert outcome["status"] == "pinned" and outcome["differences"] == []
+    """Both outcomes on trees of the test's own: an empty one (reference absent, exit 3) and the oracle standing in for the package (the
+    whole recipe runs and pins, exit 0).  A synthplayer installed in this interpreter takes precedence over either tree: then it is pinned."""
+    for tree, want in ((tmp_path / "empty", 3), (_stand_in_reference(tmp_path), 0)):
+        tree.mkdir(exist_ok=True)
+        out = tmp_path / ("pin_%s.json" % tree.name)
+        p = subprocess.run([sys.executable, str(ROOT / "tools" / "pin_oracle.py"), "--quick", "--json", str(out), "--reference", str(tree)],
+                           capture_output=True, text=True, timeout=900)
+        outcome = json.loads(out.read_text())
+        print("pin_oracle: rc %d, status %r, reference %r" % (p.returncode, outcome["status"], outcome["reference"]))
+        assert p.returncode in (0, want), p.stdout[-3000:] + p.stderr[-2000:]
+        if p.returncode == 3:
+            assert outcome["status"] == "reference absent" and outcome["reference"] is None
+            assert "UNPINNED" in p.stdout
+        else:
+            assert outcome["status"] == "pinned" and outcome["differences"] == []
+            assert outcome["reference"] in ("installed", str(tree))
 
 
 def test_case_grid_runs_against_the_oracle_itself():
@@ -39,11 +67,12 @@ def test_case_grid_runs_against_the_oracle_itself():
     assert len(P.oscillator_cases(False)) > 200
 
 
-def test_api_audit_exits_3_here_and_its_code_runs_against_the_oracle():
+def test_api_audit_exits_3_here_and_its_code_runs_against_the_oracle(tmp_path):
     """--api: the signature audit of the reference's public classes against synthesizer_amd's.  Reference absent: exit 3.  So that the
     audit itself cannot rot it runs here with the ORACLE standing in for the reference: the oracle restates upstream's classes with
     upstream's signatures as recalled, so the product's constructors must at least agree with those -- names, order, defaults."""
-    p = subprocess.run([sys.executable, str(ROOT / "tools" / "pin_oracle.py"), "--api"], capture_output=True, text=True, timeout=300)
+    p = subprocess.run([sys.executable, str(ROOT / "tools" / "pin_oracle.py"), "--api", "--reference", str(tmp_path)],
+                       capture_output=True, text=True, timeout=300)
     assert p.returncode in (0, 1, 3), p.stderr[-2000:]
     if p.returncode == 3:
         assert "UNPINNED" in p.stdout

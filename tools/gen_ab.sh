@@ -2,7 +2,7 @@
 # A/B of the materialisation kernel under variant libraries: tools/gen_ab.sh LIB [LIB ...]   (GPU box, repo root)
 for LIB in "$@"; do
   for rep in 1 2; do
-    SYNTHHIP_ALLOW_STALE=1 SYNTHHIP_LIB=$LIB python bench.py --no-configs --no-pcm-rows --cpu-frames 0 --min-seconds 0.3 --no-runs --detail /tmp/gen_ab_detail.json > /dev/null 2>/tmp/gen_ab.err || tail -3 /tmp/gen_ab.err
+    SYNTHHIP_ALLOW_STALE=1 SYNTHHIP_LIB=$LIB python bench.py --full --no-configs --no-pcm-rows --cpu-frames 0 --min-seconds 0.3 --no-runs --detail /tmp/gen_ab_detail.json > /dev/null 2>/tmp/gen_ab.err || tail -3 /tmp/gen_ab.err
     python - "$LIB" <<'P'
 import json, sys
 d = json.load(open("/tmp/gen_ab_detail.json"))

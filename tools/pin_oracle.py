@@ -36,7 +36,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 
-def find_reference():
+def find_reference(tree=None):
     """synthplayer as installed, or from a tree mounted at /root/reference (this container only)."""
     try:
         import synthplayer                                   # noqa: F401
@@ -44,8 +44,9 @@ def find_reference():
     except ImportError:
         pass
     ref = Path("/root/reference")
+    ref = Path(tree) if tree is not None else ref          # --reference: a tree of the caller's choosing
     for cand in (ref, ref / "synthesizer", ref / "src"):
-        if (cand / "synthplayer" / "oscillators.py").exists():
+        if _readable_file(cand / "synthplayer" / "oscillators.py"):
             sys.path.insert(0, str(cand))
             try:
                 import synthplayer                           # noqa: F401
@@ -53,6 +54,13 @@ def find_reference():
             except ImportError:
                 sys.path.pop(0)
     return None
+
+
+def _readable_file(path: Path) -> bool:
+    try:
+        return path.is_file()
+    except OSError:                                        # (a tree this user may not read holds no reference for it)
+        return False
 
 
 def take(osc, n, skip=0):
@@ -397,8 +405,10 @@ def main() -> int:
                          "(increment mul / div, Square int2 / mod1, Pulse < / <=, quantise int / round, envelope < / <=; singly and in pairs) and "
                          "print the readings under which it EQUALS the reference; ends with the readings that explain every such case")
     ap.add_argument("--json", default=None, help="write the outcome here as JSON")
+    ap.add_argument("--reference", metavar="DIR", default=None,
+                    help="look for synthplayer/oscillators.py in DIR (or DIR/synthesizer, DIR/src) instead of the build container's mount")
     args = ap.parse_args()
-    where = find_reference()
+    where = find_reference(args.reference)
     outcome = {"reference": where, "status": None, "differences": []}
     if where is None:
         outcome["status"] = "reference absent"
