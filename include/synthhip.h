@@ -377,6 +377,36 @@ int sh_bank_mixdown_i16_async(sh_bank* b, uint64_t start, uint32_t nframes, doub
 int sh_bank_generate_rows_i16(sh_bank* b, uint64_t start, uint32_t nframes, const sh_buf* rows_f64, size_t row_stride,
                               double scale, sh_buf* voices_out, size_t stride);
 
+/* ---- chain maps: the mixer's saturating chain over a RANGE of voices, as a value ------------------------------------------
+ * mixed = audioop.add(mixed, voice, 2) down a range of voices is, per int16 value, the map x -> clamp(x + add, lo, hi).  One map
+ * per value, 8 bytes (int32 add; int16 lo; int16 hi -- as a pair of int32: .x = add, .y = lo | hi << 16, little-endian).  A mono
+ * block has nframes maps, a stereo block 2 * nframes, interleaved L / R like the samples.  Identity: (0, -32768, 32767); the
+ * map of one voice sample s: (s, -32768, 32767).  f then g: (a1 + a2, clamp(lo1 + a2, lo2, hi2), clamp(hi1 + a2, lo2, hi2)).
+ * Applied in voice order to silence the maps of a table's consecutive ranges give the chain over the whole table; applied to x0
+ * they give audioop.add(x0, voice0), then voice1, ... -- the chain continued from an existing sample.
+ * add saturates at +-2^17 (SH_CHAIN_ADD_MAX) everywhere the library makes or reads a map: for |add| >= 65535 every int16 x
+ * already lands on lo or hi, so the map on int16 inputs is the same, and any count of voices or parts stays inside int32. */
+typedef struct sh_chain_map {
+    int32_t add;
+    int16_t lo;
+    int16_t hi;
+} sh_chain_map;
+#define SH_CHAIN_ADD_MAX 131072
+/* sh_bank_mixdown_i16 (same voices, quantiser, boundary guard and choice of route per 65 536-frame stretch, same 32 768-voice
+ * limit) ending in the composed map of the bank's voices per frame: parts_out holds nframes sh_chain_map.  _async / overflow
+ * semantics as sh_bank_mixdown_i16. */
+int sh_bank_mixdown_i16_parts(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* parts_out);
+int sh_bank_mixdown_i16_parts_async(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* parts_out);
+/* sh_mix_chain_i16 / sh_mix_chain_pan_i16 ending in the composed map per sample (parts_out: nsamples, resp. 2 * nframes, maps). */
+int sh_mix_chain_i16_parts(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nsamples, sh_buf* parts_out);
+int sh_mix_chain_pan_i16_parts(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nframes, const sh_buf* factors_lr,
+                               sh_buf* parts_out);
+/* nparts planes of nvalues maps each, plane k at parts[k * part_stride ..] (in maps), in order: composed into one map per value
+ * (out_parts may be plane 0 itself), or applied to x0 (nvalues int16; NULL: silence) into out_i16.  nparts == 0: the identity. */
+int sh_chain_parts_compose(const sh_buf* parts, uint32_t nparts, size_t part_stride, uint32_t nvalues, sh_buf* out_parts);
+int sh_chain_parts_apply(const sh_buf* parts, uint32_t nparts, size_t part_stride, uint32_t nvalues, const sh_buf* x0_i16,
+                         sh_buf* out_i16);
+
 /* ---- mixer sum bus over materialised voices ------------------------------------------ */
 /* float32: bus[i] = sum_v gains[v] * voices[v*stride+i]; gains = device buffer of nvoices x (l, r) floats */
 int sh_mix_bus_f32(const sh_buf* voices, uint32_t nvoices, size_t stride, uint32_t nframes,
@@ -524,6 +554,10 @@ int sh_dist_wait_slot(int slot);
 int sh_dist_mark_slot(int slot);
 int sh_dist_reduce_bus_lagged(sh_buf* bus_f64, size_t nvalues, int root, sh_buf* bus_f32, int slot);
 int sh_dist_wait_slot_keep(int slot);
+/* This rank's nvalues chain maps (sh_chain_map) to root's gathered[rank * nvalues ..] on the library stream (ncclGather where
+ * librccl has it, else grouped ncclSend / ncclRecv); gathered is only read on root.  Without a communicator, or in a world of
+ * one: a copy. */
+int sh_dist_gather_parts(const sh_buf* parts, size_t nvalues, int root, sh_buf* gathered);
 /* float64 bus -> float32 bus after the reduce */
 int sh_bus_finalize(const sh_buf* bus_f64, size_t nvalues, sh_buf* bus_f32);
 

@@ -122,6 +122,12 @@ _SIGNATURES = {
     "sh_mix_bus_f32": (C.c_int, [_P, C.c_uint32, C.c_size_t, C.c_uint32, _P, _P]),
     "sh_mix_chain_i16": (C.c_int, [_P, C.c_uint32, C.c_size_t, C.c_uint32, _P]),
     "sh_mix_chain_pan_i16": (C.c_int, [_P, C.c_uint32, C.c_size_t, C.c_uint32, _P, _P]),
+    "sh_bank_mixdown_i16_parts": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_double, _P]),
+    "sh_bank_mixdown_i16_parts_async": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_double, _P]),
+    "sh_mix_chain_i16_parts": (C.c_int, [_P, C.c_uint32, C.c_size_t, C.c_uint32, _P]),
+    "sh_mix_chain_pan_i16_parts": (C.c_int, [_P, C.c_uint32, C.c_size_t, C.c_uint32, _P, _P]),
+    "sh_chain_parts_compose": (C.c_int, [_P, C.c_uint32, C.c_size_t, C.c_uint32, _P]),
+    "sh_chain_parts_apply": (C.c_int, [_P, C.c_uint32, C.c_size_t, C.c_uint32, _P, _P]),
     "sh_mix_chain_gather_i16": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _P, C.c_size_t]),
     "sh_mix_chain": (C.c_int, [_P, C.c_uint32, C.c_size_t, C.c_uint32, C.c_int, _P]),
     "sh_mix_chain_gather": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_int, _P, C.c_size_t]),
@@ -166,6 +172,7 @@ _SIGNATURES = {
     "sh_dist_mark_slot": (C.c_int, [C.c_int]),
     "sh_dist_reduce_bus_lagged": (C.c_int, [_P, C.c_size_t, C.c_int, _P, C.c_int]),
     "sh_dist_wait_slot_keep": (C.c_int, [C.c_int]),
+    "sh_dist_gather_parts": (C.c_int, [_P, C.c_size_t, C.c_int, _P]),
     "sh_bus_finalize": (C.c_int, [_P, C.c_size_t, _P]),
 }
 

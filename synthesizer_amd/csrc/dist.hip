@@ -25,6 +25,11 @@ struct Rccl {
     ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;          // (optional: sh_dist_comm_info)
     ncclResult_t (*CommUserRank)(const ncclComm_t, int*) = nullptr;
     ncclResult_t (*GetVersion)(int*) = nullptr;
+    ncclResult_t (*Gather)(const void*, void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;   // (optional: sh_dist_gather_parts,
+    ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;            //  else grouped send / recv)
+    ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
+    ncclResult_t (*GroupStart)() = nullptr;
+    ncclResult_t (*GroupEnd)() = nullptr;
     ncclComm_t comm = nullptr;
     int rank = -1, world = 0;
     double* token = nullptr;     // 1-element device buffer for the barrier
@@ -63,6 +68,11 @@ int load_rccl() {
     *(void**)(&r.CommCount) = dlsym(r.lib, "ncclCommCount");
     *(void**)(&r.CommUserRank) = dlsym(r.lib, "ncclCommUserRank");
     *(void**)(&r.GetVersion) = dlsym(r.lib, "ncclGetVersion");
+    *(void**)(&r.Gather) = dlsym(r.lib, "ncclGather");
+    *(void**)(&r.Send) = dlsym(r.lib, "ncclSend");
+    *(void**)(&r.Recv) = dlsym(r.lib, "ncclRecv");
+    *(void**)(&r.GroupStart) = dlsym(r.lib, "ncclGroupStart");
+    *(void**)(&r.GroupEnd) = dlsym(r.lib, "ncclGroupEnd");
     return SH_OK;
 }
 
@@ -271,6 +281,45 @@ int sh_dist_wait_slot(int slot) {
     if (!r.comm) return sh::set_error(SH_ERR_RCCL, "sh_dist_wait_slot: sh_dist_init not called");
     if (slot < 0 || slot >= Rccl::SLOTS) return sh::set_error(SH_ERR_INVALID, "sh_dist_wait_slot: bad slot");
     SH_HIP(hipStreamWaitEvent(sh::state().stream, r.ev_done[slot], 0));    // no-op until the slot has been used
+    return SH_OK;
+}
+
+// The integer route across shards: every rank's chain maps (8 bytes per int16 value) to root, in rank order -- shards are contiguous
+// and ascend with rank, so root applies them in voice order (sh_chain_parts_apply).  The size of the float64 reduce it replaces.
+int sh_dist_gather_parts(const sh_buf* parts, size_t nvalues, int root, sh_buf* gathered) {
+    SH_REQUIRE_INIT();
+    Rccl& r = R();
+    const int world = r.comm ? r.world : 1, rank = r.comm ? r.rank : 0;
+    if (!parts || parts->bytes / 8 < nvalues) return sh::set_error(SH_ERR_INVALID, "sh_dist_gather_parts: parts buffer too small");
+    if (root < 0 || root >= world) return sh::set_error(SH_ERR_INVALID, "sh_dist_gather_parts: bad root");
+    if (rank == root && (!gathered || gathered->bytes / 8 / (size_t)world < nvalues))
+        return sh::set_error(SH_ERR_INVALID, "sh_dist_gather_parts: gathered buffer too small (world x nvalues maps on root)");
+    if (!nvalues) return SH_OK;
+    hipStream_t st = sh::state().stream;
+    char* dst = rank == root ? (char*)gathered->ptr + (size_t)rank * nvalues * 8 : nullptr;
+    if (world == 1) {
+        if (dst != parts->ptr) SH_HIP(hipMemcpyAsync(dst, parts->ptr, nvalues * 8, hipMemcpyDeviceToDevice, st));
+        return SH_OK;
+    }
+    if (r.Gather) {
+        SH_RCCL(r.Gather(parts->ptr, rank == root ? gathered->ptr : nullptr, nvalues, ncclUint64, root, r.comm, st));
+        return SH_OK;
+    }
+    if (!r.Send || !r.Recv || !r.GroupStart || !r.GroupEnd)
+        return sh::set_error(SH_ERR_RCCL, "sh_dist_gather_parts: librccl.so has neither ncclGather nor ncclSend / ncclRecv");
+    if (rank == root && dst != parts->ptr) SH_HIP(hipMemcpyAsync(dst, parts->ptr, nvalues * 8, hipMemcpyDeviceToDevice, st));
+    SH_RCCL(r.GroupStart());
+    if (rank == root) {
+        for (int k = 0; k < world; ++k) {
+            if (k == root) continue;
+            const ncclResult_t e = r.Recv((char*)gathered->ptr + (size_t)k * nvalues * 8, nvalues, ncclUint64, k, r.comm, st);
+            if (e != ncclSuccess) { (void)r.GroupEnd(); return rccl_error(e, "ncclRecv"); }
+        }
+    } else {
+        const ncclResult_t e = r.Send(parts->ptr, nvalues, ncclUint64, root, r.comm, st);
+        if (e != ncclSuccess) { (void)r.GroupEnd(); return rccl_error(e, "ncclSend"); }
+    }
+    SH_RCCL(r.GroupEnd());
     return SH_OK;
 }
 

@@ -721,6 +721,34 @@ __global__ __launch_bounds__(256) void k_mixdown_combine(const int2v* __restrict
     out[first + f] = (short)x;
 }
 
+// k_mixdown_combine's compose-only sibling (sh_bank_mixdown_i16_parts): the planes folded in order into ONE map per frame, stored as
+// sh_chain_map (include/synthhip.h) instead of applied to 0.  (|a| <= 32 768 per voice of the bank, at most 32 768 voices: int32;
+// saturated at +-SH_CHAIN_ADD_MAX on the way out, which leaves the map unchanged on int16 inputs.)
+__global__ __launch_bounds__(256) void k_mixdown_compose(const int2v* __restrict__ parts, uint32_t nplanes, size_t plane, uint32_t n,
+                                                         int2v* __restrict__ maps) {
+    const uint32_t f = (uint32_t)(sh::block_id() * 256 + threadIdx.x);
+    if (f >= n) return;
+    const int2v* __restrict__ p = parts + f;
+    int a = 0, L = -32768, U = 32767;
+    auto step = [&](const int2v v) {
+        const int lo = (int)(short)(uint16_t)((uint32_t)v.y & 0xFFFFu), hi = (int)(short)(uint16_t)((uint32_t)v.y >> 16);
+        L = min(max(L + v.x, lo), hi);
+        U = min(max(U + v.x, lo), hi);
+        a += v.x;
+    };
+    uint32_t k = 0;
+    for (; k + 4 <= nplanes; k += 4) {                          // four planes in flight
+        int2v v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = __builtin_nontemporal_load(p + (size_t)(k + u) * plane);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) step(v[u]);
+    }
+    for (; k < nplanes; ++k) step(p[(size_t)k * plane]);
+    a = min(max(a, -SH_CHAIN_ADD_MAX), SH_CHAIN_ADD_MAX);
+    maps[f] = (int2v){a, (int)((uint32_t)(uint16_t)L | ((uint32_t)(uint16_t)U << 16))};
+}
+
 // (Measured and dropped in round 3: the same materialisation walked ROW by row -- one record per workgroup held in SGPRs, contiguous runs
 // of a row per workgroup: 0.515 of HBM against 0.52; CHANGELOG item 38.)
 
@@ -981,18 +1009,23 @@ namespace {
 
 // frames [f0, f0 + len) of the call through int16 rows in a temporary and the chain kernel: where a voice needs the general code (the
 // attack and decay of the notes, voices of other kinds), whose rows the fold would have to take in voice order between the lean ones
-int mixdown_two_step(sh_bank* b, uint64_t start, uint32_t len, double scale, short* out, int* flag) {
+// (maps: the _parts form -- the chain's map per frame instead of its result, see k_mixdown_compose; out is then unused)
+int mixdown_two_step(sh_bank* b, uint64_t start, uint32_t len, double scale, short* out, int* flag, int2v* maps) {
     const size_t stride = ((size_t)len + 63) & ~(size_t)63;
     sh::Temp rows;
     int rc = rows.alloc((size_t)b->nvoices * stride * 2);
     if (rc) return rc;
     rc = generate_rows<short>(b, start, len, (short*)rows.buf.ptr, stride, scale, flag);
     if (rc) return rc;
+    if (maps) {
+        sh_buf m{maps, (size_t)len * 8, false, 0};
+        return sh_mix_chain_i16_parts(&rows.buf, b->nvoices, stride, len, &m);
+    }
     sh_buf o{out, (size_t)len * 2, false, 0};
     return sh_mix_chain_i16(&rows.buf, b->nvoices, stride, len, &o);
 }
 
-int mixdown_fused(sh_bank* b, uint64_t start, uint32_t len, double scale, short* out, int* flag) {
+int mixdown_fused(sh_bank* b, uint64_t start, uint32_t len, double scale, short* out, int* flag, int2v* maps) {
     constexpr uint32_t SEG = 65536;
     hipStream_t st = sh::state().stream;
     const uint32_t nchunks = sh::div_up(b->nvoices, 64), rsplit = 2, nplanes = nchunks * rsplit;
@@ -1026,25 +1059,24 @@ int mixdown_fused(sh_bank* b, uint64_t start, uint32_t len, double scale, short*
     if (lf == 16) SH_MIXDOWN(16); else if (lf == 8) SH_MIXDOWN(8); else SH_MIXDOWN(4);
 #undef SH_MIXDOWN
     SH_CHECK_LAUNCH("k_generate_lean_harm(fold)");
+    if (maps) {
+        hipLaunchKernelGGL(k_mixdown_compose, sh::grid1d(len, 256), dim3(256), 0, st, (const int2v*)parts.buf.ptr, nplanes, (size_t)len, len, maps);
+        SH_CHECK_LAUNCH("k_mixdown_compose");
+        return SH_OK;
+    }
     hipLaunchKernelGGL(k_mixdown_combine, sh::grid1d(len, 256), dim3(256), 0, st, (const int2v*)parts.buf.ptr, nplanes, (size_t)len, 0u, len, out);
     SH_CHECK_LAUNCH("k_mixdown_combine");
     return SH_OK;
 }
 
-}  // namespace
-
-int sh_bank_mixdown_i16_async(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* out_i16) {
-    SH_REQUIRE_INIT();
-    if (!b || !out_i16) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16: NULL argument");
-    if (nframes > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16: at most 2^32 - 65536 frames per call");
-    if (out_i16->bytes / 2 < nframes) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16: output buffer too small");
-    int rc = bank_check_plain(b, "sh_bank_mixdown_i16");
+// sh_bank_mixdown_i16 (out) and sh_bank_mixdown_i16_parts (maps): one walk over the stretches
+int bank_mixdown(const char* who, sh_bank* b, uint64_t start, uint32_t nframes, double scale, short* out, int2v* maps) {
+    int rc = bank_check_plain(b, who);
     if (rc || nframes == 0) return rc;
-    if (b->nvoices > 32768) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16: at most 32768 voices");
+    if (b->nvoices > 32768) return sh::set_error(SH_ERR_INVALID, "%s: at most 32768 voices", who);
     if (sh::state().quantise_round)
-        return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16: the fused quantiser truncates; under SH_OPT_QUANTISE_ROUND quantise float64 rows and fold them (sh_mix_chain_i16)");
+        return sh::set_error(SH_ERR_INVALID, "%s: the fused quantiser truncates; under SH_OPT_QUANTISE_ROUND quantise float64 rows and fold them (sh_mix_chain_i16)", who);
     int* flag = sh::state().flag + 1;
-    short* out = (short*)out_i16->ptr;
     // Stretches of whole 65 536-frame segments in which every voice takes the lean polynomial-Harmonics loop (its records then hold the
     // bank in voice order, silent voices -- which add nothing to a chain -- left out) are folded where the samples are made; the others
     // (the notes' attack and decay, banks with other kinds of voice, short calls) go through int16 rows and the chain kernel.
@@ -1063,11 +1095,40 @@ int sh_bank_mixdown_i16_async(sh_bank* b, uint64_t start, uint32_t nframes, doub
             if (fused && f1 - f0 >= 16 * SEG) break;          // (fused stretches: planes of 16 B per frame each -- 1024 voices: 0.5 GB per 2^20 frames; the chain is per frame, so cutting changes nothing)
             f1 += n1;
         }
-        rc = fused ? mixdown_fused(b, start + f0, f1 - f0, scale, out + f0, flag) : mixdown_two_step(b, start + f0, f1 - f0, scale, out + f0, flag);
+        short* o = out ? out + f0 : nullptr;
+        int2v* m = maps ? maps + f0 : nullptr;
+        rc = fused ? mixdown_fused(b, start + f0, f1 - f0, scale, o, flag, m) : mixdown_two_step(b, start + f0, f1 - f0, scale, o, flag, m);
         if (fused) sh::state().last_mixdown_fused += 1;
         f0 = f1;
     }
     return rc;
+}
+
+}  // namespace
+
+int sh_bank_mixdown_i16_async(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* out_i16) {
+    SH_REQUIRE_INIT();
+    if (!b || !out_i16) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16: NULL argument");
+    if (nframes > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16: at most 2^32 - 65536 frames per call");
+    if (out_i16->bytes / 2 < nframes) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16: output buffer too small");
+    return bank_mixdown("sh_bank_mixdown_i16", b, start, nframes, scale, (short*)out_i16->ptr, nullptr);
+}
+
+int sh_bank_mixdown_i16_parts_async(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* parts_out) {
+    SH_REQUIRE_INIT();
+    if (!b || !parts_out) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16_parts: NULL argument");
+    if (nframes > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16_parts: at most 2^32 - 65536 frames per call");
+    if (parts_out->bytes / 8 < nframes || ((uintptr_t)parts_out->ptr & 7))
+        return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16_parts: parts_out too small or not 8-byte aligned");
+    return bank_mixdown("sh_bank_mixdown_i16_parts", b, start, nframes, scale, nullptr, (int2v*)parts_out->ptr);
+}
+
+int sh_bank_mixdown_i16_parts(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* parts_out) {
+    SH_API_LOCK();
+    const int rc = sh_bank_mixdown_i16_parts_async(b, start, nframes, scale, parts_out);
+    if (rc) return sync_call_failed(rc);
+    if (nframes == 0) return rc;
+    return sh_overflow_check();
 }
 
 int sh_bank_mixdown_i16(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* out_i16) {

@@ -125,6 +125,50 @@ constexpr int CH_BIG = 1 << 28;
 
 __device__ __forceinline__ int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
+// A chain map as it is stored (include/synthhip.h, sh_chain_map): .x = add, saturated at +-SH_CHAIN_ADD_MAX -- for |add| >= 65535
+// every int16 input already lands on a bound, so the map is unchanged on int16 inputs and sums of any number of maps fit int32 --
+// and .y = lo | hi << 16.
+typedef int int2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int chain_add_sat(int a) { return clampi(a, -SH_CHAIN_ADD_MAX, SH_CHAIN_ADD_MAX); }
+__device__ __forceinline__ int2v chain_map(int a, int L, int U) {
+    return (int2v){chain_add_sat(a), (int)((uint32_t)(uint16_t)L | ((uint32_t)(uint16_t)U << 16))};
+}
+__device__ __forceinline__ int chain_lo(int2v m) { return (int)(short)(uint16_t)((uint32_t)m.y & 0xFFFFu); }
+__device__ __forceinline__ int chain_hi(int2v m) { return (int)(short)(uint16_t)((uint32_t)m.y >> 16); }
+
+// sh_chain_parts_compose / _apply: nparts planes of maps, plane k at parts[k * plane], folded in order per value -- composed
+// into one map (APPLY false) or applied to x0 (or 0).  Four planes in flight, 8-byte loads, one value per lane.
+template <bool APPLY>
+__global__ __launch_bounds__(256) void k_chain_parts(const int2v* parts, uint32_t nparts, size_t plane, uint32_t n,
+                                                     const short* __restrict__ x0, int2v* out_maps, short* __restrict__ out) {
+    const uint32_t f = (uint32_t)(sh::block_id() * 256 + threadIdx.x);
+    if (f >= n) return;
+    const int2v* p = parts + f;
+    int a = 0, L = -32768, U = 32767;
+    int x = (APPLY && x0) ? (int)x0[f] : 0;
+    auto step = [&](const int2v m) {
+        const int a2 = chain_add_sat(m.x), lo2 = chain_lo(m), hi2 = chain_hi(m);
+        if constexpr (APPLY) {
+            x = clampi(x + a2, lo2, hi2);
+        } else {
+            L = clampi(L + a2, lo2, hi2);
+            U = clampi(U + a2, lo2, hi2);
+            a = chain_add_sat(a + a2);
+        }
+    };
+    uint32_t k = 0;
+    for (; k + 4 <= nparts; k += 4) {
+        int2v v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = p[(size_t)(k + u) * plane];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) step(v[u]);
+    }
+    for (; k < nparts; ++k) step(p[(size_t)k * plane]);
+    if constexpr (APPLY) out[f] = (short)x;
+    else out_maps[f] = chain_map(a, L, U);
+}
+
 // Per-lane fold state for 8 samples: the sums in int32, the two clamp bounds as packed int16 pairs.  Once a range
 // holds one voice the bounds are inside the int16 range for good (L = U = "no bound" only before), and
 // bound' = clamp(bound + s, -32768, 32767) is exactly the packed saturating add: one instruction per two samples;
@@ -190,10 +234,13 @@ __device__ __forceinline__ short8v load_row8(const short* __restrict__ chunks, s
 }
 
 // WAVES waves = (WAVES / COLS) voice ranges x COLS adjacent 1 KB columns: a workgroup visits COLS KB of a row at a time.
-template <int WAVES, int COLS, bool NT>
+// PARTS (sh_mix_chain_i16_parts, sh_mix_chain_pan_i16_parts): wave 0 composes the W triples into the map of all the voices and
+// stores it (sh_chain_map, 8 bytes per sample, in maps) instead of applying it to 0.
+template <int WAVES, int COLS, bool NT, bool PARTS = false>
 __global__ __launch_bounds__(WAVES * 64) void k_mix_chain_i16(const short* __restrict__ chunks, uint32_t nvoices,
                                                               size_t stride, uint32_t nsamples,
-                                                              short* __restrict__ out, const double2* __restrict__ pan = nullptr) {
+                                                              short* __restrict__ out, const double2* __restrict__ pan = nullptr,
+                                                              int2v* __restrict__ maps = nullptr) {
     constexpr int S = 8;                                  // samples per lane: one 16-byte load per voice row
     constexpr int VG = WAVES / COLS;
     __shared__ int red[WAVES][3][S][64];
@@ -247,6 +294,22 @@ __global__ __launch_bounds__(WAVES * 64) void k_mix_chain_i16(const short* __res
         red[wave][2][j][lane] = f.hi(j);
     }
     __syncthreads();
+    if (PARTS && vg == 0 && s0 < nsamples) {
+#pragma unroll
+        for (int j = 0; j < S; ++j) {
+            int a = 0, L = -32768, U = 32767;             // (ranges of at most 32 768 voices: |a| <= 2^30)
+#pragma unroll
+            for (int g = 0; g < VG; ++g) {
+                const int w = g * COLS + col;
+                const int a2 = red[w][0][j][lane], lo2 = red[w][1][j][lane], hi2 = red[w][2][j][lane];
+                L = clampi(L + a2, lo2, hi2);
+                U = clampi(U + a2, lo2, hi2);
+                a += a2;
+            }
+            if (s0 + j < nsamples) maps[s0 + j] = chain_map(a, L, U);
+        }
+        return;
+    }
     if (vg == 0 && s0 < nsamples) {
         short8v r;
 #pragma unroll
@@ -1353,6 +1416,100 @@ int sh_mix_chain_pan_i16(const sh_buf* chunks, uint32_t nvoices, size_t stride, 
         hipLaunchKernelGGL((k_mix_chain_i16<8, 1, false>), sh::grid1d(nsamples, 512), dim3(512), 0, st, in, nvoices, stride, nsamples, (short*)out->ptr, fac);
     }
     SH_CHECK_LAUNCH("k_mix_chain_pan");
+    return SH_OK;
+}
+
+// ---- chain maps (include/synthhip.h, sh_chain_map) ---------------------------------------------------------------------------
+int sh_mix_chain_i16_parts(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nsamples, sh_buf* parts_out) {
+    SH_REQUIRE_INIT();
+    if (!chunks || !parts_out || nvoices == 0) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16_parts: NULL argument");
+    if (nvoices > 32768) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16_parts: at most 32768 voices");
+    if (nsamples > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16_parts: at most 2^32 - 65536 samples per call");
+    if (!nsamples) return SH_OK;
+    if (stride < nsamples || chunks->bytes / 2 < (size_t)(nvoices - 1) * stride + nsamples)
+        return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16_parts: chunk buffer too small");
+    if (parts_out->bytes / 8 < nsamples || ((uintptr_t)parts_out->ptr & 7))
+        return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16_parts: parts_out too small or not 8-byte aligned");
+    hipStream_t st = sh::state().stream;
+    const short* in = (const short*)chunks->ptr;
+    int2v* maps = (int2v*)parts_out->ptr;
+    // the split kernel throughout (the direct loops keep no map); long rows: one voice range per wave, eight columns per workgroup
+    const uint32_t columns = (uint32_t)sh::div_up(nsamples, 512);
+#define SH_CHAIN_PARTS(W_, C_) hipLaunchKernelGGL((k_mix_chain_i16<W_, C_, false, true>), sh::grid1d(nsamples, 512 * C_), dim3(W_ * 64), 0, st, \
+                                                  in, nvoices, stride, nsamples, (short*)nullptr, (const double2*)nullptr, maps)
+    if (nvoices < 64) SH_CHAIN_PARTS(2, 1);
+    else if (columns >= 1536) SH_CHAIN_PARTS(8, 8);
+    else if (columns >= 512) SH_CHAIN_PARTS(8, 2);
+    else SH_CHAIN_PARTS(8, 1);
+#undef SH_CHAIN_PARTS
+    SH_CHECK_LAUNCH("k_mix_chain_i16(parts)");
+    return SH_OK;
+}
+
+int sh_mix_chain_pan_i16_parts(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nframes, const sh_buf* factors_lr,
+                               sh_buf* parts_out) {
+    SH_REQUIRE_INIT();
+    if (!chunks || !parts_out || !factors_lr || nvoices == 0) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: NULL argument");
+    if (nvoices > 32768) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: at most 32768 voices");
+    if (nframes > 0x7FFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: at most 2^31 - 65536 frames per call");
+    if (!nframes) return SH_OK;
+    if (stride < nframes || chunks->bytes / 2 < (size_t)(nvoices - 1) * stride + nframes)
+        return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: chunk buffer too small");
+    if (factors_lr->bytes / 16 < nvoices) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: one (left, right) pair of doubles per voice");
+    if (parts_out->bytes / 16 < nframes || ((uintptr_t)parts_out->ptr & 7))
+        return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: parts_out too small or not 8-byte aligned");
+    hipStream_t st = sh::state().stream;
+    const short* in = (const short*)chunks->ptr;
+    const double2* fac = (const double2*)factors_lr->ptr;
+    const uint32_t nsamples = 2 * nframes;
+    int2v* maps = (int2v*)parts_out->ptr;
+    if (nvoices < 64) hipLaunchKernelGGL((k_mix_chain_i16<2, 1, false, true>), sh::grid1d(nsamples, 512), dim3(128), 0, st, in, nvoices, stride, nsamples, (short*)nullptr, fac, maps);
+    else hipLaunchKernelGGL((k_mix_chain_i16<8, 1, false, true>), sh::grid1d(nsamples, 512), dim3(512), 0, st, in, nvoices, stride, nsamples, (short*)nullptr, fac, maps);
+    SH_CHECK_LAUNCH("k_mix_chain_pan(parts)");
+    return SH_OK;
+}
+
+static int chain_parts_check(const char* who, const sh_buf* parts, uint32_t nparts, size_t part_stride, uint32_t nvalues) {
+    if (nparts == 0) return SH_OK;
+    if (!parts) return sh::set_error(SH_ERR_INVALID, "%s: NULL parts", who);
+    if (nparts > 1 && (part_stride < nvalues || part_stride == 0)) return sh::set_error(SH_ERR_INVALID, "%s: part_stride < nvalues", who);
+    const size_t cap = parts->bytes / 8;
+    if (cap < nvalues || (nparts > 1 && (size_t)(nparts - 1) > (cap - nvalues) / part_stride))
+        return sh::set_error(SH_ERR_INVALID, "%s: parts buffer too small", who);
+    if ((uintptr_t)parts->ptr & 7) return sh::set_error(SH_ERR_INVALID, "%s: parts not 8-byte aligned", who);
+    return SH_OK;
+}
+
+int sh_chain_parts_compose(const sh_buf* parts, uint32_t nparts, size_t part_stride, uint32_t nvalues, sh_buf* out_parts) {
+    SH_REQUIRE_INIT();
+    if (!out_parts) return sh::set_error(SH_ERR_INVALID, "sh_chain_parts_compose: NULL argument");
+    if (nvalues > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_chain_parts_compose: at most 2^32 - 65536 values per call");
+    int rc = chain_parts_check("sh_chain_parts_compose", parts, nparts, part_stride, nvalues);
+    if (rc) return rc;
+    if (out_parts->bytes / 8 < nvalues || ((uintptr_t)out_parts->ptr & 7))
+        return sh::set_error(SH_ERR_INVALID, "sh_chain_parts_compose: out_parts too small or not 8-byte aligned");
+    if (!nvalues) return SH_OK;
+    hipLaunchKernelGGL(k_chain_parts<false>, sh::grid1d(nvalues, 256), dim3(256), 0, sh::state().stream,
+                       nparts ? (const int2v*)parts->ptr : (const int2v*)nullptr, nparts, part_stride, nvalues, (const short*)nullptr,
+                       (int2v*)out_parts->ptr, (short*)nullptr);
+    SH_CHECK_LAUNCH("k_chain_parts(compose)");
+    return SH_OK;
+}
+
+int sh_chain_parts_apply(const sh_buf* parts, uint32_t nparts, size_t part_stride, uint32_t nvalues, const sh_buf* x0_i16,
+                         sh_buf* out_i16) {
+    SH_REQUIRE_INIT();
+    if (!out_i16) return sh::set_error(SH_ERR_INVALID, "sh_chain_parts_apply: NULL argument");
+    if (nvalues > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_chain_parts_apply: at most 2^32 - 65536 values per call");
+    int rc = chain_parts_check("sh_chain_parts_apply", parts, nparts, part_stride, nvalues);
+    if (rc) return rc;
+    if (x0_i16 && x0_i16->bytes / 2 < nvalues) return sh::set_error(SH_ERR_INVALID, "sh_chain_parts_apply: x0 too small");
+    if (out_i16->bytes / 2 < nvalues) return sh::set_error(SH_ERR_INVALID, "sh_chain_parts_apply: output too small");
+    if (!nvalues) return SH_OK;
+    hipLaunchKernelGGL(k_chain_parts<true>, sh::grid1d(nvalues, 256), dim3(256), 0, sh::state().stream,
+                       nparts ? (const int2v*)parts->ptr : (const int2v*)nullptr, nparts, part_stride, nvalues,
+                       x0_i16 ? (const short*)x0_i16->ptr : (const short*)nullptr, (int2v*)nullptr, (short*)out_i16->ptr);
+    SH_CHECK_LAUNCH("k_chain_parts(apply)");
     return SH_OK;
 }
 

@@ -462,6 +462,25 @@ class _HipBackend:
     def download(self, buf, nvalues: int) -> np.ndarray:
         return buf.download(np.float32, nvalues)
 
+    # -- the integer route (DistVoiceBank.mixdown_i16) --------------------------------------------------------------------
+    def mixdown_parts(self, nframes: int, start: int, scale: float, stereo: bool):
+        """The shard's chain maps: nframes (stereo: 2 * nframes) sh_chain_map in a device buffer."""
+        return self.local.mixdown_i16_parts_device(nframes, start, scale, stereo)
+
+    def gather_parts(self, parts, nvalues: int, root: int, rank: int, world: int):
+        """Every rank's maps to root, in rank order (RCCL on the library stream); the buffer on root, None elsewhere."""
+        gathered = N.DeviceBuffer(world * nvalues * 8) if rank == root else None
+        N.check(N.lib().sh_dist_gather_parts(parts.handle, nvalues, root, gathered.handle if gathered is not None else None))
+        return gathered
+
+    def apply_parts(self, gathered, nparts: int, nvalues: int) -> bytes:
+        """The gathered maps applied in order to silence: the int16 bytes."""
+        from .mixer import apply_chain_parts
+        out = apply_chain_parts(gathered, nvalues)
+        data = out.download_bytes(nvalues * 2)
+        out.free()
+        return data
+
 
 class DistVoiceBank:
     """This rank's shard of a voice table + the reduce of the partial buses.
@@ -577,6 +596,24 @@ class DistVoiceBank:
             self._close_slot()
         self._release_held()
         return v32
+
+    def mixdown_i16(self, nframes: int, start: int = 0, root: int = 0, scale: float = 32767.0, stereo: bool = False) -> Optional[bytes]:
+        """The reference's int16 mixdown of the WHOLE table -- every voice quantised, then ``mixed = audioop.add(mixed, voice, 2)``
+        down all the voices in order (``stereo``: every voice placed by its gains first) -- byte for byte: the int16 bytes on root,
+        None elsewhere.  Each rank leaves the chain's map of its shard per value (8 bytes), root gathers them and applies them in
+        rank order, which is voice order (the shards are contiguous and ascend with rank).  Synchronous; the float ring is flushed
+        first, so the two never interleave on the communication stream."""
+        self.flush()
+        self.backend.sync()
+        nvalues = nframes * (2 if stereo else 1)
+        if nvalues == 0:
+            return b"" if self.rank == root else None
+        parts = self.backend.mixdown_parts(nframes, start, scale, stereo)
+        gathered = self.backend.gather_parts(parts, nvalues, root, self.rank, self.world)
+        if self.rank != root:
+            self.backend.sync()
+            return None
+        return self.backend.apply_parts(gathered, self.world, nvalues)
 
     def render(self, nframes: int, start: int = 0, root: int = 0) -> Optional[np.ndarray]:
         buf = self.render_device(nframes, start, root)

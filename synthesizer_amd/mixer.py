@@ -30,7 +30,7 @@ from . import params
 from .oscillators import Oscillator, VoiceSpec, _pwm_widths, _table, pack_voices, time_step_weights
 from .sample import Sample
 
-__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "pan_gains"]
+__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
 
 
 def pan_gains(pan: float) -> Tuple[float, float]:
@@ -394,6 +394,30 @@ class VoiceBank:
         N.check(fn(self._bank.handle, start, nframes, float(scale), out.handle))
         return out
 
+    def mixdown_i16_parts_device(self, nframes: int, start: int = 0, scale: float = 32767.0, stereo: bool = False,
+                                 out: Optional[N.DeviceBuffer] = None) -> N.DeviceBuffer:
+        """``mixdown_i16_device`` (``stereo``: ``mixdown_stereo_i16_device``) as the chain's MAP instead of its result: one
+        ``sh_chain_map`` (chainmaps.CHAIN_MAP_DTYPE, 8 bytes) per int16 value -- nframes maps, or 2 * nframes interleaved L / R.
+        The maps of consecutive banks applied in order (``apply_chain_parts``) give the mixdown of their voices concatenated."""
+        nvalues = nframes * (2 if stereo else 1)
+        if out is None:
+            out = N.DeviceBuffer(max(nvalues * 8, 8))
+        if nframes == 0:
+            return out
+        L = N.lib()
+        if stereo or self._rows is not None or params.variants["quantise"] == "round":
+            rows, stride = self.generate_i16_device(nframes, start, scale)
+            try:
+                if stereo:
+                    N.check(L.sh_mix_chain_pan_i16_parts(rows.handle, self.nvoices, stride, nframes, self.pan_factors_device().handle, out.handle))
+                else:
+                    N.check(L.sh_mix_chain_i16_parts(rows.handle, self.nvoices, stride, nframes, out.handle))
+            finally:
+                rows.free()
+            return out
+        N.check(L.sh_bank_mixdown_i16_parts(self._bank.handle, start, nframes, float(scale), out.handle))
+        return out
+
     def pan_factors_device(self) -> N.DeviceBuffer:
         if self._pan_dev is None:
             self._pan_dev = N.DeviceBuffer.from_array(np.asarray(self.gains, dtype=np.float64).reshape(-1))
@@ -448,6 +472,75 @@ def mix_bus(voices: np.ndarray, gains: Sequence[Tuple[float, float]]) -> np.ndar
     for b in (vb, gb, bus):
         b.free()
     return out
+
+
+def _chain_planes(parts: Union[N.DeviceBuffer, Sequence[N.DeviceBuffer]], nvalues: int) -> Tuple[Optional[N.DeviceBuffer], int, bool]:
+    """(buffer of consecutive planes of nvalues maps, number of planes, temporary?): a sequence of buffers is copied into one."""
+    if isinstance(parts, N.DeviceBuffer):
+        nparts = parts.nbytes // (nvalues * 8) if nvalues else 0
+        return parts, nparts, False
+    parts = list(parts)
+    if not parts or nvalues == 0:
+        return None, 0, False
+    planes = N.DeviceBuffer(len(parts) * nvalues * 8)
+    for k, p in enumerate(parts):
+        N.check(N.lib().sh_buf_copy(planes.handle, k * nvalues * 8, p.handle, 0, nvalues * 8))
+    return planes, len(parts), True
+
+
+def compose_chain_parts(parts: Union[N.DeviceBuffer, Sequence[N.DeviceBuffer]], nvalues: int,
+                        out: Optional[N.DeviceBuffer] = None) -> N.DeviceBuffer:
+    """Chain maps of consecutive voice ranges (a list of buffers of ``nvalues`` maps, or one buffer of such planes back to back),
+    folded in order into ONE map per value (``sh_chain_parts_compose``)."""
+    planes, nparts, tmp = _chain_planes(parts, nvalues)
+    if out is None:
+        out = N.DeviceBuffer(max(nvalues * 8, 8))
+    N.check(N.lib().sh_chain_parts_compose(planes.handle if planes is not None else None, nparts, nvalues, nvalues, out.handle))
+    if tmp:
+        planes.free()
+    return out
+
+
+def apply_chain_parts(parts: Union[N.DeviceBuffer, Sequence[N.DeviceBuffer]], nvalues: int,
+                      x0: Optional[Union[N.DeviceBuffer, Sample]] = None, out: Optional[N.DeviceBuffer] = None) -> N.DeviceBuffer:
+    """Chain maps of consecutive voice ranges applied in order to ``x0`` (nvalues int16 in a device buffer, or a 16-bit Sample's
+    frames; None: silence) -> nvalues int16: ``audioop.add(x0, voice)`` down every voice of every range (``sh_chain_parts_apply``)."""
+    if isinstance(x0, Sample):
+        if x0.samplewidth != 2 or len(x0) * x0.nchannels < nvalues:
+            raise ValueError("x0 must be a 16-bit sample of at least nvalues samples")
+        x0 = x0._device()
+    planes, nparts, tmp = _chain_planes(parts, nvalues)
+    if out is None:
+        out = N.DeviceBuffer(max(nvalues * 2, 4))
+    N.check(N.lib().sh_chain_parts_apply(planes.handle if planes is not None else None, nparts, nvalues, nvalues,
+                                         x0.handle if x0 is not None else None, out.handle))
+    if tmp:
+        planes.free()
+    return out
+
+
+def mixdown_i16_banks(banks: Sequence[VoiceBank], nframes: int, start: int = 0, scale: float = 32767.0,
+                      stereo: bool = False) -> Sample:
+    """The reference's int16 mixdown of the banks' voices concatenated in order (mono, or ``stereo`` with every voice placed by its
+    gains): each bank leaves its chain maps in one plane of a shared buffer, one launch applies the planes to silence.  Covers
+    tables of any size (a bank holds at most 32 768 voices for the integer routes)."""
+    if not banks:
+        raise ValueError("no banks to mix")
+    rates = {b.samplerate for b in banks}
+    if len(rates) != 1:
+        raise ValueError("all banks must share one sample rate")
+    nch = 2 if stereo else 1
+    s = Sample(samplerate=rates.pop(), nchannels=nch, samplewidth=2)
+    nvalues = nframes * nch
+    if nframes == 0:
+        return s
+    planes = N.DeviceBuffer(len(banks) * nvalues * 8)
+    for k, b in enumerate(banks):
+        b.mixdown_i16_parts_device(nframes, start, scale, stereo, out=planes.view(k * nvalues * 8, nvalues * 8))
+    out = apply_chain_parts(planes, nvalues)
+    planes.free()
+    s._set_device(out, nvalues * 2)
+    return s
 
 
 def _gather(sources: Sequence[Tuple[N.DeviceBuffer, int, int]], nsamples: int, out: N.DeviceBuffer, width: int = 2,
