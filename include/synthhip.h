@@ -140,7 +140,9 @@ typedef struct sh_voice {
      * ways by up to guard_t * |t| + guard_c (t: the accumulated phase), far inside the float contract -- but where int(scale * v)
      * of such a sample lies that close to an integer, the int16 routes (sh_bank_generate_i16, sh_bank_mixdown_i16) recompute it
      * term by term from the voice's own list, guard_count sh_partial at partial[guard_offset] in the order of the reference's
-     * loop: equal integers whatever the time into the note.  guard_count = 0: no guard (the sample is quantised as it is). */
+     * loop: equal integers whatever the time into the note.  guard_count = 0: no guard (the sample is quantised as it is).  Any
+     * tolerance is honoured (from 1/8 on, every sample is summed term by term), and a list of any length: a polynomial voice whose list
+     * is longer than 255 entries takes the general code instead of the lean kernels on every route. */
     double   guard_t, guard_c;
     uint32_t guard_offset, guard_count;
 } sh_voice;

@@ -365,7 +365,7 @@ int sh_bank_create(const sh_voice* voices, uint32_t nvoices, const sh_segment* s
         if (voices[i].fm_mode == SH_FM_BUFFER || voices[i].kind == SH_BUFFER) b->first_row_voice = (long long)i;
     for (uint32_t i = 0; i < nvoices; ++i)
         if (voices[i].bias == 0.0 && !voices[i].flip &&
-            ((voices[i].kind == SH_HARMONICS && voices[i].harm_dense == 2 && voices[i].fm_mode == SH_FM_NONE) ||
+            ((voices[i].kind == SH_HARMONICS && voices[i].harm_dense == 2 && voices[i].fm_mode == SH_FM_NONE && voices[i].guard_count <= LEAN_GUARD_MAX) ||
              (voices[i].kind == SH_SINE && voices[i].fm_mode == SH_FM_SINE) ||
              (voices[i].fm_mode == SH_FM_NONE && (voices[i].kind == SH_SINE || voices[i].kind == SH_SAWTOOTH || voices[i].kind == SH_SQUARE ||
                                                   voices[i].kind == SH_TRIANGLE || voices[i].kind == SH_PULSE)))) {

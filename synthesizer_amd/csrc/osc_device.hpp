@@ -252,6 +252,10 @@ struct alignas(64) FastRec {
 };
 static_assert(offsetof(FastRec, t0_b) == 192, "FastRec: common part is 192 bytes");
 static_assert(sizeof(FastRec) == 256, "FastRec layout");
+// The longest guard list a lean record carries: its length lives in the low 8 bits of FastRec::pad1 (PrepInfo::guard_word).  A
+// polynomial voice with a longer list is no lean candidate (sh_bank_create) and never lean (prepare_voice): the general code, which reads
+// sh_voice::guard_count itself, guards it on every route.
+constexpr uint32_t LEAN_GUARD_MAX = 255;
 constexpr uint32_t LEAN_HARM = 0, LEAN_FM = 1,                 // ... and the plain waveforms without FM (t in turns, Sine: radians);
                    LEAN_SINE = 2, LEAN_SAW = 3, LEAN_SQUARE = 4, LEAN_TRIANGLE = 5, LEAN_PULSE = 6;    // Pulse: poly[0] = pulsewidth
 
@@ -388,7 +392,7 @@ __device__ __forceinline__ void prepare_voice(const BankPtrs& B, uint32_t first,
     o->seg = lo;
     info.guard_ptr = 0;
     info.guard_word = 0;
-    if (v.guard_count != 0 && v.guard_count <= 255u) {
+    if (v.guard_count != 0 && v.guard_count <= LEAN_GUARD_MAX) {
         const double t_end = fabs(t_base) + (double)nframes * fabs(dt);     // (the pieces that follow inside the launch differ from dt by ulps)
         const float tol = __double2float_ru(fma(v.guard_t, t_end, v.guard_c) * 1.000001);
         info.guard_word = ((__float_as_uint(tol) + 0xFFu) & ~0xFFu) | v.guard_count;
@@ -585,7 +589,8 @@ __device__ __forceinline__ void prepare_voice(const BankPtrs& B, uint32_t first,
         l_rot = B.lfo_rot[first + vi];
     }
     info.fast = ((flags & (FL_POLY | FL_FOLDED | FL_FM | FL_SILENT)) == (FL_POLY | FL_FOLDED) || lean_fm || lean_plain || lean_sloped) &&
-                (one_piece || two_pieces) && onset_i == 0;     // (the launch that holds the onset: general code)
+                (one_piece || two_pieces) && onset_i == 0 &&   // (the launch that holds the onset: general code)
+                v.guard_count <= LEAN_GUARD_MAX;               // (a guard list longer than a lean record holds: general code, guarded)
     info.remain = one_piece ? 0xFFFFFFFFu : (uint32_t)rem;
     info.t0_b = one_piece ? t_base : p1_t0;
     info.dt_b = one_piece ? dt : p1_dt;
@@ -1071,9 +1076,12 @@ template <int FPL>
 __device__ __forceinline__ bool guard_near(const double (&x)[FPL], double scale, double tq) {
     bool near = false;
     const double tq2 = tq + tq;
+    // (tq >= 1/2, or not a number: every sample is in reach of some integer -- and the band around 0 below is no longer safe to skip:
+    //  a fast value in [-tq, 1 - tq) may belong to a list whose sum truncates to -1 or 1)
+    if (!(tq2 < 1.0)) return true;                            // (uniform)
 #pragma unroll
     for (int j = 0; j < FPL; ++j) {
-        // (not around the integer 0: no boundary of a truncation toward zero, and where a waveform is flat at its zero crossing -- the
+        // (not around the integer 0 -- tq < 1/2: no boundary of a truncation toward zero, and where a waveform is flat at its zero crossing -- the
         //  1/k series of sixteen partials at t = pi -- one sample in 10^4 lies within reach of it: profiles/r06_guard_ab.txt)
         const double y = fma(scale, x[j], tq);
         near |= !(__builtin_amdgcn_fract(y) > tq2) && !(y >= 0.0 && y < 1.0);

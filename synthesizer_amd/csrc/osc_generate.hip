@@ -410,8 +410,8 @@ __global__ __launch_bounds__(256, (FOLD || (RowOut<OutT>::I16 && FPL == 16)) ? 3
     uint64_t nearm[NQ];                                         // (uniform) lanes with a sample of quarter h within the guard's reach of an integer
     uint32_t nearv[NQ];                                         // the smallest frac(scale v + tq) * 2^32 among the lane's frames of quarter h
     double tq = 0.0;                                            // (uniform) the record's guard distance in integer units
-    double tqm = 0.0;                                           // (uniform) tq + 1.5 * 2^20
-    uint32_t near_lo = 0;                                       // (uniform) 2 tq in units of 2^-32, plus two; 0xFFFFFFFF: every sample (a record that holds a NaN)
+    double tqm = 0.0;                                           // (uniform) tq + 2^-32 + 1.5 * 2^20
+    uint32_t near_lo = 0;                                       // (uniform) 2 tq in units of 2^-32, plus three; 0xFFFFFFFF: every sample (a record that holds a NaN, a tolerance >= 1/8)
     const bool full_tile = tile0 + 64 * FPL <= n;
     // frames 2m, 2m + 1 of the lane: int(scale * v) -- as int(scale v + tq): the same integer unless scale v lies within tq of one, which
     // is what frac(scale v + tq) <= 2 tq says; those samples are redone below (the boundary guard)
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(256, (FOLD || (RowOut<OutT>::I16 && FPL == 16)) ? 3
             // The fraction of scale v + tq as an integer: added to 1.5 * 2^20 (an ulp there is 2^-32) the sum's LOW WORD is
             // frac(scale v + tq) * 2^32 -- one FMA per sample, no v_fract_f64 (a quarter-rate instruction: with it the check cost 13-17 %
             // of the kernel, a compare per frame into a scalar register pair 18 %; profiles/r06_guard_ab.txt).  The SMALLEST low word of
-            // the quarter's samples is kept -- one v_min3_u32 per pair -- and compared once per record with 2 tq * 2^32 (+ 2: rounding).
+            // the quarter's samples is kept -- one v_min3_u32 per pair -- and compared once per record with 2 tq * 2^32 (+ 3: rounding).
             // ... except around the integer 0, which is no boundary of a truncation toward zero -- and a waveform that is FLAT at its zero
             // crossing (the 1/k series of an even number of partials at t = pi: value, slope and curvature vanish) spends one sample in
             // 10^4 within reach of it: 2 % of the quarters 5 s into the benchmark's notes, 5.5 % after 300 s, against 10^-7 of the samples in
@@ -496,14 +496,17 @@ __global__ __launch_bounds__(256, (FOLD || (RowOut<OutT>::I16 && FPL == 16)) ? 3
                 near_lo = 0;
             } else if (tol < 0.125) {
                 tq = tol >= 0x1p-31 ? tol : 0x1p-31;               // (at least two steps of the 2^-32 grid the check works on)
-                near_lo = (uint32_t)((tq + tq) * 0x1p32) + 2u;
+                near_lo = (uint32_t)((tq + tq) * 0x1p32) + 3u;
             } else {
                 // a record with a non-finite value carries an infinite tolerance (prepare_chunk), and a tolerance of 1/8 or more cannot be
                 // told from one: every sample is redone, and what is not a number is flagged there
                 tq = 0.0;
                 near_lo = 0xFFFFFFFFu;
             }
-            tqm = tq + 0x1.8p20;
+            // (tq + 2^-32: tqm and the FMA both round to the 2^-32 grid, so a sample exactly tq below an integer could land one step
+            //  short of it -- low word 0xFFFFFFFF, missed.  One step up, it lands on or above the integer; near_lo's + 3 covers the
+            //  upper edge moved by the same step)
+            tqm = (tq + 0x1p-32) + 0x1.8p20;
 #ifdef SH_AB_COUNT
             (void)0;
 #endif
@@ -621,9 +624,12 @@ __global__ __launch_bounds__(256, (FOLD || (RowOut<OutT>::I16 && FPL == 16)) ? 3
                         const double sq = fma(scale, pv * (sn * ag), tq);
                         // (an integer in reach -- but not 0: truncation toward zero has no boundary there, and a waveform that is FLAT at
                         //  its zero crossing, like the 1/k series of an even number of partials at t = pi, spends one sample in 10^4 within
-                        //  reach of it: 2-5 % of the quarters come here for that alone, tools/guard_count.py)
+                        //  reach of it: 2-5 % of the quarters come here for that alone, tools/guard_count.py).  That holds while tq < 1/2 only:
+                        //  "redo everything" (near_lo = 0xFFFFFFFF, a tolerance of 1/8 or more) redoes the band around 0 too -- a fast value just
+                        //  under 1 may belong to a list whose sum is 1 or more
                         const double wq = fma(scale, pv * (sn * ag), tqm);
-                        const bool nr = ((uint32_t)__double2loint(wq) <= near_lo && __double2hiint(wq) != 0x41380000) || !(sq == sq);
+                        const bool nr = near_lo == 0xFFFFFFFFu || ((uint32_t)__double2loint(wq) <= near_lo && __double2hiint(wq) != 0x41380000) ||
+                                        !(sq == sq);
                         int a = (int)sq;
                         if (__ballot(nr) != 0ull) {               // (uniform) some lane's frame j is in reach of an integer
                             if (nr) {

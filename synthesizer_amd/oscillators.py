@@ -293,6 +293,14 @@ def guard_bounds(partials, poly, dense) -> Tuple[float, float]:
     return per_t, const
 
 
+def guard_tolerance(bounds: Tuple[float, float], partials, amplitude: float, bias: float, gmax: float) -> Tuple[float, float]:
+    """(guard_t, guard_c) of one voice (sh_voice::guard_*): guard_bounds of its list scaled by |amplitude| and the envelope's largest
+    gain gmax, plus what the reference's own sum of the list and the bias leave (2^-50 of their mass)."""
+    per_t, const = bounds
+    a = abs(amplitude)
+    return gmax * a * per_t, gmax * (a * const + 2.0 ** -50 * (3.0 * abs(bias) + a * sum(abs(x[1]) for x in partials)))
+
+
 def pack_voices(specs: Sequence[VoiceSpec], gains: Optional[Sequence[Tuple[float, float]]] = None):
     """VoiceSpec list -> (voices, segs, coefs, partials) arrays in the C layout.  Tables and harmonic
     lists shared by several voices are stored once."""
@@ -380,11 +388,8 @@ def pack_voices(specs: Sequence[VoiceSpec], gains: Optional[Sequence[Tuple[float
         key = id(s.harm_poly) if s.harm_poly is not None else id(s.harm_dense)
         if key not in bound_cache:
             bound_cache[key] = guard_bounds(s.harm_guard, s.harm_poly, s.harm_dense)
-        per_t, const = bound_cache[key]
         gmax = max(1.0, abs(s.env.sustain_level)) if s.env is not None else 1.0
-        a = abs(s.amplitude)
-        gt = gmax * a * per_t
-        gc = gmax * (a * const + 2.0 ** -50 * (3.0 * abs(s.bias) + a * sum(abs(x[1]) for x in s.harm_guard)))
+        gt, gc = guard_tolerance(bound_cache[key], s.harm_guard, s.amplitude, s.bias, gmax)
         if not (gt < 1.0 and gc < 1.0):          # (NaN / huge amplitudes: no guard -- such a voice overflows any integer format anyway)
             g_off[i], g_cnt[i] = 0, 0
             continue
