@@ -5,11 +5,10 @@
 //   k_generate_lists      whole-bank materialisation through the launch's lean / general / silent lists
 //   k_generate_lean_harm  the lean polynomial-Harmonics records by the recurrence, sixteen frames per lane
 #include "osc_host.hpp"
+#include "chain.hpp"
 #include <stdlib.h>
 
 namespace {
-
-typedef int int2v __attribute__((ext_vector_type(2)));     // a plane element of the fused mixdown: (a, L | U << 16)
 
 // ---- the int16 forms (sh_bank_generate_i16): a row element is int(scale * v) of the float64 sample v -- Sample.from_osc_block's
 // quantiser (upstream synthplayer/sample.py; truncation toward zero, OverflowError where the value does not fit) applied where the
@@ -693,66 +692,28 @@ __global__ __launch_bounds__(256, (FOLD || (RowOut<OutT>::I16 && FPL == 16)) ? 3
         int2v* __restrict__ dst = parts + (size_t)blockIdx.y * plane + seg_first + i0;
 #pragma unroll
         for (int j = 0; j < FPL; ++j) {
-            if (i0 + (uint32_t)j * 64u < n) {
-                const uint32_t lu = (uint32_t)(uint16_t)fL[j / 2][j & 1] | ((uint32_t)(uint16_t)fU[j / 2][j & 1] << 16);
-                __builtin_nontemporal_store((int2v){fa[j], (int)lu}, dst + j * 64);
-            }
+            if (i0 + (uint32_t)j * 64u < n)
+                __builtin_nontemporal_store((int2v){fa[j], (int)shc::packed_bounds(shc::Map{fa[j], fL[j / 2][j & 1], fU[j / 2][j & 1]})}, dst + j * 64);
         }
     }
 }
 
 // The planes of k_generate_lean_harm<.., FOLD> applied in order (plane = 64-voice chunk x part: voice order): out[f] = the chain's result.
+// The planes hold exact sums (the range rule, chain.hpp): streaming loads, each plane is read once.
 __global__ __launch_bounds__(256) void k_mixdown_combine(const int2v* __restrict__ parts, uint32_t nplanes, size_t plane, uint32_t first, uint32_t n,
                                                          short* __restrict__ out) {
     const uint32_t f = (uint32_t)(sh::block_id() * 256 + threadIdx.x);
     if (f >= n) return;
-    const int2v* __restrict__ p = parts + first + f;
-    int x = 0;
-    uint32_t k = 0;
-    for (; k + 4 <= nplanes; k += 4) {                          // four planes in flight
-        int2v v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = __builtin_nontemporal_load(p + (size_t)(k + u) * plane);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int L = (int)(short)(uint16_t)((uint32_t)v[u].y & 0xFFFFu), U = (int)(short)(uint16_t)((uint32_t)v[u].y >> 16);
-            x = min(max(x + v[u].x, L), U);
-        }
-    }
-    for (; k < nplanes; ++k) {
-        const int2v v = p[(size_t)k * plane];
-        const int L = (int)(short)(uint16_t)((uint32_t)v.y & 0xFFFFu), U = (int)(short)(uint16_t)((uint32_t)v.y >> 16);
-        x = min(max(x + v.x, L), U);
-    }
-    out[first + f] = (short)x;
+    out[first + f] = (short)shc::apply_planes<shc::RANGE, true>(parts + first + f, nplanes, plane, 0);
 }
 
 // k_mixdown_combine's compose-only sibling (sh_bank_mixdown_i16_parts): the planes folded in order into ONE map per frame, stored as
-// sh_chain_map (include/synthhip.h) instead of applied to 0.  (|a| <= 32 768 per voice of the bank, at most 32 768 voices: int32;
-// saturated at +-SH_CHAIN_ADD_MAX on the way out, which leaves the map unchanged on int16 inputs.)
+// sh_chain_map (include/synthhip.h) instead of applied to 0.
 __global__ __launch_bounds__(256) void k_mixdown_compose(const int2v* __restrict__ parts, uint32_t nplanes, size_t plane, uint32_t n,
                                                          int2v* __restrict__ maps) {
     const uint32_t f = (uint32_t)(sh::block_id() * 256 + threadIdx.x);
     if (f >= n) return;
-    const int2v* __restrict__ p = parts + f;
-    int a = 0, L = -32768, U = 32767;
-    auto step = [&](const int2v v) {
-        const int lo = (int)(short)(uint16_t)((uint32_t)v.y & 0xFFFFu), hi = (int)(short)(uint16_t)((uint32_t)v.y >> 16);
-        L = min(max(L + v.x, lo), hi);
-        U = min(max(U + v.x, lo), hi);
-        a += v.x;
-    };
-    uint32_t k = 0;
-    for (; k + 4 <= nplanes; k += 4) {                          // four planes in flight
-        int2v v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = __builtin_nontemporal_load(p + (size_t)(k + u) * plane);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) step(v[u]);
-    }
-    for (; k < nplanes; ++k) step(p[(size_t)k * plane]);
-    a = min(max(a, -SH_CHAIN_ADD_MAX), SH_CHAIN_ADD_MAX);
-    maps[f] = (int2v){a, (int)((uint32_t)(uint16_t)L | ((uint32_t)(uint16_t)U << 16))};
+    maps[f] = shc::store(shc::compose_planes<shc::RANGE, true>(parts + f, nplanes, plane));
 }
 
 // (Measured and dropped in round 3: the same materialisation walked ROW by row -- one record per workgroup held in SGPRs, contiguous runs

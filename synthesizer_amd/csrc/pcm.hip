@@ -7,6 +7,7 @@
 // cross-wave combine of the mixer chain.  Built with -ffp-contract=off: audioop forms
 // prev*d + cur*(outrate-d) with two roundings and a division, and so does k_resample.
 #include "common.hpp"
+#include "chain.hpp"
 #include <mutex>
 #include <string.h>
 #include <new>
@@ -15,9 +16,6 @@
 
 namespace {
 
-typedef short short2v __attribute__((ext_vector_type(2)));
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef short short8v __attribute__((ext_vector_type(8)));
 typedef int   int4v   __attribute__((ext_vector_type(4)));
 typedef char  char16v __attribute__((ext_vector_type(16)));
 
@@ -80,7 +78,6 @@ __global__ __launch_bounds__(256) void k_quantize_f32_i16_vec(const float4v* __r
 
 // float64 -> int16, two samples per 16-byte vector; the route WaveSynth.to_sample takes
 typedef double double2v __attribute__((ext_vector_type(2)));
-typedef short short2v __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(256) void k_quantize_f64_i16_vec(const double2v* __restrict__ in, size_t nvec, double scale,
                                                               short2v* __restrict__ out, int* __restrict__ flag, int rnd = 0) {
     const size_t base = sh::block_id() * 512 + threadIdx.x;
@@ -118,260 +115,153 @@ __global__ __launch_bounds__(256) void k_add_scalar(const T* a, const T* b,
 
 
 // ---- mixer chain: mixed = add(...add(add(c0, c1), c2)..., c_{N-1}), saturating at every step ----
-// x -> clamp(x + s, lo, hi) composes into x -> clamp(x + a, L, U) (closed under composition), so
-// each wave folds a contiguous range of voices into one (a, L, U) triple per sample and wave 0
-// applies the W triples in voice order to x = 0.  Bit-exact with the sequential fold.
-constexpr int CH_BIG = 1 << 28;
+// The chain over a range of voices is one map x -> clamp(x + a, L, U) per value (chain.hpp), so each wave folds a contiguous range of
+// voices into its map and the first waves apply the W maps in voice order to x = 0.  Bit-exact with the sequential fold.
 
-__device__ __forceinline__ int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-// A chain map as it is stored (include/synthhip.h, sh_chain_map): .x = add, saturated at +-SH_CHAIN_ADD_MAX -- for |add| >= 65535
-// every int16 input already lands on a bound, so the map is unchanged on int16 inputs and sums of any number of maps fit int32 --
-// and .y = lo | hi << 16.
-typedef int int2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int chain_add_sat(int a) { return clampi(a, -SH_CHAIN_ADD_MAX, SH_CHAIN_ADD_MAX); }
-__device__ __forceinline__ int2v chain_map(int a, int L, int U) {
-    return (int2v){chain_add_sat(a), (int)((uint32_t)(uint16_t)L | ((uint32_t)(uint16_t)U << 16))};
-}
-__device__ __forceinline__ int chain_lo(int2v m) { return (int)(short)(uint16_t)((uint32_t)m.y & 0xFFFFu); }
-__device__ __forceinline__ int chain_hi(int2v m) { return (int)(short)(uint16_t)((uint32_t)m.y >> 16); }
-
-// sh_chain_parts_compose / _apply: nparts planes of maps, plane k at parts[k * plane], folded in order per value -- composed
-// into one map (APPLY false) or applied to x0 (or 0).  Four planes in flight, 8-byte loads, one value per lane.
+// sh_chain_parts_compose / _apply: nparts stored planes of maps, plane k at parts[k * plane], folded in order per value -- composed
+// into one map (APPLY false) or applied to x0 (or 0).
 template <bool APPLY>
 __global__ __launch_bounds__(256) void k_chain_parts(const int2v* parts, uint32_t nparts, size_t plane, uint32_t n,
                                                      const short* __restrict__ x0, int2v* out_maps, short* __restrict__ out) {
     const uint32_t f = (uint32_t)(sh::block_id() * 256 + threadIdx.x);
     if (f >= n) return;
-    const int2v* p = parts + f;
-    int a = 0, L = -32768, U = 32767;
-    int x = (APPLY && x0) ? (int)x0[f] : 0;
-    auto step = [&](const int2v m) {
-        const int a2 = chain_add_sat(m.x), lo2 = chain_lo(m), hi2 = chain_hi(m);
-        if constexpr (APPLY) {
-            x = clampi(x + a2, lo2, hi2);
-        } else {
-            L = clampi(L + a2, lo2, hi2);
-            U = clampi(U + a2, lo2, hi2);
-            a = chain_add_sat(a + a2);
-        }
-    };
-    uint32_t k = 0;
-    for (; k + 4 <= nparts; k += 4) {
-        int2v v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = p[(size_t)(k + u) * plane];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) step(v[u]);
-    }
-    for (; k < nparts; ++k) step(p[(size_t)k * plane]);
-    if constexpr (APPLY) out[f] = (short)x;
-    else out_maps[f] = chain_map(a, L, U);
+    if constexpr (APPLY) out[f] = (short)shc::apply_planes<shc::STORED, false>(parts + f, nparts, plane, x0 ? (int)x0[f] : 0);
+    else out_maps[f] = shc::store(shc::compose_planes<shc::STORED, false>(parts + f, nparts, plane));
 }
 
-// Per-lane fold state for 8 samples: the sums in int32, the two clamp bounds as packed int16 pairs.  Once a range
-// holds one voice the bounds are inside the int16 range for good (L = U = "no bound" only before), and
-// bound' = clamp(bound + s, -32768, 32767) is exactly the packed saturating add: one instruction per two samples;
-// the sum takes one dot-product instruction per sample ((s_lo, s_hi) . (1, 0) + a), no unpacking.
-typedef short short2v __attribute__((ext_vector_type(2)));
-struct ChainFold {
-    int a[8];
-    short2v L[4], U[4];
-    bool any;
-    __device__ __forceinline__ void init() {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { L[q] = (short2v){-32768, -32768}; U[q] = (short2v){32767, 32767}; }
-        any = false;
-    }
-    // first voice of the range: the sum starts, the bounds become the int16 range (set by init)
-    __device__ __forceinline__ void first(const short8v x) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = x[j];
-        any = true;
-    }
-    __device__ __forceinline__ void add(const short8v x) {
-#define SH_PAIR(Q_)                                                                              \
-        {                                                                                        \
-            const short2v s2 = __builtin_shufflevector(x, x, 2 * Q_, 2 * Q_ + 1);                \
-            L[Q_] = __builtin_elementwise_add_sat(L[Q_], s2);                                    \
-            U[Q_] = __builtin_elementwise_add_sat(U[Q_], s2);                                    \
-            a[2 * Q_] = __builtin_amdgcn_sdot2(s2, (short2v){1, 0}, a[2 * Q_], false);           \
-            a[2 * Q_ + 1] = __builtin_amdgcn_sdot2(s2, (short2v){0, 1}, a[2 * Q_ + 1], false);   \
+// Where a split kernel's voice v gives its 8 samples from s0.  whole(): (uniform) every voice's 8 samples are one aligned vector --
+// decided once, outside the voice loop; tail(): the ragged form, zeros past the end.
+// Strided rows (PAN forms, sh_mix_chain_pan_i16: the rows are MONO voices and each enters the fold as Sample.stereo(lf, rf) of itself,
+// shc::stereo on the four mono frames of eight stereo samples; the factors of a voice are wave-uniform: scalar loads).
+template <bool NT>
+struct RowSrc {
+    const short* __restrict__ chunks;
+    size_t stride;
+    const double2* __restrict__ pan;
+    __device__ __forceinline__ bool whole(uint32_t s0, uint32_t nsamples) const { return s0 + 7 < nsamples && (stride & (pan ? 3 : 7)) == 0; }
+    __device__ __forceinline__ short8v load(uint32_t v, uint32_t s0) const {
+        if (pan) {                                       // (uniform) s0 = the first of eight STEREO samples: four mono frames from s0 / 2
+            const double2 f = pan[v];
+            return shc::stereo<4>(sh::load_vec<NT, short4v>(chunks + v * stride + (s0 >> 1)), f.x, f.y);
         }
-        SH_PAIR(0) SH_PAIR(1) SH_PAIR(2) SH_PAIR(3)
-#undef SH_PAIR
+        return sh::load_vec<NT, short8v>(chunks + v * stride + s0);
     }
-    __device__ __forceinline__ int lo(int j) const { return any ? (int)L[j >> 1][j & 1] : -CH_BIG; }
-    __device__ __forceinline__ int hi(int j) const { return any ? (int)U[j >> 1][j & 1] : CH_BIG; }
+    __device__ __forceinline__ short8v tail(uint32_t v, uint32_t s0, uint32_t nsamples) const {
+        if (pan) {
+            const short* row = chunks + (size_t)v * stride + (s0 >> 1);
+            short4v m;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) m[j] = (s0 + 2 * j < nsamples) ? row[j] : (short)0;
+            const double2 fac = pan[v];
+            return shc::stereo<4>(m, fac.x, fac.y);
+        }
+        const short* row = chunks + (size_t)v * stride + s0;
+        short8v x;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = (s0 + j < nsamples) ? row[j] : (short)0;
+        return x;
+    }
 };
 
-// PAN forms of the two chain kernels below (sh_mix_chain_pan_i16): the rows are MONO voices and every voice enters the fold as
-// Sample.stereo(lf, rf) of itself -- audioop.tostereo: (fbound(v * lf), fbound(v * rf)) per frame, fbound = clamp to the sample
-// range, then floor -- made in registers from the 8 bytes of four mono frames; the fold is the same chain over the eight
-// stereo samples.  For every finite product fbound(p) == clamp(floor(p), -32768, 32767) (the "val < minval + 1 -> minval" branch
-// selects values whose floor is minval anyway), so a frame costs: one int -> float64 conversion, two products, two floors, two
-// conversions (saturating at the int32 range) and ONE v_cvt_pk_i16_i32, whose saturation is the clamp and whose packed result is
-// the interleaved (L, R) pair.  The factors of a voice are wave-uniform: scalar loads.
-typedef short short4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ short8v pan4(const short4v m, const double lf, const double rf) {
-    union { short8v v; short2v p[4]; } r;
+// Chunks that live where their samples live: a table of (pointer, samples available) per source instead of one padded array -- the
+// real-time mixer's loop without the staging copy (every active sample is read in place at its play position; past its end it counts
+// as silence, which the fold skips: x + 0 saturates to x).  Each load decides for itself between the vector and the ragged form.
+struct ChainSrc {
+    const short* p;
+    uint32_t n;
+    uint32_t pad;
+};
+__device__ __forceinline__ short8v chain_load8(const short* p, uint32_t n, uint32_t s0) {
+    short8v x = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (s0 + 8 <= n && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        x = *reinterpret_cast<const short8v*>(p + s0);
+    } else if (s0 < n) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const double x = (double)m[j];
-        r.p[j] = __builtin_amdgcn_cvt_pk_i16((int)floor(x * lf), (int)floor(x * rf));
+        for (int j = 0; j < 8; ++j)
+            if (s0 + j < n) x[j] = p[s0 + j];
     }
-    return r.v;
+    return x;
 }
-template <bool NT>
-__device__ __forceinline__ short8v load_row8(const short* __restrict__ chunks, size_t v, size_t stride, uint32_t s0, const double2* __restrict__ pan) {
-    if (pan) {                                           // (uniform) s0 = the first of eight STEREO samples: four mono frames from s0 / 2
-        const double2 f = pan[v];
-        return pan4(sh::load_vec<NT, short4v>(chunks + v * stride + (s0 >> 1)), f.x, f.y);
+struct TableSrc {
+    const ChainSrc* __restrict__ tab;
+    __device__ __forceinline__ bool whole(uint32_t, uint32_t) const { return true; }
+    __device__ __forceinline__ short8v load(uint32_t v, uint32_t s0) const { const ChainSrc c = tab[v]; return chain_load8(c.p, c.n, s0); }
+    __device__ __forceinline__ short8v tail(uint32_t v, uint32_t s0, uint32_t) const { return load(v, s0); }
+};
+
+// The split fold: WAVES waves = (WAVES / COLS) voice ranges x COLS adjacent 1 KB columns (a workgroup visits COLS KB of a row at a
+// time), eight samples per lane; PARTS (sh_mix_chain_i16_parts, sh_mix_chain_pan_i16_parts): the map of all the voices is stored
+// (sh_chain_map, 8 bytes per sample, in maps) instead of its result.
+template <int WAVES, int COLS, bool PARTS, typename Src>
+__device__ __forceinline__ void mix_chain_split(const Src src, uint32_t nvoices, uint32_t nsamples, short* __restrict__ out,
+                                                int2v* __restrict__ maps) {
+    constexpr int VG = WAVES / COLS;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t col = wave % COLS, vg = wave / COLS;
+    const uint32_t s0 = (((uint32_t)sh::block_id() * COLS + col) * 64 + lane) * 8;        // (grid1d folds beyond 2^21 workgroups)
+    const uint32_t per = (nvoices + VG - 1) / VG;
+    const uint32_t v0 = vg * per;
+    uint32_t v1 = v0 + per;
+    if (v1 > nvoices) v1 = nvoices;
+    shc::ChainFold f;
+    f.init();
+    if (s0 < nsamples && v0 < v1) {
+        if (src.whole(s0, nsamples)) {
+            uint32_t v = v0;
+            f.first(src.load(v, s0));                     // (a table source past its end contributes zeros: still a voice of the fold)
+            ++v;
+            for (; v + 3 < v1; v += 4) {                  // four voices in flight
+                const short8v x0 = src.load(v, s0);
+                const short8v x1 = src.load(v + 1, s0);
+                const short8v x2 = src.load(v + 2, s0);
+                const short8v x3 = src.load(v + 3, s0);
+                f.add(x0); f.add(x1); f.add(x2); f.add(x3);
+            }
+            for (; v < v1; ++v) f.add(src.load(v, s0));
+        } else {
+            for (uint32_t v = v0; v < v1; ++v) {
+                const short8v x = src.tail(v, s0, nsamples);
+                if (v == v0) f.first(x); else f.add(x);
+            }
+        }
     }
-    return sh::load_vec<NT, short8v>(chunks + v * stride + s0);
+    shc::split_store<WAVES, COLS, PARTS>(f, wave, lane, s0, nsamples, out, maps);
 }
 
-// WAVES waves = (WAVES / COLS) voice ranges x COLS adjacent 1 KB columns: a workgroup visits COLS KB of a row at a time.
-// PARTS (sh_mix_chain_i16_parts, sh_mix_chain_pan_i16_parts): wave 0 composes the W triples into the map of all the voices and
-// stores it (sh_chain_map, 8 bytes per sample, in maps) instead of applying it to 0.
 template <int WAVES, int COLS, bool NT, bool PARTS = false>
 __global__ __launch_bounds__(WAVES * 64) void k_mix_chain_i16(const short* __restrict__ chunks, uint32_t nvoices,
                                                               size_t stride, uint32_t nsamples,
                                                               short* __restrict__ out, const double2* __restrict__ pan = nullptr,
                                                               int2v* __restrict__ maps = nullptr) {
-    constexpr int S = 8;                                  // samples per lane: one 16-byte load per voice row
-    constexpr int VG = WAVES / COLS;
-    __shared__ int red[WAVES][3][S][64];
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t col = wave % COLS, vg = wave / COLS;
-    const uint32_t s0 = (((uint32_t)sh::block_id() * COLS + col) * 64 + lane) * S;       // (grid1d folds beyond 2^21 workgroups)
-    const uint32_t per = (nvoices + VG - 1) / VG;
-    const uint32_t v0 = vg * per;
-    uint32_t v1 = v0 + per;
-    if (v1 > nvoices) v1 = nvoices;
-    ChainFold f;
-    f.init();
-    const bool vec = (s0 + S - 1 < nsamples) && ((stride & (pan ? 3 : S - 1)) == 0);
-    if (s0 < nsamples && v0 < v1) {
-        if (vec) {
-            uint32_t v = v0;
-            f.first(load_row8<NT>(chunks, v, stride, s0, pan));
-            ++v;
-            for (; v + 3 < v1; v += 4) {                  // four voice rows in flight
-                const short8v x0 = load_row8<NT>(chunks, v, stride, s0, pan);
-                const short8v x1 = load_row8<NT>(chunks, v + 1, stride, s0, pan);
-                const short8v x2 = load_row8<NT>(chunks, v + 2, stride, s0, pan);
-                const short8v x3 = load_row8<NT>(chunks, v + 3, stride, s0, pan);
-                f.add(x0); f.add(x1); f.add(x2); f.add(x3);
-            }
-            for (; v < v1; ++v) f.add(load_row8<NT>(chunks, v, stride, s0, pan));
-        } else {
-            for (uint32_t v = v0; v < v1; ++v) {
-                short8v x;
-                if (pan) {
-                    const short* row = chunks + (size_t)v * stride + (s0 >> 1);
-                    short4v m;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) m[j] = (s0 + 2 * j < nsamples) ? row[j] : (short)0;
-                    const double2 fac = pan[v];
-                    x = pan4(m, fac.x, fac.y);
-                } else {
-                    const short* row = chunks + (size_t)v * stride + s0;
-#pragma unroll
-                    for (int j = 0; j < S; ++j) x[j] = (s0 + j < nsamples) ? row[j] : (short)0;
-                }
-                if (v == v0) f.first(x); else f.add(x);
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-        red[wave][0][j][lane] = f.a[j];
-        red[wave][1][j][lane] = f.lo(j);
-        red[wave][2][j][lane] = f.hi(j);
-    }
-    __syncthreads();
-    if (PARTS && vg == 0 && s0 < nsamples) {
-#pragma unroll
-        for (int j = 0; j < S; ++j) {
-            int a = 0, L = -32768, U = 32767;             // (ranges of at most 32 768 voices: |a| <= 2^30)
-#pragma unroll
-            for (int g = 0; g < VG; ++g) {
-                const int w = g * COLS + col;
-                const int a2 = red[w][0][j][lane], lo2 = red[w][1][j][lane], hi2 = red[w][2][j][lane];
-                L = clampi(L + a2, lo2, hi2);
-                U = clampi(U + a2, lo2, hi2);
-                a += a2;
-            }
-            if (s0 + j < nsamples) maps[s0 + j] = chain_map(a, L, U);
-        }
-        return;
-    }
-    if (vg == 0 && s0 < nsamples) {
-        short8v r;
-#pragma unroll
-        for (int j = 0; j < S; ++j) {
-            int x = 0;
-#pragma unroll
-            for (int g = 0; g < VG; ++g) {
-                const int w = g * COLS + col;
-                x = clampi(x + red[w][0][j][lane], red[w][1][j][lane], red[w][2][j][lane]);
-            }
-            r[j] = (short)x;
-        }
-        if (s0 + S - 1 < nsamples && ((reinterpret_cast<uintptr_t>(out + s0) & 15) == 0)) {
-            *reinterpret_cast<short8v*>(out + s0) = r;
-        } else {
-            for (uint32_t j = 0; j < S && s0 + j < nsamples; ++j) out[s0 + j] = r[j];
-        }
-    }
+    mix_chain_split<WAVES, COLS, PARTS>(RowSrc<NT>{chunks, stride, pan}, nvoices, nsamples, out, maps);
 }
 
-// Long buffers: enough columns to fill the chip without splitting the voices, so a lane simply runs the reference's
-// loop -- mixed = add_sat(mixed, row) down all the rows, packed int16 -- and a workgroup walks WAVES KB of every row.
-// No fold state, no LDS; INFLIGHT independent row loads per lane.
-template <int WAVES, int INFLIGHT, bool NT>
-__global__ __launch_bounds__(WAVES * 64) void k_mix_chain_direct(const short* __restrict__ chunks, uint32_t nvoices, size_t stride,
-                                                                 uint32_t nsamples, short* __restrict__ out) {
-    const uint32_t s0 = (uint32_t)(sh::block_id() * (WAVES * 64) + threadIdx.x) * 8;
-    if (s0 >= nsamples) return;
-    const short* col = chunks + s0;
-    if (s0 + 8 <= nsamples) {
-        short8v acc = *reinterpret_cast<const short8v*>(col);
-        uint32_t v = 1;
-        for (; v + INFLIGHT <= nvoices; v += INFLIGHT) {
-            short8v x[INFLIGHT];
-#pragma unroll
-            for (int k = 0; k < INFLIGHT; ++k) x[k] = sh::load_vec<NT, short8v>(col + (size_t)(v + k) * stride);     // NT: 0.81 -> 0.90 of the HBM peak on 2 GB
-#pragma unroll
-            for (int k = 0; k < INFLIGHT; ++k) acc = __builtin_elementwise_add_sat(acc, x[k]);
-        }
-        for (; v < nvoices; ++v) acc = __builtin_elementwise_add_sat(acc, *reinterpret_cast<const short8v*>(col + (size_t)v * stride));
-        *reinterpret_cast<short8v*>(out + s0) = acc;
-    } else {
-        for (uint32_t j = 0; s0 + j < nsamples; ++j) {
-            short acc = col[j];
-            for (uint32_t v = 1; v < nvoices; ++v) acc = __builtin_elementwise_add_sat(acc, col[(size_t)v * stride + j]);
-            out[s0 + j] = acc;
-        }
-    }
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void k_mix_chain_gather(const ChainSrc* __restrict__ tab, uint32_t nsrc, uint32_t nsamples,
+                                                                 short* __restrict__ out) {
+    mix_chain_split<WAVES, 1, false>(TableSrc{tab}, nsrc, nsamples, out, nullptr);
 }
 
-// The direct loops with S samples (F frames) per lane: for rows of MIDDLING length (a few hundred thousand samples: too few 1 KB
-// columns to fill the chip with eight samples per lane, more than the split kernels like) four samples per lane -- 8-byte loads,
-// twice the wavefronts, eight row loads in flight -- run the mono chain at 0.87 of the HBM peak where the split kernel reaches 0.74
-// (1024 rows x 480 000 samples: 166 -> 142 us).  The PAN chain -- mono rows that enter as Sample.stereo(lf, rf) of themselves, see pan4
-// -- is bound by its float64 arithmetic (ten operations per frame), not by HBM: four frames per lane at every length from ~300 000
-// frames (480 000: 290 -> 202 us, 0.61 of HBM; 960 000: 392 -> 358 us, 0.69); eight frames per lane were slower at both.
-template <int S> struct ShortVec;
-template <> struct ShortVec<8> { typedef short8v type; };
-template <> struct ShortVec<4> { typedef short4v type; };
-template <> struct ShortVec<2> { typedef short2v type; };
+// The same with the source table IN the kernel arguments (up to 64 sources: one real-time mixer turn): no table upload in front of
+// the launch -- the copy of a pageable kilobyte costs more than the kernel.
+struct ChainTab { ChainSrc e[64]; };
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void k_mix_chain_gather_args(const ChainTab tab, uint32_t nsrc, uint32_t nsamples,
+                                                                      short* __restrict__ out) {
+    mix_chain_split<WAVES, 1, false>(TableSrc{tab.e}, nsrc, nsamples, out, nullptr);
+}
 
-template <int S, int WAVES, int INFLIGHT, bool NT>
+// Long buffers: enough columns to fill the chip without splitting the voices, so a lane simply runs the reference's loop --
+// mixed = add_sat(mixed, row) down all the rows, packed int16 -- with S samples (F frames) per lane, INFLIGHT independent row loads, no
+// fold state, no LDS.  From 1536 1 KB columns eight samples per lane (NTS false: a plain store).  For rows of MIDDLING length (a few
+// hundred thousand samples: too few 1 KB columns to fill the chip with eight samples per lane, more than the split kernels like) four
+// samples per lane -- 8-byte loads, twice the wavefronts, eight row loads in flight -- run the mono chain at 0.87 of the HBM peak where
+// the split kernel reaches 0.74 (1024 rows x 480 000 samples: 166 -> 142 us).  The PAN chain -- mono rows that enter as
+// Sample.stereo(lf, rf) of themselves, see shc::stereo -- is bound by its float64 arithmetic (ten operations per frame), not by HBM:
+// four frames per lane at every length from ~300 000 frames (480 000: 290 -> 202 us, 0.61 of HBM; 960 000: 392 -> 358 us, 0.69);
+// eight frames per lane were slower at both.
+template <int S, int WAVES, int INFLIGHT, bool NT, bool NTS = true>
 __global__ __launch_bounds__(WAVES * 64) void k_mix_chain_direct_s(const short* __restrict__ chunks, uint32_t nvoices, size_t stride,
                                                                    uint32_t nsamples, short* __restrict__ out) {
     typedef typename ShortVec<S>::type vec;
@@ -384,12 +274,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_mix_chain_direct_s(const short* 
         for (; v + INFLIGHT <= nvoices; v += INFLIGHT) {
             vec x[INFLIGHT];
 #pragma unroll
-            for (int k = 0; k < INFLIGHT; ++k) x[k] = sh::load_vec<NT, vec>(col + (size_t)(v + k) * stride);
+            for (int k = 0; k < INFLIGHT; ++k) x[k] = sh::load_vec<NT, vec>(col + (size_t)(v + k) * stride);     // NT: 0.81 -> 0.90 of the HBM peak on 2 GB
 #pragma unroll
             for (int k = 0; k < INFLIGHT; ++k) acc = __builtin_elementwise_add_sat(acc, x[k]);
         }
         for (; v < nvoices; ++v) acc = __builtin_elementwise_add_sat(acc, *reinterpret_cast<const vec*>(col + (size_t)v * stride));
-        __builtin_nontemporal_store(acc, reinterpret_cast<vec*>(out + s0));
+        if (NTS) __builtin_nontemporal_store(acc, reinterpret_cast<vec*>(out + s0));
+        else *reinterpret_cast<vec*>(out + s0) = acc;
     } else {
         for (uint32_t j = 0; s0 + j < nsamples; ++j) {
             short acc = col[j];
@@ -408,133 +299,29 @@ __global__ __launch_bounds__(WAVES * 64) void k_mix_chain_pan_direct_s(const sho
     if (f0 >= nframes) return;
     const short* col = chunks + f0;
     const double SH_PCM_CONST* fac = (const double SH_PCM_CONST*)pan;
-    auto stereo = [](const vin m, const double lf, const double rf) {
-        union { vout v; short2v p[F]; } r;
-#pragma unroll
-        for (int j = 0; j < F; ++j) {
-            const double x = (double)m[j];
-            r.p[j] = __builtin_amdgcn_cvt_pk_i16((int)floor(x * lf), (int)floor(x * rf));
-        }
-        return r.v;
-    };
     if (f0 + F <= nframes) {
-        vout acc = stereo(*reinterpret_cast<const vin*>(col), fac[0], fac[1]);
+        vout acc = shc::stereo<F>(*reinterpret_cast<const vin*>(col), fac[0], fac[1]);
         uint32_t v = 1;
         for (; v + INFLIGHT <= nvoices; v += INFLIGHT) {
             vin x[INFLIGHT];
 #pragma unroll
             for (int k = 0; k < INFLIGHT; ++k) x[k] = sh::load_vec<NT, vin>(col + (size_t)(v + k) * stride);
 #pragma unroll
-            for (int k = 0; k < INFLIGHT; ++k) acc = __builtin_elementwise_add_sat(acc, stereo(x[k], fac[2 * (v + k)], fac[2 * (v + k) + 1]));
+            for (int k = 0; k < INFLIGHT; ++k) acc = __builtin_elementwise_add_sat(acc, shc::stereo<F>(x[k], fac[2 * (v + k)], fac[2 * (v + k) + 1]));
         }
-        for (; v < nvoices; ++v) acc = __builtin_elementwise_add_sat(acc, stereo(*reinterpret_cast<const vin*>(col + (size_t)v * stride), fac[2 * v], fac[2 * v + 1]));
+        for (; v < nvoices; ++v) acc = __builtin_elementwise_add_sat(acc, shc::stereo<F>(*reinterpret_cast<const vin*>(col + (size_t)v * stride), fac[2 * v], fac[2 * v + 1]));
         __builtin_nontemporal_store(acc, reinterpret_cast<vout*>(out + 2 * (size_t)f0));
     } else {
         for (uint32_t j = 0; f0 + j < nframes; ++j) {
             short2v acc = {0, 0};
             for (uint32_t v = 0; v < nvoices; ++v) {
-                const double x = (double)col[(size_t)v * stride + j];
-                const short2v p = __builtin_amdgcn_cvt_pk_i16((int)floor(x * fac[2 * v]), (int)floor(x * fac[2 * v + 1]));
+                const short2v p = shc::stereo1(col[(size_t)v * stride + j], fac[2 * v], fac[2 * v + 1]);
                 acc = v == 0 ? p : __builtin_elementwise_add_sat(acc, p);
             }
             out[2 * (size_t)(f0 + j)] = acc[0];
             out[2 * (size_t)(f0 + j) + 1] = acc[1];
         }
     }
-}
-
-// The same fold over chunks that live where their samples live: a table of (pointer, samples available) per
-// source instead of one padded array -- the real-time mixer's loop without the staging copy (every active sample is
-// read in place at its play position; past its end it counts as silence, which the fold skips: x + 0 saturates to x).
-struct ChainSrc {
-    const short* p;
-    uint32_t n;
-    uint32_t pad;
-};
-
-__device__ __forceinline__ short8v chain_load8(const short* p, uint32_t n, uint32_t s0) {
-    short8v x = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (s0 + 8 <= n && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-        x = *reinterpret_cast<const short8v*>(p + s0);
-    } else if (s0 < n) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (s0 + j < n) x[j] = p[s0 + j];
-    }
-    return x;
-}
-
-template <int WAVES>
-__device__ __forceinline__ void mix_chain_gather_body(const ChainSrc* __restrict__ tab, uint32_t nsrc, uint32_t nsamples,
-                                                      short* __restrict__ out) {
-    constexpr int S = 8;
-    __shared__ int red[WAVES][3][S][64];
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t s0 = (blockIdx.x * 64 + lane) * S;
-    const uint32_t per = (nsrc + WAVES - 1) / WAVES;
-    const uint32_t v0 = wave * per;
-    uint32_t v1 = v0 + per;
-    if (v1 > nsrc) v1 = nsrc;
-    ChainFold f;
-    f.init();
-    if (s0 < nsamples && v0 < v1) {
-        uint32_t v = v0;
-        {
-            const ChainSrc c0 = tab[v];
-            f.first(chain_load8(c0.p, c0.n, s0));         // a source past its end contributes zeros: still a voice of the fold
-            ++v;
-        }
-        for (; v + 3 < v1; v += 4) {                      // four sources in flight
-            const ChainSrc c0 = tab[v], c1 = tab[v + 1], c2 = tab[v + 2], c3 = tab[v + 3];
-            const short8v x0 = chain_load8(c0.p, c0.n, s0);
-            const short8v x1 = chain_load8(c1.p, c1.n, s0);
-            const short8v x2 = chain_load8(c2.p, c2.n, s0);
-            const short8v x3 = chain_load8(c3.p, c3.n, s0);
-            f.add(x0); f.add(x1); f.add(x2); f.add(x3);
-        }
-        for (; v < v1; ++v) {
-            const ChainSrc c0 = tab[v];
-            f.add(chain_load8(c0.p, c0.n, s0));
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-        red[wave][0][j][lane] = f.a[j];
-        red[wave][1][j][lane] = f.lo(j);
-        red[wave][2][j][lane] = f.hi(j);
-    }
-    __syncthreads();
-    if (wave == 0 && s0 < nsamples) {
-        short8v r;
-#pragma unroll
-        for (int j = 0; j < S; ++j) {
-            int x = 0;
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) x = clampi(x + red[w][0][j][lane], red[w][1][j][lane], red[w][2][j][lane]);
-            r[j] = (short)x;
-        }
-        if (s0 + S - 1 < nsamples && ((reinterpret_cast<uintptr_t>(out + s0) & 15) == 0)) {
-            *reinterpret_cast<short8v*>(out + s0) = r;
-        } else {
-            for (uint32_t j = 0; j < S && s0 + j < nsamples; ++j) out[s0 + j] = r[j];
-        }
-    }
-}
-
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void k_mix_chain_gather(const ChainSrc* __restrict__ tab, uint32_t nsrc, uint32_t nsamples,
-                                                                 short* __restrict__ out) {
-    mix_chain_gather_body<WAVES>(tab, nsrc, nsamples, out);
-}
-
-// The same with the source table IN the kernel arguments (up to 64 sources: one real-time mixer turn): no table upload in front of
-// the launch -- the copy of a pageable kilobyte costs more than the kernel.
-struct ChainTab { ChainSrc e[64]; };
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void k_mix_chain_gather_args(const ChainTab tab, uint32_t nsrc, uint32_t nsamples,
-                                                                      short* __restrict__ out) {
-    mix_chain_gather_body<WAVES>(tab.e, nsrc, nsamples, out);
 }
 
 // the direct loop over the pointer table (long samples: mix_samples of whole tracks)
@@ -1352,15 +1139,28 @@ int sh_pcm_add_host(const void* a, const void* b, size_t nbytes, int width, void
     return SH_OK;
 }
 
+// The checks of the four strided chain entry points: nvoices rows of nframes samples (pan: mono frames, two output values each) at
+// stride; out holds an int16 result (unit 2) or a map (unit 8, parts_out) per output value.  1: an empty call, nothing to launch.
+static int chain_rows_check(const char* who, const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nframes,
+                            const sh_buf* factors_lr, bool pan, const sh_buf* out, size_t unit) {
+    if (!chunks || !out || (pan && !factors_lr) || nvoices == 0) return sh::set_error(SH_ERR_INVALID, "%s: NULL argument", who);
+    if (nvoices > 32768) return sh::set_error(SH_ERR_INVALID, "%s: at most 32768 voices", who);
+    if (!pan && nframes > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "%s: at most 2^32 - 65536 samples per call", who);
+    if (pan && nframes > 0x7FFF0000u) return sh::set_error(SH_ERR_INVALID, "%s: at most 2^31 - 65536 frames per call", who);
+    if (!nframes) return 1;
+    if (stride < nframes || chunks->bytes / 2 < (size_t)(nvoices - 1) * stride + nframes)
+        return sh::set_error(SH_ERR_INVALID, "%s: chunk buffer too small", who);
+    if (pan && factors_lr->bytes / 16 < nvoices) return sh::set_error(SH_ERR_INVALID, "%s: one (left, right) pair of doubles per voice", who);
+    const size_t nvalues = (size_t)nframes * (pan ? 2 : 1);
+    if (unit == 8 && (out->bytes / 8 < nvalues || ((uintptr_t)out->ptr & 7)))
+        return sh::set_error(SH_ERR_INVALID, "%s: parts_out too small or not 8-byte aligned", who);
+    if (unit == 2 && out->bytes / 2 < nvalues) return sh::set_error(SH_ERR_INVALID, "%s: output too small", who);
+    return SH_OK;
+}
+
 int sh_mix_chain_i16(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nsamples, sh_buf* out) {
     SH_REQUIRE_INIT();
-    if (!chunks || !out || nvoices == 0) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16: NULL argument");
-    if (nvoices > 32768) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16: at most 32768 voices");
-    if (nsamples > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16: at most 2^32 - 65536 samples per call");
-    if (!nsamples) return SH_OK;
-    if (stride < nsamples || chunks->bytes / 2 < (size_t)(nvoices - 1) * stride + nsamples)
-        return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16: chunk buffer too small");
-    if (out->bytes / 2 < nsamples) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16: output too small");
+    if (int rc = chain_rows_check("sh_mix_chain_i16", chunks, nvoices, stride, nsamples, nullptr, false, out, 2)) return rc < 0 ? rc : SH_OK;
     hipStream_t st = sh::state().stream;
     // shape by the number of 1 KB columns (= waves when the voices are not split): plenty -> the direct loop
     // (6.4-6.5 TB/s at 1875 columns, where the split kernel's waves of one workgroup fetch the same column of eight
@@ -1371,16 +1171,11 @@ int sh_mix_chain_i16(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint
     // (the split kernel keeps plain loads: 1024 x 96 000 samples = 197 MB ran 13 % slower with streaming ones)
 #define SH_CHAIN(W_, C_) hipLaunchKernelGGL((k_mix_chain_i16<W_, C_, false>), sh::grid1d(nsamples, 512 * C_), dim3(W_ * 64), 0, st, \
                                             (const short*)chunks->ptr, nvoices, stride, nsamples, (short*)out->ptr)
-#define SH_DIRECT_S(S_, INF_) do { \
-        if (stream) hipLaunchKernelGGL((k_mix_chain_direct_s<S_, 4, INF_, true>), sh::grid1d(nsamples, 256 * S_), dim3(256), 0, st, (const short*)chunks->ptr, nvoices, stride, nsamples, (short*)out->ptr); \
-        else hipLaunchKernelGGL((k_mix_chain_direct_s<S_, 4, INF_, false>), sh::grid1d(nsamples, 256 * S_), dim3(256), 0, st, (const short*)chunks->ptr, nvoices, stride, nsamples, (short*)out->ptr); } while (0)
-    if (columns >= 640 && columns < 1536 && aligned) SH_DIRECT_S(4, 8);      // (measured at 937 columns; 187 columns: the split kernel, 31 against 86 us)
-    else if (columns >= 1536 && aligned) {
-        if (stream) hipLaunchKernelGGL((k_mix_chain_direct<8, 4, true>), sh::grid1d(nsamples, 512 * 8), dim3(8 * 64), 0, st,
-                                       (const short*)chunks->ptr, nvoices, stride, nsamples, (short*)out->ptr);
-        else hipLaunchKernelGGL((k_mix_chain_direct<8, 4, false>), sh::grid1d(nsamples, 512 * 8), dim3(8 * 64), 0, st,
-                                (const short*)chunks->ptr, nvoices, stride, nsamples, (short*)out->ptr);
-    }
+#define SH_DIRECT_S(S_, W_, INF_, NTS_) do { \
+        if (stream) hipLaunchKernelGGL((k_mix_chain_direct_s<S_, W_, INF_, true, NTS_>), sh::grid1d(nsamples, W_ * 64 * S_), dim3(W_ * 64), 0, st, (const short*)chunks->ptr, nvoices, stride, nsamples, (short*)out->ptr); \
+        else hipLaunchKernelGGL((k_mix_chain_direct_s<S_, W_, INF_, false, NTS_>), sh::grid1d(nsamples, W_ * 64 * S_), dim3(W_ * 64), 0, st, (const short*)chunks->ptr, nvoices, stride, nsamples, (short*)out->ptr); } while (0)
+    if (columns >= 640 && columns < 1536 && aligned) SH_DIRECT_S(4, 4, 8, true);      // (measured at 937 columns; 187 columns: the split kernel, 31 against 86 us)
+    else if (columns >= 1536 && aligned) SH_DIRECT_S(8, 8, 4, false);
 #undef SH_DIRECT_S
     else if (nvoices < 64) SH_CHAIN(2, 1);
     else if (columns >= 512) SH_CHAIN(8, 2);
@@ -1392,14 +1187,7 @@ int sh_mix_chain_i16(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint
 
 int sh_mix_chain_pan_i16(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nframes, const sh_buf* factors_lr, sh_buf* out) {
     SH_REQUIRE_INIT();
-    if (!chunks || !out || !factors_lr || nvoices == 0) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16: NULL argument");
-    if (nvoices > 32768) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16: at most 32768 voices");
-    if (nframes > 0x7FFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16: at most 2^31 - 65536 frames per call");
-    if (!nframes) return SH_OK;
-    if (stride < nframes || chunks->bytes / 2 < (size_t)(nvoices - 1) * stride + nframes)
-        return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16: chunk buffer too small");
-    if (factors_lr->bytes / 16 < nvoices) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16: one (left, right) pair of doubles per voice");
-    if (out->bytes / 4 < nframes) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16: output too small");
+    if (int rc = chain_rows_check("sh_mix_chain_pan_i16", chunks, nvoices, stride, nframes, factors_lr, true, out, 2)) return rc < 0 ? rc : SH_OK;
     hipStream_t st = sh::state().stream;
     const short* in = (const short*)chunks->ptr;
     const double2* fac = (const double2*)factors_lr->ptr;
@@ -1422,14 +1210,7 @@ int sh_mix_chain_pan_i16(const sh_buf* chunks, uint32_t nvoices, size_t stride, 
 // ---- chain maps (include/synthhip.h, sh_chain_map) ---------------------------------------------------------------------------
 int sh_mix_chain_i16_parts(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nsamples, sh_buf* parts_out) {
     SH_REQUIRE_INIT();
-    if (!chunks || !parts_out || nvoices == 0) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16_parts: NULL argument");
-    if (nvoices > 32768) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16_parts: at most 32768 voices");
-    if (nsamples > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16_parts: at most 2^32 - 65536 samples per call");
-    if (!nsamples) return SH_OK;
-    if (stride < nsamples || chunks->bytes / 2 < (size_t)(nvoices - 1) * stride + nsamples)
-        return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16_parts: chunk buffer too small");
-    if (parts_out->bytes / 8 < nsamples || ((uintptr_t)parts_out->ptr & 7))
-        return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_i16_parts: parts_out too small or not 8-byte aligned");
+    if (int rc = chain_rows_check("sh_mix_chain_i16_parts", chunks, nvoices, stride, nsamples, nullptr, false, parts_out, 8)) return rc < 0 ? rc : SH_OK;
     hipStream_t st = sh::state().stream;
     const short* in = (const short*)chunks->ptr;
     int2v* maps = (int2v*)parts_out->ptr;
@@ -1449,15 +1230,7 @@ int sh_mix_chain_i16_parts(const sh_buf* chunks, uint32_t nvoices, size_t stride
 int sh_mix_chain_pan_i16_parts(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nframes, const sh_buf* factors_lr,
                                sh_buf* parts_out) {
     SH_REQUIRE_INIT();
-    if (!chunks || !parts_out || !factors_lr || nvoices == 0) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: NULL argument");
-    if (nvoices > 32768) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: at most 32768 voices");
-    if (nframes > 0x7FFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: at most 2^31 - 65536 frames per call");
-    if (!nframes) return SH_OK;
-    if (stride < nframes || chunks->bytes / 2 < (size_t)(nvoices - 1) * stride + nframes)
-        return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: chunk buffer too small");
-    if (factors_lr->bytes / 16 < nvoices) return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: one (left, right) pair of doubles per voice");
-    if (parts_out->bytes / 16 < nframes || ((uintptr_t)parts_out->ptr & 7))
-        return sh::set_error(SH_ERR_INVALID, "sh_mix_chain_pan_i16_parts: parts_out too small or not 8-byte aligned");
+    if (int rc = chain_rows_check("sh_mix_chain_pan_i16_parts", chunks, nvoices, stride, nframes, factors_lr, true, parts_out, 8)) return rc < 0 ? rc : SH_OK;
     hipStream_t st = sh::state().stream;
     const short* in = (const short*)chunks->ptr;
     const double2* fac = (const double2*)factors_lr->ptr;

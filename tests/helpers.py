@@ -173,3 +173,23 @@ def fast_form_longdouble(coef_block, dense, t):
         if a:
             out += a * np.sin(np.longdouble(K - j) * t)
     return out
+
+
+def range_rule_maps(rows, n):
+    """The chain map over int16 rows in voice order, as the library MAKES maps (the range rule, bytes of sh_chain_map):
+    add = the exact sum, saturated at +-2^17 once; lo / hi = the sequential fold of clamp(bound + s, -32768, 32767) from
+    (-32768, 32767) -- the chain applied to -32768 and to 32767.  `rows`: an iterable of n int16 values each."""
+    from synthesizer_amd import chainmaps as CM
+    add = np.zeros(n, dtype=np.int64)
+    lo = np.full(n, -32768, dtype=np.int64)
+    hi = np.full(n, 32767, dtype=np.int64)
+    for r in rows:
+        s = np.asarray(r, dtype=np.int16).astype(np.int64)
+        add += s
+        lo = np.clip(lo + s, -32768, 32767)
+        hi = np.clip(hi + s, -32768, 32767)
+    out = np.empty(n, dtype=CM.CHAIN_MAP_DTYPE)
+    out["add"] = np.clip(add, -CM.ADD_MAX, CM.ADD_MAX)
+    out["lo"] = lo
+    out["hi"] = hi
+    return out

@@ -132,3 +132,94 @@ def test_chunked_chain_of_stereo_interleaved_values(split):
     maps = [CM.voice_maps(np.frombuffer(s, dtype=np.int16)) for s in st]
     k = len(maps) // (split + 1)
     assert CM.apply([CM.compose_all(maps[:k]), CM.compose_all(maps[k:])]).tobytes() == want
+
+
+# ---- chain.hpp (the kernels' statement of the same algebra) built for the host -------------------------------------------------
+@pytest.fixture(scope="module")
+def ch(tmp_path_factory):
+    import ctypes
+    import subprocess
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    out = tmp_path_factory.mktemp("chain") / "libchain.so"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", str(root / "tests" / "cpu_chain.cpp"), "-o", str(out)], check=True)
+    return ctypes.CDLL(str(out))
+
+
+def _ptr(a):
+    import ctypes
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _split(m):
+    lo, hi = m["lo"].astype(np.uint16).astype(np.uint32), m["hi"].astype(np.uint16).astype(np.uint32)
+    return np.ascontiguousarray(m["add"]), lo | (hi << 16)
+
+
+def _join(add, bounds):
+    out = np.empty(len(add), dtype=CM.CHAIN_MAP_DTYPE)
+    out["add"] = add
+    lohi = bounds.view(np.int16).reshape(-1, 2)
+    out["lo"], out["hi"] = lohi[:, 0], lohi[:, 1]
+    return out
+
+
+def _random_maps(rng, n):
+    """Maps as stored: any int32 add (the ends, +-2^17 and the int16 edges among them), lo <= hi anywhere in int16."""
+    edges = np.array([-2 ** 31, 2 ** 31 - 1, -CM.ADD_MAX - 1, -CM.ADD_MAX, CM.ADD_MAX, CM.ADD_MAX + 1, -65536, -65535, 65535, 65536,
+                      -32768, 32767, -1, 0, 1], dtype=np.int64)
+    add = np.where(rng.random(n) < 0.3, rng.choice(edges, n), rng.integers(-2 ** 31, 2 ** 31, n))
+    add = np.where(rng.random(n) < 0.3, rng.integers(-70000, 70000, n), add)
+    b = np.sort(rng.integers(-32768, 32768, size=(n, 2)), axis=1)
+    b[rng.random(n) < 0.1] = [-32768, 32767]
+    b[rng.random(n) < 0.05, 1] = 32767
+    m = np.empty(n, dtype=CM.CHAIN_MAP_DTYPE)
+    m["add"], m["lo"], m["hi"] = add.astype(np.int32), b[:, 0], b[:, 1]
+    return m
+
+
+def test_host_build_stored_rule_equals_chainmaps(ch):
+    rng = np.random.default_rng(5)
+    n = 200000
+    f, g = _random_maps(rng, n), _random_maps(rng, n)
+    fa, fb = _split(f)
+    ga, gb = _split(g)
+    oa, ob = np.empty(n, np.int32), np.empty(n, np.uint32)
+    ch.ch_compose_stored(_ptr(fa), _ptr(fb), _ptr(ga), _ptr(gb), ctypes_long(n), _ptr(oa), _ptr(ob))
+    assert _join(oa, ob).tobytes() == CM.compose(f, g).tobytes()
+    x = rng.integers(-32768, 32768, n).astype(np.int16)
+    x[:4] = [-32768, 32767, 0, -1]
+    out = np.empty(n, np.int16)
+    ch.ch_apply_stored(_ptr(fa), _ptr(fb), _ptr(x), ctypes_long(n), _ptr(out))
+    assert out.tobytes() == CM.apply([f], x0=x).tobytes()
+
+
+def test_host_build_range_rule_equals_its_numpy_statement(ch):
+    """The range rule saturates add once, at the end: it differs from the stored-map rule's bytes, not from its function on int16."""
+    from tests.helpers import range_rule_maps
+    rng = np.random.default_rng(6)
+    n = 20000
+    for nv in (1, 2, 9, 40):
+        rows = rng.integers(-32768, 32768, size=(nv, n)).astype(np.int16)
+        rows[:, : n // 4] = np.where(rng.random((nv, 1)) < 0.5, 32767, -32768)      # partial sums beyond 2^17 and back
+        rows[:, n // 4: n // 2] = 32767 if nv % 2 else -32768
+        rows[:, -3:] = 0
+        oa, ob = np.empty(n, np.int32), np.empty(n, np.uint32)
+        ch.ch_range_rows(_ptr(np.ascontiguousarray(rows)), ctypes_long(nv), ctypes_long(n), _ptr(oa), _ptr(ob))
+        got = _join(oa, ob)
+        assert got.tobytes() == range_rule_maps(rows, n).tobytes(), nv
+        assert CM.apply([got]).tobytes() == CM.apply([CM.voice_maps(r) for r in rows]).tobytes(), nv
+    # add 200 000 then -100 000: the range rule stores 100 000, the stored-map rule 31 072
+    rows = np.array([[32767]] * 6 + [[3398]] + [[-32768]] * 3 + [[-1696]], dtype=np.int16)
+    oa, ob = np.empty(1, np.int32), np.empty(1, np.uint32)
+    ch.ch_range_rows(_ptr(rows), ctypes_long(len(rows)), ctypes_long(1), _ptr(oa), _ptr(ob))
+    assert int(oa[0]) == 100000
+    two = np.array([200000, -100000], dtype=np.int32)
+    b = _split(CM.identity(2))[1]
+    ch.ch_compose_stored(_ptr(two[:1].copy()), _ptr(b[:1].copy()), _ptr(two[1:].copy()), _ptr(b[1:].copy()), ctypes_long(1), _ptr(oa), _ptr(ob))
+    assert int(oa[0]) == 31072
+
+
+def ctypes_long(v):
+    import ctypes
+    return ctypes.c_long(v)

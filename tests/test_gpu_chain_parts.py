@@ -229,6 +229,56 @@ def test_device_compose_and_apply_match_the_host_algebra(gpu):
         N.check(N.lib().sh_chain_parts_apply(buf.handle, nparts + 1, nvalues, nvalues, None, N.DeviceBuffer(nvalues * 2).handle))
 
 
+def test_parts_bytes_follow_the_range_rule(gpu):
+    """The maps the library MAKES, byte for byte: add = the exact sum of the voices saturated at +-2^17 once, lo / hi = the chain
+    applied to -32768 / 32767 (tests/helpers.range_rule_maps) -- not the stored-map rule, which saturates add at every step.  Loud
+    voices whose partial sums pass 2^17 and come back; sh_mix_chain_i16_parts, _pan_i16_parts, and sh_bank_mixdown_i16_parts on
+    its fused and its two-step stretches, against the rows generate_i16 returns."""
+    from synthesizer_amd import _native as N
+    from synthesizer_amd import chainmaps as CM
+    from synthesizer_amd import oscillators as G
+    from synthesizer_amd.mixer import VoiceBank
+    from tests.helpers import range_rule_maps
+    L = N.lib()
+    rng = np.random.default_rng(21)
+    for nv, n in ((23, 40001), (90, 20003)):
+        rows = rng.integers(-32768, 32768, size=(nv, n)).astype(np.int16)
+        rows[: nv // 2, : n // 3] = 32000                       # the running sum passes +2^17 ...
+        rows[nv // 2:, : n // 3] = -30000                       # ... and comes back below it
+        rows[:, n // 3: n // 2] = -32768
+        stride = n + 1
+        chunks = N.DeviceBuffer(nv * stride * 2)
+        for v in range(nv):
+            chunks.upload(rows[v], v * stride * 2)
+        maps = N.DeviceBuffer(n * 16)
+        N.check(L.sh_mix_chain_i16_parts(chunks.handle, nv, stride, n, maps.handle))
+        want = range_rule_maps(rows, n)
+        assert rows[: nv // 2, 0].astype(np.int64).sum() > CM.ADD_MAX and abs(int(want["add"][0])) < CM.ADD_MAX
+        assert want["add"][n // 3] == -CM.ADD_MAX
+        assert maps.download_bytes(n * 8) == want.tobytes(), nv
+        fac = N.DeviceBuffer.from_array(np.tile([1.5, 0.75], nv))
+        st = [np.frombuffer(audioop.tostereo(r.tobytes(), 2, 1.5, 0.75), dtype=np.int16) for r in rows]
+        N.check(L.sh_mix_chain_pan_i16_parts(chunks.handle, nv, stride, n, fac.handle, maps.handle))
+        assert maps.download_bytes(n * 16) == range_rule_maps(st, 2 * n).tobytes(), nv
+        for b in (chunks, maps, fac):
+            b.free()
+    # a bank in phase: 70 voices of amplitude 0.9 sum far beyond 2^17; from frame 0 the notes' attack and decay go through the rows
+    # (two-step), the plateau through the fused fold
+    nv = 70
+    f = rng.uniform(200.0, 210.0, nv)
+    voices = [G.EnvelopeFilter(G.Harmonics(float(f[i]), [(1, 1.0), (3, 0.2)], amplitude=0.9, phase=0.0, samplerate=SR), 0.01, 0.05, 30.0, 0.8, 0.1)
+              for i in range(nv)]
+    bank = VoiceBank(voices, gains=[(0.5, 0.5)] * nv)
+    for start, n in ((0, 70001), (SR, 30001)):
+        rows = _rows(bank, n, start)
+        want = range_rule_maps(rows, n)
+        assert np.max(np.abs(want["add"])) == CM.ADD_MAX
+        parts = bank.mixdown_i16_parts_device(n, start)
+        assert _fused(N) >= 1, start
+        assert parts.download_bytes(n * 8) == want.tobytes(), start
+        parts.free()
+
+
 def test_table_beyond_one_bank_through_mixdown_i16_banks(gpu):
     """40 000 voices: no single bank's integer route takes them (sh_bank_mixdown_i16 still refuses), two banks' maps do; short blocks."""
     from synthesizer_amd import oscillators as G

@@ -165,29 +165,70 @@ def _audioop_fold(rows, nsamples):
     return mixed
 
 
-@pytest.mark.parametrize("nsamples", [262144 + 40, 786432 + 8 + 3, 1200000])
-def test_long_buffers_every_kernel_shape(gpu, nsamples):
-    """The fold picks its kernel by buffer length (voices split over waves / two columns per workgroup / the direct
-    loop): the three shapes, through both entry points (padded array, pointer table), loud voices so that the order of
-    the saturating adds shows, ragged ends and a source off the 16-byte grid."""
+# (voices, samples, stride padding): every row of the route tables of sh_mix_chain_i16 / _pan_i16 / their _parts forms and of the
+# gather -- fewer / at least 64 voices; under 512, 512-639, 640-1535 and 1536 or more 1 KB columns; rows beyond STREAM_BYTES (72 x
+# 1 000 000 samples: 144 MB; 140 x 500 001); a stride off the 8-sample grid (the split kernels' ragged path)
+LONG_SHAPES = [
+    pytest.param(9, 262144 + 40, 0, id="262184"),
+    pytest.param(9, 786432 + 8 + 3, 0, id="786443"),
+    pytest.param(9, 1200000, 0, id="1200000"),
+    pytest.param(9, 500001, 0, id="9v-500001"),
+    pytest.param(64, 100003, 0, id="64v-100003"),
+    pytest.param(70, 300001, 0, id="70v-300001"),
+    pytest.param(140, 500001, 0, id="140v-500001-stream"),
+    pytest.param(70, 300001, 3, id="70v-300001-stride3"),
+    pytest.param(72, 1000000, 0, id="72v-1000000-stream"),
+]
+
+
+@pytest.mark.parametrize("nv, nsamples, pad", LONG_SHAPES)
+def test_long_buffers_every_kernel_shape(gpu, nv, nsamples, pad):
+    """The fold picks its kernel by buffer length and voice count (voices split over waves / two or eight columns per workgroup /
+    the direct loops), through every entry point: padded array mono and pan, their _parts forms (applied, and their bytes against
+    the range rule), and the pointer table.  Loud voices so that the order of the saturating adds shows, ragged ends and a source
+    off the 16-byte grid."""
+    import audioop
     import ctypes as C
     from synthesizer_amd import _native as N
+    from synthesizer_amd import chainmaps as CM
     from synthesizer_amd.mixer import mix_samples
-    rng = np.random.default_rng(nsamples)
-    nv = 9
+    from tests.helpers import range_rule_maps
+    rng = np.random.default_rng(nsamples + 1000 * nv + pad)
     rows = [_rand(rng, nsamples, 0.6) for _ in range(nv)]
     want = _audioop_fold(rows, nsamples)
+    L = N.lib()
     # padded array
-    stride = (nsamples + 7) // 8 * 8
+    stride = (nsamples + 7) // 8 * 8 + pad
     chunks = N.DeviceBuffer(nv * stride * 2)
     chunks.zero()
     for v, x in enumerate(rows):
         chunks.upload(x, v * stride * 2)
-    out = N.DeviceBuffer(nsamples * 2)
-    N.check(N.lib().sh_mix_chain_i16(chunks.handle, nv, stride, nsamples, out.handle))
+    out = N.DeviceBuffer(nsamples * 4)
+    N.check(L.sh_mix_chain_i16(chunks.handle, nv, stride, nsamples, out.handle))
     assert out.download_bytes(nsamples * 2) == want
-    # pointer table, ragged: sources shorter than the output, one empty, one starting 2 bytes into its buffer
-    lens = [nsamples, nsamples - 5, 1000, 0, nsamples // 2 + 1, nsamples, 8, nsamples - 1, nsamples]
+    maps = N.DeviceBuffer(nsamples * 16)
+    N.check(L.sh_mix_chain_i16_parts(chunks.handle, nv, stride, nsamples, maps.handle))
+    got = CM.from_bytes(maps.download_bytes(nsamples * 8))
+    assert CM.apply([got]).tobytes() == want
+    assert got.tobytes() == range_rule_maps(rows, nsamples).tobytes()
+    # pan: the rows as mono voices, each entering as audioop.tostereo(row, lf, rf)
+    fac = rng.uniform(0.2, 1.6, size=(nv, 2))
+    facb = N.DeviceBuffer.from_array(fac.reshape(-1))
+    stereo = [np.frombuffer(audioop.tostereo(x.tobytes(), 2, float(lf), float(rf)), dtype=np.int16) for x, (lf, rf) in zip(rows, fac)]
+    want_st = _audioop_fold(stereo, 2 * nsamples)
+    N.check(L.sh_mix_chain_pan_i16(chunks.handle, nv, stride, nsamples, facb.handle, out.handle))
+    assert out.download_bytes(nsamples * 4) == want_st
+    N.check(L.sh_mix_chain_pan_i16_parts(chunks.handle, nv, stride, nsamples, facb.handle, maps.handle))
+    got = CM.from_bytes(maps.download_bytes(nsamples * 16))
+    assert CM.apply([got]).tobytes() == want_st
+    assert got.tobytes() == range_rule_maps(stereo, 2 * nsamples).tobytes()
+    del stereo, got
+    maps.free()
+    chunks.free()
+    # pointer table, ragged: sources shorter than the output, one empty (all non-empty from 64 voices on, so that the table holds
+    # them all), one starting 2 bytes into its buffer
+    pattern = [nsamples, nsamples - 5, 1000, 0 if nv < 64 else 3, nsamples // 2 + 1, nsamples, 8, nsamples - 1, nsamples]
+    lens = [pattern[v % len(pattern)] for v in range(nv)]
     ragged = [x[:n] for x, n in zip(rows, lens)]
     want = _audioop_fold(ragged, nsamples)
     samples = [_pair(x)[0].to_device() for x in ragged]
@@ -196,7 +237,7 @@ def test_long_buffers_every_kernel_shape(gpu, nsamples):
     bufs = (C.c_void_p * 2)(shifted.handle, samples[1]._device().handle)
     offs = (C.c_size_t * 2)(1, 0)
     cnt = (C.c_uint32 * 2)(len(ragged[0]), len(ragged[1]))
-    N.check(N.lib().sh_mix_chain_gather_i16(bufs, offs, cnt, 2, nsamples, out.handle, 0))
+    N.check(L.sh_mix_chain_gather_i16(bufs, offs, cnt, 2, nsamples, out.handle, 0))
     assert out.download_bytes(nsamples * 2) == _audioop_fold(ragged[:2], nsamples)
 
 
