@@ -1,11 +1,10 @@
-// pcm.hip -- integer/float PCM kernels: quantise, saturating add (Sample.mix), the mixer's
-// saturating chain, and linear-interpolation resampling (Sample.resample).
+// pcm.hip -- integer/float PCM kernels: quantise, saturating add (Sample.mix) and the mixer's
+// saturating chain.  (Linear-interpolation resampling, Sample.resample: resample.hip.)
 //
-// These restate CPython 3.10 Modules/audioop.c (audioop_add_impl, audioop_ratecv_impl), the
-// arithmetic synthplayer's sample.py delegates to.  All of them are HBM-bound byte/integer work:
-// coalesced loads, one output element (or a small vector) per thread, no LDS except for the
-// cross-wave combine of the mixer chain.  Built with -ffp-contract=off: audioop forms
-// prev*d + cur*(outrate-d) with two roundings and a division, and so does k_resample.
+// These restate CPython 3.10 Modules/audioop.c (audioop_add_impl), the arithmetic synthplayer's
+// sample.py delegates to.  All of them are HBM-bound byte/integer work: coalesced loads, one output
+// element (or a small vector) per thread, no LDS except for the cross-wave combine of the mixer
+// chain.  Built with -ffp-contract=off (float64 products stay two roundings).
 #include "common.hpp"
 #include "chain.hpp"
 #include <mutex>
@@ -432,524 +431,6 @@ __global__ __launch_bounds__(256) void k_mix_chain_gather_w(const ChainSrcB* __r
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         if (s0 + j < nsamples) chain_put<WIDTH>(out, s0 + j, acc[j]);
-}
-
-// ---- audioop.ratecv / float32 resample ----------------------------------------------------------
-// One thread per output sample (frame m, channel c).  Output m interpolates input frames j-1 and j,
-// j = ceil(m*inrate/outrate), d = j*outrate - m*inrate (rates gcd-reduced): identical index
-// arithmetic to the reference's state machine, evaluated in closed form.
-struct RatecvArgs {
-    uint64_t n_out_samples;     // out_frames * nch
-    uint64_t m_base;            // output frame index of the launch's first frame (range launches; else 0)
-    uint32_t nch;
-    uint32_t inr, outr;
-    uint32_t step_q, step_r;    // inr / outr and inr % outr: output frame m+1 starts (step_q, step_r) after frame m
-    double   inv_outr;
-    int      shift;             // 32 - 8*width (integer PCM)
-};
-
-// how a kernel forms one output sample
-enum { RS_INT_F64 = 0,          // integer PCM through the float64 expression (any width, any rate)
-       RS_FLOAT = 1,            // float32 PCM through the float64 expression
-       RS_INT_SMALL = 2 };      // 8/16-bit PCM with reduced outrate < 65536: exact 32-bit integer arithmetic
-
-__device__ __forceinline__ void ratecv_index(const RatecvArgs& A, uint64_t m, uint64_t& j, uint32_t& d) {
-    const uint64_t M = m * (uint64_t)A.inr;
-    uint64_t q;
-    int64_t r;
-    if (M < (1ull << 52)) {
-        q = (uint64_t)floor((double)M * A.inv_outr);
-        r = (int64_t)(M - q * (uint64_t)A.outr);
-        if (r < 0) { q -= 1; r += A.outr; }
-        else if (r >= (int64_t)A.outr) { q += 1; r -= A.outr; }
-    } else {
-        q = M / A.outr;
-        r = (int64_t)(M % A.outr);
-    }
-    j = q + (r != 0);
-    d = r ? (uint32_t)(A.outr - (uint32_t)r) : 0u;
-}
-
-// (prev*d + cur*(outrate-d)) / outrate in float64, exactly as audioop forms it: two products, one sum, one
-// correctly rounded division.  The division is Markstein's sequence q = a*y, r = fma(-q, b, a),
-// q' = fma(r, y, q) with y = RN(1/b): it returns the correctly rounded quotient (checked against IEEE
-// division on 3e8 operands in tests/ and by every bit-exact parity test), at 3 instructions instead of
-// the ~12 of the generic lowering -- this kernel must stay HBM-bound.
-__device__ __forceinline__ double ratecv_value(double prev, double cur, double dd, double od, double outr, double inv_outr) {
-    const double a = prev * dd + cur * od;
-    const double q = a * inv_outr;
-    const double r = fma(-q, outr, a);
-    return fma(r, inv_outr, q);
-}
-
-// 8/16-bit PCM, reduced outrate < 65536.  audioop computes trunc(fl(N / outr)) >> s with N = (prev*d + cur*(outr-d)) << s
-// (s = 32 - bits): N is an exact float64 integer (< 2^48), a non-integer N/outr is at least 1/outr > 2^-16 away
-// from an integer while its float64 rounding error is below 2^-21, so the truncation equals integer division, and
-// trunc(.) >> s == floor(M / outr) with M = prev*d + cur*(outr-d) (|M| <= 2^(bits-1)*outr < 2^31; for M < 0 the
-// inner truncation loses less than 2^-s < 1/outr, which the floor of the arithmetic shift restores).  floor(M/outr)
-// is formed as an unsigned division of u = M + 2^(bits-1)*outr (0 <= u < 2^32): trunc(fma(u, 1/outr, 1/(2 outr))) in
-// float64 -- (u + 1/2)/outr is at least 1/(2 outr) > 2^-17 away from every integer and the evaluation error is below
-// 2^-20, so no correction step is needed.  Bit-exactness against audioop is what tests/test_gpu_pcm.py asserts on
-// both paths.
-template <typename T>
-__device__ __forceinline__ T ratecv_small_int(T prev, T cur, uint32_t d, uint32_t outr, double inv_outr) {
-    constexpr int HALF = 1 << (8 * (int)sizeof(T) - 1);
-    const int M = (int)prev * (int)d + (int)cur * (int)(outr - d);
-    const uint32_t u = (uint32_t)M + (uint32_t)HALF * outr;
-    const uint32_t q = (uint32_t)fma((double)u, inv_outr, 0.5 * inv_outr);
-    return (T)((int)q - HALF);
-}
-
-template <typename T, int MODE>
-__device__ __forceinline__ T ratecv_sample(T prev, T cur, uint32_t d, const RatecvArgs& A) {
-    if (MODE == RS_INT_SMALL) {
-        if constexpr (sizeof(T) <= 2) return ratecv_small_int<T>(prev, cur, d, A.outr, A.inv_outr);
-        else return (T)0;
-    }
-    const double dd = (double)d, od = (double)(A.outr - d), outr = (double)A.outr;
-    if (MODE == RS_FLOAT) return (T)ratecv_value((double)prev, (double)cur, dd, od, outr, A.inv_outr);
-    const int ci = (int)((unsigned)(int)cur << A.shift);                               // GETSAMPLE32
-    const int pi = (int)((unsigned)(int)prev << A.shift);
-    return (T)((int)ratecv_value((double)pi, (double)ci, dd, od, outr, A.inv_outr) >> A.shift);   // SETSAMPLE32
-}
-
-// One thread = one output frame x VEC channels, moved as one vector (VEC*sizeof(T) bytes).
-template <typename T, int VEC, int MODE>
-__global__ __launch_bounds__(256) void k_resample(const T* __restrict__ in, T* __restrict__ out, RatecvArgs A) {
-    typedef T vec_t __attribute__((ext_vector_type(VEC)));
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= A.n_out_samples) return;                     // here: number of (frame, channel group) units
-    const uint32_t groups = A.nch / VEC;
-    uint64_t m;
-    uint32_t cg;
-    if (groups == 1) { m = u; cg = 0; }
-    else if (u < 0xFFFFFFFFull) { uint32_t u32 = (uint32_t)u; uint32_t m32 = u32 / groups; m = m32; cg = u32 - m32 * groups; }
-    else { m = u / groups; cg = (uint32_t)(u - m * groups); }
-    m += A.m_base;
-    uint64_t j;
-    uint32_t d;
-    ratecv_index(A, m, j, d);
-    const size_t cur_at = (size_t)j * A.nch + (size_t)cg * VEC;
-    vec_t cur, prev, res;
-    if (VEC == 1) cur[0] = in[cur_at]; else cur = *reinterpret_cast<const vec_t*>(in + cur_at);
-    if (j && d) {
-        if (VEC == 1) prev[0] = in[cur_at - A.nch]; else prev = *reinterpret_cast<const vec_t*>(in + cur_at - A.nch);
-    } else {
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) prev[c] = (T)0;
-    }
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) res[c] = ratecv_sample<T, MODE>(prev[c], cur[c], d, A);
-    const size_t out_at = (size_t)m * A.nch + (size_t)cg * VEC;
-    // (streaming store: +4 % on the 8-channel rows; the frames-per-thread kernels below lose with it -- stereo float32 -14 %)
-    if (VEC == 1) out[out_at] = res[0]; else __builtin_nontemporal_store(res, reinterpret_cast<vec_t*>(out + out_at));
-}
-
-// Few channels (nch == VEC): one thread = FR consecutive output frames x all channels, so that the store
-// is one 8..16-byte vector even for mono 16-bit PCM (a 2-byte store per lane reaches ~1/4 of the bandwidth).
-template <typename T, int VEC, int FR, int MODE>
-__global__ __launch_bounds__(256) void k_resample_frames(const T* __restrict__ in, T* __restrict__ out, RatecvArgs A, uint64_t out_frames) {
-    typedef T vec_t __attribute__((ext_vector_type(VEC * FR)));
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const uint64_t m0 = A.m_base + u * FR;
-    if (m0 >= out_frames) return;
-    vec_t res;
-    // position of frame m0 in input frames: q + r/outr (exact), then (step_q, step_r) per output frame
-    uint64_t q;
-    uint32_t r;
-    {
-        uint64_t j0;
-        uint32_t d0;
-        ratecv_index(A, m0, j0, d0);
-        r = d0 ? A.outr - d0 : 0u;
-        q = j0 - (r != 0);
-    }
-    const uint64_t last_q_frames = out_frames - 1 - m0;           // frames after m0 that exist
-#pragma unroll
-    for (int f = 0; f < FR; ++f) {
-        const uint64_t j = q + (r != 0);
-        const uint32_t d = r ? A.outr - r : 0u;
-        if ((uint64_t)f < last_q_frames) {                        // advance, but never past the last output frame
-            r += A.step_r;
-            q += A.step_q;
-            if (r >= A.outr) { r -= A.outr; q += 1; }
-        }
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) {
-            const T cur = in[j * VEC + c];
-            const T prev = (j && d) ? in[(j - 1) * VEC + c] : (T)0;
-            res[f * VEC + c] = ratecv_sample<T, MODE>(prev, cur, d, A);
-        }
-    }
-    if (m0 + FR <= out_frames) {
-        *reinterpret_cast<vec_t*>(out + m0 * VEC) = res;
-    } else {
-        for (int f = 0; f < FR && m0 + f < out_frames; ++f)
-            for (int c = 0; c < VEC; ++c) out[(m0 + f) * VEC + c] = res[f * VEC + c];
-    }
-}
-
-// Mono / stereo: the input span of a workgroup is staged in LDS with aligned 16-byte loads (coalesced, every
-// input byte fetched once), and each thread interpolates FR consecutive output frames from LDS -- instead of
-// 2*FR narrow gathers per thread.  Used when the span fits the LDS budget (ratios up to ~10:1).
-constexpr uint32_t RS_LDS_BYTES = 48 * 1024;
-
-template <typename T, int VEC, int FR, int MODE>
-__global__ __launch_bounds__(256) void k_resample_lds(const T* __restrict__ in, T* __restrict__ out, RatecvArgs A,
-                                                      uint64_t in_frames, uint64_t out_frames) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    T* lds = reinterpret_cast<T*>(smem);
-    typedef T vec_t __attribute__((ext_vector_type(VEC * FR)));
-    typedef T ld_t __attribute__((ext_vector_type(16 / sizeof(T))));
-    constexpr uint32_t EPV = 16 / sizeof(T);                      // elements per 16-byte vector
-    const uint64_t m_first = A.m_base + (uint64_t)blockIdx.x * (256 * FR);
-    if (m_first >= out_frames) return;
-    uint64_t m_last = m_first + 256 * FR - 1;
-    if (m_last > out_frames - 1) m_last = out_frames - 1;
-    // input frames this workgroup reads: [j(m_first) - 1, j(m_last)]   (uniform)
-    uint64_t jf, jl;
-    uint32_t df, dl;
-    ratecv_index(A, m_first, jf, df);
-    ratecv_index(A, m_last, jl, dl);
-    const uint64_t lo_frame = jf ? jf - 1 : 0;
-    const uint64_t lo_elem = (lo_frame * VEC) & ~(uint64_t)(EPV - 1);            // 16-byte aligned start
-    const uint64_t hi_elem = (jl + 1) * VEC;                                      // exclusive
-    const uint64_t total_elems = in_frames * VEC;
-    const uint32_t nvec = (uint32_t)((hi_elem - lo_elem + EPV - 1) / EPV);
-    for (uint32_t v = threadIdx.x; v < nvec; v += 256) {
-        const uint64_t e = lo_elem + (uint64_t)v * EPV;
-        if (e + EPV <= total_elems) {
-            reinterpret_cast<ld_t*>(lds)[v] = *reinterpret_cast<const ld_t*>(in + e);
-        } else {
-            for (uint32_t k = 0; k < EPV; ++k) lds[v * EPV + k] = (e + k < total_elems) ? in[e + k] : (T)0;
-        }
-    }
-    __syncthreads();
-    const uint64_t m0 = m_first + (uint64_t)threadIdx.x * FR;
-    if (m0 >= out_frames) return;
-    uint64_t q;
-    uint32_t r;
-    {
-        uint64_t j0;
-        uint32_t d0;
-        ratecv_index(A, m0, j0, d0);
-        r = d0 ? A.outr - d0 : 0u;
-        q = j0 - (r != 0);
-    }
-    const uint64_t frames_after = out_frames - 1 - m0;
-    vec_t res;
-#pragma unroll
-    for (int f = 0; f < FR; ++f) {
-        const uint64_t j = q + (r != 0);
-        const uint32_t d = r ? A.outr - r : 0u;
-        if ((uint64_t)f < frames_after) {
-            r += A.step_r;
-            q += A.step_q;
-            if (r >= A.outr) { r -= A.outr; q += 1; }
-        }
-        const uint32_t at = (uint32_t)(j * VEC - lo_elem);                        // LDS element index of frame j
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) {
-            const T cur = lds[at + c];
-            const T prev = (j && d) ? lds[at - VEC + c] : (T)0;
-            res[f * VEC + c] = ratecv_sample<T, MODE>(prev, cur, d, A);
-        }
-    }
-    if (m0 + FR <= out_frames) {
-        *reinterpret_cast<vec_t*>(out + m0 * VEC) = res;
-    } else {
-        for (int f = 0; f < FR && m0 + f < out_frames; ++f)
-            for (int c = 0; c < VEC; ++c) out[(m0 + f) * VEC + c] = res[f * VEC + c];
-    }
-}
-
-// One thread's FR output frames of k_resample_small, from the staged span (LDS element 0 = input element lo_elem).  GROUPS == 2:
-// the thread's frames are two runs of FR/2, 256*FR/2 frames apart, so that each of its stores is one 16-byte vector NEXT to its
-// neighbour lanes' (a wave's store instruction then writes 1 KB of consecutive bytes; with one run of 16 16-bit frames a lane's two
-// 16-byte stores interleave with its neighbours' at a 32-byte stride).
-template <typename T, int VEC, int FR, int GROUPS = 1>
-__device__ __forceinline__ void resample_small_frames(const unsigned char* smem, T* __restrict__ out, const RatecvArgs& A, uint64_t m_first,
-                                                      uint64_t q0, uint32_t r0, uint64_t lo_elem, uint64_t out_frames) {
-    const T* lds = reinterpret_cast<const T*>(smem);
-    constexpr int FRG = FR / GROUPS;
-    typedef T vec_t __attribute__((ext_vector_type(VEC * FRG)));
-    constexpr int HALF = 1 << (8 * (int)sizeof(T) - 1);
-    uint64_t m0 = m_first + (uint64_t)threadIdx.x * FRG;
-    if (m0 >= out_frames) return;
-    // this thread's first frame: (q0, r0) advanced by threadIdx.x*FR output frames (host guarantees < 2^31)
-    uint32_t r, qe_elem;
-    {
-        const uint32_t tot = r0 + __umul24(threadIdx.x * FRG, A.inr);
-        const uint32_t dq = (uint32_t)fma((double)tot, A.inv_outr, 0.5 * A.inv_outr);   // floor(tot/outr), exact as below
-        r = tot - dq * A.outr;
-        qe_elem = (uint32_t)(q0 * VEC - lo_elem) + dq * VEC;                     // LDS element index of frame q
-    }
-    const uint32_t step_elem = A.step_q * VEC;
-    const double half_inv = 0.5 * A.inv_outr;
-    constexpr bool PAIR_IN_DWORD = 2 * VEC * sizeof(T) <= 4;
-    constexpr uint32_t MASK = (1u << (8 * sizeof(T))) - 1u;
-    constexpr uint32_t FLIP = sizeof(T) == 2 ? 0x80008000u : 0x80808080u;
-#pragma unroll
-    for (int g = 0; g < GROUPS; ++g) {
-    vec_t res;
-#pragma unroll
-    for (int f = 0; f < FRG; ++f) {
-        uint32_t pair = 0;
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) {
-            // ua = a + HALF, ub = b + HALF as unsigned bit patterns (x + HALF == x ^ HALF on the sample width)
-            uint32_t ua, ub;
-            if (PAIR_IN_DWORD) {
-                // frames q and q+1 together are <= 4 bytes at a 1- or 2-byte aligned address: two aligned dwords and a
-                // funnel shift (a misaligned ds_read_b32 is several times slower than the extra three instructions)
-                if (c == 0) {
-                    const uint32_t byte_off = qe_elem * (uint32_t)sizeof(T);
-                    const uint32_t* l32 = reinterpret_cast<const uint32_t*>(smem) + (byte_off >> 2);
-                    pair = __builtin_amdgcn_alignbit(l32[1], l32[0], (byte_off & 3u) * 8u) ^ FLIP;
-                }
-                ua = (pair >> (8 * sizeof(T) * c)) & MASK;
-                ub = (pair >> (8 * sizeof(T) * (VEC + c))) & MASK;
-            } else {
-                ua = ((uint32_t)lds[qe_elem + c] & MASK) ^ (uint32_t)HALF;
-                ub = ((uint32_t)lds[qe_elem + VEC + c] & MASK) ^ (uint32_t)HALF;
-            }
-            const uint32_t u = (uint32_t)__mul24((int)ub - (int)ua, (int)r) + __umul24(ua, A.outr);
-            // (u + 1/2)/outr is at least 1/(2 outr) > 2^-17 away from every integer and the float64 evaluation is off by
-            // less than 2^-20, so the truncation is floor(u/outr) exactly: 3 instructions, no correction step
-            const uint32_t q = (uint32_t)fma((double)u, A.inv_outr, half_inv);
-            res[f * VEC + c] = (T)(q ^ (uint32_t)HALF);
-        }
-        r += A.step_r;
-        const bool wrap = r >= A.outr;
-        r -= wrap ? A.outr : 0u;
-        qe_elem += step_elem + (wrap ? (uint32_t)VEC : 0u);
-    }
-    if (m0 + FRG <= out_frames) {
-        __builtin_nontemporal_store(res, reinterpret_cast<vec_t*>(out + m0 * VEC));
-    } else {
-        for (int f = 0; f < FRG && m0 + f < out_frames; ++f)
-            for (int c = 0; c < VEC; ++c) out[(m0 + f) * VEC + c] = res[f * VEC + c];
-    }
-    if (g + 1 < GROUPS) {
-        // on to the thread's next run: 255 * FRG frames further (the loop above has moved FRG already)
-        m0 += 256 * FRG;
-        if (m0 >= out_frames) return;
-        const uint32_t tot = r + (uint32_t)(255 * FRG) * A.inr;
-        const uint32_t dq = (uint32_t)fma((double)tot, A.inv_outr, half_inv);
-        r = tot - dq * A.outr;
-        qe_elem += dq * VEC;
-    }
-    }
-}
-
-// 8/16-bit PCM, few channels, reduced rates below 65536 (the common Sample.resample case: 16-bit mono/stereo
-// between 44.1k/48k/96k).  The generic kernels above are VALU-issue-bound there (~55 instructions per output
-// sample at 2-4 bytes of traffic each), so this one strips the arithmetic to ~20 full-rate instructions:
-//  * the workgroup's input span goes through LDS (aligned 16-byte loads), positions are 32-bit LDS-relative;
-//  * output m sits at input position q + r/outr; with a = x[q], b = x[q+1] the reference's expression is
-//    M = a*(outr-r) + b*r for every r (r == 0 gives cur = x[q], weight outr), so there is no prev/cur select;
-//  * u = M + HALF*outr = (b-a)*r + (a+HALF)*outr in 24-bit multiplies (mod 2^32; 0 <= u < 2^32);
-//  * floor(u/outr) = trunc(fma(u, 1/outr, 1/(2 outr))) in float64, exact without a correction step.  See
-//    ratecv_small_int for why the floor equals audioop's float64 expression.
-// (Measured and dropped, bit-identical both: the interpolation as ONE v_dot2_u32_u16 on packed weights -- 0.395 vs 0.391 ms on 900 MB;
-// the output frames dealt to the lanes, no LDS bank conflicts and 16 instead of 20 instructions per sample -- not faster either:
-// CHANGELOG items 39 and 22; profiles/r03_summary.md.)
-template <typename T, int VEC, int FR, int GROUPS = 1>
-__global__ __launch_bounds__(256) void k_resample_small(const T* __restrict__ in, T* __restrict__ out, RatecvArgs A,
-                                                        uint64_t in_frames, uint64_t out_frames, uint32_t span_vecs) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    T* lds = reinterpret_cast<T*>(smem);
-    typedef T ld_t __attribute__((ext_vector_type(16 / sizeof(T))));
-    constexpr uint32_t EPV = 16 / sizeof(T);
-    const uint64_t m_first = A.m_base + (uint64_t)blockIdx.x * (256 * FR);
-    if (m_first >= out_frames) return;
-    // position of the workgroup's first output frame: q0 + r0/outr   (uniform)
-    uint64_t q0;
-    uint32_t r0;
-    {
-        uint64_t jf;
-        uint32_t df;
-        ratecv_index(A, m_first, jf, df);
-        r0 = df ? A.outr - df : 0u;
-        q0 = jf - (r0 != 0);
-    }
-    const uint64_t lo_elem = (q0 * VEC) & ~(uint64_t)(EPV - 1);                  // 16-byte aligned start of the span
-    const uint64_t total_elems = in_frames * VEC;
-    for (uint32_t v = threadIdx.x; v < span_vecs; v += 256) {
-        const uint64_t e = lo_elem + (uint64_t)v * EPV;
-        if (e + EPV <= total_elems) {
-            // streaming on both sides (input read once per workgroup, output never re-read): +1..3 % on the 16-bit rows
-            reinterpret_cast<ld_t*>(lds)[v] = __builtin_nontemporal_load(reinterpret_cast<const ld_t*>(in + e));
-        } else {
-            for (uint32_t k = 0; k < EPV; ++k) lds[v * EPV + k] = (e + k < total_elems) ? in[e + k] : (T)0;
-        }
-    }
-    __syncthreads();
-    resample_small_frames<T, VEC, FR, GROUPS>(smem, out, A, m_first, q0, r0, lo_elem, out_frames);
-}
-
-// ---- 16-bit mono between rates with a SHORT period (44.1k <-> 48k <-> 96k ...: reduced outrate <= 2048) --------------------------------
-// k_resample_small needs ~23 VALU instructions per output sample (the position's remainder stepped and wrapped, the frame pair cut out of
-// two dwords, the weights), and with its 78 % of the VALU slots taken it sits between its two roofs: 0.68 of HBM whatever one of those
-// instructions is replaced by (five variants: profiles/r06_resample_ab.txt).  But output frame m and m + outr lie at the same fraction
-// r / outr, inr input frames apart: with CHUNKS of K whole periods (L = K outr output frames, K inr input frames, starting at remainder 0)
-// thread t's sixteen frames of EVERY chunk have the same weights (outr - r, r) and the same offsets into the chunk's input span.  The
-// workgroups stay (chunk C, C + grid, ...), a thread works its sixteen (weights, offset) pairs out ONCE, and a sample is
-//      an address (offset + where the span starts in its first 16-byte vector), two sign-extending 16-bit LDS reads,
-//      u = a (outr - r) + b r + 65536 outr in two 24-bit multiply-adds, floor(u / outr) by ratecv_small_int's float64 step (3 instructions) --
-// whose low sixteen bits ARE the sample (floor(M / outr) + 65536: no bias to take off again) -- 6.5 instructions instead of 23.
-// The same integers as k_resample_small's, i.e. audioop.ratecv's (tests/test_gpu_pcm.py against the live module).
-struct PeriodArgs {
-    uint64_t c0, c1;             // chunks [c0, c1), absolute: chunk C = output frames [C L, (C + 1) L) = input frames from C kinr on.  The host
-                                 // passes INTERIOR chunks only -- span wholly inside the held input, frames wholly inside the launch's range --
-                                 // so the kernel tests nothing; what lies in front of and behind them goes through k_resample_small
-    uint32_t L, kinr;            // output / input frames per chunk (K periods); L is a multiple of 8: 16-byte stores
-    uint32_t inr, outr;
-    uint32_t span_vecs;          // 16-byte vectors staged per chunk
-    uint32_t per_wg;             // consecutive chunks per workgroup
-    double   inv_outr;
-};
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// NV: 16-byte vectors of the span per thread (span_vecs <= 256 NV).  A workgroup works through per_wg CONSECUTIVE chunks and ends; the
-// span of the next chunk is loaded into registers while this one is worked on.  What the shape of the loop is for
-// (profiles/r06_resample_period.txt):
-//  * this chip counts loads and stores in ONE in-order counter (vmcnt): "wait for my loads" also waits for every store issued before
-//    them.  The next span's loads are therefore issued BEFORE the chunk's stores and waited for at the END of the turn, where the wait
-//    the compiler inserts is vmcnt(stores of this turn): the stores stay in flight across the barrier.  That needs a turn without a
-//    branch around a memory instruction (a path with fewer stores, and the count drops to zero): lanes beyond the span load its last
-//    vector again, lanes beyond the chunk's last run do that run again (same frames, same values, same address), and L is a multiple
-//    of 8, so a run is whole or absent;
-//  * workgroups that STAY for the whole call (chunks C, C + grid, ...) march in step -- all load, all compute, all store -- and reach 0.63-0.70
-//    of HBM on the 44.1 -> 48 kHz row where workgroups of ONE chunk each (dispatched as others end, their phases mixed) reach 0.72;
-//    but one chunk per workgroup pays the sixteen (weights, offset) set-ups for sixteen samples (upsampling 44.1 -> 96 kHz: 0.60
-//    against 0.70).  A few chunks per workgroup keep both.
-// VEC: channels (1: mono, a run = 8 frames; 2: stereo, a run = 4 frames -- 16 bytes either way).  All positions below are in FRAMES; a frame
-// is VEC shorts.
-template <int VEC, int NV>
-__global__ __launch_bounds__(256) void k_resample_period_i16(const short* __restrict__ in, short* __restrict__ out, PeriodArgs P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int FPR = 8 / VEC;                      // frames per run
-    constexpr uint32_t RUN2 = 256u * FPR;             // the second run lies this many frames behind the first: a wave's store instruction writes 1 KB of consecutive bytes
-    const uint32_t t = threadIdx.x;
-    const double half_inv = 0.5 * P.inv_outr;
-    // the thread's frames of a chunk: two runs (the last run of each half that lies inside the chunk: L >= RUN2 + FPR, a multiple of FPR)
-    uint32_t w0[2 * FPR], w1[2 * FPR], ob[2 * FPR];
-    const uint32_t last0 = P.L / FPR - 1u, last1 = (P.L - RUN2) / FPR - 1u;
-    const uint32_t run0[2] = {(uint32_t)FPR * (t < last0 ? t : last0), RUN2 + (uint32_t)FPR * (t < last1 ? t : last1)};
-#pragma unroll
-    for (int k = 0; k < 2 * FPR; ++k) {
-        const uint32_t e = __umul24(run0[k / FPR] + (uint32_t)(k % FPR), P.inr);  // < 2^12 * 2^16
-        const uint32_t dq = (uint32_t)fma((double)e, P.inv_outr, half_inv);        // floor(e / outr), exact (ratecv_small_int)
-        const uint32_t r = e - dq * P.outr;
-        w0[k] = P.outr - r;
-        w1[k] = r;
-        ob[k] = dq * (uint32_t)(2 * VEC);              // bytes
-    }
-    const int acc = (int)(65536u * P.outr);
-    // (the LDS address of the staged span for the hand-written reads below: 0 in this kernel -- it has no other shared memory -- but asked for, not assumed)
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-    uint64_t C = P.c0 + (uint64_t)blockIdx.x * P.per_wg;
-    if (C >= P.c1) return;
-    const uint64_t c_end = C + P.per_wg < P.c1 ? C + P.per_wg : P.c1;
-    short8v pre[NV];
-    uint32_t vi[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) vi[i] = t + 256u * i < P.span_vecs ? t + 256u * i : P.span_vecs - 1u;
-    {
-        const short8v* __restrict__ src = reinterpret_cast<const short8v*>(in + ((C * (uint64_t)P.kinr * VEC) & ~(uint64_t)7));
-#pragma unroll
-        for (int i = 0; i < NV; ++i) pre[i] = __builtin_nontemporal_load(src + vi[i]);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) reinterpret_cast<short8v*>(smem)[vi[i]] = pre[i];
-    }
-    for (;;) {
-        __syncthreads();                                   // the chunk's span is in LDS
-        const bool more = C + 1 < c_end;                   // (uniform)
-        if (more) {
-            const short8v* __restrict__ src = reinterpret_cast<const short8v*>(in + (((C + 1) * (uint64_t)P.kinr * VEC) & ~(uint64_t)7));
-            static_for<0, NV>([&](auto i_) { constexpr int i = decltype(i_)::value; pre[i] = __builtin_nontemporal_load(src + vi[i]); });
-        }
-        const uint32_t rel0b = (uint32_t)((C * (uint64_t)P.kinr * VEC) & 7) * 2u;
-        short* __restrict__ outC = out + C * (uint64_t)P.L * VEC;
-        auto run = [&](auto g_) __attribute__((always_inline)) {
-            constexpr int g = decltype(g_)::value;
-            // The run's frame pairs (a, b) out of LDS, by hand.  Mono: two sign-extending 16-bit reads per frame -- written as plain loads the
-            // compiler fuses each pair into ONE ds_read_b32 at a 2-byte-aligned address, which the LDS serves at a fraction of the rate
-            // (0.87 ms for the 900 MB row against 0.44 for k_resample_small); `volatile` loads become FLAT loads; and the D16 forms that
-            // would fill the halves of one register for a v_dot2 clear the other half on this chip (SRAM ECC).  Stereo: frames are dwords,
-            // one ds_read2_b32 per pair.  The reads are waited for inside the statement (the compiler's counters do not see them).
-            uint32_t at[FPR];
-#pragma unroll
-            for (int f = 0; f < FPR; ++f) at[f] = ob[FPR * g + f] + rel0b + lds0;
-            short8v res;
-            if constexpr (VEC == 1) {
-                int a[8], b[8];
-                asm volatile(
-                    "ds_read_i16 %0, %16\n\tds_read_i16 %8, %16 offset:2\n\t"
-                    "ds_read_i16 %1, %17\n\tds_read_i16 %9, %17 offset:2\n\t"
-                    "ds_read_i16 %2, %18\n\tds_read_i16 %10, %18 offset:2\n\t"
-                    "ds_read_i16 %3, %19\n\tds_read_i16 %11, %19 offset:2\n\t"
-                    "ds_read_i16 %4, %20\n\tds_read_i16 %12, %20 offset:2\n\t"
-                    "ds_read_i16 %5, %21\n\tds_read_i16 %13, %21 offset:2\n\t"
-                    "ds_read_i16 %6, %22\n\tds_read_i16 %14, %22 offset:2\n\t"
-                    "ds_read_i16 %7, %23\n\tds_read_i16 %15, %23 offset:2\n\t"
-                    "s_waitcnt lgkmcnt(0)"
-                    : "=&v"(a[0]), "=&v"(a[1]), "=&v"(a[2]), "=&v"(a[3]), "=&v"(a[4]), "=&v"(a[5]), "=&v"(a[6]), "=&v"(a[7]),
-                      "=&v"(b[0]), "=&v"(b[1]), "=&v"(b[2]), "=&v"(b[3]), "=&v"(b[4]), "=&v"(b[5]), "=&v"(b[6]), "=&v"(b[7])
-                    : "v"(at[0]), "v"(at[1]), "v"(at[2]), "v"(at[3]), "v"(at[4]), "v"(at[5]), "v"(at[6]), "v"(at[7])
-                    : "memory");
-#pragma unroll
-                for (int f = 0; f < 8; ++f) {
-                    const uint32_t u = (uint32_t)__mul24(a[f], (int)w0[8 * g + f]) + (uint32_t)(__mul24(b[f], (int)w1[8 * g + f]) + acc);
-                    res[f] = (short)(uint32_t)fma((double)u, P.inv_outr, half_inv);
-                }
-            } else {
-                uint64_t ab[4];                            // low dword: frame q (L | R << 16), high dword: frame q + 1
-                asm volatile(
-                    "ds_read2_b32 %0, %4 offset1:1\n\tds_read2_b32 %1, %5 offset1:1\n\t"
-                    "ds_read2_b32 %2, %6 offset1:1\n\tds_read2_b32 %3, %7 offset1:1\n\t"
-                    "s_waitcnt lgkmcnt(0)"
-                    : "=&v"(ab[0]), "=&v"(ab[1]), "=&v"(ab[2]), "=&v"(ab[3])
-                    : "v"(at[0]), "v"(at[1]), "v"(at[2]), "v"(at[3])
-                    : "memory");
-#pragma unroll
-                for (int f = 0; f < 4; ++f) {
-                    const int fa = (int)(uint32_t)ab[f], fb = (int)(uint32_t)(ab[f] >> 32);
-                    const int la = (int)(short)fa, ra = fa >> 16, lb = (int)(short)fb, rb = fb >> 16;
-                    const int k0 = (int)w0[4 * g + f], k1 = (int)w1[4 * g + f];
-                    const uint32_t ul = (uint32_t)__mul24(la, k0) + (uint32_t)(__mul24(lb, k1) + acc);
-                    const uint32_t ur = (uint32_t)__mul24(ra, k0) + (uint32_t)(__mul24(rb, k1) + acc);
-                    res[2 * f] = (short)(uint32_t)fma((double)ul, P.inv_outr, half_inv);
-                    res[2 * f + 1] = (short)(uint32_t)fma((double)ur, P.inv_outr, half_inv);
-                }
-            }
-            __builtin_nontemporal_store(res, reinterpret_cast<short8v*>(outC + (size_t)run0[g] * VEC));
-        };
-        run(std::integral_constant<int, 0>{});
-        run(std::integral_constant<int, 1>{});
-        __syncthreads();                                   // everybody has read the span
-        if (!more) break;
-        // (waits for the loads; this turn's stores stay in flight)
-        static_for<0, NV>([&](auto i_) { constexpr int i = decltype(i_)::value; reinterpret_cast<short8v*>(smem)[vi[i]] = pre[i]; });
-        C += 1;
-    }
-}
-
-uint64_t gcd_u64(uint64_t a, uint64_t b) {
-    while (b) {
-        uint64_t t = a % b;
-        a = b;
-        b = t;
-    }
-    return a;
 }
 
 int fetch_flag(int* result) {
@@ -1540,296 +1021,6 @@ int sh_mix_chain(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t
     std::vector<uint32_t> lens(nvoices, nsamples);
     for (uint32_t v = 0; v < nvoices; ++v) offs[v] = (size_t)v * stride;
     return sh_mix_chain_gather(srcs.data(), offs.data(), lens.data(), nvoices, nsamples, width, out, 0);
-}
-
-size_t sh_resample_out_frames(size_t in_frames, int inrate, int outrate) {
-    if (in_frames == 0 || inrate <= 0 || outrate <= 0) return 0;
-    uint64_t g = gcd_u64((uint64_t)inrate, (uint64_t)outrate);
-    uint64_t inr = (uint64_t)inrate / g, outr = (uint64_t)outrate / g;
-    unsigned __int128 t = (unsigned __int128)(in_frames - 1) * outr;
-    return (size_t)(t / inr) + 1;
-}
-
-// in / out are the addresses input frame 0 / output frame 0 would have (range launches pass pointers shifted back by
-// the frames they do not hold: never dereferenced outside [held input), [m_base, m_end)).  in_frames = end of the
-// held input, m_base / m_end = output frame range.
-static int resample_launch(const void* in, size_t in_frames, int nch, int width, int is_float, int inrate, int outrate,
-                           void* out, size_t m_base, size_t m_end, size_t in_lo, bool allow_period = true);
-
-// Output ranges of any length: one launch per 2^30 output samples at most (a dispatch holds fewer than 2^32 work-items per grid
-// dimension; the kernels work from absolute output positions, so a range cut at multiples of 4096 frames is the same range)
-// (in_lo: the first input frame that is held -- range launches; the kernels that stage whole chunks must not read below it)
-static int resample_dev(const void* in, size_t in_frames, int nch, int width, int is_float, int inrate, int outrate,
-                        void* out, size_t m_base, size_t m_end, size_t in_lo = 0) {
-    size_t chunk = (((size_t)1 << 30) / (size_t)nch) & ~(size_t)4095;
-    if (chunk < 4096) chunk = 4096;
-    for (size_t m = m_base; m < m_end; m += chunk) {
-        const int rc = resample_launch(in, in_frames, nch, width, is_float, inrate, outrate, out, m, m_end - m < chunk ? m_end : m + chunk, in_lo);
-        if (rc) return rc;
-    }
-    return SH_OK;
-}
-
-static int resample_launch(const void* in, size_t in_frames, int nch, int width, int is_float, int inrate, int outrate,
-                           void* out, size_t m_base, size_t m_end, size_t in_lo, bool allow_period) {
-    const size_t out_frames = m_end - m_base;        // frames this launch writes
-    uint64_t g = gcd_u64((uint64_t)inrate, (uint64_t)outrate);
-    RatecvArgs A;
-    A.nch = (uint32_t)nch;
-    A.inr = (uint32_t)((uint64_t)inrate / g);
-    A.outr = (uint32_t)((uint64_t)outrate / g);
-    A.inv_outr = 1.0 / (double)A.outr;
-    A.step_q = A.inr / A.outr;
-    A.step_r = A.inr % A.outr;
-    A.shift = 32 - 8 * width;
-    A.m_base = (uint64_t)m_base;
-    const bool small = !is_float && width <= 2 && A.outr < 65536u;
-#define SH_I(M, ...) do { if (small) M(__VA_ARGS__, RS_INT_SMALL); else M(__VA_ARGS__, RS_INT_F64); } while (0)
-    if (!out_frames) return SH_OK;
-    hipStream_t st = sh::state().stream;
-    // widest channel vector that divides nch, stays <= 16 bytes and keeps every access aligned
-    const bool aligned = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-    int vec = 1;
-    if (aligned) {
-        const int maxvec = 16 / width;
-        for (int v = maxvec; v > 1; v >>= 1)
-            if (nch % v == 0) { vec = v; break; }
-    }
-    // mono / stereo (and other narrow layouts that fit one vector): several frames per thread
-    if (aligned && nch * width <= 8 && (nch == 1 || nch == 2 || nch == 4)) {
-        int fr = 16 / (nch * width) > 8 ? 8 : 16 / (nch * width);        // 16-byte stores, at most 8 frames per thread
-        // 16-bit mono through the LDS kernel: 16 frames (two 16-byte stores) per thread -- the per-thread set-up (position of the
-        // first frame, staging loop) is a fifth of the instructions at 8 frames; +4 % (stereo, already at 16 bytes per 4 frames: -5 %)
-        // (only when the doubled input span still fits the LDS budget of that kernel: the other kernels keep 8 frames)
-        // 16-bit mono / stereo between rates with a short period: chunks of whole periods, the weights loop-invariant per thread (k_resample_period_i16)
-        if (allow_period && small && width == 2 && (nch == 1 || nch == 2) && A.inr < 65536u && A.outr <= 2048u && !sh::knobs().no_period) {
-            const uint32_t V = (uint32_t)nch, fpr = 8u / V, lmax = 512u * fpr;         // a run = 16 bytes; two runs per thread
-            const uint32_t s_out = fpr / (uint32_t)gcd_u64(A.outr, fpr);                // L = K outr must be a multiple of a run (16-byte stores)
-            uint32_t K = lmax / A.outr;
-            const uint32_t k_span = (14336u / V) / A.inr;                               // ... and the chunk's input span at most 28 KB
-            if (K > k_span) K = k_span;
-            K -= K % s_out;
-            const uint32_t L = K * A.outr;
-            if (L >= lmax / 4u * 3u) {                                                  // (three quarters of the threads' frames in use, at least)
-                PeriodArgs P;
-                P.L = L; P.kinr = K * A.inr; P.inr = A.inr; P.outr = A.outr; P.inv_outr = A.inv_outr;
-                const uint32_t off_max = (uint32_t)(((uint64_t)(L - 1) * A.inr) / A.outr);
-                P.span_vecs = (7u + (off_max + 2u) * V + 7u) / 8u;
-                const uint32_t lds_bytes = P.span_vecs * 16u;
-                // the interior chunks: frames wholly inside [m_base, m_end), span wholly inside the held input [in_lo, in_frames)
-                uint64_t cA = ((uint64_t)m_base + L - 1) / L, cB = (uint64_t)m_end / L;
-                while (cA < cB && ((cA * P.kinr * V) & ~(uint64_t)7) < (uint64_t)in_lo * V) ++cA;
-                while (cB > cA && (((cB - 1) * P.kinr * V) & ~(uint64_t)7) + 8ull * P.span_vecs > (uint64_t)in_frames * V) --cB;
-                if (cB > cA + 1) {
-                    P.c0 = cA; P.c1 = cB;
-                    // consecutive chunks per workgroup (profiles/r06_resample_period.txt; SYNTHHIP_PERIOD_CHUNKS overrides).  Mono: two -- one where
-                    // the input is the larger side (nothing to amortise the set-up against but reads), four where the output is (upsampling by
-                    // two or more).  Stereo: one (a thread's set-up is eight entries, and the longer a workgroup stays the more of them march in step).
-                    P.per_wg = sh::knobs().period_chunks > 0 ? (uint32_t)sh::knobs().period_chunks
-                             : nch == 2 || A.inr >= 2 * A.outr ? 1u : A.outr >= 2 * A.inr ? 4u : 2u;
-                    const int nvk = P.span_vecs <= 512u ? 2 : P.span_vecs <= 1024u ? 4 : 8;
-                    const dim3 gp((uint32_t)((cB - cA + P.per_wg - 1) / P.per_wg));
-#define SH_RP(V_, N_) hipLaunchKernelGGL((k_resample_period_i16<V_, N_>), gp, dim3(256), lds_bytes, st, (const short*)in, (short*)out, P)
-                    if (nch == 1) { if (nvk == 2) SH_RP(1, 2); else if (nvk == 4) SH_RP(1, 4); else SH_RP(1, 8); }
-                    else { if (nvk == 2) SH_RP(2, 2); else if (nvk == 4) SH_RP(2, 4); else SH_RP(2, 8); }
-#undef SH_RP
-                    SH_CHECK_LAUNCH("k_resample_period_i16");
-                    // ... and what lies in front of the first and behind the last interior chunk: k_resample_small (allow_period = false)
-                    int rc = SH_OK;
-                    if ((uint64_t)m_base < cA * L) rc = resample_launch(in, in_frames, nch, width, is_float, inrate, outrate, out, m_base, (size_t)(cA * L), in_lo, false);
-                    if (!rc && cB * L < (uint64_t)m_end) rc = resample_launch(in, in_frames, nch, width, is_float, inrate, outrate, out, (size_t)(cB * L), m_end, in_lo, false);
-                    return rc;
-                }
-            }
-        }
-        bool wide = false;
-        if (small && width == 2 && nch == 1 && A.inr < 65536u) {
-            const uint64_t sf2 = ((uint64_t)256 * 2 * fr * A.inr + A.outr - 1) / A.outr + 3;
-            wide = ((sf2 * nch + 8 + 7) / 8 + 1) * 16 <= RS_LDS_BYTES;
-        }
-        if (wide) fr *= 2;
-        A.n_out_samples = (uint64_t)out_frames;
-        dim3 g2(sh::div_up(sh::div_up(out_frames, fr), 256));
-        // input bytes one workgroup (256*fr output frames) touches; stage them in LDS when they fit
-        const uint64_t span_frames = ((uint64_t)256 * fr * A.inr + A.outr - 1) / A.outr + 3;
-        const uint64_t span_bytes = span_frames * nch * width + 32;
-        if (small && A.inr < 65536u) {
-            // span: frames q0 .. q0 + floor((r0 + (256*fr-1)*inr)/outr) + 1, the alignment slack of the first vector,
-            // and one more vector for the dword-pair reads
-            const uint32_t epv = 16 / width;
-            const uint64_t svecs = (span_frames * nch + epv + epv - 1) / epv + 1;
-            if (svecs * 16 <= RS_LDS_BYTES) {
-                const uint32_t span_vecs = (uint32_t)svecs, lds_bytes = span_vecs * 16;
-#define SH_RM(T, V, F) hipLaunchKernelGGL((k_resample_small<T, V, F>), g2, dim3(256), lds_bytes, st, (const T*)in, (T*)out, A, (uint64_t)in_frames, (uint64_t)m_end, span_vecs)
-                // 16-bit mono: 16 frames per thread as two runs of 8 (GROUPS = 2) -- a wave's store instruction then writes 1 KB of
-                // consecutive bytes: +0.4 / +2.2 / +4 % on 44.1 -> 48, 96 -> 44.1, 48 -> 44.1 kHz against one run of 16
-                if (wide) hipLaunchKernelGGL((k_resample_small<short, 1, 16, 2>), g2, dim3(256), lds_bytes, st, (const short*)in, (short*)out, A,
-                                             (uint64_t)in_frames, (uint64_t)m_end, span_vecs);
-                else if (width == 2) { if (nch == 1) SH_RM(short, 1, 8); else if (nch == 2) SH_RM(short, 2, 4); else SH_RM(short, 4, 2); }
-                else { if (nch == 1) SH_RM(signed char, 1, 8); else if (nch == 2) SH_RM(signed char, 2, 8); else SH_RM(signed char, 4, 4); }
-#undef SH_RM
-                SH_CHECK_LAUNCH("k_resample_small");
-                return SH_OK;
-            }
-        }
-        if (nch <= 2 && span_bytes <= RS_LDS_BYTES) {
-            const uint32_t lds_bytes = (uint32_t)((span_bytes + 15) & ~15ull);
-#define SH_RL(T, V, F, FL) hipLaunchKernelGGL((k_resample_lds<T, V, F, FL>), g2, dim3(256), lds_bytes, st, (const T*)in, (T*)out, A, (uint64_t)in_frames, (uint64_t)m_end)
-            if (is_float) { if (nch == 1) SH_RL(float, 1, 4, RS_FLOAT); else SH_RL(float, 2, 2, RS_FLOAT); }
-            else if (width == 2) { if (nch == 1) SH_I(SH_RL, short, 1, 8); else SH_I(SH_RL, short, 2, 4); }
-            else if (width == 4) { if (nch == 1) SH_RL(int, 1, 4, RS_INT_F64); else SH_RL(int, 2, 2, RS_INT_F64); }
-            else { if (nch == 1) SH_I(SH_RL, signed char, 1, 8); else SH_I(SH_RL, signed char, 2, 8); }
-#undef SH_RL
-            SH_CHECK_LAUNCH("k_resample_lds");
-            return SH_OK;
-        }
-#define SH_RF(T, V, F, FL) hipLaunchKernelGGL((k_resample_frames<T, V, F, FL>), g2, dim3(256), 0, st, (const T*)in, (T*)out, A, (uint64_t)m_end)
-        bool launched = true;
-        if (is_float) {
-            if (nch == 1) SH_RF(float, 1, 4, RS_FLOAT); else if (nch == 2) SH_RF(float, 2, 2, RS_FLOAT); else launched = false;
-        } else if (width == 2) {
-            if (nch == 1) SH_I(SH_RF, short, 1, 8); else if (nch == 2) SH_I(SH_RF, short, 2, 4); else SH_I(SH_RF, short, 4, 2);
-        } else if (width == 4) {
-            if (nch == 1) SH_RF(int, 1, 4, RS_INT_F64); else if (nch == 2) SH_RF(int, 2, 2, RS_INT_F64); else launched = false;
-        } else {
-            if (nch == 1) SH_I(SH_RF, signed char, 1, 8); else if (nch == 2) SH_I(SH_RF, signed char, 2, 8); else SH_I(SH_RF, signed char, 4, 4);
-        }
-#undef SH_RF
-        if (launched) {
-            SH_CHECK_LAUNCH("k_resample_frames");
-            return SH_OK;
-        }
-    }
-    A.n_out_samples = (uint64_t)out_frames * (nch / vec);
-    dim3 grid(sh::div_up(A.n_out_samples, 256));
-#define SH_RS(T, V, F) hipLaunchKernelGGL((k_resample<T, V, F>), grid, dim3(256), 0, st, (const T*)in, (T*)out, A)
-    if (is_float) {
-        if (vec == 4) SH_RS(float, 4, RS_FLOAT); else if (vec == 2) SH_RS(float, 2, RS_FLOAT); else SH_RS(float, 1, RS_FLOAT);
-    } else if (width == 2) {
-        if (vec == 8) SH_I(SH_RS, short, 8); else if (vec == 4) SH_I(SH_RS, short, 4);
-        else if (vec == 2) SH_I(SH_RS, short, 2); else SH_I(SH_RS, short, 1);
-    } else if (width == 4) {
-        if (vec == 4) SH_RS(int, 4, RS_INT_F64); else if (vec == 2) SH_RS(int, 2, RS_INT_F64); else SH_RS(int, 1, RS_INT_F64);
-    } else {
-        if (vec == 16) SH_I(SH_RS, signed char, 16); else if (vec == 8) SH_I(SH_RS, signed char, 8);
-        else if (vec == 4) SH_I(SH_RS, signed char, 4); else if (vec == 2) SH_I(SH_RS, signed char, 2);
-        else SH_I(SH_RS, signed char, 1);
-    }
-#undef SH_RS
-#undef SH_I
-    SH_CHECK_LAUNCH("k_resample");
-    return SH_OK;
-}
-
-// audioop.ratecv at width 3 works on GETSAMPLE32 = value << 8 and stores SETSAMPLE32 = result >> 8: the 32-bit path on
-// unpacked samples, packed again.
-static int resample24(const void* in, size_t in_frames_held, size_t in_first, int nch, int inrate, int outrate,
-                      void* out, size_t out_first, size_t out_n) {
-    sh::Temp tin, tout;
-    int rc = tin.alloc(in_frames_held * nch * 4);
-    if (!rc) rc = tout.alloc(out_n * nch * 4);
-    if (!rc) rc = sh::unpack24(in, in_frames_held * nch, 8, (int32_t*)tin.buf.ptr);
-    if (rc) return rc;
-    const size_t fb = (size_t)4 * nch;
-    const char* in0 = (const char*)tin.buf.ptr - in_first * fb;
-    char* out0 = (char*)tout.buf.ptr - out_first * fb;
-    rc = resample_dev(in0, in_first + in_frames_held, nch, 4, 0, inrate, outrate, out0, out_first, out_first + out_n);
-    if (!rc) rc = sh::pack24((const int32_t*)tout.buf.ptr, out_n * nch, 8, out);
-    return rc;
-}
-
-static int resample_check(int nch, int width, int is_float, int inrate, int outrate) {
-    if (nch < 1) return sh::set_error(SH_ERR_INVALID, "resample: # of channels should be >= 1");
-    if (width != 1 && width != 2 && width != 3 && width != 4) return sh::set_error(SH_ERR_INVALID, "resample: width %d not in {1,2,3,4}", width);
-    if (is_float && width != 4) return sh::set_error(SH_ERR_INVALID, "resample: float PCM must have width 4");
-    if (inrate <= 0 || outrate <= 0) return sh::set_error(SH_ERR_INVALID, "resample: sampling rate not > 0");
-    return SH_OK;
-}
-
-int sh_resample(const sh_buf* in, size_t in_frames, int nchannels, int width, int is_float,
-                int inrate, int outrate, sh_buf* out, size_t* out_frames) {
-    SH_REQUIRE_INIT();
-    if (!in || !out) return sh::set_error(SH_ERR_INVALID, "sh_resample: NULL argument");
-    int rc = resample_check(nchannels, width, is_float, inrate, outrate);
-    if (rc) return rc;
-    size_t nout = sh_resample_out_frames(in_frames, inrate, outrate);
-    if (in->bytes / ((size_t)width * nchannels) < in_frames) return sh::set_error(SH_ERR_INVALID, "sh_resample: input buffer smaller than in_frames");
-    if (out->bytes / ((size_t)width * nchannels) < nout) return sh::set_error(SH_ERR_INVALID, "sh_resample: output buffer too small (%zu frames needed)", nout);
-    if (out_frames) *out_frames = nout;
-    if (width == 3) return nout ? resample24(in->ptr, in_frames, 0, nchannels, inrate, outrate, out->ptr, 0, nout) : (int)SH_OK;
-    return resample_dev(in->ptr, in_frames, nchannels, width, is_float, inrate, outrate, out->ptr, 0, nout);
-}
-
-int sh_resample_span(size_t in_total_frames, int inrate, int outrate, size_t out_first, size_t out_n,
-                     size_t* in_first, size_t* in_count) {
-    if (!in_first || !in_count) return sh::set_error(SH_ERR_INVALID, "sh_resample_span: NULL argument");
-    if (inrate <= 0 || outrate <= 0) return sh::set_error(SH_ERR_INVALID, "resample: sampling rate not > 0");
-    const size_t nout = sh_resample_out_frames(in_total_frames, inrate, outrate);
-    if (out_first > nout || out_n > nout - out_first) return sh::set_error(SH_ERR_INVALID, "sh_resample_span: output range outside the %zu output frames", nout);
-    *in_first = 0;
-    *in_count = 0;
-    if (!out_n) return SH_OK;
-    const uint64_t g = gcd_u64((uint64_t)inrate, (uint64_t)outrate);
-    const unsigned __int128 inr = (uint64_t)inrate / g, outr = (uint64_t)outrate / g;
-    // output frame m interpolates input frames j-1 and j, j = ceil(m*inr/outr)
-    const uint64_t j_lo = (uint64_t)(((unsigned __int128)out_first * inr + outr - 1) / outr);
-    const uint64_t j_hi = (uint64_t)(((unsigned __int128)(out_first + out_n - 1) * inr + outr - 1) / outr);
-    uint64_t first = j_lo ? j_lo - 1 : 0;
-    first &= ~(uint64_t)15;                          // 16 frames of any layout are a multiple of 16 bytes: vector loads stay aligned
-    *in_first = (size_t)first;
-    *in_count = (size_t)(j_hi - first + 1);
-    return SH_OK;
-}
-
-int sh_resample_range(const sh_buf* in, size_t in_first, size_t in_held, int nchannels, int width, int is_float,
-                      int inrate, int outrate, size_t out_first, size_t out_n, sh_buf* out) {
-    SH_REQUIRE_INIT();
-    if (!in || !out) return sh::set_error(SH_ERR_INVALID, "sh_resample_range: NULL argument");
-    int rc = resample_check(nchannels, width, is_float, inrate, outrate);
-    if (rc) return rc;
-    if ((out_first | in_first) & 15) return sh::set_error(SH_ERR_INVALID, "sh_resample_range: ranges must start at a multiple of 16 frames");
-    const size_t fb = (size_t)width * nchannels;
-    if (in->bytes / fb < in_held) return sh::set_error(SH_ERR_INVALID, "sh_resample_range: input buffer smaller than in_held frames");
-    if (out->bytes / fb < out_n) return sh::set_error(SH_ERR_INVALID, "sh_resample_range: output buffer too small (%zu frames needed)", out_n);
-    if (!out_n) return SH_OK;
-    // the input frames the range reads (exact rational index arithmetic, as in sh_resample_span)
-    const uint64_t g = gcd_u64((uint64_t)inrate, (uint64_t)outrate);
-    const unsigned __int128 inr = (uint64_t)inrate / g, outr = (uint64_t)outrate / g;
-    const uint64_t j_lo = (uint64_t)(((unsigned __int128)out_first * inr + outr - 1) / outr);
-    const uint64_t j_hi = (uint64_t)(((unsigned __int128)(out_first + out_n - 1) * inr + outr - 1) / outr);
-    const uint64_t need_lo = j_lo ? j_lo - 1 : 0;
-    if (in_first > need_lo || j_hi >= (uint64_t)in_first + in_held)
-        return sh::set_error(SH_ERR_INVALID, "sh_resample_range: output frames [%zu,+%zu) read input frames [%llu,%llu], buffer holds [%zu,+%zu)",
-                             out_first, out_n, (unsigned long long)need_lo, (unsigned long long)j_hi, in_first, in_held);
-    if (width == 3) return resample24(in->ptr, in_held, in_first, nchannels, inrate, outrate, out->ptr, out_first, out_n);
-    const char* in0 = (const char*)in->ptr - in_first * fb;        // where input frame 0 would be
-    char* out0 = (char*)out->ptr - out_first * fb;                  // where output frame 0 would be
-    return resample_dev(in0, in_first + in_held, nchannels, width, is_float, inrate, outrate, out0, out_first, out_first + out_n, in_first);
-}
-
-int sh_resample_host(const void* in, size_t in_frames, int nchannels, int width, int is_float,
-                     int inrate, int outrate, void* out, size_t* out_frames) {
-    SH_REQUIRE_INIT();
-    int rc = resample_check(nchannels, width, is_float, inrate, outrate);
-    if (rc) return rc;
-    size_t nout = sh_resample_out_frames(in_frames, inrate, outrate);
-    if (out_frames) *out_frames = nout;
-    if (!nout) return SH_OK;
-    if (!in || !out) return sh::set_error(SH_ERR_INVALID, "sh_resample_host: NULL argument");
-    size_t fb = (size_t)width * nchannels;
-    size_t in_bytes = in_frames * fb, out_bytes = nout * fb;
-    size_t in_pad = (in_bytes + 255) & ~size_t(255);
-    rc = sh::ensure_scratch(in_pad + out_bytes);
-    if (rc) return rc;
-    char* s = (char*)sh::state().scratch;
-    hipStream_t st = sh::state().stream;
-    SH_HIP(hipMemcpyAsync(s, in, in_bytes, hipMemcpyHostToDevice, st));
-    rc = width == 3 ? resample24(s, in_frames, 0, nchannels, inrate, outrate, s + in_pad, 0, nout)
-                    : resample_dev(s, in_frames, nchannels, width, is_float, inrate, outrate, s + in_pad, 0, nout);
-    if (rc) return rc;
-    SH_HIP(hipMemcpyAsync(out, s + in_pad, out_bytes, hipMemcpyDeviceToHost, st));
-    SH_HIP(hipStreamSynchronize(st));
-    return SH_OK;
 }
 
 }  // extern "C"
