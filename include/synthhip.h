@@ -283,6 +283,8 @@ int sh_osc_render(sh_bank* bank, uint32_t voice,
 
 /* ---- filters over rendered oscillator blocks: MixingFilter (a+b),
  *      AmpModulationFilter (a*b), ClipFilter (max(min(a, p1), p0)), AbsFilter (|a|), copy / constant fill.
+ *      CLIP follows Python's min and max, which keep their FIRST argument on a tie and when a NaN makes the comparison false:
+ *      t = p1 < a ? p1 : a, then p0 > t ? p0 : t -- clip(-0.0, 0.0, 1.0) is -0.0 and a NaN sample stays NaN.
  *      a, b, out_f64: float64 device buffers; out_f32 (+ element offset) / out_host: optional float32 copies */
 typedef enum sh_ew_op { SH_EW_ADD = 0, SH_EW_MUL = 1, SH_EW_CLIP = 2, SH_EW_ABS = 3, SH_EW_COPY = 4, SH_EW_FILL = 5,
                         SH_EW_AXPY = 6 /* a + b*p0 (product rounded first): EchoFilter */,
@@ -292,7 +294,10 @@ int sh_ew_f64(int op, const sh_buf* a, size_t a_off, const sh_buf* b, size_t b_o
 
 /* exclusive running sum of n float64 values on the device (FM with an arbitrary fm_lfo):
  * out[i] = carry_in + x[0] + .. + x[i-1], i = 0..n-1 (n values).
- * carry_out (host, may be NULL) receives carry_in + x[0] + .. + x[n-1]. */
+ * carry_out (host, may be NULL) receives carry_in + x[0] + .. + x[n-1].
+ * Error bound (sh_scan_rows_f64 alike): |out[i] - exact| <= K 2^-53 (|carry_in| + |x[0]| + .. + |x[i-1]|), K = 31 + ceil(ceil(n / 2048) / 256),
+ * the rounded additions on the longest path from an input to an output; out[i] holds no part of x[i] or of anything behind it.
+ * carry_out: the same with K = 23 + ceil(ceil(n / 2048) / 256) over all n values. */
 int sh_scan_f64(const sh_buf* x, uint32_t n, double carry_in, sh_buf* out, double* carry_out);
 
 /* ---- voice bank rendering: N voices -> stereo bus (the "Mixer sum bus" over oscillator voices) */

@@ -90,15 +90,20 @@ def render(osc, n: int) -> np.ndarray:
                        C.c_double(pw), _dp(hk), _dp(ha), nh, C.c_size_t(n), _dp(out))
     else:
         lfo = osc.fm
-        assert type(lfo) is O.Sine and lfo.fm is None and getattr(osc, "pwm", None) is None
+        assert lfo.fm is None and getattr(lfo, "pwm", None) is None and getattr(osc, "pwm", None) is None
         if radians:
             phase0, inc = osc._phase * 2.0 * pi, 2.0 * pi / sr
         else:
             phase0, inc = osc._phase, 1.0 / sr
-        L.or_osc_fm_sine(kind, C.c_double(osc.frequency), C.c_double(phase0), C.c_double(inc), C.c_double(osc.amplitude),
-                         C.c_double(osc.bias), C.c_double(pw), _dp(hk), _dp(ha), nh,
-                         C.c_double(lfo._phase * 2.0 * pi), C.c_double(O._increment(lfo.frequency, lfo.samplerate, True)),
-                         C.c_double(lfo.amplitude), C.c_double(lfo.bias), C.c_size_t(n), _dp(out))
+        if type(lfo) is not O.Sine:                 # any other plain LFO: its samples first, then the same loop over them
+            fm = render(lfo, n)
+            L.or_osc_fm_buffer(kind, C.c_double(osc.frequency), C.c_double(phase0), C.c_double(inc), C.c_double(osc.amplitude),
+                               C.c_double(osc.bias), C.c_double(pw), _dp(hk), _dp(ha), nh, _dp(fm), C.c_size_t(n), _dp(out))
+        else:
+            L.or_osc_fm_sine(kind, C.c_double(osc.frequency), C.c_double(phase0), C.c_double(inc), C.c_double(osc.amplitude),
+                             C.c_double(osc.bias), C.c_double(pw), _dp(hk), _dp(ha), nh,
+                             C.c_double(lfo._phase * 2.0 * pi), C.c_double(O._increment(lfo.frequency, lfo.samplerate, True)),
+                             C.c_double(lfo.amplitude), C.c_double(lfo.bias), C.c_size_t(n), _dp(out))
     if env is not None:
         L.or_envelope(C.c_double(env._attack), C.c_double(env._decay), C.c_double(env._sustain),
                       C.c_double(env._sustain_level), C.c_double(env._release), int(env.samplerate), C.c_size_t(n), _dp(out))

@@ -79,6 +79,19 @@ void or_osc_fm_sine(int kind, double frequency, double phase0, double inc, doubl
     }
 }
 
+/* FM branch with any LFO whose samples are given (fm[i]: a plain oscillator rendered by or_osc_plain) */
+void or_osc_fm_buffer(int kind, double frequency, double phase0, double inc, double amp, double bias, double pw,
+                      const double* hk, const double* ha, int nh, const double* fm, size_t n, double* out) {
+    double phase_correction = phase0, freq_previous = frequency, t = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+        double freq = frequency * (1.0 + fm[i]);
+        phase_correction += (freq_previous - freq) * t;
+        freq_previous = freq;
+        out[i] = wave(kind, t * freq + phase_correction, amp, bias, pw, hk, ha, nh);
+        t += inc;
+    }
+}
+
 /* Linear: the level is emitted, then incremented while it lies strictly between min and max (synth_oracle.Linear) */
 void or_linear(double start, double increment, double minv, double maxv, size_t n, double* out) {
     double value = start;

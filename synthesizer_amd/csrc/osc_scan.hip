@@ -13,7 +13,8 @@ __global__ __launch_bounds__(256) void k_ew_f64(int op, const double* a, const d
     switch (op) {
     case SH_EW_ADD: v = a[i] + b[i]; break;
     case SH_EW_MUL: v = a[i] * b[i]; break;
-    case SH_EW_CLIP: { double t = a[i] < p1 ? a[i] : p1; v = t > p0 ? t : p0; } break;    // max(min(v, maximum), minimum)
+    // Python's max(min(v, maximum), minimum): on a tie (-0.0 against 0.0) and on a NaN the FIRST argument stays
+    case SH_EW_CLIP: { double t = p1 < a[i] ? p1 : a[i]; v = p0 > t ? p0 : t; } break;
     case SH_EW_ABS: v = fabs(a[i]); break;
     case SH_EW_COPY: v = a[i]; break;
     case SH_EW_AXPY: { const double e = b[i] * p0; v = a[i] + e; } break;
@@ -28,7 +29,8 @@ __global__ __launch_bounds__(256) void k_ew_f64(int op, const double* a, const d
 constexpr int SCAN_TILE = 2048;   // values per block (256 threads x 8)
 
 __device__ __forceinline__ double block_exclusive_scan_256(double x, double* sh, double& total) {
-    // sh: 256 doubles.  Hillis-Steele; plenty fast for the few MB a modulator block has.
+    // sh: 256 doubles.  Hillis-Steele; plenty fast for the few MB a modulator block has.  The exclusive value is the left neighbour's
+    // inclusive sum, which holds no part of x: `inclusive - x` would round the prefix at ulp(prefix + x) and break the bound over j < i.
     const int t = threadIdx.x;
     sh[t] = x;
     __syncthreads();
@@ -39,9 +41,9 @@ __device__ __forceinline__ double block_exclusive_scan_256(double x, double* sh,
         __syncthreads();
     }
     total = sh[255];
-    double incl = sh[t];
+    const double excl = t ? sh[t - 1] : 0.0;
     __syncthreads();
-    return incl - x;
+    return excl;
 }
 
 __global__ __launch_bounds__(256) void k_scan_tile_sums(const double* __restrict__ x, uint32_t n, double* __restrict__ sums) {

@@ -193,3 +193,143 @@ def range_rule_maps(rows, n):
     out["lo"] = lo
     out["hi"] = hi
     return out
+
+
+# ---- the float64 scans (sh_scan_f64, sh_scan_rows_f64) against exact integers ---------------------------------------------
+# Inputs live on a fixed-point grid: x_j = k_j * 2^-SCAN_GRID_BITS with integer k_j and sum |k_j| (carry included) < 2^62.  The
+# exact prefix is then an int64, every float64 any order of additions can produce is a multiple of the grid step, and
+# np.ldexp(got, SCAN_GRID_BITS) is that multiple without rounding: the error of every output is known exactly, in integers.
+SCAN_GRID_BITS = 40
+SCAN_TILE = 2048            # csrc/osc_scan.hip: values per workgroup (256 threads x 8)
+SCAN_SUMS_ROUND = 256       # tile totals scanned per round of k_scan_sums / k_scan_rows_sums
+
+
+def scan_grid(k):
+    """Integers k -> the float64 values k * 2^-40 (asserted exact: every k must be a float64 itself)."""
+    k = np.asarray(k, dtype=np.int64)
+    f = k.astype(np.float64)
+    assert np.all(np.abs(f) < 2.0 ** 62) and np.array_equal(f.astype(np.int64), k), "a grid integer that is not a float64"
+    return np.ldexp(f, -SCAN_GRID_BITS)
+
+
+def scan_to_grid(values):
+    """float64 values -> their grid integers (int64), asserting that each is finite, on the grid and inside int64."""
+    v = np.asarray(values, dtype=np.float64)
+    g = np.ldexp(v, SCAN_GRID_BITS)
+    assert np.all(np.isfinite(g)) and np.all(np.abs(g) < 2.0 ** 63), "not finite, or far outside the grid's range"
+    assert np.all(g == np.rint(g)), "a value that no sum of grid values can be"
+    return g.astype(np.int64)
+
+
+def scan_exact(k, carry_k=0):
+    """Exact exclusive prefix in grid integers: (prefix[i] = carry + sum_{j<i} k_j, total, A[i] = |carry| + sum_{j<i} |k_j|, A_total).
+    Asserts that sum |k| stays below 2^62, so that int64 holds every partial sum."""
+    k = np.asarray(k, dtype=np.int64)
+    carry_k = int(carry_k)
+    mag = np.abs(k)
+    # (a float64 estimate of the sum, good to 1e-12, against a limit 1e-3 below 2^62: the int64 sums that follow cannot wrap)
+    assert abs(carry_k) + float(np.sum(mag.astype(np.float64))) < 0.999 * 2.0 ** 62, "sum |k| reaches 2^62"
+    incl = np.cumsum(k, dtype=np.int64)
+    incl_a = np.cumsum(mag, dtype=np.int64)
+    prefix = np.empty(k.size, dtype=np.int64)
+    a = np.empty(k.size, dtype=np.int64)
+    if k.size:
+        prefix[0], a[0] = carry_k, abs(carry_k)
+        prefix[1:] = incl[:-1] + carry_k
+        a[1:] = incl_a[:-1] + abs(carry_k)
+    total = carry_k + (int(incl[-1]) if k.size else 0)
+    return prefix, total, a, abs(carry_k) + (int(incl_a[-1]) if k.size else 0)
+
+
+def scan_error(got, prefix):
+    """|got_i - exact_i| in grid steps, exactly (int64)."""
+    return np.abs(scan_to_grid(got) - np.asarray(prefix, dtype=np.int64))
+
+
+def scan_allowed(a, depth):
+    """floor(depth * 2^-53 * A_i) in grid steps, exactly, for A_i < 2^62 and depth < 1024 (int64 throughout): the first-order bound of
+    a sum whose every path from an input to the output holds at most `depth` rounded additions, |got - exact| <= depth u A with
+    u = 2^-53.  (The second-order term depth^2 u^2 A is below 2^-30 of a grid step here, and the errors are whole grid steps.)"""
+    a = np.asarray(a, dtype=np.int64)
+    assert 0 < depth < 1024
+    return depth * (a >> 53) + ((depth * (a & ((1 << 53) - 1))) >> 53)
+
+
+def scan_rounds(n):
+    """Rounds of the tile-sum loop for n values: ceil(ntiles / 256)."""
+    ntiles = -(-int(n) // SCAN_TILE)
+    return max(1, -(-ntiles // SCAN_SUMS_ROUND))
+
+
+def scan_depth(n):
+    """K of one call over n values: rounded additions on the longest path from an input to an output, counted from csrc/osc_scan.hip.
+      7   the 8 values of a thread, summed in order (the first add, to 0.0, is exact)
+      8   Hillis-Steele levels over the 256 thread sums: the tile's total
+      8   Hillis-Steele levels over the round's tile totals: the round's total
+      R-1 `carry = c + total` once per round, from the input's round to the one before the output's (R = scan_rounds(n))
+      1   sums[i] = c + ex: the tile's base
+      1   the thread's exclusive value + the tile's base (k_scan_apply)
+      7   the running adds over the thread's own 8 values
+    = 31 + R.  Shorter paths: a tile of the output's own round 32, the output's own tile 23, carry_in R + 8."""
+    return 31 + scan_rounds(n)
+
+
+def scan_carry_depth(n):
+    """The same count for carry_out of one call: 7 + 8 + 8, then at most R carry adds: 23 + R (carry_in itself: R)."""
+    return 23 + scan_rounds(n)
+
+
+def scan_chain_depth(piece_lengths):
+    """K for the outputs of the LAST of several calls chained by their carries (each carry_out fed to the next call as carry_in): an
+    input of piece q reaches piece q's carry_out in scan_carry_depth(n_q) additions, passes every piece between in scan_rounds(n_m)
+    more, and reaches an output of the last piece through its carry path, scan_rounds(n_p) + 8; an input of the last piece itself
+    has scan_depth(n_p).  The longest of these."""
+    lens = [int(x) for x in piece_lengths if int(x) > 0]
+    if not lens:
+        return 1
+    last = lens[-1]
+    best = scan_depth(last)
+    through = 0
+    for n_q in reversed(lens[:-1]):
+        best = max(best, scan_carry_depth(n_q) + through + scan_rounds(last) + 8)
+        through += scan_rounds(n_q)
+    return best
+
+
+SCAN_INPUT_KINDS = ("uniform", "modulator", "small_on_large_carry", "log_uniform")
+
+
+def scan_inputs(kind, n, rng):
+    """-> (k, carry_k): grid integers of one of the rounded-class inputs, n values, sum |k| + |carry| < 2^62."""
+    one = 1 << SCAN_GRID_BITS
+    if kind == "uniform":                       # uniform in (-1, 1)
+        return rng.integers(-one + 1, one, n, dtype=np.int64), int(rng.integers(-one, one))
+    if kind == "modulator":                     # all positive: 0.3 + 0.2 sin, 5 Hz at 48 kHz
+        t = np.arange(n, dtype=np.float64)
+        return np.rint((0.3 + 0.2 * np.sin(2.0 * math.pi * 5.0 / 48000.0 * t + 0.7)) * one).astype(np.int64), int(0.25 * one)
+    if kind == "small_on_large_carry":          # values around 1e-6 on a carry of about 1e6
+        return rng.integers(-2 * int(1e-6 * one), 2 * int(1e-6 * one) + 1, n, dtype=np.int64), (int(1.0e6 * one) >> 8 << 8) + 12345 * 256       # (a float64: ulp 2^8 grid steps up there)
+    if kind == "log_uniform":                   # magnitudes log-uniform over the grid's whole range, random signs
+        # the mean of such a draw is 2^top / (top ln 2): top = 65 - log2 n keeps the sum near 2^60 (scan_exact checks it); the carry
+        # is below 2^60.  Partial sums beyond 2^53 grid steps are where additions round: from a few thousand values on this input
+        # is exact, and the bound asks for equality by itself.
+        top = min(59.0, 65.0 - math.log2(max(n, 1)))
+        mag = np.floor(np.exp2(rng.uniform(0.0, top, n))).astype(np.int64)      # (float64 first: every magnitude is a float64)
+        return mag * rng.choice(np.array([-1, 1], dtype=np.int64), n), -int(np.floor(2.0 ** rng.uniform(0.0, 60.0)))
+    raise ValueError(kind)
+
+
+def scan_adversarial(n, tile, thread, pos, big_log2, rng, negative=False):
+    """A run of small values (|k| < 2^20) with ONE value of 2^big_log2 grid steps (big_log2 >= 53: beyond the 53 bits of the prefix in
+    front of it) at position `pos` of the 8-value group of thread `thread` in tile `tile`.  Every output in front of the large value
+    has a prefix of small values only, and the bound over j < i gives it no room for the large one.  The values of the tile in front
+    of that group sum to an odd number of grid steps, so a sum that rounds them against the large value cannot come out exact by luck."""
+    assert 53 <= big_log2 <= 60 and 0 <= pos < 8 and 0 < thread < 256
+    k = rng.integers(1, 1 << 20, n, dtype=np.int64) * rng.choice(np.array([-1, 1, 1], dtype=np.int64), n)
+    at = tile * SCAN_TILE + thread * 8 + pos
+    assert at < n
+    k[at] = -(1 << big_log2) if negative else 1 << big_log2
+    group = at - pos
+    if int(k[tile * SCAN_TILE:group].sum()) % 2 == 0:
+        k[group - 1] += 1
+    return k, int(rng.integers(1, 1 << 20)), at

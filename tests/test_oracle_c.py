@@ -28,6 +28,9 @@ SR = 48000
     lambda: O.Triangle(441.0, 0.6, phase=-0.4, bias=0.05, samplerate=SR),
     lambda: O.Triangle(-250.0, 0.5, phase=0.3, samplerate=SR),
     lambda: O.Triangle(300.0, fm_lfo=O.Sine(2.0, 0.05, samplerate=SR), samplerate=SR),
+    lambda: O.Sine(440.0, 0.9, phase=0.13, fm_lfo=O.Triangle(5.0, 0.5, phase=0.31, bias=0.02, samplerate=SR), samplerate=SR),
+    lambda: O.Sine(3520.0, 0.9, phase=0.13, fm_lfo=O.Sawtooth(5.0, 0.05, phase=0.31, bias=0.02, samplerate=SR), samplerate=SR),
+    lambda: O.Sawtooth(300.0, fm_lfo=O.Square(2.0, 0.05, samplerate=SR), samplerate=SR),
     lambda: O.Linear(-0.5, 0.00013, samplerate=SR),
     lambda: O.Linear(0.9, 0.001, min_value=-2.0, max_value=1.0, samplerate=SR),
     lambda: O.Linear(0.2, -0.0007, samplerate=SR),
