@@ -211,39 +211,6 @@ int acquire_records(sh_bank* b, uint64_t start, uint32_t nframes, hipStream_t la
     return SH_OK;
 }
 
-// The cuts of a transition launch / of the head of a materialised row (see RENDER_LEAN_HARM_SEG): with `corners`, the envelope
-// corners the voices share (sloped records: a line of any slope is lean, a corner is not) -- without, or when the voices have
-// envelopes of their own, the frame from which all of them are flat and the first sustain end -- and, between those, doubling
-// positions (at most one piece end of the phase sum per voice in [pos, 2 pos)); no segment longer than max_len.
-// seg_first[0 .. n] = launch-relative segment starts; returns n; the segments cover seg_first[n] <= nframes frames (fewer than
-// nframes only when SEG_MAX segments do not reach the end).
-uint32_t plan_segments(const sh_bank* b, uint64_t start, uint32_t nframes, uint64_t T, uint64_t max_len, bool corners,
-                              uint32_t* seg_first) {
-    const uint64_t end = start + nframes;
-    uint64_t cuts[SEG_MAX + 2];
-    uint32_t nc = 0;
-    uint64_t pos = start;
-    cuts[nc++] = pos;
-    const uint64_t flat = b->env_flat_from, rel = b->env_flat_until;       // last decay end, first sustain end
-    const bool shared = corners && !b->env_corners.empty();
-    if (!shared && pos < flat && flat < end && flat - pos <= max_len) { pos = flat; cuts[nc++] = pos; }
-    while (pos < end && nc <= SEG_MAX) {
-        uint64_t next = pos < T ? T : 2 * pos;
-        if (shared) {
-            for (uint64_t c : b->env_corners)
-                if (c > pos && c < next) { next = c; break; }
-        } else if (pos < rel && rel < next) {
-            next = rel;
-        }
-        if (next - pos > max_len) next = pos + max_len;
-        if (next >= end || (end - next <= next / 64 && !shared && end - pos <= max_len)) next = end;   // (a very short rest joins the last segment)
-        pos = next;
-        cuts[nc++] = pos;
-    }
-    for (uint32_t k = 0; k < nc; ++k) seg_first[k] = (uint32_t)(cuts[k] - start);
-    return nc - 1;
-}
-
 int grow_segment_sets(sh::Pooled& block, LaunchSet& g, uint32_t& cap, uint32_t nseg, uint32_t nvoices) {
     if (cap >= nseg && block.ptr) return SH_OK;
 #ifdef SH_GUARD_SETS

@@ -21,14 +21,12 @@
 #pragma once
 #include "common.hpp"
 #include "devmath.hpp"
+#include "genplan.hpp"
 #include <type_traits>
 
 namespace shosc {
 
-constexpr int SEG_MAX = 24;            // segments of a transition launch
-// Unequal segments of a materialised row's head (n = 0: none): entry k holds the frames [first[k], first[k] + len[k]) and reads
-// record set set[k] (the lists launch skips the segments the host can prove free of general voices)
-struct SegTab { uint32_t n; uint32_t first[SEG_MAX]; uint32_t len[SEG_MAX]; uint32_t set[SEG_MAX]; };
+// (SEG_MAX and SegTab -- the unequal segments of a materialised row's head -- live in genplan.hpp, beside the plan that fills them)
 
 // A TILE-CLASSIFIED launch (banks whose notes do not move in lock-step: onsets and envelope corners of their own).  Whether a
 // voice can take the lean loop is decided per (voice, tile of TILE_FRAMES frames), not per launch.  A pair is LEAN when the voice
@@ -715,7 +713,7 @@ __device__ __forceinline__ void prepare_chunk(const BankPtrs& B, const LaunchSet
 // past the end of the set: into the next segment's first chunk, or, from the last segment, past the array -- found in round 3
 // when the arrays of a segmented launch became neighbours in one block.)
 __host__ __device__ __forceinline__ size_t set_slots(uint32_t nvoices) { return (size_t)((nvoices + 63) / 64) * 64; }
-__device__ __forceinline__ LaunchSet segment_set(const LaunchSet& base, uint32_t s, uint32_t nvoices) {
+__host__ __device__ __forceinline__ LaunchSet segment_set(const LaunchSet& base, uint32_t s, uint32_t nvoices) {
     const uint32_t nchunks = (nvoices + 63) / 64;
     const size_t stride = set_slots(nvoices);
     LaunchSet r;

@@ -40,8 +40,8 @@ __global__ __launch_bounds__(256, FPL >= 4 ? 4 : 6) void k_generate(BankPtrs B, 
                                                   const double* __restrict__ fm_cumsum,
                                                   const double* __restrict__ pwm,
                                                   float* __restrict__ out32, double* __restrict__ out64,
-                                                  size_t stride, short* __restrict__ out16 = nullptr, double scale16 = 0.0,
-                                                  int* __restrict__ flag = nullptr) {
+                                                  size_t stride, short* __restrict__ out16, double scale16,
+                                                  int* __restrict__ flag) {
     __shared__ shm::sc_pair trig[shm::TRIG_N];
     for (uint32_t k = threadIdx.x; k < shm::TRIG_N; k += 256) trig[k] = trig_g[k];
     __syncthreads();
@@ -105,12 +105,12 @@ __global__ __launch_bounds__(256, FPL >= 4 ? 4 : 6) void k_generate(BankPtrs B, 
 // stored instead of accumulated), then the general list through voice_block, then zero-fills the rows of silent voices.
 // The lean arithmetic repeats the general code's order -- ((x * amplitude) + 0) * g0u.
 // LEAN = false: only the general and the silent list (the lean records went through k_generate_lean_harm).
-template <int FPL, bool LEAN, typename OutT = float>
+template <int FPL, bool LEAN, typename OutT>
 __global__ __launch_bounds__(256, FPL >= 4 ? 4 : 6) void k_generate_lists(BankPtrs B, const shm::sc_pair* __restrict__ trig_g,
                                                                          uint32_t nvoices, LaunchSet cur, uint64_t start, uint32_t n,
                                                                          OutT* __restrict__ out32, size_t stride,
-                                                                         SegTab tab = SegTab{0, {}, {}, {}}, uint32_t vsplit = 1,
-                                                                         double scale = 0.0, int* __restrict__ flag = nullptr) {
+                                                                         SegTab tab, uint32_t vsplit,
+                                                                         double scale, int* __restrict__ flag) {
     bool bad = false;                          // (int16 rows: a sample that does not fit)
     // tab.n != 0: the unequal segments of a row's head in ONE launch -- grid.x runs over the groups of four tiles of all segments,
     // a workgroup finds its segment and from there on works relative to it (records, frames, output).  vsplit > 1: grid.y =
@@ -339,12 +339,12 @@ __global__ __launch_bounds__(256, FPL >= 4 ? 4 : 6) void k_generate_lists(BankPt
 #ifndef SH_GEN_MINW
 #define SH_GEN_MINW 4              // wavefronts per SIMD the compiler budgets registers for (tools/ab.py build NAME -DSH_GEN_MINW=3: the A/B of round 6)
 #endif
-template <int FPL, typename OutT = float, bool FOLD = false, bool GUARD = true>
+template <int FPL, typename OutT, bool FOLD, bool GUARD>
 __global__ __launch_bounds__(256, (FOLD || (RowOut<OutT>::I16 && FPL == 16)) ? 3 : SH_GEN_MINW) void k_generate_lean_harm(const shm::sc_pair* __restrict__ trig_g, LaunchSet base, uint32_t nvoices,
                                                                uint32_t total, uint32_t seg_frames,
                                                                OutT* __restrict__ out32_all, size_t stride, SegTab tab, uint32_t rec_split,
-                                                               double scale = 0.0, int* __restrict__ flag = nullptr,
-                                                               int2v* __restrict__ parts = nullptr, size_t plane = 0) {
+                                                               double scale, int* __restrict__ flag,
+                                                               int2v* __restrict__ parts, size_t plane) {
     constexpr bool I16 = RowOut<OutT>::I16;
     static_assert(!FOLD || I16, "the fold is over int16 samples");
     __shared__ shm::sc_pair trig[shm::TRIG_N];
@@ -506,9 +506,6 @@ __global__ __launch_bounds__(256, (FOLD || (RowOut<OutT>::I16 && FPL == 16)) ? 3
             //  short of it -- low word 0xFFFFFFFF, missed.  One step up, it lands on or above the integer; near_lo's + 3 covers the
             //  upper edge moved by the same step)
             tqm = (tq + 0x1p-32) + 0x1.8p20;
-#ifdef SH_AB_COUNT
-            (void)0;
-#endif
 #pragma unroll
             for (int h = 0; h < NQ; ++h) { qmx[h] = 0; qmn[h] = 0; nearv[h] = 0xFFFFFFFFu; }
         }
@@ -749,7 +746,7 @@ int sh_osc_render(sh_bank* bank, uint32_t voice, const sh_buf* fm_cumsum, const 
                        ptrs(bank), trig_table(), voice, 1u, 1u, bank->d_launch, bank->d_launch_fm, start, n,
                        fm_cumsum ? (const double*)fm_cumsum->ptr : nullptr,
                        pwm ? (const double*)pwm->ptr : nullptr,
-                       d32, out_f64 ? (double*)out_f64->ptr : nullptr, (size_t)0);
+                       d32, out_f64 ? (double*)out_f64->ptr : nullptr, (size_t)0, (short*)nullptr, 0.0, (int*)nullptr);
     SH_CHECK_LAUNCH("k_generate");
     if (out_host) {
         SH_HIP(hipMemcpyAsync(out_host, d32, (size_t)n * 4, hipMemcpyDeviceToHost, sh::state().stream));
@@ -762,151 +759,214 @@ int sh_osc_render(sh_bank* bank, uint32_t voice, const sh_buf* fm_cumsum, const 
 
 namespace {
 
-// every voice of the bank as a row of OutT (float: the sample rounded to float32; short: int(scale * sample), *flag set where one does not fit)
+// ---- the executor: a call is planned (genplan.hpp), then its steps are walked ----------------------------------------------------------
+// The ONE place where the plan's run-time numbers become template arguments: every instantiation of the three kernels is named here.
+auto generate_kernel(int fpl) { return fpl == 4 ? &k_generate<4> : (fpl == 2 ? &k_generate<2> : &k_generate<1>); }
+template <typename OutT> auto lists_kernel(bool lean) { return lean ? &k_generate_lists<4, true, OutT> : &k_generate_lists<4, false, OutT>; }
+template <typename OutT, bool FOLD, bool GUARD> auto lean_kernel_of(int lf) {
+    return lf == 16 ? &k_generate_lean_harm<16, OutT, FOLD, GUARD> : (lf == 8 ? &k_generate_lean_harm<8, OutT, FOLD, GUARD> : &k_generate_lean_harm<4, OutT, FOLD, GUARD>);
+}
+template <typename OutT, bool FOLD> auto lean_kernel(int lf, bool guard) {       // (float rows have no boundary to guard: GUARD = true alone)
+    if constexpr (RowOut<OutT>::I16) { if (!guard) return lean_kernel_of<OutT, FOLD, false>(lf); }
+    return lean_kernel_of<OutT, FOLD, true>(lf);
+}
+
+// where a stretch of steps writes: rows (of the call, or a two-step stretch's temporary), a fused stretch's planes, the mixdown's result
+struct Dest { void* rows; size_t stride; double scale; int* flag; int2v* planes; short* mono; int2v* maps; };
+
+// one step: its record sets, then (a fused stretch: `planes`, allocated here, behind the records as ever) its launches.
+// `start`: the step's first frame; d.rows, d.mono and d.maps point at it.
 template <typename OutT>
-int generate_rows(sh_bank* b, uint64_t start, uint32_t nframes, OutT* o, size_t stride, double scale, int* flag) {
+int run_step(sh_bank* b, uint64_t start, const shg::Step& s, Dest d, sh::Temp* planes) {
+    constexpr bool F64 = std::is_same<OutT, double>::value, I16 = std::is_same<OutT, short>::value;
+    hipStream_t st = sh::state().stream;
+    const uint32_t nv = b->nvoices;
+    OutT* const o = (OutT*)d.rows;
+    LaunchSet base;
     int rc;
-    // frames per lane: 4 for long rows (one sin/cos lookup + three rotations per voice, as in k_bank_render), else 2 / 1
-    const int fpl = nframes >= 8192 ? 4 : (nframes >= 2048 ? 2 : 1);
-    const bool with_rows = b->launch_rows != nullptr;             // sh_bank_generate_rows: every voice through the general kernel, which reads the rows
-    if (!with_rows && fpl == 4 && b->lean_candidates != 0 && b->lean_fm_candidates == 0) {
-        // Long rows, every lean candidate a polynomial Harmonics voice: the lean records by the recurrence kernel at sixteen frames
-        // per lane, then the general and silent lists -- unless the segment provably has none.  Rows longer than a segment get
-        // one record set per segment, all resolved by ONE prepare launch.
-        // frames per lane of the lean kernel: sixteen on long rows (1024 x 480 000: 496 us, eight: 508), fewer when that leaves
-        // the chip short of workgroups (1024 x 48 000 at sixteen: 12 x 16 = 192 workgroups of four 1024-frame tiles)
-        int lf = 16;
-        while (lf > 4 && (uint64_t)sh::div_up(nframes, 256 * lf) * sh::div_up(b->nvoices, 64) < 512) lf /= 2;
-        const int LF = lf;
-        // workgroups per chunk of records: enough waves for several rounds of the chip's wave slots (1, 4, 8 measured: CHANGELOG item 38)
-        const uint32_t rsplit = 2;
-        // (the int16 kernels in two forms: with the boundary guard's check, and -- a bank none of whose voices carries a guard list -- without)
-        constexpr bool I16_ = RowOut<OutT>::I16;
-        const bool guard = !I16_ || b->has_guard;
-#define SH_GEN_LEAN(GRID_, ...) do { \
-            if (!I16_ || guard) { \
-                if (LF == 16) hipLaunchKernelGGL((k_generate_lean_harm<16, OutT>), GRID_, dim3(256), 0, st, __VA_ARGS__, scale, flag); \
-                else if (LF == 8) hipLaunchKernelGGL((k_generate_lean_harm<8, OutT>), GRID_, dim3(256), 0, st, __VA_ARGS__, scale, flag); \
-                else hipLaunchKernelGGL((k_generate_lean_harm<4, OutT>), GRID_, dim3(256), 0, st, __VA_ARGS__, scale, flag); \
-            } else { \
-                if (LF == 16) hipLaunchKernelGGL((k_generate_lean_harm<16, OutT, false, !I16_>), GRID_, dim3(256), 0, st, __VA_ARGS__, scale, flag); \
-                else if (LF == 8) hipLaunchKernelGGL((k_generate_lean_harm<8, OutT, false, !I16_>), GRID_, dim3(256), 0, st, __VA_ARGS__, scale, flag); \
-                else hipLaunchKernelGGL((k_generate_lean_harm<4, OutT, false, !I16_>), GRID_, dim3(256), 0, st, __VA_ARGS__, scale, flag); \
-            } } while (0)
-        constexpr uint32_t SEG = 65536;                      // frames per segment (a multiple of the 1024-frame tile)
-        hipStream_t st = sh::state().stream;
-        const uint32_t nchunks = sh::div_up(b->nvoices, 64);
-        // Rows that start with the notes (attack, decay, a dozen binades of the phase sum in the first 65 536 frames): the head
-        // is cut like a transition launch of the render path (plan_segments: where the envelopes are flat, then doubling
-        // positions) so that its voices stay lean -- one prepare launch, one lean launch, ONE lists launch over all segments with
-        // the general voices of a chunk dealt to eight workgroups; the rest of the row follows with equal segments.
-        const bool no_seg = sh::knobs().no_seg;
-        if (start < SEG && b->all_lean && !no_seg && !b->no_general_voice(start, nframes < SEG ? nframes : SEG)) {
-            uint32_t cut[SEG_MAX + 1];
-            SegTab tab, ltab;
-            tab.n = plan_segments(b, start, nframes, 64 * LF, SEG, false, cut);
-            if (tab.n >= 2) {
-                const uint32_t head = cut[tab.n];                        // frames the segments cover (all of them, or what SEG_MAX cuts reach)
-                ltab.n = 0;
-                for (uint32_t k = 0; k < tab.n; ++k) {
-                    tab.first[k] = cut[k]; tab.len[k] = cut[k + 1] - cut[k]; tab.set[k] = k;
-                    if (!b->no_general_voice(start + cut[k], cut[k + 1] - cut[k])) {     // (the lists launch: where general or silent voices can be)
-                        ltab.first[ltab.n] = cut[k]; ltab.len[ltab.n] = cut[k + 1] - cut[k]; ltab.set[ltab.n] = k;
-                        ++ltab.n;
-                    }
-                }
-                rc = grow_segment_sets(b->gen_block, b->gen_set, b->gen_segs, tab.n, b->nvoices);
-                if (rc) return rc;
-                const LaunchSet base = b->gen_set;
-                BankPtrs P = ptrs(b);
-                P.nseg = tab.n;
-                uint32_t tiles = 0, list_groups = 0;
-                for (uint32_t k = 0; k <= tab.n; ++k) P.seg_first[k] = cut[k];
-                for (uint32_t k = 0; k < tab.n; ++k) tiles += sh::div_up(tab.len[k], 64 * LF);
-                for (uint32_t k = 0; k < ltab.n; ++k) list_groups += sh::div_up(ltab.len[k], 4 * 64 * 4);
-                rc = launch_prepare_segments_var(st, false, P, base, b->nvoices, tab.n, start);
-                if (rc) return rc;
-                SH_GEN_LEAN(dim3(sh::div_up(tiles, 4), nchunks * rsplit), trig_table(), base, b->nvoices, head, SEG, o, stride, tab, rsplit);
-                SH_CHECK_LAUNCH("k_generate_lean_harm");
-                constexpr uint32_t VSPLIT = 8;
-                if (ltab.n) {
-                    hipLaunchKernelGGL((k_generate_lists<4, false, OutT>), dim3(list_groups, nchunks * VSPLIT), dim3(256), 0, st,
-                                       ptrs(b), trig_table(), b->nvoices, base, start, head, o, stride, ltab, VSPLIT, scale, flag);
-                    SH_CHECK_LAUNCH("k_generate_lists");
-                }
-                if (head == nframes) return SH_OK;
-                return generate_rows<OutT>(b, start + head, nframes - head, o + head, stride, scale, flag);
-            }
-        }
-        const uint32_t nseg = sh::div_up(nframes, SEG);
-        LaunchSet base;
-        if (nseg == 1) {
-            rc = acquire_records(b, start, nframes, st, false);
-            if (rc) return rc;
-            base = launch_set(b, b->cur);
+    if (s.records == shg::ONE_SET) {
+        rc = acquire_records(b, start, s.n, st, false);
+        if (rc) return rc;
+        base = launch_set(b, b->cur);
+    } else {
+        rc = grow_segment_sets(b->gen_block, b->gen_set, b->gen_segs, s.nseg, nv);
+        if (rc) return rc;
+        base = b->gen_set;
+        if (s.records == shg::EQUAL_SETS) {
+            rc = launch_prepare_segments(st, ptrs(b), base, nv, s.nseg, start, s.n, shg::SEG);
         } else {
-            rc = grow_segment_sets(b->gen_block, b->gen_set, b->gen_segs, nseg, b->nvoices);
-            if (rc) return rc;
-            base = b->gen_set;
-            rc = launch_prepare_segments(st, ptrs(b), base, b->nvoices, nseg, start, nframes, SEG);
-            if (rc) return rc;
+            BankPtrs P = ptrs(b);
+            P.nseg = s.nseg;
+            for (uint32_t k = 0; k <= s.nseg; ++k) P.seg_first[k] = s.seg_first[k];
+            rc = launch_prepare_segments_var(st, false, P, base, nv, s.nseg, start);
         }
-        SegTab none;
-        none.n = 0;
-        SH_GEN_LEAN(dim3(sh::div_up(nframes, 256 * LF), nchunks * rsplit), trig_table(), base, b->nvoices, nframes,
-                    nseg == 1 ? (nframes + 1023u) / 1024u * 1024u : SEG, o, stride, none, rsplit);
-#undef SH_GEN_LEAN
-        SH_CHECK_LAUNCH("k_generate_lean_harm");
-        for (uint32_t sg = 0; sg < nseg; ++sg) {
-            const uint32_t first = sg * SEG, n = nframes - first < SEG ? nframes - first : SEG;
-            if (b->no_general_voice(start + first, n)) continue;
-            LaunchSet cur = base;
-            if (nseg > 1) {
-                const size_t stride = set_slots(b->nvoices);          // (segment_set's layout)
-                cur.launch += (size_t)sg * stride; cur.fm += (size_t)sg * stride; cur.fast += (size_t)sg * stride;
-                cur.gen_idx += (size_t)sg * stride; cur.counts += (size_t)sg * 4 * nchunks;
-            }
-            SegTab no_tab;
-            no_tab.n = 0;
-            hipLaunchKernelGGL((k_generate_lists<4, false, OutT>), dim3(sh::div_up(n, 1024), nchunks), dim3(256), 0, st,
-                               ptrs(b), trig_table(), b->nvoices, cur, start + first, n, o + first, stride, no_tab, 1u, scale, flag);
-            SH_CHECK_LAUNCH("k_generate_lists");
-        }
-        return SH_OK;
+        if (rc) return rc;
     }
-    rc = acquire_records(b, start, nframes, sh::state().stream, false);
-    if (rc) return rc;
-    const uint32_t tile_groups = sh::div_up(nframes, 256 * fpl);
-    // voices per block: as many as keeps >= ~4096 blocks in flight (and gridDim.y <= 65535)
-    uint32_t vpg = 1;
-    while (vpg < 64 && (uint64_t)tile_groups * ((b->nvoices + 2 * vpg - 1) / (2 * vpg)) >= 4096) vpg *= 2;
-    while ((b->nvoices + vpg - 1) / vpg > 65535) vpg *= 2;
-    const uint32_t groups = (b->nvoices + vpg - 1) / vpg;
-    float* o32 = nullptr;
-    short* o16 = nullptr;
-    if constexpr (RowOut<OutT>::I16) o16 = o; else o32 = o;
-#define SH_GEN(F_) hipLaunchKernelGGL(k_generate<F_>, dim3(tile_groups, groups), dim3(256), 0, sh::state().stream,            \
-                                      ptrs(b), trig_table(), 0u, b->nvoices, vpg, b->d_launch, b->d_launch_fm, start, nframes, \
-                                      (const double*)nullptr, (const double*)nullptr, o32, (double*)nullptr, stride, o16, scale, flag)
-    if (!with_rows && fpl == 4 && b->lean_candidates != 0) {
-        // long rows of a bank with lean candidates: one workgroup column per 64-voice chunk, walking the launch's lists
-        SegTab no_tab;
-        no_tab.n = 0;
-        hipLaunchKernelGGL((k_generate_lists<4, true, OutT>), dim3(tile_groups, sh::div_up(b->nvoices, 64)), dim3(256), 0, sh::state().stream,
-                           ptrs(b), trig_table(), b->nvoices, launch_set(b, b->cur), start, nframes, o, stride, no_tab, 1u, scale, flag);
-    } else if (fpl == 4) SH_GEN(4); else if (fpl == 2) SH_GEN(2); else SH_GEN(1);
-#undef SH_GEN
-    SH_CHECK_LAUNCH("k_generate");
+    if (planes) {
+        rc = planes->alloc(s.temp_bytes);
+        if (rc) return rc;
+        d.planes = (int2v*)planes->buf.ptr;
+    }
+    for (const shg::Launch& l : s.launches) {
+        const dim3 grid(l.gx, l.gy);
+        switch (l.kernel) {
+        case shg::GENERATE: {
+            float* o32 = nullptr;
+            double* o64 = nullptr;
+            short* o16 = nullptr;
+            if constexpr (F64) o64 = o; else if constexpr (I16) o16 = o; else o32 = o;
+            hipLaunchKernelGGL(generate_kernel(l.fpl), grid, dim3(256), 0, st, ptrs(b), trig_table(), 0u, nv, l.split, b->d_launch, b->d_launch_fm, start, l.n,
+                               (const double*)nullptr, (const double*)nullptr, o32, o64, d.stride, o16, d.scale, d.flag);
+            SH_CHECK_LAUNCH(F64 ? "k_generate(f64 rows)" : "k_generate");
+            break;
+        }
+        case shg::LISTS:
+            if constexpr (!F64) {
+                const LaunchSet cur = s.records == shg::EQUAL_SETS ? segment_set(base, l.set, nv) : base;
+                hipLaunchKernelGGL(lists_kernel<OutT>(l.lean), grid, dim3(256), 0, st, ptrs(b), trig_table(), nv, cur, start + l.first, l.n, o + l.first, d.stride,
+                                   l.tab, l.split, d.scale, d.flag);
+                SH_CHECK_LAUNCH(l.lean ? "k_generate" : "k_generate_lists");      // (the names a failed launch has always been reported under)
+            }
+            break;
+        case shg::LEAN_HARM:
+            if constexpr (I16) {
+                if (l.fold) {
+                    hipLaunchKernelGGL((lean_kernel<short, true>(l.fpl, l.guard)), grid, dim3(256), 0, st, trig_table(), base, nv, l.n, l.seg_frames, (short*)nullptr,
+                                       (size_t)0, l.tab, l.split, d.scale, d.flag, d.planes, (size_t)l.n);
+                    SH_CHECK_LAUNCH("k_generate_lean_harm(fold)");
+                    break;
+                }
+            }
+            if constexpr (!F64) {
+                hipLaunchKernelGGL((lean_kernel<OutT, false>(l.fpl, l.guard)), grid, dim3(256), 0, st, trig_table(), base, nv, l.n, l.seg_frames, o, d.stride,
+                                   l.tab, l.split, d.scale, d.flag, (int2v*)nullptr, (size_t)0);
+                SH_CHECK_LAUNCH("k_generate_lean_harm");
+            }
+            break;
+        case shg::COMBINE:
+            hipLaunchKernelGGL(k_mixdown_combine, grid, dim3(256), 0, st, (const int2v*)d.planes, l.split, (size_t)l.n, 0u, l.n, d.mono);
+            SH_CHECK_LAUNCH("k_mixdown_combine");
+            break;
+        case shg::COMPOSE:
+            hipLaunchKernelGGL(k_mixdown_compose, grid, dim3(256), 0, st, (const int2v*)d.planes, l.split, (size_t)l.n, l.n, d.maps);
+            SH_CHECK_LAUNCH("k_mixdown_compose");
+            break;
+        }
+    }
     return SH_OK;
 }
 
-int generate_check(const char* who, sh_bank* b, uint32_t nframes, const sh_buf* voices_out, size_t stride, size_t elem) {
-    if (!b || !voices_out) return sh::set_error(SH_ERR_INVALID, "%s: NULL argument", who);
+shg::Plan plan_call(const sh_bank* b, const shg::Call& c) { return shg::plan(*b, c, sh::knobs().no_seg); }
+
+// `out`: the call's rows (d.rows, d.stride) or its mixdown (d.mono / d.maps); scale and flag as the int16 forms need them
+int run_plan(sh_bank* b, const shg::Call& c, const shg::Plan& p, const Dest& out) {
+    size_t i = 0;
+    while (i < p.steps.size()) {
+        // a stretch: the steps up to the one that closes it share a temporary (a two-step stretch's int16 rows, allocated here; a fused
+        // stretch's planes, allocated by its one step)
+        const shg::Step& open = p.steps[i];
+        sh::Temp temp;
+        Dest d = out;
+        if (open.mix != shg::ROWS) {
+            if (d.mono) d.mono += open.stretch_first;
+            if (d.maps) d.maps += open.stretch_first;
+        }
+        if (open.mix == shg::TWO_STEP) {
+            int rc = temp.alloc(open.temp_bytes);
+            if (rc) return rc;
+            d.rows = temp.buf.ptr;
+            d.stride = ((size_t)open.stretch_n + 63) & ~(size_t)63;
+        }
+        for (bool closed = false; !closed; ++i) {
+            const shg::Step& s = p.steps[i];
+            Dest ds = d;
+            int rc;
+            if (c.form == shg::ROWS_F32) { ds.rows = (float*)d.rows + s.first; rc = run_step<float>(b, c.start + s.first, s, ds, nullptr); }
+            else if (c.form == shg::ROWS_F64) { ds.rows = (double*)d.rows + s.first; rc = run_step<double>(b, c.start + s.first, s, ds, nullptr); }
+            else { ds.rows = (short*)d.rows + (s.first - s.stretch_first); rc = run_step<short>(b, c.start + s.first, s, ds, s.mix == shg::FUSED ? &temp : nullptr); }
+            if (rc) return rc;
+            closed = s.closes || s.mix == shg::ROWS;
+        }
+        if (open.mix == shg::TWO_STEP) {
+            // the stretch's int16 rows through the chain kernel: where a voice needs the general code (the attack and decay of the notes, voices of
+            // other kinds), whose rows the fold would have to take in voice order between the lean ones
+            int rc;
+            if (d.maps) {
+                sh_buf m{d.maps, (size_t)open.stretch_n * 8, false, 0};
+                rc = sh_mix_chain_i16_parts(&temp.buf, b->nvoices, d.stride, open.stretch_n, &m);
+            } else {
+                sh_buf o{d.mono, (size_t)open.stretch_n * 2, false, 0};
+                rc = sh_mix_chain_i16(&temp.buf, b->nvoices, d.stride, open.stretch_n, &o);
+            }
+            if (rc) return rc;
+        }
+    }
+    return SH_OK;
+}
+
+int call_check(const char* who, const void* b, const void* buf, uint32_t nframes) {
+    if (!b || !buf) return sh::set_error(SH_ERR_INVALID, "%s: NULL argument", who);
     if (nframes > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "%s: at most 2^32 - 65536 frames per call", who);
+    return SH_OK;
+}
+int too_small(const char* who) { return sh::set_error(SH_ERR_INVALID, "%s: output buffer too small", who); }
+
+int generate_check(const char* who, sh_bank* b, uint32_t nframes, const sh_buf* voices_out, size_t stride, size_t elem) {
+    int rc = call_check(who, b, voices_out, nframes);
+    if (rc) return rc;
     if (stride < nframes) return sh::set_error(SH_ERR_INVALID, "%s: stride < nframes", who);
-    if (nframes && voices_out->bytes / elem < (size_t)(b->nvoices - 1) * stride + nframes)
-        return sh::set_error(SH_ERR_INVALID, "%s: output buffer too small", who);
+    if (nframes && voices_out->bytes / elem < (size_t)(b->nvoices - 1) * stride + nframes) return too_small(who);
     return bank_check_plain(b, who);
+}
+
+// A synchronous call that fails part-way (kernels already enqueued may have raised the flag) must not leave the process-wide word up
+// for the next, unrelated call: lower it on the stream, behind those kernels.  (The word is shared with the _async calls: a synchronous
+// call consumes whatever overflow is pending -- include/synthhip.h says so.)
+int sync_call_failed(int rc) {
+    sh::State& st = sh::state();
+    if (st.flag) (void)hipMemsetAsync(st.flag + 1, 0, sizeof(int), st.stream);
+    return rc;
+}
+
+// the synchronous form of an _async int16 call: the call, then the overflow word
+template <typename Call>
+int sync_call(uint32_t nframes, Call&& async_call) {
+    SH_API_LOCK();
+    const int rc = async_call();
+    if (rc) return sync_call_failed(rc);
+    if (nframes == 0) return rc;
+    return sh_overflow_check();
+}
+
+// sh_bank_generate_rows[_i16]: `call` with the bank reading `rows_f64` (the lock is held across it, recursively: the rows belong to this call)
+template <typename Call>
+int with_rows(const char* who, sh_bank* b, uint32_t nframes, const sh_buf* rows_f64, size_t row_stride, Call&& call) {
+    if (!b || !rows_f64) return sh::set_error(SH_ERR_INVALID, "%s: NULL argument", who);
+    SH_API_LOCK();
+    if (!b->d_fm_row) return sh::set_error(SH_ERR_INVALID, "%s: sh_bank_set_rows has not been called", who);
+    if (row_stride < nframes) return sh::set_error(SH_ERR_INVALID, "%s: row_stride < nframes", who);
+    if (b->fm_row_max >= 0 && rows_f64->bytes / 8 < (size_t)b->fm_row_max * row_stride + nframes)
+        return sh::set_error(SH_ERR_INVALID, "%s: rows buffer too small for row %d", who, b->fm_row_max);
+    b->launch_rows = (const double*)rows_f64->ptr;
+    b->launch_row_stride = row_stride;
+    const int rc = call();
+    b->launch_rows = nullptr;
+    b->launch_row_stride = 0;
+    return rc;
+}
+
+// sh_bank_mixdown_i16 (out) and sh_bank_mixdown_i16_parts (maps): the reference's mono mixdown without the rows where the plan folds
+// a stretch (see k_generate_lean_harm, FOLD), through int16 rows and the chain kernel elsewhere
+int bank_mixdown(const char* who, sh_bank* b, uint64_t start, uint32_t nframes, double scale, short* out, int2v* maps) {
+    int rc = bank_check_plain(b, who);
+    if (rc || nframes == 0) return rc;
+    const shg::Call c{start, nframes, maps ? shg::MIXDOWN_MAPS : shg::MIXDOWN, b->launch_rows != nullptr};
+    const shg::Plan p = plan_call(b, c);
+    if (p.refused) return sh::set_error(SH_ERR_INVALID, "%s: at most 32768 voices", who);
+    if (sh::state().quantise_round)
+        return sh::set_error(SH_ERR_INVALID, "%s: the fused quantiser truncates; under SH_OPT_QUANTISE_ROUND quantise float64 rows and fold them (sh_mix_chain_i16)", who);
+    sh::state().last_mixdown_fused = p.fused;       // (the fused stretches the call PLANNED: after a call that fails part-way, more than ran)
+    return run_plan(b, c, p, Dest{nullptr, 0, scale, sh::state().flag + 1, nullptr, out, maps});
 }
 
 }  // namespace
@@ -917,7 +977,8 @@ int sh_bank_generate(sh_bank* b, uint64_t start, uint32_t nframes, sh_buf* voice
     SH_REQUIRE_INIT();
     int rc = generate_check("sh_bank_generate", b, nframes, voices_out, stride, 4);
     if (rc || nframes == 0) return rc;
-    return generate_rows<float>(b, start, nframes, (float*)voices_out->ptr, stride, 0.0, nullptr);
+    const shg::Call c{start, nframes, shg::ROWS_F32, b->launch_rows != nullptr};
+    return run_plan(b, c, plan_call(b, c), Dest{voices_out->ptr, stride, 0.0, nullptr, nullptr, nullptr, nullptr});
 }
 
 int sh_bank_generate_i16_async(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* voices_out, size_t stride) {
@@ -928,7 +989,8 @@ int sh_bank_generate_i16_async(sh_bank* b, uint64_t start, uint32_t nframes, dou
         return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_i16: stride must be even (rows are written as 32-bit pairs of samples)");
     if (sh::state().quantise_round)
         return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_i16: the fused quantiser truncates; under SH_OPT_QUANTISE_ROUND quantise float64 rows (sh_bank_generate_f64 + sh_quantize_f64)");
-    return generate_rows<short>(b, start, nframes, (short*)voices_out->ptr, stride, scale, sh::state().flag + 1);     // (word 0: the quantisers of pcm.hip)
+    const shg::Call c{start, nframes, shg::ROWS_I16, b->launch_rows != nullptr};
+    return run_plan(b, c, plan_call(b, c), Dest{voices_out->ptr, stride, scale, sh::state().flag + 1, nullptr, nullptr, nullptr});     // (word 0: the quantisers of pcm.hip)
 }
 
 #ifdef SH_AB_COUNT
@@ -952,217 +1014,58 @@ int sh_overflow_check(void) {
     return SH_OK;
 }
 
-namespace {
-// A synchronous call that fails part-way (kernels already enqueued may have raised the flag) must not leave the process-wide word up
-// for the next, unrelated call: lower it on the stream, behind those kernels.  (The word is shared with the _async calls: a synchronous
-// call consumes whatever overflow is pending -- include/synthhip.h says so.)
-int sync_call_failed(int rc) {
-    sh::State& st = sh::state();
-    if (st.flag) (void)hipMemsetAsync(st.flag + 1, 0, sizeof(int), st.stream);
-    return rc;
-}
-}  // namespace
-
 int sh_bank_generate_i16(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* voices_out, size_t stride) {
-    SH_API_LOCK();
-    const int rc = sh_bank_generate_i16_async(b, start, nframes, scale, voices_out, stride);
-    if (rc) return sync_call_failed(rc);
-    if (nframes == 0) return rc;
-    return sh_overflow_check();
+    return sync_call(nframes, [&] { return sh_bank_generate_i16_async(b, start, nframes, scale, voices_out, stride); });
 }
-
-// ---- the reference's mono mixdown without the rows (see k_generate_lean_harm, FOLD) ---------------------------------------------------
-namespace {
-
-// frames [f0, f0 + len) of the call through int16 rows in a temporary and the chain kernel: where a voice needs the general code (the
-// attack and decay of the notes, voices of other kinds), whose rows the fold would have to take in voice order between the lean ones
-// (maps: the _parts form -- the chain's map per frame instead of its result, see k_mixdown_compose; out is then unused)
-int mixdown_two_step(sh_bank* b, uint64_t start, uint32_t len, double scale, short* out, int* flag, int2v* maps) {
-    const size_t stride = ((size_t)len + 63) & ~(size_t)63;
-    sh::Temp rows;
-    int rc = rows.alloc((size_t)b->nvoices * stride * 2);
-    if (rc) return rc;
-    rc = generate_rows<short>(b, start, len, (short*)rows.buf.ptr, stride, scale, flag);
-    if (rc) return rc;
-    if (maps) {
-        sh_buf m{maps, (size_t)len * 8, false, 0};
-        return sh_mix_chain_i16_parts(&rows.buf, b->nvoices, stride, len, &m);
-    }
-    sh_buf o{out, (size_t)len * 2, false, 0};
-    return sh_mix_chain_i16(&rows.buf, b->nvoices, stride, len, &o);
-}
-
-int mixdown_fused(sh_bank* b, uint64_t start, uint32_t len, double scale, short* out, int* flag, int2v* maps) {
-    constexpr uint32_t SEG = 65536;
-    hipStream_t st = sh::state().stream;
-    const uint32_t nchunks = sh::div_up(b->nvoices, 64), rsplit = 2, nplanes = nchunks * rsplit;
-    int lf = 16;
-    while (lf > 4 && (uint64_t)sh::div_up(len, 256 * lf) * nchunks < 512) lf /= 2;
-    const uint32_t nseg = sh::div_up(len, SEG);
-    LaunchSet base;
-    int rc;
-    if (nseg == 1) {
-        rc = acquire_records(b, start, len, st, false);
-        if (rc) return rc;
-        base = launch_set(b, b->cur);
-    } else {
-        rc = grow_segment_sets(b->gen_block, b->gen_set, b->gen_segs, nseg, b->nvoices);
-        if (rc) return rc;
-        base = b->gen_set;
-        rc = launch_prepare_segments(st, ptrs(b), base, b->nvoices, nseg, start, len, SEG);
-        if (rc) return rc;
-    }
-    sh::Temp parts;
-    rc = parts.alloc((size_t)nplanes * len * sizeof(int2v));
-    if (rc) return rc;
-    SegTab none;
-    none.n = 0;
-    const dim3 grid(sh::div_up(len, 256 * lf), nplanes);
-    const uint32_t seg_frames = nseg == 1 ? (len + 1023u) / 1024u * 1024u : SEG;
-#define SH_MIXDOWN(F_) do { if (b->has_guard) hipLaunchKernelGGL((k_generate_lean_harm<F_, short, true>), grid, dim3(256), 0, st, trig_table(), base, b->nvoices, len, seg_frames, \
-                                          (short*)nullptr, (size_t)0, none, rsplit, scale, flag, (int2v*)parts.buf.ptr, (size_t)len); \
-                            else hipLaunchKernelGGL((k_generate_lean_harm<F_, short, true, false>), grid, dim3(256), 0, st, trig_table(), base, b->nvoices, len, seg_frames, \
-                                          (short*)nullptr, (size_t)0, none, rsplit, scale, flag, (int2v*)parts.buf.ptr, (size_t)len); } while (0)
-    if (lf == 16) SH_MIXDOWN(16); else if (lf == 8) SH_MIXDOWN(8); else SH_MIXDOWN(4);
-#undef SH_MIXDOWN
-    SH_CHECK_LAUNCH("k_generate_lean_harm(fold)");
-    if (maps) {
-        hipLaunchKernelGGL(k_mixdown_compose, sh::grid1d(len, 256), dim3(256), 0, st, (const int2v*)parts.buf.ptr, nplanes, (size_t)len, len, maps);
-        SH_CHECK_LAUNCH("k_mixdown_compose");
-        return SH_OK;
-    }
-    hipLaunchKernelGGL(k_mixdown_combine, sh::grid1d(len, 256), dim3(256), 0, st, (const int2v*)parts.buf.ptr, nplanes, (size_t)len, 0u, len, out);
-    SH_CHECK_LAUNCH("k_mixdown_combine");
-    return SH_OK;
-}
-
-// sh_bank_mixdown_i16 (out) and sh_bank_mixdown_i16_parts (maps): one walk over the stretches
-int bank_mixdown(const char* who, sh_bank* b, uint64_t start, uint32_t nframes, double scale, short* out, int2v* maps) {
-    int rc = bank_check_plain(b, who);
-    if (rc || nframes == 0) return rc;
-    if (b->nvoices > 32768) return sh::set_error(SH_ERR_INVALID, "%s: at most 32768 voices", who);
-    if (sh::state().quantise_round)
-        return sh::set_error(SH_ERR_INVALID, "%s: the fused quantiser truncates; under SH_OPT_QUANTISE_ROUND quantise float64 rows and fold them (sh_mix_chain_i16)", who);
-    int* flag = sh::state().flag + 1;
-    // Stretches of whole 65 536-frame segments in which every voice takes the lean polynomial-Harmonics loop (its records then hold the
-    // bank in voice order, silent voices -- which add nothing to a chain -- left out) are folded where the samples are made; the others
-    // (the notes' attack and decay, banks with other kinds of voice, short calls) go through int16 rows and the chain kernel.
-    constexpr uint32_t SEG = 65536;
-    const bool lean_bank = !b->launch_rows && b->lean_candidates != 0 && b->lean_fm_candidates == 0 && b->all_lean && nframes >= 8192;
-    uint32_t f0 = 0;
-    sh::state().last_mixdown_fused = 0;
-    while (f0 < nframes && !rc) {
-        const uint32_t n0 = nframes - f0 < SEG ? nframes - f0 : SEG;
-        const bool fused = lean_bank && b->no_general_voice(start + f0, n0);
-        uint32_t f1 = f0 + n0;
-        while (f1 < nframes) {                                // extend the stretch while the next segment is of the same sort
-            const uint32_t n1 = nframes - f1 < SEG ? nframes - f1 : SEG;
-            if ((lean_bank && b->no_general_voice(start + f1, n1)) != fused) break;
-            if (!fused && f1 - f0 >= 4 * SEG) break;          // (two-step stretches: a temporary of nvoices x 2 B per frame each)
-            if (fused && f1 - f0 >= 16 * SEG) break;          // (fused stretches: planes of 16 B per frame each -- 1024 voices: 0.5 GB per 2^20 frames; the chain is per frame, so cutting changes nothing)
-            f1 += n1;
-        }
-        short* o = out ? out + f0 : nullptr;
-        int2v* m = maps ? maps + f0 : nullptr;
-        rc = fused ? mixdown_fused(b, start + f0, f1 - f0, scale, o, flag, m) : mixdown_two_step(b, start + f0, f1 - f0, scale, o, flag, m);
-        if (fused) sh::state().last_mixdown_fused += 1;
-        f0 = f1;
-    }
-    return rc;
-}
-
-}  // namespace
 
 int sh_bank_mixdown_i16_async(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* out_i16) {
     SH_REQUIRE_INIT();
-    if (!b || !out_i16) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16: NULL argument");
-    if (nframes > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16: at most 2^32 - 65536 frames per call");
-    if (out_i16->bytes / 2 < nframes) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16: output buffer too small");
-    return bank_mixdown("sh_bank_mixdown_i16", b, start, nframes, scale, (short*)out_i16->ptr, nullptr);
+    const char* who = "sh_bank_mixdown_i16";
+    int rc = call_check(who, b, out_i16, nframes);
+    if (rc) return rc;
+    if (out_i16->bytes / 2 < nframes) return too_small(who);
+    return bank_mixdown(who, b, start, nframes, scale, (short*)out_i16->ptr, nullptr);
 }
 
 int sh_bank_mixdown_i16_parts_async(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* parts_out) {
     SH_REQUIRE_INIT();
-    if (!b || !parts_out) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16_parts: NULL argument");
-    if (nframes > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16_parts: at most 2^32 - 65536 frames per call");
+    const char* who = "sh_bank_mixdown_i16_parts";
+    int rc = call_check(who, b, parts_out, nframes);
+    if (rc) return rc;
     if (parts_out->bytes / 8 < nframes || ((uintptr_t)parts_out->ptr & 7))
         return sh::set_error(SH_ERR_INVALID, "sh_bank_mixdown_i16_parts: parts_out too small or not 8-byte aligned");
-    return bank_mixdown("sh_bank_mixdown_i16_parts", b, start, nframes, scale, nullptr, (int2v*)parts_out->ptr);
+    return bank_mixdown(who, b, start, nframes, scale, nullptr, (int2v*)parts_out->ptr);
 }
 
 int sh_bank_mixdown_i16_parts(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* parts_out) {
-    SH_API_LOCK();
-    const int rc = sh_bank_mixdown_i16_parts_async(b, start, nframes, scale, parts_out);
-    if (rc) return sync_call_failed(rc);
-    if (nframes == 0) return rc;
-    return sh_overflow_check();
+    return sync_call(nframes, [&] { return sh_bank_mixdown_i16_parts_async(b, start, nframes, scale, parts_out); });
 }
 
 int sh_bank_mixdown_i16(sh_bank* b, uint64_t start, uint32_t nframes, double scale, sh_buf* out_i16) {
-    SH_API_LOCK();
-    const int rc = sh_bank_mixdown_i16_async(b, start, nframes, scale, out_i16);
-    if (rc) return sync_call_failed(rc);
-    if (nframes == 0) return rc;
-    return sh_overflow_check();
+    return sync_call(nframes, [&] { return sh_bank_mixdown_i16_async(b, start, nframes, scale, out_i16); });
 }
 
 int sh_bank_generate_rows(sh_bank* b, uint64_t start, uint32_t nframes, const sh_buf* rows_f64, size_t row_stride,
                           sh_buf* voices_out, size_t stride) {
-    if (!b || !rows_f64) return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_rows: NULL argument");
-    SH_API_LOCK();                                           // held across sh_bank_generate (recursive): the rows belong to this call
-    if (!b->d_fm_row) return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_rows: sh_bank_set_rows has not been called");
-    if (row_stride < nframes) return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_rows: row_stride < nframes");
-    if (b->fm_row_max >= 0 && rows_f64->bytes / 8 < (size_t)b->fm_row_max * row_stride + nframes)
-        return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_rows: rows buffer too small for row %d", b->fm_row_max);
-    b->launch_rows = (const double*)rows_f64->ptr;
-    b->launch_row_stride = row_stride;
-    const int rc = sh_bank_generate(b, start, nframes, voices_out, stride);
-    b->launch_rows = nullptr;
-    b->launch_row_stride = 0;
-    return rc;
+    return with_rows("sh_bank_generate_rows", b, nframes, rows_f64, row_stride, [&] { return sh_bank_generate(b, start, nframes, voices_out, stride); });
 }
 
 int sh_bank_generate_rows_i16(sh_bank* b, uint64_t start, uint32_t nframes, const sh_buf* rows_f64, size_t row_stride,
                               double scale, sh_buf* voices_out, size_t stride) {
-    if (!b || !rows_f64) return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_rows_i16: NULL argument");
-    SH_API_LOCK();
-    if (!b->d_fm_row) return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_rows_i16: sh_bank_set_rows has not been called");
-    if (row_stride < nframes) return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_rows_i16: row_stride < nframes");
-    if (b->fm_row_max >= 0 && rows_f64->bytes / 8 < (size_t)b->fm_row_max * row_stride + nframes)
-        return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_rows_i16: rows buffer too small for row %d", b->fm_row_max);
-    b->launch_rows = (const double*)rows_f64->ptr;
-    b->launch_row_stride = row_stride;
-    const int rc = sh_bank_generate_i16(b, start, nframes, scale, voices_out, stride);
-    b->launch_rows = nullptr;
-    b->launch_row_stride = 0;
-    return rc;
+    return with_rows("sh_bank_generate_rows_i16", b, nframes, rows_f64, row_stride,
+                     [&] { return sh_bank_generate_i16(b, start, nframes, scale, voices_out, stride); });
 }
 
 int sh_bank_generate_f64(sh_bank* b, uint64_t start, uint32_t nframes, sh_buf* rows_out, size_t row0, size_t row_stride) {
     SH_REQUIRE_INIT();
-    if (!b || !rows_out) return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_f64: NULL argument");
-    if (nframes == 0) return SH_OK;
-    if (nframes > 0xFFFF0000u) return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_f64: at most 2^32 - 65536 frames per call");
+    int rc = call_check("sh_bank_generate_f64", b, rows_out, nframes);
+    if (rc || nframes == 0) return rc;
     if (row_stride < nframes || rows_out->bytes / 8 < (row0 + b->nvoices - 1) * row_stride + nframes)
         return sh::set_error(SH_ERR_INVALID, "sh_bank_generate_f64: rows buffer too small");
-    int rc = bank_check_plain(b, "sh_bank_generate_f64");
+    rc = bank_check_plain(b, "sh_bank_generate_f64");
     if (rc) return rc;
-    rc = acquire_records(b, start, nframes, sh::state().stream, false);
-    if (rc) return rc;
-    const int fpl = nframes >= 8192 ? 4 : (nframes >= 2048 ? 2 : 1);
-    const uint32_t tile_groups = sh::div_up(nframes, 256 * fpl);
-    uint32_t vpg = 1;
-    while (vpg < 64 && (uint64_t)tile_groups * ((b->nvoices + 2 * vpg - 1) / (2 * vpg)) >= 4096) vpg *= 2;
-    while ((b->nvoices + vpg - 1) / vpg > 65535) vpg *= 2;
-    const uint32_t groups = (b->nvoices + vpg - 1) / vpg;
-    double* o = (double*)rows_out->ptr + row0 * row_stride;
-#define SH_GEN64(F_) hipLaunchKernelGGL(k_generate<F_>, dim3(tile_groups, groups), dim3(256), 0, sh::state().stream,          \
-                                        ptrs(b), trig_table(), 0u, b->nvoices, vpg, b->d_launch, b->d_launch_fm, start, nframes, \
-                                        (const double*)nullptr, (const double*)nullptr, (float*)nullptr, o, row_stride)
-    if (fpl == 4) SH_GEN64(4); else if (fpl == 2) SH_GEN64(2); else SH_GEN64(1);
-#undef SH_GEN64
-    SH_CHECK_LAUNCH("k_generate(f64 rows)");
-    return SH_OK;
+    const shg::Call c{start, nframes, shg::ROWS_F64, false};
+    return run_plan(b, c, plan_call(b, c), Dest{(double*)rows_out->ptr + row0 * row_stride, row_stride, 0.0, nullptr, nullptr, nullptr, nullptr});
 }
 
 }  // extern "C"

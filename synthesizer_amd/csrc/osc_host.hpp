@@ -7,8 +7,7 @@
 
 using namespace shosc;
 
-struct sh_bank {
-    uint32_t    nvoices = 0;
+struct sh_bank : shg::BankFacts {       // (nvoices, the lean counts, has_guard, the envelope and piece facts, no_general_voice: genplan.hpp)
     sh_voice*   d_voices = nullptr;
     sh_segment* d_segs = nullptr;
     double*     d_coefs = nullptr;
@@ -22,7 +21,6 @@ struct sh_bank {
     uint32_t*   d_gen_idx_buf[NSETS] = {};
     uint32_t*   d_counts_buf[NSETS] = {};      // 4 per 64-voice chunk: lean, general, silent, -
     uint32_t*   d_hint = nullptr;
-    bool        has_guard = false;         // some voice carries a guard list (sh_voice::guard_count): the int16 kernels with the boundary check
     // one arrival counter per tile of a SELF-FOLDING launch (a render that stands alone: the last workgroup of a tile to store its
     // partial bus folds the tile's planes itself -- no k_bus_combine behind the launch); behind d_hint's 2 * nvoices words, zero
     // between launches (the folding workgroup resets its counter)
@@ -84,27 +82,11 @@ struct sh_bank {
     // the block were skipped (nobody reads them there), so only such a launch may take the set
     struct Spec { bool valid = false; uint64_t start = 0; uint32_t nframes = 0; bool sparse = false; } spec[NSETS];
     void        void_specs() { for (auto& q : spec) q.valid = false; last_target = -1; }
-    uint32_t    lean_candidates = 0;      // voices that can take the lean loop in some launch (static properties)
-    uint32_t    lean_fm_candidates = 0;   // ... of them other than polynomial Harmonics (FM Sine, plain waveforms)
-    uint32_t    lean_fmsine_candidates = 0;   // ... of them FM Sine voices (all of the lean candidates: the FM-only lean kernel)
+    uint32_t    lean_fmsine_candidates = 0;   // the lean candidates that are FM Sine voices (all of the lean candidates: the FM-only lean kernel)
     bool        last_tiled = false;       // ... and whether it was tile-classified (no classification by voice then)
     uint32_t    last_groups = 0;          // voice groups of the last sh_bank_render launch (sh_bank_launch_stats)
-    // When can a launch hold NO general voice (so that a split launch needs no general-lists kernel)?  Conservative, from
-    // static properties: every voice is a lean candidate, every envelope is on its sustain piece for the
-    // whole launch, and no phase-table piece shorter than the launch ends after its start (a launch then crosses at most one
-    // piece end per voice).  short_piece_end[k] = the largest end of any piece shorter than 2^k samples.
-    bool        all_lean = false;          // every voice is a lean candidate (of any lean kind)
     bool        has_onsets = false;        // some voice starts late (sh_voice::start_frame)
     bool        own_envelopes = false;     // the voices' envelope corners are too many to cut launches at (more than 16 distinct ones)
-    uint64_t    env_flat_from = 0, env_flat_until = ~0ull;
-    std::vector<uint64_t> env_corners;     // the distinct attack / decay / sustain / release ends of the voices, sorted (empty when there are many)
-    uint64_t    short_piece_end[34] = {};
-    bool        no_general_voice(uint64_t start, uint32_t nframes) const {
-        if (!all_lean || start < env_flat_from || start + nframes > env_flat_until) return false;
-        int k = 0;
-        while ((1ull << k) < (uint64_t)nframes) ++k;
-        return short_piece_end[k] <= start;
-    }
     float2*     d_gains = nullptr;
     uint32_t    nsegs = 0, ncoefs = 0, npartials = 0;
     std::vector<sh_voice> h_voices;    // for validation of per-call arguments
@@ -126,7 +108,6 @@ int prepare_single(sh_bank* b, uint32_t first, uint32_t count, uint64_t start, u
 // the classification of such a launch resolves the records it needs itself (launch_prepare_tiles with the set)
 int acquire_records(sh_bank* b, uint64_t start, uint32_t nframes, hipStream_t launch_stream, bool in_run, bool accept_sparse = false, bool* deferred = nullptr);
 int prepare_chunks_now(sh_bank* b, uint64_t start, uint32_t nframes, hipStream_t st);     // the set b->cur, on stream st
-uint32_t plan_segments(const sh_bank* b, uint64_t start, uint32_t nframes, uint64_t T, uint64_t max_len, bool corners, uint32_t* seg_first);
 int bank_check_plain(const sh_bank* b, const char* who);
 // `nseg` record sets for `nvoices` voices carved out of one pool-backed block (grown when it is too small; *cap = sets it holds)
 int grow_segment_sets(sh::Pooled& block, LaunchSet& g, uint32_t& cap, uint32_t nseg, uint32_t nvoices);

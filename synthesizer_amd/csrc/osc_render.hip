@@ -489,7 +489,7 @@ static int bank_render(sh_bank* b, uint64_t start, uint32_t nframes, sh_buf* bus
     uint32_t seg_first[SEG_MAX + 1];
     uint32_t nseg = 0;
     if (!tiled && split && (var == 484 || var == 4163) && b->all_lean && !K.no_seg && !b->needs_rows && !b->no_general_voice(start, nframes)) {
-        nseg = plan_segments(b, start, nframes, (uint64_t)(64 * F), ~0ull, true, seg_first);
+        nseg = plan_segments(*b, start, nframes, (uint64_t)(64 * F), ~0ull, true, seg_first);
         if (nseg < 2 || seg_first[nseg] != nframes) nseg = 0;        // nothing to cut, or more cuts than a launch carries
     }
     bool records_deferred = false;          // (a tile-classified launch without a resolved record set: its classification resolves what it needs)
