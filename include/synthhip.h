@@ -216,6 +216,8 @@ int  sh_debug_counters(sh_counters* out);
  *                                 goes through k_resample_small like any other pair of rates, not through k_resample_period_i16
  *   SYNTHHIP_PERIOD_CHUNKS=n      consecutive chunks per workgroup of k_resample_period_i16 (default: 1, 2 or 4 by the rates' ratio;
  *                                 profiles/r06_resample_period.txt)
+ *   SYNTHHIP_SEQ_ALIGN=1          k_mix_events_i16 reads an event's misaligned samples through a vector type of alignment 2 instead of
+ *                                 two aligned 16-byte loads and a funnel shift (profiles/sequence_ab.txt)
  * (SYNTHHIP_LIB, read by the Python binding, names another build of this library to load; SYNTHHIP_ALLOW_STALE=1 lets it load a
  * library whose sources have changed when rebuilding fails.) */
 
@@ -442,6 +444,26 @@ int sh_mix_chain_gather_i16(const sh_buf* const* srcs, const size_t* sample_offs
 int sh_mix_chain(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nsamples, int width, sh_buf* out);
 int sh_mix_chain_gather(const sh_buf* const* srcs, const size_t* sample_offsets, const uint32_t* nsamples_each, uint32_t nsrc,
                         uint32_t nsamples, int width, sh_buf* out, size_t out_sample_off);
+
+/* ---- a list of placed samples mixed into a track ---------------------------------------------------------------------------------
+ * Replaces: a loop of Sample.mix_at(seconds, other.at_volume(volume), other_seconds) calls (upstream synthplayer/sample.py, [RECALL];
+ * what its track-mixer example and Sample.echo do) -- one launch over one short region per call, plus a copy of the whole track
+ * whenever it grows.  Per event audioop.mul(frames, width, factor) (fbound: clamp, then floor) of srcs[src][src_sample .. +nsamples),
+ * then audioop.add into track[dst_sample ..) with saturation AT EVERY EVENT, IN LIST ORDER: the same bytes as the loop.  One launch;
+ * tiles of the track that no event touches are neither read nor written. */
+typedef struct sh_mix_event {      /* one placed sample; all positions in SAMPLES (not frames, not bytes) */
+    uint64_t dst_sample;           /* where in the track its first sample lands */
+    uint64_t src_sample;           /* first sample taken from the source buffer */
+    uint64_t nsamples;             /* may be 0 */
+    double   factor;               /* audioop.mul factor; exactly 1.0 = none */
+    uint32_t src;                  /* index into srcs */
+    uint32_t reserved;             /* 0 */
+} sh_mix_event;                    /* 40 bytes */
+/* track[0 .. track_samples) = the events applied in order, in place.  No src may be `track`.  SH_ERR_INVALID, and nothing launched,
+ * for: a source index >= nsrc, a range outside its source or the track, a non-finite factor, reserved != 0, a width other than
+ * 1 - 4, a source that is (or overlaps) the track, more than 2^32 - 65536 track samples. */
+int sh_mix_events(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event* events, uint32_t nevents,
+                  int width, sh_buf* track, size_t track_samples);
 
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads

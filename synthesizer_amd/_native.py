@@ -55,9 +55,13 @@ VOICE_DTYPE = np.dtype([
     ("noise_seed", "<u8"), ("noise_hold", "<u4"), ("reserved0", "<u4"), ("start_frame", "<u8"),
     ("guard_t", "<f8"), ("guard_c", "<f8"), ("guard_offset", "<u4"), ("guard_count", "<u4")], align=True)
 
+MIX_EVENT_DTYPE = np.dtype([("dst_sample", "<u8"), ("src_sample", "<u8"), ("nsamples", "<u8"), ("factor", "<f8"),
+                            ("src", "<u4"), ("reserved", "<u4")], align=True)          # sh_mix_event
+
 # sizes the C side must agree with (checked against the library's view in tests via sh_bank_create)
 assert SEGMENT_DTYPE.itemsize == 24 and PARTIAL_DTYPE.itemsize == 16 and ENVELOPE_DTYPE.itemsize == 80
 assert VOICE_DTYPE.itemsize == 272, VOICE_DTYPE.itemsize
+assert MIX_EVENT_DTYPE.itemsize == 40
 
 
 class Counters(C.Structure):
@@ -131,6 +135,7 @@ _SIGNATURES = {
     "sh_mix_chain_gather_i16": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _P, C.c_size_t]),
     "sh_mix_chain": (C.c_int, [_P, C.c_uint32, C.c_size_t, C.c_uint32, C.c_int, _P]),
     "sh_mix_chain_gather": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_int, _P, C.c_size_t]),
+    "sh_mix_events": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, C.c_int, _P, C.c_size_t]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),

@@ -7,6 +7,7 @@
 // chain.  Built with -ffp-contract=off (float64 products stay two roundings).
 #include "common.hpp"
 #include "chain.hpp"
+#include "pcmdev.hpp"
 #include <mutex>
 #include <string.h>
 #include <new>
@@ -383,31 +384,6 @@ struct ChainSrcB {
     uint32_t n;               // samples available
     uint32_t pad;
 };
-
-template <int WIDTH>
-__device__ __forceinline__ long long chain_get(const unsigned char* p, size_t i) {
-    if (WIDTH == 1) return (long long)(signed char)p[i];
-    if (WIDTH == 3) {
-        const unsigned char* q = p + 3 * i;
-        return (long long)((int)q[0] | ((int)q[1] << 8) | ((int)(signed char)q[2] << 16));
-    }
-    int v;
-    __builtin_memcpy(&v, p + 4 * i, 4);
-    return (long long)v;
-}
-
-template <int WIDTH>
-__device__ __forceinline__ void chain_put(unsigned char* p, size_t i, long long x) {
-    if (WIDTH == 1) { p[i] = (unsigned char)(signed char)x; return; }
-    if (WIDTH == 3) {
-        unsigned char* q = p + 3 * i;
-        const int v = (int)x;
-        q[0] = (unsigned char)(v & 0xFF); q[1] = (unsigned char)((v >> 8) & 0xFF); q[2] = (unsigned char)((v >> 16) & 0xFF);
-        return;
-    }
-    const int v = (int)x;
-    __builtin_memcpy(p + 4 * i, &v, 4);
-}
 
 template <int WIDTH>
 __global__ __launch_bounds__(256) void k_mix_chain_gather_w(const ChainSrcB* __restrict__ tab, uint32_t nsrc, uint32_t nsamples,

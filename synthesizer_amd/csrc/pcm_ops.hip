@@ -5,23 +5,12 @@
 // shuffle (DPP) reductions + one integer atomic per workgroup for max / sum of squares.
 // Built with -ffp-contract=off: audioop forms val1*lfactor + val2*rfactor with separate roundings.
 #include "common.hpp"
+#include "pcmdev.hpp"
 #include <stdlib.h>
 #include <type_traits>
 #include <vector>
 
 namespace {
-
-// audioop's fbound(): clamp, then round toward minus infinity
-__device__ __forceinline__ int fbound(double val, double minval, double maxval) {
-    if (val > maxval) val = maxval;
-    else if (val < minval + 1.0) val = minval;
-    return (int)floor(val);
-}
-
-template <typename T> struct Lim;
-template <> struct Lim<signed char> { static constexpr double lo = -128.0, hi = 127.0; };
-template <> struct Lim<short> { static constexpr double lo = -32768.0, hi = 32767.0; };
-template <> struct Lim<int> { static constexpr double lo = -2147483648.0, hi = 2147483647.0; };
 
 // out[i] = fbound(in[i] * factor)            (audioop.mul)
 template <typename T, int VEC, bool NT = false>

@@ -39,6 +39,7 @@ void load_knobs() {
     k.no_ladder = flag("SYNTHHIP_NO_LADDER");
     k.no_period = flag("SYNTHHIP_NO_PERIOD");
     k.period_chunks = (int)num("SYNTHHIP_PERIOD_CHUNKS", 0);
+    k.seq_align = (int)num("SYNTHHIP_SEQ_ALIGN", 0);
     k.variant = (int)num("SYNTHHIP_VARIANT", 0);
     k.groups = (int)num("SYNTHHIP_GROUPS", 0);
     k.pool_fill = (int)num("SYNTHHIP_POOL_FILL", -1);

@@ -30,7 +30,7 @@ from . import params
 from .oscillators import Oscillator, VoiceSpec, _pwm_widths, _table, pack_voices, time_step_weights
 from .sample import Sample
 
-__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
+__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "sequence", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
 
 
 def pan_gains(pan: float) -> Tuple[float, float]:
@@ -572,6 +572,13 @@ def mix_samples(samples: Sequence[Sample], name: str = "mix") -> Sample:
     _gather([(s._device(), 0, len(s) * s.nchannels) for s in samples], nsamples, dst, width)
     out._set_device(dst, nbytes)
     return out
+
+
+def sequence(events: Sequence[tuple], samplerate: int, nchannels: int, samplewidth: int = 2, name: str = "") -> Sample:
+    """A track made of placed samples: a new empty ``Sample`` of the given format with ``events`` -- ``(seconds, sample,
+    volume=None, sample_seconds=None)`` each -- mixed in by ``Sample.mix_at_many``: in list order, saturating at every event."""
+    track = Sample(name=name, samplerate=samplerate, nchannels=nchannels, samplewidth=samplewidth)
+    return track.mix_at_many(events)
 
 
 class _MixSource:

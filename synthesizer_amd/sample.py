@@ -553,6 +553,74 @@ class Sample:
             N.check(L.sh_pcm_add(dst.handle, start, other._device().handle, 0, n2, self.__samplewidth, dst.handle, start))
         self._set_device(dst, total)
 
+    def mix_at_many(self, events: Iterable[tuple]) -> "Sample":
+        """Mix a list of placed samples into this one: ``events`` holds ``(seconds, other, volume=None, other_seconds=None)``, and
+        the result is, byte for byte, what ::
+
+            for seconds, other, volume, other_seconds in events:
+                self.mix_at(seconds, other if volume is None else other.at_volume(volume), other_seconds)
+
+        leaves -- ``audioop.mul`` per event, ``audioop.add`` with saturation at every event, in list order, the track grown to the
+        furthest end -- in one launch (sh_mix_events) and with at most one allocation (none when nothing grows).  Negative times and
+        non-finite volumes are a ValueError.  An event whose ``other`` is this sample reads it as the events before it left it: the
+        list is cut there, and that one event goes through ``mix_at``."""
+        self._check_writable()
+        self._check_gpu_width("mix_at")
+        fb = self.__samplewidth * self.__nchannels
+        todo = []                                           # everything is checked before anything is mixed
+        for ev in events:
+            seconds, other = ev[0], ev[1]
+            volume = ev[2] if len(ev) > 2 else None
+            other_seconds = ev[3] if len(ev) > 3 else None
+            assert self.samplewidth == other.samplewidth
+            assert self.samplerate == other.samplerate
+            assert self.nchannels == other.nchannels
+            if seconds < 0 or (other_seconds is not None and other_seconds < 0):
+                raise ValueError("mix_at_many: negative time")
+            if volume is not None and not math.isfinite(volume):
+                raise ValueError("mix_at_many: volume is not finite")
+            start = fb * int(self.__samplerate * seconds)                       # frame_idx(seconds): Python floats, on the host
+            n2 = other.frame_idx(other_seconds) if other_seconds else other.__nbytes
+            todo.append((seconds, other, volume, other_seconds, start, min(n2, other.__nbytes)))
+        batch = []
+        for seconds, other, volume, other_seconds, start, n2 in todo:
+            if other is self:
+                self.__mix_events(batch)
+                batch = []
+                self.mix_at(seconds, other if volume is None else other.at_volume(volume), other_seconds)
+            else:
+                batch.append((start, other, n2, 1.0 if volume is None else float(volume)))
+        self.__mix_events(batch)
+        return self
+
+    def __mix_events(self, batch: Sequence[tuple]) -> None:
+        """The events (first byte, other, bytes, factor) -- none of them this sample -- folded in order; length -> the furthest end."""
+        if not batch:
+            return
+        n1 = self.__nbytes
+        total = max(n1, max(start + n2 for start, _o, n2, _f in batch))
+        if total == 0:
+            return
+        if total == n1 and self._device().nbytes >= n1 and not self.__dev_shared:
+            track = self.__dev                              # in place, under __mix_region's conditions
+        else:
+            track = N.DeviceBuffer(total)
+            if total > n1:
+                track.zero(n1, total - n1)
+            if n1:
+                N.check(N.lib().sh_buf_copy(track.handle, 0, self._device().handle, 0, n1))
+        w = self.__samplewidth
+        slot, bufs = {}, []
+        table = np.zeros(len(batch), dtype=N.MIX_EVENT_DTYPE)
+        for k, (start, other, n2, factor) in enumerate(batch):
+            if id(other) not in slot:
+                slot[id(other)] = len(bufs)
+                bufs.append(other._device())
+            table[k] = (start // w, 0, n2 // w, factor, slot[id(other)], 0)
+        srcs = (C.c_void_p * len(bufs))(*[b.handle for b in bufs])
+        N.check(N.lib().sh_mix_events(srcs, len(bufs), table.ctypes.data, len(table), w, track.handle, total // w))
+        self._set_device(track, total)                      # (in place: drops the host copy, it is stale now)
+
     # -- elementwise operations (upstream: thin wrappers over audioop) ---------------------------------
     def __unary(self, fn_name: str, out_nbytes: int, *args) -> "Sample":
         """frames = op(frames): run sh_<fn_name>(in, ..., out) into a fresh device buffer."""

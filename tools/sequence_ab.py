@@ -1,0 +1,155 @@
+#!/usr/bin/env python
+"""Sample.mix_at_many against the loop of Sample.mix_at calls it replaces, timed in one process on the same inputs (GPU box, repo
+root), every row checked against live audioop (mul, add on byte slices, event by event) before it is timed.
+
+Rows: the song of tests/test_gpu_sequence.py stretched to 120 s with 4096 / 32 768 events; Sample.echo-shaped lists (8 events); 64
+events that each cover a whole 10-s stereo track at start 0 -- beside mixer.mix_samples of the same 64 tracks, the aligned gather
+fold.  Per row: wall ms of the loop and of mix_at_many (median of repeated passes, each bracketed by a device sync), their ratio,
+the device time of the one call (events around it: table copy + kernel) and its logical bytes/s = (sum of event bytes + active-tile
+bytes read and written) / device time -- which may exceed the HBM peak when the instruments are served by L2.
+SYNTHHIP_SEQ_ALIGN=1: the 16-bit kernel's other way of reading misaligned event samples (include/synthhip.h)."""
+import audioop
+import os
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from synthesizer_amd import _native as N  # noqa: E402
+from synthesizer_amd import mixer  # noqa: E402
+from synthesizer_amd.sample import Sample  # noqa: E402
+
+RATE, NCH, WIDTH = 48000, 2, 2
+TILE = 2048
+
+
+def instruments(rng):
+    out = []
+    for seconds in (0.05, 0.12, 0.25, 0.4):
+        n = int(RATE * seconds)
+        decay = np.exp(-3.0 * np.arange(n) / n)[:, None]
+        out.append((rng.uniform(-1.0, 1.0, (n, NCH)) * decay * 0.5 * 32767).astype("<i2").tobytes())
+    return out
+
+
+def song(nevents, span):
+    rng = np.random.default_rng(0)
+    inst = instruments(rng)
+    starts = rng.integers(0, int(RATE * span), nevents) / RATE
+    starts[:50] = starts[0]
+    which = rng.integers(0, 4, nevents)
+    volumes = rng.choice([1.0, 1.0, 0.5, 0.8, -1.0, 0.0, 1.7], nevents)
+    return b"", inst, [(float(starts[k]), int(which[k]), float(volumes[k])) for k in range(nevents)]
+
+
+def echo_list():
+    rng = np.random.default_rng(1)
+    base = rng.integers(-12000, 12000, NCH * RATE * 5, dtype=np.int16).tobytes()
+    tail = base[-NCH * WIDTH * RATE:]                       # the last second, 8 times, 0.3 s apart, each 0.7 of the one before
+    return base, [tail], [(4.0 + 0.3 * (k + 1), 0, 0.7 ** (k + 1)) for k in range(8)]
+
+
+def whole_tracks():
+    rng = np.random.default_rng(2)
+    tracks = [rng.integers(-3000, 3000, NCH * RATE * 10, dtype=np.int16).tobytes() for _ in range(64)]
+    return b"", tracks, [(0.0, k, None) for k in range(64)]
+
+
+def oracle(base, sources, events):
+    fb = WIDTH * NCH
+    t = bytearray(base)
+    for seconds, i, volume in events:
+        frames = sources[i] if volume is None else audioop.mul(sources[i], WIDTH, volume)
+        start = fb * int(RATE * seconds)
+        end = start + len(frames)
+        if end > len(t):
+            t.extend(bytes(end - len(t)))
+        t[start:end] = audioop.add(bytes(t[start:end]), frames, WIDTH)
+    return bytes(t)
+
+
+def logical_bytes(sources, events, total_bytes):
+    active = np.zeros(total_bytes // WIDTH // TILE + 1, dtype=bool)
+    ev_bytes = 0
+    for seconds, i, _v in events:
+        s = NCH * int(RATE * seconds)
+        n = len(sources[i]) // WIDTH
+        if n:
+            active[s // TILE:(s + n - 1) // TILE + 1] = True
+            ev_bytes += n * WIDTH
+    return ev_bytes + 2 * int(active.sum()) * TILE * WIDTH
+
+
+def median_wall(fn, warm, passes):
+    for _ in range(warm):
+        fn()
+    N.sync()
+    runs = []
+    for _ in range(passes):
+        N.sync()
+        t0 = time.perf_counter()
+        fn()
+        N.sync()
+        runs.append((time.perf_counter() - t0) * 1e3)
+    return sorted(runs)[len(runs) // 2]
+
+
+def main():
+    N.ensure_init(0)
+    print("sequence_ab: SYNTHHIP_SEQ_ALIGN=%s  %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), N.device_info()["name"]), flush=True)
+    rows = [("song 120 s, 4096 events", song(4096, 120.0), 3), ("song 120 s, 32768 events", song(32768, 120.0), 2),
+            ("echo-shaped, 8 events", echo_list(), 7), ("64 x whole 10-s track", whole_tracks(), 5)]
+    for name, (base, sources, events), loop_passes in rows:
+        samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in sources]
+        start = Sample.from_raw_frames(base, WIDTH, RATE, NCH).to_device()
+        evs = [(s, samples[i], v) for s, i, v in events]
+        got = start.copy().mix_at_many(evs)
+        want = oracle(base, sources, events)
+        parity = bytes(got.view_frame_data()) == want
+        del got
+
+        def loop():
+            t = start.copy()
+            for seconds, other, volume in evs:
+                t.mix_at(seconds, other if volume is None else other.at_volume(volume))
+
+        def many():
+            start.copy().mix_at_many(evs)
+
+        loop_ms = median_wall(loop, 1, loop_passes)
+        many_ms = median_wall(many, 3, 9)
+        # the one call on its own, on a track that is already long enough (in place): device time between two events on the stream
+        track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, NCH).to_device()
+        for _ in range(3):
+            track.mix_at_many(evs)
+        dev = []
+        for _ in range(9):
+            N.sync()
+            N.timer_start()
+            track.mix_at_many(evs)
+            dev.append(N.timer_stop())
+        dev_ms = sorted(dev)[len(dev) // 2]
+        lb = logical_bytes(sources, events, len(want))
+        print("%-26s loop %9.3f ms   mix_at_many %8.3f ms   ratio %7.1fx   device (in place) %7.4f ms   logical %.3f TB/s (%.1f MB)   parity %s"
+              % (name, loop_ms, many_ms, loop_ms / many_ms, dev_ms, lb / (dev_ms * 1e-3) / 1e12, lb / 1e6, "ok" if parity else "FAILED"), flush=True)
+        if name.startswith("64 x"):
+            mixed = mixer.mix_samples(samples)
+            same = bytes(mixed.view_frame_data()) == want
+            g = []
+            for _ in range(3):
+                mixer.mix_samples(samples)
+            for _ in range(9):
+                N.sync()
+                N.timer_start()
+                mixer.mix_samples(samples)
+                g.append(N.timer_stop())
+            g_ms = sorted(g)[len(g) // 2]
+            gb = 65 * len(want)
+            print("%-26s mixer.mix_samples (aligned gather fold) device %7.4f ms   %.3f TB/s of its %.1f MB   same bytes %s"
+                  % ("", g_ms, gb / (g_ms * 1e-3) / 1e12, gb / 1e6, "ok" if same else "FAILED"), flush=True)
+
+
+if __name__ == "__main__":
+    main()
