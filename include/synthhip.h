@@ -465,6 +465,30 @@ typedef struct sh_mix_event {      /* one placed sample; all positions in SAMPLE
 int sh_mix_events(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event* events, uint32_t nevents,
                   int width, sh_buf* track, size_t track_samples);
 
+/* The same with a playback speed per event: a sampler -- one recorded note at many pitches -- in one launch.
+ * Replaces: per note, Sample.copy().speed(s) (upstream synthplayer/sample.py, [RECALL]: audioop.ratecv(frames, width, nchannels,
+ * int(rate * s), rate, None)), .at_volume(v) and mix_at(...): four to six launches and three allocations for a few thousand frames.
+ * An event with inrate != outrate contributes audioop.ratecv(srcs[src][src_sample .. + src_frames * nchannels), width, nchannels,
+ * inrate, outrate) from its output frame 0 on -- its first nsamples samples, THEN audioop.mul by factor, then the saturating add, in
+ * that order (mul and ratecv do not commute).  The resampled source is never materialised: the lane that owns a track sample forms
+ * the output frame that lands there from two input frames.  inrate == outrate is a plain event of sh_mix_events (src_frames ignored);
+ * a list may hold both kinds. */
+typedef struct sh_mix_event_rate { /* all positions in SAMPLES unless named frames */
+    uint64_t dst_sample;           /* where in the track its first sample lands */
+    uint64_t src_sample;           /* first sample of the source buffer the event may read (resampled: input frame 0) */
+    uint64_t nsamples;             /* samples landing in the track -- RESAMPLED samples for a resampled event; may be 0 */
+    uint64_t src_frames;           /* resampled: input frames the event may read from src_sample on */
+    double   factor;               /* audioop.mul factor, applied after the resample; exactly 1.0 = none */
+    uint32_t src;                  /* index into srcs */
+    uint32_t inrate, outrate;      /* audioop.ratecv's; equal: a plain event */
+    uint32_t reserved;             /* 0 */
+} sh_mix_event_rate;               /* 56 bytes */
+/* SH_ERR_INVALID, and nothing launched, for everything sh_mix_events refuses, and: a rate of 0 or >= 2^31, nchannels < 1; for a
+ * resampled event src_sample or nsamples not a multiple of nchannels, src_frames beyond the source, nsamples beyond the
+ * sh_resample_out_frames(src_frames, inrate, outrate) * nchannels samples that src_frames yield. */
+int sh_mix_events_rate(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_rate* events, uint32_t nevents,
+                       int width, int nchannels, sh_buf* track, size_t track_samples);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

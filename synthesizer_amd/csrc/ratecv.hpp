@@ -1,4 +1,4 @@
-// ratecv.hpp -- audioop.ratecv's index arithmetic and the resampler's route plan: the one statement of both.
+// ratecv.hpp -- audioop.ratecv's index arithmetic, its per-sample arithmetic and the resampler's route plan: the one statement of each.
 //
 // Rates are gcd-reduced (inr, outr).  Output frame m sits at input position q + r/outr (q = floor(m inr / outr), r = m inr mod outr) and
 // interpolates input frames j - 1 and j with weights d and outr - d: j = ceil(m inr / outr) = q + (r != 0), d = (outr - r) mod outr --
@@ -68,6 +68,43 @@ SH_HD void step(Q& q, uint32_t& r, Q step_q, uint32_t step_r, uint32_t outr, Q u
 // 1/(2 outr) > 2^-17 away from every integer, and the evaluation is off by less than 2^-20 (a quotient below 2^32, 1/outr rounded to
 // 53 bits, one rounding of the fma), so the truncation is the floor -- 3 instructions, no correction step.
 SH_HD uint32_t floor_by_outr(uint32_t u, double inv_outr) { return (uint32_t)fma((double)u, inv_outr, 0.5 * inv_outr); }
+
+// ---- one output sample (resample.hip's kernels and sequence.hip's resampled events; built with -ffp-contract=off) ---------------------
+
+// (prev*d + cur*(outrate-d)) / outrate in float64, exactly as audioop forms it: two products, one sum, one
+// correctly rounded division.  The division is Markstein's sequence q = a*y, r = fma(-q, b, a),
+// q' = fma(r, y, q) with y = RN(1/b): it returns the correctly rounded quotient (checked against IEEE
+// division on 3e8 operands in tests/ and by every bit-exact parity test), at 3 instructions instead of
+// the ~12 of the generic lowering -- k_resample must stay HBM-bound.
+SH_HD double value(double prev, double cur, double dd, double od, double outr, double inv_outr) {
+    const double a = prev * dd + cur * od;
+    const double q = a * inv_outr;
+    const double r = fma(-q, outr, a);
+    return fma(r, inv_outr, q);
+}
+
+// 8/16-bit PCM, reduced outrate < 65536.  audioop computes trunc(fl(N / outr)) >> s with N = (prev*d + cur*(outr-d)) << s
+// (s = 32 - bits): N is an exact float64 integer (< 2^48), a non-integer N/outr is at least 1/outr > 2^-16 away
+// from an integer while its float64 rounding error is below 2^-21, so the truncation equals integer division, and
+// trunc(.) >> s == floor(M / outr) with M = prev*d + cur*(outr-d) (|M| <= 2^(bits-1)*outr < 2^31; for M < 0 the
+// inner truncation loses less than 2^-s < 1/outr, which the floor of the arithmetic shift restores).  floor(M/outr)
+// is formed as an unsigned division of u = M + 2^(bits-1)*outr (0 <= u < 2^32): floor_by_outr.  Bit-exactness against
+// audioop is what tests/test_gpu_pcm.py (both paths) and tests/test_seqrate.py assert.
+template <typename T>
+SH_HD T small_int(T prev, T cur, uint32_t d, uint32_t outr, double inv_outr) {
+    constexpr int HALF = 1 << (8 * (int)sizeof(T) - 1);
+    const int M = (int)prev * (int)d + (int)cur * (int)(outr - d);
+    const uint32_t u = (uint32_t)M + (uint32_t)HALF * outr;
+    return (T)((int)floor_by_outr(u, inv_outr) - HALF);
+}
+
+// Integer PCM of any width through the float64 expression: GETSAMPLE32 (the sample in the high bits of 32: shift = 32 - 8 width), the
+// value, SETSAMPLE32 (truncation toward zero, then the arithmetic shift back).
+SH_HD int shifted_int(int prev, int cur, uint32_t d, uint32_t outr, double inv_outr, int shift) {
+    const int ci = (int)((unsigned)cur << shift);
+    const int pi = (int)((unsigned)prev << shift);
+    return (int)value((double)pi, (double)ci, (double)d, (double)(outr - d), (double)outr, inv_outr) >> shift;
+}
 
 // frames per thread of the few-channel kernels: 16-byte stores, at most 8 frames
 SH_HD constexpr int frames_per_thread(int frame_bytes) { return 16 / frame_bytes > 8 ? 8 : 16 / frame_bytes; }

@@ -29,44 +29,15 @@ struct RatecvArgs {
 
 __device__ __forceinline__ shr::Pos ratecv_pos(const RatecvArgs& A, uint64_t m) { return shr::position(m, A.inr, A.outr, A.inv_outr); }
 
-// (prev*d + cur*(outrate-d)) / outrate in float64, exactly as audioop forms it: two products, one sum, one
-// correctly rounded division.  The division is Markstein's sequence q = a*y, r = fma(-q, b, a),
-// q' = fma(r, y, q) with y = RN(1/b): it returns the correctly rounded quotient (checked against IEEE
-// division on 3e8 operands in tests/ and by every bit-exact parity test), at 3 instructions instead of
-// the ~12 of the generic lowering -- this kernel must stay HBM-bound.
-__device__ __forceinline__ double ratecv_value(double prev, double cur, double dd, double od, double outr, double inv_outr) {
-    const double a = prev * dd + cur * od;
-    const double q = a * inv_outr;
-    const double r = fma(-q, outr, a);
-    return fma(r, inv_outr, q);
-}
-
-// 8/16-bit PCM, reduced outrate < 65536.  audioop computes trunc(fl(N / outr)) >> s with N = (prev*d + cur*(outr-d)) << s
-// (s = 32 - bits): N is an exact float64 integer (< 2^48), a non-integer N/outr is at least 1/outr > 2^-16 away
-// from an integer while its float64 rounding error is below 2^-21, so the truncation equals integer division, and
-// trunc(.) >> s == floor(M / outr) with M = prev*d + cur*(outr-d) (|M| <= 2^(bits-1)*outr < 2^31; for M < 0 the
-// inner truncation loses less than 2^-s < 1/outr, which the floor of the arithmetic shift restores).  floor(M/outr)
-// is formed as an unsigned division of u = M + 2^(bits-1)*outr (0 <= u < 2^32): shr::floor_by_outr.  Bit-exactness against
-// audioop is what tests/test_gpu_pcm.py asserts on both paths.
-template <typename T>
-__device__ __forceinline__ T ratecv_small_int(T prev, T cur, uint32_t d, uint32_t outr, double inv_outr) {
-    constexpr int HALF = 1 << (8 * (int)sizeof(T) - 1);
-    const int M = (int)prev * (int)d + (int)cur * (int)(outr - d);
-    const uint32_t u = (uint32_t)M + (uint32_t)HALF * outr;
-    return (T)((int)shr::floor_by_outr(u, inv_outr) - HALF);
-}
-
+// One output sample in the launch's mode; the arithmetic itself is ratecv.hpp's (shr::value, shr::small_int, shr::shifted_int).
 template <typename T, int MODE>
 __device__ __forceinline__ T ratecv_sample(T prev, T cur, uint32_t d, const RatecvArgs& A) {
     if (MODE == RS_INT_SMALL) {
-        if constexpr (sizeof(T) <= 2) return ratecv_small_int<T>(prev, cur, d, A.outr, A.inv_outr);
+        if constexpr (sizeof(T) <= 2) return shr::small_int<T>(prev, cur, d, A.outr, A.inv_outr);
         else return (T)0;
     }
-    const double dd = (double)d, od = (double)(A.outr - d), outr = (double)A.outr;
-    if (MODE == RS_FLOAT) return (T)ratecv_value((double)prev, (double)cur, dd, od, outr, A.inv_outr);
-    const int ci = (int)((unsigned)(int)cur << A.shift);                               // GETSAMPLE32
-    const int pi = (int)((unsigned)(int)prev << A.shift);
-    return (T)((int)ratecv_value((double)pi, (double)ci, dd, od, outr, A.inv_outr) >> A.shift);   // SETSAMPLE32
+    if (MODE == RS_FLOAT) return (T)shr::value((double)prev, (double)cur, (double)d, (double)(A.outr - d), (double)A.outr, A.inv_outr);
+    return (T)shr::shifted_int((int)prev, (int)cur, d, A.outr, A.inv_outr, A.shift);
 }
 
 // One thread = one output frame x VEC channels, moved as one vector (VEC*sizeof(T) bytes).
@@ -255,7 +226,7 @@ __device__ __forceinline__ void resample_small_frames(const unsigned char* smem,
 //  * output m sits at input position q + r/outr; with a = x[q], b = x[q+1] the reference's expression is
 //    M = a*(outr-r) + b*r for every r (r == 0 gives cur = x[q], weight outr), so there is no prev/cur select;
 //  * u = M + HALF*outr = (b-a)*r + (a+HALF)*outr in 24-bit multiplies (mod 2^32; 0 <= u < 2^32);
-//  * floor(u/outr) by shr::floor_by_outr.  See ratecv_small_int for why the floor equals audioop's float64 expression.
+//  * floor(u/outr) by shr::floor_by_outr.  See shr::small_int for why the floor equals audioop's float64 expression.
 // (Measured and dropped, bit-identical both: the interpolation as ONE v_dot2_u32_u16 on packed weights -- 0.395 vs 0.391 ms on 900 MB;
 // the output frames dealt to the lanes, no LDS bank conflicts and 16 instead of 20 instructions per sample -- not faster either:
 // CHANGELOG items 39 and 22; profiles/r03_summary.md.)

@@ -1,16 +1,22 @@
-// sequence.hip -- a list of placed samples mixed into a track in one launch (sh_mix_events: Sample.mix_at_many, mixer.sequence).
+// sequence.hip -- a list of placed samples mixed into a track in one launch (sh_mix_events, sh_mix_events_rate: Sample.mix_at_many,
+// mixer.sequence).
 //
 // Per event audioop.mul (fbound: clamp, then floor) and audioop.add with saturation AT EVERY EVENT, IN LIST ORDER -- the loop of
 // Sample.mix_at calls it replaces, byte for byte.  The track is cut into tiles (seqplan.hpp); one workgroup per tile that some event
 // touches walks that tile's events in order, every lane keeping its own few track samples in registers from the one load of the base
 // to the one store of the result.  Lanes own disjoint samples and read the track only there, so the fold is in place; a source may
-// not be the track.  Built with -ffp-contract=off (the float64 product of audioop.mul stays one rounding).
+// not be the track.  sh_mix_events_rate: an event may play its source at another speed -- audioop.ratecv in front of the mul, output
+// frame m of the resampled source formed by whichever lane owns the track sample it lands on (ratecv.hpp: the position in closed form,
+// the sample arithmetic), never materialised.  Built with -ffp-contract=off (the float64 product of audioop.mul stays one rounding,
+// ratecv's prev*d + cur*(outr-d) two).
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
+#include "ratecv.hpp"
 #include "seqplan.hpp"
 #include <math.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -179,52 +185,212 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_mix_events_w(const SeqEv*
         if (s0 + j < track_samples) chain_put<WIDTH>(track, s0 + j, acc[j]);
 }
 
+// ---- events with a playback speed (sh_mix_events_rate) ----------------------------------------------------------------------------------
+// One event as these kernels read it: wave-uniform again (scalar loads), 64 bytes.  inr == outr: a plain event, src its first sample.
+// Otherwise src is input frame 0, and track sample dst + i is channel i % nch of output frame i / nch of audioop.ratecv(src, width,
+// nch, inr, outr): the host has checked that the n samples exist (n <= out_frames(source frames) * nch), so every input frame a lane
+// computes lies inside the source and the kernels test nothing but [0, n).
+struct SeqEvR {
+    const void* src;
+    double      factor;       // audioop.mul's, after the resample; exactly 1.0: none
+    double      inv_outr;     // 1.0 / outr
+    uint32_t    dst, n;       // as SeqEv's, n counting RESAMPLED samples
+    uint32_t    inr, outr;    // reduced rates
+    uint32_t    step_q, step_r;   // inr / outr, inr % outr (shr::step)
+    uint32_t    nch;
+    uint32_t    small;        // 1: shr::small_int (8/16-bit samples, outr < 65536), 0: the float64 expression (shr::shifted_int)
+    uint32_t    pad[2];
+};
+static_assert(sizeof(SeqEvR) == 64, "SeqEvR is read as one 64-byte scalar load");
+
+// A lane's N consecutive track samples from s0 on, as a resampled event gives them: zeros outside the event (the identity of the fold,
+// as seq_edge8), inside it frame m = rel / nch and channel rel % nch -- the position of the lane's first frame once (shr::position),
+// then shr::step per frame -- prev = frame j - 1 (zero when j == 0 or d == 0, as k_resample), cur = frame j, both straight from global
+// memory: an instrument is a few tens of KB that every note re-reads (L2 / TCP hits), and a lane's samples span about
+// N / nch * speed + 2 input frames.  get(i): sample i of the source, sign-extended.
+template <int WIDTH, int N, typename Get>
+__device__ __forceinline__ void seq_rate(const SeqEvR& c, uint32_t s0, Get get, int (&x)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) x[k] = 0;
+    const long long rel = (long long)s0 - (long long)c.dst;
+    if (rel + N <= 0 || rel >= (long long)c.n) return;
+    const uint32_t r0 = rel > 0 ? (uint32_t)rel : 0u;                  // the first sample of the event that this lane owns
+    uint32_t m, ch;                                                     // (nch is uniform)
+    if (c.nch == 1) { m = r0; ch = 0; }
+    else if (c.nch == 2) { m = r0 >> 1; ch = r0 & 1u; }
+    else { m = r0 / c.nch; ch = r0 - m * c.nch; }
+    shr::Pos p = shr::position(m, c.inr, c.outr, c.inv_outr);
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const long long r = rel + k;
+        if (r < 0 || r >= (long long)c.n) continue;
+        uint64_t j;
+        uint32_t d;
+        shr::index(p, c.outr, j, d);
+        const size_t at = (size_t)j * c.nch + ch;
+        const int cur = get(at);
+        const int prev = (j && d) ? get(at - c.nch) : 0;
+        if constexpr (WIDTH <= 2) {
+            typedef typename std::conditional<WIDTH == 1, signed char, short>::type T;
+            x[k] = c.small ? (int)shr::small_int<T>((T)prev, (T)cur, d, c.outr, c.inv_outr)
+                           : shr::shifted_int(prev, cur, d, c.outr, c.inv_outr, 32 - 8 * WIDTH);
+        } else {
+            x[k] = shr::shifted_int(prev, cur, d, c.outr, c.inv_outr, 32 - 8 * WIDTH);
+        }
+        if (++ch == c.nch) {
+            ch = 0;
+            shr::step<uint64_t>(p.q, p.r, (uint64_t)c.step_q, c.step_r, c.outr);
+        }
+    }
+}
+
+// k_mix_events_i16 with a speed per event: the same tile, lane and fold; a plain event of a mixed list takes seq_load8's vector
+// loads (a uniform branch on the record), a resampled one seq_rate.  One record ahead instead of INFLIGHT: a resampled event is sixteen
+// dependent-address loads and some forty instructions per sample, which is what there is to hide behind.
+template <int SCHEME>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_mix_events_rate_i16(const SeqEvR* __restrict__ ev, const uint32_t* __restrict__ tiles,
+                                                                           const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
+                                                                           uint32_t ntiles, short* track, uint32_t track_samples, int aligned) {
+    const uint32_t k = (uint32_t)sh::block_id();
+    if (k >= ntiles) return;
+    const uint32_t s0 = tiles[k] * shq::TILE_I16 + threadIdx.x * shq::LANE_SAMPLES_I16;
+    if (s0 >= track_samples) return;
+    const bool whole = aligned && s0 + 8 <= track_samples;
+    short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (whole) acc = *reinterpret_cast<const short8v*>(track + s0);
+    else
+        for (uint32_t j = 0; j < 8 && s0 + j < track_samples; ++j) acc[j] = track[s0 + j];
+    uint32_t e = first[k];
+    const uint32_t e1 = first[k + 1];
+    SeqEvR nx = ev[idx[e]];                                   // (an active tile lists at least one event)
+    while (e < e1) {
+        const SeqEvR c = nx;
+        if (++e < e1) nx = ev[idx[e]];
+        short8v x;
+        if (c.inr == c.outr) {                                // (uniform)
+            x = seq_load8<SCHEME>(SeqEv{c.src, c.factor, c.dst, c.n, {0, 0}}, s0);
+        } else {
+            gshort_p src = (gshort_p)c.src;
+            int v[8];
+            seq_rate<2, 8>(c, s0, [&](size_t i) { return (int)src[i]; }, v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x[j] = (short)v[j];
+        }
+        if (c.factor != 1.0) x = seq_mul8(x, c.factor);       // (uniform)
+        acc = __builtin_elementwise_add_sat(acc, x);
+    }
+    if (whole) *reinterpret_cast<short8v*>(track + s0) = acc;
+    else
+        for (uint32_t j = 0; j < 8 && s0 + j < track_samples; ++j) track[s0 + j] = acc[j];
+}
+
+// chain_get (pcmdev.hpp) through a pointer that says where a source lives: a pointer out of a record is read with flat loads otherwise
+// (SH_SEQ_GLOBAL above).
+typedef const SH_SEQ_GLOBAL unsigned char* gbyte_p;
+typedef int int_u1 __attribute__((aligned(1)));
+template <int WIDTH>
+__device__ __forceinline__ int seq_get(gbyte_p p, size_t i) {
+    if (WIDTH == 1) return (int)(signed char)p[i];
+    if (WIDTH == 3) {
+        gbyte_p q = p + 3 * i;
+        return (int)q[0] | ((int)q[1] << 8) | ((int)(signed char)q[2] << 16);
+    }
+    return *(const SH_SEQ_GLOBAL int_u1*)(p + 4 * i);
+}
+
+// k_mix_events_w with a speed per event (widths 1, 3, 4): the same loop, a resampled event's four samples from seq_rate.
+template <int WIDTH>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_mix_events_rate_w(const SeqEvR* __restrict__ ev, const uint32_t* __restrict__ tiles,
+                                                                         const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
+                                                                         uint32_t ntiles, unsigned char* track, uint32_t track_samples) {
+    const uint32_t k = (uint32_t)sh::block_id();
+    if (k >= ntiles) return;
+    const uint32_t s0 = tiles[k] * shq::TILE_W + threadIdx.x * shq::LANE_SAMPLES_W;
+    if (s0 >= track_samples) return;
+    constexpr long long HI = WIDTH == 1 ? 127LL : (WIDTH == 3 ? 8388607LL : 2147483647LL), LO = -HI - 1;
+    long long acc[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (s0 + j < track_samples) acc[j] = chain_get<WIDTH>(track, s0 + j);
+    const uint32_t e1 = first[k + 1];
+    for (uint32_t e = first[k]; e < e1; ++e) {
+        const SeqEvR c = ev[idx[e]];
+        gbyte_p src = (gbyte_p)c.src;
+        int v[4] = {0, 0, 0, 0};
+        bool in[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long rel = (long long)s0 + j - (long long)c.dst;
+            in[j] = rel >= 0 && rel < (long long)c.n;
+        }
+        if (c.inr == c.outr) {                                // (uniform)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (in[j]) v[j] = seq_get<WIDTH>(src, (size_t)((long long)s0 + j - (long long)c.dst));
+        } else {
+            seq_rate<WIDTH, 4>(c, s0, [&](size_t i) { return seq_get<WIDTH>(src, i); }, v);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (in[j]) {
+                long long x = v[j];
+                if (c.factor != 1.0) x = fbound((double)x * c.factor, (double)LO, (double)HI);
+                const long long t = acc[j] + x;
+                acc[j] = t > HI ? HI : (t < LO ? LO : t);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (s0 + j < track_samples) chain_put<WIDTH>(track, s0 + j, acc[j]);
+}
+
 }  // namespace
 
-extern "C" {
+// ---- host: what the two entry points share ----------------------------------------------------------------------------------------------
+namespace {
 
-int sh_mix_events(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event* events, uint32_t nevents, int width, sh_buf* track,
-                  size_t track_samples) {
-    SH_REQUIRE_INIT();
-    if (width < 1 || width > 4) return sh::set_error(SH_ERR_INVALID, "sh_mix_events: width %d not in {1, 2, 3, 4}", width);
-    if (!track || (nevents && !events) || (nsrc && !srcs)) return sh::set_error(SH_ERR_INVALID, "sh_mix_events: NULL argument");
+// the arguments in front of the events: width, pointers, the track's range, no source that is (or overlaps) the track
+int seq_check_args(const char* fn, const sh_buf* const* srcs, uint32_t nsrc, const void* events, uint32_t nevents, int width,
+                   const sh_buf* track, size_t track_samples) {
+    if (width < 1 || width > 4) return sh::set_error(SH_ERR_INVALID, "%s: width %d not in {1, 2, 3, 4}", fn, width);
+    if (!track || (nevents && !events) || (nsrc && !srcs)) return sh::set_error(SH_ERR_INVALID, "%s: NULL argument", fn);
     const size_t w = (size_t)width;
-    if (track_samples > track->bytes / w) return sh::set_error(SH_ERR_INVALID, "sh_mix_events: track range outside buffer");
+    if (track_samples > track->bytes / w) return sh::set_error(SH_ERR_INVALID, "%s: track range outside buffer", fn);
     const char* t0 = (const char*)track->ptr;
     const char* t1 = t0 + track_samples * w;
     for (uint32_t v = 0; v < nsrc; ++v) {
         if (!srcs[v]) continue;
         const char* p = (const char*)srcs[v]->ptr;
-        if (srcs[v] == track || (p < t1 && t0 < p + srcs[v]->bytes))
-            return sh::set_error(SH_ERR_INVALID, "sh_mix_events: source %u is the track", v);
+        if (srcs[v] == track || (p < t1 && t0 < p + srcs[v]->bytes)) return sh::set_error(SH_ERR_INVALID, "%s: source %u is the track", fn, v);
     }
-    std::vector<shq::Event> pe(nevents);
-    for (uint32_t e = 0; e < nevents; ++e) {
-        const sh_mix_event& m = events[e];
-        if (m.reserved != 0) return sh::set_error(SH_ERR_INVALID, "sh_mix_events: event %u: reserved must be 0", e);
-        if (!isfinite(m.factor)) return sh::set_error(SH_ERR_INVALID, "sh_mix_events: event %u: factor is not finite", e);
-        if (m.src >= nsrc || !srcs[m.src]) return sh::set_error(SH_ERR_INVALID, "sh_mix_events: event %u: no source %u", e, m.src);
-        const size_t have = srcs[m.src]->bytes / w;
-        if (m.src_sample > have || m.nsamples > have - m.src_sample)
-            return sh::set_error(SH_ERR_INVALID, "sh_mix_events: event %u: range outside its source", e);
-        pe[e] = shq::Event{m.dst_sample, m.nsamples};
-    }
+    return SH_OK;
+}
+
+// what every event is asked, whatever its kind
+template <typename Ev>
+int seq_check_event(const char* fn, const Ev& m, uint32_t e, const sh_buf* const* srcs, uint32_t nsrc) {
+    if (m.reserved != 0) return sh::set_error(SH_ERR_INVALID, "%s: event %u: reserved must be 0", fn, e);
+    if (!isfinite(m.factor)) return sh::set_error(SH_ERR_INVALID, "%s: event %u: factor is not finite", fn, e);
+    if (m.src >= nsrc || !srcs[m.src]) return sh::set_error(SH_ERR_INVALID, "%s: event %u: no source %u", fn, e, m.src);
+    return SH_OK;
+}
+
+// The plan of the checked events (dst, n), then records | tiles | first | idx as one block on the library's grow-only scratch, one copy,
+// one launch: fill(rec) writes the nevents records, launch(records, tiles, first, idx, ntiles, grid, block, stream) names the kernel.
+template <typename Rec, typename Fill, typename Launch>
+int seq_run(const char* fn, const std::vector<shq::Event>& pe, int width, size_t track_samples, Fill fill, Launch launch) {
+    const uint32_t nevents = (uint32_t)pe.size();
     const uint32_t tile = shq::tile_samples(width);
     const shq::Plan P = shq::plan(pe.data(), nevents, track_samples, tile);
-    if (P.refused == shq::EVENT_BEYOND_TRACK) return sh::set_error(SH_ERR_INVALID, "sh_mix_events: event %u: range outside the track", P.bad_event);
-    if (P.refused == shq::TRACK_TOO_LONG) return sh::set_error(SH_ERR_INVALID, "sh_mix_events: at most 2^32 - 65536 track samples per call");
-    if (P.refused) return sh::set_error(SH_ERR_INVALID, "sh_mix_events: more than 2^28 (event, tile) overlaps in one call");
+    if (P.refused == shq::EVENT_BEYOND_TRACK) return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside the track", fn, P.bad_event);
+    if (P.refused == shq::TRACK_TOO_LONG) return sh::set_error(SH_ERR_INVALID, "%s: at most 2^32 - 65536 track samples per call", fn);
+    if (P.refused) return sh::set_error(SH_ERR_INVALID, "%s: more than 2^28 (event, tile) overlaps in one call", fn);
     if (P.tiles.empty()) return SH_OK;
-
-    // one block on the library's grow-only scratch, one copy: records | tiles | first | idx
     const uint32_t nt = (uint32_t)P.tiles.size();
-    const size_t b_ev = (size_t)nevents * sizeof(SeqEv), b_tiles = (size_t)nt * 4, b_first = ((size_t)nt + 1) * 4, b_idx = P.idx.size() * 4;
+    const size_t b_ev = (size_t)nevents * sizeof(Rec), b_tiles = (size_t)nt * 4, b_first = ((size_t)nt + 1) * 4, b_idx = P.idx.size() * 4;
     std::vector<char> host(b_ev + b_tiles + b_first + b_idx);
-    SeqEv* rec = reinterpret_cast<SeqEv*>(host.data());
-    for (uint32_t e = 0; e < nevents; ++e) {
-        const sh_mix_event& m = events[e];
-        rec[e] = SeqEv{(const char*)srcs[m.src]->ptr + m.src_sample * w, m.factor, (uint32_t)m.dst_sample, (uint32_t)m.nsamples, {0, 0}};
-    }
+    fill(reinterpret_cast<Rec*>(host.data()));
     memcpy(host.data() + b_ev, P.tiles.data(), b_tiles);
     memcpy(host.data() + b_ev + b_tiles, P.first.data(), b_first);
     memcpy(host.data() + b_ev + b_tiles + b_first, P.idx.data(), b_idx);
@@ -234,22 +400,101 @@ int sh_mix_events(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event* 
     char* dev = (char*)sh::state().scratch;
     // (pageable source: staged before the call returns, ordered after earlier kernels)
     SH_HIP(hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, st));
-    const SeqEv* d_ev = (const SeqEv*)dev;
-    const uint32_t* d_tiles = (const uint32_t*)(dev + b_ev);
-    const uint32_t* d_first = (const uint32_t*)(dev + b_ev + b_tiles);
-    const uint32_t* d_idx = (const uint32_t*)(dev + b_ev + b_tiles + b_first);
-    const dim3 grid = sh::grid1d(nt, 1), block(shq::TILE_THREADS);
-    const uint32_t ns = (uint32_t)track_samples;
-    if (width == 2) {
-        const int aligned = ((uintptr_t)track->ptr & 15) == 0;
-        if (sh::knobs().seq_align == VEC2) hipLaunchKernelGGL((k_mix_events_i16<VEC2, 4>), grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (short*)track->ptr, ns, aligned);
-        else hipLaunchKernelGGL((k_mix_events_i16<FUNNEL, 4>), grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (short*)track->ptr, ns, aligned);
-    }
-    else if (width == 1) hipLaunchKernelGGL(k_mix_events_w<1>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
-    else if (width == 3) hipLaunchKernelGGL(k_mix_events_w<3>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
-    else hipLaunchKernelGGL(k_mix_events_w<4>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
-    SH_CHECK_LAUNCH("k_mix_events");
+    launch((const Rec*)dev, (const uint32_t*)(dev + b_ev), (const uint32_t*)(dev + b_ev + b_tiles), (const uint32_t*)(dev + b_ev + b_tiles + b_first),
+           nt, sh::grid1d(nt, 1), dim3(shq::TILE_THREADS), st);
+    SH_CHECK_LAUNCH(fn);
     return SH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sh_mix_events(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event* events, uint32_t nevents, int width, sh_buf* track,
+                  size_t track_samples) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_mix_events";
+    int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    if (rc) return rc;
+    const size_t w = (size_t)width;
+    std::vector<shq::Event> pe(nevents);
+    for (uint32_t e = 0; e < nevents; ++e) {
+        const sh_mix_event& m = events[e];
+        if ((rc = seq_check_event(fn, m, e, srcs, nsrc))) return rc;
+        const size_t have = srcs[m.src]->bytes / w;
+        if (m.src_sample > have || m.nsamples > have - m.src_sample)
+            return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside its source", fn, e);
+        pe[e] = shq::Event{m.dst_sample, m.nsamples};
+    }
+    const uint32_t ns = (uint32_t)track_samples;
+    return seq_run<SeqEv>(fn, pe, width, track_samples,
+        [&](SeqEv* rec) {
+            for (uint32_t e = 0; e < nevents; ++e) {
+                const sh_mix_event& m = events[e];
+                rec[e] = SeqEv{(const char*)srcs[m.src]->ptr + m.src_sample * w, m.factor, (uint32_t)m.dst_sample, (uint32_t)m.nsamples, {0, 0}};
+            }
+        },
+        [&](const SeqEv* d_ev, const uint32_t* d_tiles, const uint32_t* d_first, const uint32_t* d_idx, uint32_t nt, dim3 grid, dim3 block, hipStream_t st) {
+            if (width == 2) {
+                const int aligned = ((uintptr_t)track->ptr & 15) == 0;
+                if (sh::knobs().seq_align == VEC2) hipLaunchKernelGGL((k_mix_events_i16<VEC2, 4>), grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (short*)track->ptr, ns, aligned);
+                else hipLaunchKernelGGL((k_mix_events_i16<FUNNEL, 4>), grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (short*)track->ptr, ns, aligned);
+            }
+            else if (width == 1) hipLaunchKernelGGL(k_mix_events_w<1>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
+            else if (width == 3) hipLaunchKernelGGL(k_mix_events_w<3>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
+            else hipLaunchKernelGGL(k_mix_events_w<4>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
+        });
+}
+
+int sh_mix_events_rate(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_rate* events, uint32_t nevents, int width, int nchannels,
+                       sh_buf* track, size_t track_samples) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_mix_events_rate";
+    int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    if (rc) return rc;
+    if (nchannels < 1) return sh::set_error(SH_ERR_INVALID, "%s: # of channels should be >= 1", fn);
+    const size_t w = (size_t)width;
+    const uint64_t nch = (uint64_t)nchannels;
+    std::vector<shq::Event> pe(nevents);
+    for (uint32_t e = 0; e < nevents; ++e) {
+        const sh_mix_event_rate& m = events[e];
+        if ((rc = seq_check_event(fn, m, e, srcs, nsrc))) return rc;
+        if (!m.inrate || !m.outrate || m.inrate >= (1u << 31) || m.outrate >= (1u << 31))
+            return sh::set_error(SH_ERR_INVALID, "%s: event %u: sampling rate not in [1, 2^31)", fn, e);
+        const uint64_t have = srcs[m.src]->bytes / w;
+        if (m.src_sample > have) return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside its source", fn, e);
+        if (m.inrate == m.outrate) {
+            if (m.nsamples > have - m.src_sample) return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside its source", fn, e);
+        } else {
+            if (m.src_sample % nch || m.nsamples % nch)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: a resampled event starts and ends on whole frames", fn, e);
+            if (m.src_frames > (have - m.src_sample) / nch) return sh::set_error(SH_ERR_INVALID, "%s: event %u: src_frames outside its source", fn, e);
+            if (m.nsamples / nch > shr::out_frames(m.src_frames, shr::reduce(m.inrate, m.outrate)))
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: more samples than src_frames resample to", fn, e);
+        }
+        pe[e] = shq::Event{m.dst_sample, m.nsamples};
+    }
+    const uint32_t ns = (uint32_t)track_samples;
+    return seq_run<SeqEvR>(fn, pe, width, track_samples,
+        [&](SeqEvR* rec) {
+            for (uint32_t e = 0; e < nevents; ++e) {
+                const sh_mix_event_rate& m = events[e];
+                const shr::Rates R = shr::reduce(m.inrate, m.outrate);
+                rec[e] = SeqEvR{(const char*)srcs[m.src]->ptr + m.src_sample * w, m.factor, 1.0 / (double)R.outr, (uint32_t)m.dst_sample,
+                                (uint32_t)m.nsamples, R.inr, R.outr, R.inr / R.outr, R.inr % R.outr, (uint32_t)nchannels,
+                                width <= 2 && R.outr < 65536u ? 1u : 0u, {0, 0}};
+            }
+        },
+        [&](const SeqEvR* d_ev, const uint32_t* d_tiles, const uint32_t* d_first, const uint32_t* d_idx, uint32_t nt, dim3 grid, dim3 block, hipStream_t st) {
+            if (width == 2) {
+                const int aligned = ((uintptr_t)track->ptr & 15) == 0;
+                if (sh::knobs().seq_align == VEC2) hipLaunchKernelGGL(k_mix_events_rate_i16<VEC2>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (short*)track->ptr, ns, aligned);
+                else hipLaunchKernelGGL(k_mix_events_rate_i16<FUNNEL>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (short*)track->ptr, ns, aligned);
+            }
+            else if (width == 1) hipLaunchKernelGGL(k_mix_events_rate_w<1>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
+            else if (width == 3) hipLaunchKernelGGL(k_mix_events_rate_w<3>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
+            else hipLaunchKernelGGL(k_mix_events_rate_w<4>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
+        });
 }
 
 }  // extern "C"

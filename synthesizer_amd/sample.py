@@ -39,6 +39,12 @@ _TYPECODE = {1: "b", 2: "h", 4: "i"}
 _NPTYPE = {1: np.int8, 2: np.int16, 4: np.int32}
 
 
+def _ratecv_out_frames(in_frames: int, inrate: int, outrate: int) -> int:
+    """Frames ``audioop.ratecv`` makes of ``in_frames`` (sh_resample_out_frames, in Python integers): output frame m exists while
+    ceil(m inrate / outrate) <= in_frames - 1."""
+    return (in_frames - 1) * outrate // inrate + 1 if in_frames else 0
+
+
 class Sample:
     """Audio sample data: interleaved little-endian signed PCM."""
 
@@ -554,24 +560,33 @@ class Sample:
         self._set_device(dst, total)
 
     def mix_at_many(self, events: Iterable[tuple]) -> "Sample":
-        """Mix a list of placed samples into this one: ``events`` holds ``(seconds, other, volume=None, other_seconds=None)``, and
-        the result is, byte for byte, what ::
+        """Mix a list of placed samples into this one: ``events`` holds ``(seconds, other, volume=None, other_seconds=None,
+        speed=None)``, and the result is, byte for byte, what ::
 
-            for seconds, other, volume, other_seconds in events:
-                self.mix_at(seconds, other if volume is None else other.at_volume(volume), other_seconds)
+            for seconds, other, volume, other_seconds, speed in events:
+                o = other
+                if speed is not None:
+                    o = o.copy().speed(speed)           # audioop.ratecv(frames, width, nchannels, int(rate * speed), rate, None)
+                if volume is not None:
+                    o = o.at_volume(volume)             # audioop.mul, after the resample
+                self.mix_at(seconds, o, other_seconds)  # other_seconds cuts the resampled sample
 
-        leaves -- ``audioop.mul`` per event, ``audioop.add`` with saturation at every event, in list order, the track grown to the
-        furthest end -- in one launch (sh_mix_events) and with at most one allocation (none when nothing grows).  Negative times and
-        non-finite volumes are a ValueError.  An event whose ``other`` is this sample reads it as the events before it left it: the
-        list is cut there, and that one event goes through ``mix_at``."""
+        leaves -- ``audioop.ratecv`` and ``audioop.mul`` per event, ``audioop.add`` with saturation at every event, in list order, the
+        track grown to the furthest end -- in one launch (sh_mix_events; sh_mix_events_rate when an event has a speed: a sampler, one
+        recorded note at many pitches) and with at most one allocation (none when nothing grows).  A speed of None or 1.0, or one with
+        ``int(rate * speed) == rate``, is none.  Negative times, non-finite volumes and a speed that is not finite or outside
+        0.1 .. 10 are a ValueError, raised before anything is mixed.  An event whose ``other`` is this sample reads it as the events
+        before it left it: the list is cut there, and that one event goes through the loop's body above."""
         self._check_writable()
         self._check_gpu_width("mix_at")
         fb = self.__samplewidth * self.__nchannels
+        rate = self.__samplerate
         todo = []                                           # everything is checked before anything is mixed
         for ev in events:
             seconds, other = ev[0], ev[1]
             volume = ev[2] if len(ev) > 2 else None
             other_seconds = ev[3] if len(ev) > 3 else None
+            speed = ev[4] if len(ev) > 4 else None
             assert self.samplewidth == other.samplewidth
             assert self.samplerate == other.samplerate
             assert self.nchannels == other.nchannels
@@ -579,26 +594,44 @@ class Sample:
                 raise ValueError("mix_at_many: negative time")
             if volume is not None and not math.isfinite(volume):
                 raise ValueError("mix_at_many: volume is not finite")
-            start = fb * int(self.__samplerate * seconds)                       # frame_idx(seconds): Python floats, on the host
-            n2 = other.frame_idx(other_seconds) if other_seconds else other.__nbytes
-            todo.append((seconds, other, volume, other_seconds, start, min(n2, other.__nbytes)))
+            inrate = rate
+            if speed is not None and speed != 1.0:
+                if not math.isfinite(speed) or speed < 0.1 or speed > 10.0:
+                    raise ValueError("mix_at_many: speed must be between 0.1 and 10")
+                inrate = int(rate * speed)                                      # Sample.speed: Python floats, on the host
+                if inrate <= 0:
+                    raise ValueError("mix_at_many: speed %r leaves no sample rate" % (speed,))
+            start = fb * int(rate * seconds)                                    # frame_idx(seconds): Python floats, on the host
+            have = other.__nbytes if inrate == rate else fb * _ratecv_out_frames(other.__nbytes // fb, inrate, rate)
+            n2 = other.frame_idx(other_seconds) if other_seconds else have
+            todo.append((seconds, other, volume, other_seconds, speed, start, min(n2, have), inrate))
         batch = []
-        for seconds, other, volume, other_seconds, start, n2 in todo:
+        for seconds, other, volume, other_seconds, speed, start, n2, inrate in todo:
             if other is self:
                 self.__mix_events(batch)
                 batch = []
+                if inrate != rate:
+                    other = other.copy().speed(speed)
                 self.mix_at(seconds, other if volume is None else other.at_volume(volume), other_seconds)
             else:
-                batch.append((start, other, n2, 1.0 if volume is None else float(volume)))
+                batch.append((start, other, n2, 1.0 if volume is None else float(volume), inrate))
         self.__mix_events(batch)
         return self
 
     def __mix_events(self, batch: Sequence[tuple]) -> None:
-        """The events (first byte, other, bytes, factor) -- none of them this sample -- folded in order; length -> the furthest end."""
+        """The events (first byte, other, bytes, factor, inrate) -- none of them this sample -- folded in order; length -> the furthest
+        end.  inrate != the sample rate: the event plays ``other`` resampled from inrate to the sample rate, and bytes counts
+        resampled bytes.  The table is packed column by column (whole-array numpy operations, not a row per event)."""
         if not batch:
             return
+        starts, others, nbytes, factors, inrates = zip(*batch)
+        w = self.__samplewidth
+        rate = self.__samplerate
+        starts = np.array(starts, dtype=np.uint64)
+        nbytes = np.array(nbytes, dtype=np.uint64)
+        inrates = np.array(inrates, dtype=np.uint64)
         n1 = self.__nbytes
-        total = max(n1, max(start + n2 for start, _o, n2, _f in batch))
+        total = max(n1, int((starts + nbytes).max()))
         if total == 0:
             return
         if total == n1 and self._device().nbytes >= n1 and not self.__dev_shared:
@@ -609,16 +642,27 @@ class Sample:
                 track.zero(n1, total - n1)
             if n1:
                 N.check(N.lib().sh_buf_copy(track.handle, 0, self._device().handle, 0, n1))
-        w = self.__samplewidth
-        slot, bufs = {}, []
-        table = np.zeros(len(batch), dtype=N.MIX_EVENT_DTYPE)
-        for k, (start, other, n2, factor) in enumerate(batch):
-            if id(other) not in slot:
-                slot[id(other)] = len(bufs)
-                bufs.append(other._device())
-            table[k] = (start // w, 0, n2 // w, factor, slot[id(other)], 0)
+        slot = {}                                           # id(other) -> (index into srcs, other): one dict lookup per event, no more
+        for o in others:
+            slot.setdefault(id(o), (len(slot), o))
+        uniq = [o for _k, o in slot.values()]
+        bufs = [o._device() for o in uniq]
         srcs = (C.c_void_p * len(bufs))(*[b.handle for b in bufs])
-        N.check(N.lib().sh_mix_events(srcs, len(bufs), table.ctypes.data, len(table), w, track.handle, total // w))
+        src = np.fromiter((slot[id(o)][0] for o in others), dtype=np.uint32, count=len(others))
+        rated = bool((inrates != rate).any())
+        table = np.zeros(len(batch), dtype=N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
+        table["dst_sample"] = starts // w
+        table["nsamples"] = nbytes // w
+        table["factor"] = factors
+        table["src"] = src
+        if rated:
+            frames = np.array([o.__nbytes for o in uniq], dtype=np.uint64) // (w * self.__nchannels)
+            table["src_frames"] = frames[src]
+            table["inrate"] = inrates
+            table["outrate"] = rate
+            N.check(N.lib().sh_mix_events_rate(srcs, len(bufs), table.ctypes.data, len(table), w, self.__nchannels, track.handle, total // w))
+        else:
+            N.check(N.lib().sh_mix_events(srcs, len(bufs), table.ctypes.data, len(table), w, track.handle, total // w))
         self._set_device(track, total)                      # (in place: drops the host copy, it is stale now)
 
     # -- elementwise operations (upstream: thin wrappers over audioop) ---------------------------------

@@ -7,7 +7,13 @@ events that each cover a whole 10-s stereo track at start 0 -- beside mixer.mix_
 fold.  Per row: wall ms of the loop and of mix_at_many (median of repeated passes, each bracketed by a device sync), their ratio,
 the device time of the one call (events around it: table copy + kernel) and its logical bytes/s = (sum of event bytes + active-tile
 bytes read and written) / device time -- which may exceed the HBM peak when the instruments are served by L2.
-SYNTHHIP_SEQ_ALIGN=1: the 16-bit kernel's other way of reading misaligned event samples (include/synthhip.h)."""
+SYNTHHIP_SEQ_ALIGN=1: the 16-bit kernel's other way of reading misaligned event samples (include/synthhip.h).
+
+--sampler: events with a playback speed (sh_mix_events_rate) instead -- the 120-s song with 4096 / 32 768 events, each at 2^(k/12),
+k in [-12, 12], a quarter of them plain; the same song all downward (speed <= 1) and all upward (speed >= 2); a chord (one 1-s
+instrument, 64 notes at one start).  The loop is copy().speed().at_volume() + mix_at per event, timed TWICE (its run-to-run spread is the
+yardstick for "not slower"); live audioop.ratecv / mul / add is the check.  --sampler --trace: each row's one call five times and nothing
+else, for rocprofv3 --kernel-trace --stats."""
 import audioop
 import os
 import sys
@@ -82,6 +88,84 @@ def logical_bytes(sources, events, total_bytes):
     return ev_bytes + 2 * int(active.sum()) * TILE * WIDTH
 
 
+def sampler_song(nevents, span, lo=-12, hi=12, plain_share=4):
+    base, inst, events = song(nevents, span)
+    rng = np.random.default_rng(7)
+    k = rng.integers(lo, hi + 1, nevents)
+    plain = rng.integers(0, plain_share, nevents) == 0 if plain_share else np.zeros(nevents, dtype=bool)
+    return base, inst, [(s, i, v, None if plain[n] else float(2.0 ** (int(k[n]) / 12))) for n, (s, i, v) in enumerate(events)]
+
+
+def chord():
+    rng = np.random.default_rng(3)
+    n = RATE
+    note = (rng.uniform(-1.0, 1.0, (n, NCH)) * np.exp(-3.0 * np.arange(n) / n)[:, None] * 0.2 * 32767).astype("<i2").tobytes()
+    return b"", [note], [(0.5, 0, 0.3, float(2.0 ** ((k % 37 - 12) / 12))) for k in range(64)]
+
+
+def sampler_oracle(base, sources, events):
+    fb = WIDTH * NCH
+    t = bytearray(base)
+    for seconds, i, volume, speed in events:
+        frames = sources[i]
+        if speed is not None and int(RATE * speed) != RATE:
+            frames = audioop.ratecv(frames, WIDTH, NCH, int(RATE * speed), RATE, None)[0]
+        if volume is not None:
+            frames = audioop.mul(frames, WIDTH, volume)
+        start = fb * int(RATE * seconds)
+        end = start + len(frames)
+        if end > len(t):
+            t.extend(bytes(end - len(t)))
+        t[start:end] = audioop.add(bytes(t[start:end]), frames, WIDTH)
+    return bytes(t)
+
+
+def sampler_main():
+    N.ensure_init(0)
+    print("sampler_ab: SYNTHHIP_SEQ_ALIGN=%s  %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), N.device_info()["name"]), flush=True)
+    rows = [("sampler song 120 s, 4096 events", sampler_song(4096, 120.0), 2), ("sampler song 120 s, 32768 events", sampler_song(32768, 120.0), 1),
+            ("  all downward (speed <= 1), 4096", sampler_song(4096, 120.0, -12, -1, 0), 2),
+            ("  all upward (speed >= 2), 4096", sampler_song(4096, 120.0, 12, 24, 0), 2),
+            ("chord: 64 notes of one 1-s sample", chord(), 5)]
+    for name, (base, sources, events), loop_passes in rows:
+        samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in sources]
+        start = Sample.from_raw_frames(base, WIDTH, RATE, NCH).to_device()
+        evs = [(s, samples[i], v, None, sp) for s, i, v, sp in events]
+        want = sampler_oracle(base, sources, events)
+        parity = bytes(start.copy().mix_at_many(evs).view_frame_data()) == want
+        if "--trace" in sys.argv[1:]:           # under rocprofv3 --kernel-trace --stats: the one call only, five times per row
+            track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, NCH).to_device()
+            for _ in range(5):
+                track.mix_at_many(evs)
+            N.sync()
+            print("%-34s traced   parity %s" % (name, "ok" if parity else "FAILED"), flush=True)
+            continue
+
+        def loop():
+            t = start.copy()
+            for seconds, other, volume, _o, speed in evs:
+                o = other if speed is None else other.copy().speed(speed)
+                t.mix_at(seconds, o if volume is None else o.at_volume(volume))
+
+        def many():
+            start.copy().mix_at_many(evs)
+
+        loop_ms = [median_wall(loop, 1, loop_passes), median_wall(loop, 0, loop_passes)]
+        many_ms = median_wall(many, 3, 9)
+        track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, NCH).to_device()
+        for _ in range(3):
+            track.mix_at_many(evs)
+        dev = []
+        for _ in range(9):
+            N.sync()
+            N.timer_start()
+            track.mix_at_many(evs)
+            dev.append(N.timer_stop())
+        dev_ms = sorted(dev)[len(dev) // 2]
+        print("%-34s loop %9.3f / %9.3f ms   mix_at_many %8.3f ms   ratio %6.1fx   device (in place) %7.4f ms   %.2f us per event   parity %s"
+              % (name, loop_ms[0], loop_ms[1], many_ms, min(loop_ms) / many_ms, dev_ms, 1e3 * dev_ms / len(evs), "ok" if parity else "FAILED"), flush=True)
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -152,4 +236,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sampler_main() if "--sampler" in sys.argv[1:] else main()
