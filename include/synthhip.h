@@ -489,6 +489,36 @@ typedef struct sh_mix_event_rate { /* all positions in SAMPLES unless named fram
 int sh_mix_events_rate(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_rate* events, uint32_t nevents,
                        int width, int nchannels, sh_buf* track, size_t track_samples);
 
+/* The same into a STEREO track, with a place in the stereo field per event: mono one-shots and mono recorded notes panned into a stereo
+ * master -- a drum machine, a tracker -- in one launch.
+ * Replaces: per note, Sample.copy().speed(s).pan(p) or .stereo(left, right) (upstream synthplayer/sample.py, [RECALL]:
+ * audioop.tostereo(frames, width, left, right) of the mono frames), .at_volume(v) and mix_at(...): six to eight launches and four
+ * allocations; or a stereo copy of the instrument per (instrument, speed, pan), which reads twice the source bytes per event.
+ * An event with src_channels == 1 contributes, in this order (none of the steps commute): audioop.ratecv of the MONO frames
+ * srcs[src][src_sample .. + src_frames) when inrate != outrate, audioop.tostereo of the result -- frame f becomes
+ * (fbound(s * left), fbound(s * right)), fbound: clamp, then floor -- its first nsamples STEREO samples, audioop.mul by factor, the
+ * saturating add.  Neither the resampled nor the stereo source is materialised: the lane that owns a track frame forms it from one
+ * (plain) or two (resampled) mono input frames.  An event with src_channels == 2 is an event of sh_mix_events_rate with nchannels == 2,
+ * left and right ignored; a list may hold both kinds, plain and resampled. */
+typedef struct sh_mix_event_pan {  /* all positions in SAMPLES unless named frames; a mono source's samples are its frames */
+    uint64_t dst_sample;           /* where in the track its first sample lands; mono source: even (a left sample) */
+    uint64_t src_sample;           /* first sample of the source buffer the event may read (resampled: input frame 0) */
+    uint64_t nsamples;             /* samples landing in the TRACK (mono source: two per source or resampled frame, so even); may be 0 */
+    uint64_t src_frames;           /* resampled: input frames the event may read from src_sample on */
+    double   factor;               /* audioop.mul factor, applied after tostereo; exactly 1.0 = none */
+    double   left, right;          /* mono source: audioop.tostereo's factors */
+    uint32_t src;                  /* index into srcs */
+    uint32_t inrate, outrate;      /* audioop.ratecv's; equal: a plain event */
+    uint32_t src_channels;         /* 1: a mono source through tostereo; 2: a stereo source, as sh_mix_events_rate has it */
+    uint32_t reserved;             /* 0 */
+} sh_mix_event_pan;                /* 80 bytes */
+/* The track is stereo.  SH_ERR_INVALID, and nothing launched, for everything sh_mix_events_rate refuses (nchannels = src_channels), and:
+ * src_channels other than 1 or 2; for a mono source a non-finite left or right, an odd dst_sample or nsamples, nsamples / 2 beyond the
+ * source's samples from src_sample on (plain) or beyond the sh_resample_out_frames(src_frames, inrate, outrate) frames that src_frames
+ * yield (resampled). */
+int sh_mix_events_pan(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_pan* events, uint32_t nevents,
+                      int width, sh_buf* track, size_t track_samples);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

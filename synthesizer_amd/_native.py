@@ -59,11 +59,14 @@ MIX_EVENT_DTYPE = np.dtype([("dst_sample", "<u8"), ("src_sample", "<u8"), ("nsam
                             ("src", "<u4"), ("reserved", "<u4")], align=True)          # sh_mix_event
 MIX_EVENT_RATE_DTYPE = np.dtype([("dst_sample", "<u8"), ("src_sample", "<u8"), ("nsamples", "<u8"), ("src_frames", "<u8"), ("factor", "<f8"),
                                  ("src", "<u4"), ("inrate", "<u4"), ("outrate", "<u4"), ("reserved", "<u4")], align=True)   # sh_mix_event_rate
+MIX_EVENT_PAN_DTYPE = np.dtype([("dst_sample", "<u8"), ("src_sample", "<u8"), ("nsamples", "<u8"), ("src_frames", "<u8"), ("factor", "<f8"),
+                                ("left", "<f8"), ("right", "<f8"), ("src", "<u4"), ("inrate", "<u4"), ("outrate", "<u4"),
+                                ("src_channels", "<u4"), ("reserved", "<u4")], align=True)                                   # sh_mix_event_pan
 
 # sizes the C side must agree with (checked against the library's view in tests via sh_bank_create)
 assert SEGMENT_DTYPE.itemsize == 24 and PARTIAL_DTYPE.itemsize == 16 and ENVELOPE_DTYPE.itemsize == 80
 assert VOICE_DTYPE.itemsize == 272, VOICE_DTYPE.itemsize
-assert MIX_EVENT_DTYPE.itemsize == 40 and MIX_EVENT_RATE_DTYPE.itemsize == 56
+assert MIX_EVENT_DTYPE.itemsize == 40 and MIX_EVENT_RATE_DTYPE.itemsize == 56 and MIX_EVENT_PAN_DTYPE.itemsize == 80
 
 
 class Counters(C.Structure):
@@ -139,6 +142,7 @@ _SIGNATURES = {
     "sh_mix_chain_gather": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_int, _P, C.c_size_t]),
     "sh_mix_events": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, C.c_int, _P, C.c_size_t]),
     "sh_mix_events_rate": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_size_t]),
+    "sh_mix_events_pan": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, C.c_int, _P, C.c_size_t]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),

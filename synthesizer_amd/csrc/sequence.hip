@@ -1,5 +1,5 @@
-// sequence.hip -- a list of placed samples mixed into a track in one launch (sh_mix_events, sh_mix_events_rate: Sample.mix_at_many,
-// mixer.sequence).
+// sequence.hip -- a list of placed samples mixed into a track in one launch (sh_mix_events, sh_mix_events_rate, sh_mix_events_pan:
+// Sample.mix_at_many, mixer.sequence).
 //
 // Per event audioop.mul (fbound: clamp, then floor) and audioop.add with saturation AT EVERY EVENT, IN LIST ORDER -- the loop of
 // Sample.mix_at calls it replaces, byte for byte.  The track is cut into tiles (seqplan.hpp); one workgroup per tile that some event
@@ -7,7 +7,8 @@
 // to the one store of the result.  Lanes own disjoint samples and read the track only there, so the fold is in place; a source may
 // not be the track.  sh_mix_events_rate: an event may play its source at another speed -- audioop.ratecv in front of the mul, output
 // frame m of the resampled source formed by whichever lane owns the track sample it lands on (ratecv.hpp: the position in closed form,
-// the sample arithmetic), never materialised.  Built with -ffp-contract=off (the float64 product of audioop.mul stays one rounding,
+// the sample arithmetic), never materialised.  sh_mix_events_pan: a mono source into a stereo track -- audioop.tostereo between the
+// ratecv and the mul, in the same lane.  Built with -ffp-contract=off (the float64 product of audioop.mul stays one rounding,
 // ratecv's prev*d + cur*(outr-d) two).
 #include "common.hpp"
 #include "chain.hpp"
@@ -345,9 +346,185 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_mix_events_rate_w(const S
         if (s0 + j < track_samples) chain_put<WIDTH>(track, s0 + j, acc[j]);
 }
 
+// ---- mono sources panned into a stereo track (sh_mix_events_pan) ------------------------------------------------------------------------
+// One event as these kernels read it: SeqEvR and audioop.tostereo's two factors, wave-uniform (scalar loads), 96 bytes.  r.nch is the
+// SOURCE's channel count.  2: an event of the kernels above, left and right unused.  1: r.dst and r.n count TRACK samples, both even --
+// track frame r.dst / 2 + f is frame f of the mono source (plain) or of audioop.ratecv(src, width, 1, inr, outr) (resampled) through
+// tostereo, (fbound(s * left), fbound(s * right)), then the mul and the add of every event: ratecv, tostereo, mul, add, in that order.
+struct SeqEvP {
+    SeqEvR   r;
+    double   left, right;
+    uint32_t pad[4];
+};
+static_assert(sizeof(SeqEvP) == 96, "SeqEvP is read as a 64-byte and a 32-byte scalar load");
+
+typedef short short4v __attribute__((ext_vector_type(4)));
+typedef short short4u __attribute__((ext_vector_type(4), aligned(2)));      // four samples at any sample offset
+typedef int int2v __attribute__((ext_vector_type(2)));
+
+// seq_load8 for a mono source: a lane's eight track samples are four stereo frames, so four source samples -- eight bytes, at
+// (src - 2 dstf) mod 8 against the lane's aligned eight (all lanes start on multiples of four track frames: uniform per event).
+// FUNNEL: one aligned 8-byte load, or two and the funnel shift; VEC2: one load at the odd address; the edges sample by sample.
+template <int SCHEME>
+__device__ __forceinline__ short4v seq_load4(gshort_p src, uint32_t dstf, uint32_t nf, uint32_t f0) {
+    const long long rel = (long long)f0 - (long long)dstf;
+    short4v x = {0, 0, 0, 0};
+    if (rel + 4 <= 0 || rel >= (long long)nf) return x;
+    if constexpr (SCHEME == VEC2) {
+        if (rel >= 0 && rel + 4 <= (long long)nf) return *(const SH_SEQ_GLOBAL short4u*)(src + rel);
+    } else {
+        const uint32_t sh = (uint32_t)(((uintptr_t)src - 2 * (uintptr_t)dstf) & 7);          // (uniform) 0, 2, 4, 6
+        if (sh == 0) {
+            if (rel >= 0 && rel + 4 <= (long long)nf) return *(const SH_SEQ_GLOBAL short4v*)(src + rel);
+        } else if (rel >= 4 && rel + 8 <= (long long)nf) {
+            const SH_SEQ_GLOBAL int2v* q = (const SH_SEQ_GLOBAL int2v*)((uintptr_t)(src + rel) - sh);
+            const int2v lo = q[0], hi = q[1];
+            const uint32_t r = sh & 3;
+            union { int2v v; short4v s; } o;
+            if (sh < 4) o.v = (int2v){(int)__builtin_amdgcn_alignbyte(lo[1], lo[0], r), (int)__builtin_amdgcn_alignbyte(hi[0], lo[1], r)};
+            else o.v = (int2v){(int)__builtin_amdgcn_alignbyte(hi[0], lo[1], r), (int)__builtin_amdgcn_alignbyte(hi[1], hi[0], r)};
+            return o.s;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (rel + j >= 0 && rel + j < (long long)nf) x[j] = src[rel + j];
+    return x;
+}
+
+// a resampled mono event in frames: seq_rate's record counts what it resamples
+__device__ __forceinline__ SeqEvR seq_mono_frames(const SeqEvR& r) {
+    SeqEvR f = r;
+    f.dst = r.dst >> 1;
+    f.n = r.n >> 1;
+    return f;
+}
+
+// k_mix_events_rate_i16 with mono sources beside stereo ones: the same tile, lane and fold, one record ahead.  A stereo event exactly
+// as there; a mono one fetches four frames -- seq_load4's vector loads (plain) or seq_rate with nch == 1 (resampled), half the source
+// bytes of a stereo event -- and makes them stereo in registers.  Zeros outside the event stay zeros: fbound(0 * factor) == 0.
+template <int SCHEME>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_mix_events_pan_i16(const SeqEvP* __restrict__ ev, const uint32_t* __restrict__ tiles,
+                                                                          const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
+                                                                          uint32_t ntiles, short* track, uint32_t track_samples, int aligned) {
+    const uint32_t k = (uint32_t)sh::block_id();
+    if (k >= ntiles) return;
+    const uint32_t s0 = tiles[k] * shq::TILE_I16 + threadIdx.x * shq::LANE_SAMPLES_I16;
+    if (s0 >= track_samples) return;
+    const bool whole = aligned && s0 + 8 <= track_samples;
+    short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (whole) acc = *reinterpret_cast<const short8v*>(track + s0);
+    else
+        for (uint32_t j = 0; j < 8 && s0 + j < track_samples; ++j) acc[j] = track[s0 + j];
+    uint32_t e = first[k];
+    const uint32_t e1 = first[k + 1];
+    SeqEvP nx = ev[idx[e]];                                   // (an active tile lists at least one event)
+    while (e < e1) {
+        const SeqEvP c = nx;
+        if (++e < e1) nx = ev[idx[e]];
+        gshort_p src = (gshort_p)c.r.src;
+        short8v x;
+        if (c.r.nch == 2) {                                   // (uniform, as every branch on the record)
+            if (c.r.inr == c.r.outr) {
+                x = seq_load8<SCHEME>(SeqEv{c.r.src, c.r.factor, c.r.dst, c.r.n, {0, 0}}, s0);
+            } else {
+                int v[8];
+                seq_rate<2, 8>(c.r, s0, [&](size_t i) { return (int)src[i]; }, v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) x[j] = (short)v[j];
+            }
+        } else {
+            short4v m;
+            if (c.r.inr == c.r.outr) {
+                m = seq_load4<SCHEME>(src, c.r.dst >> 1, c.r.n >> 1, s0 >> 1);
+            } else {
+                int v[4];
+                seq_rate<2, 4>(seq_mono_frames(c.r), s0 >> 1, [&](size_t i) { return (int)src[i]; }, v);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) m[j] = (short)v[j];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double s = (double)m[j];
+                x[2 * j] = (short)fbound(s * c.left, Lim<short>::lo, Lim<short>::hi);
+                x[2 * j + 1] = (short)fbound(s * c.right, Lim<short>::lo, Lim<short>::hi);
+            }
+        }
+        if (c.r.factor != 1.0) x = seq_mul8(x, c.r.factor);
+        acc = __builtin_elementwise_add_sat(acc, x);
+    }
+    if (whole) *reinterpret_cast<short8v*>(track + s0) = acc;
+    else
+        for (uint32_t j = 0; j < 8 && s0 + j < track_samples; ++j) track[s0 + j] = acc[j];
+}
+
+// k_mix_events_rate_w with mono sources beside stereo ones (widths 1, 3, 4): a thread's four track samples are two stereo frames.
+template <int WIDTH>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_mix_events_pan_w(const SeqEvP* __restrict__ ev, const uint32_t* __restrict__ tiles,
+                                                                        const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
+                                                                        uint32_t ntiles, unsigned char* track, uint32_t track_samples) {
+    const uint32_t k = (uint32_t)sh::block_id();
+    if (k >= ntiles) return;
+    const uint32_t s0 = tiles[k] * shq::TILE_W + threadIdx.x * shq::LANE_SAMPLES_W;
+    if (s0 >= track_samples) return;
+    constexpr long long HI = WIDTH == 1 ? 127LL : (WIDTH == 3 ? 8388607LL : 2147483647LL), LO = -HI - 1;
+    long long acc[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (s0 + j < track_samples) acc[j] = chain_get<WIDTH>(track, s0 + j);
+    const uint32_t e1 = first[k + 1];
+    for (uint32_t e = first[k]; e < e1; ++e) {
+        const SeqEvP c = ev[idx[e]];
+        gbyte_p src = (gbyte_p)c.r.src;
+        int v[4] = {0, 0, 0, 0};
+        bool in[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long rel = (long long)s0 + j - (long long)c.r.dst;
+            in[j] = rel >= 0 && rel < (long long)c.r.n;
+        }
+        if (c.r.nch == 2) {                                   // (uniform, as every branch on the record)
+            if (c.r.inr == c.r.outr) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (in[j]) v[j] = seq_get<WIDTH>(src, (size_t)((long long)s0 + j - (long long)c.r.dst));
+            } else {
+                seq_rate<WIDTH, 4>(c.r, s0, [&](size_t i) { return seq_get<WIDTH>(src, i); }, v);
+            }
+        } else {
+            int m[2] = {0, 0};
+            if (c.r.inr == c.r.outr) {
+#pragma unroll
+                for (int f = 0; f < 2; ++f)                   // (dst, n and s0 are even: a frame is inside the event or outside it)
+                    if (in[2 * f]) m[f] = seq_get<WIDTH>(src, (size_t)((long long)(s0 >> 1) + f - (long long)(c.r.dst >> 1)));
+            } else {
+                seq_rate<WIDTH, 2>(seq_mono_frames(c.r), s0 >> 1, [&](size_t i) { return seq_get<WIDTH>(src, i); }, m);
+            }
+#pragma unroll
+            for (int f = 0; f < 2; ++f) {
+                const double s = (double)m[f];
+                v[2 * f] = fbound(s * c.left, (double)LO, (double)HI);
+                v[2 * f + 1] = fbound(s * c.right, (double)LO, (double)HI);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (in[j]) {
+                long long x = v[j];
+                if (c.r.factor != 1.0) x = fbound((double)x * c.r.factor, (double)LO, (double)HI);
+                const long long t = acc[j] + x;
+                acc[j] = t > HI ? HI : (t < LO ? LO : t);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (s0 + j < track_samples) chain_put<WIDTH>(track, s0 + j, acc[j]);
+}
+
 }  // namespace
 
-// ---- host: what the two entry points share ----------------------------------------------------------------------------------------------
+// ---- host: what the entry points share ----------------------------------------------------------------------------------------------
 namespace {
 
 // the arguments in front of the events: width, pointers, the track's range, no source that is (or overlaps) the track
@@ -494,6 +671,64 @@ int sh_mix_events_rate(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_ev
             else if (width == 1) hipLaunchKernelGGL(k_mix_events_rate_w<1>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
             else if (width == 3) hipLaunchKernelGGL(k_mix_events_rate_w<3>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
             else hipLaunchKernelGGL(k_mix_events_rate_w<4>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
+        });
+}
+
+int sh_mix_events_pan(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_pan* events, uint32_t nevents, int width, sh_buf* track,
+                      size_t track_samples) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_mix_events_pan";
+    int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    if (rc) return rc;
+    const size_t w = (size_t)width;
+    std::vector<shq::Event> pe(nevents);
+    for (uint32_t e = 0; e < nevents; ++e) {
+        const sh_mix_event_pan& m = events[e];
+        if ((rc = seq_check_event(fn, m, e, srcs, nsrc))) return rc;
+        if (m.src_channels != 1 && m.src_channels != 2) return sh::set_error(SH_ERR_INVALID, "%s: event %u: src_channels %u not 1 or 2", fn, e, m.src_channels);
+        if (!m.inrate || !m.outrate || m.inrate >= (1u << 31) || m.outrate >= (1u << 31))
+            return sh::set_error(SH_ERR_INVALID, "%s: event %u: sampling rate not in [1, 2^31)", fn, e);
+        const uint64_t nch = m.src_channels, have = srcs[m.src]->bytes / w;
+        uint64_t nsrc_samples = m.nsamples;                   // what the event takes of its (resampled) source
+        if (nch == 1) {
+            if (!isfinite(m.left) || !isfinite(m.right)) return sh::set_error(SH_ERR_INVALID, "%s: event %u: left / right is not finite", fn, e);
+            if (m.dst_sample % 2 || m.nsamples % 2)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: a mono source starts and ends on whole stereo frames", fn, e);
+            nsrc_samples = m.nsamples / 2;
+        }
+        if (m.src_sample > have) return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside its source", fn, e);
+        if (m.inrate == m.outrate) {
+            if (nsrc_samples > have - m.src_sample) return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside its source", fn, e);
+        } else {
+            if (m.src_sample % nch || nsrc_samples % nch)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: a resampled event starts and ends on whole frames", fn, e);
+            if (m.src_frames > (have - m.src_sample) / nch) return sh::set_error(SH_ERR_INVALID, "%s: event %u: src_frames outside its source", fn, e);
+            if (nsrc_samples / nch > shr::out_frames(m.src_frames, shr::reduce(m.inrate, m.outrate)))
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: more samples than src_frames resample to", fn, e);
+        }
+        pe[e] = shq::Event{m.dst_sample, m.nsamples};
+    }
+    const uint32_t ns = (uint32_t)track_samples;
+    return seq_run<SeqEvP>(fn, pe, width, track_samples,
+        [&](SeqEvP* rec) {
+            for (uint32_t e = 0; e < nevents; ++e) {
+                const sh_mix_event_pan& m = events[e];
+                const shr::Rates R = shr::reduce(m.inrate, m.outrate);
+                rec[e] = SeqEvP{SeqEvR{(const char*)srcs[m.src]->ptr + m.src_sample * w, m.factor, 1.0 / (double)R.outr, (uint32_t)m.dst_sample,
+                                       (uint32_t)m.nsamples, R.inr, R.outr, R.inr / R.outr, R.inr % R.outr, m.src_channels,
+                                       width <= 2 && R.outr < 65536u ? 1u : 0u, {0, 0}},
+                                m.left, m.right, {0, 0, 0, 0}};
+            }
+        },
+        [&](const SeqEvP* d_ev, const uint32_t* d_tiles, const uint32_t* d_first, const uint32_t* d_idx, uint32_t nt, dim3 grid, dim3 block, hipStream_t st) {
+            if (width == 2) {
+                const int aligned = ((uintptr_t)track->ptr & 15) == 0;
+                if (sh::knobs().seq_align == VEC2) hipLaunchKernelGGL(k_mix_events_pan_i16<VEC2>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (short*)track->ptr, ns, aligned);
+                else hipLaunchKernelGGL(k_mix_events_pan_i16<FUNNEL>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (short*)track->ptr, ns, aligned);
+            }
+            else if (width == 1) hipLaunchKernelGGL(k_mix_events_pan_w<1>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
+            else if (width == 3) hipLaunchKernelGGL(k_mix_events_pan_w<3>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
+            else hipLaunchKernelGGL(k_mix_events_pan_w<4>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
         });
 }
 

@@ -561,22 +561,30 @@ class Sample:
 
     def mix_at_many(self, events: Iterable[tuple]) -> "Sample":
         """Mix a list of placed samples into this one: ``events`` holds ``(seconds, other, volume=None, other_seconds=None,
-        speed=None)``, and the result is, byte for byte, what ::
+        speed=None, pan=None)``, and the result is, byte for byte, what ::
 
-            for seconds, other, volume, other_seconds, speed in events:
+            for seconds, other, volume, other_seconds, speed, pan in events:
                 o = other
                 if speed is not None:
                     o = o.copy().speed(speed)           # audioop.ratecv(frames, width, nchannels, int(rate * speed), rate, None)
+                if pan is not None:
+                    o = o.copy().stereo(left, right)    # audioop.tostereo of the (resampled) MONO frames
                 if volume is not None:
-                    o = o.at_volume(volume)             # audioop.mul, after the resample
-                self.mix_at(seconds, o, other_seconds)  # other_seconds cuts the resampled sample
+                    o = o.at_volume(volume)             # audioop.mul, after the resample and tostereo
+                self.mix_at(seconds, o, other_seconds)  # other_seconds cuts the resampled (stereo) sample
 
-        leaves -- ``audioop.ratecv`` and ``audioop.mul`` per event, ``audioop.add`` with saturation at every event, in list order, the
-        track grown to the furthest end -- in one launch (sh_mix_events; sh_mix_events_rate when an event has a speed: a sampler, one
-        recorded note at many pitches) and with at most one allocation (none when nothing grows).  A speed of None or 1.0, or one with
-        ``int(rate * speed) == rate``, is none.  Negative times, non-finite volumes and a speed that is not finite or outside
-        0.1 .. 10 are a ValueError, raised before anything is mixed.  An event whose ``other`` is this sample reads it as the events
-        before it left it: the list is cut there, and that one event goes through the loop's body above."""
+        leaves -- ``audioop.ratecv``, ``audioop.tostereo`` and ``audioop.mul`` per event, in that order, ``audioop.add`` with saturation
+        at every event, in list order, the track grown to the furthest end -- in one launch (sh_mix_events; sh_mix_events_rate when an
+        event has a speed: a sampler, one recorded note at many pitches; sh_mix_events_pan when one has a pan: mono instruments placed
+        in the stereo field of a stereo track, beside stereo ones) and with at most one allocation (none when nothing grows).  A speed
+        of None or 1.0, or one with ``int(rate * speed) == rate``, is none.  ``pan`` is a float -1 .. 1, ``(left, right)`` =
+        ``((1 - pan) / 2, (1 + pan) / 2)`` as ``Sample.pan`` has them, or the pair ``(left_factor, right_factor)`` of ``Sample.stereo``
+        itself (a 0 on one side: ``stereo_mix``'s "into the left / right channel only"); it needs a mono ``other`` and a stereo track.
+        A ValueError, raised before anything is mixed: negative times, non-finite volumes, a speed that is not finite or outside
+        0.1 .. 10; a pan on a stereo ``other`` or into a track that is not stereo, a pan outside -1 .. 1, a pair of another length
+        than two, a factor that is not finite.  A mono ``other`` without a pan in a stereo track fails the assertion of ``mix_at``.
+        An event whose ``other`` is this sample reads it as the events before it left it: the list is cut there, and that one event
+        goes through the loop's body above."""
         self._check_writable()
         self._check_gpu_width("mix_at")
         fb = self.__samplewidth * self.__nchannels
@@ -587,9 +595,27 @@ class Sample:
             volume = ev[2] if len(ev) > 2 else None
             other_seconds = ev[3] if len(ev) > 3 else None
             speed = ev[4] if len(ev) > 4 else None
+            pan = ev[5] if len(ev) > 5 else None
             assert self.samplewidth == other.samplewidth
             assert self.samplerate == other.samplerate
-            assert self.nchannels == other.nchannels
+            factors = None                                                      # audioop.tostereo's, of a panned event
+            if pan is None:
+                assert self.nchannels == other.nchannels
+            else:
+                if other.nchannels != 1:
+                    raise ValueError("mix_at_many: pan needs a mono sample, this one has %d channels" % other.nchannels)
+                if self.__nchannels != 2:
+                    raise ValueError("mix_at_many: pan needs a stereo track, this one has %d channels" % self.__nchannels)
+                if isinstance(pan, (tuple, list)):
+                    if len(pan) != 2:
+                        raise ValueError("mix_at_many: pan is a number or a pair (left_factor, right_factor)")
+                    factors = (float(pan[0]), float(pan[1]))
+                else:
+                    if not -1.0 <= pan <= 1.0:
+                        raise ValueError("mix_at_many: pan must be between -1 and 1")
+                    factors = ((1.0 - pan) / 2.0, (1.0 + pan) / 2.0)            # Sample.pan: Python floats, on the host
+                if not (math.isfinite(factors[0]) and math.isfinite(factors[1])):
+                    raise ValueError("mix_at_many: pan factor is not finite")
             if seconds < 0 or (other_seconds is not None and other_seconds < 0):
                 raise ValueError("mix_at_many: negative time")
             if volume is not None and not math.isfinite(volume):
@@ -602,29 +628,31 @@ class Sample:
                 if inrate <= 0:
                     raise ValueError("mix_at_many: speed %r leaves no sample rate" % (speed,))
             start = fb * int(rate * seconds)                                    # frame_idx(seconds): Python floats, on the host
-            have = other.__nbytes if inrate == rate else fb * _ratecv_out_frames(other.__nbytes // fb, inrate, rate)
-            n2 = other.frame_idx(other_seconds) if other_seconds else have
-            todo.append((seconds, other, volume, other_seconds, speed, start, min(n2, have), inrate))
+            frames = other.__nbytes // (self.__samplewidth * other.nchannels)   # (a panned event: the mono frames, a track frame each)
+            have = fb * (frames if inrate == rate else _ratecv_out_frames(frames, inrate, rate))
+            n2 = fb * int(rate * other_seconds) if other_seconds else have     # frame_idx(other_seconds) of what mix_at is handed
+            todo.append((seconds, other, volume, other_seconds, speed, start, min(n2, have), inrate, factors))
         batch = []
-        for seconds, other, volume, other_seconds, speed, start, n2, inrate in todo:
-            if other is self:
+        for seconds, other, volume, other_seconds, speed, start, n2, inrate, factors in todo:
+            if other is self:                                                   # (never panned: a panned event's other is mono, its track stereo)
                 self.__mix_events(batch)
                 batch = []
                 if inrate != rate:
                     other = other.copy().speed(speed)
                 self.mix_at(seconds, other if volume is None else other.at_volume(volume), other_seconds)
             else:
-                batch.append((start, other, n2, 1.0 if volume is None else float(volume), inrate))
+                batch.append((start, other, n2, 1.0 if volume is None else float(volume), inrate, factors))
         self.__mix_events(batch)
         return self
 
     def __mix_events(self, batch: Sequence[tuple]) -> None:
-        """The events (first byte, other, bytes, factor, inrate) -- none of them this sample -- folded in order; length -> the furthest
-        end.  inrate != the sample rate: the event plays ``other`` resampled from inrate to the sample rate, and bytes counts
-        resampled bytes.  The table is packed column by column (whole-array numpy operations, not a row per event)."""
+        """The events (first byte, other, bytes, factor, inrate, tostereo factors | None) -- none of them this sample -- folded in
+        order; length -> the furthest end.  inrate != the sample rate: the event plays ``other`` resampled from inrate to the sample
+        rate, and bytes counts resampled bytes; tostereo factors: ``other`` is mono, the track stereo, and bytes counts stereo bytes.
+        The table is packed column by column (whole-array numpy operations, not a row per event)."""
         if not batch:
             return
-        starts, others, nbytes, factors, inrates = zip(*batch)
+        starts, others, nbytes, factors, inrates, pans = zip(*batch)
         w = self.__samplewidth
         rate = self.__samplerate
         starts = np.array(starts, dtype=np.uint64)
@@ -650,16 +678,24 @@ class Sample:
         srcs = (C.c_void_p * len(bufs))(*[b.handle for b in bufs])
         src = np.fromiter((slot[id(o)][0] for o in others), dtype=np.uint32, count=len(others))
         rated = bool((inrates != rate).any())
-        table = np.zeros(len(batch), dtype=N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
+        panned = any(p is not None for p in pans)
+        table = np.zeros(len(batch), dtype=N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
         table["dst_sample"] = starts // w
         table["nsamples"] = nbytes // w
         table["factor"] = factors
         table["src"] = src
-        if rated:
-            frames = np.array([o.__nbytes for o in uniq], dtype=np.uint64) // (w * self.__nchannels)
+        if rated or panned:
+            frames = np.array([o.__nbytes // (w * o.nchannels) for o in uniq], dtype=np.uint64)
             table["src_frames"] = frames[src]
             table["inrate"] = inrates
             table["outrate"] = rate
+        if panned:
+            table["src_channels"] = np.array([o.nchannels for o in uniq], dtype=np.uint32)[src]
+            lr = np.array([p if p is not None else (0.0, 0.0) for p in pans], dtype=np.float64)
+            table["left"] = lr[:, 0]
+            table["right"] = lr[:, 1]
+            N.check(N.lib().sh_mix_events_pan(srcs, len(bufs), table.ctypes.data, len(table), w, track.handle, total // w))
+        elif rated:
             N.check(N.lib().sh_mix_events_rate(srcs, len(bufs), table.ctypes.data, len(table), w, self.__nchannels, track.handle, total // w))
         else:
             N.check(N.lib().sh_mix_events(srcs, len(bufs), table.ctypes.data, len(table), w, track.handle, total // w))

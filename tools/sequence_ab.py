@@ -13,7 +13,14 @@ SYNTHHIP_SEQ_ALIGN=1: the 16-bit kernel's other way of reading misaligned event 
 k in [-12, 12], a quarter of them plain; the same song all downward (speed <= 1) and all upward (speed >= 2); a chord (one 1-s
 instrument, 64 notes at one start).  The loop is copy().speed().at_volume() + mix_at per event, timed TWICE (its run-to-run spread is the
 yardstick for "not slower"); live audioop.ratecv / mul / add is the check.  --sampler --trace: each row's one call five times and nothing
-else, for rocprofv3 --kernel-trace --stats."""
+else, for rocprofv3 --kernel-trace --stats.
+
+--pan: a stereo sampler song (sh_mix_events_pan) -- the 120-s song with 4096 / 32 768 events, MONO instruments, each event at 2^(k/12)
+(a quarter plain) and at its own place in the stereo field (floats and factor pairs).  Three forms of the same bytes, checked against
+live audioop.ratecv / tostereo / mul / add: (a) one mix_at_many with pans; (b) the loop of copy().speed().stereo() / at_volume / mix_at
+it replaces; (c) what there was before pans: a stereo copy of the instrument per distinct (instrument, speed, pan), made once, then
+one mix_at_many of plain stereo events -- with the time to make the copies and the device bytes they take.  --pan --trace: (a)'s and (c)'s
+one call five times each, for rocprofv3 --kernel-trace."""
 import audioop
 import os
 import sys
@@ -166,6 +173,109 @@ def sampler_main():
               % (name, loop_ms[0], loop_ms[1], many_ms, min(loop_ms) / many_ms, dev_ms, 1e3 * dev_ms / len(evs), "ok" if parity else "FAILED"), flush=True)
 
 
+PANS = [0.0, -1.0, 0.3, (1.0, 0.0), (-0.5, 0.8), (1.5, 1.2), 1.0, (0.0, 0.7), -0.65, (0.4, -1.0), (2.0, 0.25), (1.0, 1.0)]
+
+
+def pan_factors(pan):
+    return (float(pan[0]), float(pan[1])) if isinstance(pan, tuple) else ((1.0 - pan) / 2.0, (1.0 + pan) / 2.0)
+
+
+def pan_song(nevents, span):
+    """sampler_song with the left channel of its instruments as mono instruments and a pan per event"""
+    _base, inst, events = sampler_song(nevents, span)
+    mono = [np.frombuffer(b, dtype="<i2")[0::2].tobytes() for b in inst]
+    return mono, [(s, i, v, sp, PANS[n % len(PANS)]) for n, (s, i, v, sp) in enumerate(events)]
+
+
+def pan_oracle(sources, events):
+    t = bytearray()
+    for seconds, i, volume, speed, pan in events:
+        frames = sources[i]
+        if speed is not None and int(RATE * speed) != RATE:
+            frames = audioop.ratecv(frames, WIDTH, 1, int(RATE * speed), RATE, None)[0]
+        frames = audioop.tostereo(frames, WIDTH, *pan_factors(pan))
+        if volume is not None:
+            frames = audioop.mul(frames, WIDTH, volume)
+        start = 2 * WIDTH * int(RATE * seconds)
+        end = start + len(frames)
+        if end > len(t):
+            t.extend(bytes(end - len(t)))
+        t[start:end] = audioop.add(bytes(t[start:end]), frames, WIDTH)
+    return bytes(t)
+
+
+def pan_main():
+    N.ensure_init(0)
+    print("sequence_pan_ab: SYNTHHIP_SEQ_ALIGN=%s  %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), N.device_info()["name"]), flush=True)
+    for nevents, loop_passes in ((4096, 3), (32768, 1)):
+        sources, events = pan_song(nevents, 120.0)
+        samples = [Sample.from_raw_frames(b, WIDTH, RATE, 1).to_device() for b in sources]
+        evs = [(s, samples[i], v, None, sp, p) for s, i, v, sp, p in events]
+        want = pan_oracle(sources, events)
+
+        def empty():
+            return Sample(samplerate=RATE, nchannels=2, samplewidth=WIDTH)
+
+        def many():                                         # (a)
+            return empty().mix_at_many(evs)
+
+        def loop():                                         # (b)
+            t = empty()
+            for seconds, other, volume, _o, speed, pan in evs:
+                o = other if speed is None else other.copy().speed(speed)
+                o = o.copy().stereo(*pan_factors(pan))
+                t.mix_at(seconds, o if volume is None else o.at_volume(volume))
+            return t
+
+        def materialise():                                  # (c), first half: one stereo copy per distinct (instrument, speed, pan)
+            made = {}
+            for _s, i, _v, sp, p in events:
+                if (i, sp, p) not in made:
+                    o = samples[i] if sp is None else samples[i].copy().speed(sp)
+                    made[(i, sp, p)] = o.copy().stereo(*pan_factors(p))
+            return made
+
+        def materialised():                                 # (c)
+            made = materialise()
+            return empty().mix_at_many([(s, made[(i, sp, p)], v) for s, i, v, sp, p in events])
+
+        if "--trace" in sys.argv[1:]:           # under rocprofv3 --kernel-trace: (a)'s one call, then (c)'s, five times each and nothing else
+            made = materialise()
+            stereo_evs = [(s, made[(i, sp, p)], v) for s, i, v, sp, p in events]
+            for lst in (evs, stereo_evs):
+                track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, 2).to_device()
+                for _ in range(5):
+                    track.mix_at_many(lst)
+                N.sync()
+            print("pan song 120 s, %5d events   traced" % nevents, flush=True)
+            continue
+        parity = [bytes(f().view_frame_data()) == want for f in (many, loop, materialised)]
+        made = materialise()
+        extra = sum(len(o) * 2 * WIDTH for o in made.values())
+        stereo_evs = [(s, made[(i, sp, p)], v) for s, i, v, sp, p in events]
+        many_ms = median_wall(many, 3, 9)
+        loop_ms = median_wall(loop, 0, loop_passes)
+        mat_ms = median_wall(materialised, 1, 5)
+        mat_only_ms = median_wall(materialise, 1, 5)
+        mat_mix_ms = median_wall(lambda: empty().mix_at_many(stereo_evs), 3, 9)
+        dev = {}
+        for name, lst in (("a", evs), ("c", stereo_evs)):  # the one call on a track that is long enough: device time (table copy + kernel)
+            track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, 2).to_device()
+            for _ in range(3):
+                track.mix_at_many(lst)
+            runs = []
+            for _ in range(9):
+                N.sync()
+                N.timer_start()
+                track.mix_at_many(lst)
+                runs.append(N.timer_stop())
+            dev[name] = sorted(runs)[len(runs) // 2]
+        print("pan song 120 s, %5d events   (a) mix_at_many with pans %9.3f ms   (b) loop %10.3f ms   (c) stereo copies + mix_at_many %9.3f ms "
+              "(= %d copies %.3f ms, %.1f MB extra on the device, + the one call %.3f ms)   a/c %.2fx   b/a %.1fx   device, in place: (a) %.4f ms  (c) %.4f ms   "
+              "parity a, b, c: %s" % (nevents, many_ms, loop_ms, mat_ms, len(made), mat_only_ms, extra / 1e6, mat_mix_ms, mat_ms / many_ms, loop_ms / many_ms,
+                                      dev["a"], dev["c"], " ".join("ok" if x else "FAILED" for x in parity)), flush=True)
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -236,4 +346,4 @@ def main():
 
 
 if __name__ == "__main__":
-    sampler_main() if "--sampler" in sys.argv[1:] else main()
+    pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
