@@ -519,6 +519,52 @@ typedef struct sh_mix_event_pan {  /* all positions in SAMPLES unless named fram
 int sh_mix_events_pan(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_pan* events, uint32_t nevents,
                       int width, sh_buf* track, size_t track_samples);
 
+/* The same with an ADSR envelope per event: a recorded or looped instrument played at a chosen length gets an attack and a release --
+ * shaped notes, one launch per track.
+ * Replaces: per note, Sample.copy().speed(s), .clip(0, length), .envelope(attack, decay, sustainlevel, release) (upstream
+ * synthplayer/sample.py, [RECALL]: split, audioop.mul of the sustain and release parts, fadein / fadeout -- int(x * f) per sample
+ * through array -- and join), .stereo(left, right), .at_volume(v) and mix_at(...): some fifteen launches and ten allocations.
+ * An event with seg_count > 0 is shaped after the ratecv and the cut and BEFORE tostereo and the mul: source sample p of the event (the
+ * p-th sample it takes of its plain or resampled source; a mono source of a stereo track: its p-th frame) lies in the first of its
+ * segments segments[seg_first .. + seg_count) whose end is > p and becomes
+ *     x = fbound(x * mul)                                        unless mul == 1.0       (audioop.mul: clamp, then floor)
+ *     x = trunc(x * (1.0 - (p - origin) * slope / numsamples))   kind 2, a fade-out      (float64, in this order, each step rounded)
+ *     x = trunc(x * ((p - origin) * slope / numsamples + offset)) kind 1, a fade-in
+ * and stays as it is past the last end.  The caller replays Sample.envelope's boundaries; nothing is materialised.  src_channels is the
+ * source's channel count: nchannels, the track's -- an event of sh_mix_events_rate -- or 1 with nchannels == 2 -- a mono source through
+ * tostereo, as sh_mix_events_pan has it.  An event with seg_count == 0 has no envelope; a list may hold every kind. */
+typedef struct sh_env_segment {    /* positions in the event's source samples */
+    uint64_t end;                  /* the segment is [the end of the one before it (0 for the first), end) */
+    uint64_t origin;               /* where a ramp's k == 0 */
+    double   mul;                  /* audioop.mul factor before the ramp; exactly 1.0 = none */
+    double   slope;                /* a ramp's: fade-in 1 - start volume, fade-out 1 - target volume */
+    double   numsamples;           /* a ramp's: samples of the whole faded stretch, > 0 */
+    double   offset;               /* a fade-in's start volume */
+    uint32_t kind;                 /* 0: no ramp, 1: fade-in, 2: fade-out */
+    uint32_t reserved;             /* 0 */
+} sh_env_segment;                  /* 56 bytes */
+typedef struct sh_mix_event_env {  /* sh_mix_event_pan's fields, then the segments */
+    uint64_t dst_sample;
+    uint64_t src_sample;
+    uint64_t nsamples;
+    uint64_t src_frames;
+    double   factor;
+    double   left, right;
+    uint32_t src;
+    uint32_t inrate, outrate;
+    uint32_t src_channels;         /* nchannels, or 1 into a stereo track: through tostereo */
+    uint32_t seg_first;            /* index into segments */
+    uint32_t seg_count;            /* 0: no envelope; at most 7 */
+    uint32_t reserved;             /* 0 */
+} sh_mix_event_env;                /* 88 bytes */
+/* SH_ERR_INVALID, the event named and nothing launched, for everything sh_mix_events_pan refuses (sh_mix_events_rate for src_channels ==
+ * nchannels), and: a width other than 1, 2 or 4 (upstream's fades have no 24-bit form), src_channels that is neither nchannels nor 1
+ * into a stereo track, more than 7 segments, segments outside the table, ends that descend or lie beyond the event's source samples
+ * (nsamples; a mono source of a stereo track: nsamples / 2), an origin beyond them, a kind other than 0 - 2, a non-finite mul, slope,
+ * numsamples or offset, a ramp with numsamples <= 0, reserved != 0 in an event or a segment it names. */
+int sh_mix_events_env(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_env* events, uint32_t nevents,
+                      const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

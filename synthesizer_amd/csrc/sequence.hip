@@ -1,5 +1,5 @@
-// sequence.hip -- a list of placed samples mixed into a track in one launch (sh_mix_events, sh_mix_events_rate, sh_mix_events_pan:
-// Sample.mix_at_many, mixer.sequence).
+// sequence.hip -- a list of placed samples mixed into a track in one launch (sh_mix_events, sh_mix_events_rate, sh_mix_events_pan,
+// sh_mix_events_env: Sample.mix_at_many, mixer.sequence).
 //
 // Per event audioop.mul (fbound: clamp, then floor) and audioop.add with saturation AT EVERY EVENT, IN LIST ORDER -- the loop of
 // Sample.mix_at calls it replaces, byte for byte.  The track is cut into tiles (seqplan.hpp); one workgroup per tile that some event
@@ -8,12 +8,14 @@
 // not be the track.  sh_mix_events_rate: an event may play its source at another speed -- audioop.ratecv in front of the mul, output
 // frame m of the resampled source formed by whichever lane owns the track sample it lands on (ratecv.hpp: the position in closed form,
 // the sample arithmetic), never materialised.  sh_mix_events_pan: a mono source into a stereo track -- audioop.tostereo between the
-// ratecv and the mul, in the same lane.  Built with -ffp-contract=off (the float64 product of audioop.mul stays one rounding,
+// ratecv and the mul, in the same lane.  sh_mix_events_env: an ADSR envelope per event -- Sample.envelope's
+// gain (seqenv.hpp) on the (resampled, cut) source samples, between the ratecv and the tostereo.  Built with -ffp-contract=off (the float64 product of audioop.mul stays one rounding,
 // ratecv's prev*d + cur*(outr-d) two).
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
 #include "ratecv.hpp"
+#include "seqenv.hpp"
 #include "seqplan.hpp"
 #include <math.h>
 #include <string.h>
@@ -522,6 +524,173 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_mix_events_pan_w(const Se
         if (s0 + j < track_samples) chain_put<WIDTH>(track, s0 + j, acc[j]);
 }
 
+// ---- an ADSR envelope per event (sh_mix_events_env) -------------------------------------------------------------------------------------
+// One event as these kernels read it: SeqEvP with its padding put to use, wave-uniform (scalar loads), 96 bytes.  r.nch is the SOURCE's
+// channel count.  tostereo == 0: an event of the rate kernels (any channel count, the track's).  tostereo == 1: a mono source into a
+// stereo track, as SeqEvP's.  nseg > 0: segs[seg0 .. seg0 + nseg) (she::Seg, seqenv.hpp) shape the event's source samples -- the samples
+// of the mono frames for a tostereo event -- after the load or the ratecv and before tostereo and the mul: ratecv, the cut, the
+// envelope, tostereo, mul, add, in that order.
+struct SeqEvE {
+    SeqEvR   r;
+    double   left, right;
+    uint32_t seg0, nseg;
+    uint32_t tostereo;
+    uint32_t pad;
+};
+static_assert(sizeof(SeqEvE) == 96, "SeqEvE is read as a 64-byte and a 32-byte scalar load");
+
+// What the tile [t0, t0 + tile) of the track takes of an event, in the event's source samples (sh = 1: a tostereo event, whose source
+// samples are track frames; dst, n, t0 and tile are even then): [tlo, thi), uniform.  The tile lists the event, so they overlap.
+__device__ __forceinline__ void seq_env_span(const SeqEvE& c, uint32_t t0, uint32_t tile, uint32_t& tlo, uint32_t& thi) {
+    const uint32_t sh = c.tostereo, d = c.r.dst >> sh, n = c.r.n >> sh, a = t0 >> sh, b = a + (tile >> sh);       // (no wrap: MAX_TRACK_SAMPLES)
+    tlo = a > d ? a - d : 0u;
+    thi = (b < d + n ? b : d + n) - d;
+}
+
+// k_mix_events_pan_i16 with an envelope per event: the same tile, lane ownership, accumulator in registers and one record ahead.  An
+// event without an envelope takes the paths of that kernel behind a uniform branch (nseg == 0); an enveloped one shapes the lane's eight
+// source samples (four mono frames for a tostereo event) with she::shape_lane -- float64 per sample only inside a ramp, one fbound
+// multiply inside the sustain, nothing inside a plain stretch, a per-sample select only in a tile that straddles a boundary.
+template <int SCHEME>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_mix_events_env_i16(const SeqEvE* __restrict__ ev, const she::Seg* __restrict__ segs,
+                                                                          const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ first,
+                                                                          const uint32_t* __restrict__ idx, uint32_t ntiles, short* track,
+                                                                          uint32_t track_samples, int aligned) {
+    const uint32_t k = (uint32_t)sh::block_id();
+    if (k >= ntiles) return;
+    const uint32_t t0 = tiles[k] * shq::TILE_I16;
+    const uint32_t s0 = t0 + threadIdx.x * shq::LANE_SAMPLES_I16;
+    if (s0 >= track_samples) return;
+    const bool whole = aligned && s0 + 8 <= track_samples;
+    short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (whole) acc = *reinterpret_cast<const short8v*>(track + s0);
+    else
+        for (uint32_t j = 0; j < 8 && s0 + j < track_samples; ++j) acc[j] = track[s0 + j];
+    uint32_t e = first[k];
+    const uint32_t e1 = first[k + 1];
+    SeqEvE nx = ev[idx[e]];                                   // (an active tile lists at least one event)
+    while (e < e1) {
+        const SeqEvE c = nx;
+        if (++e < e1) nx = ev[idx[e]];
+        gshort_p src = (gshort_p)c.r.src;
+        uint32_t tlo = 0, thi = 0;
+        if (c.nseg) seq_env_span(c, t0, shq::TILE_I16, tlo, thi);      // (uniform, as every branch on the record)
+        short8v x;
+        if (!c.tostereo) {
+            if (c.r.inr == c.r.outr) {
+                x = seq_load8<SCHEME>(SeqEv{c.r.src, c.r.factor, c.r.dst, c.r.n, {0, 0}}, s0);
+                if (c.nseg) {
+                    int v[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = (int)x[j];
+                    she::shape_lane<8>(segs + c.seg0, c.nseg, tlo, thi, (long long)s0 - (long long)c.r.dst, v, Lim<short>::lo, Lim<short>::hi);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) x[j] = (short)v[j];
+                }
+            } else {
+                int v[8];
+                seq_rate<2, 8>(c.r, s0, [&](size_t i) { return (int)src[i]; }, v);
+                if (c.nseg) she::shape_lane<8>(segs + c.seg0, c.nseg, tlo, thi, (long long)s0 - (long long)c.r.dst, v, Lim<short>::lo, Lim<short>::hi);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) x[j] = (short)v[j];
+            }
+        } else {
+            int v[4];
+            if (c.r.inr == c.r.outr) {
+                const short4v m = seq_load4<SCHEME>(src, c.r.dst >> 1, c.r.n >> 1, s0 >> 1);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = (int)m[j];
+            } else {
+                seq_rate<2, 4>(seq_mono_frames(c.r), s0 >> 1, [&](size_t i) { return (int)src[i]; }, v);
+            }
+            if (c.nseg) she::shape_lane<4>(segs + c.seg0, c.nseg, tlo, thi, (long long)(s0 >> 1) - (long long)(c.r.dst >> 1), v, Lim<short>::lo, Lim<short>::hi);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double s = (double)v[j];
+                x[2 * j] = (short)fbound(s * c.left, Lim<short>::lo, Lim<short>::hi);
+                x[2 * j + 1] = (short)fbound(s * c.right, Lim<short>::lo, Lim<short>::hi);
+            }
+        }
+        if (c.r.factor != 1.0) x = seq_mul8(x, c.r.factor);
+        acc = __builtin_elementwise_add_sat(acc, x);
+    }
+    if (whole) *reinterpret_cast<short8v*>(track + s0) = acc;
+    else
+        for (uint32_t j = 0; j < 8 && s0 + j < track_samples; ++j) track[s0 + j] = acc[j];
+}
+
+// k_mix_events_pan_w with an envelope per event (widths 1 and 4: upstream's fades have no 24-bit form): a thread's four track samples
+// are four source samples, or two mono frames of a tostereo event.
+template <int WIDTH>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_mix_events_env_w(const SeqEvE* __restrict__ ev, const she::Seg* __restrict__ segs,
+                                                                        const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ first,
+                                                                        const uint32_t* __restrict__ idx, uint32_t ntiles, unsigned char* track,
+                                                                        uint32_t track_samples) {
+    static_assert(WIDTH == 1 || WIDTH == 4, "an envelope has widths 1, 2 and 4");
+    const uint32_t k = (uint32_t)sh::block_id();
+    if (k >= ntiles) return;
+    const uint32_t t0 = tiles[k] * shq::TILE_W;
+    const uint32_t s0 = t0 + threadIdx.x * shq::LANE_SAMPLES_W;
+    if (s0 >= track_samples) return;
+    constexpr long long HI = WIDTH == 1 ? 127LL : 2147483647LL, LO = -HI - 1;
+    long long acc[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (s0 + j < track_samples) acc[j] = chain_get<WIDTH>(track, s0 + j);
+    const uint32_t e1 = first[k + 1];
+    for (uint32_t e = first[k]; e < e1; ++e) {
+        const SeqEvE c = ev[idx[e]];
+        gbyte_p src = (gbyte_p)c.r.src;
+        uint32_t tlo = 0, thi = 0;
+        if (c.nseg) seq_env_span(c, t0, shq::TILE_W, tlo, thi);        // (uniform, as every branch on the record)
+        int v[4] = {0, 0, 0, 0};
+        bool in[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long rel = (long long)s0 + j - (long long)c.r.dst;
+            in[j] = rel >= 0 && rel < (long long)c.r.n;
+        }
+        if (!c.tostereo) {
+            if (c.r.inr == c.r.outr) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (in[j]) v[j] = seq_get<WIDTH>(src, (size_t)((long long)s0 + j - (long long)c.r.dst));
+            } else {
+                seq_rate<WIDTH, 4>(c.r, s0, [&](size_t i) { return seq_get<WIDTH>(src, i); }, v);
+            }
+            if (c.nseg) she::shape_lane<4>(segs + c.seg0, c.nseg, tlo, thi, (long long)s0 - (long long)c.r.dst, v, (double)LO, (double)HI);
+        } else {
+            int m[2] = {0, 0};
+            if (c.r.inr == c.r.outr) {
+#pragma unroll
+                for (int f = 0; f < 2; ++f)                   // (dst, n and s0 are even: a frame is inside the event or outside it)
+                    if (in[2 * f]) m[f] = seq_get<WIDTH>(src, (size_t)((long long)(s0 >> 1) + f - (long long)(c.r.dst >> 1)));
+            } else {
+                seq_rate<WIDTH, 2>(seq_mono_frames(c.r), s0 >> 1, [&](size_t i) { return seq_get<WIDTH>(src, i); }, m);
+            }
+            if (c.nseg) she::shape_lane<2>(segs + c.seg0, c.nseg, tlo, thi, (long long)(s0 >> 1) - (long long)(c.r.dst >> 1), m, (double)LO, (double)HI);
+#pragma unroll
+            for (int f = 0; f < 2; ++f) {
+                const double s = (double)m[f];
+                v[2 * f] = fbound(s * c.left, (double)LO, (double)HI);
+                v[2 * f + 1] = fbound(s * c.right, (double)LO, (double)HI);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (in[j]) {
+                long long x = v[j];
+                if (c.r.factor != 1.0) x = fbound((double)x * c.r.factor, (double)LO, (double)HI);
+                const long long t = acc[j] + x;
+                acc[j] = t > HI ? HI : (t < LO ? LO : t);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (s0 + j < track_samples) chain_put<WIDTH>(track, s0 + j, acc[j]);
+}
+
 }  // namespace
 
 // ---- host: what the entry points share ----------------------------------------------------------------------------------------------
@@ -555,8 +724,9 @@ int seq_check_event(const char* fn, const Ev& m, uint32_t e, const sh_buf* const
 
 // The plan of the checked events (dst, n), then records | tiles | first | idx as one block on the library's grow-only scratch, one copy,
 // one launch: fill(rec) writes the nevents records, launch(records, tiles, first, idx, ntiles, grid, block, stream) names the kernel.
+// after_records: bytes of a second table (a multiple of 16) that fill writes behind the records and the kernel finds there.
 template <typename Rec, typename Fill, typename Launch>
-int seq_run(const char* fn, const std::vector<shq::Event>& pe, int width, size_t track_samples, Fill fill, Launch launch) {
+int seq_run(const char* fn, const std::vector<shq::Event>& pe, int width, size_t track_samples, Fill fill, Launch launch, size_t after_records = 0) {
     const uint32_t nevents = (uint32_t)pe.size();
     const uint32_t tile = shq::tile_samples(width);
     const shq::Plan P = shq::plan(pe.data(), nevents, track_samples, tile);
@@ -565,7 +735,7 @@ int seq_run(const char* fn, const std::vector<shq::Event>& pe, int width, size_t
     if (P.refused) return sh::set_error(SH_ERR_INVALID, "%s: more than 2^28 (event, tile) overlaps in one call", fn);
     if (P.tiles.empty()) return SH_OK;
     const uint32_t nt = (uint32_t)P.tiles.size();
-    const size_t b_ev = (size_t)nevents * sizeof(Rec), b_tiles = (size_t)nt * 4, b_first = ((size_t)nt + 1) * 4, b_idx = P.idx.size() * 4;
+    const size_t b_ev = (size_t)nevents * sizeof(Rec) + after_records, b_tiles = (size_t)nt * 4, b_first = ((size_t)nt + 1) * 4, b_idx = P.idx.size() * 4;
     std::vector<char> host(b_ev + b_tiles + b_first + b_idx);
     fill(reinterpret_cast<Rec*>(host.data()));
     memcpy(host.data() + b_ev, P.tiles.data(), b_tiles);
@@ -730,6 +900,91 @@ int sh_mix_events_pan(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_eve
             else if (width == 3) hipLaunchKernelGGL(k_mix_events_pan_w<3>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
             else hipLaunchKernelGGL(k_mix_events_pan_w<4>, grid, block, 0, st, d_ev, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
         });
+}
+
+int sh_mix_events_env(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_env* events, uint32_t nevents,
+                      const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_mix_events_env";
+    if (width == 3) return sh::set_error(SH_ERR_INVALID, "%s: width 3: an envelope's fades have no 24-bit form", fn);
+    int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    if (rc) return rc;
+    if (nchannels < 1) return sh::set_error(SH_ERR_INVALID, "%s: # of channels should be >= 1", fn);
+    if (nsegments && !segments) return sh::set_error(SH_ERR_INVALID, "%s: NULL argument", fn);
+    const size_t w = (size_t)width;
+    std::vector<shq::Event> pe(nevents);
+    for (uint32_t e = 0; e < nevents; ++e) {
+        const sh_mix_event_env& m = events[e];
+        if ((rc = seq_check_event(fn, m, e, srcs, nsrc))) return rc;
+        const bool tostereo = m.src_channels == 1 && nchannels == 2;
+        if (!tostereo && m.src_channels != (uint32_t)nchannels)
+            return sh::set_error(SH_ERR_INVALID, "%s: event %u: src_channels %u is neither the track's %d nor a mono source of a stereo track", fn, e, m.src_channels, nchannels);
+        if (!m.inrate || !m.outrate || m.inrate >= (1u << 31) || m.outrate >= (1u << 31))
+            return sh::set_error(SH_ERR_INVALID, "%s: event %u: sampling rate not in [1, 2^31)", fn, e);
+        const uint64_t nch = m.src_channels, have = srcs[m.src]->bytes / w;
+        uint64_t nsrc_samples = m.nsamples;                   // what the event takes of its (resampled) source
+        if (tostereo) {
+            if (!isfinite(m.left) || !isfinite(m.right)) return sh::set_error(SH_ERR_INVALID, "%s: event %u: left / right is not finite", fn, e);
+            if (m.dst_sample % 2 || m.nsamples % 2)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: a mono source starts and ends on whole stereo frames", fn, e);
+            nsrc_samples = m.nsamples / 2;
+        }
+        if (m.src_sample > have) return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside its source", fn, e);
+        if (m.inrate == m.outrate) {
+            if (nsrc_samples > have - m.src_sample) return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside its source", fn, e);
+        } else {
+            if (m.src_sample % nch || nsrc_samples % nch)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: a resampled event starts and ends on whole frames", fn, e);
+            if (m.src_frames > (have - m.src_sample) / nch) return sh::set_error(SH_ERR_INVALID, "%s: event %u: src_frames outside its source", fn, e);
+            if (nsrc_samples / nch > shr::out_frames(m.src_frames, shr::reduce(m.inrate, m.outrate)))
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: more samples than src_frames resample to", fn, e);
+        }
+        if (m.seg_count > she::MAX_SEGMENTS) return sh::set_error(SH_ERR_INVALID, "%s: event %u: more than %u segments", fn, e, she::MAX_SEGMENTS);
+        if (m.seg_count && (m.seg_first > nsegments || m.seg_count > nsegments - m.seg_first))
+            return sh::set_error(SH_ERR_INVALID, "%s: event %u: segments outside the table", fn, e);
+        uint64_t prev = 0;
+        for (uint32_t s = 0; s < m.seg_count; ++s) {
+            const sh_env_segment& g = segments[m.seg_first + s];
+            if (g.reserved != 0) return sh::set_error(SH_ERR_INVALID, "%s: event %u: segment %u: reserved must be 0", fn, e, s);
+            if (g.end < prev || g.end > nsrc_samples)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: segment %u: ends not ascending or beyond the event's source samples", fn, e, s);
+            if (g.kind > she::FADE_OUT) return sh::set_error(SH_ERR_INVALID, "%s: event %u: segment %u: kind %u not 0, 1 or 2", fn, e, s, g.kind);
+            if (!isfinite(g.mul) || !isfinite(g.slope) || !isfinite(g.numsamples) || !isfinite(g.offset))
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: segment %u: a factor is not finite", fn, e, s);
+            if (g.kind != she::NONE && !(g.numsamples > 0.0)) return sh::set_error(SH_ERR_INVALID, "%s: event %u: segment %u: a ramp needs numsamples > 0", fn, e, s);
+            if (g.origin > nsrc_samples) return sh::set_error(SH_ERR_INVALID, "%s: event %u: segment %u: origin beyond the event's source samples", fn, e, s);
+            prev = g.end;
+        }
+        pe[e] = shq::Event{m.dst_sample, m.nsamples};
+    }
+    const uint32_t ns = (uint32_t)track_samples;
+    return seq_run<SeqEvE>(fn, pe, width, track_samples,
+        [&](SeqEvE* rec) {
+            she::Seg* seg = reinterpret_cast<she::Seg*>(rec + nevents);
+            for (uint32_t s = 0; s < nsegments; ++s) {
+                const sh_env_segment& g = segments[s];        // (a segment that no event names was not checked, and no kernel reads it)
+                seg[s] = she::Seg{g.mul, g.slope, g.numsamples, g.offset, (uint32_t)g.end, (uint32_t)g.origin, g.kind, 0};
+            }
+            for (uint32_t e = 0; e < nevents; ++e) {
+                const sh_mix_event_env& m = events[e];
+                const shr::Rates R = shr::reduce(m.inrate, m.outrate);
+                rec[e] = SeqEvE{SeqEvR{(const char*)srcs[m.src]->ptr + m.src_sample * w, m.factor, 1.0 / (double)R.outr, (uint32_t)m.dst_sample,
+                                       (uint32_t)m.nsamples, R.inr, R.outr, R.inr / R.outr, R.inr % R.outr, m.src_channels,
+                                       width <= 2 && R.outr < 65536u ? 1u : 0u, {0, 0}},
+                                m.left, m.right, m.seg_count ? m.seg_first : 0u, m.seg_count, m.src_channels == 1 && nchannels == 2 ? 1u : 0u, 0};
+            }
+        },
+        [&](const SeqEvE* d_ev, const uint32_t* d_tiles, const uint32_t* d_first, const uint32_t* d_idx, uint32_t nt, dim3 grid, dim3 block, hipStream_t st) {
+            const she::Seg* d_seg = reinterpret_cast<const she::Seg*>(d_ev + nevents);
+            if (width == 2) {
+                const int aligned = ((uintptr_t)track->ptr & 15) == 0;
+                if (sh::knobs().seq_align == VEC2) hipLaunchKernelGGL(k_mix_events_env_i16<VEC2>, grid, block, 0, st, d_ev, d_seg, d_tiles, d_first, d_idx, nt, (short*)track->ptr, ns, aligned);
+                else hipLaunchKernelGGL(k_mix_events_env_i16<FUNNEL>, grid, block, 0, st, d_ev, d_seg, d_tiles, d_first, d_idx, nt, (short*)track->ptr, ns, aligned);
+            }
+            else if (width == 1) hipLaunchKernelGGL(k_mix_events_env_w<1>, grid, block, 0, st, d_ev, d_seg, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
+            else hipLaunchKernelGGL(k_mix_events_env_w<4>, grid, block, 0, st, d_ev, d_seg, d_tiles, d_first, d_idx, nt, (unsigned char*)track->ptr, ns);
+        },
+        (size_t)nsegments * sizeof(she::Seg));
 }
 
 }  // extern "C"

@@ -45,6 +45,61 @@ def _ratecv_out_frames(in_frames: int, inrate: int, outrate: int) -> int:
     return (in_frames - 1) * outrate // inrate + 1 if in_frames else 0
 
 
+def _envelope_segments(nbytes: int, width: int, nchannels: int, rate: int, attack: float, decay: float, sustainlevel: float,
+                       release: float) -> list:
+    """What ``Sample.envelope(attack, decay, sustainlevel, release)`` does to a sample of ``nbytes`` bytes, as consecutive segments
+    ``(end, mul, kind, slope, numsamples, offset, origin)`` in SAMPLES (sh_env_segment): upstream's split / amplify / fadein /
+    fadeout / join replayed in Python floats as they stand -- ``frame_idx(s) = fb * int(rate * s)``, ``duration = nbytes / rate /
+    width / nchannels``, ``min(seconds, duration)``, ``frame_idx(duration - seconds)``, ``S.duration - release`` -- so that a frame the
+    rounding leaves unfaded at the tail of the attack or the head of the decay or release part stays unfaded here.  Empty segments are
+    dropped and neighbours without a ramp and with the same mul are one.  ValueError where upstream's ``S.duration - release`` is
+    negative (it slices from the wrong end then)."""
+    fb = width * nchannels
+
+    def frame_idx(seconds):
+        return fb * int(rate * seconds)
+
+    def duration(nb):
+        return nb / rate / width / nchannels
+
+    a_len = min(frame_idx(attack), nbytes)                  # self.split(attack): frames[:end] | frames[end:]
+    d_len = min(frame_idx(decay), nbytes - a_len)           # D.split(decay)
+    s_all = nbytes - a_len - d_len                          # S, the release still in it: all of it through audioop.mul
+    rest = duration(s_all) - release
+    if rest < 0:
+        raise ValueError("mix_at_many: envelope: the release (%r s) is longer than what attack and decay leave (%r s)" % (release, duration(s_all)))
+    s_len = min(frame_idx(rest), s_all)                     # S.split(S.duration - release)
+    r_len = s_all - s_len
+    mul = float(sustainlevel) if sustainlevel < 1 else 1.0
+    parts = []                                              # (first byte, bytes, mul, kind, slope, offset)
+    a_fade = 0
+    if attack > 0:                                          # fadein: begin = frames[:frame_idx(min(seconds, duration))]
+        a_fade = min(frame_idx(min(attack, duration(a_len))), a_len)
+        parts.append((0, a_fade, 1.0, N.ENV_FADE_IN, 1.0 - 0.0, 0.0))
+    parts.append((a_fade, a_len - a_fade, 1.0, N.ENV_NONE, 0.0, 0.0))
+    d_head = d_len
+    if decay > 0:                                           # fadeout: end = frames[frame_idx(duration - min(seconds, duration)):]
+        d_head = min(frame_idx(duration(d_len) - min(decay, duration(d_len))), d_len)
+    parts.append((a_len, d_head, 1.0, N.ENV_NONE, 0.0, 0.0))
+    parts.append((a_len + d_head, d_len - d_head, 1.0, N.ENV_FADE_OUT, 1.0 - float(sustainlevel), 0.0))
+    r_head = r_len
+    if release > 0:
+        r_head = min(frame_idx(duration(r_len) - min(release, duration(r_len))), r_len)
+    s_at = a_len + d_len
+    parts.append((s_at, s_len + r_head, mul, N.ENV_NONE, 0.0, 0.0))
+    parts.append((s_at + s_len + r_head, r_len - r_head, mul, N.ENV_FADE_OUT, 1.0 - 0.0, 0.0))
+    segs = []
+    for first, nb, m, kind, slope, offset in parts:
+        if not nb:
+            continue
+        end = (first + nb) // width
+        if kind == N.ENV_NONE and segs and segs[-1][2] == N.ENV_NONE and segs[-1][1] == m:
+            segs[-1] = (end,) + segs[-1][1:]
+        else:
+            segs.append((end, m, kind, slope, float(nb // width) if kind else 0.0, offset, first // width))
+    return segs
+
+
 class Sample:
     """Audio sample data: interleaved little-endian signed PCM."""
 
@@ -561,22 +616,36 @@ class Sample:
 
     def mix_at_many(self, events: Iterable[tuple]) -> "Sample":
         """Mix a list of placed samples into this one: ``events`` holds ``(seconds, other, volume=None, other_seconds=None,
-        speed=None, pan=None)``, and the result is, byte for byte, what ::
+        speed=None, pan=None, envelope=None)``, and the result is, byte for byte, what ::
 
-            for seconds, other, volume, other_seconds, speed, pan in events:
+            for seconds, other, volume, other_seconds, speed, pan, envelope in events:
                 o = other
                 if speed is not None:
                     o = o.copy().speed(speed)           # audioop.ratecv(frames, width, nchannels, int(rate * speed), rate, None)
+                if envelope is not None:
+                    o = o.copy()
+                    if len(envelope) == 5:
+                        o.clip(0.0, envelope[4])        # the note's length, cut BEFORE the envelope: the release ends the note
+                    o.envelope(*envelope[:4])           # on the (resampled, cut) frames, before tostereo
                 if pan is not None:
-                    o = o.copy().stereo(left, right)    # audioop.tostereo of the (resampled) MONO frames
+                    o = o.copy().stereo(left, right)    # audioop.tostereo of the (resampled, shaped) MONO frames
                 if volume is not None:
-                    o = o.at_volume(volume)             # audioop.mul, after the resample and tostereo
+                    o = o.at_volume(volume)             # audioop.mul, after the resample, the envelope and tostereo
                 self.mix_at(seconds, o, other_seconds)  # other_seconds cuts the resampled (stereo) sample
 
-        leaves -- ``audioop.ratecv``, ``audioop.tostereo`` and ``audioop.mul`` per event, in that order, ``audioop.add`` with saturation
-        at every event, in list order, the track grown to the furthest end -- in one launch (sh_mix_events; sh_mix_events_rate when an
-        event has a speed: a sampler, one recorded note at many pitches; sh_mix_events_pan when one has a pan: mono instruments placed
-        in the stereo field of a stereo track, beside stereo ones) and with at most one allocation (none when nothing grows).  A speed
+        leaves -- ``audioop.ratecv``, the cut, the envelope, ``audioop.tostereo`` and ``audioop.mul`` per event, in that order,
+        ``audioop.add`` with saturation at every event, in list order, the track grown to the furthest end -- in one launch
+        (sh_mix_events; sh_mix_events_rate when an event has a speed: a sampler, one recorded note at many pitches; sh_mix_events_pan
+        when one has a pan: mono instruments placed in the stereo field of a stereo track, beside stereo ones; sh_mix_events_env when
+        one has an envelope: shaped notes) and with at most one allocation (none when nothing grows).  ``envelope`` is ``(attack, decay,
+        sustainlevel, release)`` or ``(attack, decay, sustainlevel, release, length)``, seconds and a factor 0 .. 1, with the bytes of
+        ``Sample.envelope``: the sustain and release parts through ``audioop.mul`` (clamp, floor; not at all when the level is 1), the
+        ramps ``int(x * f)`` (truncated) with ``f`` counting SAMPLES, so the two channels of a stereo frame get different factors and a
+        panned event is ramped over its mono samples; the part boundaries are upstream's float arithmetic, replayed on the host.  Parts
+        longer than the sample are what they are upstream (empty parts, an attack over the whole sample).  Its ValueErrors: a tuple
+        that is not 4 or 5 long, a negative or non-finite attack, decay, release or length, a sustainlevel outside 0 .. 1, a release
+        longer than what attack and decay leave of the sample (upstream slices from the wrong end then); 24-bit samples raise
+        NotImplementedError (upstream's fades have no 24-bit form).  A speed
         of None or 1.0, or one with ``int(rate * speed) == rate``, is none.  ``pan`` is a float -1 .. 1, ``(left, right)`` =
         ``((1 - pan) / 2, (1 + pan) / 2)`` as ``Sample.pan`` has them, or the pair ``(left_factor, right_factor)`` of ``Sample.stereo``
         itself (a 0 on one side: ``stereo_mix``'s "into the left / right channel only"); it needs a mono ``other`` and a stereo track.
@@ -590,12 +659,14 @@ class Sample:
         fb = self.__samplewidth * self.__nchannels
         rate = self.__samplerate
         todo = []                                           # everything is checked before anything is mixed
+        shaped = {}                                         # index into todo -> (envelope, its sh_env_segment rows): the enveloped events
         for ev in events:
+            nev = len(ev)
             seconds, other = ev[0], ev[1]
-            volume = ev[2] if len(ev) > 2 else None
-            other_seconds = ev[3] if len(ev) > 3 else None
-            speed = ev[4] if len(ev) > 4 else None
-            pan = ev[5] if len(ev) > 5 else None
+            volume = ev[2] if nev > 2 else None
+            other_seconds = ev[3] if nev > 3 else None
+            speed = ev[4] if nev > 4 else None
+            pan = ev[5] if nev > 5 else None
             assert self.samplewidth == other.samplewidth
             assert self.samplerate == other.samplerate
             factors = None                                                      # audioop.tostereo's, of a panned event
@@ -630,25 +701,48 @@ class Sample:
             start = fb * int(rate * seconds)                                    # frame_idx(seconds): Python floats, on the host
             frames = other.__nbytes // (self.__samplewidth * other.nchannels)   # (a panned event: the mono frames, a track frame each)
             have = fb * (frames if inrate == rate else _ratecv_out_frames(frames, inrate, rate))
+            if nev > 6 and ev[6] is not None:
+                envelope = ev[6]
+                if self.__samplewidth == 3:
+                    raise NotImplementedError("mix_at_many: envelope: 3-byte samples are not supported (fades have no 24-bit form)")
+                if not isinstance(envelope, (tuple, list)) or len(envelope) not in (4, 5):
+                    raise ValueError("mix_at_many: envelope is (attack, decay, sustainlevel, release) or (attack, decay, sustainlevel, release, length)")
+                if not all(math.isfinite(v) and v >= 0 for v in envelope[:2] + envelope[3:]):
+                    raise ValueError("mix_at_many: envelope: attack, decay, release and length are finite and not negative")
+                if not 0 <= envelope[2] <= 1:
+                    raise ValueError("mix_at_many: envelope: sustainlevel must be between 0 and 1")
+                if len(envelope) == 5:                                          # clip(0.0, length): frames[0:frame_idx(length)] of the other's own frames
+                    have = min(have, fb * int(rate * envelope[4]))
+                fbo = self.__samplewidth * other.nchannels
+                shaped[len(todo)] = (envelope, _envelope_segments(have // fb * fbo, self.__samplewidth, other.nchannels, rate, *envelope[:4]))
             n2 = fb * int(rate * other_seconds) if other_seconds else have     # frame_idx(other_seconds) of what mix_at is handed
             todo.append((seconds, other, volume, other_seconds, speed, start, min(n2, have), inrate, factors))
-        batch = []
-        for seconds, other, volume, other_seconds, speed, start, n2, inrate, factors in todo:
+        batch, envs = [], {}                                                    # envs: index into batch -> segment rows
+        for k, (seconds, other, volume, other_seconds, speed, start, n2, inrate, factors) in enumerate(todo):
             if other is self:                                                   # (never panned: a panned event's other is mono, its track stereo)
-                self.__mix_events(batch)
-                batch = []
+                self.__mix_events(batch, envs)
+                batch, envs = [], {}
                 if inrate != rate:
                     other = other.copy().speed(speed)
+                if shaped and k in shaped:
+                    envelope = shaped[k][0]
+                    other = other.copy()
+                    if len(envelope) == 5:
+                        other.clip(0.0, envelope[4])
+                    other.envelope(*envelope[:4])
                 self.mix_at(seconds, other if volume is None else other.at_volume(volume), other_seconds)
             else:
+                if shaped and k in shaped:
+                    envs[len(batch)] = shaped[k][1]
                 batch.append((start, other, n2, 1.0 if volume is None else float(volume), inrate, factors))
-        self.__mix_events(batch)
+        self.__mix_events(batch, envs)
         return self
 
-    def __mix_events(self, batch: Sequence[tuple]) -> None:
+    def __mix_events(self, batch: Sequence[tuple], envs: dict) -> None:
         """The events (first byte, other, bytes, factor, inrate, tostereo factors | None) -- none of them this sample -- folded in
         order; length -> the furthest end.  inrate != the sample rate: the event plays ``other`` resampled from inrate to the sample
         rate, and bytes counts resampled bytes; tostereo factors: ``other`` is mono, the track stereo, and bytes counts stereo bytes.
+        envs: index into batch -> _envelope_segments' rows of the events that have an envelope, cut here where the event is.
         The table is packed column by column (whole-array numpy operations, not a row per event)."""
         if not batch:
             return
@@ -679,21 +773,37 @@ class Sample:
         src = np.fromiter((slot[id(o)][0] for o in others), dtype=np.uint32, count=len(others))
         rated = bool((inrates != rate).any())
         panned = any(p is not None for p in pans)
-        table = np.zeros(len(batch), dtype=N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
+        shaped = bool(envs)
+        table = np.zeros(len(batch), dtype=N.MIX_EVENT_ENV_DTYPE if shaped else N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
         table["dst_sample"] = starts // w
         table["nsamples"] = nbytes // w
         table["factor"] = factors
         table["src"] = src
-        if rated or panned:
+        if rated or panned or shaped:
             frames = np.array([o.__nbytes // (w * o.nchannels) for o in uniq], dtype=np.uint64)
             table["src_frames"] = frames[src]
             table["inrate"] = inrates
             table["outrate"] = rate
-        if panned:
+        if panned or shaped:
             table["src_channels"] = np.array([o.nchannels for o in uniq], dtype=np.uint32)[src]
             lr = np.array([p if p is not None else (0.0, 0.0) for p in pans], dtype=np.float64)
             table["left"] = lr[:, 0]
             table["right"] = lr[:, 1]
+        if shaped:
+            rows = []
+            for i, g in envs.items():
+                taken = int(nbytes[i]) // w // (2 if pans[i] is not None else 1)       # the event's source samples, after other_seconds' cut
+                mine = [(min(r[0], taken),) + r[1:] for r in g]
+                mine = [r for k, r in enumerate(mine) if r[0] > (mine[k - 1][0] if k else 0)]      # (what the cut leaves nothing of)
+                table["seg_first"][i] = len(rows)
+                table["seg_count"][i] = len(mine)
+                rows.extend(mine)
+            segtab = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
+            for name, col in zip(("end", "mul", "kind", "slope", "numsamples", "offset", "origin"), zip(*rows) if rows else [()] * 7):
+                segtab[name] = col
+            N.check(N.lib().sh_mix_events_env(srcs, len(bufs), table.ctypes.data, len(table), segtab.ctypes.data, len(segtab), w,
+                                              self.__nchannels, track.handle, total // w))
+        elif panned:
             N.check(N.lib().sh_mix_events_pan(srcs, len(bufs), table.ctypes.data, len(table), w, track.handle, total // w))
         elif rated:
             N.check(N.lib().sh_mix_events_rate(srcs, len(bufs), table.ctypes.data, len(table), w, self.__nchannels, track.handle, total // w))

@@ -20,7 +20,15 @@ else, for rocprofv3 --kernel-trace --stats.
 live audioop.ratecv / tostereo / mul / add: (a) one mix_at_many with pans; (b) the loop of copy().speed().stereo() / at_volume / mix_at
 it replaces; (c) what there was before pans: a stereo copy of the instrument per distinct (instrument, speed, pan), made once, then
 one mix_at_many of plain stereo events -- with the time to make the copies and the device bytes they take.  --pan --trace: (a)'s and (c)'s
-one call five times each, for rocprofv3 --kernel-trace."""
+one call five times each, for rocprofv3 --kernel-trace.
+
+--env: shaped notes (sh_mix_events_env) -- the sampler song with an ADSR envelope on every note (attack, decay and release 10 %, 15 % and
+25 % of the note, sustain level 0.7) and a note length (60 % of the resampled instrument) on every other one.  One mix_at_many against the
+loop of copy().speed().clip().envelope() / at_volume / mix_at it replaces, both checked against live audioop.ratecv / mul / add and the
+fades in float64 (numpy, the expression order of upstream's int(x * f)).  Then the device time of the one call for the same notes with
+(1) no envelope at all (sh_mix_events_rate, the route such a list took before), (2) an envelope that does nothing, (3) a sustain level
+alone -- every tile inside one segment, the uniform path -- and (4) the full envelope: what the walk over the segments and the ramps cost.
+--env --trace: those four calls five times each and nothing else, for rocprofv3 --kernel-trace."""
 import audioop
 import os
 import sys
@@ -276,6 +284,138 @@ def pan_main():
                                       dev["a"], dev["c"], " ".join("ok" if x else "FAILED" for x in parity)), flush=True)
 
 
+def env_song(nevents, span):
+    """sampler_song with an envelope per event, in proportion to the note; every other note shorter than its instrument"""
+    base, inst, events = sampler_song(nevents, span)
+    out = []
+    for n, (s, i, v, sp) in enumerate(events):
+        frames = len(inst[i]) // (WIDTH * NCH)
+        if sp is not None and int(RATE * sp) != RATE:
+            frames = (frames - 1) * RATE // int(RATE * sp) + 1
+        d = frames / RATE * (0.6 if n % 2 else 1.0)
+        out.append((s, i, v, sp, (0.1 * d, 0.15 * d, 0.7, 0.25 * d) + ((d,) if n % 2 else ())))
+    return base, inst, out
+
+
+def np_envelope(frames, attack, decay, sustainlevel, release):
+    """upstream's Sample.envelope on 16-bit bytes: the splits and audioop.mul as they stand, the ramps of fadein / fadeout in numpy float64
+    (k * slope / numsamples, 1.0 - ramp or ramp + 0.0, the product, trunc: the same IEEE operations in the same order)"""
+    fb = WIDTH * NCH
+
+    def frame_idx(seconds):
+        return fb * int(RATE * seconds)
+
+    def duration(b):
+        return len(b) / RATE / WIDTH / NCH
+
+    def split(b, seconds):
+        end = frame_idx(seconds)
+        return (b[:end], b[end:]) if end != len(b) else (b, b"")
+
+    def ramped(b, slope, fadeout):
+        x = np.frombuffer(b, dtype="<i2").astype(np.float64)
+        ramp = np.arange(len(x), dtype=np.float64) * slope / (len(b) / WIDTH)
+        return np.trunc(x * ((1.0 - ramp) if fadeout else (ramp + 0.0))).astype("<i2").tobytes()
+
+    def fadeout(b, seconds, target):
+        i = frame_idx(duration(b) - min(seconds, duration(b)))
+        return b[:i] + ramped(b[i:], 1.0 - target, True)
+
+    A, D = split(frames, attack)
+    D, S = split(D, decay)
+    if sustainlevel < 1:
+        S = audioop.mul(S, WIDTH, sustainlevel)
+    S, R = split(S, duration(S) - release)
+    if attack > 0:
+        i = frame_idx(min(attack, duration(A)))
+        A = ramped(A[:i], 1.0, False) + A[i:]
+    if decay > 0:
+        D = fadeout(D, decay, sustainlevel)
+    if release > 0:
+        R = fadeout(R, release, 0.0)
+    return A + D + S + R
+
+
+def env_oracle(base, sources, events):
+    fb = WIDTH * NCH
+    t = bytearray(base)
+    for seconds, i, volume, speed, env in events:
+        frames = sources[i]
+        if speed is not None and int(RATE * speed) != RATE:
+            frames = audioop.ratecv(frames, WIDTH, NCH, int(RATE * speed), RATE, None)[0]
+        if env is not None:
+            if len(env) == 5:
+                frames = frames[:fb * int(RATE * env[4])]
+            frames = np_envelope(frames, *env[:4])
+        if volume is not None:
+            frames = audioop.mul(frames, WIDTH, volume)
+        start = fb * int(RATE * seconds)
+        end = start + len(frames)
+        if end > len(t):
+            t.extend(bytes(end - len(t)))
+        t[start:end] = audioop.add(bytes(t[start:end]), frames, WIDTH)
+    return bytes(t)
+
+
+def env_main():
+    N.ensure_init(0)
+    print("sequence_env_ab: SYNTHHIP_SEQ_ALIGN=%s  %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), N.device_info()["name"]), flush=True)
+    for nevents, loop_passes in ((4096, 2), (32768, 1)):
+        base, sources, events = env_song(nevents, 120.0)
+        samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in sources]
+        start = Sample.from_raw_frames(base, WIDTH, RATE, NCH).to_device()
+        evs = [(s, samples[i], v, None, sp, None, e) for s, i, v, sp, e in events]
+        want = env_oracle(base, sources, events)
+
+        def many():
+            return start.copy().mix_at_many(evs)
+
+        def loop():
+            t = start.copy()
+            for seconds, other, volume, _o, speed, _p, env in evs:
+                o = other if speed is None else other.copy().speed(speed)
+                o = o.copy()
+                if len(env) == 5:
+                    o.clip(0.0, env[4])
+                o.envelope(*env[:4])
+                t.mix_at(seconds, o if volume is None else o.at_volume(volume))
+            return t
+
+        # the one call in place, on a track that is long enough: device time (table copy + kernel), the same notes four ways
+        forms = [("no envelope (rate route)", [e[:5] for e in evs]),
+                 ("envelope that does nothing", [e[:6] + ((0.0, 0.0, 1.0, 0.0) + e[6][4:],) for e in evs]),
+                 ("sustain level alone", [e[:6] + ((0.0, 0.0, 0.7, 0.0) + e[6][4:],) for e in evs]),
+                 ("full envelope", evs)]
+        if "--trace" in sys.argv[1:]:           # under rocprofv3 --kernel-trace: each form's one call five times, in this order, and nothing else
+            for _name, lst in forms:
+                track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, NCH).to_device()
+                for _ in range(5):
+                    track.mix_at_many(lst)
+                N.sync()
+            print("env song 120 s, %5d events   traced: %s" % (nevents, ", ".join(n for n, _l in forms)), flush=True)
+            continue
+        parity = [bytes(f().view_frame_data()) == want for f in (many, loop)]
+        many_ms = median_wall(many, 3, 9)
+        loop_ms = [median_wall(loop, 0, loop_passes), median_wall(loop, 0, loop_passes)]
+        dev = []
+        for _name, lst in forms:
+            track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, NCH).to_device()
+            for _ in range(3):
+                track.mix_at_many(lst)
+            runs = []
+            for _ in range(15):
+                N.sync()
+                N.timer_start()
+                track.mix_at_many(lst)
+                runs.append(N.timer_stop())
+            runs.sort()
+            dev.append((runs[len(runs) // 2], runs[0], runs[-1]))
+        print("env song 120 s, %5d events   mix_at_many with envelopes %9.3f ms   loop %10.3f / %10.3f ms   ratio %6.1fx   parity one call, loop: %s"
+              % (nevents, many_ms, loop_ms[0], loop_ms[1], min(loop_ms) / many_ms, " ".join("ok" if x else "FAILED" for x in parity)), flush=True)
+        for (name, _lst), (med, lo, hi) in zip(forms, dev):
+            print("    device, in place, %-28s median %8.4f ms   (min %8.4f, max %8.4f of 15)   %.3f us per event" % (name + ":", med, lo, hi, 1e3 * med / nevents), flush=True)
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -346,4 +486,4 @@ def main():
 
 
 if __name__ == "__main__":
-    pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
