@@ -216,7 +216,7 @@ int  sh_debug_counters(sh_counters* out);
  *                                 goes through k_resample_small like any other pair of rates, not through k_resample_period_i16
  *   SYNTHHIP_PERIOD_CHUNKS=n      consecutive chunks per workgroup of k_resample_period_i16 (default: 1, 2 or 4 by the rates' ratio;
  *                                 profiles/r06_resample_period.txt)
- *   SYNTHHIP_SEQ_ALIGN=1          k_mix_events_i16 reads an event's misaligned samples through a vector type of alignment 2 instead of
+ *   SYNTHHIP_SEQ_ALIGN=1          the 16-bit sequence kernels read an event's misaligned samples through a vector type of alignment 2 instead of
  *                                 two aligned 16-byte loads and a funnel shift (profiles/sequence_ab.txt)
  * (SYNTHHIP_LIB, read by the Python binding, names another build of this library to load; SYNTHHIP_ALLOW_STALE=1 lets it load a
  * library whose sources have changed when rebuilding fails.) */

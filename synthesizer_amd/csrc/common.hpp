@@ -77,7 +77,7 @@ struct Knobs {
     bool no_period = false;        // SYNTHHIP_NO_PERIOD=1: 16-bit mono resampling between rates with a short period goes through k_resample_small (rounds 1-5), not k_resample_period_i16
     int  period_chunks = 0;        // SYNTHHIP_PERIOD_CHUNKS=n: consecutive chunks per workgroup of k_resample_period_i16 (0: by the rates' ratio)
     int  rt_cus = 0;               // SYNTHHIP_RT_CUS=n: the last n compute units are kept for real-time lanes (the library's streams leave them out)
-    int  seq_align = 0;            // SYNTHHIP_SEQ_ALIGN=1: k_mix_events_i16 reads misaligned event samples through a vector type of alignment 2 (0: two aligned loads + funnel shift; profiles/sequence_ab.txt)
+    int  seq_align = 0;            // SYNTHHIP_SEQ_ALIGN=1: the 16-bit kernels of sequence.hip (seq_load) read misaligned event samples through a vector type of alignment 2 (0: two aligned loads + funnel shift; profiles/sequence_ab.txt)
     bool no_small_pipeline = false;// SYNTHHIP_NO_SMALL_PIPELINE=1: single-group banks render on one stream (round-2 behaviour)
     int  variant = 0;              // SYNTHHIP_VARIANT=WFM: waves, frames per lane, min waves per SIMD of the render kernel (484, 444, 844, 821, 421, 211)
     int  groups = 0;               // SYNTHHIP_GROUPS: voice groups of a render launch

@@ -9,11 +9,11 @@
 
 namespace shq {
 
-// The shapes of the two kernels (their template arguments and launch bounds are these, nothing else states them): a workgroup of
+// The two lane shapes of the kernels of sequence.hip (their template arguments and launch bounds are these, nothing else states them): a workgroup of
 // TILE_THREADS lanes per active tile, LANE_SAMPLES consecutive track samples per lane.
 constexpr uint32_t TILE_THREADS = 256;
-constexpr uint32_t LANE_SAMPLES_I16 = 8;                                   // k_mix_events_i16: one aligned 16-byte vector
-constexpr uint32_t LANE_SAMPLES_W = 4;                                     // k_mix_events_w<1 | 3 | 4>
+constexpr uint32_t LANE_SAMPLES_I16 = 8;                                   // 16-bit samples (k_seq_plain16, k_seq_16): one aligned 16-byte vector
+constexpr uint32_t LANE_SAMPLES_W = 4;                                     // widths 1, 3, 4 (k_seq_w)
 constexpr uint32_t TILE_I16 = TILE_THREADS * LANE_SAMPLES_I16;             // 2048 samples
 constexpr uint32_t TILE_W = TILE_THREADS * LANE_SAMPLES_W;                 // 1024 samples
 constexpr uint32_t tile_samples(int width) { return width == 2 ? TILE_I16 : TILE_W; }
