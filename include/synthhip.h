@@ -565,6 +565,39 @@ typedef struct sh_mix_event_env {  /* sh_mix_event_pan's fields, then the segmen
 int sh_mix_events_env(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_env* events, uint32_t nevents,
                       const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples);
 
+/* The same with a sustain loop per event: a note longer than its recording -- a recorded instrument held until its release -- still in
+ * one launch and without an unrolled copy per (instrument, length).
+ * Replaces: per note, o = other.copy().clip(0, loop_end); body = other.copy().clip(loop_start, loop_end); while o.duration < length:
+ * o.join(body); o.clip(0, length) in front of the loop body that sh_mix_events_env replaces.
+ * An event with loop_frames > 0 plays src_frames VIRTUAL frames: virtual frame v is frame v of the source (counted from src_sample) while
+ * v < loop_start + loop_frames, and frame loop_start + (v - loop_start - loop_frames) % loop_frames behind that.  The loop comes FIRST:
+ * audioop.ratecv runs over the virtual frames (it interpolates across the seam, from the loop's last frame to its first; its output
+ * count is that of src_frames input frames), then the cut, the envelope, tostereo, the mul and the saturating add as above.  A note with
+ * src_frames <= loop_start + loop_frames is a plain cut.  An event with loop_frames == 0 is an event of sh_mix_events_env, loop_start
+ * ignored; a list may hold every kind.  24-bit samples may loop (every step but the envelope has a 24-bit form). */
+typedef struct sh_mix_event_loop { /* sh_mix_event_env's fields, then the loop */
+    uint64_t dst_sample;
+    uint64_t src_sample;
+    uint64_t nsamples;
+    uint64_t src_frames;           /* looped: the note's VIRTUAL frames, which may exceed the source's */
+    double   factor;
+    double   left, right;
+    uint32_t src;
+    uint32_t inrate, outrate;
+    uint32_t src_channels;
+    uint32_t seg_first;
+    uint32_t seg_count;
+    uint32_t reserved;             /* 0 */
+    uint64_t loop_start;           /* first frame of the loop region, in frames from src_sample */
+    uint64_t loop_frames;          /* frames of the loop region; 0: no loop */
+} sh_mix_event_loop;               /* 104 bytes */
+/* SH_ERR_INVALID, the event named and nothing launched, for everything sh_mix_events_env refuses -- its src_frames-beyond-the-source rule
+ * holds for events without a loop; width 3 is refused only for an event with segments -- and for a looped event: loop_start +
+ * loop_frames beyond the source's frames from src_sample on, src_sample or nsamples off whole frames, more samples than src_frames hold
+ * (plain) or resample to (resampled), src_frames * src_channels above 2^32 - 65536. */
+int sh_mix_events_loop(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_loop* events, uint32_t nevents,
+                       const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

@@ -1,11 +1,13 @@
 // sequence.hip -- a list of placed samples mixed into a track in one launch (sh_mix_events, sh_mix_events_rate, sh_mix_events_pan,
-// sh_mix_events_env: Sample.mix_at_many, mixer.sequence).
+// sh_mix_events_env, sh_mix_events_loop: Sample.mix_at_many, mixer.sequence).
 //
 // The track is cut into tiles (seqplan.hpp); one workgroup per tile that some event touches walks that tile's events IN LIST ORDER, every
 // lane keeping its own few track samples in registers from the one load of the base to the one store of the result.  Lanes own disjoint
 // samples and read the track only there, so the fold is in place; a source may not be the track.  Per event, in this order -- none of
 // the steps commute, and the bytes are those of the loop of copy().speed().clip().envelope().stereo() / at_volume / mix_at it replaces:
 //
+//   loop       a note longer than its recording: the event's frames are VIRTUAL ones, frame v of the source up to the loop's end and the
+//              loop region again and again behind it (seqloop.hpp), mapped where they are fetched; everything below sees virtual frames.
 //   fetch      the event's source samples that land on the lane's track samples, zeros outside the event (x + 0 is the identity of the
 //              saturating add, fbound(0 * f) == 0).  A plain event (inr == outr): vector loads at 16 bits (seq_load), byte-assembled
 //              samples at widths 1, 3, 4.  A resampled one: audioop.ratecv, output frame m formed by whichever lane owns the track
@@ -18,8 +20,9 @@
 //
 // A feature LEVEL says how much of the chain a list may ask for, and with it which record a kernel reads: PLAIN (fetch of plain events,
 // mul, add: sh_mix_events), RATE (+ ratecv: sh_mix_events_rate), PAN (+ tostereo: sh_mix_events_pan), ENV (+ envelope:
-// sh_mix_events_env).  seq_event is the chain up to the mul, written once: a stage above the level is removed by `if constexpr`, a stage
-// of the level that an event does not use is skipped by a wave-uniform branch on its record.  Three kernel templates call it: the plain
+// sh_mix_events_env), LOOP (+ the sustain loop: sh_mix_events_loop).  seq_event is the chain up to the mul, written once: a stage above
+// the level is removed by `if constexpr`, a stage of the level that an event does not use is skipped by a wave-uniform branch on its
+// record (a row of sh_mix_events_loop without a loop is an event of ENV).  Three kernel templates call it: the plain
 // 16-bit one (INFLIGHT records and source vectors in flight), the 16-bit one of the other levels (one record ahead) and the one of
 // widths 1, 3, 4.  Built with -ffp-contract=off (the float64 product of audioop.mul stays one rounding, ratecv's prev*d + cur*(outr-d)
 // two).
@@ -28,6 +31,7 @@
 #include "pcmdev.hpp"
 #include "ratecv.hpp"
 #include "seqenv.hpp"
+#include "seqloop.hpp"
 #include "seqplan.hpp"
 #include <math.h>
 #include <string.h>
@@ -43,7 +47,7 @@ typedef const SH_SEQ_GLOBAL short* gshort_p;
 typedef const SH_SEQ_GLOBAL unsigned char* gbyte_p;
 typedef int int_u1 __attribute__((aligned(1)));
 
-enum Level { PLAIN = 0, RATE = 1, PAN = 2, ENV = 3 };
+enum Level { PLAIN = 0, RATE = 1, PAN = 2, ENV = 3, LOOP = 4 };
 
 // ---- the records: one event as the kernels read it, wave-uniform, so fetched by scalar loads ------------------------------------------
 struct SeqEv {                // PLAIN, 32 bytes
@@ -85,15 +89,28 @@ struct SeqEvE : SeqEvR {
     uint32_t tostereo;
     uint32_t pad3;
 };
+// LOOP, 96 bytes: SeqEvE with the rest of its padding put to use (a fourth 32 bytes, held one record ahead as well, cost the 16-bit
+// kernels scalar-register spills).  loop_len() == 0: an event of ENV.  Otherwise the event plays VIRTUAL frames (seqloop.hpp): virtual
+// frame v is frame v of src while v < loop_end() and frame loop_end() - loop_len() + (v - loop_end()) % loop_len() after it; everything SeqEvR says
+// of input frames it says of virtual ones, and the host has checked that the n samples exist among the V virtual frames (V * nch < 2^32:
+// 32-bit indices).
+struct SeqEvL : SeqEvE {
+    SH_HD uint32_t loop_end() const { return pad[0]; }                    // E, frames from src
+    SH_HD uint32_t loop_len() const { return pad[1]; }                    // E - S
+    SH_HD uint32_t step_mod() const { return pad3; }                      // step_q % loop_len: what one ratecv step adds to a cursor's phase
+    SH_HD uint32_t seam() const { return loop_end() * nch; }              // the first source SAMPLE behind the head
+};
 static_assert(sizeof(SeqEv) == 32, "SeqEv is read as one 32-byte scalar load");
 static_assert(sizeof(SeqEvR) == 64, "SeqEvR is read as one 64-byte scalar load");
 static_assert(sizeof(SeqEvP) == 96 && sizeof(SeqEvE) == 96, "SeqEvP and SeqEvE are read as a 64-byte and a 32-byte scalar load");
+static_assert(sizeof(SeqEvL) == 96 && sizeof(SeqEvL) % 32 == 0, "SeqEvL is read as a 64-byte and a 32-byte scalar load");
 
 template <int LEVEL> struct SeqRec;
 template <> struct SeqRec<PLAIN> { typedef SeqEv type; };
 template <> struct SeqRec<RATE> { typedef SeqEvR type; };
 template <> struct SeqRec<PAN> { typedef SeqEvP type; };
 template <> struct SeqRec<ENV> { typedef SeqEvE type; };
+template <> struct SeqRec<LOOP> { typedef SeqEvL type; };
 
 // ---- the lane shapes: eight 16-bit samples (one aligned 16-byte vector), four samples of widths 1, 3, 4 (bytes assembled for 24-bit
 // samples, 64-bit sums for 32-bit ones -- the shape of k_mix_chain_gather_w, pcm.hip, which says why these widths get the plain loop) ----
@@ -199,8 +216,13 @@ __device__ __forceinline__ void seq_plain(const void* src, uint32_t dst, uint32_
 // then shr::step per frame -- prev = frame j - 1 (zero when j == 0 or d == 0, as k_resample), cur = frame j, both straight from global
 // memory: an instrument is a few tens of KB that every note re-reads (L2 / TCP hits), and a lane's samples span about
 // N / nch * speed + 2 input frames.  get(i): sample i of the source, sign-extended.
-template <int WIDTH, int N, typename Get>
-__device__ __forceinline__ void seq_rate(const SeqEvR& c, uint32_t s0, Get get, int (&x)[N]) {
+// A looped event (SeqEvL, loop_len != 0): positions, j and d are those of the VIRTUAL frames, and cur and prev are mapped one by one
+// (seqloop.hpp), so the interpolation runs across the seam, from frame E - 1 to frame S.  d != 0 exactly when r != 0: cur is virtual
+// frame q + 1 and prev is q; d == 0: cur is q and there is no prev.  The lane keeps the cursor of q: one division where it starts,
+// then step_mod and the carry per frame, by compare and subtract -- a step may be longer than the loop.
+template <int WIDTH, int N, typename Rec, typename Get>
+__device__ __forceinline__ void seq_rate(const Rec& c, uint32_t s0, Get get, int (&x)[N]) {
+    constexpr bool LOOPED = std::is_same<Rec, SeqEvL>::value;
 #pragma unroll
     for (int k = 0; k < N; ++k) x[k] = 0;
     const long long rel = (long long)s0 - (long long)c.dst;
@@ -211,6 +233,9 @@ __device__ __forceinline__ void seq_rate(const SeqEvR& c, uint32_t s0, Get get, 
     else if (c.nch == 2) { m = r0 >> 1; ch = r0 & 1u; }
     else { m = r0 / c.nch; ch = r0 - m * c.nch; }
     shr::Pos p = shr::position(m, c.inr, c.outr, c.inv_outr);
+    shl::Cur lc{0u, 0u};
+    if constexpr (LOOPED)
+        if (c.loop_len()) lc = shl::at((uint32_t)p.q, c.loop_end(), c.loop_len());       // (uniform branch; q < V < 2^32)
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         const long long r = rel + k;
@@ -218,9 +243,22 @@ __device__ __forceinline__ void seq_rate(const SeqEvR& c, uint32_t s0, Get get, 
         uint64_t j;
         uint32_t d;
         shr::index(p, c.outr, j, d);
-        const size_t at = (size_t)j * c.nch + ch;
-        const int cur = get(at);
-        const int prev = (j && d) ? get(at - c.nch) : 0;
+        int cur = 0, prev = 0;
+        bool mapped = false;
+        if constexpr (LOOPED) {
+            if (c.loop_len()) {
+                shl::Cur lj = lc;
+                if (d) shl::step1(lj, c.loop_end(), c.loop_len());
+                cur = get((size_t)shl::frame(lj, c.loop_end()) * c.nch + ch);
+                prev = d ? get((size_t)shl::frame(lc, c.loop_end()) * c.nch + ch) : 0;
+                mapped = true;
+            }
+        }
+        if (!mapped) {
+            const size_t at = (size_t)j * c.nch + ch;
+            cur = get(at);
+            prev = (j && d) ? get(at - c.nch) : 0;
+        }
         if constexpr (WIDTH <= 2) {
             typedef typename std::conditional<WIDTH == 1, signed char, short>::type T;
             x[k] = c.small ? (int)shr::small_int<T>((T)prev, (T)cur, d, c.outr, c.inv_outr)
@@ -230,7 +268,43 @@ __device__ __forceinline__ void seq_rate(const SeqEvR& c, uint32_t s0, Get get, 
         }
         if (++ch == c.nch) {
             ch = 0;
+            const uint64_t q0 = p.q;
             shr::step<uint64_t>(p.q, p.r, (uint64_t)c.step_q, c.step_r, c.outr);
+            if constexpr (LOOPED) {
+                if (c.loop_len()) {
+                    shl::step(lc, c.step_q, c.step_mod(), c.loop_end(), c.loop_len());
+                    if (p.q - q0 != (uint64_t)c.step_q) shl::step1(lc, c.loop_end(), c.loop_len());
+                }
+            }
+        }
+    }
+}
+
+// A lane's N consecutive samples from sample f0 on, as a plain LOOPED event gives them where its tile reaches the seam or lies behind it:
+// sample by sample through seq_get (global loads) at mapped frames, the cursor of the lane's first frame from scratch, then one frame on
+// per frame.  NOT built: a vector read inside one loop pass -- which pass, and so which alignment against the lane's vector, differs from
+// lane to lane there, so it is not wave-uniform and FUNNEL does not apply; a later A/B.
+template <int WIDTH, int N>
+__device__ __forceinline__ void seq_looped(const SeqEvL& c, uint32_t f0, int (&x)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) x[k] = 0;
+    const long long rel = (long long)f0 - (long long)c.dst;
+    if (rel + N <= 0 || rel >= (long long)c.n) return;
+    const uint32_t r0 = rel > 0 ? (uint32_t)rel : 0u;
+    uint32_t v, ch;                                                     // (nch is uniform)
+    if (c.nch == 1) { v = r0; ch = 0; }
+    else if (c.nch == 2) { v = r0 >> 1; ch = r0 & 1u; }
+    else { v = r0 / c.nch; ch = r0 - v * c.nch; }
+    shl::Cur lc = shl::at(v, c.loop_end(), c.loop_len());
+    gbyte_p src = (gbyte_p)c.src;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const long long r = rel + k;
+        if (r < 0 || r >= (long long)c.n) continue;
+        x[k] = seq_get<WIDTH>(src, (size_t)shl::frame(lc, c.loop_end()) * c.nch + ch);
+        if (++ch == c.nch) {
+            ch = 0;
+            shl::step1(lc, c.loop_end(), c.loop_len());
         }
     }
 }
@@ -256,20 +330,32 @@ __device__ __forceinline__ void seq_source(const typename SeqRec<LEVEL>::type& c
     } else {
         int v[N];                                             // (ENV: the join below carries ints, as she::shape_lane takes them)
         if (c.inr == c.outr) {                                // (uniform, as every branch on the record)
-            seq_plain<WIDTH, SCHEME, N>(c.src, c.dst, c.n, f0, x);
-            if constexpr (LEVEL == ENV) {
+            bool gathered = false;
+            if constexpr (LEVEL == LOOP) {                        // what the tile takes lies wholly in the head: the plain path below
+                if (c.loop_len() && thi > c.seam()) {
+                    seq_looped<WIDTH, N>(c, f0, v);
+                    gathered = true;
+                }
+            }
+            if (!gathered) {
+                uint32_t n = c.n;                                 // (a looped event's n may reach past the source: the head ends at the seam,
+                if constexpr (LEVEL == LOOP)                      // and seq_load's second vector must not be read behind it)
+                    if (c.loop_len() && c.seam() < n) n = c.seam();
+                seq_plain<WIDTH, SCHEME, N>(c.src, c.dst, n, f0, x);
+                if constexpr (LEVEL >= ENV) {
 #pragma unroll
-                for (int j = 0; j < N; ++j) v[j] = (int)x[j];
+                    for (int j = 0; j < N; ++j) v[j] = (int)x[j];
+                }
             }
         } else {
             gbyte_p src = (gbyte_p)c.src;
             seq_rate<WIDTH, N>(c, f0, [&](size_t i) { return seq_get<WIDTH>(src, i); }, v);
-            if constexpr (LEVEL != ENV) {
+            if constexpr (LEVEL < ENV) {
 #pragma unroll
                 for (int j = 0; j < N; ++j) x[j] = v[j];
             }
         }
-        if constexpr (LEVEL == ENV) {
+        if constexpr (LEVEL >= ENV) {
             if (c.nseg) she::shape_lane<N>(segs + c.seg0, c.nseg, tlo, thi, (long long)f0 - (long long)c.dst, v, (double)SEQ_LO<WIDTH>, (double)SEQ_HI<WIDTH>);
 #pragma unroll
             for (int j = 0; j < N; ++j) x[j] = v[j];
@@ -285,6 +371,8 @@ __device__ __forceinline__ void seq_event(const typename SeqRec<LEVEL>::type& c,
     uint32_t tlo = 0, thi = 0;
     if constexpr (LEVEL == ENV)
         if (c.nseg) seq_env_span(c, t0, SEQ_TILE<WIDTH>, tlo, thi);
+    if constexpr (LEVEL == LOOP)
+        if (c.nseg || c.loop_len()) seq_env_span(c, t0, SEQ_TILE<WIDTH>, tlo, thi);
     if constexpr (LEVEL >= PAN) {
         if (c.tostereo) {                                     // the lane's N track samples are N / 2 frames of the mono source
             typename SeqRec<LEVEL>::type f = c;
@@ -397,6 +485,18 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_16(const typename Seq
     short8v acc = seq_track_load8(track, s0, track_samples, whole);
     uint32_t e = first[k];
     const uint32_t e1 = first[k + 1];
+    if constexpr (LEVEL == LOOP) {
+        // LOOP is where the scalar registers run out: with a whole record held ahead the allocator spilled (read in the ISA).  The INDEX
+        // of the next record is held ahead instead, so one scalar load of the two is still hidden.
+        uint32_t ni = idx[e];
+        while (e < e1) {
+            const Rec c = ev[ni];
+            if (++e < e1) ni = idx[e];
+            seq_fold8(acc, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
+        }
+        seq_track_store8(track, s0, track_samples, whole, acc);
+        return;
+    }
     Rec nx = ev[idx[e]];                                      // (an active tile lists at least one event)
     while (e < e1) {
         const Rec c = nx;
@@ -530,6 +630,7 @@ struct SeqIn {
     double   factor, left, right;
     uint32_t src, inrate, outrate, src_channels, seg_first, seg_count, reserved;
     int      nchannels;
+    uint64_t loop_start = 0, loop_frames = 0;               // sh_mix_event_loop's; loop_frames == 0: none, and src_frames is what it was
     bool tostereo() const { return src_channels == 1 && nchannels == 2; }
 };
 
@@ -557,12 +658,24 @@ int seq_check_events(const char* fn, int level, In in, uint32_t nevents, const s
                 return sh::set_error(SH_ERR_INVALID, "%s: event %u: a mono source starts and ends on whole stereo frames", fn, e);
             nsrc_samples = m.nsamples / 2;
         }
-        if (m.src_sample > have || (m.inrate == m.outrate && nsrc_samples > have - m.src_sample))
+        const bool looped = m.loop_frames != 0;               // src_frames counts VIRTUAL frames then, and may exceed the source's
+        if (m.src_sample > have || (!looped && m.inrate == m.outrate && nsrc_samples > have - m.src_sample))
             return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside its source", fn, e);
+        if (looped) {
+            if (m.src_sample % nch || nsrc_samples % nch)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: a looped event starts and ends on whole frames", fn, e);
+            const uint64_t held = (have - m.src_sample) / nch;
+            if (m.loop_start > held || m.loop_frames > held - m.loop_start)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: loop outside its source", fn, e);
+            if (m.src_frames > shq::MAX_TRACK_SAMPLES / nch)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: at most 2^32 - 65536 looped samples per event", fn, e);
+            if (m.inrate == m.outrate && nsrc_samples / nch > m.src_frames)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: more samples than src_frames hold", fn, e);
+        }
         if (m.inrate != m.outrate) {
             if (m.src_sample % nch || nsrc_samples % nch)
                 return sh::set_error(SH_ERR_INVALID, "%s: event %u: a resampled event starts and ends on whole frames", fn, e);
-            if (m.src_frames > (have - m.src_sample) / nch) return sh::set_error(SH_ERR_INVALID, "%s: event %u: src_frames outside its source", fn, e);
+            if (!looped && m.src_frames > (have - m.src_sample) / nch) return sh::set_error(SH_ERR_INVALID, "%s: event %u: src_frames outside its source", fn, e);
             if (nsrc_samples / nch > shr::out_frames(m.src_frames, shr::reduce(m.inrate, m.outrate)))
                 return sh::set_error(SH_ERR_INVALID, "%s: event %u: more samples than src_frames resample to", fn, e);
         }
@@ -601,7 +714,21 @@ void seq_fill(typename SeqRec<LEVEL>::type* rec, In in, uint32_t nevents, const 
                            m.src_channels, width <= 2 && R.outr < 65536u ? 1u : 0u, {0, 0}};
             if constexpr (LEVEL == RATE) rec[e] = r;
             else if constexpr (LEVEL == PAN) rec[e] = SeqEvP{r, m.left, m.right, {0, 0}, m.tostereo() ? 1u : 0u, 0};
-            else rec[e] = SeqEvE{r, m.left, m.right, m.seg_count ? m.seg_first : 0u, m.seg_count, m.tostereo() ? 1u : 0u, 0};
+            else {
+                const SeqEvE v{r, m.left, m.right, m.seg_count ? m.seg_first : 0u, m.seg_count, m.tostereo() ? 1u : 0u, 0};
+                if constexpr (LEVEL == ENV) rec[e] = v;
+                else {
+                    // a note no longer than its head (V <= E) is a plain cut: no loop pass, an event of ENV
+                    const uint64_t E = m.loop_start + m.loop_frames;
+                    SeqEvL l{v};
+                    if (m.loop_frames && m.src_frames > E) {
+                        l.pad[0] = (uint32_t)E;
+                        l.pad[1] = (uint32_t)m.loop_frames;
+                        l.pad3 = (uint32_t)(r.step_q % m.loop_frames);
+                    }
+                    rec[e] = l;
+                }
+            }
         }
     }
 }
@@ -620,11 +747,11 @@ void seq_launch(const typename SeqRec<LEVEL>::type* ev, const she::Seg* segs, co
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, tiles, first, idx, nt, (unsigned char*)track->ptr, ns); };
         if (width == 1) go(k_seq_w<LEVEL, 1>);
         else if (width == 4) go(k_seq_w<LEVEL, 4>);
-        else if constexpr (LEVEL != ENV) go(k_seq_w<LEVEL, 3>);
+        else if constexpr (LEVEL != ENV) go(k_seq_w<LEVEL, 3>);       // (LOOP: the entry point refuses width 3 with segments)
     }
 }
 
-// What the four entry points do behind their own arguments: check, plan, records (and the segments behind them), one launch.
+// What the five entry points do behind their own arguments: check, plan, records (and the segments behind them), one launch.
 template <int LEVEL, typename In>
 int seq_mix(const char* fn, In in, const sh_buf* const* srcs, uint32_t nsrc, uint32_t nevents, const sh_env_segment* segments, uint32_t nsegments, int width,
             int nchannels, sh_buf* track, size_t track_samples) {
@@ -709,6 +836,27 @@ int sh_mix_events_env(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_eve
                      m.seg_first, m.seg_count, m.reserved, nchannels};
     };
     return seq_mix<ENV>(fn, in, srcs, nsrc, nevents, segments, nsegments, width, nchannels, track, track_samples);
+}
+
+int sh_mix_events_loop(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_loop* events, uint32_t nevents,
+                       const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_mix_events_loop";
+    const int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    if (rc) return rc;
+    if (width == 3) {                                         // 24-bit samples may loop, every other step has a 24-bit form; an envelope has none
+        for (uint32_t e = 0; e < nevents; ++e)
+            if (events[e].seg_count) return sh::set_error(SH_ERR_INVALID, "%s: event %u: width 3: an envelope's fades have no 24-bit form", fn, e);
+    }
+    auto in = [=](uint32_t e) {
+        const sh_mix_event_loop& m = events[e];
+        SeqIn v{m.dst_sample, m.src_sample, m.nsamples, m.src_frames, m.factor, m.left, m.right, m.src, m.inrate, m.outrate, m.src_channels,
+                m.seg_first, m.seg_count, m.reserved, nchannels};
+        v.loop_start = m.loop_start;
+        v.loop_frames = m.loop_frames;
+        return v;
+    };
+    return seq_mix<LOOP>(fn, in, srcs, nsrc, nevents, segments, nsegments, width, nchannels, track, track_samples);
 }
 
 }  // extern "C"

@@ -37,6 +37,7 @@ __all__ = ["Sample", "LevelMeter"]
 
 _TYPECODE = {1: "b", 2: "h", 4: "i"}
 _NPTYPE = {1: np.int8, 2: np.int16, 4: np.int32}
+_MAX_CALL_SAMPLES = 0xFFFF0000                              # shq::MAX_TRACK_SAMPLES: positions are 32 bits on the device
 
 
 def _ratecv_out_frames(in_frames: int, inrate: int, outrate: int) -> int:
@@ -98,6 +99,29 @@ def _envelope_segments(nbytes: int, width: int, nchannels: int, rate: int, attac
         else:
             segs.append((end, m, kind, slope, float(nb // width) if kind else 0.0, offset, first // width))
     return segs
+
+
+def _loop_frames(loop, rate: int, frames: Optional[int], nchannels: int) -> tuple:
+    """``(loop_start, loop_end, length)`` in seconds of a sample of ``frames`` frames as ``(S, E - S, V)`` in frames: ``S = int(rate *
+    loop_start)`` and ``E = min(int(rate * loop_end), frames)`` as ``clip`` cuts them, ``V = int(rate * length)``; ``frames`` None: E is
+    not clamped (the track as its own source: it is clamped to what the track holds when the event runs).  Its ValueErrors: not three
+    numbers, one that is not finite or negative, an empty loop after the clamp to the sample, more than one call can address."""
+    if not isinstance(loop, (tuple, list)) or len(loop) != 3:
+        raise ValueError("mix_at_many: loop is (loop_start, loop_end, length)")
+    try:
+        good = all(math.isfinite(v) and v >= 0 for v in loop)
+    except TypeError:
+        good = False
+    if not good:
+        raise ValueError("mix_at_many: loop: loop_start, loop_end and length are finite and not negative")
+    start, end, virtual = int(rate * loop[0]), int(rate * loop[1]), int(rate * loop[2])
+    if frames is not None:
+        end = min(end, frames)
+    if start >= end:
+        raise ValueError("mix_at_many: loop: no frame between loop_start (frame %d) and loop_end (frame %d)" % (start, end))
+    if virtual * nchannels > _MAX_CALL_SAMPLES:
+        raise ValueError("mix_at_many: loop: a note of %d frames is more than one call can address" % virtual)
+    return start, end - start, virtual
 
 
 class Sample:
@@ -616,10 +640,17 @@ class Sample:
 
     def mix_at_many(self, events: Iterable[tuple]) -> "Sample":
         """Mix a list of placed samples into this one: ``events`` holds ``(seconds, other, volume=None, other_seconds=None,
-        speed=None, pan=None, envelope=None)``, and the result is, byte for byte, what ::
+        speed=None, pan=None, envelope=None, loop=None)``, and the result is, byte for byte, what ::
 
-            for seconds, other, volume, other_seconds, speed, pan, envelope in events:
+            for seconds, other, volume, other_seconds, speed, pan, envelope, loop in events:
                 o = other
+                if loop is not None:                    # a sustain loop: a note longer than its recording, FIRST in the chain
+                    ls, le, length = loop               # seconds of other's own time, before speed
+                    o = other.copy().clip(0.0, le)
+                    body = other.copy().clip(ls, le)
+                    while o.duration < length:
+                        o.join(body)
+                    o.clip(0.0, length)
                 if speed is not None:
                     o = o.copy().speed(speed)           # audioop.ratecv(frames, width, nchannels, int(rate * speed), rate, None)
                 if envelope is not None:
@@ -652,6 +683,13 @@ class Sample:
         A ValueError, raised before anything is mixed: negative times, non-finite volumes, a speed that is not finite or outside
         0.1 .. 10; a pan on a stereo ``other`` or into a track that is not stereo, a pan outside -1 .. 1, a pair of another length
         than two, a factor that is not finite.  A mono ``other`` without a pan in a stereo track fails the assertion of ``mix_at``.
+        ``loop`` is ``(loop_start, loop_end, length)``: with ``S = int(rate * loop_start)``, ``E = min(int(rate * loop_end), frames)``
+        and ``V = int(rate * length)`` the note has V virtual frames, frame v of ``other`` while ``v < E`` and frame ``S + (v - E) % (E -
+        S)`` after it; ``ratecv`` runs over the virtual frames (across the seam), the envelope sees V frames, nothing is unrolled in
+        memory, and a list with a loop goes to sh_mix_events_loop, still one launch.  ``V <= E`` is a plain cut.  24-bit samples may
+        loop.  Its ValueErrors, raised before anything is mixed: not three numbers, one that is not finite or is negative, ``S >= E``,
+        ``V`` times the channel count beyond what one call can address.  Where ``other`` is this sample, E is clamped to what the track
+        holds when that event runs, so an empty loop there is found only then, after the events before it have been mixed.
         An event whose ``other`` is this sample reads it as the events before it left it: the list is cut there, and that one event
         goes through the loop's body above."""
         self._check_writable()
@@ -667,6 +705,7 @@ class Sample:
             other_seconds = ev[3] if nev > 3 else None
             speed = ev[4] if nev > 4 else None
             pan = ev[5] if nev > 5 else None
+            loop = ev[7] if nev > 7 else None
             assert self.samplewidth == other.samplewidth
             assert self.samplerate == other.samplerate
             factors = None                                                      # audioop.tostereo's, of a panned event
@@ -700,6 +739,9 @@ class Sample:
                     raise ValueError("mix_at_many: speed %r leaves no sample rate" % (speed,))
             start = fb * int(rate * seconds)                                    # frame_idx(seconds): Python floats, on the host
             frames = other.__nbytes // (self.__samplewidth * other.nchannels)   # (a panned event: the mono frames, a track frame each)
+            if loop is not None:                                                # (S, E - S, V) in frames; the note has V frames from here on
+                loop = _loop_frames(loop, rate, None if other is self else frames, other.nchannels)
+                frames = loop[2]
             have = fb * (frames if inrate == rate else _ratecv_out_frames(frames, inrate, rate))
             if nev > 6 and ev[6] is not None:
                 envelope = ev[6]
@@ -716,12 +758,18 @@ class Sample:
                 fbo = self.__samplewidth * other.nchannels
                 shaped[len(todo)] = (envelope, _envelope_segments(have // fb * fbo, self.__samplewidth, other.nchannels, rate, *envelope[:4]))
             n2 = fb * int(rate * other_seconds) if other_seconds else have     # frame_idx(other_seconds) of what mix_at is handed
-            todo.append((seconds, other, volume, other_seconds, speed, start, min(n2, have), inrate, factors))
+            todo.append((seconds, other, volume, other_seconds, speed, start, min(n2, have), inrate, factors, loop))
         batch, envs = [], {}                                                    # envs: index into batch -> segment rows
-        for k, (seconds, other, volume, other_seconds, speed, start, n2, inrate, factors) in enumerate(todo):
+        for k, (seconds, other, volume, other_seconds, speed, start, n2, inrate, factors, loop) in enumerate(todo):
             if other is self:                                                   # (never panned: a panned event's other is mono, its track stereo)
                 self.__mix_events(batch, envs)
                 batch, envs = [], {}
+                if loop is not None:                                            # clip(0.0, loop_end) of the track as it is NOW
+                    first, last = loop[0], min(loop[0] + loop[1], len(self))
+                    if first >= last:
+                        raise ValueError("mix_at_many: loop: no frame between loop_start (frame %d) and loop_end (frame %d) of the track "
+                                         "as the events before left it" % (first, last))
+                    other = other.__unrolled(first, last - first, loop[2])
                 if inrate != rate:
                     other = other.copy().speed(speed)
                 if shaped and k in shaped:
@@ -734,19 +782,35 @@ class Sample:
             else:
                 if shaped and k in shaped:
                     envs[len(batch)] = shaped[k][1]
-                batch.append((start, other, n2, 1.0 if volume is None else float(volume), inrate, factors))
+                batch.append((start, other, n2, 1.0 if volume is None else float(volume), inrate, factors, loop))
         self.__mix_events(batch, envs)
         return self
 
+    def __unrolled(self, loop_start: int, loop_frames: int, nframes: int) -> "Sample":
+        """A copy with the loop written out: frames [0, loop_start + loop_frames), then frames [loop_start, loop_start + loop_frames)
+        again and again, ``nframes`` in all -- what a looped event of mix_at_many plays, for the one whose source is the track itself."""
+        fb = self.__samplewidth * self.__nchannels
+        head, body, total = (loop_start + loop_frames) * fb, loop_frames * fb, nframes * fb
+        parts = [(self, 0, min(head, total))]
+        at = head
+        while at < total:
+            parts.append((self, loop_start * fb, min(body, total - at)))
+            at += body
+        out = Sample(name=self.name, samplerate=self.__samplerate, nchannels=self.__nchannels, samplewidth=self.__samplewidth)
+        out.__assemble(parts)
+        return out
+
     def __mix_events(self, batch: Sequence[tuple], envs: dict) -> None:
-        """The events (first byte, other, bytes, factor, inrate, tostereo factors | None) -- none of them this sample -- folded in
+        """The events (first byte, other, bytes, factor, inrate, tostereo factors | None, loop | None) -- none of them this sample -- folded in
         order; length -> the furthest end.  inrate != the sample rate: the event plays ``other`` resampled from inrate to the sample
         rate, and bytes counts resampled bytes; tostereo factors: ``other`` is mono, the track stereo, and bytes counts stereo bytes.
         envs: index into batch -> _envelope_segments' rows of the events that have an envelope, cut here where the event is.
+        loop: (loop_start, loop_frames, virtual frames) of a looped event, in frames of ``other``; one of them and the list goes to
+        sh_mix_events_loop, the events without a loop as rows with loop_frames == 0.
         The table is packed column by column (whole-array numpy operations, not a row per event)."""
         if not batch:
             return
-        starts, others, nbytes, factors, inrates, pans = zip(*batch)
+        starts, others, nbytes, factors, inrates, pans, loops = zip(*batch)
         w = self.__samplewidth
         rate = self.__samplerate
         starts = np.array(starts, dtype=np.uint64)
@@ -774,22 +838,28 @@ class Sample:
         rated = bool((inrates != rate).any())
         panned = any(p is not None for p in pans)
         shaped = bool(envs)
-        table = np.zeros(len(batch), dtype=N.MIX_EVENT_ENV_DTYPE if shaped else N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
+        looped = loops.count(None) != len(loops)
+        table = np.zeros(len(batch), dtype=N.MIX_EVENT_LOOP_DTYPE if looped else N.MIX_EVENT_ENV_DTYPE if shaped else N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
         table["dst_sample"] = starts // w
         table["nsamples"] = nbytes // w
         table["factor"] = factors
         table["src"] = src
-        if rated or panned or shaped:
+        if rated or panned or shaped or looped:
             frames = np.array([o.__nbytes // (w * o.nchannels) for o in uniq], dtype=np.uint64)
             table["src_frames"] = frames[src]
             table["inrate"] = inrates
             table["outrate"] = rate
-        if panned or shaped:
+        if panned or shaped or looped:
             table["src_channels"] = np.array([o.nchannels for o in uniq], dtype=np.uint32)[src]
             lr = np.array([p if p is not None else (0.0, 0.0) for p in pans], dtype=np.float64)
             table["left"] = lr[:, 0]
             table["right"] = lr[:, 1]
-        if shaped:
+        if looped:
+            lp = np.array([l if l is not None else (0, 0, 0) for l in loops], dtype=np.uint64)
+            table["loop_start"] = lp[:, 0]
+            table["loop_frames"] = lp[:, 1]
+            table["src_frames"] = np.where(lp[:, 1] != 0, lp[:, 2], table["src_frames"])      # a looped row: the note's virtual frames
+        if shaped or looped:
             rows = []
             for i, g in envs.items():
                 taken = int(nbytes[i]) // w // (2 if pans[i] is not None else 1)       # the event's source samples, after other_seconds' cut
@@ -801,8 +871,9 @@ class Sample:
             segtab = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
             for name, col in zip(("end", "mul", "kind", "slope", "numsamples", "offset", "origin"), zip(*rows) if rows else [()] * 7):
                 segtab[name] = col
-            N.check(N.lib().sh_mix_events_env(srcs, len(bufs), table.ctypes.data, len(table), segtab.ctypes.data, len(segtab), w,
-                                              self.__nchannels, track.handle, total // w))
+            entry = N.lib().sh_mix_events_loop if looped else N.lib().sh_mix_events_env
+            N.check(entry(srcs, len(bufs), table.ctypes.data, len(table), segtab.ctypes.data, len(segtab), w,
+                          self.__nchannels, track.handle, total // w))
         elif panned:
             N.check(N.lib().sh_mix_events_pan(srcs, len(bufs), table.ctypes.data, len(table), w, track.handle, total // w))
         elif rated:

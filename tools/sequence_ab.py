@@ -28,7 +28,14 @@ loop of copy().speed().clip().envelope() / at_volume / mix_at it replaces, both 
 fades in float64 (numpy, the expression order of upstream's int(x * f)).  Then the device time of the one call for the same notes with
 (1) no envelope at all (sh_mix_events_rate, the route such a list took before), (2) an envelope that does nothing, (3) a sustain level
 alone -- every tile inside one segment, the uniform path -- and (4) the full envelope: what the walk over the segments and the ramps cost.
---env --trace: those four calls five times each and nothing else, for rocprofv3 --kernel-trace."""
+--env --trace: those four calls five times each and nothing else, for rocprofv3 --kernel-trace.
+
+--loop: held notes (sh_mix_events_loop) -- the sampler song with every note looped to a length beyond its recording (the region from
+50 % to 90 % of the instrument, held until the note is 1.5, 2 or 2.5 times the instrument long) and an envelope with a note length (80 %
+of the resampled held note) on every note.  Three forms of the same bytes, checked against the frames unrolled in numpy and then live
+audioop.ratecv / mul / add and the fades in float64: (a) one mix_at_many with loops; (b) the loop of clip / join / speed / clip / envelope
+/ at_volume / mix_at it replaces; (c) what there was before loops: an unrolled copy per distinct (instrument, length), made once, then one
+mix_at_many of enveloped events.  --loop --trace: (a)'s and (c)'s one call five times each, for rocprofv3 --kernel-trace."""
 import audioop
 import os
 import sys
@@ -416,6 +423,113 @@ def env_main():
             print("    device, in place, %-28s median %8.4f ms   (min %8.4f, max %8.4f of 15)   %.3f us per event" % (name + ":", med, lo, hi, 1e3 * med / nevents), flush=True)
 
 
+HELD = (1.5, 2.0, 2.5)
+
+
+def loop_song(nevents, span):
+    """sampler_song with a loop and an envelope with a note length per event"""
+    base, inst, events = sampler_song(nevents, span)
+    out = []
+    for n, (s, i, v, sp) in enumerate(events):
+        dur = len(inst[i]) // (WIDTH * NCH) / RATE
+        loop = (0.5 * dur, 0.9 * dur, HELD[n % 3] * dur)
+        frames = int(RATE * loop[2])
+        if sp is not None and int(RATE * sp) != RATE:
+            frames = (frames - 1) * RATE // int(RATE * sp) + 1
+        d = 0.8 * frames / RATE
+        out.append((s, i, v, sp, (0.1 * d, 0.15 * d, 0.7, 0.25 * d, d), loop))
+    return base, inst, out
+
+
+def unrolled(frames, loop):
+    fb = WIDTH * NCH
+    a = np.frombuffer(frames, dtype=np.uint8).reshape(-1, fb)
+    S, E, V = int(RATE * loop[0]), min(int(RATE * loop[1]), len(a)), int(RATE * loop[2])
+    v = np.arange(V)
+    return a[np.where(v < E, v, S + (v - E) % (E - S))].tobytes()
+
+
+def loop_main():
+    N.ensure_init(0)
+    print("sequence_loop_ab: SYNTHHIP_SEQ_ALIGN=%s  %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), N.device_info()["name"]), flush=True)
+    for nevents, loop_passes in ((4096, 2), (32768, 1)):
+        base, sources, events = loop_song(nevents, 120.0)
+        samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in sources]
+        start = Sample.from_raw_frames(base, WIDTH, RATE, NCH).to_device()
+        evs = [(s, samples[i], v, None, sp, None, e, lp) for s, i, v, sp, e, lp in events]
+        held = {(i, lp): unrolled(sources[i], lp) for _s, i, _v, _sp, _e, lp in events}
+        keys = list(held)
+        want = env_oracle(base, [held[k] for k in keys], [(s, keys.index((i, lp)), v, sp, e) for s, i, v, sp, e, lp in events])
+
+        def many():                                         # (a)
+            return start.copy().mix_at_many(evs)
+
+        def loop():                                         # (b)
+            t = start.copy()
+            for seconds, other, volume, _o, speed, _p, env, (ls, le, length) in evs:
+                o = other.copy().clip(0.0, le)
+                body = other.copy().clip(ls, le)
+                while o.duration < length:
+                    o.join(body)
+                o.clip(0.0, length)
+                if speed is not None:
+                    o = o.copy().speed(speed)
+                o = o.copy()
+                o.clip(0.0, env[4])
+                o.envelope(*env[:4])
+                t.mix_at(seconds, o if volume is None else o.at_volume(volume))
+            return t
+
+        def materialise():                                  # (c), first half: one unrolled copy per distinct (instrument, length)
+            made = {}
+            for i, (ls, le, length) in keys:
+                o = samples[i].copy().clip(0.0, le)
+                body = samples[i].copy().clip(ls, le)
+                while o.duration < length:
+                    o.join(body)
+                made[(i, (ls, le, length))] = o.clip(0.0, length)
+            return made
+
+        def materialised():                                 # (c)
+            made = materialise()
+            return start.copy().mix_at_many([(s, made[(i, lp)], v, None, sp, None, e) for s, i, v, sp, e, lp in events])
+
+        made = materialise()
+        copy_evs = [(s, made[(i, lp)], v, None, sp, None, e) for s, i, v, sp, e, lp in events]
+        if "--trace" in sys.argv[1:]:           # under rocprofv3 --kernel-trace: (a)'s one call, then (c)'s, five times each and nothing else
+            for lst in (evs, copy_evs):
+                track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, NCH).to_device()
+                for _ in range(5):
+                    track.mix_at_many(lst)
+                N.sync()
+            print("loop song 120 s, %5d events   traced: looped, then pre-unrolled copies" % nevents, flush=True)
+            continue
+        parity = [bytes(f().view_frame_data()) == want for f in (many, loop, materialised)]
+        extra = sum(len(o) * NCH * WIDTH for o in made.values())
+        many_ms = median_wall(many, 3, 9)
+        loop_ms = median_wall(loop, 0, loop_passes)
+        mat_ms = median_wall(materialised, 1, 5)
+        mat_only_ms = median_wall(materialise, 1, 5)
+        mat_mix_ms = median_wall(lambda: start.copy().mix_at_many(copy_evs), 3, 9)
+        dev = {}
+        for name, lst in (("a", evs), ("c", copy_evs)):     # the one call on a track that is long enough: device time (table copy + kernel)
+            track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, NCH).to_device()
+            for _ in range(3):
+                track.mix_at_many(lst)
+            runs = []
+            for _ in range(15):
+                N.sync()
+                N.timer_start()
+                track.mix_at_many(lst)
+                runs.append(N.timer_stop())
+            dev[name] = sorted(runs)[len(runs) // 2]
+        print("loop song 120 s, %5d events   (a) mix_at_many with loops %9.3f ms   (b) loop of calls %10.3f ms   (c) unrolled copies + mix_at_many "
+              "%9.3f ms (= %d copies %.3f ms, %.1f MB extra on the device, + the one call %.3f ms)   a/c %.2fx   b/a %.1fx   device, in place: "
+              "(a) %.4f ms  (c) %.4f ms   parity a, b, c: %s" % (nevents, many_ms, loop_ms, mat_ms, len(made), mat_only_ms, extra / 1e6, mat_mix_ms,
+                                                                  many_ms / mat_ms, loop_ms / many_ms, dev["a"], dev["c"],
+                                                                  " ".join("ok" if x else "FAILED" for x in parity)), flush=True)
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -486,4 +600,4 @@ def main():
 
 
 if __name__ == "__main__":
-    env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
