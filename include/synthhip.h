@@ -598,6 +598,42 @@ typedef struct sh_mix_event_loop { /* sh_mix_event_env's fields, then the loop *
 int sh_mix_events_loop(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_loop* events, uint32_t nevents,
                        const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples);
 
+/* The same with a reversed event: a reversed cymbal at 300 places, or at several pitches, without a materialised reversed copy.  (A
+ * REGION of a recording -- one hit out of a drum break, a recording whose attack is skipped -- needs nothing new: src_sample and
+ * src_frames say it in every struct above.)
+ * Replaces: o = other.copy().clip(start, end).reverse() (upstream synthplayer/sample.py, [RECALL]: audioop.reverse) in front of the loop
+ * body that sh_mix_events_loop replaces.
+ * An event with SH_MIX_EVENT_REVERSED set plays a region of its source backwards, FIRST in the chain: the region as stored, forwards, is
+ * the R frames from src_sample on -- R = src_frames, or loop_start + loop_frames for a looped event (nothing behind the loop's end is
+ * played, and its src_frames counts virtual frames) -- and played sample i is stored sample R * src_channels - 1 - i: audioop.reverse
+ * turns the order of the SAMPLES round, so the frames come backwards and, in a stereo source, left and right change places.  Everything
+ * sh_mix_event_loop says of frames (loop_start, loop_frames, src_frames, the input frames of audioop.ratecv, whose prev is 0 at the
+ * first PLAYED frame) it says of the played ones.  An event without the flag is an event of sh_mix_events_loop; a list may hold every
+ * kind. */
+#define SH_MIX_EVENT_REVERSED 1u
+typedef struct sh_mix_event_rev {  /* sh_mix_event_loop's fields, then the flags */
+    uint64_t dst_sample;
+    uint64_t src_sample;           /* reversed: the first STORED sample of the region, on a whole frame */
+    uint64_t nsamples;
+    uint64_t src_frames;           /* reversed and not looped: the region's frames, honoured for a plain event as well */
+    double   factor;
+    double   left, right;
+    uint32_t src;
+    uint32_t inrate, outrate;
+    uint32_t src_channels;
+    uint32_t seg_first;
+    uint32_t seg_count;
+    uint32_t reserved;             /* 0 */
+    uint64_t loop_start;           /* in PLAYED frames */
+    uint64_t loop_frames;
+    uint32_t flags;                /* SH_MIX_EVENT_REVERSED; every other bit 0 */
+} sh_mix_event_rev;                /* 112 bytes */
+/* SH_ERR_INVALID, the event named and nothing launched, for everything sh_mix_events_loop refuses, and: a flag bit other than
+ * SH_MIX_EVENT_REVERSED; for a reversed event a src_sample off whole frames, a region that reaches beyond its source, more samples than
+ * the region holds (plain). */
+int sh_mix_events_rev(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_rev* events, uint32_t nevents,
+                      const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

@@ -1,11 +1,14 @@
 // sequence.hip -- a list of placed samples mixed into a track in one launch (sh_mix_events, sh_mix_events_rate, sh_mix_events_pan,
-// sh_mix_events_env, sh_mix_events_loop: Sample.mix_at_many, mixer.sequence).
+// sh_mix_events_env, sh_mix_events_loop, sh_mix_events_rev: Sample.mix_at_many, mixer.sequence).
 //
 // The track is cut into tiles (seqplan.hpp); one workgroup per tile that some event touches walks that tile's events IN LIST ORDER, every
 // lane keeping its own few track samples in registers from the one load of the base to the one store of the result.  Lanes own disjoint
 // samples and read the track only there, so the fold is in place; a source may not be the track.  Per event, in this order -- none of
 // the steps commute, and the bytes are those of the loop of copy().speed().clip().envelope().stereo() / at_volume / mix_at it replaces:
 //
+//   region     a slice of the recording: where the record's pointer stands and how many frames the steps below may count; reversed
+//              (audioop.reverse: the order of the SAMPLES) the pointer stands behind the slice and sample i is ptr[-1 - i] (seqrev.hpp),
+//              applied where a sample is fetched, behind the loop's map; everything below sees the reversed frames.
 //   loop       a note longer than its recording: the event's frames are VIRTUAL ones, frame v of the source up to the loop's end and the
 //              loop region again and again behind it (seqloop.hpp), mapped where they are fetched; everything below sees virtual frames.
 //   fetch      the event's source samples that land on the lane's track samples, zeros outside the event (x + 0 is the identity of the
@@ -20,7 +23,8 @@
 //
 // A feature LEVEL says how much of the chain a list may ask for, and with it which record a kernel reads: PLAIN (fetch of plain events,
 // mul, add: sh_mix_events), RATE (+ ratecv: sh_mix_events_rate), PAN (+ tostereo: sh_mix_events_pan), ENV (+ envelope:
-// sh_mix_events_env), LOOP (+ the sustain loop: sh_mix_events_loop).  seq_event is the chain up to the mul, written once: a stage above
+// sh_mix_events_env), LOOP (+ the sustain loop: sh_mix_events_loop), REV (+ reversed playback: sh_mix_events_rev; its five kernels are
+// reached from that entry point alone).  seq_event is the chain up to the mul, written once: a stage above
 // the level is removed by `if constexpr`, a stage of the level that an event does not use is skipped by a wave-uniform branch on its
 // record (a row of sh_mix_events_loop without a loop is an event of ENV).  Three kernel templates call it: the plain
 // 16-bit one (INFLIGHT records and source vectors in flight), the 16-bit one of the other levels (one record ahead) and the one of
@@ -32,6 +36,7 @@
 #include "ratecv.hpp"
 #include "seqenv.hpp"
 #include "seqloop.hpp"
+#include "seqrev.hpp"
 #include "seqplan.hpp"
 #include <math.h>
 #include <string.h>
@@ -47,7 +52,7 @@ typedef const SH_SEQ_GLOBAL short* gshort_p;
 typedef const SH_SEQ_GLOBAL unsigned char* gbyte_p;
 typedef int int_u1 __attribute__((aligned(1)));
 
-enum Level { PLAIN = 0, RATE = 1, PAN = 2, ENV = 3, LOOP = 4 };
+enum Level { PLAIN = 0, RATE = 1, PAN = 2, ENV = 3, LOOP = 4, REV = 5 };
 
 // ---- the records: one event as the kernels read it, wave-uniform, so fetched by scalar loads ------------------------------------------
 struct SeqEv {                // PLAIN, 32 bytes
@@ -100,10 +105,18 @@ struct SeqEvL : SeqEvE {
     SH_HD uint32_t step_mod() const { return pad3; }                      // step_q % loop_len: what one ratecv step adds to a cursor's phase
     SH_HD uint32_t seam() const { return loop_end() * nch; }              // the first source SAMPLE behind the head
 };
+// REV, 96 bytes: SeqEvL, and bit 1 of `small` -- a word that held 0 or 1 -- says reversed.  reversed() == 0: an event of LOOP.  Otherwise
+// src stands one sample BEHIND the event's region and sample i of what SeqEvL describes is src[-1 - i] (seqrev.hpp): dst, n, nch, the
+// rates and the loop count reversed frames, and the host has checked that the region lies inside its source.
+struct SeqEvV : SeqEvL {
+    SH_HD uint32_t reversed() const { return small >> 1; }
+    SH_HD uint32_t small_int() const { return small & 1u; }
+};
 static_assert(sizeof(SeqEv) == 32, "SeqEv is read as one 32-byte scalar load");
 static_assert(sizeof(SeqEvR) == 64, "SeqEvR is read as one 64-byte scalar load");
 static_assert(sizeof(SeqEvP) == 96 && sizeof(SeqEvE) == 96, "SeqEvP and SeqEvE are read as a 64-byte and a 32-byte scalar load");
 static_assert(sizeof(SeqEvL) == 96 && sizeof(SeqEvL) % 32 == 0, "SeqEvL is read as a 64-byte and a 32-byte scalar load");
+static_assert(sizeof(SeqEvV) == 96, "SeqEvV is SeqEvL: the flag rides in a word that is there");
 
 template <int LEVEL> struct SeqRec;
 template <> struct SeqRec<PLAIN> { typedef SeqEv type; };
@@ -111,6 +124,7 @@ template <> struct SeqRec<RATE> { typedef SeqEvR type; };
 template <> struct SeqRec<PAN> { typedef SeqEvP type; };
 template <> struct SeqRec<ENV> { typedef SeqEvE type; };
 template <> struct SeqRec<LOOP> { typedef SeqEvL type; };
+template <> struct SeqRec<REV> { typedef SeqEvV type; };
 
 // ---- the lane shapes: eight 16-bit samples (one aligned 16-byte vector), four samples of widths 1, 3, 4 (bytes assembled for 24-bit
 // samples, 64-bit sums for 32-bit ones -- the shape of k_mix_chain_gather_w, pcm.hip, which says why these widths get the plain loop) ----
@@ -137,12 +151,42 @@ template <int N> struct SeqVec<2, N> { typedef typename ShortVec<N>::type type; 
 // one by one.
 enum Scheme { FUNNEL = 0, VEC2 = 1 };
 
+// FUNNEL: the N samples at p, which lies sh bytes (0 < sh < 2 N, even, uniform) behind an aligned 2 N bytes: that vector and the next
+template <int N, typename P>
+__device__ __forceinline__ typename ShortVec<N>::type seq_funnel(P p, uint32_t sh) {
+    typedef typename ShortVec<N>::type vec;
+    typedef int words __attribute__((ext_vector_type(N / 2)));
+    constexpr int W = N / 2;
+    const SH_SEQ_GLOBAL words* q = (const SH_SEQ_GLOBAL words*)((uintptr_t)p - sh);
+    const words lo = q[0], hi = q[1];
+    int w[2 * W];
+#pragma unroll
+    for (int i = 0; i < W; ++i) { w[i] = lo[i]; w[W + i] = hi[i]; }
+    const uint32_t r = sh & 3;
+    union { words v; vec s; } o;
+    auto funnel = [&](auto K) {                       // from word K of the 2 N bytes on
+        constexpr int k = decltype(K)::value;
+#pragma unroll
+        for (int i = 0; i < W; ++i) o.v[i] = (int)__builtin_amdgcn_alignbyte(w[k + i + 1], w[k + i], r);
+    };
+    if constexpr (W == 2) {
+        if (sh < 4) funnel(std::integral_constant<int, 0>());
+        else funnel(std::integral_constant<int, 1>());
+    } else {
+        switch (sh >> 2) {                              // (uniform)
+        case 0: funnel(std::integral_constant<int, 0>()); break;
+        case 1: funnel(std::integral_constant<int, 1>()); break;
+        case 2: funnel(std::integral_constant<int, 2>()); break;
+        default: funnel(std::integral_constant<int, 3>()); break;
+        }
+    }
+    return o.s;
+}
+
 template <int N, int SCHEME>
 __device__ __forceinline__ typename ShortVec<N>::type seq_load(gshort_p src, uint32_t dst, uint32_t n, uint32_t s0) {
     typedef typename ShortVec<N>::type vec;
     typedef short vecu __attribute__((ext_vector_type(N), aligned(2)));       // N samples at any sample offset
-    typedef int words __attribute__((ext_vector_type(N / 2)));
-    constexpr int W = N / 2;
     const long long rel = (long long)s0 - (long long)dst;
     vec x = 0;
     if (rel + N <= 0 || rel >= (long long)n) return x;
@@ -153,30 +197,7 @@ __device__ __forceinline__ typename ShortVec<N>::type seq_load(gshort_p src, uin
         if (sh == 0) {
             if (rel >= 0 && rel + N <= (long long)n) return *(const SH_SEQ_GLOBAL vec*)(src + rel);
         } else if (rel >= N && rel + 2 * N <= (long long)n) {
-            const SH_SEQ_GLOBAL words* q = (const SH_SEQ_GLOBAL words*)((uintptr_t)(src + rel) - sh);
-            const words lo = q[0], hi = q[1];
-            int w[2 * W];
-#pragma unroll
-            for (int i = 0; i < W; ++i) { w[i] = lo[i]; w[W + i] = hi[i]; }
-            const uint32_t r = sh & 3;
-            union { words v; vec s; } o;
-            auto funnel = [&](auto K) {                       // from word K of the 2 N bytes on
-                constexpr int k = decltype(K)::value;
-#pragma unroll
-                for (int i = 0; i < W; ++i) o.v[i] = (int)__builtin_amdgcn_alignbyte(w[k + i + 1], w[k + i], r);
-            };
-            if constexpr (W == 2) {
-                if (sh < 4) funnel(std::integral_constant<int, 0>());
-                else funnel(std::integral_constant<int, 1>());
-            } else {
-                switch (sh >> 2) {                              // (uniform)
-                case 0: funnel(std::integral_constant<int, 0>()); break;
-                case 1: funnel(std::integral_constant<int, 1>()); break;
-                case 2: funnel(std::integral_constant<int, 2>()); break;
-                default: funnel(std::integral_constant<int, 3>()); break;
-                }
-            }
-            return o.s;
+            return seq_funnel<N>(src + rel, sh);
         }
     }
 #pragma unroll
@@ -185,9 +206,61 @@ __device__ __forceinline__ typename ShortVec<N>::type seq_load(gshort_p src, uin
     return x;
 }
 
+// The same of a REVERSED event: `end` stands one sample behind its region, and the lane's N samples from event sample rel on are the N
+// contiguous stored samples end[-rel - N .. -rel) in reverse order -- one vector load under either scheme (FUNNEL: those samples start
+// (end + 2 dst) mod 2 N bytes behind an aligned vector, uniform again, since every lane starts on a multiple of N samples), then the N
+// shorts turned round in registers.  The conditions are seq_load's, in event samples: a vector is read only where all of it holds samples
+// of the event, so no load leaves the region, let alone the buffer; lanes on the edges assemble sample by sample.
+template <int N, int SCHEME>
+__device__ __forceinline__ typename ShortVec<N>::type seq_load_rev(gshort_p end, uint32_t dst, uint32_t n, uint32_t s0) {
+    typedef typename ShortVec<N>::type vec;
+    typedef short vecu __attribute__((ext_vector_type(N), aligned(2)));
+    const long long rel = (long long)s0 - (long long)dst;
+    vec x = 0;
+    if (rel + N <= 0 || rel >= (long long)n) return x;
+    gshort_p lo = end + shv::offset(1u, (uint64_t)(rel + N - 1));      // the lowest of the lane's stored samples: event sample rel + N - 1
+    const bool inside = rel >= 0 && rel + N <= (long long)n;
+    bool got = false;
+    vec m = 0;
+    if constexpr (SCHEME == VEC2) {
+        if (inside) { m = *(const SH_SEQ_GLOBAL vecu*)lo; got = true; }
+    } else {
+        const uint32_t sh = (uint32_t)(((uintptr_t)end + 2 * (uintptr_t)dst) & (2 * N - 1));      // (uniform) 0, 2 .. 2 N - 2
+        if (sh == 0) {
+            if (inside) { m = *(const SH_SEQ_GLOBAL vec*)lo; got = true; }
+        } else if (rel >= N && rel + 2 * N <= (long long)n) {
+            m = seq_funnel<N>(lo, sh);
+            got = true;
+        }
+    }
+    if (got) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) x[j] = m[N - 1 - j];
+        return x;
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+        if (rel + j >= 0 && rel + j < (long long)n) x[j] = end[shv::offset(1u, (uint64_t)(rel + j))];
+    return x;
+}
+
 // sample i of a source of WIDTH bytes per sample, sign-extended: chain_get (pcmdev.hpp) through a pointer that says where a source lives
 template <int WIDTH>
 __device__ __forceinline__ int seq_get(gbyte_p p, size_t i) {
+    if (WIDTH == 1) return (int)(signed char)p[i];
+    if (WIDTH == 2) return (int)((gshort_p)p)[i];
+    if (WIDTH == 3) {
+        gbyte_p q = p + 3 * i;
+        return (int)q[0] | ((int)q[1] << 8) | ((int)(signed char)q[2] << 16);
+    }
+    return *(const SH_SEQ_GLOBAL int_u1*)(p + 4 * i);
+}
+
+// seq_get at an offset of either sign against the pointer (shv::offset: a reversed event's samples lie in front of it).  A copy of
+// seq_get on purpose, for the REV kernels alone: giving seq_get itself a signed index changes the instructions of the kernels of the
+// other levels, which are held to what they were (profiles/sequence_rev_ab.txt, section 1).
+template <int WIDTH>
+__device__ __forceinline__ int seq_get_at(gbyte_p p, int64_t i) {
     if (WIDTH == 1) return (int)(signed char)p[i];
     if (WIDTH == 2) return (int)((gshort_p)p)[i];
     if (WIDTH == 3) {
@@ -211,6 +284,33 @@ __device__ __forceinline__ void seq_plain(const void* src, uint32_t dst, uint32_
     }
 }
 
+// and as a plain REVERSED event gives them
+template <int WIDTH, int SCHEME, int N>
+__device__ __forceinline__ void seq_plain_rev(const void* end, uint32_t dst, uint32_t n, uint32_t f0, typename SeqVec<WIDTH, N>::type& x) {
+    if constexpr (WIDTH == 2) {
+        x = seq_load_rev<N, SCHEME>((gshort_p)end, dst, n, f0);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const long long rel = (long long)f0 + j - (long long)dst;
+            x[j] = rel >= 0 && rel < (long long)n ? seq_get_at<WIDTH>((gbyte_p)end, shv::offset(1u, (uint64_t)rel)) : 0;
+        }
+    }
+}
+
+// sample i of the frames that event c plays: of its source, or (SeqEvV, reversed) of its reversed region, mapped to memory here
+template <int WIDTH, typename Rec>
+__device__ __forceinline__ int seq_at(const Rec& c, gbyte_p src, size_t i) {
+    if constexpr (std::is_same<Rec, SeqEvV>::value) return seq_get_at<WIDTH>(src, shv::offset(c.reversed(), i));
+    else return seq_get<WIDTH>(src, i);
+}
+
+template <typename Rec>
+__device__ __forceinline__ uint32_t seq_small(const Rec& c) {          // (SeqEvV: the word carries the reversed flag as well)
+    if constexpr (std::is_same<Rec, SeqEvV>::value) return c.small_int();
+    else return c.small;
+}
+
 // A lane's N consecutive track samples from s0 on, as a resampled event gives them: zeros outside the event (the identity of the fold,
 // as seq_load's edges), inside it frame m = rel / nch and channel rel % nch -- the position of the lane's first frame once (shr::position),
 // then shr::step per frame -- prev = frame j - 1 (zero when j == 0 or d == 0, as k_resample), cur = frame j, both straight from global
@@ -220,9 +320,10 @@ __device__ __forceinline__ void seq_plain(const void* src, uint32_t dst, uint32_
 // (seqloop.hpp), so the interpolation runs across the seam, from frame E - 1 to frame S.  d != 0 exactly when r != 0: cur is virtual
 // frame q + 1 and prev is q; d == 0: cur is q and there is no prev.  The lane keeps the cursor of q: one division where it starts,
 // then step_mod and the carry per frame, by compare and subtract -- a step may be longer than the loop.
+// A reversed event (SeqEvV): positions, j, d and the cursor are those of the REVERSED frames, and get maps an index to memory last.
 template <int WIDTH, int N, typename Rec, typename Get>
 __device__ __forceinline__ void seq_rate(const Rec& c, uint32_t s0, Get get, int (&x)[N]) {
-    constexpr bool LOOPED = std::is_same<Rec, SeqEvL>::value;
+    constexpr bool LOOPED = std::is_base_of<SeqEvL, Rec>::value;
 #pragma unroll
     for (int k = 0; k < N; ++k) x[k] = 0;
     const long long rel = (long long)s0 - (long long)c.dst;
@@ -261,7 +362,7 @@ __device__ __forceinline__ void seq_rate(const Rec& c, uint32_t s0, Get get, int
         }
         if constexpr (WIDTH <= 2) {
             typedef typename std::conditional<WIDTH == 1, signed char, short>::type T;
-            x[k] = c.small ? (int)shr::small_int<T>((T)prev, (T)cur, d, c.outr, c.inv_outr)
+            x[k] = seq_small(c) ? (int)shr::small_int<T>((T)prev, (T)cur, d, c.outr, c.inv_outr)
                            : shr::shifted_int(prev, cur, d, c.outr, c.inv_outr, 32 - 8 * WIDTH);
         } else {
             x[k] = shr::shifted_int(prev, cur, d, c.outr, c.inv_outr, 32 - 8 * WIDTH);
@@ -281,11 +382,11 @@ __device__ __forceinline__ void seq_rate(const Rec& c, uint32_t s0, Get get, int
 }
 
 // A lane's N consecutive samples from sample f0 on, as a plain LOOPED event gives them where its tile reaches the seam or lies behind it:
-// sample by sample through seq_get (global loads) at mapped frames, the cursor of the lane's first frame from scratch, then one frame on
-// per frame.  NOT built: a vector read inside one loop pass -- which pass, and so which alignment against the lane's vector, differs from
+// sample by sample through seq_at (global loads; a reversed event's index is mapped to memory last) at mapped frames, the cursor of the
+// lane's first frame from scratch, then one frame on per frame.  NOT built: a vector read inside one loop pass -- which pass, and so which alignment against the lane's vector, differs from
 // lane to lane there, so it is not wave-uniform and FUNNEL does not apply; a later A/B.
-template <int WIDTH, int N>
-__device__ __forceinline__ void seq_looped(const SeqEvL& c, uint32_t f0, int (&x)[N]) {
+template <int WIDTH, int N, typename Rec>
+__device__ __forceinline__ void seq_looped(const Rec& c, uint32_t f0, int (&x)[N]) {
 #pragma unroll
     for (int k = 0; k < N; ++k) x[k] = 0;
     const long long rel = (long long)f0 - (long long)c.dst;
@@ -301,7 +402,7 @@ __device__ __forceinline__ void seq_looped(const SeqEvL& c, uint32_t f0, int (&x
     for (int k = 0; k < N; ++k) {
         const long long r = rel + k;
         if (r < 0 || r >= (long long)c.n) continue;
-        x[k] = seq_get<WIDTH>(src, (size_t)shl::frame(lc, c.loop_end()) * c.nch + ch);
+        x[k] = seq_at<WIDTH>(c, src, (size_t)shl::frame(lc, c.loop_end()) * c.nch + ch);
         if (++ch == c.nch) {
             ch = 0;
             shl::step1(lc, c.loop_end(), c.loop_len());
@@ -331,7 +432,7 @@ __device__ __forceinline__ void seq_source(const typename SeqRec<LEVEL>::type& c
         int v[N];                                             // (ENV: the join below carries ints, as she::shape_lane takes them)
         if (c.inr == c.outr) {                                // (uniform, as every branch on the record)
             bool gathered = false;
-            if constexpr (LEVEL == LOOP) {                        // what the tile takes lies wholly in the head: the plain path below
+            if constexpr (LEVEL >= LOOP) {                        // what the tile takes lies wholly in the head: the plain path below
                 if (c.loop_len() && thi > c.seam()) {
                     seq_looped<WIDTH, N>(c, f0, v);
                     gathered = true;
@@ -339,9 +440,16 @@ __device__ __forceinline__ void seq_source(const typename SeqRec<LEVEL>::type& c
             }
             if (!gathered) {
                 uint32_t n = c.n;                                 // (a looped event's n may reach past the source: the head ends at the seam,
-                if constexpr (LEVEL == LOOP)                      // and seq_load's second vector must not be read behind it)
+                if constexpr (LEVEL >= LOOP)                      // and seq_load's second vector must not be read behind it)
                     if (c.loop_len() && c.seam() < n) n = c.seam();
-                seq_plain<WIDTH, SCHEME, N>(c.src, c.dst, n, f0, x);
+                bool turned = false;
+                if constexpr (LEVEL == REV) {
+                    if (c.reversed()) {
+                        seq_plain_rev<WIDTH, SCHEME, N>(c.src, c.dst, n, f0, x);
+                        turned = true;
+                    }
+                }
+                if (!turned) seq_plain<WIDTH, SCHEME, N>(c.src, c.dst, n, f0, x);
                 if constexpr (LEVEL >= ENV) {
 #pragma unroll
                     for (int j = 0; j < N; ++j) v[j] = (int)x[j];
@@ -349,7 +457,7 @@ __device__ __forceinline__ void seq_source(const typename SeqRec<LEVEL>::type& c
             }
         } else {
             gbyte_p src = (gbyte_p)c.src;
-            seq_rate<WIDTH, N>(c, f0, [&](size_t i) { return seq_get<WIDTH>(src, i); }, v);
+            seq_rate<WIDTH, N>(c, f0, [&](size_t i) { return seq_at<WIDTH>(c, src, i); }, v);
             if constexpr (LEVEL < ENV) {
 #pragma unroll
                 for (int j = 0; j < N; ++j) x[j] = v[j];
@@ -371,7 +479,7 @@ __device__ __forceinline__ void seq_event(const typename SeqRec<LEVEL>::type& c,
     uint32_t tlo = 0, thi = 0;
     if constexpr (LEVEL == ENV)
         if (c.nseg) seq_env_span(c, t0, SEQ_TILE<WIDTH>, tlo, thi);
-    if constexpr (LEVEL == LOOP)
+    if constexpr (LEVEL >= LOOP)
         if (c.nseg || c.loop_len()) seq_env_span(c, t0, SEQ_TILE<WIDTH>, tlo, thi);
     if constexpr (LEVEL >= PAN) {
         if (c.tostereo) {                                     // the lane's N track samples are N / 2 frames of the mono source
@@ -485,7 +593,7 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_16(const typename Seq
     short8v acc = seq_track_load8(track, s0, track_samples, whole);
     uint32_t e = first[k];
     const uint32_t e1 = first[k + 1];
-    if constexpr (LEVEL == LOOP) {
+    if constexpr (LEVEL >= LOOP) {
         // LOOP is where the scalar registers run out: with a whole record held ahead the allocator spilled (read in the ISA).  The INDEX
         // of the next record is held ahead instead, so one scalar load of the two is still hidden.
         uint32_t ni = idx[e];
@@ -631,7 +739,12 @@ struct SeqIn {
     uint32_t src, inrate, outrate, src_channels, seg_first, seg_count, reserved;
     int      nchannels;
     uint64_t loop_start = 0, loop_frames = 0;               // sh_mix_event_loop's; loop_frames == 0: none, and src_frames is what it was
+    uint32_t flags = 0;                                      // sh_mix_event_rev's; SH_MIX_EVENT_REVERSED: played backwards
     bool tostereo() const { return src_channels == 1 && nchannels == 2; }
+    bool reversed() const { return (flags & SH_MIX_EVENT_REVERSED) != 0; }
+    // the frames of a reversed event's region, stored from src_sample on: nothing behind a loop's end is played, and a looped event's
+    // src_frames counts virtual frames
+    uint64_t region_frames() const { return loop_frames ? loop_start + loop_frames : src_frames; }
 };
 
 // Every refusal of an event, in the order they are reported; in(e): event e as a SeqIn.  pe: the plan's view of the checked events.
@@ -642,6 +755,7 @@ int seq_check_events(const char* fn, int level, In in, uint32_t nevents, const s
     for (uint32_t e = 0; e < nevents; ++e) {
         const SeqIn m = in(e);
         if (m.reserved != 0) return sh::set_error(SH_ERR_INVALID, "%s: event %u: reserved must be 0", fn, e);
+        if (m.flags & ~(uint32_t)SH_MIX_EVENT_REVERSED) return sh::set_error(SH_ERR_INVALID, "%s: event %u: unknown flags 0x%x", fn, e, m.flags);
         if (!isfinite(m.factor)) return sh::set_error(SH_ERR_INVALID, "%s: event %u: factor is not finite", fn, e);
         if (m.src >= nsrc || !srcs[m.src]) return sh::set_error(SH_ERR_INVALID, "%s: event %u: no source %u", fn, e, m.src);
         if (!m.tostereo() && m.src_channels != (uint32_t)m.nchannels) {
@@ -670,6 +784,13 @@ int seq_check_events(const char* fn, int level, In in, uint32_t nevents, const s
             if (m.src_frames > shq::MAX_TRACK_SAMPLES / nch)
                 return sh::set_error(SH_ERR_INVALID, "%s: event %u: at most 2^32 - 65536 looped samples per event", fn, e);
             if (m.inrate == m.outrate && nsrc_samples / nch > m.src_frames)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: more samples than src_frames hold", fn, e);
+        }
+        if (m.reversed()) {                                   // the region as stored: region_frames() whole frames from src_sample on
+            if (m.src_sample % nch) return sh::set_error(SH_ERR_INVALID, "%s: event %u: a reversed event's region starts on a whole frame", fn, e);
+            if (m.region_frames() > (have - m.src_sample) / nch)
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: reversed region outside its source", fn, e);
+            if (!looped && m.inrate == m.outrate && nsrc_samples > m.region_frames() * nch)
                 return sh::set_error(SH_ERR_INVALID, "%s: event %u: more samples than src_frames hold", fn, e);
         }
         if (m.inrate != m.outrate) {
@@ -726,7 +847,15 @@ void seq_fill(typename SeqRec<LEVEL>::type* rec, In in, uint32_t nevents, const 
                         l.pad[1] = (uint32_t)m.loop_frames;
                         l.pad3 = (uint32_t)(r.step_q % m.loop_frames);
                     }
-                    rec[e] = l;
+                    if constexpr (LEVEL == LOOP) rec[e] = l;
+                    else {
+                        SeqEvV t{l};
+                        if (m.reversed()) {                   // one sample behind the region; played sample i is src[-1 - i]
+                            t.src = (const char*)src + shv::origin(1u, m.region_frames() * m.src_channels) * (size_t)width;
+                            t.small |= 2u;
+                        }
+                        rec[e] = t;
+                    }
                 }
             }
         }
@@ -751,7 +880,7 @@ void seq_launch(const typename SeqRec<LEVEL>::type* ev, const she::Seg* segs, co
     }
 }
 
-// What the five entry points do behind their own arguments: check, plan, records (and the segments behind them), one launch.
+// What the six entry points do behind their own arguments: check, plan, records (and the segments behind them), one launch.
 template <int LEVEL, typename In>
 int seq_mix(const char* fn, In in, const sh_buf* const* srcs, uint32_t nsrc, uint32_t nevents, const sh_env_segment* segments, uint32_t nsegments, int width,
             int nchannels, sh_buf* track, size_t track_samples) {
@@ -857,6 +986,28 @@ int sh_mix_events_loop(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_ev
         return v;
     };
     return seq_mix<LOOP>(fn, in, srcs, nsrc, nevents, segments, nsegments, width, nchannels, track, track_samples);
+}
+
+int sh_mix_events_rev(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_rev* events, uint32_t nevents,
+                      const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_mix_events_rev";
+    const int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    if (rc) return rc;
+    if (width == 3) {                                         // as sh_mix_events_loop: 24-bit samples may loop and play backwards, an envelope has no 24-bit form
+        for (uint32_t e = 0; e < nevents; ++e)
+            if (events[e].seg_count) return sh::set_error(SH_ERR_INVALID, "%s: event %u: width 3: an envelope's fades have no 24-bit form", fn, e);
+    }
+    auto in = [=](uint32_t e) {
+        const sh_mix_event_rev& m = events[e];
+        SeqIn v{m.dst_sample, m.src_sample, m.nsamples, m.src_frames, m.factor, m.left, m.right, m.src, m.inrate, m.outrate, m.src_channels,
+                m.seg_first, m.seg_count, m.reserved, nchannels};
+        v.loop_start = m.loop_start;
+        v.loop_frames = m.loop_frames;
+        v.flags = m.flags;
+        return v;
+    };
+    return seq_mix<REV>(fn, in, srcs, nsrc, nevents, segments, nsegments, width, nchannels, track, track_samples);
 }
 
 }  // extern "C"

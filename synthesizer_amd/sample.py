@@ -124,6 +124,30 @@ def _loop_frames(loop, rate: int, frames: Optional[int], nchannels: int) -> tupl
     return start, end - start, virtual
 
 
+def _region_frames(region, rate: int, frames: Optional[int], duration: float) -> tuple:
+    """``(start, end)`` in seconds of a sample of ``frames`` frames as ``(first frame, frames)``, as ``clip(start, end)`` cuts them:
+    ``int(rate * start)`` and ``int(rate * end)`` under byte-slicing rules, so both clamped to the sample; ``end`` None: the sample's
+    ``duration``, a float, through the same ``int(rate * duration)``.  ``frames`` None (the track as its own source: it is cut when the
+    event runs): only the checks.  Its ValueErrors: not a pair, a start or end that is not finite or is negative, ``end < start``."""
+    if not isinstance(region, (tuple, list)) or len(region) != 2:
+        raise ValueError("mix_at_many: region is (start, end), end may be None")
+    start, end = region
+    if end is None:
+        end = duration if frames is not None else start
+    try:
+        good = math.isfinite(start) and start >= 0 and math.isfinite(end) and end >= 0
+    except TypeError:
+        good = False
+    if not good:
+        raise ValueError("mix_at_many: region: start and end are finite and not negative")
+    if end < start:
+        raise ValueError("mix_at_many: region: end (%r s) lies before start (%r s)" % (end, start))
+    if frames is None:
+        return 0, 0
+    first, last = min(int(rate * start), frames), min(int(rate * end), frames)
+    return first, last - first
+
+
 class Sample:
     """Audio sample data: interleaved little-endian signed PCM."""
 
@@ -640,14 +664,18 @@ class Sample:
 
     def mix_at_many(self, events: Iterable[tuple]) -> "Sample":
         """Mix a list of placed samples into this one: ``events`` holds ``(seconds, other, volume=None, other_seconds=None,
-        speed=None, pan=None, envelope=None, loop=None)``, and the result is, byte for byte, what ::
+        speed=None, pan=None, envelope=None, loop=None, region=None, reverse=None)``, and the result is, byte for byte, what ::
 
-            for seconds, other, volume, other_seconds, speed, pan, envelope, loop in events:
+            for seconds, other, volume, other_seconds, speed, pan, envelope, loop, region, reverse in events:
                 o = other
-                if loop is not None:                    # a sustain loop: a note longer than its recording, FIRST in the chain
-                    ls, le, length = loop               # seconds of other's own time, before speed
-                    o = other.copy().clip(0.0, le)
-                    body = other.copy().clip(ls, le)
+                if region is not None:                  # (start, end) in seconds of other's own time; end may be None
+                    o = other.copy().clip(region[0], other.duration if region[1] is None else region[1])
+                if reverse:                             # audioop.reverse: the order of the SAMPLES, channels included
+                    o = o.copy().reverse()
+                if loop is not None:                    # a sustain loop: a note longer than its recording, in o's time
+                    ls, le, length = loop               # seconds of o's own time, before speed
+                    body = o.copy().clip(ls, le)
+                    o = o.copy().clip(0.0, le)
                     while o.duration < length:
                         o.join(body)
                     o.clip(0.0, length)
@@ -690,8 +718,21 @@ class Sample:
         loop.  Its ValueErrors, raised before anything is mixed: not three numbers, one that is not finite or is negative, ``S >= E``,
         ``V`` times the channel count beyond what one call can address.  Where ``other`` is this sample, E is clamped to what the track
         holds when that event runs, so an empty loop there is found only then, after the events before it have been mixed.
+        ``region`` plays a slice of ``other`` -- one hit out of a drum break, a recording without its attack -- with ``clip``'s
+        arithmetic: frames ``[int(rate * start), int(rate * end))``, both clamped to the sample, nothing copied, no source slot per
+        slice.  ``reverse``, taken by truth value, plays the (clipped) sound backwards as ``Sample.reverse`` does: ``audioop.reverse``
+        turns the order of the SAMPLES round, so sample ``i`` of the reversed region is sample ``R - 1 - i`` of the region -- for a
+        stereo ``other`` the frames come backwards AND left and right change places; a panned event's ``other`` is mono, so nothing
+        is swapped there.  Both come FIRST: the loop's S, E and V count frames of the clipped, reversed sound and E is clamped to the
+        region's frames, ``ratecv`` runs over these frames with its ``prev`` 0 at the region's first frame, the envelope sees what
+        they resample to.  A list with regions goes where it went without them (``src_sample`` and ``src_frames`` say the slice); one
+        reversed event and the list goes to sh_mix_events_rev, still one launch.  An empty region is an empty ``other``: nothing is
+        mixed and the track grows to the event's start; with a loop it is the loop's "no frame between" ValueError.  The region's
+        ValueErrors, raised before anything is mixed: not a pair, a start or end that is not finite or is negative, ``end < start``.
+        Where ``other`` is this sample, the region is cut from the track as it is when that event runs, so an ``end`` of None (the
+        track's duration then) that lies before ``start`` is found only then, after the events before it have been mixed.
         An event whose ``other`` is this sample reads it as the events before it left it: the list is cut there, and that one event
-        goes through the loop's body above."""
+        goes through the loop's body above, region and reverse included."""
         self._check_writable()
         self._check_gpu_width("mix_at")
         fb = self.__samplewidth * self.__nchannels
@@ -706,6 +747,10 @@ class Sample:
             speed = ev[4] if nev > 4 else None
             pan = ev[5] if nev > 5 else None
             loop = ev[7] if nev > 7 else None
+            region, reverse = None, False
+            if nev > 8:
+                region = ev[8]
+                reverse = bool(ev[9]) if nev > 9 else False
             assert self.samplewidth == other.samplewidth
             assert self.samplerate == other.samplerate
             factors = None                                                      # audioop.tostereo's, of a panned event
@@ -739,6 +784,16 @@ class Sample:
                     raise ValueError("mix_at_many: speed %r leaves no sample rate" % (speed,))
             start = fb * int(rate * seconds)                                    # frame_idx(seconds): Python floats, on the host
             frames = other.__nbytes // (self.__samplewidth * other.nchannels)   # (a panned event: the mono frames, a track frame each)
+            extra = None                                                        # ((first frame, frames) of the region | None, reverse): most events have neither
+            if region is not None:                                              # the event has the region's frames from here on
+                cut = _region_frames(region, rate, None if other is self else frames, other.duration)
+                if other is self:
+                    extra = (region, reverse)                                   # (cut when the event runs)
+                else:
+                    frames = cut[1]
+                    extra = (cut, reverse)
+            elif reverse:
+                extra = (None, True)
             if loop is not None:                                                # (S, E - S, V) in frames; the note has V frames from here on
                 loop = _loop_frames(loop, rate, None if other is self else frames, other.nchannels)
                 frames = loop[2]
@@ -758,14 +813,23 @@ class Sample:
                 fbo = self.__samplewidth * other.nchannels
                 shaped[len(todo)] = (envelope, _envelope_segments(have // fb * fbo, self.__samplewidth, other.nchannels, rate, *envelope[:4]))
             n2 = fb * int(rate * other_seconds) if other_seconds else have     # frame_idx(other_seconds) of what mix_at is handed
-            todo.append((seconds, other, volume, other_seconds, speed, start, min(n2, have), inrate, factors, loop))
-        batch, envs = [], {}                                                    # envs: index into batch -> segment rows
-        for k, (seconds, other, volume, other_seconds, speed, start, n2, inrate, factors, loop) in enumerate(todo):
+            todo.append((seconds, other, volume, other_seconds, speed, start, min(n2, have), inrate, factors, loop, extra))
+        batch, envs, extras = [], {}, {}                                        # envs: index into batch -> segment rows; extras: -> (region, reverse)
+        for k, (seconds, other, volume, other_seconds, speed, start, n2, inrate, factors, loop, extra) in enumerate(todo):
             if other is self:                                                   # (never panned: a panned event's other is mono, its track stereo)
-                self.__mix_events(batch, envs)
-                batch, envs = [], {}
-                if loop is not None:                                            # clip(0.0, loop_end) of the track as it is NOW
-                    first, last = loop[0], min(loop[0] + loop[1], len(self))
+                self.__mix_events(batch, envs, extras)
+                batch, envs, extras = [], {}, {}
+                region, reverse = extra if extra is not None else (None, False)
+                if region is not None:                                          # copy().clip() of the track as it is NOW
+                    end = other.duration if region[1] is None else region[1]
+                    if end < region[0]:
+                        raise ValueError("mix_at_many: region: end (%r s: the track as the events before left it) lies before start (%r s)"
+                                         % (end, region[0]))
+                    other = other.copy().clip(region[0], end)
+                if reverse:
+                    other = other.copy().reverse()
+                if loop is not None:                                            # clip(0.0, loop_end) of the track (its region, reversed) as it is NOW
+                    first, last = loop[0], min(loop[0] + loop[1], len(other))
                     if first >= last:
                         raise ValueError("mix_at_many: loop: no frame between loop_start (frame %d) and loop_end (frame %d) of the track "
                                          "as the events before left it" % (first, last))
@@ -782,8 +846,10 @@ class Sample:
             else:
                 if shaped and k in shaped:
                     envs[len(batch)] = shaped[k][1]
+                if extra is not None:
+                    extras[len(batch)] = extra
                 batch.append((start, other, n2, 1.0 if volume is None else float(volume), inrate, factors, loop))
-        self.__mix_events(batch, envs)
+        self.__mix_events(batch, envs, extras)
         return self
 
     def __unrolled(self, loop_start: int, loop_frames: int, nframes: int) -> "Sample":
@@ -800,13 +866,18 @@ class Sample:
         out.__assemble(parts)
         return out
 
-    def __mix_events(self, batch: Sequence[tuple], envs: dict) -> None:
+    def __mix_events(self, batch: Sequence[tuple], envs: dict, extras: dict) -> None:
         """The events (first byte, other, bytes, factor, inrate, tostereo factors | None, loop | None) -- none of them this sample -- folded in
         order; length -> the furthest end.  inrate != the sample rate: the event plays ``other`` resampled from inrate to the sample
         rate, and bytes counts resampled bytes; tostereo factors: ``other`` is mono, the track stereo, and bytes counts stereo bytes.
         envs: index into batch -> _envelope_segments' rows of the events that have an envelope, cut here where the event is.
         loop: (loop_start, loop_frames, virtual frames) of a looped event, in frames of ``other``; one of them and the list goes to
         sh_mix_events_loop, the events without a loop as rows with loop_frames == 0.
+        extras: index into batch -> (region | None, reverse) of the events that have either.  region: (first frame, frames) of ``other``
+        that the event plays, which is what bytes, loop and the envelope's rows were counted over; it fills src_sample and src_frames
+        of the table the list has anyway.  reverse: one of them and the list goes to
+        sh_mix_events_rev, the rest as rows without the flag; a reversed row names its region as stored, forwards -- a looped one the
+        part of it in front of the loop's end, which is all it plays.
         The table is packed column by column (whole-array numpy operations, not a row per event)."""
         if not batch:
             return
@@ -838,8 +909,12 @@ class Sample:
         rated = bool((inrates != rate).any())
         panned = any(p is not None for p in pans)
         shaped = bool(envs)
-        looped = loops.count(None) != len(loops)
-        table = np.zeros(len(batch), dtype=N.MIX_EVENT_LOOP_DTYPE if looped else N.MIX_EVENT_ENV_DTYPE if shaped else N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
+        turned = cut = False
+        if extras:
+            turned = any(rv for _rg, rv in extras.values())
+            cut = any(rg is not None for rg, _rv in extras.values())
+        looped = turned or loops.count(None) != len(loops)
+        table = np.zeros(len(batch), dtype=N.MIX_EVENT_REV_DTYPE if turned else N.MIX_EVENT_LOOP_DTYPE if looped else N.MIX_EVENT_ENV_DTYPE if shaped else N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
         table["dst_sample"] = starts // w
         table["nsamples"] = nbytes // w
         table["factor"] = factors
@@ -854,10 +929,22 @@ class Sample:
             lr = np.array([p if p is not None else (0.0, 0.0) for p in pans], dtype=np.float64)
             table["left"] = lr[:, 0]
             table["right"] = lr[:, 1]
+        if cut:                                             # a slice of other: where it starts, and the frames every count above was made over
+            nch = np.array([o.nchannels for o in uniq], dtype=np.uint64)[src]
+            at = np.array([i for i, (rg, _rv) in extras.items() if rg is not None], dtype=np.intp)
+            rg = np.array([rg for rg, _rv in extras.values() if rg is not None], dtype=np.uint64)
+            table["src_sample"][at] = rg[:, 0] * nch[at]
+            if rated or panned or shaped or looped:
+                table["src_frames"][at] = rg[:, 1]
         if looped:
             lp = np.array([l if l is not None else (0, 0, 0) for l in loops], dtype=np.uint64)
             table["loop_start"] = lp[:, 0]
             table["loop_frames"] = lp[:, 1]
+            if turned:                                      # a reversed looped row plays the region's LAST loop_end frames: its region starts there
+                rv = np.array([i for i, (_rg, v) in extras.items() if v], dtype=np.intp)
+                table["flags"][rv] = N.MIX_EVENT_REVERSED
+                back = rv[lp[rv, 1] != 0]
+                table["src_sample"][back] += (table["src_frames"][back] - lp[back, 0] - lp[back, 1]) * table["src_channels"][back]
             table["src_frames"] = np.where(lp[:, 1] != 0, lp[:, 2], table["src_frames"])      # a looped row: the note's virtual frames
         if shaped or looped:
             rows = []
@@ -871,7 +958,7 @@ class Sample:
             segtab = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
             for name, col in zip(("end", "mul", "kind", "slope", "numsamples", "offset", "origin"), zip(*rows) if rows else [()] * 7):
                 segtab[name] = col
-            entry = N.lib().sh_mix_events_loop if looped else N.lib().sh_mix_events_env
+            entry = N.lib().sh_mix_events_rev if turned else N.lib().sh_mix_events_loop if looped else N.lib().sh_mix_events_env
             N.check(entry(srcs, len(bufs), table.ctypes.data, len(table), segtab.ctypes.data, len(segtab), w,
                           self.__nchannels, track.handle, total // w))
         elif panned:

@@ -35,7 +35,18 @@ alone -- every tile inside one segment, the uniform path -- and (4) the full env
 of the resampled held note) on every note.  Three forms of the same bytes, checked against the frames unrolled in numpy and then live
 audioop.ratecv / mul / add and the fades in float64: (a) one mix_at_many with loops; (b) the loop of clip / join / speed / clip / envelope
 / at_volume / mix_at it replaces; (c) what there was before loops: an unrolled copy per distinct (instrument, length), made once, then one
-mix_at_many of enveloped events.  --loop --trace: (a)'s and (c)'s one call five times each, for rocprofv3 --kernel-trace."""
+mix_at_many of enveloped events.  --loop --trace: (a)'s and (c)'s one call five times each, for rocprofv3 --kernel-trace.
+
+--reverse: the held notes of --loop with every other note played BACKWARDS (sh_mix_events_rev), every other one of those from a region
+(10 % to 95 % of the instrument) -- a reversed cymbal at many places and pitches.  Three forms of the same bytes, checked against
+audioop.reverse of the byte slice, the frames unrolled in numpy and then live audioop.ratecv / mul / add and the fades in float64: (a) one
+mix_at_many with regions and reversals; (b) the loop of copy().clip().reverse() / clip / join / speed / clip / envelope / at_volume /
+mix_at it replaces; (c) what there was before: a reversed copy per distinct (instrument, region), made once, then one mix_at_many of looped
+events through sh_mix_events_loop -- with both calls' device times: what the reversal in the kernel costs or saves.  Then the same notes with
+no region and no reversal, the list as --loop has it (sh_mix_events_loop: kernels this entry point does not touch), for a run of this commit
+against a run of its parent.  --reverse --trace: (a)'s and (c)'s one call five times each, for rocprofv3 --kernel-trace; then the plain
+song (no speed, no loop: the vector fetch) with every other note reversed against pre-reversed copies played forwards by the same kernel,
+five calls each."""
 import audioop
 import os
 import sys
@@ -530,6 +541,141 @@ def loop_main():
                                                                   " ".join("ok" if x else "FAILED" for x in parity)), flush=True)
 
 
+def rev_song(nevents, span):
+    """loop_song with every other note reversed, every other one of those from a region; the loop sits in what is played"""
+    base, inst, events = loop_song(nevents, span)
+    out = []
+    for n, (s, i, v, sp, e, lp) in enumerate(events):
+        dur = len(inst[i]) // (WIDTH * NCH) / RATE
+        reverse = n % 2 == 1
+        region = (0.1 * dur, 0.95 * dur) if n % 4 == 3 else None
+        out.append((s, i, v, sp, e, lp, region, reverse))
+    return base, inst, out
+
+
+def played(frames, region, reverse):
+    fb = WIDTH * NCH
+    if region is not None:
+        frames = frames[fb * int(RATE * region[0]):fb * int(RATE * region[1])]
+    return audioop.reverse(frames, WIDTH) if reverse else frames
+
+
+def plain_trace(nevents):
+    """The plain reversed fetch in one kernel, for --reverse --trace: the plain song (no speed, no loop) with every other note reversed,
+    then the same bytes from pre-reversed copies played forwards -- with one empty reversed event, so that both lists go to
+    sh_mix_events_rev and the vector fetch of a reversed event stands against that of a forward one in k_seq_16<REV>.  Both checked
+    against live audioop first; five calls each."""
+    base, sources, events = song(nevents, 120.0)
+    both = sources + [audioop.reverse(b, WIDTH) for b in sources]
+    want = oracle(base, both, [(s, i + (len(sources) if k % 2 else 0), v) for k, (s, i, v) in enumerate(events)])
+    samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in both]
+    none = (None,) * 5
+    turned = [(s, samples[i], v) + none + (None, k % 2 == 1) for k, (s, i, v) in enumerate(events)]
+    copies = [(s, samples[i + (len(sources) if k % 2 else 0)], v) for k, (s, i, v) in enumerate(events)]
+    copies.append((0.0, samples[0], None) + none + ((0.0, 0.0), True))
+    parity = []
+    for lst in (turned, copies):
+        track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, NCH).to_device()
+        parity.append(bytes(track.copy().mix_at_many(lst).view_frame_data()) == want)
+        for _ in range(5):
+            track.mix_at_many(lst)
+        N.sync()
+    print("plain song 120 s, %5d events   traced: every other note reversed in the kernel, then forwards from pre-reversed copies, both "
+          "through sh_mix_events_rev   parity: %s" % (nevents, " ".join("ok" if x else "FAILED" for x in parity)), flush=True)
+
+
+def rev_main():
+    N.ensure_init(0)
+    info = N.device_info()
+    print("sequence_rev_ab: SYNTHHIP_SEQ_ALIGN=%s  %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"]), flush=True)
+    for nevents, loop_passes in ((4096, 2), (32768, 1)):
+        base, sources, events = rev_song(nevents, 120.0)
+        samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in sources]
+        start = Sample.from_raw_frames(base, WIDTH, RATE, NCH).to_device()
+        evs = [(s, samples[i], v, None, sp, None, e, lp, rg, rv) for s, i, v, sp, e, lp, rg, rv in events]
+        plain_evs = [ev[:8] for ev in evs]                  # the list without a region or a reversal: sh_mix_events_loop, as before
+        turned = {(i, rg, rv): played(sources[i], rg, rv) for _s, i, _v, _sp, _e, _lp, rg, rv in events}
+        held = {(i, rg, rv, lp): unrolled(turned[(i, rg, rv)], lp) for _s, i, _v, _sp, _e, lp, rg, rv in events}
+        keys = list(held)
+        want = env_oracle(base, [held[k] for k in keys], [(s, keys.index((i, rg, rv, lp)), v, sp, e) for s, i, v, sp, e, lp, rg, rv in events])
+
+        def many():                                         # (a)
+            return start.copy().mix_at_many(evs)
+
+        def loop():                                         # (b)
+            t = start.copy()
+            for seconds, other, volume, _o, speed, _p, env, (ls, le, length), region, reverse in evs:
+                o = other
+                if region is not None:
+                    o = other.copy().clip(region[0], region[1])
+                if reverse:
+                    o = o.copy().reverse()
+                body = o.copy().clip(ls, le)
+                o = o.copy().clip(0.0, le)
+                while o.duration < length:
+                    o.join(body)
+                o.clip(0.0, length)
+                if speed is not None:
+                    o = o.copy().speed(speed)
+                o = o.copy()
+                o.clip(0.0, env[4])
+                o.envelope(*env[:4])
+                t.mix_at(seconds, o if volume is None else o.at_volume(volume))
+            return t
+
+        def materialise():                                  # (c), first half: one clipped, reversed copy per distinct (instrument, region)
+            made = {}
+            for i, rg, rv in turned:
+                o = samples[i]
+                if rg is not None:
+                    o = o.copy().clip(rg[0], rg[1])
+                made[(i, rg, rv)] = o.copy().reverse() if rv else o
+            return made
+
+        def materialised():                                 # (c)
+            made = materialise()
+            return start.copy().mix_at_many([(s, made[(i, rg, rv)], v, None, sp, None, e, lp) for s, i, v, sp, e, lp, rg, rv in events])
+
+        made = materialise()
+        copy_evs = [(s, made[(i, rg, rv)], v, None, sp, None, e, lp) for s, i, v, sp, e, lp, rg, rv in events]
+        if "--trace" in sys.argv[1:]:           # under rocprofv3 --kernel-trace: (a)'s one call, then (c)'s, five times each and nothing else
+            for lst in (evs, copy_evs):
+                track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, NCH).to_device()
+                for _ in range(5):
+                    track.mix_at_many(lst)
+                N.sync()
+            print("rev song 120 s, %5d events   traced: reversed in the kernel, then pre-reversed copies" % nevents, flush=True)
+            plain_trace(nevents)
+            continue
+        parity = [bytes(f().view_frame_data()) == want for f in (many, loop, materialised)]
+        extra = sum(len(o) * NCH * WIDTH for k, o in made.items() if k[1] is not None or k[2])
+        many_ms = median_wall(many, 3, 9)
+        loop_ms = median_wall(loop, 0, loop_passes)
+        mat_ms = median_wall(materialised, 1, 5)
+        mat_only_ms = median_wall(materialise, 1, 5)
+        mat_mix_ms = median_wall(lambda: start.copy().mix_at_many(copy_evs), 3, 9)
+        plain_ms = median_wall(lambda: start.copy().mix_at_many(plain_evs), 3, 9)
+        dev = {}
+        for name, lst in (("a", evs), ("c", copy_evs), ("p", plain_evs)):     # the one call on a track that is long enough: device time (table copy + kernel)
+            track = Sample.from_raw_frames(bytes(len(want)), WIDTH, RATE, NCH).to_device()
+            for _ in range(3):
+                track.mix_at_many(lst)
+            runs = []
+            for _ in range(15):
+                N.sync()
+                N.timer_start()
+                track.mix_at_many(lst)
+                runs.append(N.timer_stop())
+            dev[name] = sorted(runs)[len(runs) // 2]
+        print("rev song 120 s, %5d events   (a) mix_at_many, every other note reversed %9.3f ms   (b) loop of calls %10.3f ms   (c) reversed copies + "
+              "mix_at_many %9.3f ms (= %d copies %.3f ms, %.2f MB extra on the device, + the one call %.3f ms)   a/c %.2fx   b/a %.1fx   device, in "
+              "place: (a) sh_mix_events_rev %.4f ms  (c) sh_mix_events_loop %.4f ms   parity a, b, c: %s"
+              % (nevents, many_ms, loop_ms, mat_ms, len(made), mat_only_ms, extra / 1e6, mat_mix_ms, many_ms / mat_ms, loop_ms / many_ms, dev["a"],
+                 dev["c"], " ".join("ok" if x else "FAILED" for x in parity)), flush=True)
+        print("rev song 120 s, %5d events   the list without a region or a reversal (sh_mix_events_loop)   mix_at_many %9.3f ms   device, in place "
+              "%.4f ms" % (nevents, plain_ms, dev["p"]), flush=True)
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -600,4 +746,4 @@ def main():
 
 
 if __name__ == "__main__":
-    loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
