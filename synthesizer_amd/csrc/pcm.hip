@@ -534,7 +534,7 @@ int sh_pcm_add(const sh_buf* a, size_t a_off, const sh_buf* b, size_t b_off, siz
     if (!a || !b || !out) return sh::set_error(SH_ERR_INVALID, "sh_pcm_add: NULL argument");
     if (width == 3) {
         // audioop.add at width 3: int sum clamped to [-2^23, 2^23 - 1] == the 32-bit saturating add of the samples << 8, >> 8
-        if (nbytes % 3 || (a_off | b_off | out_off) % 3) return sh::set_error(SH_ERR_INVALID, "sh_pcm_add: not a whole number of frames");
+        if (nbytes % 3 || a_off % 3 || b_off % 3 || out_off % 3) return sh::set_error(SH_ERR_INVALID, "sh_pcm_add: not a whole number of frames");   // (each offset: 3 | 6 is no multiple of 3)
         if (a_off > a->bytes || nbytes > a->bytes - a_off || b_off > b->bytes || nbytes > b->bytes - b_off ||
             out_off > out->bytes || nbytes > out->bytes - out_off)
             return sh::set_error(SH_ERR_LENGTH, "sh_pcm_add: range outside buffer (Lengths should be the same)");

@@ -54,8 +54,9 @@ __global__ __launch_bounds__(256) void k_modulate(const T* __restrict__ in, T* _
 
 // Sample.pan(lfo=...): frame i becomes (int(l * (1 - p) / 2), int(r * (1 + p) / 2)) with p = pan[i]; a mono source
 // feeds both sides.  float64 like the Python expression (the halving is exact); a value outside the sample range
-// raises upstream (array assignment) -> flag.
-template <typename T, int NCH>
+// raises upstream (array assignment) -> flag.  PAIR: the frame is stored as one two-sample vector (out aligned to 2 * sizeof(T),
+// the host's decision); otherwise as two samples.
+template <typename T, int NCH, bool PAIR = true>
 __global__ __launch_bounds__(256) void k_pan_lfo(const T* __restrict__ in, T* __restrict__ out, size_t nframes,
                                                  const double* __restrict__ pan, int* flag) {
     const size_t i = sh::block_id() * 256 + threadIdx.x;
@@ -68,7 +69,8 @@ __global__ __launch_bounds__(256) void k_pan_lfo(const T* __restrict__ in, T* __
     if (!(tr >= LO && tr <= HI)) { *flag = 1; tr = tr > HI ? HI : LO; }
     typedef T pair_t __attribute__((ext_vector_type(2)));
     pair_t o = {(T)(long long)tl, (T)(long long)tr};
-    reinterpret_cast<pair_t*>(out)[i] = o;
+    if constexpr (PAIR) reinterpret_cast<pair_t*>(out)[i] = o;
+    else { out[2 * i] = o[0]; out[2 * i + 1] = o[1]; }
 }
 
 // out[i] = in[i] / divisor in float64              (Sample.get_frames_as_floats; waveform modulators)
@@ -95,22 +97,27 @@ __global__ __launch_bounds__(256) void k_reverse(const T* __restrict__ in, T* __
     out[i] = in[n - 1 - i];
 }
 
-// stereo -> mono: fbound(l*lfactor + r*rfactor)  (audioop.tomono); F frames per thread (16-byte loads)
-template <typename T, int F>
+// stereo -> mono: fbound(l*lfactor + r*rfactor)  (audioop.tomono); F frames per thread (16-byte loads).  The host launches F > 1 only
+// with in aligned to 16 and out to 8 bytes; PAIR (F == 1): the frame is loaded as one two-sample vector (in aligned to 2 * sizeof(T)),
+// otherwise as two samples.
+template <typename T, int F, bool PAIR = true>
 __global__ __launch_bounds__(256) void k_tomono(const T* __restrict__ in, T* __restrict__ out, size_t nunits, double lf, double rf) {
     typedef T vin __attribute__((ext_vector_type(2 * F)));
     typedef T vout __attribute__((ext_vector_type(F)));
     const size_t i = sh::block_id() * 256 + threadIdx.x;
     if (i >= nunits) return;
-    const vin v = reinterpret_cast<const vin*>(in)[i];
+    vin v;
+    if constexpr (F == 1 && !PAIR) { v[0] = in[2 * i]; v[1] = in[2 * i + 1]; }
+    else v = reinterpret_cast<const vin*>(in)[i];
     vout r;
 #pragma unroll
     for (int f = 0; f < F; ++f) r[f] = (T)fbound((double)v[2 * f] * lf + (double)v[2 * f + 1] * rf, Lim<T>::lo, Lim<T>::hi);
     if (F == 1) out[i] = r[0]; else reinterpret_cast<vout*>(out)[i] = r;
 }
 
-// mono -> stereo: (fbound(v*lfactor), fbound(v*rfactor))   (audioop.tostereo)
-template <typename T, int F>
+// mono -> stereo: (fbound(v*lfactor), fbound(v*rfactor))   (audioop.tostereo).  The host launches F > 1 only with in aligned to 8
+// and out to 16 bytes; PAIR (F == 1): the frame is stored as one two-sample vector (out aligned to 2 * sizeof(T)), otherwise as two samples.
+template <typename T, int F, bool PAIR = true>
 __global__ __launch_bounds__(256) void k_tostereo(const T* __restrict__ in, T* __restrict__ out, size_t nunits, double lf, double rf) {
     typedef T vin __attribute__((ext_vector_type(F)));
     typedef T vout __attribute__((ext_vector_type(2 * F)));
@@ -125,7 +132,8 @@ __global__ __launch_bounds__(256) void k_tostereo(const T* __restrict__ in, T* _
         r[2 * f] = (T)fbound(x * lf, Lim<T>::lo, Lim<T>::hi);
         r[2 * f + 1] = (T)fbound(x * rf, Lim<T>::lo, Lim<T>::hi);
     }
-    reinterpret_cast<vout*>(out)[i] = r;
+    if constexpr (F == 1 && !PAIR) { out[2 * i] = r[0]; out[2 * i + 1] = r[1]; }
+    else reinterpret_cast<vout*>(out)[i] = r;
 }
 
 // width conversion through the 32-bit form (GETSAMPLE32 / SETSAMPLE32)   (audioop.lin2lin)
@@ -524,7 +532,7 @@ extern "C" {
 int sh_pcm_mul(const sh_buf* in, size_t in_off, size_t nbytes, int width, double factor, sh_buf* out, size_t out_off) {
     SH_REQUIRE_INIT();
     if (width == 3) {
-        if (nbytes % 3 || (in_off | out_off) % 3) return sh::set_error(SH_ERR_INVALID, "sh_pcm_mul: not a whole number of frames");
+        if (nbytes % 3 || in_off % 3 || out_off % 3) return sh::set_error(SH_ERR_INVALID, "sh_pcm_mul: not a whole number of frames");      // (each offset: 3 | 6 is no multiple of 3)
         const size_t n = nbytes / 3;
         return via32(in, in_off, n, 8, out, out_off, n, 8, true, "sh_pcm_mul",
                      [&](sh_buf* a, sh_buf* o) { return sh_pcm_mul(a, 0, n * 4, 4, factor, o, 0); });
@@ -607,12 +615,12 @@ int sh_pcm_pan_lfo(const sh_buf* in, size_t nframes, int width, int nchannels, c
     sh::State& S = sh::state();
     rc = dispatch_width(width, [&](auto tag) {
         typedef decltype(tag) T;
-        if (nchannels == 1)
-            hipLaunchKernelGGL((k_pan_lfo<T, 1>), sh::grid1d(nframes, 256), dim3(256), 0, S.stream, (const T*)in->ptr, (T*)out->ptr, nframes,
-                               (const double*)pan_f64->ptr, S.flag);
-        else
-            hipLaunchKernelGGL((k_pan_lfo<T, 2>), sh::grid1d(nframes, 256), dim3(256), 0, S.stream, (const T*)in->ptr, (T*)out->ptr, nframes,
-                               (const double*)pan_f64->ptr, S.flag);
+        const bool pair = ((uintptr_t)out->ptr & (2 * sizeof(T) - 1)) == 0;       // a view may start on any sample: then two stores per frame
+#define SH_PAN(NCH_, PAIR_) hipLaunchKernelGGL((k_pan_lfo<T, NCH_, PAIR_>), sh::grid1d(nframes, 256), dim3(256), 0, S.stream, (const T*)in->ptr, \
+                                               (T*)out->ptr, nframes, (const double*)pan_f64->ptr, S.flag)
+        if (nchannels == 1) { if (pair) SH_PAN(1, true); else SH_PAN(1, false); }
+        else { if (pair) SH_PAN(2, true); else SH_PAN(2, false); }
+#undef SH_PAN
         hipError_t e = hipGetLastError();
         return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_pan_lfo");
     });
@@ -701,10 +709,16 @@ int sh_pcm_tomono(const sh_buf* in, size_t nframes, int width, double lfactor, d
     return dispatch_width(width, [&](auto tag) {
         typedef decltype(tag) T;
         constexpr int F = 8 / sizeof(T);                       // frames per 16-byte load
-        const size_t nvec = nframes / F, done = nvec * F;
+        // (a view may start on any sample: the vector kernel only where its 16-byte loads and 8-byte stores are aligned, the
+        // one-frame kernel's two-sample load only where a frame is)
+        const bool aligned = ((uintptr_t)in->ptr & 15) == 0 && ((uintptr_t)out->ptr & 7) == 0;
+        const bool pair = ((uintptr_t)in->ptr & (2 * sizeof(T) - 1)) == 0;
+        const size_t nvec = aligned ? nframes / F : 0, done = nvec * F;
         if (nvec) hipLaunchKernelGGL((k_tomono<T, F>), sh::grid1d(nvec, 256), dim3(256), 0, st, (const T*)in->ptr, (T*)out->ptr, nvec, lfactor, rfactor);
-        if (nframes > done) hipLaunchKernelGGL((k_tomono<T, 1>), sh::grid1d(nframes - done, 256), dim3(256), 0, st,
-                                               (const T*)in->ptr + 2 * done, (T*)out->ptr + done, nframes - done, lfactor, rfactor);
+        if (nframes > done && pair) hipLaunchKernelGGL((k_tomono<T, 1>), sh::grid1d(nframes - done, 256), dim3(256), 0, st,
+                                                       (const T*)in->ptr + 2 * done, (T*)out->ptr + done, nframes - done, lfactor, rfactor);
+        else if (nframes > done) hipLaunchKernelGGL((k_tomono<T, 1, false>), sh::grid1d(nframes - done, 256), dim3(256), 0, st,
+                                                    (const T*)in->ptr + 2 * done, (T*)out->ptr + done, nframes - done, lfactor, rfactor);
         hipError_t e = hipGetLastError();
         return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_tomono");
     });
@@ -723,10 +737,15 @@ int sh_pcm_tostereo(const sh_buf* in, size_t nframes, int width, double lfactor,
     return dispatch_width(width, [&](auto tag) {
         typedef decltype(tag) T;
         constexpr int F = 8 / sizeof(T);                       // frames per 16-byte store
-        const size_t nvec = nframes / F, done = nvec * F;
+        // (as sh_pcm_tomono: 8-byte loads and 16-byte stores only where aligned, the one-frame kernel's two-sample store only where a frame is)
+        const bool aligned = ((uintptr_t)in->ptr & 7) == 0 && ((uintptr_t)out->ptr & 15) == 0;
+        const bool pair = ((uintptr_t)out->ptr & (2 * sizeof(T) - 1)) == 0;
+        const size_t nvec = aligned ? nframes / F : 0, done = nvec * F;
         if (nvec) hipLaunchKernelGGL((k_tostereo<T, F>), sh::grid1d(nvec, 256), dim3(256), 0, st, (const T*)in->ptr, (T*)out->ptr, nvec, lfactor, rfactor);
-        if (nframes > done) hipLaunchKernelGGL((k_tostereo<T, 1>), sh::grid1d(nframes - done, 256), dim3(256), 0, st,
-                                               (const T*)in->ptr + done, (T*)out->ptr + 2 * done, nframes - done, lfactor, rfactor);
+        if (nframes > done && pair) hipLaunchKernelGGL((k_tostereo<T, 1>), sh::grid1d(nframes - done, 256), dim3(256), 0, st,
+                                                       (const T*)in->ptr + done, (T*)out->ptr + 2 * done, nframes - done, lfactor, rfactor);
+        else if (nframes > done) hipLaunchKernelGGL((k_tostereo<T, 1, false>), sh::grid1d(nframes - done, 256), dim3(256), 0, st,
+                                                    (const T*)in->ptr + done, (T*)out->ptr + 2 * done, nframes - done, lfactor, rfactor);
         hipError_t e = hipGetLastError();
         return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_tostereo");
     });

@@ -333,3 +333,62 @@ def scan_adversarial(n, tile, thread, pos, big_log2, rng, negative=False):
     if int(k[tile * SCAN_TILE:group].sum()) % 2 == 0:
         k[group - 1] += 1
     return k, int(rng.integers(1, 1 << 20)), at
+
+
+# ---- the PCM entry points through windows of larger buffers (tests/test_gpu_pcm_views.py) -----------------------------------
+# Every operand lives in a DeviceBuffer.view of a parent that is filled with a sentinel byte and keeps PCM_GUARD bytes free on both
+# sides of the window; the window starts `a` bytes after a 16-byte boundary of the parent, so `a` mod 16 is the residue of the device
+# pointer the kernels see.
+PCM_GUARD = 64
+PCM_IN_SENTINEL = 0xA5
+PCM_OUT_SENTINEL = 0x5A
+
+
+def pcm_view_call(N, inputs, out_nbytes, a_out, call, out_view_nbytes=None, untouched=False):
+    """Run `call(in_views, out_view) -> rc` on windows of sentinel-filled parents and return (rc, the out_nbytes result bytes).
+
+    inputs: a list of (data, a) or (data, a, view_nbytes): `data` (bytes) is uploaded at byte PCM_GUARD + a of its parent and the
+    window covers it (or only its first view_nbytes bytes: a window shorter than the request, inside a parent that holds all of it).
+    out_nbytes / a_out: the same for the destination (None: the call has none, out_view is None); out_view_nbytes: a shorter window.
+    Asserted after the call: every window's device pointer has the residue its case intended, mod 16; every input parent is
+    unchanged; the destination parent still holds its sentinel outside the window -- everywhere with untouched=True (a refusal)."""
+    import ctypes as C
+    L = N.lib()
+    parents, views, images = [], [], []
+    for item in inputs:
+        data, a = bytes(item[0]), int(item[1])
+        vbytes = len(data) if len(item) < 3 or item[2] is None else int(item[2])
+        img = np.full(PCM_GUARD + a + max(len(data), vbytes) + PCM_GUARD, PCM_IN_SENTINEL, dtype=np.uint8)
+        img[PCM_GUARD + a:PCM_GUARD + a + len(data)] = np.frombuffer(data, dtype=np.uint8)
+        parent = N.DeviceBuffer.from_array(img)
+        view = parent.view(PCM_GUARD + a, vbytes)
+        assert (C.cast(L.sh_buf_devptr(view.handle), C.c_void_p).value or 0) % 16 == a % 16, "input window not at the intended residue"
+        parents.append(parent)
+        views.append(view)
+        images.append(img)
+    out_parent = out_view = out_img = None
+    if out_nbytes is not None:
+        vbytes = out_nbytes if out_view_nbytes is None else int(out_view_nbytes)
+        out_img = np.full(PCM_GUARD + a_out + max(out_nbytes, vbytes) + PCM_GUARD, PCM_OUT_SENTINEL, dtype=np.uint8)
+        out_parent = N.DeviceBuffer.from_array(out_img)
+        out_view = out_parent.view(PCM_GUARD + a_out, vbytes)
+        assert (C.cast(L.sh_buf_devptr(out_view.handle), C.c_void_p).value or 0) % 16 == a_out % 16, "output window not at the intended residue"
+    try:
+        rc = call(views, out_view)
+        N.sync()
+        for parent, img in zip(parents, images):
+            assert parent.download(np.uint8, img.size).tobytes() == img.tobytes(), "an input parent was written to"
+        result = None
+        if out_parent is not None:
+            got = out_parent.download(np.uint8, out_img.size)
+            lo, hi = PCM_GUARD + a_out, PCM_GUARD + a_out + (0 if untouched else out_view.nbytes)
+            stray = np.flatnonzero(np.concatenate([got[:lo], got[hi:]]) != PCM_OUT_SENTINEL)
+            assert stray.size == 0, "destination parent written outside the window: byte %d relative to the window's start, %d bytes in all" % (
+                int(stray[0]) - lo if stray[0] < lo else int(stray[0]) - lo + (hi - lo), stray.size)
+            result = got[lo:lo + out_nbytes].tobytes()
+        return rc, result
+    finally:
+        for v in views + ([out_view] if out_view is not None else []):
+            v.free()
+        for p in parents + ([out_parent] if out_parent is not None else []):
+            p.free()

@@ -276,14 +276,38 @@ def test_level_db_matches_audioop(gpu, width, nch):
     assert e.level_db_peak == re_.level_db_peak and e.level_db_rms == re_.level_db_rms
 
 
+def _off_grid(gpu, x, width, rate, nch, offset):
+    """(sample, reference): the sample's device storage is a window `offset` bytes into a parent buffer -- asserted to lie that far
+    off the 16-byte grid, which a fresh allocation (Sample.clip's result included) never does."""
+    import ctypes as C
+    s, r = _pair(x, width, rate, nch)
+    parent = gpu.DeviceBuffer(offset + x.nbytes + 16)
+    parent.upload(x, offset)
+    view = parent.view(offset, x.nbytes)
+    assert (C.cast(gpu.lib().sh_buf_devptr(view.handle), C.c_void_p).value or 0) % 16 == offset
+    s._set_device(view, x.nbytes)
+    return s, r
+
+
 def test_level_db_unaligned_device_views(gpu):
-    """Stereo statistics of a sample whose device storage does not start on a 16-byte boundary (after clip)."""
+    """Statistics of a sample whose device storage does not start on a 16-byte boundary: stereo int16 at byte 4 (the all-scalar
+    path of k_stats_stereo), mono int16 at byte 2 and mono int8 at byte 1 (that of k_absmax_sumsq)."""
     rng = np.random.default_rng(99)
     x = _rand(rng, 2, 2 * 30011)
     s, r = _pair(x, 2, 8000, 2)
     s.to_device()
-    _same(s.clip(0.000125, 3.5), r.clip(0.000125, 3.5))          # drops one frame: 4-byte offset
+    _same(s.clip(0.000125, 3.5), r.clip(0.000125, 3.5))          # drops one frame (the result is a fresh, aligned buffer: this tests clip)
     assert s.level_db_peak == r.level_db_peak and s.level_db_rms == r.level_db_rms
+    x[1::2] = (x[1::2] * 0.25).astype(np.int16)                  # channels at different levels
+    s, r = _off_grid(gpu, x, 2, 8000, 2, 4)
+    assert s.level_db_peak == r.level_db_peak and s.level_db_rms == r.level_db_rms
+    assert s.level_db_peak[0] != s.level_db_peak[1]
+    for width, offset in ((2, 2), (1, 1)):
+        m = _rand(rng, width, 30011, 0.7)
+        s, r = _off_grid(gpu, m, width, 8000, 1, offset)
+        assert s.level_db_peak == r.level_db_peak and s.level_db_rms == r.level_db_rms
+        assert s.level_db_peak_mono == r.level_db_peak_mono and s.level_db_rms_mono == r.level_db_rms_mono
+        assert s.peak() == int(np.abs(m.astype(np.int64)).max())
 
 
 def test_level_meter_tracks_like_upstream(gpu):
