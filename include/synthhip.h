@@ -427,7 +427,8 @@ int sh_mix_chain_i16(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint
  * synthplayer/sample.py Sample.stereo -> audioop.tostereo(frames, 2, lf, rf), [RECALL]): out frame i = (L, R) with
  * L = add(add(tostereo_l(c0), tostereo_l(c1)), ...) -- per voice and channel fbound(sample * factor) (clamp, then floor), then the
  * saturating chain in voice order.  The stereo rows are never materialised: 2 bytes are read per voice-sample, 4 written per frame.
- * factors_lr: device buffer of nvoices x (left, right) doubles.  chunks[v*stride + i] int16 mono; out: nframes x 2 int16. */
+ * factors_lr: device buffer of nvoices x (left, right) doubles, 8-byte aligned (a view 2 or 4 bytes off that grid: SH_ERR_INVALID,
+ * here and in the _parts form).  chunks[v*stride + i] int16 mono; out: nframes x 2 int16. */
 int sh_mix_chain_pan_i16(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nframes, const sh_buf* factors_lr, sh_buf* out);
 /* The same fold with every chunk read where its sample lives (no staging copy): source v contributes
  * srcs[v][sample_offsets[v] .. +nsamples_each[v]) and silence after that, up to nsamples; the result goes to
@@ -461,7 +462,8 @@ typedef struct sh_mix_event {      /* one placed sample; all positions in SAMPLE
 } sh_mix_event;                    /* 40 bytes */
 /* track[0 .. track_samples) = the events applied in order, in place.  No src may be `track`.  SH_ERR_INVALID, and nothing launched,
  * for: a source index >= nsrc, a range outside its source or the track, a non-finite factor, reserved != 0, a width other than
- * 1 - 4, a source that is (or overlaps) the track, more than 2^32 - 65536 track samples. */
+ * 1 - 4, a source that is (or overlaps) the track, more than 2^32 - 65536 track samples.  "The track" is the bytes of its first
+ * track_samples samples: a source that is a view of the same allocation in front of them or behind them does not overlap it. */
 int sh_mix_events(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event* events, uint32_t nevents,
                   int width, sh_buf* track, size_t track_samples);
 

@@ -130,7 +130,8 @@ __global__ __launch_bounds__(256) void k_chain_parts(const int2v* parts, uint32_
 }
 
 // Where a split kernel's voice v gives its 8 samples from s0.  whole(): (uniform) every voice's 8 samples are one aligned vector --
-// decided once, outside the voice loop; tail(): the ragged form, zeros past the end.
+// decided once, outside the voice loop; tail(): the ragged form, zeros past the end.  vec: every row starts on the vector's grid --
+// decided on the host (rows_vec) from the row pointer AND the stride: 16 bytes for the eight mono samples, 8 for the four PAN frames.
 // Strided rows (PAN forms, sh_mix_chain_pan_i16: the rows are MONO voices and each enters the fold as Sample.stereo(lf, rf) of itself,
 // shc::stereo on the four mono frames of eight stereo samples; the factors of a voice are wave-uniform: scalar loads).
 template <bool NT>
@@ -138,7 +139,8 @@ struct RowSrc {
     const short* __restrict__ chunks;
     size_t stride;
     const double2* __restrict__ pan;
-    __device__ __forceinline__ bool whole(uint32_t s0, uint32_t nsamples) const { return s0 + 7 < nsamples && (stride & (pan ? 3 : 7)) == 0; }
+    uint32_t vec;
+    __device__ __forceinline__ bool whole(uint32_t s0, uint32_t nsamples) const { return s0 + 7 < nsamples && vec != 0; }
     __device__ __forceinline__ short8v load(uint32_t v, uint32_t s0) const {
         if (pan) {                                       // (uniform) s0 = the first of eight STEREO samples: four mono frames from s0 / 2
             const double2 f = pan[v];
@@ -232,9 +234,9 @@ __device__ __forceinline__ void mix_chain_split(const Src src, uint32_t nvoices,
 template <int WAVES, int COLS, bool NT, bool PARTS = false>
 __global__ __launch_bounds__(WAVES * 64) void k_mix_chain_i16(const short* __restrict__ chunks, uint32_t nvoices,
                                                               size_t stride, uint32_t nsamples,
-                                                              short* __restrict__ out, const double2* __restrict__ pan = nullptr,
+                                                              short* __restrict__ out, uint32_t vec, const double2* __restrict__ pan = nullptr,
                                                               int2v* __restrict__ maps = nullptr) {
-    mix_chain_split<WAVES, COLS, PARTS>(RowSrc<NT>{chunks, stride, pan}, nvoices, nsamples, out, maps);
+    mix_chain_split<WAVES, COLS, PARTS>(RowSrc<NT>{chunks, stride, pan, vec}, nvoices, nsamples, out, maps);
 }
 
 template <int WAVES>
@@ -492,7 +494,8 @@ int sh_quantize_clip_f32(const sh_buf* in_f32, size_t n, double scale, sh_buf* o
     if (!n) return SH_OK;
     {
         hipStream_t st = sh::state().stream;
-        const size_t nvec = n / 4, done = nvec * 4;
+        const bool aligned = ((uintptr_t)in_f32->ptr & 15) == 0 && ((uintptr_t)out_i16->ptr & 7) == 0;      // (a ring slot of odd length is not)
+        const size_t nvec = aligned ? n / 4 : 0, done = nvec * 4;
         if (nvec) hipLaunchKernelGGL(k_quantize_f32_i16_vec, sh::grid1d(nvec, 512), dim3(256), 0, st, (const float4v*)in_f32->ptr, nvec, scale, (short4v*)out_i16->ptr, sh::state().flag, 1);
         if (n > done) hipLaunchKernelGGL(k_quantize<short>, sh::grid1d(n - done, 256), dim3(256), 0, st,
                                          (const float*)in_f32->ptr + done, n - done, scale, -32768.0, 32767.0, (short*)out_i16->ptr + done, sh::state().flag, 1);
@@ -596,6 +599,11 @@ int sh_pcm_add_host(const void* a, const void* b, size_t nbytes, int width, void
     return SH_OK;
 }
 
+// (uniform, host) RowSrc::vec: whether every row of a strided chunk array starts on the grid of the split kernels' vector load.
+static uint32_t rows_vec(const void* chunks, size_t stride, bool pan) {
+    return (stride & (pan ? 3 : 7)) == 0 && ((uintptr_t)chunks & (pan ? 7 : 15)) == 0;
+}
+
 // The checks of the four strided chain entry points: nvoices rows of nframes samples (pan: mono frames, two output values each) at
 // stride; out holds an int16 result (unit 2) or a map (unit 8, parts_out) per output value.  1: an empty call, nothing to launch.
 static int chain_rows_check(const char* who, const sh_buf* chunks, uint32_t nvoices, size_t stride, uint32_t nframes,
@@ -608,6 +616,7 @@ static int chain_rows_check(const char* who, const sh_buf* chunks, uint32_t nvoi
     if (stride < nframes || chunks->bytes / 2 < (size_t)(nvoices - 1) * stride + nframes)
         return sh::set_error(SH_ERR_INVALID, "%s: chunk buffer too small", who);
     if (pan && factors_lr->bytes / 16 < nvoices) return sh::set_error(SH_ERR_INVALID, "%s: one (left, right) pair of doubles per voice", who);
+    if (pan && ((uintptr_t)factors_lr->ptr & 7)) return sh::set_error(SH_ERR_INVALID, "%s: factors_lr not 8-byte aligned", who);
     const size_t nvalues = (size_t)nframes * (pan ? 2 : 1);
     if (unit == 8 && (out->bytes / 8 < nvalues || ((uintptr_t)out->ptr & 7)))
         return sh::set_error(SH_ERR_INVALID, "%s: parts_out too small or not 8-byte aligned", who);
@@ -627,7 +636,7 @@ int sh_mix_chain_i16(const sh_buf* chunks, uint32_t nvoices, size_t stride, uint
     const bool stream = (size_t)nvoices * nsamples * 2 > sh::STREAM_BYTES;           // rows beyond the Infinity Cache: streaming loads
     // (the split kernel keeps plain loads: 1024 x 96 000 samples = 197 MB ran 13 % slower with streaming ones)
 #define SH_CHAIN(W_, C_) hipLaunchKernelGGL((k_mix_chain_i16<W_, C_, false>), sh::grid1d(nsamples, 512 * C_), dim3(W_ * 64), 0, st, \
-                                            (const short*)chunks->ptr, nvoices, stride, nsamples, (short*)out->ptr)
+                                            (const short*)chunks->ptr, nvoices, stride, nsamples, (short*)out->ptr, rows_vec(chunks->ptr, stride, false))
 #define SH_DIRECT_S(S_, W_, INF_, NTS_) do { \
         if (stream) hipLaunchKernelGGL((k_mix_chain_direct_s<S_, W_, INF_, true, NTS_>), sh::grid1d(nsamples, W_ * 64 * S_), dim3(W_ * 64), 0, st, (const short*)chunks->ptr, nvoices, stride, nsamples, (short*)out->ptr); \
         else hipLaunchKernelGGL((k_mix_chain_direct_s<S_, W_, INF_, false, NTS_>), sh::grid1d(nsamples, W_ * 64 * S_), dim3(W_ * 64), 0, st, (const short*)chunks->ptr, nvoices, stride, nsamples, (short*)out->ptr); } while (0)
@@ -656,9 +665,9 @@ int sh_mix_chain_pan_i16(const sh_buf* chunks, uint32_t nvoices, size_t stride, 
         if (stream) hipLaunchKernelGGL((k_mix_chain_pan_direct_s<4, 4, 8, true>), sh::grid1d(nframes, 256 * 4), dim3(256), 0, st, in, nvoices, stride, nframes, fac, (short*)out->ptr);
         else hipLaunchKernelGGL((k_mix_chain_pan_direct_s<4, 4, 8, false>), sh::grid1d(nframes, 256 * 4), dim3(256), 0, st, in, nvoices, stride, nframes, fac, (short*)out->ptr);
     } else if (nvoices < 64) {
-        hipLaunchKernelGGL((k_mix_chain_i16<2, 1, false>), sh::grid1d(nsamples, 512), dim3(128), 0, st, in, nvoices, stride, nsamples, (short*)out->ptr, fac);
+        hipLaunchKernelGGL((k_mix_chain_i16<2, 1, false>), sh::grid1d(nsamples, 512), dim3(128), 0, st, in, nvoices, stride, nsamples, (short*)out->ptr, rows_vec(in, stride, true), fac);
     } else {
-        hipLaunchKernelGGL((k_mix_chain_i16<8, 1, false>), sh::grid1d(nsamples, 512), dim3(512), 0, st, in, nvoices, stride, nsamples, (short*)out->ptr, fac);
+        hipLaunchKernelGGL((k_mix_chain_i16<8, 1, false>), sh::grid1d(nsamples, 512), dim3(512), 0, st, in, nvoices, stride, nsamples, (short*)out->ptr, rows_vec(in, stride, true), fac);
     }
     SH_CHECK_LAUNCH("k_mix_chain_pan");
     return SH_OK;
@@ -674,7 +683,7 @@ int sh_mix_chain_i16_parts(const sh_buf* chunks, uint32_t nvoices, size_t stride
     // the split kernel throughout (the direct loops keep no map); long rows: one voice range per wave, eight columns per workgroup
     const uint32_t columns = (uint32_t)sh::div_up(nsamples, 512);
 #define SH_CHAIN_PARTS(W_, C_) hipLaunchKernelGGL((k_mix_chain_i16<W_, C_, false, true>), sh::grid1d(nsamples, 512 * C_), dim3(W_ * 64), 0, st, \
-                                                  in, nvoices, stride, nsamples, (short*)nullptr, (const double2*)nullptr, maps)
+                                                  in, nvoices, stride, nsamples, (short*)nullptr, rows_vec(in, stride, false), (const double2*)nullptr, maps)
     if (nvoices < 64) SH_CHAIN_PARTS(2, 1);
     else if (columns >= 1536) SH_CHAIN_PARTS(8, 8);
     else if (columns >= 512) SH_CHAIN_PARTS(8, 2);
@@ -693,8 +702,8 @@ int sh_mix_chain_pan_i16_parts(const sh_buf* chunks, uint32_t nvoices, size_t st
     const double2* fac = (const double2*)factors_lr->ptr;
     const uint32_t nsamples = 2 * nframes;
     int2v* maps = (int2v*)parts_out->ptr;
-    if (nvoices < 64) hipLaunchKernelGGL((k_mix_chain_i16<2, 1, false, true>), sh::grid1d(nsamples, 512), dim3(128), 0, st, in, nvoices, stride, nsamples, (short*)nullptr, fac, maps);
-    else hipLaunchKernelGGL((k_mix_chain_i16<8, 1, false, true>), sh::grid1d(nsamples, 512), dim3(512), 0, st, in, nvoices, stride, nsamples, (short*)nullptr, fac, maps);
+    if (nvoices < 64) hipLaunchKernelGGL((k_mix_chain_i16<2, 1, false, true>), sh::grid1d(nsamples, 512), dim3(128), 0, st, in, nvoices, stride, nsamples, (short*)nullptr, rows_vec(in, stride, true), fac, maps);
+    else hipLaunchKernelGGL((k_mix_chain_i16<8, 1, false, true>), sh::grid1d(nsamples, 512), dim3(512), 0, st, in, nvoices, stride, nsamples, (short*)nullptr, rows_vec(in, stride, true), fac, maps);
     SH_CHECK_LAUNCH("k_mix_chain_pan(parts)");
     return SH_OK;
 }

@@ -344,22 +344,30 @@ PCM_IN_SENTINEL = 0xA5
 PCM_OUT_SENTINEL = 0x5A
 
 
-def pcm_view_call(N, inputs, out_nbytes, a_out, call, out_view_nbytes=None, untouched=False):
+def pcm_view_call(N, inputs, out_nbytes, a_out, call, out_view_nbytes=None, untouched=False, guards=None):
     """Run `call(in_views, out_view) -> rc` on windows of sentinel-filled parents and return (rc, the out_nbytes result bytes).
 
     inputs: a list of (data, a) or (data, a, view_nbytes): `data` (bytes) is uploaded at byte PCM_GUARD + a of its parent and the
     window covers it (or only its first view_nbytes bytes: a window shorter than the request, inside a parent that holds all of it).
-    out_nbytes / a_out: the same for the destination (None: the call has none, out_view is None); out_view_nbytes: a shorter window.
+    out_nbytes / a_out: the same for the destination (None: the call has none, out_view is None); out_view_nbytes: a shorter window,
+    or a longer one whose bytes behind out_nbytes must keep their sentinel.
     Asserted after the call: every window's device pointer has the residue its case intended, mod 16; every input parent is
-    unchanged; the destination parent still holds its sentinel outside the window -- everywhere with untouched=True (a refusal)."""
+    unchanged; the destination parent still holds its sentinel outside the window -- everywhere with untouched=True (a refusal).
+    guards: per input None or (before, after), bytes written over the sentinel immediately in front of and behind `data` (at most
+    PCM_GUARD each): what a kernel that reads outside its range would see."""
     import ctypes as C
     L = N.lib()
     parents, views, images = [], [], []
-    for item in inputs:
+    for k, item in enumerate(inputs):
         data, a = bytes(item[0]), int(item[1])
         vbytes = len(data) if len(item) < 3 or item[2] is None else int(item[2])
         img = np.full(PCM_GUARD + a + max(len(data), vbytes) + PCM_GUARD, PCM_IN_SENTINEL, dtype=np.uint8)
         img[PCM_GUARD + a:PCM_GUARD + a + len(data)] = np.frombuffer(data, dtype=np.uint8)
+        if guards is not None and guards[k] is not None:
+            before, after = bytes(guards[k][0]), bytes(guards[k][1])
+            assert len(before) <= PCM_GUARD and len(after) <= PCM_GUARD
+            img[PCM_GUARD + a - len(before):PCM_GUARD + a] = np.frombuffer(before, dtype=np.uint8)
+            img[PCM_GUARD + a + len(data):PCM_GUARD + a + len(data) + len(after)] = np.frombuffer(after, dtype=np.uint8)
         parent = N.DeviceBuffer.from_array(img)
         view = parent.view(PCM_GUARD + a, vbytes)
         assert (C.cast(L.sh_buf_devptr(view.handle), C.c_void_p).value or 0) % 16 == a % 16, "input window not at the intended residue"
@@ -381,7 +389,8 @@ def pcm_view_call(N, inputs, out_nbytes, a_out, call, out_view_nbytes=None, unto
         result = None
         if out_parent is not None:
             got = out_parent.download(np.uint8, out_img.size)
-            lo, hi = PCM_GUARD + a_out, PCM_GUARD + a_out + (0 if untouched else out_view.nbytes)
+            # (a window longer than the result: its surplus behind out_nbytes is guard as well)
+            lo, hi = PCM_GUARD + a_out, PCM_GUARD + a_out + (0 if untouched else min(out_view.nbytes, out_nbytes))
             stray = np.flatnonzero(np.concatenate([got[:lo], got[hi:]]) != PCM_OUT_SENTINEL)
             assert stray.size == 0, "destination parent written outside the window: byte %d relative to the window's start, %d bytes in all" % (
                 int(stray[0]) - lo if stray[0] < lo else int(stray[0]) - lo + (hi - lo), stray.size)
@@ -392,3 +401,39 @@ def pcm_view_call(N, inputs, out_nbytes, a_out, call, out_view_nbytes=None, unto
             v.free()
         for p in parents + ([out_parent] if out_parent is not None else []):
             p.free()
+
+
+def pcm_track_call(N, sources, base, a, call, surplus=0, untouched=False):
+    """The in-place form (the placed-sample mixer): `base` (bytes) is uploaded at byte PCM_GUARD + a of a parent filled with
+    PCM_OUT_SENTINEL, the window covers it and `surplus` bytes behind it; `sources` (bytes each) are fresh buffers.  Runs
+    `call(source_buffers, window, parent) -> rc` and returns (rc, the len(base) bytes of the track).  Asserted after the call: the
+    window's pointer has residue a mod 16; the parent still holds its sentinel in front of the window, in the window's surplus and
+    behind it; every source is unchanged; with untouched=True (a refusal) the track's bytes are still `base`."""
+    import ctypes as C
+    L = N.lib()
+    base = bytes(base)
+    img = np.full(PCM_GUARD + a + len(base) + surplus + PCM_GUARD, PCM_OUT_SENTINEL, dtype=np.uint8)
+    lo, hi = PCM_GUARD + a, PCM_GUARD + a + len(base)
+    img[lo:hi] = np.frombuffer(base, dtype=np.uint8)
+    parent = N.DeviceBuffer.from_array(img)
+    window = parent.view(lo, len(base) + surplus)
+    bufs = [N.DeviceBuffer.from_bytes(bytes(b)) for b in sources]
+    try:
+        assert (C.cast(L.sh_buf_devptr(window.handle), C.c_void_p).value or 0) % 16 == a % 16, "track window not at the intended residue"
+        rc = call(bufs, window, parent)
+        N.sync()
+        for k, (buf, b) in enumerate(zip(bufs, sources)):
+            assert buf.download_bytes(len(b)) == bytes(b), "source %d was written to" % k
+        got = parent.download(np.uint8, img.size)
+        stray = np.flatnonzero(np.concatenate([got[:lo], got[hi:]]) != PCM_OUT_SENTINEL)
+        assert stray.size == 0, "track parent written outside track_samples: byte %d relative to the window's start, %d bytes in all" % (
+            int(stray[0]) - lo if stray[0] < lo else int(stray[0]) - lo + (hi - lo), stray.size)
+        result = got[lo:hi].tobytes()
+        if untouched:
+            assert result == base, "a refused call wrote into the track"
+        return rc, result
+    finally:
+        window.free()
+        parent.free()
+        for b in bufs:
+            b.free()
