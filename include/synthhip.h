@@ -636,6 +636,50 @@ typedef struct sh_mix_event_rev {  /* sh_mix_event_loop's fields, then the flags
 int sh_mix_events_rev(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_rev* events, uint32_t nevents,
                       const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples);
 
+/* The same with a STEREO source's two channels weighed per event: a stereo drum break in a mono track, a stereo pad set to one side of a
+ * stereo track, without a converted copy per pair of factors.  This closes the channel matrix (mono into stereo: left / right of
+ * sh_mix_events_pan).
+ * Replaces: o = o.copy().mono(lf, rf) / o = o.copy().stereo(lf, rf) of a stereo o (upstream synthplayer/sample.py, [RECALL]:
+ * audioop.tomono; left().amplify(lf) mixed with right().amplify(rf)) where sh_mix_events_pan's tostereo stands in the loop body: behind
+ * the envelope, in front of audioop.mul.
+ * The mode is a flag bit, said per event and never derived from the channel counts (a stereo row in a stereo track is a plain event
+ * unless it says otherwise, and a row's meaning does not change with the call's nchannels):
+ *   SH_MIX_EVENT_DOWNMIX  src_channels == 2, nchannels == 1.  dst_sample and nsamples count TRACK (mono) samples; track sample
+ *                         dst_sample + f is floor(fbound(l * left + r * right)) of frame f of what the fields describe over the stereo
+ *                         source -- src_sample, src_frames, the loop and a reversed region in stereo frames / samples as for any stereo
+ *                         source, audioop.ratecv with two channels, the segments' ends and origins in stereo SAMPLES (2 per track sample).
+ *                         A reversed source has left and right swapped BEFORE the factors.  Two products and a sum, three roundings.
+ *   SH_MIX_EVENT_BALANCE  src_channels == 2, nchannels == 2.  An event of sh_mix_events_rev whose even samples then go through
+ *                         fbound(x * left) and its odd ones through fbound(x * right); a factor of exactly 1.0 does nothing.
+ * An event with neither bit is an event of sh_mix_events_rev (left / right are tostereo's for a mono source there); a list may hold every
+ * kind. */
+#define SH_MIX_EVENT_DOWNMIX 2u
+#define SH_MIX_EVENT_BALANCE 4u
+typedef struct sh_mix_event_chan { /* sh_mix_event_rev's layout */
+    uint64_t dst_sample;
+    uint64_t src_sample;
+    uint64_t nsamples;             /* TRACK samples: a downmix takes 2 * nsamples of its (resampled) source */
+    uint64_t src_frames;
+    double   factor;
+    double   left, right;          /* tostereo's, tomono's or the balance's factors */
+    uint32_t src;
+    uint32_t inrate, outrate;
+    uint32_t src_channels;
+    uint32_t seg_first;
+    uint32_t seg_count;
+    uint32_t reserved;             /* 0 */
+    uint64_t loop_start;
+    uint64_t loop_frames;
+    uint32_t flags;                /* SH_MIX_EVENT_REVERSED | one of SH_MIX_EVENT_DOWNMIX, SH_MIX_EVENT_BALANCE; every other bit 0 */
+} sh_mix_event_chan;               /* 112 bytes */
+/* SH_ERR_INVALID, the event named and nothing launched, for everything sh_mix_events_rev refuses (a downmix's src_channels of 2 in a
+ * mono track is none of it), and: a flag bit other than the three; both modes on one event; a mode on a source that is not stereo; a
+ * downmix into a track that is not mono, a balance into one that is not stereo; a left or right that is not finite; a balance whose
+ * dst_sample is odd; a downmix with dst_sample + nsamples > 2^31 - 32768 -- the kernels form its source-sample coordinates, twice the
+ * track's, in 32 bits (the limit of the track itself stays 2^32 - 65536 samples). */
+int sh_mix_events_chan(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_chan* events, uint32_t nevents,
+                       const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

@@ -69,6 +69,8 @@ MIX_EVENT_LOOP_DTYPE = np.dtype([(n, MIX_EVENT_ENV_DTYPE.fields[n][0]) for n in 
                                 [("loop_start", "<u8"), ("loop_frames", "<u8")], align=True)                                 # sh_mix_event_loop
 MIX_EVENT_REV_DTYPE = np.dtype([(n, MIX_EVENT_LOOP_DTYPE.fields[n][0]) for n in MIX_EVENT_LOOP_DTYPE.names] + [("flags", "<u4")], align=True)   # sh_mix_event_rev
 MIX_EVENT_REVERSED = 1                                                                                                       # sh_mix_event_rev.flags
+MIX_EVENT_CHAN_DTYPE = np.dtype([(n, MIX_EVENT_REV_DTYPE.fields[n][0]) for n in MIX_EVENT_REV_DTYPE.names], align=True)       # sh_mix_event_chan
+MIX_EVENT_DOWNMIX, MIX_EVENT_BALANCE = 2, 4                                                                                  # sh_mix_event_chan.flags
 ENV_SEGMENT_DTYPE = np.dtype([("end", "<u8"), ("origin", "<u8"), ("mul", "<f8"), ("slope", "<f8"), ("numsamples", "<f8"), ("offset", "<f8"),
                               ("kind", "<u4"), ("reserved", "<u4")], align=True)                                             # sh_env_segment
 ENV_NONE, ENV_FADE_IN, ENV_FADE_OUT = 0, 1, 2                                                                                # sh_env_segment.kind
@@ -78,7 +80,7 @@ assert SEGMENT_DTYPE.itemsize == 24 and PARTIAL_DTYPE.itemsize == 16 and ENVELOP
 assert VOICE_DTYPE.itemsize == 272, VOICE_DTYPE.itemsize
 assert MIX_EVENT_DTYPE.itemsize == 40 and MIX_EVENT_RATE_DTYPE.itemsize == 56 and MIX_EVENT_PAN_DTYPE.itemsize == 80
 assert MIX_EVENT_ENV_DTYPE.itemsize == 88 and ENV_SEGMENT_DTYPE.itemsize == 56 and MIX_EVENT_LOOP_DTYPE.itemsize == 104
-assert MIX_EVENT_REV_DTYPE.itemsize == 112
+assert MIX_EVENT_REV_DTYPE.itemsize == 112 and MIX_EVENT_CHAN_DTYPE.itemsize == 112
 
 
 class Counters(C.Structure):
@@ -158,6 +160,7 @@ _SIGNATURES = {
     "sh_mix_events_env": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_size_t]),
     "sh_mix_events_loop": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_size_t]),
     "sh_mix_events_rev": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_size_t]),
+    "sh_mix_events_chan": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_size_t]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),

@@ -1,10 +1,11 @@
 // sequence.hip -- a list of placed samples mixed into a track in one launch (sh_mix_events, sh_mix_events_rate, sh_mix_events_pan,
-// sh_mix_events_env, sh_mix_events_loop, sh_mix_events_rev: Sample.mix_at_many, mixer.sequence).
+// sh_mix_events_env, sh_mix_events_loop, sh_mix_events_rev, sh_mix_events_chan: Sample.mix_at_many, mixer.sequence).
 //
 // The track is cut into tiles (seqplan.hpp); one workgroup per tile that some event touches walks that tile's events IN LIST ORDER, every
 // lane keeping its own few track samples in registers from the one load of the base to the one store of the result.  Lanes own disjoint
 // samples and read the track only there, so the fold is in place; a source may not be the track.  Per event, in this order -- none of
-// the steps commute, and the bytes are those of the loop of copy().speed().clip().envelope().stereo() / at_volume / mix_at it replaces:
+// the steps commute, and the bytes are those of the loop of copy().speed().clip().envelope().stereo() or .mono() / at_volume / mix_at it
+// replaces:
 //
 //   region     a slice of the recording: where the record's pointer stands and how many frames the steps below may count; reversed
 //              (audioop.reverse: the order of the SAMPLES) the pointer stands behind the slice and sample i is ptr[-1 - i] (seqrev.hpp),
@@ -18,18 +19,23 @@
 //   the cut    the event's n: the host has checked that the samples exist.
 //   envelope   Sample.envelope's gain (she::shape_lane, seqenv.hpp) on the (resampled, cut) source samples.
 //   tostereo   a mono source into a stereo track: audioop.tostereo, frame f -> (fbound(s * left), fbound(s * right)), in the same lane.
+//   channels   a STEREO source weighed per channel, where tostereo stands (an event has one of the three or none).  Downmix, into a mono
+//              track: audioop.tomono, frame f -> fbound(l * left + r * right), two products and a sum with three roundings (k_tomono's
+//              statement) -- a lane's N track samples are 2 N source samples, fetched and shaped as two halves of N, so everything
+//              above runs over the stereo samples with coordinates doubled (2 (dst + n) in 32 bits: the entry point refuses the rest).
+//              Balance, in a stereo track: even samples fbound(x * left), odd ones fbound(x * right); a side of exactly 1.0: none.
 //   mul        audioop.mul (fbound: clamp, then floor); a factor of exactly 1.0: none.
 //   add        audioop.add, saturating AT EVERY EVENT.
 //
 // A feature LEVEL says how much of the chain a list may ask for, and with it which record a kernel reads: PLAIN (fetch of plain events,
 // mul, add: sh_mix_events), RATE (+ ratecv: sh_mix_events_rate), PAN (+ tostereo: sh_mix_events_pan), ENV (+ envelope:
 // sh_mix_events_env), LOOP (+ the sustain loop: sh_mix_events_loop), REV (+ reversed playback: sh_mix_events_rev; its five kernels are
-// reached from that entry point alone).  seq_event is the chain up to the mul, written once: a stage above
-// the level is removed by `if constexpr`, a stage of the level that an event does not use is skipped by a wave-uniform branch on its
-// record (a row of sh_mix_events_loop without a loop is an event of ENV).  Three kernel templates call it: the plain
-// 16-bit one (INFLIGHT records and source vectors in flight), the 16-bit one of the other levels (one record ahead) and the one of
-// widths 1, 3, 4.  Built with -ffp-contract=off (the float64 product of audioop.mul stays one rounding, ratecv's prev*d + cur*(outr-d)
-// two).
+// reached from that entry point alone), CHAN (+ downmix and balance: sh_mix_events_chan; five kernels again, reached from there
+// alone).  seq_event is the chain up to the mul, written once: a stage above the level is removed by `if constexpr`, a stage of the
+// level that an event does not use is skipped by a wave-uniform branch on its record (a row of sh_mix_events_loop without a loop is an
+// event of ENV).  Three kernel templates call it: the plain 16-bit one (INFLIGHT records and source vectors in flight), the 16-bit one
+// of the other levels (one record ahead) and the one of widths 1, 3, 4.  Built with -ffp-contract=off (the float64 product of
+// audioop.mul stays one rounding, ratecv's prev*d + cur*(outr-d) two, tomono's l*left + r*right three).
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
@@ -52,7 +58,7 @@ typedef const SH_SEQ_GLOBAL short* gshort_p;
 typedef const SH_SEQ_GLOBAL unsigned char* gbyte_p;
 typedef int int_u1 __attribute__((aligned(1)));
 
-enum Level { PLAIN = 0, RATE = 1, PAN = 2, ENV = 3, LOOP = 4, REV = 5 };
+enum Level { PLAIN = 0, RATE = 1, PAN = 2, ENV = 3, LOOP = 4, REV = 5, CHAN = 6 };
 
 // ---- the records: one event as the kernels read it, wave-uniform, so fetched by scalar loads ------------------------------------------
 struct SeqEv {                // PLAIN, 32 bytes
@@ -112,6 +118,12 @@ struct SeqEvV : SeqEvL {
     SH_HD uint32_t reversed() const { return small >> 1; }
     SH_HD uint32_t small_int() const { return small & 1u; }
 };
+// CHAN, 96 bytes: SeqEvV again, and the word `tostereo` -- 0 or 1 up to REV -- says which channel step the event takes (SeqMode).  NONE
+// and TOSTEREO: an event of REV.  DOWNMIX: a stereo source into a mono track -- dst and n count TRACK (mono) samples, track sample dst + f
+// is frame f of what SeqEvV describes with nch == 2 (region, reversal, loop, ratecv and envelope over the stereo samples) through
+// audioop.tomono's two factors; the host has checked that 2 (dst + n) fits 32 bits.  BALANCE: a stereo source in a stereo track, its even
+// samples through fbound(x * left) and its odd ones through fbound(x * right); dst is even.
+enum SeqMode : uint32_t { SEQ_NONE = 0, SEQ_TOSTEREO = 1, SEQ_DOWNMIX = 2, SEQ_BALANCE = 3 };
 static_assert(sizeof(SeqEv) == 32, "SeqEv is read as one 32-byte scalar load");
 static_assert(sizeof(SeqEvR) == 64, "SeqEvR is read as one 64-byte scalar load");
 static_assert(sizeof(SeqEvP) == 96 && sizeof(SeqEvE) == 96, "SeqEvP and SeqEvE are read as a 64-byte and a 32-byte scalar load");
@@ -125,6 +137,7 @@ template <> struct SeqRec<PAN> { typedef SeqEvP type; };
 template <> struct SeqRec<ENV> { typedef SeqEvE type; };
 template <> struct SeqRec<LOOP> { typedef SeqEvL type; };
 template <> struct SeqRec<REV> { typedef SeqEvV type; };
+template <> struct SeqRec<CHAN> { typedef SeqEvV type; };
 
 // ---- the lane shapes: eight 16-bit samples (one aligned 16-byte vector), four samples of widths 1, 3, 4 (bytes assembled for 24-bit
 // samples, 64-bit sums for 32-bit ones -- the shape of k_mix_chain_gather_w, pcm.hip, which says why these widths get the plain loop) ----
@@ -419,6 +432,15 @@ __device__ __forceinline__ void seq_env_span(const SeqEvE& c, uint32_t t0, uint3
     thi = (b < d + n ? b : d + n) - d;
 }
 
+// The same of a CHAN record, whose word says more than 0 or 1: a downmix's source samples are two to a track sample (the opposite shift;
+// no wrap: the host has checked 2 (dst + n), and the tile overlaps the event).
+__device__ __forceinline__ void seq_env_span_chan(const SeqEvV& c, uint32_t t0, uint32_t tile, uint32_t& tlo, uint32_t& thi) {
+    const uint32_t sh = c.tostereo == SEQ_TOSTEREO ? 1u : 0u, d = c.dst >> sh, n = c.n >> sh, a = t0 >> sh, b = a + (tile >> sh);
+    const uint32_t up = c.tostereo == SEQ_DOWNMIX ? 1u : 0u;
+    tlo = (a > d ? a - d : 0u) << up;
+    thi = ((b < d + n ? b : d + n) - d) << up;
+}
+
 // fetch and envelope: the N source samples of event c from its sample f0 on -- c.dst, c.n and f0 count what the event resamples and
 // shapes: track samples, or the frames of a tostereo event.  An enveloped event shapes them with she::shape_lane: float64 per sample only
 // inside a ramp, one fbound multiply inside the sustain, nothing inside a plain stretch, a per-sample select only in a tile that
@@ -443,7 +465,7 @@ __device__ __forceinline__ void seq_source(const typename SeqRec<LEVEL>::type& c
                 if constexpr (LEVEL >= LOOP)                      // and seq_load's second vector must not be read behind it)
                     if (c.loop_len() && c.seam() < n) n = c.seam();
                 bool turned = false;
-                if constexpr (LEVEL == REV) {
+                if constexpr (LEVEL >= REV) {
                     if (c.reversed()) {
                         seq_plain_rev<WIDTH, SCHEME, N>(c.src, c.dst, n, f0, x);
                         turned = true;
@@ -479,10 +501,39 @@ __device__ __forceinline__ void seq_event(const typename SeqRec<LEVEL>::type& c,
     uint32_t tlo = 0, thi = 0;
     if constexpr (LEVEL == ENV)
         if (c.nseg) seq_env_span(c, t0, SEQ_TILE<WIDTH>, tlo, thi);
-    if constexpr (LEVEL >= LOOP)
+    if constexpr (LEVEL == LOOP || LEVEL == REV)
         if (c.nseg || c.loop_len()) seq_env_span(c, t0, SEQ_TILE<WIDTH>, tlo, thi);
+    if constexpr (LEVEL == CHAN) {
+        if (c.nseg || c.loop_len()) seq_env_span_chan(c, t0, SEQ_TILE<WIDTH>, tlo, thi);
+        if (c.tostereo == SEQ_DOWNMIX) {                      // the lane's N mono samples are N stereo frames, 2 N source samples
+            typename SeqRec<LEVEL>::type f = c;
+            f.dst = c.dst << 1;
+            f.n = c.n << 1;
+            f.nch = 2;                                        // (as the host wrote it: said again for the compiler)
+            constexpr double LO = (double)SEQ_LO<WIDTH>, HI = (double)SEQ_HI<WIDTH>;
+#pragma nounroll
+            for (int h = 0; h < 2; ++h) {                     // one copy of the chain in the code, run on each half
+                typename SeqVec<WIDTH, N>::type m;
+                seq_source<LEVEL, WIDTH, SCHEME, N>(f, segs, tlo, thi, (s0 << 1) + (uint32_t)h * N, m);
+                int r[N / 2];                                 // audioop.tomono as k_tomono: two products, a sum, three roundings
+#pragma unroll
+                for (int j = 0; j < N / 2; ++j) r[j] = fbound((double)m[2 * j] * c.left + (double)m[2 * j + 1] * c.right, LO, HI);
+                if (h == 0) {
+#pragma unroll
+                    for (int j = 0; j < N / 2; ++j) x[j] = r[j];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < N / 2; ++j) x[N / 2 + j] = r[j];
+                }
+            }
+            return;
+        }
+    }
     if constexpr (LEVEL >= PAN) {
-        if (c.tostereo) {                                     // the lane's N track samples are N / 2 frames of the mono source
+        bool mono;                                            // (CHAN: the word carries the other modes as well)
+        if constexpr (LEVEL == CHAN) mono = c.tostereo == SEQ_TOSTEREO;
+        else mono = c.tostereo != 0;
+        if (mono) {                                           // the lane's N track samples are N / 2 frames of the mono source
             typename SeqRec<LEVEL>::type f = c;
             f.dst = c.dst >> 1;
             f.n = c.n >> 1;
@@ -499,6 +550,19 @@ __device__ __forceinline__ void seq_event(const typename SeqRec<LEVEL>::type& c,
         }
     }
     seq_source<LEVEL, WIDTH, SCHEME, N>(c, segs, tlo, thi, s0, x);
+    if constexpr (LEVEL == CHAN) {
+        if (c.tostereo == SEQ_BALANCE) {                      // lanes start on even samples, dst is even: even samples left, odd ones right
+            constexpr double LO = (double)SEQ_LO<WIDTH>, HI = (double)SEQ_HI<WIDTH>;
+            if (c.left != 1.0) {                              // (uniform; fbound(x * 1.0) == x: skipping changes no bytes)
+#pragma unroll
+                for (int j = 0; j < N; j += 2) x[j] = fbound((double)x[j] * c.left, LO, HI);
+            }
+            if (c.right != 1.0) {
+#pragma unroll
+                for (int j = 1; j < N; j += 2) x[j] = fbound((double)x[j] * c.right, LO, HI);
+            }
+        }
+    }
 }
 
 // ---- 16-bit samples ---------------------------------------------------------------------------------------------------------------------
@@ -741,6 +805,9 @@ struct SeqIn {
     uint64_t loop_start = 0, loop_frames = 0;               // sh_mix_event_loop's; loop_frames == 0: none, and src_frames is what it was
     uint32_t flags = 0;                                      // sh_mix_event_rev's; SH_MIX_EVENT_REVERSED: played backwards
     bool tostereo() const { return src_channels == 1 && nchannels == 2; }
+    bool downmix() const { return (flags & SH_MIX_EVENT_DOWNMIX) != 0; }      // sh_mix_event_chan's; the six other entry points say none
+    bool balance() const { return (flags & SH_MIX_EVENT_BALANCE) != 0; }
+    uint32_t mode() const { return tostereo() ? SEQ_TOSTEREO : downmix() ? SEQ_DOWNMIX : balance() ? SEQ_BALANCE : SEQ_NONE; }
     bool reversed() const { return (flags & SH_MIX_EVENT_REVERSED) != 0; }
     // the frames of a reversed event's region, stored from src_sample on: nothing behind a loop's end is played, and a looped event's
     // src_frames counts virtual frames
@@ -755,10 +822,22 @@ int seq_check_events(const char* fn, int level, In in, uint32_t nevents, const s
     for (uint32_t e = 0; e < nevents; ++e) {
         const SeqIn m = in(e);
         if (m.reserved != 0) return sh::set_error(SH_ERR_INVALID, "%s: event %u: reserved must be 0", fn, e);
-        if (m.flags & ~(uint32_t)SH_MIX_EVENT_REVERSED) return sh::set_error(SH_ERR_INVALID, "%s: event %u: unknown flags 0x%x", fn, e, m.flags);
+        const uint32_t known = level == CHAN ? SH_MIX_EVENT_REVERSED | SH_MIX_EVENT_DOWNMIX | SH_MIX_EVENT_BALANCE : SH_MIX_EVENT_REVERSED;
+        if (m.flags & ~known) return sh::set_error(SH_ERR_INVALID, "%s: event %u: unknown flags 0x%x", fn, e, m.flags);
+        if (m.downmix() || m.balance()) {
+            if (m.downmix() && m.balance()) return sh::set_error(SH_ERR_INVALID, "%s: event %u: downmix and balance on one event", fn, e);
+            if (m.src_channels != 2) return sh::set_error(SH_ERR_INVALID, "%s: event %u: a downmix or balance needs a stereo source, src_channels is %u", fn, e, m.src_channels);
+            if (m.downmix() && m.nchannels != 1) return sh::set_error(SH_ERR_INVALID, "%s: event %u: a downmix needs a mono track, this one has %d channels", fn, e, m.nchannels);
+            if (m.balance() && m.nchannels != 2) return sh::set_error(SH_ERR_INVALID, "%s: event %u: a balance needs a stereo track, this one has %d channels", fn, e, m.nchannels);
+            if (!isfinite(m.left) || !isfinite(m.right)) return sh::set_error(SH_ERR_INVALID, "%s: event %u: left / right is not finite", fn, e);
+            if (m.balance() && m.dst_sample % 2) return sh::set_error(SH_ERR_INVALID, "%s: event %u: a balance starts on a whole stereo frame", fn, e);
+            // the kernels form a downmix's source-sample coordinates, 2 dst and 2 n, in 32 bits
+            if (m.downmix() && (m.nsamples > shq::MAX_TRACK_SAMPLES / 2 || m.dst_sample > shq::MAX_TRACK_SAMPLES / 2 - m.nsamples))
+                return sh::set_error(SH_ERR_INVALID, "%s: event %u: a downmix ends at most 2^31 - 32768 track samples in", fn, e);
+        }
         if (!isfinite(m.factor)) return sh::set_error(SH_ERR_INVALID, "%s: event %u: factor is not finite", fn, e);
         if (m.src >= nsrc || !srcs[m.src]) return sh::set_error(SH_ERR_INVALID, "%s: event %u: no source %u", fn, e, m.src);
-        if (!m.tostereo() && m.src_channels != (uint32_t)m.nchannels) {
+        if (!m.tostereo() && !m.downmix() && m.src_channels != (uint32_t)m.nchannels) {
             if (level == PAN) return sh::set_error(SH_ERR_INVALID, "%s: event %u: src_channels %u not 1 or 2", fn, e, m.src_channels);
             return sh::set_error(SH_ERR_INVALID, "%s: event %u: src_channels %u is neither the track's %d nor a mono source of a stereo track", fn, e, m.src_channels, m.nchannels);
         }
@@ -772,6 +851,7 @@ int seq_check_events(const char* fn, int level, In in, uint32_t nevents, const s
                 return sh::set_error(SH_ERR_INVALID, "%s: event %u: a mono source starts and ends on whole stereo frames", fn, e);
             nsrc_samples = m.nsamples / 2;
         }
+        if (m.downmix()) nsrc_samples = m.nsamples * 2;
         const bool looped = m.loop_frames != 0;               // src_frames counts VIRTUAL frames then, and may exceed the source's
         if (m.src_sample > have || (!looped && m.inrate == m.outrate && nsrc_samples > have - m.src_sample))
             return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside its source", fn, e);
@@ -836,7 +916,7 @@ void seq_fill(typename SeqRec<LEVEL>::type* rec, In in, uint32_t nevents, const 
             if constexpr (LEVEL == RATE) rec[e] = r;
             else if constexpr (LEVEL == PAN) rec[e] = SeqEvP{r, m.left, m.right, {0, 0}, m.tostereo() ? 1u : 0u, 0};
             else {
-                const SeqEvE v{r, m.left, m.right, m.seg_count ? m.seg_first : 0u, m.seg_count, m.tostereo() ? 1u : 0u, 0};
+                const SeqEvE v{r, m.left, m.right, m.seg_count ? m.seg_first : 0u, m.seg_count, m.mode(), 0};
                 if constexpr (LEVEL == ENV) rec[e] = v;
                 else {
                     // a note no longer than its head (V <= E) is a plain cut: no loop pass, an event of ENV
@@ -880,7 +960,7 @@ void seq_launch(const typename SeqRec<LEVEL>::type* ev, const she::Seg* segs, co
     }
 }
 
-// What the six entry points do behind their own arguments: check, plan, records (and the segments behind them), one launch.
+// What the seven entry points do behind their own arguments: check, plan, records (and the segments behind them), one launch.
 template <int LEVEL, typename In>
 int seq_mix(const char* fn, In in, const sh_buf* const* srcs, uint32_t nsrc, uint32_t nevents, const sh_env_segment* segments, uint32_t nsegments, int width,
             int nchannels, sh_buf* track, size_t track_samples) {
@@ -1008,6 +1088,28 @@ int sh_mix_events_rev(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_eve
         return v;
     };
     return seq_mix<REV>(fn, in, srcs, nsrc, nevents, segments, nsegments, width, nchannels, track, track_samples);
+}
+
+int sh_mix_events_chan(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_chan* events, uint32_t nevents,
+                       const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_mix_events_chan";
+    const int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    if (rc) return rc;
+    if (width == 3) {                                         // as sh_mix_events_rev: tomono and mul have a 24-bit form, envelopes none
+        for (uint32_t e = 0; e < nevents; ++e)
+            if (events[e].seg_count) return sh::set_error(SH_ERR_INVALID, "%s: event %u: width 3: an envelope's fades have no 24-bit form", fn, e);
+    }
+    auto in = [=](uint32_t e) {
+        const sh_mix_event_chan& m = events[e];
+        SeqIn v{m.dst_sample, m.src_sample, m.nsamples, m.src_frames, m.factor, m.left, m.right, m.src, m.inrate, m.outrate, m.src_channels,
+                m.seg_first, m.seg_count, m.reserved, nchannels};
+        v.loop_start = m.loop_start;
+        v.loop_frames = m.loop_frames;
+        v.flags = m.flags;
+        return v;
+    };
+    return seq_mix<CHAN>(fn, in, srcs, nsrc, nevents, segments, nsegments, width, nchannels, track, track_samples);
 }
 
 }  // extern "C"

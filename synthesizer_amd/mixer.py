@@ -576,14 +576,16 @@ def mix_samples(samples: Sequence[Sample], name: str = "mix") -> Sample:
 
 def sequence(events: Sequence[tuple], samplerate: int, nchannels: int, samplewidth: int = 2, name: str = "") -> Sample:
     """A track made of placed samples: a new empty ``Sample`` of the given format with ``events`` -- ``(seconds, sample,
-    volume=None, sample_seconds=None, speed=None, pan=None, envelope=None, loop=None, region=None, reverse=None)`` each -- mixed in by
+    volume=None, sample_seconds=None, speed=None, pan=None, envelope=None, loop=None, region=None, reverse=None, channels=None)`` each -- mixed in by
     ``Sample.mix_at_many``: in list order, saturating at every event; ``region`` -- ``(start, end)``, seconds of the sample's own time, ``end``
     may be None -- plays a slice of the sample and ``reverse`` plays it backwards (``Sample.reverse``: a stereo sample's channels change
     places), both before everything else and without a copy per slice; ``loop`` -- ``(loop_start, loop_end, length)``, seconds of the sample's own time -- holds the
     (clipped, reversed) sample's loop region until the note is ``length`` long, next; ``speed`` plays the sample faster or slower (``Sample.speed``: one recorded note at many pitches),
     ``envelope`` -- ``(attack, decay, sustainlevel, release)`` or with a fifth element, the note's length -- shapes the (resampled, cut)
     sample as ``Sample.envelope`` does, ``pan`` places a mono sample in the stereo field of a stereo track (``Sample.pan``, or the
-    factor pair of ``Sample.stereo``), all of them before ``volume`` applies, in that order."""
+    factor pair of ``Sample.stereo``), ``channels`` -- ``(left_factor, right_factor)`` -- weighs the two channels of a STEREO sample in
+    pan's place (``Sample.mono`` into a mono track, ``Sample.stereo``'s balance in a stereo one), all of them before ``volume`` applies,
+    in that order."""
     track = Sample(name=name, samplerate=samplerate, nchannels=nchannels, samplewidth=samplewidth)
     return track.mix_at_many(events)
 

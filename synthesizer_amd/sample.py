@@ -40,6 +40,9 @@ _NPTYPE = {1: np.int8, 2: np.int16, 4: np.int32}
 _MAX_CALL_SAMPLES = 0xFFFF0000                              # shq::MAX_TRACK_SAMPLES: positions are 32 bits on the device
 
 
+_MAX_DOWNMIX_SOURCE_SAMPLES = 0xFFFF0000                    # sh_mix_events_chan: 2 * (dst_sample + nsamples) of a downmix, in 32 bits
+
+
 def _ratecv_out_frames(in_frames: int, inrate: int, outrate: int) -> int:
     """Frames ``audioop.ratecv`` makes of ``in_frames`` (sh_resample_out_frames, in Python integers): output frame m exists while
     ceil(m inrate / outrate) <= in_frames - 1."""
@@ -664,9 +667,9 @@ class Sample:
 
     def mix_at_many(self, events: Iterable[tuple]) -> "Sample":
         """Mix a list of placed samples into this one: ``events`` holds ``(seconds, other, volume=None, other_seconds=None,
-        speed=None, pan=None, envelope=None, loop=None, region=None, reverse=None)``, and the result is, byte for byte, what ::
+        speed=None, pan=None, envelope=None, loop=None, region=None, reverse=None, channels=None)``, and the result is, byte for byte, what ::
 
-            for seconds, other, volume, other_seconds, speed, pan, envelope, loop, region, reverse in events:
+            for seconds, other, volume, other_seconds, speed, pan, envelope, loop, region, reverse, channels in events:
                 o = other
                 if region is not None:                  # (start, end) in seconds of other's own time; end may be None
                     o = other.copy().clip(region[0], other.duration if region[1] is None else region[1])
@@ -688,6 +691,12 @@ class Sample:
                     o.envelope(*envelope[:4])           # on the (resampled, cut) frames, before tostereo
                 if pan is not None:
                     o = o.copy().stereo(left, right)    # audioop.tostereo of the (resampled, shaped) MONO frames
+                if channels is not None:                # a STEREO other, weighed per channel; never beside a pan
+                    lf, rf = channels
+                    if self.nchannels == 1:
+                        o = o.copy().mono(lf, rf)       # audioop.tomono: floor(fbound(l * lf + r * rf))
+                    else:
+                        o = o.copy().stereo(lf, rf)     # (floor(fbound(L * lf)), floor(fbound(R * rf)))
                 if volume is not None:
                     o = o.at_volume(volume)             # audioop.mul, after the resample, the envelope and tostereo
                 self.mix_at(seconds, o, other_seconds)  # other_seconds cuts the resampled (stereo) sample
@@ -731,8 +740,21 @@ class Sample:
         ValueErrors, raised before anything is mixed: not a pair, a start or end that is not finite or is negative, ``end < start``.
         Where ``other`` is this sample, the region is cut from the track as it is when that event runs, so an ``end`` of None (the
         track's duration then) that lies before ``start`` is found only then, after the events before it have been mixed.
+        ``channels`` is the pair ``(left_factor, right_factor)`` for a STEREO ``other``, where ``pan``'s step stands: behind the envelope,
+        in front of the volume.  In a mono track it is ``Sample.mono``: a stereo drum break or pad into a mono track, without a converted
+        copy per pair of factors; ``(1.0, 0.0)`` is ``Sample.left()``.  In a stereo track it is ``Sample.stereo`` of a stereo sample, a
+        balance; ``(1.0, 1.0)`` is the plain event.  Everything in front of it runs over the stereo sample as it does without it: region,
+        reverse (left and right change places there, so ``left_factor`` then weighs what was recorded on the right), loop, ``ratecv``
+        with two channels, the cut, the envelope, whose ramps count SAMPLES, so the two samples of a frame get different factors before
+        they are summed.  Everything behind it counts what ``mix_at`` is handed: ``volume`` multiplies the mono or balanced samples, and
+        ``other_seconds`` and the event's end count the track's samples.  All four widths (an envelope still has no 24-bit form).  One
+        such event and the list goes to sh_mix_events_chan, still one launch, the rest as rows without a mode.  Its ValueErrors, raised
+        before anything is mixed: not a pair, a factor that is not finite, an ``other`` that is not stereo, a track that is neither
+        mono nor stereo, a ``pan`` on the same event, a downmix that ends more than 2^31 - 32768 samples into the track (the kernels
+        address its stereo samples, two per track sample, in 32 bits).  Without ``channels`` a stereo ``other`` in a mono track fails
+        the assertion of ``mix_at``, as before.
         An event whose ``other`` is this sample reads it as the events before it left it: the list is cut there, and that one event
-        goes through the loop's body above, region and reverse included."""
+        goes through the loop's body above, region, reverse and a balance included (a downmix cannot occur there)."""
         self._check_writable()
         self._check_gpu_width("mix_at")
         fb = self.__samplewidth * self.__nchannels
@@ -751,10 +773,27 @@ class Sample:
             if nev > 8:
                 region = ev[8]
                 reverse = bool(ev[9]) if nev > 9 else False
+            channels = ev[10] if nev > 10 else None
             assert self.samplewidth == other.samplewidth
             assert self.samplerate == other.samplerate
             factors = None                                                      # audioop.tostereo's, of a panned event
-            if pan is None:
+            weights = None                                                      # audioop.tomono's or the balance's, of an event with channels
+            if channels is not None:
+                if pan is not None:
+                    raise ValueError("mix_at_many: pan and channels on one event: pan places a mono sample, channels weighs a stereo one")
+                if not isinstance(channels, (tuple, list)) or len(channels) != 2:
+                    raise ValueError("mix_at_many: channels is a pair (left_factor, right_factor)")
+                try:
+                    weights = (float(channels[0]), float(channels[1]))
+                except (TypeError, ValueError):
+                    raise ValueError("mix_at_many: channels is a pair of numbers, not %r" % (tuple(channels),)) from None
+                if not (math.isfinite(weights[0]) and math.isfinite(weights[1])):
+                    raise ValueError("mix_at_many: channels factor is not finite")
+                if other.nchannels != 2:
+                    raise ValueError("mix_at_many: channels needs a stereo sample, this one has %d channels" % other.nchannels)
+                if self.__nchannels not in (1, 2):
+                    raise ValueError("mix_at_many: channels needs a mono or stereo track, this one has %d channels" % self.__nchannels)
+            elif pan is None:
                 assert self.nchannels == other.nchannels
             else:
                 if other.nchannels != 1:
@@ -813,13 +852,19 @@ class Sample:
                 fbo = self.__samplewidth * other.nchannels
                 shaped[len(todo)] = (envelope, _envelope_segments(have // fb * fbo, self.__samplewidth, other.nchannels, rate, *envelope[:4]))
             n2 = fb * int(rate * other_seconds) if other_seconds else have     # frame_idx(other_seconds) of what mix_at is handed
+            if weights is not None and self.__nchannels == 1 and 2 * ((start + min(n2, have)) // self.__samplewidth) > _MAX_DOWNMIX_SOURCE_SAMPLES:
+                raise ValueError("mix_at_many: channels: a downmix ends at most %d samples into the track (its stereo samples are addressed "
+                                 "in 32 bits)" % (_MAX_DOWNMIX_SOURCE_SAMPLES // 2))
+            if weights is not None:
+                extra = (extra if extra is not None else (None, False)) + (weights,)
             todo.append((seconds, other, volume, other_seconds, speed, start, min(n2, have), inrate, factors, loop, extra))
         batch, envs, extras = [], {}, {}                                        # envs: index into batch -> segment rows; extras: -> (region, reverse)
         for k, (seconds, other, volume, other_seconds, speed, start, n2, inrate, factors, loop, extra) in enumerate(todo):
             if other is self:                                                   # (never panned: a panned event's other is mono, its track stereo)
                 self.__mix_events(batch, envs, extras)
                 batch, envs, extras = [], {}, {}
-                region, reverse = extra if extra is not None else (None, False)
+                region, reverse = extra[:2] if extra is not None else (None, False)
+                weights = extra[2] if extra is not None and len(extra) > 2 else None
                 if region is not None:                                          # copy().clip() of the track as it is NOW
                     end = other.duration if region[1] is None else region[1]
                     if end < region[0]:
@@ -842,6 +887,8 @@ class Sample:
                     if len(envelope) == 5:
                         other.clip(0.0, envelope[4])
                     other.envelope(*envelope[:4])
+                if weights is not None:                                         # (the track is stereo here: a balance)
+                    other = other.copy().stereo(*weights)
                 self.mix_at(seconds, other if volume is None else other.at_volume(volume), other_seconds)
             else:
                 if shaped and k in shaped:
@@ -877,7 +924,9 @@ class Sample:
         that the event plays, which is what bytes, loop and the envelope's rows were counted over; it fills src_sample and src_frames
         of the table the list has anyway.  reverse: one of them and the list goes to
         sh_mix_events_rev, the rest as rows without the flag; a reversed row names its region as stored, forwards -- a looped one the
-        part of it in front of the loop's end, which is all it plays.
+        part of it in front of the loop's end, which is all it plays.  A third element, (left_factor, right_factor), is an event's
+        ``channels``: one of them and the list goes to sh_mix_events_chan, that row with SH_MIX_EVENT_DOWNMIX (a mono track; bytes counts
+        mono bytes, the envelope's rows the stereo samples) or SH_MIX_EVENT_BALANCE (a stereo one), the rest as rows without a mode.
         The table is packed column by column (whole-array numpy operations, not a row per event)."""
         if not batch:
             return
@@ -910,11 +959,15 @@ class Sample:
         panned = any(p is not None for p in pans)
         shaped = bool(envs)
         turned = cut = False
+        weighed = {}                                        # index into batch -> (left_factor, right_factor) of the events with channels
         if extras:
+            weighed = {i: x[2] for i, x in extras.items() if len(x) > 2}
+            extras = {i: x[:2] for i, x in extras.items()}
             turned = any(rv for _rg, rv in extras.values())
             cut = any(rg is not None for rg, _rv in extras.values())
-        looped = turned or loops.count(None) != len(loops)
-        table = np.zeros(len(batch), dtype=N.MIX_EVENT_REV_DTYPE if turned else N.MIX_EVENT_LOOP_DTYPE if looped else N.MIX_EVENT_ENV_DTYPE if shaped else N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
+        flagged = turned or bool(weighed)                   # a row with a flag: the table has sh_mix_event_rev's layout, which is the looped one's and more
+        looped = flagged or loops.count(None) != len(loops)
+        table = np.zeros(len(batch), dtype=N.MIX_EVENT_CHAN_DTYPE if weighed else N.MIX_EVENT_REV_DTYPE if turned else N.MIX_EVENT_LOOP_DTYPE if looped else N.MIX_EVENT_ENV_DTYPE if shaped else N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
         table["dst_sample"] = starts // w
         table["nsamples"] = nbytes // w
         table["factor"] = factors
@@ -945,11 +998,17 @@ class Sample:
                 table["flags"][rv] = N.MIX_EVENT_REVERSED
                 back = rv[lp[rv, 1] != 0]
                 table["src_sample"][back] += (table["src_frames"][back] - lp[back, 0] - lp[back, 1]) * table["src_channels"][back]
+            for i, (lf, rf) in weighed.items():             # a stereo source weighed per channel: tomono into a mono track, a balance in a stereo one
+                table["flags"][i] |= N.MIX_EVENT_DOWNMIX if self.__nchannels == 1 else N.MIX_EVENT_BALANCE
+                table["left"][i] = lf
+                table["right"][i] = rf
             table["src_frames"] = np.where(lp[:, 1] != 0, lp[:, 2], table["src_frames"])      # a looped row: the note's virtual frames
         if shaped or looped:
             rows = []
             for i, g in envs.items():
                 taken = int(nbytes[i]) // w // (2 if pans[i] is not None else 1)       # the event's source samples, after other_seconds' cut
+                if i in weighed and self.__nchannels == 1:
+                    taken *= 2                                                          # (a downmix: two stereo samples per track sample)
                 mine = [(min(r[0], taken),) + r[1:] for r in g]
                 mine = [r for k, r in enumerate(mine) if r[0] > (mine[k - 1][0] if k else 0)]      # (what the cut leaves nothing of)
                 table["seg_first"][i] = len(rows)
@@ -958,7 +1017,7 @@ class Sample:
             segtab = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
             for name, col in zip(("end", "mul", "kind", "slope", "numsamples", "offset", "origin"), zip(*rows) if rows else [()] * 7):
                 segtab[name] = col
-            entry = N.lib().sh_mix_events_rev if turned else N.lib().sh_mix_events_loop if looped else N.lib().sh_mix_events_env
+            entry = N.lib().sh_mix_events_chan if weighed else N.lib().sh_mix_events_rev if turned else N.lib().sh_mix_events_loop if looped else N.lib().sh_mix_events_env
             N.check(entry(srcs, len(bufs), table.ctypes.data, len(table), segtab.ctypes.data, len(segtab), w,
                           self.__nchannels, track.handle, total // w))
         elif panned:

@@ -46,7 +46,18 @@ events through sh_mix_events_loop -- with both calls' device times: what the rev
 no region and no reversal, the list as --loop has it (sh_mix_events_loop: kernels this entry point does not touch), for a run of this commit
 against a run of its parent.  --reverse --trace: (a)'s and (c)'s one call five times each, for rocprofv3 --kernel-trace; then the plain
 song (no speed, no loop: the vector fetch) with every other note reversed against pre-reversed copies played forwards by the same kernel,
-five calls each."""
+five calls each.
+
+--channels: the held, shaped song of --reverse, its instruments stereo, with ``channels`` per note (sh_mix_events_chan).  Two variants:
+a MONO track with a downmix (audioop.tomono) on every note, and a stereo track with a balance on every other note.  (a) one mix_at_many
+against the loop of copy().clip().reverse() / ... / envelope / mono() or stereo() / at_volume / mix_at it replaces, the same bytes (the
+tests hold both against live audioop); (b) the one call against the same notes from copies converted BEFORE the chain -- one mono() or
+stereo() copy per distinct (instrument, factors) -- through sh_mix_events_rev: the time between two events on the stream around the call
+here (table packing, table copy and kernel), the kernels' own times under --trace.  For a downmix that is not like for like and not the
+same bytes (the copy is mono before ratecv and the envelope: half the samples to fetch, resample and shape): the ratio is the price of
+doing the downmix in the lane.  Then (c) the --reverse list without any ``channels`` (sh_mix_events_rev, kernels this entry point does
+not touch), five medians of 15 calls, for a run of this commit against a run of its parent.  --channels --trace: per variant (a)'s one
+call five times, then (b)'s converted copies five times, then (c)'s list five times, and nothing else, for rocprofv3 --kernel-trace."""
 import audioop
 import os
 import sys
@@ -676,6 +687,102 @@ def rev_main():
               "%.4f ms" % (nevents, plain_ms, dev["p"]), flush=True)
 
 
+CHANNELS = ((0.75, 0.25), (0.5, 0.5), (1.0, 0.0), (0.3, -0.9))
+
+
+def device_ms(track, lst, warm=3, runs=15):
+    """the one call on a track that is long enough: the time between two events on the stream around it (the host's packing of the
+    tables, their copy and the kernel), the median of `runs`"""
+    for _ in range(warm):
+        track.mix_at_many(lst)
+    out = []
+    for _ in range(runs):
+        N.sync()
+        N.timer_start()
+        track.mix_at_many(lst)
+        out.append(N.timer_stop())
+    return sorted(out)[len(out) // 2]
+
+
+def chan_main():
+    N.ensure_init(0)
+    info = N.device_info()
+    print("sequence_chan_ab: SYNTHHIP_SEQ_ALIGN=%s  %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"]), flush=True)
+    trace = "--trace" in sys.argv[1:]
+    for nevents, loop_passes in ((4096, 2), (32768, 1)):
+        base, sources, events = rev_song(nevents, 120.0)
+        samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in sources]
+        rev_evs = [(s, samples[i], v, None, sp, None, e, lp, rg, rv) for s, i, v, sp, e, lp, rg, rv in events]
+        frames = len(Sample.from_raw_frames(base, WIDTH, RATE, NCH).to_device().mix_at_many(rev_evs))      # the song's length: every variant's
+        for what, nch, every in (("downmix on every note, mono track", 1, 1), ("balance on every other note, stereo track", 2, 2)):
+            chans = [CHANNELS[k % 4] if k % every == 0 else None for k in range(nevents)]
+            evs = [ev + (ch,) for ev, ch in zip(rev_evs, chans)]
+            start = Sample.from_raw_frames(base, WIDTH, RATE, nch).to_device()
+            made = {}                                       # (b): converted first, one copy per distinct (instrument, factors)
+            for (_s, i, *_r), ch in zip(events, chans):
+                if ch is not None and (i, ch) not in made:
+                    made[(i, ch)] = samples[i].copy().mono(*ch) if nch == 1 else samples[i].copy().stereo(*ch)
+            copy_evs = [ev[:1] + (made[(i, ch)] if ch is not None else ev[1],) + ev[2:] for ev, (_s, i, *_r), ch in zip(rev_evs, events, chans)]
+            track = Sample.from_raw_frames(bytes(frames * nch * WIDTH), WIDTH, RATE, nch).to_device()
+            if trace:               # under rocprofv3 --kernel-trace: (a)'s one call, then (b)'s converted copies, five times each and nothing else
+                for lst in (evs, copy_evs):
+                    for _ in range(5):
+                        track.mix_at_many(lst)
+                    N.sync()
+                print("chan song 120 s, %5d events, %s   traced: sh_mix_events_chan, then %d converted copies through sh_mix_events_rev"
+                      % (nevents, what, len(made)), flush=True)
+                continue
+
+            def many():                                     # (a)
+                return start.copy().mix_at_many(evs)
+
+            def loop():                                     # (a)'s yardstick
+                t = start.copy()
+                for seconds, other, volume, _o, speed, _p, env, (ls, le, length), region, reverse, ch in evs:
+                    o = other
+                    if region is not None:
+                        o = other.copy().clip(region[0], region[1])
+                    if reverse:
+                        o = o.copy().reverse()
+                    body = o.copy().clip(ls, le)
+                    o = o.copy().clip(0.0, le)
+                    while o.duration < length:
+                        o.join(body)
+                    o.clip(0.0, length)
+                    if speed is not None:
+                        o = o.copy().speed(speed)
+                    o = o.copy()
+                    o.clip(0.0, env[4])
+                    o.envelope(*env[:4])
+                    if ch is not None:
+                        o = o.copy().mono(*ch) if nch == 1 else o.copy().stereo(*ch)
+                    t.mix_at(seconds, o if volume is None else o.at_volume(volume))
+                return t
+
+            got = many()
+            parity = len(got) == frames and bytes(got.view_frame_data()) == bytes(loop().view_frame_data())
+            del got
+            many_ms = median_wall(many, 3, 9)
+            loop_ms = median_wall(loop, 0, loop_passes)
+            dev_chan = device_ms(track, evs)
+            dev_copies = device_ms(track, copy_evs)
+            print("chan song 120 s, %5d events, %s   (a) mix_at_many %9.3f ms   loop of calls %10.3f ms   loop / one call %.1fx   (b) in place, "
+                  "between two events on the stream: sh_mix_events_chan %.4f ms   %d converted copies through sh_mix_events_rev %.4f ms   "
+                  "chan / copies %.2fx   parity one call, loop: %s"
+                  % (nevents, what, many_ms, loop_ms, loop_ms / many_ms, dev_chan, len(made), dev_copies, dev_chan / dev_copies,
+                     "ok" if parity else "FAILED"), flush=True)
+        track = Sample.from_raw_frames(bytes(frames * NCH * WIDTH), WIDTH, RATE, NCH).to_device()         # (c): no channels anywhere, a stereo track
+        if trace:
+            for _ in range(5):
+                track.mix_at_many(rev_evs)
+            N.sync()
+            print("chan song 120 s, %5d events   traced: the list without channels (sh_mix_events_rev)" % nevents, flush=True)
+            continue
+        meds = [device_ms(track, rev_evs) for _ in range(5)]
+        print("chan song 120 s, %5d events   (c) the list without channels (sh_mix_events_rev)   in place, between two events on the stream, "
+              "five medians of 15: %s ms" % (nevents, " ".join("%.4f" % m for m in meds)), flush=True)
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -746,4 +853,4 @@ def main():
 
 
 if __name__ == "__main__":
-    rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
