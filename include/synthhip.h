@@ -680,6 +680,45 @@ typedef struct sh_mix_event_chan { /* sh_mix_event_rev's layout */
 int sh_mix_events_chan(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_chan* events, uint32_t nevents,
                        const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples);
 
+/* A song of placed samples compiled once and rendered window by window: the host work of sh_mix_events_chan -- checking the events,
+ * filling the records, planning the tiles, copying the tables -- is paid by sh_seq_create, and sh_seq_render is one launch that copies
+ * nothing.  Every track sample is a fold over the events that cover it, in list order, and every step of an event's chain is evaluated
+ * from the sample's position inside the event, so a window rendered alone holds exactly the bytes of that slice of the whole song.
+ * Replaces: nothing upstream renders part of a track; this is what lets a sequenced song be streamed chunk by chunk to a player, or its
+ * middle be rendered again.
+ * sh_seq_create takes sh_mix_events_chan's arguments without the track -- the rows are sh_mix_event_chan's, a row without a mode, flag,
+ * loop or rate being the lower level's event -- and refuses what sh_mix_events_chan refuses, in the same words under its own name.  The
+ * song is track_samples long and starts as silence.  The records are written for the LOWEST feature level that covers every row
+ * (sh_seq_info.level), so a plain list is rendered by the plain kernels.  The tables go into a device block the handle owns.
+ * LIFETIME: the handle keeps POINTERS into the sources and their byte ranges, not their data: the caller keeps every source buffer
+ * alive, and unchanged, until sh_seq_destroy.
+ * sh_seq_render writes song samples [first_sample, first_sample + nsamples) to samples out_sample .. of `out`, from silence: it never
+ * reads `out` and writes every sample of the range, zeros where nothing plays.  Any sample offset is legal on either side; the steps that
+ * count parity (tostereo, balance, downmix) count the SONG's samples.  nsamples == 0: SH_OK, nothing launched.  SH_ERR_INVALID, nothing
+ * launched: a NULL argument, a range outside the song, a range outside `out`, an `out` range that overlaps a source of the song. */
+typedef struct sh_seq sh_seq;
+#define SH_SEQ_LEVEL_PLAIN 0u      /* placed, scaled, added */
+#define SH_SEQ_LEVEL_RATE  1u      /* + audioop.ratecv */
+#define SH_SEQ_LEVEL_PAN   2u      /* + a mono source into a stereo song */
+#define SH_SEQ_LEVEL_ENV   3u      /* + envelopes */
+#define SH_SEQ_LEVEL_LOOP  4u      /* + sustain loops */
+#define SH_SEQ_LEVEL_REV   5u      /* + reversed playback */
+#define SH_SEQ_LEVEL_CHAN  6u      /* + downmix and balance */
+typedef struct sh_seq_info {
+    uint64_t track_samples;        /* the song's length */
+    uint64_t pairs;                /* (event, tile) overlaps: the entries of the per-tile index */
+    uint64_t device_bytes;         /* records, segments and index on the device */
+    uint32_t nevents;
+    uint32_t ntiles;               /* tiles of the song (2048 samples at 16 bits, 1024 otherwise), idle ones included */
+    uint32_t active_tiles;         /* those that some event touches */
+    uint32_t level;                /* SH_SEQ_LEVEL_* */
+} sh_seq_info;                     /* 40 bytes */
+int sh_seq_create(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_chan* events, uint32_t nevents,
+                  const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, size_t track_samples, sh_seq** out);
+int sh_seq_render(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample);
+int sh_seq_get_info(const sh_seq* seq, sh_seq_info* out);
+int sh_seq_destroy(sh_seq* seq);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

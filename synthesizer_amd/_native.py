@@ -88,6 +88,14 @@ class Counters(C.Structure):
                 ("segmented_launches", C.c_uint64), ("tiled_launches", C.c_uint64), ("tiled_predicted", C.c_uint64)]
 
 
+class SeqInfo(C.Structure):                                                          # sh_seq_info
+    _fields_ = [("track_samples", C.c_uint64), ("pairs", C.c_uint64), ("device_bytes", C.c_uint64), ("nevents", C.c_uint32),
+                ("ntiles", C.c_uint32), ("active_tiles", C.c_uint32), ("level", C.c_uint32)]
+
+
+SEQ_LEVELS = ("plain", "rate", "pan", "env", "loop", "rev", "chan")                   # SH_SEQ_LEVEL_*
+
+
 class DevInfo(C.Structure):
     _fields_ = [("name", C.c_char * 128), ("arch", C.c_char * 32), ("compute_units", C.c_int32),
                 ("clock_mhz", C.c_int32), ("hbm_bytes", C.c_uint64), ("wavefront", C.c_int32), ("device", C.c_int32)]
@@ -161,6 +169,10 @@ _SIGNATURES = {
     "sh_mix_events_loop": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_size_t]),
     "sh_mix_events_rev": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_size_t]),
     "sh_mix_events_chan": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_size_t]),
+    "sh_seq_create": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, C.c_size_t, C.POINTER(_P)]),
+    "sh_seq_render": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t]),
+    "sh_seq_get_info": (C.c_int, [_P, C.POINTER(SeqInfo)]),
+    "sh_seq_destroy": (C.c_int, [_P]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),
@@ -379,6 +391,47 @@ class RtLane:
     def __del__(self) -> None:
         try:
             self.close()
+        except Exception:
+            pass
+
+
+class Sequence:
+    """RAII wrapper over sh_seq: a list of placed samples compiled once (records and per-tile index resident on the device), rendered
+    window by window.  ``sources`` are the DeviceBuffers the records point into: the handle keeps them alive."""
+
+    def __init__(self, sources, table: np.ndarray, segments: Optional[np.ndarray], width: int, nchannels: int, track_samples: int) -> None:
+        ensure_init()
+        assert table.dtype == MIX_EVENT_CHAN_DTYPE and (segments is None or segments.dtype == ENV_SEGMENT_DTYPE)
+        self._sources = list(sources)
+        self._h = _P()
+        srcs = (C.c_void_p * max(1, len(self._sources)))(*[b.handle for b in self._sources])
+        nseg = 0 if segments is None else len(segments)
+        check(lib().sh_seq_create(srcs, len(self._sources), _ptr(table), len(table), _ptr(segments), nseg, width, nchannels,
+                                  track_samples, C.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> dict:
+        i = SeqInfo()
+        check(lib().sh_seq_get_info(self._h, C.byref(i)))
+        return {name: getattr(i, name) for name, _ in SeqInfo._fields_}
+
+    def render(self, first_sample: int, nsamples: int, out: "DeviceBuffer", out_sample: int = 0) -> None:
+        check(lib().sh_seq_render(self._h, first_sample, nsamples, out.handle, out_sample))
+
+    def free(self) -> None:
+        if self._h:
+            try:
+                lib().sh_seq_destroy(self._h)
+            finally:
+                self._h = _P()
+                self._sources = []
+
+    def __del__(self) -> None:
+        try:
+            self.free()
         except Exception:
             pass
 

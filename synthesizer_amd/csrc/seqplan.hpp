@@ -1,6 +1,8 @@
 // seqplan.hpp -- which tiles of a track a list of placed samples touches, and which events each of them folds, in which order
 // (sh_mix_events, sequence.hip): the active tiles, heaviest first, and per tile the indices of its events in list order, as one
-// CSR array.  Plain C++17, no HIP include (tests/cpu_seqplan.cpp builds it with g++): nothing here launches or allocates on the device.
+// CSR array.  plan_by_tile is the same index for a list that is kept (sh_seq_create): EVERY tile of the song in song order, so that a
+// window of the song finds its tiles by their number.  Plain C++17, no HIP include (tests/cpu_seqplan.cpp and tests/cpu_seqtiles.cpp
+// build it with g++): nothing here launches or allocates on the device.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -61,6 +63,50 @@ inline Plan plan(const Event* ev, uint32_t nev, uint64_t track_samples, uint32_t
         const uint32_t t = P.tiles[k];
         P.first[k + 1] = P.first[k] + count[t];
         cursor[t] = P.first[k];
+    }
+    P.idx.resize((size_t)pairs);
+    for (uint32_t e = 0; e < nev; ++e) {
+        if (!ev[e].n) continue;
+        const uint32_t t0 = (uint32_t)(ev[e].dst / tile), t1 = (uint32_t)((ev[e].dst + ev[e].n - 1) / tile);
+        for (uint32_t t = t0; t <= t1; ++t) P.idx[cursor[t]++] = e;
+    }
+    return P;
+}
+
+// The same index for a song that is kept and rendered window by window (sh_seq_create, sh_seq_render): every tile of the song in SONG
+// order, tile t folding idx[first[t] .. first[t + 1]) -- an empty range where no event plays, which a window kernel renders as silence.
+// A window's workgroups find their tiles by number, so nothing is sorted and nothing names the tiles.  plan's refusals, in plan's order.
+struct TilePlan {
+    Refusal refused = OK;
+    uint32_t bad_event = 0;               // EVENT_BEYOND_TRACK: the first such event
+    uint32_t ntiles = 0;                  // ceil(track_samples / tile)
+    uint32_t active = 0;                  // tiles with at least one event
+    std::vector<uint32_t> first;          // ntiles + 1 offsets into idx
+    std::vector<uint32_t> idx;            // event indices, ascending inside a tile (= list order)
+};
+
+inline TilePlan plan_by_tile(const Event* ev, uint32_t nev, uint64_t track_samples, uint32_t tile, uint64_t max_pairs = MAX_PAIRS) {
+    TilePlan P;
+    if (track_samples > MAX_TRACK_SAMPLES) { P.refused = TRACK_TOO_LONG; return P; }
+    for (uint32_t e = 0; e < nev; ++e)
+        if (ev[e].dst > track_samples || ev[e].n > track_samples - ev[e].dst) { P.refused = EVENT_BEYOND_TRACK; P.bad_event = e; return P; }
+    const uint32_t ntiles = (uint32_t)((track_samples + tile - 1) / tile);
+    std::vector<uint32_t> count(ntiles, 0);
+    uint64_t pairs = 0;
+    for (uint32_t e = 0; e < nev; ++e) {
+        if (!ev[e].n) continue;
+        const uint32_t t0 = (uint32_t)(ev[e].dst / tile), t1 = (uint32_t)((ev[e].dst + ev[e].n - 1) / tile);
+        pairs += (uint64_t)(t1 - t0) + 1;
+        if (pairs > max_pairs) { P.refused = TOO_MANY_PAIRS; return P; }
+        for (uint32_t t = t0; t <= t1; ++t) ++count[t];
+    }
+    P.ntiles = ntiles;
+    P.first.assign((size_t)ntiles + 1, 0);
+    std::vector<uint32_t>& cursor = count;                                  // from here on: where tile t's next index goes
+    for (uint32_t t = 0; t < ntiles; ++t) {
+        if (count[t]) ++P.active;
+        P.first[t + 1] = P.first[t] + count[t];
+        cursor[t] = P.first[t];
     }
     P.idx.resize((size_t)pairs);
     for (uint32_t e = 0; e < nev; ++e) {

@@ -36,6 +36,15 @@
 // event of ENV).  Three kernel templates call it: the plain 16-bit one (INFLIGHT records and source vectors in flight), the 16-bit one
 // of the other levels (one record ahead) and the one of widths 1, 3, 4.  Built with -ffp-contract=off (the float64 product of
 // audioop.mul stays one rounding, ratecv's prev*d + cur*(outr-d) two, tomono's l*left + r*right three).
+//
+// A list that is KEPT (sh_seq_create: the checks, the records of the lowest level that covers every row, the segments and
+// shq::plan_by_tile's index -- every tile of the song in song order -- uploaded once into a block the handle owns) is rendered window by
+// window by three more templates, k_win_plain16, k_win_16 and k_win_w, which mirror the three above and call the same seq_event, seq_fold8
+// and seq_fold_w: one workgroup per song tile of the window (workgroup k takes tile lo / TILE + k; a window that is the WHOLE song takes
+// tile order[k], the tiles heaviest first, a permutation the handle keeps -- song order lost to it when measured), lanes at SONG positions, the fold started from silence, every sample of the
+// window stored (zeros in a tile no event touches) through a pointer the host has biased by out_sample - first_sample, one 16-byte
+// vector per lane where the lane lies inside the window and the host found the biased base aligned.  sh_seq_render is that one launch and
+// copies nothing; a window of the song holds the bytes of that slice of the whole song, since every track sample is its own fold.
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
@@ -46,6 +55,7 @@
 #include "seqplan.hpp"
 #include <math.h>
 #include <string.h>
+#include <new>
 #include <type_traits>
 #include <vector>
 
@@ -740,6 +750,143 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_w(const typename SeqR
     seq_track_store_w<WIDTH>(track, s0, track_samples, acc);
 }
 
+// ---- a window of a kept song (sh_seq_render) -------------------------------------------------------------------------------------------
+// The three templates again for a list that is resident (sh_seq, below): the records, the segments and plan_by_tile's index -- EVERY tile
+// of the song in song order -- were uploaded once, and a render of song samples [lo, hi) is one launch that copies nothing.  Workgroup k
+// folds song tile lo / TILE + k -- or, where the window is the whole song, tile order[k] of the handle's heaviest-first permutation (the
+// order of shq::plan: measured, profiles/sequence_plan_ab.txt); either way t0 and s0 stay SONG coordinates, so the resident index is used as it is, seq_event sees what it sees in
+// the kernels above, and the steps that count parity (tostereo, balance, downmix) count the song's samples whatever sample the window
+// starts on.  The fold starts from silence -- no load of a base -- and the lane stores to out + s0, `out` being the caller's buffer biased
+// by (out_sample - first_sample) samples on the host.  A lane wholly inside the window stores one 16-byte vector where the host found the
+// biased base on a 16-byte boundary; a lane on the window's edge, or any lane of a misaligned window, stores sample by sample inside
+// [lo, hi) alone; a lane outside the window exits.  A tile that no event touches has an empty index range and stores zeros: every sample
+// of the window is written, so the caller's buffer needs no memset.
+// `out` is the BIASED base: an address formed with integers on the host, which may lie outside the caller's buffer (below it, even wrapped,
+// when first_sample > out_sample).  It means something only as out + s for s in [lo, hi): nothing may be read or written through it
+// elsewhere, and it carries no __restrict__ and no bounds of its own.
+__device__ __forceinline__ void seq_window_store8(short* out, uint32_t s0, uint32_t lo, uint32_t hi, bool whole, const short8v acc) {
+    if (whole) *reinterpret_cast<short8v*>(out + s0) = acc;
+    else {
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j)
+            if (s0 + j >= lo && s0 + j < hi) out[s0 + j] = acc[j];
+    }
+}
+
+// the song tile of workgroup k of a window that starts at sample lo, or false: a workgroup beyond the window (a grid folded into two
+// dimensions has some) or a lane none of whose samples lie in [lo, hi)
+// order: NULL, or -- a window that is the whole song (lo == 0, hi the song's length) -- the song's tiles heaviest first, as shq::plan has
+// them: workgroup k folds tile order[k], so that a pile-up is not the last workgroup to start.
+template <int WIDTH>
+__device__ __forceinline__ bool seq_window_lane(const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, uint32_t& tile, uint32_t& t0, uint32_t& s0) {
+    uint64_t t = (uint64_t)(lo / SEQ_TILE<WIDTH>) + sh::block_id();
+    if (t * SEQ_TILE<WIDTH> >= hi) return false;              // (uniform; the whole song: workgroup k of ceil(hi / TILE))
+    if (order) t = order[t];                                  // (uniform)
+    tile = (uint32_t)t;
+    t0 = tile * SEQ_TILE<WIDTH>;
+    s0 = t0 + threadIdx.x * SEQ_LANE<WIDTH>;
+    return s0 < hi && s0 + SEQ_LANE<WIDTH> > lo;              // (no wrap: MAX_TRACK_SAMPLES)
+}
+
+// PLAIN at 16 bits: k_seq_plain16's schedule, INFLIGHT records and source vectors in flight
+template <int SCHEME, int INFLIGHT>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_win_plain16(const SeqEv* __restrict__ ev, const she::Seg* __restrict__ segs,
+                                                                   const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
+                                                                   const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, short* out, int aligned) {
+    uint32_t k, t0, s0;
+    if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
+    const bool whole = aligned && s0 >= lo && s0 + 8 <= hi;
+    short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t e = first[k];
+    const uint32_t e1 = first[k + 1];
+    if (e1 - e >= INFLIGHT) {
+        SeqEv c[INFLIGHT], nx[INFLIGHT];
+#pragma unroll
+        for (int u = 0; u < INFLIGHT; ++u) c[u] = ev[idx[e + u]];
+        for (; e + INFLIGHT <= e1; e += INFLIGHT) {
+            const bool more = e + 2 * INFLIGHT <= e1;
+            if (more) {
+#pragma unroll
+                for (int u = 0; u < INFLIGHT; ++u) nx[u] = ev[idx[e + INFLIGHT + u]];
+            }
+            short8v x[INFLIGHT];
+#pragma unroll
+            for (int u = 0; u < INFLIGHT; ++u) x[u] = seq_event8<PLAIN, SCHEME>(c[u], segs, t0, s0);
+#pragma unroll
+            for (int u = 0; u < INFLIGHT; ++u) seq_fold8(acc, x[u], c[u].factor);
+            if (more) {
+#pragma unroll
+                for (int u = 0; u < INFLIGHT; ++u) c[u] = nx[u];
+            }
+        }
+    }
+    for (; e < e1; ++e) {
+        const SeqEv c = ev[idx[e]];
+        seq_fold8(acc, seq_event8<PLAIN, SCHEME>(c, segs, t0, s0), c.factor);
+    }
+    seq_window_store8(out, s0, lo, hi, whole, acc);
+}
+
+// The other levels at 16 bits: k_seq_16's schedule, one record ahead, from LOOP on the next record's index.  An idle tile reads neither:
+// behind the last event idx holds nothing.
+template <int LEVEL, int SCHEME>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_win_16(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
+                                                              const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
+                                                              const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, short* out, int aligned) {
+    typedef typename SeqRec<LEVEL>::type Rec;
+    uint32_t k, t0, s0;
+    if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
+    const bool whole = aligned && s0 >= lo && s0 + 8 <= hi;
+    short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t e = first[k];
+    const uint32_t e1 = first[k + 1];
+    if (e < e1) {                                             // (uniform)
+        if constexpr (LEVEL >= LOOP) {
+            uint32_t ni = idx[e];
+            while (e < e1) {
+                const Rec c = ev[ni];
+                if (++e < e1) ni = idx[e];
+                seq_fold8(acc, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
+            }
+        } else {
+            Rec nx = ev[idx[e]];
+            while (e < e1) {
+                const Rec c = nx;
+                if (++e < e1) nx = ev[idx[e]];
+                seq_fold8(acc, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
+            }
+        }
+    }
+    seq_window_store8(out, s0, lo, hi, whole, acc);
+}
+
+// Widths 1, 3 and 4: k_seq_w's loop from silence, every sample of the lane that lies in the window stored
+template <int LEVEL, int WIDTH>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_win_w(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
+                                                             const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
+                                                             const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, unsigned char* out) {
+    static_assert(LEVEL != ENV || WIDTH == 1 || WIDTH == 4, "an envelope has widths 1, 2 and 4");
+    uint32_t k, t0, s0;
+    if (!seq_window_lane<WIDTH>(order, lo, hi, k, t0, s0)) return;
+    long long acc[4] = {0, 0, 0, 0};
+    const uint32_t e1 = first[k + 1];
+    for (uint32_t e = first[k]; e < e1; ++e) {
+        const typename SeqRec<LEVEL>::type c = ev[idx[e]];
+        if constexpr (LEVEL == PLAIN) {
+            const unsigned char* src = (const unsigned char*)c.src;
+            seq_fold_w<WIDTH>(acc, c.factor, s0, c.dst, c.n, [&](int, long long rel) { return chain_get<WIDTH>(src, (size_t)rel); });
+        } else {
+            int v[4];
+            seq_event<LEVEL, WIDTH, FUNNEL>(c, segs, t0, s0, v);
+            seq_fold_w<WIDTH>(acc, c.factor, s0, c.dst, c.n, [&](int j, long long) { return (long long)v[j]; });
+        }
+    }
+    unsigned char* p = out + (size_t)WIDTH * s0;             // (the biased base, as seq_window_store8's: valid at samples [lo, hi) alone)
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j)
+        if (s0 + j >= lo && s0 + j < hi) chain_put<WIDTH>(p, j, acc[j]);
+}
+
 }  // namespace
 
 // ---- host: what the entry points share ----------------------------------------------------------------------------------------------
@@ -1110,6 +1257,217 @@ int sh_mix_events_chan(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_ev
         return v;
     };
     return seq_mix<CHAN>(fn, in, srcs, nsrc, nevents, segments, nsegments, width, nchannels, track, track_samples);
+}
+
+}  // extern "C"
+
+// ---- a kept song: sh_seq ---------------------------------------------------------------------------------------------------------------
+// What sh_mix_events_chan does in front of its launch, done once: the checked events as records of the LOWEST level whose chain covers
+// every row, the segments, and plan_by_tile's index, in one device block that the handle owns (the buffer pool's, as sh_buf_alloc's; not
+// the grow-only scratch, which the next call overwrites).  The records point into the sources: the caller keeps those alive.
+struct sh_seq {
+    void*    block = nullptr;             // records | segments | first | idx | order
+    size_t   cap = 0, bytes = 0;
+    size_t   at_segs = 0, at_first = 0, at_idx = 0, at_order = 0;     // order: the tiles heaviest first, for a render of the whole song
+    int      width = 0, nchannels = 0, level = 0;
+    uint32_t nevents = 0, ntiles = 0, active_tiles = 0;
+    uint64_t track_samples = 0, pairs = 0;
+    std::vector<const char*> src_lo, src_hi;      // the byte ranges of the sources: a render's `out` may overlap none
+};
+
+namespace {
+
+// the lowest level whose chain covers the row
+int seq_row_level(const SeqIn& m) {
+    if (m.downmix() || m.balance()) return CHAN;
+    if (m.reversed()) return REV;
+    if (m.loop_frames && m.src_frames > m.loop_start + m.loop_frames) return LOOP;        // (no longer than its head: a plain cut, seq_fill)
+    if (m.seg_count) return ENV;
+    if (m.tostereo()) return PAN;
+    if (m.inrate != m.outrate) return RATE;
+    return PLAIN;
+}
+
+template <int LEVEL>
+void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out) {
+    typedef typename SeqRec<LEVEL>::type Rec;
+    const char* b = (const char*)q->block;
+    const Rec* ev = (const Rec*)b;
+    const she::Seg* segs = (const she::Seg*)(b + q->at_segs);
+    const uint32_t* first = (const uint32_t*)(b + q->at_first);
+    const uint32_t* idx = (const uint32_t*)(b + q->at_idx);
+    // the whole song: heaviest tile first (measured: profiles/sequence_plan_ab.txt); any other window: its tiles in song order
+    const uint32_t* order = lo == 0 && hi == q->track_samples ? (const uint32_t*)(b + q->at_order) : nullptr;
+    const dim3 block(shq::TILE_THREADS);
+    if (q->width == 2) {
+        const int aligned = ((uintptr_t)out & 15) == 0;       // the BIASED base: song-anchored lanes start on multiples of eight samples
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (short*)out, aligned); };
+        const bool vec2 = sh::knobs().seq_align == VEC2;
+        if constexpr (LEVEL == PLAIN) vec2 ? go(k_win_plain16<VEC2, 4>) : go(k_win_plain16<FUNNEL, 4>);
+        else vec2 ? go(k_win_16<LEVEL, VEC2>) : go(k_win_16<LEVEL, FUNNEL>);
+    } else {
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out); };
+        if (q->width == 1) go(k_win_w<LEVEL, 1>);
+        else if (q->width == 4) go(k_win_w<LEVEL, 4>);
+        else if constexpr (LEVEL != ENV) go(k_win_w<LEVEL, 3>);       // (sh_seq_create refuses width 3 with segments)
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sh_seq_create(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_chan* events, uint32_t nevents,
+                  const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, size_t track_samples, sh_seq** out) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_seq_create";
+    // The refusals in front of the events, in the ORDER sh_mix_events_chan reports them (seq_check_args without its track, the width-3
+    // refusal, then seq_mix's two), so that a call with two faults names the same one here and there.
+    if (!out) return seq_null(fn);
+    *out = nullptr;
+    if (width < 1 || width > 4) return sh::set_error(SH_ERR_INVALID, "%s: width %d not in {1, 2, 3, 4}", fn, width);
+    if ((nevents && !events) || (nsrc && !srcs)) return seq_null(fn);
+    if (width == 3) {
+        for (uint32_t e = 0; e < nevents; ++e)
+            if (events[e].seg_count) return sh::set_error(SH_ERR_INVALID, "%s: event %u: width 3: an envelope's fades have no 24-bit form", fn, e);
+    }
+    if (nchannels < 1) return sh::set_error(SH_ERR_INVALID, "%s: # of channels should be >= 1", fn);
+    if (nsegments && !segments) return seq_null(fn);
+    auto in = [=](uint32_t e) {
+        const sh_mix_event_chan& m = events[e];
+        SeqIn v{m.dst_sample, m.src_sample, m.nsamples, m.src_frames, m.factor, m.left, m.right, m.src, m.inrate, m.outrate, m.src_channels,
+                m.seg_first, m.seg_count, m.reserved, nchannels};
+        v.loop_start = m.loop_start;
+        v.loop_frames = m.loop_frames;
+        v.flags = m.flags;
+        return v;
+    };
+    std::vector<shq::Event> pe(nevents);
+    int rc = seq_check_events(fn, CHAN, in, nevents, srcs, nsrc, segments, nsegments, width, pe);
+    if (rc) return rc;
+    const shq::TilePlan P = shq::plan_by_tile(pe.data(), nevents, track_samples, shq::tile_samples(width));
+    if (P.refused == shq::EVENT_BEYOND_TRACK) return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside the track", fn, P.bad_event);
+    if (P.refused == shq::TRACK_TOO_LONG) return sh::set_error(SH_ERR_INVALID, "%s: at most 2^32 - 65536 track samples per call", fn);
+    if (P.refused) return sh::set_error(SH_ERR_INVALID, "%s: more than 2^28 (event, tile) overlaps in one call", fn);
+    int level = PLAIN;
+    for (uint32_t e = 0; e < nevents; ++e) level = std::max(level, seq_row_level(in(e)));
+    const size_t rec = level == PLAIN ? sizeof(SeqEv) : level == RATE ? sizeof(SeqEvR) : sizeof(SeqEvV);       // (PAN .. CHAN: 96 bytes)
+    sh_seq* q = new (std::nothrow) sh_seq;
+    if (!q) return sh::set_error(SH_ERR_NOMEM, "host allocation failed");
+    q->width = width;
+    q->nchannels = nchannels;
+    q->level = level;
+    q->nevents = nevents;
+    q->ntiles = P.ntiles;
+    q->active_tiles = P.active;
+    q->track_samples = track_samples;
+    q->pairs = P.idx.size();
+    q->at_segs = (size_t)nevents * rec;
+    q->at_first = q->at_segs + (size_t)nsegments * sizeof(she::Seg);
+    q->at_idx = q->at_first + P.first.size() * 4;
+    q->at_order = q->at_idx + P.idx.size() * 4;
+    q->bytes = q->at_order + (size_t)P.ntiles * 4;
+    for (uint32_t v = 0; v < nsrc; ++v) {
+        if (!srcs[v] || !srcs[v]->bytes) continue;
+        q->src_lo.push_back((const char*)srcs[v]->ptr);
+        q->src_hi.push_back((const char*)srcs[v]->ptr + srcs[v]->bytes);
+    }
+    std::vector<char> host(q->bytes);
+    switch (level) {
+    case PLAIN: seq_fill<PLAIN>(reinterpret_cast<SeqEv*>(host.data()), in, nevents, srcs, width); break;
+    case RATE: seq_fill<RATE>(reinterpret_cast<SeqEvR*>(host.data()), in, nevents, srcs, width); break;
+    case PAN: seq_fill<PAN>(reinterpret_cast<SeqEvP*>(host.data()), in, nevents, srcs, width); break;
+    case ENV: seq_fill<ENV>(reinterpret_cast<SeqEvE*>(host.data()), in, nevents, srcs, width); break;
+    case LOOP: seq_fill<LOOP>(reinterpret_cast<SeqEvL*>(host.data()), in, nevents, srcs, width); break;
+    case REV: seq_fill<REV>(reinterpret_cast<SeqEvV*>(host.data()), in, nevents, srcs, width); break;
+    default: seq_fill<CHAN>(reinterpret_cast<SeqEvV*>(host.data()), in, nevents, srcs, width); break;
+    }
+    she::Seg* seg = reinterpret_cast<she::Seg*>(host.data() + q->at_segs);
+    for (uint32_t s = 0; s < nsegments; ++s) {
+        const sh_env_segment& g = segments[s];                // (a segment that no event names was not checked, and no kernel reads it)
+        seg[s] = she::Seg{g.mul, g.slope, g.numsamples, g.offset, (uint32_t)g.end, (uint32_t)g.origin, g.kind, 0};
+    }
+    memcpy(host.data() + q->at_first, P.first.data(), P.first.size() * 4);
+    if (!P.idx.empty()) memcpy(host.data() + q->at_idx, P.idx.data(), P.idx.size() * 4);
+    if (P.ntiles) {                                           // every tile, heaviest first, ties in song order (idle tiles last)
+        std::vector<uint32_t> order(P.ntiles);
+        for (uint32_t t = 0; t < P.ntiles; ++t) order[t] = t;
+        std::stable_sort(order.begin(), order.end(),
+                         [&](uint32_t a, uint32_t b) { return P.first[a + 1] - P.first[a] > P.first[b + 1] - P.first[b]; });
+        memcpy(host.data() + q->at_order, order.data(), (size_t)P.ntiles * 4);
+    }
+    rc = sh::pool_alloc(q->bytes, &q->block, &q->cap);
+    if (rc) {
+        delete q;
+        return rc;
+    }
+    hipStream_t st = sh::state().stream;
+    hipError_t e = hipMemcpyAsync(q->block, host.data(), host.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);        // once per song: the host copy goes when this returns
+    if (e != hipSuccess) {
+        sh::pool_free(q->block, q->cap);
+        delete q;
+        return sh::hip_error(e, fn);
+    }
+    *out = q;
+    return SH_OK;
+}
+
+int sh_seq_render(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_seq_render";
+    if (!seq || !out) return seq_null(fn);
+    const size_t w = (size_t)seq->width;
+    if (first_sample > seq->track_samples || nsamples > seq->track_samples - first_sample)
+        return sh::set_error(SH_ERR_INVALID, "%s: range outside the song", fn);
+    const size_t have = out->bytes / w;
+    if (out_sample > have || nsamples > have - out_sample) return sh::set_error(SH_ERR_INVALID, "%s: range outside out", fn);
+    if (!nsamples) return SH_OK;
+    const char* o0 = (const char*)out->ptr + out_sample * w;
+    const char* o1 = o0 + nsamples * w;
+    for (size_t v = 0; v < seq->src_lo.size(); ++v)
+        if (seq->src_lo[v] < o1 && o0 < seq->src_hi[v]) return sh::set_error(SH_ERR_INVALID, "%s: out overlaps a source of the song", fn);
+    const uint32_t lo = (uint32_t)first_sample, hi = (uint32_t)(first_sample + nsamples), tile = shq::tile_samples(seq->width);
+    const uint32_t nt = (hi - 1) / tile - lo / tile + 1;
+    // the store's base, biased so that song sample s lands on out[out_sample + s - first_sample]: integer address arithmetic
+    void* biased = (void*)((uintptr_t)out->ptr + w * (uintptr_t)out_sample - w * (uintptr_t)first_sample);
+    const dim3 grid = sh::grid1d(nt, 1);
+    hipStream_t st = sh::state().stream;
+    switch (seq->level) {
+    case PLAIN: seq_window_launch<PLAIN>(seq, grid, st, lo, hi, biased); break;
+    case RATE: seq_window_launch<RATE>(seq, grid, st, lo, hi, biased); break;
+    case PAN: seq_window_launch<PAN>(seq, grid, st, lo, hi, biased); break;
+    case ENV: seq_window_launch<ENV>(seq, grid, st, lo, hi, biased); break;
+    case LOOP: seq_window_launch<LOOP>(seq, grid, st, lo, hi, biased); break;
+    case REV: seq_window_launch<REV>(seq, grid, st, lo, hi, biased); break;
+    default: seq_window_launch<CHAN>(seq, grid, st, lo, hi, biased); break;
+    }
+    SH_CHECK_LAUNCH(fn);
+    return SH_OK;
+}
+
+int sh_seq_get_info(const sh_seq* seq, sh_seq_info* out) {
+    SH_API_LOCK();
+    if (!seq || !out) return seq_null("sh_seq_get_info");
+    out->track_samples = seq->track_samples;
+    out->pairs = seq->pairs;
+    out->device_bytes = seq->bytes;
+    out->nevents = seq->nevents;
+    out->ntiles = seq->ntiles;
+    out->active_tiles = seq->active_tiles;
+    out->level = (uint32_t)seq->level;
+    return SH_OK;
+}
+
+int sh_seq_destroy(sh_seq* seq) {
+    if (!seq) return SH_OK;
+    SH_API_LOCK();
+    if (seq->block && sh::state().initialized) {
+        if (sh::has_pending()) sh::flush_pending();
+        sh::pool_free(seq->block, seq->cap);                  // (stream-ordered reuse: a render still in flight finishes first)
+    }
+    delete seq;
+    return SH_OK;
 }
 
 }  // extern "C"

@@ -30,7 +30,7 @@ from . import params
 from .oscillators import Oscillator, VoiceSpec, _pwm_widths, _table, pack_voices, time_step_weights
 from .sample import Sample
 
-__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "sequence", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
+__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "sequence", "compile_sequence", "CompiledSequence", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
 
 
 def pan_gains(pan: float) -> Tuple[float, float]:
@@ -588,6 +588,105 @@ def sequence(events: Sequence[tuple], samplerate: int, nchannels: int, samplewid
     in that order."""
     track = Sample(name=name, samplerate=samplerate, nchannels=nchannels, samplewidth=samplewidth)
     return track.mix_at_many(events)
+
+
+class CompiledSequence:
+    """A list of placed samples compiled once and rendered as often, and in whatever windows, as a player asks: ``render`` of frames
+    ``[a, b)`` holds, byte for byte, frames ``[a, b)`` of ``sequence(events, ...)``, in one launch that copies no table.  Made by
+    ``compile_sequence``.  The song sounds as its samples did WHEN IT WAS COMPILED: they are taken with ``Sample._share_device()``
+    (as ``RealTimeMixer.add_sample`` takes them), so a sample that is amplified or mixed into afterwards writes a buffer of its own, and
+    this object holds the buffers it reads.  ``close()`` (or the ``with`` block, or the last reference) frees the device tables."""
+
+    def __init__(self, events: Sequence[tuple], samplerate: int, nchannels: int, samplewidth: int = 2, name: str = "") -> None:
+        self._seq = None
+        self.name = name
+        self.samplerate, self.nchannels, self.samplewidth = int(samplerate), int(nchannels), int(samplewidth)
+        track = Sample(name=name, samplerate=samplerate, nchannels=nchannels, samplewidth=samplewidth)
+        bufs, table, segtab, nbytes = track._compile_events(events)        # every ValueError of mix_at_many, before the device is reached
+        self._fb = self.samplewidth * self.nchannels
+        self.frames = nbytes // self._fb
+        self._nevents = len(table)
+        self._seq = N.Sequence(bufs, table, segtab, self.samplewidth, self.nchannels, nbytes // self.samplewidth)
+        self.level = N.SEQ_LEVELS[self._seq.info()["level"]]
+
+    @property
+    def duration(self) -> float:
+        return self.frames / self.samplerate
+
+    def __len__(self) -> int:
+        return self.frames
+
+    def info(self) -> dict:
+        """sh_seq_info: events, tiles, active tiles, (event, tile) pairs, device bytes, level"""
+        return self._handle().info()
+
+    def _handle(self) -> "N.Sequence":
+        if self._seq is None:
+            raise ValueError("CompiledSequence: closed")
+        return self._seq
+
+    def _range(self, start_frame: int, nframes: Optional[int]) -> Tuple[int, int]:
+        start_frame = int(start_frame)
+        if start_frame < 0 or start_frame > self.frames:
+            raise ValueError("CompiledSequence: start_frame %d outside the song's %d frames" % (start_frame, self.frames))
+        nframes = self.frames - start_frame if nframes is None else int(nframes)
+        if nframes < 0 or nframes > self.frames - start_frame:
+            raise ValueError("CompiledSequence: frames [%d, %d) outside the song's %d frames" % (start_frame, start_frame + nframes, self.frames))
+        return start_frame, nframes
+
+    def render_into(self, buf: N.DeviceBuffer, byte_offset: int, start_frame: int, nframes: int) -> None:
+        """Frames ``[start_frame, start_frame + nframes)`` of the song into ``buf`` from ``byte_offset`` (a whole number of samples) on:
+        every byte of the range is written, whatever ``buf`` held."""
+        seq = self._handle()
+        start_frame, nframes = self._range(start_frame, nframes)
+        if byte_offset < 0 or byte_offset % self.samplewidth:
+            raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
+        if nframes:
+            seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth)
+
+    def render(self, start_frame: int = 0, nframes: Optional[int] = None) -> Sample:
+        """A new ``Sample``: frames ``[start_frame, start_frame + nframes)`` of the song; ``nframes`` None: to the end."""
+        self._handle()
+        start_frame, nframes = self._range(start_frame, nframes)
+        out = Sample(name=self.name, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth)
+        if nframes:
+            buf = N.DeviceBuffer(nframes * self._fb)
+            self.render_into(buf, 0, start_frame, nframes)
+            out._set_device(buf, nframes * self._fb)
+        return out
+
+    def chunks(self, chunk_frames: int) -> Generator[Sample, None, None]:
+        """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter"""
+        chunk_frames = int(chunk_frames)
+        if chunk_frames <= 0:
+            raise ValueError("CompiledSequence: chunk_frames must be positive")
+        for at in range(0, self.frames, chunk_frames):
+            yield self.render(at, min(chunk_frames, self.frames - at))
+
+    def close(self) -> None:
+        if self._seq is not None:
+            self._seq.free()
+            self._seq = None
+
+    def __enter__(self) -> "CompiledSequence":
+        return self
+
+    def __exit__(self, *_exc) -> None:
+        self.close()
+
+    def __del__(self) -> None:
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def compile_sequence(events: Sequence[tuple], samplerate: int, nchannels: int, samplewidth: int = 2, name: str = "") -> CompiledSequence:
+    """``sequence``'s arguments, compiled and kept instead of rendered once: the events are checked (the ``ValueError`` /
+    ``NotImplementedError`` cases of ``Sample.mix_at_many``, raised before anything reaches the device), packed, planned tile by tile
+    and uploaded ONCE; ``CompiledSequence.render`` / ``render_into`` / ``chunks`` then give any window of the song in one launch.  An
+    event whose sample is the track itself has no meaning here (there is no track yet)."""
+    return CompiledSequence(events, samplerate, nchannels, samplewidth, name)
 
 
 class _MixSource:

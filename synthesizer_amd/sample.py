@@ -757,6 +757,49 @@ class Sample:
         goes through the loop's body above, region, reverse and a balance included (a downmix cannot occur there)."""
         self._check_writable()
         self._check_gpu_width("mix_at")
+        todo, shaped = self._check_events(events)
+        batch, envs, extras = [], {}, {}                                        # envs: index into batch -> segment rows; extras: -> (region, reverse)
+        for k, (seconds, other, volume, other_seconds, speed, start, n2, inrate, factors, loop, extra) in enumerate(todo):
+            if other is self:                                                   # (never panned: a panned event's other is mono, its track stereo)
+                self.__mix_events(batch, envs, extras)
+                batch, envs, extras = [], {}, {}
+                region, reverse = extra[:2] if extra is not None else (None, False)
+                weights = extra[2] if extra is not None and len(extra) > 2 else None
+                if region is not None:                                          # copy().clip() of the track as it is NOW
+                    end = other.duration if region[1] is None else region[1]
+                    if end < region[0]:
+                        raise ValueError("mix_at_many: region: end (%r s: the track as the events before left it) lies before start (%r s)"
+                                         % (end, region[0]))
+                    other = other.copy().clip(region[0], end)
+                if reverse:
+                    other = other.copy().reverse()
+                if loop is not None:                                            # clip(0.0, loop_end) of the track (its region, reversed) as it is NOW
+                    first, last = loop[0], min(loop[0] + loop[1], len(other))
+                    if first >= last:
+                        raise ValueError("mix_at_many: loop: no frame between loop_start (frame %d) and loop_end (frame %d) of the track "
+                                         "as the events before left it" % (first, last))
+                    other = other.__unrolled(first, last - first, loop[2])
+                if inrate != self.__samplerate:
+                    other = other.copy().speed(speed)
+                if shaped and k in shaped:
+                    envelope = shaped[k][0]
+                    other = other.copy()
+                    if len(envelope) == 5:
+                        other.clip(0.0, envelope[4])
+                    other.envelope(*envelope[:4])
+                if weights is not None:                                         # (the track is stereo here: a balance)
+                    other = other.copy().stereo(*weights)
+                self.mix_at(seconds, other if volume is None else other.at_volume(volume), other_seconds)
+            else:
+                self._batch_event(batch, envs, extras, shaped.get(k), todo[k])
+        self.__mix_events(batch, envs, extras)
+        return self
+
+    def _check_events(self, events: Iterable[tuple]) -> tuple:
+        """Every event of a list for mix_at_many checked against this track's format, before anything is mixed or reaches the device:
+        (todo, shaped) -- todo: (seconds, other, volume, other_seconds, speed, first byte, bytes, inrate, tostereo factors | None,
+        loop in frames | None, extra | None) per event; shaped: index into todo -> (envelope, its sh_env_segment rows).  The one
+        statement of mix_at_many's ValueErrors: Sample.mix_at_many and mixer.compile_sequence both go through it."""
         fb = self.__samplewidth * self.__nchannels
         rate = self.__samplerate
         todo = []                                           # everything is checked before anything is mixed
@@ -858,46 +901,30 @@ class Sample:
             if weights is not None:
                 extra = (extra if extra is not None else (None, False)) + (weights,)
             todo.append((seconds, other, volume, other_seconds, speed, start, min(n2, have), inrate, factors, loop, extra))
-        batch, envs, extras = [], {}, {}                                        # envs: index into batch -> segment rows; extras: -> (region, reverse)
-        for k, (seconds, other, volume, other_seconds, speed, start, n2, inrate, factors, loop, extra) in enumerate(todo):
-            if other is self:                                                   # (never panned: a panned event's other is mono, its track stereo)
-                self.__mix_events(batch, envs, extras)
-                batch, envs, extras = [], {}, {}
-                region, reverse = extra[:2] if extra is not None else (None, False)
-                weights = extra[2] if extra is not None and len(extra) > 2 else None
-                if region is not None:                                          # copy().clip() of the track as it is NOW
-                    end = other.duration if region[1] is None else region[1]
-                    if end < region[0]:
-                        raise ValueError("mix_at_many: region: end (%r s: the track as the events before left it) lies before start (%r s)"
-                                         % (end, region[0]))
-                    other = other.copy().clip(region[0], end)
-                if reverse:
-                    other = other.copy().reverse()
-                if loop is not None:                                            # clip(0.0, loop_end) of the track (its region, reversed) as it is NOW
-                    first, last = loop[0], min(loop[0] + loop[1], len(other))
-                    if first >= last:
-                        raise ValueError("mix_at_many: loop: no frame between loop_start (frame %d) and loop_end (frame %d) of the track "
-                                         "as the events before left it" % (first, last))
-                    other = other.__unrolled(first, last - first, loop[2])
-                if inrate != rate:
-                    other = other.copy().speed(speed)
-                if shaped and k in shaped:
-                    envelope = shaped[k][0]
-                    other = other.copy()
-                    if len(envelope) == 5:
-                        other.clip(0.0, envelope[4])
-                    other.envelope(*envelope[:4])
-                if weights is not None:                                         # (the track is stereo here: a balance)
-                    other = other.copy().stereo(*weights)
-                self.mix_at(seconds, other if volume is None else other.at_volume(volume), other_seconds)
-            else:
-                if shaped and k in shaped:
-                    envs[len(batch)] = shaped[k][1]
-                if extra is not None:
-                    extras[len(batch)] = extra
-                batch.append((start, other, n2, 1.0 if volume is None else float(volume), inrate, factors, loop))
-        self.__mix_events(batch, envs, extras)
-        return self
+        return todo, shaped
+
+    @staticmethod
+    def _batch_event(batch: list, envs: dict, extras: dict, shape, checked: tuple) -> None:
+        """one checked event of _check_events (none whose other is the track) as a row of __mix_events' batch"""
+        _seconds, other, volume, _other_seconds, _speed, start, n2, inrate, factors, loop, extra = checked
+        if shape is not None:
+            envs[len(batch)] = shape[1]
+        if extra is not None:
+            extras[len(batch)] = extra
+        batch.append((start, other, n2, 1.0 if volume is None else float(volume), inrate, factors, loop))
+
+    def _compile_events(self, events: Iterable[tuple]) -> tuple:
+        """What mixer.compile_sequence hands sh_seq_create, this sample being the empty track that says the format: mix_at_many's checks,
+        then (the sources' device buffers, shared; the table in sh_mix_event_chan's layout; the segment table; the song's bytes)."""
+        self._check_gpu_width("mix_at")
+        todo, shaped = self._check_events(events)
+        batch, envs, extras = [], {}, {}
+        for k, checked in enumerate(todo):
+            self._batch_event(batch, envs, extras, shaped.get(k), checked)
+        if not batch:
+            return [], np.zeros(0, dtype=N.MIX_EVENT_CHAN_DTYPE), None, 0
+        bufs, table, segtab = self._pack_events(batch, envs, extras, widest=True, share=True)[:3]
+        return bufs, table, segtab, max(b[0] + b[2] for b in batch)
 
     def __unrolled(self, loop_start: int, loop_frames: int, nframes: int) -> "Sample":
         """A copy with the loop written out: frames [0, loop_start + loop_frames), then frames [loop_start, loop_start + loop_frames)
@@ -912,6 +939,90 @@ class Sample:
         out = Sample(name=self.name, samplerate=self.__samplerate, nchannels=self.__nchannels, samplewidth=self.__samplewidth)
         out.__assemble(parts)
         return out
+
+    def _pack_events(self, batch: Sequence[tuple], envs: dict, extras: dict, widest: bool = False, share: bool = False) -> tuple:
+        """__mix_events' batch as the table an entry point reads, packed column by column: (the sources' device buffers, the table, the
+        segment table | None, weighed, turned, looped, shaped, panned, rated) -- the flags say which entry point the list needs.  The
+        table has the narrowest layout that holds the list; ``widest``: sh_mix_event_chan's with every column filled, whatever the
+        list holds (sh_seq_create takes that one layout and finds the level itself).  ``share``: the sources' buffers are taken with
+        _share_device, for a reader that keeps them."""
+        starts, others, nbytes, factors, inrates, pans, loops = zip(*batch)
+        w = self.__samplewidth
+        rate = self.__samplerate
+        starts = np.array(starts, dtype=np.uint64)
+        nbytes = np.array(nbytes, dtype=np.uint64)
+        inrates = np.array(inrates, dtype=np.uint64)
+        slot = {}                                           # id(other) -> (index into srcs, other): one dict lookup per event, no more
+        for o in others:
+            slot.setdefault(id(o), (len(slot), o))
+        uniq = [o for _k, o in slot.values()]
+        bufs = [o._share_device() if share else o._device() for o in uniq]
+        src = np.fromiter((slot[id(o)][0] for o in others), dtype=np.uint32, count=len(others))
+        rated = bool((inrates != rate).any())
+        panned = any(p is not None for p in pans)
+        shaped = bool(envs)
+        turned = cut = False
+        weighed = {}                                        # index into batch -> (left_factor, right_factor) of the events with channels
+        if extras:
+            weighed = {i: x[2] for i, x in extras.items() if len(x) > 2}
+            extras = {i: x[:2] for i, x in extras.items()}
+            turned = any(rv for _rg, rv in extras.values())
+            cut = any(rg is not None for rg, _rv in extras.values())
+        flagged = turned or bool(weighed)                   # a row with a flag: the table has sh_mix_event_rev's layout, which is the looped one's and more
+        looped = flagged or loops.count(None) != len(loops)
+        wide = widest or looped                             # the columns of the loop layout and beyond are there
+        table = np.zeros(len(batch), dtype=N.MIX_EVENT_CHAN_DTYPE if weighed or widest else N.MIX_EVENT_REV_DTYPE if turned else N.MIX_EVENT_LOOP_DTYPE if looped else N.MIX_EVENT_ENV_DTYPE if shaped else N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
+        table["dst_sample"] = starts // w
+        table["nsamples"] = nbytes // w
+        table["factor"] = factors
+        table["src"] = src
+        if rated or panned or shaped or wide:
+            frames = np.array([o.__nbytes // (w * o.nchannels) for o in uniq], dtype=np.uint64)
+            table["src_frames"] = frames[src]
+            table["inrate"] = inrates
+            table["outrate"] = rate
+        if panned or shaped or wide:
+            table["src_channels"] = np.array([o.nchannels for o in uniq], dtype=np.uint32)[src]
+            lr = np.array([p if p is not None else (0.0, 0.0) for p in pans], dtype=np.float64)
+            table["left"] = lr[:, 0]
+            table["right"] = lr[:, 1]
+        if cut:                                             # a slice of other: where it starts, and the frames every count above was made over
+            nch = np.array([o.nchannels for o in uniq], dtype=np.uint64)[src]
+            at = np.array([i for i, (rg, _rv) in extras.items() if rg is not None], dtype=np.intp)
+            rg = np.array([rg for rg, _rv in extras.values() if rg is not None], dtype=np.uint64)
+            table["src_sample"][at] = rg[:, 0] * nch[at]
+            if rated or panned or shaped or wide:
+                table["src_frames"][at] = rg[:, 1]
+        if wide:
+            lp = np.array([l if l is not None else (0, 0, 0) for l in loops], dtype=np.uint64)
+            table["loop_start"] = lp[:, 0]
+            table["loop_frames"] = lp[:, 1]
+            if turned:                                      # a reversed looped row plays the region's LAST loop_end frames: its region starts there
+                rv = np.array([i for i, (_rg, v) in extras.items() if v], dtype=np.intp)
+                table["flags"][rv] = N.MIX_EVENT_REVERSED
+                back = rv[lp[rv, 1] != 0]
+                table["src_sample"][back] += (table["src_frames"][back] - lp[back, 0] - lp[back, 1]) * table["src_channels"][back]
+            for i, (lf, rf) in weighed.items():             # a stereo source weighed per channel: tomono into a mono track, a balance in a stereo one
+                table["flags"][i] |= N.MIX_EVENT_DOWNMIX if self.__nchannels == 1 else N.MIX_EVENT_BALANCE
+                table["left"][i] = lf
+                table["right"][i] = rf
+            table["src_frames"] = np.where(lp[:, 1] != 0, lp[:, 2], table["src_frames"])      # a looped row: the note's virtual frames
+        segtab = None
+        if shaped or wide:
+            rows = []
+            for i, g in envs.items():
+                taken = int(nbytes[i]) // w // (2 if pans[i] is not None else 1)       # the event's source samples, after other_seconds' cut
+                if i in weighed and self.__nchannels == 1:
+                    taken *= 2                                                          # (a downmix: two stereo samples per track sample)
+                mine = [(min(r[0], taken),) + r[1:] for r in g]
+                mine = [r for k, r in enumerate(mine) if r[0] > (mine[k - 1][0] if k else 0)]      # (what the cut leaves nothing of)
+                table["seg_first"][i] = len(rows)
+                table["seg_count"][i] = len(mine)
+                rows.extend(mine)
+            segtab = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
+            for name, col in zip(("end", "mul", "kind", "slope", "numsamples", "offset", "origin"), zip(*rows) if rows else [()] * 7):
+                segtab[name] = col
+        return bufs, table, segtab, weighed, turned, looped, shaped, panned, rated
 
     def __mix_events(self, batch: Sequence[tuple], envs: dict, extras: dict) -> None:
         """The events (first byte, other, bytes, factor, inrate, tostereo factors | None, loop | None) -- none of them this sample -- folded in
@@ -930,14 +1041,9 @@ class Sample:
         The table is packed column by column (whole-array numpy operations, not a row per event)."""
         if not batch:
             return
-        starts, others, nbytes, factors, inrates, pans, loops = zip(*batch)
         w = self.__samplewidth
-        rate = self.__samplerate
-        starts = np.array(starts, dtype=np.uint64)
-        nbytes = np.array(nbytes, dtype=np.uint64)
-        inrates = np.array(inrates, dtype=np.uint64)
         n1 = self.__nbytes
-        total = max(n1, int((starts + nbytes).max()))
+        total = max(n1, max(b[0] + b[2] for b in batch))    # first byte + bytes: the furthest end
         if total == 0:
             return
         if total == n1 and self._device().nbytes >= n1 and not self.__dev_shared:
@@ -948,75 +1054,9 @@ class Sample:
                 track.zero(n1, total - n1)
             if n1:
                 N.check(N.lib().sh_buf_copy(track.handle, 0, self._device().handle, 0, n1))
-        slot = {}                                           # id(other) -> (index into srcs, other): one dict lookup per event, no more
-        for o in others:
-            slot.setdefault(id(o), (len(slot), o))
-        uniq = [o for _k, o in slot.values()]
-        bufs = [o._device() for o in uniq]
+        bufs, table, segtab, weighed, turned, looped, shaped, panned, rated = self._pack_events(batch, envs, extras)
         srcs = (C.c_void_p * len(bufs))(*[b.handle for b in bufs])
-        src = np.fromiter((slot[id(o)][0] for o in others), dtype=np.uint32, count=len(others))
-        rated = bool((inrates != rate).any())
-        panned = any(p is not None for p in pans)
-        shaped = bool(envs)
-        turned = cut = False
-        weighed = {}                                        # index into batch -> (left_factor, right_factor) of the events with channels
-        if extras:
-            weighed = {i: x[2] for i, x in extras.items() if len(x) > 2}
-            extras = {i: x[:2] for i, x in extras.items()}
-            turned = any(rv for _rg, rv in extras.values())
-            cut = any(rg is not None for rg, _rv in extras.values())
-        flagged = turned or bool(weighed)                   # a row with a flag: the table has sh_mix_event_rev's layout, which is the looped one's and more
-        looped = flagged or loops.count(None) != len(loops)
-        table = np.zeros(len(batch), dtype=N.MIX_EVENT_CHAN_DTYPE if weighed else N.MIX_EVENT_REV_DTYPE if turned else N.MIX_EVENT_LOOP_DTYPE if looped else N.MIX_EVENT_ENV_DTYPE if shaped else N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
-        table["dst_sample"] = starts // w
-        table["nsamples"] = nbytes // w
-        table["factor"] = factors
-        table["src"] = src
-        if rated or panned or shaped or looped:
-            frames = np.array([o.__nbytes // (w * o.nchannels) for o in uniq], dtype=np.uint64)
-            table["src_frames"] = frames[src]
-            table["inrate"] = inrates
-            table["outrate"] = rate
-        if panned or shaped or looped:
-            table["src_channels"] = np.array([o.nchannels for o in uniq], dtype=np.uint32)[src]
-            lr = np.array([p if p is not None else (0.0, 0.0) for p in pans], dtype=np.float64)
-            table["left"] = lr[:, 0]
-            table["right"] = lr[:, 1]
-        if cut:                                             # a slice of other: where it starts, and the frames every count above was made over
-            nch = np.array([o.nchannels for o in uniq], dtype=np.uint64)[src]
-            at = np.array([i for i, (rg, _rv) in extras.items() if rg is not None], dtype=np.intp)
-            rg = np.array([rg for rg, _rv in extras.values() if rg is not None], dtype=np.uint64)
-            table["src_sample"][at] = rg[:, 0] * nch[at]
-            if rated or panned or shaped or looped:
-                table["src_frames"][at] = rg[:, 1]
-        if looped:
-            lp = np.array([l if l is not None else (0, 0, 0) for l in loops], dtype=np.uint64)
-            table["loop_start"] = lp[:, 0]
-            table["loop_frames"] = lp[:, 1]
-            if turned:                                      # a reversed looped row plays the region's LAST loop_end frames: its region starts there
-                rv = np.array([i for i, (_rg, v) in extras.items() if v], dtype=np.intp)
-                table["flags"][rv] = N.MIX_EVENT_REVERSED
-                back = rv[lp[rv, 1] != 0]
-                table["src_sample"][back] += (table["src_frames"][back] - lp[back, 0] - lp[back, 1]) * table["src_channels"][back]
-            for i, (lf, rf) in weighed.items():             # a stereo source weighed per channel: tomono into a mono track, a balance in a stereo one
-                table["flags"][i] |= N.MIX_EVENT_DOWNMIX if self.__nchannels == 1 else N.MIX_EVENT_BALANCE
-                table["left"][i] = lf
-                table["right"][i] = rf
-            table["src_frames"] = np.where(lp[:, 1] != 0, lp[:, 2], table["src_frames"])      # a looped row: the note's virtual frames
         if shaped or looped:
-            rows = []
-            for i, g in envs.items():
-                taken = int(nbytes[i]) // w // (2 if pans[i] is not None else 1)       # the event's source samples, after other_seconds' cut
-                if i in weighed and self.__nchannels == 1:
-                    taken *= 2                                                          # (a downmix: two stereo samples per track sample)
-                mine = [(min(r[0], taken),) + r[1:] for r in g]
-                mine = [r for k, r in enumerate(mine) if r[0] > (mine[k - 1][0] if k else 0)]      # (what the cut leaves nothing of)
-                table["seg_first"][i] = len(rows)
-                table["seg_count"][i] = len(mine)
-                rows.extend(mine)
-            segtab = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
-            for name, col in zip(("end", "mul", "kind", "slope", "numsamples", "offset", "origin"), zip(*rows) if rows else [()] * 7):
-                segtab[name] = col
             entry = N.lib().sh_mix_events_chan if weighed else N.lib().sh_mix_events_rev if turned else N.lib().sh_mix_events_loop if looped else N.lib().sh_mix_events_env
             N.check(entry(srcs, len(bufs), table.ctypes.data, len(table), segtab.ctypes.data, len(segtab), w,
                           self.__nchannels, track.handle, total // w))

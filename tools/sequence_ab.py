@@ -57,7 +57,18 @@ here (table packing, table copy and kernel), the kernels' own times under --trac
 same bytes (the copy is mono before ratecv and the envelope: half the samples to fetch, resample and shape): the ratio is the price of
 doing the downmix in the lane.  Then (c) the --reverse list without any ``channels`` (sh_mix_events_rev, kernels this entry point does
 not touch), five medians of 15 calls, for a run of this commit against a run of its parent.  --channels --trace: per variant (a)'s one
-call five times, then (b)'s converted copies five times, then (c)'s list five times, and nothing else, for rocprofv3 --kernel-trace."""
+call five times, then (b)'s converted copies five times, then (c)'s list five times, and nothing else, for rocprofv3 --kernel-trace.
+
+--plan: the songs of --channels (both variants) and of --env, 4096 / 32 768 notes, compiled once (mixer.compile_sequence) and rendered
+from the resident plan.  Per song: the one call it stands beside -- mixer.sequence (a new track) and mix_at_many in place, wall ms and the
+time between two events on the stream -- then the compile time, CompiledSequence.render() (a new Sample) and render_into (in place) of the
+whole song, wall and between two events on the stream (one launch and nothing else: the kernel), and the song streamed in windows of 4096
+frames (85.3 ms at 48 kHz), a device sync per window: ms per window aligned, the same windows three frames on into a buffer one sample off,
+and the share of the 85.3 ms a window takes.  The rendered bytes are held against mixer.sequence's first.  On a tree without
+compile_sequence only the first part runs -- that is the yardstick: the parent commit's tool has no --plan, so THIS file is run with
+the parent's package on the path, SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequence_ab.py --plan, on the
+same box in the same session, twice (the spread of the two runs is the noise).  --plan --trace: per song
+mix_at_many in place five times, then the whole-song render_into five times, and nothing else, for rocprofv3 --kernel-trace --stats."""
 import audioop
 import os
 import sys
@@ -66,7 +77,8 @@ from pathlib import Path
 
 import numpy as np
 
-sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+# --plan's yardstick is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
+sys.path.insert(0, ("--plan" in sys.argv[1:] and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
 from synthesizer_amd import _native as N  # noqa: E402
 from synthesizer_amd import mixer  # noqa: E402
 from synthesizer_amd.sample import Sample  # noqa: E402
@@ -783,6 +795,82 @@ def chan_main():
               "five medians of 15: %s ms" % (nevents, " ".join("%.4f" % m for m in meds)), flush=True)
 
 
+def plan_main():
+    N.ensure_init(0)
+    has = hasattr(mixer, "compile_sequence")
+    trace = "--trace" in sys.argv[1:]
+    info = N.device_info()
+    print("sequence_plan_ab: SYNTHHIP_SEQ_ALIGN=%s  %s  compile_sequence: %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"],
+                                                                               "yes" if has else "no (the yardstick)"), flush=True)
+    win = 4096
+    for nevents in (4096, 32768):
+        songs = []
+        _base, sources, events = rev_song(nevents, 120.0)
+        samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in sources]
+        rev_evs = [(s, samples[i], v, None, sp, None, e, lp, rg, rv) for s, i, v, sp, e, lp, rg, rv in events]
+        for what, nch, every in (("chan, downmix on every note, mono track", 1, 1), ("chan, balance on every other note, stereo track", 2, 2)):
+            songs.append((what, nch, [ev + (CHANNELS[k % 4] if k % every == 0 else None,) for k, ev in enumerate(rev_evs)]))
+        _base, inst, shaped = env_song(nevents, 120.0)
+        env_samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in inst]
+        songs.append(("env, stereo track", NCH, [(s, env_samples[i], v, None, sp, None, e) for s, i, v, sp, e in shaped]))
+        for what, nch, evs in songs:
+            whole = mixer.sequence(evs, RATE, nch, WIDTH)
+            frames, fb = len(whole), nch * WIDTH
+            track = Sample.from_raw_frames(bytes(frames * fb), WIDTH, RATE, nch).to_device()
+            cs = mixer.compile_sequence(evs, RATE, nch, WIDTH) if has else None
+            out = N.DeviceBuffer(frames * fb + 16) if has else None
+            if trace:
+                for _ in range(5):
+                    track.mix_at_many(evs)
+                N.sync()
+                for _ in range(5 if has else 0):
+                    cs.render_into(out, 0, 0, frames)
+                N.sync()
+                print("plan song 120 s, %5d events, %s   traced: mix_at_many in place x 5%s" % (nevents, what, ", render_into of the whole song x 5" if has else ""), flush=True)
+                continue
+            seq_ms = median_wall(lambda: mixer.sequence(evs, RATE, nch, WIDTH), 2, 7)
+            many_ms = median_wall(lambda: track.mix_at_many(evs), 2, 7)
+            many_dev = device_ms(track, evs, warm=1, runs=7)
+            print("plan song 120 s, %5d events, %s, %d frames   mixer.sequence %9.3f ms   mix_at_many in place %9.3f ms, between two events on "
+                  "the stream %9.4f ms" % (nevents, what, frames, seq_ms, many_ms, many_dev), flush=True)
+            if not has:
+                continue
+            want = bytes(whole.view_frame_data())
+            parity = bytes(cs.render().view_frame_data()) == want
+            compile_ms = median_wall(lambda: mixer.compile_sequence(evs, RATE, nch, WIDTH).close(), 1, 3)
+            render_ms = median_wall(lambda: cs.render(), 3, 15)
+            into_ms = median_wall(lambda: cs.render_into(out, 0, 0, frames), 3, 15)
+            devs = []
+            for _ in range(5):                              # five medians of 15: their spread is the noise
+                runs = []
+                for _ in range(15):
+                    N.sync()
+                    N.timer_start()
+                    cs.render_into(out, 0, 0, frames)
+                    runs.append(N.timer_stop())
+                devs.append(sorted(runs)[7])
+            nwin = (frames - 3) // win
+
+            def stream(shift, at):
+                for k in range(nwin):
+                    cs.render_into(out, at, k * win + shift, win)
+                    N.sync()
+
+            got = b"".join(bytes(c.view_frame_data()) for c in cs.chunks(win))
+            parity = parity and got == want
+            aligned_ms = median_wall(lambda: stream(0, 0), 1, 5) / nwin
+            off_ms = median_wall(lambda: stream(3, WIDTH), 1, 5) / nwin
+            i = cs.info()
+            print("plan song 120 s, %5d events, %s   level %s, %d tiles (%d active), %d pairs, %.2f MB resident   compile %9.3f ms   render() %8.4f ms "
+                  "(mixer.sequence / render() %.0fx)   render_into %8.4f ms (mix_at_many / render_into %.0fx)   between two events on the stream, five "
+                  "medians of 15: %s ms   windows of %d frames, %d of them: aligned %.4f ms each (%.3f %% of the 85.3 ms), three frames on into a buffer "
+                  "one sample off %.4f ms (%.2fx)   parity whole, chunks: %s"
+                  % (nevents, what, cs.level, i["ntiles"], i["active_tiles"], i["pairs"], i["device_bytes"] / 1e6, compile_ms, render_ms, seq_ms / render_ms,
+                     into_ms, many_ms / into_ms, " ".join("%.4f" % d for d in devs), win, nwin, aligned_ms, 100 * aligned_ms / (win / RATE * 1e3), off_ms,
+                     off_ms / aligned_ms, "ok" if parity else "FAILED"), flush=True)
+            cs.close()
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -853,4 +941,4 @@ def main():
 
 
 if __name__ == "__main__":
-    chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
