@@ -719,6 +719,30 @@ int sh_seq_render(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_bu
 int sh_seq_get_info(const sh_seq* seq, sh_seq_info* out);
 int sh_seq_destroy(sh_seq* seq);
 
+/* A song made of TRACKS, each with a gain given when it is RENDERED: mute, solo and faders without compiling again.  The bytes are those
+ * of this chain, which is NOT the flat list -- a track saturates on its own before its gain applies, and the master at every track:
+ *     master = silence; for t in tracks, in order:
+ *         sub = the track's events folded from silence, in list order, saturating at every event (what sh_seq_create's song holds)
+ *         if gains[t] != 1.0: sub = audioop.mul(sub, gains[t])        (clamp, then floor)
+ *         master = audioop.add(master, sub)                            (saturating; a shorter track is padded with silence)
+ * A gain of exactly 1.0 takes no multiply and one of exactly 0.0 skips the track's events (neither changes a byte).
+ * sh_seq_create_tracks takes sh_seq_create's arguments and, behind the events, track_first: ntracks + 1 offsets into `events`, track t
+ * holding rows [track_first[t], track_first[t + 1]) -- the tracks' lists one behind the other; a track may be empty.  It refuses what
+ * sh_seq_create refuses, in its words and its order, and: ntracks == 0, ntracks > SH_SEQ_MAX_TRACKS, a track_first that is NULL, does
+ * not start at 0, does not end at nevents or decreases.  The handle is sh_seq_create's (sh_seq_get_info, sh_seq_destroy), with a table
+ * of per-tile runs -- one per track with events in the tile -- behind its index.
+ * sh_seq_render_gains is sh_seq_render with ngains == the handle's track count gains, passed to the kernel BY VALUE in its arguments:
+ * one launch, nothing uploaded, copied or materialised.  SH_ERR_INVALID, nothing launched: what sh_seq_render refuses, a handle without
+ * tracks, another ngains than the handle has tracks, a gain that is not finite.  sh_seq_render of a handle with tracks renders with every
+ * gain 1.0 -- the chain above, still grouped by track.  sh_seq_get_tracks: the track count (0: a handle of sh_seq_create) and the runs. */
+#define SH_SEQ_MAX_TRACKS 32u
+int sh_seq_create_tracks(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_chan* events, uint32_t nevents,
+                         const uint32_t* track_first, uint32_t ntracks, const sh_env_segment* segments, uint32_t nsegments, int width,
+                         int nchannels, size_t track_samples, sh_seq** out);
+int sh_seq_render_gains(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                        uint32_t ngains);
+int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

@@ -173,6 +173,10 @@ _SIGNATURES = {
     "sh_seq_render": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t]),
     "sh_seq_get_info": (C.c_int, [_P, C.POINTER(SeqInfo)]),
     "sh_seq_destroy": (C.c_int, [_P]),
+    "sh_seq_create_tracks": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int,
+                                       C.c_size_t, C.POINTER(_P)]),
+    "sh_seq_render_gains": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32]),
+    "sh_seq_get_tracks": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),
@@ -397,17 +401,24 @@ class RtLane:
 
 class Sequence:
     """RAII wrapper over sh_seq: a list of placed samples compiled once (records and per-tile index resident on the device), rendered
-    window by window.  ``sources`` are the DeviceBuffers the records point into: the handle keeps them alive."""
+    window by window.  ``sources`` are the DeviceBuffers the records point into: the handle keeps them alive.  ``track_first`` (one offset
+    into ``table`` per track and the table's length behind them): a song of tracks, sh_seq_create_tracks, rendered with a gain per track."""
 
-    def __init__(self, sources, table: np.ndarray, segments: Optional[np.ndarray], width: int, nchannels: int, track_samples: int) -> None:
+    def __init__(self, sources, table: np.ndarray, segments: Optional[np.ndarray], width: int, nchannels: int, track_samples: int,
+                 track_first=None) -> None:
         ensure_init()
         assert table.dtype == MIX_EVENT_CHAN_DTYPE and (segments is None or segments.dtype == ENV_SEGMENT_DTYPE)
         self._sources = list(sources)
         self._h = _P()
         srcs = (C.c_void_p * max(1, len(self._sources)))(*[b.handle for b in self._sources])
         nseg = 0 if segments is None else len(segments)
-        check(lib().sh_seq_create(srcs, len(self._sources), _ptr(table), len(table), _ptr(segments), nseg, width, nchannels,
-                                  track_samples, C.byref(self._h)))
+        if track_first is None:
+            check(lib().sh_seq_create(srcs, len(self._sources), _ptr(table), len(table), _ptr(segments), nseg, width, nchannels,
+                                      track_samples, C.byref(self._h)))
+        else:
+            first = (C.c_uint32 * len(track_first))(*track_first)
+            check(lib().sh_seq_create_tracks(srcs, len(self._sources), _ptr(table), len(table), first, len(track_first) - 1, _ptr(segments), nseg,
+                                             width, nchannels, track_samples, C.byref(self._h)))
 
     @property
     def handle(self):
@@ -418,8 +429,18 @@ class Sequence:
         check(lib().sh_seq_get_info(self._h, C.byref(i)))
         return {name: getattr(i, name) for name, _ in SeqInfo._fields_}
 
-    def render(self, first_sample: int, nsamples: int, out: "DeviceBuffer", out_sample: int = 0) -> None:
-        check(lib().sh_seq_render(self._h, first_sample, nsamples, out.handle, out_sample))
+    def tracks(self) -> tuple:
+        """(tracks, runs): sh_seq_get_tracks; (0, 0) for a song without tracks"""
+        nt, nr = C.c_uint32(), C.c_uint32()
+        check(lib().sh_seq_get_tracks(self._h, C.byref(nt), C.byref(nr)))
+        return nt.value, nr.value
+
+    def render(self, first_sample: int, nsamples: int, out: "DeviceBuffer", out_sample: int = 0, gains=None) -> None:
+        if gains is None:
+            check(lib().sh_seq_render(self._h, first_sample, nsamples, out.handle, out_sample))
+        else:
+            g = (C.c_double * max(1, len(gains)))(*gains)
+            check(lib().sh_seq_render_gains(self._h, first_sample, nsamples, out.handle, out_sample, g, len(gains)))
 
     def free(self) -> None:
         if self._h:

@@ -117,4 +117,32 @@ inline TilePlan plan_by_tile(const Event* ev, uint32_t nev, uint64_t track_sampl
     return P;
 }
 
+// A kept song made of TRACKS (sh_seq_create_tracks): the events of the tracks are concatenated track-major, so track_of -- one track per
+// event -- does not decrease along the list, every tile's slice of plan_by_tile's idx (ascending event indices) is already in (track, list)
+// order, and idx stays as it is.  What a window kernel needs besides is where, inside a tile's slice, one track's events end and the next
+// one's begin: per tile its RUNS, one per track that has events there, in track order -- runs[rfirst[t] .. rfirst[t + 1]), run r covering
+// idx[(r == rfirst[t] ? first[t] : runs[r - 1].end) .. runs[r].end).  An idle tile has none; a tile's last run ends at first[t + 1].
+constexpr uint32_t MAX_TRACKS = 32;
+
+struct Run { uint32_t end, track; };                                       // end: exclusive, an offset into idx
+
+struct RunPlan {
+    std::vector<uint32_t> rfirst;         // ntiles + 1 offsets into runs
+    std::vector<Run> runs;
+};
+
+inline RunPlan plan_runs(const uint32_t* first, const uint32_t* idx, uint32_t ntiles, const uint32_t* track_of) {
+    RunPlan R;
+    R.rfirst.assign((size_t)ntiles + 1, 0);
+    for (uint32_t t = 0; t < ntiles; ++t) {
+        for (uint32_t e = first[t]; e < first[t + 1]; ++e) {
+            const uint32_t track = track_of[idx[e]];
+            if (e == first[t] || R.runs.back().track != track) R.runs.push_back(Run{e + 1, track});
+            else R.runs.back().end = e + 1;
+        }
+        R.rfirst[t + 1] = (uint32_t)R.runs.size();
+    }
+    return R;
+}
+
 }  // namespace shq

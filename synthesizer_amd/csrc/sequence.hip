@@ -788,16 +788,76 @@ __device__ __forceinline__ bool seq_window_lane(const uint32_t* __restrict__ ord
     return s0 < hi && s0 + SEQ_LANE<WIDTH> > lo;              // (no wrap: MAX_TRACK_SAMPLES)
 }
 
+// ---- a song made of tracks (sh_seq_create_tracks, sh_seq_render_gains): BUS = true ------------------------------------------------------
+// The reference chain is NOT the flat list: every track is folded on its own from silence (saturating at every event), scaled by a gain
+// given at RENDER time (audioop.mul: clamp, then floor; exactly 1.0: none; exactly 0.0: the track's events are not even read, since
+// fbound(x * 0.0) is 0 and adding 0 is the identity) and added, saturating, into the master in track order.  A bus lane keeps two
+// accumulators: acc, the master, and sub, the current track.  Its tile's slice of idx is cut into RUNS (shq::plan_runs): one per track
+// with events there, in track order, so the lane folds [e, run.end) into sub with the schedule of the kernel it mirrors and then sub into
+// acc -- which is seq_fold8 / seq_fold_w's own mul and add again, one level up.  The gains come BY VALUE in the kernel arguments, read at
+// a wave-uniform index by scalar loads from the kernel-argument segment (read in the ISA: no scratch): a render uploads nothing.
+struct SeqGains { double g[shq::MAX_TRACKS]; };
+struct SeqBus {
+    const uint32_t* rfirst;               // ntiles + 1 offsets into runs
+    const shq::Run* runs;
+    SeqGains        gains;
+};
+// The window templates take the bus as a trailing parameter PACK -- empty for BUS = false, whose kernels so keep the argument list, the
+// kernel-argument offsets and the instructions they had; one SeqBus for BUS = true.
+__device__ __forceinline__ const SeqBus& seq_bus(const SeqBus& b) { return b; }
+static_assert(sizeof(shq::Run) == 8 && sizeof(SeqGains) == 256, "a run is one 8-byte scalar load, the gains 256 bytes of kernel arguments");
+
 // PLAIN at 16 bits: k_seq_plain16's schedule, INFLIGHT records and source vectors in flight
-template <int SCHEME, int INFLIGHT>
+template <int SCHEME, int INFLIGHT, bool BUS = false, typename... Bus>
 __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_plain16(const SeqEv* __restrict__ ev, const she::Seg* __restrict__ segs,
                                                                    const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
-                                                                   const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, short* out, int aligned) {
+                                                                   const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, short* out, int aligned,
+                                                                   const Bus... bus_arg) {
+    static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
     uint32_t k, t0, s0;
     if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
     const bool whole = aligned && s0 >= lo && s0 + 8 <= hi;
     short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t e = first[k];
+    if constexpr (BUS) {
+        const SeqBus& bus = seq_bus(bus_arg...);
+        const uint32_t r1 = bus.rfirst[k + 1];
+        for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {       // (everything about a run is uniform)
+            const shq::Run run = bus.runs[r];
+            const double g = bus.gains.g[run.track];
+            const uint32_t e1 = run.end;
+            if (g == 0.0) { e = e1; continue; }
+            short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (e1 - e >= INFLIGHT) {
+                SeqEv c[INFLIGHT], nx[INFLIGHT];
+#pragma unroll
+                for (int u = 0; u < INFLIGHT; ++u) c[u] = ev[idx[e + u]];
+                for (; e + INFLIGHT <= e1; e += INFLIGHT) {
+                    const bool more = e + 2 * INFLIGHT <= e1;
+                    if (more) {
+#pragma unroll
+                        for (int u = 0; u < INFLIGHT; ++u) nx[u] = ev[idx[e + INFLIGHT + u]];
+                    }
+                    short8v x[INFLIGHT];
+#pragma unroll
+                    for (int u = 0; u < INFLIGHT; ++u) x[u] = seq_event8<PLAIN, SCHEME>(c[u], segs, t0, s0);
+#pragma unroll
+                    for (int u = 0; u < INFLIGHT; ++u) seq_fold8(sub, x[u], c[u].factor);
+                    if (more) {
+#pragma unroll
+                        for (int u = 0; u < INFLIGHT; ++u) c[u] = nx[u];
+                    }
+                }
+            }
+            for (; e < e1; ++e) {
+                const SeqEv c = ev[idx[e]];
+                seq_fold8(sub, seq_event8<PLAIN, SCHEME>(c, segs, t0, s0), c.factor);
+            }
+            seq_fold8(acc, sub, g);                           // the track into the master: its gain, then the saturating add
+        }
+        seq_window_store8(out, s0, lo, hi, whole, acc);
+        return;
+    }
     const uint32_t e1 = first[k + 1];
     if (e1 - e >= INFLIGHT) {
         SeqEv c[INFLIGHT], nx[INFLIGHT];
@@ -829,16 +889,47 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_plain16(const SeqEv* 
 
 // The other levels at 16 bits: k_seq_16's schedule, one record ahead, from LOOP on the next record's index.  An idle tile reads neither:
 // behind the last event idx holds nothing.
-template <int LEVEL, int SCHEME>
+template <int LEVEL, int SCHEME, bool BUS = false, typename... Bus>
 __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_16(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
                                                               const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
-                                                              const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, short* out, int aligned) {
+                                                              const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, short* out, int aligned,
+                                                              const Bus... bus_arg) {
+    static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
     typedef typename SeqRec<LEVEL>::type Rec;
     uint32_t k, t0, s0;
     if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
     const bool whole = aligned && s0 >= lo && s0 + 8 <= hi;
     short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t e = first[k];
+    if constexpr (BUS) {
+        const SeqBus& bus = seq_bus(bus_arg...);
+        const uint32_t r1 = bus.rfirst[k + 1];
+        for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {       // (uniform; a run lists at least one event)
+            const shq::Run run = bus.runs[r];
+            const double g = bus.gains.g[run.track];
+            const uint32_t e1 = run.end;
+            if (g == 0.0) { e = e1; continue; }
+            short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
+            if constexpr (LEVEL >= LOOP) {
+                uint32_t ni = idx[e];
+                while (e < e1) {
+                    const Rec c = ev[ni];
+                    if (++e < e1) ni = idx[e];
+                    seq_fold8(sub, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
+                }
+            } else {
+                Rec nx = ev[idx[e]];
+                while (e < e1) {
+                    const Rec c = nx;
+                    if (++e < e1) nx = ev[idx[e]];
+                    seq_fold8(sub, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
+                }
+            }
+            seq_fold8(acc, sub, g);
+        }
+        seq_window_store8(out, s0, lo, hi, whole, acc);
+        return;
+    }
     const uint32_t e1 = first[k + 1];
     if (e < e1) {                                             // (uniform)
         if constexpr (LEVEL >= LOOP) {
@@ -861,14 +952,51 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_16(const typename Seq
 }
 
 // Widths 1, 3 and 4: k_seq_w's loop from silence, every sample of the lane that lies in the window stored
-template <int LEVEL, int WIDTH>
+template <int LEVEL, int WIDTH, bool BUS = false, typename... Bus>
 __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_w(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
                                                              const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
-                                                             const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, unsigned char* out) {
+                                                             const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, unsigned char* out,
+                                                             const Bus... bus_arg) {
+    static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
     static_assert(LEVEL != ENV || WIDTH == 1 || WIDTH == 4, "an envelope has widths 1, 2 and 4");
     uint32_t k, t0, s0;
     if (!seq_window_lane<WIDTH>(order, lo, hi, k, t0, s0)) return;
     long long acc[4] = {0, 0, 0, 0};
+    if constexpr (BUS) {
+        constexpr long long HI = SEQ_HI<WIDTH>, LO = SEQ_LO<WIDTH>;
+        uint32_t e = first[k];
+        const SeqBus& bus = seq_bus(bus_arg...);
+        const uint32_t r1 = bus.rfirst[k + 1];
+        for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {       // (uniform)
+            const shq::Run run = bus.runs[r];
+            const double g = bus.gains.g[run.track];
+            if (g == 0.0) { e = run.end; continue; }
+            long long sub[4] = {0, 0, 0, 0};
+            for (; e < run.end; ++e) {
+                const typename SeqRec<LEVEL>::type c = ev[idx[e]];
+                if constexpr (LEVEL == PLAIN) {
+                    const unsigned char* src = (const unsigned char*)c.src;
+                    seq_fold_w<WIDTH>(sub, c.factor, s0, c.dst, c.n, [&](int, long long rel) { return chain_get<WIDTH>(src, (size_t)rel); });
+                } else {
+                    int v[4];
+                    seq_event<LEVEL, WIDTH, FUNNEL>(c, segs, t0, s0, v);
+                    seq_fold_w<WIDTH>(sub, c.factor, s0, c.dst, c.n, [&](int j, long long) { return (long long)v[j]; });
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                     // the track into the master: seq_fold_w's mul and add over the whole lane
+                long long x = sub[j];
+                if (g != 1.0) x = fbound((double)x * g, (double)LO, (double)HI);
+                const long long t = acc[j] + x;
+                acc[j] = t > HI ? HI : (t < LO ? LO : t);
+            }
+        }
+        unsigned char* p = out + (size_t)WIDTH * s0;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j)
+            if (s0 + j >= lo && s0 + j < hi) chain_put<WIDTH>(p, j, acc[j]);
+        return;
+    }
     const uint32_t e1 = first[k + 1];
     for (uint32_t e = first[k]; e < e1; ++e) {
         const typename SeqRec<LEVEL>::type c = ev[idx[e]];
@@ -1266,9 +1394,11 @@ int sh_mix_events_chan(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_ev
 // every row, the segments, and plan_by_tile's index, in one device block that the handle owns (the buffer pool's, as sh_buf_alloc's; not
 // the grow-only scratch, which the next call overwrites).  The records point into the sources: the caller keeps those alive.
 struct sh_seq {
-    void*    block = nullptr;             // records | segments | first | idx | order
+    void*    block = nullptr;             // records | segments | first | idx | order | runs | rfirst (the last two: a song of tracks)
     size_t   cap = 0, bytes = 0;
     size_t   at_segs = 0, at_first = 0, at_idx = 0, at_order = 0;     // order: the tiles heaviest first, for a render of the whole song
+    size_t   at_rfirst = 0, at_runs = 0;  // shq::plan_runs' table, behind order
+    uint32_t ntracks = 0, nruns = 0;      // ntracks == 0: sh_seq_create's flat list, no bus
     int      width = 0, nchannels = 0, level = 0;
     uint32_t nevents = 0, ntiles = 0, active_tiles = 0;
     uint64_t track_samples = 0, pairs = 0;
@@ -1289,7 +1419,7 @@ int seq_row_level(const SeqIn& m) {
 }
 
 template <int LEVEL>
-void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out) {
+void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out, const SeqGains* gains) {
     typedef typename SeqRec<LEVEL>::type Rec;
     const char* b = (const char*)q->block;
     const Rec* ev = (const Rec*)b;
@@ -1299,6 +1429,22 @@ void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, 
     // the whole song: heaviest tile first (measured: profiles/sequence_plan_ab.txt); any other window: its tiles in song order
     const uint32_t* order = lo == 0 && hi == q->track_samples ? (const uint32_t*)(b + q->at_order) : nullptr;
     const dim3 block(shq::TILE_THREADS);
+    if (q->ntracks) {                                         // a song of tracks: the same kernels with the bus, the gains by value
+        const SeqBus bus{(const uint32_t*)(b + q->at_rfirst), (const shq::Run*)(b + q->at_runs), *gains};
+        if (q->width == 2) {
+            const int aligned = ((uintptr_t)out & 15) == 0;
+            auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (short*)out, aligned, bus); };
+            const bool vec2 = sh::knobs().seq_align == VEC2;
+            if constexpr (LEVEL == PLAIN) vec2 ? go(k_win_plain16<VEC2, 4, true, SeqBus>) : go(k_win_plain16<FUNNEL, 4, true, SeqBus>);
+            else vec2 ? go(k_win_16<LEVEL, VEC2, true, SeqBus>) : go(k_win_16<LEVEL, FUNNEL, true, SeqBus>);
+        } else {
+            auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out, bus); };
+            if (q->width == 1) go(k_win_w<LEVEL, 1, true, SeqBus>);
+            else if (q->width == 4) go(k_win_w<LEVEL, 4, true, SeqBus>);
+            else if constexpr (LEVEL != ENV) go(k_win_w<LEVEL, 3, true, SeqBus>);
+        }
+        return;
+    }
     if (q->width == 2) {
         const int aligned = ((uintptr_t)out & 15) == 0;       // the BIASED base: song-anchored lanes start on multiples of eight samples
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (short*)out, aligned); };
@@ -1313,14 +1459,9 @@ void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, 
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int sh_seq_create(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_chan* events, uint32_t nevents,
-                  const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, size_t track_samples, sh_seq** out) {
-    SH_REQUIRE_INIT();
-    static const char fn[] = "sh_seq_create";
+// sh_seq_create (track_first NULL, ntracks 0) and sh_seq_create_tracks behind their names
+int seq_create(const char* fn, const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_chan* events, uint32_t nevents, const uint32_t* track_first,
+               uint32_t ntracks, bool tracks, const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, size_t track_samples, sh_seq** out) {
     // The refusals in front of the events, in the ORDER sh_mix_events_chan reports them (seq_check_args without its track, the width-3
     // refusal, then seq_mix's two), so that a call with two faults names the same one here and there.
     if (!out) return seq_null(fn);
@@ -1333,6 +1474,15 @@ int sh_seq_create(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_c
     }
     if (nchannels < 1) return sh::set_error(SH_ERR_INVALID, "%s: # of channels should be >= 1", fn);
     if (nsegments && !segments) return seq_null(fn);
+    if (tracks) {                                             // the tracks' events, concatenated: track t holds events [track_first[t], track_first[t + 1])
+        if (ntracks == 0) return sh::set_error(SH_ERR_INVALID, "%s: a song needs at least one track", fn);
+        if (ntracks > shq::MAX_TRACKS) return sh::set_error(SH_ERR_INVALID, "%s: %u tracks, at most %u", fn, ntracks, shq::MAX_TRACKS);
+        if (!track_first) return seq_null(fn);
+        if (track_first[0] != 0 || track_first[ntracks] != nevents)
+            return sh::set_error(SH_ERR_INVALID, "%s: track_first starts at 0 and ends at nevents", fn);
+        for (uint32_t t = 0; t < ntracks; ++t)
+            if (track_first[t] > track_first[t + 1]) return sh::set_error(SH_ERR_INVALID, "%s: track_first decreases at track %u", fn, t + 1);
+    }
     auto in = [=](uint32_t e) {
         const sh_mix_event_chan& m = events[e];
         SeqIn v{m.dst_sample, m.src_sample, m.nsamples, m.src_frames, m.factor, m.left, m.right, m.src, m.inrate, m.outrate, m.src_channels,
@@ -1367,6 +1517,18 @@ int sh_seq_create(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_c
     q->at_idx = q->at_first + P.first.size() * 4;
     q->at_order = q->at_idx + P.idx.size() * 4;
     q->bytes = q->at_order + (size_t)P.ntiles * 4;
+    shq::RunPlan R;
+    if (tracks) {                                             // the run table behind order, 8-byte aligned for its 8-byte rows
+        std::vector<uint32_t> track_of(nevents);
+        for (uint32_t t = 0; t < ntracks; ++t)
+            for (uint32_t e = track_first[t]; e < track_first[t + 1]; ++e) track_of[e] = t;
+        R = shq::plan_runs(P.first.data(), P.idx.data(), P.ntiles, track_of.data());
+        q->ntracks = ntracks;
+        q->nruns = (uint32_t)R.runs.size();
+        q->at_runs = (q->bytes + 7) & ~(size_t)7;
+        q->at_rfirst = q->at_runs + R.runs.size() * sizeof(shq::Run);
+        q->bytes = q->at_rfirst + R.rfirst.size() * 4;
+    }
     for (uint32_t v = 0; v < nsrc; ++v) {
         if (!srcs[v] || !srcs[v]->bytes) continue;
         q->src_lo.push_back((const char*)srcs[v]->ptr);
@@ -1396,6 +1558,10 @@ int sh_seq_create(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_c
                          [&](uint32_t a, uint32_t b) { return P.first[a + 1] - P.first[a] > P.first[b + 1] - P.first[b]; });
         memcpy(host.data() + q->at_order, order.data(), (size_t)P.ntiles * 4);
     }
+    if (tracks) {
+        if (!R.runs.empty()) memcpy(host.data() + q->at_runs, R.runs.data(), R.runs.size() * sizeof(shq::Run));
+        memcpy(host.data() + q->at_rfirst, R.rfirst.data(), R.rfirst.size() * 4);
+    }
     rc = sh::pool_alloc(q->bytes, &q->block, &q->cap);
     if (rc) {
         delete q;
@@ -1413,10 +1579,8 @@ int sh_seq_create(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_c
     return SH_OK;
 }
 
-int sh_seq_render(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample) {
-    SH_REQUIRE_INIT();
-    static const char fn[] = "sh_seq_render";
-    if (!seq || !out) return seq_null(fn);
+// sh_seq_render (gains NULL: every track at 1.0) and sh_seq_render_gains behind their names
+int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains) {
     const size_t w = (size_t)seq->width;
     if (first_sample > seq->track_samples || nsamples > seq->track_samples - first_sample)
         return sh::set_error(SH_ERR_INVALID, "%s: range outside the song", fn);
@@ -1433,16 +1597,70 @@ int sh_seq_render(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_bu
     void* biased = (void*)((uintptr_t)out->ptr + w * (uintptr_t)out_sample - w * (uintptr_t)first_sample);
     const dim3 grid = sh::grid1d(nt, 1);
     hipStream_t st = sh::state().stream;
+    SeqGains unity;
+    if (seq->ntracks && !gains) {
+        for (uint32_t t = 0; t < shq::MAX_TRACKS; ++t) unity.g[t] = 1.0;
+        gains = &unity;
+    }
     switch (seq->level) {
-    case PLAIN: seq_window_launch<PLAIN>(seq, grid, st, lo, hi, biased); break;
-    case RATE: seq_window_launch<RATE>(seq, grid, st, lo, hi, biased); break;
-    case PAN: seq_window_launch<PAN>(seq, grid, st, lo, hi, biased); break;
-    case ENV: seq_window_launch<ENV>(seq, grid, st, lo, hi, biased); break;
-    case LOOP: seq_window_launch<LOOP>(seq, grid, st, lo, hi, biased); break;
-    case REV: seq_window_launch<REV>(seq, grid, st, lo, hi, biased); break;
-    default: seq_window_launch<CHAN>(seq, grid, st, lo, hi, biased); break;
+    case PLAIN: seq_window_launch<PLAIN>(seq, grid, st, lo, hi, biased, gains); break;
+    case RATE: seq_window_launch<RATE>(seq, grid, st, lo, hi, biased, gains); break;
+    case PAN: seq_window_launch<PAN>(seq, grid, st, lo, hi, biased, gains); break;
+    case ENV: seq_window_launch<ENV>(seq, grid, st, lo, hi, biased, gains); break;
+    case LOOP: seq_window_launch<LOOP>(seq, grid, st, lo, hi, biased, gains); break;
+    case REV: seq_window_launch<REV>(seq, grid, st, lo, hi, biased, gains); break;
+    default: seq_window_launch<CHAN>(seq, grid, st, lo, hi, biased, gains); break;
     }
     SH_CHECK_LAUNCH(fn);
+    return SH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sh_seq_create(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_chan* events, uint32_t nevents,
+                  const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, size_t track_samples, sh_seq** out) {
+    SH_REQUIRE_INIT();
+    return seq_create("sh_seq_create", srcs, nsrc, events, nevents, nullptr, 0, false, segments, nsegments, width, nchannels, track_samples, out);
+}
+
+int sh_seq_create_tracks(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_event_chan* events, uint32_t nevents, const uint32_t* track_first,
+                         uint32_t ntracks, const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, size_t track_samples,
+                         sh_seq** out) {
+    SH_REQUIRE_INIT();
+    return seq_create("sh_seq_create_tracks", srcs, nsrc, events, nevents, track_first, ntracks, true, segments, nsegments, width, nchannels,
+                      track_samples, out);
+}
+
+int sh_seq_render(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_seq_render";
+    if (!seq || !out) return seq_null(fn);
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, nullptr);
+}
+
+int sh_seq_render_gains(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                        uint32_t ngains) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_seq_render_gains";
+    if (!seq || !out || !gains) return seq_null(fn);
+    if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
+    if (ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
+    SeqGains g;
+    for (uint32_t t = 0; t < shq::MAX_TRACKS; ++t) g.g[t] = 1.0;
+    for (uint32_t t = 0; t < ngains; ++t) {
+        if (!isfinite(gains[t])) return sh::set_error(SH_ERR_INVALID, "%s: gain %u is not finite", fn, t);
+        g.g[t] = gains[t];
+    }
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g);
+}
+
+int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns) {
+    SH_API_LOCK();
+    if (!seq || !ntracks || !nruns) return seq_null("sh_seq_get_tracks");
+    *ntracks = seq->ntracks;
+    *nruns = seq->nruns;
     return SH_OK;
 }
 

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import ctypes as C
 import gc
+import math
 import threading
 from typing import Callable, Dict, Generator, List, Optional, Sequence, Tuple, Union
 
@@ -30,7 +31,7 @@ from . import params
 from .oscillators import Oscillator, VoiceSpec, _pwm_widths, _table, pack_voices, time_step_weights
 from .sample import Sample
 
-__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "sequence", "compile_sequence", "CompiledSequence", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
+__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "sequence", "compile_sequence", "compile_tracks", "CompiledSequence", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
 
 
 def pan_gains(pan: float) -> Tuple[float, float]:
@@ -595,19 +596,90 @@ class CompiledSequence:
     ``[a, b)`` holds, byte for byte, frames ``[a, b)`` of ``sequence(events, ...)``, in one launch that copies no table.  Made by
     ``compile_sequence``.  The song sounds as its samples did WHEN IT WAS COMPILED: they are taken with ``Sample._share_device()``
     (as ``RealTimeMixer.add_sample`` takes them), so a sample that is amplified or mixed into afterwards writes a buffer of its own, and
-    this object holds the buffers it reads.  ``close()`` (or the ``with`` block, or the last reference) frees the device tables."""
+    this object holds the buffers it reads.  ``close()`` (or the ``with`` block, or the last reference) frees the device tables.
+    A song of TRACKS (``compile_tracks``; ``ntracks`` is their number, None for ``compile_sequence``'s songs) is, byte for byte, ::
 
-    def __init__(self, events: Sequence[tuple], samplerate: int, nchannels: int, samplewidth: int = 2, name: str = "") -> None:
+        master = Sample(...)                                # empty, the song's format
+        for t, events in enumerate(tracks):
+            sub = sequence(events, ...)                     # list order, saturating at every event
+            if gains[t] != 1.0:
+                sub.amplify(gains[t])                       # audioop.mul: clamp, then floor
+            master.mix(sub)                                 # audioop.add, saturating; the shorter one padded with silence
+
+    -- which is NOT the flat list: a track saturates on its own before its gain applies, and the master at every track -- with
+    ``gains`` given when a window is RENDERED: ``render``, ``render_into`` and ``chunks`` take ``gains=`` (one finite float per
+    track; None: all 1.0) and ``stem`` renders one track alone.  Mute, solo and fader moves compile nothing, upload nothing and
+    materialise no track: still one launch per window."""
+
+    MAX_TRACKS = 32
+
+    def __init__(self, events: Optional[Sequence[tuple]], samplerate: int, nchannels: int, samplewidth: int = 2, name: str = "",
+                 tracks: Optional[Sequence[Sequence[tuple]]] = None) -> None:
         self._seq = None
         self.name = name
+        self.ntracks = None
         self.samplerate, self.nchannels, self.samplewidth = int(samplerate), int(nchannels), int(samplewidth)
         track = Sample(name=name, samplerate=samplerate, nchannels=nchannels, samplewidth=samplewidth)
-        bufs, table, segtab, nbytes = track._compile_events(events)        # every ValueError of mix_at_many, before the device is reached
         self._fb = self.samplewidth * self.nchannels
-        self.frames = nbytes // self._fb
-        self._nevents = len(table)
-        self._seq = N.Sequence(bufs, table, segtab, self.samplewidth, self.nchannels, nbytes // self.samplewidth)
+        if tracks is None:
+            bufs, table, segtab, nbytes = track._compile_events(events)    # every ValueError of mix_at_many, before the device is reached
+            self.frames = nbytes // self._fb
+            self._nevents = len(table)
+            self._seq = N.Sequence(bufs, table, segtab, self.samplewidth, self.nchannels, nbytes // self.samplewidth)
+        else:
+            bufs, table, segtab, nbytes, track_first = self._check_tracks(track, tracks)
+            self.frames = nbytes // self._fb
+            self._nevents = len(table)
+            self._seq = N.Sequence(bufs, table, segtab, self.samplewidth, self.nchannels, nbytes // self.samplewidth, track_first=track_first)
+            self.ntracks = len(track_first) - 1
         self.level = N.SEQ_LEVELS[self._seq.info()["level"]]
+
+    @classmethod
+    def _check_tracks(cls, track: Sample, tracks) -> tuple:
+        """compile_tracks' checks, all of them before the device is reached: the number of tracks, then every track's list through
+        mix_at_many's checks, an error naming the track and the event's index in its own list; then _compile_events' tables of the tracks'
+        events one track behind the other, and where each track starts among them."""
+        if isinstance(tracks, (str, bytes)) or not hasattr(tracks, "__len__"):
+            raise ValueError("compile_tracks: tracks is a sequence of event lists")
+        if len(tracks) == 0:
+            raise ValueError("compile_tracks: a song needs at least one track")
+        if len(tracks) > cls.MAX_TRACKS:
+            raise ValueError("compile_tracks: %d tracks, at most %d" % (len(tracks), cls.MAX_TRACKS))
+        track._check_gpu_width("mix_at")
+        todo, shaped, track_first = [], {}, [0]
+        for t, events in enumerate(tracks):
+            events = list(events)
+            try:
+                one, its = track._check_events(events)
+            except (ValueError, NotImplementedError) as first:
+                for k, ev in enumerate(events):             # which event: the checks take one event at a time
+                    try:
+                        track._check_events([ev])
+                    except (ValueError, NotImplementedError) as e:
+                        raise type(e)("compile_tracks: track %d, event %d: %s" % (t, k, e)) from None
+                raise type(first)("compile_tracks: track %d: %s" % (t, first)) from None
+            for k, v in its.items():
+                shaped[len(todo) + k] = v
+            todo.extend(one)
+            track_first.append(len(todo))
+        return track._compile_checked(todo, shaped) + (track_first,)
+
+    def _gains(self, gains) -> Optional[list]:
+        """``gains`` as render hands them on: None, or ``ntracks`` finite floats -- checked before anything is launched"""
+        if gains is None:
+            return None
+        if self.ntracks is None:
+            raise ValueError("CompiledSequence: gains need a song of tracks (compile_tracks); this one has none")
+        try:
+            out = [float(g) for g in gains]
+        except (TypeError, ValueError):
+            raise ValueError("CompiledSequence: gains is a sequence of numbers, one per track") from None
+        if len(out) != self.ntracks:
+            raise ValueError("CompiledSequence: %d gains for %d tracks" % (len(out), self.ntracks))
+        for t, g in enumerate(out):
+            if not math.isfinite(g):
+                raise ValueError("CompiledSequence: gain %d is not finite" % t)
+        return out
 
     @property
     def duration(self) -> float:
@@ -634,34 +706,52 @@ class CompiledSequence:
             raise ValueError("CompiledSequence: frames [%d, %d) outside the song's %d frames" % (start_frame, start_frame + nframes, self.frames))
         return start_frame, nframes
 
-    def render_into(self, buf: N.DeviceBuffer, byte_offset: int, start_frame: int, nframes: int) -> None:
+    def render_into(self, buf: N.DeviceBuffer, byte_offset: int, start_frame: int, nframes: int, gains: Optional[Sequence[float]] = None) -> None:
         """Frames ``[start_frame, start_frame + nframes)`` of the song into ``buf`` from ``byte_offset`` (a whole number of samples) on:
-        every byte of the range is written, whatever ``buf`` held."""
+        every byte of the range is written, whatever ``buf`` held.  ``gains``: one per track of a song of tracks."""
         seq = self._handle()
+        gains = self._gains(gains)
         start_frame, nframes = self._range(start_frame, nframes)
         if byte_offset < 0 or byte_offset % self.samplewidth:
             raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
         if nframes:
-            seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth)
+            if gains is None:
+                seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth)
+            else:
+                seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains)
 
-    def render(self, start_frame: int = 0, nframes: Optional[int] = None) -> Sample:
-        """A new ``Sample``: frames ``[start_frame, start_frame + nframes)`` of the song; ``nframes`` None: to the end."""
+    def render(self, start_frame: int = 0, nframes: Optional[int] = None, gains: Optional[Sequence[float]] = None) -> Sample:
+        """A new ``Sample``: frames ``[start_frame, start_frame + nframes)`` of the song; ``nframes`` None: to the end.  ``gains``: one
+        per track of a song of tracks (None: all 1.0)."""
         self._handle()
+        gains = self._gains(gains)
         start_frame, nframes = self._range(start_frame, nframes)
         out = Sample(name=self.name, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth)
         if nframes:
             buf = N.DeviceBuffer(nframes * self._fb)
-            self.render_into(buf, 0, start_frame, nframes)
+            self.render_into(buf, 0, start_frame, nframes, gains=gains)
             out._set_device(buf, nframes * self._fb)
         return out
 
-    def chunks(self, chunk_frames: int) -> Generator[Sample, None, None]:
-        """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter"""
+    def stem(self, track: int, start_frame: int = 0, nframes: Optional[int] = None) -> Sample:
+        """One track of a song of tracks alone, at gain 1.0, as long as the window: ``render`` with one-hot gains."""
+        self._handle()
+        if self.ntracks is None:
+            raise ValueError("CompiledSequence: stem needs a song of tracks (compile_tracks); this one has none")
+        track = int(track)
+        if track < 0 or track >= self.ntracks:
+            raise ValueError("CompiledSequence: track %d outside the song's %d tracks" % (track, self.ntracks))
+        return self.render(start_frame, nframes, gains=[1.0 if t == track else 0.0 for t in range(self.ntracks)])
+
+    def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None) -> Generator[Sample, None, None]:
+        """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter.  ``gains``: as ``render``'s."""
         chunk_frames = int(chunk_frames)
         if chunk_frames <= 0:
             raise ValueError("CompiledSequence: chunk_frames must be positive")
+        self._handle()
+        gains = self._gains(gains)
         for at in range(0, self.frames, chunk_frames):
-            yield self.render(at, min(chunk_frames, self.frames - at))
+            yield self.render(at, min(chunk_frames, self.frames - at), gains=gains)
 
     def close(self) -> None:
         if self._seq is not None:
@@ -687,6 +777,15 @@ def compile_sequence(events: Sequence[tuple], samplerate: int, nchannels: int, s
     and uploaded ONCE; ``CompiledSequence.render`` / ``render_into`` / ``chunks`` then give any window of the song in one launch.  An
     event whose sample is the track itself has no meaning here (there is no track yet)."""
     return CompiledSequence(events, samplerate, nchannels, samplewidth, name)
+
+
+def compile_tracks(tracks: Sequence[Sequence[tuple]], samplerate: int, nchannels: int, samplewidth: int = 2, name: str = "") -> CompiledSequence:
+    """A song made of tracks, compiled once: ``tracks`` is a sequence of event lists (1 to 32 of them, a list may be empty), each list
+    exactly what ``sequence`` takes and checked as ``sequence`` checks it, before anything reaches the device -- an error names the track
+    and the event's index in its own list.  The song is as long as its longest track.  Every track is folded on its own and the tracks are
+    mixed in order, each at a gain given when a window is rendered (``CompiledSequence``): ``render(gains=...)``, ``render_into``,
+    ``chunks`` and ``stem`` mute, solo and balance the tracks in the one launch a window takes, with nothing compiled again."""
+    return CompiledSequence(None, samplerate, nchannels, samplewidth, name, tracks=tracks)
 
 
 class _MixSource:

@@ -918,6 +918,11 @@ class Sample:
         then (the sources' device buffers, shared; the table in sh_mix_event_chan's layout; the segment table; the song's bytes)."""
         self._check_gpu_width("mix_at")
         todo, shaped = self._check_events(events)
+        return self._compile_checked(todo, shaped)
+
+    def _compile_checked(self, todo: list, shaped: dict) -> tuple:
+        """_compile_events behind its checks: _check_events' (todo, shaped) as tables (mixer.compile_tracks checks track by track and
+        hands the tracks' events on as one list, one row per event)."""
         batch, envs, extras = [], {}, {}
         for k, checked in enumerate(todo):
             self._batch_event(batch, envs, extras, shaped.get(k), checked)

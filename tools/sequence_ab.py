@@ -68,7 +68,15 @@ and the share of the 85.3 ms a window takes.  The rendered bytes are held agains
 compile_sequence only the first part runs -- that is the yardstick: the parent commit's tool has no --plan, so THIS file is run with
 the parent's package on the path, SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequence_ab.py --plan, on the
 same box in the same session, twice (the spread of the two runs is the noise).  --plan --trace: per song
-mix_at_many in place five times, then the whole-song render_into five times, and nothing else, for rocprofv3 --kernel-trace --stats."""
+mix_at_many in place five times, then the whole-song render_into five times, and nothing else, for rocprofv3 --kernel-trace --stats.
+
+--tracks: the songs of --plan, their notes dealt over 8 tracks (note k to track k % 8), with mixed gains.  Per song, the time between two
+events on the stream (five medians of 15) of a render of the whole song and the wall time per window of 4096 frames (a device sync per
+window; every 16th window of the song) for: (a) mixer.compile_tracks' handle, one launch with the gains in its arguments; (b) the way there
+was before -- one CompiledSequence per track, each rendered, amplified and mixed into a master: 8 renders, up to 8 amplifies, 8 mixes, 8
+tracks materialised per window -- held to (a)'s bytes first; (c) a flat compile_sequence of the same notes, the same work without the bus
+(other bytes: the flat list is another chain); (d) (a) with one track muted, and one stem.  On a tree without compile_tracks only (c)
+runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequence_ab.py --tracks is the parent's own figure for (c)."""
 import audioop
 import os
 import sys
@@ -78,7 +86,7 @@ from pathlib import Path
 import numpy as np
 
 # --plan's yardstick is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
-sys.path.insert(0, ("--plan" in sys.argv[1:] and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
+sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
 from synthesizer_amd import _native as N  # noqa: E402
 from synthesizer_amd import mixer  # noqa: E402
 from synthesizer_amd.sample import Sample  # noqa: E402
@@ -871,6 +879,107 @@ def plan_main():
             cs.close()
 
 
+TRACK_GAINS = (1.0, 0.5, 0.8, 1.7, -1.0, 0.25, 1.0, 0.999)
+
+
+def five_medians(fn, runs=15):
+    """the time between two events on the stream around fn, five medians of `runs`: their spread is the noise"""
+    out = []
+    for _ in range(5):
+        one = []
+        for _ in range(runs):
+            N.sync()
+            N.timer_start()
+            fn()
+            one.append(N.timer_stop())
+        out.append(sorted(one)[runs // 2])
+    return out
+
+
+def tracks_main():
+    N.ensure_init(0)
+    has = hasattr(mixer, "compile_tracks")
+    info = N.device_info()
+    print("sequence_tracks_ab: SYNTHHIP_SEQ_ALIGN=%s  %s  compile_tracks: %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"],
+                                                                                 "yes" if has else "no (the yardstick: (c) alone)"), flush=True)
+    win, ntracks = 4096, len(TRACK_GAINS)
+    fmt = lambda v: " ".join("%.4f" % x for x in v)        # noqa: E731
+    for nevents in (4096, 32768):
+        songs = []
+        _base, sources, events = rev_song(nevents, 120.0)
+        samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in sources]
+        rev_evs = [(s, samples[i], v, None, sp, None, e, lp, rg, rv) for s, i, v, sp, e, lp, rg, rv in events]
+        for what, nch, every in (("chan, downmix on every note, mono track", 1, 1), ("chan, balance on every other note, stereo track", 2, 2)):
+            songs.append((what, nch, [ev + (CHANNELS[k % 4] if k % every == 0 else None,) for k, ev in enumerate(rev_evs)]))
+        _base, inst, shaped = env_song(nevents, 120.0)
+        env_samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in inst]
+        songs.append(("env, stereo track", NCH, [(s, env_samples[i], v, None, sp, None, e) for s, i, v, sp, e in shaped]))
+        for what, nch, evs in songs:
+            fb = nch * WIDTH
+            flat = mixer.compile_sequence(evs, RATE, nch, WIDTH)
+            frames = flat.frames
+            out = N.DeviceBuffer(frames * fb + 16)
+            wins = list(range(0, (frames - 3) // win, 16))
+
+            def stream(render):
+                for k in wins:
+                    render(k * win, win)
+                    N.sync()
+
+            c_whole = five_medians(lambda: flat.render_into(out, 0, 0, frames))
+            c_win = median_wall(lambda: stream(lambda a, n: flat.render_into(out, 0, a, n)), 1, 5) / len(wins)
+            print("tracks song 120 s, %5d events, %s, %d frames   (c) flat compile_sequence: whole song, between two events on the stream, five "
+                  "medians of 15: %s ms   a window of %d frames: %.4f ms" % (nevents, what, frames, fmt(c_whole), win, c_win), flush=True)
+            if not has:
+                flat.close()
+                continue
+            dealt = [evs[t::ntracks] for t in range(ntracks)]
+            t0 = time.perf_counter()
+            bus = mixer.compile_tracks(dealt, RATE, nch, WIDTH)
+            compile_ms = (time.perf_counter() - t0) * 1e3
+            singles = [mixer.compile_sequence(t, RATE, nch, WIDTH) for t in dealt]
+            assert bus.frames == frames
+
+            def old_way(a, n):
+                master = Sample(samplerate=RATE, nchannels=nch, samplewidth=WIDTH)
+                for cs, g in zip(singles, TRACK_GAINS):
+                    m = min(n, max(0, cs.frames - a))
+                    if m <= 0:
+                        continue
+                    sub = cs.render(a, m)
+                    if g != 1.0:
+                        sub.amplify(g)
+                    master.mix(sub)
+                return master
+
+            got = bytes(bus.render(gains=TRACK_GAINS).view_frame_data())
+            want = bytes(old_way(0, frames).view_frame_data())
+            parity = got == want + bytes(len(got) - len(want))
+            mid = (frames // 2) // win * win
+            parity = parity and bytes(bus.render(mid + 3, win, gains=TRACK_GAINS).view_frame_data()) == got[(mid + 3) * fb:(mid + 3 + win) * fb]
+            a_whole = five_medians(lambda: bus.render_into(out, 0, 0, frames, gains=TRACK_GAINS))
+            a_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, gains=TRACK_GAINS)), 1, 5) / len(wins)
+            b_whole = five_medians(lambda: old_way(0, frames), runs=5)
+            b_wall = median_wall(lambda: old_way(0, frames), 1, 5)
+            b_win = median_wall(lambda: stream(old_way), 1, 5) / len(wins)
+            muted = tuple(0.0 if t == 3 else g for t, g in enumerate(TRACK_GAINS))
+            one_hot = tuple(1.0 if t == 0 else 0.0 for t in range(ntracks))
+            d_muted = five_medians(lambda: bus.render_into(out, 0, 0, frames, gains=muted))
+            d_stem = five_medians(lambda: bus.render_into(out, 0, 0, frames, gains=one_hot))
+            unity = five_medians(lambda: bus.render_into(out, 0, 0, frames))
+            i, nruns = bus.info(), bus._seq.tracks()[1]
+            med = lambda v: sorted(v)[len(v) // 2]         # noqa: E731
+            print("tracks song 120 s, %5d events, %s   %d tracks, level %s, %d tiles, %d pairs, %d runs, %.2f MB resident, compile %.1f ms   "
+                  "(a) one launch, mixed gains: whole song %s ms   a window %.4f ms   (b) %d handles rendered, amplified, mixed: whole song, between two "
+                  "events on the stream, five medians of 5: %s ms (wall %.3f ms)   a window %.4f ms   (d) track 3 muted: %s ms   a stem: %s ms   every "
+                  "gain 1.0: %s ms   (a) / (b) whole %.3f, window %.3f   (a) / (c) whole %.3f, window %.3f   parity (a) against (b), whole and window: %s"
+                  % (nevents, what, ntracks, bus.level, i["ntiles"], i["pairs"], nruns, i["device_bytes"] / 1e6, compile_ms, fmt(a_whole), a_win, ntracks,
+                     fmt(b_whole), b_wall, b_win, fmt(d_muted), fmt(d_stem), fmt(unity), med(a_whole) / med(b_whole), a_win / b_win,
+                     med(a_whole) / med(c_whole), a_win / c_win, "ok" if parity else "FAILED"), flush=True)
+            for cs in singles + [bus, flat]:
+                cs.close()
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -941,4 +1050,4 @@ def main():
 
 
 if __name__ == "__main__":
-    plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
