@@ -417,7 +417,14 @@ int sh_chain_parts_apply(const sh_buf* parts, uint32_t nparts, size_t part_strid
                          sh_buf* out_i16);
 
 /* ---- mixer sum bus over materialised voices ------------------------------------------ */
-/* float32: bus[i] = sum_v gains[v] * voices[v*stride+i]; gains = device buffer of nvoices x (l, r) floats */
+/* float32: bus[i] = sum_v gains[v] * voices[v*stride+i]; gains = device buffer of nvoices x (l, r) floats; one fmaf per term,
+ * the order of the sum is the launch plan's (csrc/mixbus_plan.hpp).  Reads (nvoices - 1) * stride + nframes floats of `voices` (the
+ * floats between frame nframes of a row and the next row are never read), writes the first nframes * 8 bytes of bus_f32 and nothing
+ * else.  Pointers (buffers and sh_buf_view windows alike): voices and bus_f32 need their natural alignment only (4 and 8 bytes) -- a
+ * call with both on the 16-byte grid and stride % 4 == 0 takes the vector kernels, any other call gives the same sums without a
+ * 16-byte access; gains_lr must be 8-byte aligned (read as float2).  SH_ERR_INVALID, before any launch: a NULL argument,
+ * nvoices == 0, stride < nframes, voices shorter than the floats read, bus_f32 shorter than nframes * 8 bytes, gains_lr shorter than
+ * nvoices * 8 bytes or off the 8-byte grid.  nframes == 0: SH_OK, nothing written. */
 int sh_mix_bus_f32(const sh_buf* voices, uint32_t nvoices, size_t stride, uint32_t nframes,
                    const sh_buf* gains_lr, sh_buf* bus_f32);
 /* integer: the reference mixer's fold, mixed = add(add(c0, c1), c2) ... in voice order,
@@ -865,7 +872,7 @@ int sh_dist_wait_slot_keep(int slot);
  * librccl has it, else grouped ncclSend / ncclRecv); gathered is only read on root.  Without a communicator, or in a world of
  * one: a copy. */
 int sh_dist_gather_parts(const sh_buf* parts, size_t nvalues, int root, sh_buf* gathered);
-/* float64 bus -> float32 bus after the reduce */
+/* float64 bus -> float32 bus after the reduce: IEEE round to nearest, ties to even (overflow to +-inf, gradual underflow) */
 int sh_bus_finalize(const sh_buf* bus_f64, size_t nvalues, sh_buf* bus_f32);
 
 #ifdef __cplusplus

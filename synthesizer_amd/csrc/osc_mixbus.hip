@@ -1,5 +1,6 @@
 // osc_mixbus.hip -- the mixer sum bus over materialised float32 voices (HBM-bound: 4N+8 bytes per frame).
 #include "osc_host.hpp"
+#include "mixbus_plan.hpp"
 
 namespace {
 
@@ -7,6 +8,7 @@ namespace {
 // block = W waves; a wave owns 256 consecutive frames (float4 per lane) and a strided subset of
 // the voice rows of its group; partial (L,R) x4 per lane are summed across the block's waves in
 // LDS.  grid = (frame tiles, voice groups); groups > 1 write partial buses that k_bus_sum folds.
+// vec: the host (shm::plan) found the rows' base and the destination on the 16-byte grid; without it no 16-byte access is issued.
 template <bool NT>
 __device__ __forceinline__ float4 ldf4(const float* p) {
     typedef float f4v __attribute__((ext_vector_type(4)));
@@ -19,7 +21,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mix_bus_f32(const float* __restr
                                                             size_t stride, uint32_t nframes,
                                                             const float2* __restrict__ gains,
                                                             uint32_t voices_per_group,
-                                                            float2* __restrict__ out, size_t out_group_stride) {
+                                                            float2* __restrict__ out, size_t out_group_stride, uint32_t vec) {
     __shared__ float red[WAVES][8][64];
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -29,7 +31,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mix_bus_f32(const float* __restr
     uint32_t v_end = v_begin + voices_per_group;
     if (v_end > nvoices) v_end = nvoices;
     float l0 = 0, l1 = 0, l2 = 0, l3 = 0, r0 = 0, r1 = 0, r2 = 0, r3 = 0;
-    const bool full = (f0 + 3 < nframes) && ((stride & 3) == 0);
+    const bool full = (f0 + 3 < nframes) && ((stride & 3) == 0) && vec;
     if (full) {
         uint32_t v = v_begin + wave;
 #define SH_ACC(X_, G_)                                                     \
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mix_bus_f32(const float* __restr
             acc[j] = s;
         }
         float2* o = out + (size_t)g * out_group_stride + f0;
-        if (f0 + 3 < nframes) {
+        if (f0 + 3 < nframes && vec) {
             // 4 frames x (L,R) = 32 contiguous bytes
             reinterpret_cast<float4*>(o)[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
             reinterpret_cast<float4*>(o)[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
@@ -182,47 +184,41 @@ int sh_mix_bus_f32(const sh_buf* voices, uint32_t nvoices, size_t stride, uint32
     if (stride < nframes || voices->bytes / 4 < (size_t)(nvoices - 1) * stride + nframes)
         return sh::set_error(SH_ERR_INVALID, "sh_mix_bus_f32: voice buffer too small for %u x %u (stride %zu)", nvoices, nframes, stride);
     if (bus_f32->bytes < (size_t)nframes * 8) return sh::set_error(SH_ERR_INVALID, "sh_mix_bus_f32: bus too small");
-    constexpr uint32_t MIX_MAX_FRAMES = 1u << 24;            // per launch: tiles x 512 threads must stay below 2^32 work-items
-    if (nframes > MIX_MAX_FRAMES) {
-        for (uint64_t off = 0; off < nframes; off += MIX_MAX_FRAMES) {
-            const uint32_t n = nframes - off < MIX_MAX_FRAMES ? (uint32_t)(nframes - off) : MIX_MAX_FRAMES;
-            sh_buf v{(char*)voices->ptr + off * 4, voices->bytes - off * 4, false, 0};
-            sh_buf o{(char*)bus_f32->ptr + off * 8, bus_f32->bytes - off * 8, false, 0};
-            const int rc = sh_mix_bus_f32(&v, nvoices, stride, n, gains_lr, &o);
+    if (gains_lr->bytes < (size_t)nvoices * 8) return sh::set_error(SH_ERR_INVALID, "sh_mix_bus_f32: gains buffer too small");
+    if ((uintptr_t)gains_lr->ptr & 7) return sh::set_error(SH_ERR_INVALID, "sh_mix_bus_f32: gains not 8-byte aligned");      // (read as float2)
+    if (nframes > shm::MAX_FRAMES) {
+        for (uint32_t c = 0; c < shm::chunks(nframes); ++c) {
+            const shm::Chunk k = shm::chunk(nframes, c);
+            sh_buf v{(char*)voices->ptr + k.off * 4, voices->bytes - k.off * 4, false, 0};
+            sh_buf o{(char*)bus_f32->ptr + k.off * 8, bus_f32->bytes - k.off * 8, false, 0};
+            const int rc = sh_mix_bus_f32(&v, nvoices, stride, k.n, gains_lr, &o);
             if (rc) return rc;
         }
         return SH_OK;
     }
-    constexpr int W = 8;
-    const uint32_t tiles = sh::div_up(nframes, 256);
-    // enough workgroups to cover 256 CUs several times over: split the voices into groups when the
-    // frame range alone gives too few tiles
-    uint32_t groups = 1;
-    while (tiles * groups < 1024 && nvoices / (groups * 2) >= 4 * W) groups *= 2;
-    const uint32_t vpg = (nvoices + groups - 1) / groups;
-    if (gains_lr->bytes < (size_t)nvoices * 8) return sh::set_error(SH_ERR_INVALID, "sh_mix_bus_f32: gains buffer too small");
-    size_t part_bytes = groups > 1 ? (size_t)groups * nframes * 8 : 0;
-    int rc = sh::ensure_scratch(part_bytes);
+    static_assert(shm::STREAM_BYTES == sh::STREAM_BYTES, "mixbus_plan.hpp restates common.hpp");
+    constexpr int W = shm::WAVES;
+    const shm::Plan p = shm::plan(nvoices, stride, nframes, (uintptr_t)voices->ptr, (uintptr_t)bus_f32->ptr);
+    int rc = sh::ensure_scratch(p.part_bytes);
     if (rc) return rc;
     hipStream_t st = sh::state().stream;
-    const bool stream = (size_t)nvoices * nframes * 4 > sh::STREAM_BYTES;              // rows beyond the Infinity Cache: streaming loads
-    if (tiles >= 1536 && (stride & 3) == 0 && ((uintptr_t)voices->ptr & 15) == 0 && ((uintptr_t)bus_f32->ptr & 15) == 0) {
-        if (stream) hipLaunchKernelGGL((k_mix_bus_direct<8, 4, true>), sh::grid1d(nframes, 256 * 8), dim3(8 * 64), 0, st,
-                                       (const float*)voices->ptr, nvoices, stride, nframes, (const float2*)gains_lr->ptr, (float2*)bus_f32->ptr);
+    if (p.direct) {
+        if (p.stream) hipLaunchKernelGGL((k_mix_bus_direct<8, 4, true>), sh::grid1d(nframes, 256 * 8), dim3(8 * 64), 0, st,
+                                         (const float*)voices->ptr, nvoices, stride, nframes, (const float2*)gains_lr->ptr, (float2*)bus_f32->ptr);
         else hipLaunchKernelGGL((k_mix_bus_direct<8, 4, false>), sh::grid1d(nframes, 256 * 8), dim3(8 * 64), 0, st,
                                 (const float*)voices->ptr, nvoices, stride, nframes, (const float2*)gains_lr->ptr, (float2*)bus_f32->ptr);
         SH_CHECK_LAUNCH("k_mix_bus_direct");
         return SH_OK;
     }
     float2* parts = (float2*)sh::state().scratch;
-    float2* dst = groups > 1 ? parts : (float2*)bus_f32->ptr;
-    hipLaunchKernelGGL((k_mix_bus_f32<W, false>), dim3(tiles, groups), dim3(W * 64), 0, st,       // (plain loads: streaming ones gain nothing here)
-                       (const float*)voices->ptr, nvoices, stride, nframes, (const float2*)gains_lr->ptr, vpg,
-                       dst, (size_t)nframes);
+    float2* dst = p.groups > 1 ? parts : (float2*)bus_f32->ptr;
+    hipLaunchKernelGGL((k_mix_bus_f32<W, false>), dim3(p.tiles, p.groups), dim3(W * 64), 0, st,       // (plain loads: streaming ones gain nothing here)
+                       (const float*)voices->ptr, nvoices, stride, nframes, (const float2*)gains_lr->ptr, p.voices_per_group,
+                       dst, p.part_stride, p.vec);
     SH_CHECK_LAUNCH("k_mix_bus_f32");
-    if (groups > 1) {
+    if (p.groups > 1) {
         hipLaunchKernelGGL(k_bus_sum, sh::grid1d(nframes, 256), dim3(256), 0, st,
-                           (const float2*)parts, groups, (size_t)nframes, nframes, (float2*)bus_f32->ptr);
+                           (const float2*)parts, p.groups, p.part_stride, nframes, (float2*)bus_f32->ptr);
         SH_CHECK_LAUNCH("k_bus_sum");
     }
     return SH_OK;

@@ -94,7 +94,9 @@ def test_mix_bus_kernel_shapes(gpu):
     """sh_mix_bus_f32 over materialised voices: ragged sizes, voice-group split, the direct kernel, gains."""
     from synthesizer_amd.mixer import mix_bus
     rng = np.random.default_rng(5)
-    # the last two sizes are long enough (>= 1536 tiles of 256 frames) for the direct, unsplit kernel; one of them ragged
+    # (9, 393216) is long enough (>= 1536 tiles of 256 frames) and has stride % 4 == 0: the direct, unsplit kernel.  (5, 500003) is
+    # as long but its stride is odd, so it runs k_mix_bus_f32 lane by lane; the direct kernel's ragged tail needs stride > nframes
+    # (tests/test_gpu_mixbus.py, where every route is asserted against the host plan)
     for nv, nf in ((1, 1), (3, 7), (8, 255), (33, 1000), (64, 4099), (1024, 3000), (257, 1024), (9, 393216), (5, 500003)):
         v = rng.uniform(-1, 1, (nv, nf)).astype(np.float32)
         g = rng.uniform(0, 1, (nv, 2)).astype(np.float32)

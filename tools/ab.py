@@ -7,6 +7,10 @@
     python tools/ab.py config CONFIG LIB [LIB ...]          bench.py --only-config CONFIG (config2 / config3 / staggered) under each library
     python tools/ab.py shapes [WFM[:groups] ...]            the headline under SYNTHHIP_VARIANT (and SYNTHHIP_GROUPS) settings of ONE library
     python tools/ab.py diff                                 how far the shape switches move a result: float64 bus of one block, headline and config 3
+    python tools/ab.py mix LIB [LIB ...]                    sh_mix_bus_f32 on the benchmark's mix row (1024 x 480 000: k_mix_bus_direct, streaming loads) and on the
+                                                           two-step render's (1024 x 48 000: k_mix_bus_f32 in 8 groups + k_bus_sum) under each library, the libraries
+                                                           by turns, four processes each: ms per call, median of 7 timings per process
+    python tools/ab.py mixcalls                             one call of each of those shapes and of a short direct one (for a kernel trace; SYNTHHIP_LIB picks the library)
 
 (Round 5: build_variant.py, variant_diff.py, variants.py and the ab_*.sh wrappers in one file.)"""
 import json
@@ -107,7 +111,51 @@ def diff(argv):
             print(name, k, "max |diff| %.3e" % np.max(np.abs(res[name][k] - res["default"][k])), "scale %.3f" % np.max(np.abs(res["default"][k])))
 
 
-COMMANDS = {"build": build, "time": time_libs, "config": config, "shapes": shapes, "diff": diff}
+_MIX_CHILD = r'''
+import sys, time; sys.path.insert(0, ".")
+import numpy as np
+from synthesizer_amd import _native as N
+N.ensure_init(0)
+L = N.lib()
+timed = sys.argv[1] == "time"
+for nv, nf in ((1024, 480000), (1024, 48000)) + (() if timed else ((9, 393216),)):
+    v = N.DeviceBuffer(nv * nf * 4); v.zero()
+    g = N.DeviceBuffer.from_array(np.random.default_rng(0).uniform(0, 1, nv * 2).astype(np.float32))
+    bus = N.DeviceBuffer(nf * 8)
+    call = lambda: N.check(L.sh_mix_bus_f32(v.handle, nv, nf, nf, g.handle, bus.handle))
+    call(); N.sync()
+    if timed:
+        reps = 20 if nf > 100000 else 200
+        ms = []
+        for _ in range(7):
+            t = time.perf_counter()
+            for _k in range(reps):
+                call()
+            N.sync()
+            ms.append((time.perf_counter() - t) / reps * 1e3)
+        print("%d x %d: %.4f ms (median of 7; min %.4f max %.4f)" % (nv, nf, sorted(ms)[3], min(ms), max(ms)), flush=True)
+    for b in (v, g, bus):
+        b.free()
+'''
+
+
+def mix(argv):
+    for rep in range(4):
+        for lib in argv:
+            p = subprocess.run([sys.executable, "-c", _MIX_CHILD, "time"], env=dict(os.environ, SYNTHHIP_ALLOW_STALE="1", SYNTHHIP_LIB=lib),
+                               capture_output=True, text=True, timeout=300)
+            if p.returncode:
+                sys.exit("failed under %s (%d): %s" % (lib, p.returncode, p.stderr[-300:]))
+            for line in p.stdout.splitlines():
+                print("%s process %d: %s" % (Path(lib).name, rep, line), flush=True)
+
+
+def mixcalls(argv):
+    sys.argv = ["mixcalls", "calls"]                       # in this process: a kernel trace follows it without following children
+    exec(_MIX_CHILD, {"__name__": "__mixcalls__"})
+
+
+COMMANDS = {"build": build, "time": time_libs, "config": config, "shapes": shapes, "diff": diff, "mix": mix, "mixcalls": mixcalls}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in COMMANDS:
