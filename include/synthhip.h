@@ -750,6 +750,29 @@ int sh_seq_render_gains(const sh_seq* seq, size_t first_sample, size_t nsamples,
                         uint32_t ngains);
 int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns);
 
+/* The desk's METERS: sh_seq_render_gains, and from the SAME launch one row of levels per track, post-fader, and one for the master --
+ * what Sample.level_db_peak / level_db_rms read off a finished sample, taken from the values the kernel holds anyway.  For the window
+ * [first_sample, first_sample + nsamples): row t < ntracks is over audioop.mul(sub_t, gains[t]) (none at exactly 1.0; sub_t as above,
+ * padded with silence) cut to the window, row ntracks over the window's output bytes.  Per channel -- song sample s is channel s & 1 of a
+ * stereo song and channel 0 of any other, whose second channel reads 0 -- a row holds peak = max |x| (audioop.max; |-2^31| is 2^31) and
+ * the exact integer sum of x * x as sq_hi * 2^32 + sq_lo: sq_lo = sum (x * x & 0xffffffff) and sq_hi = sum (x * x >> 32) at widths 3 and
+ * 4, one sum in sq_lo and sq_hi == 0 at widths 1 and 2.  Width 3 is metered on the raw 24-bit values, as sh_pcm_stats.  A muted track
+ * (gain exactly 0.0) and a track without events in the window have all-zero rows.  Integer max and add: the rows are the same on every
+ * run and for every alignment of the window.
+ * gains == NULL with ngains == 0: every gain 1.0.  nmeters must be the handle's track count + 1.  The call is SYNCHRONOUS, as sh_pcm_stats:
+ * the handle's row table zeroed on the stream, the one launch, one copy of the rows to `meters`, one stream synchronise.  The table
+ * belongs to the handle: a handle serves ONE metered render at a time (the library's lock sees to that for its own callers).
+ * SH_ERR_INVALID, nothing launched, `out` and `meters` untouched: what sh_seq_render_gains refuses, a handle without tracks (a flat
+ * song's only row is the peak of its output), meters == NULL, another nmeters.  nsamples == 0 zeroes the rows and returns SH_OK.
+ * NOT here: pre-fader meters (they would read a muted track's events), meters of a song without tracks, clip counters. */
+typedef struct sh_seq_meter {
+    uint32_t peak[2];
+    uint64_t sq_hi[2];
+    uint64_t sq_lo[2];
+} sh_seq_meter;                    /* 40 bytes */
+int sh_seq_render_meters(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                         uint32_t ngains, sh_seq_meter* meters, uint32_t nmeters);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

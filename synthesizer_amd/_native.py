@@ -93,6 +93,10 @@ class SeqInfo(C.Structure):                                                     
                 ("ntiles", C.c_uint32), ("active_tiles", C.c_uint32), ("level", C.c_uint32)]
 
 
+class SeqMeter(C.Structure):                                                         # sh_seq_meter
+    _fields_ = [("peak", C.c_uint32 * 2), ("sq_hi", C.c_uint64 * 2), ("sq_lo", C.c_uint64 * 2)]
+
+
 SEQ_LEVELS = ("plain", "rate", "pan", "env", "loop", "rev", "chan")                   # SH_SEQ_LEVEL_*
 
 
@@ -177,6 +181,7 @@ _SIGNATURES = {
                                        C.c_size_t, C.POINTER(_P)]),
     "sh_seq_render_gains": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32]),
     "sh_seq_get_tracks": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "sh_seq_render_meters": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(SeqMeter), C.c_uint32]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),
@@ -435,7 +440,15 @@ class Sequence:
         check(lib().sh_seq_get_tracks(self._h, C.byref(nt), C.byref(nr)))
         return nt.value, nr.value
 
-    def render(self, first_sample: int, nsamples: int, out: "DeviceBuffer", out_sample: int = 0, gains=None) -> None:
+    def render(self, first_sample: int, nsamples: int, out: "DeviceBuffer", out_sample: int = 0, gains=None, meters: bool = False):
+        """``meters=True`` (a song of tracks): sh_seq_render_meters -- the same bytes and, from the same launch, one row per track and one for
+        the master, each ``(peak, sum_squares)`` of per-channel pairs, the sums exact Python ints.  Otherwise None."""
+        if meters:
+            nt = self.tracks()[0]
+            rows = (SeqMeter * (nt + 1))()
+            g = None if gains is None else (C.c_double * max(1, len(gains)))(*gains)
+            check(lib().sh_seq_render_meters(self._h, first_sample, nsamples, out.handle, out_sample, g, 0 if gains is None else len(gains), rows, nt + 1))
+            return [((r.peak[0], r.peak[1]), ((r.sq_hi[0] << 32) + r.sq_lo[0], (r.sq_hi[1] << 32) + r.sq_lo[1])) for r in rows]
         if gains is None:
             check(lib().sh_seq_render(self._h, first_sample, nsamples, out.handle, out_sample))
         else:

@@ -45,12 +45,16 @@
 // window stored (zeros in a tile no event touches) through a pointer the host has biased by out_sample - first_sample, one 16-byte
 // vector per lane where the lane lies inside the window and the host found the biased base aligned.  sh_seq_render is that one launch and
 // copies nothing; a window of the song holds the bytes of that slice of the whole song, since every track sample is its own fold.
+// A song of TRACKS (sh_seq_create_tracks) is rendered by the BUS = true instantiations of the same three templates, a gain per track in
+// the kernel arguments (sh_seq_render_gains); with the metering bus, SeqBusM, the same launch also reduces one row of levels per track,
+// post-fader, and one for the master into a table the handle owns (sh_seq_render_meters; seqmeter.hpp).
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
 #include "ratecv.hpp"
 #include "seqenv.hpp"
 #include "seqloop.hpp"
+#include "seqmeter.hpp"
 #include "seqrev.hpp"
 #include "seqplan.hpp"
 #include <math.h>
@@ -807,6 +811,100 @@ struct SeqBus {
 __device__ __forceinline__ const SeqBus& seq_bus(const SeqBus& b) { return b; }
 static_assert(sizeof(shq::Run) == 8 && sizeof(SeqGains) == 256, "a run is one 8-byte scalar load, the gains 256 bytes of kernel arguments");
 
+// ---- level meters from the same launch (sh_seq_render_meters): a second bus type, SeqBusM ------------------------------------------------
+// A metered render stores the bytes of the render with gains and, from the values the lane holds anyway, one row of levels (seqmeter.hpp:
+// per channel the peak and the exact sum of squares) per track, post-fader -- over mul(sub, gain), formed just before it is added into
+// acc -- and one for the master, over acc at the store; only samples inside [lo, hi) count.  The reduction (the guide's: partials on chip,
+// one atomic per workgroup and value): the lane's partial row; a wave reduction by __shfl_xor; the wave's first lane into a row table in
+// LDS (33 rows, 1320 bytes) by LDS atomics -- integer max and add, so the order of arrival changes nothing; behind a barrier, lane
+// 2 row + channel of the workgroup adds what its tile found for (row, channel) to the handle's device table: one atomicMax and one or two
+// atomicAdd at agent scope, none where the peak is 0.  A barrier needs every lane, so the metering kernels do NOT leave with
+// seq_window_lane's lanes outside the window: only a workgroup beyond the window leaves (seq_window_tile, uniform); a WAVE without a lane
+// in the window skips the runs (uniform: the shuffles see whole waves), and inside a wave the lanes outside fold their samples like the
+// others, count none of them (seqmeter's cut) and store none (seq_window_store8's).  Their fetches are the ones lanes beside an event
+// make in any tile: nothing outside an event's samples is read.  A muted track's run is skipped as before: its row stays zero.
+struct SeqBusM : SeqBus {
+    shmt::Row* meters;                     // ntracks + 1 rows, zeroed on the stream in front of the launch; row ntracks: the master
+    uint32_t  ntracks, nch;               // nch: the song's channels (2: sample s is channel s & 1; otherwise all are channel 0)
+};
+__device__ __forceinline__ const SeqBusM& seq_bus(const SeqBusM& b) { return b; }
+template <typename... Bus> struct SeqMetered : std::false_type {};
+template <> struct SeqMetered<SeqBusM> : std::true_type {};
+
+// seq_window_lane without the lane: false for a whole workgroup alone
+template <int WIDTH>
+__device__ __forceinline__ bool seq_window_tile(const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, uint32_t& tile, uint32_t& t0, uint32_t& s0) {
+    uint64_t t = (uint64_t)(lo / SEQ_TILE<WIDTH>) + sh::block_id();
+    if (t * SEQ_TILE<WIDTH> >= hi) return false;              // (uniform)
+    if (order) t = order[t];                                  // (uniform)
+    tile = (uint32_t)t;
+    t0 = tile * SEQ_TILE<WIDTH>;
+    s0 = t0 + threadIdx.x * SEQ_LANE<WIDTH>;
+    return true;
+}
+
+// the workgroup's row table, zeroed: every lane of the workgroup calls it (a barrier)
+__device__ __forceinline__ shmt::Row* seq_meter_begin() {
+    __shared__ shmt::Row table[shq::MAX_TRACKS + 1];
+    uint32_t* w = reinterpret_cast<uint32_t*>(table);
+    for (uint32_t i = threadIdx.x; i < sizeof(table) / 4; i += shq::TILE_THREADS) w[i] = 0u;
+    __syncthreads();
+    return table;
+}
+
+// the lanes' partial rows of one WHOLE wave into row `slot` of the workgroup's table (every lane of the wave calls it; WIDE: widths 3, 4)
+template <bool WIDE>
+__device__ __forceinline__ void seq_meter_wave(shmt::Row r, const bool stereo, shmt::Row* slot) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        shmt::Row o = shmt::zero();
+        o.peak[0] = __shfl_xor(r.peak[0], m, 64);
+        o.sq_lo[0] = __shfl_xor((unsigned long long)r.sq_lo[0], m, 64);
+        if (WIDE) o.sq_hi[0] = __shfl_xor((unsigned long long)r.sq_hi[0], m, 64);
+        if (stereo) {                                         // (uniform)
+            o.peak[1] = __shfl_xor(r.peak[1], m, 64);
+            o.sq_lo[1] = __shfl_xor((unsigned long long)r.sq_lo[1], m, 64);
+            if (WIDE) o.sq_hi[1] = __shfl_xor((unsigned long long)r.sq_hi[1], m, 64);
+        }
+        shmt::fold(r, o);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        if (r.peak[0]) {                                      // (a peak of 0: every sample 0, both sums 0)
+            atomicMax(&slot->peak[0], r.peak[0]);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&slot->sq_lo[0]), (unsigned long long)r.sq_lo[0]);
+            if (WIDE) atomicAdd(reinterpret_cast<unsigned long long*>(&slot->sq_hi[0]), (unsigned long long)r.sq_hi[0]);
+        }
+        if (stereo && r.peak[1]) {
+            atomicMax(&slot->peak[1], r.peak[1]);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&slot->sq_lo[1]), (unsigned long long)r.sq_lo[1]);
+            if (WIDE) atomicAdd(reinterpret_cast<unsigned long long*>(&slot->sq_hi[1]), (unsigned long long)r.sq_hi[1]);
+        }
+    }
+}
+
+// the workgroup's table into the handle's: every lane of the workgroup calls it (a barrier), lane 2 row + channel carries one value each
+template <bool WIDE>
+__device__ __forceinline__ void seq_meter_end(const shmt::Row* table, const SeqBusM& bus) {
+    __syncthreads();
+    const uint32_t row = threadIdx.x >> 1, c = threadIdx.x & 1u;
+    if (row > bus.ntracks) return;
+    const uint32_t peak = table[row].peak[c];
+    if (!peak) return;
+    shmt::Row* g = bus.meters + row;
+    atomicMax(&g->peak[c], peak);
+    atomicAdd(reinterpret_cast<unsigned long long*>(&g->sq_lo[c]), (unsigned long long)table[row].sq_lo[c]);
+    if (WIDE) atomicAdd(reinterpret_cast<unsigned long long*>(&g->sq_hi[c]), (unsigned long long)table[row].sq_hi[c]);
+}
+
+// audioop.mul of a folded track by its gain, as seq_fold8 forms it in front of its add
+__device__ __forceinline__ short8v seq_scale8(short8v x, const double factor) {
+    if (factor != 1.0) {                                      // (uniform)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = (short)fbound((double)x[j] * factor, Lim<short>::lo, Lim<short>::hi);
+    }
+    return x;
+}
+
 // PLAIN at 16 bits: k_seq_plain16's schedule, INFLIGHT records and source vectors in flight
 template <int SCHEME, int INFLIGHT, bool BUS = false, typename... Bus>
 __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_plain16(const SeqEv* __restrict__ ev, const she::Seg* __restrict__ segs,
@@ -814,11 +912,63 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_plain16(const SeqEv* 
                                                                    const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, short* out, int aligned,
                                                                    const Bus... bus_arg) {
     static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
+    constexpr bool METER = SeqMetered<Bus...>::value;
     uint32_t k, t0, s0;
-    if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
+    if constexpr (METER) {
+        if (!seq_window_tile<2>(order, lo, hi, k, t0, s0)) return;
+    } else {
+        if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
+    }
     const bool whole = aligned && s0 >= lo && s0 + 8 <= hi;
     short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t e = first[k];
+    if constexpr (METER) {
+        const SeqBusM& bus = seq_bus(bus_arg...);
+        shmt::Row* table = seq_meter_begin();
+        const bool stereo = bus.nch == 2;
+        if (__builtin_amdgcn_ballot_w64(s0 < hi && s0 + 8 > lo)) {                // (uniform: a wave with a lane in the window)
+            const uint32_t r1 = bus.rfirst[k + 1];
+            for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {   // the runs as below
+                const shq::Run run = bus.runs[r];
+                const double g = bus.gains.g[run.track];
+                const uint32_t e1 = run.end;
+                if (g == 0.0) { e = e1; continue; }
+                short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
+                if (e1 - e >= INFLIGHT) {
+                    SeqEv c[INFLIGHT], nx[INFLIGHT];
+#pragma unroll
+                    for (int u = 0; u < INFLIGHT; ++u) c[u] = ev[idx[e + u]];
+                    for (; e + INFLIGHT <= e1; e += INFLIGHT) {
+                        const bool more = e + 2 * INFLIGHT <= e1;
+                        if (more) {
+#pragma unroll
+                            for (int u = 0; u < INFLIGHT; ++u) nx[u] = ev[idx[e + INFLIGHT + u]];
+                        }
+                        short8v x[INFLIGHT];
+#pragma unroll
+                        for (int u = 0; u < INFLIGHT; ++u) x[u] = seq_event8<PLAIN, SCHEME>(c[u], segs, t0, s0);
+#pragma unroll
+                        for (int u = 0; u < INFLIGHT; ++u) seq_fold8(sub, x[u], c[u].factor);
+                        if (more) {
+#pragma unroll
+                            for (int u = 0; u < INFLIGHT; ++u) c[u] = nx[u];
+                        }
+                    }
+                }
+                for (; e < e1; ++e) {
+                    const SeqEv c = ev[idx[e]];
+                    seq_fold8(sub, seq_event8<PLAIN, SCHEME>(c, segs, t0, s0), c.factor);
+                }
+                sub = seq_scale8(sub, g);                     // post-fader: what the master takes of the track
+                seq_meter_wave<false>(shmt::lane<false, 8>(sub, s0, lo, hi, bus.nch), stereo, table + run.track);
+                acc = __builtin_elementwise_add_sat(acc, sub);
+            }
+            seq_meter_wave<false>(shmt::lane<false, 8>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
+            seq_window_store8(out, s0, lo, hi, whole, acc);
+        }
+        seq_meter_end<false>(table, bus);
+        return;
+    }
     if constexpr (BUS) {
         const SeqBus& bus = seq_bus(bus_arg...);
         const uint32_t r1 = bus.rfirst[k + 1];
@@ -896,11 +1046,53 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_16(const typename Seq
                                                               const Bus... bus_arg) {
     static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
     typedef typename SeqRec<LEVEL>::type Rec;
+    constexpr bool METER = SeqMetered<Bus...>::value;
     uint32_t k, t0, s0;
-    if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
+    if constexpr (METER) {
+        if (!seq_window_tile<2>(order, lo, hi, k, t0, s0)) return;
+    } else {
+        if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
+    }
     const bool whole = aligned && s0 >= lo && s0 + 8 <= hi;
     short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t e = first[k];
+    if constexpr (METER) {
+        const SeqBusM& bus = seq_bus(bus_arg...);
+        shmt::Row* table = seq_meter_begin();
+        const bool stereo = bus.nch == 2;
+        if (__builtin_amdgcn_ballot_w64(s0 < hi && s0 + 8 > lo)) {                // (uniform: a wave with a lane in the window)
+            const uint32_t r1 = bus.rfirst[k + 1];
+            for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {   // the runs as below
+                const shq::Run run = bus.runs[r];
+                const double g = bus.gains.g[run.track];
+                const uint32_t e1 = run.end;
+                if (g == 0.0) { e = e1; continue; }
+                short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
+                if constexpr (LEVEL >= LOOP) {
+                    uint32_t ni = idx[e];
+                    while (e < e1) {
+                        const Rec c = ev[ni];
+                        if (++e < e1) ni = idx[e];
+                        seq_fold8(sub, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
+                    }
+                } else {
+                    Rec nx = ev[idx[e]];
+                    while (e < e1) {
+                        const Rec c = nx;
+                        if (++e < e1) nx = ev[idx[e]];
+                        seq_fold8(sub, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
+                    }
+                }
+                sub = seq_scale8(sub, g);
+                seq_meter_wave<false>(shmt::lane<false, 8>(sub, s0, lo, hi, bus.nch), stereo, table + run.track);
+                acc = __builtin_elementwise_add_sat(acc, sub);
+            }
+            seq_meter_wave<false>(shmt::lane<false, 8>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
+            seq_window_store8(out, s0, lo, hi, whole, acc);
+        }
+        seq_meter_end<false>(table, bus);
+        return;
+    }
     if constexpr (BUS) {
         const SeqBus& bus = seq_bus(bus_arg...);
         const uint32_t r1 = bus.rfirst[k + 1];
@@ -959,9 +1151,56 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_w(const typename SeqR
                                                              const Bus... bus_arg) {
     static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
     static_assert(LEVEL != ENV || WIDTH == 1 || WIDTH == 4, "an envelope has widths 1, 2 and 4");
+    constexpr bool METER = SeqMetered<Bus...>::value;
     uint32_t k, t0, s0;
-    if (!seq_window_lane<WIDTH>(order, lo, hi, k, t0, s0)) return;
+    if constexpr (METER) {
+        if (!seq_window_tile<WIDTH>(order, lo, hi, k, t0, s0)) return;
+    } else {
+        if (!seq_window_lane<WIDTH>(order, lo, hi, k, t0, s0)) return;
+    }
     long long acc[4] = {0, 0, 0, 0};
+    if constexpr (METER) {
+        constexpr long long HI = SEQ_HI<WIDTH>, LO = SEQ_LO<WIDTH>;
+        constexpr bool WIDE = WIDTH >= 3;
+        const SeqBusM& bus = seq_bus(bus_arg...);
+        shmt::Row* table = seq_meter_begin();
+        const bool stereo = bus.nch == 2;
+        if (__builtin_amdgcn_ballot_w64(s0 < hi && s0 + 4 > lo)) {                // (uniform: a wave with a lane in the window)
+            uint32_t e = first[k];
+            const uint32_t r1 = bus.rfirst[k + 1];
+            for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {   // the runs as below
+                const shq::Run run = bus.runs[r];
+                const double g = bus.gains.g[run.track];
+                if (g == 0.0) { e = run.end; continue; }
+                long long sub[4] = {0, 0, 0, 0};
+                for (; e < run.end; ++e) {
+                    const typename SeqRec<LEVEL>::type c = ev[idx[e]];
+                    if constexpr (LEVEL == PLAIN) {
+                        const unsigned char* src = (const unsigned char*)c.src;
+                        seq_fold_w<WIDTH>(sub, c.factor, s0, c.dst, c.n, [&](int, long long rel) { return chain_get<WIDTH>(src, (size_t)rel); });
+                    } else {
+                        int v[4];
+                        seq_event<LEVEL, WIDTH, FUNNEL>(c, segs, t0, s0, v);
+                        seq_fold_w<WIDTH>(sub, c.factor, s0, c.dst, c.n, [&](int j, long long) { return (long long)v[j]; });
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (g != 1.0) sub[j] = fbound((double)sub[j] * g, (double)LO, (double)HI);       // post-fader
+                    const long long t = acc[j] + sub[j];
+                    acc[j] = t > HI ? HI : (t < LO ? LO : t);
+                }
+                seq_meter_wave<WIDE>(shmt::lane<WIDE, 4>(sub, s0, lo, hi, bus.nch), stereo, table + run.track);
+            }
+            seq_meter_wave<WIDE>(shmt::lane<WIDE, 4>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
+            unsigned char* p = out + (size_t)WIDTH * s0;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j)
+                if (s0 + j >= lo && s0 + j < hi) chain_put<WIDTH>(p, j, acc[j]);
+        }
+        seq_meter_end<WIDE>(table, bus);
+        return;
+    }
     if constexpr (BUS) {
         constexpr long long HI = SEQ_HI<WIDTH>, LO = SEQ_LO<WIDTH>;
         uint32_t e = first[k];
@@ -1394,10 +1633,11 @@ int sh_mix_events_chan(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_ev
 // every row, the segments, and plan_by_tile's index, in one device block that the handle owns (the buffer pool's, as sh_buf_alloc's; not
 // the grow-only scratch, which the next call overwrites).  The records point into the sources: the caller keeps those alive.
 struct sh_seq {
-    void*    block = nullptr;             // records | segments | first | idx | order | runs | rfirst (the last two: a song of tracks)
+    void*    block = nullptr;             // records | segments | first | idx | order | runs | rfirst | meters (the last three: a song of tracks)
     size_t   cap = 0, bytes = 0;
     size_t   at_segs = 0, at_first = 0, at_idx = 0, at_order = 0;     // order: the tiles heaviest first, for a render of the whole song
     size_t   at_rfirst = 0, at_runs = 0;  // shq::plan_runs' table, behind order
+    size_t   at_meters = 0;               // a song of tracks: ntracks + 1 rows of levels (shmt::Row) behind rfirst, written by a metered render alone
     uint32_t ntracks = 0, nruns = 0;      // ntracks == 0: sh_seq_create's flat list, no bus
     int      width = 0, nchannels = 0, level = 0;
     uint32_t nevents = 0, ntiles = 0, active_tiles = 0;
@@ -1419,7 +1659,7 @@ int seq_row_level(const SeqIn& m) {
 }
 
 template <int LEVEL>
-void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out, const SeqGains* gains) {
+void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out, const SeqGains* gains, bool metered) {
     typedef typename SeqRec<LEVEL>::type Rec;
     const char* b = (const char*)q->block;
     const Rec* ev = (const Rec*)b;
@@ -1429,6 +1669,28 @@ void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, 
     // the whole song: heaviest tile first (measured: profiles/sequence_plan_ab.txt); any other window: its tiles in song order
     const uint32_t* order = lo == 0 && hi == q->track_samples ? (const uint32_t*)(b + q->at_order) : nullptr;
     const dim3 block(shq::TILE_THREADS);
+    if (q->ntracks && metered) {                              // the same again with the metering bus: the rows go to the handle's table
+        SeqBusM bus;
+        bus.rfirst = (const uint32_t*)(b + q->at_rfirst);
+        bus.runs = (const shq::Run*)(b + q->at_runs);
+        bus.gains = *gains;
+        bus.meters = (shmt::Row*)((char*)q->block + q->at_meters);
+        bus.ntracks = q->ntracks;
+        bus.nch = (uint32_t)q->nchannels;
+        if (q->width == 2) {
+            const int aligned = ((uintptr_t)out & 15) == 0;
+            auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (short*)out, aligned, bus); };
+            const bool vec2 = sh::knobs().seq_align == VEC2;
+            if constexpr (LEVEL == PLAIN) vec2 ? go(k_win_plain16<VEC2, 4, true, SeqBusM>) : go(k_win_plain16<FUNNEL, 4, true, SeqBusM>);
+            else vec2 ? go(k_win_16<LEVEL, VEC2, true, SeqBusM>) : go(k_win_16<LEVEL, FUNNEL, true, SeqBusM>);
+        } else {
+            auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out, bus); };
+            if (q->width == 1) go(k_win_w<LEVEL, 1, true, SeqBusM>);
+            else if (q->width == 4) go(k_win_w<LEVEL, 4, true, SeqBusM>);
+            else if constexpr (LEVEL != ENV) go(k_win_w<LEVEL, 3, true, SeqBusM>);
+        }
+        return;
+    }
     if (q->ntracks) {                                         // a song of tracks: the same kernels with the bus, the gains by value
         const SeqBus bus{(const uint32_t*)(b + q->at_rfirst), (const shq::Run*)(b + q->at_runs), *gains};
         if (q->width == 2) {
@@ -1527,7 +1789,8 @@ int seq_create(const char* fn, const sh_buf* const* srcs, uint32_t nsrc, const s
         q->nruns = (uint32_t)R.runs.size();
         q->at_runs = (q->bytes + 7) & ~(size_t)7;
         q->at_rfirst = q->at_runs + R.runs.size() * sizeof(shq::Run);
-        q->bytes = q->at_rfirst + R.rfirst.size() * 4;
+        q->at_meters = (q->at_rfirst + R.rfirst.size() * 4 + 7) & ~(size_t)7;
+        q->bytes = q->at_meters + ((size_t)ntracks + 1) * sizeof(shmt::Row);
     }
     for (uint32_t v = 0; v < nsrc; ++v) {
         if (!srcs[v] || !srcs[v]->bytes) continue;
@@ -1579,14 +1842,22 @@ int seq_create(const char* fn, const sh_buf* const* srcs, uint32_t nsrc, const s
     return SH_OK;
 }
 
-// sh_seq_render (gains NULL: every track at 1.0) and sh_seq_render_gains behind their names
-int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains) {
+// sh_seq_render (gains NULL: every track at 1.0), sh_seq_render_gains and sh_seq_render_meters (meters: ntracks + 1 host rows, the handle
+// has tracks) behind their names
+int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains,
+               sh_seq_meter* meters = nullptr) {
+    static_assert(sizeof(sh_seq_meter) == sizeof(shmt::Row) && offsetof(sh_seq_meter, sq_hi) == offsetof(shmt::Row, sq_hi) &&
+                  offsetof(sh_seq_meter, sq_lo) == offsetof(shmt::Row, sq_lo), "sh_seq_meter is shmt::Row");
+    const size_t b_meters = meters ? ((size_t)seq->ntracks + 1) * sizeof(shmt::Row) : 0;
     const size_t w = (size_t)seq->width;
     if (first_sample > seq->track_samples || nsamples > seq->track_samples - first_sample)
         return sh::set_error(SH_ERR_INVALID, "%s: range outside the song", fn);
     const size_t have = out->bytes / w;
     if (out_sample > have || nsamples > have - out_sample) return sh::set_error(SH_ERR_INVALID, "%s: range outside out", fn);
-    if (!nsamples) return SH_OK;
+    if (!nsamples) {
+        if (meters) memset(meters, 0, b_meters);              // an empty window: every level 0
+        return SH_OK;
+    }
     const char* o0 = (const char*)out->ptr + out_sample * w;
     const char* o1 = o0 + nsamples * w;
     for (size_t v = 0; v < seq->src_lo.size(); ++v)
@@ -1602,16 +1873,23 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
         for (uint32_t t = 0; t < shq::MAX_TRACKS; ++t) unity.g[t] = 1.0;
         gains = &unity;
     }
+    char* table = (char*)seq->block + seq->at_meters;         // (the handle's: one metered render at a time)
+    if (meters) SH_HIP(hipMemsetAsync(table, 0, b_meters, st));
+    const bool metered = meters != nullptr;
     switch (seq->level) {
-    case PLAIN: seq_window_launch<PLAIN>(seq, grid, st, lo, hi, biased, gains); break;
-    case RATE: seq_window_launch<RATE>(seq, grid, st, lo, hi, biased, gains); break;
-    case PAN: seq_window_launch<PAN>(seq, grid, st, lo, hi, biased, gains); break;
-    case ENV: seq_window_launch<ENV>(seq, grid, st, lo, hi, biased, gains); break;
-    case LOOP: seq_window_launch<LOOP>(seq, grid, st, lo, hi, biased, gains); break;
-    case REV: seq_window_launch<REV>(seq, grid, st, lo, hi, biased, gains); break;
-    default: seq_window_launch<CHAN>(seq, grid, st, lo, hi, biased, gains); break;
+    case PLAIN: seq_window_launch<PLAIN>(seq, grid, st, lo, hi, biased, gains, metered); break;
+    case RATE: seq_window_launch<RATE>(seq, grid, st, lo, hi, biased, gains, metered); break;
+    case PAN: seq_window_launch<PAN>(seq, grid, st, lo, hi, biased, gains, metered); break;
+    case ENV: seq_window_launch<ENV>(seq, grid, st, lo, hi, biased, gains, metered); break;
+    case LOOP: seq_window_launch<LOOP>(seq, grid, st, lo, hi, biased, gains, metered); break;
+    case REV: seq_window_launch<REV>(seq, grid, st, lo, hi, biased, gains, metered); break;
+    default: seq_window_launch<CHAN>(seq, grid, st, lo, hi, biased, gains, metered); break;
     }
     SH_CHECK_LAUNCH(fn);
+    if (meters) {                                             // synchronous, as sh_pcm_stats: one small copy, one wait
+        SH_HIP(hipMemcpyAsync(meters, table, b_meters, hipMemcpyDeviceToHost, st));
+        SH_HIP(hipStreamSynchronize(st));
+    }
     return SH_OK;
 }
 
@@ -1654,6 +1932,23 @@ int sh_seq_render_gains(const sh_seq* seq, size_t first_sample, size_t nsamples,
         g.g[t] = gains[t];
     }
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g);
+}
+
+int sh_seq_render_meters(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                         uint32_t ngains, sh_seq_meter* meters, uint32_t nmeters) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_seq_render_meters";
+    if (!seq || !out || !meters || (!gains && ngains)) return seq_null(fn);
+    if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
+    if (gains && ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
+    if (nmeters != seq->ntracks + 1) return sh::set_error(SH_ERR_INVALID, "%s: %u rows for %u tracks and the master", fn, nmeters, seq->ntracks);
+    SeqGains g;
+    for (uint32_t t = 0; t < shq::MAX_TRACKS; ++t) g.g[t] = 1.0;
+    for (uint32_t t = 0; gains && t < ngains; ++t) {
+        if (!isfinite(gains[t])) return sh::set_error(SH_ERR_INVALID, "%s: gain %u is not finite", fn, t);
+        g.g[t] = gains[t];
+    }
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters);
 }
 
 int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns) {

@@ -31,7 +31,7 @@ from . import params
 from .oscillators import Oscillator, VoiceSpec, _pwm_widths, _table, pack_voices, time_step_weights
 from .sample import Sample
 
-__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "sequence", "compile_sequence", "compile_tracks", "CompiledSequence", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
+__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "sequence", "compile_sequence", "compile_tracks", "CompiledSequence", "Levels", "SongLevels", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
 
 
 def pan_gains(pan: float) -> Tuple[float, float]:
@@ -591,6 +591,64 @@ def sequence(events: Sequence[tuple], samplerate: int, nchannels: int, samplewid
     return track.mix_at_many(events)
 
 
+class Levels:
+    """The levels of one track, or of the master, in one rendered window of a song of tracks (``CompiledSequence.render(meters=True)``):
+    per channel, as ``(left, right)`` tuples, ``peak`` (``audioop.max``), ``sum_squares`` (the exact integer sum of x * x, a Python int),
+    ``rms`` (``int(sqrt(sum_squares / frames))``, as ``Sample.rms`` forms it; 0 for an empty window) and ``level_db_peak`` /
+    ``level_db_rms`` by ``Sample.level_db_peak``'s formula, ``20 log10((v + 1) / 2^(8 w - 1))`` and not below -60.  A mono song gives
+    ``left == right``, as ``Sample`` does.  It has what ``LevelMeter.update`` reads of a ``Sample`` (the two levels and ``duration``)."""
+
+    def __init__(self, peak, sum_squares, frames: int, samplewidth: int, nchannels: int, samplerate: int) -> None:
+        both = (lambda v: (int(v[0]), int(v[1]))) if nchannels == 2 else (lambda v: (int(v[0]), int(v[0])))
+        self.peak = both(peak)
+        self.sum_squares = both(sum_squares)
+        self.frames, self.samplewidth, self.nchannels, self.samplerate = int(frames), int(samplewidth), int(nchannels), int(samplerate)
+
+    @property
+    def duration(self) -> float:
+        return self.frames / self.samplerate
+
+    @property
+    def rms(self) -> Tuple[int, int]:
+        if not self.frames:
+            return 0, 0
+        return int(math.sqrt(self.sum_squares[0] / self.frames)), int(math.sqrt(self.sum_squares[1] / self.frames))
+
+    def _db(self, values) -> Tuple[float, float]:
+        maxvalue = 2 ** (8 * self.samplewidth - 1)
+        # cut off at -60 dB instead of running down to -infinity
+        return max(20.0 * math.log((values[0] + 1) / maxvalue, 10), -60.0), max(20.0 * math.log((values[1] + 1) / maxvalue, 10), -60.0)
+
+    @property
+    def level_db_peak(self) -> Tuple[float, float]:
+        return self._db(self.peak)
+
+    @property
+    def level_db_rms(self) -> Tuple[float, float]:
+        return self._db(self.rms)
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Levels) and (self.peak, self.sum_squares, self.frames, self.samplewidth, self.nchannels) == (
+            other.peak, other.sum_squares, other.frames, other.samplewidth, other.nchannels)
+
+    def __repr__(self) -> str:
+        return "Levels(peak=%r, sum_squares=%r, frames=%d)" % (self.peak, self.sum_squares, self.frames)
+
+
+class SongLevels:
+    """What a metered render returns beside its bytes: ``tracks``, one ``Levels`` per track, POST-fader (over the track as the master takes
+    it: folded on its own, times its gain; a muted track reads zero), and ``master``, over the window's output -- all from the one launch
+    that rendered the window.  ``rows``: ``N.Sequence.render(meters=True)``'s, the master last."""
+
+    def __init__(self, rows, frames: int, samplewidth: int, nchannels: int, samplerate: int) -> None:
+        made = [Levels(peak, sq, frames, samplewidth, nchannels, samplerate) for peak, sq in rows]
+        self.tracks: List[Levels] = made[:-1]
+        self.master: Levels = made[-1]
+
+    def __repr__(self) -> str:
+        return "SongLevels(tracks=%r, master=%r)" % (self.tracks, self.master)
+
+
 class CompiledSequence:
     """A list of placed samples compiled once and rendered as often, and in whatever windows, as a player asks: ``render`` of frames
     ``[a, b)`` holds, byte for byte, frames ``[a, b)`` of ``sequence(events, ...)``, in one launch that copies no table.  Made by
@@ -609,7 +667,11 @@ class CompiledSequence:
     -- which is NOT the flat list: a track saturates on its own before its gain applies, and the master at every track -- with
     ``gains`` given when a window is RENDERED: ``render``, ``render_into`` and ``chunks`` take ``gains=`` (one finite float per
     track; None: all 1.0) and ``stem`` renders one track alone.  Mute, solo and fader moves compile nothing, upload nothing and
-    materialise no track: still one launch per window."""
+    materialise no track: still one launch per window.
+    The desk's METERS: ``render``, ``render_into`` and ``chunks`` take ``meters=True`` and give, from that same launch, a
+    ``SongLevels`` -- the levels of every track post-fader and of the master in the window just rendered, exact in integers -- beside
+    the same bytes.  A handle serves one metered render at a time.  Not built: pre-fader meters (they would read a muted track's
+    events), meters of a song without tracks, clip counters."""
 
     MAX_TRACKS = 32
 
@@ -681,6 +743,17 @@ class CompiledSequence:
                 raise ValueError("CompiledSequence: gain %d is not finite" % t)
         return out
 
+    def _meters(self, meters) -> bool:
+        """``meters`` as render hands it on -- checked before anything is launched"""
+        if meters and self.ntracks is None:
+            raise ValueError("CompiledSequence: meters need a song of tracks (compile_tracks); this one has none")
+        return bool(meters)
+
+    def _levels(self, rows, nframes: int) -> SongLevels:
+        if rows is None:                                        # an empty window: nothing was launched, every level 0
+            rows = [((0, 0), (0, 0))] * (self.ntracks + 1)
+        return SongLevels(rows, nframes, self.samplewidth, self.nchannels, self.samplerate)
+
     @property
     def duration(self) -> float:
         return self.frames / self.samplerate
@@ -706,31 +779,47 @@ class CompiledSequence:
             raise ValueError("CompiledSequence: frames [%d, %d) outside the song's %d frames" % (start_frame, start_frame + nframes, self.frames))
         return start_frame, nframes
 
-    def render_into(self, buf: N.DeviceBuffer, byte_offset: int, start_frame: int, nframes: int, gains: Optional[Sequence[float]] = None) -> None:
+    def render_into(self, buf: N.DeviceBuffer, byte_offset: int, start_frame: int, nframes: int, gains: Optional[Sequence[float]] = None,
+                    meters: bool = False) -> Optional[SongLevels]:
         """Frames ``[start_frame, start_frame + nframes)`` of the song into ``buf`` from ``byte_offset`` (a whole number of samples) on:
-        every byte of the range is written, whatever ``buf`` held.  ``gains``: one per track of a song of tracks."""
+        every byte of the range is written, whatever ``buf`` held.  ``gains``: one per track of a song of tracks.  ``meters=True``: the
+        same bytes, and the window's ``SongLevels`` returned, from the same launch (the call then waits for it)."""
         seq = self._handle()
         gains = self._gains(gains)
+        meters = self._meters(meters)
         start_frame, nframes = self._range(start_frame, nframes)
         if byte_offset < 0 or byte_offset % self.samplewidth:
             raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
+        if meters:
+            rows = None
+            if nframes:
+                rows = seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains, meters=True)
+            return self._levels(rows, nframes)
         if nframes:
             if gains is None:
                 seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth)
             else:
                 seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains)
+        return None
 
-    def render(self, start_frame: int = 0, nframes: Optional[int] = None, gains: Optional[Sequence[float]] = None) -> Sample:
+    def render(self, start_frame: int = 0, nframes: Optional[int] = None, gains: Optional[Sequence[float]] = None, meters: bool = False):
         """A new ``Sample``: frames ``[start_frame, start_frame + nframes)`` of the song; ``nframes`` None: to the end.  ``gains``: one
-        per track of a song of tracks (None: all 1.0)."""
+        per track of a song of tracks (None: all 1.0).  ``meters=True``: ``(Sample, SongLevels)``, both from the one launch."""
         self._handle()
         gains = self._gains(gains)
+        meters = self._meters(meters)
         start_frame, nframes = self._range(start_frame, nframes)
         out = Sample(name=self.name, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth)
+        levels = None
         if nframes:
             buf = N.DeviceBuffer(nframes * self._fb)
-            self.render_into(buf, 0, start_frame, nframes, gains=gains)
+            if meters:
+                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=True)
+            else:
+                self.render_into(buf, 0, start_frame, nframes, gains=gains)
             out._set_device(buf, nframes * self._fb)
+        if meters:
+            return out, levels if levels is not None else self._levels(None, 0)
         return out
 
     def stem(self, track: int, start_frame: int = 0, nframes: Optional[int] = None) -> Sample:
@@ -743,15 +832,20 @@ class CompiledSequence:
             raise ValueError("CompiledSequence: track %d outside the song's %d tracks" % (track, self.ntracks))
         return self.render(start_frame, nframes, gains=[1.0 if t == track else 0.0 for t in range(self.ntracks)])
 
-    def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None) -> Generator[Sample, None, None]:
-        """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter.  ``gains``: as ``render``'s."""
+    def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None, meters: bool = False) -> Generator:
+        """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter.  ``gains``: as ``render``'s.
+        ``meters=True``: ``(Sample, SongLevels)`` pairs."""
         chunk_frames = int(chunk_frames)
         if chunk_frames <= 0:
             raise ValueError("CompiledSequence: chunk_frames must be positive")
         self._handle()
         gains = self._gains(gains)
+        meters = self._meters(meters)
         for at in range(0, self.frames, chunk_frames):
-            yield self.render(at, min(chunk_frames, self.frames - at), gains=gains)
+            if meters:
+                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=True)
+            else:
+                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains)
 
     def close(self) -> None:
         if self._seq is not None:

@@ -76,7 +76,13 @@ window; every 16th window of the song) for: (a) mixer.compile_tracks' handle, on
 was before -- one CompiledSequence per track, each rendered, amplified and mixed into a master: 8 renders, up to 8 amplifies, 8 mixes, 8
 tracks materialised per window -- held to (a)'s bytes first; (c) a flat compile_sequence of the same notes, the same work without the bus
 (other bytes: the flat list is another chain); (d) (a) with one track muted, and one stem.  On a tree without compile_tracks only (c)
-runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequence_ab.py --tracks is the parent's own figure for (c)."""
+runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequence_ab.py --tracks is the parent's own figure for (c).
+
+--meters: the stereo songs of --tracks (8 tracks, 4096 / 32 768 notes) with the desk's level meters.  Wall time with a device synchronise,
+medians, of the whole song and per window of 4096 frames, for: (a) render(gains=), the path without meters; (b) render(gains=,
+meters=True), the rows from the same launch; (c) what a caller did before -- render(gains=), then stem, amplify and the Sample's peak and
+sum-of-squares statistics for each of the 8 tracks, then the same on the master -- held to (b)'s rows first, as (b)'s bytes are to (a)'s.
+--meters-trace NEVENTS: twenty whole-song renders each of (a) and (b) of the first song and nothing else, for rocprofv3 --kernel-trace."""
 import audioop
 import os
 import sys
@@ -980,6 +986,91 @@ def tracks_main():
                 cs.close()
 
 
+def meters_songs(nevents):
+    """the stereo songs of --tracks: (what, nch, events)"""
+    _base, sources, events = rev_song(nevents, 120.0)
+    samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in sources]
+    rev_evs = [(s, samples[i], v, None, sp, None, e, lp, rg, rv) for s, i, v, sp, e, lp, rg, rv in events]
+    songs = [("chan, balance on every other note, stereo track", 2, [ev + (CHANNELS[k % 4] if k % 2 == 0 else None,) for k, ev in enumerate(rev_evs)])]
+    _base, inst, shaped = env_song(nevents, 120.0)
+    env_samples = [Sample.from_raw_frames(b, WIDTH, RATE, NCH).to_device() for b in inst]
+    songs.append(("env, stereo track", NCH, [(s, env_samples[i], v, None, sp, None, e) for s, i, v, sp, e in shaped]))
+    return songs
+
+
+def meters_main():
+    """--meters: the level meters of a song of tracks from the render's own launch.  (a) render(gains=), the code path without meters;
+    (b) render(gains=, meters=True); (c) what a caller did without them: render(gains=), then per track stem, amplify and the Sample's
+    peak and sum-of-squares calls, then the same on the master -- held to (b)'s rows first.  Wall time with a device synchronise (b and c
+    wait for their figures anyway), medians; whole song and 4096-frame windows.  --meters-trace NEVENTS: whole-song renders of (a) and (b)
+    alone, for a kernel trace of its own."""
+    N.ensure_init(0)
+    info = N.device_info()
+    trace = "--meters-trace" in sys.argv[1:]
+    sizes = (int(sys.argv[sys.argv.index("--meters-trace") + 1]),) if trace else (4096, 32768)
+    print("sequence_meters_ab: SYNTHHIP_SEQ_ALIGN=%s  %s%s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"],
+                                                            "  (trace run: 20 whole-song renders each of (a) and (b))" if trace else ""), flush=True)
+    win, ntracks = 4096, len(TRACK_GAINS)
+    for nevents in sizes:
+        for what, nch, evs in meters_songs(nevents)[:1 if trace else None]:
+            fb = nch * WIDTH
+            bus = mixer.compile_tracks([evs[t::ntracks] for t in range(ntracks)], RATE, nch, WIDTH)
+            frames = bus.frames
+            out = N.DeviceBuffer(frames * fb + 16)
+            if trace:
+                for _ in range(20):
+                    bus.render_into(out, 0, 0, frames, gains=TRACK_GAINS)
+                    bus.render_into(out, 0, 0, frames, gains=TRACK_GAINS, meters=True)
+                N.sync()
+                print("meters trace, %5d events, %s, %d frames, level %s: done" % (nevents, what, frames, bus.level), flush=True)
+                bus.close()
+                continue
+            wins = list(range(0, (frames - 3) // win, 16))
+
+            def caller(a, n):
+                """(c): the rows as ((peaks), (sums)) per track and for the master"""
+                rows = []
+                master = bus.render(a, n, gains=TRACK_GAINS)
+                for t, g in enumerate(TRACK_GAINS):
+                    sub = bus.stem(t, a, n)
+                    if g != 1.0:
+                        sub.amplify(g)
+                    rows.append(sub._channel_stats())
+                rows.append(master._channel_stats())
+                return rows
+
+            def same(lv, rows):
+                got = [(r.peak, r.sum_squares) for r in lv.tracks + [lv.master]]
+                return all(p == rp and all(abs(float(s[c]) - rs[c]) <= 1e-12 * max(1.0, rs[c]) for c in (0, 1)) for (p, s), (rp, rs) in zip(got, rows))
+
+            mid = (frames // 2) // win * win
+            parity = same(bus.render(gains=TRACK_GAINS, meters=True)[1], caller(0, frames)) and same(bus.render(mid, win, gains=TRACK_GAINS, meters=True)[1], caller(mid, win))
+            plain, lv = bus.render(mid, win, gains=TRACK_GAINS), bus.render(mid, win, gains=TRACK_GAINS, meters=True)
+            parity = parity and bytes(plain.view_frame_data()) == bytes(lv[0].view_frame_data())
+
+            def stream(render):
+                for k in wins:
+                    render(k * win, win)
+                    N.sync()
+
+            a_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, gains=TRACK_GAINS), 2, 15)
+            b_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, gains=TRACK_GAINS, meters=True), 2, 15)
+            c_whole = median_wall(lambda: caller(0, frames), 1, 5)
+            a_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, gains=TRACK_GAINS))
+            b_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, gains=TRACK_GAINS, meters=True))
+            a_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, gains=TRACK_GAINS)), 1, 5) / len(wins)
+            b_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, gains=TRACK_GAINS, meters=True)), 1, 5) / len(wins)
+            c_win = median_wall(lambda: stream(caller), 1, 3) / len(wins)
+            fmt = lambda v: " ".join("%.4f" % x for x in v)    # noqa: E731
+            print("meters song 120 s, %5d events, %s, %d tracks, level %s, %d frames   whole song, wall with a synchronise, median: (a) render(gains=) "
+                  "%.4f ms   (b) render(gains=, meters=True) %.4f ms   (c) render, 8 stems, amplify, statistics %.3f ms   between two events on the "
+                  "stream, five medians of 15: (a) %s ms   (b) %s ms   a window of %d frames, wall: (a) %.4f ms   (b) %.4f ms   (c) %.3f ms   "
+                  "(b) / (a) whole %.3f, window %.3f   (b) / (c) whole %.4f, window %.4f   (c) against (b)'s rows, and (b)'s bytes against (a)'s: %s"
+                  % (nevents, what, ntracks, bus.level, frames, a_whole, b_whole, c_whole, fmt(a_dev), fmt(b_dev), win, a_win, b_win, c_win,
+                     b_whole / a_whole, b_win / a_win, b_whole / c_whole, b_win / c_win, "ok" if parity else "FAILED"), flush=True)
+            bus.close()
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -1050,4 +1141,4 @@ def main():
 
 
 if __name__ == "__main__":
-    tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
