@@ -129,3 +129,82 @@ def test_empty_inputs(sq):
     for events, track in (([], 0), ([], 5000), ([(0, 0)], 0), ([(7, 0), (5000, 0)], 5000)):
         refused, _bad, tiles, first, idx = run_plan(sq, events, track, tile)
         assert refused == OK and tiles == [] and first == [0] and idx == []
+
+
+# ---- the same plans far out: past 2^31 samples and up to the last tile a track can have ---------------------------------------------------------
+MAX = 2 ** 32 - 65536
+DM_LIMIT = 2 ** 31 - 32768                                  # where a downmix ends at the latest (sequence.hip forms 2 * (dst + n) in 32 bits)
+
+
+def near_lists(tile):
+    """[(track samples, events)]: the four-tile song of the GPU tests (a note across the first tile edge, a pile-up in tile 1, tile 2
+    idle, the song ending mid-lane in tile 3), events on and around every tile edge with empty ones between, a whole number of tiles
+    under one long note, and two generated lists"""
+    lane = tile // 256 or 1
+    w0 = tile + 3 * lane
+    song = [(0, 300 % tile), (tile - tile // 4, tile // 2), (w0 - lane, 3 * lane), (w0 + 10, tile // 8), (w0 + 13, tile // 8), (w0 + 17, tile // 8),
+            (3 * tile, 37 * lane + 3)]
+    edges = [(0, 0), (tile - 1, 1), (tile - 1, 2), (tile, tile), (2 * tile, 0), (3 * tile - 1, tile + 1), (5, 4 * tile - 5), (4 * tile - 1, 1)]
+    lists = [(3 * tile + 37 * lane + 3, song), (4 * tile, edges), (7 * tile, [(0, 7 * tile), (3 * tile + 1, 2), (7 * tile - 2, 2)])]
+    rng = random.Random(1000 + tile)
+    for ntiles in (3, 17):
+        track = ntiles * tile - rng.randrange(1, tile)
+        events = []
+        for _ in range(60):
+            n = rng.choice([0, 1, tile - 1, tile, tile + 1, rng.randrange(0, 3 * tile)])
+            n = min(n, track)
+            events.append((rng.randrange(0, track - n + 1), n))
+        lists.append((track, events))
+    return lists
+
+
+def far_bases(tile, track, events):
+    """{name: (B, tile-aligned)}: `mid` puts the list's second tile on sample 2^31, `top` its last tile on the last tile a track can have (a
+    list of whole tiles then ends at MAX), `dm` the end of its first sounding event on the downmix limit, which is no multiple of the tile"""
+    ntiles = -(-track // tile)
+    d, n = next(e for e in events if e[1])
+    dm = DM_LIMIT - (d + n)
+    if dm % tile == 0:
+        dm -= 3
+    return {"mid": (2 ** 31 - tile, True), "top": (MAX - ntiles * tile, True), "dm": (dm, False)}
+
+
+def shifted(events, B):
+    return [(d + B, n) for d, n in events]
+
+
+def test_a_list_placed_far_out_plans_as_the_near_one_with_its_tiles_raised(sq):
+    assert sq.sq_max_track() == MAX
+    crossed = ended = 0
+    for tile in (sq.sq_tile(2), sq.sq_tile(1)):
+        for track, events in near_lists(tile):
+            refused, _bad, tiles, first, idx = run_plan(sq, events, track, tile)
+            assert refused == OK and tiles
+            for name, (B, aligned) in far_bases(tile, track, events).items():
+                what = (tile, track, len(events), name)
+                far = shifted(events, B)
+                assert B + track <= MAX and B > 2 ** 30
+                r2, _b2, tiles2, first2, idx2 = run_plan(sq, far, B + track, tile)
+                assert r2 == OK, what
+                if aligned:                                 # the near plan, every tile number raised by B / tile
+                    assert B % tile == 0 and tiles2 == [t + B // tile for t in tiles] and first2 == first and idx2 == idx, what
+                    assert max(tiles2) == (B + max(d + n for d, n in events if n) - 1) // tile < 2 ** 22, what
+                want = brute(far, tile)                     # and, aligned or not, the brute-force overlap count at the far coordinates
+                assert sorted(tiles2) == sorted(want) and len(first2) == len(tiles2) + 1 and first2[-1] == len(idx2), what
+                counts = [first2[j + 1] - first2[j] for j in range(len(tiles2))]
+                assert all(a >= b for a, b in zip(counts, counts[1:])), what
+                for j, t in enumerate(tiles2):
+                    assert idx2[first2[j]:first2[j + 1]] == want[t], (what, t)
+                crossed += any(d < 2 ** 31 < d + n for d, n in far)
+                ended += B + track == MAX
+                # one sample more than the track holds is still refused up there
+                assert run_plan(sq, far + [(B + track, 1)], B + track, tile)[:2] == (EVENT_BEYOND_TRACK, len(far)), what
+    assert crossed >= 4 and ended >= 2
+
+
+def test_the_program_of_its_own(tmp_path):
+    """cpu_seqplan.cpp with its own main: the form a sanitizer build runs (here built plainly)"""
+    exe = tmp_path / "seqplan"
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-DSEQPLAN_MAIN", str(ROOT / "tests" / "cpu_seqplan.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    assert out.startswith("seqplan: ") and out.rstrip().endswith("ok")

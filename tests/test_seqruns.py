@@ -147,3 +147,66 @@ def test_the_program_of_its_own(tmp_path):
     subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-DSEQRUNS_MAIN", str(ROOT / "tests" / "cpu_seqruns.cpp"), "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
     assert out.startswith("seqruns: 400 songs") and out.rstrip().endswith("ok")
+
+
+# ---- the runs of a song of tracks far out ------------------------------------------------------------------------------------------------------
+def run_far(sr, tracks, track_samples, tile):
+    """run_plan for a song of millions of tiles: (first, idx, rfirst) as numpy arrays, runs as (end, track)"""
+    import numpy as np
+    events = [e for t in tracks for e in t]
+    track_of = [k for k, t in enumerate(tracks) for _e in t]
+    n = len(events)
+    dst = (C.c_uint64 * max(n, 1))(*[e[0] for e in events])
+    cnt = (C.c_uint64 * max(n, 1))(*[e[1] for e in events])
+    tof = (C.c_uint32 * max(n, 1))(*track_of)
+    refused = C.c_int()
+    p = sr.sr_plan(dst, cnt, tof, n, track_samples, tile, C.byref(refused))
+    try:
+        assert refused.value == 0
+        nt, npairs, nruns = sr.sr_ntiles(p), sr.sr_npairs(p), sr.sr_nruns(p)
+        assert sr.sr_nrfirst(p) == nt + 1
+        arr = lambda ptr, count: np.ctypeslib.as_array(ptr, shape=(count,)).copy() if count else np.zeros(0, dtype=np.uint32)      # noqa: E731
+        flat = sr.sr_runs(p)[:2 * nruns]
+        return arr(sr.sr_first(p), nt + 1), arr(sr.sr_idx(p), npairs), arr(sr.sr_rfirst(p), nt + 1), list(zip(flat[0::2], flat[1::2]))
+    finally:
+        sr.sr_free(p)
+
+
+def test_a_song_of_tracks_placed_far_out_has_the_near_runs_with_its_tiles_raised(sr):
+    import numpy as np
+    from tests.test_seqplan import MAX, far_bases, near_lists
+    for tile in (2048, TILE):
+        for track, events in near_lists(tile):
+            for ntracks in (1, 3):
+                dealt = [events[k::ntracks] for k in range(ntracks)]                   # the list dealt over the tracks, each in list order
+                near_first, near_idx, near_rfirst, near_runs = check(sr, dealt, track, tile)
+                for name, (B, aligned) in far_bases(tile, track, events).items():
+                    what = (tile, track, ntracks, name)
+                    far = [[(d + B, n) for d, n in t] for t in dealt]
+                    first, idx, rfirst, runs = run_far(sr, far, B + track, tile)
+                    ntiles = len(first) - 1
+                    assert ntiles == -(-(B + track) // tile) and rfirst[0] == 0 and rfirst[-1] == len(runs), what
+                    if aligned:                             # tile t of the near song is tile t + B / tile
+                        k = B // tile
+                        assert not rfirst[:k].any() and rfirst[k:].tolist() == near_rfirst and runs == near_runs, what
+                        assert not first[:k].any() and first[k:].tolist() == near_first and idx.tolist() == near_idx, what
+                    want = {}                               # brute()'s restatement, kept per tile that has events: tile -> [(track, [events])]
+                    e = 0
+                    for trk, t in enumerate(far):
+                        for d, n in t:
+                            if n:
+                                for tl in range(d // tile, (d + n - 1) // tile + 1):
+                                    if tl not in want or want[tl][-1][0] != trk:
+                                        want.setdefault(tl, []).append((trk, []))
+                                    want[tl][-1][1].append(e)
+                            e += 1
+                    assert np.flatnonzero(np.diff(rfirst.astype(np.int64))).tolist() == sorted(want), what
+                    for tl, mine in want.items():
+                        got = runs[rfirst[tl]:rfirst[tl + 1]]
+                        assert [trk for _end, trk in got] == [trk for trk, _ev in mine], (what, tl)
+                        at = int(first[tl])
+                        for (end, _trk), (_t, evs) in zip(got, mine):
+                            assert idx[at:end].tolist() == evs, (what, tl)
+                            at = end
+                        assert at == first[tl + 1], (what, tl)
+    assert MAX // TILE > 2 ** 21

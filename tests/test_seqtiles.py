@@ -122,3 +122,59 @@ def test_each_refusal_fires_and_only_then(st):
     assert len(run(st, events, track, tile, max_pairs=12)["idx"]) == 12
     r = run(st, events, track, tile, max_pairs=11)
     assert r["refused"] == TOO_MANY_PAIRS == r["plan_refused"]
+
+
+# ---- the same index far out: a song of up to 2^22 tiles, its events in the last few ------------------------------------------------------------
+def run_far(st, events, track, tile):
+    """run() for a song of millions of tiles: first and idx as numpy arrays, nothing of plan's but its active tiles"""
+    import numpy as np
+    n = len(events)
+    dst = (C.c_uint64 * max(n, 1))(*[e[0] for e in events])
+    cnt = (C.c_uint64 * max(n, 1))(*[e[1] for e in events])
+    refused, bad, plan_refused = C.c_int(), C.c_uint32(), C.c_int()
+    p = st.st_plan(dst, cnt, n, track, tile, st.st_max_pairs(), C.byref(refused), C.byref(bad), C.byref(plan_refused))
+    try:
+        assert refused.value == OK == plan_refused.value
+        first = np.ctypeslib.as_array(st.st_first(p), shape=(st.st_nfirst(p),)).copy()
+        npairs = st.st_npairs(p)
+        idx = np.ctypeslib.as_array(st.st_idx(p), shape=(npairs,)).copy() if npairs else np.zeros(0, dtype=np.uint32)
+        return dict(ntiles=st.st_ntiles(p), active=st.st_active(p), first=first, idx=idx, tiles=st.st_plan_tiles(p)[:st.st_plan_ntiles(p)])
+    finally:
+        st.st_free(p)
+
+
+def test_a_song_placed_far_out_indexes_as_the_near_one_with_its_tiles_raised(st):
+    import numpy as np
+    from tests.test_seqplan import MAX, far_bases, near_lists, shifted
+    assert st.st_max_track() == MAX
+    longest = 0
+    for tile in (st.st_tile(2), st.st_tile(1)):
+        for track, events in near_lists(tile):
+            near = run(st, events, track, tile)
+            holds(near, events, track, tile, (tile, track))
+            for name, (B, aligned) in far_bases(tile, track, events).items():
+                what = (tile, track, len(events), name)
+                far = shifted(events, B)
+                r = run_far(st, far, B + track, tile)
+                first, idx = r["first"], r["idx"]
+                assert r["ntiles"] == -(-(B + track) // tile) == len(first) - 1 and first[0] == 0 and first[-1] == len(idx), what
+                if aligned:                                 # tile t of the near song is tile t + B / tile: nothing in front, the same index behind
+                    k = B // tile
+                    assert r["ntiles"] == k + near["ntiles"] and r["active"] == near["active"], what
+                    assert not first[:k].any() and first[k:].tolist() == near["first"] and idx.tolist() == near["idx"], what
+                want = brute(far, tile)                     # and, aligned or not, the brute-force overlap count at the far coordinates
+                counts = np.diff(first.astype(np.int64))
+                assert (counts >= 0).all() and np.flatnonzero(counts).tolist() == sorted(want) == sorted(r["tiles"]), what
+                assert r["active"] == len(want), what
+                for t, evs in want.items():
+                    assert idx[first[t]:first[t + 1]].tolist() == evs, (what, t)
+                longest = max(longest, r["ntiles"])
+    assert longest == MAX // st.st_tile(1) == 2 ** 22 - 64 > 2 ** 21     # a song of the greatest length: more tiles than one grid row takes
+
+
+def test_the_program_of_its_own(tmp_path):
+    """cpu_seqtiles.cpp with its own main: the form a sanitizer build runs (here built plainly)"""
+    exe = tmp_path / "seqtiles"
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-DSEQTILES_MAIN", str(ROOT / "tests" / "cpu_seqtiles.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    assert out.startswith("seqtiles: ") and out.rstrip().endswith("ok")
