@@ -33,21 +33,28 @@
 // reached from that entry point alone), CHAN (+ downmix and balance: sh_mix_events_chan; five kernels again, reached from there
 // alone).  seq_event is the chain up to the mul, written once: a stage above the level is removed by `if constexpr`, a stage of the
 // level that an event does not use is skipped by a wave-uniform branch on its record (a row of sh_mix_events_loop without a loop is an
-// event of ENV).  Three kernel templates call it: the plain 16-bit one (INFLIGHT records and source vectors in flight), the 16-bit one
-// of the other levels (one record ahead) and the one of widths 1, 3, 4.  Built with -ffp-contract=off (the float64 product of
-// audioop.mul stays one rounding, ratecv's prev*d + cur*(outr-d) two, tomono's l*left + r*right three).
+// event of ENV).  The loop around it -- events [e, e1) of a tile's index folded into a lane's accumulator in list order -- is a SCHEDULE,
+// and there are three, each written once: seq_walk_plain16 (PLAIN at 16 bits: INFLIGHT records and source vectors in flight),
+// seq_walk_16 (the other levels at 16 bits: one record ahead, from LOOP on the next record's index) and seq_walk_w (widths 1, 3, 4,
+// event by event).  Three kernel templates, k_seq_plain16, k_seq_16 and k_seq_w, are a schedule between the load of a tile's track
+// samples and their store.  Built with -ffp-contract=off (the float64 product of audioop.mul stays one rounding, ratecv's
+// prev*d + cur*(outr-d) two, tomono's l*left + r*right three).
 //
 // A list that is KEPT (sh_seq_create: the checks, the records of the lowest level that covers every row, the segments and
 // shq::plan_by_tile's index -- every tile of the song in song order -- uploaded once into a block the handle owns) is rendered window by
-// window by three more templates, k_win_plain16, k_win_16 and k_win_w, which mirror the three above and call the same seq_event, seq_fold8
-// and seq_fold_w: one workgroup per song tile of the window (workgroup k takes tile lo / TILE + k; a window that is the WHOLE song takes
+// window by three more templates, k_win_plain16, k_win_16 and k_win_w, which mirror the three above and call the same three schedules:
+// one workgroup per song tile of the window (workgroup k takes tile lo / TILE + k; a window that is the WHOLE song takes
 // tile order[k], the tiles heaviest first, a permutation the handle keeps -- song order lost to it when measured), lanes at SONG positions, the fold started from silence, every sample of the
 // window stored (zeros in a tile no event touches) through a pointer the host has biased by out_sample - first_sample, one 16-byte
 // vector per lane where the lane lies inside the window and the host found the biased base aligned.  sh_seq_render is that one launch and
 // copies nothing; a window of the song holds the bytes of that slice of the whole song, since every track sample is its own fold.
 // A song of TRACKS (sh_seq_create_tracks) is rendered by the BUS = true instantiations of the same three templates, a gain per track in
-// the kernel arguments (sh_seq_render_gains); with the metering bus, SeqBusM, the same launch also reduces one row of levels per track,
-// post-fader, and one for the master into a table the handle owns (sh_seq_render_meters; seqmeter.hpp).
+// the kernel arguments (sh_seq_render_gains): seq_runs, written once, walks the runs of the tile -- the kernel's schedule over a run's
+// events into a sub-mix, the sub-mix by its gain, a hook, the saturating add into the master.  With the metering bus, SeqBusM, the hook
+// reduces one row of levels per track, post-fader, and the same launch one for the master, into a table the handle owns
+// (sh_seq_render_meters; seqmeter.hpp); seq_window_bus is what a window kernel does with either bus.  On the host one launcher,
+// seq_window_launch, forwards the bus (none, SeqBus or SeqBusM) as the kernels' trailing pack, and seq_with_level turns the level a
+// handle holds into a template argument.
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
@@ -587,13 +594,18 @@ __device__ __forceinline__ short8v seq_event8(const typename SeqRec<LEVEL>::type
     return x;
 }
 
-// mul and add
-__device__ __forceinline__ void seq_fold8(short8v& acc, short8v x, const double factor) {
+// audioop.mul of a lane's samples: of an event's by its factor, of a folded track's by its gain
+__device__ __forceinline__ short8v seq_scale8(short8v x, const double factor) {
     if (factor != 1.0) {                                      // (uniform)
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = (short)fbound((double)x[j] * factor, Lim<short>::lo, Lim<short>::hi);
     }
-    acc = __builtin_elementwise_add_sat(acc, x);
+    return x;
+}
+
+// mul and add
+__device__ __forceinline__ void seq_fold8(short8v& acc, const short8v x, const double factor) {
+    acc = __builtin_elementwise_add_sat(acc, seq_scale8(x, factor));
 }
 
 // A lane's eight track samples: one aligned 16-byte load of the base, one aligned 16-byte store.  whole: the track starts on a 16-byte
@@ -612,21 +624,57 @@ __device__ __forceinline__ void seq_track_store8(short* track, uint32_t s0, uint
         for (uint32_t j = 0; j < 8 && s0 + j < track_samples; ++j) track[s0 + j] = acc[j];
 }
 
-// PLAIN at 16 bits: workgroup k folds active tile tiles[k].  INFLIGHT events' records (scalar loads, one batch ahead) and source vectors
-// are in flight before their muls and adds -- a schedule of its own, measured (profiles/sequence_ab.txt).
+// ---- widths 1, 3 and 4 ------------------------------------------------------------------------------------------------------------------
+// A lane's four 64-bit sums: a vector type, as short8v is, so that they pass through the schedule functions as one value in registers
+typedef long long llong4v __attribute__((ext_vector_type(4)));
+
+template <int WIDTH>
+__device__ __forceinline__ void seq_track_load_w(const unsigned char* track, uint32_t s0, uint32_t track_samples, llong4v& acc) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        acc[j] = 0;
+        if (s0 + j < track_samples) acc[j] = chain_get<WIDTH>(track, s0 + j);
+    }
+}
+
+template <int WIDTH>
+__device__ __forceinline__ void seq_track_store_w(unsigned char* track, uint32_t s0, uint32_t track_samples, const llong4v& acc) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (s0 + j < track_samples) chain_put<WIDTH>(track, s0 + j, acc[j]);
+}
+
+// mul and add of one sample, for an event (seq_fold_w) and for a track (seq_runs): x by the factor unless that is exactly 1.0 -- x is
+// left scaled --, then the clamped 64-bit add; the sum
+template <int WIDTH>
+__device__ __forceinline__ long long seq_mul_add_w(const long long acc, long long& x, const double factor) {
+    constexpr long long HI = SEQ_HI<WIDTH>, LO = SEQ_LO<WIDTH>;
+    if (factor != 1.0) x = fbound((double)x * factor, (double)LO, (double)HI);
+    const long long t = acc + x;
+    return t > HI ? HI : (t < LO ? LO : t);
+}
+
+// mul and add, where the event is; get(j, rel): what the event gives the lane's sample j, sample rel of the event
+template <int WIDTH, typename Get>
+__device__ __forceinline__ void seq_fold_w(llong4v& acc, const double factor, uint32_t s0, uint32_t dst, uint32_t n, Get get) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long rel = (long long)s0 + j - (long long)dst;
+        if (rel >= 0 && rel < (long long)n) {
+            long long x = get(j, rel);
+            acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, factor);
+        }
+    }
+}
+
+// ---- the schedules: events [e, e1) of idx folded into acc in list order, each written once -- the tile-list kernels call them over a
+// tile's events into the track's samples, the window kernels over a tile's events from silence or over a RUN's events into a track's
+// sub-mix (seq_runs) -----------------------------------------------------------------------------------------------------------------
+// PLAIN at 16 bits.  INFLIGHT events' records (scalar loads, one batch ahead) and source vectors are in flight before their muls and
+// adds, then a tail event by event -- a schedule of its own, measured (profiles/sequence_ab.txt).  [e, e1) may be empty.
 template <int SCHEME, int INFLIGHT>
-__global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_plain16(const SeqEv* __restrict__ ev, const she::Seg* __restrict__ segs,
-                                                                   const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ first,
-                                                                   const uint32_t* __restrict__ idx, uint32_t ntiles, short* track,
-                                                                   uint32_t track_samples, int aligned) {
-    const uint32_t k = (uint32_t)sh::block_id();
-    if (k >= ntiles) return;
-    const uint32_t t0 = tiles[k] * shq::TILE_I16, s0 = t0 + threadIdx.x * shq::LANE_SAMPLES_I16;
-    if (s0 >= track_samples) return;
-    const bool whole = aligned && s0 + 8 <= track_samples;
-    short8v acc = seq_track_load8(track, s0, track_samples, whole);
-    uint32_t e = first[k];
-    const uint32_t e1 = first[k + 1];
+__device__ __forceinline__ void seq_walk_plain16(const SeqEv* __restrict__ ev, const she::Seg* __restrict__ segs, const uint32_t* __restrict__ idx,
+                                                 uint32_t& e, const uint32_t e1, uint32_t t0, uint32_t s0, short8v& acc) {
     if (e1 - e >= INFLIGHT) {
         SeqEv c[INFLIGHT], nx[INFLIGHT];
 #pragma unroll
@@ -652,25 +700,14 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_plain16(const SeqEv* 
         const SeqEv c = ev[idx[e]];
         seq_fold8(acc, seq_event8<PLAIN, SCHEME>(c, segs, t0, s0), c.factor);
     }
-    seq_track_store8(track, s0, track_samples, whole, acc);
 }
 
-// RATE, PAN and ENV at 16 bits: the same tile, lane and fold.  One record ahead instead of INFLIGHT: a resampled event is sixteen
-// dependent-address loads and some forty instructions per sample, which is what there is to hide behind.
+// The other levels at 16 bits.  One record ahead instead of INFLIGHT: a resampled event is sixteen dependent-address loads and some forty
+// instructions per sample, which is what there is to hide behind.  e < e1: behind the last event idx holds nothing.
 template <int LEVEL, int SCHEME>
-__global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_16(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
-                                                              const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ first,
-                                                              const uint32_t* __restrict__ idx, uint32_t ntiles, short* track,
-                                                              uint32_t track_samples, int aligned) {
+__device__ __forceinline__ void seq_walk_16(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
+                                            const uint32_t* __restrict__ idx, uint32_t& e, const uint32_t e1, uint32_t t0, uint32_t s0, short8v& acc) {
     typedef typename SeqRec<LEVEL>::type Rec;
-    const uint32_t k = (uint32_t)sh::block_id();
-    if (k >= ntiles) return;
-    const uint32_t t0 = tiles[k] * shq::TILE_I16, s0 = t0 + threadIdx.x * shq::LANE_SAMPLES_I16;
-    if (s0 >= track_samples) return;
-    const bool whole = aligned && s0 + 8 <= track_samples;
-    short8v acc = seq_track_load8(track, s0, track_samples, whole);
-    uint32_t e = first[k];
-    const uint32_t e1 = first[k + 1];
     if constexpr (LEVEL >= LOOP) {
         // LOOP is where the scalar registers run out: with a whole record held ahead the allocator spilled (read in the ISA).  The INDEX
         // of the next record is held ahead instead, so one scalar load of the two is still hidden.
@@ -680,67 +717,21 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_16(const typename Seq
             if (++e < e1) ni = idx[e];
             seq_fold8(acc, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
         }
-        seq_track_store8(track, s0, track_samples, whole, acc);
-        return;
-    }
-    Rec nx = ev[idx[e]];                                      // (an active tile lists at least one event)
-    while (e < e1) {
-        const Rec c = nx;
-        if (++e < e1) nx = ev[idx[e]];
-        seq_fold8(acc, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
-    }
-    seq_track_store8(track, s0, track_samples, whole, acc);
-}
-
-// ---- widths 1, 3 and 4 ------------------------------------------------------------------------------------------------------------------
-template <int WIDTH>
-__device__ __forceinline__ void seq_track_load_w(const unsigned char* track, uint32_t s0, uint32_t track_samples, long long (&acc)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        acc[j] = 0;
-        if (s0 + j < track_samples) acc[j] = chain_get<WIDTH>(track, s0 + j);
-    }
-}
-
-template <int WIDTH>
-__device__ __forceinline__ void seq_track_store_w(unsigned char* track, uint32_t s0, uint32_t track_samples, const long long (&acc)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (s0 + j < track_samples) chain_put<WIDTH>(track, s0 + j, acc[j]);
-}
-
-// mul and add, where the event is; get(j, rel): what the event gives the lane's sample j, sample rel of the event
-template <int WIDTH, typename Get>
-__device__ __forceinline__ void seq_fold_w(long long (&acc)[4], const double factor, uint32_t s0, uint32_t dst, uint32_t n, Get get) {
-    constexpr long long HI = SEQ_HI<WIDTH>, LO = SEQ_LO<WIDTH>;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const long long rel = (long long)s0 + j - (long long)dst;
-        if (rel >= 0 && rel < (long long)n) {
-            long long x = get(j, rel);
-            if (factor != 1.0) x = fbound((double)x * factor, (double)LO, (double)HI);
-            const long long t = acc[j] + x;
-            acc[j] = t > HI ? HI : (t < LO ? LO : t);
+    } else {
+        Rec nx = ev[idx[e]];
+        while (e < e1) {
+            const Rec c = nx;
+            if (++e < e1) nx = ev[idx[e]];
+            seq_fold8(acc, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
         }
     }
 }
 
-// Every level at widths 1, 3 and 4: the reference's loop as it stands, event by event.  An envelope has widths 1, 2 and 4 (upstream's
-// fades have no 24-bit form).
+// Every level at widths 1, 3 and 4: the reference's loop as it stands, event by event.  [e, e1) may be empty.
 template <int LEVEL, int WIDTH>
-__global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_w(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
-                                                             const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ first,
-                                                             const uint32_t* __restrict__ idx, uint32_t ntiles, unsigned char* track,
-                                                             uint32_t track_samples) {
-    static_assert(LEVEL != ENV || WIDTH == 1 || WIDTH == 4, "an envelope has widths 1, 2 and 4");
-    const uint32_t k = (uint32_t)sh::block_id();
-    if (k >= ntiles) return;
-    const uint32_t t0 = tiles[k] * shq::TILE_W, s0 = t0 + threadIdx.x * shq::LANE_SAMPLES_W;
-    if (s0 >= track_samples) return;
-    long long acc[4];
-    seq_track_load_w<WIDTH>(track, s0, track_samples, acc);
-    const uint32_t e1 = first[k + 1];
-    for (uint32_t e = first[k]; e < e1; ++e) {
+__device__ __forceinline__ void seq_walk_w(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
+                                           const uint32_t* __restrict__ idx, uint32_t& e, const uint32_t e1, uint32_t t0, uint32_t s0, llong4v& acc) {
+    for (; e < e1; ++e) {
         const typename SeqRec<LEVEL>::type c = ev[idx[e]];
         if constexpr (LEVEL == PLAIN) {                        // fetched inside the fold, sample by sample, by chain_get on the generic pointer
             const unsigned char* src = (const unsigned char*)c.src;
@@ -751,6 +742,58 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_w(const typename SeqR
             seq_fold_w<WIDTH>(acc, c.factor, s0, c.dst, c.n, [&](int j, long long) { return (long long)v[j]; });
         }
     }
+}
+
+// ---- the tile-list kernels (sh_mix_events*): workgroup k folds active tile tiles[k] into the track ------------------------------------------
+// PLAIN at 16 bits
+template <int SCHEME, int INFLIGHT>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_plain16(const SeqEv* __restrict__ ev, const she::Seg* __restrict__ segs,
+                                                                   const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ first,
+                                                                   const uint32_t* __restrict__ idx, uint32_t ntiles, short* track,
+                                                                   uint32_t track_samples, int aligned) {
+    const uint32_t k = (uint32_t)sh::block_id();
+    if (k >= ntiles) return;
+    const uint32_t t0 = tiles[k] * shq::TILE_I16, s0 = t0 + threadIdx.x * shq::LANE_SAMPLES_I16;
+    if (s0 >= track_samples) return;
+    const bool whole = aligned && s0 + 8 <= track_samples;
+    short8v acc = seq_track_load8(track, s0, track_samples, whole);
+    uint32_t e = first[k];
+    seq_walk_plain16<SCHEME, INFLIGHT>(ev, segs, idx, e, first[k + 1], t0, s0, acc);
+    seq_track_store8(track, s0, track_samples, whole, acc);
+}
+
+// RATE to CHAN at 16 bits: the same tile, lane and fold
+template <int LEVEL, int SCHEME>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_16(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
+                                                              const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ first,
+                                                              const uint32_t* __restrict__ idx, uint32_t ntiles, short* track,
+                                                              uint32_t track_samples, int aligned) {
+    const uint32_t k = (uint32_t)sh::block_id();
+    if (k >= ntiles) return;
+    const uint32_t t0 = tiles[k] * shq::TILE_I16, s0 = t0 + threadIdx.x * shq::LANE_SAMPLES_I16;
+    if (s0 >= track_samples) return;
+    const bool whole = aligned && s0 + 8 <= track_samples;
+    short8v acc = seq_track_load8(track, s0, track_samples, whole);
+    uint32_t e = first[k];
+    seq_walk_16<LEVEL, SCHEME>(ev, segs, idx, e, first[k + 1], t0, s0, acc);      // (an active tile lists at least one event)
+    seq_track_store8(track, s0, track_samples, whole, acc);
+}
+
+// Every level at widths 1, 3 and 4.  An envelope has widths 1, 2 and 4 (upstream's fades have no 24-bit form).
+template <int LEVEL, int WIDTH>
+__global__ __launch_bounds__(shq::TILE_THREADS) void k_seq_w(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
+                                                             const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ first,
+                                                             const uint32_t* __restrict__ idx, uint32_t ntiles, unsigned char* track,
+                                                             uint32_t track_samples) {
+    static_assert(LEVEL != ENV || WIDTH == 1 || WIDTH == 4, "an envelope has widths 1, 2 and 4");
+    const uint32_t k = (uint32_t)sh::block_id();
+    if (k >= ntiles) return;
+    const uint32_t t0 = tiles[k] * shq::TILE_W, s0 = t0 + threadIdx.x * shq::LANE_SAMPLES_W;
+    if (s0 >= track_samples) return;
+    llong4v acc;
+    seq_track_load_w<WIDTH>(track, s0, track_samples, acc);
+    uint32_t e = first[k];
+    seq_walk_w<LEVEL, WIDTH>(ev, segs, idx, e, first[k + 1], t0, s0, acc);
     seq_track_store_w<WIDTH>(track, s0, track_samples, acc);
 }
 
@@ -777,19 +820,33 @@ __device__ __forceinline__ void seq_window_store8(short* out, uint32_t s0, uint3
     }
 }
 
+template <int WIDTH>
+__device__ __forceinline__ void seq_window_store_w(unsigned char* out, uint32_t s0, uint32_t lo, uint32_t hi, const llong4v& acc) {
+    unsigned char* p = out + (size_t)WIDTH * s0;             // (the biased base, as seq_window_store8's: valid at samples [lo, hi) alone)
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j)
+        if (s0 + j >= lo && s0 + j < hi) chain_put<WIDTH>(p, j, acc[j]);
+}
+
 // the song tile of workgroup k of a window that starts at sample lo, or false: a workgroup beyond the window (a grid folded into two
-// dimensions has some) or a lane none of whose samples lie in [lo, hi)
+// dimensions has some)
 // order: NULL, or -- a window that is the whole song (lo == 0, hi the song's length) -- the song's tiles heaviest first, as shq::plan has
 // them: workgroup k folds tile order[k], so that a pile-up is not the last workgroup to start.
 template <int WIDTH>
-__device__ __forceinline__ bool seq_window_lane(const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, uint32_t& tile, uint32_t& t0, uint32_t& s0) {
+__device__ __forceinline__ bool seq_window_tile(const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, uint32_t& tile, uint32_t& t0, uint32_t& s0) {
     uint64_t t = (uint64_t)(lo / SEQ_TILE<WIDTH>) + sh::block_id();
     if (t * SEQ_TILE<WIDTH> >= hi) return false;              // (uniform; the whole song: workgroup k of ceil(hi / TILE))
     if (order) t = order[t];                                  // (uniform)
     tile = (uint32_t)t;
     t0 = tile * SEQ_TILE<WIDTH>;
     s0 = t0 + threadIdx.x * SEQ_LANE<WIDTH>;
-    return s0 < hi && s0 + SEQ_LANE<WIDTH> > lo;              // (no wrap: MAX_TRACK_SAMPLES)
+    return true;
+}
+
+// and false as well for a lane none of whose samples lie in [lo, hi)
+template <int WIDTH>
+__device__ __forceinline__ bool seq_window_lane(const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, uint32_t& tile, uint32_t& t0, uint32_t& s0) {
+    return seq_window_tile<WIDTH>(order, lo, hi, tile, t0, s0) && s0 < hi && s0 + SEQ_LANE<WIDTH> > lo;       // (no wrap: MAX_TRACK_SAMPLES)
 }
 
 // ---- a song made of tracks (sh_seq_create_tracks, sh_seq_render_gains): BUS = true ------------------------------------------------------
@@ -798,8 +855,9 @@ __device__ __forceinline__ bool seq_window_lane(const uint32_t* __restrict__ ord
 // fbound(x * 0.0) is 0 and adding 0 is the identity) and added, saturating, into the master in track order.  A bus lane keeps two
 // accumulators: acc, the master, and sub, the current track.  Its tile's slice of idx is cut into RUNS (shq::plan_runs): one per track
 // with events there, in track order, so the lane folds [e, run.end) into sub with the schedule of the kernel it mirrors and then sub into
-// acc -- which is seq_fold8 / seq_fold_w's own mul and add again, one level up.  The gains come BY VALUE in the kernel arguments, read at
-// a wave-uniform index by scalar loads from the kernel-argument segment (read in the ISA: no scratch): a render uploads nothing.
+// acc -- which is seq_fold8 / seq_mul_add_w's own mul and add again, one level up (seq_runs).  The gains come BY VALUE in the kernel
+// arguments, read at a wave-uniform index by scalar loads from the kernel-argument segment (read in the ISA: no scratch): a render
+// uploads nothing.
 struct SeqGains { double g[shq::MAX_TRACKS]; };
 struct SeqBus {
     const uint32_t* rfirst;               // ntiles + 1 offsets into runs
@@ -808,8 +866,44 @@ struct SeqBus {
 };
 // The window templates take the bus as a trailing parameter PACK -- empty for BUS = false, whose kernels so keep the argument list, the
 // kernel-argument offsets and the instructions they had; one SeqBus for BUS = true.
-__device__ __forceinline__ const SeqBus& seq_bus(const SeqBus& b) { return b; }
 static_assert(sizeof(shq::Run) == 8 && sizeof(SeqGains) == 256, "a run is one 8-byte scalar load, the gains 256 bytes of kernel arguments");
+
+// a lane's accumulator: eight packed samples at 16 bits, four 64-bit sums at the other widths
+template <int WIDTH> struct SeqAcc { typedef llong4v type; };
+template <> struct SeqAcc<2> { typedef short8v type; };
+
+// The runs of tile k, written once for the three templates and both buses: the events from e on, run by run.  walk(e, e1, sub): the
+// schedule of the kernel, events [e, e1) into sub; hook(sub, track): what else a bus does with a track's post-fader samples (the metering
+// bus: its row).  Everything about a run is uniform, and a run lists at least one event.
+template <int WIDTH, typename Walk, typename Hook>
+__device__ __forceinline__ void seq_runs(const SeqBus& bus, uint32_t k, uint32_t e, typename SeqAcc<WIDTH>::type& acc, Walk walk, Hook hook) {
+    const uint32_t r1 = bus.rfirst[k + 1];
+    for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {
+        const shq::Run run = bus.runs[r];
+        const double g = bus.gains.g[run.track];
+        if (g == 0.0) {
+            e = run.end;
+            continue;
+        }
+        if constexpr (WIDTH == 2) {
+            short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
+            walk(e, run.end, sub);
+            sub = seq_scale8(sub, g);                         // post-fader: what the master takes of the track
+            hook(sub, run.track);
+            acc = __builtin_elementwise_add_sat(acc, sub);
+        } else {
+            llong4v sub = {0, 0, 0, 0};
+            walk(e, run.end, sub);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                long long x = sub[j];
+                acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, g);
+                sub[j] = x;
+            }
+            hook(sub, run.track);
+        }
+    }
+}
 
 // ---- level meters from the same launch (sh_seq_render_meters): a second bus type, SeqBusM ------------------------------------------------
 // A metered render stores the bytes of the render with gains and, from the values the lane holds anyway, one row of levels (seqmeter.hpp:
@@ -827,21 +921,8 @@ struct SeqBusM : SeqBus {
     shmt::Row* meters;                     // ntracks + 1 rows, zeroed on the stream in front of the launch; row ntracks: the master
     uint32_t  ntracks, nch;               // nch: the song's channels (2: sample s is channel s & 1; otherwise all are channel 0)
 };
-__device__ __forceinline__ const SeqBusM& seq_bus(const SeqBusM& b) { return b; }
 template <typename... Bus> struct SeqMetered : std::false_type {};
 template <> struct SeqMetered<SeqBusM> : std::true_type {};
-
-// seq_window_lane without the lane: false for a whole workgroup alone
-template <int WIDTH>
-__device__ __forceinline__ bool seq_window_tile(const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, uint32_t& tile, uint32_t& t0, uint32_t& s0) {
-    uint64_t t = (uint64_t)(lo / SEQ_TILE<WIDTH>) + sh::block_id();
-    if (t * SEQ_TILE<WIDTH> >= hi) return false;              // (uniform)
-    if (order) t = order[t];                                  // (uniform)
-    tile = (uint32_t)t;
-    t0 = tile * SEQ_TILE<WIDTH>;
-    s0 = t0 + threadIdx.x * SEQ_LANE<WIDTH>;
-    return true;
-}
 
 // the workgroup's row table, zeroed: every lane of the workgroup calls it (a barrier)
 __device__ __forceinline__ shmt::Row* seq_meter_begin() {
@@ -896,251 +977,85 @@ __device__ __forceinline__ void seq_meter_end(const shmt::Row* table, const SeqB
     if (WIDE) atomicAdd(reinterpret_cast<unsigned long long*>(&g->sq_hi[c]), (unsigned long long)table[row].sq_hi[c]);
 }
 
-// audioop.mul of a folded track by its gain, as seq_fold8 forms it in front of its add
-__device__ __forceinline__ short8v seq_scale8(short8v x, const double factor) {
-    if (factor != 1.0) {                                      // (uniform)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = (short)fbound((double)x[j] * factor, Lim<short>::lo, Lim<short>::hi);
-    }
-    return x;
+// What a window kernel does where it has a bus, once for the three templates: the runs of tile k into acc, then store().  The plain bus:
+// a lane that seq_window_lane kept.  s0, lo and hi, which only the metering bus needs, are ignored: one call serves both overloads.
+template <int WIDTH, typename Walk, typename Store>
+__device__ __forceinline__ void seq_window_bus(const SeqBus& bus, uint32_t k, uint32_t e, uint32_t, uint32_t, uint32_t,
+                                               typename SeqAcc<WIDTH>::type& acc, Walk walk, Store store) {
+    seq_runs<WIDTH>(bus, k, e, acc, walk, [](const typename SeqAcc<WIDTH>::type&, uint32_t) {});
+    store();
 }
 
-// PLAIN at 16 bits: k_seq_plain16's schedule, INFLIGHT records and source vectors in flight
+// The metering bus: EVERY lane of a workgroup that seq_window_tile kept, the rows of the tracks from seq_runs' hook and the master's row
+// in front of the store, the table's barriers around everything.
+template <int WIDTH, typename Walk, typename Store>
+__device__ __forceinline__ void seq_window_bus(const SeqBusM& bus, uint32_t k, uint32_t e, uint32_t s0, uint32_t lo, uint32_t hi,
+                                               typename SeqAcc<WIDTH>::type& acc, Walk walk, Store store) {
+    constexpr bool WIDE = WIDTH >= 3;
+    constexpr int N = SEQ_LANE<WIDTH>;
+    shmt::Row* table = seq_meter_begin();
+    const bool stereo = bus.nch == 2;
+    if (__builtin_amdgcn_ballot_w64(s0 < hi && s0 + N > lo)) {                    // (uniform: a wave with a lane in the window)
+        seq_runs<WIDTH>(bus, k, e, acc, walk, [&](const typename SeqAcc<WIDTH>::type& sub, uint32_t track) {
+            seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(sub, s0, lo, hi, bus.nch), stereo, table + track);
+        });
+        seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
+        store();
+    }
+    seq_meter_end<WIDE>(table, bus);
+}
+
+// PLAIN at 16 bits: k_seq_plain16's schedule
 template <int SCHEME, int INFLIGHT, bool BUS = false, typename... Bus>
 __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_plain16(const SeqEv* __restrict__ ev, const she::Seg* __restrict__ segs,
                                                                    const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
                                                                    const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, short* out, int aligned,
-                                                                   const Bus... bus_arg) {
+                                                                   const Bus... bus) {
     static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
-    constexpr bool METER = SeqMetered<Bus...>::value;
     uint32_t k, t0, s0;
-    if constexpr (METER) {
+    if constexpr (SeqMetered<Bus...>::value) {
         if (!seq_window_tile<2>(order, lo, hi, k, t0, s0)) return;
     } else {
         if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
     }
     const bool whole = aligned && s0 >= lo && s0 + 8 <= hi;
     short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto walk = [&](uint32_t& e, uint32_t e1, short8v& into) { seq_walk_plain16<SCHEME, INFLIGHT>(ev, segs, idx, e, e1, t0, s0, into); };
+    auto store = [&] { seq_window_store8(out, s0, lo, hi, whole, acc); };
     uint32_t e = first[k];
-    if constexpr (METER) {
-        const SeqBusM& bus = seq_bus(bus_arg...);
-        shmt::Row* table = seq_meter_begin();
-        const bool stereo = bus.nch == 2;
-        if (__builtin_amdgcn_ballot_w64(s0 < hi && s0 + 8 > lo)) {                // (uniform: a wave with a lane in the window)
-            const uint32_t r1 = bus.rfirst[k + 1];
-            for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {   // the runs as below
-                const shq::Run run = bus.runs[r];
-                const double g = bus.gains.g[run.track];
-                const uint32_t e1 = run.end;
-                if (g == 0.0) { e = e1; continue; }
-                short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
-                if (e1 - e >= INFLIGHT) {
-                    SeqEv c[INFLIGHT], nx[INFLIGHT];
-#pragma unroll
-                    for (int u = 0; u < INFLIGHT; ++u) c[u] = ev[idx[e + u]];
-                    for (; e + INFLIGHT <= e1; e += INFLIGHT) {
-                        const bool more = e + 2 * INFLIGHT <= e1;
-                        if (more) {
-#pragma unroll
-                            for (int u = 0; u < INFLIGHT; ++u) nx[u] = ev[idx[e + INFLIGHT + u]];
-                        }
-                        short8v x[INFLIGHT];
-#pragma unroll
-                        for (int u = 0; u < INFLIGHT; ++u) x[u] = seq_event8<PLAIN, SCHEME>(c[u], segs, t0, s0);
-#pragma unroll
-                        for (int u = 0; u < INFLIGHT; ++u) seq_fold8(sub, x[u], c[u].factor);
-                        if (more) {
-#pragma unroll
-                            for (int u = 0; u < INFLIGHT; ++u) c[u] = nx[u];
-                        }
-                    }
-                }
-                for (; e < e1; ++e) {
-                    const SeqEv c = ev[idx[e]];
-                    seq_fold8(sub, seq_event8<PLAIN, SCHEME>(c, segs, t0, s0), c.factor);
-                }
-                sub = seq_scale8(sub, g);                     // post-fader: what the master takes of the track
-                seq_meter_wave<false>(shmt::lane<false, 8>(sub, s0, lo, hi, bus.nch), stereo, table + run.track);
-                acc = __builtin_elementwise_add_sat(acc, sub);
-            }
-            seq_meter_wave<false>(shmt::lane<false, 8>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
-            seq_window_store8(out, s0, lo, hi, whole, acc);
-        }
-        seq_meter_end<false>(table, bus);
-        return;
-    }
     if constexpr (BUS) {
-        const SeqBus& bus = seq_bus(bus_arg...);
-        const uint32_t r1 = bus.rfirst[k + 1];
-        for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {       // (everything about a run is uniform)
-            const shq::Run run = bus.runs[r];
-            const double g = bus.gains.g[run.track];
-            const uint32_t e1 = run.end;
-            if (g == 0.0) { e = e1; continue; }
-            short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (e1 - e >= INFLIGHT) {
-                SeqEv c[INFLIGHT], nx[INFLIGHT];
-#pragma unroll
-                for (int u = 0; u < INFLIGHT; ++u) c[u] = ev[idx[e + u]];
-                for (; e + INFLIGHT <= e1; e += INFLIGHT) {
-                    const bool more = e + 2 * INFLIGHT <= e1;
-                    if (more) {
-#pragma unroll
-                        for (int u = 0; u < INFLIGHT; ++u) nx[u] = ev[idx[e + INFLIGHT + u]];
-                    }
-                    short8v x[INFLIGHT];
-#pragma unroll
-                    for (int u = 0; u < INFLIGHT; ++u) x[u] = seq_event8<PLAIN, SCHEME>(c[u], segs, t0, s0);
-#pragma unroll
-                    for (int u = 0; u < INFLIGHT; ++u) seq_fold8(sub, x[u], c[u].factor);
-                    if (more) {
-#pragma unroll
-                        for (int u = 0; u < INFLIGHT; ++u) c[u] = nx[u];
-                    }
-                }
-            }
-            for (; e < e1; ++e) {
-                const SeqEv c = ev[idx[e]];
-                seq_fold8(sub, seq_event8<PLAIN, SCHEME>(c, segs, t0, s0), c.factor);
-            }
-            seq_fold8(acc, sub, g);                           // the track into the master: its gain, then the saturating add
-        }
-        seq_window_store8(out, s0, lo, hi, whole, acc);
-        return;
+        seq_window_bus<2>(bus..., k, e, s0, lo, hi, acc, walk, store);
+    } else {
+        walk(e, first[k + 1], acc);
+        store();
     }
-    const uint32_t e1 = first[k + 1];
-    if (e1 - e >= INFLIGHT) {
-        SeqEv c[INFLIGHT], nx[INFLIGHT];
-#pragma unroll
-        for (int u = 0; u < INFLIGHT; ++u) c[u] = ev[idx[e + u]];
-        for (; e + INFLIGHT <= e1; e += INFLIGHT) {
-            const bool more = e + 2 * INFLIGHT <= e1;
-            if (more) {
-#pragma unroll
-                for (int u = 0; u < INFLIGHT; ++u) nx[u] = ev[idx[e + INFLIGHT + u]];
-            }
-            short8v x[INFLIGHT];
-#pragma unroll
-            for (int u = 0; u < INFLIGHT; ++u) x[u] = seq_event8<PLAIN, SCHEME>(c[u], segs, t0, s0);
-#pragma unroll
-            for (int u = 0; u < INFLIGHT; ++u) seq_fold8(acc, x[u], c[u].factor);
-            if (more) {
-#pragma unroll
-                for (int u = 0; u < INFLIGHT; ++u) c[u] = nx[u];
-            }
-        }
-    }
-    for (; e < e1; ++e) {
-        const SeqEv c = ev[idx[e]];
-        seq_fold8(acc, seq_event8<PLAIN, SCHEME>(c, segs, t0, s0), c.factor);
-    }
-    seq_window_store8(out, s0, lo, hi, whole, acc);
 }
 
-// The other levels at 16 bits: k_seq_16's schedule, one record ahead, from LOOP on the next record's index.  An idle tile reads neither:
-// behind the last event idx holds nothing.
+// The other levels at 16 bits: k_seq_16's schedule.  An idle tile reads neither record nor index: behind the last event idx holds nothing.
 template <int LEVEL, int SCHEME, bool BUS = false, typename... Bus>
 __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_16(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
                                                               const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
                                                               const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, short* out, int aligned,
-                                                              const Bus... bus_arg) {
+                                                              const Bus... bus) {
     static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
-    typedef typename SeqRec<LEVEL>::type Rec;
-    constexpr bool METER = SeqMetered<Bus...>::value;
     uint32_t k, t0, s0;
-    if constexpr (METER) {
+    if constexpr (SeqMetered<Bus...>::value) {
         if (!seq_window_tile<2>(order, lo, hi, k, t0, s0)) return;
     } else {
         if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
     }
     const bool whole = aligned && s0 >= lo && s0 + 8 <= hi;
     short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto walk = [&](uint32_t& e, uint32_t e1, short8v& into) { seq_walk_16<LEVEL, SCHEME>(ev, segs, idx, e, e1, t0, s0, into); };
+    auto store = [&] { seq_window_store8(out, s0, lo, hi, whole, acc); };
     uint32_t e = first[k];
-    if constexpr (METER) {
-        const SeqBusM& bus = seq_bus(bus_arg...);
-        shmt::Row* table = seq_meter_begin();
-        const bool stereo = bus.nch == 2;
-        if (__builtin_amdgcn_ballot_w64(s0 < hi && s0 + 8 > lo)) {                // (uniform: a wave with a lane in the window)
-            const uint32_t r1 = bus.rfirst[k + 1];
-            for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {   // the runs as below
-                const shq::Run run = bus.runs[r];
-                const double g = bus.gains.g[run.track];
-                const uint32_t e1 = run.end;
-                if (g == 0.0) { e = e1; continue; }
-                short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
-                if constexpr (LEVEL >= LOOP) {
-                    uint32_t ni = idx[e];
-                    while (e < e1) {
-                        const Rec c = ev[ni];
-                        if (++e < e1) ni = idx[e];
-                        seq_fold8(sub, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
-                    }
-                } else {
-                    Rec nx = ev[idx[e]];
-                    while (e < e1) {
-                        const Rec c = nx;
-                        if (++e < e1) nx = ev[idx[e]];
-                        seq_fold8(sub, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
-                    }
-                }
-                sub = seq_scale8(sub, g);
-                seq_meter_wave<false>(shmt::lane<false, 8>(sub, s0, lo, hi, bus.nch), stereo, table + run.track);
-                acc = __builtin_elementwise_add_sat(acc, sub);
-            }
-            seq_meter_wave<false>(shmt::lane<false, 8>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
-            seq_window_store8(out, s0, lo, hi, whole, acc);
-        }
-        seq_meter_end<false>(table, bus);
-        return;
-    }
     if constexpr (BUS) {
-        const SeqBus& bus = seq_bus(bus_arg...);
-        const uint32_t r1 = bus.rfirst[k + 1];
-        for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {       // (uniform; a run lists at least one event)
-            const shq::Run run = bus.runs[r];
-            const double g = bus.gains.g[run.track];
-            const uint32_t e1 = run.end;
-            if (g == 0.0) { e = e1; continue; }
-            short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
-            if constexpr (LEVEL >= LOOP) {
-                uint32_t ni = idx[e];
-                while (e < e1) {
-                    const Rec c = ev[ni];
-                    if (++e < e1) ni = idx[e];
-                    seq_fold8(sub, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
-                }
-            } else {
-                Rec nx = ev[idx[e]];
-                while (e < e1) {
-                    const Rec c = nx;
-                    if (++e < e1) nx = ev[idx[e]];
-                    seq_fold8(sub, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
-                }
-            }
-            seq_fold8(acc, sub, g);
-        }
-        seq_window_store8(out, s0, lo, hi, whole, acc);
-        return;
+        seq_window_bus<2>(bus..., k, e, s0, lo, hi, acc, walk, store);
+    } else {
+        const uint32_t e1 = first[k + 1];
+        if (e < e1) walk(e, e1, acc);                         // (uniform)
+        store();
     }
-    const uint32_t e1 = first[k + 1];
-    if (e < e1) {                                             // (uniform)
-        if constexpr (LEVEL >= LOOP) {
-            uint32_t ni = idx[e];
-            while (e < e1) {
-                const Rec c = ev[ni];
-                if (++e < e1) ni = idx[e];
-                seq_fold8(acc, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
-            }
-        } else {
-            Rec nx = ev[idx[e]];
-            while (e < e1) {
-                const Rec c = nx;
-                if (++e < e1) nx = ev[idx[e]];
-                seq_fold8(acc, seq_event8<LEVEL, SCHEME>(c, segs, t0, s0), c.factor);
-            }
-        }
-    }
-    seq_window_store8(out, s0, lo, hi, whole, acc);
 }
 
 // Widths 1, 3 and 4: k_seq_w's loop from silence, every sample of the lane that lies in the window stored
@@ -1148,110 +1063,25 @@ template <int LEVEL, int WIDTH, bool BUS = false, typename... Bus>
 __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_w(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
                                                              const uint32_t* __restrict__ first, const uint32_t* __restrict__ idx,
                                                              const uint32_t* __restrict__ order, uint32_t lo, uint32_t hi, unsigned char* out,
-                                                             const Bus... bus_arg) {
+                                                             const Bus... bus) {
     static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
     static_assert(LEVEL != ENV || WIDTH == 1 || WIDTH == 4, "an envelope has widths 1, 2 and 4");
-    constexpr bool METER = SeqMetered<Bus...>::value;
     uint32_t k, t0, s0;
-    if constexpr (METER) {
+    if constexpr (SeqMetered<Bus...>::value) {
         if (!seq_window_tile<WIDTH>(order, lo, hi, k, t0, s0)) return;
     } else {
         if (!seq_window_lane<WIDTH>(order, lo, hi, k, t0, s0)) return;
     }
-    long long acc[4] = {0, 0, 0, 0};
-    if constexpr (METER) {
-        constexpr long long HI = SEQ_HI<WIDTH>, LO = SEQ_LO<WIDTH>;
-        constexpr bool WIDE = WIDTH >= 3;
-        const SeqBusM& bus = seq_bus(bus_arg...);
-        shmt::Row* table = seq_meter_begin();
-        const bool stereo = bus.nch == 2;
-        if (__builtin_amdgcn_ballot_w64(s0 < hi && s0 + 4 > lo)) {                // (uniform: a wave with a lane in the window)
-            uint32_t e = first[k];
-            const uint32_t r1 = bus.rfirst[k + 1];
-            for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {   // the runs as below
-                const shq::Run run = bus.runs[r];
-                const double g = bus.gains.g[run.track];
-                if (g == 0.0) { e = run.end; continue; }
-                long long sub[4] = {0, 0, 0, 0};
-                for (; e < run.end; ++e) {
-                    const typename SeqRec<LEVEL>::type c = ev[idx[e]];
-                    if constexpr (LEVEL == PLAIN) {
-                        const unsigned char* src = (const unsigned char*)c.src;
-                        seq_fold_w<WIDTH>(sub, c.factor, s0, c.dst, c.n, [&](int, long long rel) { return chain_get<WIDTH>(src, (size_t)rel); });
-                    } else {
-                        int v[4];
-                        seq_event<LEVEL, WIDTH, FUNNEL>(c, segs, t0, s0, v);
-                        seq_fold_w<WIDTH>(sub, c.factor, s0, c.dst, c.n, [&](int j, long long) { return (long long)v[j]; });
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (g != 1.0) sub[j] = fbound((double)sub[j] * g, (double)LO, (double)HI);       // post-fader
-                    const long long t = acc[j] + sub[j];
-                    acc[j] = t > HI ? HI : (t < LO ? LO : t);
-                }
-                seq_meter_wave<WIDE>(shmt::lane<WIDE, 4>(sub, s0, lo, hi, bus.nch), stereo, table + run.track);
-            }
-            seq_meter_wave<WIDE>(shmt::lane<WIDE, 4>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
-            unsigned char* p = out + (size_t)WIDTH * s0;
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j)
-                if (s0 + j >= lo && s0 + j < hi) chain_put<WIDTH>(p, j, acc[j]);
-        }
-        seq_meter_end<WIDE>(table, bus);
-        return;
-    }
+    llong4v acc = {0, 0, 0, 0};
+    auto walk = [&](uint32_t& e, uint32_t e1, llong4v& into) { seq_walk_w<LEVEL, WIDTH>(ev, segs, idx, e, e1, t0, s0, into); };
+    auto store = [&] { seq_window_store_w<WIDTH>(out, s0, lo, hi, acc); };
+    uint32_t e = first[k];
     if constexpr (BUS) {
-        constexpr long long HI = SEQ_HI<WIDTH>, LO = SEQ_LO<WIDTH>;
-        uint32_t e = first[k];
-        const SeqBus& bus = seq_bus(bus_arg...);
-        const uint32_t r1 = bus.rfirst[k + 1];
-        for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {       // (uniform)
-            const shq::Run run = bus.runs[r];
-            const double g = bus.gains.g[run.track];
-            if (g == 0.0) { e = run.end; continue; }
-            long long sub[4] = {0, 0, 0, 0};
-            for (; e < run.end; ++e) {
-                const typename SeqRec<LEVEL>::type c = ev[idx[e]];
-                if constexpr (LEVEL == PLAIN) {
-                    const unsigned char* src = (const unsigned char*)c.src;
-                    seq_fold_w<WIDTH>(sub, c.factor, s0, c.dst, c.n, [&](int, long long rel) { return chain_get<WIDTH>(src, (size_t)rel); });
-                } else {
-                    int v[4];
-                    seq_event<LEVEL, WIDTH, FUNNEL>(c, segs, t0, s0, v);
-                    seq_fold_w<WIDTH>(sub, c.factor, s0, c.dst, c.n, [&](int j, long long) { return (long long)v[j]; });
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {                     // the track into the master: seq_fold_w's mul and add over the whole lane
-                long long x = sub[j];
-                if (g != 1.0) x = fbound((double)x * g, (double)LO, (double)HI);
-                const long long t = acc[j] + x;
-                acc[j] = t > HI ? HI : (t < LO ? LO : t);
-            }
-        }
-        unsigned char* p = out + (size_t)WIDTH * s0;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j)
-            if (s0 + j >= lo && s0 + j < hi) chain_put<WIDTH>(p, j, acc[j]);
-        return;
+        seq_window_bus<WIDTH>(bus..., k, e, s0, lo, hi, acc, walk, store);
+    } else {
+        walk(e, first[k + 1], acc);
+        store();
     }
-    const uint32_t e1 = first[k + 1];
-    for (uint32_t e = first[k]; e < e1; ++e) {
-        const typename SeqRec<LEVEL>::type c = ev[idx[e]];
-        if constexpr (LEVEL == PLAIN) {
-            const unsigned char* src = (const unsigned char*)c.src;
-            seq_fold_w<WIDTH>(acc, c.factor, s0, c.dst, c.n, [&](int, long long rel) { return chain_get<WIDTH>(src, (size_t)rel); });
-        } else {
-            int v[4];
-            seq_event<LEVEL, WIDTH, FUNNEL>(c, segs, t0, s0, v);
-            seq_fold_w<WIDTH>(acc, c.factor, s0, c.dst, c.n, [&](int j, long long) { return (long long)v[j]; });
-        }
-    }
-    unsigned char* p = out + (size_t)WIDTH * s0;             // (the biased base, as seq_window_store8's: valid at samples [lo, hi) alone)
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j)
-        if (s0 + j >= lo && s0 + j < hi) chain_put<WIDTH>(p, j, acc[j]);
 }
 
 }  // namespace
@@ -1327,6 +1157,36 @@ struct SeqIn {
     // src_frames counts virtual frames
     uint64_t region_frames() const { return loop_frames ? loop_start + loop_frames : src_frames; }
 };
+
+// sh_mix_event_chan as a SeqIn, and sh_mix_event_rev, _loop and _env, whose fields are its first ones, for the fields they have
+template <typename Ev>
+SeqIn seq_in(const Ev& m, int nchannels) {
+    SeqIn v{m.dst_sample, m.src_sample, m.nsamples, m.src_frames, m.factor, m.left, m.right, m.src, m.inrate, m.outrate, m.src_channels,
+            m.seg_first, m.seg_count, m.reserved, nchannels};
+    if constexpr (!std::is_same<Ev, sh_mix_event_env>::value) {
+        v.loop_start = m.loop_start;
+        v.loop_frames = m.loop_frames;
+        if constexpr (!std::is_same<Ev, sh_mix_event_loop>::value) v.flags = m.flags;
+    }
+    return v;
+}
+
+// 24-bit samples may loop, play backwards and be downmixed, every other step has a 24-bit form; an envelope has none: the first event
+// of a width-3 list that has segments is refused
+template <typename Ev>
+int seq_check_width3(const char* fn, const Ev* events, uint32_t nevents, int width) {
+    for (uint32_t e = 0; width == 3 && e < nevents; ++e)
+        if (events[e].seg_count) return sh::set_error(SH_ERR_INVALID, "%s: event %u: width 3: an envelope's fades have no 24-bit form", fn, e);
+    return SH_OK;
+}
+
+// the caller's segments as the kernels read them (a segment that no event names was not checked, and no kernel reads it)
+void seq_segments(she::Seg* dst, const sh_env_segment* segments, uint32_t n) {
+    for (uint32_t s = 0; s < n; ++s) {
+        const sh_env_segment& g = segments[s];
+        dst[s] = she::Seg{g.mul, g.slope, g.numsamples, g.offset, (uint32_t)g.end, (uint32_t)g.origin, g.kind, 0};
+    }
+}
 
 // Every refusal of an event, in the order they are reported; in(e): event e as a SeqIn.  pe: the plan's view of the checked events.
 template <typename In>
@@ -1487,11 +1347,7 @@ int seq_mix(const char* fn, In in, const sh_buf* const* srcs, uint32_t nsrc, uin
     return seq_run<Rec>(fn, pe, width, track_samples,
         [&](Rec* rec) {
             seq_fill<LEVEL>(rec, in, nevents, srcs, width);
-            she::Seg* seg = reinterpret_cast<she::Seg*>(rec + nevents);
-            for (uint32_t s = 0; s < nsegments; ++s) {
-                const sh_env_segment& g = segments[s];        // (a segment that no event names was not checked, and no kernel reads it)
-                seg[s] = she::Seg{g.mul, g.slope, g.numsamples, g.offset, (uint32_t)g.end, (uint32_t)g.origin, g.kind, 0};
-            }
+            seq_segments(reinterpret_cast<she::Seg*>(rec + nevents), segments, nsegments);
         },
         [&](const Rec* d_ev, const uint32_t* d_tiles, const uint32_t* d_first, const uint32_t* d_idx, uint32_t nt, dim3 grid, dim3 block, hipStream_t st) {
             seq_launch<LEVEL>(d_ev, reinterpret_cast<const she::Seg*>(d_ev + nevents), d_tiles, d_first, d_idx, nt, grid, block, st, width, track,
@@ -1553,11 +1409,7 @@ int sh_mix_events_env(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_eve
     if (width == 3) return sh::set_error(SH_ERR_INVALID, "%s: width 3: an envelope's fades have no 24-bit form", fn);
     const int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
     if (rc) return rc;
-    auto in = [=](uint32_t e) {
-        const sh_mix_event_env& m = events[e];
-        return SeqIn{m.dst_sample, m.src_sample, m.nsamples, m.src_frames, m.factor, m.left, m.right, m.src, m.inrate, m.outrate, m.src_channels,
-                     m.seg_first, m.seg_count, m.reserved, nchannels};
-    };
+    auto in = [=](uint32_t e) { return seq_in(events[e], nchannels); };
     return seq_mix<ENV>(fn, in, srcs, nsrc, nevents, segments, nsegments, width, nchannels, track, track_samples);
 }
 
@@ -1565,20 +1417,10 @@ int sh_mix_events_loop(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_ev
                        const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples) {
     SH_REQUIRE_INIT();
     static const char fn[] = "sh_mix_events_loop";
-    const int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    if (!rc) rc = seq_check_width3(fn, events, nevents, width);
     if (rc) return rc;
-    if (width == 3) {                                         // 24-bit samples may loop, every other step has a 24-bit form; an envelope has none
-        for (uint32_t e = 0; e < nevents; ++e)
-            if (events[e].seg_count) return sh::set_error(SH_ERR_INVALID, "%s: event %u: width 3: an envelope's fades have no 24-bit form", fn, e);
-    }
-    auto in = [=](uint32_t e) {
-        const sh_mix_event_loop& m = events[e];
-        SeqIn v{m.dst_sample, m.src_sample, m.nsamples, m.src_frames, m.factor, m.left, m.right, m.src, m.inrate, m.outrate, m.src_channels,
-                m.seg_first, m.seg_count, m.reserved, nchannels};
-        v.loop_start = m.loop_start;
-        v.loop_frames = m.loop_frames;
-        return v;
-    };
+    auto in = [=](uint32_t e) { return seq_in(events[e], nchannels); };
     return seq_mix<LOOP>(fn, in, srcs, nsrc, nevents, segments, nsegments, width, nchannels, track, track_samples);
 }
 
@@ -1586,21 +1428,10 @@ int sh_mix_events_rev(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_eve
                       const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples) {
     SH_REQUIRE_INIT();
     static const char fn[] = "sh_mix_events_rev";
-    const int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    if (!rc) rc = seq_check_width3(fn, events, nevents, width);
     if (rc) return rc;
-    if (width == 3) {                                         // as sh_mix_events_loop: 24-bit samples may loop and play backwards, an envelope has no 24-bit form
-        for (uint32_t e = 0; e < nevents; ++e)
-            if (events[e].seg_count) return sh::set_error(SH_ERR_INVALID, "%s: event %u: width 3: an envelope's fades have no 24-bit form", fn, e);
-    }
-    auto in = [=](uint32_t e) {
-        const sh_mix_event_rev& m = events[e];
-        SeqIn v{m.dst_sample, m.src_sample, m.nsamples, m.src_frames, m.factor, m.left, m.right, m.src, m.inrate, m.outrate, m.src_channels,
-                m.seg_first, m.seg_count, m.reserved, nchannels};
-        v.loop_start = m.loop_start;
-        v.loop_frames = m.loop_frames;
-        v.flags = m.flags;
-        return v;
-    };
+    auto in = [=](uint32_t e) { return seq_in(events[e], nchannels); };
     return seq_mix<REV>(fn, in, srcs, nsrc, nevents, segments, nsegments, width, nchannels, track, track_samples);
 }
 
@@ -1608,21 +1439,10 @@ int sh_mix_events_chan(const sh_buf* const* srcs, uint32_t nsrc, const sh_mix_ev
                        const sh_env_segment* segments, uint32_t nsegments, int width, int nchannels, sh_buf* track, size_t track_samples) {
     SH_REQUIRE_INIT();
     static const char fn[] = "sh_mix_events_chan";
-    const int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    int rc = seq_check_args(fn, srcs, nsrc, events, nevents, width, track, track_samples);
+    if (!rc) rc = seq_check_width3(fn, events, nevents, width);
     if (rc) return rc;
-    if (width == 3) {                                         // as sh_mix_events_rev: tomono and mul have a 24-bit form, envelopes none
-        for (uint32_t e = 0; e < nevents; ++e)
-            if (events[e].seg_count) return sh::set_error(SH_ERR_INVALID, "%s: event %u: width 3: an envelope's fades have no 24-bit form", fn, e);
-    }
-    auto in = [=](uint32_t e) {
-        const sh_mix_event_chan& m = events[e];
-        SeqIn v{m.dst_sample, m.src_sample, m.nsamples, m.src_frames, m.factor, m.left, m.right, m.src, m.inrate, m.outrate, m.src_channels,
-                m.seg_first, m.seg_count, m.reserved, nchannels};
-        v.loop_start = m.loop_start;
-        v.loop_frames = m.loop_frames;
-        v.flags = m.flags;
-        return v;
-    };
+    auto in = [=](uint32_t e) { return seq_in(events[e], nchannels); };
     return seq_mix<CHAN>(fn, in, srcs, nsrc, nevents, segments, nsegments, width, nchannels, track, track_samples);
 }
 
@@ -1658,9 +1478,21 @@ int seq_row_level(const SeqIn& m) {
     return PLAIN;
 }
 
-template <int LEVEL>
-void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out, const SeqGains* gains, bool metered) {
+// f(std::integral_constant<int, L>()) for the level L that a handle holds as a number
+template <int L = PLAIN, typename F>
+void seq_with_level(int level, F f) {
+    if constexpr (L == CHAN) f(std::integral_constant<int, CHAN>());
+    else if (level == L) f(std::integral_constant<int, L>());
+    else seq_with_level<L + 1>(level, f);
+}
+
+// Which window kernel: the width, at 16 bits the way misaligned event samples are read and whether the biased base lies on a 16-byte
+// boundary.  bus: nothing (a flat list), a SeqBus (a song of tracks: the same kernels with the bus, the gains by value) or a SeqBusM (the
+// metering bus: the rows go to the handle's table), forwarded as the kernels' trailing pack.
+template <int LEVEL, typename... Bus>
+void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out, const Bus&... bus) {
     typedef typename SeqRec<LEVEL>::type Rec;
+    constexpr bool BUS = sizeof...(Bus) != 0;
     const char* b = (const char*)q->block;
     const Rec* ev = (const Rec*)b;
     const she::Seg* segs = (const she::Seg*)(b + q->at_segs);
@@ -1669,55 +1501,17 @@ void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, 
     // the whole song: heaviest tile first (measured: profiles/sequence_plan_ab.txt); any other window: its tiles in song order
     const uint32_t* order = lo == 0 && hi == q->track_samples ? (const uint32_t*)(b + q->at_order) : nullptr;
     const dim3 block(shq::TILE_THREADS);
-    if (q->ntracks && metered) {                              // the same again with the metering bus: the rows go to the handle's table
-        SeqBusM bus;
-        bus.rfirst = (const uint32_t*)(b + q->at_rfirst);
-        bus.runs = (const shq::Run*)(b + q->at_runs);
-        bus.gains = *gains;
-        bus.meters = (shmt::Row*)((char*)q->block + q->at_meters);
-        bus.ntracks = q->ntracks;
-        bus.nch = (uint32_t)q->nchannels;
-        if (q->width == 2) {
-            const int aligned = ((uintptr_t)out & 15) == 0;
-            auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (short*)out, aligned, bus); };
-            const bool vec2 = sh::knobs().seq_align == VEC2;
-            if constexpr (LEVEL == PLAIN) vec2 ? go(k_win_plain16<VEC2, 4, true, SeqBusM>) : go(k_win_plain16<FUNNEL, 4, true, SeqBusM>);
-            else vec2 ? go(k_win_16<LEVEL, VEC2, true, SeqBusM>) : go(k_win_16<LEVEL, FUNNEL, true, SeqBusM>);
-        } else {
-            auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out, bus); };
-            if (q->width == 1) go(k_win_w<LEVEL, 1, true, SeqBusM>);
-            else if (q->width == 4) go(k_win_w<LEVEL, 4, true, SeqBusM>);
-            else if constexpr (LEVEL != ENV) go(k_win_w<LEVEL, 3, true, SeqBusM>);
-        }
-        return;
-    }
-    if (q->ntracks) {                                         // a song of tracks: the same kernels with the bus, the gains by value
-        const SeqBus bus{(const uint32_t*)(b + q->at_rfirst), (const shq::Run*)(b + q->at_runs), *gains};
-        if (q->width == 2) {
-            const int aligned = ((uintptr_t)out & 15) == 0;
-            auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (short*)out, aligned, bus); };
-            const bool vec2 = sh::knobs().seq_align == VEC2;
-            if constexpr (LEVEL == PLAIN) vec2 ? go(k_win_plain16<VEC2, 4, true, SeqBus>) : go(k_win_plain16<FUNNEL, 4, true, SeqBus>);
-            else vec2 ? go(k_win_16<LEVEL, VEC2, true, SeqBus>) : go(k_win_16<LEVEL, FUNNEL, true, SeqBus>);
-        } else {
-            auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out, bus); };
-            if (q->width == 1) go(k_win_w<LEVEL, 1, true, SeqBus>);
-            else if (q->width == 4) go(k_win_w<LEVEL, 4, true, SeqBus>);
-            else if constexpr (LEVEL != ENV) go(k_win_w<LEVEL, 3, true, SeqBus>);
-        }
-        return;
-    }
     if (q->width == 2) {
         const int aligned = ((uintptr_t)out & 15) == 0;       // the BIASED base: song-anchored lanes start on multiples of eight samples
-        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (short*)out, aligned); };
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (short*)out, aligned, bus...); };
         const bool vec2 = sh::knobs().seq_align == VEC2;
-        if constexpr (LEVEL == PLAIN) vec2 ? go(k_win_plain16<VEC2, 4>) : go(k_win_plain16<FUNNEL, 4>);
-        else vec2 ? go(k_win_16<LEVEL, VEC2>) : go(k_win_16<LEVEL, FUNNEL>);
+        if constexpr (LEVEL == PLAIN) vec2 ? go(k_win_plain16<VEC2, 4, BUS, Bus...>) : go(k_win_plain16<FUNNEL, 4, BUS, Bus...>);
+        else vec2 ? go(k_win_16<LEVEL, VEC2, BUS, Bus...>) : go(k_win_16<LEVEL, FUNNEL, BUS, Bus...>);
     } else {
-        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out); };
-        if (q->width == 1) go(k_win_w<LEVEL, 1>);
-        else if (q->width == 4) go(k_win_w<LEVEL, 4>);
-        else if constexpr (LEVEL != ENV) go(k_win_w<LEVEL, 3>);       // (sh_seq_create refuses width 3 with segments)
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out, bus...); };
+        if (q->width == 1) go(k_win_w<LEVEL, 1, BUS, Bus...>);
+        else if (q->width == 4) go(k_win_w<LEVEL, 4, BUS, Bus...>);
+        else if constexpr (LEVEL != ENV) go(k_win_w<LEVEL, 3, BUS, Bus...>);       // (sh_seq_create refuses width 3 with segments)
     }
 }
 
@@ -1730,10 +1524,8 @@ int seq_create(const char* fn, const sh_buf* const* srcs, uint32_t nsrc, const s
     *out = nullptr;
     if (width < 1 || width > 4) return sh::set_error(SH_ERR_INVALID, "%s: width %d not in {1, 2, 3, 4}", fn, width);
     if ((nevents && !events) || (nsrc && !srcs)) return seq_null(fn);
-    if (width == 3) {
-        for (uint32_t e = 0; e < nevents; ++e)
-            if (events[e].seg_count) return sh::set_error(SH_ERR_INVALID, "%s: event %u: width 3: an envelope's fades have no 24-bit form", fn, e);
-    }
+    int rc = seq_check_width3(fn, events, nevents, width);
+    if (rc) return rc;
     if (nchannels < 1) return sh::set_error(SH_ERR_INVALID, "%s: # of channels should be >= 1", fn);
     if (nsegments && !segments) return seq_null(fn);
     if (tracks) {                                             // the tracks' events, concatenated: track t holds events [track_first[t], track_first[t + 1])
@@ -1745,17 +1537,9 @@ int seq_create(const char* fn, const sh_buf* const* srcs, uint32_t nsrc, const s
         for (uint32_t t = 0; t < ntracks; ++t)
             if (track_first[t] > track_first[t + 1]) return sh::set_error(SH_ERR_INVALID, "%s: track_first decreases at track %u", fn, t + 1);
     }
-    auto in = [=](uint32_t e) {
-        const sh_mix_event_chan& m = events[e];
-        SeqIn v{m.dst_sample, m.src_sample, m.nsamples, m.src_frames, m.factor, m.left, m.right, m.src, m.inrate, m.outrate, m.src_channels,
-                m.seg_first, m.seg_count, m.reserved, nchannels};
-        v.loop_start = m.loop_start;
-        v.loop_frames = m.loop_frames;
-        v.flags = m.flags;
-        return v;
-    };
+    auto in = [=](uint32_t e) { return seq_in(events[e], nchannels); };
     std::vector<shq::Event> pe(nevents);
-    int rc = seq_check_events(fn, CHAN, in, nevents, srcs, nsrc, segments, nsegments, width, pe);
+    rc = seq_check_events(fn, CHAN, in, nevents, srcs, nsrc, segments, nsegments, width, pe);
     if (rc) return rc;
     const shq::TilePlan P = shq::plan_by_tile(pe.data(), nevents, track_samples, shq::tile_samples(width));
     if (P.refused == shq::EVENT_BEYOND_TRACK) return sh::set_error(SH_ERR_INVALID, "%s: event %u: range outside the track", fn, P.bad_event);
@@ -1798,20 +1582,11 @@ int seq_create(const char* fn, const sh_buf* const* srcs, uint32_t nsrc, const s
         q->src_hi.push_back((const char*)srcs[v]->ptr + srcs[v]->bytes);
     }
     std::vector<char> host(q->bytes);
-    switch (level) {
-    case PLAIN: seq_fill<PLAIN>(reinterpret_cast<SeqEv*>(host.data()), in, nevents, srcs, width); break;
-    case RATE: seq_fill<RATE>(reinterpret_cast<SeqEvR*>(host.data()), in, nevents, srcs, width); break;
-    case PAN: seq_fill<PAN>(reinterpret_cast<SeqEvP*>(host.data()), in, nevents, srcs, width); break;
-    case ENV: seq_fill<ENV>(reinterpret_cast<SeqEvE*>(host.data()), in, nevents, srcs, width); break;
-    case LOOP: seq_fill<LOOP>(reinterpret_cast<SeqEvL*>(host.data()), in, nevents, srcs, width); break;
-    case REV: seq_fill<REV>(reinterpret_cast<SeqEvV*>(host.data()), in, nevents, srcs, width); break;
-    default: seq_fill<CHAN>(reinterpret_cast<SeqEvV*>(host.data()), in, nevents, srcs, width); break;
-    }
-    she::Seg* seg = reinterpret_cast<she::Seg*>(host.data() + q->at_segs);
-    for (uint32_t s = 0; s < nsegments; ++s) {
-        const sh_env_segment& g = segments[s];                // (a segment that no event names was not checked, and no kernel reads it)
-        seg[s] = she::Seg{g.mul, g.slope, g.numsamples, g.offset, (uint32_t)g.end, (uint32_t)g.origin, g.kind, 0};
-    }
+    seq_with_level(level, [&](auto L) {
+        constexpr int LEVEL = decltype(L)::value;
+        seq_fill<LEVEL>(reinterpret_cast<typename SeqRec<LEVEL>::type*>(host.data()), in, nevents, srcs, width);
+    });
+    seq_segments(reinterpret_cast<she::Seg*>(host.data() + q->at_segs), segments, nsegments);
     memcpy(host.data() + q->at_first, P.first.data(), P.first.size() * 4);
     if (!P.idx.empty()) memcpy(host.data() + q->at_idx, P.idx.data(), P.idx.size() * 4);
     if (P.ntiles) {                                           // every tile, heaviest first, ties in song order (idle tiles last)
@@ -1842,6 +1617,16 @@ int seq_create(const char* fn, const sh_buf* const* srcs, uint32_t nsrc, const s
     return SH_OK;
 }
 
+// the gains of a render as the kernels take them: the caller's ngains (NULL: none given), every finite; 1.0 for every other track
+int seq_gains(const char* fn, const double* gains, uint32_t ngains, SeqGains& out) {
+    for (uint32_t t = 0; t < shq::MAX_TRACKS; ++t) out.g[t] = 1.0;
+    for (uint32_t t = 0; gains && t < ngains; ++t) {
+        if (!isfinite(gains[t])) return sh::set_error(SH_ERR_INVALID, "%s: gain %u is not finite", fn, t);
+        out.g[t] = gains[t];
+    }
+    return SH_OK;
+}
+
 // sh_seq_render (gains NULL: every track at 1.0), sh_seq_render_gains and sh_seq_render_meters (meters: ntracks + 1 host rows, the handle
 // has tracks) behind their names
 int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains,
@@ -1868,23 +1653,24 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
     void* biased = (void*)((uintptr_t)out->ptr + w * (uintptr_t)out_sample - w * (uintptr_t)first_sample);
     const dim3 grid = sh::grid1d(nt, 1);
     hipStream_t st = sh::state().stream;
-    SeqGains unity;
-    if (seq->ntracks && !gains) {
-        for (uint32_t t = 0; t < shq::MAX_TRACKS; ++t) unity.g[t] = 1.0;
-        gains = &unity;
-    }
     char* table = (char*)seq->block + seq->at_meters;         // (the handle's: one metered render at a time)
     if (meters) SH_HIP(hipMemsetAsync(table, 0, b_meters, st));
-    const bool metered = meters != nullptr;
-    switch (seq->level) {
-    case PLAIN: seq_window_launch<PLAIN>(seq, grid, st, lo, hi, biased, gains, metered); break;
-    case RATE: seq_window_launch<RATE>(seq, grid, st, lo, hi, biased, gains, metered); break;
-    case PAN: seq_window_launch<PAN>(seq, grid, st, lo, hi, biased, gains, metered); break;
-    case ENV: seq_window_launch<ENV>(seq, grid, st, lo, hi, biased, gains, metered); break;
-    case LOOP: seq_window_launch<LOOP>(seq, grid, st, lo, hi, biased, gains, metered); break;
-    case REV: seq_window_launch<REV>(seq, grid, st, lo, hi, biased, gains, metered); break;
-    default: seq_window_launch<CHAN>(seq, grid, st, lo, hi, biased, gains, metered); break;
+    SeqBusM bus{};                                            // (a song of tracks; its SeqBus part is the plain bus)
+    if (seq->ntracks) {
+        bus.rfirst = (const uint32_t*)((const char*)seq->block + seq->at_rfirst);
+        bus.runs = (const shq::Run*)((const char*)seq->block + seq->at_runs);
+        if (gains) bus.gains = *gains;
+        else seq_gains(fn, nullptr, 0, bus.gains);
+        bus.meters = (shmt::Row*)table;
+        bus.ntracks = seq->ntracks;
+        bus.nch = (uint32_t)seq->nchannels;
     }
+    seq_with_level(seq->level, [&](auto L) {
+        constexpr int LEVEL = decltype(L)::value;
+        if (!seq->ntracks) seq_window_launch<LEVEL>(seq, grid, st, lo, hi, biased);
+        else if (!meters) seq_window_launch<LEVEL, SeqBus>(seq, grid, st, lo, hi, biased, bus);
+        else seq_window_launch<LEVEL, SeqBusM>(seq, grid, st, lo, hi, biased, bus);
+    });
     SH_CHECK_LAUNCH(fn);
     if (meters) {                                             // synchronous, as sh_pcm_stats: one small copy, one wait
         SH_HIP(hipMemcpyAsync(meters, table, b_meters, hipMemcpyDeviceToHost, st));
@@ -1926,11 +1712,8 @@ int sh_seq_render_gains(const sh_seq* seq, size_t first_sample, size_t nsamples,
     if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
     if (ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
     SeqGains g;
-    for (uint32_t t = 0; t < shq::MAX_TRACKS; ++t) g.g[t] = 1.0;
-    for (uint32_t t = 0; t < ngains; ++t) {
-        if (!isfinite(gains[t])) return sh::set_error(SH_ERR_INVALID, "%s: gain %u is not finite", fn, t);
-        g.g[t] = gains[t];
-    }
+    const int rc = seq_gains(fn, gains, ngains, g);
+    if (rc) return rc;
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g);
 }
 
@@ -1943,11 +1726,8 @@ int sh_seq_render_meters(const sh_seq* seq, size_t first_sample, size_t nsamples
     if (gains && ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
     if (nmeters != seq->ntracks + 1) return sh::set_error(SH_ERR_INVALID, "%s: %u rows for %u tracks and the master", fn, nmeters, seq->ntracks);
     SeqGains g;
-    for (uint32_t t = 0; t < shq::MAX_TRACKS; ++t) g.g[t] = 1.0;
-    for (uint32_t t = 0; gains && t < ngains; ++t) {
-        if (!isfinite(gains[t])) return sh::set_error(SH_ERR_INVALID, "%s: gain %u is not finite", fn, t);
-        g.g[t] = gains[t];
-    }
+    const int rc = seq_gains(fn, gains, ngains, g);
+    if (rc) return rc;
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters);
 }
 

@@ -5,6 +5,10 @@ never come from the product.  Rate 8192, sources of a few hundred frames, as the
 mid-lane in tile 3 and whose tile 2 no event touches; one list per feature level."""
 import audioop
 import ctypes as C
+import os
+import subprocess
+import sys
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -13,7 +17,7 @@ from tests.test_gpu_channels import FACTORS, _chan_table, _mix_events_chan, orac
 from tests.test_gpu_enveloped import _differs
 from tests.test_gpu_looped import LANE, LOOPS, RATE, SPEEDS, TILE, _out_frames
 from tests.test_gpu_reversed import LENGTHS, as_samples, named, with_samples
-from tests.test_gpu_sequence import _pcm
+from tests.test_gpu_sequence import OTHER_SCHEME, ROOT, _pcm
 
 pytestmark = pytest.mark.gpu
 
@@ -165,6 +169,20 @@ def test_windows_of_every_level_through_the_entry_point(gpu, level, width):
             assert got == exp, "window [%d, %d) at out_sample %d: %d bytes differ" % (a, b, out_sample, _differs(got, exp))
             assert front == b"\x5a" * 64 and behind == b"\x5a" * 64, (a, b, out_sample)
     seq.free()
+
+
+def in_a_child_under_the_other_alignment_scheme(path, ids):
+    """SYNTHHIP_SEQ_ALIGN is read once per process (sh_init): the named cases of the file again, in a fresh child under the scheme that is
+    not the default"""
+    env = dict(os.environ, SYNTHHIP_SEQ_ALIGN=OTHER_SCHEME)
+    me = str(Path(path).resolve())
+    p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider"] + [me + "::" + i for i in ids],
+                       cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "%d passed" % len(ids) in p.stdout and "failed" not in p.stdout, p.stdout[-3000:] + p.stderr[-1000:]
+
+
+def test_windows_of_every_level_at_16_bits_under_the_other_alignment_scheme(gpu):
+    in_a_child_under_the_other_alignment_scheme(__file__, ["test_windows_of_every_level_through_the_entry_point[%s-2]" % lv for lv in LEVELS])
 
 
 @pytest.mark.parametrize("level, width", [("plain", 2), ("rev", 2), ("downmix", 2), ("balance", 2), ("pan", 1), ("loop", 3), ("env", 4)])

@@ -4,7 +4,8 @@ sh_seq_render_meters -- against live ``audioop`` and integers.  The expected row
 track order), cut to the window and reduced here with numpy int64 / uint64 and Python ints: per channel (song sample s is channel s & 1
 of a stereo song) the peak, max |x|, and the exact sum of x * x.  Expected values never come from the product.  Rate 8192 and the
 four-tile songs of the neighbouring files; one song per kernel template: 16-bit plain (k_win_plain16), the 16-bit stereo balance song at
-level chan (k_win_16), widths 1, 3, 4 plain (k_win_w), and the stereo balance song at width 4 beside them (two channels of two sums)."""
+level chan (k_win_16, the next record's index held ahead) and the 16-bit rate song (k_win_16, a whole record held ahead), widths 1, 3, 4
+plain (k_win_w), and the stereo balance song at width 4 beside them (two channels of two sums)."""
 import audioop
 import ctypes as C
 import math
@@ -12,7 +13,7 @@ import math
 import numpy as np
 import pytest
 
-from tests.test_gpu_compiled import _ev, song, windows
+from tests.test_gpu_compiled import LEVEL_NAME, _ev, in_a_child_under_the_other_alignment_scheme, song, windows
 from tests.test_gpu_looped import LANE, RATE, TILE
 from tests.test_gpu_reversed import as_samples, named, with_samples
 from tests.test_gpu_sequence import _pcm
@@ -88,7 +89,7 @@ def check_against_audioop(key, subs, gains, width, nch, a, b, rows):
 
 
 # ---- the songs, one per kernel template ----------------------------------------------------------------------------------------------------
-SONGS = [("bus", 2), ("balance", 2), ("bus", 1), ("bus", 3), ("bus", 4), ("balance", 4)]
+SONGS = [("bus", 2), ("balance", 2), ("rate", 2), ("bus", 1), ("bus", 3), ("bus", 4), ("balance", 4)]
 
 
 def the_song(kind, width):
@@ -101,7 +102,7 @@ def the_song(kind, width):
     key = ("subs", kind, width)
     if key not in _POST:
         _POST[key] = subs_of(instruments, tracks, width, nch)
-    return instruments, tracks, nch, _POST[key], total, "chan"
+    return instruments, tracks, nch, _POST[key], total, LEVEL_NAME.get(kind, kind)
 
 
 def the_windows(kind, width, total):
@@ -155,6 +156,11 @@ def test_rows_equal_the_reference_and_the_bytes_are_the_unmetered_render(gpu, ki
             if 2 * T <= a and b <= 3 * T:
                 assert rows == [ZERO] * 4                       # the idle tile: nothing sounds
     seq.free()
+
+
+def test_rows_of_every_16_bit_song_under_the_other_alignment_scheme(gpu):
+    in_a_child_under_the_other_alignment_scheme(
+        __file__, ["test_rows_equal_the_reference_and_the_bytes_are_the_unmetered_render[%s-%d]" % s for s in SONGS if s[1] == 2])
 
 
 # ---- 3: the edge mask --------------------------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from tests.test_gpu_channels import oracle
-from tests.test_gpu_compiled import HELD, LEVEL_NAME, LEVELS, _ev, render_window, song, windows
+from tests.test_gpu_compiled import HELD, LEVEL_NAME, LEVELS, _ev, in_a_child_under_the_other_alignment_scheme, render_window, song, windows
 from tests.test_gpu_enveloped import _differs
 from tests.test_gpu_looped import LANE, RATE, TILE
 from tests.test_gpu_reversed import as_samples, named, with_samples
@@ -187,6 +187,10 @@ def test_windows_of_every_level_through_the_entry_point(gpu, level, width):
                 assert got == exp, "gains %s, window [%d, %d) at out_sample %d: %d bytes differ" % (gains, a, b, out_sample, _differs(got, exp))
                 assert front == b"\x5a" * 64 and behind == b"\x5a" * 64, (gains, a, b, out_sample)
     seq.free()
+
+
+def test_windows_of_every_level_at_16_bits_under_the_other_alignment_scheme(gpu):
+    in_a_child_under_the_other_alignment_scheme(__file__, ["test_windows_of_every_level_through_the_entry_point[%s-2]" % lv for lv in LEVELS])
 
 
 # ---- 4: run shapes -------------------------------------------------------------------------------------------------------------------------
