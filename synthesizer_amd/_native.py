@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from pathlib import Path
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -98,6 +98,29 @@ class SeqMeter(C.Structure):                                                    
 
 
 SEQ_LEVELS = ("plain", "rate", "pan", "env", "loop", "rev", "chan")                   # SH_SEQ_LEVEL_*
+
+
+class MixLevel(NamedTuple):
+    """One rung of the placed-sample mixer's ladder: the table layout a list of that level is packed in, the entry point that reads it,
+    and which of the three signatures the entry point has (``segments``: the segment table and its length behind the event table;
+    ``nchannels``: the track's channel count behind the sample width)."""
+    name: str
+    dtype: np.dtype
+    entry: str
+    segments: bool
+    nchannels: bool
+
+
+# in SEQ_LEVELS' order: a list's level is the highest rung one of its events needs, and every layout holds the columns of those below it
+MIX_LEVELS = (MixLevel("plain", MIX_EVENT_DTYPE, "sh_mix_events", False, False),
+              MixLevel("rate", MIX_EVENT_RATE_DTYPE, "sh_mix_events_rate", False, True),
+              MixLevel("pan", MIX_EVENT_PAN_DTYPE, "sh_mix_events_pan", False, False),
+              MixLevel("env", MIX_EVENT_ENV_DTYPE, "sh_mix_events_env", True, True),
+              MixLevel("loop", MIX_EVENT_LOOP_DTYPE, "sh_mix_events_loop", True, True),
+              MixLevel("rev", MIX_EVENT_REV_DTYPE, "sh_mix_events_rev", True, True),
+              MixLevel("chan", MIX_EVENT_CHAN_DTYPE, "sh_mix_events_chan", True, True))
+assert tuple(level.name for level in MIX_LEVELS) == SEQ_LEVELS
+LEVEL_PLAIN, LEVEL_RATE, LEVEL_PAN, LEVEL_ENV, LEVEL_LOOP, LEVEL_REV, LEVEL_CHAN = range(len(MIX_LEVELS))
 
 
 class DevInfo(C.Structure):

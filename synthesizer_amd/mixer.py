@@ -708,11 +708,11 @@ class CompiledSequence:
         if len(tracks) > cls.MAX_TRACKS:
             raise ValueError("compile_tracks: %d tracks, at most %d" % (len(tracks), cls.MAX_TRACKS))
         track._check_gpu_width("mix_at")
-        todo, shaped, track_first = [], {}, [0]
+        checked, track_first = [], [0]
         for t, events in enumerate(tracks):
             events = list(events)
             try:
-                one, its = track._check_events(events)
+                checked.extend(track._check_events(events))
             except (ValueError, NotImplementedError) as first:
                 for k, ev in enumerate(events):             # which event: the checks take one event at a time
                     try:
@@ -720,11 +720,8 @@ class CompiledSequence:
                     except (ValueError, NotImplementedError) as e:
                         raise type(e)("compile_tracks: track %d, event %d: %s" % (t, k, e)) from None
                 raise type(first)("compile_tracks: track %d: %s" % (t, first)) from None
-            for k, v in its.items():
-                shaped[len(todo) + k] = v
-            todo.extend(one)
-            track_first.append(len(todo))
-        return track._compile_checked(todo, shaped) + (track_first,)
+            track_first.append(len(checked))
+        return track._compile_checked(checked) + (track_first,)
 
     def _gains(self, gains) -> Optional[list]:
         """``gains`` as render hands them on: None, or ``ntracks`` finite floats -- checked before anything is launched"""

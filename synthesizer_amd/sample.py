@@ -26,7 +26,7 @@ import array
 import ctypes as C
 import math
 import wave
-from typing import BinaryIO, Iterable, Optional, Sequence, Tuple, Union
+from typing import BinaryIO, Iterable, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -149,6 +149,84 @@ def _region_frames(region, rate: int, frames: Optional[int], duration: float) ->
         return 0, 0
     first, last = min(int(rate * start), frames), min(int(rate * end), frames)
     return first, last - first
+
+
+def _channel_weights(channels, other_nchannels: int, track_nchannels: int) -> tuple:
+    """``channels`` of an event as ``(left_factor, right_factor)`` in floats, for a stereo ``other`` and a mono or stereo track"""
+    if not isinstance(channels, (tuple, list)) or len(channels) != 2:
+        raise ValueError("mix_at_many: channels is a pair (left_factor, right_factor)")
+    try:
+        weights = (float(channels[0]), float(channels[1]))
+    except (TypeError, ValueError):
+        raise ValueError("mix_at_many: channels is a pair of numbers, not %r" % (tuple(channels),)) from None
+    if not (math.isfinite(weights[0]) and math.isfinite(weights[1])):
+        raise ValueError("mix_at_many: channels factor is not finite")
+    if other_nchannels != 2:
+        raise ValueError("mix_at_many: channels needs a stereo sample, this one has %d channels" % other_nchannels)
+    if track_nchannels not in (1, 2):
+        raise ValueError("mix_at_many: channels needs a mono or stereo track, this one has %d channels" % track_nchannels)
+    return weights
+
+
+def _pan_factors(pan, other_nchannels: int, track_nchannels: int) -> tuple:
+    """``pan`` of an event -- a float -1 .. 1 or the pair itself -- as ``audioop.tostereo``'s ``(left_factor, right_factor)``, for a mono
+    ``other`` and a stereo track"""
+    if other_nchannels != 1:
+        raise ValueError("mix_at_many: pan needs a mono sample, this one has %d channels" % other_nchannels)
+    if track_nchannels != 2:
+        raise ValueError("mix_at_many: pan needs a stereo track, this one has %d channels" % track_nchannels)
+    if isinstance(pan, (tuple, list)):
+        if len(pan) != 2:
+            raise ValueError("mix_at_many: pan is a number or a pair (left_factor, right_factor)")
+        factors = (float(pan[0]), float(pan[1]))
+    else:
+        if not -1.0 <= pan <= 1.0:
+            raise ValueError("mix_at_many: pan must be between -1 and 1")
+        factors = ((1.0 - pan) / 2.0, (1.0 + pan) / 2.0)    # Sample.pan: Python floats, on the host
+    if not (math.isfinite(factors[0]) and math.isfinite(factors[1])):
+        raise ValueError("mix_at_many: pan factor is not finite")
+    return factors
+
+
+def _envelope_rows(envelope, frames: int, width: int, nchannels: int, rate: int) -> tuple:
+    """``envelope`` of an event whose (resampled) ``other`` has ``frames`` frames of ``nchannels`` channels: (the frames the note's length
+    leaves, _envelope_segments' rows over them)"""
+    if width == 3:
+        raise NotImplementedError("mix_at_many: envelope: 3-byte samples are not supported (fades have no 24-bit form)")
+    if not isinstance(envelope, (tuple, list)) or len(envelope) not in (4, 5):
+        raise ValueError("mix_at_many: envelope is (attack, decay, sustainlevel, release) or (attack, decay, sustainlevel, release, length)")
+    if not all(math.isfinite(v) and v >= 0 for v in envelope[:2] + envelope[3:]):
+        raise ValueError("mix_at_many: envelope: attack, decay, release and length are finite and not negative")
+    if not 0 <= envelope[2] <= 1:
+        raise ValueError("mix_at_many: envelope: sustainlevel must be between 0 and 1")
+    if len(envelope) == 5:                                  # clip(0.0, length): frames[0:frame_idx(length)] of the other's own frames
+        frames = min(frames, int(rate * envelope[4]))
+    return frames, _envelope_segments(frames * width * nchannels, width, nchannels, rate, *envelope[:4])
+
+
+class _Event(NamedTuple):
+    """One checked event of mix_at_many, as Sample._check_events leaves it.  What the caller gave, then what the checks made of it."""
+    seconds: float
+    other: "Sample"
+    volume: Optional[float]
+    other_seconds: Optional[float]
+    speed: Optional[float]
+    start: int                                              # the first byte of the track it touches
+    nbytes: int                                             # bytes of the track it covers: resampled, stereo if panned, mono if downmixed, cut
+    inrate: int                                             # != the track's rate: ``other`` is resampled from it, and nbytes counts resampled bytes
+    pan: Optional[tuple]                                    # audioop.tostereo's (left, right): ``other`` is mono, the track stereo
+    loop: Optional[tuple]                                   # (loop_start, loop_frames, virtual frames), in frames of the region
+    region: Optional[tuple]                                 # (first frame, frames) of ``other``: what nbytes, loop and segments were counted over
+    reverse: bool
+    weights: Optional[tuple]                                # ``channels``: a downmix in a mono track, a balance in a stereo one
+    envelope: Optional[tuple]                               # as the caller gave it
+    segments: Optional[list]                                # _envelope_segments' rows, over the uncut note
+    level: int                                              # the highest rung of N.MIX_LEVELS that an attribute of this event needs
+    own_region: Optional[tuple]                             # ``other`` is the track itself: the caller's (start, end) in SECONDS, cut when the event runs
+
+
+_new_event = tuple.__new__                                  # (as _Event._make builds one: a third of the time of _Event(...) per event)
+_NO_MORE = (None,) * 9                                      # what an event shorter than the full 11 leaves unsaid
 
 
 class Sample:
@@ -757,102 +835,64 @@ class Sample:
         goes through the loop's body above, region, reverse and a balance included (a downmix cannot occur there)."""
         self._check_writable()
         self._check_gpu_width("mix_at")
-        todo, shaped = self._check_events(events)
-        batch, envs, extras = [], {}, {}                                        # envs: index into batch -> segment rows; extras: -> (region, reverse)
-        for k, (seconds, other, volume, other_seconds, speed, start, n2, inrate, factors, loop, extra) in enumerate(todo):
-            if other is self:                                                   # (never panned: a panned event's other is mono, its track stereo)
-                self.__mix_events(batch, envs, extras)
-                batch, envs, extras = [], {}, {}
-                region, reverse = extra[:2] if extra is not None else (None, False)
-                weights = extra[2] if extra is not None and len(extra) > 2 else None
-                if region is not None:                                          # copy().clip() of the track as it is NOW
-                    end = other.duration if region[1] is None else region[1]
-                    if end < region[0]:
-                        raise ValueError("mix_at_many: region: end (%r s: the track as the events before left it) lies before start (%r s)"
-                                         % (end, region[0]))
-                    other = other.copy().clip(region[0], end)
-                if reverse:
-                    other = other.copy().reverse()
-                if loop is not None:                                            # clip(0.0, loop_end) of the track (its region, reversed) as it is NOW
-                    first, last = loop[0], min(loop[0] + loop[1], len(other))
-                    if first >= last:
-                        raise ValueError("mix_at_many: loop: no frame between loop_start (frame %d) and loop_end (frame %d) of the track "
-                                         "as the events before left it" % (first, last))
-                    other = other.__unrolled(first, last - first, loop[2])
-                if inrate != self.__samplerate:
-                    other = other.copy().speed(speed)
-                if shaped and k in shaped:
-                    envelope = shaped[k][0]
-                    other = other.copy()
-                    if len(envelope) == 5:
-                        other.clip(0.0, envelope[4])
-                    other.envelope(*envelope[:4])
-                if weights is not None:                                         # (the track is stereo here: a balance)
-                    other = other.copy().stereo(*weights)
-                self.mix_at(seconds, other if volume is None else other.at_volume(volume), other_seconds)
-            else:
-                self._batch_event(batch, envs, extras, shaped.get(k), todo[k])
-        self.__mix_events(batch, envs, extras)
+        batch = []                                                              # the events since the last one whose other is this sample
+        for e in self._check_events(events):
+            if e.other is not self:
+                batch.append(e)
+                continue
+            self.__mix_events(batch)                                            # it reads the track as the events before it left it
+            batch = []
+            other = e.other                                                     # (never panned: a panned event's other is mono, its track stereo)
+            if e.own_region is not None:                                        # copy().clip() of the track as it is NOW
+                first, end = e.own_region
+                if end is None:
+                    end = other.duration
+                if end < first:
+                    raise ValueError("mix_at_many: region: end (%r s: the track as the events before left it) lies before start (%r s)"
+                                     % (end, first))
+                other = other.copy().clip(first, end)
+            if e.reverse:
+                other = other.copy().reverse()
+            if e.loop is not None:                                              # clip(0.0, loop_end) of the track (its region, reversed) as it is NOW
+                first, last = e.loop[0], min(e.loop[0] + e.loop[1], len(other))
+                if first >= last:
+                    raise ValueError("mix_at_many: loop: no frame between loop_start (frame %d) and loop_end (frame %d) of the track "
+                                     "as the events before left it" % (first, last))
+                other = other.__unrolled(first, last - first, e.loop[2])
+            if e.inrate != self.__samplerate:
+                other = other.copy().speed(e.speed)
+            if e.envelope is not None:
+                other = other.copy()
+                if len(e.envelope) == 5:
+                    other.clip(0.0, e.envelope[4])
+                other.envelope(*e.envelope[:4])
+            if e.weights is not None:                                           # (the track is stereo here: a balance)
+                other = other.copy().stereo(*e.weights)
+            self.mix_at(e.seconds, other if e.volume is None else other.at_volume(e.volume), e.other_seconds)
+        self.__mix_events(batch)
         return self
 
-    def _check_events(self, events: Iterable[tuple]) -> tuple:
-        """Every event of a list for mix_at_many checked against this track's format, before anything is mixed or reaches the device:
-        (todo, shaped) -- todo: (seconds, other, volume, other_seconds, speed, first byte, bytes, inrate, tostereo factors | None,
-        loop in frames | None, extra | None) per event; shaped: index into todo -> (envelope, its sh_env_segment rows).  The one
-        statement of mix_at_many's ValueErrors: Sample.mix_at_many and mixer.compile_sequence both go through it."""
-        fb = self.__samplewidth * self.__nchannels
-        rate = self.__samplerate
-        todo = []                                           # everything is checked before anything is mixed
-        shaped = {}                                         # index into todo -> (envelope, its sh_env_segment rows): the enveloped events
+    def _check_events(self, events: Iterable[tuple]) -> list:
+        """Every event of a list for mix_at_many checked against this track's format, before anything is mixed or reaches the device: one
+        _Event each.  The one statement of mix_at_many's ValueErrors (Sample.mix_at_many, mixer.compile_sequence and mixer.compile_tracks
+        all go through it); the order of the checks is the order in which an event's faults are reported."""
+        w, nch, rate = self.__samplewidth, self.__nchannels, self.__samplerate
+        fb = w * nch
+        checked = []                                        # everything is checked before anything is mixed
         for ev in events:
-            nev = len(ev)
-            seconds, other = ev[0], ev[1]
-            volume = ev[2] if nev > 2 else None
-            other_seconds = ev[3] if nev > 3 else None
-            speed = ev[4] if nev > 4 else None
-            pan = ev[5] if nev > 5 else None
-            loop = ev[7] if nev > 7 else None
-            region, reverse = None, False
-            if nev > 8:
-                region = ev[8]
-                reverse = bool(ev[9]) if nev > 9 else False
-            channels = ev[10] if nev > 10 else None
+            seconds, other, volume, other_seconds, speed, pan, envelope, loop, region, reverse, channels = (*ev, *_NO_MORE)[:11]
+            reverse = bool(reverse)
             assert self.samplewidth == other.samplewidth
             assert self.samplerate == other.samplerate
-            factors = None                                                      # audioop.tostereo's, of a panned event
-            weights = None                                                      # audioop.tomono's or the balance's, of an event with channels
+            weights = None
             if channels is not None:
                 if pan is not None:
                     raise ValueError("mix_at_many: pan and channels on one event: pan places a mono sample, channels weighs a stereo one")
-                if not isinstance(channels, (tuple, list)) or len(channels) != 2:
-                    raise ValueError("mix_at_many: channels is a pair (left_factor, right_factor)")
-                try:
-                    weights = (float(channels[0]), float(channels[1]))
-                except (TypeError, ValueError):
-                    raise ValueError("mix_at_many: channels is a pair of numbers, not %r" % (tuple(channels),)) from None
-                if not (math.isfinite(weights[0]) and math.isfinite(weights[1])):
-                    raise ValueError("mix_at_many: channels factor is not finite")
-                if other.nchannels != 2:
-                    raise ValueError("mix_at_many: channels needs a stereo sample, this one has %d channels" % other.nchannels)
-                if self.__nchannels not in (1, 2):
-                    raise ValueError("mix_at_many: channels needs a mono or stereo track, this one has %d channels" % self.__nchannels)
+                weights = _channel_weights(channels, other.nchannels, nch)
             elif pan is None:
                 assert self.nchannels == other.nchannels
             else:
-                if other.nchannels != 1:
-                    raise ValueError("mix_at_many: pan needs a mono sample, this one has %d channels" % other.nchannels)
-                if self.__nchannels != 2:
-                    raise ValueError("mix_at_many: pan needs a stereo track, this one has %d channels" % self.__nchannels)
-                if isinstance(pan, (tuple, list)):
-                    if len(pan) != 2:
-                        raise ValueError("mix_at_many: pan is a number or a pair (left_factor, right_factor)")
-                    factors = (float(pan[0]), float(pan[1]))
-                else:
-                    if not -1.0 <= pan <= 1.0:
-                        raise ValueError("mix_at_many: pan must be between -1 and 1")
-                    factors = ((1.0 - pan) / 2.0, (1.0 + pan) / 2.0)            # Sample.pan: Python floats, on the host
-                if not (math.isfinite(factors[0]) and math.isfinite(factors[1])):
-                    raise ValueError("mix_at_many: pan factor is not finite")
+                pan = _pan_factors(pan, other.nchannels, nch)
             if seconds < 0 or (other_seconds is not None and other_seconds < 0):
                 raise ValueError("mix_at_many: negative time")
             if volume is not None and not math.isfinite(volume):
@@ -865,71 +905,47 @@ class Sample:
                 if inrate <= 0:
                     raise ValueError("mix_at_many: speed %r leaves no sample rate" % (speed,))
             start = fb * int(rate * seconds)                                    # frame_idx(seconds): Python floats, on the host
-            frames = other.__nbytes // (self.__samplewidth * other.nchannels)   # (a panned event: the mono frames, a track frame each)
-            extra = None                                                        # ((first frame, frames) of the region | None, reverse): most events have neither
+            frames = other.__nbytes // (w * other.nchannels)                    # (a panned event: the mono frames, a track frame each)
+            own = other is self                                                 # the track as its own source: cut and clamped when the event runs
+            own_region = None
             if region is not None:                                              # the event has the region's frames from here on
-                cut = _region_frames(region, rate, None if other is self else frames, other.duration)
-                if other is self:
-                    extra = (region, reverse)                                   # (cut when the event runs)
+                cut = _region_frames(region, rate, None if own else frames, other.duration)
+                if own:
+                    own_region, region = region, None
                 else:
-                    frames = cut[1]
-                    extra = (cut, reverse)
-            elif reverse:
-                extra = (None, True)
-            if loop is not None:                                                # (S, E - S, V) in frames; the note has V frames from here on
-                loop = _loop_frames(loop, rate, None if other is self else frames, other.nchannels)
+                    region, frames = cut, cut[1]
+            if loop is not None:                                                # the note has V frames from here on
+                loop = _loop_frames(loop, rate, None if own else frames, other.nchannels)
                 frames = loop[2]
-            have = fb * (frames if inrate == rate else _ratecv_out_frames(frames, inrate, rate))
-            if nev > 6 and ev[6] is not None:
-                envelope = ev[6]
-                if self.__samplewidth == 3:
-                    raise NotImplementedError("mix_at_many: envelope: 3-byte samples are not supported (fades have no 24-bit form)")
-                if not isinstance(envelope, (tuple, list)) or len(envelope) not in (4, 5):
-                    raise ValueError("mix_at_many: envelope is (attack, decay, sustainlevel, release) or (attack, decay, sustainlevel, release, length)")
-                if not all(math.isfinite(v) and v >= 0 for v in envelope[:2] + envelope[3:]):
-                    raise ValueError("mix_at_many: envelope: attack, decay, release and length are finite and not negative")
-                if not 0 <= envelope[2] <= 1:
-                    raise ValueError("mix_at_many: envelope: sustainlevel must be between 0 and 1")
-                if len(envelope) == 5:                                          # clip(0.0, length): frames[0:frame_idx(length)] of the other's own frames
-                    have = min(have, fb * int(rate * envelope[4]))
-                fbo = self.__samplewidth * other.nchannels
-                shaped[len(todo)] = (envelope, _envelope_segments(have // fb * fbo, self.__samplewidth, other.nchannels, rate, *envelope[:4]))
-            n2 = fb * int(rate * other_seconds) if other_seconds else have     # frame_idx(other_seconds) of what mix_at is handed
-            if weights is not None and self.__nchannels == 1 and 2 * ((start + min(n2, have)) // self.__samplewidth) > _MAX_DOWNMIX_SOURCE_SAMPLES:
+            if inrate != rate:
+                frames = _ratecv_out_frames(frames, inrate, rate)
+            segments = None
+            if envelope is not None:
+                frames, segments = _envelope_rows(envelope, frames, w, other.nchannels, rate)
+            have = fb * frames                                                  # a frame of other (resampled, shaped) is a frame of the track
+            n2 = min(fb * int(rate * other_seconds), have) if other_seconds else have      # frame_idx(other_seconds) of what mix_at is handed
+            if weights is not None and nch == 1 and 2 * ((start + n2) // w) > _MAX_DOWNMIX_SOURCE_SAMPLES:
                 raise ValueError("mix_at_many: channels: a downmix ends at most %d samples into the track (its stereo samples are addressed "
                                  "in 32 bits)" % (_MAX_DOWNMIX_SOURCE_SAMPLES // 2))
-            if weights is not None:
-                extra = (extra if extra is not None else (None, False)) + (weights,)
-            todo.append((seconds, other, volume, other_seconds, speed, start, min(n2, have), inrate, factors, loop, extra))
-        return todo, shaped
-
-    @staticmethod
-    def _batch_event(batch: list, envs: dict, extras: dict, shape, checked: tuple) -> None:
-        """one checked event of _check_events (none whose other is the track) as a row of __mix_events' batch"""
-        _seconds, other, volume, _other_seconds, _speed, start, n2, inrate, factors, loop, extra = checked
-        if shape is not None:
-            envs[len(batch)] = shape[1]
-        if extra is not None:
-            extras[len(batch)] = extra
-        batch.append((start, other, n2, 1.0 if volume is None else float(volume), inrate, factors, loop))
+            level = (N.LEVEL_CHAN if weights is not None else N.LEVEL_REV if reverse else N.LEVEL_LOOP if loop is not None else
+                     N.LEVEL_ENV if segments is not None else N.LEVEL_PAN if pan is not None else N.LEVEL_RATE if inrate != rate else N.LEVEL_PLAIN)
+            checked.append(_new_event(_Event, (seconds, other, volume, other_seconds, speed, start, n2, inrate, pan, loop, region, reverse, weights,
+                                               envelope, segments, level, own_region)))
+        return checked
 
     def _compile_events(self, events: Iterable[tuple]) -> tuple:
         """What mixer.compile_sequence hands sh_seq_create, this sample being the empty track that says the format: mix_at_many's checks,
         then (the sources' device buffers, shared; the table in sh_mix_event_chan's layout; the segment table; the song's bytes)."""
         self._check_gpu_width("mix_at")
-        todo, shaped = self._check_events(events)
-        return self._compile_checked(todo, shaped)
+        return self._compile_checked(self._check_events(events))
 
-    def _compile_checked(self, todo: list, shaped: dict) -> tuple:
-        """_compile_events behind its checks: _check_events' (todo, shaped) as tables (mixer.compile_tracks checks track by track and
-        hands the tracks' events on as one list, one row per event)."""
-        batch, envs, extras = [], {}, {}
-        for k, checked in enumerate(todo):
-            self._batch_event(batch, envs, extras, shaped.get(k), checked)
-        if not batch:
-            return [], np.zeros(0, dtype=N.MIX_EVENT_CHAN_DTYPE), None, 0
-        bufs, table, segtab = self._pack_events(batch, envs, extras, widest=True, share=True)[:3]
-        return bufs, table, segtab, max(b[0] + b[2] for b in batch)
+    def _compile_checked(self, checked: list) -> tuple:
+        """_compile_events behind its checks (mixer.compile_tracks checks track by track and hands the tracks' events on as one list, one
+        row per event)."""
+        if not checked:
+            return [], np.zeros(0, dtype=N.MIX_LEVELS[N.LEVEL_CHAN].dtype), None, 0
+        bufs, table, segtab, _level = self._pack_events(checked, widest=True, share=True)
+        return bufs, table, segtab, max(e.start + e.nbytes for e in checked)
 
     def __unrolled(self, loop_start: int, loop_frames: int, nframes: int) -> "Sample":
         """A copy with the loop written out: frames [0, loop_start + loop_frames), then frames [loop_start, loop_start + loop_frames)
@@ -945,79 +961,70 @@ class Sample:
         out.__assemble(parts)
         return out
 
-    def _pack_events(self, batch: Sequence[tuple], envs: dict, extras: dict, widest: bool = False, share: bool = False) -> tuple:
-        """__mix_events' batch as the table an entry point reads, packed column by column: (the sources' device buffers, the table, the
-        segment table | None, weighed, turned, looped, shaped, panned, rated) -- the flags say which entry point the list needs.  The
-        table has the narrowest layout that holds the list; ``widest``: sh_mix_event_chan's with every column filled, whatever the
-        list holds (sh_seq_create takes that one layout and finds the level itself).  ``share``: the sources' buffers are taken with
-        _share_device, for a reader that keeps them."""
-        starts, others, nbytes, factors, inrates, pans, loops = zip(*batch)
-        w = self.__samplewidth
-        rate = self.__samplerate
-        starts = np.array(starts, dtype=np.uint64)
-        nbytes = np.array(nbytes, dtype=np.uint64)
-        inrates = np.array(inrates, dtype=np.uint64)
+    def _pack_events(self, batch: Sequence[_Event], widest: bool = False, share: bool = False) -> tuple:
+        """Checked events as the table an entry point reads, packed column by column (whole-array numpy operations, not a row per event):
+        (the sources' device buffers, the table, the segment table | None, the level).  The level is the highest of the rows' levels and
+        the table has that rung's layout, the narrowest that holds the list; ``widest``: the top rung, whatever the list holds
+        (sh_seq_create takes that one layout and finds the level itself).  A column group is filled from the rung up that first has it.
+        ``share``: the sources' buffers are taken with _share_device, for a reader that keeps them."""
+        col = dict(zip(_Event._fields, zip(*batch)))         # the records' fields as columns
+        w, nch, rate = self.__samplewidth, self.__nchannels, self.__samplerate
+        level = N.LEVEL_CHAN if widest else max(col["level"])
+        others, pans, weights = col["other"], col["pan"], col["weights"]
+        nbytes = np.array(col["nbytes"], dtype=np.uint64)
         slot = {}                                           # id(other) -> (index into srcs, other): one dict lookup per event, no more
         for o in others:
             slot.setdefault(id(o), (len(slot), o))
         uniq = [o for _k, o in slot.values()]
         bufs = [o._share_device() if share else o._device() for o in uniq]
         src = np.fromiter((slot[id(o)][0] for o in others), dtype=np.uint32, count=len(others))
-        rated = bool((inrates != rate).any())
-        panned = any(p is not None for p in pans)
-        shaped = bool(envs)
-        turned = cut = False
-        weighed = {}                                        # index into batch -> (left_factor, right_factor) of the events with channels
-        if extras:
-            weighed = {i: x[2] for i, x in extras.items() if len(x) > 2}
-            extras = {i: x[:2] for i, x in extras.items()}
-            turned = any(rv for _rg, rv in extras.values())
-            cut = any(rg is not None for rg, _rv in extras.values())
-        flagged = turned or bool(weighed)                   # a row with a flag: the table has sh_mix_event_rev's layout, which is the looped one's and more
-        looped = flagged or loops.count(None) != len(loops)
-        wide = widest or looped                             # the columns of the loop layout and beyond are there
-        table = np.zeros(len(batch), dtype=N.MIX_EVENT_CHAN_DTYPE if weighed or widest else N.MIX_EVENT_REV_DTYPE if turned else N.MIX_EVENT_LOOP_DTYPE if looped else N.MIX_EVENT_ENV_DTYPE if shaped else N.MIX_EVENT_PAN_DTYPE if panned else N.MIX_EVENT_RATE_DTYPE if rated else N.MIX_EVENT_DTYPE)
-        table["dst_sample"] = starts // w
+        table = np.zeros(len(batch), dtype=N.MIX_LEVELS[level].dtype)
+        table["dst_sample"] = np.array(col["start"], dtype=np.uint64) // w
         table["nsamples"] = nbytes // w
-        table["factor"] = factors
+        table["factor"] = [1.0 if v is None else float(v) for v in col["volume"]]
         table["src"] = src
-        if rated or panned or shaped or wide:
+        if level >= N.LEVEL_RATE:
             frames = np.array([o.__nbytes // (w * o.nchannels) for o in uniq], dtype=np.uint64)
             table["src_frames"] = frames[src]
-            table["inrate"] = inrates
+            table["inrate"] = np.array(col["inrate"], dtype=np.uint64)
             table["outrate"] = rate
-        if panned or shaped or wide:
+        if level >= N.LEVEL_PAN:
             table["src_channels"] = np.array([o.nchannels for o in uniq], dtype=np.uint32)[src]
             lr = np.array([p if p is not None else (0.0, 0.0) for p in pans], dtype=np.float64)
             table["left"] = lr[:, 0]
             table["right"] = lr[:, 1]
-        if cut:                                             # a slice of other: where it starts, and the frames every count above was made over
-            nch = np.array([o.nchannels for o in uniq], dtype=np.uint64)[src]
-            at = np.array([i for i, (rg, _rv) in extras.items() if rg is not None], dtype=np.intp)
-            rg = np.array([rg for rg, _rv in extras.values() if rg is not None], dtype=np.uint64)
-            table["src_sample"][at] = rg[:, 0] * nch[at]
-            if rated or panned or shaped or wide:
+        regions = col["region"]
+        if regions.count(None) != len(regions):             # a slice of other: where it starts, and the frames every count above was made over
+            at = [i for i, rg in enumerate(regions) if rg is not None]
+            src_nch = np.array([o.nchannels for o in uniq], dtype=np.uint64)[src]
+            rg = np.array([regions[i] for i in at], dtype=np.uint64)
+            table["src_sample"][at] = rg[:, 0] * src_nch[at]
+            if level >= N.LEVEL_RATE:
                 table["src_frames"][at] = rg[:, 1]
-        if wide:
-            lp = np.array([l if l is not None else (0, 0, 0) for l in loops], dtype=np.uint64)
+        if level >= N.LEVEL_LOOP:                           # (a row without a loop: loop_frames == 0)
+            lp = np.array([l if l is not None else (0, 0, 0) for l in col["loop"]], dtype=np.uint64)
             table["loop_start"] = lp[:, 0]
             table["loop_frames"] = lp[:, 1]
-            if turned:                                      # a reversed looped row plays the region's LAST loop_end frames: its region starts there
-                rv = np.array([i for i, (_rg, v) in extras.items() if v], dtype=np.intp)
-                table["flags"][rv] = N.MIX_EVENT_REVERSED
-                back = rv[lp[rv, 1] != 0]
-                table["src_sample"][back] += (table["src_frames"][back] - lp[back, 0] - lp[back, 1]) * table["src_channels"][back]
-            for i, (lf, rf) in weighed.items():             # a stereo source weighed per channel: tomono into a mono track, a balance in a stereo one
-                table["flags"][i] |= N.MIX_EVENT_DOWNMIX if self.__nchannels == 1 else N.MIX_EVENT_BALANCE
-                table["left"][i] = lf
-                table["right"][i] = rf
+        if level >= N.LEVEL_REV:                            # a reversed row names its region as stored, forwards -- a looped one the part of
+            rv = np.flatnonzero(col["reverse"])             # it in front of the loop's end, which is all it plays: its region starts there
+            table["flags"][rv] = N.MIX_EVENT_REVERSED
+            back = rv[lp[rv, 1] != 0]
+            table["src_sample"][back] += (table["src_frames"][back] - lp[back, 0] - lp[back, 1]) * table["src_channels"][back]
+        if level >= N.LEVEL_CHAN:                           # a stereo source weighed per channel: tomono into a mono track, a balance in a stereo one
+            for i, lf_rf in enumerate(weights):
+                if lf_rf is not None:
+                    table["flags"][i] |= N.MIX_EVENT_DOWNMIX if nch == 1 else N.MIX_EVENT_BALANCE
+                    table["left"][i], table["right"][i] = lf_rf
+        if level >= N.LEVEL_LOOP:
             table["src_frames"] = np.where(lp[:, 1] != 0, lp[:, 2], table["src_frames"])      # a looped row: the note's virtual frames
         segtab = None
-        if shaped or wide:
+        if level >= N.LEVEL_ENV:                            # the envelopes' rows, cut here where the event is
             rows = []
-            for i, g in envs.items():
+            for i, g in enumerate(col["segments"]):
+                if g is None:
+                    continue
                 taken = int(nbytes[i]) // w // (2 if pans[i] is not None else 1)       # the event's source samples, after other_seconds' cut
-                if i in weighed and self.__nchannels == 1:
+                if weights[i] is not None and nch == 1:
                     taken *= 2                                                          # (a downmix: two stereo samples per track sample)
                 mine = [(min(r[0], taken),) + r[1:] for r in g]
                 mine = [r for k, r in enumerate(mine) if r[0] > (mine[k - 1][0] if k else 0)]      # (what the cut leaves nothing of)
@@ -1025,30 +1032,17 @@ class Sample:
                 table["seg_count"][i] = len(mine)
                 rows.extend(mine)
             segtab = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
-            for name, col in zip(("end", "mul", "kind", "slope", "numsamples", "offset", "origin"), zip(*rows) if rows else [()] * 7):
-                segtab[name] = col
-        return bufs, table, segtab, weighed, turned, looped, shaped, panned, rated
+            for name, column in zip(("end", "mul", "kind", "slope", "numsamples", "offset", "origin"), zip(*rows) if rows else [()] * 7):
+                segtab[name] = column
+        return bufs, table, segtab, level
 
-    def __mix_events(self, batch: Sequence[tuple], envs: dict, extras: dict) -> None:
-        """The events (first byte, other, bytes, factor, inrate, tostereo factors | None, loop | None) -- none of them this sample -- folded in
-        order; length -> the furthest end.  inrate != the sample rate: the event plays ``other`` resampled from inrate to the sample
-        rate, and bytes counts resampled bytes; tostereo factors: ``other`` is mono, the track stereo, and bytes counts stereo bytes.
-        envs: index into batch -> _envelope_segments' rows of the events that have an envelope, cut here where the event is.
-        loop: (loop_start, loop_frames, virtual frames) of a looped event, in frames of ``other``; one of them and the list goes to
-        sh_mix_events_loop, the events without a loop as rows with loop_frames == 0.
-        extras: index into batch -> (region | None, reverse) of the events that have either.  region: (first frame, frames) of ``other``
-        that the event plays, which is what bytes, loop and the envelope's rows were counted over; it fills src_sample and src_frames
-        of the table the list has anyway.  reverse: one of them and the list goes to
-        sh_mix_events_rev, the rest as rows without the flag; a reversed row names its region as stored, forwards -- a looped one the
-        part of it in front of the loop's end, which is all it plays.  A third element, (left_factor, right_factor), is an event's
-        ``channels``: one of them and the list goes to sh_mix_events_chan, that row with SH_MIX_EVENT_DOWNMIX (a mono track; bytes counts
-        mono bytes, the envelope's rows the stereo samples) or SH_MIX_EVENT_BALANCE (a stereo one), the rest as rows without a mode.
-        The table is packed column by column (whole-array numpy operations, not a row per event)."""
+    def __mix_events(self, batch: Sequence[_Event]) -> None:
+        """Checked events -- none of them this sample's own -- folded in order, in one launch; length -> the furthest end."""
         if not batch:
             return
         w = self.__samplewidth
         n1 = self.__nbytes
-        total = max(n1, max(b[0] + b[2] for b in batch))    # first byte + bytes: the furthest end
+        total = max(n1, max(e.start + e.nbytes for e in batch))                 # the furthest end
         if total == 0:
             return
         if total == n1 and self._device().nbytes >= n1 and not self.__dev_shared:
@@ -1059,18 +1053,15 @@ class Sample:
                 track.zero(n1, total - n1)
             if n1:
                 N.check(N.lib().sh_buf_copy(track.handle, 0, self._device().handle, 0, n1))
-        bufs, table, segtab, weighed, turned, looped, shaped, panned, rated = self._pack_events(batch, envs, extras)
-        srcs = (C.c_void_p * len(bufs))(*[b.handle for b in bufs])
-        if shaped or looped:
-            entry = N.lib().sh_mix_events_chan if weighed else N.lib().sh_mix_events_rev if turned else N.lib().sh_mix_events_loop if looped else N.lib().sh_mix_events_env
-            N.check(entry(srcs, len(bufs), table.ctypes.data, len(table), segtab.ctypes.data, len(segtab), w,
-                          self.__nchannels, track.handle, total // w))
-        elif panned:
-            N.check(N.lib().sh_mix_events_pan(srcs, len(bufs), table.ctypes.data, len(table), w, track.handle, total // w))
-        elif rated:
-            N.check(N.lib().sh_mix_events_rate(srcs, len(bufs), table.ctypes.data, len(table), w, self.__nchannels, track.handle, total // w))
-        else:
-            N.check(N.lib().sh_mix_events(srcs, len(bufs), table.ctypes.data, len(table), w, track.handle, total // w))
+        bufs, table, segtab, level = self._pack_events(batch)
+        rung = N.MIX_LEVELS[level]
+        args = [(C.c_void_p * len(bufs))(*[b.handle for b in bufs]), len(bufs), table.ctypes.data, len(table)]
+        if rung.segments:
+            args += [segtab.ctypes.data, len(segtab)]
+        args.append(w)
+        if rung.nchannels:
+            args.append(self.__nchannels)
+        N.check(getattr(N.lib(), rung.entry)(*args, track.handle, total // w))
         self._set_device(track, total)                      # (in place: drops the host copy, it is stale now)
 
     # -- elementwise operations (upstream: thin wrappers over audioop) ---------------------------------
