@@ -8,9 +8,11 @@
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
+#include "pcmhost.hpp"
 #include <mutex>
 #include <string.h>
 #include <new>
+#include <type_traits>
 
 #define SH_PCM_CONST __attribute__((address_space(4)))
 
@@ -411,17 +413,6 @@ __global__ __launch_bounds__(256) void k_mix_chain_gather_w(const ChainSrcB* __r
         if (s0 + j < nsamples) chain_put<WIDTH>(out, s0 + j, acc[j]);
 }
 
-int fetch_flag(int* result) {
-    sh::State& s = sh::state();
-    SH_HIP(hipMemcpyAsync(s.flag_host, s.flag, sizeof(int), hipMemcpyDeviceToHost, s.stream));
-    SH_HIP(hipStreamSynchronize(s.stream));
-    *result = s.flag_host[0];
-    if (*result) {
-        SH_HIP(hipMemsetAsync(s.flag, 0, sizeof(int), s.stream));
-    }
-    return SH_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -430,61 +421,48 @@ int sh_quantize_f32(const sh_buf* in_f32, size_t in_off, size_t n, double scale,
                     sh_buf* out_pcm, size_t out_off) {
     SH_REQUIRE_INIT();
     if (!in_f32 || !out_pcm) return sh::set_error(SH_ERR_INVALID, "sh_quantize_f32: NULL argument");
-    if (width != 1 && width != 2 && width != 4) return sh::set_error(SH_ERR_INVALID, "sh_quantize_f32: width %d not in {1,2,4}", width);
+    if (!valid_width(width)) return bad_width("sh_quantize_f32", width);
     if (in_off > in_f32->bytes / 4 || n > in_f32->bytes / 4 - in_off) return sh::set_error(SH_ERR_INVALID, "sh_quantize_f32: input range outside buffer");
     if (out_off > out_pcm->bytes / width || n > out_pcm->bytes / width - out_off) return sh::set_error(SH_ERR_INVALID, "sh_quantize_f32: output range outside buffer");
     if (!n) return SH_OK;
     const double lo = -ldexp(1.0, 8 * width - 1), hi = ldexp(1.0, 8 * width - 1) - 1.0;
     const float* in = (const float*)in_f32->ptr + in_off;
-    const dim3 grid = sh::grid1d(n, 256);
     hipStream_t st = sh::state().stream;
     int* flag = sh::state().flag;
     const int rnd = sh::state().quantise_round;
-    if (width == 2) {
-        short* o = (short*)out_pcm->ptr + out_off;
-        const bool aligned = ((uintptr_t)in & 15) == 0 && ((uintptr_t)o & 7) == 0;
-        const size_t nvec = aligned ? n / 4 : 0, done = nvec * 4;
-        if (nvec) hipLaunchKernelGGL(k_quantize_f32_i16_vec, sh::grid1d(nvec, 512), dim3(256), 0, st, (const float4v*)in, nvec, scale, (short4v*)o, flag, 0, rnd);
-        if (n > done) hipLaunchKernelGGL(k_quantize<short>, sh::grid1d(n - done, 256), dim3(256), 0, st, in + done, n - done, scale, lo, hi, o + done, flag, 0, rnd);
-    }
-    else if (width == 1) hipLaunchKernelGGL(k_quantize<signed char>, grid, dim3(256), 0, st, in, n, scale, lo, hi, (signed char*)out_pcm->ptr + out_off, flag, 0, rnd);
-    else hipLaunchKernelGGL(k_quantize<int>, grid, dim3(256), 0, st, in, n, scale, lo, hi, (int*)out_pcm->ptr + out_off, flag, 0, rnd);
-    SH_CHECK_LAUNCH("k_quantize");
-    int overflow = 0;
-    int rc = fetch_flag(&overflow);
-    if (rc) return rc;
-    if (overflow) return sh::set_error(SH_ERR_OVERFLOW, "signed integer out of range for sample width %d", width);
-    return SH_OK;
+    const int rc = dispatch_width(width, [&](auto tag) {
+        typedef decltype(tag) T;
+        T* o = (T*)out_pcm->ptr + out_off;
+        const VecSplit s = vec_split(sizeof(T) == 2 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)o & 7) == 0, n, 4);      // the vector kernel is the 16-bit one
+        if (s.nvec) hipLaunchKernelGGL(k_quantize_f32_i16_vec, sh::grid1d(s.nvec, 512), dim3(256), 0, st, (const float4v*)in, s.nvec, scale, (short4v*)o, flag, 0, rnd);
+        if (s.rest) hipLaunchKernelGGL(k_quantize<T>, sh::grid1d(s.rest, 256), dim3(256), 0, st, in + s.done, s.rest, scale, lo, hi, o + s.done, flag, 0, rnd);
+        return launch_result("k_quantize");
+    });
+    return rc ? rc : take_overflow(width);
 }
 
 int sh_quantize_f64(const sh_buf* in_f64, size_t in_off, size_t n, double scale, int width,
                     sh_buf* out_pcm, size_t out_off) {
     SH_REQUIRE_INIT();
     if (!in_f64 || !out_pcm) return sh::set_error(SH_ERR_INVALID, "sh_quantize_f64: NULL argument");
-    if (width != 1 && width != 2 && width != 4) return sh::set_error(SH_ERR_INVALID, "sh_quantize_f64: width %d not in {1,2,4}", width);
+    if (!valid_width(width)) return bad_width("sh_quantize_f64", width);
     if (in_off > in_f64->bytes / 8 || n > in_f64->bytes / 8 - in_off) return sh::set_error(SH_ERR_INVALID, "sh_quantize_f64: input range outside buffer");
     if (out_off > out_pcm->bytes / width || n > out_pcm->bytes / width - out_off) return sh::set_error(SH_ERR_INVALID, "sh_quantize_f64: output range outside buffer");
     if (!n) return SH_OK;
     const double lo = -ldexp(1.0, 8 * width - 1), hi = ldexp(1.0, 8 * width - 1) - 1.0;
     const double* in = (const double*)in_f64->ptr + in_off;
-    const dim3 grid = sh::grid1d(n, 256);
     hipStream_t st = sh::state().stream;
     int* flag = sh::state().flag;
     const int rnd = sh::state().quantise_round;
-    if (width == 2) {
-        short* out = (short*)out_pcm->ptr + out_off;
-        const bool aligned = ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 3) == 0;
-        const size_t nvec = aligned ? n / 2 : 0, done = nvec * 2;
-        if (nvec) hipLaunchKernelGGL(k_quantize_f64_i16_vec, sh::grid1d(nvec, 512), dim3(256), 0, st, (const double2v*)in, nvec, scale, (short2v*)out, flag, rnd);
-        if (n > done) hipLaunchKernelGGL((k_quantize<short, double>), sh::grid1d(n - done, 256), dim3(256), 0, st, in + done, n - done, scale, lo, hi, out + done, flag, 0, rnd);
-    } else if (width == 1) hipLaunchKernelGGL((k_quantize<signed char, double>), grid, dim3(256), 0, st, in, n, scale, lo, hi, (signed char*)out_pcm->ptr + out_off, flag, 0, rnd);
-    else hipLaunchKernelGGL((k_quantize<int, double>), grid, dim3(256), 0, st, in, n, scale, lo, hi, (int*)out_pcm->ptr + out_off, flag, 0, rnd);
-    SH_CHECK_LAUNCH("k_quantize");
-    int overflow = 0;
-    int rc = fetch_flag(&overflow);
-    if (rc) return rc;
-    if (overflow) return sh::set_error(SH_ERR_OVERFLOW, "signed integer out of range for sample width %d", width);
-    return SH_OK;
+    const int rc = dispatch_width(width, [&](auto tag) {
+        typedef decltype(tag) T;
+        T* o = (T*)out_pcm->ptr + out_off;
+        const VecSplit s = vec_split(sizeof(T) == 2 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)o & 3) == 0, n, 2);      // the vector kernel is the 16-bit one
+        if (s.nvec) hipLaunchKernelGGL(k_quantize_f64_i16_vec, sh::grid1d(s.nvec, 512), dim3(256), 0, st, (const double2v*)in, s.nvec, scale, (short2v*)o, flag, rnd);
+        if (s.rest) hipLaunchKernelGGL((k_quantize<T, double>), sh::grid1d(s.rest, 256), dim3(256), 0, st, in + s.done, s.rest, scale, lo, hi, o + s.done, flag, 0, rnd);
+        return launch_result("k_quantize");
+    });
+    return rc ? rc : take_overflow(width);
 }
 
 int sh_quantize_clip_f32(const sh_buf* in_f32, size_t n, double scale, sh_buf* out_i16) {
@@ -495,10 +473,10 @@ int sh_quantize_clip_f32(const sh_buf* in_f32, size_t n, double scale, sh_buf* o
     {
         hipStream_t st = sh::state().stream;
         const bool aligned = ((uintptr_t)in_f32->ptr & 15) == 0 && ((uintptr_t)out_i16->ptr & 7) == 0;      // (a ring slot of odd length is not)
-        const size_t nvec = aligned ? n / 4 : 0, done = nvec * 4;
-        if (nvec) hipLaunchKernelGGL(k_quantize_f32_i16_vec, sh::grid1d(nvec, 512), dim3(256), 0, st, (const float4v*)in_f32->ptr, nvec, scale, (short4v*)out_i16->ptr, sh::state().flag, 1);
-        if (n > done) hipLaunchKernelGGL(k_quantize<short>, sh::grid1d(n - done, 256), dim3(256), 0, st,
-                                         (const float*)in_f32->ptr + done, n - done, scale, -32768.0, 32767.0, (short*)out_i16->ptr + done, sh::state().flag, 1);
+        const VecSplit s = vec_split(aligned, n, 4);
+        if (s.nvec) hipLaunchKernelGGL(k_quantize_f32_i16_vec, sh::grid1d(s.nvec, 512), dim3(256), 0, st, (const float4v*)in_f32->ptr, s.nvec, scale, (short4v*)out_i16->ptr, sh::state().flag, 1);
+        if (s.rest) hipLaunchKernelGGL(k_quantize<short>, sh::grid1d(s.rest, 256), dim3(256), 0, st,
+                                       (const float*)in_f32->ptr + s.done, s.rest, scale, -32768.0, 32767.0, (short*)out_i16->ptr + s.done, sh::state().flag, 1);
     }
     SH_CHECK_LAUNCH("k_quantize(clip)");
     return SH_OK;
@@ -506,29 +484,17 @@ int sh_quantize_clip_f32(const sh_buf* in_f32, size_t n, double scale, sh_buf* o
 
 static int pcm_add_dev(const char* a, const char* b, char* o, size_t nbytes, int width) {
     hipStream_t st = sh::state().stream;
-    const bool aligned = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)o) & 15) == 0;
-    size_t nvec = aligned ? nbytes / 16 : 0;
-    size_t done = nvec * 16;
-    if (nvec) {
-        const dim3 grid = sh::grid1d(nvec, 256);
-        const bool stream = 2 * nbytes > sh::STREAM_BYTES;
-#define SH_ADD(V_) do { if (stream) hipLaunchKernelGGL((k_add_vec<V_, true>), grid, dim3(256), 0, st, (const V_*)a, (const V_*)b, (V_*)o, nvec); \
-                        else hipLaunchKernelGGL((k_add_vec<V_, false>), grid, dim3(256), 0, st, (const V_*)a, (const V_*)b, (V_*)o, nvec); } while (0)
-        if (width == 2) SH_ADD(short8v);
-        else if (width == 4) SH_ADD(int4v);
-        else SH_ADD(char16v);
-#undef SH_ADD
-        SH_CHECK_LAUNCH("k_add_vec");
-    }
-    size_t rest = (nbytes - done) / width;
-    if (rest) {
-        const dim3 grid = sh::grid1d(rest, 256);
-        if (width == 2) hipLaunchKernelGGL(k_add_scalar<short>, grid, dim3(256), 0, st, (const short*)(a + done), (const short*)(b + done), (short*)(o + done), rest);
-        else if (width == 4) hipLaunchKernelGGL(k_add_scalar<int>, grid, dim3(256), 0, st, (const int*)(a + done), (const int*)(b + done), (int*)(o + done), rest);
-        else hipLaunchKernelGGL(k_add_scalar<signed char>, grid, dim3(256), 0, st, (const signed char*)(a + done), (const signed char*)(b + done), (signed char*)(o + done), rest);
-        SH_CHECK_LAUNCH("k_add_scalar");
-    }
-    return SH_OK;
+    return dispatch_width(width, [&](auto tag) {
+        typedef decltype(tag) T;
+        typedef typename std::conditional<sizeof(T) == 1, char16v, typename std::conditional<sizeof(T) == 2, short8v, int4v>::type>::type V;
+        const T *pa = (const T*)a, *pb = (const T*)b;
+        T* po = (T*)o;
+        const VecSplit s = vec_split((((uintptr_t)a | (uintptr_t)b | (uintptr_t)o) & 15) == 0, nbytes / sizeof(T), 16 / sizeof(T));
+        if (s.nvec && 2 * nbytes > sh::STREAM_BYTES) hipLaunchKernelGGL((k_add_vec<V, true>), sh::grid1d(s.nvec, 256), dim3(256), 0, st, (const V*)pa, (const V*)pb, (V*)po, s.nvec);
+        else if (s.nvec) hipLaunchKernelGGL((k_add_vec<V, false>), sh::grid1d(s.nvec, 256), dim3(256), 0, st, (const V*)pa, (const V*)pb, (V*)po, s.nvec);
+        if (s.rest) hipLaunchKernelGGL(k_add_scalar<T>, sh::grid1d(s.rest, 256), dim3(256), 0, st, pa + s.done, pb + s.done, po + s.done, s.rest);
+        return launch_result("k_add");
+    });
 }
 
 int sh_pcm_add(const sh_buf* a, size_t a_off, const sh_buf* b, size_t b_off, size_t nbytes, int width,
@@ -552,7 +518,7 @@ int sh_pcm_add(const sh_buf* a, size_t a_off, const sh_buf* b, size_t b_off, siz
         if (!rc) rc = sh::pack24((const int32_t*)ta.buf.ptr, n, 8, (char*)out->ptr + out_off);
         return rc;
     }
-    if (width != 1 && width != 2 && width != 4) return sh::set_error(SH_ERR_INVALID, "sh_pcm_add: width %d not in {1,2,4}", width);
+    if (!valid_width(width)) return bad_width("sh_pcm_add", width);
     if (nbytes % width) return sh::set_error(SH_ERR_INVALID, "sh_pcm_add: not a whole number of frames");
     if (a_off > a->bytes || nbytes > a->bytes - a_off || b_off > b->bytes || nbytes > b->bytes - b_off ||
         out_off > out->bytes || nbytes > out->bytes - out_off)
@@ -581,7 +547,7 @@ int sh_pcm_add_host(const void* a, const void* b, size_t nbytes, int width, void
         SH_HIP(hipStreamSynchronize(st3));
         return SH_OK;
     }
-    if (width != 1 && width != 2 && width != 4) return sh::set_error(SH_ERR_INVALID, "sh_pcm_add_host: width %d not in {1,2,4}", width);
+    if (!valid_width(width)) return bad_width("sh_pcm_add_host", width);
     if (nbytes % width) return sh::set_error(SH_ERR_INVALID, "sh_pcm_add_host: not a whole number of frames");
     if (!nbytes) return SH_OK;
     if (!a || !b || !out) return sh::set_error(SH_ERR_INVALID, "sh_pcm_add_host: NULL argument");

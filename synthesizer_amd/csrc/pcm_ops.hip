@@ -6,9 +6,9 @@
 // Built with -ffp-contract=off: audioop forms val1*lfactor + val2*rfactor with separate roundings.
 #include "common.hpp"
 #include "pcmdev.hpp"
+#include "pcmhost.hpp"
 #include <stdlib.h>
 #include <type_traits>
-#include <vector>
 
 namespace {
 
@@ -145,8 +145,9 @@ __global__ __launch_bounds__(256) void k_lin2lin(const TI* __restrict__ in, TO* 
     out[i] = (TO)(v32 >> (32 - 8 * (int)sizeof(TO)));
 }
 
-// reductions: acc[0] = max |v| (unsigned), acc[1] = sum v*v (u64, exact for widths 1 and 2)
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+// reductions over a wavefront, lane 0 holds the result
+template <typename A>
+__device__ __forceinline__ A wave_sum(A v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;
@@ -160,268 +161,123 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
     return v;
 }
 
-template <typename T, int INFLIGHT>
-__global__ __launch_bounds__(256) void k_absmax_sumsq(const T* __restrict__ in, size_t n, unsigned long long* __restrict__ acc) {
-    __shared__ unsigned long long s_sum[4];
-    __shared__ unsigned s_max[4];
-    unsigned mx = 0;
-    unsigned long long sq = 0;
+// lane 0 of each of the four waves has left its channel's maximum and sum in LDS: thread c < NCH folds channel c's four, the waves in
+// order, into out[c] = max, out[NCH + c] = sum (A = double: as its bit pattern)
+template <typename A, int NCH>
+__device__ __forceinline__ void stats_record(unsigned (&mx)[NCH], A (&sq)[NCH], unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long s_sum[4][NCH];
+    __shared__ unsigned s_max[4][NCH];
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        mx[c] = wave_max_u32(mx[c]);
+        sq[c] = wave_sum(sq[c]);
+        if (lane == 0) { s_sum[wave][c] = __builtin_bit_cast(unsigned long long, sq[c]); s_max[wave][c] = mx[c]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < NCH) {
+        const unsigned c = threadIdx.x;
+        unsigned m = s_max[0][c];
+        for (int w = 1; w < 4; ++w) m = s_max[w][c] > m ? s_max[w][c] : m;
+        A t = __builtin_bit_cast(A, s_sum[0][c]);
+        for (int w = 1; w < 4; ++w) t += __builtin_bit_cast(A, s_sum[w][c]);
+        out[c] = (unsigned long long)m;
+        out[NCH + c] = __builtin_bit_cast(unsigned long long, t);
+    }
+}
+
+// audioop.max and the sum of squares of audioop.rms, per channel of NCH interleaved ones, in one read.  (Stereo: Sample.level_db_peak /
+// level_db_rms -- upstream takes audioop.tomono(frames, w, 1, 0) and (.., 0, 1), two copies, and runs audioop.max / rms over each: four
+// passes and two temporaries.)  A 16-byte vector holds whole frames, so element c belongs to channel c mod NCH.
+// part[2 NCH b ..] = the workgroup's max |x| per channel, then its sums: u64, exact, for widths 1 and 2; for width 4, where squares
+// do not fit u64 sums exactly, float64 bit patterns -- the squares added per thread, then a fixed tree: close to, but not
+// bit-identical with, audioop's sequential float64 sum (documented).
+template <typename T, int NCH>
+__global__ __launch_bounds__(256) void k_pcm_stats(const T* __restrict__ in, size_t nframes, unsigned long long* __restrict__ part) {
+    typedef typename std::conditional<sizeof(T) == 4, double, unsigned long long>::type acc_t;
+    unsigned mx[NCH] = {};
+    acc_t sq[NCH] = {};
+    auto take = [&](int c, long long v) {
+        const unsigned a = (unsigned)(v < 0 ? -v : v);
+        mx[c] = a > mx[c] ? a : mx[c];
+        if constexpr (sizeof(T) == 4) sq[c] += (double)v * (double)v;
+        else sq[c] += (unsigned long long)(v * v);
+    };
     constexpr int V = 16 / sizeof(T);
     typedef T vec_t __attribute__((ext_vector_type(V)));
-    const size_t nvec = ((reinterpret_cast<uintptr_t>(in) & 15) == 0) ? n / V : 0;
+    const vec_t* vin = reinterpret_cast<const vec_t*>(in);
+    const size_t nvec = ((reinterpret_cast<uintptr_t>(in) & 15) == 0) ? nframes * NCH / V : 0;
+    const size_t step = (size_t)gridDim.x * 256;
     if constexpr (sizeof(T) == 2) {
         // 16-bit: packed arithmetic, two samples per instruction.  |x| = max(x, 0 - x) as int16 pairs, read as
-        // uint16 (so |-32768| = 32768 comes out right); running maximum as uint16 pairs; a pair's squares summed
-        // by the dot-product instruction (<= 2^31, fits uint32) and added to the 64-bit total.
+        // uint16 (so |-32768| = 32768 comes out right); running maximum as uint16 pairs; mono: a pair's squares summed
+        // by the dot-product instruction (<= 2^31, fits uint32) and added to the 64-bit total; stereo: a pair is a frame, one
+        // 24-bit multiply per channel.
         typedef short s2 __attribute__((ext_vector_type(2)));
         typedef unsigned short u2 __attribute__((ext_vector_type(2)));
         u2 mx2 = {0, 0};
-#define SH_PAIR(X_, A_, B_)                                                            \
-            {                                                                            \
-                const s2 v = __builtin_shufflevector(X_, X_, A_, B_);                    \
-                const s2 neg = (s2){0, 0} - v;                                           \
-                const u2 au = __builtin_bit_cast(u2, __builtin_elementwise_max(v, neg)); \
-                mx2 = __builtin_elementwise_max(mx2, au);                                \
-                sq += (unsigned long long)__builtin_amdgcn_udot2(au, au, 0u, false);     \
-            }
+        auto pair = [&](const s2 v) {
+            const s2 neg = (s2){0, 0} - v;
+            const u2 au = __builtin_bit_cast(u2, __builtin_elementwise_max(v, neg));
+            mx2 = __builtin_elementwise_max(mx2, au);
+            if constexpr (NCH == 1) sq[0] += (unsigned long long)__builtin_amdgcn_udot2(au, au, 0u, false);
+            else { sq[0] += (unsigned long long)__umul24(au[0], au[0]); sq[1] += (unsigned long long)__umul24(au[1], au[1]); }
+        };
+        auto pairs = [&](const vec_t x) {
+            pair(__builtin_shufflevector(x, x, 0, 1)); pair(__builtin_shufflevector(x, x, 2, 3));
+            pair(__builtin_shufflevector(x, x, 4, 5)); pair(__builtin_shufflevector(x, x, 6, 7));
+        };
         // a workgroup reads INFLIGHT * 4 KB contiguous per turn (the loads in flight are neighbours, not a grid apart:
         // the whole chip then sweeps one window of memory at a time, which the DRAM pages like)
-        const size_t step = (size_t)gridDim.x * 256 * INFLIGHT;
+        constexpr int INFLIGHT = 4;
         size_t i = (size_t)blockIdx.x * 256 * INFLIGHT + threadIdx.x;
-        for (; i + (INFLIGHT - 1) * 256 < nvec; i += step) {
+        for (; i + (INFLIGHT - 1) * 256 < nvec; i += step * INFLIGHT) {
             vec_t x[INFLIGHT];
 #pragma unroll
-            for (int k = 0; k < INFLIGHT; ++k) x[k] = __builtin_nontemporal_load(reinterpret_cast<const vec_t*>(in) + i + k * 256);
+            for (int k = 0; k < INFLIGHT; ++k) x[k] = __builtin_nontemporal_load(vin + i + k * 256);
 #pragma unroll
-            for (int k = 0; k < INFLIGHT; ++k) { SH_PAIR(x[k], 0, 1) SH_PAIR(x[k], 2, 3) SH_PAIR(x[k], 4, 5) SH_PAIR(x[k], 6, 7) }
+            for (int k = 0; k < INFLIGHT; ++k) pairs(x[k]);
         }
         if (i < nvec) {                                            // the last, partial turn of this workgroup
 #pragma unroll
-            for (int k = 0; k < INFLIGHT; ++k) {
-                if (i + k * 256 < nvec) {
-                    const vec_t x = reinterpret_cast<const vec_t*>(in)[i + k * 256];
-                    SH_PAIR(x, 0, 1) SH_PAIR(x, 2, 3) SH_PAIR(x, 4, 5) SH_PAIR(x, 6, 7)
-                }
-            }
+            for (int k = 0; k < INFLIGHT; ++k)
+                if (i + k * 256 < nvec) pairs(vin[i + k * 256]);
         }
-#undef SH_PAIR
-        mx = mx2[0] > mx2[1] ? mx2[0] : mx2[1];
-    } else {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-        const vec_t x = reinterpret_cast<const vec_t*>(in)[i];
-#pragma unroll
-        for (int c = 0; c < V; ++c) {
-            const long long v = (long long)x[c];
-            const unsigned a = (unsigned)(v < 0 ? -v : v);
-            mx = a > mx ? a : mx;
-            sq += (unsigned long long)(v * v);
-        }
-    }
-    }
-    for (size_t i = nvec * V + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const long long v = (long long)in[i];
-        const unsigned a = (unsigned)(v < 0 ? -v : v);
-        mx = a > mx ? a : mx;
-        sq += (unsigned long long)(v * v);
-    }
-    mx = wave_max_u32(mx);
-    sq = wave_sum_u64(sq);
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { s_sum[wave] = sq; s_max[wave] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-        unsigned m = s_max[0];
-        for (int w = 1; w < 4; ++w) m = s_max[w] > m ? s_max[w] : m;
-        // per-workgroup results, folded by k_stats_fold: thousands of atomics on two addresses serialise (10 ns each,
-        // 40 % of this kernel's time at 4096 workgroups)
-        acc[2 * blockIdx.x] = (unsigned long long)m;
-        acc[2 * blockIdx.x + 1] = t;
-    }
-}
-
-// one workgroup: out[0] = max, out[1] = sum over the per-workgroup pairs (integer: exact, order-independent)
-__global__ __launch_bounds__(256) void k_stats_fold(const unsigned long long* __restrict__ part, unsigned nblocks,
-                                                    unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long s_sum[4];
-    __shared__ unsigned s_max[4];
-    unsigned mx = 0;
-    unsigned long long sq = 0;
-    for (unsigned b = threadIdx.x; b < nblocks; b += 256) {
-        const unsigned m = (unsigned)part[2 * b];
-        mx = m > mx ? m : mx;
-        sq += part[2 * b + 1];
-    }
-    mx = wave_max_u32(mx);
-    sq = wave_sum_u64(sq);
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { s_sum[wave] = sq; s_max[wave] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned m = s_max[0];
-        for (int w = 1; w < 4; ++w) m = s_max[w] > m ? s_max[w] : m;
-        out[0] = (unsigned long long)m;
-        out[1] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-    }
-}
-
-// Interleaved stereo, both channels in one pass (Sample.level_db_peak / level_db_rms: upstream takes
-// audioop.tomono(frames, w, 1, 0) and (.., 0, 1), two copies, and runs audioop.max / rms over each -- four passes and
-// two temporaries; here: one read).  A 16-byte vector holds whole frames, so even elements are left, odd right.
-// part[4b..4b+3] = max|L|, max|R|, sum L^2, sum R^2; for width 4 the sums are float64 bit patterns.
-template <typename T>
-__global__ __launch_bounds__(256) void k_stats_stereo(const T* __restrict__ in, size_t nframes, unsigned long long* __restrict__ part) {
-    __shared__ unsigned long long s_sum[4][2];
-    __shared__ unsigned s_max[4][2];
-    typedef typename std::conditional<sizeof(T) == 4, double, unsigned long long>::type acc_t;
-    unsigned mxl = 0, mxr = 0;
-    acc_t sql = 0, sqr = 0;
-    constexpr int V = 16 / sizeof(T);
-    typedef T vec_t __attribute__((ext_vector_type(V)));
-    const size_t n = nframes * 2;
-    const size_t nvec = ((reinterpret_cast<uintptr_t>(in) & 15) == 0) ? n / V : 0;
-    const size_t step = (size_t)gridDim.x * 256;
-    if constexpr (sizeof(T) == 2) {
-        typedef short s2 __attribute__((ext_vector_type(2)));
-        typedef unsigned short u2 __attribute__((ext_vector_type(2)));
-        u2 mx2 = {0, 0};
-#define SH_FRAME(X_, A_, B_)                                                             \
-            {                                                                            \
-                const s2 v = __builtin_shufflevector(X_, X_, A_, B_);                    \
-                const s2 neg = (s2){0, 0} - v;                                           \
-                const u2 au = __builtin_bit_cast(u2, __builtin_elementwise_max(v, neg)); \
-                mx2 = __builtin_elementwise_max(mx2, au);                                \
-                sql += (unsigned long long)__umul24(au[0], au[0]);                       \
-                sqr += (unsigned long long)__umul24(au[1], au[1]);                       \
-            }
-        constexpr int INFLIGHT = 4;                                 // neighbouring loads, as in k_absmax_sumsq
-        const size_t bstep = step * INFLIGHT;
-        size_t i = (size_t)blockIdx.x * 256 * INFLIGHT + threadIdx.x;
-        for (; i + (INFLIGHT - 1) * 256 < nvec; i += bstep) {
-            vec_t x[INFLIGHT];
-#pragma unroll
-            for (int k = 0; k < INFLIGHT; ++k) x[k] = __builtin_nontemporal_load(reinterpret_cast<const vec_t*>(in) + i + k * 256);
-#pragma unroll
-            for (int k = 0; k < INFLIGHT; ++k) { SH_FRAME(x[k], 0, 1) SH_FRAME(x[k], 2, 3) SH_FRAME(x[k], 4, 5) SH_FRAME(x[k], 6, 7) }
-        }
-        if (i < nvec) {
-#pragma unroll
-            for (int k = 0; k < INFLIGHT; ++k) {
-                if (i + k * 256 < nvec) {
-                    const vec_t x = reinterpret_cast<const vec_t*>(in)[i + k * 256];
-                    SH_FRAME(x, 0, 1) SH_FRAME(x, 2, 3) SH_FRAME(x, 4, 5) SH_FRAME(x, 6, 7)
-                }
-            }
-        }
-#undef SH_FRAME
-        mxl = mx2[0];
-        mxr = mx2[1];
+        if constexpr (NCH == 1) mx[0] = mx2[0] > mx2[1] ? mx2[0] : mx2[1];
+        else { mx[0] = mx2[0]; mx[1] = mx2[1]; }
     } else {
         for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += step) {
-            const vec_t x = reinterpret_cast<const vec_t*>(in)[i];
+            const vec_t x = vin[i];
 #pragma unroll
-            for (int c = 0; c < V; c += 2) {
-                const long long l = (long long)x[c], r = (long long)x[c + 1];
-                const unsigned al = (unsigned)(l < 0 ? -l : l), ar = (unsigned)(r < 0 ? -r : r);
-                mxl = al > mxl ? al : mxl;
-                mxr = ar > mxr ? ar : mxr;
-                if constexpr (sizeof(T) == 4) { sql += (double)l * (double)l; sqr += (double)r * (double)r; }
-                else { sql += (unsigned long long)(l * l); sqr += (unsigned long long)(r * r); }
-            }
+            for (int c = 0; c < V; ++c) take(c % NCH, (long long)x[c]);
         }
     }
-    for (size_t f = nvec * V / 2 + (size_t)blockIdx.x * 256 + threadIdx.x; f < nframes; f += step) {
-        const long long l = (long long)in[2 * f], r = (long long)in[2 * f + 1];
-        const unsigned al = (unsigned)(l < 0 ? -l : l), ar = (unsigned)(r < 0 ? -r : r);
-        mxl = al > mxl ? al : mxl;
-        mxr = ar > mxr ? ar : mxr;
-        if constexpr (sizeof(T) == 4) { sql += (double)l * (double)l; sqr += (double)r * (double)r; }
-        else { sql += (unsigned long long)(l * l); sqr += (unsigned long long)(r * r); }
-    }
-    mxl = wave_max_u32(mxl);
-    mxr = wave_max_u32(mxr);
-    if constexpr (sizeof(T) == 4) {
+    for (size_t f = nvec * V / NCH + (size_t)blockIdx.x * 256 + threadIdx.x; f < nframes; f += step) {
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { sql += __shfl_down(sql, o, 64); sqr += __shfl_down(sqr, o, 64); }
-    } else {
-        sql = wave_sum_u64(sql);
-        sqr = wave_sum_u64(sqr);
+        for (int c = 0; c < NCH; ++c) take(c, (long long)in[NCH * f + c]);
     }
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_sum[wave][0] = __builtin_bit_cast(unsigned long long, sql);
-        s_sum[wave][1] = __builtin_bit_cast(unsigned long long, sqr);
-        s_max[wave][0] = mxl;
-        s_max[wave][1] = mxr;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        const unsigned c = threadIdx.x;
-        unsigned m = s_max[0][c];
-        for (int w = 1; w < 4; ++w) m = s_max[w][c] > m ? s_max[w][c] : m;
-        acc_t t = __builtin_bit_cast(acc_t, s_sum[0][c]);
-        for (int w = 1; w < 4; ++w) t += __builtin_bit_cast(acc_t, s_sum[w][c]);
-        part[4 * (size_t)blockIdx.x + c] = (unsigned long long)m;
-        part[4 * (size_t)blockIdx.x + 2 + c] = __builtin_bit_cast(unsigned long long, t);
-    }
+    // per-workgroup records, folded by k_pcm_stats_fold: thousands of atomics on two addresses serialise (10 ns each,
+    // 40 % of this kernel's time at 4096 workgroups)
+    stats_record<acc_t, NCH>(mx, sq, part + 2 * NCH * (size_t)blockIdx.x);
 }
 
-// one workgroup: out[0..3] = max L, max R, sum L^2, sum R^2 over the per-workgroup quadruples (F64: sums are float64,
-// added in a fixed order: thread t takes workgroups t, t+256, ...; then the 64-lane tree; then the four waves)
-template <bool F64>
-__global__ __launch_bounds__(256) void k_stats_fold_stereo(const unsigned long long* __restrict__ part, unsigned nblocks,
-                                                           unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long s_sum[4][2];
-    __shared__ unsigned s_max[4][2];
+// one workgroup: out = the records of nblocks workgroups folded into one (integer sums: exact, order-independent; F64: the sums are
+// float64, added in a fixed order: thread t takes workgroups t, t+256, ...; then the 64-lane tree; then the four waves)
+template <int NCH, bool F64>
+__global__ __launch_bounds__(256) void k_pcm_stats_fold(const unsigned long long* __restrict__ part, unsigned nblocks,
+                                                        unsigned long long* __restrict__ out) {
     typedef typename std::conditional<F64, double, unsigned long long>::type acc_t;
-    unsigned mxl = 0, mxr = 0;
-    acc_t sql = 0, sqr = 0;
+    unsigned mx[NCH] = {};
+    acc_t sq[NCH] = {};
     for (unsigned b = threadIdx.x; b < nblocks; b += 256) {
-        const unsigned ml = (unsigned)part[4 * b], mr = (unsigned)part[4 * b + 1];
-        mxl = ml > mxl ? ml : mxl;
-        mxr = mr > mxr ? mr : mxr;
-        sql += __builtin_bit_cast(acc_t, part[4 * b + 2]);
-        sqr += __builtin_bit_cast(acc_t, part[4 * b + 3]);
-    }
-    mxl = wave_max_u32(mxl);
-    mxr = wave_max_u32(mxr);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sql += __shfl_down(sql, o, 64); sqr += __shfl_down(sqr, o, 64); }
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_sum[wave][0] = __builtin_bit_cast(unsigned long long, sql);
-        s_sum[wave][1] = __builtin_bit_cast(unsigned long long, sqr);
-        s_max[wave][0] = mxl;
-        s_max[wave][1] = mxr;
+        for (int c = 0; c < NCH; ++c) {
+            const unsigned m = (unsigned)part[2 * NCH * b + c];
+            mx[c] = m > mx[c] ? m : mx[c];
+            sq[c] += __builtin_bit_cast(acc_t, part[2 * NCH * b + NCH + c]);
+        }
     }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        const unsigned c = threadIdx.x;
-        unsigned m = s_max[0][c];
-        for (int w = 1; w < 4; ++w) m = s_max[w][c] > m ? s_max[w][c] : m;
-        acc_t t = __builtin_bit_cast(acc_t, s_sum[0][c]);
-        for (int w = 1; w < 4; ++w) t += __builtin_bit_cast(acc_t, s_sum[w][c]);
-        out[c] = (unsigned long long)m;
-        out[2 + c] = __builtin_bit_cast(unsigned long long, t);
-    }
-}
-
-// width 4: squares do not fit u64 sums exactly; accumulate the squares in float64 per thread, then a fixed
-// tree -- close to, but not bit-identical with, audioop's sequential float64 sum (documented).
-__global__ __launch_bounds__(256) void k_sumsq_f64(const int* __restrict__ in, size_t n, double* __restrict__ part) {
-    __shared__ double s[256];
-    double sq = 0.0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const double v = (double)in[i];
-        sq += v * v;
-    }
-    s[threadIdx.x] = sq;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = s[0];
+    stats_record<acc_t, NCH>(mx, sq, out);
 }
 
 // 24-bit <-> 32-bit: a thread converts four samples (12 bytes <-> 16 bytes); the 12 bytes are read / written as three
@@ -468,24 +324,6 @@ __global__ __launch_bounds__(256) void k_pack24(const int* __restrict__ in, size
     }
 }
 
-template <typename F>
-int dispatch_width(int width, F&& f) {
-    if (width == 1) return f((signed char)0);
-    if (width == 2) return f((short)0);
-    if (width == 4) return f((int)0);
-    return sh::set_error(SH_ERR_INVALID, "sample width %d not in {1,2,4}", width);
-}
-
-inline bool valid_width(int width) { return width == 1 || width == 2 || width == 4; }      // (width 3 is diverted to the 32-bit kernels before this test)
-int bad_width(const char* who, int width) { return sh::set_error(SH_ERR_INVALID, "%s: sample width %d not in {1,2,4}", who, width); }
-
-int check_io(const sh_buf* in, size_t in_off, size_t in_bytes, const sh_buf* out, size_t out_off, size_t out_bytes, const char* who) {
-    if (!in || !out) return sh::set_error(SH_ERR_INVALID, "%s: NULL buffer", who);
-    if (in_off > in->bytes || in_bytes > in->bytes - in_off) return sh::set_error(SH_ERR_INVALID, "%s: input range outside buffer", who);
-    if (out_off > out->bytes || out_bytes > out->bytes - out_off) return sh::set_error(SH_ERR_INVALID, "%s: output range outside buffer", who);
-    return SH_OK;
-}
-
 }  // namespace
 
 namespace sh {
@@ -511,11 +349,10 @@ namespace {
 template <typename F>
 int via32(const sh_buf* in, size_t in_off, size_t nin, int shift_in, sh_buf* out, size_t out_off, size_t nout, int shift_out,
           bool inplace, const char* who, F&& op32) {
-    if (!in || !out) return sh::set_error(SH_ERR_INVALID, "%s: NULL buffer", who);
-    if (in_off > in->bytes || nin * 3 > in->bytes - in_off) return sh::set_error(SH_ERR_INVALID, "%s: input range outside buffer", who);
-    if (out_off > out->bytes || nout * 3 > out->bytes - out_off) return sh::set_error(SH_ERR_INVALID, "%s: output range outside buffer", who);
+    int rc = check_io(in, in_off, nin * 3, out, out_off, nout * 3, who);
+    if (rc) return rc;
     sh::Temp tin, tout;
-    int rc = tin.alloc(nin * 4);
+    rc = tin.alloc(nin * 4);
     if (rc) return rc;
     if (!inplace) { rc = tout.alloc(nout * 4); if (rc) return rc; }
     rc = sh::unpack24((const char*)in->ptr + in_off, nin, shift_in, (int32_t*)tin.buf.ptr);
@@ -524,6 +361,52 @@ int via32(const sh_buf* in, size_t in_off, size_t nin, int shift_in, sh_buf* out
     rc = op32(&tin.buf, o32);
     if (rc) return rc;
     return sh::pack24((const int32_t*)o32->ptr, nout, shift_out, (char*)out->ptr + out_off);
+}
+
+// sh_pcm_stats (NCH 1) and sh_pcm_stats_stereo (NCH 2): max |x| and the sum of squares per channel over nframes frames of a width the
+// caller has checked, into max_abs[NCH] / sum_squares[NCH] (either may be NULL).  A refusal leaves them alone.
+template <int NCH>
+int pcm_stats(const char* who, const sh_buf* in, size_t nframes, int width, uint32_t* max_abs, double* sum_squares) {
+    if (!in || nframes > in->bytes / (NCH * (size_t)width)) return sh::set_error(SH_ERR_INVALID, "%s: range outside buffer", who);
+    const size_t n = nframes * NCH;
+    if (width == 3) {                           // the raw 24-bit values as int32
+        sh::Temp t32;
+        int rc3 = t32.alloc(n * 4);
+        if (rc3) return rc3;
+        rc3 = sh::unpack24(in->ptr, n, 0, (int32_t*)t32.buf.ptr);
+        if (rc3) return rc3;
+        return pcm_stats<NCH>(who, &t32.buf, nframes, 4, max_abs, sum_squares);
+    }
+    for (int c = 0; c < NCH; ++c) {
+        if (max_abs) max_abs[c] = 0;
+        if (sum_squares) sum_squares[c] = 0.0;
+    }
+    if (!n) return SH_OK;
+    // 512 workgroups x 4 neighbouring 16-byte loads in flight per lane: 6.0 TB/s on 900 MB; 4096 workgroups with the four
+    // loads a grid apart read the same data at 4.2-4.8 (DESIGN.md section 4 item 15)
+    const unsigned blocks = n / 8192 < 512 ? (unsigned)(n / 8192 + 1) : 512u;
+    constexpr size_t R = 2 * NCH;                                                // words of a record: a maximum and a sum per channel
+    int rc = sh::ensure_scratch((1 + (size_t)blocks) * R * 8);
+    if (rc) return rc;
+    hipStream_t st = sh::state().stream;
+    unsigned long long* acc = (unsigned long long*)sh::state().scratch;          // the result's record; then one per workgroup
+    rc = dispatch_width(width, [&](auto tag) {
+        typedef decltype(tag) T;
+        hipLaunchKernelGGL((k_pcm_stats<T, NCH>), dim3(blocks), dim3(256), 0, st, (const T*)in->ptr, nframes, acc + R);
+        return launch_result("k_pcm_stats");
+    });
+    if (rc) return rc;
+    if (width == 4) hipLaunchKernelGGL((k_pcm_stats_fold<NCH, true>), dim3(1), dim3(256), 0, st, (const unsigned long long*)(acc + R), blocks, acc);
+    else hipLaunchKernelGGL((k_pcm_stats_fold<NCH, false>), dim3(1), dim3(256), 0, st, (const unsigned long long*)(acc + R), blocks, acc);
+    SH_CHECK_LAUNCH("k_pcm_stats_fold");
+    unsigned long long host_acc[R];
+    SH_HIP(hipMemcpyAsync(host_acc, acc, sizeof host_acc, hipMemcpyDeviceToHost, st));
+    SH_HIP(hipStreamSynchronize(st));
+    for (int c = 0; c < NCH; ++c) {
+        if (max_abs) max_abs[c] = (uint32_t)host_acc[c];
+        if (sum_squares) sum_squares[c] = width == 4 ? __builtin_bit_cast(double, host_acc[NCH + c]) : (double)host_acc[NCH + c];
+    }
+    return SH_OK;
 }
 }  // namespace
 
@@ -542,19 +425,17 @@ int sh_pcm_mul(const sh_buf* in, size_t in_off, size_t nbytes, int width, double
     if (rc) return rc;
     if (nbytes % width || (in_off | out_off) % width) return sh::set_error(SH_ERR_INVALID, "sh_pcm_mul: not a whole number of frames");
     if (!nbytes) return SH_OK;
-    const char* ip = (const char*)in->ptr + in_off;
-    char* op = (char*)out->ptr + out_off;
     hipStream_t st = sh::state().stream;
     return dispatch_width(width, [&](auto tag) {
         typedef decltype(tag) T;
         constexpr int V = 16 / sizeof(T);
-        const bool aligned = (((uintptr_t)ip | (uintptr_t)op) & 15) == 0;
-        size_t nvec = aligned ? nbytes / 16 : 0, done = nvec * 16, rest = (nbytes - done) / sizeof(T);
-        if (nvec && nbytes > sh::STREAM_BYTES) hipLaunchKernelGGL((k_mul<T, V, true>), sh::grid1d(nvec, 256), dim3(256), 0, st, (const T*)ip, (T*)op, nvec, factor);
-        else if (nvec) hipLaunchKernelGGL((k_mul<T, V, false>), sh::grid1d(nvec, 256), dim3(256), 0, st, (const T*)ip, (T*)op, nvec, factor);
-        if (rest) hipLaunchKernelGGL((k_mul<T, 1>), sh::grid1d(rest, 256), dim3(256), 0, st, (const T*)(ip + done), (T*)(op + done), rest, factor);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_mul");
+        const T* ip = (const T*)((const char*)in->ptr + in_off);
+        T* op = (T*)((char*)out->ptr + out_off);
+        const VecSplit s = vec_split((((uintptr_t)ip | (uintptr_t)op) & 15) == 0, nbytes / sizeof(T), V);
+        if (s.nvec && nbytes > sh::STREAM_BYTES) hipLaunchKernelGGL((k_mul<T, V, true>), sh::grid1d(s.nvec, 256), dim3(256), 0, st, ip, op, s.nvec, factor);
+        else if (s.nvec) hipLaunchKernelGGL((k_mul<T, V, false>), sh::grid1d(s.nvec, 256), dim3(256), 0, st, ip, op, s.nvec, factor);
+        if (s.rest) hipLaunchKernelGGL((k_mul<T, 1>), sh::grid1d(s.rest, 256), dim3(256), 0, st, ip + s.done, op + s.done, s.rest, factor);
+        return launch_result("k_mul");
     });
 }
 
@@ -572,8 +453,7 @@ int sh_pcm_fade(const sh_buf* in, size_t in_off, size_t nbytes, int width, int f
         typedef decltype(tag) T;
         hipLaunchKernelGGL(k_fade<T>, sh::grid1d(n, 256), dim3(256), 0, st, (const T*)((const char*)in->ptr + in_off),
                            (T*)((char*)out->ptr + out_off), n, slope, (double)nbytes / (double)width, offset, fadeout);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_fade");
+        return launch_result("k_fade");
     });
 }
 
@@ -591,22 +471,14 @@ int sh_pcm_modulate(const sh_buf* in, size_t nbytes, int width, const sh_buf* mo
         typedef decltype(tag) T;
         hipLaunchKernelGGL(k_modulate<T>, sh::grid1d(n, 256), dim3(256), 0, S.stream, (const T*)in->ptr, (T*)out->ptr, n,
                            (const double*)mod_f64->ptr, nmod, S.flag);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_modulate");
+        return launch_result("k_modulate");
     });
-    if (rc) return rc;
-    SH_HIP(hipMemcpyAsync(S.flag_host, S.flag, sizeof(int), hipMemcpyDeviceToHost, S.stream));
-    SH_HIP(hipStreamSynchronize(S.stream));
-    if (S.flag_host[0]) {
-        SH_HIP(hipMemsetAsync(S.flag, 0, sizeof(int), S.stream));
-        return sh::set_error(SH_ERR_OVERFLOW, "signed integer out of range for sample width %d", width);
-    }
-    return SH_OK;
+    return rc ? rc : take_overflow(width);
 }
 
 int sh_pcm_pan_lfo(const sh_buf* in, size_t nframes, int width, int nchannels, const sh_buf* pan_f64, sh_buf* out) {
     SH_REQUIRE_INIT();
-    if (width != 1 && width != 2 && width != 4) return sh::set_error(SH_ERR_INVALID, "sh_pcm_pan_lfo: width %d not in {1,2,4}", width);
+    if (!valid_width(width)) return bad_width("sh_pcm_pan_lfo", width);
     if (nchannels != 1 && nchannels != 2) return sh::set_error(SH_ERR_INVALID, "sh_pcm_pan_lfo: %d channels (1 or 2)", nchannels);
     int rc = check_io(in, 0, nframes * width * nchannels, out, 0, nframes * width * 2, "sh_pcm_pan_lfo");
     if (rc) return rc;
@@ -621,22 +493,14 @@ int sh_pcm_pan_lfo(const sh_buf* in, size_t nframes, int width, int nchannels, c
         if (nchannels == 1) { if (pair) SH_PAN(1, true); else SH_PAN(1, false); }
         else { if (pair) SH_PAN(2, true); else SH_PAN(2, false); }
 #undef SH_PAN
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_pan_lfo");
+        return launch_result("k_pan_lfo");
     });
-    if (rc) return rc;
-    SH_HIP(hipMemcpyAsync(S.flag_host, S.flag, sizeof(int), hipMemcpyDeviceToHost, S.stream));
-    SH_HIP(hipStreamSynchronize(S.stream));
-    if (S.flag_host[0]) {
-        SH_HIP(hipMemsetAsync(S.flag, 0, sizeof(int), S.stream));
-        return sh::set_error(SH_ERR_OVERFLOW, "signed integer out of range for sample width %d", width);
-    }
-    return SH_OK;
+    return rc ? rc : take_overflow(width);
 }
 
 int sh_pcm_to_f64(const sh_buf* in, size_t nsamples, int width, double divisor, sh_buf* out_f64) {
     SH_REQUIRE_INIT();
-    if (width != 1 && width != 2 && width != 4) return sh::set_error(SH_ERR_INVALID, "sh_pcm_to_f64: width %d not in {1,2,4}", width);
+    if (!valid_width(width)) return bad_width("sh_pcm_to_f64", width);
     int rc = check_io(in, 0, nsamples * width, out_f64, 0, nsamples * 8, "sh_pcm_to_f64");
     if (rc) return rc;
     if (!(divisor != 0.0)) return sh::set_error(SH_ERR_INVALID, "sh_pcm_to_f64: divisor is zero");
@@ -645,8 +509,7 @@ int sh_pcm_to_f64(const sh_buf* in, size_t nsamples, int width, double divisor, 
     return dispatch_width(width, [&](auto tag) {
         typedef decltype(tag) T;
         hipLaunchKernelGGL(k_to_f64<T>, sh::grid1d(nsamples, 256), dim3(256), 0, st, (const T*)in->ptr, (double*)out_f64->ptr, nsamples, divisor);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_to_f64");
+        return launch_result("k_to_f64");
     });
 }
 
@@ -668,8 +531,7 @@ int sh_pcm_bias(const sh_buf* in, size_t nbytes, int width, int bias, sh_buf* ou
     return dispatch_width(width, [&](auto tag) {
         typedef decltype(tag) T;
         hipLaunchKernelGGL(k_bias<T>, sh::grid1d(n, 256), dim3(256), 0, st, (const T*)in->ptr, (T*)out->ptr, n, bias);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_bias");
+        return launch_result("k_bias");
     });
 }
 
@@ -691,8 +553,7 @@ int sh_pcm_reverse(const sh_buf* in, size_t nbytes, int width, sh_buf* out) {
     return dispatch_width(width, [&](auto tag) {
         typedef decltype(tag) T;
         hipLaunchKernelGGL(k_reverse<T>, sh::grid1d(n, 256), dim3(256), 0, st, (const T*)in->ptr, (T*)out->ptr, n);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_reverse");
+        return launch_result("k_reverse");
     });
 }
 
@@ -713,14 +574,13 @@ int sh_pcm_tomono(const sh_buf* in, size_t nframes, int width, double lfactor, d
         // one-frame kernel's two-sample load only where a frame is)
         const bool aligned = ((uintptr_t)in->ptr & 15) == 0 && ((uintptr_t)out->ptr & 7) == 0;
         const bool pair = ((uintptr_t)in->ptr & (2 * sizeof(T) - 1)) == 0;
-        const size_t nvec = aligned ? nframes / F : 0, done = nvec * F;
-        if (nvec) hipLaunchKernelGGL((k_tomono<T, F>), sh::grid1d(nvec, 256), dim3(256), 0, st, (const T*)in->ptr, (T*)out->ptr, nvec, lfactor, rfactor);
-        if (nframes > done && pair) hipLaunchKernelGGL((k_tomono<T, 1>), sh::grid1d(nframes - done, 256), dim3(256), 0, st,
-                                                       (const T*)in->ptr + 2 * done, (T*)out->ptr + done, nframes - done, lfactor, rfactor);
-        else if (nframes > done) hipLaunchKernelGGL((k_tomono<T, 1, false>), sh::grid1d(nframes - done, 256), dim3(256), 0, st,
-                                                    (const T*)in->ptr + 2 * done, (T*)out->ptr + done, nframes - done, lfactor, rfactor);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_tomono");
+        const VecSplit s = vec_split(aligned, nframes, F);
+        if (s.nvec) hipLaunchKernelGGL((k_tomono<T, F>), sh::grid1d(s.nvec, 256), dim3(256), 0, st, (const T*)in->ptr, (T*)out->ptr, s.nvec, lfactor, rfactor);
+        if (s.rest && pair) hipLaunchKernelGGL((k_tomono<T, 1>), sh::grid1d(s.rest, 256), dim3(256), 0, st,
+                                               (const T*)in->ptr + 2 * s.done, (T*)out->ptr + s.done, s.rest, lfactor, rfactor);
+        else if (s.rest) hipLaunchKernelGGL((k_tomono<T, 1, false>), sh::grid1d(s.rest, 256), dim3(256), 0, st,
+                                            (const T*)in->ptr + 2 * s.done, (T*)out->ptr + s.done, s.rest, lfactor, rfactor);
+        return launch_result("k_tomono");
     });
 }
 
@@ -740,14 +600,13 @@ int sh_pcm_tostereo(const sh_buf* in, size_t nframes, int width, double lfactor,
         // (as sh_pcm_tomono: 8-byte loads and 16-byte stores only where aligned, the one-frame kernel's two-sample store only where a frame is)
         const bool aligned = ((uintptr_t)in->ptr & 7) == 0 && ((uintptr_t)out->ptr & 15) == 0;
         const bool pair = ((uintptr_t)out->ptr & (2 * sizeof(T) - 1)) == 0;
-        const size_t nvec = aligned ? nframes / F : 0, done = nvec * F;
-        if (nvec) hipLaunchKernelGGL((k_tostereo<T, F>), sh::grid1d(nvec, 256), dim3(256), 0, st, (const T*)in->ptr, (T*)out->ptr, nvec, lfactor, rfactor);
-        if (nframes > done && pair) hipLaunchKernelGGL((k_tostereo<T, 1>), sh::grid1d(nframes - done, 256), dim3(256), 0, st,
-                                                       (const T*)in->ptr + done, (T*)out->ptr + 2 * done, nframes - done, lfactor, rfactor);
-        else if (nframes > done) hipLaunchKernelGGL((k_tostereo<T, 1, false>), sh::grid1d(nframes - done, 256), dim3(256), 0, st,
-                                                    (const T*)in->ptr + done, (T*)out->ptr + 2 * done, nframes - done, lfactor, rfactor);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_tostereo");
+        const VecSplit s = vec_split(aligned, nframes, F);
+        if (s.nvec) hipLaunchKernelGGL((k_tostereo<T, F>), sh::grid1d(s.nvec, 256), dim3(256), 0, st, (const T*)in->ptr, (T*)out->ptr, s.nvec, lfactor, rfactor);
+        if (s.rest && pair) hipLaunchKernelGGL((k_tostereo<T, 1>), sh::grid1d(s.rest, 256), dim3(256), 0, st,
+                                               (const T*)in->ptr + s.done, (T*)out->ptr + 2 * s.done, s.rest, lfactor, rfactor);
+        else if (s.rest) hipLaunchKernelGGL((k_tostereo<T, 1, false>), sh::grid1d(s.rest, 256), dim3(256), 0, st,
+                                            (const T*)in->ptr + s.done, (T*)out->ptr + 2 * s.done, s.rest, lfactor, rfactor);
+        return launch_result("k_tostereo");
     });
 }
 
@@ -755,7 +614,7 @@ int sh_pcm_lin2lin(const sh_buf* in, size_t nsamples, int width, int new_width, 
     SH_REQUIRE_INIT();
     if (width == 3 || new_width == 3) {
         if (!in || !out) return sh::set_error(SH_ERR_INVALID, "sh_pcm_lin2lin: NULL buffer");
-        if ((width != 1 && width != 2 && width != 3 && width != 4) || (new_width != 1 && new_width != 2 && new_width != 3 && new_width != 4))
+        if (!valid_width3(width) || !valid_width3(new_width))
             return sh::set_error(SH_ERR_INVALID, "sh_pcm_lin2lin: widths %d -> %d not in {1,2,3,4}", width, new_width);
         if (nsamples * (size_t)width > in->bytes || nsamples * (size_t)new_width > out->bytes)
             return sh::set_error(SH_ERR_INVALID, "sh_pcm_lin2lin: range outside buffer");
@@ -772,125 +631,27 @@ int sh_pcm_lin2lin(const sh_buf* in, size_t nsamples, int width, int new_width, 
     if (rc) return rc;
     if (!nsamples) return SH_OK;
     hipStream_t st = sh::state().stream;
-    const dim3 grid = sh::grid1d(nsamples, 256);
-#define SH_L2L(TI, TO) hipLaunchKernelGGL((k_lin2lin<TI, TO>), grid, dim3(256), 0, st, (const TI*)in->ptr, (TO*)out->ptr, nsamples)
-    if (width == 1 && new_width == 1) SH_L2L(signed char, signed char);
-    else if (width == 1 && new_width == 2) SH_L2L(signed char, short);
-    else if (width == 1 && new_width == 4) SH_L2L(signed char, int);
-    else if (width == 2 && new_width == 1) SH_L2L(short, signed char);
-    else if (width == 2 && new_width == 2) SH_L2L(short, short);
-    else if (width == 2 && new_width == 4) SH_L2L(short, int);
-    else if (width == 4 && new_width == 1) SH_L2L(int, signed char);
-    else if (width == 4 && new_width == 2) SH_L2L(int, short);
-    else if (width == 4 && new_width == 4) SH_L2L(int, int);
-    else return sh::set_error(SH_ERR_INVALID, "sh_pcm_lin2lin: widths %d -> %d not in {1,2,4}", width, new_width);
-#undef SH_L2L
-    SH_CHECK_LAUNCH("k_lin2lin");
-    return SH_OK;
+    return dispatch_width(width, [&](auto tin) {
+        return dispatch_width(new_width, [&](auto tout) {
+            typedef decltype(tin) TI;
+            typedef decltype(tout) TO;
+            hipLaunchKernelGGL((k_lin2lin<TI, TO>), sh::grid1d(nsamples, 256), dim3(256), 0, st, (const TI*)in->ptr, (TO*)out->ptr, nsamples);
+            return launch_result("k_lin2lin");
+        });
+    });
 }
 
 int sh_pcm_stats(const sh_buf* in, size_t nbytes, int width, uint32_t* max_abs, double* sum_squares) {
     SH_REQUIRE_INIT();
-    if (width == 3) {                           // raw 24-bit values (audioop.max / rms read GETRAWSAMPLE)
-        if (!in || nbytes > in->bytes || nbytes % 3) return sh::set_error(SH_ERR_INVALID, "sh_pcm_stats: range outside buffer / not whole samples");
-        const size_t n = nbytes / 3;
-        sh::Temp t32;
-        int rc3 = t32.alloc(n * 4);
-        if (rc3) return rc3;
-        rc3 = sh::unpack24(in->ptr, n, 0, (int32_t*)t32.buf.ptr);
-        if (rc3) return rc3;
-        return sh_pcm_stats(&t32.buf, n * 4, 4, max_abs, sum_squares);
-    }
-    if (!valid_width(width)) return bad_width("sh_pcm_stats", width);
-    if (!in || nbytes > in->bytes) return sh::set_error(SH_ERR_INVALID, "sh_pcm_stats: range outside buffer");
+    if (!valid_width3(width)) return bad_width("sh_pcm_stats", width);           // (width 3: raw 24-bit values, audioop.max / rms read GETRAWSAMPLE)
     if (nbytes % width) return sh::set_error(SH_ERR_INVALID, "sh_pcm_stats: not a whole number of frames");
-    if (max_abs) *max_abs = 0;
-    if (sum_squares) *sum_squares = 0.0;
-    if (!nbytes) return SH_OK;
-    const size_t n = nbytes / width;
-    // 512 workgroups x 4 neighbouring 16-byte loads in flight per lane: 6.0 TB/s on 900 MB; 4096 workgroups with the four
-    // loads a grid apart read the same data at 4.2-4.8 (DESIGN.md section 4 item 15)
-    const unsigned blocks = n / 8192 < 512 ? (unsigned)(n / 8192 + 1) : 512u;
-    int rc = sh::ensure_scratch(16 + (size_t)blocks * 24);
-    if (rc) return rc;
-    hipStream_t st = sh::state().stream;
-    unsigned long long* acc = (unsigned long long*)sh::state().scratch;          // [0..1]: result; then per-workgroup pairs
-    unsigned long long* pairs = acc + 2;
-    double* part = (double*)(pairs + 2 * (size_t)blocks);
-    rc = dispatch_width(width, [&](auto tag) {
-        typedef decltype(tag) T;
-        hipLaunchKernelGGL((k_absmax_sumsq<T, 4>), dim3(blocks), dim3(256), 0, st, (const T*)in->ptr, n, pairs);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_absmax_sumsq");
-    });
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_stats_fold, dim3(1), dim3(256), 0, st, (const unsigned long long*)pairs, blocks, acc);
-    SH_CHECK_LAUNCH("k_stats_fold");
-    if (width == 4) {
-        hipLaunchKernelGGL(k_sumsq_f64, dim3(blocks), dim3(256), 0, st, (const int*)in->ptr, n, part);
-        SH_CHECK_LAUNCH("k_sumsq_f64");
-    }
-    unsigned long long host_acc[2];
-    SH_HIP(hipMemcpyAsync(host_acc, acc, 16, hipMemcpyDeviceToHost, st));
-    std::vector<double> host_part;
-    if (width == 4) {
-        host_part.resize(blocks);
-        SH_HIP(hipMemcpyAsync(host_part.data(), part, (size_t)blocks * 8, hipMemcpyDeviceToHost, st));
-    }
-    SH_HIP(hipStreamSynchronize(st));
-    if (max_abs) *max_abs = (uint32_t)host_acc[0];
-    if (sum_squares) {
-        if (width == 4) {
-            double t = 0.0;
-            for (double p : host_part) t += p;
-            *sum_squares = t;
-        } else {
-            *sum_squares = (double)host_acc[1];
-        }
-    }
-    return SH_OK;
+    return pcm_stats<1>("sh_pcm_stats", in, nbytes / width, width, max_abs, sum_squares);
 }
 
 int sh_pcm_stats_stereo(const sh_buf* in, size_t nframes, int width, uint32_t max_abs[2], double sum_squares[2]) {
     SH_REQUIRE_INIT();
-    if (width == 3) {
-        if (!in || nframes > in->bytes / 6) return sh::set_error(SH_ERR_INVALID, "sh_pcm_stats_stereo: range outside buffer");
-        sh::Temp t32;
-        int rc3 = t32.alloc(nframes * 8);
-        if (rc3) return rc3;
-        rc3 = sh::unpack24(in->ptr, nframes * 2, 0, (int32_t*)t32.buf.ptr);
-        if (rc3) return rc3;
-        return sh_pcm_stats_stereo(&t32.buf, nframes, 4, max_abs, sum_squares);
-    }
-    if (width != 1 && width != 2 && width != 4) return sh::set_error(SH_ERR_INVALID, "sh_pcm_stats_stereo: width %d not in {1,2,4}", width);
-    if (!in || nframes > in->bytes / (2 * (size_t)width)) return sh::set_error(SH_ERR_INVALID, "sh_pcm_stats_stereo: range outside buffer");
-    if (max_abs) max_abs[0] = max_abs[1] = 0;
-    if (sum_squares) sum_squares[0] = sum_squares[1] = 0.0;
-    if (!nframes) return SH_OK;
-    const unsigned blocks = nframes / 4096 < 512 ? (unsigned)(nframes / 4096 + 1) : 512u;
-    int rc = sh::ensure_scratch(32 + (size_t)blocks * 32);
-    if (rc) return rc;
-    hipStream_t st = sh::state().stream;
-    unsigned long long* acc = (unsigned long long*)sh::state().scratch;          // [0..3]: result; then per-workgroup quadruples
-    unsigned long long* quads = acc + 4;
-    rc = dispatch_width(width, [&](auto tag) {
-        typedef decltype(tag) T;
-        hipLaunchKernelGGL(k_stats_stereo<T>, dim3(blocks), dim3(256), 0, st, (const T*)in->ptr, nframes, quads);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? (int)SH_OK : sh::hip_error(e, "k_stats_stereo");
-    });
-    if (rc) return rc;
-    if (width == 4) hipLaunchKernelGGL(k_stats_fold_stereo<true>, dim3(1), dim3(256), 0, st, (const unsigned long long*)quads, blocks, acc);
-    else hipLaunchKernelGGL(k_stats_fold_stereo<false>, dim3(1), dim3(256), 0, st, (const unsigned long long*)quads, blocks, acc);
-    SH_CHECK_LAUNCH("k_stats_fold_stereo");
-    unsigned long long host_acc[4];
-    SH_HIP(hipMemcpyAsync(host_acc, acc, 32, hipMemcpyDeviceToHost, st));
-    SH_HIP(hipStreamSynchronize(st));
-    for (int c = 0; c < 2; ++c) {
-        if (max_abs) max_abs[c] = (uint32_t)host_acc[c];
-        if (sum_squares) sum_squares[c] = width == 4 ? __builtin_bit_cast(double, host_acc[2 + c]) : (double)host_acc[2 + c];
-    }
-    return SH_OK;
+    if (!valid_width3(width)) return bad_width("sh_pcm_stats_stereo", width);
+    return pcm_stats<2>("sh_pcm_stats_stereo", in, nframes, width, max_abs, sum_squares);
 }
 
 }  // extern "C"

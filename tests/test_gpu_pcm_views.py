@@ -392,7 +392,7 @@ def _stats_sets(rng, width, n, tail_index):
 @pytest.mark.parametrize("width", [1, 2, 3, 4])
 def test_stats(gpu, width):
     """sh_pcm_stats: audioop.max, and the sum of squares from exact Python integers.  On a window off the 16-byte grid the whole
-    buffer goes through the grid-strided scalar loop of k_absmax_sumsq (the raw 24-bit samples through k_unpack24's byte path)."""
+    buffer goes through the grid-strided scalar loop of k_pcm_stats (the raw 24-bit samples through k_unpack24's byte path)."""
     L = gpu.lib()
     rng = np.random.default_rng(100 + width)
     V = 16 // (4 if width == 3 else width)
@@ -452,6 +452,58 @@ def test_stats_stereo(gpu, width):
                         assert Fraction(sq[c]) == exact[c], (width, n, label, a, c, sq[c], exact[c])
                     else:
                         _assert_sumsq(sq[c], exact[c], n, (width, n, label, a, c))
+
+
+EVERY_WORKGROUP = 512 * 8192 + 3 * 8192 + 5                # samples: all 512 workgroups live, some with one turn more, one partial turn, a scalar tail
+
+
+def _exact_sumsq(v):
+    """The sum of squares of int64 values below 2^31 in magnitude as a Python integer: the squares' 32-bit halves, each summed in uint64
+    (4.2 M x 2^32 < 2^64)."""
+    sq = v * v
+    return (int((sq >> 32).sum(dtype=np.uint64)) << 32) + int((sq & 0xFFFFFFFF).sum(dtype=np.uint64))
+
+
+@pytest.mark.parametrize("nch", [1, 2])
+@pytest.mark.parametrize("width", [2, 3, 4])
+def test_stats_every_workgroup(gpu, width, nch):
+    """The one kernel and its fold with every workgroup at work: 512 records (the fold's second round, b += 256), full turns of four
+    loads and a partial one at width 2, a scalar tail -- on an aligned window and on one a sample off (all scalar).  "small": values
+    below 2^15, the right channel at a quarter of the left's range; 4.2 M x 2^30 < 2^53, so every order of additions must return the
+    exact sum -- a dropped or doubled element cannot hide.  "full": full-range values without the most negative one, which is then
+    placed once, in the right (or only) channel of the first frame of an aligned window's scalar tail (the last frame where whole vectors
+    leave no tail: stereo at widths 3 and 4); the bound is _assert_sumsq's."""
+    L = gpu.lib()
+    rng = np.random.default_rng(300 + 10 * width + nch)
+    lo, hi = lo_hi(width)
+    V = 16 // (4 if width == 3 else width)
+    nframes = EVERY_WORKGROUP // nch
+    n = nframes * nch
+    small = rng.integers(-(1 << 15) + 1, 1 << 15, n, dtype=np.int64)
+    small[nch - 1::nch] //= 4 if nch == 2 else 1
+    full = rng.integers(lo + 1, hi + 1, n, dtype=np.int64)
+    full[min(n // V * V, n - nch) + nch - 1] = lo
+    for label, x in (("small", small), ("full", full)):
+        raw = encode(x, width)
+        exact = [_exact_sumsq(x[c::nch]) for c in range(nch)]
+        want_max = [audioop.max(encode(x[c::nch], width), width) for c in range(nch)]
+        if label == "small":
+            assert max(exact) < 1 << 53
+        else:
+            assert want_max[nch - 1] == 1 << (8 * width - 1) and (nch == 1 or want_max[0] < want_max[1])
+        for a in (0, width):
+            mx, sq = (C.c_uint32 * 2)(12345, 12345), (C.c_double * 2)(-1.0, -1.0)
+            if nch == 1:
+                call = lambda iv, ov: L.sh_pcm_stats(iv[0].handle, len(raw), width, mx, sq)
+            else:
+                call = lambda iv, ov: L.sh_pcm_stats_stereo(iv[0].handle, nframes, width, mx, sq)
+            rc, _ = pcm_view_call(gpu, [(raw, a)], None, 0, call)
+            assert rc == 0 and list(mx)[:nch] == want_max, (width, nch, label, a, rc, list(mx), want_max)
+            for c in range(nch):
+                if width == 2:
+                    assert Fraction(sq[c]) == exact[c], (width, nch, label, a, c, sq[c], exact[c])
+                else:
+                    _assert_sumsq(sq[c], exact[c], nframes, (width, nch, label, a, c))
 
 
 # ---- refusals: bounds are the WINDOW's, not the allocation's ---------------------------------------------------------------------

@@ -291,7 +291,7 @@ def _off_grid(gpu, x, width, rate, nch, offset):
 
 def test_level_db_unaligned_device_views(gpu):
     """Statistics of a sample whose device storage does not start on a 16-byte boundary: stereo int16 at byte 4 (the all-scalar
-    path of k_stats_stereo), mono int16 at byte 2 and mono int8 at byte 1 (that of k_absmax_sumsq)."""
+    path of k_pcm_stats<T, 2>), mono int16 at byte 2 and mono int8 at byte 1 (that of k_pcm_stats<T, 1>)."""
     rng = np.random.default_rng(99)
     x = _rand(rng, 2, 2 * 30011)
     s, r = _pair(x, 2, 8000, 2)

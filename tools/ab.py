@@ -10,6 +10,8 @@
     python tools/ab.py mix LIB [LIB ...]                    sh_mix_bus_f32 on the benchmark's mix row (1024 x 480 000: k_mix_bus_direct, streaming loads) and on the
                                                            two-step render's (1024 x 48 000: k_mix_bus_f32 in 8 groups + k_bus_sum) under each library, the libraries
                                                            by turns, four processes each: ms per call, median of 7 timings per process
+    python tools/ab.py pcm LIB [LIB ...]                    the benchmark's rows of the elementwise and statistics PCM entry points (900 MB int16, 1200 MB float) and
+                                                           sh_pcm_stats at width 4 under each library, by turns, four processes each: ms per call, median of 7 loops
     python tools/ab.py mixcalls                             one call of each of those shapes and of a short direct one (for a kernel trace; SYNTHHIP_LIB picks the library)
 
 (Round 5: build_variant.py, variant_diff.py, variants.py and the ab_*.sh wrappers in one file.)"""
@@ -139,10 +141,44 @@ for nv, nf in ((1024, 480000), (1024, 48000)) + (() if timed else ((9, 393216),)
 '''
 
 
-def mix(argv):
+_PCM_CHILD = r'''
+import sys, ctypes, statistics; sys.path.insert(0, ".")
+import numpy as np
+from synthesizer_amd import _native as N
+N.ensure_init(0)
+L = N.lib()
+n, nq, nq64 = 900_000_000, 300_000_000, 150_000_000          # bench.py pcm_rows: the same calls on the same sizes
+chunks, src, dst = N.DeviceBuffer(2 * n), N.DeviceBuffer(4 * nq), N.DeviceBuffer(2 * nq)
+pcm = np.random.default_rng(1).integers(-3000, 3000, 1 << 24).astype(np.int16)
+flt = np.random.default_rng(0).uniform(-1, 1, 1 << 24).astype(np.float32)
+for buf, img in ((chunks, pcm), (src, flt)):
+    for off in range(0, buf.nbytes, img.nbytes):
+        buf.upload(img[:min(len(img), (buf.nbytes - off) // img.itemsize)], off)
+mx, sq = (ctypes.c_uint32 * 2)(), (ctypes.c_double * 2)()
+rows = (("pcm_stats_i16_900MB", lambda: L.sh_pcm_stats(chunks.handle, n, 2, mx, sq)),
+        ("pcm_stats_stereo_i16_900MB", lambda: L.sh_pcm_stats_stereo(chunks.handle, n // 4, 2, mx, sq)),
+        ("pcm_stats_i32_900MB", lambda: L.sh_pcm_stats(chunks.handle, n, 4, mx, sq)),
+        ("pcm_mul_i16_900MB", lambda: L.sh_pcm_mul(chunks.handle, 0, n, 2, 0.7071, src.handle, 0)),
+        ("pcm_tomono_i16_900MB", lambda: L.sh_pcm_tomono(chunks.handle, n // 4, 2, 0.5, 0.5, src.handle)),
+        ("pcm_add_i16_900MB", lambda: L.sh_pcm_add(chunks.handle, 0, chunks.handle, n, n, 2, src.handle, 0)),
+        ("quantize_f32_to_i16_1200MB", lambda: L.sh_quantize_f32(src.handle, 0, nq, 32767.0, 2, dst.handle, 0)),
+        ("quantize_f64_to_i16_1200MB", lambda: L.sh_quantize_f64(src.handle, 0, nq64, 32767.0, 2, dst.handle, 0)))
+for name, call in rows[:3] + rows[6:] + rows[3:6]:             # (the rows that overwrite src after the ones that read it)
+    N.check(call()); N.sync()
+    ms = []
+    for _ in range(7):
+        N.timer_start()
+        for _k in range(5):
+            N.check(call())
+        ms.append(N.timer_stop() / 5)
+    print("%s: %.4f ms (median of 7; min %.4f max %.4f)" % (name, statistics.median(ms), min(ms), max(ms)), flush=True)
+'''
+
+
+def _by_turns(child, argv):
     for rep in range(4):
         for lib in argv:
-            p = subprocess.run([sys.executable, "-c", _MIX_CHILD, "time"], env=dict(os.environ, SYNTHHIP_ALLOW_STALE="1", SYNTHHIP_LIB=lib),
+            p = subprocess.run([sys.executable, "-c", child, "time"], env=dict(os.environ, SYNTHHIP_ALLOW_STALE="1", SYNTHHIP_LIB=lib),
                                capture_output=True, text=True, timeout=300)
             if p.returncode:
                 sys.exit("failed under %s (%d): %s" % (lib, p.returncode, p.stderr[-300:]))
@@ -150,12 +186,20 @@ def mix(argv):
                 print("%s process %d: %s" % (Path(lib).name, rep, line), flush=True)
 
 
+def mix(argv):
+    _by_turns(_MIX_CHILD, argv)
+
+
+def pcm(argv):
+    _by_turns(_PCM_CHILD, argv)
+
+
 def mixcalls(argv):
     sys.argv = ["mixcalls", "calls"]                       # in this process: a kernel trace follows it without following children
     exec(_MIX_CHILD, {"__name__": "__mixcalls__"})
 
 
-COMMANDS = {"build": build, "time": time_libs, "config": config, "shapes": shapes, "diff": diff, "mix": mix, "mixcalls": mixcalls}
+COMMANDS = {"build": build, "time": time_libs, "config": config, "shapes": shapes, "diff": diff, "mix": mix, "pcm": pcm, "mixcalls": mixcalls}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in COMMANDS:
