@@ -1,121 +1,27 @@
 """GPU parity of ``channels`` per event in Sample.mix_at_many / mixer.sequence / sh_mix_events_chan -- a stereo sample downmixed into a mono
-track (audioop.tomono) or balanced in a stereo one, in one launch -- against live ``audioop`` on byte slices.  The oracle is
-tests/test_gpu_reversed.py's ``played_source`` chain as it stands, run over the STEREO source up to the envelope, then the new step --
+track (audioop.tomono) or balanced in a stereo one, in one launch -- against live ``audioop`` on byte slices.  The reference is
+tests/seqref.py (source, mix): the chain as it stands, run over the STEREO source up to the envelope, then the new step --
 ``audioop.tomono(data, w, lf, rf)`` for a downmix; for a balance ``tomono(1, 0)`` -> ``mul(lf)`` -> ``tostereo(1, 0)`` added with
 ``audioop.add`` to its right-hand twin -- then ``mul``, the cut of ``other_seconds`` in TRACK samples, ``add`` with saturation at every
 event, in list order.  Expected bytes never come from the product.  Rate 8192, sources of a few hundred frames, tracks of three tiles, as
 the sibling files have them."""
 import audioop
-import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from tests.helpers import pcm_track_call
-from tests.test_gpu_enveloped import _differs, envelope_bytes
-from tests.test_gpu_looped import LANE, LOOPS, RATE, SPEEDS, STARTS, TILE, _out_frames
-from tests.test_gpu_reversed import HELD, LENGTHS, _spy, as_samples, named, played_source, with_samples
-from tests.test_gpu_sequence import OTHER_SCHEME, ROOT, _pcm, _sample
+from tests.seqcases import (FACTORS, LENGTHS, LOOPS, SPEEDS, STARTS, as_samples, event_table, in_a_child_under_the_other_alignment_scheme, mix_events,
+                            named, sample_of, spy, with_samples)
+from tests.seqref import LANE, TILE, balance, differs, discriminates, mix, out_frames, pcm, weigh
 
 pytestmark = pytest.mark.gpu
 
-RIGHT, BEFORE_ENVELOPE, BEFORE_REVERSAL, AFTER_MUL, SWAPPED, N_IN_STEREO = \
-    "right", "channels before the envelope", "channels before the reversal", "channels after the mul", "factors swapped", \
-    "a downmix's n counted in stereo samples"
-WRONG = {1: (BEFORE_ENVELOPE, BEFORE_REVERSAL, AFTER_MUL, N_IN_STEREO), 2: (BEFORE_ENVELOPE, BEFORE_REVERSAL, AFTER_MUL, SWAPPED)}
-FACTORS = [(0.75, -0.25), (1.0, 0.0), (0.5, 0.5), (0.0, 1.0), (1.5, 1.2), (1.0, 1.0), (0.3, 1.0)]
-
-
-# ---- the oracle ------------------------------------------------------------------------------------------------------------------------
-def balance(data: bytes, width, lf, rf) -> bytes:
-    """Sample.stereo of a stereo sample: left().amplify(lf).stereo(1, 0) mixed with right().amplify(rf).stereo(0, 1); a last sample
-    without its frame is the left one of a frame whose right one is cut off again"""
-    odd = len(data) // width % 2
-    if odd:
-        data = data + bytes(width)
-    left = audioop.tostereo(audioop.mul(audioop.tomono(data, width, 1, 0), width, lf), width, 1, 0)
-    right = audioop.tostereo(audioop.mul(audioop.tomono(data, width, 0, 1), width, rf), width, 0, 1)
-    out = audioop.add(left, right, width)
-    return out[:len(out) - width] if odd else out
-
-
-def weigh(data: bytes, width, nch, lf, rf) -> bytes:
-    return audioop.tomono(data, width, lf, rf) if nch == 1 else balance(data, width, lf, rf)
-
-
-def chan_source(data, width, rate, nch, volume, other_seconds, speed, pan, env, loop, region, reverse, channels, order=RIGHT) -> bytes:
-    """what mix_at is handed for one event: played_source's chain over the stereo source, the new step where pan's stands, the mul, the
-    cut -- or one of the wrong orders"""
-    if channels is None:
-        return played_source(data, width, rate, nch, volume, other_seconds, speed, pan, env, loop, region, reverse)
-    assert pan is None
-    lf, rf = channels
-    if order == SWAPPED or (order == BEFORE_REVERSAL and reverse):      # weighed first and turned round after: lf stays with the stored left
-        lf, rf = rf, lf
-    early = order == BEFORE_ENVELOPE and env is not None
-    x = played_source(data, width, rate, 2, volume if order == AFTER_MUL else None, None, speed, None, None if early else env, loop, region, reverse)
-    x = weigh(x, width, nch, lf, rf)
-    if early:
-        if len(env) == 5:
-            x = x[:width * nch * int(rate * env[4])]
-        x = envelope_bytes(x, width, nch, rate, *env[:4])
-    if volume is not None and order != AFTER_MUL:
-        x = audioop.mul(x, width, volume)
-    if other_seconds:
-        x = x[:width * (2 if order == N_IN_STEREO else nch) * int(rate * other_seconds)]
-    return x
-
-
-def oracle(track: bytes, events, width, rate, nch, order=RIGHT) -> bytes:
-    """events: (seconds, source bytes, volume, other_seconds, speed, pan, envelope, loop, region, reverse, channels), one after another
-    like mix_at"""
-    fb = width * nch
-    t = bytearray(track)
-    for seconds, data, volume, other_seconds, speed, pan, env, loop, region, reverse, channels in events:
-        frames = chan_source(data, width, rate, nch, volume, other_seconds, speed, pan, env, loop, region, reverse, channels, order)
-        start = fb * int(rate * seconds)
-        end = start + len(frames)
-        if end > len(t):
-            t.extend(bytes(end - len(t)))
-        t[start:end] = audioop.add(bytes(t[start:end]), frames, width)
-    return bytes(t)
-
-
-def discriminates(want, events, width, nch, base=b""):
-    """the expected bytes differ from each wrong order's: on the CPU, with audioop alone, before the GPU is asked.  (24-bit samples
-    have no envelope, so no order against it.)"""
-    differs = {}
-    for order in WRONG[nch]:
-        if order == BEFORE_ENVELOPE and width == 3:
-            continue
-        b = oracle(base, events, width, RATE, nch, order)
-        m = min(len(want), len(b))
-        differs[order] = _differs(want[:m], b[:m]) + abs(len(want) - len(b))
-    print("width %d, %d channels: bytes of %d that differ from the wrong orders: %s" % (width, nch, len(want), differs))
-    assert all(n > 0 for n in differs.values()), differs
+RATE = 8192
+HELD = [300, 211, 97]                                       # frames of the instruments, stereo and mono
 
 
 # ---- 1: plain downmixes and balances, through the entry point (track offsets count samples there) -------------------------------------------
-def _chan_table(N, rows):
-    """rows: sh_mix_event_chan's fields in order, the tail may be left out"""
-    t = np.zeros(len(rows), dtype=N.MIX_EVENT_CHAN_DTYPE)
-    for k, r in enumerate(rows):
-        t[k] = tuple(r) + (0,) * (17 - len(r))
-    return t
-
-
-def _mix_events_chan(N, srcs, events, segments, width, nchannels, track, track_samples):
-    arr = (C.c_void_p * max(1, len(srcs)))(*[b.handle for b in srcs])
-    return N.lib().sh_mix_events_chan(arr, len(srcs), events.ctypes.data if len(events) else None, len(events),
-                                      segments.ctypes.data if segments is not None and len(segments) else None,
-                                      len(segments) if segments is not None else 0, width, nchannels,
-                                      track.handle if track is not None else None, track_samples)
-
-
 _PLAIN = {}
 
 
@@ -129,9 +35,9 @@ def plain_cases(width, nch):
     tile, lane = TILE[width], LANE[width]
     per = 2 // nch                                          # source samples per track sample
     held = (400, 311, tile * per + 900)                     # samples
-    sources = [_pcm(rng, width, held[0], 1.0), _pcm(rng, width, held[1], 0.5), _pcm(rng, width, held[2], 0.5)]
+    sources = [pcm(rng, width, held[0], 1.0), pcm(rng, width, held[1], 0.5), pcm(rng, width, held[2], 0.5)]
     ntrack = 3 * tile - 6
-    base = _pcm(np.random.default_rng(width), width, ntrack, 0.3)
+    base = pcm(np.random.default_rng(width), width, ntrack, 0.3)
     rows = []
     k = 0
     for F in LENGTHS:                                       # frames
@@ -170,7 +76,7 @@ def plain_cases(width, nch):
 
 def _plain_table(N, rows, nch):
     flag = N.MIX_EVENT_DOWNMIX if nch == 1 else N.MIX_EVENT_BALANCE
-    return _chan_table(N, [(dst, a, n, 0, f, lf, rf, i, RATE, RATE, 2, 0, 0, 0, 0, 0, flag) for dst, i, a, n, f, lf, rf in rows])
+    return event_table(N, "chan", [(dst, a, n, 0, f, lf, rf, i, RATE, RATE, 2, 0, 0, 0, 0, 0, flag) for dst, i, a, n, f, lf, rf in rows])
 
 
 @pytest.mark.parametrize("nch", [1, 2])
@@ -209,33 +115,28 @@ def test_plain_downmix_and_balance_at_every_offset(gpu, width, nch):
     bufs = [N.DeviceBuffer.from_bytes(b) for b in sources]
     track = N.DeviceBuffer.from_bytes(base)
     table = _plain_table(N, rows, nch)
-    assert _mix_events_chan(N, bufs, table, None, width, nch, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
+    assert mix_events(N, "chan", bufs, table, None, width, nch, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
     got = track.download_bytes(len(base))
-    assert got == want, "%d bytes differ" % _differs(got, want)
+    assert got == want, "%d bytes differ" % differs(got, want)
     # the same rows without the mode: a stereo source in a mono track is refused; in a stereo track they are rows of sh_mix_events_rev
     track = N.DeviceBuffer.from_bytes(base)
     table["flags"] = 0
     if nch == 1:
-        assert _mix_events_chan(N, bufs, table, None, width, nch, track, ntrack) == N.SH_ERR_INVALID
+        assert mix_events(N, "chan", bufs, table, None, width, nch, track, ntrack) == N.SH_ERR_INVALID
         assert track.download_bytes(len(base)) == base
     else:
         for dst, i, a, n, f, _lf, _rf in rows:
             data = sources[i][a * width:(a + n) * width]
             data = audioop.mul(data, width, f) if f != 1.0 else data
             wrong[dst * width:(dst + n) * width] = audioop.add(bytes(wrong[dst * width:(dst + n) * width]), data, width)
-        assert _mix_events_chan(N, bufs, table, None, width, nch, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
+        assert mix_events(N, "chan", bufs, table, None, width, nch, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
         assert track.download_bytes(len(base)) == bytes(wrong) != want
 
 
 def test_channels_under_the_other_alignment_scheme(gpu):
     """SYNTHHIP_SEQ_ALIGN is read once per process (sh_init): the 16-bit cases again in a child under the scheme that is not the default"""
-    env = dict(os.environ, SYNTHHIP_SEQ_ALIGN=OTHER_SCHEME)
-    me = str(Path(__file__).resolve())
-    p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider",
-                        me + "::test_plain_downmix_and_balance_at_every_offset[2-1]", me + "::test_plain_downmix_and_balance_at_every_offset[2-2]",
-                        me + "::test_channels_crossed_with_the_rest_of_the_chain[2-1]", me + "::test_channels_crossed_with_the_rest_of_the_chain[2-2]"],
-                       cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "4 passed" in p.stdout and "failed" not in p.stdout, p.stdout[-3000:] + p.stderr[-1000:]
+    in_a_child_under_the_other_alignment_scheme(__file__, ["%s[2-%d]" % (t, n) for t in ("test_plain_downmix_and_balance_at_every_offset", "test_channels_crossed_with_the_rest_of_the_chain")
+                                                           for n in (1, 2)])
 
 
 # ---- 2, 3: each stage with the new one, through Sample.mix_at_many; the order ------------------------------------------------------------------
@@ -252,7 +153,7 @@ def notes(width, nch, seed=0):
         return _CACHE[key]
     rng = np.random.default_rng(3000 * seed + 10 * width + nch)
     track_frames = 3 * TILE[width] // nch
-    instruments = [(_pcm(rng, width, 2 * n, 0.6), 2) for n in HELD] + [(_pcm(rng, width, n, 0.6), 1) for n in HELD]
+    instruments = [(pcm(rng, width, 2 * n, 0.6), 2) for n in HELD] + [(pcm(rng, width, n, 0.6), 1) for n in HELD]
     events = []
     for k in range(84):
         speed = SPEEDS[k % 7]
@@ -281,7 +182,7 @@ def notes(width, nch, seed=0):
             V = max(2, (150 + (37 * k) % 500) * inrate // RATE)
             loop = (S / RATE, (S + L) / RATE, V / RATE)
             R = V
-        out = _out_frames(R, inrate, RATE)
+        out = out_frames(R, inrate, RATE)
         env = None
         if (k & 2) and width != 3:
             dur = (0.61 * out + 0.37) / RATE
@@ -326,15 +227,15 @@ def test_channels_crossed_with_the_rest_of_the_chain(gpu, width, nch, monkeypatc
     from synthesizer_amd import mixer
     instruments, events = notes(width, nch)
     _has_every_stage(events, width, nch)
-    want = oracle(b"", named(instruments, events), width, RATE, nch)
+    want = mix(b"", named(instruments, events), width, RATE, nch)
     assert 2 * TILE[width] * width < len(want) <= 3 * TILE[width] * width
-    discriminates(want, named(instruments, events), width, nch)
-    samples = as_samples(instruments, width)
-    calls = _spy(N, monkeypatch)
+    discriminates(want, named(instruments, events), width, RATE, nch, "chan")
+    samples = as_samples(instruments, width, RATE)
+    calls = spy(N, monkeypatch)
     got = mixer.sequence(with_samples(samples, events), RATE, nch, width, name="weighed")
     assert calls == ["sh_mix_events_chan"]                                               # one launch
     assert got.name == "weighed" and got.nchannels == nch and len(got) * nch * width == len(want)
-    assert bytes(got.view_frame_data()) == want, "%d bytes differ" % _differs(bytes(got.view_frame_data()), want)
+    assert bytes(got.view_frame_data()) == want, "%d bytes differ" % differs(bytes(got.view_frame_data()), want)
     for (b, c), smp in zip(instruments, samples):
         assert bytes(smp.view_frame_data()) == b and smp.nchannels == c                 # the instruments are untouched
 
@@ -345,11 +246,11 @@ def test_channels_into_a_track_that_holds_something(gpu, width, nch, monkeypatch
     """mixed in place over a base that is not silence"""
     N = gpu
     instruments, events = notes(width, nch, seed=1)
-    base = _pcm(np.random.default_rng(5), width, 3 * TILE[width], 0.3)
-    want = oracle(base, named(instruments, events), width, RATE, nch)
-    discriminates(want, named(instruments, events), width, nch, base)
-    calls = _spy(N, monkeypatch)
-    got = _sample(base, width, RATE, nch).mix_at_many(with_samples(as_samples(instruments, width), events))
+    base = pcm(np.random.default_rng(5), width, 3 * TILE[width], 0.3)
+    want = mix(base, named(instruments, events), width, RATE, nch)
+    discriminates(want, named(instruments, events), width, RATE, nch, "chan", base)
+    calls = spy(N, monkeypatch)
+    got = sample_of(base, width, RATE, nch).mix_at_many(with_samples(as_samples(instruments, width, RATE), events))
     assert calls == ["sh_mix_events_chan"]
     assert bytes(got.view_frame_data()) == want
 
@@ -358,7 +259,7 @@ def test_channels_into_a_track_that_holds_something(gpu, width, nch, monkeypatch
 def test_each_stage_alone_with_a_downmix_and_with_a_balance(gpu, width):
     """one stage and the new step per list, so that a failure names its stage"""
     rng = np.random.default_rng(90 + width)
-    src = _pcm(rng, width, 2 * 300, 0.9)
+    src = pcm(rng, width, 2 * 300, 0.9)
     env = (0.004, 0.006, 0.5, 0.008, 0.03)
     stages = {
         "speed up": dict(speed=2.5), "speed down": dict(speed=0.37),
@@ -375,14 +276,14 @@ def test_each_stage_alone_with_a_downmix_and_with_a_balance(gpu, width):
                 continue
             e = (9 / RATE, None, kw.get("volume"), kw.get("other_seconds"), kw.get("speed"), None, kw.get("envelope"), kw.get("loop"),
                  kw.get("region"), kw.get("reverse"), (0.75, -0.5))
-            want = oracle(b"", [e[:1] + (src,) + e[2:]], width, RATE, nch)
-            assert want != oracle(b"", [e[:1] + (src,) + e[2:10] + ((1.0, 0.0),)], width, RATE, nch)
-            got = _sample(b"", width, RATE, nch).mix_at_many([e[:1] + (_sample(src, width, RATE, 2),) + e[2:]])
+            want = mix(b"", [e[:1] + (src,) + e[2:]], width, RATE, nch)
+            assert want != mix(b"", [e[:1] + (src,) + e[2:10] + ((1.0, 0.0),)], width, RATE, nch)
+            got = sample_of(b"", width, RATE, nch).mix_at_many([e[:1] + (sample_of(src, width, RATE, 2),) + e[2:]])
             assert bytes(got.view_frame_data()) == want, (what, nch)
     # (1.0, 0.0) into a mono track is Sample.left(); (1.0, 1.0) in a stereo one the plain event
-    got = _sample(b"", width, RATE, 1).mix_at_many([(0.0, _sample(src, width, RATE, 2), None, None, None, None, None, None, None, None, (1.0, 0.0))])
-    assert bytes(got.view_frame_data()) == audioop.tomono(src, width, 1, 0) == bytes(_sample(src, width, RATE, 2).left().view_frame_data())
-    got = _sample(b"", width, RATE, 2).mix_at_many([(0.0, _sample(src, width, RATE, 2), None, None, None, None, None, None, None, None, (1.0, 1.0))])
+    got = sample_of(b"", width, RATE, 1).mix_at_many([(0.0, sample_of(src, width, RATE, 2), None, None, None, None, None, None, None, None, (1.0, 0.0))])
+    assert bytes(got.view_frame_data()) == audioop.tomono(src, width, 1, 0) == bytes(sample_of(src, width, RATE, 2).left().view_frame_data())
+    got = sample_of(b"", width, RATE, 2).mix_at_many([(0.0, sample_of(src, width, RATE, 2), None, None, None, None, None, None, None, None, (1.0, 1.0))])
     assert bytes(got.view_frame_data()) == src
 
 
@@ -390,9 +291,9 @@ def test_each_stage_alone_with_a_downmix_and_with_a_balance(gpu, width):
 def test_the_same_bytes_as_the_documented_loop_of_sample_calls(gpu, width, nch):
     instruments, events = notes(width, nch)
     events = events[:84:5]
-    samples = as_samples(instruments, width)
-    base = _pcm(np.random.default_rng(9), width, 3 * TILE[width], 0.3)
-    loop_ = _sample(base, width, RATE, nch)
+    samples = as_samples(instruments, width, RATE)
+    base = pcm(np.random.default_rng(9), width, 3 * TILE[width], 0.3)
+    loop_ = sample_of(base, width, RATE, nch)
     for seconds, i, volume, other_seconds, speed, pan, envelope, loop, region, reverse, channels in events:
         other = samples[i]
         o = other
@@ -422,33 +323,33 @@ def test_the_same_bytes_as_the_documented_loop_of_sample_calls(gpu, width, nch):
         if volume is not None:
             o = o.at_volume(volume)
         loop_.mix_at(seconds, o, other_seconds)
-    many = _sample(base, width, RATE, nch).mix_at_many(with_samples(samples, events))
+    many = sample_of(base, width, RATE, nch).mix_at_many(with_samples(samples, events))
     assert len(many) == len(loop_)
-    assert bytes(many.view_frame_data()) == bytes(loop_.view_frame_data()) == oracle(base, named(instruments, events), width, RATE, nch)
+    assert bytes(many.view_frame_data()) == bytes(loop_.view_frame_data()) == mix(base, named(instruments, events), width, RATE, nch)
 
 
 def test_the_track_as_its_own_balanced_source(gpu, monkeypatch):
     N = gpu
     width, nch = 2, 2
     instruments, events = notes(width, nch)
-    samples = as_samples(instruments, width)
-    calls = _spy(N, monkeypatch)
-    base = _pcm(np.random.default_rng(3), width, 3 * TILE[width], 0.3)
-    t = _sample(base, width, RATE, nch)
+    samples = as_samples(instruments, width, RATE)
+    calls = spy(N, monkeypatch)
+    base = pcm(np.random.default_rng(3), width, 3 * TILE[width], 0.3)
+    t = sample_of(base, width, RATE, nch)
     first, last = events[:20], events[20:40]
     own = (0.05, None, 0.4, 0.1, 1.5, None, None, None, (0.01, 0.2), True, (0.75, -0.25))
     t.mix_at_many(with_samples(samples, first) + [own[:1] + (t,) + own[2:]] + with_samples(samples, last))
     assert calls == ["sh_mix_events_chan", "sh_mix_events_chan"]                         # the list is cut at the track; one launch per side
-    mid = oracle(base, named(instruments, first), width, RATE, nch)
-    mid = oracle(mid, [own[:1] + (mid,) + own[2:]], width, RATE, nch)
-    assert bytes(t.view_frame_data()) == oracle(mid, named(instruments, last), width, RATE, nch)
+    mid = mix(base, named(instruments, first), width, RATE, nch)
+    mid = mix(mid, [own[:1] + (mid,) + own[2:]], width, RATE, nch)
+    assert bytes(t.view_frame_data()) == mix(mid, named(instruments, last), width, RATE, nch)
 
 
 # ---- 4: the entry point --------------------------------------------------------------------------------------------------------------------
 def test_the_entry_point_refuses_on_the_host_and_leaves_the_track(gpu):
     N = gpu
     rng = np.random.default_rng(28)
-    src, base = _pcm(rng, 2, 1000), _pcm(rng, 2, 5000)
+    src, base = pcm(rng, 2, 1000), pcm(rng, 2, 5000)
     s, t = N.DeviceBuffer.from_bytes(src), N.DeviceBuffer.from_bytes(base)
     nan = float("nan")
     D, B, R = N.MIX_EVENT_DOWNMIX, N.MIX_EVENT_BALANCE, N.MIX_EVENT_REVERSED
@@ -492,32 +393,31 @@ def test_the_entry_point_refuses_on_the_host_and_leaves_the_track(gpu):
         "range outside its source": (bal[:1] + (402,) + bal[2:], b"range outside its source"),
     })):
         for what, (row, message) in bad.items():
-            assert _mix_events_chan(N, [s], _chan_table(N, [ok, row]), segs, 2, nch, t, 5000) == N.SH_ERR_INVALID, what
+            assert mix_events(N, "chan", [s], event_table(N, "chan", [ok, row]), segs, 2, nch, t, 5000) == N.SH_ERR_INVALID, what
             err = N.lib().sh_last_error()
             assert err.startswith(b"sh_mix_events_chan") and b"event 1" in err and message in err, (what, err)
             assert t.download_bytes(len(base)) == base, what
     # sh_mix_events_rev keeps refusing the new bits
-    from tests.test_gpu_reversed import _mix_events_rev, _rev_table
     for nch, row in ((1, down), (2, bal), (2, bal[:16] + (B | R,))):
-        assert _mix_events_rev(N, [s], _rev_table(N, [row]), None, 2, nch, t, 5000) == N.SH_ERR_INVALID
+        assert mix_events(N, "rev", [s], event_table(N, "rev", [row]), None, 2, nch, t, 5000) == N.SH_ERR_INVALID
         assert b"event 0" in N.lib().sh_last_error() and b"unknown flags" in N.lib().sh_last_error()
         assert t.download_bytes(len(base)) == base
     # width 3 with segments; width 3 without them may be downmixed
     s3, t3 = N.DeviceBuffer.from_bytes(bytes(3000)), N.DeviceBuffer.from_bytes(bytes(15000))
     shaped = down[:11] + (0, 1) + down[13:]
-    assert _mix_events_chan(N, [s3], _chan_table(N, [down, shaped]), segs, 3, 1, t3, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "chan", [s3], event_table(N, "chan", [down, shaped]), segs, 3, 1, t3, 5000) == N.SH_ERR_INVALID
     assert b"event 1" in N.lib().sh_last_error()
     assert t3.download_bytes(15000) == bytes(15000)
-    assert _mix_events_chan(N, [s3], _chan_table(N, [down]), None, 3, 1, t3, 5000) == N.SH_OK, N.lib().sh_last_error()
+    assert mix_events(N, "chan", [s3], event_table(N, "chan", [down]), None, 3, 1, t3, 5000) == N.SH_OK, N.lib().sh_last_error()
     for width in (0, 5, -2):
-        assert _mix_events_chan(N, [s], _chan_table(N, [down]), None, width, 1, t, 5000) == N.SH_ERR_INVALID
-    assert _mix_events_chan(N, [s], _chan_table(N, [down]), None, 2, 0, t, 5000) == N.SH_ERR_INVALID
-    assert _mix_events_chan(N, [s, t], _chan_table(N, [down]), None, 2, 1, t, 5000) == N.SH_ERR_INVALID       # a source that is the track
-    assert _mix_events_chan(N, [s], _chan_table(N, [down]), None, 2, 1, t, 5001) == N.SH_ERR_INVALID
-    assert _mix_events_chan(N, [s], _chan_table(N, []), None, 2, 1, t, 5000) == N.SH_OK
+        assert mix_events(N, "chan", [s], event_table(N, "chan", [down]), None, width, 1, t, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "chan", [s], event_table(N, "chan", [down]), None, 2, 0, t, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "chan", [s, t], event_table(N, "chan", [down]), None, 2, 1, t, 5000) == N.SH_ERR_INVALID       # a source that is the track
+    assert mix_events(N, "chan", [s], event_table(N, "chan", [down]), None, 2, 1, t, 5001) == N.SH_ERR_INVALID
+    assert mix_events(N, "chan", [s], event_table(N, "chan", []), None, 2, 1, t, 5000) == N.SH_OK
     assert t.download_bytes(len(base)) == base                                                           # nothing was launched
     # and what it accepts: the downmix, the downmix backwards, a plain mono row beside them; then the balance in a stereo track
-    assert _mix_events_chan(N, [s], _chan_table(N, [down, back, plain]), None, 2, 1, t, 5000) == N.SH_OK, N.lib().sh_last_error()
+    assert mix_events(N, "chan", [s], event_table(N, "chan", [down, back, plain]), None, 2, 1, t, 5000) == N.SH_OK, N.lib().sh_last_error()
     want = bytearray(base)
     x = audioop.mul(audioop.tomono(src[400:1600], 2, 0.75, -0.25), 2, 0.5)
     want[200:800] = audioop.add(base[200:800], x, 2)
@@ -526,7 +426,7 @@ def test_the_entry_point_refuses_on_the_host_and_leaves_the_track(gpu):
     want[0:40] = audioop.add(bytes(want[0:40]), src[20:60], 2)
     assert t.download_bytes(len(base)) == bytes(want)
     t = N.DeviceBuffer.from_bytes(base)
-    assert _mix_events_chan(N, [s], _chan_table(N, [bal, bal[:16] + (B | R,)]), None, 2, 2, t, 5000) == N.SH_OK, N.lib().sh_last_error()
+    assert mix_events(N, "chan", [s], event_table(N, "chan", [bal, bal[:16] + (B | R,)]), None, 2, 2, t, 5000) == N.SH_OK, N.lib().sh_last_error()
     want = bytearray(base)
     want[200:1400] = audioop.add(base[200:1400], audioop.mul(balance(src[400:1600], 2, 0.75, -0.25), 2, 0.5), 2)
     x = audioop.mul(balance(audioop.reverse(src[400:1600], 2), 2, 0.75, -0.25), 2, 0.5)
@@ -544,7 +444,7 @@ def test_the_track_as_an_unaligned_window(gpu, nch):
     sources, base, rows, want = plain_cases(width, nch)
     ns = len(base) // width
     table = _plain_table(N, rows, nch)
-    rc, got = pcm_track_call(N, sources, base, 3 * width, lambda bufs, win, par: _mix_events_chan(N, bufs, table, None, width, nch, win, ns),
+    rc, got = pcm_track_call(N, sources, base, 3 * width, lambda bufs, win, par: mix_events(N, "chan", bufs, table, None, width, nch, win, ns),
                              surplus=16 * width)
     assert rc == N.SH_OK, N.lib().sh_last_error()
-    assert got == want, "%d bytes differ" % _differs(got, want)
+    assert got == want, "%d bytes differ" % differs(got, want)

@@ -1,113 +1,31 @@
 """GPU parity of a sustain loop per event in Sample.mix_at_many / mixer.sequence / sh_mix_events_loop -- notes longer than their recording,
 in one launch -- against bytes unrolled on the host by the frame formula (virtual frame v is frame v of the source while v < E, frame
-S + (v - E) % (E - S) after it) and then the written-out chain of tests/test_gpu_enveloped.py with live ``audioop``: ``ratecv`` over the
+S + (v - E) % (E - S) after it; tests/seqref.py: unroll) and then the rest of its chain (source, mix) with live ``audioop``: ``ratecv`` over the
 unrolled frames, the cut, the envelope, ``tostereo``, ``mul``, the cut, ``add`` with saturation at every event, in list order.  Expected
 bytes never come from the product.  Rate 8192 (a power of two: frame / RATE seconds are exact), sources of a few hundred frames, tracks
 of three tiles (a 16-bit tile is 2048 samples, the others 1024)."""
 import audioop
-import ctypes as C
-import os
-import subprocess
-import sys
 from math import gcd
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from tests.test_gpu_enveloped import _differs, envelope_bytes, shaped_source
-from tests.test_gpu_sequence import OTHER_SCHEME, ROOT, _pcm, _sample
+from tests.seqcases import (LOOPS, SHAPED_RATE, SPEEDS, STARTS, as_samples, call_level, event_table, in_a_child_under_the_other_alignment_scheme, lists,
+                            mix_events, named, rows_of, sample_of, shaped_notes, spy, with_samples)
+from tests.seqref import LANE, TILE, differs, discriminates, mix, out_frames, pcm, unroll, unroll_frames
 
 pytestmark = pytest.mark.gpu
 
 RATE = 8192
-TILE = {1: 1024, 2: 2048, 3: 1024, 4: 1024}
-LANE = {1: 4, 2: 8, 3: 4, 4: 4}
-LOOPS = [1, 2, 3, 7, 8, 9, 65]
-STARTS = [0, 1, 5]
-SPEEDS = [None, 0.1, 0.37, 0.999, 1.001, 2.5, 10]          # tests/test_gpu_sampler.py's
-RIGHT, LOOP_AFTER_RATECV, LOOP_AFTER_ENVELOPE = "right", "loop after ratecv", "loop after the envelope"
-
-
-# ---- the oracle ------------------------------------------------------------------------------------------------------------------------
-def loop_frames(loop, rate, frames):
-    S, E, V = int(rate * loop[0]), min(int(rate * loop[1]), frames), int(rate * loop[2])
-    assert S < E
-    return S, E, V
-
-
-def unroll_frames(data: bytes, fb, S, E, V) -> bytes:
-    """the V virtual frames of a looped note, by the frame formula"""
-    idx = [v if v < E else S + (v - E) % (E - S) for v in range(V)]
-    return np.frombuffer(data, dtype=np.uint8).reshape(-1, fb)[idx].tobytes() if V else b""
-
-
-def unroll(data: bytes, width, snch, rate, loop) -> bytes:
-    fb = width * snch
-    return unroll_frames(data, fb, *loop_frames(loop, rate, len(data) // fb))
-
-
-def looped_source(data, width, rate, nch, volume, other_seconds, speed, pan, env, loop, order=RIGHT) -> bytes:
-    """what mix_at is handed for one event: the loop FIRST, then shaped_source's chain -- or one of the wrong orders"""
-    snch = nch if pan is None else 1
-    if loop is None or order == RIGHT:
-        if loop is not None:
-            data = unroll(data, width, snch, rate, loop)
-        return shaped_source(data, width, rate, nch, volume, other_seconds, speed, pan, env)
-    inrate = rate if speed is None else int(rate * speed)
-    if inrate != rate:
-        data = audioop.ratecv(data, width, snch, inrate, rate, None)[0]
-    if order == LOOP_AFTER_ENVELOPE and env is not None:
-        if len(env) == 5:
-            data = data[:width * snch * int(rate * env[4])]
-        data = envelope_bytes(data, width, snch, rate, *env[:4])
-        env = None
-    data = unroll(data, width, snch, rate, loop)
-    return shaped_source(data, width, rate, nch, volume, other_seconds, None, pan, env)
-
-
-def oracle(track: bytes, events, width, rate, nch, order=RIGHT) -> bytes:
-    """events: (seconds, source bytes, volume, other_seconds, speed, pan, envelope, loop), applied one after another like upstream's mix_at"""
-    fb = width * nch
-    t = bytearray(track)
-    for seconds, data, volume, other_seconds, speed, pan, env, loop in events:
-        frames = looped_source(data, width, rate, nch, volume, other_seconds, speed, pan, env, loop, order)
-        start = fb * int(rate * seconds)
-        end = start + len(frames)
-        if end > len(t):
-            t.extend(bytes(end - len(t)))
-        t[start:end] = audioop.add(bytes(t[start:end]), frames, width)
-    return bytes(t)
-
-
-def _out_frames(n, inrate, rate):
-    return (n - 1) * rate // inrate + 1 if n else 0
 
 
 # ---- 1: plain looped events, through the entry point (track offsets count samples there) -------------------------------------------------
-def _loop_table(N, rows):
-    """rows: (dst_sample, src_sample, nsamples, src_frames, factor, left, right, src, inrate, outrate, src_channels, seg_first, seg_count,
-    reserved, loop_start, loop_frames), the tail may be left out"""
-    t = np.zeros(len(rows), dtype=N.MIX_EVENT_LOOP_DTYPE)
-    for k, r in enumerate(rows):
-        t[k] = tuple(r) + (0,) * (16 - len(r))
-    return t
-
-
-def _mix_events_loop(N, srcs, events, segments, width, nchannels, track, track_samples):
-    arr = (C.c_void_p * max(1, len(srcs)))(*[b.handle for b in srcs])
-    return N.lib().sh_mix_events_loop(arr, len(srcs), events.ctypes.data if len(events) else None, len(events),
-                                      segments.ctypes.data if segments is not None and len(segments) else None,
-                                      len(segments) if segments is not None else 0, width, nchannels,
-                                      track.handle if track is not None else None, track_samples)
-
-
 def plain_cases(width, nch):
     """(sources, rows as (dst_sample, source, S, L, V, factor)): every loop length at every track offset 0 .. 15, the starts, the four
     kinds of V and the volumes in turn; then notes over three tiles"""
     rng = np.random.default_rng(10 * width + nch)
     tile = TILE[width]
-    sources = [_pcm(rng, width, nch * n, 0.5) for n in (300, 211)]
+    sources = [pcm(rng, width, nch * n, 0.5) for n in (300, 211)]
     rows = []
     k = 0
     for L in LOOPS:
@@ -151,7 +69,7 @@ def test_plain_looped_events_at_every_offset(gpu, width, nch):
     tile, lane = TILE[width], LANE[width]
     sources, rows = plain_cases(width, nch)
     ntrack = 3 * tile - 6
-    base = _pcm(np.random.default_rng(width), width, ntrack, 0.3)
+    base = pcm(np.random.default_rng(width), width, ntrack, 0.3)
     # the list has the hard places
     seams = [(dst + (S + L) * nch) % lane for dst, _i, S, L, V, _f in rows if V > S + L]
     assert set(seams) == set(range(lane)), "the seam does not meet a lane's samples at every position"
@@ -165,23 +83,18 @@ def test_plain_looped_events_at_every_offset(gpu, width, nch):
     want = plain_want(base, sources, rows, width, nch)
     bufs = [N.DeviceBuffer.from_bytes(b) for b in sources]
     track = N.DeviceBuffer.from_bytes(base)
-    table = _loop_table(N, [(dst, 0, V * nch, V, f, 0.0, 0.0, i, RATE, RATE, nch, 0, 0, 0, S, L) for dst, i, S, L, V, f in rows])
-    assert _mix_events_loop(N, bufs, table, None, width, nch, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
+    table = event_table(N, "loop", [(dst, 0, V * nch, V, f, 0.0, 0.0, i, RATE, RATE, nch, 0, 0, 0, S, L) for dst, i, S, L, V, f in rows])
+    assert mix_events(N, "loop", bufs, table, None, width, nch, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
     got = track.download_bytes(len(base))
-    assert got == want, "%d bytes differ" % _differs(got, want)
+    assert got == want, "%d bytes differ" % differs(got, want)
     # on the parent the eighth element does nothing: the bytes of the unlooped notes are others
     assert want != plain_want(base, sources, [(d, i, S, L, min(V, S + L), f) for d, i, S, L, V, f in rows], width, nch)
 
 
 def test_plain_looped_events_under_the_other_alignment_scheme(gpu):
     """SYNTHHIP_SEQ_ALIGN is read once per process (sh_init): the 16-bit cases again in a child under the scheme that is not the default"""
-    env = dict(os.environ, SYNTHHIP_SEQ_ALIGN=OTHER_SCHEME)
-    me = str(Path(__file__).resolve())
-    p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider",
-                        me + "::test_plain_looped_events_at_every_offset[2-1]", me + "::test_plain_looped_events_at_every_offset[2-2]",
-                        me + "::test_loops_crossed_with_speed_pan_envelope_volume_and_other_seconds[2]"],
-                       cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "3 passed" in p.stdout and "failed" not in p.stdout, p.stdout[-3000:] + p.stderr[-1000:]
+    in_a_child_under_the_other_alignment_scheme(__file__, ["test_plain_looped_events_at_every_offset[2-1]", "test_plain_looped_events_at_every_offset[2-2]",
+                                                           "test_loops_crossed_with_speed_pan_envelope_volume_and_other_seconds[2]"])
 
 
 # ---- 2: crossed with the rest, through Sample.mix_at_many ---------------------------------------------------------------------------------
@@ -197,9 +110,9 @@ def notes(width, nch=2, seed=0, scale=0.6, loud=False):
     rng = np.random.default_rng(1000 * seed + 10 * width + nch)
     track_frames = 3 * TILE[width] // nch
     lengths = [300, 211, 97]
-    instruments = [(_pcm(rng, width, n, scale), 1) for n in lengths]
+    instruments = [(pcm(rng, width, n, scale), 1) for n in lengths]
     if nch == 2:
-        instruments += [(_pcm(rng, width, 2 * n, scale), 2) for n in lengths]
+        instruments += [(pcm(rng, width, 2 * n, scale), 2) for n in lengths]
     events = []
     for k in range(98):
         speed = SPEEDS[k % 7]
@@ -210,7 +123,7 @@ def notes(width, nch=2, seed=0, scale=0.6, loud=False):
         out = 150 + (37 * k) % 600                          # frames the note lands on, about
         inrate = RATE if speed is None else int(RATE * speed)
         V = max(2, out * inrate // RATE)
-        out = _out_frames(V, inrate, RATE)
+        out = out_frames(V, inrate, RATE)
         pan = [0.3, (1.0, 0.0), -0.65, (1.5, 1.2)][k % 4] if (k & 1) and nch == 2 else None
         env = None
         if (k & 2) and width != 3:
@@ -225,18 +138,6 @@ def notes(width, nch=2, seed=0, scale=0.6, loud=False):
     return _CACHE[key]
 
 
-def named(instruments, events):
-    return [(e[0], instruments[e[1]][0]) + tuple(e[2:]) for e in events]
-
-
-def with_samples(samples, events):
-    return [(e[0], samples[e[1]]) + tuple(e[2:]) for e in events]
-
-
-def as_samples(instruments, width, rate=RATE):
-    return [_sample(b, width, rate, c) for b, c in instruments]
-
-
 @pytest.mark.parametrize("width", [1, 2, 3, 4])
 def test_loops_crossed_with_speed_pan_envelope_volume_and_other_seconds(gpu, width):
     from synthesizer_amd import mixer
@@ -248,14 +149,14 @@ def test_loops_crossed_with_speed_pan_envelope_volume_and_other_seconds(gpu, wid
     if width != 3:                                          # a note length that falls inside a loop pass, behind the head
         assert any(e[6] is not None and e[4] is None and int(RATE * e[6][4]) > round(RATE * e[7][1]) and
                    (int(RATE * e[6][4]) - round(RATE * e[7][1])) % round(RATE * (e[7][1] - e[7][0])) for e in events)
-    want = oracle(b"", named(instruments, events), width, RATE, 2)
+    want = mix(b"", named(instruments, events), width, RATE, 2)
     assert 2 * TILE[width] * width < len(want) <= 3 * TILE[width] * width
-    unlooped = oracle(b"", [e[:7] + (None,) for e in named(instruments, events)], width, RATE, 2) if width == 3 else None
+    unlooped = mix(b"", [e[:7] + (None,) for e in named(instruments, events)], width, RATE, 2) if width == 3 else None
     assert unlooped is None or unlooped != want
-    samples = as_samples(instruments, width)
+    samples = as_samples(instruments, width, RATE)
     got = mixer.sequence(with_samples(samples, events), RATE, 2, width, name="held")
     assert got.name == "held" and len(got) * 2 * width == len(want)
-    assert bytes(got.view_frame_data()) == want, "%d bytes differ" % _differs(bytes(got.view_frame_data()), want)
+    assert bytes(got.view_frame_data()) == want, "%d bytes differ" % differs(bytes(got.view_frame_data()), want)
     for (b, c), smp in zip(instruments, samples):
         assert bytes(smp.view_frame_data()) == b and smp.nchannels == c                 # the instruments are untouched
 
@@ -265,7 +166,7 @@ def test_a_looped_note_at_a_reduced_outrate_of_65536_or_more(gpu, nch):
     """96 kHz against int(96000 * speed) coprime to it: the float64 route (shr::shifted_int) of the 16-bit kernel over virtual frames"""
     rate = 96000
     rng = np.random.default_rng(7 + nch)
-    instruments = [(_pcm(rng, 2, nch * n, 1.0), nch) for n in (9, 700, 301)]
+    instruments = [(pcm(rng, 2, nch * n, 1.0), nch) for n in (9, 700, 301)]
     speeds = [2 ** (7 / 12), 0.5, 0.999999, None, 1.00002, 2 ** (-7 / 12)]
     assert sum(1 for sp in speeds if sp and rate // gcd(int(rate * sp), rate) >= 65536) >= 3
     events = []
@@ -276,18 +177,18 @@ def test_a_looped_note_at_a_reduced_outrate_of_65536_or_more(gpu, nch):
         S = min(STARTS[k % 3], F - L) if k % 2 else F - L
         events.append((int(rng.integers(0, 3000)) / rate, i, [None, 0.7, -1.3][k % 3], None, speeds[k % 6], None, None,
                        ((S + 0.5) / rate, (S + L + 0.5) / rate, (900.5 + 13 * k) / rate)))
-    base = _pcm(rng, 2, nch * 5000, 0.5)
-    want = oracle(base, named(instruments, events), 2, rate, nch)
+    base = pcm(rng, 2, nch * 5000, 0.5)
+    want = mix(base, named(instruments, events), 2, rate, nch)
     samples = as_samples(instruments, 2, rate)
-    got = _sample(base, 2, rate, nch).mix_at_many(with_samples(samples, events))
+    got = sample_of(base, 2, rate, nch).mix_at_many(with_samples(samples, events))
     assert bytes(got.view_frame_data()) == want
 
 
 # ---- 3: the order ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("width", [1, 2, 4])
-def test_the_oracle_tells_the_right_order_from_each_wrong_one(gpu, width):
+def order_notes(width):
+    """every event has a loop, a speed and an envelope that the resampled recording holds, so that every wrong order can be formed"""
     rng = np.random.default_rng(40 + width)
-    instruments = [(_pcm(rng, width, 400, 0.6), 1), (_pcm(rng, width, 2 * 300, 0.6), 2)]
+    instruments = [(pcm(rng, width, 400, 0.6), 1), (pcm(rng, width, 2 * 300, 0.6), 2)]
     events = []
     for k in range(24):
         i = k % 2
@@ -297,13 +198,16 @@ def test_the_oracle_tells_the_right_order_from_each_wrong_one(gpu, width):
         env = (0.113 * dur, 0.171 * dur, 0.5, 0.233 * dur, dur)
         events.append((int(rng.integers(0, 900)) / RATE, i, [None, 0.7][k % 2], None, speed, 0.3 if i == 0 else None, env,
                        (S / RATE, (S + L) / RATE, (500 + 11 * k) / RATE)))
-    want = oracle(b"", named(instruments, events), width, RATE, 2)
-    wrong = {order: oracle(b"", named(instruments, events), width, RATE, 2, order) for order in (LOOP_AFTER_RATECV, LOOP_AFTER_ENVELOPE)}
-    differs = {order: _differs(want[:min(len(want), len(b))], b[:min(len(want), len(b))]) + abs(len(want) - len(b)) for order, b in wrong.items()}
-    print("width %d: bytes of %d that differ from the wrong orders: %s" % (width, len(want), differs))
-    assert all(n > 0 for n in differs.values()), differs
-    samples = as_samples(instruments, width)
-    got = _sample(b"", width, RATE, 2).mix_at_many(with_samples(samples, events))
+    return instruments, events
+
+
+@pytest.mark.parametrize("width", [1, 2, 4])
+def test_the_oracle_tells_the_right_order_from_each_wrong_one(gpu, width):
+    instruments, events = order_notes(width)
+    want = mix(b"", named(instruments, events), width, RATE, 2)
+    discriminates(want, named(instruments, events), width, RATE, 2, "loop")
+    samples = as_samples(instruments, width, RATE)
+    got = sample_of(b"", width, RATE, 2).mix_at_many(with_samples(samples, events))
     assert bytes(got.view_frame_data()) == want
 
 
@@ -311,8 +215,8 @@ def test_the_oracle_tells_the_right_order_from_each_wrong_one(gpu, width):
 @pytest.mark.parametrize("width", [1, 2, 3, 4])
 def test_loud_looped_events_saturate_in_list_order(gpu, width):
     instruments, events = notes(width, 2, seed=4, scale=1.0, loud=True)
-    want = oracle(b"", named(instruments, events), width, RATE, 2)
-    back = oracle(b"", named(instruments, events[::-1]), width, RATE, 2)
+    want = mix(b"", named(instruments, events), width, RATE, 2)
+    back = mix(b"", named(instruments, events[::-1]), width, RATE, 2)
     if width == 3:
         v = np.frombuffer(want, dtype=np.uint8).reshape(-1, 3)
         assert (v == (255, 255, 127)).all(axis=1).any() and (v == (0, 0, 128)).all(axis=1).any()
@@ -320,11 +224,11 @@ def test_loud_looped_events_saturate_in_list_order(gpu, width):
         v = np.frombuffer(want, dtype={1: np.int8, 2: "<i2", 4: "<i4"}[width])
         hi = 2 ** (8 * width - 1) - 1
         assert (v == hi).any() and (v == -hi - 1).any()
-    assert len(back) == len(want) and _differs(want, back) > 0                           # saturating at every event: the order matters
-    samples = as_samples(instruments, width)
-    got = _sample(b"", width, RATE, 2).mix_at_many(with_samples(samples, events))
+    assert len(back) == len(want) and differs(want, back) > 0                           # saturating at every event: the order matters
+    samples = as_samples(instruments, width, RATE)
+    got = sample_of(b"", width, RATE, 2).mix_at_many(with_samples(samples, events))
     assert bytes(got.view_frame_data()) == want
-    got = _sample(b"", width, RATE, 2).mix_at_many(with_samples(samples, events[::-1]))
+    got = sample_of(b"", width, RATE, 2).mix_at_many(with_samples(samples, events[::-1]))
     assert bytes(got.view_frame_data()) == back
 
 
@@ -333,9 +237,9 @@ def test_loud_looped_events_saturate_in_list_order(gpu, width):
 def test_the_same_bytes_as_the_loop_of_clip_join_speed_envelope_stereo_at_volume_and_mix_at(gpu, width, nch):
     instruments, events = notes(width, nch)
     events = events[::2][:28] + events[1::2][:14]
-    samples = as_samples(instruments, width)
-    base = _pcm(np.random.default_rng(9), width, 3 * TILE[width], 0.3)
-    loop_ = _sample(base, width, RATE, nch)
+    samples = as_samples(instruments, width, RATE)
+    base = pcm(np.random.default_rng(9), width, 3 * TILE[width], 0.3)
+    loop_ = sample_of(base, width, RATE, nch)
     for seconds, i, volume, other_seconds, speed, pan, envelope, loop in events:
         ls, le, length = loop
         o = samples[i].copy().clip(0.0, le)
@@ -355,51 +259,42 @@ def test_the_same_bytes_as_the_loop_of_clip_join_speed_envelope_stereo_at_volume
         if volume is not None:
             o = o.at_volume(volume)
         loop_.mix_at(seconds, o, other_seconds)
-    many = _sample(base, width, RATE, nch).mix_at_many(with_samples(samples, events))
+    many = sample_of(base, width, RATE, nch).mix_at_many(with_samples(samples, events))
     assert len(many) == len(loop_)
-    assert bytes(many.view_frame_data()) == bytes(loop_.view_frame_data()) == oracle(base, named(instruments, events), width, RATE, nch)
+    assert bytes(many.view_frame_data()) == bytes(loop_.view_frame_data()) == mix(base, named(instruments, events), width, RATE, nch)
 
 
 # ---- 6: the levels ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("width", [1, 2, 4])
 def test_a_list_of_env_gives_the_same_bytes_through_the_loop_entry_point(gpu, width):
-    from tests.test_gpu_sequence_levels import _rows, _run, lists
     N = gpu
     sources, base, _A, _B, C_, _wa, _wb, want_c = lists(width)
     bufs = [N.DeviceBuffer.from_bytes(b) for b in sources]
-    rows = _rows(C_, sources, width)
-    through_env = _run(N, "env", rows, bufs, base, width)
-    table = _loop_table(N, [(d, 0, n, sf, f, l, r, s, i, o, c, 0, 0, 0, 0, 0) for d, n, sf, f, l, r, s, i, o, c in rows])
-    track = N.DeviceBuffer.from_bytes(base)
-    assert _mix_events_loop(N, bufs, table, None, width, 2, track, len(base) // width) == N.SH_OK, N.lib().sh_last_error()
-    assert track.download_bytes(len(base)) == through_env == want_c
+    rows = rows_of(C_, sources, width)
+    got = {}
+    for level in ("env", "loop"):
+        track = N.DeviceBuffer.from_bytes(base)
+        assert call_level(N, level, rows, bufs, width, track, len(base) // width) == N.SH_OK, (level, N.lib().sh_last_error())
+        got[level] = track.download_bytes(len(base))
+    assert got["loop"] == got["env"] == want_c
 
 
 def test_a_list_without_a_loop_reaches_the_entry_point_it_reached_before(gpu, monkeypatch):
     N = gpu
     instruments, events = notes(2)
-    samples = as_samples(instruments, 2)
-    calls = []
-    real = N.lib()
-
-    class Spy:
-        def __getattr__(self, name):
-            if name.startswith("sh_mix_events"):
-                calls.append(name)
-            return getattr(real, name)
-    monkeypatch.setattr(N, "lib", lambda: Spy())
-    from tests import test_gpu_enveloped as E                # its list: envelopes that fit the recordings as they are
-    e_instruments, e_events = E.notes(2, 2)
-    e_samples = E.as_samples(e_instruments, 2)
+    samples = as_samples(instruments, 2, RATE)
+    calls = spy(N, monkeypatch)
+    e_instruments, e_events = shaped_notes(2, 2)            # the envelope file's list: envelopes that fit the recordings as they are
+    e_samples = as_samples(e_instruments, 2, SHAPED_RATE)
     unlooped = [(s_, e_samples[i], v, o, sp, p, e, None) for s_, i, v, o, sp, p, e in e_events]
-    got = _sample(b"", 2, E.RATE, 2).mix_at_many(unlooped)
+    got = sample_of(b"", 2, SHAPED_RATE, 2).mix_at_many(unlooped)
     assert calls == ["sh_mix_events_env"]
-    assert bytes(got.view_frame_data()) == E.oracle(b"", E.named(e_instruments, e_events), 2, E.RATE, 2)
+    assert bytes(got.view_frame_data()) == mix(b"", named(e_instruments, e_events), 2, SHAPED_RATE, 2)
     del calls[:]
-    _sample(b"", 2, E.RATE, 2).mix_at_many([e[:6] + (None, None) for e in unlooped])
+    sample_of(b"", 2, SHAPED_RATE, 2).mix_at_many([e[:6] + (None, None) for e in unlooped])
     assert calls == ["sh_mix_events_pan"]
     del calls[:]
-    _sample(b"", 2, RATE, 2).mix_at_many(with_samples(samples, events[:40]))
+    sample_of(b"", 2, RATE, 2).mix_at_many(with_samples(samples, events[:40]))
     assert calls == ["sh_mix_events_loop"]
 
 
@@ -410,26 +305,18 @@ def test_looped_and_unlooped_events_in_one_list_and_the_track_as_a_looped_source
     instruments, events = notes(width, nch)
     events = [e if k % 3 else e[:6] + (None, None) for k, e in enumerate(events)]      # (an envelope sized for the held note does not fit the recording)
     assert any(e[7] is None for e in events[:50]) and any(e[7] is not None and e[6] is not None for e in events[:50])
-    samples = as_samples(instruments, width)
-    calls = []
-    real = N.lib()
-
-    class Spy:
-        def __getattr__(self, name):
-            if name.startswith("sh_mix_events"):
-                calls.append(name)
-            return getattr(real, name)
-    monkeypatch.setattr(N, "lib", lambda: Spy())
-    base = _pcm(np.random.default_rng(3), width, 3 * TILE[width], 0.3)
-    t = _sample(base, width, RATE, nch)
+    samples = as_samples(instruments, width, RATE)
+    calls = spy(N, monkeypatch)
+    base = pcm(np.random.default_rng(3), width, 3 * TILE[width], 0.3)
+    t = sample_of(base, width, RATE, nch)
     first, last = events[:30], events[30:50]
     env = (0.02, 0.03, 0.5, 0.05, 0.2)
     own = (0.05, None, 0.4, None, 1.5, None, env, (100 / RATE, 171 / RATE, 0.4))
     t.mix_at_many(with_samples(samples, first) + [own[:1] + (t,) + own[2:]] + with_samples(samples, last))
     assert calls == ["sh_mix_events_loop", "sh_mix_events_loop"]                         # the list is cut at the track; one launch per side
-    mid = oracle(base, named(instruments, first), width, RATE, nch)
-    mid = oracle(mid, [own[:1] + (mid,) + own[2:]], width, RATE, nch)
-    assert bytes(t.view_frame_data()) == oracle(mid, named(instruments, last), width, RATE, nch)
+    mid = mix(base, named(instruments, first), width, RATE, nch)
+    mid = mix(mid, [own[:1] + (mid,) + own[2:]], width, RATE, nch)
+    assert bytes(t.view_frame_data()) == mix(mid, named(instruments, last), width, RATE, nch)
 
 
 def test_the_track_as_a_looped_source_is_clamped_to_what_the_events_before_left(gpu):
@@ -437,22 +324,22 @@ def test_the_track_as_a_looped_source_is_clamped_to_what_the_events_before_left(
     grown part, and beyond its end -- not to what it held when the list was read"""
     width, nch = 2, 2
     instruments, events = notes(width, nch)
-    samples = as_samples(instruments, width)
+    samples = as_samples(instruments, width, RATE)
     first, last = events[:30], events[30:40]
-    mid = oracle(b"", named(instruments, first), width, RATE, nch)
+    mid = mix(b"", named(instruments, first), width, RATE, nch)
     frames = len(mid) // (width * nch)
     assert frames > 1000
     inside = (0.05, None, 0.4, None, 1.5, None, (0.02, 0.03, 0.5, 0.05, 0.2), (100 / RATE, 171 / RATE, 0.4))
     beyond = (0.01, None, -0.7, 0.3, None, None, None, ((frames - 300) / RATE, (frames + 500) / RATE, (frames + 900) / RATE))
-    t = _sample(b"", width, RATE, nch)
+    t = sample_of(b"", width, RATE, nch)
     t.mix_at_many(with_samples(samples, first) + [inside[:1] + (t,) + inside[2:], beyond[:1] + (t,) + beyond[2:]] + with_samples(samples, last))
-    want = oracle(mid, [inside[:1] + (mid,) + inside[2:]], width, RATE, nch)
+    want = mix(mid, [inside[:1] + (mid,) + inside[2:]], width, RATE, nch)
     assert len(want) // (width * nch) < frames + 500                                     # the second loop's end lies beyond the track still
-    want = oracle(want, [beyond[:1] + (want,) + beyond[2:]], width, RATE, nch)
-    want = oracle(want, named(instruments, last), width, RATE, nch)
+    want = mix(want, [beyond[:1] + (want,) + beyond[2:]], width, RATE, nch)
+    want = mix(want, named(instruments, last), width, RATE, nch)
     assert bytes(t.view_frame_data()) == want
     # a loop that is empty in the track as the events before left it: found when that event runs
-    t = _sample(b"", width, RATE, nch)
+    t = sample_of(b"", width, RATE, nch)
     with pytest.raises(ValueError, match="mix_at_many: loop"):
         t.mix_at_many(with_samples(samples, first) + [(0.0, t, None, None, None, None, None, ((frames + 10) / RATE, (frames + 90) / RATE, 3.0))])
     assert bytes(t.view_frame_data()) == mid
@@ -462,7 +349,7 @@ def test_the_track_as_a_looped_source_is_clamped_to_what_the_events_before_left(
 def test_the_entry_point_refuses_on_the_host_and_leaves_the_track(gpu):
     N = gpu
     rng = np.random.default_rng(26)
-    src, base = _pcm(rng, 2, 1000), _pcm(rng, 2, 5000)
+    src, base = pcm(rng, 2, 1000), pcm(rng, 2, 5000)
     s, t = N.DeviceBuffer.from_bytes(src), N.DeviceBuffer.from_bytes(base)
     nan = float("nan")
     segs = np.zeros(1, dtype=N.ENV_SEGMENT_DTYPE)
@@ -495,26 +382,26 @@ def test_the_entry_point_refuses_on_the_host_and_leaves_the_track(gpu):
     }
     for what, row in bad.items():
         rows = [ok, row]
-        assert _mix_events_loop(N, [s], _loop_table(N, rows), segs, 2, 2, t, 5000) == N.SH_ERR_INVALID, what
+        assert mix_events(N, "loop", [s], event_table(N, "loop", rows), segs, 2, 2, t, 5000) == N.SH_ERR_INVALID, what
         err = N.lib().sh_last_error()
         assert err.startswith(b"sh_mix_events_loop") and b"event 1" in err, (what, err)      # the event is named
         assert t.download_bytes(len(base)) == base, what
     # width 3 with segments; width 3 without them may loop
     s3, t3 = N.DeviceBuffer.from_bytes(bytes(3000)), N.DeviceBuffer.from_bytes(bytes(15000))
     shaped = ok[:11] + (0, 1) + ok[13:]
-    assert _mix_events_loop(N, [s3], _loop_table(N, [ok, shaped]), segs, 3, 2, t3, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "loop", [s3], event_table(N, "loop", [ok, shaped]), segs, 3, 2, t3, 5000) == N.SH_ERR_INVALID
     assert b"event 1" in N.lib().sh_last_error()
     assert t3.download_bytes(15000) == bytes(15000)
-    assert _mix_events_loop(N, [s3], _loop_table(N, [ok]), None, 3, 2, t3, 5000) == N.SH_OK, N.lib().sh_last_error()
+    assert mix_events(N, "loop", [s3], event_table(N, "loop", [ok]), None, 3, 2, t3, 5000) == N.SH_OK, N.lib().sh_last_error()
     for width in (0, 5, -2):
-        assert _mix_events_loop(N, [s], _loop_table(N, [ok]), None, width, 2, t, 5000) == N.SH_ERR_INVALID
-    assert _mix_events_loop(N, [s], _loop_table(N, [ok]), None, 2, 0, t, 5000) == N.SH_ERR_INVALID
-    assert _mix_events_loop(N, [s, t], _loop_table(N, [ok]), None, 2, 2, t, 5000) == N.SH_ERR_INVALID      # a source that is the track
-    assert _mix_events_loop(N, [s], _loop_table(N, [ok]), None, 2, 2, t, 5001) == N.SH_ERR_INVALID
-    assert _mix_events_loop(N, [s], _loop_table(N, []), None, 2, 2, t, 5000) == N.SH_OK
+        assert mix_events(N, "loop", [s], event_table(N, "loop", [ok]), None, width, 2, t, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "loop", [s], event_table(N, "loop", [ok]), None, 2, 0, t, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "loop", [s, t], event_table(N, "loop", [ok]), None, 2, 2, t, 5000) == N.SH_ERR_INVALID      # a source that is the track
+    assert mix_events(N, "loop", [s], event_table(N, "loop", [ok]), None, 2, 2, t, 5001) == N.SH_ERR_INVALID
+    assert mix_events(N, "loop", [s], event_table(N, "loop", []), None, 2, 2, t, 5000) == N.SH_OK
     assert t.download_bytes(len(base)) == base                                                         # nothing was launched
     # and what it accepts: the stereo note, then the mono one through tostereo
-    assert _mix_events_loop(N, [s], _loop_table(N, [ok, mono]), None, 2, 2, t, 5000) == N.SH_OK, N.lib().sh_last_error()
+    assert mix_events(N, "loop", [s], event_table(N, "loop", [ok, mono]), None, 2, 2, t, 5000) == N.SH_OK, N.lib().sh_last_error()
     want = bytearray(base)
     held = audioop.mul(unroll_frames(src, 4, 100, 300, 900), 2, 0.5)
     want[200:3800] = audioop.add(base[200:3800], held, 2)

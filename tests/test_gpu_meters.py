@@ -1,5 +1,5 @@
 """GPU parity of the level meters of a song of tracks -- CompiledSequence.render(..., meters=True) / N.Sequence.render(meters=True) /
-sh_seq_render_meters -- against live ``audioop`` and integers.  The expected rows come from tests/test_gpu_tracks.py's per-track oracle
+sh_seq_render_meters -- against live ``audioop`` and integers.  The expected rows come from tests/seqcases.py's per-track reference
 (every track folded on its own, ``audioop.mul`` by its gain -- none at exactly 1.0 --, padded with silence; the master ``audioop.add`` in
 track order), cut to the window and reduced here with numpy int64 / uint64 and Python ints: per channel (song sample s is channel s & 1
 of a stereo song) the peak, max |x|, and the exact sum of x * x.  Expected values never come from the product.  Rate 8192 and the
@@ -13,16 +13,13 @@ import math
 import numpy as np
 import pytest
 
-from tests.test_gpu_compiled import LEVEL_NAME, _ev, in_a_child_under_the_other_alignment_scheme, song, windows
-from tests.test_gpu_looped import LANE, RATE, TILE
-from tests.test_gpu_reversed import as_samples, named, with_samples
-from tests.test_gpu_sequence import _pcm
-from tests.test_gpu_tracks import GAINS, bus_song, ints, master, raw_tracks, subs_of
+from tests.seqcases import (GAINS, RATE, _ev, as_samples, bus_song, in_a_child_under_the_other_alignment_scheme, master, metered, post_fader, raw_tracks,
+                            reference, subs_of, the_song, windows, with_samples)
+from tests.seqref import LANE, TILE, pcm
 
 pytestmark = pytest.mark.gpu
 
 ZERO = ((0, 0), (0, 0))
-U32, MASK = np.uint64(32), np.uint64(0xFFFFFFFF)
 
 
 # ---- the reference ---------------------------------------------------------------------------------------------------------------------
@@ -31,40 +28,6 @@ def to_bytes(v, width):
     if width == 3:
         return v.astype("<i4").view(np.uint8).reshape(-1, 4)[:, :3].tobytes()
     return v.astype({1: np.int8, 2: "<i2", 4: "<i4"}[width]).tobytes()
-
-
-def row_of(x, a, nch):
-    """the row of song samples a .. a + len(x): ((peak, peak), (sum, sum)), the sums Python ints formed from two uint64 sums"""
-    peak, sq = [0, 0], [0, 0]
-    for c in range(2 if nch == 2 else 1):
-        v = x[(c - a) % 2::2] if nch == 2 else x            # song sample a + i is channel (a + i) & 1
-        if len(v):
-            m = np.abs(v).astype(np.uint64)                  # |-2^31| = 2^31, taken in int64
-            s = m * m                                        # <= 2^62
-            peak[c] = int(m.max())
-            sq[c] = (int((s >> U32).sum(dtype=np.uint64)) << 32) + int((s & MASK).sum(dtype=np.uint64))
-    return tuple(peak), tuple(sq)
-
-
-_POST = {}
-
-
-def post_fader(key, subs, gains, width):
-    """(the tracks as the master takes them, the master), as int64 arrays of the song's length; made once per song and gain vector"""
-    if (key, gains) not in _POST:
-        total = max([len(s) for s in subs] + [0])
-        scaled = []
-        for sub, g in zip(subs, [1.0] * len(subs) if gains is None else gains):
-            if g != 1.0:
-                sub = audioop.mul(sub, width, g)
-            scaled.append(ints(sub + bytes(total - len(sub)), width))
-        _POST[(key, gains)] = (scaled, ints(master(subs, gains, width), width), master(subs, gains, width))
-    return _POST[(key, gains)]
-
-
-def reference(key, subs, gains, width, nch, a, b):
-    scaled, mast, _bytes = post_fader(key, subs, gains, width)
-    return [row_of(x[a:b], a, nch) for x in scaled] + [row_of(mast[a:b], a, nch)]
 
 
 def check_against_audioop(key, subs, gains, width, nch, a, b, rows):
@@ -92,35 +55,11 @@ def check_against_audioop(key, subs, gains, width, nch, a, b, rows):
 SONGS = [("bus", 2), ("balance", 2), ("rate", 2), ("bus", 1), ("bus", 3), ("bus", 4), ("balance", 4)]
 
 
-def the_song(kind, width):
-    """(instruments, tracks, nch, the sub-mixes, total samples, level)"""
-    if kind == "bus":
-        instruments, tracks, subs, total = bus_song(width)
-        return instruments, tracks, 1, subs, total, "plain"
-    instruments, events, nch, _flat, total = song(kind, width)
-    tracks = [events[0::3], events[1::3], events[2::3]]         # the list dealt over three tracks, as tests/test_gpu_tracks.py deals it
-    key = ("subs", kind, width)
-    if key not in _POST:
-        _POST[key] = subs_of(instruments, tracks, width, nch)
-    return instruments, tracks, nch, _POST[key], total, LEVEL_NAME.get(kind, kind)
-
-
 def the_windows(kind, width, total):
     """whole song (the heaviest-first permutation), mid-lane start and end, across a tile's edge, one sample, inside the idle tile, the
     pile-up, (balance) an odd first sample; and one lane, and a window that ends at the song's mid-lane end"""
     T, L = TILE[width], LANE[width]
     return windows(kind if kind == "balance" else "plain", width, total) + [(2 * L, 3 * L), (T + 5, total)]
-
-
-def metered(N, seq, width, a, b, gains, out_sample=0):
-    """(rows, the rendered bytes, the guards intact) of a metered render into a 0x5A-filled buffer"""
-    n = b - a
-    inner = (out_sample + n) * width
-    parent = N.DeviceBuffer.from_bytes(b"\x5a" * (64 + inner + 64))
-    rows = seq.render(a, n, parent.view(64, inner), out_sample, gains=gains, meters=True)
-    got = parent.download_bytes(64 + inner + 64)
-    at = 64 + out_sample * width
-    return rows, got[at:at + n * width], got[:at] == b"\x5a" * at and got[at + n * width:] == b"\x5a" * 64
 
 
 def plain(N, seq, width, a, b, gains):
@@ -174,7 +113,7 @@ def test_full_scale_samples_beside_the_window_in_its_edge_lanes_do_not_count(gpu
     rng = np.random.default_rng(70 + width)
     quiet = rng.integers(-top // 8, top // 8, n)
     spiky = to_bytes(np.concatenate([[-top], quiet, [top - 1]]), width)     # full scale at samples a - 1 and a + n, quiet between
-    instruments = [(spiky, 1), (_pcm(rng, width, 300, 0.1), 1)]
+    instruments = [(spiky, 1), (pcm(rng, width, 300, 0.1), 1)]
     tracks = [[_ev(a - 1, 0)], [_ev(a - 40, 1, 0.5), _ev(a + n - 100, 1)]]
     subs = subs_of(instruments, tracks, width, 1)
     key = ("edge", width)
@@ -200,7 +139,7 @@ def test_a_track_that_sounds_only_left_reads_zero_on_the_right(gpu, how, width):
     T = TILE[width]
     rng = np.random.default_rng(80 + width)
     src_ch = 2 if how == "channels" else 1
-    instruments = [(_pcm(rng, width, 600 * src_ch, 0.5), src_ch), (_pcm(rng, width, 300 * src_ch, 0.4), src_ch)]
+    instruments = [(pcm(rng, width, 600 * src_ch, 0.5), src_ch), (pcm(rng, width, 300 * src_ch, 0.4), src_ch)]
     left_only = dict(channels=(1.0, 0.0)) if how == "channels" else dict(pan=(1.0, 0.0))
     both = dict(channels=(0.75, 0.5)) if how == "channels" else dict(pan=(0.5, 1.0))
     F = T // 2
@@ -209,7 +148,7 @@ def test_a_track_that_sounds_only_left_reads_zero_on_the_right(gpu, how, width):
     subs = subs_of(instruments, tracks, width, 2)
     key = (how, width)
     total = max(len(s) for s in subs) // width
-    samples = as_samples(instruments, width)
+    samples = as_samples(instruments, width, RATE)
     with mixer.compile_tracks([with_samples(samples, t) for t in tracks], RATE, 2, width) as cs:
         assert cs.level == ("chan" if how == "channels" else "pan") and cs.frames == total // 2
         for gains in (None, (1.7, 0.5)):
@@ -276,7 +215,7 @@ def test_a_sum_of_squares_past_two_to_the_64_at_width_four(gpu):
     T, L = TILE[4], LANE[4]
     rng = np.random.default_rng(91)
     loud = np.concatenate([[-2 ** 31] * 7, rng.integers(-2 ** 31, 2 ** 31, 500), [-2 ** 31] * 3])
-    instruments = [(to_bytes(loud, 4), 1), (_pcm(rng, 4, 300, 0.3), 1)]
+    instruments = [(to_bytes(loud, 4), 1), (pcm(rng, 4, 300, 0.3), 1)]
     tracks = [[_ev(T - 200, 0)], [_ev(T - 100, 1, 0.5), _ev(5, 1)]]
     subs = subs_of(instruments, tracks, 4, 1)
     key = ("wide", 4)
@@ -298,7 +237,7 @@ def test_a_sum_of_squares_past_two_to_the_53_at_width_three(gpu):
     T = TILE[3]
     rng = np.random.default_rng(93)
     loud = rng.choice([-2 ** 23, 2 ** 23 - 1, 2 ** 23 - 3], 600)
-    instruments = [(to_bytes(loud, 3), 1), (_pcm(rng, 3, 300, 0.3), 1)]
+    instruments = [(to_bytes(loud, 3), 1), (pcm(rng, 3, 300, 0.3), 1)]
     tracks = [[_ev(T - 250, 0)], [_ev(T - 100, 1, 0.5)]]
     subs = subs_of(instruments, tracks, 3, 1)
     key = ("wide", 3)

@@ -7,29 +7,23 @@ the gather's sources and the outputs are DeviceBuffer.view windows at chosen res
 (tests/helpers.py: pcm_view_call, pcm_track_call), which assert the pointer's residue, untouched inputs and untouched bytes around
 every window.
 
-References, none of them the library: the audioop oracles of tests/test_gpu_sequence_levels.py (lists), tests/test_gpu_looped.py and
-tests/test_gpu_reversed.py (oracle) for the track; the loop of live audioop.add / audioop.tostereo for the chain
+References, none of them the library: tests/seqref.py (mix) over the lists of tests/seqcases.py (lists) and the shaped lists below for
+the track; the loop of live audioop.add / audioop.tostereo for the chain
 (tests/test_gpu_realtime_mixer.py: _audioop_fold).  Every comparison is byte equality.  tests/test_mix_view_refs.py checks the case
 tables below without a GPU.
 """
 import audioop
 import ctypes as C
 import functools
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from tests import test_gpu_looped as LP
-from tests import test_gpu_reversed as RV
 from tests.helpers import PCM_GUARD, PCM_OUT_SENTINEL, pcm_track_call, pcm_view_call
+from tests.seqcases import RATE, as_samples, call_level, in_a_child_under_the_other_alignment_scheme, lists, named, rows_of, sample_of, with_samples
+from tests.seqref import mix, out_frames, pcm, source
 from tests.test_gpu_pcm_views import _check, residues
 from tests.test_gpu_realtime_mixer import _audioop_fold, _rand_pcm
-from tests.test_gpu_sequence import OTHER_SCHEME, ROOT, _pcm, _sample
-from tests.test_gpu_sequence_levels import RATE, _rows, lists
 
 pytestmark = pytest.mark.gpu
 
@@ -40,42 +34,21 @@ SURPLUS = 16                                               # samples of window b
 LEVELS = {"A": ["plain", "rate", "pan", "env"], "B": ["rate", "pan", "env"], "C": ["pan", "env"]}
 
 
-def _call_level(N, level, rows, bufs, width, track, ns):
-    """one call of the entry point of `level` (tests/test_gpu_sequence_levels.py: _run) on `track`"""
-    if level == "plain":
-        t = np.array([(d, 0, n, f, s, 0) for d, n, _sf, f, _l, _r, s, _i, _o, _c in rows], dtype=N.MIX_EVENT_DTYPE)
-    elif level == "rate":
-        t = np.array([(d, 0, n, sf, f, s, i, o, 0) for d, n, sf, f, _l, _r, s, i, o, _c in rows], dtype=N.MIX_EVENT_RATE_DTYPE)
-    elif level == "pan":
-        t = np.array([(d, 0, n, sf, f, l, r, s, i, o, c, 0) for d, n, sf, f, l, r, s, i, o, c in rows], dtype=N.MIX_EVENT_PAN_DTYPE)
-    else:
-        t = np.array([(d, 0, n, sf, f, l, r, s, i, o, c, 0, 0, 0) for d, n, sf, f, l, r, s, i, o, c in rows], dtype=N.MIX_EVENT_ENV_DTYPE)
-    arr = (C.c_void_p * len(bufs))(*[b.handle for b in bufs])
-    lib = N.lib()
-    if level == "plain":
-        return lib.sh_mix_events(arr, len(bufs), t.ctypes.data, len(t), width, track.handle, ns)
-    if level == "rate":
-        return lib.sh_mix_events_rate(arr, len(bufs), t.ctypes.data, len(t), width, 2, track.handle, ns)
-    if level == "pan":
-        return lib.sh_mix_events_pan(arr, len(bufs), t.ctypes.data, len(t), width, track.handle, ns)
-    return lib.sh_mix_events_env(arr, len(bufs), t.ctypes.data, len(t), None, 0, width, 2, track.handle, ns)
-
-
 @pytest.mark.parametrize("width", [1, 2, 3, 4])
 def test_track_windows_plain_rate_pan_env(gpu, width):
-    """the lists of tests/test_gpu_sequence_levels.py into a track window at every residue, track_samples the window and 16 samples
+    """the lists of tests/seqcases.py into a track window at every residue, track_samples the window and 16 samples
     short of it: audioop's bytes, the same at every residue, nothing written around the track"""
     N = gpu
     sources, base, A, B, C_, want_a, want_b, want_c = lists(width)
     ns = len(base) // width
     for name, lst, want in (("A", A, want_a), ("B", B, want_b), ("C", C_, want_c)):
-        rows = _rows(lst, sources, width)
+        rows = rows_of(lst, sources, width)
         for level in LEVELS[name]:
             if level == "env" and width == 3:               # an envelope's fades have no 24-bit form
                 continue
             for a in residues(width):
                 for surplus in (0, SURPLUS * width):
-                    rc, got = pcm_track_call(N, sources, base, a, lambda bufs, win, par: _call_level(N, level, rows, bufs, width, win, ns), surplus=surplus)
+                    rc, got = pcm_track_call(N, sources, base, a, lambda bufs, win, par: call_level(N, level, rows, bufs, width, win, ns), surplus=surplus)
                     _check(rc, got, want, (name, level, width, a, surplus))
 
 
@@ -105,12 +78,12 @@ SHAPED = {
 
 @functools.lru_cache(maxsize=None)
 def shaped(kind, width):
-    """-> (instruments as (bytes, channels), base, events as tests/test_gpu_reversed.py has them (8-tuples for "loop"), audioop's
+    """-> (instruments as (bytes, channels), base, events of ten fields in the ladder's order (8-tuples for "loop"), audioop's
     bytes, [(first track sample, samples) per event]).  Made once, never changed."""
     rng = np.random.default_rng(900 + 10 * width + (kind == "rev"))
     sources, base = lists(width)[:2]
     track_frames = len(base) // (2 * width)
-    instruments = [(_pcm(rng, width, n, 0.6), 1) for n in HELD] + [(_pcm(rng, width, 2 * n, 0.6), 2) for n in HELD[:2]]
+    instruments = [(pcm(rng, width, n, 0.6), 1) for n in HELD] + [(pcm(rng, width, 2 * n, 0.6), 2) for n in HELD[:2]]
     events, spans = [], []
     for i, volume, other_seconds, speed, pan, shaped_, loop, region, reverse, where in SHAPED[kind]:
         data, snch = instruments[i]
@@ -120,24 +93,21 @@ def shaped(kind, width):
         R = frames if region is None else (frames - region[0] if region[1] is None else region[1])
         lp = None if loop is None else (loop[0] / RATE, (loop[0] + loop[1]) / RATE, loop[2] / RATE)
         inrate = RATE if speed is None else int(RATE * speed)
-        out = LP._out_frames(R if loop is None else loop[2], inrate, RATE)
+        out = out_frames(R if loop is None else loop[2], inrate, RATE)
         env = None
         if shaped_ and width != 3:
             dur = (0.61 * out + 0.37) / RATE
             env = (0.113 * dur, 0.171 * dur, 0.5, 0.233 * dur, dur)
-        played = RV.played_source(data, width, RATE, 2, volume, other_seconds, speed, pan, env, lp, reg, reverse)
+        played = source(data, width, RATE, 2, volume=volume, other_seconds=other_seconds, speed=speed, pan=pan, env=env, loop=lp, region=reg, reverse=reverse)
         out = len(played) // (2 * width)
         frame = track_frames - out if where == "end" else where
         assert 0 <= frame and frame + out <= track_frames
         events.append((frame / RATE, i, volume, other_seconds, speed, pan, env, lp, reg, reverse))
         spans.append((2 * frame, 2 * out))
-    named = RV.named(instruments, events)
+    want = mix(base, named(instruments, events), width, RATE, 2)
     if kind == "loop":
         assert all(e[8] is None and not e[9] for e in events)
         events = [e[:8] for e in events]
-        want = LP.oracle(base, [e[:8] for e in named], width, RATE, 2)
-    else:
-        want = RV.oracle(base, named, width, RATE, 2)
     assert len(want) == len(base) and want != base
     return instruments, base, events, want, spans
 
@@ -163,10 +133,10 @@ def _recorded_call(N, monkeypatch, kind, width):
                 calls.append((name, (srcs, nsrc, table, segs, w, nch, ns)))
                 return fn(*args)
             return watched
-    samples = RV.as_samples(instruments, width)
+    samples = as_samples(instruments, width, RATE)
     with monkeypatch.context() as m:
         m.setattr(N, "lib", lambda: Spy())
-        got = _sample(base, width, RATE, 2).mix_at_many(RV.with_samples(samples, events))
+        got = sample_of(base, width, RATE, 2).mix_at_many(with_samples(samples, events))
     assert [c[0] for c in calls] == ["sh_mix_events_" + kind], calls
     assert bytes(got.view_frame_data()) == want               # (a fresh aligned track: what the other tests already cover)
     return calls[0][0], calls[0][1], samples
@@ -195,12 +165,8 @@ def test_track_windows_loop_rev(gpu, monkeypatch, width, kind):
 
 def test_track_windows_under_the_other_alignment_scheme(gpu):
     """SYNTHHIP_SEQ_ALIGN is read once per process (sh_init): the 16-bit cases again in a child under the scheme that is not the default"""
-    env = dict(os.environ, SYNTHHIP_SEQ_ALIGN=OTHER_SCHEME)
-    me = str(Path(__file__).resolve())
-    p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider",
-                        me + "::test_track_windows_plain_rate_pan_env[2]", me + "::test_track_windows_loop_rev[2-loop]",
-                        me + "::test_track_windows_loop_rev[2-rev]"], cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "3 passed" in p.stdout and "failed" not in p.stdout, p.stdout[-3000:] + p.stderr[-1000:]
+    in_a_child_under_the_other_alignment_scheme(__file__, ["test_track_windows_plain_rate_pan_env[2]", "test_track_windows_loop_rev[2-loop]",
+                                                           "test_track_windows_loop_rev[2-rev]"])
 
 
 # ---- 2: refusals are checked against the window and track_samples -------------------------------------------------------------------
@@ -214,8 +180,8 @@ def test_track_refusals_against_the_window(gpu, width):
     lib = N.lib()
     rng = np.random.default_rng(width)
     ns = 200
-    base = _pcm(rng, width, ns, 0.4)
-    src = _pcm(rng, width, 8, 0.4)
+    base = pcm(rng, width, ns, 0.4)
+    src = pcm(rng, width, 8, 0.4)
 
     def plain(events, track_samples, extra=()):
         def call(bufs, win, par):

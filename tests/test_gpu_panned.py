@@ -1,70 +1,25 @@
 """GPU parity of a pan per event in Sample.mix_at_many / mixer.sequence / sh_mix_events_pan -- mono instruments placed in the stereo field
 of a stereo track, in one launch -- against live ``audioop``: ``ratecv`` of the mono frames, then ``tostereo``, then ``mul``, then the cut,
 then ``add`` with saturation at every event, in list order, on byte slices; the arithmetic of the loop of ``copy().speed().stereo()``,
-``at_volume`` and ``mix_at`` it replaces.  Expected bytes never come from the product."""
+``at_volume`` and ``mix_at`` it replaces (tests/seqref.py: source, mix, and the three wrong orders of the pan level).  Expected bytes never
+come from the product."""
 import audioop
-import ctypes as C
 from math import gcd
 
 import numpy as np
 import pytest
 
-from tests.test_gpu_sequence import RATE, VOLUMES, _pcm, _sample
+from tests.seqcases import SONG_RATE as RATE, VOLUMES, event_table, in_a_child_under_the_other_alignment_scheme, mix_events, sample_of
+from tests.seqref import WRONG, differs, mix, pcm
 
 pytestmark = pytest.mark.gpu
 
 # float pans (Sample.pan's), pairs with a 0 (stereo_mix's "into one channel only"), negative factors, factors above 1
 PANS = [0.0, -1.0, 0.3, (1.0, 0.0), (-0.5, 0.8), (1.5, 1.2), 1.0, (0.0, 0.7), -0.65, (0.4, -1.0), (2.0, 0.25), (1.0, 1.0)]
 
-RIGHT, MUL_FIRST, FOLDED, STEREO_FIRST = range(4)
-
-
-def factors(pan):
-    if isinstance(pan, tuple):
-        return float(pan[0]), float(pan[1])
-    return (1.0 - pan) / 2.0, (1.0 + pan) / 2.0           # Sample.pan upstream
-
-
-def oracle(track: bytes, events, width, rate, order=RIGHT) -> bytes:
-    """The track is stereo.  events: (seconds, source bytes, volume | None, other_seconds | None, speed | None, pan | None) -- a source
-    with a pan is mono, one without is stereo -- applied like upstream's copy().speed(), stereo(), at_volume() and mix_at, one after
-    another.  order: RIGHT, or one of the three WRONG orders, to show that each can be told from it."""
-    fb = 2 * width
-    t = bytearray(track)
-    for seconds, frames, volume, other_seconds, speed, pan in events:
-        nch = 2 if pan is None else 1
-        inrate = rate if speed is None else int(rate * speed)
-        left, right = factors(pan) if pan is not None else (None, None)
-        if pan is not None and order == STEREO_FIRST:
-            frames, nch = audioop.tostereo(frames, width, left, right), 2
-        if inrate != rate:
-            frames = audioop.ratecv(frames, width, nch, inrate, rate, None)[0]
-        if pan is None or order == STEREO_FIRST:
-            if volume is not None:
-                frames = audioop.mul(frames, width, volume)
-        elif order == RIGHT:
-            frames = audioop.tostereo(frames, width, left, right)
-            if volume is not None:
-                frames = audioop.mul(frames, width, volume)
-        elif order == MUL_FIRST:
-            if volume is not None:
-                frames = audioop.mul(frames, width, volume)
-            frames = audioop.tostereo(frames, width, left, right)
-        else:
-            v = 1.0 if volume is None else volume
-            frames = audioop.tostereo(frames, width, left * v, right * v)
-        if other_seconds:
-            frames = frames[:fb * int(rate * other_seconds)]
-        start = fb * int(rate * seconds)
-        end = start + len(frames)
-        if end > len(t):
-            t.extend(bytes(end - len(t)))
-        t[start:end] = audioop.add(bytes(t[start:end]), frames, width)
-    return bytes(t)
-
 
 def panned_song(nevents=3000, span=20.0):
-    """test_gpu_sequence's song with mono instruments (0 .. 3) and two stereo ones (4, 5) into a stereo track: a speed 2^(k/12) per
+    """the plain file's song (tests/seqcases.py: hits_song) with mono instruments (0 .. 3) and two stereo ones (4, 5) into a stereo track: a speed 2^(k/12) per
     event, a quarter of them None; a pan per event of a mono instrument, cycling through PANS"""
     rng = np.random.default_rng(0)
     instruments = []
@@ -86,20 +41,14 @@ def panned_song(nevents=3000, span=20.0):
     return instruments, events
 
 
-def _differs(a: bytes, b: bytes) -> int:
-    assert len(a) == len(b)
-    return int(np.count_nonzero(np.frombuffer(a, dtype=np.uint8) != np.frombuffer(b, dtype=np.uint8)))
-
-
 # ---- 1: a stereo song ------------------------------------------------------------------------------------------------------------------
 def test_a_stereo_song_of_mono_instruments(gpu):
     from synthesizer_amd import mixer
     instruments, events = panned_song()
     named = [(s, instruments[i], v, o, sp, p) for s, i, v, o, sp, p in events]
-    want = oracle(b"", named, 2, RATE)
+    want = mix(b"", named, 2, RATE, 2)
     # the oracle must be able to tell the order ratecv -> tostereo -> mul from the three wrong ones
-    wrong = {name: _differs(want, oracle(b"", named, 2, RATE, order))
-             for name, order in (("mul before tostereo", MUL_FIRST), ("volume folded into the factors", FOLDED), ("tostereo before ratecv", STEREO_FIRST))}
+    wrong = {order: differs(want, mix(b"", named, 2, RATE, 2, order)) for order in WRONG["pan"]}
     off_vector = sum(1 for e in events if (2 * int(RATE * e[0])) % 8)
     panned = sum(1 for e in events if e[5] is not None)
     resampled = sum(1 for e in events if e[5] is not None and e[4] is not None and int(RATE * e[4]) != RATE)
@@ -108,7 +57,7 @@ def test_a_stereo_song_of_mono_instruments(gpu):
     assert all(n > 0 for n in wrong.values()), wrong
     assert off_vector > 0 and 0 < resampled < panned < len(events)
     assert {type(e[5]) for e in events} == {float, tuple, type(None)}
-    samples = [_sample(b, 2, RATE, 1 if i < 4 else 2) for i, b in enumerate(instruments)]
+    samples = [sample_of(b, 2, RATE, 1 if i < 4 else 2) for i, b in enumerate(instruments)]
     got = mixer.sequence([(s, samples[i], v, o, sp, p) for s, i, v, o, sp, p in events], RATE, 2, 2, name="panned")
     assert got.name == "panned" and (got.samplerate, got.nchannels, got.samplewidth) == (RATE, 2, 2)
     assert len(got) * 4 == len(want)
@@ -119,7 +68,7 @@ def test_a_stereo_song_of_mono_instruments(gpu):
 def test_the_same_bytes_as_the_loop_of_speed_stereo_at_volume_and_mix_at(gpu):
     from synthesizer_amd.sample import Sample
     instruments, events = panned_song(300, 3.0)
-    samples = [_sample(b, 2, RATE, 1 if i < 4 else 2) for i, b in enumerate(instruments)]
+    samples = [sample_of(b, 2, RATE, 1 if i < 4 else 2) for i, b in enumerate(instruments)]
     evs = []
     for k, (s, i, v, _o, sp, p) in enumerate(events):
         evs.append((s, samples[i], None if k % 5 == 0 else v, 0.03 if k % 7 == 0 else None, 1.0 if k % 13 == 0 else sp, p))
@@ -129,8 +78,8 @@ def test_the_same_bytes_as_the_loop_of_speed_stereo_at_volume_and_mix_at(gpu):
     assert any(e[2] is None for e in panned) and any(e[3] for e in panned) and any(e[0] == 0.0 for e in panned)
     assert any(e[4] is None for e in panned) and any(e[4] == 1.0 for e in panned) and any(e[4] not in (None, 1.0) and e[3] for e in panned)
     assert 0 < len(panned) < len(evs)
-    base = _pcm(np.random.default_rng(1), 2, 2 * RATE, 0.3)
-    loop = _sample(base, 2, RATE, 2)
+    base = pcm(np.random.default_rng(1), 2, 2 * RATE, 0.3)
+    loop = sample_of(base, 2, RATE, 2)
     for seconds, other, volume, other_seconds, speed, pan in evs:
         o = other
         if speed is not None:
@@ -140,10 +89,10 @@ def test_the_same_bytes_as_the_loop_of_speed_stereo_at_volume_and_mix_at(gpu):
         if volume is not None:
             o = o.at_volume(volume)
         loop.mix_at(seconds, o, other_seconds)
-    many = _sample(base, 2, RATE, 2).mix_at_many(evs)
+    many = sample_of(base, 2, RATE, 2).mix_at_many(evs)
     assert isinstance(many, Sample) and len(many) == len(loop) > RATE and many.nchannels == 2
     assert bytes(many.view_frame_data()) == bytes(loop.view_frame_data())
-    want = oracle(base, [(s, instruments[samples.index(o)], v, os_, sp, p) for s, o, v, os_, sp, p in evs], 2, RATE)
+    want = mix(base, [(s, instruments[samples.index(o)], v, os_, sp, p) for s, o, v, os_, sp, p in evs], 2, RATE, 2)
     assert bytes(many.view_frame_data()) == want
     for i, (b, smp) in enumerate(zip(instruments, samples)):
         assert bytes(smp.view_frame_data()) == b and smp.nchannels == (1 if i < 4 else 2)       # the instruments are untouched
@@ -159,9 +108,9 @@ def _every_offset(width, rate, seed):
     rng = np.random.default_rng(seed)
     tile = 2048 if width == 2 else 1024                     # track samples; half as many stereo frames
     lengths = [1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 64, 100, tile // 2 - 1, tile // 2, tile // 2 + 1, tile - 1, tile, tile + 1, 3 * tile + 5]
-    sources = [_pcm(rng, width, n, 0.4) for n in lengths] + [_pcm(rng, width, 2 * n, 0.4) for n in (5, 300, tile + 3)]    # the last three: stereo
+    sources = [pcm(rng, width, n, 0.4) for n in lengths] + [pcm(rng, width, 2 * n, 0.4) for n in (5, 300, tile + 3)]    # the last three: stereo
     track_frames = 6 * tile
-    base = _pcm(rng, width, 2 * track_frames, 0.4)
+    base = pcm(rng, width, 2 * track_frames, 0.4)
     events = []
     for k in range(735):
         i = k % len(lengths) if k % 6 else len(lengths) + (k // 6) % 3
@@ -186,9 +135,9 @@ def _every_offset(width, rate, seed):
 def test_widths_speeds_volumes_factors_and_every_offset(gpu, width):
     rate = 8192                                        # (a power of two: seconds = frame / rate is exact)
     sources, nmono, base, events = _every_offset(width, rate, 300 + width)
-    want = oracle(base, [(s, sources[i], v, o, sp, p) for s, i, v, o, sp, p in events], width, rate)
-    samples = [_sample(b, width, rate, 1 if i < nmono else 2) for i, b in enumerate(sources)]
-    got = _sample(base, width, rate, 2).mix_at_many([(s, samples[i], v, o, sp, p) for s, i, v, o, sp, p in events])
+    want = mix(base, [(s, sources[i], v, o, sp, p) for s, i, v, o, sp, p in events], width, rate, 2)
+    samples = [sample_of(b, width, rate, 1 if i < nmono else 2) for i, b in enumerate(sources)]
+    got = sample_of(base, width, rate, 2).mix_at_many([(s, samples[i], v, o, sp, p) for s, i, v, o, sp, p in events])
     assert len(got) * width * 2 == len(want) > len(base)
     assert bytes(got.view_frame_data()) == want
 
@@ -198,33 +147,19 @@ def test_a_reduced_outrate_of_65536_or_more_at_16_bits(gpu):
     """96 kHz against int(96000 * speed) coprime to it: the float64 route of the 16-bit kernel on panned events, beside the integer one"""
     rate = 96000
     rng = np.random.default_rng(78)
-    sources = [_pcm(rng, 2, n, 1.0) for n in (1, 9, 700, 5000)]
-    base = _pcm(rng, 2, 2 * 30000, 0.5)
+    sources = [pcm(rng, 2, n, 1.0) for n in (1, 9, 700, 5000)]
+    base = pcm(rng, 2, 2 * 30000, 0.5)
     speeds = [2 ** (7 / 12), 0.5, 0.999999, None, 1.00002, 2 ** (-7 / 12)]
     assert sum(1 for sp in speeds if sp and rate // gcd(int(rate * sp), rate) >= 65536) >= 3
     assert any(sp and int(rate * sp) != rate and rate // gcd(int(rate * sp), rate) < 65536 for sp in speeds)
     events = [(int(rng.integers(0, 28000)) / rate, k % 4, [None, 0.7, -1.3][k % 3], None, speeds[k % 6], PANS[k % len(PANS)]) for k in range(96)]
-    want = oracle(base, [(s, sources[i], v, o, sp, p) for s, i, v, o, sp, p in events], 2, rate)
-    samples = [_sample(b, 2, rate, 1) for b in sources]
-    got = _sample(base, 2, rate, 2).mix_at_many([(s, samples[i], v, o, sp, p) for s, i, v, o, sp, p in events])
+    want = mix(base, [(s, sources[i], v, o, sp, p) for s, i, v, o, sp, p in events], 2, rate, 2)
+    samples = [sample_of(b, 2, rate, 1) for b in sources]
+    got = sample_of(base, 2, rate, 2).mix_at_many([(s, samples[i], v, o, sp, p) for s, i, v, o, sp, p in events])
     assert bytes(got.view_frame_data()) == want
 
 
 # ---- 5: the C entry point --------------------------------------------------------------------------------------------------------------
-def _table(N, rows):
-    """rows: (dst_sample, src_sample, nsamples, src_frames, factor, left, right, src, inrate, outrate, src_channels[, reserved])"""
-    t = np.zeros(len(rows), dtype=N.MIX_EVENT_PAN_DTYPE)
-    for k, r in enumerate(rows):
-        t[k] = tuple(r) + (0,) * (12 - len(r))
-    return t
-
-
-def _mix_events_pan(N, srcs, table, width, track, track_samples):
-    arr = (C.c_void_p * max(1, len(srcs)))(*[b.handle for b in srcs])
-    return N.lib().sh_mix_events_pan(arr, len(srcs), table.ctypes.data if len(table) else None, len(table), width,
-                                       track.handle if track is not None else None, track_samples)
-
-
 @pytest.mark.parametrize("width", [1, 2, 3, 4])
 def test_the_entry_point_with_sub_ranges_of_sources(gpu, width):
     """src_sample != 0, sources that are views into one buffer off the 16-byte grid, mono and stereo, plain and resampled rows in one
@@ -232,8 +167,8 @@ def test_the_entry_point_with_sub_ranges_of_sources(gpu, width):
     N = gpu
     rng = np.random.default_rng(240 + width)
     nsrc_samples, ntrack, outrate = 9000, 30000, 44100
-    src = _pcm(rng, width, nsrc_samples, 0.5)
-    base = _pcm(rng, width, ntrack, 0.5)
+    src = pcm(rng, width, nsrc_samples, 0.5)
+    base = pcm(rng, width, ntrack, 0.5)
     whole = N.DeviceBuffer.from_bytes(src)
     view = whole.view(6 * width, (nsrc_samples - 6) * width)          # a source whose device memory starts off the 16-byte grid
     inrates = [outrate, 22050, 44099, 48000, 4410, 441000, 62366]
@@ -271,14 +206,14 @@ def test_the_entry_point_with_sub_ranges_of_sources(gpu, width):
     for nch in (1, 2):
         assert any(r[8] == r[9] and r[10] == nch and r[1] and r[7] for r in rows) and any(r[8] != r[9] and r[10] == nch and r[1] and r[7] for r in rows)
     track = N.DeviceBuffer.from_bytes(base)
-    assert _mix_events_pan(N, [whole, view], _table(N, rows), width, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
+    assert mix_events(N, "pan", [whole, view], event_table(N, "pan", rows), None, width, None, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
     assert track.download_bytes(len(base)) == bytes(want)
 
 
 def test_the_entry_point_refuses_on_the_host(gpu):
     N = gpu
     rng = np.random.default_rng(26)
-    src, base = _pcm(rng, 2, 1000), _pcm(rng, 2, 5000)
+    src, base = pcm(rng, 2, 1000), pcm(rng, 2, 5000)
     s, t = N.DeviceBuffer.from_bytes(src), N.DeviceBuffer.from_bytes(base)
     nan, inf = float("nan"), float("inf")
     ok = (100, 0, 1000, 500, 0.5, 0.3, 0.7, 0, 22050, 44100, 1)        # 500 mono frames at half speed: 999 frames, 500 of them taken
@@ -320,22 +255,22 @@ def test_the_entry_point_refuses_on_the_host(gpu):
         "odd nsamples, plain": [ok2, (0, 0, 11, 0, 1.0, 1.0, 1.0, 0, 44100, 44100, 1)],
     }
     for what, rows in bad.items():
-        assert _mix_events_pan(N, [s], _table(N, rows), 2, t, 5000) == N.SH_ERR_INVALID, what
+        assert mix_events(N, "pan", [s], event_table(N, "pan", rows), None, 2, None, t, 5000) == N.SH_ERR_INVALID, what
         assert N.lib().sh_last_error().startswith(b"sh_mix_events_pan"), what
     for width in (0, 5, -2):
-        assert _mix_events_pan(N, [s], _table(N, [ok]), width, t, 5000) == N.SH_ERR_INVALID
-    assert _mix_events_pan(N, [s, t], _table(N, [ok]), 2, t, 5000) == N.SH_ERR_INVALID             # a source that is the track
-    assert _mix_events_pan(N, [t.view(200, 400)], _table(N, [(0, 0, 10, 5, 1.0, 1.0, 1.0, 0, 22050, 44100, 1)]), 2, t, 5000) == N.SH_ERR_INVALID
-    assert _mix_events_pan(N, [s], _table(N, [ok]), 2, t, 5001) == N.SH_ERR_INVALID                # the track range outside its buffer
-    assert _mix_events_pan(N, [s], _table(N, [ok]), 2, None, 0) == N.SH_ERR_INVALID
+        assert mix_events(N, "pan", [s], event_table(N, "pan", [ok]), None, width, None, t, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "pan", [s, t], event_table(N, "pan", [ok]), None, 2, None, t, 5000) == N.SH_ERR_INVALID             # a source that is the track
+    assert mix_events(N, "pan", [t.view(200, 400)], event_table(N, "pan", [(0, 0, 10, 5, 1.0, 1.0, 1.0, 0, 22050, 44100, 1)]), None, 2, None, t, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "pan", [s], event_table(N, "pan", [ok]), None, 2, None, t, 5001) == N.SH_ERR_INVALID                # the track range outside its buffer
+    assert mix_events(N, "pan", [s], event_table(N, "pan", [ok]), None, 2, None, None, 0) == N.SH_ERR_INVALID
     assert t.download_bytes(len(base)) == base                                                       # nothing was launched
-    assert _mix_events_pan(N, [s], _table(N, []), 2, t, 5000) == N.SH_OK
+    assert mix_events(N, "pan", [s], event_table(N, "pan", []), None, 2, None, t, 5000) == N.SH_OK
     empty_ends = [(5000, 1000, 0, 0, 1.0, 1.0, 1.0, 0, 22050, 44100, 1), (5000, 1000, 0, 0, 1.0, 1.0, 1.0, 0, 44100, 44100, 2), (0, 0, 0, 0, 1.0, 0.5, 0.5, 0, 44100, 44100, 1)]
-    assert _mix_events_pan(N, [s], _table(N, empty_ends), 2, t, 5000) == N.SH_OK                   # empty ranges at the very ends
+    assert mix_events(N, "pan", [s], event_table(N, "pan", empty_ends), None, 2, None, t, 5000) == N.SH_OK                   # empty ranges at the very ends
     assert t.download_bytes(len(base)) == base
     # exactly what 5 mono frames yield (9 frames = 18 track samples), a stereo row with NaN for the factors it ignores, a plain mono row
     rows = [ok, (18, 0, 18, 5, 1.0, -1.0, 2.0, 0, 22050, 44100, 1), ok2, (4000, 500, 1000, 0, 1.0, 1.0, 0.0, 0, 44100, 44100, 1)]
-    assert _mix_events_pan(N, [s], _table(N, rows), 2, t, 5000) == N.SH_OK, N.lib().sh_last_error()
+    assert mix_events(N, "pan", [s], event_table(N, "pan", rows), None, 2, None, t, 5000) == N.SH_OK, N.lib().sh_last_error()
     want = bytearray(base)
     want[200:2200] = audioop.add(base[200:2200], audioop.mul(audioop.tostereo(audioop.ratecv(src, 2, 1, 22050, 44100, None)[0][:1000], 2, 0.3, 0.7), 2, 0.5), 2)
     want[36:72] = audioop.add(bytes(want[36:72]), audioop.tostereo(audioop.ratecv(src[:10], 2, 1, 22050, 44100, None)[0], 2, -1.0, 2.0), 2)
@@ -348,54 +283,54 @@ def test_the_entry_point_refuses_on_the_host(gpu):
 def test_in_place_and_the_refusals_of_mix_at_many(gpu):
     rate = 8192
     rng = np.random.default_rng(6)
-    a, b, c = _pcm(rng, 2, 2 * 8192, 0.6), _pcm(rng, 2, 3000, 0.6), _pcm(rng, 2, 500, 0.6)
-    B, Cc = (_sample(x, 2, rate, 1) for x in (b, c))
+    a, b, c = pcm(rng, 2, 2 * 8192, 0.6), pcm(rng, 2, 3000, 0.6), pcm(rng, 2, 500, 0.6)
+    B, Cc = (sample_of(x, 2, rate, 1) for x in (b, c))
     # growth: a slowed-down sample runs beyond the end, another starts beyond it
     evs = [(0.9, B, None, None, 0.5, 0.5), (0.5, Cc, 0.5, None, 2.0, (0.0, 1.0)), (3.0, Cc, None, None, None, -1.0)]
-    t = _sample(a, 2, rate, 2).mix_at_many(evs)
-    want = oracle(a, [(0.9, b, None, None, 0.5, 0.5), (0.5, c, 0.5, None, 2.0, (0.0, 1.0)), (3.0, c, None, None, None, -1.0)], 2, rate)
+    t = sample_of(a, 2, rate, 2).mix_at_many(evs)
+    want = mix(a, [(0.9, b, None, None, 0.5, 0.5), (0.5, c, 0.5, None, 2.0, (0.0, 1.0)), (3.0, c, None, None, None, -1.0)], 2, rate, 2)
     assert len(want) > 4 * 3 * 8192 and len(t) * 4 == len(want) and bytes(t.view_frame_data()) == want
     # no growth: in place, the same device buffer object before and after; the sources untouched
-    t = _sample(a, 2, rate, 2).to_device()
+    t = sample_of(a, 2, rate, 2).to_device()
     dev = t._device()
     evs = [(0.25, B, None, None, 1.5, 0.1), (0.0, Cc, -1.0, None, None, (1.0, 0.0)), (0.9, Cc, None, 0.01, 0.5, (1.2, -0.3))]
     t.mix_at_many(evs)
     assert t._device() is dev
-    assert bytes(t.view_frame_data()) == oracle(a, [(0.25, b, None, None, 1.5, 0.1), (0.0, c, -1.0, None, None, (1.0, 0.0)),
-                                                   (0.9, c, None, 0.01, 0.5, (1.2, -0.3))], 2, rate)
+    assert bytes(t.view_frame_data()) == mix(a, [(0.25, b, None, None, 1.5, 0.1), (0.0, c, -1.0, None, None, (1.0, 0.0)),
+                                                   (0.9, c, None, 0.01, 0.5, (1.2, -0.3))], 2, rate, 2)
     assert bytes(B.view_frame_data()) == b and bytes(Cc.view_frame_data()) == c and B.nchannels == Cc.nchannels == 1
     # the refusals: ValueError, and nothing mixed before the error
-    S = _sample(a[:400], 2, rate, 2)
-    t = _sample(a, 2, rate, 2)
+    S = sample_of(a[:400], 2, rate, 2)
+    t = sample_of(a, 2, rate, 2)
     for bad in ((0.2, S, None, None, None, 0.5), (0.2, t, None, None, None, 0.5), (0.2, B, None, None, None, 1.5), (0.2, B, None, None, None, -1.01),
                 (0.2, B, None, None, None, float("nan")), (0.2, B, None, None, None, (1.0, float("inf"))), (0.2, B, None, None, None, (float("nan"), 0.0)),
                 (0.2, B, None, None, None, (1.0,)), (0.2, B, None, None, None, (1.0, 0.5, 0.5)), (0.2, B, None, None, None, ())):
         with pytest.raises(ValueError, match="mix_at_many"):
             t.mix_at_many([(0.1, B, None, None, 0.5, 0.0), bad])
     with pytest.raises(ValueError, match="mix_at_many"):
-        _sample(b, 2, rate, 1).mix_at_many([(0.1, Cc, None, None, None, 0.0)])      # a track that is not stereo
+        sample_of(b, 2, rate, 1).mix_at_many([(0.1, Cc, None, None, None, 0.0)])      # a track that is not stereo
     with pytest.raises(AssertionError):
         t.mix_at_many([(0.1, B, None, None, 0.5, 0.0), (0.2, B)])                   # a mono sample without a pan: mix_at's assertion, as before
     assert bytes(t.view_frame_data()) == a and len(t) == 8192
     with pytest.raises(RuntimeError):
-        _sample(a, 2, rate, 2).lock().mix_at_many([(0.1, B, None, None, 0.5, 0.0)])
-    got = _sample(a, 2, rate, 2).mix_at_many([(0.1, B.lock(), 0.5, None, 0.5, -0.25)])     # a locked SOURCE is only read
-    assert bytes(got.view_frame_data()) == oracle(a, [(0.1, b, 0.5, None, 0.5, -0.25)], 2, rate)
+        sample_of(a, 2, rate, 2).lock().mix_at_many([(0.1, B, None, None, 0.5, 0.0)])
+    got = sample_of(a, 2, rate, 2).mix_at_many([(0.1, B.lock(), 0.5, None, 0.5, -0.25)])     # a locked SOURCE is only read
+    assert bytes(got.view_frame_data()) == mix(a, [(0.1, b, 0.5, None, 0.5, -0.25)], 2, rate, 2)
     assert bytes(B.view_frame_data()) == b
     # `other is self` cuts the list as before; the panned events on both sides of it are batches of their own
-    t = _sample(a, 2, rate, 2)
+    t = sample_of(a, 2, rate, 2)
     t.mix_at_many([(0.1, B, 0.9, None, 1.25, 0.3), (0.05, t, 0.5, 0.2, 0.8), (0.3, Cc, None, None, None, (0.0, 1.0))])
-    mid = oracle(a, [(0.1, b, 0.9, None, 1.25, 0.3)], 2, rate)
-    mid = oracle(mid, [(0.05, mid, 0.5, 0.2, 0.8, None)], 2, rate)
-    assert bytes(t.view_frame_data()) == oracle(mid, [(0.3, c, None, None, None, (0.0, 1.0))], 2, rate)
+    mid = mix(a, [(0.1, b, 0.9, None, 1.25, 0.3)], 2, rate, 2)
+    mid = mix(mid, [(0.05, mid, 0.5, 0.2, 0.8, None)], 2, rate, 2)
+    assert bytes(t.view_frame_data()) == mix(mid, [(0.3, c, None, None, None, (0.0, 1.0))], 2, rate, 2)
 
 
 def test_a_second_call_with_the_same_shapes_allocates_nothing(gpu):
     N = gpu
     instruments, events = panned_song(400, 2.0)
-    samples = [_sample(b, 2, RATE, 1 if i < 4 else 2).to_device() for i, b in enumerate(instruments)]
+    samples = [sample_of(b, 2, RATE, 1 if i < 4 else 2).to_device() for i, b in enumerate(instruments)]
     evs = [(s, samples[i], v, o, sp, p) for s, i, v, o, sp, p in events]
-    track = _sample(bytes(4 * RATE * 3), 2, RATE, 2).to_device()
+    track = sample_of(bytes(4 * RATE * 3), 2, RATE, 2).to_device()
     dev = track._device()
     track.mix_at_many(evs)
     N.sync()
@@ -405,7 +340,7 @@ def test_a_second_call_with_the_same_shapes_allocates_nothing(gpu):
     assert after["device_allocs"] == before["device_allocs"] and after["device_frees"] == before["device_frees"]
     assert after["stream_syncs"] == before["stream_syncs"] and after["pool_hits"] == before["pool_hits"]
     assert track._device() is dev
-    want = oracle(bytes(4 * RATE * 3), [(s, instruments[i], v, o, sp, p) for s, i, v, o, sp, p in events] * 2, 2, RATE)
+    want = mix(bytes(4 * RATE * 3), [(s, instruments[i], v, o, sp, p) for s, i, v, o, sp, p in events] * 2, 2, RATE, 2)
     assert bytes(track.view_frame_data()) == want
 
 
@@ -413,12 +348,6 @@ def test_a_second_call_with_the_same_shapes_allocates_nothing(gpu):
 def test_both_alignment_schemes_give_the_same_bytes():
     """SYNTHHIP_SEQ_ALIGN is read once per process (sh_init): the song, the 16-bit route tests, every offset and the sub-ranges of sources
     again under the scheme that is not the default."""
-    import os
-    import subprocess
-    import sys
-    from pathlib import Path
-    from tests.test_gpu_sequence import OTHER_SCHEME, ROOT
-    env = dict(os.environ, SYNTHHIP_SEQ_ALIGN=OTHER_SCHEME)
-    p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider", str(Path(__file__).resolve()),
-                        "-k", "stereo_song or every_offset or sub_ranges or 65536"], cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0 and "10 passed" in p.stdout and "failed" not in p.stdout, p.stdout[-3000:] + p.stderr[-1000:]
+    in_a_child_under_the_other_alignment_scheme(__file__, ["test_a_stereo_song_of_mono_instruments", "test_a_reduced_outrate_of_65536_or_more_at_16_bits"] +
+                                                ["%s[%d]" % (t, w) for t in ("test_widths_speeds_volumes_factors_and_every_offset", "test_the_entry_point_with_sub_ranges_of_sources")
+                                                  for w in (1, 2, 3, 4)])

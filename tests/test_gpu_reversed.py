@@ -1,110 +1,31 @@
 """GPU parity of a region and of reversed playback per event in Sample.mix_at_many / mixer.sequence / sh_mix_events_rev -- slices of a
 recording, forwards or backwards, in one launch -- against live ``audioop`` on byte slices: the region cut as ``clip`` cuts it
 (``data[fb * int(rate * start):fb * int(rate * end)]``), ``audioop.reverse`` of the slice (the order of the SAMPLES), and then
-tests/test_gpu_looped.py's ``looped_source`` / ``oracle`` chain as it stands: the loop unrolled over the clipped, reversed frames, ``ratecv``,
+the rest of the chain of tests/seqref.py (source, mix) as it stands: the loop unrolled over the clipped, reversed frames, ``ratecv``,
 the cut, the envelope, ``tostereo``, ``mul``, the cut, ``add`` with saturation at every event, in list order.  Expected bytes never come
 from the product.  Rate 8192, sources of a few hundred frames, tracks of three tiles, as that file has them."""
 import audioop
-import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from tests.test_gpu_enveloped import _differs, shaped_source
-from tests.test_gpu_looped import LANE, LOOPS, RATE, SPEEDS, STARTS, TILE, _out_frames, looped_source, unroll
-from tests.test_gpu_sequence import OTHER_SCHEME, ROOT, _pcm, _sample
+from tests.seqcases import (LENGTHS, LOOPS, SPEEDS, STARTS, as_samples, event_table, in_a_child_under_the_other_alignment_scheme, mix_events, named,
+                            sample_of, spy, with_samples)
+from tests.seqref import LANE, TILE, differs, discriminates, mix, out_frames, pcm, unroll
 
 pytestmark = pytest.mark.gpu
 
-LENGTHS = [1, 7, 8, 9, 15, 16, 17, 65]                      # of a region
-RIGHT, UNREVERSED, REVERSE_AFTER_LOOP, REVERSE_AFTER_RATECV, REGION_AFTER_REVERSAL = \
-    "right", "not reversed", "reverse after the loop", "reverse after ratecv", "the region cut after the reversal"
-WRONG = (UNREVERSED, REVERSE_AFTER_LOOP, REVERSE_AFTER_RATECV, REGION_AFTER_REVERSAL)
-
-
-# ---- the oracle ------------------------------------------------------------------------------------------------------------------------
-def cut(data: bytes, width, snch, rate, region) -> bytes:
-    """other.copy().clip(region[0], other.duration if region[1] is None else region[1]): byte slicing"""
-    fb = width * snch
-    end = len(data) / rate / width / snch if region[1] is None else region[1]
-    assert end >= region[0]
-    return data[fb * int(rate * region[0]):fb * int(rate * end)]
-
-
-def played_source(data, width, rate, nch, volume, other_seconds, speed, pan, env, loop, region, reverse, order=RIGHT) -> bytes:
-    """what mix_at is handed for one event: the region and the reversal FIRST, then looped_source's chain -- or one of the wrong orders"""
-    snch = nch if pan is None else 1
-    if order == REGION_AFTER_REVERSAL and region is not None and reverse:
-        data = cut(audioop.reverse(data, width), width, snch, rate, region)
-        return looped_source(data, width, rate, nch, volume, other_seconds, speed, pan, env, loop)
-    if region is not None:
-        data = cut(data, width, snch, rate, region)
-    if not reverse or order == UNREVERSED:
-        return looped_source(data, width, rate, nch, volume, other_seconds, speed, pan, env, loop)
-    if order in (RIGHT, REGION_AFTER_REVERSAL):
-        return looped_source(audioop.reverse(data, width), width, rate, nch, volume, other_seconds, speed, pan, env, loop)
-    if loop is not None:
-        data = unroll(data, width, snch, rate, loop)
-    inrate = rate if speed is None else int(rate * speed)
-    if order == REVERSE_AFTER_RATECV and inrate != rate:
-        data = audioop.ratecv(data, width, snch, inrate, rate, None)[0]
-        speed = None
-    return shaped_source(audioop.reverse(data, width), width, rate, nch, volume, other_seconds, speed, pan, env)
-
-
-def oracle(track: bytes, events, width, rate, nch, order=RIGHT) -> bytes:
-    """events: (seconds, source bytes, volume, other_seconds, speed, pan, envelope, loop, region, reverse), one after another like mix_at"""
-    fb = width * nch
-    t = bytearray(track)
-    for seconds, data, volume, other_seconds, speed, pan, env, loop, region, reverse in events:
-        frames = played_source(data, width, rate, nch, volume, other_seconds, speed, pan, env, loop, region, reverse, order)
-        start = fb * int(rate * seconds)
-        end = start + len(frames)
-        if end > len(t):
-            t.extend(bytes(end - len(t)))
-        t[start:end] = audioop.add(bytes(t[start:end]), frames, width)
-    return bytes(t)
-
-
-def discriminates(want, events, width, nch, base=b""):
-    """the expected bytes differ from each wrong order's: on the CPU, with audioop alone, before the GPU is asked"""
-    differs = {}
-    for order in WRONG:
-        b = oracle(base, events, width, RATE, nch, order)
-        m = min(len(want), len(b))
-        differs[order] = _differs(want[:m], b[:m]) + abs(len(want) - len(b))
-    print("width %d: bytes of %d that differ from the wrong orders: %s" % (width, len(want), differs))
-    assert all(n > 0 for n in differs.values()), differs
+RATE = 8192
 
 
 # ---- 1: plain reversed events, through the entry point (track offsets count samples there) -------------------------------------------------
-def _rev_table(N, rows):
-    """rows: sh_mix_event_rev's fields in order, the tail may be left out"""
-    t = np.zeros(len(rows), dtype=N.MIX_EVENT_REV_DTYPE)
-    for k, r in enumerate(rows):
-        t[k] = tuple(r) + (0,) * (17 - len(r))
-    return t
-
-
-def _mix_events_rev(N, srcs, events, segments, width, nchannels, track, track_samples):
-    arr = (C.c_void_p * max(1, len(srcs)))(*[b.handle for b in srcs])
-    return N.lib().sh_mix_events_rev(arr, len(srcs), events.ctypes.data if len(events) else None, len(events),
-                                     segments.ctypes.data if segments is not None and len(segments) else None,
-                                     len(segments) if segments is not None else 0, width, nchannels,
-                                     track.handle if track is not None else None, track_samples)
-
-
 def plain_cases(width, nch):
     """(sources, rows as (dst_sample, source, first frame, frames, samples taken, factor)): every region length at every track offset
     0 .. 15, the starts, regions on the buffer's first and last sample and the factors in turn; then notes over three tiles"""
     rng = np.random.default_rng(20 * width + nch)
     tile = TILE[width]
     held = (300, 211, (tile + 700) // nch)                  # frames
-    sources = [_pcm(rng, width, nch * n, 0.5) for n in held]
+    sources = [pcm(rng, width, nch * n, 0.5) for n in held]
     rows = []
     k = 0
     lengths = LENGTHS if nch == 1 else LENGTHS + [(n + 1) // 2 for n in LENGTHS]      # stereo: that many frames, and that many samples' worth
@@ -151,7 +72,7 @@ def test_plain_reversed_events_at_every_offset(gpu, width, nch):
     sources, rows = plain_cases(width, nch)
     held = [len(b) // (width * nch) for b in sources]
     ntrack = 3 * tile - 6
-    base = _pcm(np.random.default_rng(width), width, ntrack, 0.3)
+    base = pcm(np.random.default_rng(width), width, ntrack, 0.3)
     # the list has the hard places
     for F in LENGTHS:
         assert {dst % 16 for dst, _i, _a, f, _n, _x in rows if f == F} == set(range(16))
@@ -167,26 +88,21 @@ def test_plain_reversed_events_at_every_offset(gpu, width, nch):
     assert want != plain_want(base, sources, rows, width, nch, reverse=False)             # what the parent mixes: the flag does something
     bufs = [N.DeviceBuffer.from_bytes(b) for b in sources]
     track = N.DeviceBuffer.from_bytes(base)
-    table = _rev_table(N, [(dst, a * nch, n, F, f, 0.0, 0.0, i, RATE, RATE, nch, 0, 0, 0, 0, 0, 1) for dst, i, a, F, n, f in rows])
-    assert _mix_events_rev(N, bufs, table, None, width, nch, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
+    table = event_table(N, "rev", [(dst, a * nch, n, F, f, 0.0, 0.0, i, RATE, RATE, nch, 0, 0, 0, 0, 0, 1) for dst, i, a, F, n, f in rows])
+    assert mix_events(N, "rev", bufs, table, None, width, nch, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
     got = track.download_bytes(len(base))
-    assert got == want, "%d bytes differ" % _differs(got, want)
+    assert got == want, "%d bytes differ" % differs(got, want)
     # and the same rows without the flag are rows of sh_mix_events_loop: the region forwards
     track = N.DeviceBuffer.from_bytes(base)
     table["flags"] = 0
-    assert _mix_events_rev(N, bufs, table, None, width, nch, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
+    assert mix_events(N, "rev", bufs, table, None, width, nch, track, ntrack) == N.SH_OK, N.lib().sh_last_error()
     assert track.download_bytes(len(base)) == plain_want(base, sources, rows, width, nch, reverse=False)
 
 
 def test_reversed_events_under_the_other_alignment_scheme(gpu):
     """SYNTHHIP_SEQ_ALIGN is read once per process (sh_init): the 16-bit cases again in a child under the scheme that is not the default"""
-    env = dict(os.environ, SYNTHHIP_SEQ_ALIGN=OTHER_SCHEME)
-    me = str(Path(__file__).resolve())
-    p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider",
-                        me + "::test_plain_reversed_events_at_every_offset[2-1]", me + "::test_plain_reversed_events_at_every_offset[2-2]",
-                        me + "::test_reversed_crossed_with_the_rest_of_the_chain[2]"],
-                       cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "3 passed" in p.stdout and "failed" not in p.stdout, p.stdout[-3000:] + p.stderr[-1000:]
+    in_a_child_under_the_other_alignment_scheme(__file__, ["test_plain_reversed_events_at_every_offset[2-1]", "test_plain_reversed_events_at_every_offset[2-2]",
+                                                           "test_reversed_crossed_with_the_rest_of_the_chain[2]"])
 
 
 # ---- 2: crossed with the rest, through Sample.mix_at_many ---------------------------------------------------------------------------------
@@ -205,9 +121,9 @@ def notes(width, nch=2, seed=0, scale=0.6, loud=False):
         return _CACHE[key]
     rng = np.random.default_rng(2000 * seed + 10 * width + nch)
     track_frames = 3 * TILE[width] // nch
-    instruments = [(_pcm(rng, width, n, scale), 1) for n in HELD]
+    instruments = [(pcm(rng, width, n, scale), 1) for n in HELD]
     if nch == 2:
-        instruments += [(_pcm(rng, width, 2 * n, scale), 2) for n in HELD]
+        instruments += [(pcm(rng, width, 2 * n, scale), 2) for n in HELD]
     events = []
     for k in range(98):
         speed = SPEEDS[k % 7]
@@ -231,7 +147,7 @@ def notes(width, nch=2, seed=0, scale=0.6, loud=False):
             V = max(2, (150 + (37 * k) % 600) * inrate // RATE)
             loop = (S / RATE, (S + L) / RATE, V / RATE)
             R = V
-        out = _out_frames(R, inrate, RATE)
+        out = out_frames(R, inrate, RATE)
         pan = [0.3, (1.0, 0.0), -0.65, (1.5, 1.2)][k % 4] if (k & 1) and nch == 2 else None
         env = None
         if (k & 2) and width != 3:
@@ -244,31 +160,6 @@ def notes(width, nch=2, seed=0, scale=0.6, loud=False):
         events.append((frame / RATE, i + (3 if nch == 2 and pan is None else 0), volume, other_seconds, speed, pan, env, loop, region, reverse))
     _CACHE[key] = (instruments, events)
     return _CACHE[key]
-
-
-def named(instruments, events):
-    return [(e[0], instruments[e[1]][0]) + tuple(e[2:]) for e in events]
-
-
-def with_samples(samples, events):
-    return [(e[0], samples[e[1]]) + tuple(e[2:]) for e in events]
-
-
-def as_samples(instruments, width, rate=RATE):
-    return [_sample(b, width, rate, c) for b, c in instruments]
-
-
-def _spy(N, monkeypatch):
-    calls = []
-    real = N.lib()
-
-    class Spy:
-        def __getattr__(self, name):
-            if name.startswith("sh_mix_events"):
-                calls.append(name)
-            return getattr(real, name)
-    monkeypatch.setattr(N, "lib", lambda: Spy())
-    return calls
 
 
 @pytest.mark.parametrize("width", [1, 2, 3, 4])
@@ -284,15 +175,15 @@ def test_reversed_crossed_with_the_rest_of_the_chain(gpu, width):
     assert any(e[8] is not None and e[8][1] is None for e in turned)
     if width == 3:
         assert any(e[7] is not None for e in turned)                                                  # 24-bit, reversed and looped
-    want = oracle(b"", named(instruments, events), width, RATE, 2)
+    want = mix(b"", named(instruments, events), width, RATE, 2)
     assert 2 * TILE[width] * width < len(want) <= 3 * TILE[width] * width
     # on the parent the ninth and tenth element do nothing: other bytes
-    assert want != oracle(b"", [e[:8] + (None, None) for e in named(instruments, events)], width, RATE, 2)
-    discriminates(want, named(instruments, events), width, 2)
-    samples = as_samples(instruments, width)
+    assert want != mix(b"", [e[:8] + (None, None) for e in named(instruments, events)], width, RATE, 2)
+    discriminates(want, named(instruments, events), width, RATE, 2, "rev")
+    samples = as_samples(instruments, width, RATE)
     got = mixer.sequence(with_samples(samples, events), RATE, 2, width, name="turned")
     assert got.name == "turned" and len(got) * 2 * width == len(want)
-    assert bytes(got.view_frame_data()) == want, "%d bytes differ" % _differs(bytes(got.view_frame_data()), want)
+    assert bytes(got.view_frame_data()) == want, "%d bytes differ" % differs(bytes(got.view_frame_data()), want)
     for (b, c), smp in zip(instruments, samples):
         assert bytes(smp.view_frame_data()) == b and smp.nchannels == c                 # the instruments are untouched
 
@@ -301,10 +192,10 @@ def test_reversed_crossed_with_the_rest_of_the_chain(gpu, width):
 def test_reversed_into_a_track_that_holds_something(gpu, nch, monkeypatch):
     N = gpu
     instruments, events = notes(2, nch)
-    base = _pcm(np.random.default_rng(5), 2, 3 * TILE[2], 0.3)
-    want = oracle(base, named(instruments, events), 2, RATE, nch)
-    calls = _spy(N, monkeypatch)
-    got = _sample(base, 2, RATE, nch).mix_at_many(with_samples(as_samples(instruments, 2), events))
+    base = pcm(np.random.default_rng(5), 2, 3 * TILE[2], 0.3)
+    want = mix(base, named(instruments, events), 2, RATE, nch)
+    calls = spy(N, monkeypatch)
+    got = sample_of(base, 2, RATE, nch).mix_at_many(with_samples(as_samples(instruments, 2, RATE), events))
     assert calls == ["sh_mix_events_rev"]                                                # one launch
     assert bytes(got.view_frame_data()) == want
 
@@ -316,22 +207,22 @@ def test_a_reversed_stereo_sample_comes_backwards_with_left_and_right_swapped(gp
     channels in the other order.  Stated on the frames themselves, with numpy, and held against audioop and the product."""
     rng = np.random.default_rng(60 + width)
     F, a, b = 200, 30, 171
-    data = _pcm(rng, width, 2 * F, 0.9)
+    data = pcm(rng, width, 2 * F, 0.9)
     frames = np.frombuffer(data, dtype=np.uint8).reshape(F, 2, width)                    # frame, channel, byte
     swapped = frames[a:b][::-1, ::-1, :].tobytes()                                       # frames backwards AND left <-> right
     framewise = frames[a:b][::-1, :, :].tobytes()                                        # what a frame-wise reversal would be
     assert swapped == audioop.reverse(data[a * 2 * width:b * 2 * width], width) != framewise
-    event = (8 / RATE, _sample(data, width, RATE, 2), None, None, None, None, None, None, (a / RATE, b / RATE), True)
-    got = bytes(_sample(b"", width, RATE, 2).mix_at_many([event]).view_frame_data())
+    event = (8 / RATE, sample_of(data, width, RATE, 2), None, None, None, None, None, None, (a / RATE, b / RATE), True)
+    got = bytes(sample_of(b"", width, RATE, 2).mix_at_many([event]).view_frame_data())
     assert got == bytes(8 * 2 * width) + swapped
     left_in = frames[a:b, 0, :].tobytes()
     got_frames = np.frombuffer(got, dtype=np.uint8).reshape(-1, 2, width)[8:]
     assert got_frames[::-1, 1, :].tobytes() == left_in                                   # the source's left channel plays on the right
     # a mono sample panned: nothing to swap, the frames come backwards
-    mono = _pcm(rng, width, F, 0.9)
+    mono = pcm(rng, width, F, 0.9)
     m = np.frombuffer(mono, dtype=np.uint8).reshape(F, width)
     want = audioop.tostereo(m[a:b][::-1].tobytes(), width, 1.0, 0.0)
-    got = _sample(b"", width, RATE, 2).mix_at_many([(0.0, _sample(mono, width, RATE, 1), None, None, None, (1.0, 0.0), None, None, (a / RATE, b / RATE), True)])
+    got = sample_of(b"", width, RATE, 2).mix_at_many([(0.0, sample_of(mono, width, RATE, 1), None, None, None, (1.0, 0.0), None, None, (a / RATE, b / RATE), True)])
     assert bytes(got.view_frame_data()) == want
 
 
@@ -340,7 +231,7 @@ def test_a_reversed_stereo_sample_comes_backwards_with_left_and_right_swapped(gp
 def test_a_region_forwards_goes_to_the_entry_point_of_its_level(gpu, width, monkeypatch):
     N = gpu
     rng = np.random.default_rng(70 + width)
-    mono, stereo = _pcm(rng, width, 300, 0.6), _pcm(rng, width, 2 * 211, 0.6)
+    mono, stereo = pcm(rng, width, 300, 0.6), pcm(rng, width, 2 * 211, 0.6)
     env = (0.002, 0.003, 0.5, 0.004, 0.02) if width != 3 else None
     region, tail = (5 / RATE, 190 / RATE), (100 / RATE, None)
     tiers = [
@@ -351,28 +242,27 @@ def test_a_region_forwards_goes_to_the_entry_point_of_its_level(gpu, width, monk
         ("sh_mix_events_loop", [(0.01, 0, 0.5, None, 0.999, 0.3, env, (0.01, 0.5, 0.09), region, None), (0.1, 1, None, None, None, None, None, None, tail, None)]),
     ]
     instruments = [(mono, 1), (stereo, 2)]
-    calls = _spy(N, monkeypatch)
+    calls = spy(N, monkeypatch)
     for entry, events in tiers:
         if width == 3 and entry == "sh_mix_events_env":
             continue                                        # (no envelope at 24 bits: the list would be the pan level's again)
         del calls[:]
-        want = oracle(b"", named(instruments, events), width, RATE, 2)
-        assert want != oracle(b"", [e[:8] + (None, None) for e in named(instruments, events)], width, RATE, 2)
-        got = _sample(b"", width, RATE, 2).mix_at_many(with_samples(as_samples(instruments, width), events))
+        want = mix(b"", named(instruments, events), width, RATE, 2)
+        assert want != mix(b"", [e[:8] + (None, None) for e in named(instruments, events)], width, RATE, 2)
+        got = sample_of(b"", width, RATE, 2).mix_at_many(with_samples(as_samples(instruments, width, RATE), events))
         assert calls == [entry]
         assert bytes(got.view_frame_data()) == want, entry
     # an empty region: nothing is mixed, the track grows to the event's start
     del calls[:]
-    got = _sample(b"", width, RATE, 2).mix_at_many([(0.01, _sample(stereo, width, RATE, 2), None, None, None, None, None, None, (0.5, 0.6), True)])
+    got = sample_of(b"", width, RATE, 2).mix_at_many([(0.01, sample_of(stereo, width, RATE, 2), None, None, None, None, None, None, (0.5, 0.6), True)])
     assert bytes(got.view_frame_data()) == bytes(2 * width * int(RATE * 0.01))
 
 
 # ---- 5: the order ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("width", [1, 2, 3, 4])
-def test_the_oracle_tells_the_right_order_from_each_wrong_one(gpu, width):
+def order_notes(width):
     """every event has a region, a reversal, a loop and a speed, so that every wrong order can be formed for every event"""
     rng = np.random.default_rng(80 + width)
-    instruments = [(_pcm(rng, width, 400, 0.6), 1), (_pcm(rng, width, 2 * 300, 0.6), 2)]
+    instruments = [(pcm(rng, width, 400, 0.6), 1), (pcm(rng, width, 2 * 300, 0.6), 2)]
     events = []
     for k in range(24):
         i = k % 2
@@ -380,9 +270,15 @@ def test_the_oracle_tells_the_right_order_from_each_wrong_one(gpu, width):
         S, L = [40, 41, 45][k % 3], LOOPS[2 + k % 5]
         events.append((int(rng.integers(0, 900)) / RATE, i, [None, 0.7][k % 2], None, speed, 0.3 if i == 0 else None, None,
                        (S / RATE, (S + L) / RATE, (300 + 11 * k) / RATE), ((3 + k) / RATE, (250 - 2 * k) / RATE), True))
-    want = oracle(b"", named(instruments, events), width, RATE, 2)
-    discriminates(want, named(instruments, events), width, 2)
-    got = _sample(b"", width, RATE, 2).mix_at_many(with_samples(as_samples(instruments, width), events))
+    return instruments, events
+
+
+@pytest.mark.parametrize("width", [1, 2, 3, 4])
+def test_the_oracle_tells_the_right_order_from_each_wrong_one(gpu, width):
+    instruments, events = order_notes(width)
+    want = mix(b"", named(instruments, events), width, RATE, 2)
+    discriminates(want, named(instruments, events), width, RATE, 2, "rev")
+    got = sample_of(b"", width, RATE, 2).mix_at_many(with_samples(as_samples(instruments, width, RATE), events))
     assert bytes(got.view_frame_data()) == want
 
 
@@ -390,8 +286,8 @@ def test_the_oracle_tells_the_right_order_from_each_wrong_one(gpu, width):
 @pytest.mark.parametrize("width", [1, 2, 3, 4])
 def test_loud_reversed_events_saturate_in_list_order(gpu, width):
     instruments, events = notes(width, 2, seed=4, scale=1.0, loud=True)
-    want = oracle(b"", named(instruments, events), width, RATE, 2)
-    back = oracle(b"", named(instruments, events[::-1]), width, RATE, 2)
+    want = mix(b"", named(instruments, events), width, RATE, 2)
+    back = mix(b"", named(instruments, events[::-1]), width, RATE, 2)
     if width == 3:
         v = np.frombuffer(want, dtype=np.uint8).reshape(-1, 3)
         assert (v == (255, 255, 127)).all(axis=1).any() and (v == (0, 0, 128)).all(axis=1).any()
@@ -399,11 +295,11 @@ def test_loud_reversed_events_saturate_in_list_order(gpu, width):
         v = np.frombuffer(want, dtype={1: np.int8, 2: "<i2", 4: "<i4"}[width])
         hi = 2 ** (8 * width - 1) - 1
         assert (v == hi).any() and (v == -hi - 1).any()
-    assert len(back) == len(want) and _differs(want, back) > 0                           # saturating at every event: the order matters
-    samples = as_samples(instruments, width)
-    got = _sample(b"", width, RATE, 2).mix_at_many(with_samples(samples, events))
+    assert len(back) == len(want) and differs(want, back) > 0                           # saturating at every event: the order matters
+    samples = as_samples(instruments, width, RATE)
+    got = sample_of(b"", width, RATE, 2).mix_at_many(with_samples(samples, events))
     assert bytes(got.view_frame_data()) == want
-    got = _sample(b"", width, RATE, 2).mix_at_many(with_samples(samples, events[::-1]))
+    got = sample_of(b"", width, RATE, 2).mix_at_many(with_samples(samples, events[::-1]))
     assert bytes(got.view_frame_data()) == back
 
 
@@ -412,9 +308,9 @@ def test_loud_reversed_events_saturate_in_list_order(gpu, width):
 def test_the_same_bytes_as_the_documented_loop_of_sample_calls(gpu, width, nch):
     instruments, events = notes(width, nch)
     events = events[:21:2] + events[49::3]
-    samples = as_samples(instruments, width)
-    base = _pcm(np.random.default_rng(9), width, 3 * TILE[width], 0.3)
-    loop_ = _sample(base, width, RATE, nch)
+    samples = as_samples(instruments, width, RATE)
+    base = pcm(np.random.default_rng(9), width, 3 * TILE[width], 0.3)
+    loop_ = sample_of(base, width, RATE, nch)
     for seconds, i, volume, other_seconds, speed, pan, envelope, loop, region, reverse in events:
         other = samples[i]
         o = other
@@ -441,9 +337,9 @@ def test_the_same_bytes_as_the_documented_loop_of_sample_calls(gpu, width, nch):
         if volume is not None:
             o = o.at_volume(volume)
         loop_.mix_at(seconds, o, other_seconds)
-    many = _sample(base, width, RATE, nch).mix_at_many(with_samples(samples, events))
+    many = sample_of(base, width, RATE, nch).mix_at_many(with_samples(samples, events))
     assert len(many) == len(loop_)
-    assert bytes(many.view_frame_data()) == bytes(loop_.view_frame_data()) == oracle(base, named(instruments, events), width, RATE, nch)
+    assert bytes(many.view_frame_data()) == bytes(loop_.view_frame_data()) == mix(base, named(instruments, events), width, RATE, nch)
 
 
 # ---- 8: the track as a source ------------------------------------------------------------------------------------------------------------------
@@ -451,27 +347,27 @@ def test_the_track_as_a_reversed_region_of_itself(gpu, monkeypatch):
     N = gpu
     width, nch = 2, 2
     instruments, events = notes(width, nch)
-    samples = as_samples(instruments, width)
-    calls = _spy(N, monkeypatch)
-    base = _pcm(np.random.default_rng(3), width, 3 * TILE[width], 0.3)
-    t = _sample(base, width, RATE, nch)
+    samples = as_samples(instruments, width, RATE)
+    calls = spy(N, monkeypatch)
+    base = pcm(np.random.default_rng(3), width, 3 * TILE[width], 0.3)
+    t = sample_of(base, width, RATE, nch)
     first, last = events[:30], events[30:50]
     own = (0.05, None, 0.4, None, 1.5, None, (0.02, 0.03, 0.5, 0.05, 0.2), (100 / RATE, 171 / RATE, 0.4), (0.01, 0.1), True)
     tail = (0.02, None, -0.6, 0.05, None, None, None, None, (0.3, None), True)           # to the end of the track as it is then
     t.mix_at_many(with_samples(samples, first) + [own[:1] + (t,) + own[2:], tail[:1] + (t,) + tail[2:]] + with_samples(samples, last))
     assert calls == ["sh_mix_events_rev", "sh_mix_events_rev"]                           # the list is cut at the track; one launch per side
-    mid = oracle(base, named(instruments, first), width, RATE, nch)
-    mid = oracle(mid, [own[:1] + (mid,) + own[2:]], width, RATE, nch)
-    assert mid != oracle(mid, [own[:1] + (mid,) + own[2:8] + (None, None)], width, RATE, nch)
-    mid = oracle(mid, [tail[:1] + (mid,) + tail[2:]], width, RATE, nch)
-    assert bytes(t.view_frame_data()) == oracle(mid, named(instruments, last), width, RATE, nch)
+    mid = mix(base, named(instruments, first), width, RATE, nch)
+    mid = mix(mid, [own[:1] + (mid,) + own[2:]], width, RATE, nch)
+    assert mid != mix(mid, [own[:1] + (mid,) + own[2:8] + (None, None)], width, RATE, nch)
+    mid = mix(mid, [tail[:1] + (mid,) + tail[2:]], width, RATE, nch)
+    assert bytes(t.view_frame_data()) == mix(mid, named(instruments, last), width, RATE, nch)
 
 
 # ---- 9: the entry point ------------------------------------------------------------------------------------------------------------------------
 def test_the_entry_point_refuses_on_the_host_and_leaves_the_track(gpu):
     N = gpu
     rng = np.random.default_rng(27)
-    src, base = _pcm(rng, 2, 1000), _pcm(rng, 2, 5000)
+    src, base = pcm(rng, 2, 1000), pcm(rng, 2, 5000)
     s, t = N.DeviceBuffer.from_bytes(src), N.DeviceBuffer.from_bytes(base)
     nan = float("nan")
     segs = np.zeros(1, dtype=N.ENV_SEGMENT_DTYPE)
@@ -507,26 +403,26 @@ def test_the_entry_point_refuses_on_the_host_and_leaves_the_track(gpu):
     }
     for what, (row, message) in bad.items():
         rows = [ok, row]
-        assert _mix_events_rev(N, [s], _rev_table(N, rows), segs, 2, 2, t, 5000) == N.SH_ERR_INVALID, what
+        assert mix_events(N, "rev", [s], event_table(N, "rev", rows), segs, 2, 2, t, 5000) == N.SH_ERR_INVALID, what
         err = N.lib().sh_last_error()
         assert err.startswith(b"sh_mix_events_rev") and b"event 1" in err and message in err, (what, err)
         assert t.download_bytes(len(base)) == base, what
     # width 3 with segments; width 3 without them may play backwards
     s3, t3 = N.DeviceBuffer.from_bytes(bytes(3000)), N.DeviceBuffer.from_bytes(bytes(15000))
     shaped = ok[:11] + (0, 1) + ok[13:]
-    assert _mix_events_rev(N, [s3], _rev_table(N, [ok, shaped]), segs, 3, 2, t3, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "rev", [s3], event_table(N, "rev", [ok, shaped]), segs, 3, 2, t3, 5000) == N.SH_ERR_INVALID
     assert b"event 1" in N.lib().sh_last_error()
     assert t3.download_bytes(15000) == bytes(15000)
-    assert _mix_events_rev(N, [s3], _rev_table(N, [ok]), None, 3, 2, t3, 5000) == N.SH_OK, N.lib().sh_last_error()
+    assert mix_events(N, "rev", [s3], event_table(N, "rev", [ok]), None, 3, 2, t3, 5000) == N.SH_OK, N.lib().sh_last_error()
     for width in (0, 5, -2):
-        assert _mix_events_rev(N, [s], _rev_table(N, [ok]), None, width, 2, t, 5000) == N.SH_ERR_INVALID
-    assert _mix_events_rev(N, [s], _rev_table(N, [ok]), None, 2, 0, t, 5000) == N.SH_ERR_INVALID
-    assert _mix_events_rev(N, [s, t], _rev_table(N, [ok]), None, 2, 2, t, 5000) == N.SH_ERR_INVALID        # a source that is the track
-    assert _mix_events_rev(N, [s], _rev_table(N, [ok]), None, 2, 2, t, 5001) == N.SH_ERR_INVALID
-    assert _mix_events_rev(N, [s], _rev_table(N, []), None, 2, 2, t, 5000) == N.SH_OK
+        assert mix_events(N, "rev", [s], event_table(N, "rev", [ok]), None, width, 2, t, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "rev", [s], event_table(N, "rev", [ok]), None, 2, 0, t, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "rev", [s, t], event_table(N, "rev", [ok]), None, 2, 2, t, 5000) == N.SH_ERR_INVALID        # a source that is the track
+    assert mix_events(N, "rev", [s], event_table(N, "rev", [ok]), None, 2, 2, t, 5001) == N.SH_ERR_INVALID
+    assert mix_events(N, "rev", [s], event_table(N, "rev", []), None, 2, 2, t, 5000) == N.SH_OK
     assert t.download_bytes(len(base)) == base                                                          # nothing was launched
     # and what it accepts: the reversed region, the reversed held note, then the mono one through tostereo
-    assert _mix_events_rev(N, [s], _rev_table(N, [ok, held, mono]), None, 2, 2, t, 5000) == N.SH_OK, N.lib().sh_last_error()
+    assert mix_events(N, "rev", [s], event_table(N, "rev", [ok, held, mono]), None, 2, 2, t, 5000) == N.SH_OK, N.lib().sh_last_error()
     want = bytearray(base)
     x = audioop.mul(audioop.reverse(src[400:1600], 2), 2, 0.5)
     want[200:1400] = audioop.add(base[200:1400], x, 2)

@@ -1,76 +1,23 @@
 """GPU parity of Sample.mix_at_many / mixer.sequence / sh_mix_events: a list of placed samples mixed into a track in one launch,
 against live ``audioop`` -- ``mul`` per event, ``add`` with saturation at every event, in list order, on byte slices -- the arithmetic of
-the loop of ``Sample.mix_at`` calls it replaces.  Expected bytes never come from the product."""
+the loop of ``Sample.mix_at`` calls it replaces (tests/seqref.py: mix).  Expected bytes never come from the product."""
 import audioop
-import ctypes as C
 import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+from tests.seqcases import ROOT, SONG_NCH as NCH, SONG_RATE as RATE, event_table, hits_song as song, in_a_child_under_the_other_alignment_scheme, mix_events, sample_of
+from tests.seqref import SELF, mix, pcm
+
 pytestmark = pytest.mark.gpu
-
-ROOT = Path(__file__).resolve().parent.parent
-OTHER_SCHEME = "1"      # SYNTHHIP_SEQ_ALIGN of the scheme that is not the default (include/synthhip.h)
-SELF = object()            # an event whose source is the track itself, as earlier events left it
-
-
-def _sample(data: bytes, width, rate, nch):
-    from synthesizer_amd.sample import Sample
-    return Sample.from_raw_frames(data, width, rate, nch)
-
-
-def oracle(track: bytes, events, width, rate, nch) -> bytes:
-    """events: (seconds, source bytes | SELF, volume | None, other_seconds | None), applied like upstream's mix_at, one after another"""
-    fb = width * nch
-    t = bytearray(track)
-    for seconds, src, volume, other_seconds in events:
-        frames = bytes(t) if src is SELF else src
-        if volume is not None:
-            frames = audioop.mul(frames, width, volume)
-        if other_seconds:
-            frames = frames[:fb * int(rate * other_seconds)]
-        start = fb * int(rate * seconds)
-        end = start + len(frames)
-        if end > len(t):
-            t.extend(bytes(end - len(t)))
-        t[start:end] = audioop.add(bytes(t[start:end]), frames, width)
-    return bytes(t)
-
-
-def _pcm(rng, width, nsamples, scale=1.0) -> bytes:
-    if width == 3:
-        v = rng.integers(int(-8388608 * scale), int(8388607 * scale) + 1, nsamples, dtype=np.int64)
-        return (v.astype("<i4").view(np.uint8).reshape(-1, 4)[:, :3]).tobytes()
-    hi = 2 ** (8 * width - 1)
-    return rng.integers(int(-hi * scale), int((hi - 1) * scale) + 1, nsamples, dtype=np.int64).astype({1: np.int8, 2: "<i2", 4: "<i4"}[width]).tobytes()
 
 
 # ---- 1, 2: the song ------------------------------------------------------------------------------------------------------------------
-RATE, NCH = 48000, 2
-VOLUMES = [1.0, 1.0, 0.5, 0.8, -1.0, 0.0, 1.7]
-
-
-def song(nevents=3000, span=20.0):
-    rng = np.random.default_rng(0)
-    instruments = []
-    for seconds in (0.05, 0.12, 0.25, 0.4):
-        n = int(RATE * seconds)
-        decay = np.exp(-3.0 * np.arange(n) / n)[:, None]
-        noise = rng.uniform(-1.0, 1.0, (n, NCH))
-        instruments.append((noise * decay * 0.5 * 32767).astype("<i2").tobytes())
-    starts = rng.integers(0, int(RATE * span), nevents) / RATE
-    starts[:50] = starts[0]
-    which = rng.integers(0, 4, nevents)
-    volumes = rng.choice(VOLUMES, nevents)
-    return instruments, [(float(starts[k]), int(which[k]), float(volumes[k])) for k in range(nevents)]
-
-
 def test_the_song(gpu):
     from synthesizer_amd import mixer
     instruments, events = song()
-    want = oracle(b"", [(s, instruments[i], v, None) for s, i, v in events], 2, RATE, NCH)
+    want = mix(b"", [(s, instruments[i], v, None) for s, i, v in events], 2, RATE, NCH)
     # the oracle must be able to tell an ordered saturating fold from an unordered one, and aligned starts from any start
     nsamples = len(want) // 2
     total = np.zeros(nsamples, dtype=np.int64)
@@ -80,13 +27,13 @@ def test_the_song(gpu):
         total[at:at + len(x)] += x
     w = np.frombuffer(want, dtype="<i2")
     differs_from_sum = int(np.count_nonzero(np.clip(total, -32768, 32767) != w))
-    backwards = oracle(b"", [(s, instruments[i], v, None) for s, i, v in reversed(events)], 2, RATE, NCH)
+    backwards = mix(b"", [(s, instruments[i], v, None) for s, i, v in reversed(events)], 2, RATE, NCH)
     differs_from_reversed = int(np.count_nonzero(np.frombuffer(backwards, dtype="<i2") != w))
     off_vector = sum(1 for s, _i, _v in events if (NCH * int(RATE * s)) % 8)
     print("song: %d samples, %d on a bound, %d differ from clamp(sum), %d from the reversed list, %d of %d starts off a multiple of eight samples"
           % (nsamples, int(np.count_nonzero((w == 32767) | (w == -32768))), differs_from_sum, differs_from_reversed, off_vector, len(events)))
     assert differs_from_sum > 0 and differs_from_reversed > 0 and off_vector > 0
-    samples = [_sample(b, 2, RATE, NCH) for b in instruments]
+    samples = [sample_of(b, 2, RATE, NCH) for b in instruments]
     got = mixer.sequence([(s, samples[i], v) for s, i, v in events], RATE, NCH, 2, name="song")
     assert got.name == "song" and (got.samplerate, got.nchannels, got.samplewidth) == (RATE, NCH, 2)
     assert bytes(got.view_frame_data()) == want
@@ -96,31 +43,28 @@ def test_the_same_bytes_as_the_loop_of_mix_at(gpu):
     """The definition: mix_at / at_volume on the product, event by event (volume None and other_seconds among them)."""
     from synthesizer_amd.sample import Sample
     instruments, events = song(300, 3.0)
-    samples = [_sample(b, 2, RATE, NCH) for b in instruments]
+    samples = [sample_of(b, 2, RATE, NCH) for b in instruments]
     evs = [(s, samples[i], None if k % 5 == 0 else v, 0.03 if k % 7 == 0 else None) for k, (s, i, v) in enumerate(events)]
     evs[10] = (0.0,) + evs[10][1:]
-    base = _pcm(np.random.default_rng(1), 2, NCH * RATE, 0.3)
-    loop = _sample(base, 2, RATE, NCH)
+    base = pcm(np.random.default_rng(1), 2, NCH * RATE, 0.3)
+    loop = sample_of(base, 2, RATE, NCH)
     for seconds, other, volume, other_seconds in evs:
         loop.mix_at(seconds, other if volume is None else other.at_volume(volume), other_seconds)
-    many = _sample(base, 2, RATE, NCH).mix_at_many(evs)
+    many = sample_of(base, 2, RATE, NCH).mix_at_many(evs)
     assert isinstance(many, Sample) and len(many) == len(loop) > RATE
     assert bytes(many.view_frame_data()) == bytes(loop.view_frame_data())
-    want = oracle(base, [(s, instruments[samples.index(o)], v, os_) for s, o, v, os_ in evs], 2, RATE, NCH)
+    want = mix(base, [(s, instruments[samples.index(o)], v, os_) for s, o, v, os_ in evs], 2, RATE, NCH)
     assert bytes(many.view_frame_data()) == want
 
 
 # ---- 3: widths, channels, every offset ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nch", [1, 2])
-@pytest.mark.parametrize("width", [1, 2, 3, 4])
-def test_widths_channels_and_every_offset(gpu, width, nch):
-    rate = 8192                                        # (a power of two: seconds = frame / rate is exact)
+def _every_offset(width, nch, rate):
     rng = np.random.default_rng(100 * width + nch)
     tile = 2048 if width == 2 else 1024
     lengths = [1, 2, 7, 8, 9, 15, 16, 17, 31, 64, 100, tile - 1, tile, tile + 1, 3 * tile + 5, 5 * tile]
-    sources = [_pcm(rng, width, nch * ((n + nch - 1) // nch), 0.4) for n in lengths]
+    sources = [pcm(rng, width, nch * ((n + nch - 1) // nch), 0.4) for n in lengths]
     track_frames = 12 * tile
-    base = _pcm(rng, width, nch * track_frames, 0.4)
+    base = pcm(rng, width, nch * track_frames, 0.4)
     events = []
     for k in range(320):
         i = k % len(sources)
@@ -136,24 +80,19 @@ def test_widths_channels_and_every_offset(gpu, width, nch):
         other_seconds = (nframes // 2) / rate if k % 11 == 0 and nframes > 1 else None
         events.append((frame / rate, i, volume, other_seconds))
     assert {(nch * int(rate * s)) % 16 for s, _i, _v, _o in events} == set(range(0, 16, nch))
-    want = oracle(base, [(s, sources[i], v, o) for s, i, v, o in events], width, rate, nch)
-    samples = [_sample(b, width, rate, nch) for b in sources]
-    got = _sample(base, width, rate, nch).mix_at_many([(s, samples[i], v, o) for s, i, v, o in events])
+    return sources, base, events
+
+
+@pytest.mark.parametrize("nch", [1, 2])
+@pytest.mark.parametrize("width", [1, 2, 3, 4])
+def test_widths_channels_and_every_offset(gpu, width, nch):
+    rate = 8192                                        # (a power of two: seconds = frame / rate is exact)
+    sources, base, events = _every_offset(width, nch, rate)
+    want = mix(base, [(s, sources[i], v, o) for s, i, v, o in events], width, rate, nch)
+    samples = [sample_of(b, width, rate, nch) for b in sources]
+    got = sample_of(base, width, rate, nch).mix_at_many([(s, samples[i], v, o) for s, i, v, o in events])
     assert len(got) * width * nch == len(want) > len(base)
     assert bytes(got.view_frame_data()) == want
-
-
-def _events_table(N, rows):
-    t = np.zeros(len(rows), dtype=N.MIX_EVENT_DTYPE)
-    for k, r in enumerate(rows):
-        t[k] = tuple(r) + (0,) * (6 - len(r))
-    return t
-
-
-def _mix_events(N, srcs, table, width, track, track_samples):
-    arr = (C.c_void_p * max(1, len(srcs)))(*[b.handle for b in srcs])
-    return N.lib().sh_mix_events(arr, len(srcs), table.ctypes.data if len(table) else None, len(table), width,
-                                   track.handle if track is not None else None, track_samples)
 
 
 @pytest.mark.parametrize("width", [1, 2, 3, 4])
@@ -162,8 +101,8 @@ def test_the_entry_point_with_sub_ranges_of_sources(gpu, width):
     N = gpu
     rng = np.random.default_rng(40 + width)
     nsrc_samples, ntrack = 9000, 30000
-    src = _pcm(rng, width, nsrc_samples, 0.5)
-    base = _pcm(rng, width, ntrack, 0.5)
+    src = pcm(rng, width, nsrc_samples, 0.5)
+    base = pcm(rng, width, ntrack, 0.5)
     whole = N.DeviceBuffer.from_bytes(src)
     view = whole.view(6 * width, (nsrc_samples - 6) * width)          # a source whose device memory starts off the 16-byte grid
     rows, want = [], bytearray(base)
@@ -182,7 +121,7 @@ def test_the_entry_point_with_sub_ranges_of_sources(gpu, width):
             frames = audioop.mul(frames, width, factor)
         want[d * width:(d + n) * width] = audioop.add(bytes(want[d * width:(d + n) * width]), frames, width)
     track = N.DeviceBuffer.from_bytes(base)
-    assert _mix_events(N, [whole, view], _events_table(N, rows), width, track, ntrack) == N.SH_OK
+    assert mix_events(N, "plain", [whole, view], event_table(N, "plain", rows), None, width, None, track, ntrack) == N.SH_OK
     assert track.download_bytes(len(base)) == bytes(want)
 
 
@@ -193,36 +132,36 @@ def test_growth_in_place_and_the_corner_cases(gpu):
     N = gpu
     rate = 8192
     rng = np.random.default_rng(5)
-    a, b, c = _pcm(rng, 2, 8192, 0.6), _pcm(rng, 2, 3000, 0.6), _pcm(rng, 2, 500, 0.6)
-    A, B, Cc = (_sample(x, 2, rate, 1) for x in (a, b, c))
+    a, b, c = pcm(rng, 2, 8192, 0.6), pcm(rng, 2, 3000, 0.6), pcm(rng, 2, 500, 0.6)
+    A, B, Cc = (sample_of(x, 2, rate, 1) for x in (a, b, c))
     # growth: events beyond the end -- a gap of silence, then the sample
-    t = _sample(a, 2, rate, 1).mix_at_many([(2.0, B), (0.5, Cc, 0.5), (3.0, Cc)])
-    want = oracle(a, [(2.0, b, None, None), (0.5, c, 0.5, None), (3.0, c, None, None)], 2, rate, 1)
+    t = sample_of(a, 2, rate, 1).mix_at_many([(2.0, B), (0.5, Cc, 0.5), (3.0, Cc)])
+    want = mix(a, [(2.0, b, None, None), (0.5, c, 0.5, None), (3.0, c, None, None)], 2, rate, 1)
     assert len(t) == 3 * 8192 + 500 and bytes(t.view_frame_data()) == want
     assert not np.frombuffer(want, dtype="<i2")[8192:16384].any()
     # no growth: in place, the same device buffer object before and after; the sources untouched
-    t = _sample(a, 2, rate, 1).to_device()
+    t = sample_of(a, 2, rate, 1).to_device()
     dev = t._device()
     t.mix_at_many([(0.25, B), (0.0, Cc, -1.0), (0.9, Cc, None, 0.01)])
     assert t._device() is dev
-    assert bytes(t.view_frame_data()) == oracle(a, [(0.25, b, None, None), (0.0, c, -1.0, None), (0.9, c, None, 0.01)], 2, rate, 1)
+    assert bytes(t.view_frame_data()) == mix(a, [(0.25, b, None, None), (0.0, c, -1.0, None), (0.9, c, None, 0.01)], 2, rate, 1)
     assert bytes(B.view_frame_data()) == b and bytes(Cc.view_frame_data()) == c
     # empty list, zero-length events, an empty track
-    t = _sample(a, 2, rate, 1)
+    t = sample_of(a, 2, rate, 1)
     assert t.mix_at_many([]) is t and bytes(t.view_frame_data()) == a
-    empty = _sample(b"", 2, rate, 1)
+    empty = sample_of(b"", 2, rate, 1)
     t.mix_at_many([(0.5, empty), (0.1, B, 1.0, 0.00001), (0.0, empty, 0.5)])
     assert bytes(t.view_frame_data()) == a and len(t) == 8192
     t.mix_at_many([(1.5, empty)])                      # a zero-length event beyond the end still grows the track, as mix_at does
-    assert bytes(t.view_frame_data()) == oracle(a, [(1.5, b"", None, None)], 2, rate, 1) and len(t) == 12288
+    assert bytes(t.view_frame_data()) == mix(a, [(1.5, b"", None, None)], 2, rate, 1) and len(t) == 12288
     assert len(mixer.sequence([], rate, 1)) == 0 and len(mixer.sequence([(0.0, empty)], rate, 1)) == 0
     # `other is self` in the middle of a list: it reads the track as the events before it left it
-    t = _sample(a, 2, rate, 1)
+    t = sample_of(a, 2, rate, 1)
     t.mix_at_many([(0.1, B, 0.9), (0.05, t, 0.5, 0.2), (0.3, Cc), (0.0, t), (0.7, Cc, 1.5)])
-    assert bytes(t.view_frame_data()) == oracle(a, [(0.1, b, 0.9, None), (0.05, SELF, 0.5, 0.2), (0.3, c, None, None), (0.0, SELF, None, None),
+    assert bytes(t.view_frame_data()) == mix(a, [(0.1, b, 0.9, None), (0.05, SELF, 0.5, 0.2), (0.3, c, None, None), (0.0, SELF, None, None),
                                                    (0.7, c, 1.5, None)], 2, rate, 1)
     # a locked track; bad arguments as mix_at gives them, and nothing mixed before the error
-    t = _sample(a, 2, rate, 1)
+    t = sample_of(a, 2, rate, 1)
     with pytest.raises(ValueError):
         t.mix_at_many([(0.1, B), (-0.5, B)])
     with pytest.raises(ValueError):
@@ -230,30 +169,30 @@ def test_growth_in_place_and_the_corner_cases(gpu):
     with pytest.raises(ValueError):
         t.mix_at_many([(0.5, B, float("inf"))])
     with pytest.raises(AssertionError):
-        t.mix_at_many([(0.1, B), (0.5, _sample(a, 2, rate, 2))])
+        t.mix_at_many([(0.1, B), (0.5, sample_of(a, 2, rate, 2))])
     with pytest.raises(AssertionError):
-        t.mix_at_many([(0.5, _sample(a, 4, rate, 1))])
+        t.mix_at_many([(0.5, sample_of(a, 4, rate, 1))])
     with pytest.raises(AssertionError):
-        t.mix_at_many([(0.5, _sample(a, 2, rate + 1, 1))])
+        t.mix_at_many([(0.5, sample_of(a, 2, rate + 1, 1))])
     assert bytes(t.view_frame_data()) == a
     with pytest.raises(RuntimeError):
-        _sample(a, 2, rate, 1).lock().mix_at_many([(0.1, B)])
-    assert bytes(_sample(a, 2, rate, 1).mix_at_many([(0.1, B.lock(), 0.5)]).view_frame_data()) == oracle(a, [(0.1, b, 0.5, None)], 2, rate, 1)
+        sample_of(a, 2, rate, 1).lock().mix_at_many([(0.1, B)])
+    assert bytes(sample_of(a, 2, rate, 1).mix_at_many([(0.1, B.lock(), 0.5)]).view_frame_data()) == mix(a, [(0.1, b, 0.5, None)], 2, rate, 1)
     # a track a RealTimeMixer streams from is never written in place: what the mixer plays does not change
-    t = _sample(a, 2, rate, 1).to_device()
+    t = sample_of(a, 2, rate, 1).to_device()
     m = RealTimeMixer(2048)
     m.add_sample(t)
     t.mix_at_many([(0.0, Cc), (0.1, B)])
-    assert bytes(t.view_frame_data()) == oracle(a, [(0.0, c, None, None), (0.1, b, None, None)], 2, rate, 1)
+    assert bytes(t.view_frame_data()) == mix(a, [(0.0, c, None, None), (0.1, b, None, None)], 2, rate, 1)
     chunks = m.chunks()
     assert bytes(next(chunks)) + bytes(next(chunks)) == a[:4096]
     # -32768 x -1.0 -> 32767 (fbound clamps the product), at every width; volume None == 1.0
     for width in (1, 2, 3, 4):
         lowest = (-(2 ** (8 * width - 1))).to_bytes(width, "little", signed=True) * 40
-        got = mixer.sequence([(0.0, _sample(lowest, width, rate, 1), -1.0)], rate, 1, width)
+        got = mixer.sequence([(0.0, sample_of(lowest, width, rate, 1), -1.0)], rate, 1, width)
         assert bytes(got.view_frame_data()) == (2 ** (8 * width - 1) - 1).to_bytes(width, "little", signed=True) * 40 == audioop.mul(lowest, width, -1.0)
-    x = _sample(a, 2, rate, 1).mix_at_many([(0.2, B), (0.21, Cc)])
-    y = _sample(a, 2, rate, 1).mix_at_many([(0.2, B, 1.0), (0.21, Cc, 1.0)])
+    x = sample_of(a, 2, rate, 1).mix_at_many([(0.2, B), (0.21, Cc)])
+    y = sample_of(a, 2, rate, 1).mix_at_many([(0.2, B, 1.0), (0.21, Cc, 1.0)])
     assert bytes(x.view_frame_data()) == bytes(y.view_frame_data())
 
 
@@ -261,7 +200,7 @@ def test_growth_in_place_and_the_corner_cases(gpu):
 def test_the_entry_point_refuses_on_the_host(gpu):
     N = gpu
     rng = np.random.default_rng(6)
-    src, base = _pcm(rng, 2, 1000), _pcm(rng, 2, 5000)
+    src, base = pcm(rng, 2, 1000), pcm(rng, 2, 5000)
     s, t = N.DeviceBuffer.from_bytes(src), N.DeviceBuffer.from_bytes(base)
     ok = (100, 0, 1000, 0.5, 0)
     bad = {
@@ -275,19 +214,19 @@ def test_the_entry_point_refuses_on_the_host(gpu):
         "reserved": [ok, (0, 0, 10, 1.0, 0, 7)],
     }
     for what, rows in bad.items():
-        assert _mix_events(N, [s], _events_table(N, rows), 2, t, 5000) == N.SH_ERR_INVALID, what
+        assert mix_events(N, "plain", [s], event_table(N, "plain", rows), None, 2, None, t, 5000) == N.SH_ERR_INVALID, what
         assert N.lib().sh_last_error().startswith(b"sh_mix_events"), what
     for width in (0, 5, -2):
-        assert _mix_events(N, [s], _events_table(N, [ok]), width, t, 5000) == N.SH_ERR_INVALID
-    assert _mix_events(N, [s, t], _events_table(N, [ok]), 2, t, 5000) == N.SH_ERR_INVALID            # a source that is the track
-    assert _mix_events(N, [t.view(200, 400)], _events_table(N, [(0, 0, 10, 1.0, 0)]), 2, t, 5000) == N.SH_ERR_INVALID       # ... or a window of it
-    assert _mix_events(N, [s], _events_table(N, [ok]), 2, t, 5001) == N.SH_ERR_INVALID                # the track range outside its buffer
-    assert _mix_events(N, [s], _events_table(N, [ok]), 2, None, 0) == N.SH_ERR_INVALID
+        assert mix_events(N, "plain", [s], event_table(N, "plain", [ok]), None, width, None, t, 5000) == N.SH_ERR_INVALID
+    assert mix_events(N, "plain", [s, t], event_table(N, "plain", [ok]), None, 2, None, t, 5000) == N.SH_ERR_INVALID            # a source that is the track
+    assert mix_events(N, "plain", [t.view(200, 400)], event_table(N, "plain", [(0, 0, 10, 1.0, 0)]), None, 2, None, t, 5000) == N.SH_ERR_INVALID       # ... or a window of it
+    assert mix_events(N, "plain", [s], event_table(N, "plain", [ok]), None, 2, None, t, 5001) == N.SH_ERR_INVALID                # the track range outside its buffer
+    assert mix_events(N, "plain", [s], event_table(N, "plain", [ok]), None, 2, None, None, 0) == N.SH_ERR_INVALID
     assert t.download_bytes(len(base)) == base                                                          # nothing was launched
-    assert _mix_events(N, [s], _events_table(N, []), 2, t, 5000) == N.SH_OK
-    assert _mix_events(N, [s], _events_table(N, [(5000, 1000, 0, 1.0, 0)]), 2, t, 5000) == N.SH_OK      # empty ranges at the very ends
+    assert mix_events(N, "plain", [s], event_table(N, "plain", []), None, 2, None, t, 5000) == N.SH_OK
+    assert mix_events(N, "plain", [s], event_table(N, "plain", [(5000, 1000, 0, 1.0, 0)]), None, 2, None, t, 5000) == N.SH_OK      # empty ranges at the very ends
     assert t.download_bytes(len(base)) == base
-    assert _mix_events(N, [s], _events_table(N, [ok]), 2, t, 5000) == N.SH_OK
+    assert mix_events(N, "plain", [s], event_table(N, "plain", [ok]), None, 2, None, t, 5000) == N.SH_OK
     want = bytearray(base)
     want[200:2200] = audioop.add(base[200:2200], audioop.mul(src, 2, 0.5), 2)
     assert t.download_bytes(len(base)) == bytes(want)
@@ -313,14 +252,14 @@ def test_sequence_against_the_reference_sample(gpu):
     from synthesizer_amd import mixer
     rate, nch = 22050, 2
     rng = np.random.default_rng(8)
-    hits = [_pcm(rng, 2, nch * n, 0.7) for n in (300, 2500, 9000)]
+    hits = [pcm(rng, 2, nch * n, 0.7) for n in (300, 2500, 9000)]
     events = [(float(rng.uniform(0, 1.5)), int(rng.integers(0, 3)), [None, 0.6, 1.3, -0.9][k % 4], [None, None, 0.05][k % 3]) for k in range(120)]
     events[3] = (0.0,) + events[3][1:]
     ref = RefSample(b"", 2, rate, nch)
     refs = [RefSample(h, 2, rate, nch) for h in hits]
     for seconds, i, volume, other_seconds in events:
         ref.mix_at(seconds, refs[i] if volume is None else refs[i].at_volume(volume), other_seconds)
-    samples = [_sample(h, 2, rate, nch) for h in hits]
+    samples = [sample_of(h, 2, rate, nch) for h in hits]
     got = mixer.sequence([(s, samples[i], v, o) for s, i, v, o in events], rate, nch)
     assert len(got) == len(ref) and bytes(got.view_frame_data()) == ref.frames
 
@@ -329,9 +268,9 @@ def test_sequence_against_the_reference_sample(gpu):
 def test_a_second_call_with_the_same_shapes_allocates_nothing(gpu):
     N = gpu
     instruments, events = song(400, 2.0)
-    samples = [_sample(b, 2, RATE, NCH).to_device() for b in instruments]
+    samples = [sample_of(b, 2, RATE, NCH).to_device() for b in instruments]
     evs = [(s, samples[i], v) for s, i, v in events]
-    track = _sample(bytes(2 * NCH * RATE * 3), 2, RATE, NCH).to_device()
+    track = sample_of(bytes(2 * NCH * RATE * 3), 2, RATE, NCH).to_device()
     track.mix_at_many(evs)
     N.sync()
     before = N.debug_counters()
@@ -339,7 +278,7 @@ def test_a_second_call_with_the_same_shapes_allocates_nothing(gpu):
     after = N.debug_counters()
     assert after["device_allocs"] == before["device_allocs"] and after["device_frees"] == before["device_frees"]
     assert after["stream_syncs"] == before["stream_syncs"] and after["pool_hits"] == before["pool_hits"]
-    want = oracle(bytes(2 * NCH * RATE * 3), [(s, instruments[i], v, None) for s, i, v in events] * 2, 2, RATE, NCH)
+    want = mix(bytes(2 * NCH * RATE * 3), [(s, instruments[i], v, None) for s, i, v in events] * 2, 2, RATE, NCH)
     assert bytes(track.view_frame_data()) == want
 
 
@@ -347,9 +286,5 @@ def test_a_second_call_with_the_same_shapes_allocates_nothing(gpu):
 def test_the_other_alignment_scheme_gives_the_same_bytes(gpu):
     """SYNTHHIP_SEQ_ALIGN selects between two schedules of the same loads (read once, by sh_init: a child process): the song, every
     offset and the sub-ranges of sources again under the one that is not the default."""
-    import os
-    import sys
-    env = dict(os.environ, SYNTHHIP_SEQ_ALIGN=OTHER_SCHEME)
-    p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider", str(Path(__file__).resolve()),
-                        "-k", "the_song or every_offset or sub_ranges"], cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0 and " passed" in p.stdout and "failed" not in p.stdout, p.stdout[-3000:] + p.stderr[-1000:]
+    in_a_child_under_the_other_alignment_scheme(__file__, ["test_the_song"] + ["test_widths_channels_and_every_offset[%d-%d]" % (w, n) for w in (1, 2, 3, 4) for n in (1, 2)] +
+                                                ["test_the_entry_point_with_sub_ranges_of_sources[%d]" % w for w in (1, 2, 3, 4)])

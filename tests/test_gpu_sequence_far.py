@@ -5,7 +5,7 @@ that wraps or one tile number in the wrong width would go unnoticed by songs of 
 
 Nothing large is computed on the CPU.  The reference chain places an event by padding silence in front of it, so for a base B that is a
 multiple of the channel count the bytes of the far window [B + a, B + b) are the bytes [a, b) of the same list placed at 0: the near
-songs of tests/test_gpu_compiled.py, test_gpu_tracks.py and test_gpu_meters.py (their live-``audioop`` oracles and their self-check) are
+songs of tests/seqcases.py that the compiled, tracks and meters files render (the live-``audioop`` reference and their self-check) are
 used as they stand, the product's packer makes the table of the NEAR list, and B is added to the table's ``dst_sample`` column -- the
 table is an input of the entry points.  Expected bytes come from ``audioop`` alone, never from the product.  A compiled song's length is
 only a number and a window of it renders into a small buffer; the mixing kernels get a track of that many bytes of which only the
@@ -21,14 +21,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests.test_gpu_channels import _mix_events_chan, oracle
-from tests.test_gpu_compiled import HELD, LEVEL_NAME, LEVELS, _ev, _seq_create, check_song, compiled_raw, render_window, song, windows
-from tests.test_gpu_enveloped import _differs
-from tests.test_gpu_looped import LANE, RATE, TILE, _mix_events_loop
-from tests.test_gpu_meters import metered, reference, the_song
-from tests.test_gpu_reversed import _mix_events_rev, as_samples, named, with_samples
-from tests.test_gpu_sequence import _pcm
-from tests.test_gpu_tracks import GAINS, WithGains, master, raw_tracks, subs_of
+from tests.seqcases import (GAINS, HELD, LEVEL_NAME, LEVELS, RATE, WithGains, _ev, as_samples, check_song, compiled_raw, master, metered, mix_events, named,
+                            raw_tracks, reference, render_window, seq_create, song, subs_of, the_song, windows, with_samples)
+from tests.seqref import LANE, TILE, differs, mix, pcm
 
 pytestmark = pytest.mark.gpu
 
@@ -83,7 +78,7 @@ def check_windows(N, seq, width, want, B, wins, out_samples=(0, 1, 8)):
         exp = far_bytes(want, B, a, b, width)
         for out_sample in out_samples:
             got, front, behind = render_window(N, seq, width, a, b, out_sample)
-            assert got == exp, "window [%d, %d) = B + [%d, %d) at out_sample %d: %d bytes differ" % (a, b, a - B, b - B, out_sample, _differs(got, exp))
+            assert got == exp, "window [%d, %d) = B + [%d, %d) at out_sample %d: %d bytes differ" % (a, b, a - B, b - B, out_sample, differs(got, exp))
             assert front == b"\x5a" * 64 and behind == b"\x5a" * 64, (a, b, out_sample)
 
 
@@ -99,7 +94,7 @@ def with_last_row(level, width):
         T = TILE[width]
         rest = {"pan": dict(pan=(1.0, 1.0))}.get(level, {})
         events = events + [_ev(4 * T // nch - HELD[2], 2, 0.9, **rest)]
-        want = oracle(b"", named(instruments, events), width, RATE, nch)
+        want = mix(b"", named(instruments, events), width, RATE, nch)
         assert len(want) == 4 * T * width
         _LAST[(level, width)] = (instruments, events, nch, want)
     return _LAST[(level, width)]
@@ -143,10 +138,10 @@ def test_windows_of_a_far_downmix_song(gpu, width, row):
     wins = [(B + a, B + b) for a, b in windows("downmix", width, total) if (a, b) != (0, total)] + [(B - 5, B + L + 2)]
     if row:
         at = total + 32768 + T + 7                          # near; far it starts at sample 2^31 + T + 7
-        instruments = instruments + [(_pcm(np.random.default_rng(7000 + width), width, HELD[2], 0.6), 1)]
+        instruments = instruments + [(pcm(np.random.default_rng(7000 + width), width, HELD[2], 0.6), 1)]
         events = events + [_ev(at, 3, 0.8)]
         near = want
-        want = oracle(b"", named(instruments, events), width, RATE, 1)
+        want = mix(b"", named(instruments, events), width, RATE, 1)
         assert want[:len(near)] == near and len(want) == (at + HELD[2]) * width and B + at > 2 ** 31
         wins += [(B + total - 5, B + total + 3), (2 ** 31 - 1, 2 ** 31 + 1), (B + at - 3, B + at + HELD[2]), (B + at + 1, B + at + 2)]
         total = at + HELD[2]
@@ -183,7 +178,7 @@ def test_a_song_of_exactly_the_greatest_length(gpu, level, width):
     err = lib.sh_last_error()
     assert err.startswith(b"sh_seq_render") and b"range outside the song" in err, err
     assert out.download_bytes(64) == b"\x5a" * 64
-    rc, h = _seq_create(N, args[0], table, args[2], width, nch, MAX + 1)
+    rc, h = seq_create(N, args[0], table, args[2], width, nch, MAX + 1)
     err = lib.sh_last_error()
     assert rc == N.SH_ERR_INVALID and not h.value and err.startswith(b"sh_seq_create") and b"2^32 - 65536" in err, err
     seq.free()
@@ -221,7 +216,7 @@ def test_the_whole_far_song_in_one_launch_on_a_folded_grid(gpu, tracks):
             assert out.download_bytes(64, at) == b"\x5a" * 64, at
         seq.render(0, MAX, out, 0, gains=gains)
         got = out.download_bytes(4 * T, B)
-        assert got == want, "%d bytes of the song differ" % _differs(got, want)
+        assert got == want, "%d bytes of the song differ" % differs(got, want)
         K = 65536
         for at in (0, 2 ** 31 - K // 2, B - K):
             assert out.download_bytes(K, at) == bytes(K), at
@@ -258,7 +253,7 @@ def test_tracks_and_meters_far_out(gpu, kind, width, base):
         for a, b in wins:
             exp = want[a * width:b * width]
             got, front, behind = render_window(N, WithGains(seq, gains), width, B + a, B + b, 1)
-            assert got == exp, "gains %s, window B + [%d, %d): %d bytes differ" % (gains, a, b, _differs(got, exp))
+            assert got == exp, "gains %s, window B + [%d, %d): %d bytes differ" % (gains, a, b, differs(got, exp))
             assert front == b"\x5a" * 64 and behind == b"\x5a" * 64, (gains, a, b)
             rows, metered_bytes, guards = metered(N, seq, width, B + a, B + b, gains)
             ref = reference((kind, width), subs, gains, width, nch, a, b)
@@ -268,33 +263,17 @@ def test_tracks_and_meters_far_out(gpu, kind, width, base):
 
 
 # ---- (e) the mixing kernels through the seven entry points ---------------------------------------------------------------------------------
-LOWER = {"plain": "MIX_EVENT_DTYPE", "rate": "MIX_EVENT_RATE_DTYPE", "pan": "MIX_EVENT_PAN_DTYPE", "env": "MIX_EVENT_ENV_DTYPE",
-         "loop": "MIX_EVENT_LOOP_DTYPE", "rev": "MIX_EVENT_REV_DTYPE", "downmix": "MIX_EVENT_CHAN_DTYPE", "balance": "MIX_EVENT_CHAN_DTYPE"}
-
-
 def mix_through(N, level, bufs, table, segtab, width, nch, track, track_samples):
     """one call of the level's own entry point: the chan table narrowed to that entry point's struct (the fields it lacks hold nothing in
-    a list of its level), as tests/test_gpu_sequence_levels.py's _run narrows the lower four"""
-    dtype = getattr(N, LOWER[level])
+    a list of its level)"""
+    name = LEVEL_NAME.get(level, level)
+    dtype = N.MIX_LEVELS[N.SEQ_LEVELS.index(name)].dtype
     t = np.zeros(len(table), dtype=dtype)
-    for name in dtype.names:
-        t[name] = table[name]
-    for name in set(table.dtype.names) - set(dtype.names):
-        assert not table[name].any() or name in ("src_frames", "inrate", "outrate", "src_channels"), (level, name)
-    lib = N.lib()
-    arr = (C.c_void_p * len(bufs))(*[b.handle for b in bufs])
-    seg = segtab.ctypes.data if segtab is not None and len(segtab) else None
-    nseg = len(segtab) if segtab is not None else 0
-    if level == "plain":
-        return lib.sh_mix_events(arr, len(bufs), t.ctypes.data, len(t), width, track.handle, track_samples)
-    if level == "rate":
-        return lib.sh_mix_events_rate(arr, len(bufs), t.ctypes.data, len(t), width, nch, track.handle, track_samples)
-    if level == "pan":
-        return lib.sh_mix_events_pan(arr, len(bufs), t.ctypes.data, len(t), width, track.handle, track_samples)
-    if level == "env":
-        return lib.sh_mix_events_env(arr, len(bufs), t.ctypes.data, len(t), seg, nseg, width, nch, track.handle, track_samples)
-    call = {"loop": _mix_events_loop, "rev": _mix_events_rev}.get(level, _mix_events_chan)
-    return call(N, bufs, t, segtab, width, nch, track, track_samples)
+    for field in dtype.names:
+        t[field] = table[field]
+    for field in set(table.dtype.names) - set(dtype.names):
+        assert not table[field].any() or field in ("src_frames", "inrate", "outrate", "src_channels"), (level, field)
+    return mix_events(N, name, bufs, t, segtab, width, nch, track, track_samples)
 
 
 @pytest.mark.parametrize("level, width, base", [(lv, w, "mid") for lv, w in EVERY] + [("downmix", w, "dm") for w in (1, 2, 3, 4)] +
@@ -311,8 +290,8 @@ def test_the_mixing_kernels_far_out(gpu, level, width, base):
     else:
         instruments, events, nch, _silent, total = song(level, width)
     B = base_of(base, width, total)
-    quiet = _pcm(np.random.default_rng(8000 + 10 * LEVELS.index(level) + width), width, total, 0.4)
-    want = oracle(quiet, named(instruments, events), width, RATE, nch)
+    quiet = pcm(np.random.default_rng(8000 + 10 * LEVELS.index(level) + width), width, total, 0.4)
+    want = mix(quiet, named(instruments, events), width, RATE, nch)
     assert len(want) == len(quiet) and want != quiet        # every event fits: the entry points do not grow a track
     (args, _kw), _samples = raw_tracks(_Pack, instruments, [events], nch, width)
     bufs, table, segtab, _w, _nch, packed = args
@@ -329,7 +308,7 @@ def test_the_mixing_kernels_far_out(gpu, level, width, base):
     finally:
         track.free()
     mixed = got[len(front):len(front) + len(quiet)]
-    assert mixed == want, "%d bytes differ (%d from the untouched base)" % (_differs(mixed, want), _differs(mixed, quiet))
+    assert mixed == want, "%d bytes differ (%d from the untouched base)" % (differs(mixed, want), differs(mixed, quiet))
     assert got[:len(front)] == front and got[len(front) + len(quiet):] == behind
 
 
@@ -337,14 +316,14 @@ def test_the_mixing_kernels_far_out(gpu, level, width, base):
 def test_the_product_compiles_and_renders_a_song_of_the_greatest_length(gpu):
     from synthesizer_amd import mixer
     rng = np.random.default_rng(99)
-    instruments = [(_pcm(rng, 2, HELD[2], 0.9), 1), (_pcm(rng, 2, HELD[1], 0.9), 1)]
+    instruments = [(pcm(rng, 2, HELD[2], 0.9), 1), (pcm(rng, 2, HELD[1], 0.9), 1)]
     near = [(0, 0, 0.8), (50, 1, 1.7), (400 - HELD[2], 0, None)]
-    want = oracle(b"", named(instruments, [_ev(*e) for e in near]), 2, RATE, 1)
+    want = mix(b"", named(instruments, [_ev(*e) for e in near]), 2, RATE, 1)
     assert len(want) == 2 * 400
     B = MAX - 400
     far = [_ev(B + f, i, v) for f, i, v in near]
     assert all(int(RATE * e[0]) == B + f for e, (f, _i, _v) in zip(far, near))      # seconds = frame / 8192 is exact
-    samples = as_samples(instruments, 2)
+    samples = as_samples(instruments, 2, RATE)
     with mixer.compile_sequence(with_samples(samples, far), RATE, 1, 2, name="far") as cs:
         assert len(cs) == cs.frames == MAX and cs.level == "plain" and cs.info()["ntiles"] == MAX // TILE[2]
         got = cs.render(MAX - 300, 300)

@@ -1,8 +1,8 @@
 """GPU parity of a song made of tracks -- mixer.compile_tracks / CompiledSequence(gains=...) / sh_seq_create_tracks, sh_seq_render_gains --
-against live ``audioop`` on byte slices.  The expected bytes are the reference chain: tests/test_gpu_channels.py's ``oracle`` (the whole
+against live ``audioop`` on byte slices.  The expected bytes are the reference chain: tests/seqref.py's ``mix`` (the whole
 event chain, event after event like mix_at) run ONCE PER TRACK, ``audioop.mul`` by the track's gain (none at exactly 1.0), the shorter
 tracks padded with silence, ``audioop.add`` in track order -- then sliced per window.  Expected bytes never come from the product.  Rate
-8192, instruments of 97 to 600 frames and a song of four tiles that ends mid-lane with one idle tile, as tests/test_gpu_compiled.py has them.
+8192, instruments of 97 to 600 frames and a song of four tiles that ends mid-lane with one idle tile, as tests/seqcases.py has them.
 
 Gain vectors that hold only 0.0 and 1.0 form no product at all (a gain of 1.0 takes no multiply, one of 0.0 skips the track), so there is
 no truncated form for them to differ from: the floor-against-truncation assertion is made for every vector that multiplies."""
@@ -12,41 +12,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests.test_gpu_channels import oracle
-from tests.test_gpu_compiled import HELD, LEVEL_NAME, LEVELS, _ev, in_a_child_under_the_other_alignment_scheme, render_window, song, windows
-from tests.test_gpu_enveloped import _differs
-from tests.test_gpu_looped import LANE, RATE, TILE
-from tests.test_gpu_reversed import as_samples, named, with_samples
-from tests.test_gpu_sequence import _pcm
+from tests.seqcases import (GAINS, LEVEL_NAME, LEVELS, RATE, WithGains, _ev, as_samples, bus_song, in_a_child_under_the_other_alignment_scheme, ints,
+                            master, named, raw_tracks, render_window, song, subs_of, windows, with_samples)
+from tests.seqref import LANE, TILE, differs, mix, pcm
 
 pytestmark = pytest.mark.gpu
-
-GAINS = [(0.5, 1.0, -1.7), (0.0, 1.0, 0.0), (1.0, 1.0, 1.0), (0.999, 2.5, 0.37)]
-
-
-# ---- the oracle ------------------------------------------------------------------------------------------------------------------------
-def subs_of(instruments, tracks, width, nch):
-    """every track on its own, event after event: the one place the event chain is evaluated"""
-    return [oracle(b"", named(instruments, t), width, RATE, nch) for t in tracks]
-
-
-def master(subs, gains, width):
-    """the reference chain behind the sub-mixes: mul (none at 1.0), pad, add, in track order"""
-    total = max([len(s) for s in subs] + [0])
-    out = bytes(total)
-    for sub, g in zip(subs, [1.0] * len(subs) if gains is None else gains):
-        if g != 1.0:
-            sub = audioop.mul(sub, width, g)
-        out = audioop.add(out, sub + bytes(total - len(sub)), width)
-    return out
-
-
-def ints(data, width):
-    if width == 3:
-        a = np.frombuffer(data, dtype=np.uint8).reshape(-1, 3).astype(np.int64)
-        v = a[:, 0] | (a[:, 1] << 8) | (a[:, 2] << 16)
-        return np.where(v >= 1 << 23, v - (1 << 24), v)
-    return np.frombuffer(data, dtype={1: np.int8, 2: "<i2", 4: "<i4"}[width]).astype(np.int64)
 
 
 def full_scale(width):
@@ -58,54 +28,6 @@ def saturates(data, width):
     return hi == full_scale(width) or lo == -full_scale(width) - 1
 
 
-class WithGains:
-    """N.Sequence behind tests/test_gpu_compiled.py's render_window, which calls render(first, n, out, out_sample)"""
-
-    def __init__(self, seq, gains):
-        self.seq, self.gains = seq, gains
-
-    def render(self, a, n, out, out_sample):
-        self.seq.render(a, n, out, out_sample, gains=self.gains)
-
-
-def raw_tracks(N, instruments, tracks, nch, width):
-    """the song through the C entry point: the product's packer makes the table (an input), N.Sequence is sh_seq_create_tracks' thin wrapper"""
-    from synthesizer_amd.sample import Sample
-    samples = as_samples(instruments, width)
-    track = Sample(samplerate=RATE, nchannels=nch, samplewidth=width)
-    bufs, table, segtab, nbytes = track._compile_events(with_samples(samples, [e for t in tracks for e in t]))
-    first = [0]
-    for t in tracks:
-        first.append(first[-1] + len(t))
-    return N.Sequence(bufs, table, segtab, width, nch, nbytes // width, track_first=first), samples
-
-
-# ---- the bus song: three tracks, loud notes of two of them on one another ------------------------------------------------------------------
-_BUS = {}
-
-
-def bus_song(width):
-    """(instruments, tracks, the sub-mixes, total samples), made once.  Mono.  Track 0 and track 1 pile the loud instrument up inside
-    [T + 3 L, 3 T + L) with opposite signs; track 2 is absent from that tile, and tile 3 holds nothing but the last track's note; tile 2 is
-    idle and the song ends mid-lane."""
-    if width in _BUS:
-        return _BUS[width]
-    T, L = TILE[width], LANE[width]
-    rng = np.random.default_rng(900 + width)
-    instruments = [(_pcm(rng, width, HELD[0], 1.0), 1), (_pcm(rng, width, HELD[1], 0.6), 1), (_pcm(rng, width, HELD[2], 0.6), 1)]
-    w0, tail = T + 3 * L, 37 * L + 3
-    tracks = [
-        [_ev(0, 1, 0.8), _ev(T - 300, 0, 0.5), _ev(w0 + 10, 0, 1.7, 200), _ev(w0 + 13, 0, 1.7, 200)],
-        [_ev(w0 - 100, 1, None), _ev(w0 + 10, 0, -1.7, 200), _ev(w0 + 17, 0, -1.7, 200)],
-        [_ev(5, 2, 1.3), _ev(3 * T, 1, 1.2, tail)],
-    ]
-    subs = subs_of(instruments, tracks, width, 1)
-    total = max(len(s) for s in subs) // width
-    assert 3 * T < total < 4 * T and total % L != 0
-    _BUS[width] = (instruments, tracks, subs, total)
-    return _BUS[width]
-
-
 # ---- 1: grouping decides bytes ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("width", [1, 2, 3, 4])
 def test_grouping_decides_bytes(gpu, width):
@@ -114,17 +36,17 @@ def test_grouping_decides_bytes(gpu, width):
     T, L = TILE[width], LANE[width]
     lo, hi = (T + 3 * L) * width, (3 * T + L) * width
     grouped = master(subs, None, width)
-    flat = oracle(b"", named(instruments, [e for t in tracks for e in t]), width, RATE, 1)
+    flat = mix(b"", named(instruments, [e for t in tracks for e in t]), width, RATE, 1)
     assert len(grouped) == len(flat) == total * width
     assert grouped[lo:hi] != flat[lo:hi], "the chain of sub-mixes is the flat list"
     assert saturates(grouped[lo:hi], width) and saturates(flat[lo:hi], width), "nothing saturates"
     assert all(saturates(s[lo:hi], width) for s in subs[:2])   # the two tracks saturate on their own, and the third is absent from their tile
     assert subs[2][T * width:2 * T * width] == bytes(T * width)
-    samples = as_samples(instruments, width)
+    samples = as_samples(instruments, width, RATE)
     with mixer.compile_tracks([with_samples(samples, t) for t in tracks], RATE, 1, width, name="bus") as cs:
         assert cs.ntracks == 3 and cs.frames == total and cs.level == "plain"
         got = bytes(cs.render().view_frame_data())
-        assert got == grouped, "%d bytes differ from the grouped oracle (%d from the flat one)" % (_differs(got, grouped), _differs(got, flat))
+        assert got == grouped, "%d bytes differ from the grouped oracle (%d from the flat one)" % (differs(got, grouped), differs(got, flat))
         assert cs._seq.tracks() == (3, 6)                       # tile 0: all three tracks, tile 1: two, tile 2: none, tile 3: the last
     with mixer.compile_sequence(with_samples(samples, [e for t in tracks for e in t]), RATE, 1, width) as cs:
         assert cs.ntracks is None and cs._seq.tracks() == (0, 0) and bytes(cs.render().view_frame_data()) == flat
@@ -149,12 +71,12 @@ def test_gains_and_stems(gpu, width):
             assert truncated > 0, gains
         if 0.5 in gains:
             assert floored > 0, "no negative product lands on .5"
-    samples = as_samples(instruments, width)
+    samples = as_samples(instruments, width, RATE)
     with mixer.compile_tracks([with_samples(samples, t) for t in tracks], RATE, 1, width) as cs:
         for gains in GAINS:
             want = master(subs, gains, width)
             got = bytes(cs.render(gains=gains).view_frame_data())
-            assert got == want, (gains, _differs(got, want))
+            assert got == want, (gains, differs(got, want))
         assert master(subs, GAINS[0], width) != master(subs, GAINS[3], width) != master(subs, None, width)
         for t, sub in enumerate(subs):
             got = cs.stem(t)
@@ -184,7 +106,7 @@ def test_windows_of_every_level_through_the_entry_point(gpu, level, width):
             assert not idle or exp == bytes((b - a) * width), (a, b)
             for out_sample in (0, 1):
                 got, front, behind = render_window(N, seq if gains is None else WithGains(seq, gains), width, a, b, out_sample)
-                assert got == exp, "gains %s, window [%d, %d) at out_sample %d: %d bytes differ" % (gains, a, b, out_sample, _differs(got, exp))
+                assert got == exp, "gains %s, window [%d, %d) at out_sample %d: %d bytes differ" % (gains, a, b, out_sample, differs(got, exp))
                 assert front == b"\x5a" * 64 and behind == b"\x5a" * 64, (gains, a, b, out_sample)
     seq.free()
 
@@ -197,7 +119,7 @@ def test_windows_of_every_level_at_16_bits_under_the_other_alignment_scheme(gpu)
 def test_a_track_with_no_events_at_all(gpu):
     from synthesizer_amd import mixer
     instruments, tracks, subs, total = bus_song(2)
-    samples = as_samples(instruments, 2)
+    samples = as_samples(instruments, 2, RATE)
     with mixer.compile_tracks([with_samples(samples, t) for t in (tracks[0], [], tracks[1], tracks[2], [])], RATE, 1) as cs:
         assert cs.ntracks == 5 and cs._seq.tracks() == (5, 6)
         for gains in ((0.5, 123.0, 1.0, -1.7, 0.0), (1.0, 0.0, 1.0, 1.0, -3.0)):
@@ -213,14 +135,14 @@ def test_runs_of_one_three_four_five_and_nine_events_in_a_plain_16_bit_tile(gpu)
     same runs in another order, so that each length starts a tile's walk and ends it"""
     from synthesizer_amd import mixer
     rng = np.random.default_rng(41)
-    instruments = [(_pcm(rng, 2, 300, 0.5), 1), (_pcm(rng, 2, 97, 0.9), 1)]
+    instruments = [(pcm(rng, 2, 300, 0.5), 1), (pcm(rng, 2, 97, 0.9), 1)]
     vols = [None, 0.5, 1.7, -1.0, 0.37]
     k = 0
     tracks = []
     for n in (1, 3, 4, 5, 9):
         tracks.append([_ev(40 + 11 * (k + j), (k + j) % 2, vols[(k + j) % 5]) for j in range(n)])
         k += n
-    samples = as_samples(instruments, 2)
+    samples = as_samples(instruments, 2, RATE)
     for order in ((0, 1, 2, 3, 4), (4, 2, 0, 3, 1)):
         dealt = [tracks[i] for i in order]
         subs = subs_of(instruments, dealt, 2, 1)
@@ -236,13 +158,13 @@ def test_runs_of_one_three_four_five_and_nine_events_in_a_plain_16_bit_tile(gpu)
 def test_thirty_two_tracks_of_one_event_each_on_one_tile(gpu, width):
     from synthesizer_amd import mixer
     rng = np.random.default_rng(43 + width)
-    instruments = [(_pcm(rng, width, 300, 0.3), 1), (_pcm(rng, width, 97, 0.2), 1)]
+    instruments = [(pcm(rng, width, 300, 0.3), 1), (pcm(rng, width, 97, 0.2), 1)]
     tracks = [[_ev(7 * t, t % 2, [None, 0.9, -1.0][t % 3])] for t in range(32)]
     gains = [[1.0, 0.0, 0.5, -1.7, 2.5, 0.999, 0.37, 1.0][t % 8] for t in range(32)]
     subs = subs_of(instruments, tracks, width, 1)
     want = master(subs, gains, width)
     assert saturates(want, width)
-    samples = as_samples(instruments, width)
+    samples = as_samples(instruments, width, RATE)
     with mixer.compile_tracks([with_samples(samples, t) for t in tracks], RATE, 1, width) as cs:
         assert cs.ntracks == 32 and cs._seq.tracks() == (32, 32)
         assert bytes(cs.render(gains=gains).view_frame_data()) == want
@@ -255,7 +177,7 @@ def test_thirty_two_tracks_of_one_event_each_on_one_tile(gpu, width):
 def test_one_track_is_compile_sequence_of_the_same_list(gpu, level):
     from synthesizer_amd import mixer
     instruments, events, nch, want, total = song(level, 2)
-    samples = as_samples(instruments, 2)
+    samples = as_samples(instruments, 2, RATE)
     with mixer.compile_tracks([with_samples(samples, events)], RATE, nch) as one, mixer.compile_sequence(with_samples(samples, events), RATE, nch) as flat:
         assert one.ntracks == 1 and flat.ntracks is None and one.level == flat.level == LEVEL_NAME.get(level, level) and one.frames == flat.frames
         assert bytes(one.render().view_frame_data()) == bytes(flat.render().view_frame_data()) == want
@@ -271,7 +193,7 @@ def test_chunks_with_gains_that_change_between_them(gpu, level, width):
     instruments, events, nch, _flat, total = song(level, width)
     tracks = [events[0::3], events[1::3], events[2::3]]
     subs = subs_of(instruments, tracks, width, nch)
-    samples = as_samples(instruments, width)
+    samples = as_samples(instruments, width, RATE)
     fb = width * nch
     g1, g2 = (0.5, 1.0, -1.7), (0.999, 0.0, 2.5)
     w1, w2 = master(subs, g1, width), master(subs, g2, width)
@@ -300,7 +222,7 @@ def test_every_refusal_comes_before_any_launch(gpu, monkeypatch):
     N = gpu
     from synthesizer_amd import mixer
     instruments, tracks, subs, total = bus_song(2)
-    samples = as_samples(instruments, 2)
+    samples = as_samples(instruments, 2, RATE)
     made = []
     real = N.Sequence
     monkeypatch.setattr(N, "Sequence", lambda *a, **k: made.append(a) or real(*a, **k))

@@ -7,8 +7,9 @@ import pytest
 from tests import test_gpu_mix_views as M
 from tests import test_gpu_quantize_views as Q
 from tests import test_gpu_resample_views as R
+from tests.seqcases import ROOT, lists, named, rows_of
+from tests.seqref import discriminates
 from tests.test_gpu_pcm_views import residues
-from tests.test_gpu_sequence_levels import _rows, lists
 from tests.test_ratecv_plan import rc  # noqa: F401  (the fixture: tests/cpu_ratecv.cpp built with g++)
 
 LANE = {1: 4, 2: 8, 3: 4, 4: 4}
@@ -16,7 +17,7 @@ LANE = {1: 4, 2: 8, 3: 4, 4: 4}
 
 def test_the_route_table_names_every_route_and_the_host_plan_agrees(rc):  # noqa: F811
     assert {c[0] for c in R.CASES} == set(R.ROUTES) - {"NONE"}
-    src = M.ROOT / "synthesizer_amd" / "csrc" / "ratecv.hpp"
+    src = ROOT / "synthesizer_amd" / "csrc" / "ratecv.hpp"
     text = src.read_text()
     enum = text[text.index("enum Route {"):]
     enum = enum[:enum.index("};")]
@@ -75,7 +76,7 @@ def test_every_track_list_ends_on_the_last_sample_and_has_an_event_shorter_than_
     ns = len(base) // width
     assert ns % 8 and (ns + M.SURPLUS) * width + 2 * M.PCM_GUARD < 1 << 20
     for lst in (A, B, C_):
-        rows = _rows(lst, sources, width)
+        rows = rows_of(lst, sources, width)
         assert any(d + n == ns for d, n, *_ in rows) and any(0 < n < LANE[width] for _d, n, *_ in rows)
     for kind in ("loop", "rev"):
         instruments, base2, events, want, spans = M.shaped(kind, width)
@@ -83,12 +84,12 @@ def test_every_track_list_ends_on_the_last_sample_and_has_an_event_shorter_than_
         assert any(d + n == ns for d, n in spans) and any(0 < n < LANE[width] for _d, n in spans)
         tile = 2048 if width == 2 else 1024
         assert any(d < tile < d + n for d, n in spans)                                   # across a tile edge
-        full = M.RV.named(instruments, [e + (None, False) if len(e) == 8 else e for e in events])
+        full = named(instruments, [e + (None, False) if len(e) == 8 else e for e in events])
         assert any(e[7] is not None and e[4] is not None for e in full)                # looped and resampled
         assert any(e[6] is not None for e in full) or width == 3                       # an envelope
         if kind == "rev":
             assert any(e[9] and e[8] is not None for e in full)                        # reversed from a region
-            M.RV.discriminates(want, full, width, 2, base)
+            discriminates(want, full, width, M.RATE, 2, "rev", base)
     assert {r % 16 for r in residues(width)} >= {0, width, 8, 16 - width}
 
 
