@@ -773,6 +773,25 @@ typedef struct sh_seq_meter {
 int sh_seq_render_meters(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
                          uint32_t ngains, sh_seq_meter* meters, uint32_t nmeters);
 
+/* The desk's PAN POTS and MASTER FADER: sh_seq_render_gains (with meters != NULL: sh_seq_render_meters) of a STEREO song of tracks with
+ * two more steps, both given when a window is rendered and passed to the kernel BY VALUE -- still one launch, nothing uploaded:
+ *     master = silence; for t in tracks, in order:
+ *         sub = the track's events folded from silence
+ *         if gains[t] != 1.0: sub = audioop.mul(sub, gains[t])                                  (clamp, then floor)
+ *         sub = (fbound(L * pans[2 t]), fbound(R * pans[2 t + 1])) per frame (L, R)             (Sample.stereo of a stereo sample)
+ *         master = audioop.add(master, sub)
+ *     if master_gain != 1.0: master = audioop.mul(master, master_gain)                          (once, behind the last track)
+ * Two roundings per track, the gain first: not one product, and the master's gain on the saturated master.  A factor of exactly 1.0
+ * takes no multiply; a track whose two factors are both exactly 0.0 is skipped like a muted one (all-zero row).  Song sample s takes
+ * the left factor where s is even, whatever sample the window starts on.
+ * pans: 2 * ntracks doubles, left then right per track; NULL with npans == 0: no pan.  gains: NULL with ngains == 0: every gain 1.0.
+ * meters: NULL with nmeters == 0: unmetered, asynchronous as sh_seq_render_gains; otherwise ntracks + 1 rows as sh_seq_render_meters
+ * gives them, a track's row over what the master takes of it (post-fader and post-pan), the master's over the stored bytes.
+ * SH_ERR_INVALID, nothing launched, `out` and `meters` untouched: what sh_seq_render_gains refuses, a handle without tracks, pans on a
+ * song whose nchannels != 2, another ngains, npans or nmeters than the handle's tracks ask for, a factor that is not finite. */
+int sh_seq_render_desk(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                       uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

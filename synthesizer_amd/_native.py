@@ -205,6 +205,8 @@ _SIGNATURES = {
     "sh_seq_render_gains": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32]),
     "sh_seq_get_tracks": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "sh_seq_render_meters": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(SeqMeter), C.c_uint32]),
+    "sh_seq_render_desk": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
+                                     C.c_double, C.POINTER(SeqMeter), C.c_uint32]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),
@@ -463,20 +465,32 @@ class Sequence:
         check(lib().sh_seq_get_tracks(self._h, C.byref(nt), C.byref(nr)))
         return nt.value, nr.value
 
-    def render(self, first_sample: int, nsamples: int, out: "DeviceBuffer", out_sample: int = 0, gains=None, meters: bool = False):
+    def render(self, first_sample: int, nsamples: int, out: "DeviceBuffer", out_sample: int = 0, gains=None, meters: bool = False, pans=None,
+               master=None):
         """``meters=True`` (a song of tracks): sh_seq_render_meters -- the same bytes and, from the same launch, one row per track and one for
-        the master, each ``(peak, sum_squares)`` of per-channel pairs, the sums exact Python ints.  Otherwise None."""
+        the master, each ``(peak, sum_squares)`` of per-channel pairs, the sums exact Python ints.  Otherwise None.
+        ``pans`` (2 * ntracks factors, left then right per track) or ``master`` (a gain) given: sh_seq_render_desk, with or without meters."""
+        def doubles(v):
+            return None if v is None else (C.c_double * max(1, len(v)))(*v)
+
+        def count(v):
+            return 0 if v is None else len(v)
+        desk = pans is not None or master is not None
+        rows, nrows = None, 0
         if meters:
-            nt = self.tracks()[0]
-            rows = (SeqMeter * (nt + 1))()
-            g = None if gains is None else (C.c_double * max(1, len(gains)))(*gains)
-            check(lib().sh_seq_render_meters(self._h, first_sample, nsamples, out.handle, out_sample, g, 0 if gains is None else len(gains), rows, nt + 1))
-            return [((r.peak[0], r.peak[1]), ((r.sq_hi[0] << 32) + r.sq_lo[0], (r.sq_hi[1] << 32) + r.sq_lo[1])) for r in rows]
-        if gains is None:
+            nrows = self.tracks()[0] + 1
+            rows = (SeqMeter * nrows)()
+        if desk:
+            check(lib().sh_seq_render_desk(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans), count(pans),
+                                           1.0 if master is None else master, rows, nrows))
+        elif meters:
+            check(lib().sh_seq_render_meters(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), rows, nrows))
+        elif gains is None:
             check(lib().sh_seq_render(self._h, first_sample, nsamples, out.handle, out_sample))
         else:
-            g = (C.c_double * max(1, len(gains)))(*gains)
-            check(lib().sh_seq_render_gains(self._h, first_sample, nsamples, out.handle, out_sample, g, len(gains)))
+            check(lib().sh_seq_render_gains(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), len(gains)))
+        if meters:
+            return [((r.peak[0], r.peak[1]), ((r.sq_hi[0] << 32) + r.sq_lo[0], (r.sq_hi[1] << 32) + r.sq_lo[1])) for r in rows]
 
     def free(self) -> None:
         if self._h:

@@ -54,7 +54,10 @@
 // reduces one row of levels per track, post-fader, and the same launch one for the master, into a table the handle owns
 // (sh_seq_render_meters; seqmeter.hpp); seq_window_bus is what a window kernel does with either bus.  On the host one launcher,
 // seq_window_launch, forwards the bus (none, SeqBus or SeqBusM) as the kernels' trailing pack, and seq_with_level turns the level a
-// handle holds into a template argument.
+// handle holds into a template argument.  The DESK buses, SeqBusD and SeqBusDM, are the two buses again with a pan pot per track and a
+// master fader, by value in the kernel arguments like the gains (sh_seq_render_desk): in seq_runs the sub-mix by its gain, THEN by its
+// pan factors (even samples the left one, odd ones the right one: a stereo sample's Sample.stereo), then the hook and the add; behind the
+// last run the master by the master's gain, once, in front of its meter row and the store.
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
@@ -868,20 +871,69 @@ struct SeqBus {
 // kernel-argument offsets and the instructions they had; one SeqBus for BUS = true.
 static_assert(sizeof(shq::Run) == 8 && sizeof(SeqGains) == 256, "a run is one 8-byte scalar load, the gains 256 bytes of kernel arguments");
 
+// The DESK (sh_seq_render_desk): a pan pot per track and a master fader on either bus, by value in the kernel arguments as the gains
+// are and read at wave-uniform indices as they are -- 520 more bytes of arguments, nothing uploaded.  pan[2 t] and pan[2 t + 1]: what
+// Sample.stereo(left, right) of a STEREO sample takes, applied to track t's sub-mix BEHIND its gain (two roundings, not one product):
+// even samples fbound(x * left), odd ones fbound(x * right); a factor of exactly 1.0: none; both exactly 0.0: the track's events are
+// not read, as at a gain of 0.0.  master: audioop.mul of the saturated master, once, behind the last track; exactly 1.0: none.
+struct SeqDesk {
+    double pan[2 * shq::MAX_TRACKS];
+    double master;
+};
+struct SeqBusD : SeqBus, SeqDesk {};
+template <typename Bus> constexpr bool SEQ_DESK = std::is_base_of<SeqDesk, Bus>::value;
+static_assert(sizeof(SeqDesk) == 520 && sizeof(SeqBusD) == sizeof(SeqBus) + sizeof(SeqDesk), "the desk: 520 bytes of kernel arguments behind the bus");
+
 // a lane's accumulator: eight packed samples at 16 bits, four 64-bit sums at the other widths
 template <int WIDTH> struct SeqAcc { typedef llong4v type; };
 template <> struct SeqAcc<2> { typedef short8v type; };
 
-// The runs of tile k, written once for the three templates and both buses: the events from e on, run by run.  walk(e, e1, sub): the
-// schedule of the kernel, events [e, e1) into sub; hook(sub, track): what else a bus does with a track's post-fader samples (the metering
-// bus: its row).  Everything about a run is uniform, and a run lists at least one event.
-template <int WIDTH, typename Walk, typename Hook>
-__device__ __forceinline__ void seq_runs(const SeqBus& bus, uint32_t k, uint32_t e, typename SeqAcc<WIDTH>::type& acc, Walk walk, Hook hook) {
+// a track's pan step and the master's gain on a lane's samples: seq_scale8's arithmetic at 16 bits, seq_mul_add_w's at widths 1, 3, 4.
+// Lanes start on even song samples, so sample j of a lane is a left one where j is even, whatever sample the window starts on.
+__device__ __forceinline__ short8v seq_pan8(short8v x, const double left, const double right) {
+    if (left != 1.0) {                                        // (uniform)
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) x[j] = (short)fbound((double)x[j] * left, Lim<short>::lo, Lim<short>::hi);
+    }
+    if (right != 1.0) {
+#pragma unroll
+        for (int j = 1; j < 8; j += 2) x[j] = (short)fbound((double)x[j] * right, Lim<short>::lo, Lim<short>::hi);
+    }
+    return x;
+}
+
+template <int WIDTH>
+__device__ __forceinline__ long long seq_scale_w(const long long x, const double factor) {
+    return factor != 1.0 ? (long long)fbound((double)x * factor, (double)SEQ_LO<WIDTH>, (double)SEQ_HI<WIDTH>) : x;
+}
+
+template <int WIDTH>
+__device__ __forceinline__ void seq_master(typename SeqAcc<WIDTH>::type& acc, const double gain) {
+    if constexpr (WIDTH == 2) {
+        acc = seq_scale8(acc, gain);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = seq_scale_w<WIDTH>(acc[j], gain);
+    }
+}
+
+// The runs of tile k, written once for the three templates and every bus: the events from e on, run by run.  walk(e, e1, sub): the
+// schedule of the kernel, events [e, e1) into sub; hook(sub, track): what else a bus does with a track's samples as the master takes them,
+// post-fader and (a desk bus) post-pan (the metering buses: its row).  Everything about a run is uniform, and a run lists at least one event.
+template <int WIDTH, typename Bus, typename Walk, typename Hook>
+__device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e, typename SeqAcc<WIDTH>::type& acc, Walk walk, Hook hook) {
     const uint32_t r1 = bus.rfirst[k + 1];
     for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {
         const shq::Run run = bus.runs[r];
         const double g = bus.gains.g[run.track];
-        if (g == 0.0) {
+        double left = 1.0, right = 1.0;
+        bool silent = g == 0.0;
+        if constexpr (SEQ_DESK<Bus>) {
+            left = bus.pan[2 * run.track];
+            right = bus.pan[2 * run.track + 1];
+            silent = silent || (left == 0.0 && right == 0.0);
+        }
+        if (silent) {
             e = run.end;
             continue;
         }
@@ -889,6 +941,7 @@ __device__ __forceinline__ void seq_runs(const SeqBus& bus, uint32_t k, uint32_t
             short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
             walk(e, run.end, sub);
             sub = seq_scale8(sub, g);                         // post-fader: what the master takes of the track
+            if constexpr (SEQ_DESK<Bus>) sub = seq_pan8(sub, left, right);
             hook(sub, run.track);
             acc = __builtin_elementwise_add_sat(acc, sub);
         } else {
@@ -897,7 +950,12 @@ __device__ __forceinline__ void seq_runs(const SeqBus& bus, uint32_t k, uint32_t
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 long long x = sub[j];
-                acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, g);
+                if constexpr (SEQ_DESK<Bus>) {                // the gain, then the pan: two roundings
+                    x = seq_scale_w<WIDTH>(x, g);
+                    acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, j & 1 ? right : left);
+                } else {
+                    acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, g);
+                }
                 sub[j] = x;
             }
             hook(sub, run.track);
@@ -921,8 +979,10 @@ struct SeqBusM : SeqBus {
     shmt::Row* meters;                     // ntracks + 1 rows, zeroed on the stream in front of the launch; row ntracks: the master
     uint32_t  ntracks, nch;               // nch: the song's channels (2: sample s is channel s & 1; otherwise all are channel 0)
 };
+struct SeqBusDM : SeqBusM, SeqDesk {};    // the desk with meters: a track's row post-fader and post-pan, the master's over the stored bytes
 template <typename... Bus> struct SeqMetered : std::false_type {};
 template <> struct SeqMetered<SeqBusM> : std::true_type {};
+template <> struct SeqMetered<SeqBusDM> : std::true_type {};
 
 // the workgroup's row table, zeroed: every lane of the workgroup calls it (a barrier)
 __device__ __forceinline__ shmt::Row* seq_meter_begin() {
@@ -977,32 +1037,32 @@ __device__ __forceinline__ void seq_meter_end(const shmt::Row* table, const SeqB
     if (WIDE) atomicAdd(reinterpret_cast<unsigned long long*>(&g->sq_hi[c]), (unsigned long long)table[row].sq_hi[c]);
 }
 
-// What a window kernel does where it has a bus, once for the three templates: the runs of tile k into acc, then store().  The plain bus:
-// a lane that seq_window_lane kept.  s0, lo and hi, which only the metering bus needs, are ignored: one call serves both overloads.
-template <int WIDTH, typename Walk, typename Store>
-__device__ __forceinline__ void seq_window_bus(const SeqBus& bus, uint32_t k, uint32_t e, uint32_t, uint32_t, uint32_t,
-                                               typename SeqAcc<WIDTH>::type& acc, Walk walk, Store store) {
-    seq_runs<WIDTH>(bus, k, e, acc, walk, [](const typename SeqAcc<WIDTH>::type&, uint32_t) {});
-    store();
-}
-
-// The metering bus: EVERY lane of a workgroup that seq_window_tile kept, the rows of the tracks from seq_runs' hook and the master's row
+// What a window kernel does where it has a bus, once for the three templates: the runs of tile k into acc, (a desk bus) the master's gain,
+// then store().  A plain bus: a lane that seq_window_lane kept; s0, lo and hi, which only a metering bus needs, are ignored.
+// A metering bus: EVERY lane of a workgroup that seq_window_tile kept, the rows of the tracks from seq_runs' hook and the master's row
 // in front of the store, the table's barriers around everything.
-template <int WIDTH, typename Walk, typename Store>
-__device__ __forceinline__ void seq_window_bus(const SeqBusM& bus, uint32_t k, uint32_t e, uint32_t s0, uint32_t lo, uint32_t hi,
+template <int WIDTH, typename Bus, typename Walk, typename Store>
+__device__ __forceinline__ void seq_window_bus(const Bus& bus, uint32_t k, uint32_t e, uint32_t s0, uint32_t lo, uint32_t hi,
                                                typename SeqAcc<WIDTH>::type& acc, Walk walk, Store store) {
-    constexpr bool WIDE = WIDTH >= 3;
-    constexpr int N = SEQ_LANE<WIDTH>;
-    shmt::Row* table = seq_meter_begin();
-    const bool stereo = bus.nch == 2;
-    if (__builtin_amdgcn_ballot_w64(s0 < hi && s0 + N > lo)) {                    // (uniform: a wave with a lane in the window)
-        seq_runs<WIDTH>(bus, k, e, acc, walk, [&](const typename SeqAcc<WIDTH>::type& sub, uint32_t track) {
-            seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(sub, s0, lo, hi, bus.nch), stereo, table + track);
-        });
-        seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
+    if constexpr (!SeqMetered<Bus>::value) {
+        seq_runs<WIDTH>(bus, k, e, acc, walk, [](const typename SeqAcc<WIDTH>::type&, uint32_t) {});
+        if constexpr (SEQ_DESK<Bus>) seq_master<WIDTH>(acc, bus.master);
         store();
+    } else {
+        constexpr bool WIDE = WIDTH >= 3;
+        constexpr int N = SEQ_LANE<WIDTH>;
+        shmt::Row* table = seq_meter_begin();
+        const bool stereo = bus.nch == 2;
+        if (__builtin_amdgcn_ballot_w64(s0 < hi && s0 + N > lo)) {                    // (uniform: a wave with a lane in the window)
+            seq_runs<WIDTH>(bus, k, e, acc, walk, [&](const typename SeqAcc<WIDTH>::type& sub, uint32_t track) {
+                seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(sub, s0, lo, hi, bus.nch), stereo, table + track);
+            });
+            if constexpr (SEQ_DESK<Bus>) seq_master<WIDTH>(acc, bus.master);
+            seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
+            store();
+        }
+        seq_meter_end<WIDE>(table, bus);
     }
-    seq_meter_end<WIDE>(table, bus);
 }
 
 // PLAIN at 16 bits: k_seq_plain16's schedule
@@ -1487,8 +1547,9 @@ void seq_with_level(int level, F f) {
 }
 
 // Which window kernel: the width, at 16 bits the way misaligned event samples are read and whether the biased base lies on a 16-byte
-// boundary.  bus: nothing (a flat list), a SeqBus (a song of tracks: the same kernels with the bus, the gains by value) or a SeqBusM (the
-// metering bus: the rows go to the handle's table), forwarded as the kernels' trailing pack.
+// boundary.  bus: nothing (a flat list), a SeqBus (a song of tracks: the same kernels with the bus, the gains by value), a SeqBusM (the
+// metering bus: the rows go to the handle's table) or one of the two with the desk (SeqBusD, SeqBusDM: pans and the master's gain by
+// value as well), forwarded as the kernels' trailing pack.
 template <int LEVEL, typename... Bus>
 void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out, const Bus&... bus) {
     typedef typename SeqRec<LEVEL>::type Rec;
@@ -1627,10 +1688,23 @@ int seq_gains(const char* fn, const double* gains, uint32_t ngains, SeqGains& ou
     return SH_OK;
 }
 
-// sh_seq_render (gains NULL: every track at 1.0), sh_seq_render_gains and sh_seq_render_meters (meters: ntracks + 1 host rows, the handle
-// has tracks) behind their names
+// the desk of a render as the kernels take it: the caller's npans == 2 * ntracks factors (NULL: no pan), every one and the master's gain
+// finite; (1.0, 1.0) for every other track
+int seq_desk(const char* fn, const double* pans, uint32_t npans, double master_gain, SeqDesk& out) {
+    for (uint32_t i = 0; i < 2 * shq::MAX_TRACKS; ++i) out.pan[i] = 1.0;
+    for (uint32_t i = 0; pans && i < npans; ++i) {
+        if (!isfinite(pans[i])) return sh::set_error(SH_ERR_INVALID, "%s: pan %u: %s factor is not finite", fn, i / 2, i % 2 ? "right" : "left");
+        out.pan[i] = pans[i];
+    }
+    if (!isfinite(master_gain)) return sh::set_error(SH_ERR_INVALID, "%s: master gain is not finite", fn);
+    out.master = master_gain;
+    return SH_OK;
+}
+
+// sh_seq_render (gains NULL: every track at 1.0), sh_seq_render_gains, sh_seq_render_meters (meters: ntracks + 1 host rows, the handle
+// has tracks) and sh_seq_render_desk (desk: the pans and the master's gain, the handle has tracks; with or without meters) behind their names
 int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains,
-               sh_seq_meter* meters = nullptr) {
+               sh_seq_meter* meters = nullptr, const SeqDesk* desk = nullptr) {
     static_assert(sizeof(sh_seq_meter) == sizeof(shmt::Row) && offsetof(sh_seq_meter, sq_hi) == offsetof(shmt::Row, sq_hi) &&
                   offsetof(sh_seq_meter, sq_lo) == offsetof(shmt::Row, sq_lo), "sh_seq_meter is shmt::Row");
     const size_t b_meters = meters ? ((size_t)seq->ntracks + 1) * sizeof(shmt::Row) : 0;
@@ -1655,7 +1729,8 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
     hipStream_t st = sh::state().stream;
     char* table = (char*)seq->block + seq->at_meters;         // (the handle's: one metered render at a time)
     if (meters) SH_HIP(hipMemsetAsync(table, 0, b_meters, st));
-    SeqBusM bus{};                                            // (a song of tracks; its SeqBus part is the plain bus)
+    SeqBusDM bus{};                                           // (a song of tracks; its SeqBusM part is the metering bus, whose SeqBus part is the plain one)
+    if (desk) static_cast<SeqDesk&>(bus) = *desk;
     if (seq->ntracks) {
         bus.rfirst = (const uint32_t*)((const char*)seq->block + seq->at_rfirst);
         bus.runs = (const shq::Run*)((const char*)seq->block + seq->at_runs);
@@ -1668,8 +1743,15 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
     seq_with_level(seq->level, [&](auto L) {
         constexpr int LEVEL = decltype(L)::value;
         if (!seq->ntracks) seq_window_launch<LEVEL>(seq, grid, st, lo, hi, biased);
-        else if (!meters) seq_window_launch<LEVEL, SeqBus>(seq, grid, st, lo, hi, biased, bus);
-        else seq_window_launch<LEVEL, SeqBusM>(seq, grid, st, lo, hi, biased, bus);
+        else if (!desk && !meters) seq_window_launch<LEVEL, SeqBus>(seq, grid, st, lo, hi, biased, bus);
+        else if (!desk) seq_window_launch<LEVEL, SeqBusM>(seq, grid, st, lo, hi, biased, bus);
+        else if (meters) seq_window_launch<LEVEL, SeqBusDM>(seq, grid, st, lo, hi, biased, bus);
+        else {
+            SeqBusD plain{};
+            static_cast<SeqBus&>(plain) = bus;
+            static_cast<SeqDesk&>(plain) = bus;
+            seq_window_launch<LEVEL, SeqBusD>(seq, grid, st, lo, hi, biased, plain);
+        }
     });
     SH_CHECK_LAUNCH(fn);
     if (meters) {                                             // synchronous, as sh_pcm_stats: one small copy, one wait
@@ -1729,6 +1811,24 @@ int sh_seq_render_meters(const sh_seq* seq, size_t first_sample, size_t nsamples
     const int rc = seq_gains(fn, gains, ngains, g);
     if (rc) return rc;
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters);
+}
+
+int sh_seq_render_desk(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                       uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_seq_render_desk";
+    if (!seq || !out || (!gains && ngains) || (!pans && npans) || (!meters && nmeters)) return seq_null(fn);
+    if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
+    if (pans && seq->nchannels != 2) return sh::set_error(SH_ERR_INVALID, "%s: pans need a stereo song, this one has %d channels", fn, seq->nchannels);
+    if (gains && ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
+    if (pans && npans != 2 * seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u pan factors for %u tracks (two each)", fn, npans, seq->ntracks);
+    if (meters && nmeters != seq->ntracks + 1) return sh::set_error(SH_ERR_INVALID, "%s: %u rows for %u tracks and the master", fn, nmeters, seq->ntracks);
+    SeqGains g;
+    SeqDesk d;
+    int rc = seq_gains(fn, gains, ngains, g);
+    if (!rc) rc = seq_desk(fn, pans, npans, master_gain, d);
+    if (rc) return rc;
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d);
 }
 
 int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns) {

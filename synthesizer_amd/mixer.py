@@ -668,9 +668,28 @@ class CompiledSequence:
     ``gains`` given when a window is RENDERED: ``render``, ``render_into`` and ``chunks`` take ``gains=`` (one finite float per
     track; None: all 1.0) and ``stem`` renders one track alone.  Mute, solo and fader moves compile nothing, upload nothing and
     materialise no track: still one launch per window.
+    The desk's PAN POTS and MASTER FADER, of a stereo song of tracks: the same calls take ``pans=`` (one entry per track: None, a number
+    -1 .. 1 -- ``Sample.pan``'s factors ``((1 - p) / 2, (1 + p) / 2)``, centre halves both sides -- or a pair ``(left_factor,
+    right_factor)`` of finite floats) and ``master=`` (one finite float), and the chain is, byte for byte, ::
+
+        master = Sample(...)
+        for t, events in enumerate(tracks):
+            sub = sequence(events, ...)
+            if gains[t] != 1.0:
+                sub.amplify(gains[t])                       # audioop.mul: clamp, then floor
+            if pans[t] is not None:
+                sub.stereo(lf_t, rf_t)                      # a stereo sample's balance: (fbound(L * lf), fbound(R * rf))
+            master.mix(sub)                                 # audioop.add, saturating
+        if master_gain != 1.0:
+            master.amplify(master_gain)                     # once, behind the last track
+
+    -- two roundings per track, the gain first (not one product ``g * lf``, not the pan first), and the master's gain on the
+    saturated master, not on each track.  A factor of exactly 1.0 takes no multiply: ``None`` and ``(1.0, 1.0)`` give the same bytes.
+    Still one launch per window, nothing uploaded; ``stem`` stays at gain 1.0 without pan or master.
     The desk's METERS: ``render``, ``render_into`` and ``chunks`` take ``meters=True`` and give, from that same launch, a
     ``SongLevels`` -- the levels of every track post-fader and of the master in the window just rendered, exact in integers -- beside
-    the same bytes.  A handle serves one metered render at a time.  Not built: pre-fader meters (they would read a muted track's
+    the same bytes; with ``pans`` a track's levels are post-fader and post-pan, with ``master`` the master's are over the bytes
+    returned.  A handle serves one metered render at a time.  Not built: pre-fader meters (they would read a muted track's
     events), meters of a song without tracks, clip counters."""
 
     MAX_TRACKS = 32
@@ -746,6 +765,60 @@ class CompiledSequence:
             raise ValueError("CompiledSequence: meters need a song of tracks (compile_tracks); this one has none")
         return bool(meters)
 
+    def _pans(self, pans) -> Optional[list]:
+        """``pans`` as render hands them on: None (no track has a pan step), or ``2 * ntracks`` finite floats, left then right per track,
+        (1.0, 1.0) where the entry is None -- checked before anything is launched"""
+        if pans is None:
+            return None
+        if self.ntracks is None:
+            raise ValueError("CompiledSequence: pans need a song of tracks (compile_tracks); this one has none")
+        if self.nchannels != 2:
+            raise ValueError("CompiledSequence: pans need a stereo song, this one has %d channels" % self.nchannels)
+        if isinstance(pans, (str, bytes)) or not hasattr(pans, "__len__"):
+            raise ValueError("CompiledSequence: pans is a sequence, one entry per track")
+        if len(pans) != self.ntracks:
+            raise ValueError("CompiledSequence: %d pans for %d tracks" % (len(pans), self.ntracks))
+        out = []
+        for t, pan in enumerate(pans):
+            if pan is None:
+                factors = (1.0, 1.0)
+            elif isinstance(pan, (tuple, list)):
+                try:
+                    factors = (float(pan[0]), float(pan[1])) if len(pan) == 2 else None
+                except (TypeError, ValueError):
+                    factors = None
+                if factors is None or not (math.isfinite(factors[0]) and math.isfinite(factors[1])):
+                    raise ValueError("CompiledSequence: pan %d is not a pair (left_factor, right_factor) of finite numbers" % t)
+            else:
+                try:
+                    pan = float(pan)
+                except (TypeError, ValueError):
+                    raise ValueError("CompiledSequence: pan %d is None, a number or a pair (left_factor, right_factor)" % t) from None
+                if not -1.0 <= pan <= 1.0:
+                    raise ValueError("CompiledSequence: pan %d must be between -1 and 1" % t)
+                factors = ((1.0 - pan) / 2.0, (1.0 + pan) / 2.0)    # Sample.pan: Python floats, on the host
+            out.extend(factors)
+        return None if all(f == 1.0 for f in out) else out
+
+    def _master(self, master) -> Optional[float]:
+        """``master`` as render hands it on: None (no step: None or exactly 1.0) or a finite float -- checked before anything is launched"""
+        if master is None:
+            return None
+        if self.ntracks is None:
+            raise ValueError("CompiledSequence: master needs a song of tracks (compile_tracks); this one has none")
+        try:
+            master = float(master)
+        except (TypeError, ValueError):
+            raise ValueError("CompiledSequence: master is a number") from None
+        if not math.isfinite(master):
+            raise ValueError("CompiledSequence: master is not finite")
+        return None if master == 1.0 else master
+
+    @staticmethod
+    def _desk(pans, master) -> dict:
+        """the keywords of the desk for N.Sequence.render: none at all where neither step is asked for (the entry points there were)"""
+        return {} if pans is None and master is None else {"pans": pans, "master": master}
+
     def _levels(self, rows, nframes: int) -> SongLevels:
         if rows is None:                                        # an empty window: nothing was launched, every level 0
             rows = [((0, 0), (0, 0))] * (self.ntracks + 1)
@@ -777,43 +850,49 @@ class CompiledSequence:
         return start_frame, nframes
 
     def render_into(self, buf: N.DeviceBuffer, byte_offset: int, start_frame: int, nframes: int, gains: Optional[Sequence[float]] = None,
-                    meters: bool = False) -> Optional[SongLevels]:
+                    meters: bool = False, pans: Optional[Sequence] = None, master: Optional[float] = None) -> Optional[SongLevels]:
         """Frames ``[start_frame, start_frame + nframes)`` of the song into ``buf`` from ``byte_offset`` (a whole number of samples) on:
         every byte of the range is written, whatever ``buf`` held.  ``gains``: one per track of a song of tracks.  ``meters=True``: the
-        same bytes, and the window's ``SongLevels`` returned, from the same launch (the call then waits for it)."""
+        same bytes, and the window's ``SongLevels`` returned, from the same launch (the call then waits for it).  ``pans``, ``master``:
+        a pan per track and the master's gain of a stereo song of tracks (``CompiledSequence``), in that same launch."""
         seq = self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
+        desk = self._desk(self._pans(pans), self._master(master))
         start_frame, nframes = self._range(start_frame, nframes)
         if byte_offset < 0 or byte_offset % self.samplewidth:
             raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
         if meters:
             rows = None
             if nframes:
-                rows = seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains, meters=True)
+                rows = seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains, meters=True,
+                                  **desk)
             return self._levels(rows, nframes)
         if nframes:
-            if gains is None:
+            if gains is None and not desk:
                 seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth)
             else:
-                seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains)
+                seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains, **desk)
         return None
 
-    def render(self, start_frame: int = 0, nframes: Optional[int] = None, gains: Optional[Sequence[float]] = None, meters: bool = False):
+    def render(self, start_frame: int = 0, nframes: Optional[int] = None, gains: Optional[Sequence[float]] = None, meters: bool = False,
+               pans: Optional[Sequence] = None, master: Optional[float] = None):
         """A new ``Sample``: frames ``[start_frame, start_frame + nframes)`` of the song; ``nframes`` None: to the end.  ``gains``: one
-        per track of a song of tracks (None: all 1.0).  ``meters=True``: ``(Sample, SongLevels)``, both from the one launch."""
+        per track of a song of tracks (None: all 1.0).  ``meters=True``: ``(Sample, SongLevels)``, both from the one launch.  ``pans``:
+        one entry per track of a stereo song of tracks (None, a number -1 .. 1 or a pair of factors); ``master``: the master's gain."""
         self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
+        self._pans(pans), self._master(master)                 # (checked here as well: before the buffer is made)
         start_frame, nframes = self._range(start_frame, nframes)
         out = Sample(name=self.name, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth)
         levels = None
         if nframes:
             buf = N.DeviceBuffer(nframes * self._fb)
             if meters:
-                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=True)
+                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=True, pans=pans, master=master)
             else:
-                self.render_into(buf, 0, start_frame, nframes, gains=gains)
+                self.render_into(buf, 0, start_frame, nframes, gains=gains, pans=pans, master=master)
             out._set_device(buf, nframes * self._fb)
         if meters:
             return out, levels if levels is not None else self._levels(None, 0)
@@ -829,20 +908,22 @@ class CompiledSequence:
             raise ValueError("CompiledSequence: track %d outside the song's %d tracks" % (track, self.ntracks))
         return self.render(start_frame, nframes, gains=[1.0 if t == track else 0.0 for t in range(self.ntracks)])
 
-    def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None, meters: bool = False) -> Generator:
-        """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter.  ``gains``: as ``render``'s.
-        ``meters=True``: ``(Sample, SongLevels)`` pairs."""
+    def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None, meters: bool = False, pans: Optional[Sequence] = None,
+               master: Optional[float] = None) -> Generator:
+        """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter.  ``gains``, ``pans``, ``master``: as
+        ``render``'s.  ``meters=True``: ``(Sample, SongLevels)`` pairs."""
         chunk_frames = int(chunk_frames)
         if chunk_frames <= 0:
             raise ValueError("CompiledSequence: chunk_frames must be positive")
         self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
+        self._pans(pans), self._master(master)
         for at in range(0, self.frames, chunk_frames):
             if meters:
-                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=True)
+                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=True, pans=pans, master=master)
             else:
-                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains)
+                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, pans=pans, master=master)
 
     def close(self) -> None:
         if self._seq is not None:
@@ -875,7 +956,10 @@ def compile_tracks(tracks: Sequence[Sequence[tuple]], samplerate: int, nchannels
     exactly what ``sequence`` takes and checked as ``sequence`` checks it, before anything reaches the device -- an error names the track
     and the event's index in its own list.  The song is as long as its longest track.  Every track is folded on its own and the tracks are
     mixed in order, each at a gain given when a window is rendered (``CompiledSequence``): ``render(gains=...)``, ``render_into``,
-    ``chunks`` and ``stem`` mute, solo and balance the tracks in the one launch a window takes, with nothing compiled again."""
+    ``chunks`` and ``stem`` mute, solo and balance the tracks in the one launch a window takes, with nothing compiled again.  A stereo
+    song's tracks have a pan pot each and the song a master fader, given the same way: ``render(gains=..., pans=..., master=...)`` is
+    ``sub.amplify(gain)``, then ``sub.stereo(left_factor, right_factor)``, per track, the saturating ``mix`` in track order and one
+    ``master.amplify(master_gain)`` behind the last track (``CompiledSequence`` has the chain)."""
     return CompiledSequence(None, samplerate, nchannels, samplewidth, name, tracks=tracks)
 
 

@@ -82,7 +82,13 @@ runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequ
 medians, of the whole song and per window of 4096 frames, for: (a) render(gains=), the path without meters; (b) render(gains=,
 meters=True), the rows from the same launch; (c) what a caller did before -- render(gains=), then stem, amplify and the Sample's peak and
 sum-of-squares statistics for each of the 8 tracks, then the same on the master -- held to (b)'s rows first, as (b)'s bytes are to (a)'s.
---meters-trace NEVENTS: twenty whole-song renders each of (a) and (b) of the first song and nothing else, for rocprofv3 --kernel-trace."""
+--meters-trace NEVENTS: twenty whole-song renders each of (a) and (b) of the first song and nothing else, for rocprofv3 --kernel-trace.
+
+--desk: the stereo chan song of --meters (8 tracks, 4096 / 32 768 notes) with a pan pot per track and a master fader.  Wall time with a
+device synchronise, medians, of the whole song and per window of 4096 frames, for: (a) render(gains=, pans=, master=), the one launch;
+(b) the caller's way without it -- eight stems, each amplified and balanced (Sample.stereo), mixed in track order, the mix amplified --
+held to (a)'s bytes first; (c) render(gains=) alone, the launch (a) adds its two steps to.  On a tree without pans= only (c) runs:
+SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequence_ab.py --desk is the parent's own figure for (c)."""
 import audioop
 import os
 import sys
@@ -91,8 +97,8 @@ from pathlib import Path
 
 import numpy as np
 
-# --plan's yardstick is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
-sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
+# the yardstick of --plan, --tracks and --desk is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
+sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
 from synthesizer_amd import _native as N  # noqa: E402
 from synthesizer_amd import mixer  # noqa: E402
 from synthesizer_amd.sample import Sample  # noqa: E402
@@ -1071,6 +1077,76 @@ def meters_main():
             bus.close()
 
 
+DESK_PANS = (0.3, None, (1.5, 0.25), -1.0, (0.999, 0.37), 0.0, None, -0.37)
+DESK_MASTER = 0.7
+
+
+def desk_main():
+    """--desk: a pan per track and a master fader in the render's own launch.  (a) render(gains=, pans=, master=); (b) what a caller did
+    without them: eight stems, amplify, stereo, mix, amplify -- held to (a)'s bytes first; (c) render(gains=) alone.  Wall time with a
+    device synchronise, medians; whole song and 4096-frame windows.  A tree whose render has no pans= runs (c) alone."""
+    import inspect
+    N.ensure_init(0)
+    info = N.device_info()
+    has = "pans" in inspect.signature(mixer.CompiledSequence.render).parameters
+    print("sequence_desk_ab: SYNTHHIP_SEQ_ALIGN=%s  %s  pans= and master=: %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"],
+                                                                                "yes" if has else "no (the yardstick: (c) alone)"), flush=True)
+    win, ntracks = 4096, len(TRACK_GAINS)
+    factors = [None if p is None else pan_factors(p) for p in DESK_PANS]
+    for nevents in (4096, 32768):
+        what, nch, evs = meters_songs(nevents)[0]
+        fb = nch * WIDTH
+        bus = mixer.compile_tracks([evs[t::ntracks] for t in range(ntracks)], RATE, nch, WIDTH)
+        frames = bus.frames
+        out = N.DeviceBuffer(frames * fb + 16)
+        wins = list(range(0, (frames - 3) // win, 16))
+
+        def stream(render):
+            for k in wins:
+                render(k * win, win)
+                N.sync()
+
+        c_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, gains=TRACK_GAINS), 2, 15)
+        c_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, gains=TRACK_GAINS))
+        c_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, gains=TRACK_GAINS)), 1, 5) / len(wins)
+        fmt = lambda v: " ".join("%.4f" % x for x in v)    # noqa: E731
+        head = "desk song 120 s, %5d events, %s, %d tracks, level %s, %d frames   " % (nevents, what, ntracks, bus.level, frames)
+        tail = "(c) render(gains=): whole song, wall with a synchronise, median %.4f ms   between two events on the stream, five medians of 15: %s ms   " \
+               "a window of %d frames, wall %.4f ms" % (c_whole, fmt(c_dev), win, c_win)
+        if not has:
+            print(head + tail, flush=True)
+            bus.close()
+            continue
+
+        def caller(a, n):
+            """(b): the window as a caller made it with stems"""
+            master = Sample(samplerate=RATE, nchannels=nch, samplewidth=WIDTH)
+            for t, g in enumerate(TRACK_GAINS):
+                sub = bus.stem(t, a, n)
+                if g != 1.0:
+                    sub.amplify(g)
+                if factors[t] is not None:
+                    sub.stereo(*factors[t])
+                master.mix(sub)
+            return master.amplify(DESK_MASTER)
+
+        desk = dict(gains=TRACK_GAINS, pans=DESK_PANS, master=DESK_MASTER)
+        mid = (frames // 2) // win * win
+        parity = bytes(bus.render(**desk).view_frame_data()) == bytes(caller(0, frames).view_frame_data()) and \
+            bytes(bus.render(mid + 3, win, **desk).view_frame_data()) == bytes(caller(mid + 3, win).view_frame_data())
+        a_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, **desk), 2, 15)
+        a_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, **desk))
+        a_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, **desk)), 1, 5) / len(wins)
+        b_whole = median_wall(lambda: caller(0, frames), 1, 5)
+        b_win = median_wall(lambda: stream(caller), 1, 3) / len(wins)
+        print(head + "(a) render(gains=, pans=, master=): whole song, wall with a synchronise, median %.4f ms   between two events on the stream, five "
+              "medians of 15: %s ms   a window, wall %.4f ms   (b) 8 stems, amplify, stereo, mix, amplify: whole song, wall %.3f ms   a window, wall "
+              "%.3f ms   %s   (a) / (b) whole %.4f, window %.4f   (a) / (c) whole %.3f, window %.3f   (a)'s bytes against (b)'s, whole and window: %s"
+              % (a_whole, fmt(a_dev), a_win, b_whole, b_win, tail, a_whole / b_whole, a_win / b_win, a_whole / c_whole, a_win / c_win,
+                 "ok" if parity else "FAILED"), flush=True)
+        bus.close()
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -1141,4 +1217,4 @@ def main():
 
 
 if __name__ == "__main__":
-    meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
