@@ -21,7 +21,7 @@
 #pragma once
 #include "common.hpp"
 #include "devmath.hpp"
-#include "genplan.hpp"
+#include "renderplan.hpp"
 #include <type_traits>
 
 namespace shosc {
@@ -41,7 +41,7 @@ namespace shosc {
 //     tile: every frame is looked up from the piece that holds it (up to three compares), no recurrence across the ends.
 // A pair that sounds but holds two corners (or an onset without an attack) or more piece ends takes the general code for that
 // tile only; the rest is silent.  One bit per pair in two masks per (tile, chunk of 64 voices): the kernels walk set bits.
-constexpr uint32_t TILE_FRAMES = 512;         // = the lean render kernel's tile (four waves, eight frames per lane)
+// (TILE_FRAMES = 512, the lean render kernel's tile -- four waves, eight frames per lane -- lives in renderplan.hpp, beside the plan that counts tiles)
 constexpr uint32_t TILE_MAX_PIECES = 3;
 struct alignas(64) TileRec {
     double t0, dt;                // t(i) = fma(i - tile0, dt, t0): the accumulated phase at the tile's first frame, its piece's step
@@ -61,7 +61,7 @@ struct alignas(64) TileRec {
                                   // high 32 bits: the voice's position in its chunk of 64 (the lean kernel finds its polynomial by it)
 };
 constexpr uint32_t TILE_WALK_PIECES = 16;     // pieces a walk pair may touch (lanes 0 .. 15 fetch one each)
-static_assert(sizeof(TileRec) == 128 && offsetof(TileRec, GL) == 64 && offsetof(TileRec, tb) == 80 && offsetof(TileRec, split) == 112, "TileRec layout");
+static_assert(sizeof(TileRec) == TILE_REC_BYTES && sizeof(TileRec) == 128 && offsetof(TileRec, GL) == 64 && offsetof(TileRec, tb) == 80 && offsetof(TileRec, split) == 112, "TileRec layout");
 // lane `src` (wave-uniform) of a float64 vector value
 __device__ __forceinline__ double readlane_f64(double v, uint32_t src) {
     union { double d; int u[2]; } a, b;
@@ -1290,10 +1290,7 @@ __device__ __forceinline__ void lean_harm_frames(double s0, double c0, double s1
 // tiles of a note, whose phase sum runs through a binade every few frames.  (Round 3, first version: a dependent load per
 // piece end and tile, three tiles per wave: 32 us as a kernel of its own, and inside the render kernel its workgroups cost the
 // launch 28 us.)
-#ifndef SH_TPW
-#define SH_TPW 3
-#endif
-constexpr uint32_t TILES_PER_WAVE = SH_TPW;
+// (TILES_PER_WAVE = SH_TPW, 3 unless the build says otherwise: renderplan.hpp)
 constexpr int TILE_WIN = 6;
 template <typename V>
 __device__ __forceinline__ V win_pick(const V (&a)[TILE_WIN], uint32_t r, V beyond) {

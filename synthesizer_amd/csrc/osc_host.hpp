@@ -7,14 +7,14 @@
 
 using namespace shosc;
 
-struct sh_bank : shg::BankFacts {       // (nvoices, the lean counts, has_guard, the envelope and piece facts, no_general_voice: genplan.hpp)
+struct sh_bank : shr::Facts {       // (nvoices, the lean counts, has_guard, the envelope and piece facts, no_general_voice: genplan.hpp; what render shapes read besides: renderplan.hpp)
     sh_voice*   d_voices = nullptr;
     sh_segment* d_segs = nullptr;
     double*     d_coefs = nullptr;
     sh_partial* d_partials = nullptr;
     // launch records, four sets: launch n reads one while its first workgroups resolve the records of the block expected
     // two launches later (start + 2 * nframes) into another; launch n-1, on the other stream, holds two more
-    static constexpr int NSETS = 4;
+    static constexpr int NSETS = shosc::NSETS;
     VoiceLaunch* d_launch_buf[NSETS] = {};
     VoiceFM*    d_launch_fm_buf[NSETS] = {};
     FastRec*    d_fast_buf[NSETS] = {};
@@ -24,7 +24,7 @@ struct sh_bank : shg::BankFacts {       // (nvoices, the lean counts, has_guard,
     // one arrival counter per tile of a SELF-FOLDING launch (a render that stands alone: the last workgroup of a tile to store its
     // partial bus folds the tile's planes itself -- no k_bus_combine behind the launch); behind d_hint's 2 * nvoices words, zero
     // between launches (the folding workgroup resets its counter)
-    static constexpr uint32_t SELF_TILES = 16384;
+    static constexpr uint32_t SELF_TILES = shosc::SELF_TILES;
     uint32_t*   d_self() const { return d_hint + 2 * (size_t)nvoices; }
     // This bank's run of pipelined renders (same shape, consecutive blocks), the folds it still owes, and its ring of
     // partial-bus buffers: launch n writes ring slot n % 4, launch n + 2 (same stream) folds it.  Per bank, so that two banks
@@ -49,7 +49,8 @@ struct sh_bank : shg::BankFacts {       // (nvoices, the lean counts, has_guard,
     sh::Pooled  tile_block[NTILESETS];
     TileSet     tile_set[NTILESETS] = {};
     uint32_t    tile_carved[NTILESETS] = {0, 0, 0, 0};   // tiles the set was carved for
-    struct TileSpec { bool valid = false; uint64_t start = 0; uint32_t nframes = 0, groups = 0; } tile_spec[NTILESETS];
+    using TileSpec = shr::TileSetSpec;
+    TileSpec    tile_spec[NTILESETS];
     uint32_t    tile_count = 0;            // tile-classified launches so far
     struct Range { const char* lo; const char* hi; };
     Range       last_direct[3] = {};       // what the last launch wrote itself (single-group launches: float32 / float64 / PCM bus)
@@ -70,31 +71,21 @@ struct sh_bank : shg::BankFacts {       // (nvoices, the lean counts, has_guard,
     LaunchSet   gen_set = {};
     uint32_t    gen_segs = 0;
     double2*    d_seg_rot = nullptr;       // (cos, sin)(64*dt) per table piece
-    std::vector<uint64_t> chunk_span;      // (host copy)
-    uint64_t*   d_chunk_span = nullptr;    // [chunk][2]: first onset, last frame of sound + 1 of the chunk's voices
+    uint64_t*   d_chunk_span = nullptr;    // [chunk][2]: first onset, last frame of sound + 1 of the chunk's voices (host copy: Facts::chunk_span)
     double*     d_polys = nullptr;         // [slot][16]: the polynomial of a polynomial-Harmonics voice, by voice
     double2*    d_lfo_rot = nullptr;       // (cos, sin)(64*lfo_d) per voice
     VoiceLaunch* d_launch = nullptr;       // the set the next kernel reads
     VoiceFM*    d_launch_fm = nullptr;
     int         cur = 0;                   // the set the last launch read
     int         last_target = -1;          // the set the last render launch is filling (-1: none)
-    // what each set holds (or will); sparse: resolved for a tile-classified launch -- the chunks whose voices are all silent in
-    // the block were skipped (nobody reads them there), so only such a launch may take the set
-    struct Spec { bool valid = false; uint64_t start = 0; uint32_t nframes = 0; bool sparse = false; } spec[NSETS];
+    using Spec = shr::SetSpec;             // what each set holds (or will)
+    Spec        spec[NSETS];
     void        void_specs() { for (auto& q : spec) q.valid = false; last_target = -1; }
-    uint32_t    lean_fmsine_candidates = 0;   // the lean candidates that are FM Sine voices (all of the lean candidates: the FM-only lean kernel)
     bool        last_tiled = false;       // ... and whether it was tile-classified (no classification by voice then)
     uint32_t    last_groups = 0;          // voice groups of the last sh_bank_render launch (sh_bank_launch_stats)
-    bool        has_onsets = false;        // some voice starts late (sh_voice::start_frame)
-    bool        own_envelopes = false;     // the voices' envelope corners are too many to cut launches at (more than 16 distinct ones)
     float2*     d_gains = nullptr;
     uint32_t    nsegs = 0, ncoefs = 0, npartials = 0;
     std::vector<sh_voice> h_voices;    // for validation of per-call arguments
-    // (nearly: nine in ten) every voice can be a lean pair of a tile-classified launch: polynomial Harmonics or a plain Sine / Sawtooth / Square /
-    // Triangle / Pulse, no FM, no bias, not mirrored; tile_waveforms: some of them are no Harmonics / Sine (the tiles kernel with the
-    // waveform branch)
-    bool        tile_all = false, tile_waveforms = false;
-    long long   first_row_voice = -1;  // the first voice that reads a modulation / sample row (SH_FM_BUFFER, SH_BUFFER); -1: none
 };
 
 namespace shosc {

@@ -67,7 +67,7 @@ struct NextArgs {
     uint64_t  next_start;
     uint32_t  prep_wgs;
 };
-enum { LEAN_K_HARM = 0, LEAN_K_ALL = 1, LEAN_K_FM = 2, LEAN_K_REST = 3 };     // which kinds of lean record a bank can hold (static); _REST: a run of a list
+// (LEAN_K_HARM / _ALL / _FM / _REST -- which kinds of lean record a bank can hold (static); _REST: a run of a list -- renderplan.hpp)
 // osc_render_lean.hip: k_render_lean<W, F, M, kinds, seg> of shape var = W F M (4163, 484, 444, 844, 821) on `st`; SH_ERR_INVALID for a
 // shape that has no lean kernel (421, 211: banks of fewer than 64 voices never split a launch)
 int launch_render_lean(int var, int kinds, bool seg, dim3 grid, hipStream_t st, const LaunchArgs& A, const NextArgs& N, const FoldIn& F, double2* parts);
@@ -77,7 +77,7 @@ int launch_render_combined(int var, int mode, dim3 grid, hipStream_t st, const L
 
 namespace {
 
-constexpr uint32_t GEN_SPLIT = 2;      // general workgroups per tile of a tile-classified launch (each writes a plane of general parts; <= groups)
+// (GEN_SPLIT = 2, general workgroups per tile of a tile-classified launch -- each writes a plane of general parts; <= groups -- renderplan.hpp)
 
 // -DSH_DIAG (tools/ab.py build; never the shipped library): every wavefront of a render launch leaves the 100 MHz timestamps of
 // its phases and the SIMD it ran on in g_diag (four banks by block number: launches of a stream of blocks overlap pairwise);
@@ -1270,7 +1270,7 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_render_tiles(LaunchArgs A,
 // walked directly).  One voice group: the workgroup writes the caller's bus itself; several (banks without lean candidates,
 // SYNTHHIP_NO_SPLIT): partial buses, folded by the launch two on like a split launch's.
 // =====================================================================================================================================
-enum { COMBINED_DIRECT = 0, COMBINED_LEAN_HARM = 1, COMBINED_LEAN_ALL = 2 };
+// (COMBINED_DIRECT / _LEAN_HARM / _LEAN_ALL: renderplan.hpp)
 template <int WAVES, int FPL, int MINW, int MODE>
 __global__ __launch_bounds__(WAVES * 64, MINW) void k_render_combined(LaunchArgs A, NextArgs N, FoldIn F, double2* __restrict__ parts, BusOut out) {
     const uint32_t ngroups = groups_of_grid(N.prep_wgs);
