@@ -792,6 +792,39 @@ int sh_seq_render_meters(const sh_seq* seq, size_t first_sample, size_t nsamples
 int sh_seq_render_desk(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
                        uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters);
 
+/* The desk's FADER AUTOMATION: fader moves per track in SONG samples, uploaded once (sh_seq_auto_create) and applied by
+ * sh_seq_render_auto -- sh_seq_render_desk with one more step per track, behind its gain and in front of its pan; still one launch,
+ * nothing uploaded by a render (the table's two pointers travel by value):
+ *     master = silence; for t in tracks, in order:
+ *         sub = the track's events folded from silence
+ *         if gains[t] != 1.0: sub = audioop.mul(sub, gains[t])                                  (clamp, then floor)
+ *         for each segment of track t with kind 1, song samples s in [the end of the one before it, end):
+ *             sub[s] = trunc(sub[s] * ((s - origin) * slope / numsamples + offset))              (float64, in this order; toward zero)
+ *         sub = (fbound(L * pans[2 t]), fbound(R * pans[2 t + 1])) per frame (L, R)
+ *         master = audioop.add(master, sub)
+ *     if master_gain != 1.0: master = audioop.mul(master, master_gain)
+ * -- Sample.fadein's expression (sh_mix_events_env's kind 1) with s counting interleaved SAMPLES of the song, whatever window is rendered.
+ * A move from volume v0 to v1 over frames [a, b) of a song of nch channels is {end = b nch, origin = a nch, mul = 1.0, slope = v1 - v0,
+ * numsamples = (b - a) nch, offset = v0, kind = 1}; a hold (v0 == v1) is trunc(x * v), NOT audioop.mul's floor.  Segments of kind 0 fill
+ * the gaps; past a track's last segment nothing is shaped.  A track's row of levels is read behind its moves, as the master takes it; a
+ * muted track is still skipped.  A kernel finds a tile's first segment by binary search, so a long list of moves costs log2 of its length.
+ * sh_seq_auto_create: segments[seg_first[t] .. seg_first[t + 1]) are track t's, ntracks + 1 offsets.  SH_ERR_INVALID: a NULL argument, a
+ * handle without tracks, width 3 (the fades have no 24-bit form), another ntracks than the handle's, a seg_first that does not start at
+ * 0, does not end at nsegments or decreases; a segment whose reserved is not 0, whose end does not lie past the one before or lies past
+ * the song, whose kind is not 0 or 1 or whose mul is not exactly 1.0; a move whose origin is not its first sample, whose numsamples is
+ * smaller than its length, or whose volumes (offset, offset + slope) are not finite or leave 0 .. 1 -- so the factor never exceeds 1 and
+ * the result never leaves the width's range.  The handle keeps nothing of `seq` but its track count, width, channels and length.
+ * sh_seq_render_auto takes sh_seq_render_desk's arguments and the automation's handle; pans == NULL with npans == 0 and master_gain == 1.0
+ * mean no desk step.  SH_ERR_INVALID, nothing launched, `out` and `meters` untouched: what sh_seq_render_desk refuses, automation ==
+ * NULL, a handle made for another song (other track count, width, channels or length), width 3. */
+typedef struct sh_seq_auto sh_seq_auto;
+int sh_seq_auto_create(const sh_seq* seq, const sh_env_segment* segments, uint32_t nsegments, const uint32_t* seg_first, uint32_t ntracks,
+                       sh_seq_auto** out);
+int sh_seq_auto_destroy(sh_seq_auto* automation);
+int sh_seq_render_auto(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                       uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters,
+                       const sh_seq_auto* automation);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

@@ -207,6 +207,10 @@ _SIGNATURES = {
     "sh_seq_render_meters": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(SeqMeter), C.c_uint32]),
     "sh_seq_render_desk": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
                                      C.c_double, C.POINTER(SeqMeter), C.c_uint32]),
+    "sh_seq_auto_create": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(_P)]),
+    "sh_seq_auto_destroy": (C.c_int, [_P]),
+    "sh_seq_render_auto": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
+                                     C.c_double, C.POINTER(SeqMeter), C.c_uint32, _P]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),
@@ -466,10 +470,11 @@ class Sequence:
         return nt.value, nr.value
 
     def render(self, first_sample: int, nsamples: int, out: "DeviceBuffer", out_sample: int = 0, gains=None, meters: bool = False, pans=None,
-               master=None):
+               master=None, automation: Optional["SeqAutomation"] = None):
         """``meters=True`` (a song of tracks): sh_seq_render_meters -- the same bytes and, from the same launch, one row per track and one for
         the master, each ``(peak, sum_squares)`` of per-channel pairs, the sums exact Python ints.  Otherwise None.
-        ``pans`` (2 * ntracks factors, left then right per track) or ``master`` (a gain) given: sh_seq_render_desk, with or without meters."""
+        ``pans`` (2 * ntracks factors, left then right per track) or ``master`` (a gain) given: sh_seq_render_desk, with or without meters.
+        ``automation`` (a ``SeqAutomation`` of this song) given: sh_seq_render_auto, with or without any of the others."""
         def doubles(v):
             return None if v is None else (C.c_double * max(1, len(v)))(*v)
 
@@ -480,7 +485,10 @@ class Sequence:
         if meters:
             nrows = self.tracks()[0] + 1
             rows = (SeqMeter * nrows)()
-        if desk:
+        if automation is not None:
+            check(lib().sh_seq_render_auto(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans), count(pans),
+                                           1.0 if master is None else master, rows, nrows, automation.handle))
+        elif desk:
             check(lib().sh_seq_render_desk(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans), count(pans),
                                            1.0 if master is None else master, rows, nrows))
         elif meters:
@@ -499,6 +507,37 @@ class Sequence:
             finally:
                 self._h = _P()
                 self._sources = []
+
+    def __del__(self) -> None:
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class SeqAutomation:
+    """RAII wrapper over sh_seq_auto: the fader moves of a song of tracks -- ``segments`` (ENV_SEGMENT_DTYPE rows in SONG samples, the tracks'
+    one behind the other) and ``seg_first`` (one offset per track and the table's length behind them) -- uploaded once into a device table
+    of its own; ``Sequence.render(automation=)`` applies it."""
+
+    def __init__(self, seq: Sequence, segments: np.ndarray, seg_first) -> None:
+        ensure_init()
+        assert segments.dtype == ENV_SEGMENT_DTYPE and len(seg_first) >= 2 and seg_first[-1] == len(segments)
+        self._h = _P()
+        first = (C.c_uint32 * len(seg_first))(*seg_first)
+        check(lib().sh_seq_auto_create(seq.handle, _ptr(segments), len(segments), first, len(seg_first) - 1,
+                                       C.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def free(self) -> None:
+        if self._h:
+            try:
+                lib().sh_seq_auto_destroy(self._h)
+            finally:
+                self._h = _P()
 
     def __del__(self) -> None:
         try:

@@ -57,11 +57,15 @@
 // handle holds into a template argument.  The DESK buses, SeqBusD and SeqBusDM, are the two buses again with a pan pot per track and a
 // master fader, by value in the kernel arguments like the gains (sh_seq_render_desk): in seq_runs the sub-mix by its gain, THEN by its
 // pan factors (even samples the left one, odd ones the right one: a stereo sample's Sample.stereo), then the hook and the add; behind the
-// last run the master by the master's gain, once, in front of its meter row and the store.
+// last run the master by the master's gain, once, in front of its meter row and the store.  The AUTOMATION buses, SeqBusA and SeqBusAM,
+// are the desk buses again with a table of fader moves per track (seqauto.hpp; sh_seq_auto_create uploads it once, sh_seq_render_auto
+// passes its two pointers by value): in seq_runs the sub-mix by its gain, THEN through the track's segments at its song positions
+// (int(x * f), the fade's truncation), then the pan, the hook and the add.
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
 #include "ratecv.hpp"
+#include "seqauto.hpp"
 #include "seqenv.hpp"
 #include "seqloop.hpp"
 #include "seqmeter.hpp"
@@ -884,6 +888,20 @@ struct SeqBusD : SeqBus, SeqDesk {};
 template <typename Bus> constexpr bool SEQ_DESK = std::is_base_of<SeqDesk, Bus>::value;
 static_assert(sizeof(SeqDesk) == 520 && sizeof(SeqBusD) == sizeof(SeqBus) + sizeof(SeqDesk), "the desk: 520 bytes of kernel arguments behind the bus");
 
+// AUTOMATION (sh_seq_render_auto): fader moves per track on either desk bus -- a table a handle of its own keeps on the device
+// (sh_seq_auto), its two pointers by value in the kernel arguments: a render uploads nothing.  Track t's segments are
+// asegs[afirst[t] .. afirst[t + 1]) (she::Seg in SONG samples, the ends ascending, plain segments in the gaps), applied to the track's
+// sub-mix BEHIND its gain and IN FRONT of its pan: sample s of a segment becomes int(x * ((s - origin) * slope / numsamples + offset)),
+// she::gain's fade-in, truncated toward zero.  Per run the first segment that ends past the tile's first sample is found by binary search
+// (sha::find: uniform, scalar loads), and the lane's samples are shaped from there on (sha::shape_from).  Widths 1, 2 and 4: upstream's
+// fades have no 24-bit form.
+struct SeqAuto {
+    const she::Seg* asegs;
+    const uint32_t* afirst;               // ntracks + 1 offsets into asegs
+};
+struct SeqBusA : SeqBusD, SeqAuto {};
+template <typename... Bus> constexpr bool SEQ_AUTO = (std::is_base_of<SeqAuto, Bus>::value || ...);
+
 // a lane's accumulator: eight packed samples at 16 bits, four 64-bit sums at the other widths
 template <int WIDTH> struct SeqAcc { typedef llong4v type; };
 template <> struct SeqAcc<2> { typedef short8v type; };
@@ -920,6 +938,7 @@ __device__ __forceinline__ void seq_master(typename SeqAcc<WIDTH>::type& acc, co
 // The runs of tile k, written once for the three templates and every bus: the events from e on, run by run.  walk(e, e1, sub): the
 // schedule of the kernel, events [e, e1) into sub; hook(sub, track): what else a bus does with a track's samples as the master takes them,
 // post-fader and (a desk bus) post-pan (the metering buses: its row).  Everything about a run is uniform, and a run lists at least one event.
+// An automation bus: the track's fader moves between the gain and the pan, at the lane's SONG positions (tile k starts at k * TILE).
 template <int WIDTH, typename Bus, typename Walk, typename Hook>
 __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e, typename SeqAcc<WIDTH>::type& acc, Walk walk, Hook hook) {
     const uint32_t r1 = bus.rfirst[k + 1];
@@ -937,20 +956,50 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
             e = run.end;
             continue;
         }
+        [[maybe_unused]] const she::Seg* asegs = nullptr;    // (an automation bus: the track's segments, from the first that ends past t0)
+        [[maybe_unused]] uint32_t an = 0, ai = 0;
+        [[maybe_unused]] const uint32_t t0 = k * SEQ_TILE<WIDTH>;
+        if constexpr (SEQ_AUTO<Bus>) {
+            const uint32_t a0 = bus.afirst[run.track];
+            asegs = bus.asegs + a0;
+            an = bus.afirst[run.track + 1] - a0;
+            ai = sha::find(asegs, an, t0);
+        }
         if constexpr (WIDTH == 2) {
             short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
             walk(e, run.end, sub);
             sub = seq_scale8(sub, g);                         // post-fader: what the master takes of the track
+            if constexpr (SEQ_AUTO<Bus>) {
+                if (ai < an) {                                // (uniform: behind the track's last segment nothing is shaped)
+                    int v[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = (int)sub[j];
+                    sha::shape_from<8>(asegs, an, ai, t0, t0 + SEQ_TILE<2>, (long long)t0 + threadIdx.x * SEQ_LANE<2>, v, (double)SEQ_LO<2>, (double)SEQ_HI<2>);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) sub[j] = (short)v[j];
+                }
+            }
             if constexpr (SEQ_DESK<Bus>) sub = seq_pan8(sub, left, right);
             hook(sub, run.track);
             acc = __builtin_elementwise_add_sat(acc, sub);
         } else {
             llong4v sub = {0, 0, 0, 0};
             walk(e, run.end, sub);
+            if constexpr (SEQ_AUTO<Bus>) {                    // the gain over all four first, then the segments; the pan below
+                int v[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = (int)seq_scale_w<WIDTH>(sub[j], g);
+                sha::shape_from<4>(asegs, an, ai, t0, t0 + SEQ_TILE<WIDTH>, (long long)t0 + threadIdx.x * SEQ_LANE<WIDTH>, v, (double)SEQ_LO<WIDTH>,
+                                   (double)SEQ_HI<WIDTH>);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sub[j] = v[j];
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 long long x = sub[j];
-                if constexpr (SEQ_DESK<Bus>) {                // the gain, then the pan: two roundings
+                if constexpr (SEQ_AUTO<Bus>) {                // (scaled and shaped above)
+                    acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, j & 1 ? right : left);
+                } else if constexpr (SEQ_DESK<Bus>) {         // the gain, then the pan: two roundings
                     x = seq_scale_w<WIDTH>(x, g);
                     acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, j & 1 ? right : left);
                 } else {
@@ -980,9 +1029,11 @@ struct SeqBusM : SeqBus {
     uint32_t  ntracks, nch;               // nch: the song's channels (2: sample s is channel s & 1; otherwise all are channel 0)
 };
 struct SeqBusDM : SeqBusM, SeqDesk {};    // the desk with meters: a track's row post-fader and post-pan, the master's over the stored bytes
+struct SeqBusAM : SeqBusDM, SeqAuto {};   // and with automation: a track's row behind its fader moves as well
 template <typename... Bus> struct SeqMetered : std::false_type {};
 template <> struct SeqMetered<SeqBusM> : std::true_type {};
 template <> struct SeqMetered<SeqBusDM> : std::true_type {};
+template <> struct SeqMetered<SeqBusAM> : std::true_type {};
 
 // the workgroup's row table, zeroed: every lane of the workgroup calls it (a barrier)
 __device__ __forceinline__ shmt::Row* seq_meter_begin() {
@@ -1525,6 +1576,16 @@ struct sh_seq {
     std::vector<const char*> src_lo, src_hi;      // the byte ranges of the sources: a render's `out` may overlap none
 };
 
+// Fader automation of a song of tracks (sh_seq_auto_create): the tracks' segments and where each track's start, uploaded once into a
+// block this handle owns; what it says of the song it was made for is what sh_seq_render_auto holds a song to.
+struct sh_seq_auto {
+    void*    block = nullptr;             // segments (she::Seg) | first (ntracks + 1 offsets)
+    size_t   cap = 0, bytes = 0, at_first = 0;
+    uint32_t ntracks = 0, nsegments = 0;
+    int      width = 0, nchannels = 0;
+    uint64_t track_samples = 0;
+};
+
 namespace {
 
 // the lowest level whose chain covers the row
@@ -1572,7 +1633,7 @@ void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, 
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out, bus...); };
         if (q->width == 1) go(k_win_w<LEVEL, 1, BUS, Bus...>);
         else if (q->width == 4) go(k_win_w<LEVEL, 4, BUS, Bus...>);
-        else if constexpr (LEVEL != ENV) go(k_win_w<LEVEL, 3, BUS, Bus...>);       // (sh_seq_create refuses width 3 with segments)
+        else if constexpr (LEVEL != ENV && !SEQ_AUTO<Bus...>) go(k_win_w<LEVEL, 3, BUS, Bus...>);       // (sh_seq_create refuses width 3 with segments, sh_seq_render_auto width 3)
     }
 }
 
@@ -1702,9 +1763,10 @@ int seq_desk(const char* fn, const double* pans, uint32_t npans, double master_g
 }
 
 // sh_seq_render (gains NULL: every track at 1.0), sh_seq_render_gains, sh_seq_render_meters (meters: ntracks + 1 host rows, the handle
-// has tracks) and sh_seq_render_desk (desk: the pans and the master's gain, the handle has tracks; with or without meters) behind their names
+// has tracks), sh_seq_render_desk (desk: the pans and the master's gain, the handle has tracks; with or without meters) and
+// sh_seq_render_auto (au: the automation's table, with a desk) behind their names
 int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains,
-               sh_seq_meter* meters = nullptr, const SeqDesk* desk = nullptr) {
+               sh_seq_meter* meters = nullptr, const SeqDesk* desk = nullptr, const SeqAuto* au = nullptr) {
     static_assert(sizeof(sh_seq_meter) == sizeof(shmt::Row) && offsetof(sh_seq_meter, sq_hi) == offsetof(shmt::Row, sq_hi) &&
                   offsetof(sh_seq_meter, sq_lo) == offsetof(shmt::Row, sq_lo), "sh_seq_meter is shmt::Row");
     const size_t b_meters = meters ? ((size_t)seq->ntracks + 1) * sizeof(shmt::Row) : 0;
@@ -1745,7 +1807,18 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
         if (!seq->ntracks) seq_window_launch<LEVEL>(seq, grid, st, lo, hi, biased);
         else if (!desk && !meters) seq_window_launch<LEVEL, SeqBus>(seq, grid, st, lo, hi, biased, bus);
         else if (!desk) seq_window_launch<LEVEL, SeqBusM>(seq, grid, st, lo, hi, biased, bus);
-        else if (meters) seq_window_launch<LEVEL, SeqBusDM>(seq, grid, st, lo, hi, biased, bus);
+        else if (au && meters) {
+            SeqBusAM moved{};
+            static_cast<SeqBusDM&>(moved) = bus;
+            static_cast<SeqAuto&>(moved) = *au;
+            seq_window_launch<LEVEL, SeqBusAM>(seq, grid, st, lo, hi, biased, moved);
+        } else if (au) {
+            SeqBusA moved{};
+            static_cast<SeqBus&>(moved) = bus;
+            static_cast<SeqDesk&>(moved) = bus;
+            static_cast<SeqAuto&>(moved) = *au;
+            seq_window_launch<LEVEL, SeqBusA>(seq, grid, st, lo, hi, biased, moved);
+        } else if (meters) seq_window_launch<LEVEL, SeqBusDM>(seq, grid, st, lo, hi, biased, bus);
         else {
             SeqBusD plain{};
             static_cast<SeqBus&>(plain) = bus;
@@ -1829,6 +1902,105 @@ int sh_seq_render_desk(const sh_seq* seq, size_t first_sample, size_t nsamples, 
     if (!rc) rc = seq_desk(fn, pans, npans, master_gain, d);
     if (rc) return rc;
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d);
+}
+
+int sh_seq_auto_create(const sh_seq* seq, const sh_env_segment* segments, uint32_t nsegments, const uint32_t* seg_first, uint32_t ntracks,
+                       sh_seq_auto** out) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_seq_auto_create";
+    if (!out) return seq_null(fn);
+    *out = nullptr;
+    if (!seq || !seg_first || (nsegments && !segments)) return seq_null(fn);
+    if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
+    if (seq->width == 3) return sh::set_error(SH_ERR_INVALID, "%s: width 3: a fader move's fade has no 24-bit form", fn);
+    if (ntracks != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u lanes for %u tracks", fn, ntracks, seq->ntracks);
+    if (seg_first[0] != 0 || seg_first[ntracks] != nsegments) return sh::set_error(SH_ERR_INVALID, "%s: seg_first starts at 0 and ends at nsegments", fn);
+    for (uint32_t t = 0; t < ntracks; ++t)
+        if (seg_first[t] > seg_first[t + 1]) return sh::set_error(SH_ERR_INVALID, "%s: seg_first decreases at track %u", fn, t + 1);
+    for (uint32_t t = 0; t < ntracks; ++t) {
+        uint64_t prev = 0;
+        for (uint32_t s = seg_first[t]; s < seg_first[t + 1]; ++s) {
+            const sh_env_segment& g = segments[s];
+            const uint32_t k = s - seg_first[t];
+            if (g.reserved != 0) return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: reserved must be 0", fn, t, k);
+            if (g.end <= prev || g.end > seq->track_samples)
+                return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: ends not ascending or beyond the song", fn, t, k);
+            if (g.kind > she::FADE_IN) return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: kind %u not 0 or 1", fn, t, k, g.kind);
+            if (g.mul != 1.0) return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: mul must be 1.0 (a track's gain is the render's)", fn, t, k);
+            if (g.kind == she::FADE_IN) {
+                // k runs over [0, end - origin) and numsamples covers it, so the factor stays between the two volumes, both inside 0 .. 1
+                if (g.origin != prev) return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: a move's origin is its first sample", fn, t, k);
+                if (!(g.numsamples >= (double)(g.end - g.origin)))
+                    return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: numsamples shorter than the move", fn, t, k);
+                if (!isfinite(g.numsamples) || !(g.offset >= 0.0 && g.offset <= 1.0) || !(g.slope >= -g.offset && g.slope <= 1.0 - g.offset))
+                    return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: a volume is not finite or outside 0 .. 1", fn, t, k);
+            }
+            prev = g.end;
+        }
+    }
+    sh_seq_auto* a = new (std::nothrow) sh_seq_auto;
+    if (!a) return sh::set_error(SH_ERR_NOMEM, "host allocation failed");
+    a->ntracks = ntracks;
+    a->nsegments = nsegments;
+    a->width = seq->width;
+    a->nchannels = seq->nchannels;
+    a->track_samples = seq->track_samples;
+    a->at_first = (size_t)nsegments * sizeof(she::Seg);
+    a->bytes = a->at_first + ((size_t)ntracks + 1) * 4;
+    std::vector<char> host(a->bytes);
+    seq_segments(reinterpret_cast<she::Seg*>(host.data()), segments, nsegments);
+    memcpy(host.data() + a->at_first, seg_first, ((size_t)ntracks + 1) * 4);
+    int rc = sh::pool_alloc(a->bytes, &a->block, &a->cap);
+    if (rc) {
+        delete a;
+        return rc;
+    }
+    hipStream_t st = sh::state().stream;
+    hipError_t e = hipMemcpyAsync(a->block, host.data(), host.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);        // once per automation: the host copy goes when this returns
+    if (e != hipSuccess) {
+        sh::pool_free(a->block, a->cap);
+        delete a;
+        return sh::hip_error(e, fn);
+    }
+    *out = a;
+    return SH_OK;
+}
+
+int sh_seq_auto_destroy(sh_seq_auto* a) {
+    if (!a) return SH_OK;
+    SH_API_LOCK();
+    if (a->block && sh::state().initialized) {
+        if (sh::has_pending()) sh::flush_pending();
+        sh::pool_free(a->block, a->cap);                      // (stream-ordered reuse: a render still in flight finishes first)
+    }
+    delete a;
+    return SH_OK;
+}
+
+int sh_seq_render_auto(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                       uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters,
+                       const sh_seq_auto* automation) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_seq_render_auto";
+    if (!seq || !out || !automation || (!gains && ngains) || (!pans && npans) || (!meters && nmeters)) return seq_null(fn);
+    if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
+    if (seq->width == 3) return sh::set_error(SH_ERR_INVALID, "%s: width 3: a fader move's fade has no 24-bit form", fn);
+    if (automation->ntracks != seq->ntracks || automation->width != seq->width || automation->nchannels != seq->nchannels ||
+        automation->track_samples != seq->track_samples)
+        return sh::set_error(SH_ERR_INVALID, "%s: the automation was made for another song (%u tracks, width %d, %d channels, %llu samples)", fn,
+                             automation->ntracks, automation->width, automation->nchannels, (unsigned long long)automation->track_samples);
+    if (pans && seq->nchannels != 2) return sh::set_error(SH_ERR_INVALID, "%s: pans need a stereo song, this one has %d channels", fn, seq->nchannels);
+    if (gains && ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
+    if (pans && npans != 2 * seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u pan factors for %u tracks (two each)", fn, npans, seq->ntracks);
+    if (meters && nmeters != seq->ntracks + 1) return sh::set_error(SH_ERR_INVALID, "%s: %u rows for %u tracks and the master", fn, nmeters, seq->ntracks);
+    SeqGains g;
+    SeqDesk d;
+    int rc = seq_gains(fn, gains, ngains, g);
+    if (!rc) rc = seq_desk(fn, pans, npans, master_gain, d);
+    if (rc) return rc;
+    const SeqAuto au{(const she::Seg*)automation->block, (const uint32_t*)((const char*)automation->block + automation->at_first)};
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, &au);
 }
 
 int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns) {

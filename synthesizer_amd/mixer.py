@@ -21,6 +21,7 @@ from __future__ import annotations
 import ctypes as C
 import gc
 import math
+import operator
 import threading
 from typing import Callable, Dict, Generator, List, Optional, Sequence, Tuple, Union
 
@@ -31,7 +32,7 @@ from . import params
 from .oscillators import Oscillator, VoiceSpec, _pwm_widths, _table, pack_voices, time_step_weights
 from .sample import Sample
 
-__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "sequence", "compile_sequence", "compile_tracks", "CompiledSequence", "Levels", "SongLevels", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
+__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "sequence", "compile_sequence", "compile_tracks", "CompiledSequence", "Levels", "SongLevels", "Automation", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
 
 
 def pan_gains(pan: float) -> Tuple[float, float]:
@@ -649,6 +650,42 @@ class SongLevels:
         return "SongLevels(tracks=%r, master=%r)" % (self.tracks, self.master)
 
 
+class Automation:
+    """The fader moves of a song of tracks, made by ``CompiledSequence.automation(lanes)`` and given to that song's ``render``,
+    ``render_into`` and ``chunks`` as ``automation=``: per track a list of pieces ``(start_frame, end_frame, from_volume, to_volume)``,
+    packed as segments in song samples and uploaded ONCE into a small device table that this object owns.  ``pieces`` has the checked
+    lanes (a tuple of tuples per track, pieces at exactly (1.0, 1.0) dropped), ``segments`` and ``seg_first`` the packed table.
+    ``close()`` (or the ``with`` block, or the last reference) frees the table."""
+
+    def __init__(self, song: "CompiledSequence", pieces: tuple, segments: np.ndarray, seg_first: list) -> None:
+        self._auto = None
+        self._song = song
+        self.pieces, self.segments, self.seg_first = pieces, segments, seg_first
+        self._auto = N.SeqAutomation(song._handle(), segments, seg_first)
+
+    def _handle(self) -> "N.SeqAutomation":
+        if self._auto is None:
+            raise ValueError("Automation: closed")
+        return self._auto
+
+    def close(self) -> None:
+        if self._auto is not None:
+            self._auto.free()
+            self._auto = None
+
+    def __enter__(self) -> "Automation":
+        return self
+
+    def __exit__(self, *_exc) -> None:
+        self.close()
+
+    def __del__(self) -> None:
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CompiledSequence:
     """A list of placed samples compiled once and rendered as often, and in whatever windows, as a player asks: ``render`` of frames
     ``[a, b)`` holds, byte for byte, frames ``[a, b)`` of ``sequence(events, ...)``, in one launch that copies no table.  Made by
@@ -690,7 +727,36 @@ class CompiledSequence:
     ``SongLevels`` -- the levels of every track post-fader and of the master in the window just rendered, exact in integers -- beside
     the same bytes; with ``pans`` a track's levels are post-fader and post-pan, with ``master`` the master's are over the bytes
     returned.  A handle serves one metered render at a time.  Not built: pre-fader meters (they would read a muted track's
-    events), meters of a song without tracks, clip counters."""
+    events), meters of a song without tracks, clip counters.
+    The desk's FADER AUTOMATION: ``automation(lanes)`` takes, per track, None or a list of pieces ``(start_frame, end_frame, from_volume,
+    to_volume)`` in SONG frames -- ascending, not overlapping, volumes finite and within 0.0 .. 1.0 (a static gain above 1 stays with
+    ``gains``) -- and uploads them once; ``render``, ``render_into`` and ``chunks`` take the ``Automation`` it returns as
+    ``automation=``, and the chain is, byte for byte, ::
+
+        master = Sample(...)
+        for t, events in enumerate(tracks):
+            sub = sequence(events, ...)
+            if gains[t] != 1.0:
+                sub.amplify(gains[t])
+            for (a, b, v0, v1) in pieces[t]:                # the fader moves: behind the gain, in front of the pan
+                n = (b - a) * nchannels                     # numsamples, a float
+                for k in range(n):                          # k counts SAMPLES from the piece's first, interleaved
+                    x = sub[a * nchannels + k]
+                    sub[a * nchannels + k] = int(x * (k * (v1 - v0) / n + v0))    # a Python float product, truncated toward zero
+            if pans[t] is not None:
+                sub.stereo(lf_t, rf_t)
+            master.mix(sub)
+        if master_gain != 1.0:
+            master.amplify(master_gain)
+
+    -- ``Sample.fadein``'s expression: a piece with ``to_volume == 1.0`` is ``Sample.fadein(seconds, from_volume)`` of that clip of the
+    track and one with ``from_volume == 1.0`` is ``Sample.fadeout(seconds, to_volume)``, byte for byte.  A HOLD (``from_volume ==
+    to_volume``) is ``int(x * v)``, the fade's truncation toward zero, NOT ``audioop.mul``'s floor: it differs from a gain of ``v`` on
+    negative samples.  Outside its pieces a track is untouched, and pieces at exactly (1.0, 1.0) are dropped.  A window's bytes are
+    that slice of the whole song's whatever the window: positions count from the piece's first sample in the song.  Post-fader meters read
+    a track behind its moves, as the master takes it; a muted track is still skipped; ``stem`` stays plain.  Still one launch per window
+    and nothing uploaded by a render.  Width 3 has no automation (``NotImplementedError``: upstream's fades have no 24-bit form, as for
+    envelopes)."""
 
     MAX_TRACKS = 32
 
@@ -815,9 +881,96 @@ class CompiledSequence:
         return None if master == 1.0 else master
 
     @staticmethod
-    def _desk(pans, master) -> dict:
-        """the keywords of the desk for N.Sequence.render: none at all where neither step is asked for (the entry points there were)"""
+    def _desk(pans, master, automation=None) -> dict:
+        """the keywords of the desk for N.Sequence.render: none at all where no step is asked for (the entry points there were)"""
+        if automation is not None:
+            return {"pans": pans, "master": master, "automation": automation}
         return {} if pans is None and master is None else {"pans": pans, "master": master}
+
+    def _automation(self, automation) -> Optional["N.SeqAutomation"]:
+        """``automation`` as render hands it on: None, or the native handle of an ``Automation`` that THIS song made -- checked before
+        anything is launched"""
+        if automation is None:
+            return None
+        if not isinstance(automation, Automation) or automation._song is not self:
+            raise ValueError("CompiledSequence: automation is None or an Automation made by this song's automation()")
+        return automation._handle()
+
+    def automation(self, lanes) -> Automation:
+        """The fader moves of this song of tracks (``CompiledSequence`` has the chain): ``lanes`` has one entry per track, None or a list
+        of pieces ``(start_frame, end_frame, from_volume, to_volume)`` -- song frames, ascending, not overlapping, ``start < end <=
+        len(song)``, volumes finite and within 0.0 .. 1.0.  A hold (``from_volume == to_volume``) is ``int(x * v)``: the fade's truncation
+        toward zero, not ``audioop.mul``'s floor.  Everything is checked before the device is reached, a ``ValueError`` naming the track
+        and the piece; pieces at exactly (1.0, 1.0) are dropped; the rest are uploaded once into a table the returned ``Automation`` owns."""
+        self._handle()
+        pieces = self._check_lanes(lanes)
+        segments, seg_first = self._pack_lanes(pieces, self.nchannels)
+        return Automation(self, pieces, segments, seg_first)
+
+    def _check_lanes(self, lanes) -> tuple:
+        if self.ntracks is None:
+            raise ValueError("CompiledSequence: automation needs a song of tracks (compile_tracks); this one has none")
+        if self.samplewidth == 3:
+            raise NotImplementedError("CompiledSequence: automation: width 3: a fade has no 24-bit form")
+        if isinstance(lanes, (str, bytes)) or not hasattr(lanes, "__len__"):
+            raise ValueError("CompiledSequence: automation: lanes is a sequence, one entry per track")
+        if len(lanes) != self.ntracks:
+            raise ValueError("CompiledSequence: automation: %d lanes for %d tracks" % (len(lanes), self.ntracks))
+        out = []
+        for t, lane in enumerate(lanes):
+            if lane is None:
+                out.append(())
+                continue
+            if isinstance(lane, (str, bytes)) or not hasattr(lane, "__iter__"):
+                raise ValueError("CompiledSequence: automation: track %d: a lane is None or a list of pieces" % t)
+            kept, prev = [], 0
+            for k, piece in enumerate(lane):
+                where = "CompiledSequence: automation: track %d, piece %d: " % (t, k)
+                if isinstance(piece, (str, bytes)) or not hasattr(piece, "__len__") or len(piece) != 4:
+                    raise ValueError(where + "a piece is (start_frame, end_frame, from_volume, to_volume)")
+                try:
+                    if isinstance(piece[0], bool) or isinstance(piece[1], bool):
+                        raise TypeError
+                    a, b = operator.index(piece[0]), operator.index(piece[1])
+                except TypeError:
+                    raise ValueError(where + "start_frame and end_frame are integers") from None
+                try:
+                    v0, v1 = float(piece[2]), float(piece[3])
+                except (TypeError, ValueError):
+                    raise ValueError(where + "a piece is (start_frame, end_frame, from_volume, to_volume), four numbers") from None
+                if a < 0 or a >= b:
+                    raise ValueError(where + "frames [%d, %d): a piece starts at 0 or later and ends behind its start" % (a, b))
+                if b > self.frames:
+                    raise ValueError(where + "frames [%d, %d) end past the song's %d frames" % (a, b, self.frames))
+                if a < prev:
+                    raise ValueError(where + "starts at frame %d, before the piece in front of it ends (%d)" % (a, prev))
+                for name, v in (("from_volume", v0), ("to_volume", v1)):
+                    if not math.isfinite(v) or not 0.0 <= v <= 1.0:
+                        raise ValueError(where + "%s %r is not a finite number within 0.0 .. 1.0" % (name, v))
+                prev = b
+                if not (v0 == 1.0 and v1 == 1.0):
+                    kept.append((a, b, v0, v1))
+            out.append(tuple(kept))
+        return tuple(out)
+
+    @staticmethod
+    def _pack_lanes(pieces: tuple, nchannels: int) -> tuple:
+        """the checked lanes as sh_env_segment rows in song SAMPLES, the tracks' one behind the other, and where each track's start: a
+        piece is a fade-in segment (origin its first sample, numsamples its length, slope ``v1 - v0``, offset ``v0``, mul 1.0), a plain
+        segment fills the gap in front of it"""
+        rows, seg_first = [], [0]
+        for lane in pieces:
+            at = 0
+            for a, b, v0, v1 in lane:
+                if a * nchannels > at:
+                    rows.append((a * nchannels, 0, 1.0, 0.0, 0.0, 0.0, N.ENV_NONE))
+                rows.append((b * nchannels, a * nchannels, 1.0, v1 - v0, float((b - a) * nchannels), v0, N.ENV_FADE_IN))
+                at = b * nchannels
+            seg_first.append(len(rows))
+        segments = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
+        for name, column in zip(("end", "origin", "mul", "slope", "numsamples", "offset", "kind"), zip(*rows) if rows else [()] * 7):
+            segments[name] = column
+        return segments, seg_first
 
     def _levels(self, rows, nframes: int) -> SongLevels:
         if rows is None:                                        # an empty window: nothing was launched, every level 0
@@ -850,15 +1003,17 @@ class CompiledSequence:
         return start_frame, nframes
 
     def render_into(self, buf: N.DeviceBuffer, byte_offset: int, start_frame: int, nframes: int, gains: Optional[Sequence[float]] = None,
-                    meters: bool = False, pans: Optional[Sequence] = None, master: Optional[float] = None) -> Optional[SongLevels]:
+                    meters: bool = False, pans: Optional[Sequence] = None, master: Optional[float] = None,
+                    automation: Optional[Automation] = None) -> Optional[SongLevels]:
         """Frames ``[start_frame, start_frame + nframes)`` of the song into ``buf`` from ``byte_offset`` (a whole number of samples) on:
         every byte of the range is written, whatever ``buf`` held.  ``gains``: one per track of a song of tracks.  ``meters=True``: the
         same bytes, and the window's ``SongLevels`` returned, from the same launch (the call then waits for it).  ``pans``, ``master``:
-        a pan per track and the master's gain of a stereo song of tracks (``CompiledSequence``), in that same launch."""
+        a pan per track and the master's gain of a stereo song of tracks (``CompiledSequence``), in that same launch.  ``automation``:
+        None or an ``Automation`` made by this song's ``automation()``: its fader moves, in that same launch."""
         seq = self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
-        desk = self._desk(self._pans(pans), self._master(master))
+        desk = self._desk(self._pans(pans), self._master(master), self._automation(automation))
         start_frame, nframes = self._range(start_frame, nframes)
         if byte_offset < 0 or byte_offset % self.samplewidth:
             raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
@@ -876,23 +1031,24 @@ class CompiledSequence:
         return None
 
     def render(self, start_frame: int = 0, nframes: Optional[int] = None, gains: Optional[Sequence[float]] = None, meters: bool = False,
-               pans: Optional[Sequence] = None, master: Optional[float] = None):
+               pans: Optional[Sequence] = None, master: Optional[float] = None, automation: Optional[Automation] = None):
         """A new ``Sample``: frames ``[start_frame, start_frame + nframes)`` of the song; ``nframes`` None: to the end.  ``gains``: one
         per track of a song of tracks (None: all 1.0).  ``meters=True``: ``(Sample, SongLevels)``, both from the one launch.  ``pans``:
-        one entry per track of a stereo song of tracks (None, a number -1 .. 1 or a pair of factors); ``master``: the master's gain."""
+        one entry per track of a stereo song of tracks (None, a number -1 .. 1 or a pair of factors); ``master``: the master's gain;
+        ``automation``: this song's fader moves (``automation()``)."""
         self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
-        self._pans(pans), self._master(master)                 # (checked here as well: before the buffer is made)
+        self._pans(pans), self._master(master), self._automation(automation)      # (checked here as well: before the buffer is made)
         start_frame, nframes = self._range(start_frame, nframes)
         out = Sample(name=self.name, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth)
         levels = None
         if nframes:
             buf = N.DeviceBuffer(nframes * self._fb)
             if meters:
-                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=True, pans=pans, master=master)
+                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=True, pans=pans, master=master, automation=automation)
             else:
-                self.render_into(buf, 0, start_frame, nframes, gains=gains, pans=pans, master=master)
+                self.render_into(buf, 0, start_frame, nframes, gains=gains, pans=pans, master=master, automation=automation)
             out._set_device(buf, nframes * self._fb)
         if meters:
             return out, levels if levels is not None else self._levels(None, 0)
@@ -909,21 +1065,22 @@ class CompiledSequence:
         return self.render(start_frame, nframes, gains=[1.0 if t == track else 0.0 for t in range(self.ntracks)])
 
     def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None, meters: bool = False, pans: Optional[Sequence] = None,
-               master: Optional[float] = None) -> Generator:
-        """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter.  ``gains``, ``pans``, ``master``: as
-        ``render``'s.  ``meters=True``: ``(Sample, SongLevels)`` pairs."""
+               master: Optional[float] = None, automation: Optional[Automation] = None) -> Generator:
+        """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter.  ``gains``, ``pans``, ``master``,
+        ``automation``: as ``render``'s (the joined chunks are the whole render's bytes whatever ``chunk_frames`` cuts).
+        ``meters=True``: ``(Sample, SongLevels)`` pairs."""
         chunk_frames = int(chunk_frames)
         if chunk_frames <= 0:
             raise ValueError("CompiledSequence: chunk_frames must be positive")
         self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
-        self._pans(pans), self._master(master)
+        self._pans(pans), self._master(master), self._automation(automation)
         for at in range(0, self.frames, chunk_frames):
             if meters:
-                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=True, pans=pans, master=master)
+                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=True, pans=pans, master=master, automation=automation)
             else:
-                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, pans=pans, master=master)
+                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, pans=pans, master=master, automation=automation)
 
     def close(self) -> None:
         if self._seq is not None:

@@ -88,7 +88,16 @@ sum-of-squares statistics for each of the 8 tracks, then the same on the master 
 device synchronise, medians, of the whole song and per window of 4096 frames, for: (a) render(gains=, pans=, master=), the one launch;
 (b) the caller's way without it -- eight stems, each amplified and balanced (Sample.stereo), mixed in track order, the mix amplified --
 held to (a)'s bytes first; (c) render(gains=) alone, the launch (a) adds its two steps to.  On a tree without pans= only (c) runs:
-SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequence_ab.py --desk is the parent's own figure for (c)."""
+SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequence_ab.py --desk is the parent's own figure for (c).
+
+--auto: the song of --desk with fader automation: every track has a fade-in over its first 2 to 9 seconds, a long hold at unity and a
+fade-out over its last 3 to 10.  Wall time with a device synchronise, medians, of the whole song and per window of 4096 frames, for:
+(a) render(gains=, pans=, master=, automation=), the one launch; (b) the caller's way -- per track a stem, amplify, per move the whole
+move's stem amplified and faded (Sample.fadein / fadeout), clipped to the window and joined between what lies around it, then stereo, mix
+and the master's amplify -- held to (a)'s bytes first, whole song and a window three frames off inside a fade; (c) render(gains=, pans=,
+master=) without automation.  On a tree without automation= only (c) runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit>
+python tools/sequence_ab.py --auto is the parent's own figure for (c), row (d).  --auto-trace NEVENTS: twenty whole-song renders each of
+(c) and (a) and nothing else, for rocprofv3 --kernel-trace."""
 import audioop
 import os
 import sys
@@ -97,8 +106,8 @@ from pathlib import Path
 
 import numpy as np
 
-# the yardstick of --plan, --tracks and --desk is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
-sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
+# the yardstick of --plan, --tracks, --desk and --auto is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
+sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
 from synthesizer_amd import _native as N  # noqa: E402
 from synthesizer_amd import mixer  # noqa: E402
 from synthesizer_amd.sample import Sample  # noqa: E402
@@ -1147,6 +1156,108 @@ def desk_main():
         bus.close()
 
 
+def auto_lanes(frames):
+    """a fade-in, a long hold at unity and a fade-out on every track: whole seconds, so that Sample.fadein's seconds are exact frames"""
+    return [[(0, (2 + t) * RATE, t / 8.0, 1.0), (frames - (3 + t) * RATE, frames, 1.0, t / 10.0)] for t in range(len(TRACK_GAINS))]
+
+
+def auto_main():
+    """--auto: fader automation in the render's own launch.  (a) render(gains=, pans=, master=, automation=); (b) the caller's way with
+    stems, Sample.fadein / fadeout, clip and join -- held to (a)'s bytes first; (c) render(gains=, pans=, master=).  Wall time with a
+    device synchronise, medians; whole song and 4096-frame windows.  A tree whose render has no automation= runs (c) alone."""
+    import inspect
+    N.ensure_init(0)
+    info = N.device_info()
+    has = "automation" in inspect.signature(mixer.CompiledSequence.render).parameters
+    trace = "--auto-trace" in sys.argv[1:]
+    sizes = (int(sys.argv[sys.argv.index("--auto-trace") + 1]),) if trace else (4096, 32768)
+    print("sequence_auto_ab: SYNTHHIP_SEQ_ALIGN=%s  %s  automation=: %s%s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"],
+          "yes" if has else "no (the yardstick: (c) alone)", "  (trace run: 20 whole-song renders each of (c) and (a))" if trace else ""), flush=True)
+    win, ntracks = 4096, len(TRACK_GAINS)
+    factors = [None if p is None else pan_factors(p) for p in DESK_PANS]
+    desk = dict(gains=TRACK_GAINS, pans=DESK_PANS, master=DESK_MASTER)
+    for nevents in sizes:
+        what, nch, evs = meters_songs(nevents)[0]
+        fb = nch * WIDTH
+        bus = mixer.compile_tracks([evs[t::ntracks] for t in range(ntracks)], RATE, nch, WIDTH)
+        frames = bus.frames
+        out = N.DeviceBuffer(frames * fb + 16)
+        wins = list(range(0, (frames - 3) // win, 16))
+
+        def stream(render):
+            for k in wins:
+                render(k * win, win)
+                N.sync()
+
+        if trace:
+            auto = bus.automation(auto_lanes(frames))
+            for _ in range(20):
+                bus.render_into(out, 0, 0, frames, **desk)
+                bus.render_into(out, 0, 0, frames, automation=auto, **desk)
+            N.sync()
+            print("auto trace, %5d events, %s, %d frames, level %s: done" % (nevents, what, frames, bus.level), flush=True)
+            auto.close()
+            bus.close()
+            continue
+        c_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, **desk), 2, 15)
+        c_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, **desk))
+        c_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, **desk)), 1, 5) / len(wins)
+        fmt = lambda v: " ".join("%.4f" % x for x in v)    # noqa: E731
+        head = "auto song 120 s, %5d events, %s, %d tracks, level %s, %d frames   " % (nevents, what, ntracks, bus.level, frames)
+        tail = "(c) render(gains=, pans=, master=): whole song, wall with a synchronise, median %.4f ms   between two events on the stream, five medians " \
+               "of 15: %s ms   a window of %d frames, wall %.4f ms" % (c_whole, fmt(c_dev), win, c_win)
+        if not has:
+            print(head + tail, flush=True)
+            bus.close()
+            continue
+        lanes = auto_lanes(frames)
+        auto = bus.automation(lanes)
+        at = lambda f: (f + 0.5) / RATE                     # noqa: E731  (seconds that Sample.frame_idx turns back into frame f)
+
+        def caller(a, n):
+            """(b): the window as a caller made it with stems and Sample's fades"""
+            master = Sample(samplerate=RATE, nchannels=nch, samplewidth=WIDTH)
+            for t, g in enumerate(TRACK_GAINS):
+                sub = bus.stem(t, a, n)
+                if g != 1.0:
+                    sub.amplify(g)
+                for pa, pb, v0, v1 in lanes[t]:
+                    lo, hi = max(a, pa), min(a + n, pb)
+                    if lo >= hi:
+                        continue
+                    move = bus.stem(t, pa, pb - pa)         # the whole move: k counts from its first sample, numsamples is its length
+                    if g != 1.0:
+                        move.amplify(g)
+                    move.fadein(move.duration, v0) if v1 == 1.0 else move.fadeout(move.duration, v1)
+                    move.clip(at(lo - pa), at(hi - pa))
+                    behind = sub.copy().clip(at(hi - a), at(n))
+                    sub.clip(0.0, at(lo - a)).join(move).join(behind)
+                if factors[t] is not None:
+                    sub.stereo(*factors[t])
+                master.mix(sub)
+            return master.amplify(DESK_MASTER)
+
+        inside = lanes[3][0][1] // 2 // win * win + 3       # a window three frames off inside track 3's fade-in (and others')
+        assert any(pa < inside and inside + win < pb for lane in lanes for pa, pb, _v0, _v1 in lane)
+        parity = bytes(bus.render(automation=auto, **desk).view_frame_data()) == bytes(caller(0, frames).view_frame_data()) and \
+            bytes(bus.render(inside, win, automation=auto, **desk).view_frame_data()) == bytes(caller(inside, win).view_frame_data())
+        differs = bytes(bus.render(inside, win, automation=auto, **desk).view_frame_data()) != bytes(bus.render(inside, win, **desk).view_frame_data())
+        a_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, automation=auto, **desk), 2, 15)
+        a_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, automation=auto, **desk))
+        a_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, automation=auto, **desk)), 1, 5) / len(wins)
+        b_whole = median_wall(lambda: caller(0, frames), 1, 3)
+        b_win = median_wall(lambda: stream(caller), 1, 3) / len(wins)
+        print(head + "(a) render(gains=, pans=, master=, automation=): whole song, wall with a synchronise, median %.4f ms   between two events on the "
+              "stream, five medians of 15: %s ms   a window, wall %.4f ms   (b) stems, amplify, fadein / fadeout, clip, join, stereo, mix, amplify: whole "
+              "song, wall %.3f ms   a window, wall %.3f ms   %s   (a) / (b) whole %.4f, window %.4f   (a) / (c) whole %.3f, window %.3f   (a)'s bytes "
+              "against (b)'s, whole and a window inside a fade: %s   (a) differs from (c) there: %s"
+              % (a_whole, fmt(a_dev), a_win, b_whole, b_win, tail, a_whole / b_whole, a_win / b_win, a_whole / c_whole, a_win / c_win,
+                 "ok" if parity else "FAILED", "yes" if differs else "NO"), flush=True)
+        assert parity and differs
+        auto.close()
+        bus.close()
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -1217,4 +1328,4 @@ def main():
 
 
 if __name__ == "__main__":
-    desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
