@@ -825,6 +825,37 @@ int sh_seq_render_auto(const sh_seq* seq, size_t first_sample, size_t nsamples, 
                        uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters,
                        const sh_seq_auto* automation);
 
+/* The desk's GROUP BUSES: at most SH_SEQ_MAX_GROUPS runs of consecutive tracks [first, end), ascending and not overlapping, given when a
+ * window is rendered; the tracks of a group are mixed into a bus of their own, which saturates ON ITS OWN, takes one gain and one pan and
+ * enters the master where the group's LAST track stands.  sh_seq_render_groups is sh_seq_render_auto with that level between the tracks
+ * and the master; still one launch, nothing uploaded by a render (the group table travels by value):
+ *     master = silence; for t in tracks, in order:
+ *         sub = the track's events folded from silence; its gain, its fader moves, its pan    (as sh_seq_render_auto)
+ *         if t lies in group g:
+ *             if t == first_g: bus = silence
+ *             bus = audioop.add(bus, sub)
+ *             if t == end_g - 1:
+ *                 if gain_g != 1.0: bus = audioop.mul(bus, gain_g)                            (clamp, then floor: ONE rounding over the sum)
+ *                 bus = (fbound(L * left_g), fbound(R * right_g)) per frame (L, R)              (a factor of exactly 1.0: none)
+ *                 master = audioop.add(master, bus)
+ *         else: master = audioop.add(master, sub)
+ *     if master_gain != 1.0: master = audioop.mul(master, master_gain)
+ * -- not a gain on each track (floor(g (a + b)) != floor(g a) + floor(g b)) and not the flat list (the group clips before the master
+ * sees it).  A group whose gain is exactly 0.0, or whose factors are both exactly 0.0, skips its tracks' events as a muted track does;
+ * its row and its tracks' rows read zero.  automation may be NULL (no fader moves); gains, pans and master_gain as sh_seq_render_desk's.
+ * meters: NULL, or ntracks + 1 + ngroups rows -- the tracks and the master where sh_seq_render_desk has them, group g in row
+ * ntracks + 1 + g, over what the master takes of it (behind its gain and pan); a track's row is what its bus takes of it.
+ * SH_ERR_INVALID, nothing launched, `out` and `meters` untouched: what sh_seq_render_desk refuses and, with a handle, what
+ * sh_seq_render_auto refuses (an automation handle at width 3 among it); ngroups == 0 or > SH_SEQ_MAX_GROUPS; groups == NULL; an entry
+ * with first >= end, with end > ntracks, or that starts in front of the previous entry's end; a gain or factor that is not finite;
+ * factors other than (1.0, 1.0) on a song that is not stereo; nmeters other than ntracks + 1 + ngroups where meters is given.  The
+ * error text names the entry.  Not built: automation of a group, groups inside groups. */
+typedef struct sh_seq_group { uint32_t first, end; double gain; double left, right; } sh_seq_group;   /* 32 bytes */
+#define SH_SEQ_MAX_GROUPS 8u
+int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                         uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters,
+                         const sh_seq_auto* automation /* may be NULL */, const sh_seq_group* groups, uint32_t ngroups);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

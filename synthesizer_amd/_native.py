@@ -97,6 +97,11 @@ class SeqMeter(C.Structure):                                                    
     _fields_ = [("peak", C.c_uint32 * 2), ("sq_hi", C.c_uint64 * 2), ("sq_lo", C.c_uint64 * 2)]
 
 
+class SeqGroup(C.Structure):                                                         # sh_seq_group
+    _fields_ = [("first", C.c_uint32), ("end", C.c_uint32), ("gain", C.c_double), ("left", C.c_double), ("right", C.c_double)]
+
+
+SEQ_MAX_GROUPS = 8                                                                    # SH_SEQ_MAX_GROUPS
 SEQ_LEVELS = ("plain", "rate", "pan", "env", "loop", "rev", "chan")                   # SH_SEQ_LEVEL_*
 
 
@@ -211,6 +216,8 @@ _SIGNATURES = {
     "sh_seq_auto_destroy": (C.c_int, [_P]),
     "sh_seq_render_auto": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
                                      C.c_double, C.POINTER(SeqMeter), C.c_uint32, _P]),
+    "sh_seq_render_groups": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
+                                       C.c_double, C.POINTER(SeqMeter), C.c_uint32, _P, C.POINTER(SeqGroup), C.c_uint32]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),
@@ -470,11 +477,13 @@ class Sequence:
         return nt.value, nr.value
 
     def render(self, first_sample: int, nsamples: int, out: "DeviceBuffer", out_sample: int = 0, gains=None, meters: bool = False, pans=None,
-               master=None, automation: Optional["SeqAutomation"] = None):
+               master=None, automation: Optional["SeqAutomation"] = None, groups=None):
         """``meters=True`` (a song of tracks): sh_seq_render_meters -- the same bytes and, from the same launch, one row per track and one for
         the master, each ``(peak, sum_squares)`` of per-channel pairs, the sums exact Python ints.  Otherwise None.
         ``pans`` (2 * ntracks factors, left then right per track) or ``master`` (a gain) given: sh_seq_render_desk, with or without meters.
-        ``automation`` (a ``SeqAutomation`` of this song) given: sh_seq_render_auto, with or without any of the others."""
+        ``automation`` (a ``SeqAutomation`` of this song) given: sh_seq_render_auto, with or without any of the others.
+        ``groups`` (a non-empty list of ``(first_track, end_track, gain, left, right)``) given: sh_seq_render_groups, with or without any
+        of the others; the rows of the groups follow the master's."""
         def doubles(v):
             return None if v is None else (C.c_double * max(1, len(v)))(*v)
 
@@ -483,9 +492,14 @@ class Sequence:
         desk = pans is not None or master is not None
         rows, nrows = None, 0
         if meters:
-            nrows = self.tracks()[0] + 1
+            nrows = self.tracks()[0] + 1 + (len(groups) if groups else 0)
             rows = (SeqMeter * nrows)()
-        if automation is not None:
+        if groups:
+            table = (SeqGroup * len(groups))(*[SeqGroup(*g) for g in groups])
+            check(lib().sh_seq_render_groups(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans),
+                                             count(pans), 1.0 if master is None else master, rows, nrows,
+                                             None if automation is None else automation.handle, table, len(groups)))
+        elif automation is not None:
             check(lib().sh_seq_render_auto(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans), count(pans),
                                            1.0 if master is None else master, rows, nrows, automation.handle))
         elif desk:

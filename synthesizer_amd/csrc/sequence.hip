@@ -60,13 +60,17 @@
 // last run the master by the master's gain, once, in front of its meter row and the store.  The AUTOMATION buses, SeqBusA and SeqBusAM,
 // are the desk buses again with a table of fader moves per track (seqauto.hpp; sh_seq_auto_create uploads it once, sh_seq_render_auto
 // passes its two pointers by value): in seq_runs the sub-mix by its gain, THEN through the track's segments at its song positions
-// (int(x * f), the fade's truncation), then the pan, the hook and the add.
+// (int(x * f), the fade's truncation), then the pan, the hook and the add.  The GROUP buses, SeqBusG and SeqBusGM (width 3: SeqBusG3,
+// SeqBusGM3), are the whole desk again with a table of group buses by value (seqgroup.hpp; sh_seq_render_groups): in seq_runs a third
+// accumulator between sub and acc takes the tracks of the open group and is closed -- the group's gain, its pan, the hook for its row,
+// the add into the master -- in front of the first run that is not of the group and behind the last run.
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
 #include "ratecv.hpp"
 #include "seqauto.hpp"
 #include "seqenv.hpp"
+#include "seqgroup.hpp"
 #include "seqloop.hpp"
 #include "seqmeter.hpp"
 #include "seqrev.hpp"
@@ -902,6 +906,22 @@ struct SeqAuto {
 struct SeqBusA : SeqBusD, SeqAuto {};
 template <typename... Bus> constexpr bool SEQ_AUTO = (std::is_base_of<SeqAuto, Bus>::value || ...);
 
+// GROUP BUSES (sh_seq_render_groups): runs of consecutive tracks mixed into a bus of their own between the track and the master -- the
+// table of seqgroup.hpp by value in the kernel arguments, 232 more bytes, read at wave-uniform indices as the gains are; a render still
+// uploads nothing.  A bus lane keeps a THIRD accumulator, grp, between sub and acc: a track of a group is added, saturating, into grp
+// and not into acc; where the next run's track belongs to another group or to none, and behind the last run, the open group is CLOSED:
+// grp by the group's gain (audioop.mul, one rounding over the saturated sum), by its pan factors, the hook for its meter row, the
+// saturating add into acc -- seq_scale8 / seq_pan8 / seq_scale_w / seq_mul_add_w one level up.  The runs of a tile come in track
+// order, so a group enters the master where its last track stands; tracks without a run in the tile add zeros, and a group without one
+// never opens (fbound(0 * g) == 0).  A group at gain 0.0 or pan (0.0, 0.0) skips its tracks' events as a muted track does.  These
+// buses carry the WHOLE desk so that the kernel count does not double: at widths 1, 2 and 4 the automation's two pointers as well,
+// NULL meaning no moves (a uniform branch); width 3, which has no automation, derives them from the desk buses.
+struct SeqGroups { shg::Table groups; };
+struct SeqBusG : SeqBusA, SeqGroups {};
+struct SeqBusG3 : SeqBusD, SeqGroups {};
+template <typename... Bus> constexpr bool SEQ_GROUPS = (std::is_base_of<SeqGroups, Bus>::value || ...);
+static_assert(shg::MAX_TRACKS == shq::MAX_TRACKS && sizeof(SeqBusG) == sizeof(SeqBusA) + sizeof(shg::Table), "the groups: 232 bytes of kernel arguments behind the bus");
+
 // a lane's accumulator: eight packed samples at 16 bits, four 64-bit sums at the other widths
 template <int WIDTH> struct SeqAcc { typedef llong4v type; };
 template <> struct SeqAcc<2> { typedef short8v type; };
@@ -936,11 +956,34 @@ __device__ __forceinline__ void seq_master(typename SeqAcc<WIDTH>::type& acc, co
 }
 
 // The runs of tile k, written once for the three templates and every bus: the events from e on, run by run.  walk(e, e1, sub): the
-// schedule of the kernel, events [e, e1) into sub; hook(sub, track): what else a bus does with a track's samples as the master takes them,
+// schedule of the kernel, events [e, e1) into sub; hook(sub, row): what else a bus does with a track's samples as its bus takes them,
 // post-fader and (a desk bus) post-pan (the metering buses: its row).  Everything about a run is uniform, and a run lists at least one event.
 // An automation bus: the track's fader moves between the gain and the pan, at the lane's SONG positions (tile k starts at k * TILE).
+// A group bus: a track of a group goes into grp, the open group's bus, and a group is closed -- its gain, its pan, hook(grp, its row),
+// into acc -- in front of the first run that is not of it and behind the last run; opening and closing are uniform.
 template <int WIDTH, typename Bus, typename Walk, typename Hook>
 __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e, typename SeqAcc<WIDTH>::type& acc, Walk walk, Hook hook) {
+    [[maybe_unused]] typename SeqAcc<WIDTH>::type grp = {};  // (a group bus: the open group's samples)
+    [[maybe_unused]] uint32_t open = shg::NONE, of = shg::NONE;
+    [[maybe_unused]] auto close = [&] {                       // the open group into the master
+        if constexpr (SEQ_GROUPS<Bus>) {
+            const double gg = bus.groups.gain[open], gl = bus.groups.pan[2 * open], gr = bus.groups.pan[2 * open + 1];
+            if constexpr (WIDTH == 2) {
+                grp = seq_pan8(seq_scale8(grp, gg), gl, gr);
+                hook(grp, bus.groups.row0 + open);
+                acc = __builtin_elementwise_add_sat(acc, grp);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    long long x = seq_scale_w<WIDTH>(grp[j], gg);
+                    acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, j & 1 ? gr : gl);
+                    grp[j] = x;
+                }
+                hook(grp, bus.groups.row0 + open);
+            }
+            open = shg::NONE;
+        }
+    };
     const uint32_t r1 = bus.rfirst[k + 1];
     for (uint32_t r = bus.rfirst[k]; r < r1; ++r) {
         const shq::Run run = bus.runs[r];
@@ -952,18 +995,34 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
             right = bus.pan[2 * run.track + 1];
             silent = silent || (left == 0.0 && right == 0.0);
         }
+        if constexpr (SEQ_GROUPS<Bus>) {
+            of = shg::group_of(bus.groups, run.track);
+            if (open != shg::NONE && of != open) close();
+            if (of != shg::NONE)
+                silent = silent || bus.groups.gain[of] == 0.0 || (bus.groups.pan[2 * of] == 0.0 && bus.groups.pan[2 * of + 1] == 0.0);
+        }
         if (silent) {
             e = run.end;
             continue;
+        }
+        if constexpr (SEQ_GROUPS<Bus>) {
+            if (of != shg::NONE && open == shg::NONE) {       // the group opens: from silence
+                grp = typename SeqAcc<WIDTH>::type{};
+                open = of;
+            }
         }
         [[maybe_unused]] const she::Seg* asegs = nullptr;    // (an automation bus: the track's segments, from the first that ends past t0)
         [[maybe_unused]] uint32_t an = 0, ai = 0;
         [[maybe_unused]] const uint32_t t0 = k * SEQ_TILE<WIDTH>;
         if constexpr (SEQ_AUTO<Bus>) {
-            const uint32_t a0 = bus.afirst[run.track];
-            asegs = bus.asegs + a0;
-            an = bus.afirst[run.track + 1] - a0;
-            ai = sha::find(asegs, an, t0);
+            bool moves = true;
+            if constexpr (SEQ_GROUPS<Bus>) moves = bus.asegs != nullptr;      // (uniform: a group bus without automation)
+            if (moves) {
+                const uint32_t a0 = bus.afirst[run.track];
+                asegs = bus.asegs + a0;
+                an = bus.afirst[run.track + 1] - a0;
+                ai = sha::find(asegs, an, t0);
+            }
         }
         if constexpr (WIDTH == 2) {
             short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -981,7 +1040,10 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
             }
             if constexpr (SEQ_DESK<Bus>) sub = seq_pan8(sub, left, right);
             hook(sub, run.track);
-            acc = __builtin_elementwise_add_sat(acc, sub);
+            bool grouped = false;
+            if constexpr (SEQ_GROUPS<Bus>) grouped = of != shg::NONE;
+            if (grouped) grp = __builtin_elementwise_add_sat(grp, sub);
+            else acc = __builtin_elementwise_add_sat(acc, sub);
         } else {
             llong4v sub = {0, 0, 0, 0};
             walk(e, run.end, sub);
@@ -994,21 +1056,37 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
 #pragma unroll
                 for (int j = 0; j < 4; ++j) sub[j] = v[j];
             }
+            if constexpr (SEQ_GROUPS<Bus>) {                  // (the desk's steps into the bus that takes the track: whole values, uniform)
+                llong4v into = of != shg::NONE ? grp : acc;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                long long x = sub[j];
-                if constexpr (SEQ_AUTO<Bus>) {                // (scaled and shaped above)
-                    acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, j & 1 ? right : left);
-                } else if constexpr (SEQ_DESK<Bus>) {         // the gain, then the pan: two roundings
-                    x = seq_scale_w<WIDTH>(x, g);
-                    acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, j & 1 ? right : left);
-                } else {
-                    acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, g);
+                for (int j = 0; j < 4; ++j) {
+                    long long x = sub[j];
+                    if constexpr (!SEQ_AUTO<Bus>) x = seq_scale_w<WIDTH>(x, g);
+                    into[j] = seq_mul_add_w<WIDTH>(into[j], x, j & 1 ? right : left);
+                    sub[j] = x;
                 }
-                sub[j] = x;
+                if (of != shg::NONE) grp = into;
+                else acc = into;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    long long x = sub[j];
+                    if constexpr (SEQ_AUTO<Bus>) {            // (scaled and shaped above)
+                        acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, j & 1 ? right : left);
+                    } else if constexpr (SEQ_DESK<Bus>) {     // the gain, then the pan: two roundings
+                        x = seq_scale_w<WIDTH>(x, g);
+                        acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, j & 1 ? right : left);
+                    } else {
+                        acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, g);
+                    }
+                    sub[j] = x;
+                }
             }
             hook(sub, run.track);
         }
+    }
+    if constexpr (SEQ_GROUPS<Bus>) {
+        if (open != shg::NONE) close();                       // (uniform)
     }
 }
 
@@ -1034,10 +1112,17 @@ template <typename... Bus> struct SeqMetered : std::false_type {};
 template <> struct SeqMetered<SeqBusM> : std::true_type {};
 template <> struct SeqMetered<SeqBusDM> : std::true_type {};
 template <> struct SeqMetered<SeqBusAM> : std::true_type {};
+// The group buses with meters: ntracks + 1 + ngroups rows -- tracks and the master where they were, group g in row ntracks + 1 + g, over
+// what the master takes of it (behind its gain and pan); a track's row stays what its bus takes of it.  A table of their own size in LDS.
+struct SeqBusGM : SeqBusAM, SeqGroups {};
+struct SeqBusGM3 : SeqBusDM, SeqGroups {};
+template <> struct SeqMetered<SeqBusGM> : std::true_type {};
+template <> struct SeqMetered<SeqBusGM3> : std::true_type {};
 
-// the workgroup's row table, zeroed: every lane of the workgroup calls it (a barrier)
+// the workgroup's row table, zeroed: every lane of the workgroup calls it (a barrier).  ROWS: 33, or 41 with the rows of the groups
+template <uint32_t ROWS = shq::MAX_TRACKS + 1>
 __device__ __forceinline__ shmt::Row* seq_meter_begin() {
-    __shared__ shmt::Row table[shq::MAX_TRACKS + 1];
+    __shared__ shmt::Row table[ROWS];
     uint32_t* w = reinterpret_cast<uint32_t*>(table);
     for (uint32_t i = threadIdx.x; i < sizeof(table) / 4; i += shq::TILE_THREADS) w[i] = 0u;
     __syncthreads();
@@ -1075,11 +1160,13 @@ __device__ __forceinline__ void seq_meter_wave(shmt::Row r, const bool stereo, s
 }
 
 // the workgroup's table into the handle's: every lane of the workgroup calls it (a barrier), lane 2 row + channel carries one value each
+// (groups: the rows of a group bus behind the master's; 2 * 41 lanes at the most, of TILE_THREADS)
 template <bool WIDE>
-__device__ __forceinline__ void seq_meter_end(const shmt::Row* table, const SeqBusM& bus) {
+__device__ __forceinline__ void seq_meter_end(const shmt::Row* table, const SeqBusM& bus, const uint32_t groups = 0) {
+    static_assert(2 * (shq::MAX_TRACKS + 1 + shg::MAX_GROUPS) <= shq::TILE_THREADS, "a lane per row and channel");
     __syncthreads();
     const uint32_t row = threadIdx.x >> 1, c = threadIdx.x & 1u;
-    if (row > bus.ntracks) return;
+    if (row > bus.ntracks + groups) return;
     const uint32_t peak = table[row].peak[c];
     if (!peak) return;
     shmt::Row* g = bus.meters + row;
@@ -1102,17 +1189,20 @@ __device__ __forceinline__ void seq_window_bus(const Bus& bus, uint32_t k, uint3
     } else {
         constexpr bool WIDE = WIDTH >= 3;
         constexpr int N = SEQ_LANE<WIDTH>;
-        shmt::Row* table = seq_meter_begin();
+        shmt::Row* table;
+        if constexpr (SEQ_GROUPS<Bus>) table = seq_meter_begin<shq::MAX_TRACKS + 1 + shg::MAX_GROUPS>();
+        else table = seq_meter_begin();
         const bool stereo = bus.nch == 2;
         if (__builtin_amdgcn_ballot_w64(s0 < hi && s0 + N > lo)) {                    // (uniform: a wave with a lane in the window)
-            seq_runs<WIDTH>(bus, k, e, acc, walk, [&](const typename SeqAcc<WIDTH>::type& sub, uint32_t track) {
-                seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(sub, s0, lo, hi, bus.nch), stereo, table + track);
+            seq_runs<WIDTH>(bus, k, e, acc, walk, [&](const typename SeqAcc<WIDTH>::type& sub, uint32_t row) {
+                seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(sub, s0, lo, hi, bus.nch), stereo, table + row);
             });
             if constexpr (SEQ_DESK<Bus>) seq_master<WIDTH>(acc, bus.master);
             seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
             store();
         }
-        seq_meter_end<WIDE>(table, bus);
+        if constexpr (SEQ_GROUPS<Bus>) seq_meter_end<WIDE>(table, bus, bus.groups.n);
+        else seq_meter_end<WIDE>(table, bus);
     }
 }
 
@@ -1610,7 +1700,8 @@ void seq_with_level(int level, F f) {
 // Which window kernel: the width, at 16 bits the way misaligned event samples are read and whether the biased base lies on a 16-byte
 // boundary.  bus: nothing (a flat list), a SeqBus (a song of tracks: the same kernels with the bus, the gains by value), a SeqBusM (the
 // metering bus: the rows go to the handle's table) or one of the two with the desk (SeqBusD, SeqBusDM: pans and the master's gain by
-// value as well), forwarded as the kernels' trailing pack.
+// value as well), with automation (SeqBusA, SeqBusAM) or with groups (SeqBusG, SeqBusGM; width 3: SeqBusG3, SeqBusGM3), forwarded as
+// the kernels' trailing pack.
 template <int LEVEL, typename... Bus>
 void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out, const Bus&... bus) {
     typedef typename SeqRec<LEVEL>::type Rec;
@@ -1623,7 +1714,11 @@ void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, 
     // the whole song: heaviest tile first (measured: profiles/sequence_plan_ab.txt); any other window: its tiles in song order
     const uint32_t* order = lo == 0 && hi == q->track_samples ? (const uint32_t*)(b + q->at_order) : nullptr;
     const dim3 block(shq::TILE_THREADS);
-    if (q->width == 2) {
+    constexpr bool W3 = SEQ_GROUPS<Bus...> && !SEQ_AUTO<Bus...>;      // a group bus derived from a desk bus: width 3's, and only width 3's
+    if constexpr (W3) {
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out, bus...); };
+        if constexpr (LEVEL != ENV) go(k_win_w<LEVEL, 3, BUS, Bus...>);
+    } else if (q->width == 2) {
         const int aligned = ((uintptr_t)out & 15) == 0;       // the BIASED base: song-anchored lanes start on multiples of eight samples
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (short*)out, aligned, bus...); };
         const bool vec2 = sh::knobs().seq_align == VEC2;
@@ -1722,7 +1817,8 @@ int seq_create(const char* fn, const sh_buf* const* srcs, uint32_t nsrc, const s
         if (!R.runs.empty()) memcpy(host.data() + q->at_runs, R.runs.data(), R.runs.size() * sizeof(shq::Run));
         memcpy(host.data() + q->at_rfirst, R.rfirst.data(), R.rfirst.size() * 4);
     }
-    rc = sh::pool_alloc(q->bytes, &q->block, &q->cap);
+    // (a song of tracks: behind the song's tables, which `bytes` counts, room for the rows of a metered render's groups)
+    rc = sh::pool_alloc(q->bytes + (tracks ? shg::MAX_GROUPS * sizeof(shmt::Row) : 0), &q->block, &q->cap);
     if (rc) {
         delete q;
         return rc;
@@ -1762,14 +1858,17 @@ int seq_desk(const char* fn, const double* pans, uint32_t npans, double master_g
     return SH_OK;
 }
 
+template <typename T> struct SeqBaseOf { typedef T type; };
+
 // sh_seq_render (gains NULL: every track at 1.0), sh_seq_render_gains, sh_seq_render_meters (meters: ntracks + 1 host rows, the handle
 // has tracks), sh_seq_render_desk (desk: the pans and the master's gain, the handle has tracks; with or without meters) and
-// sh_seq_render_auto (au: the automation's table, with a desk) behind their names
+// sh_seq_render_auto (au: the automation's table, with a desk) and sh_seq_render_groups (groups: the group table, with a desk, with or
+// without au; meters: ntracks + 1 + ngroups rows) behind their names
 int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains,
-               sh_seq_meter* meters = nullptr, const SeqDesk* desk = nullptr, const SeqAuto* au = nullptr) {
+               sh_seq_meter* meters = nullptr, const SeqDesk* desk = nullptr, const SeqAuto* au = nullptr, const shg::Table* groups = nullptr) {
     static_assert(sizeof(sh_seq_meter) == sizeof(shmt::Row) && offsetof(sh_seq_meter, sq_hi) == offsetof(shmt::Row, sq_hi) &&
                   offsetof(sh_seq_meter, sq_lo) == offsetof(shmt::Row, sq_lo), "sh_seq_meter is shmt::Row");
-    const size_t b_meters = meters ? ((size_t)seq->ntracks + 1) * sizeof(shmt::Row) : 0;
+    const size_t b_meters = meters ? ((size_t)seq->ntracks + 1 + (groups ? groups->n : 0)) * sizeof(shmt::Row) : 0;
     const size_t w = (size_t)seq->width;
     if (first_sample > seq->track_samples || nsamples > seq->track_samples - first_sample)
         return sh::set_error(SH_ERR_INVALID, "%s: range outside the song", fn);
@@ -1807,7 +1906,19 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
         if (!seq->ntracks) seq_window_launch<LEVEL>(seq, grid, st, lo, hi, biased);
         else if (!desk && !meters) seq_window_launch<LEVEL, SeqBus>(seq, grid, st, lo, hi, biased, bus);
         else if (!desk) seq_window_launch<LEVEL, SeqBusM>(seq, grid, st, lo, hi, biased, bus);
-        else if (au && meters) {
+        else if (groups) {                                    // (with a desk: the whole desk rides on a group bus, au or none)
+            auto grouped = [&](auto moved, auto base) {       // moved: the group bus; base: which bus of the handle's it is made of
+                typedef decltype(moved) G;
+                typedef typename decltype(base)::type B;
+                static_cast<B&>(moved) = bus;
+                static_cast<SeqDesk&>(moved) = bus;
+                if constexpr (SEQ_AUTO<G>) static_cast<SeqAuto&>(moved) = au ? *au : SeqAuto{nullptr, nullptr};
+                moved.groups = *groups;
+                seq_window_launch<LEVEL, G>(seq, grid, st, lo, hi, biased, moved);
+            };
+            if (seq->width == 3) meters ? grouped(SeqBusGM3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG3{}, SeqBaseOf<SeqBus>());
+            else meters ? grouped(SeqBusGM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG{}, SeqBaseOf<SeqBus>());
+        } else if (au && meters) {
             SeqBusAM moved{};
             static_cast<SeqBusDM&>(moved) = bus;
             static_cast<SeqAuto&>(moved) = *au;
@@ -2001,6 +2112,56 @@ int sh_seq_render_auto(const sh_seq* seq, size_t first_sample, size_t nsamples, 
     if (rc) return rc;
     const SeqAuto au{(const she::Seg*)automation->block, (const uint32_t*)((const char*)automation->block + automation->at_first)};
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, &au);
+}
+
+int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                         uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters,
+                         const sh_seq_auto* automation, const sh_seq_group* groups, uint32_t ngroups) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_seq_render_groups";
+    static_assert(sizeof(sh_seq_group) == sizeof(shg::Group) && offsetof(sh_seq_group, gain) == offsetof(shg::Group, gain) &&
+                  offsetof(sh_seq_group, right) == offsetof(shg::Group, right) && SH_SEQ_MAX_GROUPS == shg::MAX_GROUPS, "sh_seq_group is shg::Group");
+    if (!seq || !out || (!gains && ngains) || (!pans && npans) || (!meters && nmeters)) return seq_null(fn);
+    if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
+    if (automation) {
+        if (seq->width == 3) return sh::set_error(SH_ERR_INVALID, "%s: width 3: a fader move's fade has no 24-bit form", fn);
+        if (automation->ntracks != seq->ntracks || automation->width != seq->width || automation->nchannels != seq->nchannels ||
+            automation->track_samples != seq->track_samples)
+            return sh::set_error(SH_ERR_INVALID, "%s: the automation was made for another song (%u tracks, width %d, %d channels, %llu samples)", fn,
+                                 automation->ntracks, automation->width, automation->nchannels, (unsigned long long)automation->track_samples);
+    }
+    if (pans && seq->nchannels != 2) return sh::set_error(SH_ERR_INVALID, "%s: pans need a stereo song, this one has %d channels", fn, seq->nchannels);
+    if (gains && ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
+    if (pans && npans != 2 * seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u pan factors for %u tracks (two each)", fn, npans, seq->ntracks);
+    if (ngroups == 0 || ngroups > shg::MAX_GROUPS) return sh::set_error(SH_ERR_INVALID, "%s: %u groups, 1 to %u", fn, ngroups, shg::MAX_GROUPS);
+    if (!groups) return seq_null(fn);
+    const shg::Group* gs = reinterpret_cast<const shg::Group*>(groups);
+    const shg::Verdict v = shg::check(gs, ngroups, seq->ntracks, seq->nchannels);
+    const sh_seq_group& b = groups[v.entry];
+    switch (v.why) {
+    case shg::OK: break;
+    case shg::RANGE_EMPTY: return sh::set_error(SH_ERR_INVALID, "%s: group %u: tracks [%u, %u): an empty range", fn, v.entry, b.first, b.end);
+    case shg::RANGE_BEYOND: return sh::set_error(SH_ERR_INVALID, "%s: group %u: tracks [%u, %u) of %u", fn, v.entry, b.first, b.end, seq->ntracks);
+    case shg::RANGE_ORDER:
+        return sh::set_error(SH_ERR_INVALID, "%s: group %u: starts at track %u, in front of the end of the group before it", fn, v.entry, b.first);
+    case shg::GAIN_NOT_FINITE: return sh::set_error(SH_ERR_INVALID, "%s: group %u: gain is not finite", fn, v.entry);
+    case shg::PAN_NOT_FINITE: return sh::set_error(SH_ERR_INVALID, "%s: group %u: left / right is not finite", fn, v.entry);
+    case shg::PAN_NOT_STEREO:
+        return sh::set_error(SH_ERR_INVALID, "%s: group %u: a pan needs a stereo song, this one has %d channels", fn, v.entry, seq->nchannels);
+    default: return sh::set_error(SH_ERR_INVALID, "%s: %u groups, 1 to %u", fn, ngroups, shg::MAX_GROUPS);
+    }
+    if (meters && nmeters != seq->ntracks + 1 + ngroups)
+        return sh::set_error(SH_ERR_INVALID, "%s: %u rows for %u tracks, the master and %u groups", fn, nmeters, seq->ntracks, ngroups);
+    SeqGains g;
+    SeqDesk d;
+    int rc = seq_gains(fn, gains, ngains, g);
+    if (!rc) rc = seq_desk(fn, pans, npans, master_gain, d);
+    if (rc) return rc;
+    shg::Table table;
+    shg::pack(gs, ngroups, seq->ntracks, table);
+    SeqAuto au{nullptr, nullptr};
+    if (automation) au = SeqAuto{(const she::Seg*)automation->block, (const uint32_t*)((const char*)automation->block + automation->at_first)};
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, automation ? &au : nullptr, &table);
 }
 
 int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns) {

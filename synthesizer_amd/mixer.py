@@ -639,14 +639,20 @@ class Levels:
 class SongLevels:
     """What a metered render returns beside its bytes: ``tracks``, one ``Levels`` per track, POST-fader (over the track as the master takes
     it: folded on its own, times its gain; a muted track reads zero), and ``master``, over the window's output -- all from the one launch
-    that rendered the window.  ``rows``: ``N.Sequence.render(meters=True)``'s, the master last."""
+    that rendered the window.  ``groups``: one ``Levels`` per group bus of a render with ``groups=``, over the bus as the master takes it
+    (behind the group's gain and pan); empty without groups.  ``rows``: ``N.Sequence.render(meters=True)``'s -- the tracks, the master,
+    then the ``ngroups`` groups."""
 
-    def __init__(self, rows, frames: int, samplewidth: int, nchannels: int, samplerate: int) -> None:
+    def __init__(self, rows, frames: int, samplewidth: int, nchannels: int, samplerate: int, ngroups: int = 0) -> None:
         made = [Levels(peak, sq, frames, samplewidth, nchannels, samplerate) for peak, sq in rows]
-        self.tracks: List[Levels] = made[:-1]
-        self.master: Levels = made[-1]
+        at = len(made) - 1 - ngroups
+        self.tracks: List[Levels] = made[:at]
+        self.master: Levels = made[at]
+        self.groups: List[Levels] = made[at + 1:]
 
     def __repr__(self) -> str:
+        if self.groups:
+            return "SongLevels(tracks=%r, master=%r, groups=%r)" % (self.tracks, self.master, self.groups)
         return "SongLevels(tracks=%r, master=%r)" % (self.tracks, self.master)
 
 
@@ -756,7 +762,37 @@ class CompiledSequence:
     that slice of the whole song's whatever the window: positions count from the piece's first sample in the song.  Post-fader meters read
     a track behind its moves, as the master takes it; a muted track is still skipped; ``stem`` stays plain.  Still one launch per window
     and nothing uploaded by a render.  Width 3 has no automation (``NotImplementedError``: upstream's fades have no 24-bit form, as for
-    envelopes)."""
+    envelopes).
+    The desk's GROUP BUSES: ``groups=`` of ``render``, ``render_into`` and ``chunks`` is a list of at most 8 entries ``(first_track,
+    end_track, gain)`` or ``(first_track, end_track, gain, pan)`` -- runs of consecutive tracks ``[first_track, end_track)``, ascending
+    and not overlapping; ``gain`` a finite number or None for 1.0; ``pan`` what one entry of ``pans`` may be, on stereo songs only.  A
+    track outside every entry goes straight to the master.  The chain is, byte for byte, ::
+
+        master = Sample(...)
+        for t, events in enumerate(tracks):
+            sub = sequence(events, ...)                     # then its gain, its fader moves and its pan, as above
+            if t lies in group g:
+                if t == first_g:
+                    bus = Sample(...)
+                bus.mix(sub)                                # the group saturates ON ITS OWN, at every track
+                if t == end_g - 1:
+                    if gain_g != 1.0:
+                        bus.amplify(gain_g)                 # audioop.mul: ONE rounding over the saturated sum
+                    if pan_g is not None:
+                        bus.stereo(lf_g, rf_g)
+                    master.mix(bus)                         # the group enters the master where its LAST track stands
+            else:
+                master.mix(sub)
+        if master_gain != 1.0:
+            master.amplify(master_gain)
+
+    -- not a gain on each track (``floor(g * (a + b)) != floor(g * a) + floor(g * b)``) and not the flat list (the group clips before
+    the master sees it).  A group whose gain is exactly 0.0, or whose pan factors are both exactly 0.0, skips its tracks' events as a
+    muted track does; its levels and its tracks' read zero.  With ``meters=True`` ``SongLevels.groups`` holds one ``Levels`` per group,
+    over the bus as the master takes it, behind its gain and pan; a track's levels stay what its bus takes of it.  A group's bus alone
+    is already ``render(gains=<solo of its tracks>)``.  Still one launch per window and nothing uploaded by a render; ``groups=None``
+    or an empty list is the render without groups.  Not built: automation lanes on a group, groups inside groups, a ``stem`` of a
+    group."""
 
     MAX_TRACKS = 32
 
@@ -881,11 +917,82 @@ class CompiledSequence:
         return None if master == 1.0 else master
 
     @staticmethod
-    def _desk(pans, master, automation=None) -> dict:
+    def _desk(pans, master, automation=None, groups=None) -> dict:
         """the keywords of the desk for N.Sequence.render: none at all where no step is asked for (the entry points there were)"""
+        if groups is not None:
+            desk = {"pans": pans, "master": master, "groups": groups}
+            if automation is not None:
+                desk["automation"] = automation
+            return desk
         if automation is not None:
             return {"pans": pans, "master": master, "automation": automation}
         return {} if pans is None and master is None else {"pans": pans, "master": master}
+
+    MAX_GROUPS = N.SEQ_MAX_GROUPS
+
+    def _groups(self, groups) -> Optional[list]:
+        """``groups`` as render hands them on: None (None or an empty list: no group bus), or a list of ``(first_track, end_track, gain,
+        left_factor, right_factor)`` -- integers and finite floats, (1.0, 1.0) where the entry has no pan -- checked before anything is
+        launched"""
+        if groups is None:
+            return None
+        if self.ntracks is None:
+            raise ValueError("CompiledSequence: groups need a song of tracks (compile_tracks); this one has none")
+        if isinstance(groups, (str, bytes)) or not hasattr(groups, "__len__"):
+            raise ValueError("CompiledSequence: groups is a sequence of (first_track, end_track, gain) or (first_track, end_track, gain, pan)")
+        if len(groups) > self.MAX_GROUPS:
+            raise ValueError("CompiledSequence: %d groups, at most %d" % (len(groups), self.MAX_GROUPS))
+        out, prev = [], 0
+        for k, entry in enumerate(groups):
+            where = "CompiledSequence: group %d: " % k
+            if isinstance(entry, (str, bytes)) or not hasattr(entry, "__len__") or len(entry) not in (3, 4):
+                raise ValueError(where + "an entry is (first_track, end_track, gain) or (first_track, end_track, gain, pan)")
+            try:
+                if isinstance(entry[0], bool) or isinstance(entry[1], bool):
+                    raise TypeError
+                first, end = operator.index(entry[0]), operator.index(entry[1])
+            except TypeError:
+                raise ValueError(where + "first_track and end_track are integers") from None
+            if first < 0 or end > self.ntracks:
+                raise ValueError(where + "tracks [%d, %d) outside the song's %d tracks" % (first, end, self.ntracks))
+            if first >= end:
+                raise ValueError(where + "tracks [%d, %d): an empty range" % (first, end))
+            if first < prev:
+                raise ValueError(where + "starts at track %d, before the group in front of it ends (%d)" % (first, prev))
+            gain = 1.0 if entry[2] is None else entry[2]
+            try:
+                if isinstance(gain, (str, bytes)):
+                    raise TypeError
+                gain = float(gain)
+            except (TypeError, ValueError):
+                raise ValueError(where + "gain is None or a finite number") from None
+            if not math.isfinite(gain):
+                raise ValueError(where + "gain is not finite")
+            pan = entry[3] if len(entry) == 4 else None
+            if pan is None:
+                factors = (1.0, 1.0)
+            elif self.nchannels != 2:
+                raise ValueError(where + "a pan needs a stereo song, this one has %d channels" % self.nchannels)
+            elif isinstance(pan, (tuple, list)):
+                try:
+                    factors = (float(pan[0]), float(pan[1])) if len(pan) == 2 else None
+                except (TypeError, ValueError):
+                    factors = None
+                if factors is None or not (math.isfinite(factors[0]) and math.isfinite(factors[1])):
+                    raise ValueError(where + "pan is not a pair (left_factor, right_factor) of finite numbers")
+            else:
+                try:
+                    if isinstance(pan, (str, bytes)):
+                        raise TypeError
+                    pan = float(pan)
+                except (TypeError, ValueError):
+                    raise ValueError(where + "pan is None, a number or a pair (left_factor, right_factor)") from None
+                if not -1.0 <= pan <= 1.0:
+                    raise ValueError(where + "pan must be between -1 and 1")
+                factors = ((1.0 - pan) / 2.0, (1.0 + pan) / 2.0)    # Sample.pan: Python floats, on the host
+            prev = end
+            out.append((first, end, gain, factors[0], factors[1]))
+        return out or None
 
     def _automation(self, automation) -> Optional["N.SeqAutomation"]:
         """``automation`` as render hands it on: None, or the native handle of an ``Automation`` that THIS song made -- checked before
@@ -972,9 +1079,11 @@ class CompiledSequence:
             segments[name] = column
         return segments, seg_first
 
-    def _levels(self, rows, nframes: int) -> SongLevels:
+    def _levels(self, rows, nframes: int, ngroups: int = 0) -> SongLevels:
         if rows is None:                                        # an empty window: nothing was launched, every level 0
-            rows = [((0, 0), (0, 0))] * (self.ntracks + 1)
+            rows = [((0, 0), (0, 0))] * (self.ntracks + 1 + ngroups)
+        if ngroups:
+            return SongLevels(rows, nframes, self.samplewidth, self.nchannels, self.samplerate, ngroups)
         return SongLevels(rows, nframes, self.samplewidth, self.nchannels, self.samplerate)
 
     @property
@@ -1004,16 +1113,18 @@ class CompiledSequence:
 
     def render_into(self, buf: N.DeviceBuffer, byte_offset: int, start_frame: int, nframes: int, gains: Optional[Sequence[float]] = None,
                     meters: bool = False, pans: Optional[Sequence] = None, master: Optional[float] = None,
-                    automation: Optional[Automation] = None) -> Optional[SongLevels]:
+                    automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> Optional[SongLevels]:
         """Frames ``[start_frame, start_frame + nframes)`` of the song into ``buf`` from ``byte_offset`` (a whole number of samples) on:
         every byte of the range is written, whatever ``buf`` held.  ``gains``: one per track of a song of tracks.  ``meters=True``: the
         same bytes, and the window's ``SongLevels`` returned, from the same launch (the call then waits for it).  ``pans``, ``master``:
         a pan per track and the master's gain of a stereo song of tracks (``CompiledSequence``), in that same launch.  ``automation``:
-        None or an ``Automation`` made by this song's ``automation()``: its fader moves, in that same launch."""
+        None or an ``Automation`` made by this song's ``automation()``: its fader moves, in that same launch.  ``groups``: None or the
+        group buses (``CompiledSequence``), in that same launch; the levels then hold a ``Levels`` per group as well."""
         seq = self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
-        desk = self._desk(self._pans(pans), self._master(master), self._automation(automation))
+        groups = self._groups(groups)
+        desk = self._desk(self._pans(pans), self._master(master), self._automation(automation), groups)
         start_frame, nframes = self._range(start_frame, nframes)
         if byte_offset < 0 or byte_offset % self.samplewidth:
             raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
@@ -1022,7 +1133,7 @@ class CompiledSequence:
             if nframes:
                 rows = seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains, meters=True,
                                   **desk)
-            return self._levels(rows, nframes)
+            return self._levels(rows, nframes, len(groups)) if groups else self._levels(rows, nframes)
         if nframes:
             if gains is None and not desk:
                 seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth)
@@ -1031,27 +1142,31 @@ class CompiledSequence:
         return None
 
     def render(self, start_frame: int = 0, nframes: Optional[int] = None, gains: Optional[Sequence[float]] = None, meters: bool = False,
-               pans: Optional[Sequence] = None, master: Optional[float] = None, automation: Optional[Automation] = None):
+               pans: Optional[Sequence] = None, master: Optional[float] = None, automation: Optional[Automation] = None,
+               groups: Optional[Sequence] = None):
         """A new ``Sample``: frames ``[start_frame, start_frame + nframes)`` of the song; ``nframes`` None: to the end.  ``gains``: one
         per track of a song of tracks (None: all 1.0).  ``meters=True``: ``(Sample, SongLevels)``, both from the one launch.  ``pans``:
         one entry per track of a stereo song of tracks (None, a number -1 .. 1 or a pair of factors); ``master``: the master's gain;
-        ``automation``: this song's fader moves (``automation()``)."""
+        ``automation``: this song's fader moves (``automation()``); ``groups``: at most 8 entries ``(first_track, end_track, gain)`` or
+        ``(first_track, end_track, gain, pan)``, the group buses (``CompiledSequence`` has the chain)."""
         self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
         self._pans(pans), self._master(master), self._automation(automation)      # (checked here as well: before the buffer is made)
+        ngroups = len(self._groups(groups) or ())
         start_frame, nframes = self._range(start_frame, nframes)
         out = Sample(name=self.name, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth)
         levels = None
         if nframes:
             buf = N.DeviceBuffer(nframes * self._fb)
             if meters:
-                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=True, pans=pans, master=master, automation=automation)
+                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=True, pans=pans, master=master, automation=automation,
+                                          groups=groups)
             else:
-                self.render_into(buf, 0, start_frame, nframes, gains=gains, pans=pans, master=master, automation=automation)
+                self.render_into(buf, 0, start_frame, nframes, gains=gains, pans=pans, master=master, automation=automation, groups=groups)
             out._set_device(buf, nframes * self._fb)
         if meters:
-            return out, levels if levels is not None else self._levels(None, 0)
+            return out, levels if levels is not None else self._levels(None, 0, ngroups)
         return out
 
     def stem(self, track: int, start_frame: int = 0, nframes: Optional[int] = None) -> Sample:
@@ -1065,9 +1180,9 @@ class CompiledSequence:
         return self.render(start_frame, nframes, gains=[1.0 if t == track else 0.0 for t in range(self.ntracks)])
 
     def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None, meters: bool = False, pans: Optional[Sequence] = None,
-               master: Optional[float] = None, automation: Optional[Automation] = None) -> Generator:
+               master: Optional[float] = None, automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> Generator:
         """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter.  ``gains``, ``pans``, ``master``,
-        ``automation``: as ``render``'s (the joined chunks are the whole render's bytes whatever ``chunk_frames`` cuts).
+        ``automation``, ``groups``: as ``render``'s (the joined chunks are the whole render's bytes whatever ``chunk_frames`` cuts).
         ``meters=True``: ``(Sample, SongLevels)`` pairs."""
         chunk_frames = int(chunk_frames)
         if chunk_frames <= 0:
@@ -1075,12 +1190,13 @@ class CompiledSequence:
         self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
-        self._pans(pans), self._master(master), self._automation(automation)
+        self._pans(pans), self._master(master), self._automation(automation), self._groups(groups)
         for at in range(0, self.frames, chunk_frames):
             if meters:
-                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=True, pans=pans, master=master, automation=automation)
+                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=True, pans=pans, master=master, automation=automation,
+                                  groups=groups)
             else:
-                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, pans=pans, master=master, automation=automation)
+                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, pans=pans, master=master, automation=automation, groups=groups)
 
     def close(self) -> None:
         if self._seq is not None:

@@ -97,7 +97,14 @@ move's stem amplified and faded (Sample.fadein / fadeout), clipped to the window
 and the master's amplify -- held to (a)'s bytes first, whole song and a window three frames off inside a fade; (c) render(gains=, pans=,
 master=) without automation.  On a tree without automation= only (c) runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit>
 python tools/sequence_ab.py --auto is the parent's own figure for (c), row (d).  --auto-trace NEVENTS: twenty whole-song renders each of
-(c) and (a) and nothing else, for rocprofv3 --kernel-trace."""
+(c) and (a) and nothing else, for rocprofv3 --kernel-trace.
+
+--groups: the song of --desk with group buses: its 8 tracks in 3 groups (tracks 1-2, 3-4, 6-7, each with a gain, two with a pan) and 2
+loose tracks.  Wall time with a device synchronise, medians, of the whole song and per window of 4096 frames, for: (a) render(gains=,
+pans=, master=, groups=), the one launch; (b) the caller's way -- every group rendered with every other track muted, amplify and stereo
+on it, the stretches of loose tracks in between rendered the same way, everything mixed in order, the master's amplify -- held to (a)'s
+bytes first; (c) render(gains=, pans=, master=) without groups.  On a tree without groups= only (c) runs: SEQUENCE_AB_TREE=<a built
+checkout of the parent commit> python tools/sequence_ab.py --groups is the parent's own figure for (c), row (d)."""
 import audioop
 import os
 import sys
@@ -106,8 +113,8 @@ from pathlib import Path
 
 import numpy as np
 
-# the yardstick of --plan, --tracks, --desk and --auto is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
-sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
+# the yardstick of --plan, --tracks, --desk, --auto and --groups is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
+sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:] or "--groups" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
 from synthesizer_amd import _native as N  # noqa: E402
 from synthesizer_amd import mixer  # noqa: E402
 from synthesizer_amd.sample import Sample  # noqa: E402
@@ -1258,6 +1265,88 @@ def auto_main():
         bus.close()
 
 
+GROUPS = [(1, 3, 0.8, (0.999, 0.37)), (3, 5, 1.3, -0.37), (6, 8, 0.6, None)]       # 8 tracks: three groups, tracks 0 and 5 loose
+
+
+def groups_main():
+    """--groups: group buses in the render's own launch.  (a) render(gains=, pans=, master=, groups=); (b) the caller's way: every group
+    rendered with every other track muted, amplify and stereo on it, the stretches of loose tracks in between rendered the same way, all
+    mixed in order, then the master's gain -- held to (a)'s bytes first; (c) render(gains=, pans=, master=).  Wall time with a device
+    synchronise, medians; whole song and 4096-frame windows.  A tree whose render has no groups= runs (c) alone."""
+    import inspect
+    N.ensure_init(0)
+    info = N.device_info()
+    has = "groups" in inspect.signature(mixer.CompiledSequence.render).parameters
+    print("sequence_groups_ab: SYNTHHIP_SEQ_ALIGN=%s  %s  groups=: %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"],
+          "yes" if has else "no (the yardstick: (c) alone)"), flush=True)
+    win, ntracks = 4096, len(TRACK_GAINS)
+    desk = dict(gains=TRACK_GAINS, pans=DESK_PANS, master=DESK_MASTER)
+    # the desk in order: (first, end, gain, factors) of a group, (first, end, None, None) of a stretch of loose tracks
+    parts, at = [], 0
+    for first, end, g, pan in GROUPS:
+        if first > at:
+            parts.append((at, first, None, None))
+        parts.append((first, end, g, None if pan is None else pan_factors(pan)))
+        at = end
+    if at < ntracks:
+        parts.append((at, ntracks, None, None))
+    for nevents in (4096, 32768):
+        what, nch, evs = meters_songs(nevents)[0]
+        fb = nch * WIDTH
+        bus = mixer.compile_tracks([evs[t::ntracks] for t in range(ntracks)], RATE, nch, WIDTH)
+        frames = bus.frames
+        out = N.DeviceBuffer(frames * fb + 16)
+        wins = list(range(0, (frames - 3) // win, 16))
+
+        def stream(render):
+            for k in wins:
+                render(k * win, win)
+                N.sync()
+
+        c_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, **desk), 2, 15)
+        c_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, **desk))
+        c_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, **desk)), 1, 5) / len(wins)
+        fmt = lambda v: " ".join("%.4f" % x for x in v)    # noqa: E731
+        head = "groups song 120 s, %5d events, %s, %d tracks, level %s, %d frames   " % (nevents, what, ntracks, bus.level, frames)
+        tail = "(c) render(gains=, pans=, master=): whole song, wall with a synchronise, median %.4f ms   between two events on the stream, five medians " \
+               "of 15: %s ms   a window of %d frames, wall %.4f ms" % (c_whole, fmt(c_dev), win, c_win)
+        if not has:
+            print(head + tail, flush=True)
+            bus.close()
+            continue
+
+        def caller(a, n):
+            """(b): the window as a caller made it: one render per group or stretch, the others muted"""
+            master = Sample(samplerate=RATE, nchannels=nch, samplewidth=WIDTH)
+            for first, end, g, factors in parts:
+                solo = [TRACK_GAINS[t] if first <= t < end else 0.0 for t in range(ntracks)]
+                part = bus.render(a, n, gains=solo, pans=DESK_PANS)
+                if g is not None and g != 1.0:
+                    part.amplify(g)
+                if factors is not None:
+                    part.stereo(*factors)
+                master.mix(part)
+            return master.amplify(DESK_MASTER)
+
+        mid = (frames // 2) // win * win
+        parity = bytes(bus.render(groups=GROUPS, **desk).view_frame_data()) == bytes(caller(0, frames).view_frame_data()) and \
+            bytes(bus.render(mid + 3, win, groups=GROUPS, **desk).view_frame_data()) == bytes(caller(mid + 3, win).view_frame_data())
+        differs = bytes(bus.render(groups=GROUPS, **desk).view_frame_data()) != bytes(bus.render(**desk).view_frame_data())
+        a_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, groups=GROUPS, **desk), 2, 15)
+        a_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, groups=GROUPS, **desk))
+        a_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, groups=GROUPS, **desk)), 1, 5) / len(wins)
+        b_whole = median_wall(lambda: caller(0, frames), 1, 5)
+        b_win = median_wall(lambda: stream(caller), 1, 3) / len(wins)
+        print(head + "(a) render(gains=, pans=, master=, groups=): whole song, wall with a synchronise, median %.4f ms   between two events on the "
+              "stream, five medians of 15: %s ms   a window, wall %.4f ms   (b) %d renders with the others muted, amplify, stereo, mix, amplify: whole "
+              "song, wall %.3f ms   a window, wall %.3f ms   %s   (a) / (b) whole %.4f, window %.4f   (a) / (c) whole %.3f, window %.3f   (a)'s bytes "
+              "against (b)'s, whole and window: %s   (a) differs from (c): %s"
+              % (a_whole, fmt(a_dev), a_win, len(parts), b_whole, b_win, tail, a_whole / b_whole, a_win / b_win, a_whole / c_whole, a_win / c_win,
+                 "ok" if parity else "FAILED", "yes" if differs else "NO"), flush=True)
+        assert parity and differs
+        bus.close()
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -1328,4 +1417,4 @@ def main():
 
 
 if __name__ == "__main__":
-    auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    groups_main() if "--groups" in sys.argv[1:] else auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
