@@ -849,12 +849,32 @@ int sh_seq_render_auto(const sh_seq* seq, size_t first_sample, size_t nsamples, 
  * sh_seq_render_auto refuses (an automation handle at width 3 among it); ngroups == 0 or > SH_SEQ_MAX_GROUPS; groups == NULL; an entry
  * with first >= end, with end > ntracks, or that starts in front of the previous entry's end; a gain or factor that is not finite;
  * factors other than (1.0, 1.0) on a song that is not stereo; nmeters other than ntracks + 1 + ngroups where meters is given.  The
- * error text names the entry.  Not built: automation of a group, groups inside groups. */
+ * error text names the entry; an automation handle that rides a group this call does not name (below).  Not built: groups inside
+ * groups. */
 typedef struct sh_seq_group { uint32_t first, end; double gain; double left, right; } sh_seq_group;   /* 32 bytes */
 #define SH_SEQ_MAX_GROUPS 8u
 int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
                          uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters,
                          const sh_seq_auto* automation /* may be NULL */, const sh_seq_group* groups, uint32_t ngroups);
+
+/* The desk's BUS RIDES: fader moves on a group's bus and on the master, in the same table and the same launch.  sh_seq_auto_create_buses is
+ * sh_seq_auto_create with ntracks + 1 + ngroups lanes in the meter table's row order -- tracks 0 .. ntracks - 1, the master at ntracks,
+ * group g at ntracks + 1 + g -- so seg_first holds ntracks + 1 + ngroups + 1 offsets; ngroups is 0 .. SH_SEQ_MAX_GROUPS.  The chain:
+ *     ... if t == end_g - 1:
+ *             if gain_g != 1.0: bus = audioop.mul(bus, gain_g)
+ *             bus[s] = trunc(bus[s] * ((s - origin) * slope / numsamples + offset)) over the segments of group g's lane    (NEW)
+ *             bus = (fbound(L * left_g), fbound(R * right_g)) per frame;  master = audioop.add(master, bus)
+ *     if master_gain != 1.0: master = audioop.mul(master, master_gain)
+ *     master[s] = trunc(master[s] * (...)) over the segments of the master's lane                                           (NEW)
+ * -- the group's ride behind its gain and in front of its pan, over the saturated bus (not a ride of each of its tracks); the master's
+ * behind its gain, over the saturated master: Sample.fadein / fadeout of the mix.  Positions are song samples whatever the window.  A
+ * group's row of levels is read behind its ride and pan, the master's over the stored bytes.  Every segment is held to sh_seq_auto_create's
+ * rules, the error text naming `master` or `group g` where that says `track t`.  sh_seq_render_auto and sh_seq_render_groups take a
+ * handle from either function: one without a segment on a bus lane renders exactly as one from sh_seq_auto_create; a master ride needs
+ * no groups (sh_seq_render_auto); SH_ERR_INVALID, nothing launched: a handle with a segment on group g's lane given to
+ * sh_seq_render_auto, or to sh_seq_render_groups with ngroups <= g. */
+int sh_seq_auto_create_buses(const sh_seq* seq, const sh_env_segment* segments, uint32_t nsegments, const uint32_t* seg_first, uint32_t ntracks,
+                             uint32_t ngroups, sh_seq_auto** out);
 
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads

@@ -213,6 +213,7 @@ _SIGNATURES = {
     "sh_seq_render_desk": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
                                      C.c_double, C.POINTER(SeqMeter), C.c_uint32]),
     "sh_seq_auto_create": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(_P)]),
+    "sh_seq_auto_create_buses": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "sh_seq_auto_destroy": (C.c_int, [_P]),
     "sh_seq_render_auto": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
                                      C.c_double, C.POINTER(SeqMeter), C.c_uint32, _P]),
@@ -483,7 +484,8 @@ class Sequence:
         ``pans`` (2 * ntracks factors, left then right per track) or ``master`` (a gain) given: sh_seq_render_desk, with or without meters.
         ``automation`` (a ``SeqAutomation`` of this song) given: sh_seq_render_auto, with or without any of the others.
         ``groups`` (a non-empty list of ``(first_track, end_track, gain, left, right)``) given: sh_seq_render_groups, with or without any
-        of the others; the rows of the groups follow the master's."""
+        of the others; the rows of the groups follow the master's.  An ``automation`` with lanes of the buses (``SeqAutomation(...,
+        ngroups)``) goes the same two ways: a master ride alone needs no ``groups``, a ride on group ``g`` more than ``g`` of them."""
         def doubles(v):
             return None if v is None else (C.c_double * max(1, len(v)))(*v)
 
@@ -532,15 +534,24 @@ class Sequence:
 class SeqAutomation:
     """RAII wrapper over sh_seq_auto: the fader moves of a song of tracks -- ``segments`` (ENV_SEGMENT_DTYPE rows in SONG samples, the tracks'
     one behind the other) and ``seg_first`` (one offset per track and the table's length behind them) -- uploaded once into a device table
-    of its own; ``Sequence.render(automation=)`` applies it."""
+    of its own; ``Sequence.render(automation=)`` applies it.  With ``ngroups`` the table also holds the lanes of the BUSES, in the meter
+    table's row order: the master's behind the last track's, then the groups' (sh_seq_auto_create_buses); a render with such a handle
+    names every group it rides."""
 
-    def __init__(self, seq: Sequence, segments: np.ndarray, seg_first) -> None:
+    def __init__(self, seq: Sequence, segments: np.ndarray, seg_first, ngroups: Optional[int] = None) -> None:
+        """``ngroups`` None: one lane per track (sh_seq_auto_create).  A number 0 .. SEQ_MAX_GROUPS: the lanes of the buses behind the
+        tracks', in the meter table's row order -- the master's, then ``ngroups`` groups' (sh_seq_auto_create_buses)."""
         ensure_init()
         assert segments.dtype == ENV_SEGMENT_DTYPE and len(seg_first) >= 2 and seg_first[-1] == len(segments)
         self._h = _P()
         first = (C.c_uint32 * len(seg_first))(*seg_first)
-        check(lib().sh_seq_auto_create(seq.handle, _ptr(segments), len(segments), first, len(seg_first) - 1,
-                                       C.byref(self._h)))
+        if ngroups is None:
+            check(lib().sh_seq_auto_create(seq.handle, _ptr(segments), len(segments), first, len(seg_first) - 1,
+                                           C.byref(self._h)))
+        else:
+            assert 0 <= ngroups and len(seg_first) >= ngroups + 3
+            check(lib().sh_seq_auto_create_buses(seq.handle, _ptr(segments), len(segments), first, len(seg_first) - 2 - ngroups, ngroups,
+                                                 C.byref(self._h)))
 
     @property
     def handle(self):

@@ -63,7 +63,11 @@
 // (int(x * f), the fade's truncation), then the pan, the hook and the add.  The GROUP buses, SeqBusG and SeqBusGM (width 3: SeqBusG3,
 // SeqBusGM3), are the whole desk again with a table of group buses by value (seqgroup.hpp; sh_seq_render_groups): in seq_runs a third
 // accumulator between sub and acc takes the tracks of the open group and is closed -- the group's gain, its pan, the hook for its row,
-// the add into the master -- in front of the first run that is not of the group and behind the last run.
+// the add into the master -- in front of the first run that is not of the group and behind the last run.  The buses that RIDE, SeqBusR and
+// SeqBusRM (widths 1, 2 and 4), are the group buses again with fader moves on the two bus levels (sh_seq_auto_create_buses: the lanes of
+// the master and of the groups behind the tracks' in the automation's table, no kernel argument of their own): in the close the group's
+// bus through its lane between its gain and its pan, in seq_window_bus the master through its lane behind the master's gain; seq_ride
+// states the shaping once for track, group and master.
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
@@ -922,6 +926,17 @@ struct SeqBusG3 : SeqBusD, SeqGroups {};
 template <typename... Bus> constexpr bool SEQ_GROUPS = (std::is_base_of<SeqGroups, Bus>::value || ...);
 static_assert(shg::MAX_TRACKS == shq::MAX_TRACKS && sizeof(SeqBusG) == sizeof(SeqBusA) + sizeof(shg::Table), "the groups: 232 bytes of kernel arguments behind the bus");
 
+// BUS RIDES (sh_seq_auto_create_buses): fader moves on the two bus levels -- a group's bus shaped through a lane of its own BEHIND the
+// group's gain and IN FRONT of its pan, the master through one BEHIND the master's gain, over the saturated sum in both places.  No new
+// kernel argument: the lanes stand in the automation's table in the meter table's row order (seqauto.hpp), the master's at
+// groups.row0 - 1 and group g's at groups.row0 + g, behind the tracks', and index the afirst / asegs that a group bus carries anyway.
+// The table of such a handle always has an offset for every one of the MAX_GROUPS group lanes, so a render may name more groups than
+// the handle rides.  A tag, and two more bus types at widths 1, 2 and 4; a handle without a segment on a bus lane never gets here.
+struct SeqRides {};
+struct SeqBusR : SeqBusG, SeqRides {};
+template <typename... Bus> constexpr bool SEQ_RIDES = (std::is_base_of<SeqRides, Bus>::value || ...);
+static_assert(sizeof(SeqBusR) == sizeof(SeqBusG) && sha::MAX_GROUP_LANES == shg::MAX_GROUPS, "the rides: no kernel argument of their own");
+
 // a lane's accumulator: eight packed samples at 16 bits, four 64-bit sums at the other widths
 template <int WIDTH> struct SeqAcc { typedef llong4v type; };
 template <> struct SeqAcc<2> { typedef short8v type; };
@@ -955,6 +970,30 @@ __device__ __forceinline__ void seq_master(typename SeqAcc<WIDTH>::type& acc, co
     }
 }
 
+// "Shape this accumulator through lane `lane` of the automation's table", stated once for the buses that ride (SeqBusR, SeqBusRM) -- a
+// track's sub-mix, a group's bus and the master: a lane's samples of tile k at their SONG positions, one binary search at the tile's first
+// sample (sha::find) and one walk from there (sha::shape_from); everything but x and the lane's position is wave-uniform, and behind the
+// lane's last segment nothing is shaped.  x holds saturated samples of the width, so they pass through int unchanged.
+template <int WIDTH>
+__device__ __forceinline__ void seq_ride(typename SeqAcc<WIDTH>::type& x, const SeqAuto& au, const uint32_t lane, const uint32_t k) {
+    constexpr int N = SEQ_LANE<WIDTH>;
+    const uint32_t t0 = k * SEQ_TILE<WIDTH>;
+    const uint32_t a0 = au.afirst[lane];
+    const she::Seg* segs = au.asegs + a0;
+    const uint32_t n = au.afirst[lane + 1] - a0;
+    const uint32_t i = sha::find(segs, n, t0);
+    if (i >= n) return;                                       // (uniform)
+    int v[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = (int)x[j];
+    sha::shape_from<N>(segs, n, i, t0, t0 + SEQ_TILE<WIDTH>, (long long)t0 + threadIdx.x * N, v, (double)SEQ_LO<WIDTH>, (double)SEQ_HI<WIDTH>);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        if constexpr (WIDTH == 2) x[j] = (short)v[j];
+        else x[j] = v[j];
+    }
+}
+
 // The runs of tile k, written once for the three templates and every bus: the events from e on, run by run.  walk(e, e1, sub): the
 // schedule of the kernel, events [e, e1) into sub; hook(sub, row): what else a bus does with a track's samples as its bus takes them,
 // post-fader and (a desk bus) post-pan (the metering buses: its row).  Everything about a run is uniform, and a run lists at least one event.
@@ -968,7 +1007,24 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
     [[maybe_unused]] auto close = [&] {                       // the open group into the master
         if constexpr (SEQ_GROUPS<Bus>) {
             const double gg = bus.groups.gain[open], gl = bus.groups.pan[2 * open], gr = bus.groups.pan[2 * open + 1];
-            if constexpr (WIDTH == 2) {
+            if constexpr (SEQ_RIDES<Bus> && WIDTH == 2) {     // the group's ride: behind its gain, in front of its pan
+                grp = seq_scale8(grp, gg);
+                seq_ride<2>(grp, bus, sha::group_lane(bus.groups.row0, open), k);
+                grp = seq_pan8(grp, gl, gr);
+                hook(grp, bus.groups.row0 + open);
+                acc = __builtin_elementwise_add_sat(acc, grp);
+            } else if constexpr (SEQ_RIDES<Bus>) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) grp[j] = seq_scale_w<WIDTH>(grp[j], gg);
+                seq_ride<WIDTH>(grp, bus, sha::group_lane(bus.groups.row0, open), k);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    long long x = grp[j];
+                    acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, j & 1 ? gr : gl);
+                    grp[j] = x;
+                }
+                hook(grp, bus.groups.row0 + open);
+            } else if constexpr (WIDTH == 2) {
                 grp = seq_pan8(seq_scale8(grp, gg), gl, gr);
                 hook(grp, bus.groups.row0 + open);
                 acc = __builtin_elementwise_add_sat(acc, grp);
@@ -1014,7 +1070,7 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
         [[maybe_unused]] const she::Seg* asegs = nullptr;    // (an automation bus: the track's segments, from the first that ends past t0)
         [[maybe_unused]] uint32_t an = 0, ai = 0;
         [[maybe_unused]] const uint32_t t0 = k * SEQ_TILE<WIDTH>;
-        if constexpr (SEQ_AUTO<Bus>) {
+        if constexpr (SEQ_AUTO<Bus> && !SEQ_RIDES<Bus>) {       // (a bus that rides searches in seq_ride)
             bool moves = true;
             if constexpr (SEQ_GROUPS<Bus>) moves = bus.asegs != nullptr;      // (uniform: a group bus without automation)
             if (moves) {
@@ -1028,7 +1084,9 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
             short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
             walk(e, run.end, sub);
             sub = seq_scale8(sub, g);                         // post-fader: what the master takes of the track
-            if constexpr (SEQ_AUTO<Bus>) {
+            if constexpr (SEQ_RIDES<Bus>) {
+                seq_ride<2>(sub, bus, run.track, k);
+            } else if constexpr (SEQ_AUTO<Bus>) {
                 if (ai < an) {                                // (uniform: behind the track's last segment nothing is shaped)
                     int v[8];
 #pragma unroll
@@ -1047,7 +1105,11 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
         } else {
             llong4v sub = {0, 0, 0, 0};
             walk(e, run.end, sub);
-            if constexpr (SEQ_AUTO<Bus>) {                    // the gain over all four first, then the segments; the pan below
+            if constexpr (SEQ_RIDES<Bus>) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sub[j] = seq_scale_w<WIDTH>(sub[j], g);
+                seq_ride<WIDTH>(sub, bus, run.track, k);
+            } else if constexpr (SEQ_AUTO<Bus>) {             // the gain over all four first, then the segments; the pan below
                 int v[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] = (int)seq_scale_w<WIDTH>(sub[j], g);
@@ -1118,6 +1180,8 @@ struct SeqBusGM : SeqBusAM, SeqGroups {};
 struct SeqBusGM3 : SeqBusDM, SeqGroups {};
 template <> struct SeqMetered<SeqBusGM> : std::true_type {};
 template <> struct SeqMetered<SeqBusGM3> : std::true_type {};
+struct SeqBusRM : SeqBusGM, SeqRides {};  // the buses that ride, with meters: a group's row behind its ride and pan, the master's behind its ride
+template <> struct SeqMetered<SeqBusRM> : std::true_type {};
 
 // the workgroup's row table, zeroed: every lane of the workgroup calls it (a barrier).  ROWS: 33, or 41 with the rows of the groups
 template <uint32_t ROWS = shq::MAX_TRACKS + 1>
@@ -1185,6 +1249,7 @@ __device__ __forceinline__ void seq_window_bus(const Bus& bus, uint32_t k, uint3
     if constexpr (!SeqMetered<Bus>::value) {
         seq_runs<WIDTH>(bus, k, e, acc, walk, [](const typename SeqAcc<WIDTH>::type&, uint32_t) {});
         if constexpr (SEQ_DESK<Bus>) seq_master<WIDTH>(acc, bus.master);
+        if constexpr (SEQ_RIDES<Bus>) seq_ride<WIDTH>(acc, bus, sha::master_lane(bus.groups.row0), k);      // the master's ride: behind its gain
         store();
     } else {
         constexpr bool WIDE = WIDTH >= 3;
@@ -1198,6 +1263,7 @@ __device__ __forceinline__ void seq_window_bus(const Bus& bus, uint32_t k, uint3
                 seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(sub, s0, lo, hi, bus.nch), stereo, table + row);
             });
             if constexpr (SEQ_DESK<Bus>) seq_master<WIDTH>(acc, bus.master);
+            if constexpr (SEQ_RIDES<Bus>) seq_ride<WIDTH>(acc, bus, sha::master_lane(bus.groups.row0), k);      // (in front of the master's row: over the stored bytes)
             seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
             store();
         }
@@ -1669,9 +1735,12 @@ struct sh_seq {
 // Fader automation of a song of tracks (sh_seq_auto_create): the tracks' segments and where each track's start, uploaded once into a
 // block this handle owns; what it says of the song it was made for is what sh_seq_render_auto holds a song to.
 struct sh_seq_auto {
-    void*    block = nullptr;             // segments (she::Seg) | first (ntracks + 1 offsets)
+    void*    block = nullptr;             // segments (she::Seg) | first (ntracks + 1 offsets; sh_seq_auto_create_buses: ntracks + 1 + MAX_GROUPS + 1)
     size_t   cap = 0, bytes = 0, at_first = 0;
     uint32_t ntracks = 0, nsegments = 0;
+    uint32_t ngroups = 0;                 // sh_seq_auto_create_buses: the group lanes it was given
+    uint32_t ridden = 0;                  // one past the last group lane that has a segment; 0: no group rides
+    bool     buses = false;               // a bus lane -- the master's or a group's -- has a segment: the kernels that ride
     int      width = 0, nchannels = 0;
     uint64_t track_samples = 0;
 };
@@ -1700,8 +1769,8 @@ void seq_with_level(int level, F f) {
 // Which window kernel: the width, at 16 bits the way misaligned event samples are read and whether the biased base lies on a 16-byte
 // boundary.  bus: nothing (a flat list), a SeqBus (a song of tracks: the same kernels with the bus, the gains by value), a SeqBusM (the
 // metering bus: the rows go to the handle's table) or one of the two with the desk (SeqBusD, SeqBusDM: pans and the master's gain by
-// value as well), with automation (SeqBusA, SeqBusAM) or with groups (SeqBusG, SeqBusGM; width 3: SeqBusG3, SeqBusGM3), forwarded as
-// the kernels' trailing pack.
+// value as well), with automation (SeqBusA, SeqBusAM), with groups (SeqBusG, SeqBusGM; width 3: SeqBusG3, SeqBusGM3) or with groups and
+// rides of the buses (SeqBusR, SeqBusRM), forwarded as the kernels' trailing pack.
 template <int LEVEL, typename... Bus>
 void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out, const Bus&... bus) {
     typedef typename SeqRec<LEVEL>::type Rec;
@@ -1863,9 +1932,11 @@ template <typename T> struct SeqBaseOf { typedef T type; };
 // sh_seq_render (gains NULL: every track at 1.0), sh_seq_render_gains, sh_seq_render_meters (meters: ntracks + 1 host rows, the handle
 // has tracks), sh_seq_render_desk (desk: the pans and the master's gain, the handle has tracks; with or without meters) and
 // sh_seq_render_auto (au: the automation's table, with a desk) and sh_seq_render_groups (groups: the group table, with a desk, with or
-// without au; meters: ntracks + 1 + ngroups rows) behind their names
+// without au; meters: ntracks + 1 + ngroups rows; rides: au has a segment on a bus lane, and groups may then be the empty table) behind
+// their names
 int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains,
-               sh_seq_meter* meters = nullptr, const SeqDesk* desk = nullptr, const SeqAuto* au = nullptr, const shg::Table* groups = nullptr) {
+               sh_seq_meter* meters = nullptr, const SeqDesk* desk = nullptr, const SeqAuto* au = nullptr, const shg::Table* groups = nullptr,
+               bool rides = false) {
     static_assert(sizeof(sh_seq_meter) == sizeof(shmt::Row) && offsetof(sh_seq_meter, sq_hi) == offsetof(shmt::Row, sq_hi) &&
                   offsetof(sh_seq_meter, sq_lo) == offsetof(shmt::Row, sq_lo), "sh_seq_meter is shmt::Row");
     const size_t b_meters = meters ? ((size_t)seq->ntracks + 1 + (groups ? groups->n : 0)) * sizeof(shmt::Row) : 0;
@@ -1917,6 +1988,7 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
                 seq_window_launch<LEVEL, G>(seq, grid, st, lo, hi, biased, moved);
             };
             if (seq->width == 3) meters ? grouped(SeqBusGM3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG3{}, SeqBaseOf<SeqBus>());
+            else if (rides) meters ? grouped(SeqBusRM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusR{}, SeqBaseOf<SeqBus>());      // (au: a table with bus lanes)
             else meters ? grouped(SeqBusGM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG{}, SeqBaseOf<SeqBus>());
         } else if (au && meters) {
             SeqBusAM moved{};
@@ -2015,39 +2087,35 @@ int sh_seq_render_desk(const sh_seq* seq, size_t first_sample, size_t nsamples, 
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d);
 }
 
-int sh_seq_auto_create(const sh_seq* seq, const sh_env_segment* segments, uint32_t nsegments, const uint32_t* seg_first, uint32_t ntracks,
-                       sh_seq_auto** out) {
-    SH_REQUIRE_INIT();
-    static const char fn[] = "sh_seq_auto_create";
+// sh_seq_auto_create (buses false: ntracks lanes) and sh_seq_auto_create_buses (ntracks + 1 + ngroups lanes in the meter table's row order)
+// behind their names: sha::check's verdict in words, then the table on the device.  Who a lane is: a track, the master or a group.
+static int seq_auto_make(const char* fn, const sh_seq* seq, const sh_env_segment* segments, uint32_t nsegments, const uint32_t* seg_first,
+                         uint32_t ntracks, uint32_t ngroups, bool buses, sh_seq_auto** out) {
     if (!out) return seq_null(fn);
     *out = nullptr;
     if (!seq || !seg_first || (nsegments && !segments)) return seq_null(fn);
     if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
     if (seq->width == 3) return sh::set_error(SH_ERR_INVALID, "%s: width 3: a fader move's fade has no 24-bit form", fn);
     if (ntracks != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u lanes for %u tracks", fn, ntracks, seq->ntracks);
-    if (seg_first[0] != 0 || seg_first[ntracks] != nsegments) return sh::set_error(SH_ERR_INVALID, "%s: seg_first starts at 0 and ends at nsegments", fn);
-    for (uint32_t t = 0; t < ntracks; ++t)
-        if (seg_first[t] > seg_first[t + 1]) return sh::set_error(SH_ERR_INVALID, "%s: seg_first decreases at track %u", fn, t + 1);
-    for (uint32_t t = 0; t < ntracks; ++t) {
-        uint64_t prev = 0;
-        for (uint32_t s = seg_first[t]; s < seg_first[t + 1]; ++s) {
-            const sh_env_segment& g = segments[s];
-            const uint32_t k = s - seg_first[t];
-            if (g.reserved != 0) return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: reserved must be 0", fn, t, k);
-            if (g.end <= prev || g.end > seq->track_samples)
-                return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: ends not ascending or beyond the song", fn, t, k);
-            if (g.kind > she::FADE_IN) return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: kind %u not 0 or 1", fn, t, k, g.kind);
-            if (g.mul != 1.0) return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: mul must be 1.0 (a track's gain is the render's)", fn, t, k);
-            if (g.kind == she::FADE_IN) {
-                // k runs over [0, end - origin) and numsamples covers it, so the factor stays between the two volumes, both inside 0 .. 1
-                if (g.origin != prev) return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: a move's origin is its first sample", fn, t, k);
-                if (!(g.numsamples >= (double)(g.end - g.origin)))
-                    return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: numsamples shorter than the move", fn, t, k);
-                if (!isfinite(g.numsamples) || !(g.offset >= 0.0 && g.offset <= 1.0) || !(g.slope >= -g.offset && g.slope <= 1.0 - g.offset))
-                    return sh::set_error(SH_ERR_INVALID, "%s: track %u: segment %u: a volume is not finite or outside 0 .. 1", fn, t, k);
-            }
-            prev = g.end;
-        }
+    if (buses && ngroups > shg::MAX_GROUPS) return sh::set_error(SH_ERR_INVALID, "%s: %u group lanes, 0 to %u", fn, ngroups, shg::MAX_GROUPS);
+    const uint32_t nlanes = buses ? sha::lanes(ntracks, ngroups) : ntracks;
+    const sha::Verdict v = sha::check(segments, nsegments, seg_first, nlanes, seq->track_samples);
+    char who[32];
+    if (v.lane < ntracks || !buses) snprintf(who, sizeof who, "track %u", v.lane);
+    else if (v.lane == ntracks) snprintf(who, sizeof who, "master");
+    else snprintf(who, sizeof who, "group %u", v.lane - ntracks - 1);
+    const uint32_t k = v.segment;
+    switch (v.why) {
+    case sha::OK: break;
+    case sha::FIRST_ENDS: return sh::set_error(SH_ERR_INVALID, "%s: seg_first starts at 0 and ends at nsegments", fn);
+    case sha::FIRST_DECREASES: return sh::set_error(SH_ERR_INVALID, "%s: seg_first decreases at %s", fn, who);
+    case sha::RESERVED: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: reserved must be 0", fn, who, k);
+    case sha::ENDS: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: ends not ascending or beyond the song", fn, who, k);
+    case sha::KIND: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: kind %u not 0 or 1", fn, who, k, segments[seg_first[v.lane] + k].kind);
+    case sha::MUL: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: mul must be 1.0 (a track's gain is the render's)", fn, who, k);
+    case sha::ORIGIN: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: a move's origin is its first sample", fn, who, k);
+    case sha::NUMSAMPLES: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: numsamples shorter than the move", fn, who, k);
+    default: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: a volume is not finite or outside 0 .. 1", fn, who, k);
     }
     sh_seq_auto* a = new (std::nothrow) sh_seq_auto;
     if (!a) return sh::set_error(SH_ERR_NOMEM, "host allocation failed");
@@ -2056,11 +2124,22 @@ int sh_seq_auto_create(const sh_seq* seq, const sh_env_segment* segments, uint32
     a->width = seq->width;
     a->nchannels = seq->nchannels;
     a->track_samples = seq->track_samples;
+    // with bus lanes the table holds an offset for EVERY group lane a render may name (the kernels read afirst[row0 + g + 1] for g < the
+    // render's groups): the lanes that were not given are empty, at nsegments
+    const size_t noffsets = buses ? (size_t)sha::lanes(ntracks, shg::MAX_GROUPS) + 1 : (size_t)ntracks + 1;
+    if (buses) {
+        a->ngroups = ngroups;
+        for (uint32_t g = 0; g < ngroups; ++g)
+            if (seg_first[ntracks + 1 + g] < seg_first[ntracks + 2 + g]) a->ridden = g + 1;
+        a->buses = a->ridden != 0 || seg_first[ntracks] < seg_first[ntracks + 1];
+    }
     a->at_first = (size_t)nsegments * sizeof(she::Seg);
-    a->bytes = a->at_first + ((size_t)ntracks + 1) * 4;
+    a->bytes = a->at_first + noffsets * 4;
     std::vector<char> host(a->bytes);
     seq_segments(reinterpret_cast<she::Seg*>(host.data()), segments, nsegments);
-    memcpy(host.data() + a->at_first, seg_first, ((size_t)ntracks + 1) * 4);
+    uint32_t* first = reinterpret_cast<uint32_t*>(host.data() + a->at_first);
+    memcpy(first, seg_first, ((size_t)nlanes + 1) * 4);
+    for (size_t i = (size_t)nlanes + 1; i < noffsets; ++i) first[i] = nsegments;
     int rc = sh::pool_alloc(a->bytes, &a->block, &a->cap);
     if (rc) {
         delete a;
@@ -2076,6 +2155,18 @@ int sh_seq_auto_create(const sh_seq* seq, const sh_env_segment* segments, uint32
     }
     *out = a;
     return SH_OK;
+}
+
+int sh_seq_auto_create(const sh_seq* seq, const sh_env_segment* segments, uint32_t nsegments, const uint32_t* seg_first, uint32_t ntracks,
+                       sh_seq_auto** out) {
+    SH_REQUIRE_INIT();
+    return seq_auto_make("sh_seq_auto_create", seq, segments, nsegments, seg_first, ntracks, 0, false, out);
+}
+
+int sh_seq_auto_create_buses(const sh_seq* seq, const sh_env_segment* segments, uint32_t nsegments, const uint32_t* seg_first, uint32_t ntracks,
+                             uint32_t ngroups, sh_seq_auto** out) {
+    SH_REQUIRE_INIT();
+    return seq_auto_make("sh_seq_auto_create_buses", seq, segments, nsegments, seg_first, ntracks, ngroups, true, out);
 }
 
 int sh_seq_auto_destroy(sh_seq_auto* a) {
@@ -2111,6 +2202,14 @@ int sh_seq_render_auto(const sh_seq* seq, size_t first_sample, size_t nsamples, 
     if (!rc) rc = seq_desk(fn, pans, npans, master_gain, d);
     if (rc) return rc;
     const SeqAuto au{(const she::Seg*)automation->block, (const uint32_t*)((const char*)automation->block + automation->at_first)};
+    if (automation->ridden)
+        return sh::set_error(SH_ERR_INVALID, "%s: the automation rides group %u, which this call does not name (sh_seq_render_groups does)", fn,
+                             automation->ridden - 1);
+    if (automation->buses) {                                  // a master ride alone: the kernels that ride, no group in the table
+        shg::Table none;
+        shg::pack(nullptr, 0, seq->ntracks, none);
+        return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, &au, &none, true);
+    }
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, &au);
 }
 
@@ -2150,6 +2249,8 @@ int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples
         return sh::set_error(SH_ERR_INVALID, "%s: group %u: a pan needs a stereo song, this one has %d channels", fn, v.entry, seq->nchannels);
     default: return sh::set_error(SH_ERR_INVALID, "%s: %u groups, 1 to %u", fn, ngroups, shg::MAX_GROUPS);
     }
+    if (automation && automation->ridden > ngroups)
+        return sh::set_error(SH_ERR_INVALID, "%s: the automation rides group %u, and this call names %u groups", fn, automation->ridden - 1, ngroups);
     if (meters && nmeters != seq->ntracks + 1 + ngroups)
         return sh::set_error(SH_ERR_INVALID, "%s: %u rows for %u tracks, the master and %u groups", fn, nmeters, seq->ntracks, ngroups);
     SeqGains g;
@@ -2161,7 +2262,8 @@ int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples
     shg::pack(gs, ngroups, seq->ntracks, table);
     SeqAuto au{nullptr, nullptr};
     if (automation) au = SeqAuto{(const she::Seg*)automation->block, (const uint32_t*)((const char*)automation->block + automation->at_first)};
-    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, automation ? &au : nullptr, &table);
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, automation ? &au : nullptr, &table,
+                      automation && automation->buses);
 }
 
 int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns) {

@@ -661,13 +661,22 @@ class Automation:
     ``render_into`` and ``chunks`` as ``automation=``: per track a list of pieces ``(start_frame, end_frame, from_volume, to_volume)``,
     packed as segments in song samples and uploaded ONCE into a small device table that this object owns.  ``pieces`` has the checked
     lanes (a tuple of tuples per track, pieces at exactly (1.0, 1.0) dropped), ``segments`` and ``seg_first`` the packed table.
+    ``master`` and ``groups`` hold the checked lanes of the BUSES (``automation(lanes, master=, groups=)``): the master's pieces and a
+    tuple per group lane; ``rides`` is one past the last group lane that kept a piece, 0 where none did -- a render with this object
+    names at least that many groups.
     ``close()`` (or the ``with`` block, or the last reference) frees the table."""
 
-    def __init__(self, song: "CompiledSequence", pieces: tuple, segments: np.ndarray, seg_first: list) -> None:
+    def __init__(self, song: "CompiledSequence", pieces: tuple, segments: np.ndarray, seg_first: list, master: tuple = (),
+                 groups: tuple = ()) -> None:
         self._auto = None
         self._song = song
         self.pieces, self.segments, self.seg_first = pieces, segments, seg_first
-        self._auto = N.SeqAutomation(song._handle(), segments, seg_first)
+        self.master, self.groups = master, groups
+        self.rides = max([g + 1 for g, lane in enumerate(groups) if lane] + [0])      # one past the last group that has a piece
+        if master or self.rides:                                # the lanes of the buses behind the tracks': the entry point that takes them
+            self._auto = N.SeqAutomation(song._handle(), segments, seg_first, len(groups))
+        else:
+            self._auto = N.SeqAutomation(song._handle(), segments, seg_first)
 
     def _handle(self) -> "N.SeqAutomation":
         if self._auto is None:
@@ -791,8 +800,40 @@ class CompiledSequence:
     muted track does; its levels and its tracks' read zero.  With ``meters=True`` ``SongLevels.groups`` holds one ``Levels`` per group,
     over the bus as the master takes it, behind its gain and pan; a track's levels stay what its bus takes of it.  A group's bus alone
     is already ``render(gains=<solo of its tracks>)``.  Still one launch per window and nothing uploaded by a render; ``groups=None``
-    or an empty list is the render without groups.  Not built: automation lanes on a group, groups inside groups, a ``stem`` of a
-    group."""
+    or an empty list is the render without groups.
+    The desk's BUS RIDES: ``automation(lanes, master=, groups=)`` takes a lane for the master and one per group as well -- ``master`` None
+    or a list of pieces, ``groups`` None or at most 8 entries, each None or a list of pieces, entry ``g`` riding the bus of entry ``g`` of
+    whatever ``groups=`` a render names -- checked as a track's lane is and uploaded in the same table.  With ``ride(x, pieces)`` the
+    fader moves' expression above, the chain is, byte for byte, ::
+
+        master = Sample(...)
+        for t, events in enumerate(tracks):
+            sub = sequence(events, ...)                     # then its gain, its fader moves and its pan, as above
+            if t lies in group g:
+                if t == first_g:
+                    bus = Sample(...)
+                bus.mix(sub)
+                if t == end_g - 1:
+                    if gain_g != 1.0:
+                        bus.amplify(gain_g)                 # audioop.mul over the saturated sum
+                    ride(bus, group_lanes[g])               # the group's ride: behind its gain, in front of its pan
+                    if pan_g is not None:
+                        bus.stereo(lf_g, rf_g)
+                    master.mix(bus)
+            else:
+                master.mix(sub)
+        if master_gain != 1.0:
+            master.amplify(master_gain)
+        ride(master, master_lane)                           # the master's ride: behind its gain, on the saturated master
+
+    -- a fade of the drum bus is not a fade of each drum (the group saturates on its own, and ``int((a + b) * f)`` is not ``int(a * f) +
+    int(b * f)``), and a master piece ending at 1.0 is ``Sample.fadein(seconds, from_volume)`` of that clip of the MIX, one starting at
+    1.0 ``Sample.fadeout(seconds, to_volume)``: the fade-out of a whole song.  Positions are song frames, so a window, a chunk or a
+    ``render_into`` at an odd sample offset holds that slice of the whole song's bytes.  With ``meters=True`` a group's levels are read
+    behind its ride and pan, the master's over the bytes returned.  A group at gain 0.0 or pan (0.0, 0.0) still skips its tracks' events.
+    An ``Automation`` that rides group ``g`` needs a render whose ``groups=`` has more than ``g`` entries (``ValueError`` before anything
+    is launched); a master ride alone needs no ``groups=``.  One without a piece on a bus lane is the ``Automation`` there was.  Still one
+    launch per window and nothing uploaded by a render.  Not built: groups inside groups, a ``stem`` of a group, pan automation."""
 
     MAX_TRACKS = 32
 
@@ -994,27 +1035,35 @@ class CompiledSequence:
             out.append((first, end, gain, factors[0], factors[1]))
         return out or None
 
-    def _automation(self, automation) -> Optional["N.SeqAutomation"]:
-        """``automation`` as render hands it on: None, or the native handle of an ``Automation`` that THIS song made -- checked before
+    def _automation(self, automation, groups=None) -> Optional["N.SeqAutomation"]:
+        """``automation`` as render hands it on: None, or the native handle of an ``Automation`` that THIS song made; one that rides
+        group ``g`` needs a render that names more than ``g`` groups (``groups``: what ``_groups`` made of the render's) -- checked before
         anything is launched"""
         if automation is None:
             return None
         if not isinstance(automation, Automation) or automation._song is not self:
             raise ValueError("CompiledSequence: automation is None or an Automation made by this song's automation()")
-        return automation._handle()
+        handle = automation._handle()
+        if automation.rides > len(groups or ()):
+            raise ValueError("CompiledSequence: the automation rides group %d, and this render names %d groups" % (automation.rides - 1, len(groups or ())))
+        return handle
 
-    def automation(self, lanes) -> Automation:
+    def automation(self, lanes, master=None, groups=None) -> Automation:
         """The fader moves of this song of tracks (``CompiledSequence`` has the chain): ``lanes`` has one entry per track, None or a list
         of pieces ``(start_frame, end_frame, from_volume, to_volume)`` -- song frames, ascending, not overlapping, ``start < end <=
         len(song)``, volumes finite and within 0.0 .. 1.0.  A hold (``from_volume == to_volume``) is ``int(x * v)``: the fade's truncation
-        toward zero, not ``audioop.mul``'s floor.  Everything is checked before the device is reached, a ``ValueError`` naming the track
-        and the piece; pieces at exactly (1.0, 1.0) are dropped; the rest are uploaded once into a table the returned ``Automation`` owns."""
+        toward zero, not ``audioop.mul``'s floor.  ``master``: None or such a list for the master, behind its gain.  ``groups``: None or a
+        sequence of at most 8 entries, each None or such a list; entry ``g`` rides the bus of entry ``g`` of whatever ``groups=`` a render
+        names, behind the group's gain and in front of its pan.  Everything is checked before the device is reached, a ``ValueError``
+        naming the track (``master``, ``group g``) and the piece; pieces at exactly (1.0, 1.0) are dropped; the rest are uploaded once into
+        a table the returned ``Automation`` owns."""
         self._handle()
-        pieces = self._check_lanes(lanes)
-        segments, seg_first = self._pack_lanes(pieces, self.nchannels)
-        return Automation(self, pieces, segments, seg_first)
+        pieces, master, groups = self._check_lanes(lanes, master, groups)
+        segments, seg_first = self._pack_lanes(pieces, self.nchannels, master, groups)
+        return Automation(self, pieces, segments, seg_first, master, groups)
 
-    def _check_lanes(self, lanes) -> tuple:
+    def _check_lanes(self, lanes, master=None, groups=None) -> tuple:
+        """(the tracks' lanes, the master's lane, the groups' lanes), checked: every lane through ``_check_lane``"""
         if self.ntracks is None:
             raise ValueError("CompiledSequence: automation needs a song of tracks (compile_tracks); this one has none")
         if self.samplewidth == 3:
@@ -1023,49 +1072,60 @@ class CompiledSequence:
             raise ValueError("CompiledSequence: automation: lanes is a sequence, one entry per track")
         if len(lanes) != self.ntracks:
             raise ValueError("CompiledSequence: automation: %d lanes for %d tracks" % (len(lanes), self.ntracks))
-        out = []
-        for t, lane in enumerate(lanes):
-            if lane is None:
-                out.append(())
-                continue
-            if isinstance(lane, (str, bytes)) or not hasattr(lane, "__iter__"):
-                raise ValueError("CompiledSequence: automation: track %d: a lane is None or a list of pieces" % t)
-            kept, prev = [], 0
-            for k, piece in enumerate(lane):
-                where = "CompiledSequence: automation: track %d, piece %d: " % (t, k)
-                if isinstance(piece, (str, bytes)) or not hasattr(piece, "__len__") or len(piece) != 4:
-                    raise ValueError(where + "a piece is (start_frame, end_frame, from_volume, to_volume)")
-                try:
-                    if isinstance(piece[0], bool) or isinstance(piece[1], bool):
-                        raise TypeError
-                    a, b = operator.index(piece[0]), operator.index(piece[1])
-                except TypeError:
-                    raise ValueError(where + "start_frame and end_frame are integers") from None
-                try:
-                    v0, v1 = float(piece[2]), float(piece[3])
-                except (TypeError, ValueError):
-                    raise ValueError(where + "a piece is (start_frame, end_frame, from_volume, to_volume), four numbers") from None
-                if a < 0 or a >= b:
-                    raise ValueError(where + "frames [%d, %d): a piece starts at 0 or later and ends behind its start" % (a, b))
-                if b > self.frames:
-                    raise ValueError(where + "frames [%d, %d) end past the song's %d frames" % (a, b, self.frames))
-                if a < prev:
-                    raise ValueError(where + "starts at frame %d, before the piece in front of it ends (%d)" % (a, prev))
-                for name, v in (("from_volume", v0), ("to_volume", v1)):
-                    if not math.isfinite(v) or not 0.0 <= v <= 1.0:
-                        raise ValueError(where + "%s %r is not a finite number within 0.0 .. 1.0" % (name, v))
-                prev = b
-                if not (v0 == 1.0 and v1 == 1.0):
-                    kept.append((a, b, v0, v1))
-            out.append(tuple(kept))
-        return tuple(out)
+        if groups is not None:
+            if isinstance(groups, (str, bytes)) or not hasattr(groups, "__len__"):
+                raise ValueError("CompiledSequence: automation: groups is None or a sequence, one entry per group")
+            if len(groups) > self.MAX_GROUPS:
+                raise ValueError("CompiledSequence: automation: %d group lanes, at most %d" % (len(groups), self.MAX_GROUPS))
+        return (tuple(self._check_lane("track %d" % t, lane) for t, lane in enumerate(lanes)), self._check_lane("master", master),
+                tuple(self._check_lane("group %d" % g, lane) for g, lane in enumerate(groups or ())))
+
+    def _check_lane(self, who: str, lane) -> tuple:
+        """one lane -- a track's, the master's or a group's -- as a tuple of pieces ``(start_frame, end_frame, from_volume, to_volume)``,
+        integers and floats, those at exactly (1.0, 1.0) dropped; ``who`` names it in the errors"""
+        if lane is None:
+            return ()
+        if isinstance(lane, (str, bytes)) or not hasattr(lane, "__iter__"):
+            raise ValueError("CompiledSequence: automation: %s: a lane is None or a list of pieces" % who)
+        kept, prev = [], 0
+        for k, piece in enumerate(lane):
+            where = "CompiledSequence: automation: %s, piece %d: " % (who, k)
+            if isinstance(piece, (str, bytes)) or not hasattr(piece, "__len__") or len(piece) != 4:
+                raise ValueError(where + "a piece is (start_frame, end_frame, from_volume, to_volume)")
+            try:
+                if isinstance(piece[0], bool) or isinstance(piece[1], bool):
+                    raise TypeError
+                a, b = operator.index(piece[0]), operator.index(piece[1])
+            except TypeError:
+                raise ValueError(where + "start_frame and end_frame are integers") from None
+            try:
+                v0, v1 = float(piece[2]), float(piece[3])
+            except (TypeError, ValueError):
+                raise ValueError(where + "a piece is (start_frame, end_frame, from_volume, to_volume), four numbers") from None
+            if a < 0 or a >= b:
+                raise ValueError(where + "frames [%d, %d): a piece starts at 0 or later and ends behind its start" % (a, b))
+            if b > self.frames:
+                raise ValueError(where + "frames [%d, %d) end past the song's %d frames" % (a, b, self.frames))
+            if a < prev:
+                raise ValueError(where + "starts at frame %d, before the piece in front of it ends (%d)" % (a, prev))
+            for name, v in (("from_volume", v0), ("to_volume", v1)):
+                if not math.isfinite(v) or not 0.0 <= v <= 1.0:
+                    raise ValueError(where + "%s %r is not a finite number within 0.0 .. 1.0" % (name, v))
+            prev = b
+            if not (v0 == 1.0 and v1 == 1.0):
+                kept.append((a, b, v0, v1))
+        return tuple(kept)
 
     @staticmethod
-    def _pack_lanes(pieces: tuple, nchannels: int) -> tuple:
+    def _pack_lanes(pieces: tuple, nchannels: int, master: tuple = (), groups: tuple = ()) -> tuple:
         """the checked lanes as sh_env_segment rows in song SAMPLES, the tracks' one behind the other, and where each track's start: a
         piece is a fade-in segment (origin its first sample, numsamples its length, slope ``v1 - v0``, offset ``v0``, mul 1.0), a plain
-        segment fills the gap in front of it"""
+        segment fills the gap in front of it.  Where a bus lane -- the master's or a group's -- holds a piece, the lanes of the buses
+        follow the tracks' in the meter table's row order: the master's at ``ntracks``, group ``g``'s at ``ntracks + 1 + g``; where none
+        does, the table is the tracks' alone"""
         rows, seg_first = [], [0]
+        if master or any(groups):
+            pieces = tuple(pieces) + (master,) + tuple(groups)
         for lane in pieces:
             at = 0
             for a, b, v0, v1 in lane:
@@ -1124,7 +1184,7 @@ class CompiledSequence:
         gains = self._gains(gains)
         meters = self._meters(meters)
         groups = self._groups(groups)
-        desk = self._desk(self._pans(pans), self._master(master), self._automation(automation), groups)
+        desk = self._desk(self._pans(pans), self._master(master), self._automation(automation, groups), groups)
         start_frame, nframes = self._range(start_frame, nframes)
         if byte_offset < 0 or byte_offset % self.samplewidth:
             raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
@@ -1152,8 +1212,9 @@ class CompiledSequence:
         self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
-        self._pans(pans), self._master(master), self._automation(automation)      # (checked here as well: before the buffer is made)
+        self._pans(pans), self._master(master)                  # (checked here as well: before the buffer is made)
         ngroups = len(self._groups(groups) or ())
+        self._automation(automation, self._groups(groups))
         start_frame, nframes = self._range(start_frame, nframes)
         out = Sample(name=self.name, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth)
         levels = None
@@ -1190,7 +1251,7 @@ class CompiledSequence:
         self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
-        self._pans(pans), self._master(master), self._automation(automation), self._groups(groups)
+        self._pans(pans), self._master(master), self._automation(automation, self._groups(groups))
         for at in range(0, self.frames, chunk_frames):
             if meters:
                 yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=True, pans=pans, master=master, automation=automation,

@@ -104,7 +104,14 @@ loose tracks.  Wall time with a device synchronise, medians, of the whole song a
 pans=, master=, groups=), the one launch; (b) the caller's way -- every group rendered with every other track muted, amplify and stereo
 on it, the stretches of loose tracks in between rendered the same way, everything mixed in order, the master's amplify -- held to (a)'s
 bytes first; (c) render(gains=, pans=, master=) without groups.  On a tree without groups= only (c) runs: SEQUENCE_AB_TREE=<a built
-checkout of the parent commit> python tools/sequence_ab.py --groups is the parent's own figure for (c), row (d)."""
+checkout of the parent commit> python tools/sequence_ab.py --groups is the parent's own figure for (c), row (d).
+
+--buses: the song of --groups with a ride on each group's bus and a master fade-in / hold / fade-out (automation(lanes, master=,
+groups=)).  The same three rows: (a) render(gains=, pans=, master=, groups=, automation=), the one launch; (b) the caller's way -- every
+group's stem with the other tracks muted, amplify, Sample.fadein / fadeout over the whole piece, clip, join, stereo, mix, the master's
+amplify, then the master's fades in PCM steps the same way -- held to (a)'s bytes first; (c) render(gains=, pans=, master=, groups=)
+without bus lanes.  On a tree whose automation() has no master= only (c) runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit>
+python tools/sequence_ab.py --buses is the parent's own figure for (c), row (d)."""
 import audioop
 import os
 import sys
@@ -113,8 +120,8 @@ from pathlib import Path
 
 import numpy as np
 
-# the yardstick of --plan, --tracks, --desk, --auto and --groups is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
-sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:] or "--groups" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
+# the yardstick of --plan, --tracks, --desk, --auto, --groups and --buses is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
+sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:] or "--groups" in sys.argv[1:] or "--buses" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
 from synthesizer_amd import _native as N  # noqa: E402
 from synthesizer_amd import mixer  # noqa: E402
 from synthesizer_amd.sample import Sample  # noqa: E402
@@ -1347,6 +1354,122 @@ def groups_main():
         bus.close()
 
 
+def bus_lanes(frames):
+    """(the groups' lanes, the master's lane): a ride on each group of GROUPS -- a fade-out, a fade-in, a fade-in and a fade-out -- and on
+    the master a fade-in, a hold at unity (no piece) and the fade-out of the whole song; whole seconds, so that Sample.fadein's seconds
+    are exact frames, and every piece ends or starts at 1.0, so that Sample.fadein / fadeout state it"""
+    groups = [[(20 * RATE, 30 * RATE, 1.0, 0.25)], [(10 * RATE, 25 * RATE, 0.3, 1.0)], [(0, 8 * RATE, 0.0, 1.0), (frames - 10 * RATE, frames, 1.0, 0.5)]]
+    return groups, [(0, 4 * RATE, 0.0, 1.0), (frames - 6 * RATE, frames, 1.0, 0.0)]
+
+
+def buses_main():
+    """--buses: rides of the group buses and of the master in the render's own launch, on the song of --groups.  (a) render(gains=, pans=,
+    master=, groups=, automation=<a ride on each group, a master fade-in / hold / fade-out>); (b) the caller's way: every group's stem with
+    the other tracks muted, amplify, the ride with Sample.fadein / fadeout over the whole piece, clip and join, stereo, mix, the master's
+    amplify, then the master's fades the same way -- held to (a)'s bytes first; (c) render(gains=, pans=, master=, groups=) without bus
+    lanes.  Wall time with a device synchronise, medians; whole song and 4096-frame windows.  A tree whose automation() has no master=
+    runs (c) alone: the parent's figure, row (d)."""
+    import inspect
+    N.ensure_init(0)
+    info = N.device_info()
+    has = "master" in inspect.signature(mixer.CompiledSequence.automation).parameters
+    print("sequence_buses_ab: SYNTHHIP_SEQ_ALIGN=%s  %s  automation(master=, groups=): %s" % (
+        os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"], "yes" if has else "no (the yardstick: (c) alone)"), flush=True)
+    win, ntracks = 4096, len(TRACK_GAINS)
+    desk = dict(gains=TRACK_GAINS, pans=DESK_PANS, master=DESK_MASTER, groups=GROUPS)
+    parts, at_track = [], 0                                     # the desk in order: (first, end, gain, factors, which group) or a loose stretch
+    for k, (first, end, g, pan) in enumerate(GROUPS):
+        if first > at_track:
+            parts.append((at_track, first, None, None, None))
+        parts.append((first, end, g, None if pan is None else pan_factors(pan), k))
+        at_track = end
+    if at_track < ntracks:
+        parts.append((at_track, ntracks, None, None, None))
+    for nevents in (4096, 32768):
+        what, nch, evs = meters_songs(nevents)[0]
+        fb = nch * WIDTH
+        bus = mixer.compile_tracks([evs[t::ntracks] for t in range(ntracks)], RATE, nch, WIDTH)
+        frames = bus.frames
+        out = N.DeviceBuffer(frames * fb + 16)
+        wins = list(range(0, (frames - 3) // win, 16))
+
+        def stream(render):
+            for k in wins:
+                render(k * win, win)
+                N.sync()
+
+        c_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, **desk), 2, 15)
+        c_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, **desk))
+        c_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, **desk)), 1, 5) / len(wins)
+        fmt = lambda v: " ".join("%.4f" % x for x in v)    # noqa: E731
+        head = "buses song 120 s, %5d events, %s, %d tracks, level %s, %d frames   " % (nevents, what, ntracks, bus.level, frames)
+        tail = "(c) render(gains=, pans=, master=, groups=): whole song, wall with a synchronise, median %.4f ms   between two events on the stream, " \
+               "five medians of 15: %s ms   a window of %d frames, wall %.4f ms" % (c_whole, fmt(c_dev), win, c_win)
+        if not has:
+            print(head + tail, flush=True)
+            bus.close()
+            continue
+        glanes, mlane = bus_lanes(frames)
+        auto = bus.automation([None] * ntracks, master=mlane, groups=glanes)
+        at = lambda f: (f + 0.5) / RATE                     # noqa: E731  (seconds that Sample.frame_idx turns back into frame f)
+
+        def rode(sample, a, n, pieces, whole):
+            """``sample``, frames [a, a + n) of a bus behind its gain, with the pieces that reach into it: each faded over its WHOLE length
+            (``whole(pa, length)`` makes that stretch of the bus) -- k counts from the piece's first sample --, clipped and joined in"""
+            for pa, pb, v0, v1 in pieces:
+                lo, hi = max(a, pa), min(a + n, pb)
+                if lo >= hi:
+                    continue
+                move = whole(pa, pb - pa)
+                move.fadein(move.duration, v0) if v1 == 1.0 else move.fadeout(move.duration, v1)
+                move.clip(at(lo - pa), at(hi - pa))
+                behind = sample.copy().clip(at(hi - a), at(n))
+                sample.clip(0.0, at(lo - a)).join(move).join(behind)
+            return sample
+
+        def stem(first, end, g, a, n):
+            solo = [TRACK_GAINS[t] if first <= t < end else 0.0 for t in range(ntracks)]
+            part = bus.render(a, n, gains=solo, pans=DESK_PANS)
+            return part.amplify(g) if g is not None and g != 1.0 else part
+
+        def mixdown(a, n):
+            """the master behind its gain and in front of its ride: one render per group or stretch, the others muted"""
+            master = Sample(samplerate=RATE, nchannels=nch, samplewidth=WIDTH)
+            for first, end, g, factors, k in parts:
+                part = stem(first, end, g, a, n)
+                if k is not None:
+                    part = rode(part, a, n, glanes[k], lambda pa, length: stem(first, end, g, pa, length))
+                if factors is not None:
+                    part.stereo(*factors)
+                master.mix(part)
+            return master.amplify(DESK_MASTER)
+
+        def caller(a, n):
+            """(b): the window as a caller made it"""
+            return rode(mixdown(a, n), a, n, mlane, mixdown)
+
+        inside = (2 * RATE) // win * win + 3                    # a window three frames off inside the master's fade-in and group 2's
+        assert mlane[0][0] < inside and inside + win < mlane[0][1] and glanes[2][0][0] < inside and inside + win < glanes[2][0][1]
+        render = lambda *w: bytes(bus.render(*w, automation=auto, **desk).view_frame_data())      # noqa: E731
+        parity = render() == bytes(caller(0, frames).view_frame_data()) and render(inside, win) == bytes(caller(inside, win).view_frame_data())
+        differs = render(inside, win) != bytes(bus.render(inside, win, **desk).view_frame_data())
+        a_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, automation=auto, **desk), 2, 15)
+        a_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, automation=auto, **desk))
+        a_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, automation=auto, **desk)), 1, 5) / len(wins)
+        b_whole = median_wall(lambda: caller(0, frames), 1, 3)
+        b_win = median_wall(lambda: stream(caller), 1, 3) / len(wins)
+        print(head + "(a) render(gains=, pans=, master=, groups=, automation=<bus lanes>): whole song, wall with a synchronise, median %.4f ms   between "
+              "two events on the stream, five medians of 15: %s ms   a window, wall %.4f ms   (b) %d stems with the others muted, amplify, fadein / "
+              "fadeout, clip, join, stereo, mix, amplify, the master's fades: whole song, wall %.3f ms   a window, wall %.3f ms   %s   (a) / (b) whole "
+              "%.4f, window %.4f   (a) / (c) whole %.3f, window %.3f   (a)'s bytes against (b)'s, whole and a window inside two fades: %s   (a) differs "
+              "from (c) there: %s"
+              % (a_whole, fmt(a_dev), a_win, len(parts), b_whole, b_win, tail, a_whole / b_whole, a_win / b_win, a_whole / c_whole, a_win / c_win,
+                 "ok" if parity else "FAILED", "yes" if differs else "NO"), flush=True)
+        assert parity and differs
+        auto.close()
+        bus.close()
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -1417,4 +1540,4 @@ def main():
 
 
 if __name__ == "__main__":
-    groups_main() if "--groups" in sys.argv[1:] else auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    buses_main() if "--buses" in sys.argv[1:] else groups_main() if "--groups" in sys.argv[1:] else auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
