@@ -876,6 +876,40 @@ int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples
 int sh_seq_auto_create_buses(const sh_seq* seq, const sh_env_segment* segments, uint32_t nsegments, const uint32_t* seg_first, uint32_t ntracks,
                              uint32_t ngroups, sh_seq_auto** out);
 
+/* The desk's PAN RIDES, of a STEREO song: pan moves of a track and of a group's bus, in the same table and the same launch.
+ * sh_seq_auto_create_pans is sh_seq_auto_create_buses (segments, seg_first, ntracks, ngroups: as there) plus a second array of segments,
+ * the PAN LANES: ntracks + ngroups of them, the tracks' and then the groups', pan_segments[pan_first[l] .. pan_first[l + 1]) lane l's,
+ * ntracks + ngroups + 1 offsets.  A pan move over frames [a, b) from pan p0 to p1 (-1.0 .. 1.0) is {kind = 3, origin = 2 a, end = 2 b
+ * (song SAMPLES, both even), numsamples = b - a (FRAMES), offset = p0, slope = p1 - p0, mul = 1.0}; segments of kind 0 fill the gaps.
+ * The chain is sh_seq_render_groups' with the two static pan steps replaced where a move covers a frame:
+ *     sub = the track folded from silence; audioop.mul(gains[t]); the track's fader moves                      (unchanged)
+ *     for each frame f of the song, (L, R) = sub's frame f:
+ *         if f lies in a move [a, b) of track t's pan lane, with k = f - a:
+ *             p = k * slope / numsamples + offset                                   (float64, in this order; k counts FRAMES, in 64 bits)
+ *             (L, R) = (trunc(L * (1.0 - p) / 2.0), trunc(R * (1.0 + p) / 2.0))     (toward zero: Sample.pan(lfo=...)'s expression)
+ *         else:
+ *             (L, R) = (fbound(L * pans[2 t]), fbound(R * pans[2 t + 1]))           (the static pan, unchanged)
+ *     ... into the group's bus or the master as before; and a group's bus the same way: behind its gain and its fader ride, group g's
+ *     pan lane stands where its static factors (left_g, right_g) stand.
+ * The move REPLACES the static pan inside its frames, it is not applied on top of it.  A hold (slope 0) is trunc(x * (1 -+ p) / 2), NOT
+ * Sample.stereo's floor: a hold at 0.0 differs from static factors (0.5, 0.5) on every negative odd sample.  A track or group whose STATIC
+ * factors are both exactly 0.0, or whose gain is 0.0, is still skipped entirely, moves or not.  A track's row of levels is read behind its
+ * pan lane, a group's behind its ride and its pan lane, the master's over the stored bytes.  Positions are song samples whatever the
+ * window.  |p| <= 1 up to one rounding, so no result leaves the width's range and nothing is clamped (csrc/seqpan.hpp has the proof).
+ * SH_ERR_INVALID: what sh_seq_auto_create_buses refuses; a song whose nchannels != 2; pan_first NULL, or pan_segments NULL with
+ * npan_segments != 0; a pan_first that does not start at 0, does not end at npan_segments or decreases; a pan segment whose reserved is
+ * not 0, whose end does not lie past the one before or lies past the song, whose end is odd, whose kind is not 0 or 3 or whose mul is
+ * not exactly 1.0; a move whose origin is not its first sample, whose numsamples is smaller than its frames, or whose pans (offset,
+ * offset + slope) are not finite or leave -1 .. 1.  The error text names `track t pan` or `group g pan` and the segment.
+ * sh_seq_render_auto and sh_seq_render_groups take the handle: one without a pan segment renders exactly as one from
+ * sh_seq_auto_create_buses; tracks' pan moves need no groups (sh_seq_render_auto); SH_ERR_INVALID, nothing launched: a handle with a
+ * segment on group g's pan lane given to sh_seq_render_auto, or to sh_seq_render_groups with ngroups <= g.  Not built: groups inside
+ * groups, a stem of a group, automation at width 3. */
+#define SH_ENV_PAN 3u
+int sh_seq_auto_create_pans(const sh_seq* seq, const sh_env_segment* segments, uint32_t nsegments, const uint32_t* seg_first, uint32_t ntracks,
+                            uint32_t ngroups, const sh_env_segment* pan_segments, uint32_t npan_segments, const uint32_t* pan_first,
+                            sh_seq_auto** out);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

@@ -73,7 +73,8 @@ MIX_EVENT_CHAN_DTYPE = np.dtype([(n, MIX_EVENT_REV_DTYPE.fields[n][0]) for n in 
 MIX_EVENT_DOWNMIX, MIX_EVENT_BALANCE = 2, 4                                                                                  # sh_mix_event_chan.flags
 ENV_SEGMENT_DTYPE = np.dtype([("end", "<u8"), ("origin", "<u8"), ("mul", "<f8"), ("slope", "<f8"), ("numsamples", "<f8"), ("offset", "<f8"),
                               ("kind", "<u4"), ("reserved", "<u4")], align=True)                                             # sh_env_segment
-ENV_NONE, ENV_FADE_IN, ENV_FADE_OUT = 0, 1, 2                                                                                # sh_env_segment.kind
+ENV_PAN = 3                                     # sh_env_segment.kind of a pan move (SH_ENV_PAN; sh_seq_auto_create_pans' pan lanes only)
+ENV_NONE, ENV_FADE_IN, ENV_FADE_OUT = 0, 1, 2                                                                              # sh_env_segment.kind
 
 # sizes the C side must agree with (checked against the library's view in tests via sh_bank_create)
 assert SEGMENT_DTYPE.itemsize == 24 and PARTIAL_DTYPE.itemsize == 16 and ENVELOPE_DTYPE.itemsize == 80
@@ -214,6 +215,8 @@ _SIGNATURES = {
                                      C.c_double, C.POINTER(SeqMeter), C.c_uint32]),
     "sh_seq_auto_create": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(_P)]),
     "sh_seq_auto_create_buses": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "sh_seq_auto_create_pans": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32),
+                                          C.POINTER(_P)]),
     "sh_seq_auto_destroy": (C.c_int, [_P]),
     "sh_seq_render_auto": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
                                      C.c_double, C.POINTER(SeqMeter), C.c_uint32, _P]),
@@ -538,14 +541,24 @@ class SeqAutomation:
     table's row order: the master's behind the last track's, then the groups' (sh_seq_auto_create_buses); a render with such a handle
     names every group it rides."""
 
-    def __init__(self, seq: Sequence, segments: np.ndarray, seg_first, ngroups: Optional[int] = None) -> None:
+    def __init__(self, seq: Sequence, segments: np.ndarray, seg_first, ngroups: Optional[int] = None, pan_segments: Optional[np.ndarray] = None,
+                 pan_first=None) -> None:
         """``ngroups`` None: one lane per track (sh_seq_auto_create).  A number 0 .. SEQ_MAX_GROUPS: the lanes of the buses behind the
-        tracks', in the meter table's row order -- the master's, then ``ngroups`` groups' (sh_seq_auto_create_buses)."""
+        tracks', in the meter table's row order -- the master's, then ``ngroups`` groups' (sh_seq_auto_create_buses).  ``pan_segments``
+        (ENV_SEGMENT_DTYPE rows, moves of kind ENV_PAN) and ``pan_first`` given, with ``ngroups``: the PAN lanes as well, the tracks'
+        and then ``ngroups`` groups', ``ntracks + ngroups + 1`` offsets (sh_seq_auto_create_pans)."""
         ensure_init()
         assert segments.dtype == ENV_SEGMENT_DTYPE and len(seg_first) >= 2 and seg_first[-1] == len(segments)
         self._h = _P()
         first = (C.c_uint32 * len(seg_first))(*seg_first)
-        if ngroups is None:
+        if pan_segments is not None:
+            assert ngroups is not None and 0 <= ngroups and len(seg_first) >= ngroups + 3 and pan_segments.dtype == ENV_SEGMENT_DTYPE
+            ntracks = len(seg_first) - 2 - ngroups
+            assert len(pan_first) == ntracks + ngroups + 1 and pan_first[-1] == len(pan_segments)
+            pfirst = (C.c_uint32 * len(pan_first))(*pan_first)
+            check(lib().sh_seq_auto_create_pans(seq.handle, _ptr(segments), len(segments), first, ntracks, ngroups, _ptr(pan_segments),
+                                                len(pan_segments), pfirst, C.byref(self._h)))
+        elif ngroups is None:
             check(lib().sh_seq_auto_create(seq.handle, _ptr(segments), len(segments), first, len(seg_first) - 1,
                                            C.byref(self._h)))
         else:

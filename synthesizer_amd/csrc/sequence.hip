@@ -67,12 +67,15 @@
 // SeqBusRM (widths 1, 2 and 4), are the group buses again with fader moves on the two bus levels (sh_seq_auto_create_buses: the lanes of
 // the master and of the groups behind the tracks' in the automation's table, no kernel argument of their own): in the close the group's
 // bus through its lane between its gain and its pan, in seq_window_bus the master through its lane behind the master's gain; seq_ride
-// states the shaping once for track, group and master.
+// states the shaping once for track, group and master.  The buses that PAN, SeqBusP and SeqBusPM (widths 1, 2 and 4), are the buses that
+// ride again with pan moves (sh_seq_auto_create_pans; seqpan.hpp): a track's sub-mix and a group's bus pass a pan lane of the same table
+// where they passed their static pan -- seq_pan_ride, once for both; still no kernel argument of their own.
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
 #include "ratecv.hpp"
 #include "seqauto.hpp"
+#include "seqpan.hpp"
 #include "seqenv.hpp"
 #include "seqgroup.hpp"
 #include "seqloop.hpp"
@@ -937,6 +940,16 @@ struct SeqBusR : SeqBusG, SeqRides {};
 template <typename... Bus> constexpr bool SEQ_RIDES = (std::is_base_of<SeqRides, Bus>::value || ...);
 static_assert(sizeof(SeqBusR) == sizeof(SeqBusG) && sha::MAX_GROUP_LANES == shg::MAX_GROUPS, "the rides: no kernel argument of their own");
 
+// PAN RIDES (sh_seq_auto_create_pans): pan moves of a track and of a group's bus, Sample.pan(lfo=...)'s expression per frame (seqpan.hpp),
+// where a pan lane has a move; elsewhere the static factors as ever.  No new kernel argument either: the pan lanes stand in the same
+// table behind the fader lanes' offsets -- track t's at shp::track_lane(row0, t), group g's at shp::group_lane(row0, g) -- and their
+// segments behind the fader lanes' segments.  A tag, and two more bus types at widths 1, 2 and 4 on top of the buses that ride; a handle
+// without a pan move never gets here.
+struct SeqPans {};
+struct SeqBusP : SeqBusR, SeqPans {};
+template <typename... Bus> constexpr bool SEQ_PANS = (std::is_base_of<SeqPans, Bus>::value || ...);
+static_assert(sizeof(SeqBusP) == sizeof(SeqBusG) && SH_ENV_PAN == shp::PAN, "the pan rides: no kernel argument of their own");
+
 // a lane's accumulator: eight packed samples at 16 bits, four 64-bit sums at the other widths
 template <int WIDTH> struct SeqAcc { typedef llong4v type; };
 template <> struct SeqAcc<2> { typedef short8v type; };
@@ -994,6 +1007,33 @@ __device__ __forceinline__ void seq_ride(typename SeqAcc<WIDTH>::type& x, const 
     }
 }
 
+// "Pass this accumulator through pan lane `lane` of the automation's table", stated once for the buses that pan (SeqBusP, SeqBusPM) -- a
+// track's sub-mix and a group's bus, where their static pan stands: one binary search at the tile's first sample, then one of
+// shp::shape_from's uniform paths.  false: no move reaches into the tile and NOTHING was done -- the caller applies the static factors
+// with the code it always had (seq_pan8, seq_mul_add_w); true: x is panned, by the move where one holds the frame and by left / right
+// where none does.
+template <int WIDTH>
+__device__ __forceinline__ bool seq_pan_ride(typename SeqAcc<WIDTH>::type& x, const SeqAuto& au, const uint32_t lane, const uint32_t k, const double left,
+                                             const double right) {
+    constexpr int N = SEQ_LANE<WIDTH>;
+    const uint32_t t0 = k * SEQ_TILE<WIDTH>;
+    const uint32_t a0 = au.afirst[lane];
+    const she::Seg* segs = au.asegs + a0;
+    const uint32_t n = au.afirst[lane + 1] - a0;
+    const uint32_t i = sha::find(segs, n, t0);
+    if (shp::plain(segs, n, i, t0 + SEQ_TILE<WIDTH>)) return false;      // (uniform)
+    int v[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = (int)x[j];
+    shp::shape_from<N>(segs, n, i, t0, t0 + SEQ_TILE<WIDTH>, (long long)t0 + threadIdx.x * N, v, left, right, (double)SEQ_LO<WIDTH>, (double)SEQ_HI<WIDTH>);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        if constexpr (WIDTH == 2) x[j] = (short)v[j];
+        else x[j] = v[j];
+    }
+    return true;
+}
+
 // The runs of tile k, written once for the three templates and every bus: the events from e on, run by run.  walk(e, e1, sub): the
 // schedule of the kernel, events [e, e1) into sub; hook(sub, row): what else a bus does with a track's samples as its bus takes them,
 // post-fader and (a desk bus) post-pan (the metering buses: its row).  Everything about a run is uniform, and a run lists at least one event.
@@ -1007,7 +1047,25 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
     [[maybe_unused]] auto close = [&] {                       // the open group into the master
         if constexpr (SEQ_GROUPS<Bus>) {
             const double gg = bus.groups.gain[open], gl = bus.groups.pan[2 * open], gr = bus.groups.pan[2 * open + 1];
-            if constexpr (SEQ_RIDES<Bus> && WIDTH == 2) {     // the group's ride: behind its gain, in front of its pan
+            if constexpr (SEQ_PANS<Bus> && WIDTH == 2) {      // the group's pan ride: where its static pan stands
+                grp = seq_scale8(grp, gg);
+                seq_ride<2>(grp, bus, sha::group_lane(bus.groups.row0, open), k);
+                if (!seq_pan_ride<2>(grp, bus, shp::group_lane(bus.groups.row0, open), k, gl, gr)) grp = seq_pan8(grp, gl, gr);
+                hook(grp, bus.groups.row0 + open);
+                acc = __builtin_elementwise_add_sat(acc, grp);
+            } else if constexpr (SEQ_PANS<Bus>) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) grp[j] = seq_scale_w<WIDTH>(grp[j], gg);
+                seq_ride<WIDTH>(grp, bus, sha::group_lane(bus.groups.row0, open), k);
+                const bool rode = seq_pan_ride<WIDTH>(grp, bus, shp::group_lane(bus.groups.row0, open), k, gl, gr);      // (uniform)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    long long x = grp[j];
+                    acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, rode ? 1.0 : (j & 1 ? gr : gl));
+                    grp[j] = x;
+                }
+                hook(grp, bus.groups.row0 + open);
+            } else if constexpr (SEQ_RIDES<Bus> && WIDTH == 2) {     // the group's ride: behind its gain, in front of its pan
                 grp = seq_scale8(grp, gg);
                 seq_ride<2>(grp, bus, sha::group_lane(bus.groups.row0, open), k);
                 grp = seq_pan8(grp, gl, gr);
@@ -1096,7 +1154,9 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
                     for (int j = 0; j < 8; ++j) sub[j] = (short)v[j];
                 }
             }
-            if constexpr (SEQ_DESK<Bus>) sub = seq_pan8(sub, left, right);
+            if constexpr (SEQ_PANS<Bus>) {                    // the track's pan ride: where its static pan stands
+                if (!seq_pan_ride<2>(sub, bus, shp::track_lane(bus.groups.row0, run.track), k, left, right)) sub = seq_pan8(sub, left, right);
+            } else if constexpr (SEQ_DESK<Bus>) sub = seq_pan8(sub, left, right);
             hook(sub, run.track);
             bool grouped = false;
             if constexpr (SEQ_GROUPS<Bus>) grouped = of != shg::NONE;
@@ -1109,6 +1169,9 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
 #pragma unroll
                 for (int j = 0; j < 4; ++j) sub[j] = seq_scale_w<WIDTH>(sub[j], g);
                 seq_ride<WIDTH>(sub, bus, run.track, k);
+                if constexpr (SEQ_PANS<Bus>) {                // the track's pan ride; a tile it panned takes no static factor below
+                    if (seq_pan_ride<WIDTH>(sub, bus, shp::track_lane(bus.groups.row0, run.track), k, left, right)) left = right = 1.0;
+                }
             } else if constexpr (SEQ_AUTO<Bus>) {             // the gain over all four first, then the segments; the pan below
                 int v[4];
 #pragma unroll
@@ -1182,6 +1245,8 @@ template <> struct SeqMetered<SeqBusGM> : std::true_type {};
 template <> struct SeqMetered<SeqBusGM3> : std::true_type {};
 struct SeqBusRM : SeqBusGM, SeqRides {};  // the buses that ride, with meters: a group's row behind its ride and pan, the master's behind its ride
 template <> struct SeqMetered<SeqBusRM> : std::true_type {};
+struct SeqBusPM : SeqBusRM, SeqPans {};   // the buses that pan, with meters: a track's row behind its pan ride, a group's behind its ride and its pan ride
+template <> struct SeqMetered<SeqBusPM> : std::true_type {};
 
 // the workgroup's row table, zeroed: every lane of the workgroup calls it (a barrier).  ROWS: 33, or 41 with the rows of the groups
 template <uint32_t ROWS = shq::MAX_TRACKS + 1>
@@ -1736,11 +1801,14 @@ struct sh_seq {
 // block this handle owns; what it says of the song it was made for is what sh_seq_render_auto holds a song to.
 struct sh_seq_auto {
     void*    block = nullptr;             // segments (she::Seg) | first (ntracks + 1 offsets; sh_seq_auto_create_buses: ntracks + 1 + MAX_GROUPS + 1)
+                                          // sh_seq_auto_create_pans: the pan lanes' segments behind the others, their ntracks + MAX_GROUPS + 1 offsets behind the others'
     size_t   cap = 0, bytes = 0, at_first = 0;
     uint32_t ntracks = 0, nsegments = 0;
     uint32_t ngroups = 0;                 // sh_seq_auto_create_buses: the group lanes it was given
     uint32_t ridden = 0;                  // one past the last group lane that has a segment; 0: no group rides
     bool     buses = false;               // a bus lane -- the master's or a group's -- has a segment: the kernels that ride
+    uint32_t panned = 0;                  // sh_seq_auto_create_pans: one past the last group PAN lane that has a segment; 0: none
+    bool     pans = false;                // a pan lane -- a track's or a group's -- has a segment: the kernels that pan
     int      width = 0, nchannels = 0;
     uint64_t track_samples = 0;
 };
@@ -1770,7 +1838,7 @@ void seq_with_level(int level, F f) {
 // boundary.  bus: nothing (a flat list), a SeqBus (a song of tracks: the same kernels with the bus, the gains by value), a SeqBusM (the
 // metering bus: the rows go to the handle's table) or one of the two with the desk (SeqBusD, SeqBusDM: pans and the master's gain by
 // value as well), with automation (SeqBusA, SeqBusAM), with groups (SeqBusG, SeqBusGM; width 3: SeqBusG3, SeqBusGM3) or with groups and
-// rides of the buses (SeqBusR, SeqBusRM), forwarded as the kernels' trailing pack.
+// rides of the buses (SeqBusR, SeqBusRM) or with pan rides on top of those (SeqBusP, SeqBusPM), forwarded as the kernels' trailing pack.
 template <int LEVEL, typename... Bus>
 void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out, const Bus&... bus) {
     typedef typename SeqRec<LEVEL>::type Rec;
@@ -1932,11 +2000,11 @@ template <typename T> struct SeqBaseOf { typedef T type; };
 // sh_seq_render (gains NULL: every track at 1.0), sh_seq_render_gains, sh_seq_render_meters (meters: ntracks + 1 host rows, the handle
 // has tracks), sh_seq_render_desk (desk: the pans and the master's gain, the handle has tracks; with or without meters) and
 // sh_seq_render_auto (au: the automation's table, with a desk) and sh_seq_render_groups (groups: the group table, with a desk, with or
-// without au; meters: ntracks + 1 + ngroups rows; rides: au has a segment on a bus lane, and groups may then be the empty table) behind
-// their names
+// without au; meters: ntracks + 1 + ngroups rows; rides: au has a segment on a bus lane, and groups may then be the empty table; pans: au
+// has a segment on a pan lane, likewise) behind their names
 int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains,
                sh_seq_meter* meters = nullptr, const SeqDesk* desk = nullptr, const SeqAuto* au = nullptr, const shg::Table* groups = nullptr,
-               bool rides = false) {
+               bool rides = false, bool pans = false) {
     static_assert(sizeof(sh_seq_meter) == sizeof(shmt::Row) && offsetof(sh_seq_meter, sq_hi) == offsetof(shmt::Row, sq_hi) &&
                   offsetof(sh_seq_meter, sq_lo) == offsetof(shmt::Row, sq_lo), "sh_seq_meter is shmt::Row");
     const size_t b_meters = meters ? ((size_t)seq->ntracks + 1 + (groups ? groups->n : 0)) * sizeof(shmt::Row) : 0;
@@ -1988,6 +2056,7 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
                 seq_window_launch<LEVEL, G>(seq, grid, st, lo, hi, biased, moved);
             };
             if (seq->width == 3) meters ? grouped(SeqBusGM3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG3{}, SeqBaseOf<SeqBus>());
+            else if (pans) meters ? grouped(SeqBusPM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusP{}, SeqBaseOf<SeqBus>());       // (au: a table with pan lanes)
             else if (rides) meters ? grouped(SeqBusRM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusR{}, SeqBaseOf<SeqBus>());      // (au: a table with bus lanes)
             else meters ? grouped(SeqBusGM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG{}, SeqBaseOf<SeqBus>());
         } else if (au && meters) {
@@ -2089,15 +2158,19 @@ int sh_seq_render_desk(const sh_seq* seq, size_t first_sample, size_t nsamples, 
 
 // sh_seq_auto_create (buses false: ntracks lanes) and sh_seq_auto_create_buses (ntracks + 1 + ngroups lanes in the meter table's row order)
 // behind their names: sha::check's verdict in words, then the table on the device.  Who a lane is: a track, the master or a group.
+// sh_seq_auto_create_pans (pans true): the bus lanes and, in pan_segments and pan_first, ntracks + ngroups pan lanes held to shp::check.
 static int seq_auto_make(const char* fn, const sh_seq* seq, const sh_env_segment* segments, uint32_t nsegments, const uint32_t* seg_first,
-                         uint32_t ntracks, uint32_t ngroups, bool buses, sh_seq_auto** out) {
+                         uint32_t ntracks, uint32_t ngroups, bool buses, sh_seq_auto** out, bool pans = false,
+                         const sh_env_segment* pan_segments = nullptr, uint32_t npan = 0, const uint32_t* pan_first = nullptr) {
     if (!out) return seq_null(fn);
     *out = nullptr;
     if (!seq || !seg_first || (nsegments && !segments)) return seq_null(fn);
+    if (pans && (!pan_first || (npan && !pan_segments))) return seq_null(fn);
     if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
     if (seq->width == 3) return sh::set_error(SH_ERR_INVALID, "%s: width 3: a fader move's fade has no 24-bit form", fn);
     if (ntracks != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u lanes for %u tracks", fn, ntracks, seq->ntracks);
     if (buses && ngroups > shg::MAX_GROUPS) return sh::set_error(SH_ERR_INVALID, "%s: %u group lanes, 0 to %u", fn, ngroups, shg::MAX_GROUPS);
+    if (pans && seq->nchannels != 2) return sh::set_error(SH_ERR_INVALID, "%s: a pan needs a stereo song, this one has %d channels", fn, seq->nchannels);
     const uint32_t nlanes = buses ? sha::lanes(ntracks, ngroups) : ntracks;
     const sha::Verdict v = sha::check(segments, nsegments, seg_first, nlanes, seq->track_samples);
     char who[32];
@@ -2117,6 +2190,25 @@ static int seq_auto_make(const char* fn, const sh_seq* seq, const sh_env_segment
     case sha::NUMSAMPLES: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: numsamples shorter than the move", fn, who, k);
     default: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: a volume is not finite or outside 0 .. 1", fn, who, k);
     }
+    if (pans) {                                               // the pan lanes: the tracks', then the groups'
+        const shp::Verdict p = shp::check(pan_segments, npan, pan_first, shp::lanes(ntracks, ngroups), seq->track_samples);
+        if (p.lane < ntracks) snprintf(who, sizeof who, "track %u pan", p.lane);
+        else snprintf(who, sizeof who, "group %u pan", p.lane - ntracks);
+        const uint32_t j = p.segment;
+        switch (p.why) {
+        case shp::OK: break;
+        case shp::FIRST_ENDS: return sh::set_error(SH_ERR_INVALID, "%s: pan_first starts at 0 and ends at npan_segments", fn);
+        case shp::FIRST_DECREASES: return sh::set_error(SH_ERR_INVALID, "%s: pan_first decreases at %s", fn, who);
+        case shp::RESERVED: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: reserved must be 0", fn, who, j);
+        case shp::ENDS: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: ends not ascending or beyond the song", fn, who, j);
+        case shp::ODD: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: an odd end (a pan segment holds whole frames)", fn, who, j);
+        case shp::KIND: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: kind %u not 0 or 3", fn, who, j, pan_segments[pan_first[p.lane] + j].kind);
+        case shp::MUL: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: mul must be 1.0", fn, who, j);
+        case shp::ORIGIN: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: a move's origin is its first sample", fn, who, j);
+        case shp::NUMSAMPLES: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: numsamples smaller than the move's frames", fn, who, j);
+        default: return sh::set_error(SH_ERR_INVALID, "%s: %s: segment %u: a pan is not finite or outside -1 .. 1", fn, who, j);
+        }
+    }
     sh_seq_auto* a = new (std::nothrow) sh_seq_auto;
     if (!a) return sh::set_error(SH_ERR_NOMEM, "host allocation failed");
     a->ntracks = ntracks;
@@ -2133,13 +2225,27 @@ static int seq_auto_make(const char* fn, const sh_seq* seq, const sh_env_segment
             if (seg_first[ntracks + 1 + g] < seg_first[ntracks + 2 + g]) a->ridden = g + 1;
         a->buses = a->ridden != 0 || seg_first[ntracks] < seg_first[ntracks + 1];
     }
-    a->at_first = (size_t)nsegments * sizeof(she::Seg);
-    a->bytes = a->at_first + noffsets * 4;
+    // with pan lanes the pan segments follow the others and their offsets the others', for every track and every group lane a render may
+    // name (shp::track_lane, shp::group_lane), counted from the table's first segment as the others are
+    const size_t npanoffsets = pans ? (size_t)shp::lanes(ntracks, shg::MAX_GROUPS) + 1 : 0;
+    if (pans) {
+        const uint32_t npanlanes = shp::lanes(ntracks, ngroups);
+        for (uint32_t g = 0; g < ngroups; ++g)
+            if (pan_first[ntracks + g] < pan_first[ntracks + g + 1]) a->panned = g + 1;
+        a->pans = pan_first[npanlanes] != 0;
+    }
+    a->at_first = ((size_t)nsegments + npan) * sizeof(she::Seg);
+    a->bytes = a->at_first + (noffsets + npanoffsets) * 4;
     std::vector<char> host(a->bytes);
     seq_segments(reinterpret_cast<she::Seg*>(host.data()), segments, nsegments);
+    if (pans) seq_segments(reinterpret_cast<she::Seg*>(host.data()) + nsegments, pan_segments, npan);
     uint32_t* first = reinterpret_cast<uint32_t*>(host.data() + a->at_first);
     memcpy(first, seg_first, ((size_t)nlanes + 1) * 4);
     for (size_t i = (size_t)nlanes + 1; i < noffsets; ++i) first[i] = nsegments;
+    if (pans) {
+        const uint32_t npanlanes = shp::lanes(ntracks, ngroups);
+        for (size_t i = 0; i < npanoffsets; ++i) first[noffsets + i] = nsegments + (i <= npanlanes ? pan_first[i] : npan);
+    }
     int rc = sh::pool_alloc(a->bytes, &a->block, &a->cap);
     if (rc) {
         delete a;
@@ -2167,6 +2273,14 @@ int sh_seq_auto_create_buses(const sh_seq* seq, const sh_env_segment* segments, 
                              uint32_t ngroups, sh_seq_auto** out) {
     SH_REQUIRE_INIT();
     return seq_auto_make("sh_seq_auto_create_buses", seq, segments, nsegments, seg_first, ntracks, ngroups, true, out);
+}
+
+int sh_seq_auto_create_pans(const sh_seq* seq, const sh_env_segment* segments, uint32_t nsegments, const uint32_t* seg_first, uint32_t ntracks,
+                            uint32_t ngroups, const sh_env_segment* pan_segments, uint32_t npan_segments, const uint32_t* pan_first,
+                            sh_seq_auto** out) {
+    SH_REQUIRE_INIT();
+    return seq_auto_make("sh_seq_auto_create_pans", seq, segments, nsegments, seg_first, ntracks, ngroups, true, out, true, pan_segments, npan_segments,
+                         pan_first);
 }
 
 int sh_seq_auto_destroy(sh_seq_auto* a) {
@@ -2205,10 +2319,13 @@ int sh_seq_render_auto(const sh_seq* seq, size_t first_sample, size_t nsamples, 
     if (automation->ridden)
         return sh::set_error(SH_ERR_INVALID, "%s: the automation rides group %u, which this call does not name (sh_seq_render_groups does)", fn,
                              automation->ridden - 1);
-    if (automation->buses) {                                  // a master ride alone: the kernels that ride, no group in the table
+    if (automation->panned)
+        return sh::set_error(SH_ERR_INVALID, "%s: the automation rides the pan of group %u, which this call does not name (sh_seq_render_groups does)", fn,
+                             automation->panned - 1);
+    if (automation->buses || automation->pans) {              // a master ride or tracks' pan rides alone: the kernels that ride, no group in the table
         shg::Table none;
         shg::pack(nullptr, 0, seq->ntracks, none);
-        return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, &au, &none, true);
+        return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, &au, &none, true, automation->pans);
     }
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, &au);
 }
@@ -2251,6 +2368,8 @@ int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples
     }
     if (automation && automation->ridden > ngroups)
         return sh::set_error(SH_ERR_INVALID, "%s: the automation rides group %u, and this call names %u groups", fn, automation->ridden - 1, ngroups);
+    if (automation && automation->panned > ngroups)
+        return sh::set_error(SH_ERR_INVALID, "%s: the automation rides the pan of group %u, and this call names %u groups", fn, automation->panned - 1, ngroups);
     if (meters && nmeters != seq->ntracks + 1 + ngroups)
         return sh::set_error(SH_ERR_INVALID, "%s: %u rows for %u tracks, the master and %u groups", fn, nmeters, seq->ntracks, ngroups);
     SeqGains g;
@@ -2263,7 +2382,7 @@ int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples
     SeqAuto au{nullptr, nullptr};
     if (automation) au = SeqAuto{(const she::Seg*)automation->block, (const uint32_t*)((const char*)automation->block + automation->at_first)};
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, automation ? &au : nullptr, &table,
-                      automation && automation->buses);
+                      automation && (automation->buses || automation->pans), automation && automation->pans);
 }
 
 int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns) {

@@ -664,16 +664,25 @@ class Automation:
     ``master`` and ``groups`` hold the checked lanes of the BUSES (``automation(lanes, master=, groups=)``): the master's pieces and a
     tuple per group lane; ``rides`` is one past the last group lane that kept a piece, 0 where none did -- a render with this object
     names at least that many groups.
+    ``pans`` and ``group_pans`` hold the checked PAN lanes (``automation(lanes, pans=, group_pans=)``): a tuple of pieces ``(start_frame,
+    end_frame, from_pan, to_pan)`` per track and per group lane, none dropped; ``pan_segments`` and ``pan_first`` their packed table
+    (None where no pan lane holds a piece: the object is then the one there was); ``pan_rides`` is one past the last group pan lane
+    that holds a piece -- a render names at least that many groups as well.
     ``close()`` (or the ``with`` block, or the last reference) frees the table."""
 
     def __init__(self, song: "CompiledSequence", pieces: tuple, segments: np.ndarray, seg_first: list, master: tuple = (),
-                 groups: tuple = ()) -> None:
+                 groups: tuple = (), pans: tuple = (), group_pans: tuple = (), pan_segments: Optional[np.ndarray] = None,
+                 pan_first: Optional[list] = None) -> None:
         self._auto = None
         self._song = song
         self.pieces, self.segments, self.seg_first = pieces, segments, seg_first
         self.master, self.groups = master, groups
+        self.pans, self.group_pans, self.pan_segments, self.pan_first = pans, group_pans, pan_segments, pan_first
         self.rides = max([g + 1 for g, lane in enumerate(groups) if lane] + [0])      # one past the last group that has a piece
-        if master or self.rides:                                # the lanes of the buses behind the tracks': the entry point that takes them
+        self.pan_rides = max([g + 1 for g, lane in enumerate(group_pans) if lane] + [0])
+        if pan_segments is not None:                            # pan lanes: the entry point that takes them, the buses' lanes in front
+            self._auto = N.SeqAutomation(song._handle(), segments, seg_first, len(seg_first) - 2 - len(pieces), pan_segments, pan_first)
+        elif master or self.rides:                              # the lanes of the buses behind the tracks': the entry point that takes them
             self._auto = N.SeqAutomation(song._handle(), segments, seg_first, len(groups))
         else:
             self._auto = N.SeqAutomation(song._handle(), segments, seg_first)
@@ -833,7 +842,33 @@ class CompiledSequence:
     behind its ride and pan, the master's over the bytes returned.  A group at gain 0.0 or pan (0.0, 0.0) still skips its tracks' events.
     An ``Automation`` that rides group ``g`` needs a render whose ``groups=`` has more than ``g`` entries (``ValueError`` before anything
     is launched); a master ride alone needs no ``groups=``.  One without a piece on a bus lane is the ``Automation`` there was.  Still one
-    launch per window and nothing uploaded by a render.  Not built: groups inside groups, a ``stem`` of a group, pan automation."""
+    launch per window and nothing uploaded by a render.
+    The desk's PAN RIDES, of a stereo song: ``automation(lanes, pans=, group_pans=)`` takes pan lanes as well -- ``pans`` None or one
+    entry per track, ``group_pans`` None or at most 8 entries (entry ``g`` riding the pan of entry ``g`` of a render's ``groups=``), each
+    None or a list of pieces ``(start_frame, end_frame, from_pan, to_pan)`` in SONG frames, ascending, not overlapping, pans finite and
+    within -1.0 .. 1.0 -- uploaded once in the same table.  The chain is the one above with the two pan steps replaced where a piece
+    covers a frame, byte for byte ::
+
+        def pan_ride(x, pieces, lf, rf):                    # x: a track behind its gain and fader moves, a bus behind its gain and ride
+            y = x.copy().stereo(lf, rf)                     # outside the pieces: the static pan, as ever
+            for (a, b, p0, p1) in pieces:
+                n = b - a                                   # FRAMES
+                for k in range(n):                          # k counts FRAMES from the piece's first
+                    p = k * (p1 - p0) / n + p0              # Python floats, in this order
+                    L, R = x[a + k]
+                    y[a + k] = (int(L * (1.0 - p) / 2.0), int(R * (1.0 + p) / 2.0))    # truncated toward zero
+            return y
+
+    -- a piece is ``Sample.pan(lfo=[k * (p1 - p0) / n + p0 for k in range(n)])`` of that clip.  The ride REPLACES the static pan inside
+    its frames; it is not applied on top of it: the pot has one position.  No piece is dropped: a HOLD (``p0 == p1``) is
+    ``int(x * (1 -+ p) / 2)``, truncated toward zero, NOT ``Sample.stereo``'s floor -- a hold at 0.0 differs from the static pan 0.0
+    on every negative odd sample.  A track or group whose STATIC factors are both exactly 0.0, or whose gain is 0.0, is still skipped
+    entirely, pieces or not.  With ``meters=True`` a track's levels are read behind its pan ride, a group's behind its ride and its
+    pan ride, the master's over the bytes returned.  Positions are song frames: a window, a chunk or a ``render_into`` at an odd sample
+    offset holds that slice of the whole song's bytes.  An ``Automation`` that rides the pan of group ``g`` needs a render whose
+    ``groups=`` has more than ``g`` entries (``ValueError`` before anything is launched); one without a pan piece is the
+    ``Automation`` there was.  Still one launch per window and nothing uploaded by a render.  Not built: groups inside groups, a
+    ``stem`` of a group, automation at width 3."""
 
     MAX_TRACKS = 32
 
@@ -1046,9 +1081,12 @@ class CompiledSequence:
         handle = automation._handle()
         if automation.rides > len(groups or ()):
             raise ValueError("CompiledSequence: the automation rides group %d, and this render names %d groups" % (automation.rides - 1, len(groups or ())))
+        if automation.pan_rides > len(groups or ()):
+            raise ValueError("CompiledSequence: the automation rides the pan of group %d, and this render names %d groups"
+                             % (automation.pan_rides - 1, len(groups or ())))
         return handle
 
-    def automation(self, lanes, master=None, groups=None) -> Automation:
+    def automation(self, lanes, master=None, groups=None, pans=None, group_pans=None) -> Automation:
         """The fader moves of this song of tracks (``CompiledSequence`` has the chain): ``lanes`` has one entry per track, None or a list
         of pieces ``(start_frame, end_frame, from_volume, to_volume)`` -- song frames, ascending, not overlapping, ``start < end <=
         len(song)``, volumes finite and within 0.0 .. 1.0.  A hold (``from_volume == to_volume``) is ``int(x * v)``: the fade's truncation
@@ -1056,11 +1094,93 @@ class CompiledSequence:
         sequence of at most 8 entries, each None or such a list; entry ``g`` rides the bus of entry ``g`` of whatever ``groups=`` a render
         names, behind the group's gain and in front of its pan.  Everything is checked before the device is reached, a ``ValueError``
         naming the track (``master``, ``group g``) and the piece; pieces at exactly (1.0, 1.0) are dropped; the rest are uploaded once into
-        a table the returned ``Automation`` owns."""
+        a table the returned ``Automation`` owns.  ``pans`` (None or one entry per track) and ``group_pans`` (None or at most 8 entries,
+        entry ``g`` for the pan of group ``g``), of a stereo song: each entry None or a list of pieces ``(start_frame, end_frame,
+        from_pan, to_pan)``, pans finite and within -1.0 .. 1.0 -- ``Sample.pan(lfo=...)`` of a linear sweep, in place of the static pan
+        inside the piece; a ``ValueError`` names ``track t pan`` or ``group g pan`` and the piece, and no piece is dropped."""
         self._handle()
         pieces, master, groups = self._check_lanes(lanes, master, groups)
-        segments, seg_first = self._pack_lanes(pieces, self.nchannels, master, groups)
-        return Automation(self, pieces, segments, seg_first, master, groups)
+        pans, group_pans = self._check_pan_lanes(pans, group_pans)
+        if not any(pans) and not any(group_pans):               # no pan piece: what was packed, and the entry points reached, before
+            segments, seg_first = self._pack_lanes(pieces, self.nchannels, master, groups)
+            return Automation(self, pieces, segments, seg_first, master, groups, pans, group_pans)
+        ngroups = max(len(groups), len(group_pans))             # both sets of lanes for the same groups, the missing ones empty
+        segments, seg_first = self._pack_lanes(pieces, self.nchannels, master, groups + ((),) * (ngroups - len(groups)), buses=True)
+        pan_segments, pan_first = self._pack_pan_lanes(pans or ((),) * self.ntracks, group_pans + ((),) * (ngroups - len(group_pans)))
+        return Automation(self, pieces, segments, seg_first, master, groups, pans, group_pans, pan_segments, pan_first)
+
+    def _check_pan_lanes(self, pans, group_pans) -> tuple:
+        """(the tracks' pan lanes, the groups' pan lanes), checked: ``()`` for None, else every lane through ``_check_pan_lane``"""
+        if pans is None and group_pans is None:
+            return (), ()
+        if self.nchannels != 2:
+            raise ValueError("CompiledSequence: automation: pans need a stereo song, this one has %d channels" % self.nchannels)
+        if pans is not None:
+            if isinstance(pans, (str, bytes)) or not hasattr(pans, "__len__"):
+                raise ValueError("CompiledSequence: automation: pans is None or a sequence, one entry per track")
+            if len(pans) != self.ntracks:
+                raise ValueError("CompiledSequence: automation: %d pan lanes for %d tracks" % (len(pans), self.ntracks))
+        if group_pans is not None:
+            if isinstance(group_pans, (str, bytes)) or not hasattr(group_pans, "__len__"):
+                raise ValueError("CompiledSequence: automation: group_pans is None or a sequence, one entry per group")
+            if len(group_pans) > self.MAX_GROUPS:
+                raise ValueError("CompiledSequence: automation: %d group pan lanes, at most %d" % (len(group_pans), self.MAX_GROUPS))
+        return (tuple(self._check_pan_lane("track %d pan" % t, lane) for t, lane in enumerate(pans or ())),
+                tuple(self._check_pan_lane("group %d pan" % g, lane) for g, lane in enumerate(group_pans or ())))
+
+    def _check_pan_lane(self, who: str, lane) -> tuple:
+        """one pan lane -- a track's or a group's -- as a tuple of pieces ``(start_frame, end_frame, from_pan, to_pan)``, integers and
+        floats, every piece kept (a hold at 0.0 is a step of its own); ``who`` names it in the errors"""
+        if lane is None:
+            return ()
+        if isinstance(lane, (str, bytes)) or not hasattr(lane, "__iter__"):
+            raise ValueError("CompiledSequence: automation: %s: a lane is None or a list of pieces" % who)
+        kept, prev = [], 0
+        for k, piece in enumerate(lane):
+            where = "CompiledSequence: automation: %s, piece %d: " % (who, k)
+            if isinstance(piece, (str, bytes)) or not hasattr(piece, "__len__") or len(piece) != 4:
+                raise ValueError(where + "a piece is (start_frame, end_frame, from_pan, to_pan)")
+            try:
+                if isinstance(piece[0], bool) or isinstance(piece[1], bool):
+                    raise TypeError
+                a, b = operator.index(piece[0]), operator.index(piece[1])
+            except TypeError:
+                raise ValueError(where + "start_frame and end_frame are integers") from None
+            try:
+                p0, p1 = float(piece[2]), float(piece[3])
+            except (TypeError, ValueError):
+                raise ValueError(where + "a piece is (start_frame, end_frame, from_pan, to_pan), four numbers") from None
+            if a < 0 or a >= b:
+                raise ValueError(where + "frames [%d, %d): a piece starts at 0 or later and ends behind its start" % (a, b))
+            if b > self.frames:
+                raise ValueError(where + "frames [%d, %d) end past the song's %d frames" % (a, b, self.frames))
+            if a < prev:
+                raise ValueError(where + "starts at frame %d, before the piece in front of it ends (%d)" % (a, prev))
+            for name, p in (("from_pan", p0), ("to_pan", p1)):
+                if not math.isfinite(p) or not -1.0 <= p <= 1.0:
+                    raise ValueError(where + "%s %r is not a finite number within -1.0 .. 1.0" % (name, p))
+            prev = b
+            kept.append((a, b, p0, p1))
+        return tuple(kept)
+
+    @staticmethod
+    def _pack_pan_lanes(pans: tuple, group_pans: tuple) -> tuple:
+        """the checked pan lanes as sh_env_segment rows in song SAMPLES of a stereo song, the tracks' one behind the other and then the
+        groups', and where each lane's start: a piece over frames ``[a, b)`` is a pan move (kind ``ENV_PAN``, origin ``2 a``, end ``2 b``,
+        numsamples ``b - a`` -- its FRAMES --, slope ``p1 - p0``, offset ``p0``, mul 1.0), a plain segment fills the gap in front of it"""
+        rows, seg_first = [], [0]
+        for lane in tuple(pans) + tuple(group_pans):
+            at = 0
+            for a, b, p0, p1 in lane:
+                if 2 * a > at:
+                    rows.append((2 * a, 0, 1.0, 0.0, 0.0, 0.0, N.ENV_NONE))
+                rows.append((2 * b, 2 * a, 1.0, p1 - p0, float(b - a), p0, N.ENV_PAN))
+                at = 2 * b
+            seg_first.append(len(rows))
+        segments = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
+        for name, column in zip(("end", "origin", "mul", "slope", "numsamples", "offset", "kind"), zip(*rows) if rows else [()] * 7):
+            segments[name] = column
+        return segments, seg_first
 
     def _check_lanes(self, lanes, master=None, groups=None) -> tuple:
         """(the tracks' lanes, the master's lane, the groups' lanes), checked: every lane through ``_check_lane``"""
@@ -1117,14 +1237,15 @@ class CompiledSequence:
         return tuple(kept)
 
     @staticmethod
-    def _pack_lanes(pieces: tuple, nchannels: int, master: tuple = (), groups: tuple = ()) -> tuple:
+    def _pack_lanes(pieces: tuple, nchannels: int, master: tuple = (), groups: tuple = (), buses: bool = False) -> tuple:
         """the checked lanes as sh_env_segment rows in song SAMPLES, the tracks' one behind the other, and where each track's start: a
         piece is a fade-in segment (origin its first sample, numsamples its length, slope ``v1 - v0``, offset ``v0``, mul 1.0), a plain
         segment fills the gap in front of it.  Where a bus lane -- the master's or a group's -- holds a piece, the lanes of the buses
         follow the tracks' in the meter table's row order: the master's at ``ntracks``, group ``g``'s at ``ntracks + 1 + g``; where none
-        does, the table is the tracks' alone"""
+        does, the table is the tracks' alone -- unless ``buses`` asks for the lanes of the buses anyway (an ``Automation`` with pan
+        lanes: its entry point takes them)"""
         rows, seg_first = [], [0]
-        if master or any(groups):
+        if buses or master or any(groups):
             pieces = tuple(pieces) + (master,) + tuple(groups)
         for lane in pieces:
             at = 0

@@ -111,7 +111,14 @@ groups=)).  The same three rows: (a) render(gains=, pans=, master=, groups=, aut
 group's stem with the other tracks muted, amplify, Sample.fadein / fadeout over the whole piece, clip, join, stereo, mix, the master's
 amplify, then the master's fades in PCM steps the same way -- held to (a)'s bytes first; (c) render(gains=, pans=, master=, groups=)
 without bus lanes.  On a tree whose automation() has no master= only (c) runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit>
-python tools/sequence_ab.py --buses is the parent's own figure for (c), row (d)."""
+python tools/sequence_ab.py --buses is the parent's own figure for (c), row (d).
+
+--pans: the song of --buses, bus lanes and all, with a pan sweep on every track and on one group (automation(lanes, master=, groups=, pans=,
+group_pans=)).  (a) render(gains=, pans=, master=, groups=, automation=<bus lanes and pan lanes>), the one launch; (b) the caller's way --
+every track's stem, clipped at every move, Sample.pan(lfo=ramp) on the clips a piece covers and stereo on the rest, joined, mixed into
+its group's bus or the master, the buses' amplify, fades, pan steps the same way, the master's amplify and fades -- held to (a)'s bytes
+first; (c) the same render with an Automation that has the bus lanes and no pan lanes.  On a tree whose automation() has no pans= only (c)
+runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequence_ab.py --pans is the parent's own figure for (c), row (d)."""
 import audioop
 import os
 import sys
@@ -120,8 +127,8 @@ from pathlib import Path
 
 import numpy as np
 
-# the yardstick of --plan, --tracks, --desk, --auto, --groups and --buses is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
-sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:] or "--groups" in sys.argv[1:] or "--buses" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
+# the yardstick of --plan, --tracks, --desk, --auto, --groups, --buses and --pans is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
+sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:] or "--groups" in sys.argv[1:] or "--buses" in sys.argv[1:] or "--pans" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
 from synthesizer_amd import _native as N  # noqa: E402
 from synthesizer_amd import mixer  # noqa: E402
 from synthesizer_amd.sample import Sample  # noqa: E402
@@ -1470,6 +1477,156 @@ def buses_main():
         bus.close()
 
 
+def pan_lanes(ntracks):
+    """(the tracks' pan lanes, the groups' pan lanes): every track travels across the stereo field once, over a stretch of its own and
+    in alternating directions; group 1 of GROUPS sweeps from left of centre to right of it"""
+    tracks = [[((5 + 3 * t) * RATE, (35 + 9 * t) * RATE, -1.0 if t % 2 else 1.0, 1.0 if t % 2 else -1.0)] for t in range(ntracks)]
+    return tracks, [None, [(12 * RATE, 60 * RATE, -0.8, 0.6)], None]
+
+
+def pans_main():
+    """--pans: pan rides of the tracks and of a group in the render's own launch, on the song of --buses with its bus lanes.  (a) render(gains=,
+    pans=, master=, groups=, automation=<bus lanes and pan lanes>); (b) the caller's way: every track's stem, clipped at every move,
+    Sample.pan(lfo=ramp) on the clips a piece covers, stereo on the rest, join, mix, and the buses' steps of --buses with the group's pan
+    step the same way -- held to (a)'s bytes first; (c) the same render with an Automation without pan lanes.  Wall time with a device
+    synchronise, medians; whole song and 4096-frame windows.  A tree whose automation() has no pans= runs (c) alone: the parent's figure,
+    row (d)."""
+    import inspect
+    N.ensure_init(0)
+    info = N.device_info()
+    has = "pans" in inspect.signature(mixer.CompiledSequence.automation).parameters
+    print("sequence_pans_ab: SYNTHHIP_SEQ_ALIGN=%s  %s  automation(pans=, group_pans=): %s" % (
+        os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"], "yes" if has else "no (the yardstick: (c) alone)"), flush=True)
+    win, ntracks = 4096, len(TRACK_GAINS)
+    desk = dict(gains=TRACK_GAINS, pans=DESK_PANS, master=DESK_MASTER, groups=GROUPS)
+    parts, at_track = [], 0                                     # the desk in order: (first, end, gain, static pan, which group) or a loose stretch
+    for k, (first, end, g, pan) in enumerate(GROUPS):
+        if first > at_track:
+            parts.append((at_track, first, None, None, None))
+        parts.append((first, end, g, pan, k))
+        at_track = end
+    if at_track < ntracks:
+        parts.append((at_track, ntracks, None, None, None))
+    for nevents in (4096, 32768):
+        what, nch, evs = meters_songs(nevents)[0]
+        fb = nch * WIDTH
+        bus = mixer.compile_tracks([evs[t::ntracks] for t in range(ntracks)], RATE, nch, WIDTH)
+        frames = bus.frames
+        out = N.DeviceBuffer(frames * fb + 16)
+        wins = list(range(0, (frames - 3) // win, 16))
+        glanes, mlane = bus_lanes(frames)
+        plain = bus.automation([None] * ntracks, master=mlane, groups=glanes)
+
+        def stream(render):
+            for k in wins:
+                render(k * win, win)
+                N.sync()
+
+        c_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, automation=plain, **desk), 2, 15)
+        c_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, automation=plain, **desk))
+        c_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, automation=plain, **desk)), 1, 5) / len(wins)
+        fmt = lambda v: " ".join("%.4f" % x for x in v)    # noqa: E731
+        head = "pans song 120 s, %5d events, %s, %d tracks, level %s, %d frames   " % (nevents, what, ntracks, bus.level, frames)
+        tail = "(c) render(gains=, pans=, master=, groups=, automation=<bus lanes>): whole song, wall with a synchronise, median %.4f ms   between two " \
+               "events on the stream, five medians of 15: %s ms   a window of %d frames, wall %.4f ms" % (c_whole, fmt(c_dev), win, c_win)
+        if not has:
+            print(head + tail, flush=True)
+            plain.close()
+            bus.close()
+            continue
+        tpans, gpans = pan_lanes(ntracks)
+        auto = bus.automation([None] * ntracks, master=mlane, groups=glanes, pans=tpans, group_pans=gpans)
+        at = lambda f: (f + 0.5) / RATE                     # noqa: E731  (seconds that Sample.frame_idx turns back into frame f)
+
+        def panned(sample, a, n, pieces, pan):
+            """``sample``, frames [a, a + n) of a track or a bus in front of its pan step: clipped at every move, Sample.pan(lfo=ramp) on the
+            clips a piece covers -- the ramp's values counted from the piece's first frame --, the static pan on the rest, joined"""
+            clips, pos = [], a
+
+            def rest(lo, hi):
+                clip = sample.copy().clip(at(lo - a), at(hi - a))
+                clips.append(clip if pan is None else clip.stereo(*pan_factors(pan)))
+            for pa, pb, p0, p1 in pieces or ():
+                lo, hi = max(a, pa), min(a + n, pb)
+                if lo >= hi:
+                    continue
+                if lo > pos:
+                    rest(pos, lo)
+                length = pb - pa
+                ramp = [k * (p1 - p0) / length + p0 for k in range(lo - pa, hi - pa)]
+                clips.append(sample.copy().clip(at(lo - a), at(hi - a)).pan(lfo=ramp))
+                pos = hi
+            if pos < a + n:
+                rest(pos, a + n)
+            whole = clips[0]
+            for clip in clips[1:]:
+                whole.join(clip)
+            return whole
+
+        def rode(sample, a, n, pieces, whole):
+            """--buses' way of a fader ride: each piece that reaches into the window faded over its WHOLE length, clipped and joined in"""
+            for pa, pb, v0, v1 in pieces:
+                lo, hi = max(a, pa), min(a + n, pb)
+                if lo >= hi:
+                    continue
+                move = whole(pa, pb - pa)
+                move.fadein(move.duration, v0) if v1 == 1.0 else move.fadeout(move.duration, v1)
+                move.clip(at(lo - pa), at(hi - pa))
+                behind = sample.copy().clip(at(hi - a), at(n))
+                sample.clip(0.0, at(lo - a)).join(move).join(behind)
+            return sample
+
+        def track(t, a, n):
+            """track t as its bus takes it: its stem at its gain, then its pan step"""
+            return panned(bus.render(a, n, gains=[TRACK_GAINS[t] if u == t else 0.0 for u in range(ntracks)]), a, n, tpans[t], DESK_PANS[t])
+
+        def scaled(first, end, g, a, n):
+            """a group's bus behind its gain, in front of its ride"""
+            grp = Sample(samplerate=RATE, nchannels=nch, samplewidth=WIDTH)
+            for t in range(first, end):
+                grp.mix(track(t, a, n))
+            return grp.amplify(g) if g != 1.0 else grp
+
+        def mixdown(a, n):
+            """the master behind its gain and in front of its ride"""
+            master = Sample(samplerate=RATE, nchannels=nch, samplewidth=WIDTH)
+            for first, end, g, pan, k in parts:
+                if k is None:
+                    for t in range(first, end):
+                        master.mix(track(t, a, n))
+                    continue
+                grp = rode(scaled(first, end, g, a, n), a, n, glanes[k], lambda pa, length: scaled(first, end, g, pa, length))
+                master.mix(panned(grp, a, n, gpans[k], pan))
+            return master.amplify(DESK_MASTER)
+
+        def caller(a, n):
+            """(b): the window as a caller made it"""
+            return rode(mixdown(a, n), a, n, mlane, mixdown)
+
+        inside = (22 * RATE) // win * win + 3                   # a window three frames off inside group 0's fade, group 1's sweep and five tracks' sweeps
+        assert glanes[0][0][0] < inside and inside + win < glanes[0][0][1] and gpans[1][0][0] < inside and inside + win < gpans[1][0][1]
+        assert sum(lane[0][0] < inside and inside + win < lane[0][1] for lane in tpans) >= 4
+        render = lambda *w: bytes(bus.render(*w, automation=auto, **desk).view_frame_data())      # noqa: E731
+        parity = render() == bytes(caller(0, frames).view_frame_data()) and render(inside, win) == bytes(caller(inside, win).view_frame_data())
+        differs = render(inside, win) != bytes(bus.render(inside, win, automation=plain, **desk).view_frame_data())
+        a_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, automation=auto, **desk), 2, 15)
+        a_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, automation=auto, **desk))
+        a_win = median_wall(lambda: stream(lambda a, n: bus.render_into(out, 0, a, n, automation=auto, **desk)), 1, 5) / len(wins)
+        b_whole = median_wall(lambda: caller(0, frames), 0, 3)
+        b_win = median_wall(lambda: stream(caller), 0, 3) / len(wins)
+        print(head + "(a) render(gains=, pans=, master=, groups=, automation=<bus lanes and pan lanes>): whole song, wall with a synchronise, median "
+              "%.4f ms   between two events on the stream, five medians of 15: %s ms   a window, wall %.4f ms   (b) %d stems, clip, Sample.pan(lfo=ramp), "
+              "stereo, join, mix, the buses' amplify, fades and pan steps, the master's amplify and fades: whole song, wall %.3f ms   a window, wall "
+              "%.3f ms   %s   (a) / (b) whole %.5f, window %.4f   (a) / (c) whole %.3f, window %.3f   (a)'s bytes against (b)'s, whole and a window "
+              "inside the sweeps: %s   (a) differs from (c) there: %s"
+              % (a_whole, fmt(a_dev), a_win, ntracks, b_whole, b_win, tail, a_whole / b_whole, a_win / b_win, a_whole / c_whole, a_win / c_win,
+                 "ok" if parity else "FAILED", "yes" if differs else "NO"), flush=True)
+        assert parity and differs
+        auto.close()
+        plain.close()
+        bus.close()
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -1540,4 +1697,4 @@ def main():
 
 
 if __name__ == "__main__":
-    buses_main() if "--buses" in sys.argv[1:] else groups_main() if "--groups" in sys.argv[1:] else auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    pans_main() if "--pans" in sys.argv[1:] else buses_main() if "--buses" in sys.argv[1:] else groups_main() if "--groups" in sys.argv[1:] else auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
