@@ -910,6 +910,28 @@ int sh_seq_auto_create_pans(const sh_seq* seq, const sh_env_segment* segments, u
                             uint32_t ngroups, const sh_env_segment* pan_segments, uint32_t npan_segments, const uint32_t* pan_first,
                             sh_seq_auto** out);
 
+/* The desk's LEVEL HISTORY: the rows of the meters per BLOCK of the window, from the launch that renders it.  A block is one tile of the
+ * SONG's tile grid -- TILE = 2048 samples at width 2, 1024 at widths 1, 3 and 4 -- cut to the window: a render of song samples [lo, hi) has
+ *     nblocks = (hi - 1) / TILE - lo / TILE + 1                                                   (0 for an empty window)
+ * blocks, block j counting song samples [max(lo, (lo / TILE + j) * TILE), min(hi, (lo / TILE + j + 1) * TILE)): the first and the last
+ * may be partial, and a song block that lies whole inside two windows reads the same from both.  sh_seq_render_history is
+ * sh_seq_render_groups -- the same chain, the same bytes -- with three changes: ngroups may be 0 (groups NULL), automation may be NULL, and
+ * instead of meters / nmeters it takes `rows`, a host array of nblocks * nrows rows, block-major: row r of block j at rows[j * nrows + r],
+ * nrows == ntracks + 1 + ngroups in the meter table's order (tracks, master, groups).  Each row is what the meters of a render of that
+ * block's own samples return: post-fader, post-moves and post-pan for a track, over the bus as the master takes it for a group, over the
+ * stored bytes for the master; a muted or skipped track or group and an idle tile read zero; a mono song fills channel 0.  Folding all
+ * blocks (max of the peaks, integer sums of sq_hi and of sq_lo) gives exactly the rows of the metered render of the window.  Every block
+ * is written by the one workgroup that folds its tile: no atomics, no zeroing, the same table on every run.  The device table is the
+ * library's scratch, sized for the call; one launch, one copy of nblocks * nrows rows, one wait.  An empty window writes nothing and
+ * succeeds (nblocks 0).  SH_ERR_INVALID, nothing launched, `out` and `rows` untouched: what sh_seq_render_groups refuses apart from
+ * ngroups == 0; nrows other than ntracks + 1 + ngroups; nblocks other than the window's; rows NULL with a window that is not empty; an
+ * automation handle with a segment on a bus lane or on a pan lane (rides of buses and pans have no history yet).  SH_ERR_NOMEM: the
+ * table cannot be allocated.  Not built: a history with bus rides or pan rides, a history without rendering the bytes, clip counters. */
+int sh_seq_render_history(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                          uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* rows, uint32_t nrows,
+                          uint32_t nblocks, const sh_seq_auto* automation /* may be NULL */, const sh_seq_group* groups /* NULL: none */,
+                          uint32_t ngroups);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

@@ -102,7 +102,10 @@ class SeqGroup(C.Structure):                                                    
     _fields_ = [("first", C.c_uint32), ("end", C.c_uint32), ("gain", C.c_double), ("left", C.c_double), ("right", C.c_double)]
 
 
+SEQ_METER_DTYPE = np.dtype([("peak", "<u4", (2,)), ("sq_hi", "<u8", (2,)), ("sq_lo", "<u8", (2,))])      # sh_seq_meter, 40 bytes, no padding
+assert SEQ_METER_DTYPE.itemsize == C.sizeof(SeqMeter) == 40
 SEQ_MAX_GROUPS = 8                                                                    # SH_SEQ_MAX_GROUPS
+SEQ_TILE_SAMPLES = {1: 1024, 2: 2048, 3: 1024, 4: 1024}                               # shq::tile_samples(width): a block of a level history
 SEQ_LEVELS = ("plain", "rate", "pan", "env", "loop", "rev", "chan")                   # SH_SEQ_LEVEL_*
 
 
@@ -222,6 +225,8 @@ _SIGNATURES = {
                                      C.c_double, C.POINTER(SeqMeter), C.c_uint32, _P]),
     "sh_seq_render_groups": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
                                        C.c_double, C.POINTER(SeqMeter), C.c_uint32, _P, C.POINTER(SeqGroup), C.c_uint32]),
+    "sh_seq_render_history": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
+                                        C.c_double, C.POINTER(SeqMeter), C.c_uint32, C.c_uint32, _P, C.POINTER(SeqGroup), C.c_uint32]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),
@@ -454,6 +459,7 @@ class Sequence:
         ensure_init()
         assert table.dtype == MIX_EVENT_CHAN_DTYPE and (segments is None or segments.dtype == ENV_SEGMENT_DTYPE)
         self._sources = list(sources)
+        self._width = width
         self._h = _P()
         srcs = (C.c_void_p * max(1, len(self._sources)))(*[b.handle for b in self._sources])
         nseg = 0 if segments is None else len(segments)
@@ -488,7 +494,14 @@ class Sequence:
         ``automation`` (a ``SeqAutomation`` of this song) given: sh_seq_render_auto, with or without any of the others.
         ``groups`` (a non-empty list of ``(first_track, end_track, gain, left, right)``) given: sh_seq_render_groups, with or without any
         of the others; the rows of the groups follow the master's.  An ``automation`` with lanes of the buses (``SeqAutomation(...,
-        ngroups)``) goes the same two ways: a master ride alone needs no ``groups``, a ride on group ``g`` more than ``g`` of them."""
+        ngroups)``) goes the same two ways: a master ride alone needs no ``groups``, a ride on group ``g`` more than ``g`` of them.
+        ``meters="history"`` (a song of tracks): sh_seq_render_history -- the same bytes and, from the same launch, the rows per BLOCK of the
+        window, a block being one tile of the song's grid (``SEQ_TILE_SAMPLES[width]`` samples) cut to the window: a numpy array of shape
+        ``(nblocks, nrows)`` and dtype ``SEQ_METER_DTYPE`` (sh_seq_meter's fields; a sum is ``(sq_hi << 32) + sq_lo``), rows in the order
+        ``meters=True`` has them.  With or without any of the others, ``groups`` empty or None included."""
+        if not isinstance(meters, bool) and not (isinstance(meters, str) and meters == "history"):
+            raise ValueError("Sequence.render: meters is True, False or \"history\", not %r" % (meters,))
+
         def doubles(v):
             return None if v is None else (C.c_double * max(1, len(v)))(*v)
 
@@ -496,6 +509,17 @@ class Sequence:
             return 0 if v is None else len(v)
         desk = pans is not None or master is not None
         rows, nrows = None, 0
+        if meters == "history":
+            tile = SEQ_TILE_SAMPLES[self._width]
+            nblocks = (first_sample + nsamples - 1) // tile - first_sample // tile + 1 if nsamples > 0 else 0
+            nrows = self.tracks()[0] + 1 + (len(groups) if groups else 0)
+            blocks = np.zeros((nblocks, nrows), dtype=SEQ_METER_DTYPE)
+            rows = blocks.ctypes.data_as(C.POINTER(SeqMeter)) if nblocks else None
+            table = (SeqGroup * len(groups))(*[SeqGroup(*g) for g in groups]) if groups else None
+            check(lib().sh_seq_render_history(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans),
+                                              count(pans), 1.0 if master is None else master, rows, nrows, nblocks,
+                                              None if automation is None else automation.handle, table, len(groups) if groups else 0))
+            return blocks
         if meters:
             nrows = self.tracks()[0] + 1 + (len(groups) if groups else 0)
             rows = (SeqMeter * nrows)()

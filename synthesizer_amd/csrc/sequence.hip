@@ -69,7 +69,9 @@
 // bus through its lane between its gain and its pan, in seq_window_bus the master through its lane behind the master's gain; seq_ride
 // states the shaping once for track, group and master.  The buses that PAN, SeqBusP and SeqBusPM (widths 1, 2 and 4), are the buses that
 // ride again with pan moves (sh_seq_auto_create_pans; seqpan.hpp): a track's sub-mix and a group's bus pass a pan lane of the same table
-// where they passed their static pan -- seq_pan_ride, once for both; still no kernel argument of their own.
+// where they passed their static pan -- seq_pan_ride, once for both; still no kernel argument of their own.  The HISTORY buses, SeqBusGH
+// (width 3: SeqBusGH3), are the metering group buses again whose workgroups keep their rows: the table a workgroup reduced in LDS is
+// stored as the block of its song tile in a table of blocks (sh_seq_render_history; seqhist.hpp), by plain stores -- seq_hist_end.
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
@@ -78,6 +80,7 @@
 #include "seqpan.hpp"
 #include "seqenv.hpp"
 #include "seqgroup.hpp"
+#include "seqhist.hpp"
 #include "seqloop.hpp"
 #include "seqmeter.hpp"
 #include "seqrev.hpp"
@@ -1247,6 +1250,18 @@ struct SeqBusRM : SeqBusGM, SeqRides {};  // the buses that ride, with meters: a
 template <> struct SeqMetered<SeqBusRM> : std::true_type {};
 struct SeqBusPM : SeqBusRM, SeqPans {};   // the buses that pan, with meters: a track's row behind its pan ride, a group's behind its ride and its pan ride
 template <> struct SeqMetered<SeqBusPM> : std::true_type {};
+// The HISTORY buses (sh_seq_render_history; seqhist.hpp): the metering group buses again -- the whole desk, NULL pointers meaning no moves,
+// the empty table no groups -- whose workgroups KEEP their table instead of merging it: bus.meters points at a table of blocks, one per
+// song tile of the window, and the workgroup that folds tile k stores its ntracks + 1 + groups.n rows as block k - lo / TILE.  No new
+// kernel argument: the first tile and the row count are in the kernel already.  A tag, and one bus type at widths 1, 2 and 4 and one at
+// width 3; the buses that ride and pan have none.
+struct SeqHistory {};
+struct SeqBusGH : SeqBusGM, SeqHistory {};
+struct SeqBusGH3 : SeqBusGM3, SeqHistory {};
+template <> struct SeqMetered<SeqBusGH> : std::true_type {};
+template <> struct SeqMetered<SeqBusGH3> : std::true_type {};
+template <typename... Bus> constexpr bool SEQ_HISTORY = (std::is_base_of<SeqHistory, Bus>::value || ...);
+static_assert(sizeof(SeqBusGH) == sizeof(SeqBusGM) && sizeof(SeqBusGH3) == sizeof(SeqBusGM3), "the history: no kernel argument of its own");
 
 // the workgroup's row table, zeroed: every lane of the workgroup calls it (a barrier).  ROWS: 33, or 41 with the rows of the groups
 template <uint32_t ROWS = shq::MAX_TRACKS + 1>
@@ -1304,6 +1319,20 @@ __device__ __forceinline__ void seq_meter_end(const shmt::Row* table, const SeqB
     if (WIDE) atomicAdd(reinterpret_cast<unsigned long long*>(&g->sq_hi[c]), (unsigned long long)table[row].sq_hi[c]);
 }
 
+// the workgroup's table as block `tile - lo / TILE` of the history's: every lane of the workgroup calls it (a barrier), lane 2 row + channel
+// STORES its three values of (row, channel), zeros as well -- the block has this one writer, so nothing merges and nothing was zeroed
+template <int WIDTH>
+__device__ __forceinline__ void seq_hist_end(const shmt::Row* table, const SeqBusM& bus, const uint32_t groups, const uint32_t tile, const uint32_t lo) {
+    static_assert(2 * (shq::MAX_TRACKS + 1 + shg::MAX_GROUPS) <= shq::TILE_THREADS, "a lane per row and channel");
+    __syncthreads();
+    const uint32_t row = threadIdx.x >> 1, c = threadIdx.x & 1u, nrows = bus.ntracks + 1 + groups;
+    if (row >= nrows) return;
+    shmt::Row* g = bus.meters + shhs::row_at(shhs::block_of(tile, lo, SEQ_TILE<WIDTH>), nrows, row);
+    g->peak[c] = table[row].peak[c];
+    g->sq_hi[c] = table[row].sq_hi[c];
+    g->sq_lo[c] = table[row].sq_lo[c];
+}
+
 // What a window kernel does where it has a bus, once for the three templates: the runs of tile k into acc, (a desk bus) the master's gain,
 // then store().  A plain bus: a lane that seq_window_lane kept; s0, lo and hi, which only a metering bus needs, are ignored.
 // A metering bus: EVERY lane of a workgroup that seq_window_tile kept, the rows of the tracks from seq_runs' hook and the master's row
@@ -1332,7 +1361,8 @@ __device__ __forceinline__ void seq_window_bus(const Bus& bus, uint32_t k, uint3
             seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
             store();
         }
-        if constexpr (SEQ_GROUPS<Bus>) seq_meter_end<WIDE>(table, bus, bus.groups.n);
+        if constexpr (SEQ_HISTORY<Bus>) seq_hist_end<WIDTH>(table, bus, bus.groups.n, k, lo);      // (k: the song tile, in song order whatever workgroup folds it)
+        else if constexpr (SEQ_GROUPS<Bus>) seq_meter_end<WIDE>(table, bus, bus.groups.n);
         else seq_meter_end<WIDE>(table, bus);
     }
 }
@@ -2001,20 +2031,21 @@ template <typename T> struct SeqBaseOf { typedef T type; };
 // has tracks), sh_seq_render_desk (desk: the pans and the master's gain, the handle has tracks; with or without meters) and
 // sh_seq_render_auto (au: the automation's table, with a desk) and sh_seq_render_groups (groups: the group table, with a desk, with or
 // without au; meters: ntracks + 1 + ngroups rows; rides: au has a segment on a bus lane, and groups may then be the empty table; pans: au
-// has a segment on a pan lane, likewise) behind their names
+// has a segment on a pan lane, likewise) and sh_seq_render_history (history: meters is a table of BLOCKS, nblocks * nrows host rows; the
+// device table is the library's scratch, sized for the call, and needs no zeroing) behind their names
 int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains,
                sh_seq_meter* meters = nullptr, const SeqDesk* desk = nullptr, const SeqAuto* au = nullptr, const shg::Table* groups = nullptr,
-               bool rides = false, bool pans = false) {
+               bool rides = false, bool pans = false, bool history = false) {
     static_assert(sizeof(sh_seq_meter) == sizeof(shmt::Row) && offsetof(sh_seq_meter, sq_hi) == offsetof(shmt::Row, sq_hi) &&
                   offsetof(sh_seq_meter, sq_lo) == offsetof(shmt::Row, sq_lo), "sh_seq_meter is shmt::Row");
-    const size_t b_meters = meters ? ((size_t)seq->ntracks + 1 + (groups ? groups->n : 0)) * sizeof(shmt::Row) : 0;
+    const size_t b_rows = meters ? ((size_t)seq->ntracks + 1 + (groups ? groups->n : 0)) * sizeof(shmt::Row) : 0;
     const size_t w = (size_t)seq->width;
     if (first_sample > seq->track_samples || nsamples > seq->track_samples - first_sample)
         return sh::set_error(SH_ERR_INVALID, "%s: range outside the song", fn);
     const size_t have = out->bytes / w;
     if (out_sample > have || nsamples > have - out_sample) return sh::set_error(SH_ERR_INVALID, "%s: range outside out", fn);
     if (!nsamples) {
-        if (meters) memset(meters, 0, b_meters);              // an empty window: every level 0
+        if (meters && !history) memset(meters, 0, b_rows);    // an empty window: every level 0 (a history: no block)
         return SH_OK;
     }
     const char* o0 = (const char*)out->ptr + out_sample * w;
@@ -2022,13 +2053,18 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
     for (size_t v = 0; v < seq->src_lo.size(); ++v)
         if (seq->src_lo[v] < o1 && o0 < seq->src_hi[v]) return sh::set_error(SH_ERR_INVALID, "%s: out overlaps a source of the song", fn);
     const uint32_t lo = (uint32_t)first_sample, hi = (uint32_t)(first_sample + nsamples), tile = shq::tile_samples(seq->width);
-    const uint32_t nt = (hi - 1) / tile - lo / tile + 1;
+    const uint32_t nt = shhs::nblocks(lo, hi, tile);          // the song tiles of the window: its workgroups, and a history's blocks
     // the store's base, biased so that song sample s lands on out[out_sample + s - first_sample]: integer address arithmetic
     void* biased = (void*)((uintptr_t)out->ptr + w * (uintptr_t)out_sample - w * (uintptr_t)first_sample);
     const dim3 grid = sh::grid1d(nt, 1);
     hipStream_t st = sh::state().stream;
+    const size_t b_meters = history ? (size_t)nt * b_rows : b_rows;      // (a history: a block of rows per tile of the window, shhs::nblocks)
     char* table = (char*)seq->block + seq->at_meters;         // (the handle's: one metered render at a time)
-    if (meters) SH_HIP(hipMemsetAsync(table, 0, b_meters, st));
+    if (history) {                                            // the library's scratch, in front of the launch: every block has one writer, no memset
+        const int rc = sh::ensure_scratch(b_meters);
+        if (rc) return rc;
+        table = (char*)sh::state().scratch;
+    } else if (meters) SH_HIP(hipMemsetAsync(table, 0, b_meters, st));
     SeqBusDM bus{};                                           // (a song of tracks; its SeqBusM part is the metering bus, whose SeqBus part is the plain one)
     if (desk) static_cast<SeqDesk&>(bus) = *desk;
     if (seq->ntracks) {
@@ -2055,7 +2091,8 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
                 moved.groups = *groups;
                 seq_window_launch<LEVEL, G>(seq, grid, st, lo, hi, biased, moved);
             };
-            if (seq->width == 3) meters ? grouped(SeqBusGM3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG3{}, SeqBaseOf<SeqBus>());
+            if (history) seq->width == 3 ? grouped(SeqBusGH3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusGH{}, SeqBaseOf<SeqBusM>());
+            else if (seq->width == 3) meters ? grouped(SeqBusGM3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG3{}, SeqBaseOf<SeqBus>());
             else if (pans) meters ? grouped(SeqBusPM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusP{}, SeqBaseOf<SeqBus>());       // (au: a table with pan lanes)
             else if (rides) meters ? grouped(SeqBusRM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusR{}, SeqBaseOf<SeqBus>());      // (au: a table with bus lanes)
             else meters ? grouped(SeqBusGM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG{}, SeqBaseOf<SeqBus>());
@@ -2330,14 +2367,14 @@ int sh_seq_render_auto(const sh_seq* seq, size_t first_sample, size_t nsamples, 
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, &au);
 }
 
-int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
-                         uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters,
-                         const sh_seq_auto* automation, const sh_seq_group* groups, uint32_t ngroups) {
-    SH_REQUIRE_INIT();
-    static const char fn[] = "sh_seq_render_groups";
+// sh_seq_render_groups (history false: meters is NULL or nmeters == ntracks + 1 + ngroups rows, at least one group) and
+// sh_seq_render_history (history true: meters is nblocks blocks of nmeters rows each, groups and automation may be none) behind their names
+static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample,
+                              const double* gains, uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters,
+                              uint32_t nmeters, uint32_t nblocks, const sh_seq_auto* automation, const sh_seq_group* groups, uint32_t ngroups) {
     static_assert(sizeof(sh_seq_group) == sizeof(shg::Group) && offsetof(sh_seq_group, gain) == offsetof(shg::Group, gain) &&
                   offsetof(sh_seq_group, right) == offsetof(shg::Group, right) && SH_SEQ_MAX_GROUPS == shg::MAX_GROUPS, "sh_seq_group is shg::Group");
-    if (!seq || !out || (!gains && ngains) || (!pans && npans) || (!meters && nmeters)) return seq_null(fn);
+    if (!seq || !out || (!gains && ngains) || (!pans && npans) || (!meters && nmeters && !history)) return seq_null(fn);
     if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
     if (automation) {
         if (seq->width == 3) return sh::set_error(SH_ERR_INVALID, "%s: width 3: a fader move's fade has no 24-bit form", fn);
@@ -2349,11 +2386,13 @@ int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples
     if (pans && seq->nchannels != 2) return sh::set_error(SH_ERR_INVALID, "%s: pans need a stereo song, this one has %d channels", fn, seq->nchannels);
     if (gains && ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
     if (pans && npans != 2 * seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u pan factors for %u tracks (two each)", fn, npans, seq->ntracks);
-    if (ngroups == 0 || ngroups > shg::MAX_GROUPS) return sh::set_error(SH_ERR_INVALID, "%s: %u groups, 1 to %u", fn, ngroups, shg::MAX_GROUPS);
-    if (!groups) return seq_null(fn);
+    if ((ngroups == 0 && !history) || ngroups > shg::MAX_GROUPS)
+        return sh::set_error(SH_ERR_INVALID, "%s: %u groups, %u to %u", fn, ngroups, history ? 0u : 1u, shg::MAX_GROUPS);
+    if (!groups && ngroups) return seq_null(fn);
     const shg::Group* gs = reinterpret_cast<const shg::Group*>(groups);
-    const shg::Verdict v = shg::check(gs, ngroups, seq->ntracks, seq->nchannels);
-    const sh_seq_group& b = groups[v.entry];
+    const shg::Verdict v = ngroups ? shg::check(gs, ngroups, seq->ntracks, seq->nchannels) : shg::Verdict{shg::OK, 0};
+    static const sh_seq_group nogroup{};
+    const sh_seq_group& b = ngroups ? groups[v.entry] : nogroup;
     switch (v.why) {
     case shg::OK: break;
     case shg::RANGE_EMPTY: return sh::set_error(SH_ERR_INVALID, "%s: group %u: tracks [%u, %u): an empty range", fn, v.entry, b.first, b.end);
@@ -2364,14 +2403,24 @@ int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples
     case shg::PAN_NOT_FINITE: return sh::set_error(SH_ERR_INVALID, "%s: group %u: left / right is not finite", fn, v.entry);
     case shg::PAN_NOT_STEREO:
         return sh::set_error(SH_ERR_INVALID, "%s: group %u: a pan needs a stereo song, this one has %d channels", fn, v.entry, seq->nchannels);
-    default: return sh::set_error(SH_ERR_INVALID, "%s: %u groups, 1 to %u", fn, ngroups, shg::MAX_GROUPS);
+    default: return sh::set_error(SH_ERR_INVALID, "%s: %u groups, %u to %u", fn, ngroups, history ? 0u : 1u, shg::MAX_GROUPS);
     }
+    if (history && automation && (automation->buses || automation->pans))
+        return sh::set_error(SH_ERR_INVALID, "%s: the automation rides a %s: rides of buses and pans have no history yet", fn,
+                             automation->pans ? "pan" : "bus");
     if (automation && automation->ridden > ngroups)
         return sh::set_error(SH_ERR_INVALID, "%s: the automation rides group %u, and this call names %u groups", fn, automation->ridden - 1, ngroups);
     if (automation && automation->panned > ngroups)
         return sh::set_error(SH_ERR_INVALID, "%s: the automation rides the pan of group %u, and this call names %u groups", fn, automation->panned - 1, ngroups);
-    if (meters && nmeters != seq->ntracks + 1 + ngroups)
+    if ((meters || history) && nmeters != seq->ntracks + 1 + ngroups)
         return sh::set_error(SH_ERR_INVALID, "%s: %u rows for %u tracks, the master and %u groups", fn, nmeters, seq->ntracks, ngroups);
+    if (history) {                                            // the window's blocks, counted as the kernels count them (a window outside the song: seq_render says so)
+        const bool inside = first_sample <= seq->track_samples && nsamples <= seq->track_samples - first_sample;
+        const uint32_t want = inside ? shhs::nblocks(first_sample, first_sample + nsamples, shq::tile_samples(seq->width)) : nblocks;
+        if (nblocks != want)
+            return sh::set_error(SH_ERR_INVALID, "%s: %u blocks for a window of %u (song tiles of %u samples)", fn, nblocks, want, shq::tile_samples(seq->width));
+        if (!meters && nblocks) return seq_null(fn);
+    }
     SeqGains g;
     SeqDesk d;
     int rc = seq_gains(fn, gains, ngains, g);
@@ -2382,7 +2431,23 @@ int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples
     SeqAuto au{nullptr, nullptr};
     if (automation) au = SeqAuto{(const she::Seg*)automation->block, (const uint32_t*)((const char*)automation->block + automation->at_first)};
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, automation ? &au : nullptr, &table,
-                      automation && (automation->buses || automation->pans), automation && automation->pans);
+                      automation && (automation->buses || automation->pans), automation && automation->pans, history);
+}
+
+int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                         uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters,
+                         const sh_seq_auto* automation, const sh_seq_group* groups, uint32_t ngroups) {
+    SH_REQUIRE_INIT();
+    return seq_render_grouped("sh_seq_render_groups", false, seq, first_sample, nsamples, out, out_sample, gains, ngains, pans, npans, master_gain, meters,
+                              nmeters, 0, automation, groups, ngroups);
+}
+
+int sh_seq_render_history(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                          uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* rows, uint32_t nrows,
+                          uint32_t nblocks, const sh_seq_auto* automation, const sh_seq_group* groups, uint32_t ngroups) {
+    SH_REQUIRE_INIT();
+    return seq_render_grouped("sh_seq_render_history", true, seq, first_sample, nsamples, out, out_sample, gains, ngains, pans, npans, master_gain, rows,
+                              nrows, nblocks, automation, groups, ngroups);
 }
 
 int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns) {

@@ -650,10 +650,133 @@ class SongLevels:
         self.master: Levels = made[at]
         self.groups: List[Levels] = made[at + 1:]
 
+    def __eq__(self, other) -> bool:
+        return isinstance(other, SongLevels) and (self.tracks, self.master, self.groups) == (other.tracks, other.master, other.groups)
+
     def __repr__(self) -> str:
         if self.groups:
             return "SongLevels(tracks=%r, master=%r, groups=%r)" % (self.tracks, self.master, self.groups)
         return "SongLevels(tracks=%r, master=%r)" % (self.tracks, self.master)
+
+
+class SongHistory:
+    """The levels of a rendered window OVER TIME (``CompiledSequence.render(meters="history")``): one ``SongLevels`` per BLOCK, all from the
+    one launch that rendered the window.  Blocks are anchored to the SONG, not to the window: block index ``i`` covers song frames
+    ``[i * block_frames, (i + 1) * block_frames)``, cut to the window, so the first and the last block of a window may be partial and a
+    block that lies whole inside two windows reads the same from both.  As rendered, ``block_frames`` is one tile of the song's grid
+    (2048 samples at 16 bits, 1024 at the other widths, over the channels); ``fold(n)`` gives coarser ones.
+
+    ``start_frame``, ``frames``: the window.  ``nblocks`` (``len()``).  ``starts[j]``: the song frame where block ``j``'s counted range
+    begins.  ``history[j]`` (``self[j]``): block ``j``'s ``SongLevels``, whose ``Levels.frames`` is the number of frames counted in that
+    block, so ``rms`` is right in a partial one.  ``total()``: the window's ``SongLevels``, equal to what ``meters=True`` returns for it.
+    ``peaks()``: the peaks as a numpy array ``(nblocks, nrows, 2)``, rows in table order (tracks, master, groups), for drawing; a mono
+    song has ``left == right`` there as in ``Levels``.  ``peak`` (uint32) and ``sum_squares`` (Python ints) are the arrays behind them,
+    shaped ``(nblocks, nrows, 2)``, a mono song's channel 1 reading 0.  A rendered history keeps the table as it came back (``parts``:
+    the two 64-bit sums of every row) and forms Python ints where they are asked for -- a block that is indexed, ``total()``,
+    ``fold(n)``, ``sum_squares`` -- so that the render's call costs no pass over the table in Python."""
+
+    def __init__(self, peak, sum_squares, first_block: int, block_frames: int, start_frame: int, frames: int, samplewidth: int, nchannels: int,
+                 samplerate: int, ngroups: int = 0, parts=None) -> None:
+        self.peak = np.asarray(peak, dtype=np.uint32)
+        self._parts = None if parts is None else (np.asarray(parts[0], dtype=np.uint64), np.asarray(parts[1], dtype=np.uint64))
+        self._sq = None if sum_squares is None else np.asarray(sum_squares, dtype=object)
+        held = [a.shape for a in (self._sq,) + (self._parts or ()) if a is not None]
+        if self.peak.ndim != 3 or self.peak.shape[2] != 2 or not held or any(shape != self.peak.shape for shape in held):
+            raise ValueError("SongHistory: peak and sum_squares are (nblocks, nrows, 2) arrays")
+        self.first_block, self.block_frames = int(first_block), int(block_frames)
+        self.start_frame, self.frames = int(start_frame), int(frames)
+        self.samplewidth, self.nchannels, self.samplerate, self.ngroups = int(samplewidth), int(nchannels), int(samplerate), int(ngroups)
+        self.nblocks = int(self.peak.shape[0])
+        end = self.start_frame + self.frames
+        want = (end - 1) // self.block_frames - self.start_frame // self.block_frames + 1 if self.frames > 0 else 0
+        if self.block_frames <= 0 or self.nblocks != want or (self.nblocks and self.first_block != self.start_frame // self.block_frames):
+            raise ValueError("SongHistory: %d blocks of %d frames from block %d for frames [%d, %d)" % (
+                self.nblocks, self.block_frames, self.first_block, self.start_frame, end))
+        edges = (self.first_block + np.arange(self.nblocks + 1, dtype=np.int64)) * self.block_frames      # the song's grid, cut to the window
+        lows, highs = np.maximum(edges[:-1], self.start_frame), np.minimum(edges[1:], end)
+        self.starts: List[int] = lows.tolist()
+        self.block_counts: List[int] = (highs - lows).tolist()     # the frames counted in each block
+        self.history = self
+
+    @classmethod
+    def from_blocks(cls, blocks, nrows: int, tile_samples: int, start_frame: int, frames: int, samplewidth: int, nchannels: int, samplerate: int,
+                    ngroups: int = 0) -> "SongHistory":
+        """``blocks``: ``N.Sequence.render(meters="history")``'s array ``(nblocks, nrows)`` of sh_seq_meter rows, or None for an empty window"""
+        if blocks is None or not len(blocks):
+            peak = np.zeros((0, nrows, 2), dtype=np.uint32)
+            parts = (np.zeros((0, nrows, 2), dtype=np.uint64),) * 2
+        else:
+            peak, parts = blocks["peak"], (blocks["sq_hi"], blocks["sq_lo"])
+        block_frames = tile_samples // nchannels
+        return cls(peak, None, start_frame // block_frames, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups, parts=parts)
+
+    @property
+    def sum_squares(self) -> np.ndarray:
+        if self._sq is None:                                    # Python ints: a sum passes 2^64 at width 4
+            self._sq = (self._parts[0].astype(object) << 32) + self._parts[1].astype(object)
+        return self._sq
+
+    def __len__(self) -> int:
+        return self.nblocks
+
+    def _rows(self, peak, sq) -> list:
+        return [((int(p[0]), int(p[1])), (int(q[0]), int(q[1]))) for p, q in zip(peak, sq)]
+
+    def __getitem__(self, j: int) -> SongLevels:
+        j = operator.index(j)
+        if j < -self.nblocks or j >= self.nblocks:
+            raise IndexError("SongHistory: block %d of %d" % (j, self.nblocks))
+        j %= self.nblocks
+        sq = self._sq[j] if self._sq is not None else [((int(h[0]) << 32) + int(lo[0]), (int(h[1]) << 32) + int(lo[1]))
+                                                       for h, lo in zip(self._parts[0][j], self._parts[1][j])]
+        return SongLevels(self._rows(self.peak[j], sq), self.block_counts[j], self.samplewidth, self.nchannels, self.samplerate,
+                          self.ngroups)
+
+    def __iter__(self):
+        return (self[j] for j in range(self.nblocks))
+
+    def _sums(self, a: int, b: int) -> np.ndarray:
+        """the sums of blocks ``[a, b)`` added up, ``(nrows, 2)`` Python ints.  A rendered table's two 64-bit parts are added apart, 2^20
+        blocks at a time in uint64 (a block is at most 2048 samples: a part stays below 2^43, 2^20 of them below 2^63), then as ints."""
+        if self._sq is not None:
+            return self._sq[a:b].sum(axis=0)
+        hi = lo = np.zeros(self.peak.shape[1:], dtype=object)
+        for at in range(a, b, 1 << 20):
+            hi = hi + self._parts[0][at:min(b, at + (1 << 20))].sum(axis=0, dtype=np.uint64).astype(object)
+            lo = lo + self._parts[1][at:min(b, at + (1 << 20))].sum(axis=0, dtype=np.uint64).astype(object)
+        return (hi << 32) + lo
+
+    def total(self) -> SongLevels:
+        """the whole window's levels: max of the peaks, sum of the sums (an empty window: every level 0)"""
+        if not self.nblocks:
+            return SongLevels([((0, 0), (0, 0))] * self.peak.shape[1], 0, self.samplewidth, self.nchannels, self.samplerate, self.ngroups)
+        return SongLevels(self._rows(self.peak.max(axis=0), self._sums(0, self.nblocks)), self.frames, self.samplewidth, self.nchannels,
+                          self.samplerate, self.ngroups)
+
+    def fold(self, n: int) -> "SongHistory":
+        """Blocks ``n`` times as long: the blocks merged by ``song block index // n``, so that the result does not depend on where the
+        window began -- peaks take the max, sums add as Python ints, frames add."""
+        n = operator.index(n)
+        if n <= 0:
+            raise ValueError("SongHistory: fold(n) needs a positive n")
+        if not self.nblocks:
+            return SongHistory(self.peak, self.sum_squares, 0, self.block_frames * n, self.start_frame, self.frames, self.samplewidth, self.nchannels,
+                               self.samplerate, self.ngroups)
+        first = self.first_block // n
+        cuts = [0] + [j for j in range(1, self.nblocks) if (self.first_block + j) % n == 0] + [self.nblocks]
+        peak = np.stack([self.peak[a:b].max(axis=0) for a, b in zip(cuts, cuts[1:])])
+        sq = np.stack([self._sums(a, b) for a, b in zip(cuts, cuts[1:])])
+        return SongHistory(peak, sq, first, self.block_frames * n, self.start_frame, self.frames, self.samplewidth, self.nchannels, self.samplerate,
+                           self.ngroups)
+
+    def peaks(self) -> np.ndarray:
+        out = self.peak.copy()
+        if self.nchannels != 2:
+            out[:, :, 1] = out[:, :, 0]
+        return out
+
+    def __repr__(self) -> str:
+        return "SongHistory(%d blocks of %d frames, frames [%d, %d))" % (self.nblocks, self.block_frames, self.start_frame, self.start_frame + self.frames)
 
 
 class Automation:
@@ -752,6 +875,13 @@ class CompiledSequence:
     the same bytes; with ``pans`` a track's levels are post-fader and post-pan, with ``master`` the master's are over the bytes
     returned.  A handle serves one metered render at a time.  Not built: pre-fader meters (they would read a muted track's
     events), meters of a song without tracks, clip counters.
+    The desk's LEVEL HISTORY: ``meters="history"`` gives, still from that one launch, a ``SongHistory`` instead -- the same levels per
+    BLOCK of the window, a block being one tile of the SONG's grid (1024 frames of a 16-bit stereo song, 62 to 125 ms at the tests'
+    rate, 10 to 21 ms at 48 kHz) cut to the window: ``history[j]`` is the ``SongLevels`` that ``meters=True`` gives for block ``j``'s
+    own frames, ``total()`` the one it gives for the window, ``fold(n)`` coarser blocks, ``peaks()`` an array to draw.  Blocks are
+    anchored to the song, so a block that lies whole inside two windows reads the same from both.  With gains, pans, master, groups
+    and the tracks' fader moves.  Not built (``NotImplementedError``): a history with an ``Automation`` that rides a bus or a pan; a
+    history without rendering the bytes; clip counters.
     The desk's FADER AUTOMATION: ``automation(lanes)`` takes, per track, None or a list of pieces ``(start_frame, end_frame, from_volume,
     to_volume)`` in SONG frames -- ascending, not overlapping, volumes finite and within 0.0 .. 1.0 (a static gain above 1 stays with
     ``gains``) -- and uploads them once; ``render``, ``render_into`` and ``chunks`` take the ``Automation`` it returns as
@@ -939,9 +1069,25 @@ class CompiledSequence:
 
     def _meters(self, meters) -> bool:
         """``meters`` as render hands it on -- checked before anything is launched"""
+        if not isinstance(meters, bool) and not (isinstance(meters, str) and meters == "history"):
+            raise ValueError("CompiledSequence: meters is True, False or \"history\", not %r" % (meters,))
         if meters and self.ntracks is None:
             raise ValueError("CompiledSequence: meters need a song of tracks (compile_tracks); this one has none")
-        return bool(meters)
+        if meters == "history" and N.SEQ_TILE_SAMPLES[self.samplewidth] % self.nchannels:
+            raise ValueError("CompiledSequence: a level history needs blocks of whole frames: %d channels do not divide a block of %d samples"
+                             % (self.nchannels, N.SEQ_TILE_SAMPLES[self.samplewidth]))
+        return meters
+
+    @staticmethod
+    def _no_history_of(meters, automation) -> None:
+        """a level history with an ``Automation`` that rides a bus or a pan: not built -- said before anything is launched"""
+        if meters == "history" and automation is not None and (automation.master or automation.rides or automation.pan_segments is not None):
+            raise NotImplementedError("CompiledSequence: rides of buses and pans have no level history yet (meters=\"history\" with an "
+                                      "Automation that has master, group or pan pieces)")
+
+    def _history(self, blocks, start_frame: int, nframes: int, ngroups: int) -> SongHistory:
+        return SongHistory.from_blocks(blocks, self.ntracks + 1 + ngroups, N.SEQ_TILE_SAMPLES[self.samplewidth], start_frame, nframes, self.samplewidth, self.nchannels,
+                                       self.samplerate, ngroups)
 
     def _pans(self, pans) -> Optional[list]:
         """``pans`` as render hands them on: None (no track has a pan step), or ``2 * ntracks`` finite floats, left then right per track,
@@ -1294,21 +1440,30 @@ class CompiledSequence:
 
     def render_into(self, buf: N.DeviceBuffer, byte_offset: int, start_frame: int, nframes: int, gains: Optional[Sequence[float]] = None,
                     meters: bool = False, pans: Optional[Sequence] = None, master: Optional[float] = None,
-                    automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> Optional[SongLevels]:
+                    automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> Union[None, SongLevels, SongHistory]:
         """Frames ``[start_frame, start_frame + nframes)`` of the song into ``buf`` from ``byte_offset`` (a whole number of samples) on:
         every byte of the range is written, whatever ``buf`` held.  ``gains``: one per track of a song of tracks.  ``meters=True``: the
         same bytes, and the window's ``SongLevels`` returned, from the same launch (the call then waits for it).  ``pans``, ``master``:
         a pan per track and the master's gain of a stereo song of tracks (``CompiledSequence``), in that same launch.  ``automation``:
         None or an ``Automation`` made by this song's ``automation()``: its fader moves, in that same launch.  ``groups``: None or the
-        group buses (``CompiledSequence``), in that same launch; the levels then hold a ``Levels`` per group as well."""
+        group buses (``CompiledSequence``), in that same launch; the levels then hold a ``Levels`` per group as well.
+        ``meters="history"``: the same bytes, and the window's ``SongHistory`` returned -- its levels per block of the song's tile grid,
+        still from that one launch."""
         seq = self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
         groups = self._groups(groups)
         desk = self._desk(self._pans(pans), self._master(master), self._automation(automation, groups), groups)
+        self._no_history_of(meters, automation)
         start_frame, nframes = self._range(start_frame, nframes)
         if byte_offset < 0 or byte_offset % self.samplewidth:
             raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
+        if meters == "history":
+            blocks = None
+            if nframes:
+                blocks = seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains,
+                                    meters="history", **desk)
+            return self._history(blocks, start_frame, nframes, len(groups or ()))
         if meters:
             rows = None
             if nframes:
@@ -1326,7 +1481,8 @@ class CompiledSequence:
                pans: Optional[Sequence] = None, master: Optional[float] = None, automation: Optional[Automation] = None,
                groups: Optional[Sequence] = None):
         """A new ``Sample``: frames ``[start_frame, start_frame + nframes)`` of the song; ``nframes`` None: to the end.  ``gains``: one
-        per track of a song of tracks (None: all 1.0).  ``meters=True``: ``(Sample, SongLevels)``, both from the one launch.  ``pans``:
+        per track of a song of tracks (None: all 1.0).  ``meters=True``: ``(Sample, SongLevels)``, both from the one launch;
+        ``meters="history"``: ``(Sample, SongHistory)``, the levels per block of the song's tile grid, from the one launch as well.  ``pans``:
         one entry per track of a stereo song of tracks (None, a number -1 .. 1 or a pair of factors); ``master``: the master's gain;
         ``automation``: this song's fader moves (``automation()``); ``groups``: at most 8 entries ``(first_track, end_track, gain)`` or
         ``(first_track, end_track, gain, pan)``, the group buses (``CompiledSequence`` has the chain)."""
@@ -1336,17 +1492,20 @@ class CompiledSequence:
         self._pans(pans), self._master(master)                  # (checked here as well: before the buffer is made)
         ngroups = len(self._groups(groups) or ())
         self._automation(automation, self._groups(groups))
+        self._no_history_of(meters, automation)
         start_frame, nframes = self._range(start_frame, nframes)
         out = Sample(name=self.name, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth)
         levels = None
         if nframes:
             buf = N.DeviceBuffer(nframes * self._fb)
             if meters:
-                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=True, pans=pans, master=master, automation=automation,
+                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=meters, pans=pans, master=master, automation=automation,
                                           groups=groups)
             else:
                 self.render_into(buf, 0, start_frame, nframes, gains=gains, pans=pans, master=master, automation=automation, groups=groups)
             out._set_device(buf, nframes * self._fb)
+        if meters == "history":
+            return out, levels if levels is not None else self._history(None, start_frame, 0, ngroups)
         if meters:
             return out, levels if levels is not None else self._levels(None, 0, ngroups)
         return out
@@ -1365,7 +1524,7 @@ class CompiledSequence:
                master: Optional[float] = None, automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> Generator:
         """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter.  ``gains``, ``pans``, ``master``,
         ``automation``, ``groups``: as ``render``'s (the joined chunks are the whole render's bytes whatever ``chunk_frames`` cuts).
-        ``meters=True``: ``(Sample, SongLevels)`` pairs."""
+        ``meters=True``: ``(Sample, SongLevels)`` pairs; ``meters="history"``: ``(Sample, SongHistory)`` pairs."""
         chunk_frames = int(chunk_frames)
         if chunk_frames <= 0:
             raise ValueError("CompiledSequence: chunk_frames must be positive")
@@ -1373,9 +1532,10 @@ class CompiledSequence:
         gains = self._gains(gains)
         meters = self._meters(meters)
         self._pans(pans), self._master(master), self._automation(automation, self._groups(groups))
+        self._no_history_of(meters, automation)
         for at in range(0, self.frames, chunk_frames):
             if meters:
-                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=True, pans=pans, master=master, automation=automation,
+                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=meters, pans=pans, master=master, automation=automation,
                                   groups=groups)
             else:
                 yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, pans=pans, master=master, automation=automation, groups=groups)

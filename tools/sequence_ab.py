@@ -118,7 +118,13 @@ group_pans=)).  (a) render(gains=, pans=, master=, groups=, automation=<bus lane
 every track's stem, clipped at every move, Sample.pan(lfo=ramp) on the clips a piece covers and stereo on the rest, joined, mixed into
 its group's bus or the master, the buses' amplify, fades, pan steps the same way, the master's amplify and fades -- held to (a)'s bytes
 first; (c) the same render with an Automation that has the bus lanes and no pan lanes.  On a tree whose automation() has no pans= only (c)
-runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequence_ab.py --pans is the parent's own figure for (c), row (d)."""
+runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequence_ab.py --pans is the parent's own figure for (c), row (d).
+
+--history: the song of --groups (the stereo chan song, 8 tracks, 3 groups, the desk) and its levels over time.  Wall time with a device
+synchronise, medians, of the whole song, for: (a) one render(meters="history", ...), the one launch, the table of blocks read back; (b) the
+caller's way today -- chunks(block_frames, meters=True, ...) over the whole song, one metered render per block -- whose master rows are
+held to (a)'s first; (c) the same render with meters=True.  On a tree without meters="history" only (c) runs: SEQUENCE_AB_TREE=<a built
+checkout of the parent commit> python tools/sequence_ab.py --history is the parent's own figure for (c), row (d)."""
 import audioop
 import os
 import sys
@@ -127,8 +133,8 @@ from pathlib import Path
 
 import numpy as np
 
-# the yardstick of --plan, --tracks, --desk, --auto, --groups, --buses and --pans is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
-sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:] or "--groups" in sys.argv[1:] or "--buses" in sys.argv[1:] or "--pans" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
+# the yardstick of --plan, --tracks, --desk, --auto, --groups, --buses, --pans and --history is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
+sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:] or "--groups" in sys.argv[1:] or "--buses" in sys.argv[1:] or "--pans" in sys.argv[1:] or "--history" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
 from synthesizer_amd import _native as N  # noqa: E402
 from synthesizer_amd import mixer  # noqa: E402
 from synthesizer_amd.sample import Sample  # noqa: E402
@@ -1627,6 +1633,58 @@ def pans_main():
         bus.close()
 
 
+def history_main():
+    """--history: the levels of the whole song per block of the song's tile grid.  (a) render_into(meters="history", gains=, pans=, master=,
+    groups=), the one launch; (b) the caller's way today: chunks(block_frames, meters=True, ...) over the whole song, one metered render
+    per block -- its master rows held to (a)'s first; (c) render_into(meters=True, ...) of the whole song.  Wall time with a device
+    synchronise, medians.  A tree without meters="history" runs (c) alone."""
+    N.ensure_init(0)
+    info = N.device_info()
+    has = hasattr(mixer, "SongHistory")
+    print("sequence_history_ab: SYNTHHIP_SEQ_ALIGN=%s  %s  meters=\"history\": %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"],
+          "yes" if has else "no (the yardstick: (c) alone)"), flush=True)
+    ntracks = len(TRACK_GAINS)
+    desk = dict(gains=TRACK_GAINS, pans=DESK_PANS, master=DESK_MASTER, groups=GROUPS)
+    for nevents in (4096, 32768):
+        what, nch, evs = meters_songs(nevents)[0]
+        fb = nch * WIDTH
+        bus = mixer.compile_tracks([evs[t::ntracks] for t in range(ntracks)], RATE, nch, WIDTH)
+        frames = bus.frames
+        out = N.DeviceBuffer(frames * fb + 16)
+        c_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, meters=True, **desk), 2, 15)
+        c_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, meters=True, **desk))
+        fmt = lambda v: " ".join("%.4f" % x for x in v)    # noqa: E731
+        head = "history song 120 s, %5d events, %s, %d tracks, %d groups, level %s, %d frames   " % (nevents, what, ntracks, len(GROUPS), bus.level, frames)
+        tail = "(c) render(meters=True, gains=, pans=, master=, groups=): whole song, wall with a synchronise, median %.4f ms   between two events on " \
+               "the stream, five medians of 15: %s ms" % (c_whole, fmt(c_dev))
+        if not has:
+            print(head + tail, flush=True)
+            bus.close()
+            continue
+        block = TILE // nch
+
+        def caller():
+            """(b): a metered render per block, the levels kept"""
+            return [lv for _s, lv in bus.chunks(block, meters=True, **desk)]
+
+        h = bus.render_into(out, 0, 0, frames, meters="history", **desk)
+        theirs = caller()
+        parity = h.nblocks == len(theirs) and all(h[j] == lv for j, lv in enumerate(theirs)) and h.total() == bus.render_into(out, 0, 0, frames, meters=True, **desk)
+        a_whole = median_wall(lambda: bus.render_into(out, 0, 0, frames, meters="history", **desk), 2, 15)
+        a_dev = five_medians(lambda: bus.render_into(out, 0, 0, frames, meters="history", **desk))
+        a_raw = median_wall(lambda: bus._handle().render(0, frames * nch, out, 0, gains=list(TRACK_GAINS), meters="history", pans=bus._pans(DESK_PANS),
+                                                         master=DESK_MASTER, groups=bus._groups(GROUPS)), 2, 15)
+        b_whole = median_wall(caller, 1, 3)
+        print(head + "(a) render(meters=\"history\", gains=, pans=, master=, groups=): %d blocks of %d frames, %d rows each: whole song, wall with a "
+              "synchronise, median %.4f ms (the entry point alone, without the SongHistory: %.4f ms)   between two events on the stream, five medians "
+              "of 15: %s ms   (b) chunks(%d, meters=True, ...), %d metered renders: whole song, wall %.3f ms   %s   (a) / (b) %.5f   (a) / (c) %.3f   "
+              "(a)'s blocks against (b)'s levels and its total against (c)'s: %s"
+              % (h.nblocks, block, ntracks + 1 + len(GROUPS), a_whole, a_raw, fmt(a_dev), block, len(theirs), b_whole, tail, a_whole / b_whole,
+                 a_whole / c_whole, "ok" if parity else "FAILED"), flush=True)
+        assert parity
+        bus.close()
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -1697,4 +1755,4 @@ def main():
 
 
 if __name__ == "__main__":
-    pans_main() if "--pans" in sys.argv[1:] else buses_main() if "--buses" in sys.argv[1:] else groups_main() if "--groups" in sys.argv[1:] else auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    history_main() if "--history" in sys.argv[1:] else pans_main() if "--pans" in sys.argv[1:] else buses_main() if "--buses" in sys.argv[1:] else groups_main() if "--groups" in sys.argv[1:] else auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
