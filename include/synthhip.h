@@ -926,11 +926,36 @@ int sh_seq_auto_create_pans(const sh_seq* seq, const sh_env_segment* segments, u
  * succeeds (nblocks 0).  SH_ERR_INVALID, nothing launched, `out` and `rows` untouched: what sh_seq_render_groups refuses apart from
  * ngroups == 0; nrows other than ntracks + 1 + ngroups; nblocks other than the window's; rows NULL with a window that is not empty; an
  * automation handle with a segment on a bus lane or on a pan lane (rides of buses and pans have no history yet).  SH_ERR_NOMEM: the
- * table cannot be allocated.  Not built: a history with bus rides or pan rides, a history without rendering the bytes, clip counters. */
+ * table cannot be allocated.  Not built: a history with bus rides or pan rides, a history without rendering the bytes. */
 int sh_seq_render_history(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
                           uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* rows, uint32_t nrows,
                           uint32_t nblocks, const sh_seq_auto* automation /* may be NULL */, const sh_seq_group* groups /* NULL: none */,
                           uint32_t ngroups);
+
+/* The history's OVERS: sh_seq_render_history -- the same arguments, the same chain, the same bytes, the same levels per block, the same
+ * checks and refusals -- whose rows carry, behind the levels, `clipped`: per channel the number of the block's samples at which AT LEAST
+ * ONE of the row's OWN steps was clamped (csrc/seqclip.hpp states the contract).  A step is clamped where the value it would have produced
+ * without the clamp lies outside the width's range [LO, HI]; a sample counts ONCE per row, however many steps clamped at it.  Track t's
+ * steps: every saturating add of an event's samples into the track's sub-mix, the track's amplify(gain), its static pan factors.  Group
+ * g's: every saturating add of a track into the group's bus, the group's amplify(gain), its pan factors.  The master's: every saturating
+ * add of a track or a group into the master, the master's amplify(master_gain).  An add clamps where the exact integer sum of the
+ * saturated accumulator and the addend is > HI or < LO; a multiply by a factor f != 1.0 clamps where floor(p) > HI or floor(p) < LO, p
+ * the float64 product audioop.mul forms (a product in (HI, HI + 1) floors to HI and is no over).  A row counts its OWN stage only: a track
+ * that clipped does not make its group or the master count.  Not counted: what an event does to its own samples in front of the add (its
+ * volume, pan, channel factors, envelope), and the tracks' fader moves, which cannot leave the range.  A muted or skipped track or group
+ * and an idle tile count 0; a mono song fills channel 0.  Counts add over blocks.  SH_ERR_INVALID, nothing launched: what
+ * sh_seq_render_history refuses, a bus ride or pan ride with a message of its own.  Not built: overs of an event's own chain, overs with
+ * bus or pan rides. */
+typedef struct sh_seq_meter_clips {
+    uint32_t peak[2];
+    uint64_t sq_hi[2];
+    uint64_t sq_lo[2];
+    uint32_t clipped[2];
+} sh_seq_meter_clips;              /* 48 bytes: sh_seq_meter, then the counts */
+int sh_seq_render_clips(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                        uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter_clips* rows, uint32_t nrows,
+                        uint32_t nblocks, const sh_seq_auto* automation /* may be NULL */, const sh_seq_group* groups /* NULL: none */,
+                        uint32_t ngroups);
 
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads

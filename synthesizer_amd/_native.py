@@ -104,6 +104,12 @@ class SeqGroup(C.Structure):                                                    
 
 SEQ_METER_DTYPE = np.dtype([("peak", "<u4", (2,)), ("sq_hi", "<u8", (2,)), ("sq_lo", "<u8", (2,))])      # sh_seq_meter, 40 bytes, no padding
 assert SEQ_METER_DTYPE.itemsize == C.sizeof(SeqMeter) == 40
+class SeqMeterClips(C.Structure):                                                    # sh_seq_meter_clips
+    _fields_ = SeqMeter._fields_ + [("clipped", C.c_uint32 * 2)]
+
+
+SEQ_METER_CLIPS_DTYPE = np.dtype(SEQ_METER_DTYPE.descr + [("clipped", "<u4", (2,))])    # sh_seq_meter_clips, 48 bytes, no padding
+assert SEQ_METER_CLIPS_DTYPE.itemsize == C.sizeof(SeqMeterClips) == 48
 SEQ_MAX_GROUPS = 8                                                                    # SH_SEQ_MAX_GROUPS
 SEQ_TILE_SAMPLES = {1: 1024, 2: 2048, 3: 1024, 4: 1024}                               # shq::tile_samples(width): a block of a level history
 SEQ_LEVELS = ("plain", "rate", "pan", "env", "loop", "rev", "chan")                   # SH_SEQ_LEVEL_*
@@ -227,6 +233,8 @@ _SIGNATURES = {
                                        C.c_double, C.POINTER(SeqMeter), C.c_uint32, _P, C.POINTER(SeqGroup), C.c_uint32]),
     "sh_seq_render_history": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
                                         C.c_double, C.POINTER(SeqMeter), C.c_uint32, C.c_uint32, _P, C.POINTER(SeqGroup), C.c_uint32]),
+    "sh_seq_render_clips": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
+                                      C.c_double, C.POINTER(SeqMeterClips), C.c_uint32, C.c_uint32, _P, C.POINTER(SeqGroup), C.c_uint32]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),
@@ -487,7 +495,7 @@ class Sequence:
         return nt.value, nr.value
 
     def render(self, first_sample: int, nsamples: int, out: "DeviceBuffer", out_sample: int = 0, gains=None, meters: bool = False, pans=None,
-               master=None, automation: Optional["SeqAutomation"] = None, groups=None):
+               master=None, automation: Optional["SeqAutomation"] = None, groups=None, clips: bool = False):
         """``meters=True`` (a song of tracks): sh_seq_render_meters -- the same bytes and, from the same launch, one row per track and one for
         the master, each ``(peak, sum_squares)`` of per-channel pairs, the sums exact Python ints.  Otherwise None.
         ``pans`` (2 * ntracks factors, left then right per track) or ``master`` (a gain) given: sh_seq_render_desk, with or without meters.
@@ -498,9 +506,13 @@ class Sequence:
         ``meters="history"`` (a song of tracks): sh_seq_render_history -- the same bytes and, from the same launch, the rows per BLOCK of the
         window, a block being one tile of the song's grid (``SEQ_TILE_SAMPLES[width]`` samples) cut to the window: a numpy array of shape
         ``(nblocks, nrows)`` and dtype ``SEQ_METER_DTYPE`` (sh_seq_meter's fields; a sum is ``(sq_hi << 32) + sq_lo``), rows in the order
-        ``meters=True`` has them.  With or without any of the others, ``groups`` empty or None included."""
+        ``meters=True`` has them.  With or without any of the others, ``groups`` empty or None included.
+        ``clips=True`` with ``meters="history"``: sh_seq_render_clips -- the same, the array's dtype ``SEQ_METER_CLIPS_DTYPE``: a field
+        ``clipped`` behind the levels, per channel the block's samples at which the row's own arithmetic was clamped."""
         if not isinstance(meters, bool) and not (isinstance(meters, str) and meters == "history"):
             raise ValueError("Sequence.render: meters is True, False or \"history\", not %r" % (meters,))
+        if clips and meters != "history":
+            raise ValueError("Sequence.render: clips=True counts per block of a history: it needs meters=\"history\"")
 
         def doubles(v):
             return None if v is None else (C.c_double * max(1, len(v)))(*v)
@@ -513,10 +525,11 @@ class Sequence:
             tile = SEQ_TILE_SAMPLES[self._width]
             nblocks = (first_sample + nsamples - 1) // tile - first_sample // tile + 1 if nsamples > 0 else 0
             nrows = self.tracks()[0] + 1 + (len(groups) if groups else 0)
-            blocks = np.zeros((nblocks, nrows), dtype=SEQ_METER_DTYPE)
-            rows = blocks.ctypes.data_as(C.POINTER(SeqMeter)) if nblocks else None
+            blocks = np.zeros((nblocks, nrows), dtype=SEQ_METER_CLIPS_DTYPE if clips else SEQ_METER_DTYPE)
+            rows = blocks.ctypes.data_as(C.POINTER(SeqMeterClips if clips else SeqMeter)) if nblocks else None
             table = (SeqGroup * len(groups))(*[SeqGroup(*g) for g in groups]) if groups else None
-            check(lib().sh_seq_render_history(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans),
+            entry = lib().sh_seq_render_clips if clips else lib().sh_seq_render_history
+            check(entry(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans),
                                               count(pans), 1.0 if master is None else master, rows, nrows, nblocks,
                                               None if automation is None else automation.handle, table, len(groups) if groups else 0))
             return blocks

@@ -71,12 +71,17 @@
 // ride again with pan moves (sh_seq_auto_create_pans; seqpan.hpp): a track's sub-mix and a group's bus pass a pan lane of the same table
 // where they passed their static pan -- seq_pan_ride, once for both; still no kernel argument of their own.  The HISTORY buses, SeqBusGH
 // (width 3: SeqBusGH3), are the metering group buses again whose workgroups keep their rows: the table a workgroup reduced in LDS is
-// stored as the block of its song tile in a table of blocks (sh_seq_render_history; seqhist.hpp), by plain stores -- seq_hist_end.
+// stored as the block of its song tile in a table of blocks (sh_seq_render_history; seqhist.hpp), by plain stores -- seq_hist_end.  The
+// buses that COUNT OVERS, SeqBusGC (width 3: SeqBusGC3), are the history buses again whose lanes fold into COUNTING accumulators -- the
+// samples and one sticky flag per sample, set where a step of the bus's own arithmetic was clamped (seqclip.hpp: an add whose exact sum
+// leaves the range, a multiply whose floor does) -- through the same schedules and the same seq_runs, which are generic in the
+// accumulator's type; a row carries the count of flagged samples behind its levels (sh_seq_render_clips).
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
 #include "ratecv.hpp"
 #include "seqauto.hpp"
+#include "seqclip.hpp"
 #include "seqpan.hpp"
 #include "seqenv.hpp"
 #include "seqgroup.hpp"
@@ -629,6 +634,42 @@ __device__ __forceinline__ void seq_fold8(short8v& acc, const short8v x, const d
     acc = __builtin_elementwise_add_sat(acc, seq_scale8(x, factor));
 }
 
+// A COUNTING accumulator (seqclip.hpp; the buses that count overs, SeqBusGC): a lane's samples and one sticky over-flag per sample -- 0 or
+// -1, a vector comparison's lanes, at 16 bits; bit j of a word at widths 1, 3, 4.  The schedules below are generic in the accumulator's
+// type, so either kind passes through the same schedule text.
+typedef unsigned short ushort8v __attribute__((ext_vector_type(8)));
+struct SeqAccC8 { short8v v; short8v over; };
+// seq_v: a lane's samples, of either kind of accumulator
+__device__ __forceinline__ short8v& seq_v(short8v& a) { return a; }
+__device__ __forceinline__ const short8v& seq_v(const short8v& a) { return a; }
+__device__ __forceinline__ short8v& seq_v(SeqAccC8& a) { return a.v; }
+__device__ __forceinline__ const short8v& seq_v(const SeqAccC8& a) { return a.v; }
+
+// the saturating add of a lane's samples into a bus; counting: a packed add clamped exactly where the saturating and the WRAPPING packed
+// sums differ (the wrapping one formed unsigned: tests/cpu_seqclip.cpp holds shcl::add_clamps16 to the exact sum) -- into's own step, so
+// x's flags stay with x
+__device__ __forceinline__ void seq_add8(short8v& into, const short8v& x) { into = __builtin_elementwise_add_sat(into, x); }
+__device__ __forceinline__ void seq_add8(SeqAccC8& into, const short8v x) {
+    const short8v sat = __builtin_elementwise_add_sat(into.v, x);
+    into.over |= (ushort8v)sat != (ushort8v)into.v + (ushort8v)x;
+    into.v = sat;
+}
+__device__ __forceinline__ void seq_add8(SeqAccC8& into, const SeqAccC8& x) { seq_add8(into, x.v); }
+
+// mul and add, counting: the event's own mul is not counted (the sample as placed), the add is the track's
+__device__ __forceinline__ void seq_fold8(SeqAccC8& acc, const short8v x, const double factor) { seq_add8(acc, seq_scale8(x, factor)); }
+
+// audioop.mul of a bus's samples by its gain, counting: floor(p) against the range in front of fbound, then seq_scale8's bytes
+__device__ __forceinline__ SeqAccC8 seq_scale8(SeqAccC8 a, const double factor) {
+    if (factor != 1.0) {                                      // (uniform)
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (shcl::mul_clamps<2>((double)a.v[j] * factor)) a.over[j] = (short)-1;
+    }
+    a.v = seq_scale8(a.v, factor);
+    return a;
+}
+
 // A lane's eight track samples: one aligned 16-byte load of the base, one aligned 16-byte store.  whole: the track starts on a 16-byte
 // boundary (a view that does not: sample by sample) and all eight samples exist.
 __device__ __forceinline__ short8v seq_track_load8(const short* track, uint32_t s0, uint32_t track_samples, bool whole) {
@@ -675,15 +716,59 @@ __device__ __forceinline__ long long seq_mul_add_w(const long long acc, long lon
     return t > HI ? HI : (t < LO ? LO : t);
 }
 
+// the same, and whether each of its two steps clamped (seqclip.hpp): the scaling is a step of x's row -- a track's or a group's pan --,
+// the add one of the destination's
+template <int WIDTH>
+__device__ __forceinline__ long long seq_mul_add_w(const long long acc, long long& x, const double factor, bool& scaled, bool& added) {
+    scaled = factor != 1.0 && shcl::mul_clamps<WIDTH>((double)x * factor);
+    const long long sum = seq_mul_add_w<WIDTH>(acc, x, factor);      // (x: scaled now)
+    added = shcl::add_clamps<WIDTH>(acc, x);
+    return sum;
+}
+
+// the counting accumulator of these widths: four sums and four sticky flags, bit j sample j's
+struct SeqAccCW { llong4v v; uint32_t over; };
+__device__ __forceinline__ llong4v& seq_v(llong4v& a) { return a; }
+__device__ __forceinline__ const llong4v& seq_v(const llong4v& a) { return a; }
+__device__ __forceinline__ llong4v& seq_v(SeqAccCW& a) { return a.v; }
+__device__ __forceinline__ const llong4v& seq_v(const SeqAccCW& a) { return a.v; }
+// a counting accumulator's flags as shcl::lane reads them
+__device__ __forceinline__ const short8v& seq_flags(const SeqAccC8& a) { return a.over; }
+__device__ __forceinline__ shcl::Bits seq_flags(const SeqAccCW& a) { return shcl::Bits{a.over}; }
+
+// sample j of `from` (x: its value, left scaled) by the factor and into sample j of `into`: seq_mul_add_w; counting: the scaling's flag
+// to `from`, the add's to `into`.  An EVENT's sample has no row: seq_add_w drops its scaling's flag (the sample as placed).
+template <int WIDTH>
+__device__ __forceinline__ void seq_into_w(llong4v& into, const int j, llong4v&, long long& x, const double factor) {
+    into[j] = seq_mul_add_w<WIDTH>(into[j], x, factor);
+}
+template <int WIDTH>
+__device__ __forceinline__ void seq_into_w(SeqAccCW& into, const int j, SeqAccCW& from, long long& x, const double factor) {
+    bool scaled, added;
+    into.v[j] = seq_mul_add_w<WIDTH>(into.v[j], x, factor, scaled, added);
+    from.over |= (uint32_t)scaled << j;
+    into.over |= (uint32_t)added << j;
+}
+template <int WIDTH>
+__device__ __forceinline__ void seq_add_w(llong4v& acc, const int j, long long& x, const double factor) {
+    acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, factor);
+}
+template <int WIDTH>
+__device__ __forceinline__ void seq_add_w(SeqAccCW& acc, const int j, long long& x, const double factor) {
+    bool scaled, added;
+    acc.v[j] = seq_mul_add_w<WIDTH>(acc.v[j], x, factor, scaled, added);
+    acc.over |= (uint32_t)added << j;
+}
+
 // mul and add, where the event is; get(j, rel): what the event gives the lane's sample j, sample rel of the event
-template <int WIDTH, typename Get>
-__device__ __forceinline__ void seq_fold_w(llong4v& acc, const double factor, uint32_t s0, uint32_t dst, uint32_t n, Get get) {
+template <int WIDTH, typename Acc, typename Get>
+__device__ __forceinline__ void seq_fold_w(Acc& acc, const double factor, uint32_t s0, uint32_t dst, uint32_t n, Get get) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const long long rel = (long long)s0 + j - (long long)dst;
         if (rel >= 0 && rel < (long long)n) {
             long long x = get(j, rel);
-            acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, factor);
+            seq_add_w<WIDTH>(acc, j, x, factor);
         }
     }
 }
@@ -693,9 +778,9 @@ __device__ __forceinline__ void seq_fold_w(llong4v& acc, const double factor, ui
 // sub-mix (seq_runs) -----------------------------------------------------------------------------------------------------------------
 // PLAIN at 16 bits.  INFLIGHT events' records (scalar loads, one batch ahead) and source vectors are in flight before their muls and
 // adds, then a tail event by event -- a schedule of its own, measured (profiles/sequence_ab.txt).  [e, e1) may be empty.
-template <int SCHEME, int INFLIGHT>
+template <int SCHEME, int INFLIGHT, typename Acc>
 __device__ __forceinline__ void seq_walk_plain16(const SeqEv* __restrict__ ev, const she::Seg* __restrict__ segs, const uint32_t* __restrict__ idx,
-                                                 uint32_t& e, const uint32_t e1, uint32_t t0, uint32_t s0, short8v& acc) {
+                                                 uint32_t& e, const uint32_t e1, uint32_t t0, uint32_t s0, Acc& acc) {
     if (e1 - e >= INFLIGHT) {
         SeqEv c[INFLIGHT], nx[INFLIGHT];
 #pragma unroll
@@ -725,9 +810,9 @@ __device__ __forceinline__ void seq_walk_plain16(const SeqEv* __restrict__ ev, c
 
 // The other levels at 16 bits.  One record ahead instead of INFLIGHT: a resampled event is sixteen dependent-address loads and some forty
 // instructions per sample, which is what there is to hide behind.  e < e1: behind the last event idx holds nothing.
-template <int LEVEL, int SCHEME>
+template <int LEVEL, int SCHEME, typename Acc>
 __device__ __forceinline__ void seq_walk_16(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
-                                            const uint32_t* __restrict__ idx, uint32_t& e, const uint32_t e1, uint32_t t0, uint32_t s0, short8v& acc) {
+                                            const uint32_t* __restrict__ idx, uint32_t& e, const uint32_t e1, uint32_t t0, uint32_t s0, Acc& acc) {
     typedef typename SeqRec<LEVEL>::type Rec;
     if constexpr (LEVEL >= LOOP) {
         // LOOP is where the scalar registers run out: with a whole record held ahead the allocator spilled (read in the ISA).  The INDEX
@@ -749,9 +834,9 @@ __device__ __forceinline__ void seq_walk_16(const typename SeqRec<LEVEL>::type* 
 }
 
 // Every level at widths 1, 3 and 4: the reference's loop as it stands, event by event.  [e, e1) may be empty.
-template <int LEVEL, int WIDTH>
+template <int LEVEL, int WIDTH, typename Acc>
 __device__ __forceinline__ void seq_walk_w(const typename SeqRec<LEVEL>::type* __restrict__ ev, const she::Seg* __restrict__ segs,
-                                           const uint32_t* __restrict__ idx, uint32_t& e, const uint32_t e1, uint32_t t0, uint32_t s0, llong4v& acc) {
+                                           const uint32_t* __restrict__ idx, uint32_t& e, const uint32_t e1, uint32_t t0, uint32_t s0, Acc& acc) {
     for (; e < e1; ++e) {
         const typename SeqRec<LEVEL>::type c = ev[idx[e]];
         if constexpr (LEVEL == PLAIN) {                        // fetched inside the fold, sample by sample, by chain_get on the generic pointer
@@ -971,9 +1056,34 @@ __device__ __forceinline__ short8v seq_pan8(short8v x, const double left, const 
     return x;
 }
 
+// counting: floor(p) against the range in front of fbound, then seq_pan8's bytes
+__device__ __forceinline__ SeqAccC8 seq_pan8(SeqAccC8 a, const double left, const double right) {
+    if (left != 1.0) {                                        // (uniform)
+#pragma unroll
+        for (int j = 0; j < 8; j += 2)
+            if (shcl::mul_clamps<2>((double)a.v[j] * left)) a.over[j] = (short)-1;
+    }
+    if (right != 1.0) {
+#pragma unroll
+        for (int j = 1; j < 8; j += 2)
+            if (shcl::mul_clamps<2>((double)a.v[j] * right)) a.over[j] = (short)-1;
+    }
+    a.v = seq_pan8(a.v, left, right);
+    return a;
+}
+
 template <int WIDTH>
 __device__ __forceinline__ long long seq_scale_w(const long long x, const double factor) {
     return factor != 1.0 ? (long long)fbound((double)x * factor, (double)SEQ_LO<WIDTH>, (double)SEQ_HI<WIDTH>) : x;
+}
+
+// sample j of a bus by its gain: seq_scale_w's value; counting: whether it clamped, into the bus's flag
+template <int WIDTH>
+__device__ __forceinline__ long long seq_gain_w(const llong4v& a, const int j, const double gain) { return seq_scale_w<WIDTH>(a[j], gain); }
+template <int WIDTH>
+__device__ __forceinline__ long long seq_gain_w(SeqAccCW& a, const int j, const double gain) {
+    if (gain != 1.0 && shcl::mul_clamps<WIDTH>((double)a.v[j] * gain)) a.over |= 1u << j;
+    return seq_scale_w<WIDTH>(a.v[j], gain);
 }
 
 template <int WIDTH>
@@ -984,6 +1094,13 @@ __device__ __forceinline__ void seq_master(typename SeqAcc<WIDTH>::type& acc, co
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] = seq_scale_w<WIDTH>(acc[j], gain);
     }
+}
+template <int WIDTH>
+__device__ __forceinline__ void seq_master(SeqAccC8& acc, const double gain) { acc = seq_scale8(acc, gain); }
+template <int WIDTH>
+__device__ __forceinline__ void seq_master(SeqAccCW& acc, const double gain) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc.v[j] = seq_gain_w<WIDTH>(acc, j, gain);
 }
 
 // "Shape this accumulator through lane `lane` of the automation's table", stated once for the buses that ride (SeqBusR, SeqBusRM) -- a
@@ -1043,9 +1160,11 @@ __device__ __forceinline__ bool seq_pan_ride(typename SeqAcc<WIDTH>::type& x, co
 // An automation bus: the track's fader moves between the gain and the pan, at the lane's SONG positions (tile k starts at k * TILE).
 // A group bus: a track of a group goes into grp, the open group's bus, and a group is closed -- its gain, its pan, hook(grp, its row),
 // into acc -- in front of the first run that is not of it and behind the last run; opening and closing are uniform.
-template <int WIDTH, typename Bus, typename Walk, typename Hook>
-__device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e, typename SeqAcc<WIDTH>::type& acc, Walk walk, Hook hook) {
-    [[maybe_unused]] typename SeqAcc<WIDTH>::type grp = {};  // (a group bus: the open group's samples)
+// Acc: the accumulator's type, the same for sub, grp and acc -- a lane's samples, or (a bus that counts overs) a counting accumulator,
+// whose flags each bus carries through its own steps and the hook receives next to the samples.
+template <int WIDTH, typename Bus, typename Acc, typename Walk, typename Hook>
+__device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e, Acc& acc, Walk walk, Hook hook) {
+    [[maybe_unused]] Acc grp = {};                            // (a group bus: the open group's samples)
     [[maybe_unused]] uint32_t open = shg::NONE, of = shg::NONE;
     [[maybe_unused]] auto close = [&] {                       // the open group into the master
         if constexpr (SEQ_GROUPS<Bus>) {
@@ -1088,13 +1207,13 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
             } else if constexpr (WIDTH == 2) {
                 grp = seq_pan8(seq_scale8(grp, gg), gl, gr);
                 hook(grp, bus.groups.row0 + open);
-                acc = __builtin_elementwise_add_sat(acc, grp);
+                seq_add8(acc, grp);
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    long long x = seq_scale_w<WIDTH>(grp[j], gg);
-                    acc[j] = seq_mul_add_w<WIDTH>(acc[j], x, j & 1 ? gr : gl);
-                    grp[j] = x;
+                    long long x = seq_gain_w<WIDTH>(grp, j, gg);
+                    seq_into_w<WIDTH>(acc, j, grp, x, j & 1 ? gr : gl);
+                    seq_v(grp)[j] = x;
                 }
                 hook(grp, bus.groups.row0 + open);
             }
@@ -1124,7 +1243,7 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
         }
         if constexpr (SEQ_GROUPS<Bus>) {
             if (of != shg::NONE && open == shg::NONE) {       // the group opens: from silence
-                grp = typename SeqAcc<WIDTH>::type{};
+                grp = Acc{};
                 open = of;
             }
         }
@@ -1142,7 +1261,7 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
             }
         }
         if constexpr (WIDTH == 2) {
-            short8v sub = {0, 0, 0, 0, 0, 0, 0, 0};
+            Acc sub = {};
             walk(e, run.end, sub);
             sub = seq_scale8(sub, g);                         // post-fader: what the master takes of the track
             if constexpr (SEQ_RIDES<Bus>) {
@@ -1151,10 +1270,10 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
                 if (ai < an) {                                // (uniform: behind the track's last segment nothing is shaped)
                     int v[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = (int)sub[j];
+                    for (int j = 0; j < 8; ++j) v[j] = (int)seq_v(sub)[j];
                     sha::shape_from<8>(asegs, an, ai, t0, t0 + SEQ_TILE<2>, (long long)t0 + threadIdx.x * SEQ_LANE<2>, v, (double)SEQ_LO<2>, (double)SEQ_HI<2>);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) sub[j] = (short)v[j];
+                    for (int j = 0; j < 8; ++j) seq_v(sub)[j] = (short)v[j];
                 }
             }
             if constexpr (SEQ_PANS<Bus>) {                    // the track's pan ride: where its static pan stands
@@ -1163,10 +1282,10 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
             hook(sub, run.track);
             bool grouped = false;
             if constexpr (SEQ_GROUPS<Bus>) grouped = of != shg::NONE;
-            if (grouped) grp = __builtin_elementwise_add_sat(grp, sub);
-            else acc = __builtin_elementwise_add_sat(acc, sub);
+            if (grouped) seq_add8(grp, sub);
+            else seq_add8(acc, sub);
         } else {
-            llong4v sub = {0, 0, 0, 0};
+            Acc sub = {};
             walk(e, run.end, sub);
             if constexpr (SEQ_RIDES<Bus>) {
 #pragma unroll
@@ -1178,20 +1297,20 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
             } else if constexpr (SEQ_AUTO<Bus>) {             // the gain over all four first, then the segments; the pan below
                 int v[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = (int)seq_scale_w<WIDTH>(sub[j], g);
+                for (int j = 0; j < 4; ++j) v[j] = (int)seq_gain_w<WIDTH>(sub, j, g);
                 sha::shape_from<4>(asegs, an, ai, t0, t0 + SEQ_TILE<WIDTH>, (long long)t0 + threadIdx.x * SEQ_LANE<WIDTH>, v, (double)SEQ_LO<WIDTH>,
                                    (double)SEQ_HI<WIDTH>);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) sub[j] = v[j];
+                for (int j = 0; j < 4; ++j) seq_v(sub)[j] = v[j];
             }
             if constexpr (SEQ_GROUPS<Bus>) {                  // (the desk's steps into the bus that takes the track: whole values, uniform)
-                llong4v into = of != shg::NONE ? grp : acc;
+                Acc into = of != shg::NONE ? grp : acc;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    long long x = sub[j];
-                    if constexpr (!SEQ_AUTO<Bus>) x = seq_scale_w<WIDTH>(x, g);
-                    into[j] = seq_mul_add_w<WIDTH>(into[j], x, j & 1 ? right : left);
-                    sub[j] = x;
+                    long long x = seq_v(sub)[j];
+                    if constexpr (!SEQ_AUTO<Bus>) x = seq_gain_w<WIDTH>(sub, j, g);
+                    seq_into_w<WIDTH>(into, j, sub, x, j & 1 ? right : left);
+                    seq_v(sub)[j] = x;
                 }
                 if (of != shg::NONE) grp = into;
                 else acc = into;
@@ -1263,6 +1382,22 @@ template <> struct SeqMetered<SeqBusGH3> : std::true_type {};
 template <typename... Bus> constexpr bool SEQ_HISTORY = (std::is_base_of<SeqHistory, Bus>::value || ...);
 static_assert(sizeof(SeqBusGH) == sizeof(SeqBusGM) && sizeof(SeqBusGH3) == sizeof(SeqBusGM3), "the history: no kernel argument of its own");
 
+// The buses that COUNT OVERS (sh_seq_render_clips; seqclip.hpp): the history buses again whose lanes keep counting accumulators -- sub,
+// grp and acc each with a sticky flag per sample, set where one of the bus's own steps clamped -- and whose rows carry, behind the levels,
+// the count of flagged samples per channel: a table of 48-byte rows in LDS and in the table of blocks.  A tag and no new kernel argument;
+// one bus type at widths 1, 2 and 4 and one at width 3.
+struct SeqClips {};
+struct SeqBusGC : SeqBusGH, SeqClips {};
+struct SeqBusGC3 : SeqBusGH3, SeqClips {};
+template <> struct SeqMetered<SeqBusGC> : std::true_type {};
+template <> struct SeqMetered<SeqBusGC3> : std::true_type {};
+template <typename... Bus> constexpr bool SEQ_CLIPS = (std::is_base_of<SeqClips, Bus>::value || ...);
+static_assert(sizeof(SeqBusGC) == sizeof(SeqBusGM) && sizeof(SeqBusGC3) == sizeof(SeqBusGM3), "the overs: no kernel argument of their own");
+// what a window kernel's lane accumulates in: the samples, or with a bus that counts the counting accumulator
+template <int WIDTH, typename... Bus> struct SeqWinAcc {
+    typedef typename std::conditional<SEQ_CLIPS<Bus...>, typename std::conditional<WIDTH == 2, SeqAccC8, SeqAccCW>::type, typename SeqAcc<WIDTH>::type>::type type;
+};
+
 // the workgroup's row table, zeroed: every lane of the workgroup calls it (a barrier).  ROWS: 33, or 41 with the rows of the groups
 template <uint32_t ROWS = shq::MAX_TRACKS + 1>
 __device__ __forceinline__ shmt::Row* seq_meter_begin() {
@@ -1303,6 +1438,31 @@ __device__ __forceinline__ void seq_meter_wave(shmt::Row r, const bool stereo, s
     }
 }
 
+// the same of a bus that counts: 41 rows of 48 bytes
+__device__ __forceinline__ shcl::Row* seq_clip_begin() {
+    __shared__ shcl::Row table[shq::MAX_TRACKS + 1 + shg::MAX_GROUPS];
+    uint32_t* w = reinterpret_cast<uint32_t*>(table);
+    for (uint32_t i = threadIdx.x; i < sizeof(table) / 4; i += shq::TILE_THREADS) w[i] = 0u;
+    __syncthreads();
+    return table;
+}
+
+// the lanes' partial counts of one WHOLE wave into row `slot` of the workgroup's table, beside seq_meter_wave: a wave reduction by
+// __shfl_xor, then the wave's first lane by an LDS integer add (none where the count is 0)
+__device__ __forceinline__ void seq_clip_wave(shcl::Count c, const bool stereo, shcl::Row* slot) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        shcl::Count o{{0u, 0u}};
+        o.c[0] = __shfl_xor(c.c[0], m, 64);
+        if (stereo) o.c[1] = __shfl_xor(c.c[1], m, 64);      // (uniform)
+        shcl::fold(c, o);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        if (c.c[0]) atomicAdd(&slot->clipped[0], c.c[0]);
+        if (stereo && c.c[1]) atomicAdd(&slot->clipped[1], c.c[1]);
+    }
+}
+
 // the workgroup's table into the handle's: every lane of the workgroup calls it (a barrier), lane 2 row + channel carries one value each
 // (groups: the rows of a group bus behind the master's; 2 * 41 lanes at the most, of TILE_THREADS)
 template <bool WIDE>
@@ -1320,26 +1480,30 @@ __device__ __forceinline__ void seq_meter_end(const shmt::Row* table, const SeqB
 }
 
 // the workgroup's table as block `tile - lo / TILE` of the history's: every lane of the workgroup calls it (a barrier), lane 2 row + channel
-// STORES its three values of (row, channel), zeros as well -- the block has this one writer, so nothing merges and nothing was zeroed
-template <int WIDTH>
-__device__ __forceinline__ void seq_hist_end(const shmt::Row* table, const SeqBusM& bus, const uint32_t groups, const uint32_t tile, const uint32_t lo) {
+// STORES its three values of (row, channel), zeros as well -- the block has this one writer, so nothing merges and nothing was zeroed.
+// R: the row, shmt::Row or (a bus that counts) shcl::Row, whose count is a fourth value; bus.meters is a table of R.
+template <int WIDTH, typename R>
+__device__ __forceinline__ void seq_hist_end(const R* table, const SeqBusM& bus, const uint32_t groups, const uint32_t tile, const uint32_t lo) {
     static_assert(2 * (shq::MAX_TRACKS + 1 + shg::MAX_GROUPS) <= shq::TILE_THREADS, "a lane per row and channel");
     __syncthreads();
     const uint32_t row = threadIdx.x >> 1, c = threadIdx.x & 1u, nrows = bus.ntracks + 1 + groups;
     if (row >= nrows) return;
-    shmt::Row* g = bus.meters + shhs::row_at(shhs::block_of(tile, lo, SEQ_TILE<WIDTH>), nrows, row);
+    R* g = reinterpret_cast<R*>(bus.meters) + shhs::row_at(shhs::block_of(tile, lo, SEQ_TILE<WIDTH>), nrows, row);
     g->peak[c] = table[row].peak[c];
     g->sq_hi[c] = table[row].sq_hi[c];
     g->sq_lo[c] = table[row].sq_lo[c];
+    if constexpr (std::is_same<R, shcl::Row>::value) g->clipped[c] = table[row].clipped[c];
 }
 
 // What a window kernel does where it has a bus, once for the three templates: the runs of tile k into acc, (a desk bus) the master's gain,
 // then store().  A plain bus: a lane that seq_window_lane kept; s0, lo and hi, which only a metering bus needs, are ignored.
 // A metering bus: EVERY lane of a workgroup that seq_window_tile kept, the rows of the tracks from seq_runs' hook and the master's row
 // in front of the store, the table's barriers around everything.
-template <int WIDTH, typename Bus, typename Walk, typename Store>
-__device__ __forceinline__ void seq_window_bus(const Bus& bus, uint32_t k, uint32_t e, uint32_t s0, uint32_t lo, uint32_t hi,
-                                               typename SeqAcc<WIDTH>::type& acc, Walk walk, Store store) {
+// A bus that counts overs: acc is a counting accumulator, the table's rows are shcl::Row, and every row takes its bus's flags beside its
+// samples -- the master's in front of the store.
+template <int WIDTH, typename Bus, typename Acc, typename Walk, typename Store>
+__device__ __forceinline__ void seq_window_bus(const Bus& bus, uint32_t k, uint32_t e, uint32_t s0, uint32_t lo, uint32_t hi, Acc& acc, Walk walk,
+                                               Store store) {
     if constexpr (!SeqMetered<Bus>::value) {
         seq_runs<WIDTH>(bus, k, e, acc, walk, [](const typename SeqAcc<WIDTH>::type&, uint32_t) {});
         if constexpr (SEQ_DESK<Bus>) seq_master<WIDTH>(acc, bus.master);
@@ -1348,17 +1512,21 @@ __device__ __forceinline__ void seq_window_bus(const Bus& bus, uint32_t k, uint3
     } else {
         constexpr bool WIDE = WIDTH >= 3;
         constexpr int N = SEQ_LANE<WIDTH>;
-        shmt::Row* table;
-        if constexpr (SEQ_GROUPS<Bus>) table = seq_meter_begin<shq::MAX_TRACKS + 1 + shg::MAX_GROUPS>();
+        constexpr bool CLIPS = SEQ_CLIPS<Bus>;
+        typename std::conditional<CLIPS, shcl::Row, shmt::Row>::type* table;
+        if constexpr (CLIPS) table = seq_clip_begin();
+        else if constexpr (SEQ_GROUPS<Bus>) table = seq_meter_begin<shq::MAX_TRACKS + 1 + shg::MAX_GROUPS>();
         else table = seq_meter_begin();
         const bool stereo = bus.nch == 2;
+        auto meter = [&](const Acc& x, uint32_t row) {         // a bus's samples (and flags) as they stand into its row
+            seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(seq_v(x), s0, lo, hi, bus.nch), stereo, table + row);
+            if constexpr (CLIPS) seq_clip_wave(shcl::lane<N>(seq_flags(x), s0, lo, hi, bus.nch), stereo, table + row);
+        };
         if (__builtin_amdgcn_ballot_w64(s0 < hi && s0 + N > lo)) {                    // (uniform: a wave with a lane in the window)
-            seq_runs<WIDTH>(bus, k, e, acc, walk, [&](const typename SeqAcc<WIDTH>::type& sub, uint32_t row) {
-                seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(sub, s0, lo, hi, bus.nch), stereo, table + row);
-            });
+            seq_runs<WIDTH>(bus, k, e, acc, walk, meter);
             if constexpr (SEQ_DESK<Bus>) seq_master<WIDTH>(acc, bus.master);
             if constexpr (SEQ_RIDES<Bus>) seq_ride<WIDTH>(acc, bus, sha::master_lane(bus.groups.row0), k);      // (in front of the master's row: over the stored bytes)
-            seq_meter_wave<WIDE>(shmt::lane<WIDE, N>(acc, s0, lo, hi, bus.nch), stereo, table + bus.ntracks);
+            meter(acc, bus.ntracks);
             store();
         }
         if constexpr (SEQ_HISTORY<Bus>) seq_hist_end<WIDTH>(table, bus, bus.groups.n, k, lo);      // (k: the song tile, in song order whatever workgroup folds it)
@@ -1381,9 +1549,9 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_plain16(const SeqEv* 
         if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
     }
     const bool whole = aligned && s0 >= lo && s0 + 8 <= hi;
-    short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto walk = [&](uint32_t& e, uint32_t e1, short8v& into) { seq_walk_plain16<SCHEME, INFLIGHT>(ev, segs, idx, e, e1, t0, s0, into); };
-    auto store = [&] { seq_window_store8(out, s0, lo, hi, whole, acc); };
+    typename SeqWinAcc<2, Bus...>::type acc = {};
+    auto walk = [&](uint32_t& e, uint32_t e1, auto& into) { seq_walk_plain16<SCHEME, INFLIGHT>(ev, segs, idx, e, e1, t0, s0, into); };
+    auto store = [&] { seq_window_store8(out, s0, lo, hi, whole, seq_v(acc)); };
     uint32_t e = first[k];
     if constexpr (BUS) {
         seq_window_bus<2>(bus..., k, e, s0, lo, hi, acc, walk, store);
@@ -1407,9 +1575,9 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_16(const typename Seq
         if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
     }
     const bool whole = aligned && s0 >= lo && s0 + 8 <= hi;
-    short8v acc = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto walk = [&](uint32_t& e, uint32_t e1, short8v& into) { seq_walk_16<LEVEL, SCHEME>(ev, segs, idx, e, e1, t0, s0, into); };
-    auto store = [&] { seq_window_store8(out, s0, lo, hi, whole, acc); };
+    typename SeqWinAcc<2, Bus...>::type acc = {};
+    auto walk = [&](uint32_t& e, uint32_t e1, auto& into) { seq_walk_16<LEVEL, SCHEME>(ev, segs, idx, e, e1, t0, s0, into); };
+    auto store = [&] { seq_window_store8(out, s0, lo, hi, whole, seq_v(acc)); };
     uint32_t e = first[k];
     if constexpr (BUS) {
         seq_window_bus<2>(bus..., k, e, s0, lo, hi, acc, walk, store);
@@ -1434,9 +1602,9 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_w(const typename SeqR
     } else {
         if (!seq_window_lane<WIDTH>(order, lo, hi, k, t0, s0)) return;
     }
-    llong4v acc = {0, 0, 0, 0};
-    auto walk = [&](uint32_t& e, uint32_t e1, llong4v& into) { seq_walk_w<LEVEL, WIDTH>(ev, segs, idx, e, e1, t0, s0, into); };
-    auto store = [&] { seq_window_store_w<WIDTH>(out, s0, lo, hi, acc); };
+    typename SeqWinAcc<WIDTH, Bus...>::type acc = {};
+    auto walk = [&](uint32_t& e, uint32_t e1, auto& into) { seq_walk_w<LEVEL, WIDTH>(ev, segs, idx, e, e1, t0, s0, into); };
+    auto store = [&] { seq_window_store_w<WIDTH>(out, s0, lo, hi, seq_v(acc)); };
     uint32_t e = first[k];
     if constexpr (BUS) {
         seq_window_bus<WIDTH>(bus..., k, e, s0, lo, hi, acc, walk, store);
@@ -2032,13 +2200,17 @@ template <typename T> struct SeqBaseOf { typedef T type; };
 // sh_seq_render_auto (au: the automation's table, with a desk) and sh_seq_render_groups (groups: the group table, with a desk, with or
 // without au; meters: ntracks + 1 + ngroups rows; rides: au has a segment on a bus lane, and groups may then be the empty table; pans: au
 // has a segment on a pan lane, likewise) and sh_seq_render_history (history: meters is a table of BLOCKS, nblocks * nrows host rows; the
-// device table is the library's scratch, sized for the call, and needs no zeroing) behind their names
+// device table is the library's scratch, sized for the call, and needs no zeroing) and sh_seq_render_clips (clips: a history whose rows
+// are sh_seq_meter_clips, 48 bytes) behind their names
 int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains,
-               sh_seq_meter* meters = nullptr, const SeqDesk* desk = nullptr, const SeqAuto* au = nullptr, const shg::Table* groups = nullptr,
-               bool rides = false, bool pans = false, bool history = false) {
+               void* meters = nullptr, const SeqDesk* desk = nullptr, const SeqAuto* au = nullptr, const shg::Table* groups = nullptr,
+               bool rides = false, bool pans = false, bool history = false, bool clips = false) {
     static_assert(sizeof(sh_seq_meter) == sizeof(shmt::Row) && offsetof(sh_seq_meter, sq_hi) == offsetof(shmt::Row, sq_hi) &&
                   offsetof(sh_seq_meter, sq_lo) == offsetof(shmt::Row, sq_lo), "sh_seq_meter is shmt::Row");
-    const size_t b_rows = meters ? ((size_t)seq->ntracks + 1 + (groups ? groups->n : 0)) * sizeof(shmt::Row) : 0;
+    static_assert(sizeof(sh_seq_meter_clips) == sizeof(shcl::Row) && offsetof(sh_seq_meter_clips, sq_hi) == offsetof(sh_seq_meter, sq_hi) &&
+                  offsetof(sh_seq_meter_clips, sq_lo) == offsetof(sh_seq_meter, sq_lo) && offsetof(sh_seq_meter_clips, clipped) == sizeof(shmt::Row),
+                  "sh_seq_meter_clips is shcl::Row: sh_seq_meter, then the counts");
+    const size_t b_rows = meters ? ((size_t)seq->ntracks + 1 + (groups ? groups->n : 0)) * (clips ? sizeof(shcl::Row) : sizeof(shmt::Row)) : 0;
     const size_t w = (size_t)seq->width;
     if (first_sample > seq->track_samples || nsamples > seq->track_samples - first_sample)
         return sh::set_error(SH_ERR_INVALID, "%s: range outside the song", fn);
@@ -2091,7 +2263,8 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
                 moved.groups = *groups;
                 seq_window_launch<LEVEL, G>(seq, grid, st, lo, hi, biased, moved);
             };
-            if (history) seq->width == 3 ? grouped(SeqBusGH3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusGH{}, SeqBaseOf<SeqBusM>());
+            if (clips) seq->width == 3 ? grouped(SeqBusGC3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusGC{}, SeqBaseOf<SeqBusM>());
+            else if (history) seq->width == 3 ? grouped(SeqBusGH3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusGH{}, SeqBaseOf<SeqBusM>());
             else if (seq->width == 3) meters ? grouped(SeqBusGM3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG3{}, SeqBaseOf<SeqBus>());
             else if (pans) meters ? grouped(SeqBusPM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusP{}, SeqBaseOf<SeqBus>());       // (au: a table with pan lanes)
             else if (rides) meters ? grouped(SeqBusRM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusR{}, SeqBaseOf<SeqBus>());      // (au: a table with bus lanes)
@@ -2368,10 +2541,12 @@ int sh_seq_render_auto(const sh_seq* seq, size_t first_sample, size_t nsamples, 
 }
 
 // sh_seq_render_groups (history false: meters is NULL or nmeters == ntracks + 1 + ngroups rows, at least one group) and
-// sh_seq_render_history (history true: meters is nblocks blocks of nmeters rows each, groups and automation may be none) behind their names
+// sh_seq_render_history (history true: meters is nblocks blocks of nmeters rows each, groups and automation may be none) and
+// sh_seq_render_clips (history and clips true: the same, the rows sh_seq_meter_clips) behind their names
 static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample,
-                              const double* gains, uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters,
-                              uint32_t nmeters, uint32_t nblocks, const sh_seq_auto* automation, const sh_seq_group* groups, uint32_t ngroups) {
+                              const double* gains, uint32_t ngains, const double* pans, uint32_t npans, double master_gain, void* meters,
+                              uint32_t nmeters, uint32_t nblocks, const sh_seq_auto* automation, const sh_seq_group* groups, uint32_t ngroups,
+                              bool clips = false) {
     static_assert(sizeof(sh_seq_group) == sizeof(shg::Group) && offsetof(sh_seq_group, gain) == offsetof(shg::Group, gain) &&
                   offsetof(sh_seq_group, right) == offsetof(shg::Group, right) && SH_SEQ_MAX_GROUPS == shg::MAX_GROUPS, "sh_seq_group is shg::Group");
     if (!seq || !out || (!gains && ngains) || (!pans && npans) || (!meters && nmeters && !history)) return seq_null(fn);
@@ -2405,6 +2580,9 @@ static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, s
         return sh::set_error(SH_ERR_INVALID, "%s: group %u: a pan needs a stereo song, this one has %d channels", fn, v.entry, seq->nchannels);
     default: return sh::set_error(SH_ERR_INVALID, "%s: %u groups, %u to %u", fn, ngroups, history ? 0u : 1u, shg::MAX_GROUPS);
     }
+    if (clips && automation && (automation->buses || automation->pans))
+        return sh::set_error(SH_ERR_INVALID, "%s: the automation rides a %s: overs are not counted through rides of buses and pans yet", fn,
+                             automation->pans ? "pan" : "bus");
     if (history && automation && (automation->buses || automation->pans))
         return sh::set_error(SH_ERR_INVALID, "%s: the automation rides a %s: rides of buses and pans have no history yet", fn,
                              automation->pans ? "pan" : "bus");
@@ -2431,7 +2609,7 @@ static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, s
     SeqAuto au{nullptr, nullptr};
     if (automation) au = SeqAuto{(const she::Seg*)automation->block, (const uint32_t*)((const char*)automation->block + automation->at_first)};
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, automation ? &au : nullptr, &table,
-                      automation && (automation->buses || automation->pans), automation && automation->pans, history);
+                      automation && (automation->buses || automation->pans), automation && automation->pans, history, clips);
 }
 
 int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
@@ -2448,6 +2626,14 @@ int sh_seq_render_history(const sh_seq* seq, size_t first_sample, size_t nsample
     SH_REQUIRE_INIT();
     return seq_render_grouped("sh_seq_render_history", true, seq, first_sample, nsamples, out, out_sample, gains, ngains, pans, npans, master_gain, rows,
                               nrows, nblocks, automation, groups, ngroups);
+}
+
+int sh_seq_render_clips(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                        uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter_clips* rows, uint32_t nrows,
+                        uint32_t nblocks, const sh_seq_auto* automation, const sh_seq_group* groups, uint32_t ngroups) {
+    SH_REQUIRE_INIT();
+    return seq_render_grouped("sh_seq_render_clips", true, seq, first_sample, nsamples, out, out_sample, gains, ngains, pans, npans, master_gain, rows,
+                              nrows, nblocks, automation, groups, ngroups, true);
 }
 
 int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns) {

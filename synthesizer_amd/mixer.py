@@ -597,12 +597,16 @@ class Levels:
     per channel, as ``(left, right)`` tuples, ``peak`` (``audioop.max``), ``sum_squares`` (the exact integer sum of x * x, a Python int),
     ``rms`` (``int(sqrt(sum_squares / frames))``, as ``Sample.rms`` forms it; 0 for an empty window) and ``level_db_peak`` /
     ``level_db_rms`` by ``Sample.level_db_peak``'s formula, ``20 log10((v + 1) / 2^(8 w - 1))`` and not below -60.  A mono song gives
-    ``left == right``, as ``Sample`` does.  It has what ``LevelMeter.update`` reads of a ``Sample`` (the two levels and ``duration``)."""
+    ``left == right``, as ``Sample`` does.  It has what ``LevelMeter.update`` reads of a ``Sample`` (the two levels and ``duration``).
+    ``clipped``: None, or (a render with ``clips=True``) the OVERS as a ``(left, right)`` tuple of ints, with the mono rule of ``peak``:
+    the number of samples at which the row's own arithmetic was clamped (``CompiledSequence`` has the definition).  Two ``Levels``
+    compare their counts only where both have them."""
 
-    def __init__(self, peak, sum_squares, frames: int, samplewidth: int, nchannels: int, samplerate: int) -> None:
+    def __init__(self, peak, sum_squares, frames: int, samplewidth: int, nchannels: int, samplerate: int, clipped=None) -> None:
         both = (lambda v: (int(v[0]), int(v[1]))) if nchannels == 2 else (lambda v: (int(v[0]), int(v[0])))
         self.peak = both(peak)
         self.sum_squares = both(sum_squares)
+        self.clipped = None if clipped is None else both(clipped)
         self.frames, self.samplewidth, self.nchannels, self.samplerate = int(frames), int(samplewidth), int(nchannels), int(samplerate)
 
     @property
@@ -630,9 +634,12 @@ class Levels:
 
     def __eq__(self, other) -> bool:
         return isinstance(other, Levels) and (self.peak, self.sum_squares, self.frames, self.samplewidth, self.nchannels) == (
-            other.peak, other.sum_squares, other.frames, other.samplewidth, other.nchannels)
+            other.peak, other.sum_squares, other.frames, other.samplewidth, other.nchannels) and (
+            self.clipped is None or other.clipped is None or self.clipped == other.clipped)
 
     def __repr__(self) -> str:
+        if self.clipped is not None:
+            return "Levels(peak=%r, sum_squares=%r, frames=%d, clipped=%r)" % (self.peak, self.sum_squares, self.frames, self.clipped)
         return "Levels(peak=%r, sum_squares=%r, frames=%d)" % (self.peak, self.sum_squares, self.frames)
 
 
@@ -641,10 +648,10 @@ class SongLevels:
     it: folded on its own, times its gain; a muted track reads zero), and ``master``, over the window's output -- all from the one launch
     that rendered the window.  ``groups``: one ``Levels`` per group bus of a render with ``groups=``, over the bus as the master takes it
     (behind the group's gain and pan); empty without groups.  ``rows``: ``N.Sequence.render(meters=True)``'s -- the tracks, the master,
-    then the ``ngroups`` groups."""
+    then the ``ngroups`` groups; a row is ``(peak, sum_squares)`` or, with overs, ``(peak, sum_squares, clipped)``."""
 
     def __init__(self, rows, frames: int, samplewidth: int, nchannels: int, samplerate: int, ngroups: int = 0) -> None:
-        made = [Levels(peak, sq, frames, samplewidth, nchannels, samplerate) for peak, sq in rows]
+        made = [Levels(row[0], row[1], frames, samplewidth, nchannels, samplerate, row[2] if len(row) > 2 else None) for row in rows]
         at = len(made) - 1 - ngroups
         self.tracks: List[Levels] = made[:at]
         self.master: Levels = made[at]
@@ -673,11 +680,17 @@ class SongHistory:
     song has ``left == right`` there as in ``Levels``.  ``peak`` (uint32) and ``sum_squares`` (Python ints) are the arrays behind them,
     shaped ``(nblocks, nrows, 2)``, a mono song's channel 1 reading 0.  A rendered history keeps the table as it came back (``parts``:
     the two 64-bit sums of every row) and forms Python ints where they are asked for -- a block that is indexed, ``total()``,
-    ``fold(n)``, ``sum_squares`` -- so that the render's call costs no pass over the table in Python."""
+    ``fold(n)``, ``sum_squares`` -- so that the render's call costs no pass over the table in Python.
+    A history rendered with ``clips=True`` carries the OVERS as well: ``clipped()`` is a numpy array ``(nblocks, nrows, 2)`` of counts,
+    rows and the mono rule as ``peaks()`` has them (None without counts); every block's ``Levels.clipped`` holds its row's, and
+    ``total()`` and ``fold(n)`` add the counts."""
 
     def __init__(self, peak, sum_squares, first_block: int, block_frames: int, start_frame: int, frames: int, samplewidth: int, nchannels: int,
-                 samplerate: int, ngroups: int = 0, parts=None) -> None:
+                 samplerate: int, ngroups: int = 0, parts=None, clipped=None) -> None:
         self.peak = np.asarray(peak, dtype=np.uint32)
+        self._clipped = None if clipped is None else np.asarray(clipped, dtype=np.uint64)       # (a mono song's channel 1 reads 0, as peak's)
+        if self._clipped is not None and self._clipped.shape != self.peak.shape:
+            raise ValueError("SongHistory: clipped is an (nblocks, nrows, 2) array as peak is")
         self._parts = None if parts is None else (np.asarray(parts[0], dtype=np.uint64), np.asarray(parts[1], dtype=np.uint64))
         self._sq = None if sum_squares is None else np.asarray(sum_squares, dtype=object)
         held = [a.shape for a in (self._sq,) + (self._parts or ()) if a is not None]
@@ -700,15 +713,20 @@ class SongHistory:
 
     @classmethod
     def from_blocks(cls, blocks, nrows: int, tile_samples: int, start_frame: int, frames: int, samplewidth: int, nchannels: int, samplerate: int,
-                    ngroups: int = 0) -> "SongHistory":
-        """``blocks``: ``N.Sequence.render(meters="history")``'s array ``(nblocks, nrows)`` of sh_seq_meter rows, or None for an empty window"""
+                    ngroups: int = 0, clips: bool = False) -> "SongHistory":
+        """``blocks``: ``N.Sequence.render(meters="history")``'s array ``(nblocks, nrows)`` of sh_seq_meter rows (with ``clips=True`` of
+        sh_seq_meter_clips rows: the field ``clipped`` says so), or None for an empty window, whose history has counts where ``clips``"""
+        counted = clips if blocks is None else "clipped" in (blocks.dtype.names or ())
         if blocks is None or not len(blocks):
             peak = np.zeros((0, nrows, 2), dtype=np.uint32)
             parts = (np.zeros((0, nrows, 2), dtype=np.uint64),) * 2
+            clipped = np.zeros((0, nrows, 2), dtype=np.uint64) if counted else None
         else:
             peak, parts = blocks["peak"], (blocks["sq_hi"], blocks["sq_lo"])
+            clipped = blocks["clipped"] if counted else None
         block_frames = tile_samples // nchannels
-        return cls(peak, None, start_frame // block_frames, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups, parts=parts)
+        return cls(peak, None, start_frame // block_frames, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups, parts=parts,
+                   clipped=clipped)
 
     @property
     def sum_squares(self) -> np.ndarray:
@@ -719,7 +737,9 @@ class SongHistory:
     def __len__(self) -> int:
         return self.nblocks
 
-    def _rows(self, peak, sq) -> list:
+    def _rows(self, peak, sq, clipped=None) -> list:
+        if clipped is not None:
+            return [((int(p[0]), int(p[1])), (int(q[0]), int(q[1])), (int(c[0]), int(c[1]))) for p, q, c in zip(peak, sq, clipped)]
         return [((int(p[0]), int(p[1])), (int(q[0]), int(q[1]))) for p, q in zip(peak, sq)]
 
     def __getitem__(self, j: int) -> SongLevels:
@@ -729,8 +749,8 @@ class SongHistory:
         j %= self.nblocks
         sq = self._sq[j] if self._sq is not None else [((int(h[0]) << 32) + int(lo[0]), (int(h[1]) << 32) + int(lo[1]))
                                                        for h, lo in zip(self._parts[0][j], self._parts[1][j])]
-        return SongLevels(self._rows(self.peak[j], sq), self.block_counts[j], self.samplewidth, self.nchannels, self.samplerate,
-                          self.ngroups)
+        return SongLevels(self._rows(self.peak[j], sq, None if self._clipped is None else self._clipped[j]), self.block_counts[j], self.samplewidth,
+                          self.nchannels, self.samplerate, self.ngroups)
 
     def __iter__(self):
         return (self[j] for j in range(self.nblocks))
@@ -749,8 +769,10 @@ class SongHistory:
     def total(self) -> SongLevels:
         """the whole window's levels: max of the peaks, sum of the sums (an empty window: every level 0)"""
         if not self.nblocks:
-            return SongLevels([((0, 0), (0, 0))] * self.peak.shape[1], 0, self.samplewidth, self.nchannels, self.samplerate, self.ngroups)
-        return SongLevels(self._rows(self.peak.max(axis=0), self._sums(0, self.nblocks)), self.frames, self.samplewidth, self.nchannels,
+            zero = ((0, 0), (0, 0)) if self._clipped is None else ((0, 0), (0, 0), (0, 0))
+            return SongLevels([zero] * self.peak.shape[1], 0, self.samplewidth, self.nchannels, self.samplerate, self.ngroups)
+        counts = None if self._clipped is None else self._clipped.sum(axis=0, dtype=np.uint64)
+        return SongLevels(self._rows(self.peak.max(axis=0), self._sums(0, self.nblocks), counts), self.frames, self.samplewidth, self.nchannels,
                           self.samplerate, self.ngroups)
 
     def fold(self, n: int) -> "SongHistory":
@@ -761,16 +783,26 @@ class SongHistory:
             raise ValueError("SongHistory: fold(n) needs a positive n")
         if not self.nblocks:
             return SongHistory(self.peak, self.sum_squares, 0, self.block_frames * n, self.start_frame, self.frames, self.samplewidth, self.nchannels,
-                               self.samplerate, self.ngroups)
+                               self.samplerate, self.ngroups, clipped=self._clipped)
         first = self.first_block // n
         cuts = [0] + [j for j in range(1, self.nblocks) if (self.first_block + j) % n == 0] + [self.nblocks]
         peak = np.stack([self.peak[a:b].max(axis=0) for a, b in zip(cuts, cuts[1:])])
         sq = np.stack([self._sums(a, b) for a, b in zip(cuts, cuts[1:])])
+        counts = None if self._clipped is None else np.stack([self._clipped[a:b].sum(axis=0, dtype=np.uint64) for a, b in zip(cuts, cuts[1:])])
         return SongHistory(peak, sq, first, self.block_frames * n, self.start_frame, self.frames, self.samplewidth, self.nchannels, self.samplerate,
-                           self.ngroups)
+                           self.ngroups, clipped=counts)
 
     def peaks(self) -> np.ndarray:
         out = self.peak.copy()
+        if self.nchannels != 2:
+            out[:, :, 1] = out[:, :, 0]
+        return out
+
+    def clipped(self) -> Optional[np.ndarray]:
+        """the overs per block, row and channel (a history rendered with ``clips=True``; None otherwise)"""
+        if self._clipped is None:
+            return None
+        out = self._clipped.copy()
         if self.nchannels != 2:
             out[:, :, 1] = out[:, :, 0]
         return out
@@ -874,14 +906,29 @@ class CompiledSequence:
     ``SongLevels`` -- the levels of every track post-fader and of the master in the window just rendered, exact in integers -- beside
     the same bytes; with ``pans`` a track's levels are post-fader and post-pan, with ``master`` the master's are over the bytes
     returned.  A handle serves one metered render at a time.  Not built: pre-fader meters (they would read a muted track's
-    events), meters of a song without tracks, clip counters.
+    events), meters of a song without tracks.
     The desk's LEVEL HISTORY: ``meters="history"`` gives, still from that one launch, a ``SongHistory`` instead -- the same levels per
     BLOCK of the window, a block being one tile of the SONG's grid (1024 frames of a 16-bit stereo song, 62 to 125 ms at the tests'
     rate, 10 to 21 ms at 48 kHz) cut to the window: ``history[j]`` is the ``SongLevels`` that ``meters=True`` gives for block ``j``'s
     own frames, ``total()`` the one it gives for the window, ``fold(n)`` coarser blocks, ``peaks()`` an array to draw.  Blocks are
     anchored to the song, so a block that lies whole inside two windows reads the same from both.  With gains, pans, master, groups
     and the tracks' fader moves.  Not built (``NotImplementedError``): a history with an ``Automation`` that rides a bus or a pan; a
-    history without rendering the bytes; clip counters.
+    history without rendering the bytes.
+    The desk's OVERS: with ``meters="history"`` the same calls take ``clips=True``, and the ``SongHistory`` then says, still from that one
+    launch, which bus clipped and where: ``clipped()`` per block, row (tracks, master, groups) and channel, ``Levels.clipped`` in every
+    block's levels, ``total()`` and ``fold(n)`` adding the counts.  ``clipped`` is the number of samples of that channel in the block at
+    which AT LEAST ONE of the row's OWN steps was clamped -- a step is clamped where the value it would have produced without the clamp
+    lies outside the width's range ``[LO, HI]`` --, a sample counting ONCE per row however many steps clamped at it.  A track's steps:
+    every saturating add of an event's samples into its sub-mix (``mix_at``'s ``audioop.add``), its ``amplify(gain)``, its static pan
+    factors.  A group's: every saturating add of a track into its bus, its ``amplify(gain)``, its pan factors.  The master's: every
+    saturating add of a track or a group into it, its ``amplify(master_gain)``.  An add clamps where the exact integer sum of the
+    saturated accumulator and the addend is ``> HI`` or ``< LO``; a multiply by a factor ``f != 1.0`` clamps where ``floor(p) > HI`` or
+    ``floor(p) < LO``, ``p`` being the float64 product ``audioop.mul`` forms (a product in ``(HI, HI + 1)`` floors to ``HI`` and is no
+    over).  A row counts its own stage only: a track that clipped does not make its group or the master count.  Not counted: what an
+    event does to its own samples before the add (its volume, pan, channel factors, envelope -- the sample as placed) and the tracks'
+    fader moves, which cannot leave the range.  A muted or skipped track or group and an idle tile count 0; a mono song fills channel
+    0.  The bytes, the peaks and the sums are those of the call without ``clips``.  ``clips=True`` without ``meters="history"`` is a
+    ``ValueError``.  Not built (``NotImplementedError``): overs of an event's own chain, overs with bus or pan rides.
     The desk's FADER AUTOMATION: ``automation(lanes)`` takes, per track, None or a list of pieces ``(start_frame, end_frame, from_volume,
     to_volume)`` in SONG frames -- ascending, not overlapping, volumes finite and within 0.0 .. 1.0 (a static gain above 1 stays with
     ``gains``) -- and uploads them once; ``render``, ``render_into`` and ``chunks`` take the ``Automation`` it returns as
@@ -1085,9 +1132,22 @@ class CompiledSequence:
             raise NotImplementedError("CompiledSequence: rides of buses and pans have no level history yet (meters=\"history\" with an "
                                       "Automation that has master, group or pan pieces)")
 
-    def _history(self, blocks, start_frame: int, nframes: int, ngroups: int) -> SongHistory:
+    @staticmethod
+    def _clips(clips, meters, automation) -> bool:
+        """``clips`` as render hands it on: the overs are counted per block of a level history and, as the history, not through rides of
+        buses and pans -- said before anything is launched"""
+        if not clips:
+            return False
+        if meters != "history":
+            raise ValueError("CompiledSequence: clips=True counts the overs per block of a level history: it needs meters=\"history\"")
+        if automation is not None and (automation.master or automation.rides or automation.pan_segments is not None):
+            raise NotImplementedError("CompiledSequence: overs are not counted through rides of buses and pans yet (clips=True with an "
+                                      "Automation that has master, group or pan pieces)")
+        return True
+
+    def _history(self, blocks, start_frame: int, nframes: int, ngroups: int, clips: bool = False) -> SongHistory:
         return SongHistory.from_blocks(blocks, self.ntracks + 1 + ngroups, N.SEQ_TILE_SAMPLES[self.samplewidth], start_frame, nframes, self.samplewidth, self.nchannels,
-                                       self.samplerate, ngroups)
+                                       self.samplerate, ngroups, clips=clips)
 
     def _pans(self, pans) -> Optional[list]:
         """``pans`` as render hands them on: None (no track has a pan step), or ``2 * ntracks`` finite floats, left then right per track,
@@ -1440,7 +1500,7 @@ class CompiledSequence:
 
     def render_into(self, buf: N.DeviceBuffer, byte_offset: int, start_frame: int, nframes: int, gains: Optional[Sequence[float]] = None,
                     meters: bool = False, pans: Optional[Sequence] = None, master: Optional[float] = None,
-                    automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> Union[None, SongLevels, SongHistory]:
+                    automation: Optional[Automation] = None, groups: Optional[Sequence] = None, clips: bool = False) -> Union[None, SongLevels, SongHistory]:
         """Frames ``[start_frame, start_frame + nframes)`` of the song into ``buf`` from ``byte_offset`` (a whole number of samples) on:
         every byte of the range is written, whatever ``buf`` held.  ``gains``: one per track of a song of tracks.  ``meters=True``: the
         same bytes, and the window's ``SongLevels`` returned, from the same launch (the call then waits for it).  ``pans``, ``master``:
@@ -1448,22 +1508,26 @@ class CompiledSequence:
         None or an ``Automation`` made by this song's ``automation()``: its fader moves, in that same launch.  ``groups``: None or the
         group buses (``CompiledSequence``), in that same launch; the levels then hold a ``Levels`` per group as well.
         ``meters="history"``: the same bytes, and the window's ``SongHistory`` returned -- its levels per block of the song's tile grid,
-        still from that one launch."""
+        still from that one launch.  ``clips=True`` (with ``meters="history"``): the history carries the overs per block as well
+        (``CompiledSequence``), still from that one launch."""
         seq = self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
         groups = self._groups(groups)
         desk = self._desk(self._pans(pans), self._master(master), self._automation(automation, groups), groups)
+        clips = self._clips(clips, meters, automation)
         self._no_history_of(meters, automation)
         start_frame, nframes = self._range(start_frame, nframes)
         if byte_offset < 0 or byte_offset % self.samplewidth:
             raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
         if meters == "history":
             blocks = None
+            if clips:
+                desk = dict(desk, clips=True)
             if nframes:
                 blocks = seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains,
                                     meters="history", **desk)
-            return self._history(blocks, start_frame, nframes, len(groups or ()))
+            return self._history(blocks, start_frame, nframes, len(groups or ()), clips)
         if meters:
             rows = None
             if nframes:
@@ -1479,33 +1543,38 @@ class CompiledSequence:
 
     def render(self, start_frame: int = 0, nframes: Optional[int] = None, gains: Optional[Sequence[float]] = None, meters: bool = False,
                pans: Optional[Sequence] = None, master: Optional[float] = None, automation: Optional[Automation] = None,
-               groups: Optional[Sequence] = None):
+               groups: Optional[Sequence] = None, clips: bool = False):
         """A new ``Sample``: frames ``[start_frame, start_frame + nframes)`` of the song; ``nframes`` None: to the end.  ``gains``: one
         per track of a song of tracks (None: all 1.0).  ``meters=True``: ``(Sample, SongLevels)``, both from the one launch;
         ``meters="history"``: ``(Sample, SongHistory)``, the levels per block of the song's tile grid, from the one launch as well.  ``pans``:
         one entry per track of a stereo song of tracks (None, a number -1 .. 1 or a pair of factors); ``master``: the master's gain;
         ``automation``: this song's fader moves (``automation()``); ``groups``: at most 8 entries ``(first_track, end_track, gain)`` or
-        ``(first_track, end_track, gain, pan)``, the group buses (``CompiledSequence`` has the chain)."""
+        ``(first_track, end_track, gain, pan)``, the group buses (``CompiledSequence`` has the chain).  ``clips=True`` (with
+        ``meters="history"``): the ``SongHistory`` carries the overs per block."""
         self._handle()
         gains = self._gains(gains)
         meters = self._meters(meters)
         self._pans(pans), self._master(master)                  # (checked here as well: before the buffer is made)
         ngroups = len(self._groups(groups) or ())
         self._automation(automation, self._groups(groups))
+        clips = self._clips(clips, meters, automation)
         self._no_history_of(meters, automation)
         start_frame, nframes = self._range(start_frame, nframes)
         out = Sample(name=self.name, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth)
         levels = None
         if nframes:
             buf = N.DeviceBuffer(nframes * self._fb)
-            if meters:
+            if clips:
+                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=meters, pans=pans, master=master, automation=automation,
+                                          groups=groups, clips=True)
+            elif meters:
                 levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=meters, pans=pans, master=master, automation=automation,
                                           groups=groups)
             else:
                 self.render_into(buf, 0, start_frame, nframes, gains=gains, pans=pans, master=master, automation=automation, groups=groups)
             out._set_device(buf, nframes * self._fb)
         if meters == "history":
-            return out, levels if levels is not None else self._history(None, start_frame, 0, ngroups)
+            return out, levels if levels is not None else self._history(None, start_frame, 0, ngroups, clips)
         if meters:
             return out, levels if levels is not None else self._levels(None, 0, ngroups)
         return out
@@ -1521,10 +1590,12 @@ class CompiledSequence:
         return self.render(start_frame, nframes, gains=[1.0 if t == track else 0.0 for t in range(self.ntracks)])
 
     def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None, meters: bool = False, pans: Optional[Sequence] = None,
-               master: Optional[float] = None, automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> Generator:
+               master: Optional[float] = None, automation: Optional[Automation] = None, groups: Optional[Sequence] = None,
+               clips: bool = False) -> Generator:
         """The song as consecutive ``Sample``s of ``chunk_frames`` frames, the last one shorter.  ``gains``, ``pans``, ``master``,
         ``automation``, ``groups``: as ``render``'s (the joined chunks are the whole render's bytes whatever ``chunk_frames`` cuts).
-        ``meters=True``: ``(Sample, SongLevels)`` pairs; ``meters="history"``: ``(Sample, SongHistory)`` pairs."""
+        ``meters=True``: ``(Sample, SongLevels)`` pairs; ``meters="history"``: ``(Sample, SongHistory)`` pairs, with ``clips=True`` each
+        with its overs."""
         chunk_frames = int(chunk_frames)
         if chunk_frames <= 0:
             raise ValueError("CompiledSequence: chunk_frames must be positive")
@@ -1532,9 +1603,13 @@ class CompiledSequence:
         gains = self._gains(gains)
         meters = self._meters(meters)
         self._pans(pans), self._master(master), self._automation(automation, self._groups(groups))
+        clips = self._clips(clips, meters, automation)
         self._no_history_of(meters, automation)
         for at in range(0, self.frames, chunk_frames):
-            if meters:
+            if clips:
+                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=meters, pans=pans, master=master, automation=automation,
+                                  groups=groups, clips=True)
+            elif meters:
                 yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=meters, pans=pans, master=master, automation=automation,
                                   groups=groups)
             else:

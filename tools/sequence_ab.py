@@ -124,7 +124,12 @@ runs: SEQUENCE_AB_TREE=<a built checkout of the parent commit> python tools/sequ
 synchronise, medians, of the whole song, for: (a) one render(meters="history", ...), the one launch, the table of blocks read back; (b) the
 caller's way today -- chunks(block_frames, meters=True, ...) over the whole song, one metered render per block -- whose master rows are
 held to (a)'s first; (c) the same render with meters=True.  On a tree without meters="history" only (c) runs: SEQUENCE_AB_TREE=<a built
-checkout of the parent commit> python tools/sequence_ab.py --history is the parent's own figure for (c), row (d)."""
+checkout of the parent commit> python tools/sequence_ab.py --history is the parent's own figure for (c), row (d).
+--clips: the song of --history and the overs of its level history.  Wall time with a device synchronise, medians, and the time between two
+events on the stream, of the whole song and of a 4096-frame window, for: (a) render_into(meters="history", clips=True, ...); (c) the same
+call without clips; and meters=True.  On a tree without clips= only (c) and meters=True run: SEQUENCE_AB_TREE=<a built checkout of the parent
+commit> python tools/sequence_ab.py --clips is the parent's own figure for both, row (d).  --clips-trace: (a) and (c) a few times each and
+nothing else, for a kernel trace in a run of its own."""
 import audioop
 import os
 import sys
@@ -134,7 +139,7 @@ from pathlib import Path
 import numpy as np
 
 # the yardstick of --plan, --tracks, --desk, --auto, --groups, --buses, --pans and --history is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
-sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:] or "--groups" in sys.argv[1:] or "--buses" in sys.argv[1:] or "--pans" in sys.argv[1:] or "--history" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
+sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:] or "--groups" in sys.argv[1:] or "--buses" in sys.argv[1:] or "--pans" in sys.argv[1:] or "--history" in sys.argv[1:] or "--clips" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
 from synthesizer_amd import _native as N  # noqa: E402
 from synthesizer_amd import mixer  # noqa: E402
 from synthesizer_amd.sample import Sample  # noqa: E402
@@ -1685,6 +1690,56 @@ def history_main():
         bus.close()
 
 
+def clips_main(trace=False):
+    """--clips: what the overs cost.  (a) render_into(meters="history", clips=True, gains=, pans=, master=, groups=) of the whole song and of a
+    4096-frame window; (c) the same call without clips; (m) meters=True.  A tree without clips= runs (c) and (m) alone."""
+    import inspect
+    N.ensure_init(0)
+    info = N.device_info()
+    has = "clips" in inspect.signature(mixer.CompiledSequence.render_into).parameters
+    print("sequence_clips_ab: SYNTHHIP_SEQ_ALIGN=%s  %s  clips=: %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"],
+          "yes" if has else "no (the yardstick: (c) and meters=True alone)"), flush=True)
+    ntracks = len(TRACK_GAINS)
+    desk = dict(gains=TRACK_GAINS, pans=DESK_PANS, master=DESK_MASTER, groups=GROUPS)
+    fmt = lambda v: " ".join("%.4f" % x for x in v)        # noqa: E731
+    for nevents in (4096, 32768):
+        what, nch, evs = meters_songs(nevents)[0]
+        fb = nch * WIDTH
+        bus = mixer.compile_tracks([evs[t::ntracks] for t in range(ntracks)], RATE, nch, WIDTH)
+        frames = bus.frames
+        out = N.DeviceBuffer(frames * fb + 16)
+        win = 4096
+        at = (22 * RATE) // win * win + 3                      # a window three frames off the tile grid, inside the song
+        whole = lambda **kw: bus.render_into(out, 0, 0, frames, **kw, **desk)       # noqa: E731
+        window = lambda **kw: bus.render_into(out, 0, at, win, **kw, **desk)        # noqa: E731
+        if trace:
+            for _ in range(5):
+                whole(meters="history", clips=True)
+                whole(meters="history")
+                window(meters="history", clips=True)
+                window(meters="history")
+            N.sync()
+            bus.close()
+            continue
+        head = "clips song 120 s, %5d events, %s, %d tracks, %d groups, level %s, %d frames   " % (nevents, what, ntracks, len(GROUPS), bus.level, frames)
+        rows = []
+        for name, kw in (("(c) render(meters=\"history\", ...)", dict(meters="history")), ("(m) render(meters=True, ...)", dict(meters=True))) + \
+                ((("(a) render(meters=\"history\", clips=True, ...)", dict(meters="history", clips=True)),) if has else ()):
+            rows.append((name, median_wall(lambda: whole(**kw), 2, 15), five_medians(lambda: whole(**kw)), median_wall(lambda: window(**kw), 2, 15),
+                         five_medians(lambda: window(**kw))))
+        text = "   ".join("%s: whole song, wall with a synchronise, median %.4f ms, between two events on the stream, five medians of 15: %s ms; a window of "
+                          "%d frames, wall %.4f ms, events %s ms" % (name, w, fmt(wd), win, x, fmt(xd)) for name, w, wd, x, xd in rows)
+        if has:
+            h, plain = whole(meters="history", clips=True), whole(meters="history")
+            counted = h.clipped().sum(axis=0)
+            parity = plain.clipped() is None and h.total() == plain.total() and all(h[j] == plain[j] for j in range(0, h.nblocks, 97))
+            text += "   (a) / (c) whole %.3f, window %.3f   overs of the whole song per row (left, right): %s   (a)'s levels against (c)'s: %s" % (
+                rows[2][1] / rows[0][1], rows[2][3] / rows[0][3], counted.tolist(), "ok" if parity else "FAILED")
+            assert parity
+        print(head + text, flush=True)
+        bus.close()
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -1755,4 +1810,4 @@ def main():
 
 
 if __name__ == "__main__":
-    history_main() if "--history" in sys.argv[1:] else pans_main() if "--pans" in sys.argv[1:] else buses_main() if "--buses" in sys.argv[1:] else groups_main() if "--groups" in sys.argv[1:] else auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    clips_main("--clips-trace" in sys.argv[1:]) if "--clips" in sys.argv[1:] or "--clips-trace" in sys.argv[1:] else history_main() if "--history" in sys.argv[1:] else pans_main() if "--pans" in sys.argv[1:] else buses_main() if "--buses" in sys.argv[1:] else groups_main() if "--groups" in sys.argv[1:] else auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
