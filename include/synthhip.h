@@ -957,6 +957,27 @@ int sh_seq_render_clips(const sh_seq* seq, size_t first_sample, size_t nsamples,
                         uint32_t nblocks, const sh_seq_auto* automation /* may be NULL */, const sh_seq_group* groups /* NULL: none */,
                         uint32_t ngroups);
 
+/* The desk's STEMS: the samples of every bus, from ONE launch that walks every event once (csrc/seqstem.hpp states the contract).
+ * sh_seq_render_stems is sh_seq_render_groups without meters -- the same chain, the same arguments with the same meaning, ngroups may be 0
+ * (groups NULL) and automation may be NULL or any handle of the song: track lanes, bus rides, pan rides -- that writes, instead of the
+ * master alone, nplanes == ntracks + 1 + ngroups PLANES of nsamples samples each into `out`, in the meter table's row order: track t in
+ * plane t, the master in plane ntracks, group g in plane ntracks + 1 + g.  Plane r is samples [out_sample + r * plane_samples,
+ * out_sample + r * plane_samples + nsamples) of `out`, and holds exactly the samples over which sh_seq_render_groups' meters of the same
+ * call read row r: a track as its bus takes it (its gain, its fader moves, its pan or pan ride), a group's bus as the master takes it
+ * (saturated at every track, its gain, its ride, its pan or pan ride), the master's plane the bytes sh_seq_render_groups stores.  A
+ * muted or skipped track or group is all zeros.  EVERY byte of every plane is written whatever `out` held, idle tiles and muted rows
+ * included, and no byte of `out` outside the planes' windows: none in front, none behind, none in the gaps where plane_samples >
+ * nsamples.  At width 2 the store is one 16-byte vector per lane where plane 0's first sample lies (first_sample mod 8) samples behind
+ * a 16-byte boundary and plane_samples is a multiple of 8; any other geometry is stored sample by sample and is the same bytes.
+ * Asynchronous on the library's stream, as sh_seq_render_groups without meters; nothing is zeroed or copied in front of the launch.
+ * nsamples == 0 writes nothing and succeeds.  SH_ERR_INVALID, nothing launched, `out` untouched: what sh_seq_render_groups refuses apart
+ * from ngroups == 0; a song without tracks; nplanes other than ntracks + 1 + ngroups; plane_samples < nsamples; a last plane that ends
+ * outside `out`; a span of all planes, gaps included, that overlaps a source of the song -- each by a message of its own.  Not built:
+ * stems together with meters, a history or overs in the same launch; pre-fader stems; the raw group bus in front of its gain. */
+int sh_seq_render_stems(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, size_t plane_samples,
+                        uint32_t nplanes, const double* gains, uint32_t ngains, const double* pans, uint32_t npans, double master_gain,
+                        const sh_seq_auto* automation /* may be NULL */, const sh_seq_group* groups /* NULL: none */, uint32_t ngroups);
+
 /* ---- the real-time lane -------------------------------------------------------------------------------------------------------
  * Replaces: the thread upstream's playback.py runs its mixer on (the output thread pulls RealTimeMixer.chunks() while other threads
  * make sound).  Every entry point above holds the library's one lock and enqueues on its one stream pair: a mixer turn from another

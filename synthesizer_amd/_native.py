@@ -235,6 +235,8 @@ _SIGNATURES = {
                                         C.c_double, C.POINTER(SeqMeter), C.c_uint32, C.c_uint32, _P, C.POINTER(SeqGroup), C.c_uint32]),
     "sh_seq_render_clips": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
                                       C.c_double, C.POINTER(SeqMeterClips), C.c_uint32, C.c_uint32, _P, C.POINTER(SeqGroup), C.c_uint32]),
+    "sh_seq_render_stems": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
+                                      C.POINTER(C.c_double), C.c_uint32, C.c_double, _P, C.POINTER(SeqGroup), C.c_uint32]),
     "sh_rt_create": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "sh_rt_destroy": (C.c_int, [_P]),
     "sh_rt_acquire": (C.c_int, [_P, _P]),
@@ -555,6 +557,22 @@ class Sequence:
             check(lib().sh_seq_render_gains(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), len(gains)))
         if meters:
             return [((r.peak[0], r.peak[1]), ((r.sq_hi[0] << 32) + r.sq_lo[0], (r.sq_hi[1] << 32) + r.sq_lo[1])) for r in rows]
+
+    def stems(self, first_sample: int, nsamples: int, out: "DeviceBuffer", out_sample: int, plane_samples: int, gains=None, pans=None, master=None,
+              automation: Optional["SeqAutomation"] = None, groups=None) -> None:
+        """sh_seq_render_stems (a song of tracks): the desk of ``render`` with the same keywords, and instead of the master alone
+        ``ntracks + 1 + len(groups)`` planes of ``nsamples`` samples, ``plane_samples`` apart from ``out_sample`` on, in the meter rows'
+        order -- the tracks as their bus takes them, the master, the groups as the master takes them.  One launch, asynchronous."""
+        def doubles(v):
+            return None if v is None else (C.c_double * max(1, len(v)))(*v)
+
+        def count(v):
+            return 0 if v is None else len(v)
+        ngroups = len(groups) if groups else 0
+        table = (SeqGroup * ngroups)(*[SeqGroup(*g) for g in groups]) if ngroups else None
+        check(lib().sh_seq_render_stems(self._h, first_sample, nsamples, out.handle, out_sample, plane_samples, self.tracks()[0] + 1 + ngroups,
+                                        doubles(gains), count(gains), doubles(pans), count(pans), 1.0 if master is None else master,
+                                        None if automation is None else automation.handle, table, ngroups))
 
     def free(self) -> None:
         if self._h:

@@ -75,7 +75,13 @@
 // buses that COUNT OVERS, SeqBusGC (width 3: SeqBusGC3), are the history buses again whose lanes fold into COUNTING accumulators -- the
 // samples and one sticky flag per sample, set where a step of the bus's own arithmetic was clamped (seqclip.hpp: an add whose exact sum
 // leaves the range, a multiply whose floor does) -- through the same schedules and the same seq_runs, which are generic in the
-// accumulator's type; a row carries the count of flagged samples behind its levels (sh_seq_render_clips).
+// accumulator's type; a row carries the count of flagged samples behind its levels (sh_seq_render_clips).  The STEMS buses, SeqBusGS,
+// SeqBusRS and SeqBusPS (width 3: SeqBusGS3), are the group buses, the buses that ride and the buses that pan again -- not the metering
+// ones: no table, no barrier -- whose lanes STORE every bus where a metering bus reduces it (sh_seq_render_stems; seqstem.hpp): the
+// kernels hand seq_stems_bus a store that takes a destination and the samples, seq_runs' hook stores a track's or a group's samples into plane `row` of the
+// caller's buffer -- row * stride bytes behind plane 0, the stride being the one new kernel argument, 64 bits --, the master goes to plane
+// ntracks, and behind the runs every row that no hook stored in this tile gets the lane's samples as zeros, so that each sample of each
+// plane has one writer and nothing is zeroed in front of the launch.
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
@@ -90,6 +96,7 @@
 #include "seqmeter.hpp"
 #include "seqrev.hpp"
 #include "seqplan.hpp"
+#include "seqstem.hpp"
 #include <math.h>
 #include <string.h>
 #include <new>
@@ -1038,6 +1045,22 @@ struct SeqBusP : SeqBusR, SeqPans {};
 template <typename... Bus> constexpr bool SEQ_PANS = (std::is_base_of<SeqPans, Bus>::value || ...);
 static_assert(sizeof(SeqBusP) == sizeof(SeqBusG) && SH_ENV_PAN == shp::PAN, "the pan rides: no kernel argument of their own");
 
+// The STEMS buses (sh_seq_render_stems; seqstem.hpp): the group buses, the buses that ride and the buses that pan again -- the whole desk,
+// NULL pointers meaning no moves, the empty table no groups -- whose lanes STORE every bus where a metering bus reduces it: track t's
+// samples as seq_runs' hook receives them into plane t, a group's into plane groups.row0 + g, the master's into plane groups.row0 - 1,
+// plane r standing r * stride BYTES behind plane 0 (64-bit).  A tag that carries the stride -- the one new kernel argument -- and one bus
+// type on each of SeqBusG, SeqBusR and SeqBusP (widths 1, 2 and 4: a table without bus lanes or without pan lanes must not reach a kernel
+// that reads them) and one on SeqBusG3 (width 3).  They are NOT metering buses: no table, no barrier, lanes outside the window leave.
+struct SeqStems { uint64_t stride; };
+struct SeqBusGS : SeqBusG, SeqStems {};
+struct SeqBusRS : SeqBusR, SeqStems {};
+struct SeqBusPS : SeqBusP, SeqStems {};
+struct SeqBusGS3 : SeqBusG3, SeqStems {};
+template <typename... Bus> constexpr bool SEQ_STEMS = (std::is_base_of<SeqStems, Bus>::value || ...);
+static_assert(sizeof(SeqBusGS) == sizeof(SeqBusG) + 8 && sizeof(SeqBusPS) == sizeof(SeqBusG) + 8 && sizeof(SeqBusGS3) == sizeof(SeqBusG3) + 8 &&
+              shst::MAX_ROWS == shq::MAX_TRACKS + 1 + shg::MAX_GROUPS && shst::MAX_ROWS <= 64,
+              "the stems: the stride, 8 bytes of kernel arguments behind the bus; a bit of one 64-bit mask per plane");
+
 // a lane's accumulator: eight packed samples at 16 bits, four 64-bit sums at the other widths
 template <int WIDTH> struct SeqAcc { typedef llong4v type; };
 template <> struct SeqAcc<2> { typedef short8v type; };
@@ -1495,6 +1518,37 @@ __device__ __forceinline__ void seq_hist_end(const R* table, const SeqBusM& bus,
     if constexpr (std::is_same<R, shcl::Row>::value) g->clipped[c] = table[row].clipped[c];
 }
 
+// What a window kernel does where it has a STEMS bus (sh_seq_render_stems; seqstem.hpp), once for the three templates: a lane that
+// seq_window_lane kept, as with a plain bus.  put(to, x): the kernel's window store of a lane's samples x at the lane's song position
+// through the biased base `to` -- seq_window_store8 / seq_window_store_w with their cut to [lo, hi) and the aligned fast path --, stated
+// once per template and used for every plane, the master's too.  seq_runs' hook puts a bus's samples into plane `row` and marks the row
+// in a wave-uniform mask; the master, behind its gain and its ride, goes to plane groups.row0 - 1; behind the runs every row that no hook
+// stored -- a muted or skipped track, a track or a group without a run in this tile, all of them in an idle tile -- gets the lane's samples
+// as zeros, so that every sample of every plane has this one writer and nothing zeroes the planes in front of the launch.
+// (A function and a store of their own, beside seq_window_bus and the kernels' store(): giving THAT lambda the destination and the samples
+// as parameters changed the register allocation of 25 of the 508 existing kernels, which are held to what they were
+// -- profiles/sequence_stems_ab.txt, section 1.)
+template <int WIDTH, typename Bus, typename Walk, typename Put, typename Out>
+__device__ __forceinline__ void seq_stems_bus(const Bus& bus, uint32_t k, uint32_t e, typename SeqAcc<WIDTH>::type& acc, Walk walk, Put put, Out* out) {
+    typedef typename SeqAcc<WIDTH>::type V;
+    auto plane = [&](uint32_t row) {                          // (the biased base of plane `row`: valid at samples [lo, hi) alone, as `out` is)
+        return reinterpret_cast<Out*>(reinterpret_cast<unsigned char*>(out) + shst::plane_offset(row, bus.stride));
+    };
+    uint64_t stored = 0;                                      // (uniform: bit `row` set where a hook stored the row in this tile)
+    seq_runs<WIDTH>(bus, k, e, acc, walk, [&](const V& x, uint32_t row) {
+        put(plane(row), x);
+        stored |= 1ull << row;
+    });
+    seq_master<WIDTH>(acc, bus.master);
+    if constexpr (SEQ_RIDES<Bus>) seq_ride<WIDTH>(acc, bus, sha::master_lane(bus.groups.row0), k);      // the master's ride: behind its gain
+    const uint32_t master = bus.groups.row0 - 1u, nrows = bus.groups.row0 + bus.groups.n;
+    put(plane(master), acc);
+    stored |= 1ull << master;
+    const V zeros = {};
+    for (uint32_t row = 0; row < nrows; ++row)
+        if (!((stored >> row) & 1ull)) put(plane(row), zeros);      // (uniform)
+}
+
 // What a window kernel does where it has a bus, once for the three templates: the runs of tile k into acc, (a desk bus) the master's gain,
 // then store().  A plain bus: a lane that seq_window_lane kept; s0, lo and hi, which only a metering bus needs, are ignored.
 // A metering bus: EVERY lane of a workgroup that seq_window_tile kept, the rows of the tracks from seq_runs' hook and the master's row
@@ -1553,7 +1607,9 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_plain16(const SeqEv* 
     auto walk = [&](uint32_t& e, uint32_t e1, auto& into) { seq_walk_plain16<SCHEME, INFLIGHT>(ev, segs, idx, e, e1, t0, s0, into); };
     auto store = [&] { seq_window_store8(out, s0, lo, hi, whole, seq_v(acc)); };
     uint32_t e = first[k];
-    if constexpr (BUS) {
+    if constexpr (SEQ_STEMS<Bus...>) {
+        seq_stems_bus<2>(bus..., k, e, acc, walk, [&](short* to, const short8v& x) { seq_window_store8(to, s0, lo, hi, whole, x); }, out);
+    } else if constexpr (BUS) {
         seq_window_bus<2>(bus..., k, e, s0, lo, hi, acc, walk, store);
     } else {
         walk(e, first[k + 1], acc);
@@ -1579,7 +1635,9 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_16(const typename Seq
     auto walk = [&](uint32_t& e, uint32_t e1, auto& into) { seq_walk_16<LEVEL, SCHEME>(ev, segs, idx, e, e1, t0, s0, into); };
     auto store = [&] { seq_window_store8(out, s0, lo, hi, whole, seq_v(acc)); };
     uint32_t e = first[k];
-    if constexpr (BUS) {
+    if constexpr (SEQ_STEMS<Bus...>) {
+        seq_stems_bus<2>(bus..., k, e, acc, walk, [&](short* to, const short8v& x) { seq_window_store8(to, s0, lo, hi, whole, x); }, out);
+    } else if constexpr (BUS) {
         seq_window_bus<2>(bus..., k, e, s0, lo, hi, acc, walk, store);
     } else {
         const uint32_t e1 = first[k + 1];
@@ -1606,7 +1664,9 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_w(const typename SeqR
     auto walk = [&](uint32_t& e, uint32_t e1, auto& into) { seq_walk_w<LEVEL, WIDTH>(ev, segs, idx, e, e1, t0, s0, into); };
     auto store = [&] { seq_window_store_w<WIDTH>(out, s0, lo, hi, seq_v(acc)); };
     uint32_t e = first[k];
-    if constexpr (BUS) {
+    if constexpr (SEQ_STEMS<Bus...>) {
+        seq_stems_bus<WIDTH>(bus..., k, e, acc, walk, [&](unsigned char* to, const llong4v& x) { seq_window_store_w<WIDTH>(to, s0, lo, hi, x); }, out);
+    } else if constexpr (BUS) {
         seq_window_bus<WIDTH>(bus..., k, e, s0, lo, hi, acc, walk, store);
     } else {
         walk(e, first[k + 1], acc);
@@ -2054,7 +2114,8 @@ void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, 
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out, bus...); };
         if constexpr (LEVEL != ENV) go(k_win_w<LEVEL, 3, BUS, Bus...>);
     } else if (q->width == 2) {
-        const int aligned = ((uintptr_t)out & 15) == 0;       // the BIASED base: song-anchored lanes start on multiples of eight samples
+        int aligned = ((uintptr_t)out & 15) == 0;             // the BIASED base: song-anchored lanes start on multiples of eight samples
+        if constexpr (SEQ_STEMS<Bus...>) aligned = (shst::aligned((uint64_t)(uintptr_t)out, bus.stride) && ...);      // (stems: of EVERY plane)
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (short*)out, aligned, bus...); };
         const bool vec2 = sh::knobs().seq_align == VEC2;
         if constexpr (LEVEL == PLAIN) vec2 ? go(k_win_plain16<VEC2, 4, BUS, Bus...>) : go(k_win_plain16<FUNNEL, 4, BUS, Bus...>);
@@ -2201,10 +2262,12 @@ template <typename T> struct SeqBaseOf { typedef T type; };
 // without au; meters: ntracks + 1 + ngroups rows; rides: au has a segment on a bus lane, and groups may then be the empty table; pans: au
 // has a segment on a pan lane, likewise) and sh_seq_render_history (history: meters is a table of BLOCKS, nblocks * nrows host rows; the
 // device table is the library's scratch, sized for the call, and needs no zeroing) and sh_seq_render_clips (clips: a history whose rows
-// are sh_seq_meter_clips, 48 bytes) behind their names
+// are sh_seq_meter_clips, 48 bytes) and sh_seq_render_stems (stems: the planes' stride in bytes and their count, checked by the caller
+// against `out`; with groups, no meters; out_sample is plane 0's) behind their names
+struct SeqStemsCall { uint64_t stride; uint32_t nplanes; };
 int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains,
                void* meters = nullptr, const SeqDesk* desk = nullptr, const SeqAuto* au = nullptr, const shg::Table* groups = nullptr,
-               bool rides = false, bool pans = false, bool history = false, bool clips = false) {
+               bool rides = false, bool pans = false, bool history = false, bool clips = false, const SeqStemsCall* stems = nullptr) {
     static_assert(sizeof(sh_seq_meter) == sizeof(shmt::Row) && offsetof(sh_seq_meter, sq_hi) == offsetof(shmt::Row, sq_hi) &&
                   offsetof(sh_seq_meter, sq_lo) == offsetof(shmt::Row, sq_lo), "sh_seq_meter is shmt::Row");
     static_assert(sizeof(sh_seq_meter_clips) == sizeof(shcl::Row) && offsetof(sh_seq_meter_clips, sq_hi) == offsetof(sh_seq_meter, sq_hi) &&
@@ -2222,6 +2285,12 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
     }
     const char* o0 = (const char*)out->ptr + out_sample * w;
     const char* o1 = o0 + nsamples * w;
+    if (stems) {                                              // from the first sample of plane 0 to the last of the last plane, gaps included
+        const char* s1 = o0 + shst::span(stems->nplanes, stems->stride / w, nsamples) * w;
+        for (size_t v = 0; v < seq->src_lo.size(); ++v)
+            if (shst::overlaps((uint64_t)(uintptr_t)o0, (uint64_t)(uintptr_t)s1, (uint64_t)(uintptr_t)seq->src_lo[v], (uint64_t)(uintptr_t)seq->src_hi[v]))
+                return sh::set_error(SH_ERR_INVALID, "%s: the span of the %u planes overlaps a source of the song", fn, stems->nplanes);
+    }
     for (size_t v = 0; v < seq->src_lo.size(); ++v)
         if (seq->src_lo[v] < o1 && o0 < seq->src_hi[v]) return sh::set_error(SH_ERR_INVALID, "%s: out overlaps a source of the song", fn);
     const uint32_t lo = (uint32_t)first_sample, hi = (uint32_t)(first_sample + nsamples), tile = shq::tile_samples(seq->width);
@@ -2261,9 +2330,15 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
                 static_cast<SeqDesk&>(moved) = bus;
                 if constexpr (SEQ_AUTO<G>) static_cast<SeqAuto&>(moved) = au ? *au : SeqAuto{nullptr, nullptr};
                 moved.groups = *groups;
+                if constexpr (SEQ_STEMS<G>) moved.stride = stems->stride;
                 seq_window_launch<LEVEL, G>(seq, grid, st, lo, hi, biased, moved);
             };
-            if (clips) seq->width == 3 ? grouped(SeqBusGC3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusGC{}, SeqBaseOf<SeqBusM>());
+            if (stems) {                                      // (no meters; au: which lanes its table holds says which kernel may read it)
+                if (seq->width == 3) grouped(SeqBusGS3{}, SeqBaseOf<SeqBus>());
+                else if (pans) grouped(SeqBusPS{}, SeqBaseOf<SeqBus>());
+                else if (rides) grouped(SeqBusRS{}, SeqBaseOf<SeqBus>());
+                else grouped(SeqBusGS{}, SeqBaseOf<SeqBus>());
+            } else if (clips) seq->width == 3 ? grouped(SeqBusGC3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusGC{}, SeqBaseOf<SeqBusM>());
             else if (history) seq->width == 3 ? grouped(SeqBusGH3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusGH{}, SeqBaseOf<SeqBusM>());
             else if (seq->width == 3) meters ? grouped(SeqBusGM3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG3{}, SeqBaseOf<SeqBus>());
             else if (pans) meters ? grouped(SeqBusPM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusP{}, SeqBaseOf<SeqBus>());       // (au: a table with pan lanes)
@@ -2542,11 +2617,13 @@ int sh_seq_render_auto(const sh_seq* seq, size_t first_sample, size_t nsamples, 
 
 // sh_seq_render_groups (history false: meters is NULL or nmeters == ntracks + 1 + ngroups rows, at least one group) and
 // sh_seq_render_history (history true: meters is nblocks blocks of nmeters rows each, groups and automation may be none) and
-// sh_seq_render_clips (history and clips true: the same, the rows sh_seq_meter_clips) behind their names
+// sh_seq_render_clips (history and clips true: the same, the rows sh_seq_meter_clips) and sh_seq_render_stems (stems: no meters, groups
+// and automation may be none, any automation; the planes' geometry is checked here, behind the desk's refusals) behind their names
+struct SeqStemsArgs { size_t plane_samples; uint32_t nplanes; };
 static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample,
                               const double* gains, uint32_t ngains, const double* pans, uint32_t npans, double master_gain, void* meters,
                               uint32_t nmeters, uint32_t nblocks, const sh_seq_auto* automation, const sh_seq_group* groups, uint32_t ngroups,
-                              bool clips = false) {
+                              bool clips = false, const SeqStemsArgs* stems = nullptr) {
     static_assert(sizeof(sh_seq_group) == sizeof(shg::Group) && offsetof(sh_seq_group, gain) == offsetof(shg::Group, gain) &&
                   offsetof(sh_seq_group, right) == offsetof(shg::Group, right) && SH_SEQ_MAX_GROUPS == shg::MAX_GROUPS, "sh_seq_group is shg::Group");
     if (!seq || !out || (!gains && ngains) || (!pans && npans) || (!meters && nmeters && !history)) return seq_null(fn);
@@ -2561,8 +2638,9 @@ static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, s
     if (pans && seq->nchannels != 2) return sh::set_error(SH_ERR_INVALID, "%s: pans need a stereo song, this one has %d channels", fn, seq->nchannels);
     if (gains && ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
     if (pans && npans != 2 * seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u pan factors for %u tracks (two each)", fn, npans, seq->ntracks);
-    if ((ngroups == 0 && !history) || ngroups > shg::MAX_GROUPS)
-        return sh::set_error(SH_ERR_INVALID, "%s: %u groups, %u to %u", fn, ngroups, history ? 0u : 1u, shg::MAX_GROUPS);
+    const bool nogroups = history || stems;                   // (a history and stems: ngroups may be 0)
+    if ((ngroups == 0 && !nogroups) || ngroups > shg::MAX_GROUPS)
+        return sh::set_error(SH_ERR_INVALID, "%s: %u groups, %u to %u", fn, ngroups, nogroups ? 0u : 1u, shg::MAX_GROUPS);
     if (!groups && ngroups) return seq_null(fn);
     const shg::Group* gs = reinterpret_cast<const shg::Group*>(groups);
     const shg::Verdict v = ngroups ? shg::check(gs, ngroups, seq->ntracks, seq->nchannels) : shg::Verdict{shg::OK, 0};
@@ -2578,7 +2656,23 @@ static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, s
     case shg::PAN_NOT_FINITE: return sh::set_error(SH_ERR_INVALID, "%s: group %u: left / right is not finite", fn, v.entry);
     case shg::PAN_NOT_STEREO:
         return sh::set_error(SH_ERR_INVALID, "%s: group %u: a pan needs a stereo song, this one has %d channels", fn, v.entry, seq->nchannels);
-    default: return sh::set_error(SH_ERR_INVALID, "%s: %u groups, %u to %u", fn, ngroups, history ? 0u : 1u, shg::MAX_GROUPS);
+    default: return sh::set_error(SH_ERR_INVALID, "%s: %u groups, %u to %u", fn, ngroups, nogroups ? 0u : 1u, shg::MAX_GROUPS);
+    }
+    SeqStemsCall planes{0, 0};
+    if (stems) {                                              // the planes' geometry (seqstem.hpp), each refusal by a message of its own
+        const size_t w = (size_t)seq->width;
+        switch (shst::check(stems->nplanes, seq->ntracks, ngroups, stems->plane_samples, nsamples, out_sample, out->bytes / w)) {
+        case shst::OK: break;
+        case shst::PLANES:
+            return sh::set_error(SH_ERR_INVALID, "%s: %u planes for %u tracks, the master and %u groups", fn, stems->nplanes, seq->ntracks, ngroups);
+        case shst::STRIDE:
+            return sh::set_error(SH_ERR_INVALID, "%s: planes %llu samples apart for a window of %llu: they would overlap", fn,
+                                 (unsigned long long)stems->plane_samples, (unsigned long long)nsamples);
+        default:
+            return sh::set_error(SH_ERR_INVALID, "%s: the last of %u planes ends outside out (%llu samples from sample %llu on, planes %llu apart)", fn,
+                                 stems->nplanes, (unsigned long long)(out->bytes / w), (unsigned long long)out_sample, (unsigned long long)stems->plane_samples);
+        }
+        planes = SeqStemsCall{shst::stride_bytes(stems->plane_samples, (uint32_t)seq->width), stems->nplanes};
     }
     if (clips && automation && (automation->buses || automation->pans))
         return sh::set_error(SH_ERR_INVALID, "%s: the automation rides a %s: overs are not counted through rides of buses and pans yet", fn,
@@ -2609,7 +2703,7 @@ static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, s
     SeqAuto au{nullptr, nullptr};
     if (automation) au = SeqAuto{(const she::Seg*)automation->block, (const uint32_t*)((const char*)automation->block + automation->at_first)};
     return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, automation ? &au : nullptr, &table,
-                      automation && (automation->buses || automation->pans), automation && automation->pans, history, clips);
+                      automation && (automation->buses || automation->pans), automation && automation->pans, history, clips, stems ? &planes : nullptr);
 }
 
 int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
@@ -2634,6 +2728,18 @@ int sh_seq_render_clips(const sh_seq* seq, size_t first_sample, size_t nsamples,
     SH_REQUIRE_INIT();
     return seq_render_grouped("sh_seq_render_clips", true, seq, first_sample, nsamples, out, out_sample, gains, ngains, pans, npans, master_gain, rows,
                               nrows, nblocks, automation, groups, ngroups, true);
+}
+
+int sh_seq_render_stems(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, size_t plane_samples,
+                        uint32_t nplanes, const double* gains, uint32_t ngains, const double* pans, uint32_t npans, double master_gain,
+                        const sh_seq_auto* automation, const sh_seq_group* groups, uint32_t ngroups) {
+    SH_REQUIRE_INIT();
+    static const char fn[] = "sh_seq_render_stems";
+    if (seq && !seq->ntracks)
+        return sh::set_error(SH_ERR_INVALID, "%s: a flat song has no stems: it has no tracks (sh_seq_create_tracks makes a song that has)", fn);
+    const SeqStemsArgs stems{plane_samples, nplanes};
+    return seq_render_grouped(fn, false, seq, first_sample, nsamples, out, out_sample, gains, ngains, pans, npans, master_gain, nullptr, 0, 0, automation,
+                              groups, ngroups, false, &stems);
 }
 
 int sh_seq_get_tracks(const sh_seq* seq, uint32_t* ntracks, uint32_t* nruns) {

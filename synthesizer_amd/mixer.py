@@ -32,7 +32,7 @@ from . import params
 from .oscillators import Oscillator, VoiceSpec, _pwm_widths, _table, pack_voices, time_step_weights
 from .sample import Sample
 
-__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "sequence", "compile_sequence", "compile_tracks", "CompiledSequence", "Levels", "SongLevels", "Automation", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
+__all__ = ["VoiceBank", "RealTimeMixer", "mix_samples", "sequence", "compile_sequence", "compile_tracks", "CompiledSequence", "Levels", "SongLevels", "SongStems", "Automation", "pan_gains", "compose_chain_parts", "apply_chain_parts", "mixdown_i16_banks"]
 
 
 def pan_gains(pan: float) -> Tuple[float, float]:
@@ -811,6 +811,33 @@ class SongHistory:
         return "SongHistory(%d blocks of %d frames, frames [%d, %d))" % (self.nblocks, self.block_frames, self.start_frame, self.start_frame + self.frames)
 
 
+class SongStems:
+    """The stems of a window of a song of tracks, made by ``CompiledSequence.stems``: every bus of the desk as a ``Sample`` of the window's
+    length, all from one launch into one device buffer.  ``tracks[t]``: track ``t`` as its bus takes it -- behind its gain, its fader moves
+    and its pan or pan ride; ``groups[g]``: group ``g``'s bus as the master takes it -- behind its gain, its ride and its pan or pan ride;
+    ``master``: the bytes ``render`` returns for the same arguments.  Each is exactly the samples over which ``meters=True`` of the same call
+    reads its row; a muted or skipped track or group is silence.  Every ``Sample`` is a view of the one buffer and keeps it alive on its
+    own, so it outlives this object."""
+
+    def __init__(self, tracks: Sequence[Sample], master: Sample, groups: Sequence[Sample], start_frame: int, frames: int) -> None:
+        self.tracks = list(tracks)
+        self.master = master
+        self.groups = list(groups)
+        self.start_frame = int(start_frame)
+        self.frames = int(frames)
+
+    def rows(self) -> list:
+        """all of them in plane order, which is the meter rows': the tracks, the master, the groups"""
+        return self.tracks + [self.master] + self.groups
+
+    def __len__(self) -> int:
+        return len(self.tracks) + 1 + len(self.groups)
+
+    def __repr__(self) -> str:
+        return "SongStems(%d tracks, the master, %d groups, frames [%d, %d))" % (len(self.tracks), len(self.groups), self.start_frame,
+                                                                                  self.start_frame + self.frames)
+
+
 class Automation:
     """The fader moves of a song of tracks, made by ``CompiledSequence.automation(lanes)`` and given to that song's ``render``,
     ``render_into`` and ``chunks`` as ``automation=``: per track a list of pieces ``(start_frame, end_frame, from_volume, to_volume)``,
@@ -929,6 +956,15 @@ class CompiledSequence:
     fader moves, which cannot leave the range.  A muted or skipped track or group and an idle tile count 0; a mono song fills channel
     0.  The bytes, the peaks and the sums are those of the call without ``clips``.  ``clips=True`` without ``meters="history"`` is a
     ``ValueError``.  Not built (``NotImplementedError``): overs of an event's own chain, overs with bus or pan rides.
+    The desk's STEMS: ``stems(start_frame, nframes, gains=, pans=, master=, automation=, groups=)`` hands over the SAMPLES those rows are
+    read over -- a ``SongStems`` of one ``Sample`` per track (as its bus takes it: behind its gain, its fader moves and its pan or pan
+    ride), one per group (its bus as the master takes it: saturated at every track, behind its gain, its ride and its pan or pan ride) and
+    the master (``render``'s bytes) -- from ONE launch that walks every event once, into one device buffer the ``Sample``s are views of;
+    ``stems_into`` writes the planes into a caller's buffer.  Plane ``r`` holds exactly what ``meters=True`` of the same call reads row
+    ``r`` over; a muted or skipped track or group is silence; every byte of every plane is written and none beside them.  With every desk
+    the song can make: gains, pans, master, groups, fader moves, bus rides, pan rides; widths 1 to 4 (no automation at width 3), mono
+    and stereo.  ``stem(t)`` is something else: the raw track at gain 1.0, no desk.  Not built: stems together with meters, a history or
+    overs in the same launch; ``chunks`` of stems; pre-fader stems; the raw group bus in front of its gain.
     The desk's FADER AUTOMATION: ``automation(lanes)`` takes, per track, None or a list of pieces ``(start_frame, end_frame, from_volume,
     to_volume)`` in SONG frames -- ascending, not overlapping, volumes finite and within 0.0 .. 1.0 (a static gain above 1 stays with
     ``gains``) -- and uploads them once; ``render``, ``render_into`` and ``chunks`` take the ``Automation`` it returns as
@@ -1588,6 +1624,64 @@ class CompiledSequence:
         if track < 0 or track >= self.ntracks:
             raise ValueError("CompiledSequence: track %d outside the song's %d tracks" % (track, self.ntracks))
         return self.render(start_frame, nframes, gains=[1.0 if t == track else 0.0 for t in range(self.ntracks)])
+
+    def _stems_desk(self, gains, pans, master, automation, groups) -> dict:
+        """the keywords of a stems call for N.Sequence.stems, checked by the helpers ``render`` uses -- before anything is made or launched"""
+        if self.ntracks is None:
+            raise ValueError("CompiledSequence: stems need a song of tracks (compile_tracks); this one has none")
+        gains = self._gains(gains)
+        groups = self._groups(groups)
+        return {"gains": gains, "pans": self._pans(pans), "master": self._master(master), "automation": self._automation(automation, groups),
+                "groups": groups}
+
+    @staticmethod
+    def stems_plane_frames(nframes: int, nchannels: int, samplewidth: int) -> int:
+        """The smallest plane stride, in frames, that is at least ``nframes`` and keeps every plane on the store's 16-byte grid
+        (csrc/seqstem.hpp: the stride in bytes a multiple of 16): the 16-bit kernels then store whole vectors in every plane."""
+        fb = nchannels * samplewidth
+        unit = 16 // math.gcd(16, fb)
+        return (nframes + unit - 1) // unit * unit
+
+    def stems_into(self, buf: N.DeviceBuffer, byte_offset: int, plane_frames: int, start_frame: int, nframes: int,
+                   gains: Optional[Sequence[float]] = None, pans: Optional[Sequence] = None, master: Optional[float] = None,
+                   automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> None:
+        """The stems of frames ``[start_frame, start_frame + nframes)`` into ``buf``: ``ntracks + 1 + len(groups)`` planes of ``nframes``
+        frames, plane ``r`` from ``byte_offset + r * plane_frames`` frames on (``plane_frames >= nframes``), in the meter rows' order --
+        the tracks, the master, the groups (``SongStems`` says what each holds).  Every byte of every plane is written, whatever ``buf``
+        held, and none between or around them.  One launch; the desk's keywords are ``render``'s."""
+        seq = self._handle()
+        desk = self._stems_desk(gains, pans, master, automation, groups)
+        start_frame, nframes = self._range(start_frame, nframes)
+        plane_frames = int(plane_frames)
+        if byte_offset < 0 or byte_offset % self.samplewidth:
+            raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
+        if plane_frames < nframes:
+            raise ValueError("CompiledSequence: planes %d frames apart for a window of %d frames" % (plane_frames, nframes))
+        if nframes:
+            seq.stems(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, plane_frames * self.nchannels, **desk)
+        return None
+
+    def stems(self, start_frame: int = 0, nframes: Optional[int] = None, gains: Optional[Sequence[float]] = None, pans: Optional[Sequence] = None,
+              master: Optional[float] = None, automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> SongStems:
+        """The stems of frames ``[start_frame, start_frame + nframes)`` (``nframes`` None: to the end) of a song of tracks: a
+        ``SongStems`` -- every track as its bus takes it, every group's bus as the master takes it, and the master, each a ``Sample`` of
+        the window's length -- from ONE launch that walks every event once, into one device buffer the ``Sample``s share.  The desk's
+        keywords are ``render``'s, and each stem is exactly what ``meters=True`` of the same call reads its row over.  (``stem(t)`` is
+        something else: the raw track at gain 1.0, without the desk.)"""
+        self._handle()
+        desk = self._stems_desk(gains, pans, master, automation, groups)
+        start_frame, nframes = self._range(start_frame, nframes)
+        ngroups = len(desk["groups"] or ())
+        nrows = self.ntracks + 1 + ngroups
+        names = ["%s:track %d" % (self.name, t) for t in range(self.ntracks)] + ["%s:master" % self.name] + ["%s:group %d" % (self.name, g) for g in range(ngroups)]
+        outs = [Sample(name=n, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth) for n in names]
+        if nframes:
+            plane_frames = self.stems_plane_frames(nframes, self.nchannels, self.samplewidth)
+            buf = N.DeviceBuffer(nrows * plane_frames * self._fb)
+            self.stems_into(buf, 0, plane_frames, start_frame, nframes, gains=gains, pans=pans, master=master, automation=automation, groups=groups)
+            for r, out in enumerate(outs):
+                out._set_device(buf.view(r * plane_frames * self._fb, nframes * self._fb), nframes * self._fb)
+        return SongStems(outs[:self.ntracks], outs[self.ntracks], outs[self.ntracks + 1:], start_frame, nframes)
 
     def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None, meters: bool = False, pans: Optional[Sequence] = None,
                master: Optional[float] = None, automation: Optional[Automation] = None, groups: Optional[Sequence] = None,

@@ -129,7 +129,14 @@ checkout of the parent commit> python tools/sequence_ab.py --history is the pare
 events on the stream, of the whole song and of a 4096-frame window, for: (a) render_into(meters="history", clips=True, ...); (c) the same
 call without clips; and meters=True.  On a tree without clips= only (c) and meters=True run: SEQUENCE_AB_TREE=<a built checkout of the parent
 commit> python tools/sequence_ab.py --clips is the parent's own figure for both, row (d).  --clips-trace: (a) and (c) a few times each and
-nothing else, for a kernel trace in a run of its own."""
+nothing else, for a kernel trace in a run of its own.
+--stems: the song of --pans (8 tracks, 3 groups, bus rides and pan rides) and the samples of every bus.  Wall time with a device
+synchronise, medians, and the time between two events on the stream, of the whole song and of a 4096-frame window, for: (a) one
+stems_into, 12 planes from one launch; (b) the caller's way -- 12 renders with everything else muted, the tracks through a second desk and
+a second Automation that holds their lanes alone, the groups through a third one without the master's lane -- into the same planes, held
+to (a)'s bytes first; (c) render_into with the same desk.  On a tree without stems_into only (c) runs: SEQUENCE_AB_TREE=<a built checkout
+of the parent commit> python tools/sequence_ab.py --stems is the parent's own figure for (c), row (d).  --stems-trace: (a), (b) and (c)
+five times each and nothing else, for a kernel trace in a run of its own."""
 import audioop
 import os
 import sys
@@ -139,7 +146,7 @@ from pathlib import Path
 import numpy as np
 
 # the yardstick of --plan, --tracks, --desk, --auto, --groups, --buses, --pans and --history is another checkout's package (SEQUENCE_AB_TREE); every other mode measures this tree, whatever the environment says
-sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:] or "--groups" in sys.argv[1:] or "--buses" in sys.argv[1:] or "--pans" in sys.argv[1:] or "--history" in sys.argv[1:] or "--clips" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
+sys.path.insert(0, (("--plan" in sys.argv[1:] or "--tracks" in sys.argv[1:] or "--desk" in sys.argv[1:] or "--auto" in sys.argv[1:] or "--groups" in sys.argv[1:] or "--buses" in sys.argv[1:] or "--pans" in sys.argv[1:] or "--history" in sys.argv[1:] or "--clips" in sys.argv[1:] or "--stems" in sys.argv[1:]) and os.environ.get("SEQUENCE_AB_TREE")) or str(Path(__file__).resolve().parent.parent))
 from synthesizer_amd import _native as N  # noqa: E402
 from synthesizer_amd import mixer  # noqa: E402
 from synthesizer_amd.sample import Sample  # noqa: E402
@@ -1740,6 +1747,99 @@ def clips_main(trace=False):
         bus.close()
 
 
+def stems_main(trace=False):
+    """--stems: every bus of the desk from one launch, on the song of --pans (8 tracks, 3 groups, bus lanes and pan lanes).  (a) one
+    stems_into of the whole song and of a 4096-frame window; (b) the caller's way: one render per row with everything else muted -- a track
+    through a second desk (no groups, no master gain) and a second Automation holding the tracks' lanes alone, a group through a third
+    Automation without the master's lane, the master as it is -- into the same planes, held to (a)'s bytes first; (c) render_into with the
+    same desk.  Wall time with a device synchronise, medians of 15.  A tree without stems_into runs (c) alone: the parent's figure, row (d).
+    --stems-trace: each call five times and nothing else, for a kernel trace."""
+    N.ensure_init(0)
+    info = N.device_info()
+    has = hasattr(mixer.CompiledSequence, "stems_into")
+    print("sequence_stems_ab: SYNTHHIP_SEQ_ALIGN=%s  %s  stems_into: %s" % (os.environ.get("SYNTHHIP_SEQ_ALIGN", "0"), info["name"] or info["arch"],
+          "yes" if has else "no (the yardstick: (c) alone)"), flush=True)
+    win, ntracks = 4096, len(TRACK_GAINS)
+    desk = dict(gains=TRACK_GAINS, pans=DESK_PANS, master=DESK_MASTER, groups=GROUPS)
+    nrows = ntracks + 1 + len(GROUPS)
+    fmt = lambda v: " ".join("%.4f" % x for x in v)        # noqa: E731
+    for nevents in (4096, 32768):
+        what, nch, evs = meters_songs(nevents)[0]
+        fb = nch * WIDTH
+        bus = mixer.compile_tracks([evs[t::ntracks] for t in range(ntracks)], RATE, nch, WIDTH)
+        frames = bus.frames
+        glanes, mlane = bus_lanes(frames)
+        tpans, gpans = pan_lanes(ntracks)
+        auto = bus.automation([None] * ntracks, master=mlane, groups=glanes, pans=tpans, group_pans=gpans)
+        at = (22 * RATE) // win * win + 3                      # a window three frames off the tile grid, inside the sweeps
+        out = N.DeviceBuffer(frames * fb + 16)
+        c_whole = lambda: bus.render_into(out, 0, 0, frames, automation=auto, **desk)      # noqa: E731
+        c_win = lambda: bus.render_into(out, 0, at, win, automation=auto, **desk)           # noqa: E731
+        head = "stems song 120 s, %5d events, %s, %d tracks, %d groups, %d rows, level %s, %d frames   " % (
+            nevents, what, ntracks, len(GROUPS), nrows, bus.level, frames)
+        if not has:
+            if not trace:
+                print(head + "(c) render_into(gains=, pans=, master=, groups=, automation=): whole song, wall with a synchronise, median %.4f ms, between "
+                      "two events on the stream, five medians of 15: %s ms; a window of %d frames, wall %.4f ms, events %s ms"
+                      % (median_wall(c_whole, 2, 15), fmt(five_medians(c_whole)), win, median_wall(c_win, 2, 15), fmt(five_medians(c_win))), flush=True)
+            auto.close()
+            bus.close()
+            continue
+        plane = bus.stems_plane_frames(frames, nch, WIDTH)
+        wplane = bus.stems_plane_frames(win, nch, WIDTH)
+        planes = N.DeviceBuffer(nrows * plane * fb)
+        theirs = N.DeviceBuffer(nrows * plane * fb)
+        a_whole = lambda: bus.stems_into(planes, 0, plane, 0, frames, automation=auto, **desk)     # noqa: E731
+        a_win = lambda: bus.stems_into(planes, 0, wplane, at, win, automation=auto, **desk)         # noqa: E731
+        # (b): the second desk and the second and third Automation a caller has to build
+        tracks_only = bus.automation([None] * ntracks, pans=tpans)
+        no_master = bus.automation([None] * ntracks, groups=glanes, pans=tpans, group_pans=gpans)
+
+        def caller(a, n, stride):
+            for t in range(ntracks):                            # a track as its bus takes it: no groups, no master gain, its own lanes
+                bus.render_into(theirs, t * stride * fb, a, n, gains=[TRACK_GAINS[t] if u == t else 0.0 for u in range(ntracks)], pans=DESK_PANS,
+                                automation=tracks_only)
+            bus.render_into(theirs, ntracks * stride * fb, a, n, automation=auto, **desk)
+            for k, (first, end, _g, _pan) in enumerate(GROUPS):  # a group as the master takes it: its tracks alone, no master gain, no master ride
+                bus.render_into(theirs, (ntracks + 1 + k) * stride * fb, a, n, gains=[TRACK_GAINS[u] if first <= u < end else 0.0 for u in range(ntracks)],
+                                pans=DESK_PANS, groups=GROUPS, automation=no_master)
+        b_whole = lambda: caller(0, frames, plane)              # noqa: E731
+        b_win = lambda: caller(at, win, wplane)                 # noqa: E731
+        if trace:
+            for _ in range(5):
+                a_whole(), b_whole(), c_whole(), a_win(), b_win(), c_win()
+            N.sync()
+        else:
+            parity = True
+            for mine, other, n, stride in ((a_win, b_win, win, wplane), (a_whole, b_whole, frames, plane)):
+                planes.zero()
+                theirs.zero()
+                mine()
+                other()
+                N.sync()
+                size = ((nrows - 1) * stride + n) * fb
+                step = 1 << 26
+                for off in range(0, size, step):
+                    parity = parity and planes.download_bytes(min(step, size - off), off) == theirs.download_bytes(min(step, size - off), off)
+            c_whole()                                           # (planes holds (a)'s whole song: its master plane against the render's bytes)
+            N.sync()
+            head_bytes = min(1 << 24, frames * fb)
+            master_same = planes.download_bytes(head_bytes, ntracks * plane * fb) == out.download_bytes(head_bytes)
+            rows =[(name, median_wall(w, 2, 15), five_medians(w), median_wall(x, 2, 15), five_medians(x)) for name, w, x in (
+                ("(a) stems_into: %d planes, one launch" % nrows, a_whole, a_win), ("(b) %d renders with mutes, a second desk, three Automations" % nrows, b_whole, b_win),
+                ("(c) render_into with the same desk", c_whole, c_win))]
+            text = "   ".join("%s: whole song, wall with a synchronise, median %.4f ms, between two events on the stream, five medians of 15: %s ms; a window "
+                              "of %d frames, wall %.4f ms, events %s ms" % (name, w, fmt(wd), win, x, fmt(xd)) for name, w, wd, x, xd in rows)
+            print(head + text + "   (a) / (b) whole %.3f, window %.3f   (a) / (c) whole %.3f, window %.3f   bytes written by (a): whole %.1f MB, window %.3f MB   "
+                  "(b)'s bytes against (a)'s, whole and window, every plane: %s   (a)'s master plane against (c)'s bytes: %s"
+                  % (rows[0][1] / rows[1][1], rows[0][3] / rows[1][3], rows[0][1] / rows[2][1], rows[0][3] / rows[2][3], nrows * frames * fb / 1e6,
+                     nrows * win * fb / 1e6, "ok" if parity else "FAILED", "ok" if master_same else "FAILED"), flush=True)
+            assert parity and master_same
+        for h in (tracks_only, no_master, auto):
+            h.close()
+        bus.close()
+
+
 def median_wall(fn, warm, passes):
     for _ in range(warm):
         fn()
@@ -1810,4 +1910,4 @@ def main():
 
 
 if __name__ == "__main__":
-    clips_main("--clips-trace" in sys.argv[1:]) if "--clips" in sys.argv[1:] or "--clips-trace" in sys.argv[1:] else history_main() if "--history" in sys.argv[1:] else pans_main() if "--pans" in sys.argv[1:] else buses_main() if "--buses" in sys.argv[1:] else groups_main() if "--groups" in sys.argv[1:] else auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
+    stems_main("--stems-trace" in sys.argv[1:]) if "--stems" in sys.argv[1:] or "--stems-trace" in sys.argv[1:] else clips_main("--clips-trace" in sys.argv[1:]) if "--clips" in sys.argv[1:] or "--clips-trace" in sys.argv[1:] else history_main() if "--history" in sys.argv[1:] else pans_main() if "--pans" in sys.argv[1:] else buses_main() if "--buses" in sys.argv[1:] else groups_main() if "--groups" in sys.argv[1:] else auto_main() if "--auto" in sys.argv[1:] or "--auto-trace" in sys.argv[1:] else desk_main() if "--desk" in sys.argv[1:] else meters_main() if "--meters" in sys.argv[1:] or "--meters-trace" in sys.argv[1:] else tracks_main() if "--tracks" in sys.argv[1:] else plan_main() if "--plan" in sys.argv[1:] else chan_main() if "--channels" in sys.argv[1:] else rev_main() if "--reverse" in sys.argv[1:] else loop_main() if "--loop" in sys.argv[1:] else env_main() if "--env" in sys.argv[1:] else pan_main() if "--pan" in sys.argv[1:] else sampler_main() if "--sampler" in sys.argv[1:] else main()
