@@ -50,43 +50,23 @@
 // copies nothing; a window of the song holds the bytes of that slice of the whole song, since every track sample is its own fold.
 // A song of TRACKS (sh_seq_create_tracks) is rendered by the BUS = true instantiations of the same three templates, a gain per track in
 // the kernel arguments (sh_seq_render_gains): seq_runs, written once, walks the runs of the tile -- the kernel's schedule over a run's
-// events into a sub-mix, the sub-mix by its gain, a hook, the saturating add into the master.  With the metering bus, SeqBusM, the hook
+// events into a sub-mix, the sub-mix by its gain, a hook, the saturating add into the master.  With a metering bus (METERS) the hook
 // reduces one row of levels per track, post-fader, and the same launch one for the master, into a table the handle owns
 // (sh_seq_render_meters; seqmeter.hpp); seq_window_bus is what a window kernel does with either bus.  On the host one launcher,
-// seq_window_launch, forwards the bus (none, SeqBus or SeqBusM) as the kernels' trailing pack, and seq_with_level turns the level a
-// handle holds into a template argument.  The DESK buses, SeqBusD and SeqBusDM, are the two buses again with a pan pot per track and a
-// master fader, by value in the kernel arguments like the gains (sh_seq_render_desk): in seq_runs the sub-mix by its gain, THEN by its
-// pan factors (even samples the left one, odd ones the right one: a stereo sample's Sample.stereo), then the hook and the add; behind the
-// last run the master by the master's gain, once, in front of its meter row and the store.  The AUTOMATION buses, SeqBusA and SeqBusAM,
-// are the desk buses again with a table of fader moves per track (seqauto.hpp; sh_seq_auto_create uploads it once, sh_seq_render_auto
-// passes its two pointers by value): in seq_runs the sub-mix by its gain, THEN through the track's segments at its song positions
-// (int(x * f), the fade's truncation), then the pan, the hook and the add.  The GROUP buses, SeqBusG and SeqBusGM (width 3: SeqBusG3,
-// SeqBusGM3), are the whole desk again with a table of group buses by value (seqgroup.hpp; sh_seq_render_groups): in seq_runs a third
-// accumulator between sub and acc takes the tracks of the open group and is closed -- the group's gain, its pan, the hook for its row,
-// the add into the master -- in front of the first run that is not of the group and behind the last run.  The buses that RIDE, SeqBusR and
-// SeqBusRM (widths 1, 2 and 4), are the group buses again with fader moves on the two bus levels (sh_seq_auto_create_buses: the lanes of
-// the master and of the groups behind the tracks' in the automation's table, no kernel argument of their own): in the close the group's
-// bus through its lane between its gain and its pan, in seq_window_bus the master through its lane behind the master's gain; seq_ride
-// states the shaping once for track, group and master.  The buses that PAN, SeqBusP and SeqBusPM (widths 1, 2 and 4), are the buses that
-// ride again with pan moves (sh_seq_auto_create_pans; seqpan.hpp): a track's sub-mix and a group's bus pass a pan lane of the same table
-// where they passed their static pan -- seq_pan_ride, once for both; still no kernel argument of their own.  The HISTORY buses, SeqBusGH
-// (width 3: SeqBusGH3), are the metering group buses again whose workgroups keep their rows: the table a workgroup reduced in LDS is
-// stored as the block of its song tile in a table of blocks (sh_seq_render_history; seqhist.hpp), by plain stores -- seq_hist_end.  The
-// buses that COUNT OVERS, SeqBusGC (width 3: SeqBusGC3), are the history buses again whose lanes fold into COUNTING accumulators -- the
-// samples and one sticky flag per sample, set where a step of the bus's own arithmetic was clamped (seqclip.hpp: an add whose exact sum
-// leaves the range, a multiply whose floor does) -- through the same schedules and the same seq_runs, which are generic in the
-// accumulator's type; a row carries the count of flagged samples behind its levels (sh_seq_render_clips).  The STEMS buses, SeqBusGS,
-// SeqBusRS and SeqBusPS (width 3: SeqBusGS3), are the group buses, the buses that ride and the buses that pan again -- not the metering
-// ones: no table, no barrier -- whose lanes STORE every bus where a metering bus reduces it (sh_seq_render_stems; seqstem.hpp): the
-// kernels hand seq_stems_bus a store that takes a destination and the samples, seq_runs' hook stores a track's or a group's samples into plane `row` of the
-// caller's buffer -- row * stride bytes behind plane 0, the stride being the one new kernel argument, 64 bits --, the master goes to plane
-// ntracks, and behind the runs every row that no hook stored in this tile gets the lane's samples as zeros, so that each sample of each
-// plane has one writer and nothing is zeroed in front of the launch.
+// seq_window_launch, forwards the bus as the kernels' trailing pack: none, or a SeqBusOf<F> -- ONE bus type, F the set of FEATURES of
+// seqbus.hpp, whose route() says which set a call takes; seq_with_level turns the level a handle holds into a template argument and
+// seq_with_bus the set of features.  What each feature adds to this chain is stated once, above its part or its function: the DESK (a
+// pan pot per track and a master fader: SeqDesk), AUTOMATION (fader moves per track: SeqAuto), GROUPS (a third accumulator between sub
+// and acc, closed into the master: SeqGroups), RIDES and PANS (moves on the bus levels and of the pans, lanes of the automation's table
+// and no kernel argument: seq_ride, seq_pan_ride), the HISTORY (the rows a workgroup reduced, kept per song tile: seq_hist_end), the
+// OVERS (counting accumulators through the same schedules and the same seq_runs, which are generic in the accumulator's type) and the
+// STEMS (the lanes STORE every bus where a metering bus reduces it: SeqStems, seq_stems_bus).
 #include "common.hpp"
 #include "chain.hpp"
 #include "pcmdev.hpp"
 #include "ratecv.hpp"
 #include "seqauto.hpp"
+#include "seqbus.hpp"
 #include "seqclip.hpp"
 #include "seqpan.hpp"
 #include "seqenv.hpp"
@@ -101,6 +81,7 @@
 #include <string.h>
 #include <new>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -641,7 +622,7 @@ __device__ __forceinline__ void seq_fold8(short8v& acc, const short8v x, const d
     acc = __builtin_elementwise_add_sat(acc, seq_scale8(x, factor));
 }
 
-// A COUNTING accumulator (seqclip.hpp; the buses that count overs, SeqBusGC): a lane's samples and one sticky over-flag per sample -- 0 or
+// A COUNTING accumulator (seqclip.hpp; the buses that count overs, shb::CLIPS): a lane's samples and one sticky over-flag per sample -- 0 or
 // -1, a vector comparison's lanes, at 16 bits; bit j of a word at widths 1, 3, 4.  The schedules below are generic in the accumulator's
 // type, so either kind passes through the same schedule text.
 typedef unsigned short ushort8v __attribute__((ext_vector_type(8)));
@@ -978,10 +959,17 @@ struct SeqBus {
     SeqGains        gains;
 };
 // The window templates take the bus as a trailing parameter PACK -- empty for BUS = false, whose kernels so keep the argument list, the
-// kernel-argument offsets and the instructions they had; one SeqBus for BUS = true.
+// kernel-argument offsets and the instructions they had; one SeqBusOf<F> for BUS = true.
 static_assert(sizeof(shq::Run) == 8 && sizeof(SeqGains) == 256, "a run is one 8-byte scalar load, the gains 256 bytes of kernel arguments");
 
-// The DESK (sh_seq_render_desk): a pan pot per track and a master fader on either bus, by value in the kernel arguments as the gains
+// The METERS' part (shb::METERS; sh_seq_render_meters -- what the kernels do with it stands in front of seq_meter_begin): 16 bytes of
+// kernel arguments behind the bus.
+struct SeqMeters {
+    shmt::Row* meters;                     // ntracks + 1 rows, zeroed on the stream in front of the launch; row ntracks: the master
+    uint32_t  ntracks, nch;               // nch: the song's channels (2: sample s is channel s & 1; otherwise all are channel 0)
+};
+
+// The DESK (shb::DESK; sh_seq_render_desk): a pan pot per track and a master fader on either bus, by value in the kernel arguments as the gains
 // are and read at wave-uniform indices as they are -- 520 more bytes of arguments, nothing uploaded.  pan[2 t] and pan[2 t + 1]: what
 // Sample.stereo(left, right) of a STEREO sample takes, applied to track t's sub-mix BEHIND its gain (two roundings, not one product):
 // even samples fbound(x * left), odd ones fbound(x * right); a factor of exactly 1.0: none; both exactly 0.0: the track's events are
@@ -990,11 +978,8 @@ struct SeqDesk {
     double pan[2 * shq::MAX_TRACKS];
     double master;
 };
-struct SeqBusD : SeqBus, SeqDesk {};
-template <typename Bus> constexpr bool SEQ_DESK = std::is_base_of<SeqDesk, Bus>::value;
-static_assert(sizeof(SeqDesk) == 520 && sizeof(SeqBusD) == sizeof(SeqBus) + sizeof(SeqDesk), "the desk: 520 bytes of kernel arguments behind the bus");
 
-// AUTOMATION (sh_seq_render_auto): fader moves per track on either desk bus -- a table a handle of its own keeps on the device
+// AUTOMATION (shb::AUTO; sh_seq_render_auto): fader moves per track on a desk bus -- a table a handle of its own keeps on the device
 // (sh_seq_auto), its two pointers by value in the kernel arguments: a render uploads nothing.  Track t's segments are
 // asegs[afirst[t] .. afirst[t + 1]) (she::Seg in SONG samples, the ends ascending, plain segments in the gaps), applied to the track's
 // sub-mix BEHIND its gain and IN FRONT of its pan: sample s of a segment becomes int(x * ((s - origin) * slope / numsamples + offset)),
@@ -1005,10 +990,8 @@ struct SeqAuto {
     const she::Seg* asegs;
     const uint32_t* afirst;               // ntracks + 1 offsets into asegs
 };
-struct SeqBusA : SeqBusD, SeqAuto {};
-template <typename... Bus> constexpr bool SEQ_AUTO = (std::is_base_of<SeqAuto, Bus>::value || ...);
 
-// GROUP BUSES (sh_seq_render_groups): runs of consecutive tracks mixed into a bus of their own between the track and the master -- the
+// GROUP BUSES (shb::GROUPS; sh_seq_render_groups): runs of consecutive tracks mixed into a bus of their own between the track and the master -- the
 // table of seqgroup.hpp by value in the kernel arguments, 232 more bytes, read at wave-uniform indices as the gains are; a render still
 // uploads nothing.  A bus lane keeps a THIRD accumulator, grp, between sub and acc: a track of a group is added, saturating, into grp
 // and not into acc; where the next run's track belongs to another group or to none, and behind the last run, the open group is CLOSED:
@@ -1017,49 +1000,61 @@ template <typename... Bus> constexpr bool SEQ_AUTO = (std::is_base_of<SeqAuto, B
 // order, so a group enters the master where its last track stands; tracks without a run in the tile add zeros, and a group without one
 // never opens (fbound(0 * g) == 0).  A group at gain 0.0 or pan (0.0, 0.0) skips its tracks' events as a muted track does.  These
 // buses carry the WHOLE desk so that the kernel count does not double: at widths 1, 2 and 4 the automation's two pointers as well,
-// NULL meaning no moves (a uniform branch); width 3, which has no automation, derives them from the desk buses.
+// NULL meaning no moves (a uniform branch); width 3, which has no automation, goes without them (shb::valid_at).
 struct SeqGroups { shg::Table groups; };
-struct SeqBusG : SeqBusA, SeqGroups {};
-struct SeqBusG3 : SeqBusD, SeqGroups {};
-template <typename... Bus> constexpr bool SEQ_GROUPS = (std::is_base_of<SeqGroups, Bus>::value || ...);
-static_assert(shg::MAX_TRACKS == shq::MAX_TRACKS && sizeof(SeqBusG) == sizeof(SeqBusA) + sizeof(shg::Table), "the groups: 232 bytes of kernel arguments behind the bus");
 
-// BUS RIDES (sh_seq_auto_create_buses): fader moves on the two bus levels -- a group's bus shaped through a lane of its own BEHIND the
+// BUS RIDES (shb::RIDES; sh_seq_auto_create_buses): fader moves on the two bus levels -- a group's bus shaped through a lane of its own BEHIND the
 // group's gain and IN FRONT of its pan, the master through one BEHIND the master's gain, over the saturated sum in both places.  No new
 // kernel argument: the lanes stand in the automation's table in the meter table's row order (seqauto.hpp), the master's at
 // groups.row0 - 1 and group g's at groups.row0 + g, behind the tracks', and index the afirst / asegs that a group bus carries anyway.
 // The table of such a handle always has an offset for every one of the MAX_GROUPS group lanes, so a render may name more groups than
-// the handle rides.  A tag, and two more bus types at widths 1, 2 and 4; a handle without a segment on a bus lane never gets here.
-struct SeqRides {};
-struct SeqBusR : SeqBusG, SeqRides {};
-template <typename... Bus> constexpr bool SEQ_RIDES = (std::is_base_of<SeqRides, Bus>::value || ...);
-static_assert(sizeof(SeqBusR) == sizeof(SeqBusG) && sha::MAX_GROUP_LANES == shg::MAX_GROUPS, "the rides: no kernel argument of their own");
+// the handle rides.  A bit and nothing else, on the group buses of widths 1, 2 and 4, with and without meters; a handle without a segment
+// on a bus lane never gets here (shb::route).
 
-// PAN RIDES (sh_seq_auto_create_pans): pan moves of a track and of a group's bus, Sample.pan(lfo=...)'s expression per frame (seqpan.hpp),
+// PAN RIDES (shb::PANS; sh_seq_auto_create_pans): pan moves of a track and of a group's bus, Sample.pan(lfo=...)'s expression per frame (seqpan.hpp),
 // where a pan lane has a move; elsewhere the static factors as ever.  No new kernel argument either: the pan lanes stand in the same
 // table behind the fader lanes' offsets -- track t's at shp::track_lane(row0, t), group g's at shp::group_lane(row0, g) -- and their
-// segments behind the fader lanes' segments.  A tag, and two more bus types at widths 1, 2 and 4 on top of the buses that ride; a handle
-// without a pan move never gets here.
-struct SeqPans {};
-struct SeqBusP : SeqBusR, SeqPans {};
-template <typename... Bus> constexpr bool SEQ_PANS = (std::is_base_of<SeqPans, Bus>::value || ...);
-static_assert(sizeof(SeqBusP) == sizeof(SeqBusG) && SH_ENV_PAN == shp::PAN, "the pan rides: no kernel argument of their own");
+// segments behind the fader lanes' segments.  A bit and nothing else, on top of the buses that ride; a handle without a pan move never
+// gets here.
 
-// The STEMS buses (sh_seq_render_stems; seqstem.hpp): the group buses, the buses that ride and the buses that pan again -- the whole desk,
+// The STEMS (shb::STEMS; sh_seq_render_stems; seqstem.hpp): the group buses, the buses that ride and the buses that pan again -- the whole desk,
 // NULL pointers meaning no moves, the empty table no groups -- whose lanes STORE every bus where a metering bus reduces it: track t's
 // samples as seq_runs' hook receives them into plane t, a group's into plane groups.row0 + g, the master's into plane groups.row0 - 1,
-// plane r standing r * stride BYTES behind plane 0 (64-bit).  A tag that carries the stride -- the one new kernel argument -- and one bus
-// type on each of SeqBusG, SeqBusR and SeqBusP (widths 1, 2 and 4: a table without bus lanes or without pan lanes must not reach a kernel
-// that reads them) and one on SeqBusG3 (width 3).  They are NOT metering buses: no table, no barrier, lanes outside the window leave.
+// plane r standing r * stride BYTES behind plane 0 (64-bit).  A part that carries the stride -- the one new kernel argument -- on the
+// group bus, the bus that rides and the bus that pans (widths 1, 2 and 4: a table without bus lanes or without pan lanes must not reach a
+// kernel that reads them) and on width 3's group bus.  They are NOT metering buses: no table, no barrier, lanes outside the window leave.
 struct SeqStems { uint64_t stride; };
-struct SeqBusGS : SeqBusG, SeqStems {};
-struct SeqBusRS : SeqBusR, SeqStems {};
-struct SeqBusPS : SeqBusP, SeqStems {};
-struct SeqBusGS3 : SeqBusG3, SeqStems {};
-template <typename... Bus> constexpr bool SEQ_STEMS = (std::is_base_of<SeqStems, Bus>::value || ...);
-static_assert(sizeof(SeqBusGS) == sizeof(SeqBusG) + 8 && sizeof(SeqBusPS) == sizeof(SeqBusG) + 8 && sizeof(SeqBusGS3) == sizeof(SeqBusG3) + 8 &&
-              shst::MAX_ROWS == shq::MAX_TRACKS + 1 + shg::MAX_GROUPS && shst::MAX_ROWS <= 64,
-              "the stems: the stride, 8 bytes of kernel arguments behind the bus; a bit of one 64-bit mask per plane");
+
+// ONE bus type for every set of features F (seqbus.hpp): the plain bus, then the parts F has in this one order -- the layout of the
+// kernel arguments.  A part F lacks is an empty base of a type of its own, which takes no room, so the parts behind it stand where they
+// stood; RIDES, PANS, HISTORY and CLIPS are bits and nothing else.  SEQ_DESK ... SEQ_CLIPS read the bits (an empty pack: none).
+template <uint32_t BIT> struct SeqNoPart {};
+template <uint32_t F, uint32_t BIT, typename Part> using SeqPart = typename std::conditional<(F & BIT) != 0, Part, SeqNoPart<BIT>>::type;
+template <uint32_t F>
+struct SeqBusOf : SeqBus, SeqPart<F, shb::METERS, SeqMeters>, SeqPart<F, shb::DESK, SeqDesk>, SeqPart<F, shb::AUTO, SeqAuto>,
+                  SeqPart<F, shb::GROUPS, SeqGroups>, SeqPart<F, shb::STEMS, SeqStems> {
+    static constexpr uint32_t FEATURES = F;
+};
+template <typename... Bus> constexpr uint32_t SEQ_MASK = (0u | ... | Bus::FEATURES);
+template <typename... Bus> constexpr bool SEQ_METERS = (SEQ_MASK<Bus...> & shb::METERS) != 0;
+template <typename... Bus> constexpr bool SEQ_DESK = (SEQ_MASK<Bus...> & shb::DESK) != 0;
+template <typename... Bus> constexpr bool SEQ_AUTO = (SEQ_MASK<Bus...> & shb::AUTO) != 0;
+template <typename... Bus> constexpr bool SEQ_GROUPS = (SEQ_MASK<Bus...> & shb::GROUPS) != 0;
+template <typename... Bus> constexpr bool SEQ_RIDES = (SEQ_MASK<Bus...> & shb::RIDES) != 0;
+template <typename... Bus> constexpr bool SEQ_PANS = (SEQ_MASK<Bus...> & shb::PANS) != 0;
+template <typename... Bus> constexpr bool SEQ_HISTORY = (SEQ_MASK<Bus...> & shb::HISTORY) != 0;
+template <typename... Bus> constexpr bool SEQ_CLIPS = (SEQ_MASK<Bus...> & shb::CLIPS) != 0;
+template <typename... Bus> constexpr bool SEQ_STEMS = (SEQ_MASK<Bus...> & shb::STEMS) != 0;
+// every route's kernel arguments: the 272 bytes of the plain bus, then the parts it has -- the meters' 16, the desk's 520, the automation's 16,
+// the groups' 232, the stems' 8 -- each behind the one before it and nothing between them; rides, pan rides, a history and overs add none
+constexpr size_t seq_bus_bytes(uint32_t f) {
+    return 272 + (f & shb::METERS ? 16 : 0) + (f & shb::DESK ? 520 : 0) + (f & shb::AUTO ? 16 : 0) + (f & shb::GROUPS ? 232 : 0) + (f & shb::STEMS ? 8 : 0);
+}
+template <uint32_t... I> constexpr bool seq_bus_layouts(std::integer_sequence<uint32_t, I...>) { return ((sizeof(SeqBusOf<shb::ROUTES[I]>) == seq_bus_bytes(shb::ROUTES[I])) && ...); }
+static_assert(seq_bus_layouts(std::make_integer_sequence<uint32_t, shb::NROUTES>()) && sizeof(SeqBus) == 272 && sizeof(SeqMeters) == 16 && sizeof(SeqDesk) == 520 &&
+              sizeof(SeqAuto) == 16 && sizeof(SeqGroups) == 232 && sizeof(SeqStems) == 8, "every bus is its parts, in the one order, and nothing else");
+static_assert(shg::MAX_TRACKS == shq::MAX_TRACKS && sha::MAX_GROUP_LANES == shg::MAX_GROUPS && SH_ENV_PAN == shp::PAN &&
+              shst::MAX_ROWS == shq::MAX_TRACKS + 1 + shg::MAX_GROUPS && shst::MAX_ROWS <= 64, "the lanes of the rides; the stems: a bit of one 64-bit mask per plane");
 
 // a lane's accumulator: eight packed samples at 16 bits, four 64-bit sums at the other widths
 template <int WIDTH> struct SeqAcc { typedef llong4v type; };
@@ -1126,7 +1121,7 @@ __device__ __forceinline__ void seq_master(SeqAccCW& acc, const double gain) {
     for (int j = 0; j < 4; ++j) acc.v[j] = seq_gain_w<WIDTH>(acc, j, gain);
 }
 
-// "Shape this accumulator through lane `lane` of the automation's table", stated once for the buses that ride (SeqBusR, SeqBusRM) -- a
+// "Shape this accumulator through lane `lane` of the automation's table", stated once for the buses that ride (shb::RIDES) -- a
 // track's sub-mix, a group's bus and the master: a lane's samples of tile k at their SONG positions, one binary search at the tile's first
 // sample (sha::find) and one walk from there (sha::shape_from); everything but x and the lane's position is wave-uniform, and behind the
 // lane's last segment nothing is shaped.  x holds saturated samples of the width, so they pass through int unchanged.
@@ -1150,7 +1145,7 @@ __device__ __forceinline__ void seq_ride(typename SeqAcc<WIDTH>::type& x, const 
     }
 }
 
-// "Pass this accumulator through pan lane `lane` of the automation's table", stated once for the buses that pan (SeqBusP, SeqBusPM) -- a
+// "Pass this accumulator through pan lane `lane` of the automation's table", stated once for the buses that pan (shb::PANS) -- a
 // track's sub-mix and a group's bus, where their static pan stands: one binary search at the tile's first sample, then one of
 // shp::shape_from's uniform paths.  false: no move reaches into the tile and NOTHING was done -- the caller applies the static factors
 // with the code it always had (seq_pan8, seq_mul_add_w); true: x is panned, by the move where one holds the frame and by left / right
@@ -1360,7 +1355,7 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
     }
 }
 
-// ---- level meters from the same launch (sh_seq_render_meters): a second bus type, SeqBusM ------------------------------------------------
+// ---- level meters from the same launch (sh_seq_render_meters): the buses with shb::METERS ---------------------------------------------
 // A metered render stores the bytes of the render with gains and, from the values the lane holds anyway, one row of levels (seqmeter.hpp:
 // per channel the peak and the exact sum of squares) per track, post-fader -- over mul(sub, gain), formed just before it is added into
 // acc -- and one for the master, over acc at the store; only samples inside [lo, hi) count.  The reduction (the guide's: partials on chip,
@@ -1372,50 +1367,20 @@ __device__ __forceinline__ void seq_runs(const Bus& bus, uint32_t k, uint32_t e,
 // in the window skips the runs (uniform: the shuffles see whole waves), and inside a wave the lanes outside fold their samples like the
 // others, count none of them (seqmeter's cut) and store none (seq_window_store8's).  Their fetches are the ones lanes beside an event
 // make in any tile: nothing outside an event's samples is read.  A muted track's run is skipped as before: its row stays zero.
-struct SeqBusM : SeqBus {
-    shmt::Row* meters;                     // ntracks + 1 rows, zeroed on the stream in front of the launch; row ntracks: the master
-    uint32_t  ntracks, nch;               // nch: the song's channels (2: sample s is channel s & 1; otherwise all are channel 0)
-};
-struct SeqBusDM : SeqBusM, SeqDesk {};    // the desk with meters: a track's row post-fader and post-pan, the master's over the stored bytes
-struct SeqBusAM : SeqBusDM, SeqAuto {};   // and with automation: a track's row behind its fader moves as well
-template <typename... Bus> struct SeqMetered : std::false_type {};
-template <> struct SeqMetered<SeqBusM> : std::true_type {};
-template <> struct SeqMetered<SeqBusDM> : std::true_type {};
-template <> struct SeqMetered<SeqBusAM> : std::true_type {};
-// The group buses with meters: ntracks + 1 + ngroups rows -- tracks and the master where they were, group g in row ntracks + 1 + g, over
-// what the master takes of it (behind its gain and pan); a track's row stays what its bus takes of it.  A table of their own size in LDS.
-struct SeqBusGM : SeqBusAM, SeqGroups {};
-struct SeqBusGM3 : SeqBusDM, SeqGroups {};
-template <> struct SeqMetered<SeqBusGM> : std::true_type {};
-template <> struct SeqMetered<SeqBusGM3> : std::true_type {};
-struct SeqBusRM : SeqBusGM, SeqRides {};  // the buses that ride, with meters: a group's row behind its ride and pan, the master's behind its ride
-template <> struct SeqMetered<SeqBusRM> : std::true_type {};
-struct SeqBusPM : SeqBusRM, SeqPans {};   // the buses that pan, with meters: a track's row behind its pan ride, a group's behind its ride and its pan ride
-template <> struct SeqMetered<SeqBusPM> : std::true_type {};
-// The HISTORY buses (sh_seq_render_history; seqhist.hpp): the metering group buses again -- the whole desk, NULL pointers meaning no moves,
-// the empty table no groups -- whose workgroups KEEP their table instead of merging it: bus.meters points at a table of blocks, one per
-// song tile of the window, and the workgroup that folds tile k stores its ntracks + 1 + groups.n rows as block k - lo / TILE.  No new
-// kernel argument: the first tile and the row count are in the kernel already.  A tag, and one bus type at widths 1, 2 and 4 and one at
-// width 3; the buses that ride and pan have none.
-struct SeqHistory {};
-struct SeqBusGH : SeqBusGM, SeqHistory {};
-struct SeqBusGH3 : SeqBusGM3, SeqHistory {};
-template <> struct SeqMetered<SeqBusGH> : std::true_type {};
-template <> struct SeqMetered<SeqBusGH3> : std::true_type {};
-template <typename... Bus> constexpr bool SEQ_HISTORY = (std::is_base_of<SeqHistory, Bus>::value || ...);
-static_assert(sizeof(SeqBusGH) == sizeof(SeqBusGM) && sizeof(SeqBusGH3) == sizeof(SeqBusGM3), "the history: no kernel argument of its own");
-
-// The buses that COUNT OVERS (sh_seq_render_clips; seqclip.hpp): the history buses again whose lanes keep counting accumulators -- sub,
-// grp and acc each with a sticky flag per sample, set where one of the bus's own steps clamped -- and whose rows carry, behind the levels,
-// the count of flagged samples per channel: a table of 48-byte rows in LDS and in the table of blocks.  A tag and no new kernel argument;
-// one bus type at widths 1, 2 and 4 and one at width 3.
-struct SeqClips {};
-struct SeqBusGC : SeqBusGH, SeqClips {};
-struct SeqBusGC3 : SeqBusGH3, SeqClips {};
-template <> struct SeqMetered<SeqBusGC> : std::true_type {};
-template <> struct SeqMetered<SeqBusGC3> : std::true_type {};
-template <typename... Bus> constexpr bool SEQ_CLIPS = (std::is_base_of<SeqClips, Bus>::value || ...);
-static_assert(sizeof(SeqBusGC) == sizeof(SeqBusGM) && sizeof(SeqBusGC3) == sizeof(SeqBusGM3), "the overs: no kernel argument of their own");
+// With the desk a track's row is post-fader and post-pan and the master's over the stored bytes; with automation a track's row stands
+// behind its fader moves as well.  With groups: ntracks + 1 + ngroups rows -- tracks and the master where they were, group g in row
+// ntracks + 1 + g, over what the master takes of it (behind its gain and pan); a track's row stays what its bus takes of it; a table of
+// their own size in LDS.  With rides a group's row stands behind its ride and pan and the master's behind its ride; with pan rides a
+// track's row behind its pan ride, a group's behind its ride and its pan ride.
+// The HISTORY (shb::HISTORY; sh_seq_render_history; seqhist.hpp): the metering group buses again -- the whole desk, NULL pointers meaning no
+// moves, the empty table no groups -- whose workgroups KEEP their table instead of merging it: bus.meters points at a table of blocks, one
+// per song tile of the window, and the workgroup that folds tile k stores its ntracks + 1 + groups.n rows as block k - lo / TILE.  No new
+// kernel argument: the first tile and the row count are in the kernel already.  A bit and nothing else, at widths 1, 2 and 4 and at width
+// 3; the buses that ride and pan have none.
+// The OVERS (shb::CLIPS; sh_seq_render_clips; seqclip.hpp): a history again whose lanes keep counting accumulators -- sub, grp and acc each
+// with a sticky flag per sample, set where one of the bus's own steps clamped -- and whose rows carry, behind the levels, the count of
+// flagged samples per channel: a table of 48-byte rows in LDS and in the table of blocks.  A bit and no new kernel argument, at widths 1, 2
+// and 4 and at width 3.
 // what a window kernel's lane accumulates in: the samples, or with a bus that counts the counting accumulator
 template <int WIDTH, typename... Bus> struct SeqWinAcc {
     typedef typename std::conditional<SEQ_CLIPS<Bus...>, typename std::conditional<WIDTH == 2, SeqAccC8, SeqAccCW>::type, typename SeqAcc<WIDTH>::type>::type type;
@@ -1489,7 +1454,7 @@ __device__ __forceinline__ void seq_clip_wave(shcl::Count c, const bool stereo, 
 // the workgroup's table into the handle's: every lane of the workgroup calls it (a barrier), lane 2 row + channel carries one value each
 // (groups: the rows of a group bus behind the master's; 2 * 41 lanes at the most, of TILE_THREADS)
 template <bool WIDE>
-__device__ __forceinline__ void seq_meter_end(const shmt::Row* table, const SeqBusM& bus, const uint32_t groups = 0) {
+__device__ __forceinline__ void seq_meter_end(const shmt::Row* table, const SeqMeters& bus, const uint32_t groups = 0) {
     static_assert(2 * (shq::MAX_TRACKS + 1 + shg::MAX_GROUPS) <= shq::TILE_THREADS, "a lane per row and channel");
     __syncthreads();
     const uint32_t row = threadIdx.x >> 1, c = threadIdx.x & 1u;
@@ -1506,7 +1471,7 @@ __device__ __forceinline__ void seq_meter_end(const shmt::Row* table, const SeqB
 // STORES its three values of (row, channel), zeros as well -- the block has this one writer, so nothing merges and nothing was zeroed.
 // R: the row, shmt::Row or (a bus that counts) shcl::Row, whose count is a fourth value; bus.meters is a table of R.
 template <int WIDTH, typename R>
-__device__ __forceinline__ void seq_hist_end(const R* table, const SeqBusM& bus, const uint32_t groups, const uint32_t tile, const uint32_t lo) {
+__device__ __forceinline__ void seq_hist_end(const R* table, const SeqMeters& bus, const uint32_t groups, const uint32_t tile, const uint32_t lo) {
     static_assert(2 * (shq::MAX_TRACKS + 1 + shg::MAX_GROUPS) <= shq::TILE_THREADS, "a lane per row and channel");
     __syncthreads();
     const uint32_t row = threadIdx.x >> 1, c = threadIdx.x & 1u, nrows = bus.ntracks + 1 + groups;
@@ -1558,7 +1523,7 @@ __device__ __forceinline__ void seq_stems_bus(const Bus& bus, uint32_t k, uint32
 template <int WIDTH, typename Bus, typename Acc, typename Walk, typename Store>
 __device__ __forceinline__ void seq_window_bus(const Bus& bus, uint32_t k, uint32_t e, uint32_t s0, uint32_t lo, uint32_t hi, Acc& acc, Walk walk,
                                                Store store) {
-    if constexpr (!SeqMetered<Bus>::value) {
+    if constexpr (!SEQ_METERS<Bus>) {
         seq_runs<WIDTH>(bus, k, e, acc, walk, [](const typename SeqAcc<WIDTH>::type&, uint32_t) {});
         if constexpr (SEQ_DESK<Bus>) seq_master<WIDTH>(acc, bus.master);
         if constexpr (SEQ_RIDES<Bus>) seq_ride<WIDTH>(acc, bus, sha::master_lane(bus.groups.row0), k);      // the master's ride: behind its gain
@@ -1597,7 +1562,7 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_plain16(const SeqEv* 
                                                                    const Bus... bus) {
     static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
     uint32_t k, t0, s0;
-    if constexpr (SeqMetered<Bus...>::value) {
+    if constexpr (SEQ_METERS<Bus...>) {
         if (!seq_window_tile<2>(order, lo, hi, k, t0, s0)) return;
     } else {
         if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
@@ -1625,7 +1590,7 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_16(const typename Seq
                                                               const Bus... bus) {
     static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
     uint32_t k, t0, s0;
-    if constexpr (SeqMetered<Bus...>::value) {
+    if constexpr (SEQ_METERS<Bus...>) {
         if (!seq_window_tile<2>(order, lo, hi, k, t0, s0)) return;
     } else {
         if (!seq_window_lane<2>(order, lo, hi, k, t0, s0)) return;
@@ -1655,7 +1620,7 @@ __global__ __launch_bounds__(shq::TILE_THREADS) void k_win_w(const typename SeqR
     static_assert(sizeof...(Bus) == (BUS ? 1 : 0), "the bus, and only with BUS");
     static_assert(LEVEL != ENV || WIDTH == 1 || WIDTH == 4, "an envelope has widths 1, 2 and 4");
     uint32_t k, t0, s0;
-    if constexpr (SeqMetered<Bus...>::value) {
+    if constexpr (SEQ_METERS<Bus...>) {
         if (!seq_window_tile<WIDTH>(order, lo, hi, k, t0, s0)) return;
     } else {
         if (!seq_window_lane<WIDTH>(order, lo, hi, k, t0, s0)) return;
@@ -2092,11 +2057,32 @@ void seq_with_level(int level, F f) {
     else seq_with_level<L + 1>(level, f);
 }
 
+// f(std::integral_constant<uint32_t, F>()) for the route F (one of shb::ROUTES) that a call takes; any other number: nothing, so that the
+// kernels of the 22 routes are the only ones there are
+template <uint32_t I = 0, typename F>
+void seq_with_bus(uint32_t route, F f) {
+    if constexpr (I < shb::NROUTES) {
+        if (route == shb::ROUTES[I]) f(std::integral_constant<uint32_t, shb::ROUTES[I]>());
+        else seq_with_bus<I + 1>(route, f);
+    }
+}
+
+// the bus of route F out of one that holds every part: the parts F has, part by part
+template <uint32_t F>
+SeqBusOf<F> seq_bus_parts(const SeqBusOf<shb::PARTS>& all) {
+    SeqBusOf<F> bus{};
+    static_cast<SeqBus&>(bus) = all;
+    if constexpr ((F & shb::METERS) != 0) static_cast<SeqMeters&>(bus) = all;
+    if constexpr ((F & shb::DESK) != 0) static_cast<SeqDesk&>(bus) = all;
+    if constexpr ((F & shb::AUTO) != 0) static_cast<SeqAuto&>(bus) = all;
+    if constexpr ((F & shb::GROUPS) != 0) static_cast<SeqGroups&>(bus) = all;
+    if constexpr ((F & shb::STEMS) != 0) static_cast<SeqStems&>(bus) = all;
+    return bus;
+}
+
 // Which window kernel: the width, at 16 bits the way misaligned event samples are read and whether the biased base lies on a 16-byte
-// boundary.  bus: nothing (a flat list), a SeqBus (a song of tracks: the same kernels with the bus, the gains by value), a SeqBusM (the
-// metering bus: the rows go to the handle's table) or one of the two with the desk (SeqBusD, SeqBusDM: pans and the master's gain by
-// value as well), with automation (SeqBusA, SeqBusAM), with groups (SeqBusG, SeqBusGM; width 3: SeqBusG3, SeqBusGM3) or with groups and
-// rides of the buses (SeqBusR, SeqBusRM) or with pan rides on top of those (SeqBusP, SeqBusPM), forwarded as the kernels' trailing pack.
+// boundary.  bus: nothing (a flat list) or the SeqBusOf<F> of one of shb::ROUTES (a song of tracks: the same kernels with the bus, its
+// parts by value), forwarded as the kernels' trailing pack; shb::valid_at says at which widths the kernels of F exist.
 template <int LEVEL, typename... Bus>
 void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, uint32_t hi, void* out, const Bus&... bus) {
     typedef typename SeqRec<LEVEL>::type Rec;
@@ -2109,7 +2095,7 @@ void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, 
     // the whole song: heaviest tile first (measured: profiles/sequence_plan_ab.txt); any other window: its tiles in song order
     const uint32_t* order = lo == 0 && hi == q->track_samples ? (const uint32_t*)(b + q->at_order) : nullptr;
     const dim3 block(shq::TILE_THREADS);
-    constexpr bool W3 = SEQ_GROUPS<Bus...> && !SEQ_AUTO<Bus...>;      // a group bus derived from a desk bus: width 3's, and only width 3's
+    constexpr bool AT3 = !BUS || shb::valid_at(SEQ_MASK<Bus...>, 3), W3 = BUS && AT3 && !shb::valid_at(SEQ_MASK<Bus...>, 2);      // W3: a group bus without automation, width 3's and only width 3's
     if constexpr (W3) {
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out, bus...); };
         if constexpr (LEVEL != ENV) go(k_win_w<LEVEL, 3, BUS, Bus...>);
@@ -2124,7 +2110,7 @@ void seq_window_launch(const sh_seq* q, dim3 grid, hipStream_t st, uint32_t lo, 
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ev, segs, first, idx, order, lo, hi, (unsigned char*)out, bus...); };
         if (q->width == 1) go(k_win_w<LEVEL, 1, BUS, Bus...>);
         else if (q->width == 4) go(k_win_w<LEVEL, 4, BUS, Bus...>);
-        else if constexpr (LEVEL != ENV && !SEQ_AUTO<Bus...>) go(k_win_w<LEVEL, 3, BUS, Bus...>);       // (sh_seq_create refuses width 3 with segments, sh_seq_render_auto width 3)
+        else if constexpr (LEVEL != ENV && AT3) go(k_win_w<LEVEL, 3, BUS, Bus...>);       // (sh_seq_create refuses width 3 with segments, sh_seq_render_auto width 3)
     }
 }
 
@@ -2254,25 +2240,55 @@ int seq_desk(const char* fn, const double* pans, uint32_t npans, double master_g
     return SH_OK;
 }
 
-template <typename T> struct SeqBaseOf { typedef T type; };
+// The refusals that every render with a desk shares (seq_render_desk, seq_render_grouped), behind their own NULL checks and in the order
+// both report them: no tracks; automation (where given) at width 3 or made for another song; pans on a
+// mono song; the gains' count; the pans' count.
+int seq_desk_args(const char* fn, const sh_seq* seq, const sh_seq_auto* automation, const double* gains, uint32_t ngains, const double* pans, uint32_t npans) {
+    if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
+    if (automation) {
+        if (seq->width == 3) return sh::set_error(SH_ERR_INVALID, "%s: width 3: a fader move's fade has no 24-bit form", fn);
+        if (automation->ntracks != seq->ntracks || automation->width != seq->width || automation->nchannels != seq->nchannels ||
+            automation->track_samples != seq->track_samples)
+            return sh::set_error(SH_ERR_INVALID, "%s: the automation was made for another song (%u tracks, width %d, %d channels, %llu samples)", fn,
+                                 automation->ntracks, automation->width, automation->nchannels, (unsigned long long)automation->track_samples);
+    }
+    if (pans && seq->nchannels != 2) return sh::set_error(SH_ERR_INVALID, "%s: pans need a stereo song, this one has %d channels", fn, seq->nchannels);
+    if (gains && ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
+    if (pans && npans != 2 * seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u pan factors for %u tracks (two each)", fn, npans, seq->ntracks);
+    return SH_OK;
+}
 
-// sh_seq_render (gains NULL: every track at 1.0), sh_seq_render_gains, sh_seq_render_meters (meters: ntracks + 1 host rows, the handle
-// has tracks), sh_seq_render_desk (desk: the pans and the master's gain, the handle has tracks; with or without meters) and
-// sh_seq_render_auto (au: the automation's table, with a desk) and sh_seq_render_groups (groups: the group table, with a desk, with or
-// without au; meters: ntracks + 1 + ngroups rows; rides: au has a segment on a bus lane, and groups may then be the empty table; pans: au
-// has a segment on a pan lane, likewise) and sh_seq_render_history (history: meters is a table of BLOCKS, nblocks * nrows host rows; the
-// device table is the library's scratch, sized for the call, and needs no zeroing) and sh_seq_render_clips (clips: a history whose rows
-// are sh_seq_meter_clips, 48 bytes) and sh_seq_render_stems (stems: the planes' stride in bytes and their count, checked by the caller
-// against `out`; with groups, no meters; out_sample is plane 0's) behind their names
-struct SeqStemsCall { uint64_t stride; uint32_t nplanes; };
-int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqGains* gains,
-               void* meters = nullptr, const SeqDesk* desk = nullptr, const SeqAuto* au = nullptr, const shg::Table* groups = nullptr,
-               bool rides = false, bool pans = false, bool history = false, bool clips = false, const SeqStemsCall* stems = nullptr) {
+// the table of an automation's handle as the kernels take it (none: NULL pointers, no moves)
+SeqAuto seq_auto_of(const sh_seq_auto* a) {
+    if (!a) return SeqAuto{nullptr, nullptr};
+    return SeqAuto{(const she::Seg*)a->block, (const uint32_t*)((const char*)a->block + a->at_first)};
+}
+
+// What a render is told beside the handle and the window (every entry point fills what it has; sh_seq_render nothing).  told: the entry
+// point says rides, pans, history and clips; seq_render reads the rest off the handle and the pointers.
+struct SeqCall {
+    const SeqGains* gains = nullptr;      // NULL: every track at 1.0
+    void* meters = nullptr;               // host rows: ntracks + 1 (+ ngroups with groups); told.history: a table of BLOCKS, nblocks * nrows rows -- the device
+                                          // table is then the library's scratch, sized for the call, and needs no zeroing; told.clips: rows of 48 bytes
+    const SeqDesk* desk = nullptr;        // the pans and the master's gain; the handle has tracks
+    const SeqAuto* au = nullptr;          // with a desk; told.rides: its table has a segment on a bus lane, told.pans: on a pan lane
+    const shg::Table* groups = nullptr;   // with a desk, with or without au; the empty table where au rides the master or tracks' pans alone
+    uint64_t stride = 0; uint32_t nplanes = 0;      // stems (nplanes != 0): the planes' stride in bytes and their count, checked by the caller against
+                                          // `out`; with groups, no meters; out_sample is plane 0's
+    shb::Call told{};
+};
+int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const SeqCall& call = SeqCall()) {
     static_assert(sizeof(sh_seq_meter) == sizeof(shmt::Row) && offsetof(sh_seq_meter, sq_hi) == offsetof(shmt::Row, sq_hi) &&
                   offsetof(sh_seq_meter, sq_lo) == offsetof(shmt::Row, sq_lo), "sh_seq_meter is shmt::Row");
     static_assert(sizeof(sh_seq_meter_clips) == sizeof(shcl::Row) && offsetof(sh_seq_meter_clips, sq_hi) == offsetof(sh_seq_meter, sq_hi) &&
                   offsetof(sh_seq_meter_clips, sq_lo) == offsetof(sh_seq_meter, sq_lo) && offsetof(sh_seq_meter_clips, clipped) == sizeof(shmt::Row),
                   "sh_seq_meter_clips is shcl::Row: sh_seq_meter, then the counts");
+    shb::Call told = call.told;
+    told.tracks = seq->ntracks != 0, told.width = seq->width, told.stems = call.nplanes != 0;
+    told.meters = call.meters != nullptr, told.desk = call.desk != nullptr, told.automation = call.au != nullptr, told.groups = call.groups != nullptr;
+    void* const meters = call.meters;
+    const shg::Table* const groups = call.groups;
+    const bool history = told.history, clips = told.clips;
     const size_t b_rows = meters ? ((size_t)seq->ntracks + 1 + (groups ? groups->n : 0)) * (clips ? sizeof(shcl::Row) : sizeof(shmt::Row)) : 0;
     const size_t w = (size_t)seq->width;
     if (first_sample > seq->track_samples || nsamples > seq->track_samples - first_sample)
@@ -2285,11 +2301,11 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
     }
     const char* o0 = (const char*)out->ptr + out_sample * w;
     const char* o1 = o0 + nsamples * w;
-    if (stems) {                                              // from the first sample of plane 0 to the last of the last plane, gaps included
-        const char* s1 = o0 + shst::span(stems->nplanes, stems->stride / w, nsamples) * w;
+    if (told.stems) {                                         // from the first sample of plane 0 to the last of the last plane, gaps included
+        const char* s1 = o0 + shst::span(call.nplanes, call.stride / w, nsamples) * w;
         for (size_t v = 0; v < seq->src_lo.size(); ++v)
             if (shst::overlaps((uint64_t)(uintptr_t)o0, (uint64_t)(uintptr_t)s1, (uint64_t)(uintptr_t)seq->src_lo[v], (uint64_t)(uintptr_t)seq->src_hi[v]))
-                return sh::set_error(SH_ERR_INVALID, "%s: the span of the %u planes overlaps a source of the song", fn, stems->nplanes);
+                return sh::set_error(SH_ERR_INVALID, "%s: the span of the %u planes overlaps a source of the song", fn, call.nplanes);
     }
     for (size_t v = 0; v < seq->src_lo.size(); ++v)
         if (seq->src_lo[v] < o1 && o0 < seq->src_hi[v]) return sh::set_error(SH_ERR_INVALID, "%s: out overlaps a source of the song", fn);
@@ -2306,62 +2322,25 @@ int seq_render(const char* fn, const sh_seq* seq, size_t first_sample, size_t ns
         if (rc) return rc;
         table = (char*)sh::state().scratch;
     } else if (meters) SH_HIP(hipMemsetAsync(table, 0, b_meters, st));
-    SeqBusDM bus{};                                           // (a song of tracks; its SeqBusM part is the metering bus, whose SeqBus part is the plain one)
-    if (desk) static_cast<SeqDesk&>(bus) = *desk;
+    SeqBusOf<shb::PARTS> bus{};                               // every part a bus may carry (no automation: NULL pointers, no moves); the route takes its own
+    if (call.desk) static_cast<SeqDesk&>(bus) = *call.desk;
+    if (call.au) static_cast<SeqAuto&>(bus) = *call.au;
+    if (groups) bus.groups = *groups;
+    bus.stride = call.stride;
     if (seq->ntracks) {
         bus.rfirst = (const uint32_t*)((const char*)seq->block + seq->at_rfirst);
         bus.runs = (const shq::Run*)((const char*)seq->block + seq->at_runs);
-        if (gains) bus.gains = *gains;
+        if (call.gains) bus.gains = *call.gains;
         else seq_gains(fn, nullptr, 0, bus.gains);
         bus.meters = (shmt::Row*)table;
         bus.ntracks = seq->ntracks;
         bus.nch = (uint32_t)seq->nchannels;
     }
+    const uint32_t route = shb::route(told);
     seq_with_level(seq->level, [&](auto L) {
         constexpr int LEVEL = decltype(L)::value;
-        if (!seq->ntracks) seq_window_launch<LEVEL>(seq, grid, st, lo, hi, biased);
-        else if (!desk && !meters) seq_window_launch<LEVEL, SeqBus>(seq, grid, st, lo, hi, biased, bus);
-        else if (!desk) seq_window_launch<LEVEL, SeqBusM>(seq, grid, st, lo, hi, biased, bus);
-        else if (groups) {                                    // (with a desk: the whole desk rides on a group bus, au or none)
-            auto grouped = [&](auto moved, auto base) {       // moved: the group bus; base: which bus of the handle's it is made of
-                typedef decltype(moved) G;
-                typedef typename decltype(base)::type B;
-                static_cast<B&>(moved) = bus;
-                static_cast<SeqDesk&>(moved) = bus;
-                if constexpr (SEQ_AUTO<G>) static_cast<SeqAuto&>(moved) = au ? *au : SeqAuto{nullptr, nullptr};
-                moved.groups = *groups;
-                if constexpr (SEQ_STEMS<G>) moved.stride = stems->stride;
-                seq_window_launch<LEVEL, G>(seq, grid, st, lo, hi, biased, moved);
-            };
-            if (stems) {                                      // (no meters; au: which lanes its table holds says which kernel may read it)
-                if (seq->width == 3) grouped(SeqBusGS3{}, SeqBaseOf<SeqBus>());
-                else if (pans) grouped(SeqBusPS{}, SeqBaseOf<SeqBus>());
-                else if (rides) grouped(SeqBusRS{}, SeqBaseOf<SeqBus>());
-                else grouped(SeqBusGS{}, SeqBaseOf<SeqBus>());
-            } else if (clips) seq->width == 3 ? grouped(SeqBusGC3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusGC{}, SeqBaseOf<SeqBusM>());
-            else if (history) seq->width == 3 ? grouped(SeqBusGH3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusGH{}, SeqBaseOf<SeqBusM>());
-            else if (seq->width == 3) meters ? grouped(SeqBusGM3{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG3{}, SeqBaseOf<SeqBus>());
-            else if (pans) meters ? grouped(SeqBusPM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusP{}, SeqBaseOf<SeqBus>());       // (au: a table with pan lanes)
-            else if (rides) meters ? grouped(SeqBusRM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusR{}, SeqBaseOf<SeqBus>());      // (au: a table with bus lanes)
-            else meters ? grouped(SeqBusGM{}, SeqBaseOf<SeqBusM>()) : grouped(SeqBusG{}, SeqBaseOf<SeqBus>());
-        } else if (au && meters) {
-            SeqBusAM moved{};
-            static_cast<SeqBusDM&>(moved) = bus;
-            static_cast<SeqAuto&>(moved) = *au;
-            seq_window_launch<LEVEL, SeqBusAM>(seq, grid, st, lo, hi, biased, moved);
-        } else if (au) {
-            SeqBusA moved{};
-            static_cast<SeqBus&>(moved) = bus;
-            static_cast<SeqDesk&>(moved) = bus;
-            static_cast<SeqAuto&>(moved) = *au;
-            seq_window_launch<LEVEL, SeqBusA>(seq, grid, st, lo, hi, biased, moved);
-        } else if (meters) seq_window_launch<LEVEL, SeqBusDM>(seq, grid, st, lo, hi, biased, bus);
-        else {
-            SeqBusD plain{};
-            static_cast<SeqBus&>(plain) = bus;
-            static_cast<SeqDesk&>(plain) = bus;
-            seq_window_launch<LEVEL, SeqBusD>(seq, grid, st, lo, hi, biased, plain);
-        }
+        if (route == shb::NO_BUS) seq_window_launch<LEVEL>(seq, grid, st, lo, hi, biased);
+        else seq_with_bus(route, [&](auto F) { seq_window_launch<LEVEL>(seq, grid, st, lo, hi, biased, seq_bus_parts<decltype(F)::value>(bus)); });
     });
     SH_CHECK_LAUNCH(fn);
     if (meters) {                                             // synchronous, as sh_pcm_stats: one small copy, one wait
@@ -2393,7 +2372,7 @@ int sh_seq_render(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_bu
     SH_REQUIRE_INIT();
     static const char fn[] = "sh_seq_render";
     if (!seq || !out) return seq_null(fn);
-    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, nullptr);
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample);
 }
 
 int sh_seq_render_gains(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
@@ -2406,7 +2385,9 @@ int sh_seq_render_gains(const sh_seq* seq, size_t first_sample, size_t nsamples,
     SeqGains g;
     const int rc = seq_gains(fn, gains, ngains, g);
     if (rc) return rc;
-    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g);
+    SeqCall call;
+    call.gains = &g;
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, call);
 }
 
 int sh_seq_render_meters(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
@@ -2420,25 +2401,9 @@ int sh_seq_render_meters(const sh_seq* seq, size_t first_sample, size_t nsamples
     SeqGains g;
     const int rc = seq_gains(fn, gains, ngains, g);
     if (rc) return rc;
-    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters);
-}
-
-int sh_seq_render_desk(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
-                       uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters) {
-    SH_REQUIRE_INIT();
-    static const char fn[] = "sh_seq_render_desk";
-    if (!seq || !out || (!gains && ngains) || (!pans && npans) || (!meters && nmeters)) return seq_null(fn);
-    if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
-    if (pans && seq->nchannels != 2) return sh::set_error(SH_ERR_INVALID, "%s: pans need a stereo song, this one has %d channels", fn, seq->nchannels);
-    if (gains && ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
-    if (pans && npans != 2 * seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u pan factors for %u tracks (two each)", fn, npans, seq->ntracks);
-    if (meters && nmeters != seq->ntracks + 1) return sh::set_error(SH_ERR_INVALID, "%s: %u rows for %u tracks and the master", fn, nmeters, seq->ntracks);
-    SeqGains g;
-    SeqDesk d;
-    int rc = seq_gains(fn, gains, ngains, g);
-    if (!rc) rc = seq_desk(fn, pans, npans, master_gain, d);
-    if (rc) return rc;
-    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d);
+    SeqCall call;
+    call.gains = &g, call.meters = meters;
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, call);
 }
 
 // sh_seq_auto_create (buses false: ntracks lanes) and sh_seq_auto_create_buses (ntracks + 1 + ngroups lanes in the meter table's row order)
@@ -2579,40 +2544,48 @@ int sh_seq_auto_destroy(sh_seq_auto* a) {
     return SH_OK;
 }
 
+// sh_seq_render_desk (automation NULL) and sh_seq_render_auto behind their names
+static int seq_render_desk(const char* fn, const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                           uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters,
+                           const sh_seq_auto* automation) {
+    if (!seq || !out || (!gains && ngains) || (!pans && npans) || (!meters && nmeters)) return seq_null(fn);
+    int rc = seq_desk_args(fn, seq, automation, gains, ngains, pans, npans);
+    if (rc) return rc;
+    if (meters && nmeters != seq->ntracks + 1) return sh::set_error(SH_ERR_INVALID, "%s: %u rows for %u tracks and the master", fn, nmeters, seq->ntracks);
+    SeqGains g;
+    SeqDesk d;
+    rc = seq_gains(fn, gains, ngains, g);
+    if (!rc) rc = seq_desk(fn, pans, npans, master_gain, d);
+    if (rc) return rc;
+    const SeqAuto au = seq_auto_of(automation);
+    SeqCall call;
+    call.gains = &g, call.meters = meters, call.desk = &d, call.au = automation ? &au : nullptr;
+    shg::Table none;
+    if (automation && automation->ridden)
+        return sh::set_error(SH_ERR_INVALID, "%s: the automation rides group %u, which this call does not name (sh_seq_render_groups does)", fn,
+                             automation->ridden - 1);
+    if (automation && automation->panned)
+        return sh::set_error(SH_ERR_INVALID, "%s: the automation rides the pan of group %u, which this call does not name (sh_seq_render_groups does)", fn,
+                             automation->panned - 1);
+    if (automation && (automation->buses || automation->pans)) {      // a master ride or tracks' pan rides alone: the kernels that ride, an empty group table
+        shg::pack(nullptr, 0, seq->ntracks, none);
+        call.groups = &none, call.told.rides = true, call.told.pans = automation->pans;
+    }
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, call);
+}
+
+int sh_seq_render_desk(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
+                       uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters) {
+    SH_REQUIRE_INIT();
+    return seq_render_desk("sh_seq_render_desk", seq, first_sample, nsamples, out, out_sample, gains, ngains, pans, npans, master_gain, meters, nmeters, nullptr);
+}
+
 int sh_seq_render_auto(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
                        uint32_t ngains, const double* pans, uint32_t npans, double master_gain, sh_seq_meter* meters, uint32_t nmeters,
                        const sh_seq_auto* automation) {
     SH_REQUIRE_INIT();
-    static const char fn[] = "sh_seq_render_auto";
-    if (!seq || !out || !automation || (!gains && ngains) || (!pans && npans) || (!meters && nmeters)) return seq_null(fn);
-    if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
-    if (seq->width == 3) return sh::set_error(SH_ERR_INVALID, "%s: width 3: a fader move's fade has no 24-bit form", fn);
-    if (automation->ntracks != seq->ntracks || automation->width != seq->width || automation->nchannels != seq->nchannels ||
-        automation->track_samples != seq->track_samples)
-        return sh::set_error(SH_ERR_INVALID, "%s: the automation was made for another song (%u tracks, width %d, %d channels, %llu samples)", fn,
-                             automation->ntracks, automation->width, automation->nchannels, (unsigned long long)automation->track_samples);
-    if (pans && seq->nchannels != 2) return sh::set_error(SH_ERR_INVALID, "%s: pans need a stereo song, this one has %d channels", fn, seq->nchannels);
-    if (gains && ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
-    if (pans && npans != 2 * seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u pan factors for %u tracks (two each)", fn, npans, seq->ntracks);
-    if (meters && nmeters != seq->ntracks + 1) return sh::set_error(SH_ERR_INVALID, "%s: %u rows for %u tracks and the master", fn, nmeters, seq->ntracks);
-    SeqGains g;
-    SeqDesk d;
-    int rc = seq_gains(fn, gains, ngains, g);
-    if (!rc) rc = seq_desk(fn, pans, npans, master_gain, d);
-    if (rc) return rc;
-    const SeqAuto au{(const she::Seg*)automation->block, (const uint32_t*)((const char*)automation->block + automation->at_first)};
-    if (automation->ridden)
-        return sh::set_error(SH_ERR_INVALID, "%s: the automation rides group %u, which this call does not name (sh_seq_render_groups does)", fn,
-                             automation->ridden - 1);
-    if (automation->panned)
-        return sh::set_error(SH_ERR_INVALID, "%s: the automation rides the pan of group %u, which this call does not name (sh_seq_render_groups does)", fn,
-                             automation->panned - 1);
-    if (automation->buses || automation->pans) {              // a master ride or tracks' pan rides alone: the kernels that ride, no group in the table
-        shg::Table none;
-        shg::pack(nullptr, 0, seq->ntracks, none);
-        return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, &au, &none, true, automation->pans);
-    }
-    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, &au);
+    if (!automation) return seq_null("sh_seq_render_auto");
+    return seq_render_desk("sh_seq_render_auto", seq, first_sample, nsamples, out, out_sample, gains, ngains, pans, npans, master_gain, meters, nmeters, automation);
 }
 
 // sh_seq_render_groups (history false: meters is NULL or nmeters == ntracks + 1 + ngroups rows, at least one group) and
@@ -2627,17 +2600,8 @@ static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, s
     static_assert(sizeof(sh_seq_group) == sizeof(shg::Group) && offsetof(sh_seq_group, gain) == offsetof(shg::Group, gain) &&
                   offsetof(sh_seq_group, right) == offsetof(shg::Group, right) && SH_SEQ_MAX_GROUPS == shg::MAX_GROUPS, "sh_seq_group is shg::Group");
     if (!seq || !out || (!gains && ngains) || (!pans && npans) || (!meters && nmeters && !history)) return seq_null(fn);
-    if (!seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: the song has no tracks (sh_seq_create_tracks makes one that has)", fn);
-    if (automation) {
-        if (seq->width == 3) return sh::set_error(SH_ERR_INVALID, "%s: width 3: a fader move's fade has no 24-bit form", fn);
-        if (automation->ntracks != seq->ntracks || automation->width != seq->width || automation->nchannels != seq->nchannels ||
-            automation->track_samples != seq->track_samples)
-            return sh::set_error(SH_ERR_INVALID, "%s: the automation was made for another song (%u tracks, width %d, %d channels, %llu samples)", fn,
-                                 automation->ntracks, automation->width, automation->nchannels, (unsigned long long)automation->track_samples);
-    }
-    if (pans && seq->nchannels != 2) return sh::set_error(SH_ERR_INVALID, "%s: pans need a stereo song, this one has %d channels", fn, seq->nchannels);
-    if (gains && ngains != seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u gains for %u tracks", fn, ngains, seq->ntracks);
-    if (pans && npans != 2 * seq->ntracks) return sh::set_error(SH_ERR_INVALID, "%s: %u pan factors for %u tracks (two each)", fn, npans, seq->ntracks);
+    int rc = seq_desk_args(fn, seq, automation, gains, ngains, pans, npans);
+    if (rc) return rc;
     const bool nogroups = history || stems;                   // (a history and stems: ngroups may be 0)
     if ((ngroups == 0 && !nogroups) || ngroups > shg::MAX_GROUPS)
         return sh::set_error(SH_ERR_INVALID, "%s: %u groups, %u to %u", fn, ngroups, nogroups ? 0u : 1u, shg::MAX_GROUPS);
@@ -2658,7 +2622,7 @@ static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, s
         return sh::set_error(SH_ERR_INVALID, "%s: group %u: a pan needs a stereo song, this one has %d channels", fn, v.entry, seq->nchannels);
     default: return sh::set_error(SH_ERR_INVALID, "%s: %u groups, %u to %u", fn, ngroups, nogroups ? 0u : 1u, shg::MAX_GROUPS);
     }
-    SeqStemsCall planes{0, 0};
+    SeqCall call;
     if (stems) {                                              // the planes' geometry (seqstem.hpp), each refusal by a message of its own
         const size_t w = (size_t)seq->width;
         switch (shst::check(stems->nplanes, seq->ntracks, ngroups, stems->plane_samples, nsamples, out_sample, out->bytes / w)) {
@@ -2672,7 +2636,7 @@ static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, s
             return sh::set_error(SH_ERR_INVALID, "%s: the last of %u planes ends outside out (%llu samples from sample %llu on, planes %llu apart)", fn,
                                  stems->nplanes, (unsigned long long)(out->bytes / w), (unsigned long long)out_sample, (unsigned long long)stems->plane_samples);
         }
-        planes = SeqStemsCall{shst::stride_bytes(stems->plane_samples, (uint32_t)seq->width), stems->nplanes};
+        call.stride = shst::stride_bytes(stems->plane_samples, (uint32_t)seq->width), call.nplanes = stems->nplanes;
     }
     if (clips && automation && (automation->buses || automation->pans))
         return sh::set_error(SH_ERR_INVALID, "%s: the automation rides a %s: overs are not counted through rides of buses and pans yet", fn,
@@ -2695,15 +2659,16 @@ static int seq_render_grouped(const char* fn, bool history, const sh_seq* seq, s
     }
     SeqGains g;
     SeqDesk d;
-    int rc = seq_gains(fn, gains, ngains, g);
+    rc = seq_gains(fn, gains, ngains, g);
     if (!rc) rc = seq_desk(fn, pans, npans, master_gain, d);
     if (rc) return rc;
     shg::Table table;
     shg::pack(gs, ngroups, seq->ntracks, table);
-    SeqAuto au{nullptr, nullptr};
-    if (automation) au = SeqAuto{(const she::Seg*)automation->block, (const uint32_t*)((const char*)automation->block + automation->at_first)};
-    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, &g, meters, &d, automation ? &au : nullptr, &table,
-                      automation && (automation->buses || automation->pans), automation && automation->pans, history, clips, stems ? &planes : nullptr);
+    const SeqAuto au = seq_auto_of(automation);
+    call.gains = &g, call.meters = meters, call.desk = &d, call.au = automation ? &au : nullptr, call.groups = &table;
+    call.told.rides = automation && (automation->buses || automation->pans), call.told.pans = automation && automation->pans;
+    call.told.history = history, call.told.clips = clips;
+    return seq_render(fn, seq, first_sample, nsamples, out, out_sample, call);
 }
 
 int sh_seq_render_groups(const sh_seq* seq, size_t first_sample, size_t nsamples, sh_buf* out, size_t out_sample, const double* gains,
