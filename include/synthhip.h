@@ -1045,6 +1045,25 @@ int sh_pcm_stats(const sh_buf* in, size_t nbytes, int width, uint32_t* max_abs, 
  * audioop.tomono(frames, w, 1, 0) / (.., 0, 1) + audioop.max / audioop.rms sequence of Sample.level_db_peak /
  * level_db_rms and LevelMeter.update (upstream synthplayer/sample.py, [RECALL], tree not mounted). */
 int sh_pcm_stats_stereo(const sh_buf* in, size_t nframes, int width, uint32_t max_abs[2], double sum_squares[2]);
+/* The levels PER BLOCK of PCM that lies in device memory, exact in integers, for one plane or many, in one launch (csrc/pcmblocks.hpp
+ * has the geometry).  The input: nframes frames of nch (1 or 2) interleaved channels of `width` bytes (1, 2, 4, or 3: the raw 24-bit
+ * values, as sh_pcm_stats), from sample `sample_offset` of `in` on; nplanes such planes, plane r beginning r * plane_samples samples
+ * behind plane 0 (any whole number of samples, at least nframes * nch where there is more than one plane; the stems of
+ * sh_seq_render_stems are such planes).  Nothing outside the planes is read, and the rows do not depend on their alignment.
+ * Positions are FRAMES in 64 bits: frame i of the input stands at grid frame origin_frame + i, and block j of the call is grid block
+ * origin_frame / block_frames + j, cut to [origin_frame, origin_frame + nframes) -- sh_seq_render_history's rule with frames in place
+ * of tiles and any block size: nblocks = (origin_frame + nframes - 1) / block_frames - origin_frame / block_frames + 1 (0 for an empty
+ * window), the first and the last block may be partial, and a block that lies whole inside two calls reads the same from both.
+ * rows: a HOST array of nblocks * nplanes sh_seq_meter, block-major, row r of block j at j * nplanes + r: per channel the peak
+ * (audioop.max) and the exact integer sum of squares sq_hi * 2^32 + sq_lo -- one sum (sq_hi == 0) at widths 1 and 2, two at widths 3
+ * and 4; a mono input fills channel 0 and leaves channel 1 at 0.  Integer max and integer add only: the same table on every run.
+ * SYNCHRONOUS, as sh_seq_render_history: one launch (two where a block is longer than 8192 samples: its parts are folded by a second,
+ * small kernel; at width 3 an unpacking launch per plane in front), the table copied back, one wait.  SH_ERR_INVALID, each with a
+ * message of its own and before anything is launched or written: nch not 1 or 2, a bad width, block_frames == 0, nplanes == 0,
+ * plane_samples < nframes * nch with more than one plane, a last plane that ends outside in, nblocks other than the count above,
+ * rows == NULL with a non-empty window.  nframes == 0 with nblocks == 0 succeeds and launches nothing. */
+int sh_pcm_level_blocks(const sh_buf* in, size_t sample_offset, size_t nframes, int nch, int width, size_t plane_samples, uint32_t nplanes,
+                        uint64_t origin_frame, uint64_t block_frames, sh_seq_meter* rows /* host, nblocks * nplanes */, size_t nblocks);
 
 /* ---- Sample.resample -> audioop.ratecv(frames, width, nchannels, inrate, outrate, None) */
 size_t sh_resample_out_frames(size_t in_frames, int inrate, int outrate);

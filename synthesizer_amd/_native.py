@@ -113,6 +113,7 @@ assert SEQ_METER_CLIPS_DTYPE.itemsize == C.sizeof(SeqMeterClips) == 48
 SEQ_MAX_GROUPS = 8                                                                    # SH_SEQ_MAX_GROUPS
 SEQ_TILE_SAMPLES = {1: 1024, 2: 2048, 3: 1024, 4: 1024}                               # shq::tile_samples(width): a block of a level history
 SEQ_LEVELS = ("plain", "rate", "pan", "env", "loop", "rev", "chan")                   # SH_SEQ_LEVEL_*
+PCM_PART_SAMPLES = 8192                                                               # shpb::PART_SAMPLES (csrc/pcmblocks.hpp): a block up to this long is one part
 
 
 class MixLevel(NamedTuple):
@@ -258,6 +259,8 @@ _SIGNATURES = {
     "sh_pcm_lin2lin": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, _P]),
     "sh_pcm_stats": (C.c_int, [_P, C.c_size_t, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
     "sh_pcm_stats_stereo": (C.c_int, [_P, C.c_size_t, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
+    "sh_pcm_level_blocks": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(SeqMeter),
+                                      C.c_size_t]),
     "sh_resample_out_frames": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int]),
     "sh_resample": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_size_t)]),
     "sh_resample_span": (C.c_int, [C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -637,6 +640,19 @@ class SeqAutomation:
             self.free()
         except Exception:
             pass
+
+
+def pcm_level_blocks(buf: "DeviceBuffer", sample_offset: int, nframes: int, nch: int, width: int, plane_samples: int, nplanes: int,
+                     origin_frame: int, block_frames: int) -> np.ndarray:
+    """sh_pcm_level_blocks: the levels per block of ``nplanes`` planes of PCM in ``buf`` -- ``nframes`` frames of ``nch`` channels from
+    sample ``sample_offset`` on, the planes ``plane_samples`` samples apart -- on the frame grid of ``block_frames`` on which the first
+    frame stands at ``origin_frame``: a numpy array of shape ``(nblocks, nplanes)`` and dtype ``SEQ_METER_DTYPE``, as
+    ``Sequence.render(meters="history")`` returns it.  One launch, synchronous; an empty window launches nothing."""
+    nblocks = (origin_frame + nframes - 1) // block_frames - origin_frame // block_frames + 1 if nframes > 0 else 0
+    blocks = np.zeros((nblocks, nplanes), dtype=SEQ_METER_DTYPE)
+    rows = blocks.ctypes.data_as(C.POINTER(SeqMeter)) if blocks.size else None
+    check(lib().sh_pcm_level_blocks(buf.handle, sample_offset, nframes, nch, width, plane_samples, nplanes, origin_frame, block_frames, rows, nblocks))
+    return blocks
 
 
 def debug_counters() -> dict:

@@ -7,6 +7,7 @@
 #include "common.hpp"
 #include "pcmdev.hpp"
 #include "pcmhost.hpp"
+#include "pcmblocks.hpp"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -280,6 +281,169 @@ __global__ __launch_bounds__(256) void k_pcm_stats_fold(const unsigned long long
     stats_record<acc_t, NCH>(mx, sq, out);
 }
 
+// ---- the levels per block of PCM in device memory (sh_pcm_level_blocks; pcmblocks.hpp has the geometry and the arithmetic) ----------------
+// what the two kernels are handed: frames in 64 bits, as the header counts them
+struct LevelBlocks {
+    const void* in;             // the first sample of plane 0
+    uint64_t plane_samples;     // plane r begins r * plane_samples samples behind it
+    uint64_t n, origin, B;      // the call's frames, the grid frame of the first, the block
+    uint64_t first;             // origin / B
+    uint32_t shift;             // a block has 2^shift part slots: shpb::slot_shift(the longest block)
+    uint64_t nwg;               // nblocks << shift: the workgroups of one plane
+    uint32_t nplanes, r0;       // the rows of a block; the plane of blockIdx.z == 0 in this launch
+    shmt::Row* out;             // row (w * nplanes + r) of workgroup w of plane r: the table where shift == 0, the partial rows otherwise
+};
+
+// a wave's rows into lane 0's: shmt::fold over the six shuffle steps (fields a width or a channel count never fills stay the constant 0)
+template <int NCH, bool WIDE>
+__device__ __forceinline__ shmt::Row wave_fold_row(shmt::Row r) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        shmt::Row q = shmt::zero();
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            q.peak[c] = __shfl_down(r.peak[c], o, 64);
+            q.sq_lo[c] = __shfl_down((unsigned long long)r.sq_lo[c], o, 64);
+            if constexpr (WIDE) q.sq_hi[c] = __shfl_down((unsigned long long)r.sq_hi[c], o, 64);
+        }
+        shmt::fold(r, q);
+    }
+    return r;
+}
+
+// One workgroup per (part slot, plane): the samples [s0, s1) of its block's cut range in its plane, and nothing else -- a scalar head up
+// to the 16-byte boundary, 16-byte vectors, a scalar tail; a plane that starts off the sample grid (a view cut at an odd byte) has no
+// such boundary and is all head.  Scalar samples are assembled from bytes (memcpy), so they need no alignment.  In a stereo plane a part
+// starts on a frame (s0 is even), so a scalar sample's channel is its index's parity; a vector holds whole frames, element e of every
+// vector belongs to channel (head + e) & 1, and the vectors' row changes sides once, behind the loop, where the head is odd.
+// At 16 bits the packed forms of k_pcm_stats: |x| as uint16 pairs, mono a pair's squares by the dot product, stereo a 24-bit
+// multiply per channel.  The lanes' rows fold by wave shuffle, the four waves' through LDS behind the one barrier, and thread
+// 2 * 0 + channel stores its channel of the row: one writer per row, zeros too, no atomics, nothing zeroed first.
+template <typename T, int NCH>
+__global__ __launch_bounds__(256) void k_pcm_level_blocks(const LevelBlocks g) {
+    constexpr bool WIDE = sizeof(T) == 4;
+    constexpr uint32_t V = 16 / sizeof(T);
+    typedef T vec_t __attribute__((ext_vector_type(V)));
+    const uint64_t w = sh::block_id();
+    if (w >= g.nwg) return;                                    // (a launch folded into two dimensions rounds up)
+    const uint32_t r = g.r0 + blockIdx.z;
+    const uint64_t j = w >> g.shift, p = w - (j << g.shift);
+    uint64_t a, b, s0, s1;
+    shpb::range(g.first, j, g.origin, g.n, g.B, a, b);
+    shpb::part((b - a) * NCH, p, s0, s1);
+    const unsigned char* x = (const unsigned char*)g.in + ((uint64_t)r * g.plane_samples + (a - g.origin) * NCH + s0) * sizeof(T);
+    const uint32_t cnt = (uint32_t)(s1 - s0);                  // at most shpb::PART_SAMPLES
+    const uintptr_t at = (uintptr_t)x;
+    uint32_t head = cnt;
+    if (at % sizeof(T) == 0) {
+        head = (uint32_t)((16 - (at & 15)) & 15) / (uint32_t)sizeof(T);
+        if (head > cnt) head = cnt;
+    }
+    const uint32_t nvec = (cnt - head) / V, tail = head + nvec * V;
+    auto sample = [&](uint32_t i) {
+        T v;
+        __builtin_memcpy(&v, x + (size_t)i * sizeof(T), sizeof(T));
+        return (long long)v;
+    };
+    shmt::Row row = shmt::zero();
+    auto one = [&](uint32_t i) {                               // shpb::take with both channels' adds spelled out: the other side adds 0
+        const long long q = sample(i);
+        const bool right = NCH == 2 && (i & 1);
+        shmt::add<WIDE>(row, 0, right ? 0 : q);
+        if constexpr (NCH == 2) shmt::add<WIDE>(row, 1, right ? q : 0);
+    };
+    for (uint32_t i = threadIdx.x; i < head; i += 256) one(i);
+    for (uint32_t i = tail + threadIdx.x; i < cnt; i += 256) one(i);
+
+    const vec_t* vin = reinterpret_cast<const vec_t*>(x + (size_t)head * sizeof(T));
+    shmt::Row vrow = shmt::zero();                             // by element parity
+    constexpr uint32_t INFLIGHT = 4;
+    uint32_t v = threadIdx.x;
+    if constexpr (sizeof(T) == 2) {
+        typedef short s2 __attribute__((ext_vector_type(2)));
+        typedef unsigned short u2 __attribute__((ext_vector_type(2)));
+        u2 mx2 = {0, 0};
+        unsigned long long sq[NCH] = {};
+        auto pair = [&](const s2 q) {
+            const s2 neg = (s2){0, 0} - q;
+            const u2 au = __builtin_bit_cast(u2, __builtin_elementwise_max(q, neg));       // read as uint16: |-32768| = 32768
+            mx2 = __builtin_elementwise_max(mx2, au);
+            if constexpr (NCH == 1) sq[0] += (unsigned long long)__builtin_amdgcn_udot2(au, au, 0u, false);
+            else { sq[0] += (unsigned long long)__umul24(au[0], au[0]); sq[1] += (unsigned long long)__umul24(au[1], au[1]); }
+        };
+        auto pairs = [&](const vec_t q) {
+            pair(__builtin_shufflevector(q, q, 0, 1)); pair(__builtin_shufflevector(q, q, 2, 3));
+            pair(__builtin_shufflevector(q, q, 4, 5)); pair(__builtin_shufflevector(q, q, 6, 7));
+        };
+        for (; v + (INFLIGHT - 1) * 256 < nvec; v += INFLIGHT * 256) {
+            vec_t q[INFLIGHT];
+#pragma unroll
+            for (uint32_t k = 0; k < INFLIGHT; ++k) q[k] = vin[v + k * 256];
+#pragma unroll
+            for (uint32_t k = 0; k < INFLIGHT; ++k) pairs(q[k]);
+        }
+        for (; v < nvec; v += 256) pairs(vin[v]);
+        if constexpr (NCH == 1) { vrow.peak[0] = mx2[0] > mx2[1] ? mx2[0] : mx2[1]; vrow.sq_lo[0] = sq[0]; }
+        else { vrow.peak[0] = mx2[0]; vrow.peak[1] = mx2[1]; vrow.sq_lo[0] = sq[0]; vrow.sq_lo[1] = sq[1]; }
+    } else {
+        auto all = [&](const vec_t q) {
+#pragma unroll
+            for (uint32_t e = 0; e < V; ++e) shmt::add<WIDE>(vrow, (int)(e % NCH), (long long)q[e]);
+        };
+        for (; v + (INFLIGHT - 1) * 256 < nvec; v += INFLIGHT * 256) {
+            vec_t q[INFLIGHT];
+#pragma unroll
+            for (uint32_t k = 0; k < INFLIGHT; ++k) q[k] = vin[v + k * 256];
+#pragma unroll
+            for (uint32_t k = 0; k < INFLIGHT; ++k) all(q[k]);
+        }
+        for (; v < nvec; v += 256) all(vin[v]);
+    }
+    if constexpr (NCH == 2) {                                  // the vectors began on a right sample: the two sides change places (by
+        const uint64_t m = (head & 1) ? ~0ull : 0ull;          // mask, so that no field of a row in registers is picked by a variable)
+        const uint32_t tp = (vrow.peak[0] ^ vrow.peak[1]) & (uint32_t)m;
+        const uint64_t th = (vrow.sq_hi[0] ^ vrow.sq_hi[1]) & m, tl = (vrow.sq_lo[0] ^ vrow.sq_lo[1]) & m;
+        vrow.peak[0] ^= tp, vrow.peak[1] ^= tp, vrow.sq_hi[0] ^= th, vrow.sq_hi[1] ^= th, vrow.sq_lo[0] ^= tl, vrow.sq_lo[1] ^= tl;
+    }
+    shmt::fold(row, vrow);
+
+    __shared__ shmt::Row s_rows[4];
+    row = wave_fold_row<NCH, WIDE>(row);
+    if ((threadIdx.x & 63) == 0) {
+        shmt::Row& mine = s_rows[threadIdx.x >> 6];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) mine.peak[c] = row.peak[c], mine.sq_hi[c] = row.sq_hi[c], mine.sq_lo[c] = row.sq_lo[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const uint32_t c = threadIdx.x;
+        uint32_t peak = s_rows[0].peak[c];
+        uint64_t hi = s_rows[0].sq_hi[c], lo = s_rows[0].sq_lo[c];
+        for (int k = 1; k < 4; ++k) {
+            peak = s_rows[k].peak[c] > peak ? s_rows[k].peak[c] : peak;
+            hi += s_rows[k].sq_hi[c];
+            lo += s_rows[k].sq_lo[c];
+        }
+        shmt::Row* out = g.out + ((size_t)w * g.nplanes + r);
+        out->peak[c] = peak;
+        out->sq_hi[c] = hi;
+        out->sq_lo[c] = lo;
+    }
+}
+
+// the partial rows of a call whose blocks have 2^shift part slots into the table: one wave per row of the table -- the four waves of a
+// workgroup take four consecutive blocks of plane r0 + blockIdx.z -- its lanes over the slots, shmt::fold all the way, lane 0 stores the row
+__global__ __launch_bounds__(256) void k_pcm_level_fold(const shmt::Row* __restrict__ parts, uint32_t shift, uint64_t nblocks, uint32_t nplanes, uint32_t r0,
+                                                        shmt::Row* __restrict__ table) {
+    const uint64_t j = sh::block_id() * 4 + (threadIdx.x >> 6);
+    if (j >= nblocks) return;
+    const uint32_t r = r0 + blockIdx.z;
+    shmt::Row sum = shmt::zero();
+    for (uint64_t p = threadIdx.x & 63; p >> shift == 0; p += 64) shmt::fold(sum, parts[((j << shift) + p) * nplanes + r]);
+    sum = wave_fold_row<2, true>(sum);
+    if ((threadIdx.x & 63) == 0) table[j * nplanes + r] = sum;
+}
+
 // 24-bit <-> 32-bit: a thread converts four samples (12 bytes <-> 16 bytes); the 12 bytes are read / written as three
 // dwords when the 3-byte stream starts on a dword boundary, byte by byte otherwise (the tail always is).
 __global__ __launch_bounds__(256) void k_unpack24(const unsigned char* __restrict__ in, size_t n, int shift, int* __restrict__ out, int dwords) {
@@ -408,9 +572,90 @@ int pcm_stats(const char* who, const sh_buf* in, size_t nframes, int width, uint
     }
     return SH_OK;
 }
+
+// sh_pcm_level_blocks behind its checks: nblocks > 0 blocks of the planes at `base` (samples of T, `stride` apart) into rows, synchronously
+template <typename T>
+int level_blocks_run(const void* base, size_t stride, size_t nframes, int nch, uint32_t nplanes, uint64_t origin, uint64_t B,
+                     sh_seq_meter* rows, size_t nblocks) {
+    static_assert(sizeof(sh_seq_meter) == sizeof(shmt::Row), "sh_seq_meter is shmt::Row");
+    const char* fn = "sh_pcm_level_blocks";
+    LevelBlocks g{};
+    g.in = base, g.plane_samples = stride, g.n = nframes, g.origin = origin, g.B = B, g.first = origin / B;
+    g.shift = shpb::slot_shift(shpb::longest(origin, nframes, B) * (uint64_t)nch);
+    g.nwg = (uint64_t)nblocks << g.shift;
+    g.nplanes = nplanes;
+    if (g.nwg > (uint64_t)sh::GRID_X_MAX * 65535u) return sh::set_error(SH_ERR_INVALID, "%s: %llu parts of blocks are more than one launch takes", fn, (unsigned long long)g.nwg);
+    // the library's scratch, sized for the call: the table, and behind it the partial rows of a call whose blocks have more than one part
+    const size_t b_table = nblocks * (size_t)nplanes * sizeof(shmt::Row);
+    const size_t b_parts = g.shift ? (size_t)g.nwg * nplanes * sizeof(shmt::Row) : 0;
+    int rc = sh::ensure_scratch(b_table + b_parts);
+    if (rc) return rc;
+    shmt::Row* table = (shmt::Row*)sh::state().scratch;
+    g.out = g.shift ? table + nblocks * (size_t)nplanes : table;
+    hipStream_t st = sh::state().stream;
+    dim3 grid = sh::grid1d(g.nwg, 1);
+    for (g.r0 = 0; g.r0 < nplanes; g.r0 += 65535u) {          // (a grid's third dimension holds 65535 planes)
+        grid.z = nplanes - g.r0 < 65535u ? nplanes - g.r0 : 65535u;
+        if (nch == 1) hipLaunchKernelGGL((k_pcm_level_blocks<T, 1>), grid, dim3(256), 0, st, g);
+        else hipLaunchKernelGGL((k_pcm_level_blocks<T, 2>), grid, dim3(256), 0, st, g);
+        SH_CHECK_LAUNCH("k_pcm_level_blocks");
+    }
+    if (g.shift) {
+        grid = sh::grid1d(nblocks, 4);
+        for (uint32_t r0 = 0; r0 < nplanes; r0 += 65535u) {
+            grid.z = nplanes - r0 < 65535u ? nplanes - r0 : 65535u;
+            hipLaunchKernelGGL(k_pcm_level_fold, grid, dim3(256), 0, st, (const shmt::Row*)g.out, g.shift, (uint64_t)nblocks, nplanes, r0, table);
+            SH_CHECK_LAUNCH("k_pcm_level_fold");
+        }
+    }
+    SH_HIP(hipMemcpyAsync(rows, table, b_table, hipMemcpyDeviceToHost, st));
+    SH_HIP(hipStreamSynchronize(st));
+    return SH_OK;
+}
 }  // namespace
 
 extern "C" {
+
+int sh_pcm_level_blocks(const sh_buf* in, size_t sample_offset, size_t nframes, int nch, int width, size_t plane_samples, uint32_t nplanes,
+                        uint64_t origin_frame, uint64_t block_frames, sh_seq_meter* rows, size_t nblocks) {
+    SH_REQUIRE_INIT();
+    const char* fn = "sh_pcm_level_blocks";
+    if (!in) return sh::set_error(SH_ERR_INVALID, "%s: NULL buffer", fn);
+    if (nch != 1 && nch != 2) return sh::set_error(SH_ERR_INVALID, "%s: %d channels (1 or 2)", fn, nch);
+    if (!valid_width3(width)) return sh::set_error(SH_ERR_INVALID, "%s: sample width %d not in {1,2,3,4}", fn, width);
+    if (!block_frames) return sh::set_error(SH_ERR_INVALID, "%s: blocks of 0 frames", fn);
+    if (!nplanes) return sh::set_error(SH_ERR_INVALID, "%s: 0 planes", fn);
+    const size_t have = in->bytes / (size_t)width, n = nframes * (size_t)nch;
+    if (nplanes > 1 && (nframes > SIZE_MAX / (size_t)nch || plane_samples < n))
+        return sh::set_error(SH_ERR_INVALID, "%s: planes %llu samples apart for a window of %llu: they would overlap", fn,
+                             (unsigned long long)plane_samples, (unsigned long long)n);
+    bool inside = nframes <= SIZE_MAX / (size_t)nch && sample_offset <= have && n <= have - sample_offset;
+    if (inside && nplanes > 1) inside = plane_samples <= (have - sample_offset - n) / (nplanes - 1);
+    if (!inside)
+        return sh::set_error(SH_ERR_INVALID, "%s: the last of %u planes ends outside in (%llu samples from sample %llu on, planes %llu apart)", fn, nplanes,
+                             (unsigned long long)have, (unsigned long long)sample_offset, (unsigned long long)plane_samples);
+    if (origin_frame + nframes < origin_frame) return sh::set_error(SH_ERR_INVALID, "%s: the window ends past 2^64 frames", fn);
+    const uint64_t want = shpb::nblocks(origin_frame, nframes, block_frames);
+    if ((uint64_t)nblocks != want)
+        return sh::set_error(SH_ERR_INVALID, "%s: %llu blocks for a window of %llu (blocks of %llu frames)", fn, (unsigned long long)nblocks,
+                             (unsigned long long)want, (unsigned long long)block_frames);
+    if (!rows && nblocks) return sh::set_error(SH_ERR_INVALID, "%s: NULL rows", fn);
+    if (!nframes) return SH_OK;                               // an empty window: no block, nothing launched
+    const char* base = (const char*)in->ptr + sample_offset * (size_t)width;
+    if (width == 3) {                                         // the raw 24-bit values as int32, plane by plane into planes n samples apart
+        sh::Temp t32;
+        int rc = t32.alloc((size_t)nplanes * n * 4);
+        if (rc) return rc;
+        for (uint32_t r = 0; r < nplanes; ++r) {
+            rc = sh::unpack24(base + (size_t)r * plane_samples * 3, n, 0, (int32_t*)t32.buf.ptr + (size_t)r * n);
+            if (rc) return rc;
+        }
+        return level_blocks_run<int>(t32.buf.ptr, n, nframes, nch, nplanes, origin_frame, block_frames, rows, nblocks);
+    }
+    return dispatch_width(width, [&](auto tag) {
+        return level_blocks_run<decltype(tag)>(base, plane_samples, nframes, nch, nplanes, origin_frame, block_frames, rows, nblocks);
+    });
+}
 
 int sh_pcm_mul(const sh_buf* in, size_t in_off, size_t nbytes, int width, double factor, sh_buf* out, size_t out_off) {
     SH_REQUIRE_INIT();

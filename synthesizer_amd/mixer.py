@@ -811,20 +811,96 @@ class SongHistory:
         return "SongHistory(%d blocks of %d frames, frames [%d, %d))" % (self.nblocks, self.block_frames, self.start_frame, self.start_frame + self.frames)
 
 
+def _block_frames(who: str, block_frames) -> int:
+    if isinstance(block_frames, bool) or not isinstance(block_frames, (int, np.integer)) or block_frames <= 0:
+        raise ValueError("%s: block_frames is a positive int, not %r" % (who, block_frames))
+    return int(block_frames)
+
+
+def _levels_format(who: str, sample: Sample) -> None:
+    if sample.nchannels not in (1, 2):
+        raise ValueError("%s: a level history needs a mono or stereo sample, this one has %d channels" % (who, sample.nchannels))
+    if sample.samplewidth not in (1, 2, 3, 4):
+        raise ValueError("%s: a level history needs samples of 1 to 4 bytes, these have %d" % (who, sample.samplewidth))
+
+
+def _block_history(blocks, nrows: int, block_frames: int, start_frame: int, frames: int, samplewidth: int, nchannels: int, samplerate: int,
+                   ngroups: int = 0) -> SongHistory:
+    """``N.pcm_level_blocks``' array ``(nblocks, nrows)`` (None: an empty window) as a ``SongHistory`` on the grid of ``block_frames``"""
+    first = start_frame // block_frames
+    if blocks is None or not len(blocks):
+        empty = np.zeros((0, nrows, 2), dtype=np.uint64)
+        return SongHistory(empty, None, first, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups, parts=(empty, empty))
+    peak, hi, lo = blocks["peak"], blocks["sq_hi"], blocks["sq_lo"]
+    if frames * nchannels >= 1 << 32:
+        # SongHistory adds a table's two 64-bit sums 2^20 blocks at a time in uint64, which holds while a channel of the window has fewer
+        # than 2^32 samples (a sum is below 2^32 a sample); a longer window hands it Python ints
+        return SongHistory(peak, (hi.astype(object) << 32) + lo.astype(object), first, block_frames, start_frame, frames, samplewidth, nchannels,
+                           samplerate, ngroups)
+    return SongHistory(peak, None, first, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups, parts=(hi, lo))
+
+
+def level_history(sample: Sample, block_frames: int, origin_frame: int = 0) -> SongHistory:
+    """The levels of any ``Sample`` (a recording, a resampled file, a finished mix) OVER TIME, in one launch: a ``SongHistory`` with one
+    row per block, the master's -- ``history[j].master`` is the ``Levels`` of block ``j``: per channel ``peak`` (``audioop.max``) and the
+    exact integer ``sum_squares``, at every width.  Frame ``i`` of the sample stands at frame ``origin_frame + i`` of a grid of
+    ``block_frames`` frames, so the first and the last block may be partial and the halves of a sample cut on a block boundary give the
+    blocks of the whole.  ``total()``, ``fold(n)``, ``peaks()`` and ``starts`` are ``SongHistory``'s.  Mono and stereo only."""
+    block_frames = _block_frames("level_history", block_frames)
+    if isinstance(origin_frame, bool) or not isinstance(origin_frame, (int, np.integer)) or origin_frame < 0:
+        raise ValueError("level_history: origin_frame is a non-negative int, not %r" % (origin_frame,))
+    _levels_format("level_history", sample)
+    origin_frame, frames = int(origin_frame), len(sample)
+    nch, width = sample.nchannels, sample.samplewidth
+    blocks = N.pcm_level_blocks(sample._device(), 0, frames, nch, width, frames * nch, 1, origin_frame, block_frames) if frames else None
+    return _block_history(blocks, 1, block_frames, origin_frame, frames, width, nch, sample.samplerate)
+
+
 class SongStems:
     """The stems of a window of a song of tracks, made by ``CompiledSequence.stems``: every bus of the desk as a ``Sample`` of the window's
     length, all from one launch into one device buffer.  ``tracks[t]``: track ``t`` as its bus takes it -- behind its gain, its fader moves
     and its pan or pan ride; ``groups[g]``: group ``g``'s bus as the master takes it -- behind its gain, its ride and its pan or pan ride;
     ``master``: the bytes ``render`` returns for the same arguments.  Each is exactly the samples over which ``meters=True`` of the same call
     reads its row; a muted or skipped track or group is silence.  Every ``Sample`` is a view of the one buffer and keeps it alive on its
-    own, so it outlives this object."""
+    own, so it outlives this object.  ``level_history(block_frames)``: the levels of every stem per block of the song's frame grid, a
+    ``SongHistory`` with the rows and the meaning of ``render(meters="history")`` -- one launch over all planes where the object knows
+    its buffer (``buffer``, ``plane_frames``: the one device buffer and the planes' stride in frames; ``tile_frames``: the song's tile
+    in frames, the default block -- ``CompiledSequence.stems`` hands them on), one launch per row where it was built by hand."""
 
-    def __init__(self, tracks: Sequence[Sample], master: Sample, groups: Sequence[Sample], start_frame: int, frames: int) -> None:
+    def __init__(self, tracks: Sequence[Sample], master: Sample, groups: Sequence[Sample], start_frame: int, frames: int, *,
+                 buffer: Optional[N.DeviceBuffer] = None, plane_frames: Optional[int] = None, tile_frames: Optional[int] = None) -> None:
         self.tracks = list(tracks)
         self.master = master
         self.groups = list(groups)
         self.start_frame = int(start_frame)
         self.frames = int(frames)
+        if (buffer is None) != (plane_frames is None):
+            raise ValueError("SongStems: buffer and plane_frames come together")
+        self._buffer = buffer
+        self._plane_frames = None if plane_frames is None else int(plane_frames)
+        self._tile_frames = None if tile_frames is None else int(tile_frames)
+
+    def level_history(self, block_frames: Optional[int] = None) -> SongHistory:
+        """The levels of every stem OVER TIME: a ``SongHistory`` whose rows are the tracks, the master and the groups, block ``i`` covering
+        song frames ``[i * block_frames, (i + 1) * block_frames)`` cut to the window (``block_frames`` None: the song's tile, the block
+        of ``render(meters="history")``).  Exact integers read off the stems' own samples (sh_pcm_level_blocks)."""
+        master = self.master
+        nch, width, rate = master.nchannels, master.samplewidth, master.samplerate
+        if block_frames is None:
+            block_frames = self._tile_frames if self._tile_frames is not None else max(1, N.SEQ_TILE_SAMPLES[width] // nch)
+        block_frames = _block_frames("SongStems", block_frames)
+        _levels_format("SongStems", master)
+        rows = self.rows()
+        if any((s.nchannels, s.samplewidth, len(s)) != (nch, width, self.frames) for s in rows):
+            raise ValueError("SongStems: every stem has the master's format and the window's %d frames" % self.frames)
+        blocks = None
+        if self.frames:
+            if self._buffer is not None:
+                blocks = N.pcm_level_blocks(self._buffer, 0, self.frames, nch, width, self._plane_frames * nch, len(rows), self.start_frame, block_frames)
+            else:
+                blocks = np.concatenate([N.pcm_level_blocks(s._device(), 0, self.frames, nch, width, self.frames * nch, 1, self.start_frame, block_frames)
+                                         for s in rows], axis=1)
+        return _block_history(blocks, len(rows), block_frames, self.start_frame, self.frames, width, nch, rate, len(self.groups))
 
     def rows(self) -> list:
         """all of them in plane order, which is the meter rows': the tracks, the master, the groups"""
@@ -940,7 +1016,10 @@ class CompiledSequence:
     own frames, ``total()`` the one it gives for the window, ``fold(n)`` coarser blocks, ``peaks()`` an array to draw.  Blocks are
     anchored to the song, so a block that lies whole inside two windows reads the same from both.  With gains, pans, master, groups
     and the tracks' fader moves.  Not built (``NotImplementedError``): a history with an ``Automation`` that rides a bus or a pan; a
-    history without rendering the bytes.
+    history without rendering the bytes.  The route for a desk that RIDES, and for blocks of any size: ``level_history(...)`` --
+    ``stems(...)`` of the same desk, every one the song can make, and then ``SongStems.level_history``, the levels per block read off
+    the stems' own samples: two launches, the same rows in the same order (tracks, master, groups), ``total()`` what ``meters=True``
+    gives.
     The desk's OVERS: with ``meters="history"`` the same calls take ``clips=True``, and the ``SongHistory`` then says, still from that one
     launch, which bus clipped and where: ``clipped()`` per block, row (tracks, master, groups) and channel, ``Levels.clipped`` in every
     block's levels, ``total()`` and ``fold(n)`` adding the counts.  ``clipped`` is the number of samples of that channel in the block at
@@ -1163,7 +1242,8 @@ class CompiledSequence:
 
     @staticmethod
     def _no_history_of(meters, automation) -> None:
-        """a level history with an ``Automation`` that rides a bus or a pan: not built -- said before anything is launched"""
+        """a level history with an ``Automation`` that rides a bus or a pan: not built in the riding kernels -- said before anything is
+        launched.  The route for such a desk is ``level_history(...)``: its stems, and their levels per block (two launches)."""
         if meters == "history" and automation is not None and (automation.master or automation.rides or automation.pan_segments is not None):
             raise NotImplementedError("CompiledSequence: rides of buses and pans have no level history yet (meters=\"history\" with an "
                                       "Automation that has master, group or pan pieces)")
@@ -1675,13 +1755,26 @@ class CompiledSequence:
         nrows = self.ntracks + 1 + ngroups
         names = ["%s:track %d" % (self.name, t) for t in range(self.ntracks)] + ["%s:master" % self.name] + ["%s:group %d" % (self.name, g) for g in range(ngroups)]
         outs = [Sample(name=n, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth) for n in names]
+        buf = plane_frames = None
         if nframes:
             plane_frames = self.stems_plane_frames(nframes, self.nchannels, self.samplewidth)
             buf = N.DeviceBuffer(nrows * plane_frames * self._fb)
             self.stems_into(buf, 0, plane_frames, start_frame, nframes, gains=gains, pans=pans, master=master, automation=automation, groups=groups)
             for r, out in enumerate(outs):
                 out._set_device(buf.view(r * plane_frames * self._fb, nframes * self._fb), nframes * self._fb)
-        return SongStems(outs[:self.ntracks], outs[self.ntracks], outs[self.ntracks + 1:], start_frame, nframes)
+        return SongStems(outs[:self.ntracks], outs[self.ntracks], outs[self.ntracks + 1:], start_frame, nframes, buffer=buf, plane_frames=plane_frames,
+                         tile_frames=max(1, N.SEQ_TILE_SAMPLES[self.samplewidth] // self.nchannels))
+
+    def level_history(self, start_frame: int = 0, nframes: Optional[int] = None, block_frames: Optional[int] = None,
+                      gains: Optional[Sequence[float]] = None, pans: Optional[Sequence] = None, master: Optional[float] = None,
+                      automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> SongHistory:
+        """The levels of frames ``[start_frame, start_frame + nframes)`` OVER TIME for EVERY desk ``stems`` takes, rides of buses and pan
+        rides included: ``stems(...)`` followed by ``SongStems.level_history(block_frames)`` -- two launches.  The ``SongHistory`` has the
+        shape and the meaning of ``render(meters="history")``'s (rows: tracks, master, groups; ``total()`` what ``meters=True`` gives);
+        ``block_frames`` None: the song's tile in frames, else any positive int.  The bytes are not returned: ``stems`` keeps them."""
+        if block_frames is not None:
+            block_frames = _block_frames("CompiledSequence", block_frames)
+        return self.stems(start_frame, nframes, gains=gains, pans=pans, master=master, automation=automation, groups=groups).level_history(block_frames)
 
     def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None, meters: bool = False, pans: Optional[Sequence] = None,
                master: Optional[float] = None, automation: Optional[Automation] = None, groups: Optional[Sequence] = None,

@@ -1100,6 +1100,12 @@ class Sample:
         from math import sqrt
         return int(sqrt(sq.value / float(n)))
 
+    def level_history(self, block_frames: int, origin_frame: int = 0):
+        """The levels over time, per block of ``block_frames`` frames, in one launch: ``mixer.level_history(self, ...)``'s ``SongHistory``
+        (one row per block, ``history[j].master``; exact integer sums at every width)."""
+        from .mixer import level_history                        # (lazily: mixer imports this module)
+        return level_history(self, block_frames, origin_frame)
+
     def _channel_stats(self) -> Tuple[Tuple[int, int], Tuple[float, float]]:
         """((max|L|, max|R|), (sum L^2, sum R^2)) of a stereo sample, one pass on the device."""
         mx = (C.c_uint32 * 2)()
