@@ -462,6 +462,22 @@ class RtLane:
             pass
 
 
+def _doubles(v):
+    """None, or a C array of doubles (of one element at least)"""
+    return None if v is None else (C.c_double * max(1, len(v)))(*v)
+
+
+def _count(v) -> int:
+    return 0 if v is None else len(v)
+
+
+def _group_table(groups) -> tuple:
+    """(the sh_seq_group table of a desk's groups, their number): (None, 0) where there are none"""
+    if not groups:
+        return None, 0
+    return (SeqGroup * len(groups))(*[SeqGroup(*g) for g in groups]), len(groups)
+
+
 class Sequence:
     """RAII wrapper over sh_seq: a list of placed samples compiled once (records and per-tile index resident on the device), rendered
     window by window.  ``sources`` are the DeviceBuffers the records point into: the handle keeps them alive.  ``track_first`` (one offset
@@ -518,12 +534,6 @@ class Sequence:
             raise ValueError("Sequence.render: meters is True, False or \"history\", not %r" % (meters,))
         if clips and meters != "history":
             raise ValueError("Sequence.render: clips=True counts per block of a history: it needs meters=\"history\"")
-
-        def doubles(v):
-            return None if v is None else (C.c_double * max(1, len(v)))(*v)
-
-        def count(v):
-            return 0 if v is None else len(v)
         desk = pans is not None or master is not None
         rows, nrows = None, 0
         if meters == "history":
@@ -532,32 +542,32 @@ class Sequence:
             nrows = self.tracks()[0] + 1 + (len(groups) if groups else 0)
             blocks = np.zeros((nblocks, nrows), dtype=SEQ_METER_CLIPS_DTYPE if clips else SEQ_METER_DTYPE)
             rows = blocks.ctypes.data_as(C.POINTER(SeqMeterClips if clips else SeqMeter)) if nblocks else None
-            table = (SeqGroup * len(groups))(*[SeqGroup(*g) for g in groups]) if groups else None
+            table, ngroups = _group_table(groups)
             entry = lib().sh_seq_render_clips if clips else lib().sh_seq_render_history
-            check(entry(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans),
-                                              count(pans), 1.0 if master is None else master, rows, nrows, nblocks,
-                                              None if automation is None else automation.handle, table, len(groups) if groups else 0))
+            check(entry(self._h, first_sample, nsamples, out.handle, out_sample, _doubles(gains), _count(gains), _doubles(pans),
+                                              _count(pans), 1.0 if master is None else master, rows, nrows, nblocks,
+                                              None if automation is None else automation.handle, table, ngroups))
             return blocks
         if meters:
             nrows = self.tracks()[0] + 1 + (len(groups) if groups else 0)
             rows = (SeqMeter * nrows)()
         if groups:
-            table = (SeqGroup * len(groups))(*[SeqGroup(*g) for g in groups])
-            check(lib().sh_seq_render_groups(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans),
-                                             count(pans), 1.0 if master is None else master, rows, nrows,
-                                             None if automation is None else automation.handle, table, len(groups)))
+            table, ngroups = _group_table(groups)
+            check(lib().sh_seq_render_groups(self._h, first_sample, nsamples, out.handle, out_sample, _doubles(gains), _count(gains), _doubles(pans),
+                                             _count(pans), 1.0 if master is None else master, rows, nrows,
+                                             None if automation is None else automation.handle, table, ngroups))
         elif automation is not None:
-            check(lib().sh_seq_render_auto(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans), count(pans),
+            check(lib().sh_seq_render_auto(self._h, first_sample, nsamples, out.handle, out_sample, _doubles(gains), _count(gains), _doubles(pans), _count(pans),
                                            1.0 if master is None else master, rows, nrows, automation.handle))
         elif desk:
-            check(lib().sh_seq_render_desk(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), doubles(pans), count(pans),
+            check(lib().sh_seq_render_desk(self._h, first_sample, nsamples, out.handle, out_sample, _doubles(gains), _count(gains), _doubles(pans), _count(pans),
                                            1.0 if master is None else master, rows, nrows))
         elif meters:
-            check(lib().sh_seq_render_meters(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), count(gains), rows, nrows))
+            check(lib().sh_seq_render_meters(self._h, first_sample, nsamples, out.handle, out_sample, _doubles(gains), _count(gains), rows, nrows))
         elif gains is None:
             check(lib().sh_seq_render(self._h, first_sample, nsamples, out.handle, out_sample))
         else:
-            check(lib().sh_seq_render_gains(self._h, first_sample, nsamples, out.handle, out_sample, doubles(gains), len(gains)))
+            check(lib().sh_seq_render_gains(self._h, first_sample, nsamples, out.handle, out_sample, _doubles(gains), len(gains)))
         if meters:
             return [((r.peak[0], r.peak[1]), ((r.sq_hi[0] << 32) + r.sq_lo[0], (r.sq_hi[1] << 32) + r.sq_lo[1])) for r in rows]
 
@@ -566,15 +576,9 @@ class Sequence:
         """sh_seq_render_stems (a song of tracks): the desk of ``render`` with the same keywords, and instead of the master alone
         ``ntracks + 1 + len(groups)`` planes of ``nsamples`` samples, ``plane_samples`` apart from ``out_sample`` on, in the meter rows'
         order -- the tracks as their bus takes them, the master, the groups as the master takes them.  One launch, asynchronous."""
-        def doubles(v):
-            return None if v is None else (C.c_double * max(1, len(v)))(*v)
-
-        def count(v):
-            return 0 if v is None else len(v)
-        ngroups = len(groups) if groups else 0
-        table = (SeqGroup * ngroups)(*[SeqGroup(*g) for g in groups]) if ngroups else None
+        table, ngroups = _group_table(groups)
         check(lib().sh_seq_render_stems(self._h, first_sample, nsamples, out.handle, out_sample, plane_samples, self.tracks()[0] + 1 + ngroups,
-                                        doubles(gains), count(gains), doubles(pans), count(pans), 1.0 if master is None else master,
+                                        _doubles(gains), _count(gains), _doubles(pans), _count(pans), 1.0 if master is None else master,
                                         None if automation is None else automation.handle, table, ngroups))
 
     def free(self) -> None:

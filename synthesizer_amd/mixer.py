@@ -23,7 +23,7 @@ import gc
 import math
 import operator
 import threading
-from typing import Callable, Dict, Generator, List, Optional, Sequence, Tuple, Union
+from typing import Callable, Dict, Generator, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -714,19 +714,29 @@ class SongHistory:
     @classmethod
     def from_blocks(cls, blocks, nrows: int, tile_samples: int, start_frame: int, frames: int, samplewidth: int, nchannels: int, samplerate: int,
                     ngroups: int = 0, clips: bool = False) -> "SongHistory":
-        """``blocks``: ``N.Sequence.render(meters="history")``'s array ``(nblocks, nrows)`` of sh_seq_meter rows (with ``clips=True`` of
-        sh_seq_meter_clips rows: the field ``clipped`` says so), or None for an empty window, whose history has counts where ``clips``"""
+        """``of_blocks`` on the grid of a song's tile: ``tile_samples`` samples over the channels"""
+        return cls.of_blocks(blocks, nrows, tile_samples // nchannels, start_frame, frames, samplewidth, nchannels, samplerate, ngroups, clips)
+
+    @classmethod
+    def of_blocks(cls, blocks, nrows: int, block_frames: int, start_frame: int, frames: int, samplewidth: int, nchannels: int, samplerate: int,
+                  ngroups: int = 0, clips: bool = False) -> "SongHistory":
+        """``blocks``: an array ``(nblocks, nrows)`` of sh_seq_meter rows on the grid of ``block_frames`` -- ``N.Sequence.render(meters=
+        "history")``'s or ``N.pcm_level_blocks``' (with ``clips=True`` the render's are sh_seq_meter_clips rows: the field ``clipped`` says
+        so) -- or None for an empty window, whose history has counts where ``clips``"""
         counted = clips if blocks is None else "clipped" in (blocks.dtype.names or ())
+        first = start_frame // block_frames
         if blocks is None or not len(blocks):
-            peak = np.zeros((0, nrows, 2), dtype=np.uint32)
-            parts = (np.zeros((0, nrows, 2), dtype=np.uint64),) * 2
-            clipped = np.zeros((0, nrows, 2), dtype=np.uint64) if counted else None
-        else:
-            peak, parts = blocks["peak"], (blocks["sq_hi"], blocks["sq_lo"])
-            clipped = blocks["clipped"] if counted else None
-        block_frames = tile_samples // nchannels
-        return cls(peak, None, start_frame // block_frames, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups, parts=parts,
-                   clipped=clipped)
+            empty = np.zeros((0, nrows, 2), dtype=np.uint64)
+            return cls(empty, None, first, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups, parts=(empty, empty),
+                       clipped=empty if counted else None)
+        peak, hi, lo = blocks["peak"], blocks["sq_hi"], blocks["sq_lo"]
+        clipped = blocks["clipped"] if counted else None
+        if frames * nchannels >= 1 << 32:
+            # _sums adds a table's two 64-bit sums 2^20 blocks at a time in uint64, which holds while a channel of the window has fewer
+            # than 2^32 samples (a sum is below 2^32 a sample); a longer window hands over Python ints
+            return cls(peak, (hi.astype(object) << 32) + lo.astype(object), first, block_frames, start_frame, frames, samplewidth, nchannels,
+                       samplerate, ngroups, clipped=clipped)
+        return cls(peak, None, first, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups, parts=(hi, lo), clipped=clipped)
 
     @property
     def sum_squares(self) -> np.ndarray:
@@ -824,22 +834,6 @@ def _levels_format(who: str, sample: Sample) -> None:
         raise ValueError("%s: a level history needs samples of 1 to 4 bytes, these have %d" % (who, sample.samplewidth))
 
 
-def _block_history(blocks, nrows: int, block_frames: int, start_frame: int, frames: int, samplewidth: int, nchannels: int, samplerate: int,
-                   ngroups: int = 0) -> SongHistory:
-    """``N.pcm_level_blocks``' array ``(nblocks, nrows)`` (None: an empty window) as a ``SongHistory`` on the grid of ``block_frames``"""
-    first = start_frame // block_frames
-    if blocks is None or not len(blocks):
-        empty = np.zeros((0, nrows, 2), dtype=np.uint64)
-        return SongHistory(empty, None, first, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups, parts=(empty, empty))
-    peak, hi, lo = blocks["peak"], blocks["sq_hi"], blocks["sq_lo"]
-    if frames * nchannels >= 1 << 32:
-        # SongHistory adds a table's two 64-bit sums 2^20 blocks at a time in uint64, which holds while a channel of the window has fewer
-        # than 2^32 samples (a sum is below 2^32 a sample); a longer window hands it Python ints
-        return SongHistory(peak, (hi.astype(object) << 32) + lo.astype(object), first, block_frames, start_frame, frames, samplewidth, nchannels,
-                           samplerate, ngroups)
-    return SongHistory(peak, None, first, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups, parts=(hi, lo))
-
-
 def level_history(sample: Sample, block_frames: int, origin_frame: int = 0) -> SongHistory:
     """The levels of any ``Sample`` (a recording, a resampled file, a finished mix) OVER TIME, in one launch: a ``SongHistory`` with one
     row per block, the master's -- ``history[j].master`` is the ``Levels`` of block ``j``: per channel ``peak`` (``audioop.max``) and the
@@ -853,7 +847,7 @@ def level_history(sample: Sample, block_frames: int, origin_frame: int = 0) -> S
     origin_frame, frames = int(origin_frame), len(sample)
     nch, width = sample.nchannels, sample.samplewidth
     blocks = N.pcm_level_blocks(sample._device(), 0, frames, nch, width, frames * nch, 1, origin_frame, block_frames) if frames else None
-    return _block_history(blocks, 1, block_frames, origin_frame, frames, width, nch, sample.samplerate)
+    return SongHistory.of_blocks(blocks, 1, block_frames, origin_frame, frames, width, nch, sample.samplerate)
 
 
 class SongStems:
@@ -900,7 +894,7 @@ class SongStems:
             else:
                 blocks = np.concatenate([N.pcm_level_blocks(s._device(), 0, self.frames, nch, width, self.frames * nch, 1, self.start_frame, block_frames)
                                          for s in rows], axis=1)
-        return _block_history(blocks, len(rows), block_frames, self.start_frame, self.frames, width, nch, rate, len(self.groups))
+        return SongHistory.of_blocks(blocks, len(rows), block_frames, self.start_frame, self.frames, width, nch, rate, len(self.groups))
 
     def rows(self) -> list:
         """all of them in plane order, which is the meter rows': the tracks, the master, the groups"""
@@ -945,6 +939,11 @@ class Automation:
         else:
             self._auto = N.SeqAutomation(song._handle(), segments, seg_first)
 
+    @property
+    def rides_buses(self) -> bool:
+        """whether a piece rides a bus or a pan: the master's fader, a group's, a track's pan or a group's"""
+        return bool(self.master or self.rides or self.pan_segments is not None)
+
     def _handle(self) -> "N.SeqAutomation":
         if self._auto is None:
             raise ValueError("Automation: closed")
@@ -966,6 +965,80 @@ class Automation:
             self.close()
         except Exception:
             pass
+
+
+class _LaneKind(NamedTuple):
+    """what a lane of an ``Automation`` rides: the word in its pieces' names and messages, the low end of its range (the high end is
+    1.0), and whether a piece at exactly (1.0, 1.0) is dropped"""
+    name: str
+    low: float
+    drops_unity: bool
+
+
+_FADER_LANE = _LaneKind("volume", 0.0, True)        # a hold at 1.0 is no step
+_PAN_LANE = _LaneKind("pan", -1.0, False)           # every piece kept: a hold at any pan stands in place of the static one
+
+
+def _pan_factors(pan, who: str, index: int, strings: bool = True) -> Tuple[float, float]:
+    """one pan entry of a desk that is not None (None is (1.0, 1.0), at the caller) -- a number -1 .. 1 or a pair of factors -- as
+    ``(left_factor, right_factor)``; ``who % index`` opens the messages (``pan 2``, ``group 1: pan``), and where ``strings`` is False a ``str`` is no number"""
+    if isinstance(pan, (tuple, list)):
+        try:
+            factors = (float(pan[0]), float(pan[1])) if len(pan) == 2 else None
+        except (TypeError, ValueError):
+            factors = None
+        if factors is None or not (math.isfinite(factors[0]) and math.isfinite(factors[1])):
+            raise ValueError("CompiledSequence: " + who % index + " is not a pair (left_factor, right_factor) of finite numbers")
+        return factors
+    try:
+        if not strings and isinstance(pan, (str, bytes)):
+            raise TypeError
+        pan = float(pan)
+    except (TypeError, ValueError):
+        raise ValueError("CompiledSequence: " + who % index + " is None, a number or a pair (left_factor, right_factor)") from None
+    if not -1.0 <= pan <= 1.0:
+        raise ValueError("CompiledSequence: " + who % index + " must be between -1 and 1")
+    return (1.0 - pan) / 2.0, (1.0 + pan) / 2.0             # Sample.pan: Python floats, on the host
+
+
+class _DeskCall(NamedTuple):
+    """The desk of one call of a compiled song, checked (``CompiledSequence._desk_call``): ``gains`` None or a list of floats, ``meters``
+    False, True or "history", ``pans`` None or the flat factors, ``master`` None or a float, ``automation`` None or the ``Automation``,
+    ``groups`` None or the table's rows, ``clips`` a bool, ``ngroups`` the number of groups -- None wherever the desk has no such step."""
+    gains: Optional[list]
+    meters: Union[bool, str]
+    pans: Optional[list]
+    master: Optional[float]
+    automation: Optional[Automation]
+    groups: Optional[list]
+    clips: bool
+    ngroups: int
+
+    def render_keywords(self) -> dict:
+        """The keywords ``N.Sequence.render`` is handed, which pick its entry point: none at all for a plain render; ``gains`` (and
+        ``meters`` where asked for) alone where the desk has no step; else ``pans`` and ``master`` with them, ``groups`` and ``automation``
+        only where there are some; ``clips`` only where asked for."""
+        gains, meters, pans, master, automation, groups, clips, _ = self
+        if pans is None and master is None and automation is None and groups is None:
+            if gains is None and not meters:
+                return {}                                       # a plain render: the entry point there was before there were tracks
+            keywords = {"gains": gains}
+        else:
+            keywords = {"gains": gains, "pans": pans, "master": master}
+            if groups is not None:
+                keywords["groups"] = groups
+            if automation is not None:
+                keywords["automation"] = automation._handle()
+        if meters:
+            keywords["meters"] = meters
+        if clips:
+            keywords["clips"] = True
+        return keywords
+
+    def stems_keywords(self) -> dict:
+        """the keywords ``N.Sequence.stems`` is handed: always all five"""
+        return {"gains": self.gains, "pans": self.pans, "master": self.master, "groups": self.groups,
+                "automation": None if self.automation is None else self.automation._handle()}
 
 
 class CompiledSequence:
@@ -1244,7 +1317,7 @@ class CompiledSequence:
     def _no_history_of(meters, automation) -> None:
         """a level history with an ``Automation`` that rides a bus or a pan: not built in the riding kernels -- said before anything is
         launched.  The route for such a desk is ``level_history(...)``: its stems, and their levels per block (two launches)."""
-        if meters == "history" and automation is not None and (automation.master or automation.rides or automation.pan_segments is not None):
+        if meters == "history" and automation is not None and automation.rides_buses:
             raise NotImplementedError("CompiledSequence: rides of buses and pans have no level history yet (meters=\"history\" with an "
                                       "Automation that has master, group or pan pieces)")
 
@@ -1256,14 +1329,14 @@ class CompiledSequence:
             return False
         if meters != "history":
             raise ValueError("CompiledSequence: clips=True counts the overs per block of a level history: it needs meters=\"history\"")
-        if automation is not None and (automation.master or automation.rides or automation.pan_segments is not None):
+        if automation is not None and automation.rides_buses:
             raise NotImplementedError("CompiledSequence: overs are not counted through rides of buses and pans yet (clips=True with an "
                                       "Automation that has master, group or pan pieces)")
         return True
 
     def _history(self, blocks, start_frame: int, nframes: int, ngroups: int, clips: bool = False) -> SongHistory:
-        return SongHistory.from_blocks(blocks, self.ntracks + 1 + ngroups, N.SEQ_TILE_SAMPLES[self.samplewidth], start_frame, nframes, self.samplewidth, self.nchannels,
-                                       self.samplerate, ngroups, clips=clips)
+        return SongHistory.of_blocks(blocks, self.ntracks + 1 + ngroups, N.SEQ_TILE_SAMPLES[self.samplewidth] // self.nchannels, start_frame, nframes,
+                                     self.samplewidth, self.nchannels, self.samplerate, ngroups, clips=clips)
 
     def _pans(self, pans) -> Optional[list]:
         """``pans`` as render hands them on: None (no track has a pan step), or ``2 * ntracks`` finite floats, left then right per track,
@@ -1278,27 +1351,8 @@ class CompiledSequence:
             raise ValueError("CompiledSequence: pans is a sequence, one entry per track")
         if len(pans) != self.ntracks:
             raise ValueError("CompiledSequence: %d pans for %d tracks" % (len(pans), self.ntracks))
-        out = []
-        for t, pan in enumerate(pans):
-            if pan is None:
-                factors = (1.0, 1.0)
-            elif isinstance(pan, (tuple, list)):
-                try:
-                    factors = (float(pan[0]), float(pan[1])) if len(pan) == 2 else None
-                except (TypeError, ValueError):
-                    factors = None
-                if factors is None or not (math.isfinite(factors[0]) and math.isfinite(factors[1])):
-                    raise ValueError("CompiledSequence: pan %d is not a pair (left_factor, right_factor) of finite numbers" % t)
-            else:
-                try:
-                    pan = float(pan)
-                except (TypeError, ValueError):
-                    raise ValueError("CompiledSequence: pan %d is None, a number or a pair (left_factor, right_factor)" % t) from None
-                if not -1.0 <= pan <= 1.0:
-                    raise ValueError("CompiledSequence: pan %d must be between -1 and 1" % t)
-                factors = ((1.0 - pan) / 2.0, (1.0 + pan) / 2.0)    # Sample.pan: Python floats, on the host
-            out.extend(factors)
-        return None if all(f == 1.0 for f in out) else out
+        out = [f for t, pan in enumerate(pans) for f in ((1.0, 1.0) if pan is None else _pan_factors(pan, "pan %d", t))]
+        return None if out.count(1.0) == len(out) else out        # (every factor == 1.0: no track has a pan step)
 
     def _master(self, master) -> Optional[float]:
         """``master`` as render hands it on: None (no step: None or exactly 1.0) or a finite float -- checked before anything is launched"""
@@ -1314,18 +1368,6 @@ class CompiledSequence:
             raise ValueError("CompiledSequence: master is not finite")
         return None if master == 1.0 else master
 
-    @staticmethod
-    def _desk(pans, master, automation=None, groups=None) -> dict:
-        """the keywords of the desk for N.Sequence.render: none at all where no step is asked for (the entry points there were)"""
-        if groups is not None:
-            desk = {"pans": pans, "master": master, "groups": groups}
-            if automation is not None:
-                desk["automation"] = automation
-            return desk
-        if automation is not None:
-            return {"pans": pans, "master": master, "automation": automation}
-        return {} if pans is None and master is None else {"pans": pans, "master": master}
-
     MAX_GROUPS = N.SEQ_MAX_GROUPS
 
     def _groups(self, groups) -> Optional[list]:
@@ -1340,73 +1382,72 @@ class CompiledSequence:
             raise ValueError("CompiledSequence: groups is a sequence of (first_track, end_track, gain) or (first_track, end_track, gain, pan)")
         if len(groups) > self.MAX_GROUPS:
             raise ValueError("CompiledSequence: %d groups, at most %d" % (len(groups), self.MAX_GROUPS))
-        out, prev = [], 0
+        out, prev, where = [], 0, "CompiledSequence: group %d: "
         for k, entry in enumerate(groups):
-            where = "CompiledSequence: group %d: " % k
             if isinstance(entry, (str, bytes)) or not hasattr(entry, "__len__") or len(entry) not in (3, 4):
-                raise ValueError(where + "an entry is (first_track, end_track, gain) or (first_track, end_track, gain, pan)")
+                raise ValueError(where % k + "an entry is (first_track, end_track, gain) or (first_track, end_track, gain, pan)")
             try:
                 if isinstance(entry[0], bool) or isinstance(entry[1], bool):
                     raise TypeError
                 first, end = operator.index(entry[0]), operator.index(entry[1])
             except TypeError:
-                raise ValueError(where + "first_track and end_track are integers") from None
+                raise ValueError(where % k + "first_track and end_track are integers") from None
             if first < 0 or end > self.ntracks:
-                raise ValueError(where + "tracks [%d, %d) outside the song's %d tracks" % (first, end, self.ntracks))
+                raise ValueError(where % k + "tracks [%d, %d) outside the song's %d tracks" % (first, end, self.ntracks))
             if first >= end:
-                raise ValueError(where + "tracks [%d, %d): an empty range" % (first, end))
+                raise ValueError(where % k + "tracks [%d, %d): an empty range" % (first, end))
             if first < prev:
-                raise ValueError(where + "starts at track %d, before the group in front of it ends (%d)" % (first, prev))
+                raise ValueError(where % k + "starts at track %d, before the group in front of it ends (%d)" % (first, prev))
             gain = 1.0 if entry[2] is None else entry[2]
             try:
                 if isinstance(gain, (str, bytes)):
                     raise TypeError
                 gain = float(gain)
             except (TypeError, ValueError):
-                raise ValueError(where + "gain is None or a finite number") from None
+                raise ValueError(where % k + "gain is None or a finite number") from None
             if not math.isfinite(gain):
-                raise ValueError(where + "gain is not finite")
+                raise ValueError(where % k + "gain is not finite")
             pan = entry[3] if len(entry) == 4 else None
             if pan is None:
                 factors = (1.0, 1.0)
             elif self.nchannels != 2:
-                raise ValueError(where + "a pan needs a stereo song, this one has %d channels" % self.nchannels)
-            elif isinstance(pan, (tuple, list)):
-                try:
-                    factors = (float(pan[0]), float(pan[1])) if len(pan) == 2 else None
-                except (TypeError, ValueError):
-                    factors = None
-                if factors is None or not (math.isfinite(factors[0]) and math.isfinite(factors[1])):
-                    raise ValueError(where + "pan is not a pair (left_factor, right_factor) of finite numbers")
+                raise ValueError(where % k + "a pan needs a stereo song, this one has %d channels" % self.nchannels)
             else:
-                try:
-                    if isinstance(pan, (str, bytes)):
-                        raise TypeError
-                    pan = float(pan)
-                except (TypeError, ValueError):
-                    raise ValueError(where + "pan is None, a number or a pair (left_factor, right_factor)") from None
-                if not -1.0 <= pan <= 1.0:
-                    raise ValueError(where + "pan must be between -1 and 1")
-                factors = ((1.0 - pan) / 2.0, (1.0 + pan) / 2.0)    # Sample.pan: Python floats, on the host
+                factors = _pan_factors(pan, "group %d: pan", k, strings=False)
             prev = end
             out.append((first, end, gain, factors[0], factors[1]))
         return out or None
 
-    def _automation(self, automation, groups=None) -> Optional["N.SeqAutomation"]:
-        """``automation`` as render hands it on: None, or the native handle of an ``Automation`` that THIS song made; one that rides
-        group ``g`` needs a render that names more than ``g`` groups (``groups``: what ``_groups`` made of the render's) -- checked before
-        anything is launched"""
+    def _automation(self, automation, groups=None) -> Optional[Automation]:
+        """``automation`` as a call takes it: None, or an open ``Automation`` that THIS song made; one that rides group ``g`` needs a
+        render that names more than ``g`` groups (``groups``: what ``_groups`` made of the render's) -- checked before anything is
+        launched"""
         if automation is None:
             return None
         if not isinstance(automation, Automation) or automation._song is not self:
             raise ValueError("CompiledSequence: automation is None or an Automation made by this song's automation()")
-        handle = automation._handle()
+        automation._handle()
         if automation.rides > len(groups or ()):
             raise ValueError("CompiledSequence: the automation rides group %d, and this render names %d groups" % (automation.rides - 1, len(groups or ())))
         if automation.pan_rides > len(groups or ()):
             raise ValueError("CompiledSequence: the automation rides the pan of group %d, and this render names %d groups"
                              % (automation.pan_rides - 1, len(groups or ())))
-        return handle
+        return automation
+
+    def _desk_call(self, gains, meters, pans, master, automation, groups, clips, *, stems: bool = False) -> _DeskCall:
+        """Every check of a call's desk, once and in one order, whichever door the call came through -- before a buffer is made or
+        anything is launched: the song is open, (``stems``) has tracks, then gains, meters, groups, pans, master, the automation against
+        the checked groups, clips, and the history that rides do not have."""
+        self._handle()
+        if stems and self.ntracks is None:
+            raise ValueError("CompiledSequence: stems need a song of tracks (compile_tracks); this one has none")
+        gains = self._gains(gains)
+        meters = self._meters(meters)
+        groups = self._groups(groups)
+        call = _DeskCall(gains, meters, self._pans(pans), self._master(master), self._automation(automation, groups), groups,
+                         self._clips(clips, meters, automation), len(groups or ()))
+        self._no_history_of(meters, automation)
+        return call
 
     def automation(self, lanes, master=None, groups=None, pans=None, group_pans=None) -> Automation:
         """The fader moves of this song of tracks (``CompiledSequence`` has the chain): ``lanes`` has one entry per track, None or a list
@@ -1432,7 +1473,7 @@ class CompiledSequence:
         return Automation(self, pieces, segments, seg_first, master, groups, pans, group_pans, pan_segments, pan_first)
 
     def _check_pan_lanes(self, pans, group_pans) -> tuple:
-        """(the tracks' pan lanes, the groups' pan lanes), checked: ``()`` for None, else every lane through ``_check_pan_lane``"""
+        """(the tracks' pan lanes, the groups' pan lanes), checked: ``()`` for None, else every lane through ``_check_lane``"""
         if pans is None and group_pans is None:
             return (), ()
         if self.nchannels != 2:
@@ -1447,62 +1488,16 @@ class CompiledSequence:
                 raise ValueError("CompiledSequence: automation: group_pans is None or a sequence, one entry per group")
             if len(group_pans) > self.MAX_GROUPS:
                 raise ValueError("CompiledSequence: automation: %d group pan lanes, at most %d" % (len(group_pans), self.MAX_GROUPS))
-        return (tuple(self._check_pan_lane("track %d pan" % t, lane) for t, lane in enumerate(pans or ())),
-                tuple(self._check_pan_lane("group %d pan" % g, lane) for g, lane in enumerate(group_pans or ())))
-
-    def _check_pan_lane(self, who: str, lane) -> tuple:
-        """one pan lane -- a track's or a group's -- as a tuple of pieces ``(start_frame, end_frame, from_pan, to_pan)``, integers and
-        floats, every piece kept (a hold at 0.0 is a step of its own); ``who`` names it in the errors"""
-        if lane is None:
-            return ()
-        if isinstance(lane, (str, bytes)) or not hasattr(lane, "__iter__"):
-            raise ValueError("CompiledSequence: automation: %s: a lane is None or a list of pieces" % who)
-        kept, prev = [], 0
-        for k, piece in enumerate(lane):
-            where = "CompiledSequence: automation: %s, piece %d: " % (who, k)
-            if isinstance(piece, (str, bytes)) or not hasattr(piece, "__len__") or len(piece) != 4:
-                raise ValueError(where + "a piece is (start_frame, end_frame, from_pan, to_pan)")
-            try:
-                if isinstance(piece[0], bool) or isinstance(piece[1], bool):
-                    raise TypeError
-                a, b = operator.index(piece[0]), operator.index(piece[1])
-            except TypeError:
-                raise ValueError(where + "start_frame and end_frame are integers") from None
-            try:
-                p0, p1 = float(piece[2]), float(piece[3])
-            except (TypeError, ValueError):
-                raise ValueError(where + "a piece is (start_frame, end_frame, from_pan, to_pan), four numbers") from None
-            if a < 0 or a >= b:
-                raise ValueError(where + "frames [%d, %d): a piece starts at 0 or later and ends behind its start" % (a, b))
-            if b > self.frames:
-                raise ValueError(where + "frames [%d, %d) end past the song's %d frames" % (a, b, self.frames))
-            if a < prev:
-                raise ValueError(where + "starts at frame %d, before the piece in front of it ends (%d)" % (a, prev))
-            for name, p in (("from_pan", p0), ("to_pan", p1)):
-                if not math.isfinite(p) or not -1.0 <= p <= 1.0:
-                    raise ValueError(where + "%s %r is not a finite number within -1.0 .. 1.0" % (name, p))
-            prev = b
-            kept.append((a, b, p0, p1))
-        return tuple(kept)
+        return (tuple(self._check_lane("track %d pan" % t, lane, _PAN_LANE) for t, lane in enumerate(pans or ())),
+                tuple(self._check_lane("group %d pan" % g, lane, _PAN_LANE) for g, lane in enumerate(group_pans or ())))
 
     @staticmethod
     def _pack_pan_lanes(pans: tuple, group_pans: tuple) -> tuple:
         """the checked pan lanes as sh_env_segment rows in song SAMPLES of a stereo song, the tracks' one behind the other and then the
         groups', and where each lane's start: a piece over frames ``[a, b)`` is a pan move (kind ``ENV_PAN``, origin ``2 a``, end ``2 b``,
         numsamples ``b - a`` -- its FRAMES --, slope ``p1 - p0``, offset ``p0``, mul 1.0), a plain segment fills the gap in front of it"""
-        rows, seg_first = [], [0]
-        for lane in tuple(pans) + tuple(group_pans):
-            at = 0
-            for a, b, p0, p1 in lane:
-                if 2 * a > at:
-                    rows.append((2 * a, 0, 1.0, 0.0, 0.0, 0.0, N.ENV_NONE))
-                rows.append((2 * b, 2 * a, 1.0, p1 - p0, float(b - a), p0, N.ENV_PAN))
-                at = 2 * b
-            seg_first.append(len(rows))
-        segments = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
-        for name, column in zip(("end", "origin", "mul", "slope", "numsamples", "offset", "kind"), zip(*rows) if rows else [()] * 7):
-            segments[name] = column
-        return segments, seg_first
+        rows, seg_first = CompiledSequence._lane_rows(tuple(pans) + tuple(group_pans), 2, 1, N.ENV_PAN)
+        return CompiledSequence._segments(rows), seg_first
 
     def _check_lanes(self, lanes, master=None, groups=None) -> tuple:
         """(the tracks' lanes, the master's lane, the groups' lanes), checked: every lane through ``_check_lane``"""
@@ -1522,18 +1517,20 @@ class CompiledSequence:
         return (tuple(self._check_lane("track %d" % t, lane) for t, lane in enumerate(lanes)), self._check_lane("master", master),
                 tuple(self._check_lane("group %d" % g, lane) for g, lane in enumerate(groups or ())))
 
-    def _check_lane(self, who: str, lane) -> tuple:
-        """one lane -- a track's, the master's or a group's -- as a tuple of pieces ``(start_frame, end_frame, from_volume, to_volume)``,
-        integers and floats, those at exactly (1.0, 1.0) dropped; ``who`` names it in the errors"""
+    def _check_lane(self, who: str, lane, what: _LaneKind = _FADER_LANE) -> tuple:
+        """one lane -- a track's, the master's or a group's, of faders or (``what``) of pans -- as a tuple of pieces ``(start_frame,
+        end_frame, from_volume, to_volume)`` or ``(start_frame, end_frame, from_pan, to_pan)``, integers and floats; a fader's pieces at
+        exactly (1.0, 1.0) are dropped, every pan piece is kept (a hold at 0.0 is a step of its own); ``who`` names it in the errors"""
         if lane is None:
             return ()
         if isinstance(lane, (str, bytes)) or not hasattr(lane, "__iter__"):
             raise ValueError("CompiledSequence: automation: %s: a lane is None or a list of pieces" % who)
+        form = "a piece is (start_frame, end_frame, from_%s, to_%s)" % (what.name, what.name)
         kept, prev = [], 0
         for k, piece in enumerate(lane):
             where = "CompiledSequence: automation: %s, piece %d: " % (who, k)
             if isinstance(piece, (str, bytes)) or not hasattr(piece, "__len__") or len(piece) != 4:
-                raise ValueError(where + "a piece is (start_frame, end_frame, from_volume, to_volume)")
+                raise ValueError(where + form)
             try:
                 if isinstance(piece[0], bool) or isinstance(piece[1], bool):
                     raise TypeError
@@ -1543,20 +1540,43 @@ class CompiledSequence:
             try:
                 v0, v1 = float(piece[2]), float(piece[3])
             except (TypeError, ValueError):
-                raise ValueError(where + "a piece is (start_frame, end_frame, from_volume, to_volume), four numbers") from None
+                raise ValueError(where + form + ", four numbers") from None
             if a < 0 or a >= b:
                 raise ValueError(where + "frames [%d, %d): a piece starts at 0 or later and ends behind its start" % (a, b))
             if b > self.frames:
                 raise ValueError(where + "frames [%d, %d) end past the song's %d frames" % (a, b, self.frames))
             if a < prev:
                 raise ValueError(where + "starts at frame %d, before the piece in front of it ends (%d)" % (a, prev))
-            for name, v in (("from_volume", v0), ("to_volume", v1)):
-                if not math.isfinite(v) or not 0.0 <= v <= 1.0:
-                    raise ValueError(where + "%s %r is not a finite number within 0.0 .. 1.0" % (name, v))
+            for end, v in (("from", v0), ("to", v1)):
+                if not math.isfinite(v) or not what.low <= v <= 1.0:
+                    raise ValueError(where + "%s_%s %r is not a finite number within %r .. 1.0" % (end, what.name, v, what.low))
             prev = b
-            if not (v0 == 1.0 and v1 == 1.0):
+            if not (what.drops_unity and v0 == 1.0 and v1 == 1.0):
                 kept.append((a, b, v0, v1))
         return tuple(kept)
+
+    @staticmethod
+    def _lane_rows(lanes, samples_per_frame: int, unit: int, kind: int) -> tuple:
+        """checked lanes as sh_env_segment rows in song SAMPLES, one lane behind the other, and where each lane's start: a piece over
+        frames ``[a, b)`` is a move of ``kind`` (origin its first sample, numsamples ``(b - a) * unit``, slope ``v1 - v0``, offset ``v0``,
+        mul 1.0), a plain segment fills the gap in front of it"""
+        rows, seg_first = [], [0]
+        for lane in lanes:
+            at = 0
+            for a, b, v0, v1 in lane:
+                if a * samples_per_frame > at:
+                    rows.append((a * samples_per_frame, 0, 1.0, 0.0, 0.0, 0.0, N.ENV_NONE))
+                rows.append((b * samples_per_frame, a * samples_per_frame, 1.0, v1 - v0, float((b - a) * unit), v0, kind))
+                at = b * samples_per_frame
+            seg_first.append(len(rows))
+        return rows, seg_first
+
+    @staticmethod
+    def _segments(rows: list) -> np.ndarray:
+        segments = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
+        for name, column in zip(("end", "origin", "mul", "slope", "numsamples", "offset", "kind"), zip(*rows) if rows else [()] * 7):
+            segments[name] = column
+        return segments
 
     @staticmethod
     def _pack_lanes(pieces: tuple, nchannels: int, master: tuple = (), groups: tuple = (), buses: bool = False) -> tuple:
@@ -1566,21 +1586,10 @@ class CompiledSequence:
         follow the tracks' in the meter table's row order: the master's at ``ntracks``, group ``g``'s at ``ntracks + 1 + g``; where none
         does, the table is the tracks' alone -- unless ``buses`` asks for the lanes of the buses anyway (an ``Automation`` with pan
         lanes: its entry point takes them)"""
-        rows, seg_first = [], [0]
         if buses or master or any(groups):
             pieces = tuple(pieces) + (master,) + tuple(groups)
-        for lane in pieces:
-            at = 0
-            for a, b, v0, v1 in lane:
-                if a * nchannels > at:
-                    rows.append((a * nchannels, 0, 1.0, 0.0, 0.0, 0.0, N.ENV_NONE))
-                rows.append((b * nchannels, a * nchannels, 1.0, v1 - v0, float((b - a) * nchannels), v0, N.ENV_FADE_IN))
-                at = b * nchannels
-            seg_first.append(len(rows))
-        segments = np.zeros(len(rows), dtype=N.ENV_SEGMENT_DTYPE)
-        for name, column in zip(("end", "origin", "mul", "slope", "numsamples", "offset", "kind"), zip(*rows) if rows else [()] * 7):
-            segments[name] = column
-        return segments, seg_first
+        rows, seg_first = CompiledSequence._lane_rows(pieces, nchannels, nchannels, N.ENV_FADE_IN)
+        return CompiledSequence._segments(rows), seg_first
 
     def _levels(self, rows, nframes: int, ngroups: int = 0) -> SongLevels:
         if rows is None:                                        # an empty window: nothing was launched, every level 0
@@ -1626,36 +1635,33 @@ class CompiledSequence:
         ``meters="history"``: the same bytes, and the window's ``SongHistory`` returned -- its levels per block of the song's tile grid,
         still from that one launch.  ``clips=True`` (with ``meters="history"``): the history carries the overs per block as well
         (``CompiledSequence``), still from that one launch."""
-        seq = self._handle()
-        gains = self._gains(gains)
-        meters = self._meters(meters)
-        groups = self._groups(groups)
-        desk = self._desk(self._pans(pans), self._master(master), self._automation(automation, groups), groups)
-        clips = self._clips(clips, meters, automation)
-        self._no_history_of(meters, automation)
+        call = self._desk_call(gains, meters, pans, master, automation, groups, clips)
         start_frame, nframes = self._range(start_frame, nframes)
         if byte_offset < 0 or byte_offset % self.samplewidth:
             raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
-        if meters == "history":
-            blocks = None
-            if clips:
-                desk = dict(desk, clips=True)
-            if nframes:
-                blocks = seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains,
-                                    meters="history", **desk)
-            return self._history(blocks, start_frame, nframes, len(groups or ()), clips)
-        if meters:
-            rows = None
-            if nframes:
-                rows = seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains, meters=True,
-                                  **desk)
-            return self._levels(rows, nframes, len(groups)) if groups else self._levels(rows, nframes)
+        return self._render_into(buf, byte_offset, start_frame, nframes, call)
+
+    def _render_into(self, buf: Optional[N.DeviceBuffer], byte_offset: int, start_frame: int, nframes: int, call: _DeskCall):
+        """the one launch of a checked call over a checked window, and what its meters give -- of an empty window, for which nothing is
+        launched (``buf`` may be None), every level 0 and a history without blocks"""
+        got = None
         if nframes:
-            if gains is None and not desk:
-                seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth)
-            else:
-                seq.render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, gains=gains, **desk)
+            got = self._handle().render(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth,
+                                        **call.render_keywords())
+        if call.meters == "history":
+            return self._history(got, start_frame, nframes, call.ngroups, call.clips)
+        if call.meters:
+            return self._levels(got, nframes, call.ngroups)
         return None
+
+    def _render(self, start_frame: int, nframes: int, call: _DeskCall):
+        """a checked call over a checked window into a new ``Sample``, with its levels where the call has meters"""
+        out = Sample(name=self.name, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth)
+        buf = N.DeviceBuffer(nframes * self._fb) if nframes else None
+        levels = self._render_into(buf, 0, start_frame, nframes, call)
+        if buf is not None:
+            out._set_device(buf, nframes * self._fb)
+        return (out, levels) if call.meters else out
 
     def render(self, start_frame: int = 0, nframes: Optional[int] = None, gains: Optional[Sequence[float]] = None, meters: bool = False,
                pans: Optional[Sequence] = None, master: Optional[float] = None, automation: Optional[Automation] = None,
@@ -1667,33 +1673,8 @@ class CompiledSequence:
         ``automation``: this song's fader moves (``automation()``); ``groups``: at most 8 entries ``(first_track, end_track, gain)`` or
         ``(first_track, end_track, gain, pan)``, the group buses (``CompiledSequence`` has the chain).  ``clips=True`` (with
         ``meters="history"``): the ``SongHistory`` carries the overs per block."""
-        self._handle()
-        gains = self._gains(gains)
-        meters = self._meters(meters)
-        self._pans(pans), self._master(master)                  # (checked here as well: before the buffer is made)
-        ngroups = len(self._groups(groups) or ())
-        self._automation(automation, self._groups(groups))
-        clips = self._clips(clips, meters, automation)
-        self._no_history_of(meters, automation)
-        start_frame, nframes = self._range(start_frame, nframes)
-        out = Sample(name=self.name, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth)
-        levels = None
-        if nframes:
-            buf = N.DeviceBuffer(nframes * self._fb)
-            if clips:
-                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=meters, pans=pans, master=master, automation=automation,
-                                          groups=groups, clips=True)
-            elif meters:
-                levels = self.render_into(buf, 0, start_frame, nframes, gains=gains, meters=meters, pans=pans, master=master, automation=automation,
-                                          groups=groups)
-            else:
-                self.render_into(buf, 0, start_frame, nframes, gains=gains, pans=pans, master=master, automation=automation, groups=groups)
-            out._set_device(buf, nframes * self._fb)
-        if meters == "history":
-            return out, levels if levels is not None else self._history(None, start_frame, 0, ngroups, clips)
-        if meters:
-            return out, levels if levels is not None else self._levels(None, 0, ngroups)
-        return out
+        call = self._desk_call(gains, meters, pans, master, automation, groups, clips)     # (checked before the buffer is made)
+        return self._render(*self._range(start_frame, nframes), call)
 
     def stem(self, track: int, start_frame: int = 0, nframes: Optional[int] = None) -> Sample:
         """One track of a song of tracks alone, at gain 1.0, as long as the window: ``render`` with one-hot gains."""
@@ -1704,15 +1685,6 @@ class CompiledSequence:
         if track < 0 or track >= self.ntracks:
             raise ValueError("CompiledSequence: track %d outside the song's %d tracks" % (track, self.ntracks))
         return self.render(start_frame, nframes, gains=[1.0 if t == track else 0.0 for t in range(self.ntracks)])
-
-    def _stems_desk(self, gains, pans, master, automation, groups) -> dict:
-        """the keywords of a stems call for N.Sequence.stems, checked by the helpers ``render`` uses -- before anything is made or launched"""
-        if self.ntracks is None:
-            raise ValueError("CompiledSequence: stems need a song of tracks (compile_tracks); this one has none")
-        gains = self._gains(gains)
-        groups = self._groups(groups)
-        return {"gains": gains, "pans": self._pans(pans), "master": self._master(master), "automation": self._automation(automation, groups),
-                "groups": groups}
 
     @staticmethod
     def stems_plane_frames(nframes: int, nchannels: int, samplewidth: int) -> int:
@@ -1729,17 +1701,20 @@ class CompiledSequence:
         frames, plane ``r`` from ``byte_offset + r * plane_frames`` frames on (``plane_frames >= nframes``), in the meter rows' order --
         the tracks, the master, the groups (``SongStems`` says what each holds).  Every byte of every plane is written, whatever ``buf``
         held, and none between or around them.  One launch; the desk's keywords are ``render``'s."""
-        seq = self._handle()
-        desk = self._stems_desk(gains, pans, master, automation, groups)
+        call = self._desk_call(gains, False, pans, master, automation, groups, False, stems=True)
         start_frame, nframes = self._range(start_frame, nframes)
         plane_frames = int(plane_frames)
         if byte_offset < 0 or byte_offset % self.samplewidth:
             raise ValueError("CompiledSequence: byte_offset %d is not a whole number of %d-byte samples" % (byte_offset, self.samplewidth))
         if plane_frames < nframes:
             raise ValueError("CompiledSequence: planes %d frames apart for a window of %d frames" % (plane_frames, nframes))
+        return self._stems_into(buf, byte_offset, plane_frames, start_frame, nframes, call)
+
+    def _stems_into(self, buf: N.DeviceBuffer, byte_offset: int, plane_frames: int, start_frame: int, nframes: int, call: _DeskCall) -> None:
+        """the one launch of a checked stems call over a checked window; none for an empty one"""
         if nframes:
-            seq.stems(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth, plane_frames * self.nchannels, **desk)
-        return None
+            self._handle().stems(start_frame * self.nchannels, nframes * self.nchannels, buf, byte_offset // self.samplewidth,
+                                 plane_frames * self.nchannels, **call.stems_keywords())
 
     def stems(self, start_frame: int = 0, nframes: Optional[int] = None, gains: Optional[Sequence[float]] = None, pans: Optional[Sequence] = None,
               master: Optional[float] = None, automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> SongStems:
@@ -1748,10 +1723,12 @@ class CompiledSequence:
         the window's length -- from ONE launch that walks every event once, into one device buffer the ``Sample``s share.  The desk's
         keywords are ``render``'s, and each stem is exactly what ``meters=True`` of the same call reads its row over.  (``stem(t)`` is
         something else: the raw track at gain 1.0, without the desk.)"""
-        self._handle()
-        desk = self._stems_desk(gains, pans, master, automation, groups)
-        start_frame, nframes = self._range(start_frame, nframes)
-        ngroups = len(desk["groups"] or ())
+        call = self._desk_call(gains, False, pans, master, automation, groups, False, stems=True)
+        return self._stems(*self._range(start_frame, nframes), call)
+
+    def _stems(self, start_frame: int, nframes: int, call: _DeskCall) -> SongStems:
+        """a checked stems call over a checked window into one new buffer, every stem a view of it"""
+        ngroups = call.ngroups
         nrows = self.ntracks + 1 + ngroups
         names = ["%s:track %d" % (self.name, t) for t in range(self.ntracks)] + ["%s:master" % self.name] + ["%s:group %d" % (self.name, g) for g in range(ngroups)]
         outs = [Sample(name=n, samplerate=self.samplerate, nchannels=self.nchannels, samplewidth=self.samplewidth) for n in names]
@@ -1759,7 +1736,7 @@ class CompiledSequence:
         if nframes:
             plane_frames = self.stems_plane_frames(nframes, self.nchannels, self.samplewidth)
             buf = N.DeviceBuffer(nrows * plane_frames * self._fb)
-            self.stems_into(buf, 0, plane_frames, start_frame, nframes, gains=gains, pans=pans, master=master, automation=automation, groups=groups)
+            self._stems_into(buf, 0, plane_frames, start_frame, nframes, call)
             for r, out in enumerate(outs):
                 out._set_device(buf.view(r * plane_frames * self._fb, nframes * self._fb), nframes * self._fb)
         return SongStems(outs[:self.ntracks], outs[self.ntracks], outs[self.ntracks + 1:], start_frame, nframes, buffer=buf, plane_frames=plane_frames,
@@ -1774,7 +1751,8 @@ class CompiledSequence:
         ``block_frames`` None: the song's tile in frames, else any positive int.  The bytes are not returned: ``stems`` keeps them."""
         if block_frames is not None:
             block_frames = _block_frames("CompiledSequence", block_frames)
-        return self.stems(start_frame, nframes, gains=gains, pans=pans, master=master, automation=automation, groups=groups).level_history(block_frames)
+        call = self._desk_call(gains, False, pans, master, automation, groups, False, stems=True)
+        return self._stems(*self._range(start_frame, nframes), call).level_history(block_frames)
 
     def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None, meters: bool = False, pans: Optional[Sequence] = None,
                master: Optional[float] = None, automation: Optional[Automation] = None, groups: Optional[Sequence] = None,
@@ -1786,21 +1764,9 @@ class CompiledSequence:
         chunk_frames = int(chunk_frames)
         if chunk_frames <= 0:
             raise ValueError("CompiledSequence: chunk_frames must be positive")
-        self._handle()
-        gains = self._gains(gains)
-        meters = self._meters(meters)
-        self._pans(pans), self._master(master), self._automation(automation, self._groups(groups))
-        clips = self._clips(clips, meters, automation)
-        self._no_history_of(meters, automation)
+        call = self._desk_call(gains, meters, pans, master, automation, groups, clips)     # once, for every chunk
         for at in range(0, self.frames, chunk_frames):
-            if clips:
-                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=meters, pans=pans, master=master, automation=automation,
-                                  groups=groups, clips=True)
-            elif meters:
-                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, meters=meters, pans=pans, master=master, automation=automation,
-                                  groups=groups)
-            else:
-                yield self.render(at, min(chunk_frames, self.frames - at), gains=gains, pans=pans, master=master, automation=automation, groups=groups)
+            yield self._render(at, min(chunk_frames, self.frames - at), call)
 
     def close(self) -> None:
         if self._seq is not None:

@@ -13,9 +13,7 @@ from oracle import pcm_oracle
 from oracle.sample_oracle import RefSample
 from synthesizer_amd import _native as N
 from synthesizer_amd import mixer
-from tests.test_channels_host import _fake
-from tests.test_desk_host import _calls, _Lib, _Seq
-from tests.test_enveloped_host import RATE, _mono, _stereo
+from tests.songhost import RATE, _calls, _clip, _fake, _Lib, _mono, _piece, _Seq, _stereo
 
 nan, inf = float("nan"), float("inf")
 
@@ -237,17 +235,6 @@ def test_the_new_symbols_are_declared_beside_the_one_they_extend():
 
 
 # ---- the reference expression ----------------------------------------------------------------------------------------------------------
-def _piece(v, n, v0, v1):
-    """the chain's step on one clip of n samples: Python ints and floats"""
-    return [int(x * (k * (v1 - v0) / float(n) + v0)) for k, x in enumerate(v)]
-
-
-def _clip(rng, width, n):
-    bits = 8 * width
-    v = rng.integers(-(1 << (bits - 1)), 1 << (bits - 1), n, dtype=np.int64)
-    edge = [-(1 << (bits - 1)), (1 << (bits - 1)) - 1, -1][:n]
-    v[:len(edge)] = edge
-    return v
 
 
 @pytest.mark.parametrize("width", [1, 2, 4])

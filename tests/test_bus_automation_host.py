@@ -12,33 +12,9 @@ import pytest
 from oracle.sample_oracle import RefSample
 from synthesizer_amd import _native as N
 from synthesizer_amd import mixer
-from tests.test_automation_host import _clip, _piece
-from tests.test_channels_host import _fake
-from tests.test_desk_host import _calls, _Lib, _Seq
-from tests.test_enveloped_host import RATE, _mono, _stereo
+from tests.songhost import RATE, _Auto, _calls, _clip, _fake, _Lib, _piece, _rows, _Seq, _song, _stereo
 
 nan, inf = float("nan"), float("inf")
-
-
-class _Auto:
-    """N.SeqAutomation as the mixer sees it: what it was handed, the arguments behind the third as well"""
-    made = []
-
-    def __init__(self, seq, segments, seg_first, *rest):
-        self.seq, self.segments, self.seg_first, self.rest, self.freed = seq, segments, seg_first, rest, False
-        _Auto.made.append(self)
-
-    def free(self):
-        self.freed = True
-
-
-def _song(monkeypatch, nch=2, width=2):
-    _fake(monkeypatch)
-    monkeypatch.setattr(N, "Sequence", _Seq)
-    monkeypatch.setattr(N, "SeqAutomation", _Auto)
-    del _Auto.made[:]
-    a = _stereo(1000, width) if nch == 2 else _mono(1000, width)
-    return mixer.compile_tracks([[(0.0, a), (0.5, a, 0.5)], [], [(0.25, a)]], RATE, nch, width)
 
 
 # ---- the checks ---------------------------------------------------------------------------------------------------------------------------
@@ -116,8 +92,6 @@ def test_width_3_a_song_without_tracks_and_a_closed_song(monkeypatch):
 
 
 # ---- the packed table ----------------------------------------------------------------------------------------------------------------------
-def _rows(g):
-    return [tuple(g[k][f] for f in ("end", "origin", "mul", "slope", "numsamples", "offset", "kind", "reserved")) for k in range(len(g))]
 
 
 @pytest.mark.parametrize("nch", [1, 2])

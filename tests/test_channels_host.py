@@ -9,7 +9,8 @@ import pytest
 
 from synthesizer_amd import _native as N
 from synthesizer_amd.sample import Sample
-from tests.test_enveloped_host import RATE, _Buf, _layout, _mono, _no_library, _stereo
+from tests.songhost import RATE, _fake, _mono, _stereo
+from tests.test_enveloped_host import _layout, _no_library
 from tests.test_reversed_host import REV_FIELDS, _RevLib
 
 nan, inf = float("nan"), float("inf")
@@ -30,13 +31,6 @@ class _ChanLib(_RevLib):
             self.args = args[6:8]                           # width, nchannels
             return call(*args)
         return chan_call
-
-
-def _fake(monkeypatch):
-    lib = _ChanLib()
-    monkeypatch.setattr(N, "lib", lambda: lib)
-    monkeypatch.setattr(N, "DeviceBuffer", _Buf)
-    return lib
 
 
 def _entries(lib):

@@ -1,5 +1,5 @@
 """What the overs of a compiled song's level history -- ``clips=True`` on ``CompiledSequence.render``, ``render_into`` and ``chunks``,
-``Levels.clipped``, ``SongHistory.clipped()`` -- need of the host alone (no GPU; the fake native layer of tests/test_history_host.py): what
+``Levels.clipped``, ``SongHistory.clipped()`` -- need of the host alone (no GPU; the fake native layer of tests/songhost.py): what
 is refused before a launch, that ``clips=False`` hands on exactly the keywords there were, which entry point the binding reaches, and the
 arithmetic of ``SongHistory`` with counts (``total``, ``fold``, ``clipped()``, ``Levels`` equality with and without counts).  The counts
 themselves: tests/test_gpu_clips.py."""
@@ -12,27 +12,8 @@ import pytest
 
 from synthesizer_amd import _native as N
 from synthesizer_amd import mixer
-from tests.test_bus_automation_host import _Auto
-from tests.test_channels_host import _fake
-from tests.test_desk_host import _calls, _Lib, _Seq
-from tests.test_enveloped_host import RATE, _mono, _stereo
+from tests.songhost import RATE, _Auto, _calls, _ClipSeq, _fake, _Lib, _mono, _stereo
 from tests.test_history_host import hand_made
-
-
-class _ClipSeq(_Seq):
-    """tests/test_desk_host._Seq, whose history is the array N.Sequence.render hands back -- with the field ``clipped`` where clips=True"""
-
-    def render(self, first_sample, nsamples, out, out_sample=0, **kw):
-        if kw.get("meters") == "history":
-            self.rendered.append((first_sample, nsamples, out_sample, kw))
-            nblocks = (first_sample + nsamples - 1) // 2048 - first_sample // 2048 + 1
-            blocks = np.zeros((nblocks, 4 + len(kw.get("groups") or ())), dtype=N.SEQ_METER_CLIPS_DTYPE if kw.get("clips") else N.SEQ_METER_DTYPE)
-            blocks["peak"][:, :, 0] = np.arange(nblocks)[:, None] + first_sample // 2048
-            if kw.get("clips"):
-                blocks["clipped"][:, :, 0] = 10 * (np.arange(nblocks)[:, None] + first_sample // 2048) + np.arange(blocks.shape[1])[None, :]
-                blocks["clipped"][:, :, 1] = 1
-            return blocks
-        return _Seq.render(self, first_sample, nsamples, out, out_sample, **kw)
 
 
 def _song(monkeypatch, nch=2):

@@ -10,9 +10,10 @@ import pytest
 from synthesizer_amd import _native as N
 from synthesizer_amd import mixer
 from synthesizer_amd.sample import Sample
+from tests.songhost import RATE, _fake, _mono, _stereo
 from tests.test_abi import HEADER
-from tests.test_channels_host import _ev, _fake
-from tests.test_enveloped_host import RATE, _mono, _no_library, _stereo
+from tests.test_channels_host import _ev
+from tests.test_enveloped_host import _no_library
 
 nan, inf = float("nan"), float("inf")
 

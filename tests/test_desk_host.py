@@ -8,28 +8,9 @@ import pytest
 
 from synthesizer_amd import _native as N
 from synthesizer_amd import mixer
-from tests.test_channels_host import _fake
-from tests.test_enveloped_host import RATE, _mono, _stereo
+from tests.songhost import RATE, _calls, _fake, _Lib, _mono, _Seq, _stereo
 
 nan, inf = float("nan"), float("inf")
-
-
-class _Seq:
-    """N.Sequence as the mixer sees it: what each render was handed"""
-
-    def __init__(self, sources, table, segments, width, nchannels, track_samples, track_first=None):
-        self.rendered = []
-
-    def info(self):
-        return {"level": 0, "device_bytes": 0}
-
-    def render(self, first_sample, nsamples, out, out_sample=0, **kw):
-        self.rendered.append((first_sample, nsamples, out_sample, kw))
-        if kw.get("meters"):
-            return [((0, 0), (0, 0))] * 4
-
-    def free(self):
-        pass
 
 
 def _song(monkeypatch, nch=2):
@@ -37,12 +18,6 @@ def _song(monkeypatch, nch=2):
     monkeypatch.setattr(N, "Sequence", _Seq)
     a = _stereo(1000) if nch == 2 else _mono(1000)
     return mixer.compile_tracks([[(0.0, a), (0.5, a, 0.5)], [], [(0.25, a)]], RATE, nch)
-
-
-def _calls(cs, **kw):
-    """the ways a keyword reaches a render"""
-    return (lambda: cs.render(**kw), lambda: cs.render(3, 0, **kw), lambda: cs.render_into(N.DeviceBuffer(100), 0, 0, 10, **kw),
-            lambda: next(cs.chunks(100, **kw)))
 
 
 @pytest.mark.parametrize("bad, message", [
@@ -150,21 +125,6 @@ def test_what_render_hands_on(monkeypatch):
     for call in _calls(cs, pans=(0.3, None, None)) + _calls(cs, master=0.5):
         with pytest.raises(ValueError, match="closed"):
             call()
-
-
-class _Lib:
-    """the entry points N.Sequence.render reaches, by name, with their arguments"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def entry(*args):
-            self.calls.append((name, args))
-            if name == "sh_seq_get_tracks":
-                args[1]._obj.value = 3
-            return 0
-        return entry
 
 
 def test_the_binding_calls_the_new_entry_point_only_when_a_step_is_given(monkeypatch):

@@ -11,13 +11,13 @@ import pytest
 
 from oracle.sample_oracle import RefSample
 from synthesizer_amd import _native as N
-from synthesizer_amd.sample import Sample, _envelope_segments
+from synthesizer_amd.sample import _envelope_segments
+from tests.songhost import RATE, _Buf, _mono, _stereo
 
 ROOT = Path(__file__).resolve().parent.parent
 EVENT_FIELDS = ["dst_sample", "src_sample", "nsamples", "src_frames", "factor", "left", "right", "src", "inrate", "outrate", "src_channels",
                 "seg_first", "seg_count", "reserved"]
 SEGMENT_FIELDS = ["end", "origin", "mul", "slope", "numsamples", "offset", "kind", "reserved"]
-RATE = 8000
 
 
 def _layout(tmp_path, struct, fields):
@@ -39,14 +39,6 @@ def test_the_structs_match_the_header(tmp_path):
     G = N.ENV_SEGMENT_DTYPE
     assert _layout(tmp_path, "sh_env_segment", SEGMENT_FIELDS) == [G.itemsize] + [G.fields[f][1] for f in SEGMENT_FIELDS] == [56, 0, 8, 16, 24, 32, 40, 48, 52]
     assert G.names == tuple(SEGMENT_FIELDS)
-
-
-def _mono(n=1000, width=2):
-    return Sample.from_raw_frames(bytes(width * n), width, RATE, 1)
-
-
-def _stereo(n=1000, width=2):
-    return Sample.from_raw_frames(bytes(2 * width * n), width, RATE, 2)
 
 
 def _no_library(monkeypatch):
@@ -170,20 +162,6 @@ def test_the_replayed_boundaries_are_refsamples_where_the_rounding_bites(width, 
 
 
 # ---- which entry point, which table -------------------------------------------------------------------------------------------------------
-class _Buf:
-    handle = None
-
-    def __init__(self, nbytes=0):
-        self.nbytes = nbytes
-
-    @classmethod
-    def from_bytes(cls, data):
-        return cls(len(data))
-
-    def zero(self, *_a):
-        pass
-
-
 class _Lib:
     """Every entry point answers SH_OK; the calls and the tables they were handed are kept."""
     DTYPES = {"sh_mix_events": "MIX_EVENT_DTYPE", "sh_mix_events_rate": "MIX_EVENT_RATE_DTYPE", "sh_mix_events_pan": "MIX_EVENT_PAN_DTYPE",

@@ -8,9 +8,7 @@ import pytest
 
 from synthesizer_amd import _native as N
 from synthesizer_amd import mixer
-from tests.test_channels_host import _fake
-from tests.test_desk_host import _calls, _Lib, _Seq
-from tests.test_enveloped_host import RATE, _mono, _stereo
+from tests.songhost import RATE, _calls, _fake, _Lib, _mono, _Seq, _stereo
 
 nan, inf = float("nan"), float("inf")
 

@@ -1,5 +1,5 @@
 """What the level history of a compiled song of tracks -- ``CompiledSequence.render(meters="history")`` and ``mixer.SongHistory`` -- needs of
-the host alone (no GPU; the fakes of tests/test_desk_host.py and tests/test_bus_automation_host.py): ``SongHistory`` built from hand-made
+the host alone (no GPU; the fakes of tests/songhost.py): ``SongHistory`` built from hand-made
 rows against Python integers (indexing, ``starts``, the frames of partial edge blocks, ``total()``, ``fold(n)`` from a window that starts
 mid-group, ``peaks()``, a mono song's ``left == right``), the validation of ``meters=``, and which entry points and keywords
 ``meters=True``, ``meters=False`` and ``meters="history"`` reach.  The levels themselves: tests/test_gpu_history.py."""
@@ -12,10 +12,7 @@ import pytest
 
 from synthesizer_amd import _native as N
 from synthesizer_amd import mixer
-from tests.test_bus_automation_host import _Auto
-from tests.test_channels_host import _fake
-from tests.test_desk_host import _calls, _Lib, _Seq
-from tests.test_enveloped_host import RATE, _mono, _stereo
+from tests.songhost import RATE, _Auto, _calls, _fake, _Lib, _mono, _Seq, _stereo
 
 
 # ---- hand-made rows -------------------------------------------------------------------------------------------------------------------
@@ -157,7 +154,7 @@ def test_from_blocks_forms_the_sums_in_python_integers():
 
 # ---- meters= ------------------------------------------------------------------------------------------------------------------------------
 class _HistSeq(_Seq):
-    """tests/test_desk_host._Seq, whose history is the array N.Sequence.render hands back: one row set per song tile of the window"""
+    """tests/songhost._Seq, whose history is the array N.Sequence.render hands back: one row set per song tile of the window"""
 
     def render(self, first_sample, nsamples, out, out_sample=0, **kw):
         if kw.get("meters") == "history":

@@ -14,11 +14,8 @@ import pytest
 from synthesizer_amd import _native as N
 from synthesizer_amd import mixer
 from synthesizer_amd.sample import Sample
-from tests.test_bus_automation_host import _Auto
-from tests.test_channels_host import _fake
-from tests.test_desk_host import _Lib
-from tests.test_enveloped_host import RATE, _mono, _stereo
-from tests.test_stems_host import _song, _StemBuf
+from tests.songhost import RATE, _Auto, _fake, _Lib, _mono, _StemBuf, _stereo
+from tests.test_stems_host import _song
 
 
 def _record(monkeypatch):

@@ -8,7 +8,8 @@ import pytest
 
 from synthesizer_amd import _native as N
 from synthesizer_amd.sample import Sample
-from tests.test_enveloped_host import EVENT_FIELDS, RATE, _fake_library, _layout, _Lib, _mono, _no_library, _stereo
+from tests.songhost import RATE, _mono, _stereo
+from tests.test_enveloped_host import EVENT_FIELDS, _fake_library, _layout, _Lib, _no_library
 
 LOOP_FIELDS = EVENT_FIELDS + ["loop_start", "loop_frames"]
 nan, inf = float("nan"), float("inf")

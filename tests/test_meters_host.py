@@ -11,8 +11,7 @@ import pytest
 
 from synthesizer_amd import _native as N
 from synthesizer_amd import mixer
-from tests.test_channels_host import _fake
-from tests.test_enveloped_host import RATE, _mono
+from tests.songhost import RATE, _fake, _mono
 
 
 class _Seq:

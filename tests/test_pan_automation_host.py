@@ -1,5 +1,5 @@
 """What the pan rides of a compiled stereo song of tracks -- ``CompiledSequence.automation(lanes, pans=, group_pans=)`` -- need of the host
-alone (no GPU; the fakes of tests/test_bus_automation_host.py): every check of the new arguments raised before the native layer is reached,
+alone (no GPU; the fakes of tests/songhost.py): every check of the new arguments raised before the native layer is reached,
 the pieces packed into rows and offsets, no piece dropped, an automation without a pan piece made and handed on exactly as before, a pan
 ride on a group refused by a render that does not name the group, and a piece over a clip against ``RefSample.pan(lfo=...)``.  The bytes:
 tests/test_gpu_pan_automation.py."""
@@ -12,11 +12,7 @@ import pytest
 from oracle.sample_oracle import RefSample
 from synthesizer_amd import _native as N
 from synthesizer_amd import mixer
-from tests.test_automation_host import _clip
-from tests.test_bus_automation_host import _Auto, _rows, _song
-from tests.test_channels_host import _fake
-from tests.test_desk_host import _calls, _Lib, _Seq
-from tests.test_enveloped_host import RATE, _stereo
+from tests.songhost import RATE, _Auto, _calls, _clip, _fake, _Lib, _rows, _Seq, _song, _stereo
 
 nan, inf = float("nan"), float("inf")
 

@@ -6,7 +6,8 @@ import pytest
 
 from synthesizer_amd import _native as N
 from synthesizer_amd.sample import Sample, _region_frames
-from tests.test_enveloped_host import RATE, _layout, _mono, _no_library, _stereo
+from tests.songhost import RATE, _mono, _stereo
+from tests.test_enveloped_host import _layout, _no_library
 from tests.test_looped_host import LOOP_FIELDS, _LoopLib
 
 REV_FIELDS = LOOP_FIELDS + ["flags"]

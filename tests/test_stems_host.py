@@ -1,5 +1,5 @@
 """What the stems of a compiled song -- ``CompiledSequence.stems`` and ``stems_into``, ``SongStems``, ``N.Sequence.stems``,
-sh_seq_render_stems -- need of the host alone (no GPU; the fake native layer of tests/test_desk_host.py and tests/test_clips_host.py):
+sh_seq_render_stems -- need of the host alone (no GPU; the fake native layer of tests/songhost.py):
 that ``stems`` hands on exactly the desk's keywords plus the stride, that the stride it picks keeps every plane on the store's 16-byte
 grid, what is refused before any buffer is made, that the new symbol is declared in the header and bound, and that ``stem()`` is still
 ``render`` with one-hot gains.  The bytes: tests/test_gpu_stems.py."""
@@ -11,32 +11,13 @@ import pytest
 
 from synthesizer_amd import _native as N
 from synthesizer_amd import mixer
-from tests.test_bus_automation_host import _Auto
-from tests.test_channels_host import _fake
-from tests.test_desk_host import _Lib, _Seq
-from tests.test_enveloped_host import RATE, _Buf, _mono, _stereo
+from tests.songhost import RATE, _Auto, _fake, _Lib, _mono, _Seq, _StemBuf, _stereo
 
 nan, inf = float("nan"), float("inf")
 
 
-class _StemBuf(_Buf):
-    """a device buffer as the mixer sees it: every one that was made, and every view that was cut from it"""
-    made = []
-
-    def __init__(self, nbytes=0):
-        _Buf.__init__(self, nbytes)
-        self.views, self.parent = [], None
-        _StemBuf.made.append(self)
-
-    def view(self, offset, nbytes):
-        v = _StemBuf.__new__(_StemBuf)
-        v.nbytes, v.views, v.parent = nbytes, [], self
-        self.views.append((offset, nbytes))
-        return v
-
-
 class _StemSeq(_Seq):
-    """tests/test_desk_host._Seq, which also keeps what each stems call was handed"""
+    """tests/songhost._Seq, which also keeps what each stems call was handed"""
 
     def __init__(self, *a, **kw):
         _Seq.__init__(self, *a, **kw)
