@@ -1064,6 +1064,20 @@ int sh_pcm_stats_stereo(const sh_buf* in, size_t nframes, int width, uint32_t ma
  * rows == NULL with a non-empty window.  nframes == 0 with nblocks == 0 succeeds and launches nothing. */
 int sh_pcm_level_blocks(const sh_buf* in, size_t sample_offset, size_t nframes, int nch, int width, size_t plane_samples, uint32_t nplanes,
                         uint64_t origin_frame, uint64_t block_frames, sh_seq_meter* rows /* host, nblocks * nplanes */, size_t nblocks);
+/* The waveform EXTREMES per block of the same PCM, for drawing: per block and channel the smallest and the largest sample as signed
+ * values of the width (audioop.minmax of that channel's samples; width 1 signed, width 3 the sign-extended 24-bit value).  A mono
+ * input fills channel 0 and stores lo[1] = hi[1] = 0.  Every block of a call counts at least one frame, so the identity of the fold
+ * (lo = INT32_MAX, hi = INT32_MIN) never reaches the table.  csrc/pcmextent.hpp has the row, csrc/pcmblocks.hpp the geometry. */
+typedef struct sh_pcm_extent {
+    int32_t lo[2];
+    int32_t hi[2];
+} sh_pcm_extent;                   /* 16 bytes */
+/* sh_pcm_level_blocks' arguments, planes, grid, block-major table and refusals (each message under this function's name), with rows a
+ * HOST array of nblocks * nplanes sh_pcm_extent.  Integer min and max only: the same table on every run and for every split.
+ * SYNCHRONOUS: one launch, one wave per block and plane (two launches where a block is longer than 8192 samples; at width 3 an
+ * unpacking launch per plane in front), the table copied back, one wait.  nframes == 0 with nblocks == 0 succeeds and launches nothing. */
+int sh_pcm_extent_blocks(const sh_buf* in, size_t sample_offset, size_t nframes, int nch, int width, size_t plane_samples, uint32_t nplanes,
+                         uint64_t origin_frame, uint64_t block_frames, sh_pcm_extent* rows /* host, nblocks * nplanes */, size_t nblocks);
 
 /* ---- Sample.resample -> audioop.ratecv(frames, width, nchannels, inrate, outrate, None) */
 size_t sh_resample_out_frames(size_t in_frames, int inrate, int outrate);

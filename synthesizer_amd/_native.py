@@ -110,6 +110,12 @@ class SeqMeterClips(C.Structure):                                               
 
 SEQ_METER_CLIPS_DTYPE = np.dtype(SEQ_METER_DTYPE.descr + [("clipped", "<u4", (2,))])    # sh_seq_meter_clips, 48 bytes, no padding
 assert SEQ_METER_CLIPS_DTYPE.itemsize == C.sizeof(SeqMeterClips) == 48
+class PcmExtent(C.Structure):                                                        # sh_pcm_extent
+    _fields_ = [("lo", C.c_int32 * 2), ("hi", C.c_int32 * 2)]
+
+
+PCM_EXTENT_DTYPE = np.dtype([("lo", "<i4", (2,)), ("hi", "<i4", (2,))])               # sh_pcm_extent, 16 bytes, no padding
+assert PCM_EXTENT_DTYPE.itemsize == C.sizeof(PcmExtent) == 16
 SEQ_MAX_GROUPS = 8                                                                    # SH_SEQ_MAX_GROUPS
 SEQ_TILE_SAMPLES = {1: 1024, 2: 2048, 3: 1024, 4: 1024}                               # shq::tile_samples(width): a block of a level history
 SEQ_LEVELS = ("plain", "rate", "pan", "env", "loop", "rev", "chan")                   # SH_SEQ_LEVEL_*
@@ -261,6 +267,8 @@ _SIGNATURES = {
     "sh_pcm_stats_stereo": (C.c_int, [_P, C.c_size_t, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
     "sh_pcm_level_blocks": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(SeqMeter),
                                       C.c_size_t]),
+    "sh_pcm_extent_blocks": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(PcmExtent),
+                                       C.c_size_t]),
     "sh_resample_out_frames": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int]),
     "sh_resample": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_size_t)]),
     "sh_resample_span": (C.c_int, [C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -656,6 +664,18 @@ def pcm_level_blocks(buf: "DeviceBuffer", sample_offset: int, nframes: int, nch:
     blocks = np.zeros((nblocks, nplanes), dtype=SEQ_METER_DTYPE)
     rows = blocks.ctypes.data_as(C.POINTER(SeqMeter)) if blocks.size else None
     check(lib().sh_pcm_level_blocks(buf.handle, sample_offset, nframes, nch, width, plane_samples, nplanes, origin_frame, block_frames, rows, nblocks))
+    return blocks
+
+
+def pcm_extent_blocks(buf: "DeviceBuffer", sample_offset: int, nframes: int, nch: int, width: int, plane_samples: int, nplanes: int,
+                      origin_frame: int, block_frames: int) -> np.ndarray:
+    """sh_pcm_extent_blocks: the waveform extremes per block of the planes ``pcm_level_blocks`` describes, on its grid: a numpy array of
+    shape ``(nblocks, nplanes)`` and dtype ``PCM_EXTENT_DTYPE`` -- per channel ``lo`` and ``hi``, the smallest and the largest sample
+    (``audioop.minmax``), a mono input's channel 1 reading 0.  One launch, synchronous; an empty window launches nothing."""
+    nblocks = (origin_frame + nframes - 1) // block_frames - origin_frame // block_frames + 1 if nframes > 0 else 0
+    blocks = np.zeros((nblocks, nplanes), dtype=PCM_EXTENT_DTYPE)
+    rows = blocks.ctypes.data_as(C.POINTER(PcmExtent)) if blocks.size else None
+    check(lib().sh_pcm_extent_blocks(buf.handle, sample_offset, nframes, nch, width, plane_samples, nplanes, origin_frame, block_frames, rows, nblocks))
     return blocks
 
 

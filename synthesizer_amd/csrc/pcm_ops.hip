@@ -8,7 +8,9 @@
 #include "pcmdev.hpp"
 #include "pcmhost.hpp"
 #include "pcmblocks.hpp"
+#include "pcmextent.hpp"
 #include <stdlib.h>
+#include <limits>
 #include <type_traits>
 
 namespace {
@@ -444,6 +446,124 @@ __global__ __launch_bounds__(256) void k_pcm_level_fold(const shmt::Row* __restr
     if ((threadIdx.x & 63) == 0) table[j * nplanes + r] = sum;
 }
 
+// ---- the waveform extremes per block of PCM in device memory (sh_pcm_extent_blocks; pcmextent.hpp has the row, pcmblocks.hpp the geometry) --
+// a wave's rows into lane 0's: shpe::fold over the six shuffle steps (a mono input's channel 1 stays the constant identity)
+template <int NCH>
+__device__ __forceinline__ shpe::Row wave_fold_extent(shpe::Row r) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        shpe::Row q = shpe::identity();
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            q.lo[c] = __shfl_down(r.lo[c], o, 64);
+            q.hi[c] = __shfl_down(r.hi[c], o, 64);
+        }
+        shpe::fold(r, q);
+    }
+    return r;
+}
+
+// One WAVE per (part slot, plane), four to a workgroup: wave 4 * block_id + (threadIdx.x >> 6) of plane r0 + blockIdx.z finds its block
+// and slot by the shift (g.nwg counts waves here, g.out holds shpe::Row), so the waves of a workgroup take consecutive slots of one
+// plane and share nothing.  The wave's number is read into a scalar register, so the geometry is scalar arithmetic.  A wave reads the
+// samples [s0, s1) of its block's cut range in its plane and nothing else, as k_pcm_level_blocks divides them: a scalar head up to the
+// 16-byte boundary, 16-byte vectors (up to four in flight per lane), a scalar tail; scalar samples are assembled from bytes, so a view
+// cut at an odd byte is all head.  The vectors fold into two accumulators of their own type by elementwise min and max -- one statement
+// for every width, packed at 16 bits -- whose element e goes to channel e % NCH behind the loop; where a stereo plane's head is odd the
+// two sides change places once, there.  A lane that loaded no vector leaves its accumulators out, so an empty slot yields the identity.
+// The lanes fold by wave shuffle and lane 0 stores the row, with the mono rule where it is a row of the table: no LDS, no barrier, no
+// atomics, one writer per row, nothing zeroed first.
+template <typename T, int NCH>
+__global__ __launch_bounds__(256) void k_pcm_extent_blocks(const LevelBlocks g) {
+    constexpr uint32_t V = 16 / sizeof(T);
+    typedef T vec_t __attribute__((ext_vector_type(V)));
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t w = sh::block_id() * 4 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (w >= g.nwg) return;                                    // (the last workgroup's waves past the end; a launch folded into two dimensions rounds up)
+    const uint32_t r = g.r0 + blockIdx.z;
+    const uint64_t j = w >> g.shift, p = w - (j << g.shift);
+    uint64_t a, b, s0, s1;
+    shpb::range(g.first, j, g.origin, g.n, g.B, a, b);
+    shpb::part((b - a) * NCH, p, s0, s1);
+    const unsigned char* x = (const unsigned char*)g.in + ((uint64_t)r * g.plane_samples + (a - g.origin) * NCH + s0) * sizeof(T);
+    const uint32_t cnt = (uint32_t)(s1 - s0);                  // at most shpb::PART_SAMPLES
+    const uintptr_t at = (uintptr_t)x;
+    uint32_t head = cnt;
+    if (at % sizeof(T) == 0) {
+        head = (uint32_t)((16 - (at & 15)) & 15) / (uint32_t)sizeof(T);
+        if (head > cnt) head = cnt;
+    }
+    const uint32_t nvec = (cnt - head) / V, tail = head + nvec * V;
+    shpe::Row row = shpe::identity();
+    auto one = [&](uint32_t i) {                               // shpe::take with both channels spelled out: the other side takes its identity
+        T v;
+        __builtin_memcpy(&v, x + (size_t)i * sizeof(T), sizeof(T));
+        const int32_t q = (int32_t)v;
+        const bool right = NCH == 2 && (i & 1);
+        const int32_t l0 = right ? INT32_MAX : q, h0 = right ? INT32_MIN : q;
+        row.lo[0] = l0 < row.lo[0] ? l0 : row.lo[0];
+        row.hi[0] = h0 > row.hi[0] ? h0 : row.hi[0];
+        if constexpr (NCH == 2) {
+            const int32_t l1 = right ? q : INT32_MAX, h1 = right ? q : INT32_MIN;
+            row.lo[1] = l1 < row.lo[1] ? l1 : row.lo[1];
+            row.hi[1] = h1 > row.hi[1] ? h1 : row.hi[1];
+        }
+    };
+    for (uint32_t i = lane; i < head; i += 64) one(i);
+    for (uint32_t i = tail + lane; i < cnt; i += 64) one(i);
+
+    const vec_t* vin = reinterpret_cast<const vec_t*>(x + (size_t)head * sizeof(T));
+    vec_t mn = (vec_t)(std::numeric_limits<T>::max()), mx = (vec_t)(std::numeric_limits<T>::min());
+    constexpr uint32_t INFLIGHT = 4;
+    uint32_t v = lane;
+    for (; v + (INFLIGHT - 1) * 64 < nvec; v += INFLIGHT * 64) {
+        vec_t q[INFLIGHT];
+#pragma unroll
+        for (uint32_t k = 0; k < INFLIGHT; ++k) q[k] = vin[v + k * 64];
+#pragma unroll
+        for (uint32_t k = 0; k < INFLIGHT; ++k) mn = __builtin_elementwise_min(mn, q[k]), mx = __builtin_elementwise_max(mx, q[k]);
+    }
+    for (; v < nvec; v += 64) {
+        const vec_t q = vin[v];
+        mn = __builtin_elementwise_min(mn, q), mx = __builtin_elementwise_max(mx, q);
+    }
+    shpe::Row vrow = shpe::identity();                         // by element parity
+    if (lane < nvec) {
+#pragma unroll
+        for (uint32_t e = 0; e < V; ++e) {
+            const int32_t l = (int32_t)mn[e], h = (int32_t)mx[e];
+            vrow.lo[e % NCH] = l < vrow.lo[e % NCH] ? l : vrow.lo[e % NCH];
+            vrow.hi[e % NCH] = h > vrow.hi[e % NCH] ? h : vrow.hi[e % NCH];
+        }
+    }
+    if (NCH == 2 && (head & 1)) {                              // the vectors began on a right sample: the two sides change places
+        const int32_t l = vrow.lo[0], h = vrow.hi[0];
+        vrow.lo[0] = vrow.lo[1], vrow.hi[0] = vrow.hi[1], vrow.lo[1] = l, vrow.hi[1] = h;
+    }
+    shpe::fold(row, vrow);
+    row = wave_fold_extent<NCH>(row);
+    if (lane == 0) {
+        if (!g.shift) row = shpe::stored(row, NCH);            // a row of the table: the mono rule (a partial row keeps the identity)
+        typedef int32_t row_t __attribute__((ext_vector_type(4)));
+        const row_t q = {row.lo[0], row.lo[1], row.hi[0], row.hi[1]};
+        reinterpret_cast<row_t*>(g.out)[(size_t)w * g.nplanes + r] = q;       // (the library's scratch: rows stand on 16 bytes)
+    }
+}
+
+// the partial rows of a call whose blocks have 2^shift part slots into the table: one wave per table row, as k_pcm_level_fold -- the four
+// waves of a workgroup take four consecutive blocks of plane r0 + blockIdx.z -- its lanes over the slots, shpe::fold all the way, lane 0
+// stores the row with the mono rule
+__global__ __launch_bounds__(256) void k_pcm_extent_fold(const shpe::Row* __restrict__ parts, uint32_t shift, uint64_t nblocks, uint32_t nplanes, uint32_t r0,
+                                                         uint32_t nch, shpe::Row* __restrict__ table) {
+    const uint64_t j = sh::block_id() * 4 + (threadIdx.x >> 6);
+    if (j >= nblocks) return;
+    const uint32_t r = r0 + blockIdx.z;
+    shpe::Row all = shpe::identity();
+    for (uint64_t p = threadIdx.x & 63; p >> shift == 0; p += 64) shpe::fold(all, parts[((j << shift) + p) * nplanes + r]);
+    all = wave_fold_extent<2>(all);
+    if ((threadIdx.x & 63) == 0) table[j * nplanes + r] = shpe::stored(all, nch);
+}
+
 // 24-bit <-> 32-bit: a thread converts four samples (12 bytes <-> 16 bytes); the 12 bytes are read / written as three
 // dwords when the 3-byte stream starts on a dword boundary, byte by byte otherwise (the tail always is).
 __global__ __launch_bounds__(256) void k_unpack24(const unsigned char* __restrict__ in, size_t n, int shift, int* __restrict__ out, int dwords) {
@@ -612,14 +732,52 @@ int level_blocks_run(const void* base, size_t stride, size_t nframes, int nch, u
     SH_HIP(hipStreamSynchronize(st));
     return SH_OK;
 }
-}  // namespace
 
-extern "C" {
+// sh_pcm_extent_blocks behind its checks, as level_blocks_run: one wave per part slot, four to a workgroup; the partial rows of a call
+// whose blocks have more than one part folded by k_pcm_extent_fold; the table through the library's scratch, one copy, one wait
+template <typename T>
+int extent_blocks_run(const void* base, size_t stride, size_t nframes, int nch, uint32_t nplanes, uint64_t origin, uint64_t B,
+                      sh_pcm_extent* rows, size_t nblocks) {
+    static_assert(sizeof(sh_pcm_extent) == sizeof(shpe::Row), "sh_pcm_extent is shpe::Row");
+    const char* fn = "sh_pcm_extent_blocks";
+    LevelBlocks g{};
+    g.in = base, g.plane_samples = stride, g.n = nframes, g.origin = origin, g.B = B, g.first = origin / B;
+    g.shift = shpb::slot_shift(shpb::longest(origin, nframes, B) * (uint64_t)nch);
+    g.nwg = (uint64_t)nblocks << g.shift;                     // waves here
+    g.nplanes = nplanes;
+    if ((g.nwg + 3) / 4 > (uint64_t)sh::GRID_X_MAX * 65535u) return sh::set_error(SH_ERR_INVALID, "%s: %llu parts of blocks are more than one launch takes", fn, (unsigned long long)g.nwg);
+    const size_t b_table = nblocks * (size_t)nplanes * sizeof(shpe::Row);
+    const size_t b_parts = g.shift ? (size_t)g.nwg * nplanes * sizeof(shpe::Row) : 0;
+    int rc = sh::ensure_scratch(b_table + b_parts);
+    if (rc) return rc;
+    shpe::Row* table = (shpe::Row*)sh::state().scratch;
+    shpe::Row* parts = g.shift ? table + nblocks * (size_t)nplanes : table;
+    g.out = reinterpret_cast<shmt::Row*>(parts);              // (the kernel stores shpe::Row there)
+    hipStream_t st = sh::state().stream;
+    dim3 grid = sh::grid1d(g.nwg, 4);
+    for (g.r0 = 0; g.r0 < nplanes; g.r0 += 65535u) {          // (a grid's third dimension holds 65535 planes)
+        grid.z = nplanes - g.r0 < 65535u ? nplanes - g.r0 : 65535u;
+        if (nch == 1) hipLaunchKernelGGL((k_pcm_extent_blocks<T, 1>), grid, dim3(256), 0, st, g);
+        else hipLaunchKernelGGL((k_pcm_extent_blocks<T, 2>), grid, dim3(256), 0, st, g);
+        SH_CHECK_LAUNCH("k_pcm_extent_blocks");
+    }
+    if (g.shift) {
+        grid = sh::grid1d(nblocks, 4);
+        for (uint32_t r0 = 0; r0 < nplanes; r0 += 65535u) {
+            grid.z = nplanes - r0 < 65535u ? nplanes - r0 : 65535u;
+            hipLaunchKernelGGL(k_pcm_extent_fold, grid, dim3(256), 0, st, (const shpe::Row*)parts, g.shift, (uint64_t)nblocks, nplanes, r0, (uint32_t)nch, table);
+            SH_CHECK_LAUNCH("k_pcm_extent_fold");
+        }
+    }
+    SH_HIP(hipMemcpyAsync(rows, table, b_table, hipMemcpyDeviceToHost, st));
+    SH_HIP(hipStreamSynchronize(st));
+    return SH_OK;
+}
 
-int sh_pcm_level_blocks(const sh_buf* in, size_t sample_offset, size_t nframes, int nch, int width, size_t plane_samples, uint32_t nplanes,
-                        uint64_t origin_frame, uint64_t block_frames, sh_seq_meter* rows, size_t nblocks) {
-    SH_REQUIRE_INIT();
-    const char* fn = "sh_pcm_level_blocks";
+// what sh_pcm_level_blocks and sh_pcm_extent_blocks refuse, in this order, each under the caller's name `fn`, before anything is
+// launched or written
+int blocks_check(const char* fn, const sh_buf* in, size_t sample_offset, size_t nframes, int nch, int width, size_t plane_samples, uint32_t nplanes,
+                 uint64_t origin_frame, uint64_t block_frames, const void* rows, size_t nblocks) {
     if (!in) return sh::set_error(SH_ERR_INVALID, "%s: NULL buffer", fn);
     if (nch != 1 && nch != 2) return sh::set_error(SH_ERR_INVALID, "%s: %d channels (1 or 2)", fn, nch);
     if (!valid_width3(width)) return sh::set_error(SH_ERR_INVALID, "%s: sample width %d not in {1,2,3,4}", fn, width);
@@ -640,9 +798,17 @@ int sh_pcm_level_blocks(const sh_buf* in, size_t sample_offset, size_t nframes, 
         return sh::set_error(SH_ERR_INVALID, "%s: %llu blocks for a window of %llu (blocks of %llu frames)", fn, (unsigned long long)nblocks,
                              (unsigned long long)want, (unsigned long long)block_frames);
     if (!rows && nblocks) return sh::set_error(SH_ERR_INVALID, "%s: NULL rows", fn);
-    if (!nframes) return SH_OK;                               // an empty window: no block, nothing launched
+    return SH_OK;
+}
+
+// the planes of a checked call of at least one frame as the kernels read them: run(tag, base, stride) with tag a sample of the kernels'
+// type and the planes `stride` samples apart from `base` on -- at width 3 the raw 24-bit values as int32, unpacked plane by plane
+// into planes nframes * nch samples apart
+template <typename Run>
+int blocks_planes(const sh_buf* in, size_t sample_offset, size_t nframes, int nch, int width, size_t plane_samples, uint32_t nplanes, Run&& run) {
+    const size_t n = nframes * (size_t)nch;
     const char* base = (const char*)in->ptr + sample_offset * (size_t)width;
-    if (width == 3) {                                         // the raw 24-bit values as int32, plane by plane into planes n samples apart
+    if (width == 3) {
         sh::Temp t32;
         int rc = t32.alloc((size_t)nplanes * n * 4);
         if (rc) return rc;
@@ -650,10 +816,31 @@ int sh_pcm_level_blocks(const sh_buf* in, size_t sample_offset, size_t nframes, 
             rc = sh::unpack24(base + (size_t)r * plane_samples * 3, n, 0, (int32_t*)t32.buf.ptr + (size_t)r * n);
             if (rc) return rc;
         }
-        return level_blocks_run<int>(t32.buf.ptr, n, nframes, nch, nplanes, origin_frame, block_frames, rows, nblocks);
+        return run((int)0, (const void*)t32.buf.ptr, n);
     }
-    return dispatch_width(width, [&](auto tag) {
-        return level_blocks_run<decltype(tag)>(base, plane_samples, nframes, nch, nplanes, origin_frame, block_frames, rows, nblocks);
+    return dispatch_width(width, [&](auto tag) { return run(tag, (const void*)base, plane_samples); });
+}
+}  // namespace
+
+extern "C" {
+
+int sh_pcm_level_blocks(const sh_buf* in, size_t sample_offset, size_t nframes, int nch, int width, size_t plane_samples, uint32_t nplanes,
+                        uint64_t origin_frame, uint64_t block_frames, sh_seq_meter* rows, size_t nblocks) {
+    SH_REQUIRE_INIT();
+    int rc = blocks_check("sh_pcm_level_blocks", in, sample_offset, nframes, nch, width, plane_samples, nplanes, origin_frame, block_frames, rows, nblocks);
+    if (rc || !nframes) return rc;                            // an empty window: no block, nothing launched
+    return blocks_planes(in, sample_offset, nframes, nch, width, plane_samples, nplanes, [&](auto tag, const void* base, size_t stride) {
+        return level_blocks_run<decltype(tag)>(base, stride, nframes, nch, nplanes, origin_frame, block_frames, rows, nblocks);
+    });
+}
+
+int sh_pcm_extent_blocks(const sh_buf* in, size_t sample_offset, size_t nframes, int nch, int width, size_t plane_samples, uint32_t nplanes,
+                         uint64_t origin_frame, uint64_t block_frames, sh_pcm_extent* rows, size_t nblocks) {
+    SH_REQUIRE_INIT();
+    int rc = blocks_check("sh_pcm_extent_blocks", in, sample_offset, nframes, nch, width, plane_samples, nplanes, origin_frame, block_frames, rows, nblocks);
+    if (rc || !nframes) return rc;
+    return blocks_planes(in, sample_offset, nframes, nch, width, plane_samples, nplanes, [&](auto tag, const void* base, size_t stride) {
+        return extent_blocks_run<decltype(tag)>(base, stride, nframes, nch, nplanes, origin_frame, block_frames, rows, nblocks);
     });
 }
 

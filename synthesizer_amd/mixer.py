@@ -666,6 +666,22 @@ class SongLevels:
         return "SongLevels(tracks=%r, master=%r)" % (self.tracks, self.master)
 
 
+def _grid_blocks(who: str, nblocks: int, first_block: int, block_frames: int, start_frame: int, frames: int) -> Tuple[List[int], List[int]]:
+    """the blocks of a window on the song's frame grid, checked: where each block's counted range begins and the frames it counts"""
+    end = start_frame + frames
+    want = (end - 1) // block_frames - start_frame // block_frames + 1 if frames > 0 else 0
+    if block_frames <= 0 or nblocks != want or (nblocks and first_block != start_frame // block_frames):
+        raise ValueError("%s: %d blocks of %d frames from block %d for frames [%d, %d)" % (who, nblocks, block_frames, first_block, start_frame, end))
+    edges = (first_block + np.arange(nblocks + 1, dtype=np.int64)) * block_frames      # the song's grid, cut to the window
+    lows, highs = np.maximum(edges[:-1], start_frame), np.minimum(edges[1:], end)
+    return lows.tolist(), (highs - lows).tolist()
+
+
+def _fold_cuts(first_block: int, nblocks: int, n: int) -> List[int]:
+    """where ``nblocks`` blocks from song block ``first_block`` on are cut when merged by ``song block index // n``"""
+    return [0] + [j for j in range(1, nblocks) if (first_block + j) % n == 0] + [nblocks]
+
+
 class SongHistory:
     """The levels of a rendered window OVER TIME (``CompiledSequence.render(meters="history")``): one ``SongLevels`` per BLOCK, all from the
     one launch that rendered the window.  Blocks are anchored to the SONG, not to the window: block index ``i`` covers song frames
@@ -700,15 +716,7 @@ class SongHistory:
         self.start_frame, self.frames = int(start_frame), int(frames)
         self.samplewidth, self.nchannels, self.samplerate, self.ngroups = int(samplewidth), int(nchannels), int(samplerate), int(ngroups)
         self.nblocks = int(self.peak.shape[0])
-        end = self.start_frame + self.frames
-        want = (end - 1) // self.block_frames - self.start_frame // self.block_frames + 1 if self.frames > 0 else 0
-        if self.block_frames <= 0 or self.nblocks != want or (self.nblocks and self.first_block != self.start_frame // self.block_frames):
-            raise ValueError("SongHistory: %d blocks of %d frames from block %d for frames [%d, %d)" % (
-                self.nblocks, self.block_frames, self.first_block, self.start_frame, end))
-        edges = (self.first_block + np.arange(self.nblocks + 1, dtype=np.int64)) * self.block_frames      # the song's grid, cut to the window
-        lows, highs = np.maximum(edges[:-1], self.start_frame), np.minimum(edges[1:], end)
-        self.starts: List[int] = lows.tolist()
-        self.block_counts: List[int] = (highs - lows).tolist()     # the frames counted in each block
+        self.starts, self.block_counts = _grid_blocks("SongHistory", self.nblocks, self.first_block, self.block_frames, self.start_frame, self.frames)
         self.history = self
 
     @classmethod
@@ -795,7 +803,7 @@ class SongHistory:
             return SongHistory(self.peak, self.sum_squares, 0, self.block_frames * n, self.start_frame, self.frames, self.samplewidth, self.nchannels,
                                self.samplerate, self.ngroups, clipped=self._clipped)
         first = self.first_block // n
-        cuts = [0] + [j for j in range(1, self.nblocks) if (self.first_block + j) % n == 0] + [self.nblocks]
+        cuts = _fold_cuts(self.first_block, self.nblocks, n)
         peak = np.stack([self.peak[a:b].max(axis=0) for a, b in zip(cuts, cuts[1:])])
         sq = np.stack([self._sums(a, b) for a, b in zip(cuts, cuts[1:])])
         counts = None if self._clipped is None else np.stack([self._clipped[a:b].sum(axis=0, dtype=np.uint64) for a, b in zip(cuts, cuts[1:])])
@@ -821,17 +829,120 @@ class SongHistory:
         return "SongHistory(%d blocks of %d frames, frames [%d, %d))" % (self.nblocks, self.block_frames, self.start_frame, self.start_frame + self.frames)
 
 
+class Waveform:
+    """The waveform EXTREMES of a window OVER TIME, for drawing (``Sample.waveform``, ``SongStems.waveform``, ``CompiledSequence.waveform``):
+    per block, row and channel the smallest and the largest sample, ``lo`` and ``hi`` -- ``audioop.minmax`` of that channel's samples in
+    that block, signed values of the sample width -- read off the samples in device memory in one launch.  What a peak row cannot say is
+    here: a DC offset, a half-wave, which way a transient points.  Blocks are anchored to the SONG as ``SongHistory``'s are: block index
+    ``i`` covers song frames ``[i * block_frames, (i + 1) * block_frames)`` cut to the window, so the first and the last block may be
+    partial and a block that lies whole inside two windows reads the same from both.
+
+    ``lo``, ``hi``: int32 arrays ``(nblocks, nrows, 2)``, rows in table order (tracks, master, groups; one row for a ``Sample``), a
+    mono input's channel 1 reading 0.  ``start_frame``, ``frames``, ``first_block``, ``block_frames``, ``nblocks`` (``len()``),
+    ``starts``, ``block_counts``, ``samplewidth``, ``nchannels``, ``samplerate``, ``ngroups``: as ``SongHistory`` has them.
+    ``extents()``: ``(nblocks, nrows, 2, 2)`` as ``[..., channel, (lo, hi)]``, a mono input's channel 1 a copy of channel 0 -- the pairs
+    to draw; ``self[j]``: block ``j``'s ``(nrows, 2, 2)`` of them.  ``peaks()``: ``max(-lo, hi)`` as uint32, ``SongHistory.peaks()`` of
+    the same call (``|-32768|`` is 32768).  ``total()``: the window's ``(lo, hi)``, each ``(nrows, 2)``.  ``fold(n)``: blocks ``n`` times
+    as long, the zoom."""
+
+    def __init__(self, lo, hi, first_block: int, block_frames: int, start_frame: int, frames: int, samplewidth: int, nchannels: int,
+                 samplerate: int, ngroups: int = 0) -> None:
+        self.lo, self.hi = np.asarray(lo, dtype=np.int32), np.asarray(hi, dtype=np.int32)
+        if self.lo.ndim != 3 or self.lo.shape[2] != 2 or self.hi.shape != self.lo.shape:
+            raise ValueError("Waveform: lo and hi are (nblocks, nrows, 2) arrays")
+        self.first_block, self.block_frames = int(first_block), int(block_frames)
+        self.start_frame, self.frames = int(start_frame), int(frames)
+        self.samplewidth, self.nchannels, self.samplerate, self.ngroups = int(samplewidth), int(nchannels), int(samplerate), int(ngroups)
+        self.nblocks = int(self.lo.shape[0])
+        self.starts, self.block_counts = _grid_blocks("Waveform", self.nblocks, self.first_block, self.block_frames, self.start_frame, self.frames)
+
+    @classmethod
+    def of_blocks(cls, blocks, nrows: int, block_frames: int, start_frame: int, frames: int, samplewidth: int, nchannels: int, samplerate: int,
+                  ngroups: int = 0) -> "Waveform":
+        """``blocks``: ``N.pcm_extent_blocks``' array ``(nblocks, nrows)`` of sh_pcm_extent rows on the grid of ``block_frames``, or None
+        for an empty window"""
+        if blocks is None or not len(blocks):
+            empty = np.zeros((0, nrows, 2), dtype=np.int32)
+            return cls(empty, empty, start_frame // block_frames, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups)
+        return cls(blocks["lo"], blocks["hi"], start_frame // block_frames, block_frames, start_frame, frames, samplewidth, nchannels, samplerate, ngroups)
+
+    def __len__(self) -> int:
+        return self.nblocks
+
+    def _both(self, a: np.ndarray) -> np.ndarray:
+        """a copy with a mono input's channel 0 in channel 1 as well"""
+        out = a.copy()
+        if self.nchannels != 2:
+            out[..., 1] = out[..., 0]
+        return out
+
+    def extents(self) -> np.ndarray:
+        return np.stack([self._both(self.lo), self._both(self.hi)], axis=-1)
+
+    def __getitem__(self, j: int) -> np.ndarray:
+        j = operator.index(j)
+        if j < -self.nblocks or j >= self.nblocks:
+            raise IndexError("Waveform: block %d of %d" % (j, self.nblocks))
+        j %= self.nblocks
+        return np.stack([self._both(self.lo[j]), self._both(self.hi[j])], axis=-1)
+
+    def __iter__(self):
+        return (self[j] for j in range(self.nblocks))
+
+    def peaks(self) -> np.ndarray:
+        return self._both(np.maximum(-self.lo.astype(np.int64), self.hi.astype(np.int64)).astype(np.uint32))
+
+    def _identity(self) -> Tuple[np.ndarray, np.ndarray]:
+        """``audioop.minmax`` of no sample per row and channel -- the identity of min and max -- a mono input's channel 1 reading 0"""
+        lo = np.full(self.lo.shape[1:], np.iinfo(np.int32).max, dtype=np.int32)
+        hi = np.full(self.lo.shape[1:], np.iinfo(np.int32).min, dtype=np.int32)
+        if self.nchannels != 2:
+            lo[:, 1] = hi[:, 1] = 0
+        return lo, hi
+
+    def total(self) -> Tuple[np.ndarray, np.ndarray]:
+        """the whole window's ``(lo, hi)``, each ``(nrows, 2)``: min of the lows, max of the highs (an empty window: what
+        ``audioop.minmax`` gives for no sample, 2^31 - 1 and -2^31)"""
+        if not self.nblocks:
+            return self._identity()
+        return self.lo.min(axis=0), self.hi.max(axis=0)
+
+    def fold(self, n: int) -> "Waveform":
+        """Blocks ``n`` times as long: the blocks merged by ``song block index // n``, so that the result does not depend on where the
+        window began -- min of ``lo``, max of ``hi``."""
+        n = operator.index(n)
+        if n <= 0:
+            raise ValueError("Waveform: fold(n) needs a positive n")
+        if not self.nblocks:
+            return Waveform(self.lo, self.hi, 0, self.block_frames * n, self.start_frame, self.frames, self.samplewidth, self.nchannels,
+                            self.samplerate, self.ngroups)
+        cuts = _fold_cuts(self.first_block, self.nblocks, n)
+        lo = np.stack([self.lo[a:b].min(axis=0) for a, b in zip(cuts, cuts[1:])])
+        hi = np.stack([self.hi[a:b].max(axis=0) for a, b in zip(cuts, cuts[1:])])
+        return Waveform(lo, hi, self.first_block // n, self.block_frames * n, self.start_frame, self.frames, self.samplewidth, self.nchannels,
+                        self.samplerate, self.ngroups)
+
+    def __repr__(self) -> str:
+        return "Waveform(%d blocks of %d frames, frames [%d, %d))" % (self.nblocks, self.block_frames, self.start_frame, self.start_frame + self.frames)
+
+
 def _block_frames(who: str, block_frames) -> int:
     if isinstance(block_frames, bool) or not isinstance(block_frames, (int, np.integer)) or block_frames <= 0:
         raise ValueError("%s: block_frames is a positive int, not %r" % (who, block_frames))
     return int(block_frames)
 
 
-def _levels_format(who: str, sample: Sample) -> None:
+def _origin_frame(who: str, origin_frame) -> int:
+    if isinstance(origin_frame, bool) or not isinstance(origin_frame, (int, np.integer)) or origin_frame < 0:
+        raise ValueError("%s: origin_frame is a non-negative int, not %r" % (who, origin_frame))
+    return int(origin_frame)
+
+
+def _levels_format(who: str, sample: Sample, what: str = "a level history") -> None:
     if sample.nchannels not in (1, 2):
-        raise ValueError("%s: a level history needs a mono or stereo sample, this one has %d channels" % (who, sample.nchannels))
+        raise ValueError("%s: %s needs a mono or stereo sample, this one has %d channels" % (who, what, sample.nchannels))
     if sample.samplewidth not in (1, 2, 3, 4):
-        raise ValueError("%s: a level history needs samples of 1 to 4 bytes, these have %d" % (who, sample.samplewidth))
+        raise ValueError("%s: %s needs samples of 1 to 4 bytes, these have %d" % (who, what, sample.samplewidth))
 
 
 def level_history(sample: Sample, block_frames: int, origin_frame: int = 0) -> SongHistory:
@@ -841,13 +952,26 @@ def level_history(sample: Sample, block_frames: int, origin_frame: int = 0) -> S
     ``block_frames`` frames, so the first and the last block may be partial and the halves of a sample cut on a block boundary give the
     blocks of the whole.  ``total()``, ``fold(n)``, ``peaks()`` and ``starts`` are ``SongHistory``'s.  Mono and stereo only."""
     block_frames = _block_frames("level_history", block_frames)
-    if isinstance(origin_frame, bool) or not isinstance(origin_frame, (int, np.integer)) or origin_frame < 0:
-        raise ValueError("level_history: origin_frame is a non-negative int, not %r" % (origin_frame,))
+    origin_frame = _origin_frame("level_history", origin_frame)
     _levels_format("level_history", sample)
-    origin_frame, frames = int(origin_frame), len(sample)
+    frames = len(sample)
     nch, width = sample.nchannels, sample.samplewidth
     blocks = N.pcm_level_blocks(sample._device(), 0, frames, nch, width, frames * nch, 1, origin_frame, block_frames) if frames else None
     return SongHistory.of_blocks(blocks, 1, block_frames, origin_frame, frames, width, nch, sample.samplerate)
+
+
+def waveform(sample: Sample, block_frames: int, origin_frame: int = 0) -> Waveform:
+    """The waveform extremes of any ``Sample`` OVER TIME, in one launch: a ``Waveform`` with one row per block -- per channel the
+    smallest and the largest sample of block ``j`` (``audioop.minmax``) in ``lo[j, 0]`` and ``hi[j, 0]``, at every width -- on
+    ``level_history``'s grid: frame ``i`` of the sample stands at frame ``origin_frame + i`` of a grid of ``block_frames`` frames.  One
+    block per pixel column draws the overview; ``fold(n)`` zooms out.  Mono and stereo only."""
+    block_frames = _block_frames("waveform", block_frames)
+    origin_frame = _origin_frame("waveform", origin_frame)
+    _levels_format("waveform", sample, "a waveform")
+    frames = len(sample)
+    nch, width = sample.nchannels, sample.samplewidth
+    blocks = N.pcm_extent_blocks(sample._device(), 0, frames, nch, width, frames * nch, 1, origin_frame, block_frames) if frames else None
+    return Waveform.of_blocks(blocks, 1, block_frames, origin_frame, frames, width, nch, sample.samplerate)
 
 
 class SongStems:
@@ -859,7 +983,9 @@ class SongStems:
     own, so it outlives this object.  ``level_history(block_frames)``: the levels of every stem per block of the song's frame grid, a
     ``SongHistory`` with the rows and the meaning of ``render(meters="history")`` -- one launch over all planes where the object knows
     its buffer (``buffer``, ``plane_frames``: the one device buffer and the planes' stride in frames; ``tile_frames``: the song's tile
-    in frames, the default block -- ``CompiledSequence.stems`` hands them on), one launch per row where it was built by hand."""
+    in frames, the default block -- ``CompiledSequence.stems`` hands them on), one launch per row where it was built by hand.
+    ``waveform(block_frames)``: the smallest and the largest sample of every stem per block of the same grid, a ``Waveform``, by the
+    same route."""
 
     def __init__(self, tracks: Sequence[Sample], master: Sample, groups: Sequence[Sample], start_frame: int, frames: int, *,
                  buffer: Optional[N.DeviceBuffer] = None, plane_frames: Optional[int] = None, tile_frames: Optional[int] = None) -> None:
@@ -878,23 +1004,41 @@ class SongStems:
         """The levels of every stem OVER TIME: a ``SongHistory`` whose rows are the tracks, the master and the groups, block ``i`` covering
         song frames ``[i * block_frames, (i + 1) * block_frames)`` cut to the window (``block_frames`` None: the song's tile, the block
         of ``render(meters="history")``).  Exact integers read off the stems' own samples (sh_pcm_level_blocks)."""
+        blocks, nrows, block_frames = self._per_block(N.pcm_level_blocks, block_frames, "a level history")
         master = self.master
-        nch, width, rate = master.nchannels, master.samplewidth, master.samplerate
+        return SongHistory.of_blocks(blocks, nrows, block_frames, self.start_frame, self.frames, master.samplewidth, master.nchannels, master.samplerate,
+                                     len(self.groups))
+
+    def waveform(self, block_frames: Optional[int] = None) -> Waveform:
+        """The waveform extremes of every stem OVER TIME, for drawing: a ``Waveform`` whose rows are the tracks, the master and the groups,
+        on ``level_history``'s grid and with its default block -- per block, row and channel the smallest and the largest sample, read
+        off the stems' own samples (sh_pcm_extent_blocks): one launch over all planes where the object knows its buffer, one per row
+        where it was built by hand."""
+        blocks, nrows, block_frames = self._per_block(N.pcm_extent_blocks, block_frames, "a waveform")
+        master = self.master
+        return Waveform.of_blocks(blocks, nrows, block_frames, self.start_frame, self.frames, master.samplewidth, master.nchannels, master.samplerate,
+                                  len(self.groups))
+
+    def _per_block(self, table, block_frames: Optional[int], what: str) -> tuple:
+        """the checked call behind ``level_history`` and ``waveform``: ``table`` -- ``N.pcm_level_blocks`` or ``N.pcm_extent_blocks`` -- over
+        all planes of the one buffer, or row by row; (its array ``(nblocks, nrows)`` or None for an empty window, nrows, the block)"""
+        master = self.master
+        nch, width = master.nchannels, master.samplewidth
         if block_frames is None:
             block_frames = self._tile_frames if self._tile_frames is not None else max(1, N.SEQ_TILE_SAMPLES[width] // nch)
         block_frames = _block_frames("SongStems", block_frames)
-        _levels_format("SongStems", master)
+        _levels_format("SongStems", master, what)
         rows = self.rows()
         if any((s.nchannels, s.samplewidth, len(s)) != (nch, width, self.frames) for s in rows):
             raise ValueError("SongStems: every stem has the master's format and the window's %d frames" % self.frames)
         blocks = None
         if self.frames:
             if self._buffer is not None:
-                blocks = N.pcm_level_blocks(self._buffer, 0, self.frames, nch, width, self._plane_frames * nch, len(rows), self.start_frame, block_frames)
+                blocks = table(self._buffer, 0, self.frames, nch, width, self._plane_frames * nch, len(rows), self.start_frame, block_frames)
             else:
-                blocks = np.concatenate([N.pcm_level_blocks(s._device(), 0, self.frames, nch, width, self.frames * nch, 1, self.start_frame, block_frames)
+                blocks = np.concatenate([table(s._device(), 0, self.frames, nch, width, self.frames * nch, 1, self.start_frame, block_frames)
                                          for s in rows], axis=1)
-        return SongHistory.of_blocks(blocks, len(rows), block_frames, self.start_frame, self.frames, width, nch, rate, len(self.groups))
+        return blocks, len(rows), block_frames
 
     def rows(self) -> list:
         """all of them in plane order, which is the meter rows': the tracks, the master, the groups"""
@@ -1753,6 +1897,18 @@ class CompiledSequence:
             block_frames = _block_frames("CompiledSequence", block_frames)
         call = self._desk_call(gains, False, pans, master, automation, groups, False, stems=True)
         return self._stems(*self._range(start_frame, nframes), call).level_history(block_frames)
+
+    def waveform(self, start_frame: int = 0, nframes: Optional[int] = None, block_frames: Optional[int] = None,
+                 gains: Optional[Sequence[float]] = None, pans: Optional[Sequence] = None, master: Optional[float] = None,
+                 automation: Optional[Automation] = None, groups: Optional[Sequence] = None) -> Waveform:
+        """The waveform extremes of frames ``[start_frame, start_frame + nframes)`` OVER TIME, for drawing, for EVERY desk ``stems`` takes:
+        ``stems(...)`` followed by ``SongStems.waveform(block_frames)`` -- two launches.  The ``Waveform``'s rows are the tracks, the
+        master and the groups, its blocks ``level_history``'s (``block_frames`` None: the song's tile in frames, else any positive
+        int).  The bytes are not returned: ``stems`` keeps them."""
+        if block_frames is not None:
+            block_frames = _block_frames("CompiledSequence", block_frames)
+        call = self._desk_call(gains, False, pans, master, automation, groups, False, stems=True)
+        return self._stems(*self._range(start_frame, nframes), call).waveform(block_frames)
 
     def chunks(self, chunk_frames: int, gains: Optional[Sequence[float]] = None, meters: bool = False, pans: Optional[Sequence] = None,
                master: Optional[float] = None, automation: Optional[Automation] = None, groups: Optional[Sequence] = None,

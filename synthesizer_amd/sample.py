@@ -1106,6 +1106,12 @@ class Sample:
         from .mixer import level_history                        # (lazily: mixer imports this module)
         return level_history(self, block_frames, origin_frame)
 
+    def waveform(self, block_frames: int, origin_frame: int = 0):
+        """The waveform extremes over time, per block of ``block_frames`` frames, in one launch, for drawing: ``mixer.waveform(self,
+        ...)``'s ``Waveform`` (per block and channel the smallest and the largest sample, ``audioop.minmax``, at every width)."""
+        from .mixer import waveform                             # (lazily: mixer imports this module)
+        return waveform(self, block_frames, origin_frame)
+
     def _channel_stats(self) -> Tuple[Tuple[int, int], Tuple[float, float]]:
         """((max|L|, max|R|), (sum L^2, sum R^2)) of a stereo sample, one pass on the device."""
         mx = (C.c_uint32 * 2)()

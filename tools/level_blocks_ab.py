@@ -3,6 +3,7 @@
 
     python tools/level_blocks_ab.py            the table below
     python tools/level_blocks_ab.py --trace    each (a) five times and nothing else, for rocprofv3 --kernel-trace --stats -- python ...
+    python tools/level_blocks_ab.py --extents [--trace]    the waveform extremes of the same two buffers (extents() below; profiles/waveform_ab.txt)
 
 Wall time with a device synchronise, medians of 15 after a warm-up of every shape; the compared variants run by turns in one process.
 (a)  one level_history at 1024-frame blocks: of a 120-s, 48-kHz stereo 16-bit Sample, and of the 12-plane stems buffer of the --stems
@@ -133,5 +134,76 @@ def main(trace=False):
     bus.close()
 
 
+def numpy_extents(pcm, block):
+    """the caller's way: (lo, hi), each (nblocks, channels), of a [frames, channels] array by reshape, min and max per block"""
+    whole = len(pcm) // block
+    body = pcm[:whole * block].reshape(whole, block, pcm.shape[1])
+    lo, hi = body.min(axis=1), body.max(axis=1)
+    if len(pcm) % block:                                        # the last, partial block
+        lo, hi = np.vstack([lo, pcm[whole * block:].min(axis=0)]), np.vstack([hi, pcm[whole * block:].max(axis=0)])
+    return lo, hi
+
+
+def extents(trace=False):
+    """--extents: the waveform extremes (sh_pcm_extent_blocks) of main()'s two buffers at 1024-frame blocks.
+    (a)  waveform(1024): of the Sample, and of the 12-plane stems buffer in one launch.
+    (b)  the caller's way today: get_frames_numpy() of the same PCM (of each of the twelve stems), reshaped, min / max per block.  The
+         PCM lies in device memory and nowhere else, so every pass downloads it: a fresh Sample over a view of the same bytes, which
+         holds no host copy.  (b)'s table is held to (a)'s first.
+    (c)  --extents --trace: each waveform and each level_history five times and nothing else, for rocprofv3 --kernel-trace --stats in a
+         run of its own: k_pcm_extent_blocks next to k_pcm_level_blocks on the same buffers in the same session."""
+    N.ensure_init(0)
+    info = N.device_info()
+    print("level_blocks_ab --extents: %s" % (info["name"] or info["arch"]), flush=True)
+    fb = 2 * WIDTH
+    frames = 120 * RATE
+    pcm = np.random.default_rng(0).integers(-32768, 32768, size=2 * frames, dtype=np.int16)
+    sample = Sample.from_raw_frames(pcm.tobytes(), WIDTH, RATE, 2).to_device()
+    ntracks = len(S.TRACK_GAINS)
+    what, nch, evs = S.meters_songs(4096)[0]
+    bus = mixer.compile_tracks([evs[t::ntracks] for t in range(ntracks)], RATE, nch, WIDTH)
+    glanes, mlane = S.bus_lanes(bus.frames)
+    tpans, gpans = S.pan_lanes(ntracks)
+    auto = bus.automation([None] * ntracks, master=mlane, groups=glanes, pans=tpans, group_pans=gpans)
+    stems = bus.stems(automation=auto, gains=S.TRACK_GAINS, pans=S.DESK_PANS, master=S.DESK_MASTER, groups=S.GROUPS)
+    nrows, plane = len(stems), stems._plane_frames
+    a_sample = lambda: sample.waveform(BLOCK)                   # noqa: E731
+    a_stems = lambda: stems.waveform(BLOCK)                     # noqa: E731
+    if trace:
+        for fn in (a_sample, lambda: sample.level_history(BLOCK), a_stems, lambda: stems.level_history(BLOCK)):
+            for _ in range(5):
+                fn()
+        N.sync()
+        return
+
+    def fresh(buf, offset, nframes):
+        """the same bytes as a Sample that holds no host copy"""
+        s = Sample(samplerate=RATE, nchannels=2, samplewidth=WIDTH)
+        s._set_device(buf.view(offset, nframes * fb), nframes * fb)
+        return s
+    b_sample = lambda: numpy_extents(fresh(sample._device(), 0, frames).get_frames_numpy(), BLOCK)      # noqa: E731
+    b_stems = lambda: [numpy_extents(fresh(stems._buffer, r * plane * fb, bus.frames).get_frames_numpy(), BLOCK) for r in range(nrows)]      # noqa: E731
+    w, (lo, hi) = a_sample(), b_sample()
+    assert np.array_equal(w.lo[:, 0], lo) and np.array_equal(w.hi[:, 0], hi), "the Sample: numpy's table is not waveform's"
+    ws, per_row = a_stems(), b_stems()
+    for r, (lo, hi) in enumerate(per_row):
+        assert np.array_equal(ws.lo[:, r], lo) and np.array_equal(ws.hi[:, r], hi), "stem %d: numpy's table is not waveform's" % r
+    assert np.array_equal(w.peaks(), sample.level_history(BLOCK).peaks()) and np.array_equal(ws.peaks(), stems.level_history(BLOCK).peaks())
+    print("(a) / (b)  a Sample of 120 s, 48 kHz, stereo, 16 bits: %d frames, %d blocks of %d frames; (b)'s table equals (a)'s" % (frames, len(w), BLOCK), flush=True)
+    show("", frames * fb, by_turns({"(a) Sample.waveform(1024): one launch, the table copied back": a_sample,
+                                    "(b) get_frames_numpy() of the same PCM, reshape, min / max per block": b_sample,
+                                    "    Sample.level_history(1024), for scale": lambda: sample.level_history(BLOCK)}))
+    print("(a) / (b)  the stems of the --stems song (%s): %d planes of %d frames, %d blocks of %d frames; (b)'s tables equal (a)'s"
+          % (what, nrows, bus.frames, len(ws), BLOCK), flush=True)
+    show("", nrows * bus.frames * fb, by_turns({"(a) SongStems.waveform(1024): one launch over %d planes" % nrows: a_stems,
+                                               "(b) get_frames_numpy() of each of the %d stems, reshape, min / max" % nrows: b_stems,
+                                               "    SongStems.level_history(1024), for scale": lambda: stems.level_history(BLOCK)}, warm=1))
+    auto.close()
+    bus.close()
+
+
 if __name__ == "__main__":
-    main("--trace" in sys.argv[1:])
+    if "--extents" in sys.argv[1:]:
+        extents("--trace" in sys.argv[1:])
+    else:
+        main("--trace" in sys.argv[1:])
