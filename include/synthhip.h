@@ -1079,6 +1079,24 @@ typedef struct sh_pcm_extent {
 int sh_pcm_extent_blocks(const sh_buf* in, size_t sample_offset, size_t nframes, int nch, int width, size_t plane_samples, uint32_t nplanes,
                          uint64_t origin_frame, uint64_t block_frames, sh_pcm_extent* rows /* host, nblocks * nplanes */, size_t nblocks);
 
+/* ---- Sample.convolve: a finite impulse response (a room, a plate, a cabinet, a filter) over PCM in device memory, in the direct
+ * form and EXACT (csrc/pcmfir.hpp has the contract).  The input: in_frames frames of nch (1 or 2) interleaved channels of `width` (1
+ * or 2) bytes from byte in_off of `in` on; the response: ir_frames frames (1 .. 2^22) of ir_nch channels of the same width from byte
+ * ir_off of `ir` on -- ir_nch == 1: the one response over every channel; ir_nch == 2 == nch: left over left, right over right.  The
+ * result has in_frames + ir_frames - 1 frames (0 where in_frames == 0) of nch channels: per channel and frame the exact integer sum of
+ * response[k] * input[i - k], input outside its frames counting as 0, then ONE rounding, audioop.mul's: fbound(sum * factor) --
+ * clamped to the width's limits, then floor.  With at most 2^22 taps every partial sum stays below 2^53, so the float64 FMA chain of
+ * the kernel is integer arithmetic and the bytes do not depend on how the work is divided.  The call writes frames [first, first +
+ * nframes) of the result to byte out_off of `out` on, and those bytes are that slice of the whole result's bytes.  All offsets are
+ * BYTES, and any byte will do: the kernels read and write sample by sample and ask for no alignment.  Asynchronous on the
+ * library's stream, as sh_pcm_mul: two launches (the response to float64 in the library's scratch, then one workgroup per tile of
+ * 2048 frames and channel).
+ * SH_ERR_INVALID, each with a message of its own and before anything is launched or written: a width other than 1 or 2, nch not 1
+ * or 2, ir_nch not 1 and not nch, ir_frames == 0 or above 2^22, a factor that is not finite, a window past the result, an operand that
+ * reaches past its buffer, out overlapping in or ir.  An empty window succeeds and launches nothing. */
+int sh_pcm_convolve(const sh_buf* in, size_t in_off, uint64_t in_frames, int nch, int width, const sh_buf* ir, size_t ir_off, uint32_t ir_frames,
+                    int ir_nch, double factor, uint64_t first, uint64_t nframes, sh_buf* out, size_t out_off);
+
 /* ---- Sample.resample -> audioop.ratecv(frames, width, nchannels, inrate, outrate, None) */
 size_t sh_resample_out_frames(size_t in_frames, int inrate, int outrate);
 /* width 1/2/4 integer PCM (bit-exact audioop arithmetic); is_float!=0: float32 PCM (width must be 4) */

@@ -120,6 +120,9 @@ SEQ_MAX_GROUPS = 8                                                              
 SEQ_TILE_SAMPLES = {1: 1024, 2: 2048, 3: 1024, 4: 1024}                               # shq::tile_samples(width): a block of a level history
 SEQ_LEVELS = ("plain", "rate", "pan", "env", "loop", "rev", "chan")                   # SH_SEQ_LEVEL_*
 PCM_PART_SAMPLES = 8192                                                               # shpb::PART_SAMPLES (csrc/pcmblocks.hpp): a block up to this long is one part
+PCM_FIR_MAX_TAPS = 1 << 22                                                            # shpf::MAX_TAPS (csrc/pcmfir.hpp): up to here the float64 sum is the integer sum
+PCM_FIR_TILE_FRAMES = 2048                                                            # shpf::TILE_FRAMES: the output frames of one workgroup of sh_pcm_convolve
+PCM_FIR_TAP_CHUNK = 1024                                                              # shpf::TAP_CHUNK: the taps under one staged span of the input
 
 
 class MixLevel(NamedTuple):
@@ -269,6 +272,8 @@ _SIGNATURES = {
                                       C.c_size_t]),
     "sh_pcm_extent_blocks": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(PcmExtent),
                                        C.c_size_t]),
+    "sh_pcm_convolve": (C.c_int, [_P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint32, C.c_int, C.c_double, C.c_uint64, C.c_uint64,
+                                  _P, C.c_size_t]),
     "sh_resample_out_frames": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int]),
     "sh_resample": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_size_t)]),
     "sh_resample_span": (C.c_int, [C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

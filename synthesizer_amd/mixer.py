@@ -974,6 +974,70 @@ def waveform(sample: Sample, block_frames: int, origin_frame: int = 0) -> Wavefo
     return Waveform.of_blocks(blocks, 1, block_frames, origin_frame, frames, width, nch, sample.samplerate)
 
 
+def _convolve_call(who: str, sample: Sample, ir: Sample, factor, start_frame, nframes) -> Tuple[float, int, int]:
+    """what a convolution refuses, before any call into the library: ``(factor, start_frame, nframes)`` of the checked call"""
+    if sample.nchannels not in (1, 2) or ir.nchannels not in (1, 2):
+        raise ValueError("%s: mono and stereo only, not %d channels under a response of %d" % (who, sample.nchannels, ir.nchannels))
+    if sample.samplewidth in (3, 4):
+        raise NotImplementedError("%s: %d-byte samples are not built: the exact sum needs more than a float64 there (make_16bit() first)"
+                                  % (who, sample.samplewidth))
+    if sample.samplewidth not in (1, 2):
+        raise ValueError("%s: samples of 1 or 2 bytes, not %d" % (who, sample.samplewidth))
+    if ir.samplewidth != sample.samplewidth:
+        raise ValueError("%s: the response has samples of %d bytes, the sample of %d" % (who, ir.samplewidth, sample.samplewidth))
+    if ir.samplerate != sample.samplerate:
+        raise ValueError("%s: the response is at %d Hz, the sample at %d (resample one of them)" % (who, ir.samplerate, sample.samplerate))
+    if ir.nchannels == 2 and sample.nchannels == 1:
+        raise ValueError("%s: a stereo response over a mono sample: make the sample stereo first (sample.stereo())" % who)
+    if len(ir) == 0:
+        raise ValueError("%s: an empty response" % who)
+    if len(ir) > N.PCM_FIR_MAX_TAPS:
+        raise ValueError("%s: a response of %d frames: at most 2**22 = %d keep the sum exact" % (who, len(ir), N.PCM_FIR_MAX_TAPS))
+    factor = 1.0 / 2 ** (8 * sample.samplewidth - 1) if factor is None else float(factor)
+    if not math.isfinite(factor):
+        raise ValueError("%s: the factor %r is not finite" % (who, factor))
+    total = len(sample) + len(ir) - 1 if len(sample) else 0
+    if isinstance(start_frame, bool) or not isinstance(start_frame, (int, np.integer)) or start_frame < 0:
+        raise ValueError("%s: start_frame is a non-negative int, not %r" % (who, start_frame))
+    if nframes is None:
+        nframes = max(total - start_frame, 0)
+    if isinstance(nframes, bool) or not isinstance(nframes, (int, np.integer)) or nframes < 0:
+        raise ValueError("%s: nframes is a non-negative int or None, not %r" % (who, nframes))
+    if start_frame + nframes > total:
+        raise ValueError("%s: frames [%d, %d) reach past the result's %d" % (who, start_frame, start_frame + nframes, total))
+    return factor, int(start_frame), int(nframes)
+
+
+def convolve_into(buf: N.DeviceBuffer, byte_offset: int, sample: Sample, ir: Sample, factor: Optional[float] = None, start_frame: int = 0,
+                  nframes: Optional[int] = None) -> int:
+    """Frames ``[start_frame, start_frame + nframes)`` of ``convolve(sample, ir, factor)`` into the caller's device buffer from byte
+    ``byte_offset`` on (``nframes`` None: to the result's end); returns the frames written.  Asynchronous; the buffer may not overlap
+    ``sample``'s or ``ir``'s."""
+    factor, start_frame, nframes = _convolve_call("convolve_into", sample, ir, factor, start_frame, nframes)
+    if nframes:
+        N.check(N.lib().sh_pcm_convolve(sample._device().handle, 0, len(sample), sample.nchannels, sample.samplewidth, ir._device().handle, 0, len(ir),
+                                        ir.nchannels, factor, start_frame, nframes, buf.handle, byte_offset))
+    return nframes
+
+
+def convolve(sample: Sample, ir: Sample, factor: Optional[float] = None, start_frame: int = 0, nframes: Optional[int] = None) -> Sample:
+    """``sample`` through the impulse response ``ir`` -- a room, a plate, a cabinet, any FIR filter -- as a new ``Sample``, computed in HBM
+    in the direct form and EXACT: per channel, frame ``i`` is ``fbound(factor * sum of ir[k] * sample[i - k])``, the sum the exact integer
+    and ``fbound`` ``audioop.mul``'s last step (clamp, then floor), so the bytes are those of ``numpy.convolve`` on int64 and that one
+    rounding.  The whole result has ``len(sample) + len(ir) - 1`` frames; ``start_frame`` and ``nframes`` choose a window of it, whose bytes
+    are that slice of the whole result's.  ``factor`` None: ``1 / 2 ** (8 * samplewidth - 1)``, a response at full scale being about
+    unity.  A mono response goes over every channel; a stereo one needs a stereo sample, left over left and right over right.  Widths 1
+    and 2, up to 2**22 taps.  The input is read only: a locked one is fine."""
+    factor, start_frame, nframes = _convolve_call("convolve", sample, ir, factor, start_frame, nframes)
+    out = Sample(name=sample.name, samplerate=sample.samplerate, nchannels=sample.nchannels, samplewidth=sample.samplewidth)
+    if nframes:
+        nbytes = nframes * sample.nchannels * sample.samplewidth
+        buf = N.DeviceBuffer(nbytes)
+        convolve_into(buf, 0, sample, ir, factor, start_frame, nframes)
+        out._set_device(buf, nbytes)
+    return out
+
+
 class SongStems:
     """The stems of a window of a song of tracks, made by ``CompiledSequence.stems``: every bus of the desk as a ``Sample`` of the window's
     length, all from one launch into one device buffer.  ``tracks[t]``: track ``t`` as its bus takes it -- behind its gain, its fader moves

@@ -1082,6 +1082,20 @@ class Sample:
         self._set_device(dst, n)
         return self
 
+    def convolve(self, ir: "Sample", factor: Optional[float] = None, tail: bool = True) -> "Sample":
+        """Run the sample through the impulse response ``ir`` (a room, a plate, a cabinet, any FIR filter), in place and exact:
+        ``mixer.convolve(self, ir, factor)``'s bytes.  ``factor`` None: ``1 / 2 ** (8 * samplewidth - 1)``.  ``tail=True`` keeps the
+        ``len(ir) - 1`` frames that ring on behind the sample's end, ``tail=False`` the first ``len(self)`` frames.  Widths 1 and 2."""
+        self._check_writable()
+        self._check_gpu_width("convolve")
+        from .mixer import convolve                             # (lazily: mixer imports this module)
+        out = convolve(self, ir, factor, 0, None if tail else len(self))
+        if len(out):
+            self._set_device(out._device(), len(out) * self.__nchannels * self.__samplewidth)
+        else:
+            self._set_host(b"")
+        return self
+
     def peak(self) -> int:
         """Maximum absolute sample value (audioop.max)."""
         self._check_gpu_width("peak")
