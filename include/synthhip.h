@@ -1097,6 +1097,24 @@ int sh_pcm_extent_blocks(const sh_buf* in, size_t sample_offset, size_t nframes,
 int sh_pcm_convolve(const sh_buf* in, size_t in_off, uint64_t in_frames, int nch, int width, const sh_buf* ir, size_t ir_off, uint32_t ir_frames,
                     int ir_nch, double factor, uint64_t first, uint64_t nframes, sh_buf* out, size_t out_off);
 
+/* ---- Sample.resample_fir: a rational, band-limited sample-rate conversion of PCM in device memory -- zero-stuff by `up`, filter with
+ * integer taps, keep every `down`-th frame -- in polyphase form and EXACT (csrc/pcmresample.hpp has the contract).  The input:
+ * in_frames frames of nch (1 or 2) interleaved channels of `width` (1 or 2) bytes from byte in_off of `in` on; the taps: ntaps
+ * (1 .. 2^22) int16 values from byte taps_off of `taps` on, ONE bank for every channel, 16 bits whatever `width` is.  The result has
+ * sh_pcm_resample_fir_frames(in_frames, up, down) = ceil(in_frames * up / down) frames of nch channels: per channel and frame j the
+ * exact integer sum over k of taps[k] * u[j * down + delay - k], u being the input with up - 1 zeros behind every frame and zeros
+ * outside it, then ONE rounding, audioop.mul's: fbound(sum * factor).  up and down need not be coprime.  The bytes depend on the input,
+ * the taps, up, down, delay and factor alone.  The call writes frames [first, first + nframes) of the result to byte out_off of `out`
+ * on: that slice of the whole result's bytes.  All offsets are BYTES, and any byte will do.  Asynchronous on the library's stream, as
+ * sh_pcm_convolve: two launches (the taps of every phase to float64 rows in the library's scratch, then the arithmetic).
+ * SH_ERR_INVALID, each with a message of its own and before anything is launched or written: a width other than 1 or 2, nch not 1
+ * or 2, ntaps == 0 or above 2^22, up or down 0, up above 4096, a ratio whose stride (down, times ceil(8 / up) where up < 8) times 63
+ * plus 1024 exceeds 32768 frames (convert in two steps), delay >= ntaps, a factor that is not finite, a window past the result, an
+ * operand that reaches past its buffer, out overlapping in or taps, a NULL buffer.  An empty window succeeds and launches nothing. */
+int sh_pcm_resample_fir(const sh_buf* in, size_t in_off, uint64_t in_frames, int nch, int width, const sh_buf* taps, size_t taps_off, uint32_t ntaps,
+                        uint32_t up, uint32_t down, uint32_t delay, double factor, uint64_t first, uint64_t nframes, sh_buf* out, size_t out_off);
+uint64_t sh_pcm_resample_fir_frames(uint64_t in_frames, uint32_t up, uint32_t down);   /* pure, works without a device */
+
 /* ---- Sample.resample -> audioop.ratecv(frames, width, nchannels, inrate, outrate, None) */
 size_t sh_resample_out_frames(size_t in_frames, int inrate, int outrate);
 /* width 1/2/4 integer PCM (bit-exact audioop arithmetic); is_float!=0: float32 PCM (width must be 4) */

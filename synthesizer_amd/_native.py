@@ -123,6 +123,24 @@ PCM_PART_SAMPLES = 8192                                                         
 PCM_FIR_MAX_TAPS = 1 << 22                                                            # shpf::MAX_TAPS (csrc/pcmfir.hpp): up to here the float64 sum is the integer sum
 PCM_FIR_TILE_FRAMES = 2048                                                            # shpf::TILE_FRAMES: the output frames of one workgroup of sh_pcm_convolve
 PCM_FIR_TAP_CHUNK = 1024                                                              # shpf::TAP_CHUNK: the taps under one staged span of the input
+PCM_RESAMPLE_MAX_TAPS = 1 << 22                                                       # shpr::MAX_TAPS (csrc/pcmresample.hpp)
+PCM_RESAMPLE_MAX_UP = 4096                                                            # shpr::MAX_UP: the largest `up` of sh_pcm_resample_fir
+PCM_RESAMPLE_LANE_OUTPUTS = 8                                                         # shpr::LANE_OUTPUTS: R, the outputs of one lane
+PCM_RESAMPLE_BLOCK_GROUPS = 64                                                        # shpr::BLOCK_GROUPS: the groups (of P = copies * up outputs) of one wave
+PCM_RESAMPLE_WAVES = 4                                                                # shpr::WAVES: of a workgroup; with fewer than 4 residue chunks it owns up to 4 blocks
+PCM_RESAMPLE_STEP_CHUNK = 1024                                                        # shpr::STEP_CHUNK: the steps under one staged span of the input
+PCM_RESAMPLE_STEP_UNROLL = 2                                                          # shpr::STEP_UNROLL: the rows' length is a multiple of it
+PCM_RESAMPLE_STAGED_SAMPLES = 32768                                                   # shpr::STAGED_SAMPLES: the staged span's bound
+
+
+def pcm_resample_copies(up: int) -> int:
+    """shpr::copies: the periods of `up` outputs that make one group (P = copies * up >= 8 outputs, a stride of copies * down frames)"""
+    return 1 if up >= PCM_RESAMPLE_LANE_OUTPUTS else -(-PCM_RESAMPLE_LANE_OUTPUTS // up)
+
+
+def pcm_resample_stride_fits(up: int, down: int) -> bool:
+    """shpr::stride_fits: whether the 64 lanes of a wave, copies * down frames apart, lie inside one staged span"""
+    return (PCM_RESAMPLE_BLOCK_GROUPS - 1) * pcm_resample_copies(up) * down + PCM_RESAMPLE_STEP_CHUNK <= PCM_RESAMPLE_STAGED_SAMPLES
 
 
 class MixLevel(NamedTuple):
@@ -274,6 +292,9 @@ _SIGNATURES = {
                                        C.c_size_t]),
     "sh_pcm_convolve": (C.c_int, [_P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint32, C.c_int, C.c_double, C.c_uint64, C.c_uint64,
                                   _P, C.c_size_t]),
+    "sh_pcm_resample_fir": (C.c_int, [_P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
+                                      C.c_uint64, C.c_uint64, _P, C.c_size_t]),
+    "sh_pcm_resample_fir_frames": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
     "sh_resample_out_frames": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int]),
     "sh_resample": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_size_t)]),
     "sh_resample_span": (C.c_int, [C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

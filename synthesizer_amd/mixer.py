@@ -1038,6 +1038,108 @@ def convolve(sample: Sample, ir: Sample, factor: Optional[float] = None, start_f
     return out
 
 
+def lowpass_taps(up: int, down: int, zero_crossings: int = 16, beta: float = 8.6) -> np.ndarray:
+    """The default tap bank of ``resample_fir`` for the ratio ``up / down``, designed on the host: a Kaiser-windowed sinc cut at the lower
+    of the two Nyquist frequencies, as int16 with unity at ``2**14`` -- ``q = max(up, down)``, ``m = 2 * zero_crossings * q + 1`` taps,
+    ``h[k] = rint(2**14 * (up / q) * sinc((k - (m - 1) / 2) / q) * kaiser(m, beta)[k])``.  Symmetric; its largest tap is 16384 where
+    ``up >= down``.  With ``factor = 2**-14`` and ``delay = (m - 1) // 2`` the converted signal keeps its level and its place in time."""
+    for name, v in (("up", up), ("down", down), ("zero_crossings", zero_crossings)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError("lowpass_taps: %s is a positive int, not %r" % (name, v))
+    q = max(int(up), int(down))
+    m = 2 * int(zero_crossings) * q + 1
+    if m > N.PCM_RESAMPLE_MAX_TAPS:
+        raise ValueError("lowpass_taps: %d taps: at most 2**22 = %d keep the sum exact" % (m, N.PCM_RESAMPLE_MAX_TAPS))
+    k = np.arange(m, dtype=np.float64)
+    return np.rint(2.0 ** 14 * (int(up) / q) * np.sinc((k - (m - 1) / 2) / q) * np.kaiser(m, float(beta))).astype(np.int16)
+
+
+def _resample_fir_call(who: str, sample: Sample, samplerate, taps, factor, delay, start_frame, nframes):
+    """what a conversion refuses, before any call into the library: ``(up, down, taps, factor, delay, start_frame, nframes)`` of the checked
+    call, ``taps`` a 16-bit mono ``Sample``"""
+    if isinstance(samplerate, bool) or not isinstance(samplerate, (int, np.integer)) or samplerate < 1:
+        raise ValueError("%s: samplerate is a positive int, not %r" % (who, samplerate))
+    if sample.nchannels not in (1, 2):
+        raise ValueError("%s: mono and stereo only, not %d channels" % (who, sample.nchannels))
+    if sample.samplewidth in (3, 4):
+        raise NotImplementedError("%s: %d-byte samples are not built: the exact sum needs more than a float64 there (make_16bit() first)"
+                                  % (who, sample.samplewidth))
+    if sample.samplewidth not in (1, 2):
+        raise ValueError("%s: samples of 1 or 2 bytes, not %d" % (who, sample.samplewidth))
+    g = math.gcd(int(samplerate), sample.samplerate)
+    up, down = int(samplerate) // g, sample.samplerate // g
+    if up > N.PCM_RESAMPLE_MAX_UP:
+        raise ValueError("%s: %d Hz to %d Hz is %d/%d: up is at most %d (convert in two steps)" % (who, sample.samplerate, samplerate, up, down, N.PCM_RESAMPLE_MAX_UP))
+    if not N.pcm_resample_stride_fits(up, down):
+        raise ValueError("%s: %d Hz to %d Hz is %d/%d: a stride of %d frames is too long for one step (convert in two steps)"
+                         % (who, sample.samplerate, samplerate, up, down, N.pcm_resample_copies(up) * down))
+    if taps is None:
+        taps = lowpass_taps(up, down)
+    if isinstance(taps, np.ndarray):
+        if taps.dtype != np.int16 or taps.ndim != 1:
+            raise ValueError("%s: taps are a one-dimensional int16 array, not %s of %d dimensions" % (who, taps.dtype, taps.ndim))
+        taps = Sample.from_raw_frames(np.ascontiguousarray(taps).tobytes(), 2, int(samplerate), 1)
+    elif not isinstance(taps, Sample):
+        raise ValueError("%s: taps are None, a numpy int16 array or a 16-bit mono Sample, not %r" % (who, type(taps).__name__))
+    elif taps.samplewidth != 2 or taps.nchannels != 1:
+        raise ValueError("%s: taps are a 16-bit mono Sample, not %d bytes and %d channels (a stereo bank is not built)" % (who, taps.samplewidth, taps.nchannels))
+    m = len(taps)
+    if m == 0:
+        raise ValueError("%s: no taps" % who)
+    if m > N.PCM_RESAMPLE_MAX_TAPS:
+        raise ValueError("%s: %d taps: at most 2**22 = %d keep the sum exact" % (who, m, N.PCM_RESAMPLE_MAX_TAPS))
+    factor = 2.0 ** -14 if factor is None else float(factor)
+    if not math.isfinite(factor):
+        raise ValueError("%s: the factor %r is not finite" % (who, factor))
+    if delay is None:
+        delay = (m - 1) // 2
+    if isinstance(delay, bool) or not isinstance(delay, (int, np.integer)) or not 0 <= delay < m:
+        raise ValueError("%s: delay is an int in [0, %d), not %r" % (who, m, delay))
+    total = -(-len(sample) * up // down)
+    if isinstance(start_frame, bool) or not isinstance(start_frame, (int, np.integer)) or start_frame < 0:
+        raise ValueError("%s: start_frame is a non-negative int, not %r" % (who, start_frame))
+    if nframes is None:
+        nframes = max(total - start_frame, 0)
+    if isinstance(nframes, bool) or not isinstance(nframes, (int, np.integer)) or nframes < 0:
+        raise ValueError("%s: nframes is a non-negative int or None, not %r" % (who, nframes))
+    if start_frame + nframes > total:
+        raise ValueError("%s: frames [%d, %d) reach past the result's %d" % (who, start_frame, start_frame + nframes, total))
+    return up, down, taps, factor, int(delay), int(start_frame), int(nframes)
+
+
+def resample_fir_into(buf: N.DeviceBuffer, byte_offset: int, sample: Sample, samplerate: int, taps=None, factor: Optional[float] = None,
+                      delay: Optional[int] = None, start_frame: int = 0, nframes: Optional[int] = None) -> int:
+    """Frames ``[start_frame, start_frame + nframes)`` of ``resample_fir(sample, samplerate, taps, factor, delay)`` into the caller's device
+    buffer from byte ``byte_offset`` on (``nframes`` None: to the result's end); returns the frames written.  Asynchronous; the buffer may
+    not overlap ``sample``'s or the taps'."""
+    up, down, taps, factor, delay, start_frame, nframes = _resample_fir_call("resample_fir_into", sample, samplerate, taps, factor, delay, start_frame, nframes)
+    if nframes:
+        N.check(N.lib().sh_pcm_resample_fir(sample._device().handle, 0, len(sample), sample.nchannels, sample.samplewidth, taps._device().handle, 0, len(taps),
+                                            up, down, delay, factor, start_frame, nframes, buf.handle, byte_offset))
+    return nframes
+
+
+def resample_fir(sample: Sample, samplerate: int, taps=None, factor: Optional[float] = None, delay: Optional[int] = None, start_frame: int = 0,
+                 nframes: Optional[int] = None) -> Sample:
+    """``sample`` converted to ``samplerate`` by a band-limited, rational resampler, as a new ``Sample``, computed in HBM and EXACT: with
+    ``up / down`` the two rates over their gcd, per channel frame ``j`` is ``fbound(factor * sum of taps[k] * u[j * down + delay - k])``, ``u``
+    being the sample with ``up - 1`` zeros behind every frame -- the sum the exact integer, ``fbound`` ``audioop.mul``'s last step -- so the
+    bytes are those of ``numpy.convolve`` on int64 over the stuffed signal, every ``down``-th frame of it, and that one rounding.  The whole
+    result has ``ceil(len(sample) * up / down)`` frames; ``start_frame`` and ``nframes`` choose a window, whose bytes are that slice of the whole
+    result's.  ``taps`` None: ``lowpass_taps(up, down)``; otherwise a numpy int16 array or a 16-bit mono ``Sample`` of up to 2**22 taps, one
+    bank for every channel.  ``factor`` None: ``2**-14``, the default bank's unity; ``delay`` None: ``(len(taps) - 1) // 2``, a symmetric
+    bank's centre.  Widths 1 and 2; ``up`` at most 4096.  The input is read only: a locked one is fine.  (``Sample.resample`` and ``speed``
+    remain ``audioop.ratecv``'s linear interpolation, byte for byte.)"""
+    up, down, taps, factor, delay, start_frame, nframes = _resample_fir_call("resample_fir", sample, samplerate, taps, factor, delay, start_frame, nframes)
+    out = Sample(name=sample.name, samplerate=int(samplerate), nchannels=sample.nchannels, samplewidth=sample.samplewidth)
+    if nframes:
+        nbytes = nframes * sample.nchannels * sample.samplewidth
+        buf = N.DeviceBuffer(nbytes)
+        resample_fir_into(buf, 0, sample, samplerate, taps, factor, delay, start_frame, nframes)
+        out._set_device(buf, nbytes)
+    return out
+
+
 class SongStems:
     """The stems of a window of a song of tracks, made by ``CompiledSequence.stems``: every bus of the desk as a ``Sample`` of the window's
     length, all from one launch into one device buffer.  ``tracks[t]``: track ``t`` as its bus takes it -- behind its gain, its fader moves

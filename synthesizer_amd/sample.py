@@ -1372,6 +1372,23 @@ class Sample:
         self.__samplerate = samplerate
         return self
 
+    def resample_fir(self, samplerate: int, taps=None, factor: Optional[float] = None, delay: Optional[int] = None) -> "Sample":
+        """Resample to a different rate through a band-limited polyphase FIR, in place and exact: ``mixer.resample_fir(self, samplerate,
+        taps, factor, delay)``'s bytes (``taps`` None: ``mixer.lowpass_taps`` of the ratio, a Kaiser-windowed sinc).  No tone above the
+        new Nyquist frequency folds back and the top of the band keeps its level, which ``resample`` -- ``audioop.ratecv``'s linear
+        interpolation, byte for byte -- does not promise.  The same rate with ``taps`` None leaves the sample as it is.  Widths 1 and 2."""
+        self._check_writable()
+        if samplerate == self.__samplerate and taps is None:
+            return self
+        from .mixer import resample_fir                         # (lazily: mixer imports this module; it refuses widths 3 and 4)
+        out = resample_fir(self, samplerate, taps, factor, delay)
+        if len(out):
+            self._set_device(out._device(), len(out) * self.__nchannels * self.__samplewidth)
+        else:
+            self._set_host(b"")
+        self.__samplerate = int(samplerate)
+        return self
+
 
 class LevelMeter:
     """Sound level tracker on the decibel scale (0 dB = full scale) with peak hold: a peak stays for 0.4 s of audio,
