@@ -1115,6 +1115,27 @@ int sh_pcm_resample_fir(const sh_buf* in, size_t in_off, uint64_t in_frames, int
                         uint32_t up, uint32_t down, uint32_t delay, double factor, uint64_t first, uint64_t nframes, sh_buf* out, size_t out_off);
 uint64_t sh_pcm_resample_fir_frames(uint64_t in_frames, uint32_t up, uint32_t down);   /* pure, works without a device */
 
+/* ---- Sample.limit: a look-ahead peak limiter (a brick wall) over PCM in device memory, EXACT in integers (csrc/pcmlimit.hpp has the
+ * contract).  The input: in_frames frames of nch (1 or 2) interleaved channels of `width` (1, 2 or 4) bytes from byte in_off of `in`
+ * on.  With ONE = 2^30 and HI = 2^(8 width - 1) - 1, per frame i: p = the largest magnitude of the frame's channels (one gain per
+ * frame: the channels are linked); g[i] = ONE where p <= ceiling, else floor(ceiling * ONE / p);
+ *     G[i] = min(ONE, min over j >= i of g[j] + (j - i) * s_a, min over j < i of g[j] + (i - j) * s_r),
+ * s_a = slope(attack_frames), s_r = slope(release_frames), slope(f) = ONE where f <= 1, else ceil(ONE / f) -- a linear ramp down in
+ * front of a peak and a linear ramp up behind it; and the sample is (x * G[i]) >> 30, the floor of the signed 64-bit product.  No
+ * float anywhere.  G[i] <= g[i], so no sample of the result exceeds the ceiling in magnitude; where G[i] == ONE the frame is
+ * untouched.  The bytes depend on the input, ceiling, attack_frames and release_frames alone.  The call writes frames [first, first +
+ * nframes) of the result (which has in_frames frames) to byte out_off of `out` on and their gains G as uint32 to byte gain_off of
+ * `gain` on: that slice of the whole result's bytes -- peaks outside the window still shape the gain inside it.  `out` or `gain` may
+ * be NULL, not both.  IN PLACE: `out` may be exactly the window's own bytes of the input (out's address == in's + first frames).
+ * All offsets are BYTES, and any byte will do.  Asynchronous on the library's stream, as sh_pcm_convolve: two launches (two
+ * summaries per tile of 2048 frames into the library's scratch, then one workgroup per tile of the window).
+ * SH_ERR_INVALID, each with a message of its own and before anything is launched or written: a width other than 1, 2 or 4, nch not
+ * 1 or 2, a ceiling of 0 or above HI, attack_frames or release_frames above 2^20, a window past in_frames, an operand that reaches
+ * past its buffer, out overlapping in in any way but exactly the window's own bytes, gain overlapping in or out, both destinations
+ * NULL, a NULL input.  An empty window succeeds and launches nothing. */
+int sh_pcm_limit(const sh_buf* in, size_t in_off, uint64_t in_frames, int nch, int width, uint32_t ceiling, uint32_t attack_frames,
+                 uint32_t release_frames, uint64_t first, uint64_t nframes, sh_buf* out, size_t out_off, sh_buf* gain, size_t gain_off);
+
 /* ---- Sample.resample -> audioop.ratecv(frames, width, nchannels, inrate, outrate, None) */
 size_t sh_resample_out_frames(size_t in_frames, int inrate, int outrate);
 /* width 1/2/4 integer PCM (bit-exact audioop arithmetic); is_float!=0: float32 PCM (width must be 4) */

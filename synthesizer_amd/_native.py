@@ -131,6 +131,9 @@ PCM_RESAMPLE_WAVES = 4                                                          
 PCM_RESAMPLE_STEP_CHUNK = 1024                                                        # shpr::STEP_CHUNK: the steps under one staged span of the input
 PCM_RESAMPLE_STEP_UNROLL = 2                                                          # shpr::STEP_UNROLL: the rows' length is a multiple of it
 PCM_RESAMPLE_STAGED_SAMPLES = 32768                                                   # shpr::STAGED_SAMPLES: the staged span's bound
+PCM_LIMIT_ONE = 1 << 30                                                               # shpl::ONE (csrc/pcmlimit.hpp): unity of sh_pcm_limit's gains
+PCM_LIMIT_TILE_FRAMES = 2048                                                          # shpl::TILE_FRAMES: the frames of one workgroup of sh_pcm_limit, on the sample's own grid
+PCM_LIMIT_MAX_FRAMES = 1 << 20                                                        # shpl::MAX_FRAMES: the longest attack and the longest release
 
 
 def pcm_resample_copies(up: int) -> int:
@@ -295,6 +298,8 @@ _SIGNATURES = {
     "sh_pcm_resample_fir": (C.c_int, [_P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
                                       C.c_uint64, C.c_uint64, _P, C.c_size_t]),
     "sh_pcm_resample_fir_frames": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    "sh_pcm_limit": (C.c_int, [_P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P, C.c_size_t, _P,
+                               C.c_size_t]),
     "sh_resample_out_frames": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int]),
     "sh_resample": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_size_t)]),
     "sh_resample_span": (C.c_int, [C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

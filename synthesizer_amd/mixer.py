@@ -1038,6 +1038,80 @@ def convolve(sample: Sample, ir: Sample, factor: Optional[float] = None, start_f
     return out
 
 
+def _limit_call(who: str, sample: Sample, ceiling, attack_frames, release_frames, start_frame, nframes) -> Tuple[int, int, int, int, int]:
+    """what a limiter refuses, before any call into the library: ``(ceiling, attack_frames, release_frames, start_frame, nframes)`` of
+    the checked call"""
+    if sample.nchannels not in (1, 2):
+        raise ValueError("%s: mono and stereo only, not %d channels" % (who, sample.nchannels))
+    if sample.samplewidth == 3:
+        raise NotImplementedError("%s: 3-byte samples are not built" % who)
+    if sample.samplewidth not in (1, 2, 4):
+        raise ValueError("%s: samples of 1, 2 or 4 bytes, not %d" % (who, sample.samplewidth))
+    hi = 2 ** (8 * sample.samplewidth - 1) - 1
+    if isinstance(ceiling, bool) or not isinstance(ceiling, (int, np.integer)) or not 1 <= ceiling <= hi:
+        raise ValueError("%s: the ceiling is an int in [1, %d] (sample steps), not %r" % (who, hi, ceiling))
+    for name, v in (("attack_frames", attack_frames), ("release_frames", release_frames)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= N.PCM_LIMIT_MAX_FRAMES:
+            raise ValueError("%s: %s is an int in [0, 2**20 = %d], not %r" % (who, name, N.PCM_LIMIT_MAX_FRAMES, v))
+    total = len(sample)
+    if isinstance(start_frame, bool) or not isinstance(start_frame, (int, np.integer)) or start_frame < 0:
+        raise ValueError("%s: start_frame is a non-negative int, not %r" % (who, start_frame))
+    if nframes is None:
+        nframes = max(total - start_frame, 0)
+    if isinstance(nframes, bool) or not isinstance(nframes, (int, np.integer)) or nframes < 0:
+        raise ValueError("%s: nframes is a non-negative int or None, not %r" % (who, nframes))
+    if start_frame + nframes > total:
+        raise ValueError("%s: frames [%d, %d) reach past the sample's %d" % (who, start_frame, start_frame + nframes, total))
+    return int(ceiling), int(attack_frames), int(release_frames), int(start_frame), int(nframes)
+
+
+def limit_into(buf: N.DeviceBuffer, byte_offset: int, sample: Sample, ceiling: int, attack_frames: int, release_frames: int, start_frame: int = 0,
+               nframes: Optional[int] = None) -> int:
+    """Frames ``[start_frame, start_frame + nframes)`` of ``limit(sample, ceiling, attack_frames, release_frames)`` into the caller's
+    device buffer from byte ``byte_offset`` on (``nframes`` None: to the sample's end); returns the frames written.  Asynchronous; the
+    buffer may not overlap ``sample``'s -- except as exactly the window's own bytes of it, which is the call in place."""
+    ceiling, attack_frames, release_frames, start_frame, nframes = _limit_call("limit_into", sample, ceiling, attack_frames, release_frames, start_frame, nframes)
+    if nframes:
+        N.check(N.lib().sh_pcm_limit(sample._device().handle, 0, len(sample), sample.nchannels, sample.samplewidth, ceiling, attack_frames, release_frames,
+                                     start_frame, nframes, buf.handle, byte_offset, None, 0))
+    return nframes
+
+
+def limit(sample: Sample, ceiling: int, attack_frames: int, release_frames: int, start_frame: int = 0, nframes: Optional[int] = None) -> Sample:
+    """``sample`` under a look-ahead peak limiter -- a brick wall at ``ceiling`` sample steps -- as a new ``Sample``, computed in HBM and
+    EXACT in integers.  With ``ONE = 2**30``, per frame: ``p`` the largest magnitude of the frame's channels (one gain per frame, so
+    the stereo image holds), ``g = ONE`` where ``p <= ceiling``, else ``ceiling * ONE // p``; the gain ``G[i]`` is the smallest of
+    ``ONE``, ``g[j] + (j - i) * s_a`` over the frames ``j >= i`` and ``g[j] + (i - j) * s_r`` over the frames ``j < i`` -- a linear ramp down
+    over about ``attack_frames`` in front of a peak, a linear ramp up over about ``release_frames`` behind it, ``s = ONE`` for 0 or 1
+    frames and else ``ceil(ONE / frames)``; and the sample is ``(x * G[i]) >> 30``.  No sample of the result exceeds the ceiling in
+    magnitude, and a frame whose gain is ``ONE`` is untouched.  ``start_frame`` and ``nframes`` choose a window, whose bytes are that slice
+    of the whole result's: peaks outside the window still shape the gain inside it.  Widths 1, 2 and 4; attack and release up to
+    2**20 frames.  The input is read only: a locked one is fine."""
+    ceiling, attack_frames, release_frames, start_frame, nframes = _limit_call("limit", sample, ceiling, attack_frames, release_frames, start_frame, nframes)
+    out = Sample(name=sample.name, samplerate=sample.samplerate, nchannels=sample.nchannels, samplewidth=sample.samplewidth)
+    if nframes:
+        nbytes = nframes * sample.nchannels * sample.samplewidth
+        buf = N.DeviceBuffer(nbytes)
+        limit_into(buf, 0, sample, ceiling, attack_frames, release_frames, start_frame, nframes)
+        out._set_device(buf, nbytes)
+    return out
+
+
+def limit_gain(sample: Sample, ceiling: int, attack_frames: int, release_frames: int, start_frame: int = 0, nframes: Optional[int] = None) -> np.ndarray:
+    """The gain-reduction trace of ``limit``: ``G`` over the window as a numpy ``uint32`` array, one value per frame, ``2**30`` being unity
+    (``G / 2**30`` is what a meter draws).  Nothing of the sample is written.  Synchronous: the array is copied back."""
+    ceiling, attack_frames, release_frames, start_frame, nframes = _limit_call("limit_gain", sample, ceiling, attack_frames, release_frames, start_frame, nframes)
+    if not nframes:
+        return np.zeros(0, dtype=np.uint32)
+    plane = N.DeviceBuffer(nframes * 4)
+    try:
+        N.check(N.lib().sh_pcm_limit(sample._device().handle, 0, len(sample), sample.nchannels, sample.samplewidth, ceiling, attack_frames, release_frames,
+                                     start_frame, nframes, None, 0, plane.handle, 0))
+        return plane.download(np.uint32, nframes)
+    finally:
+        plane.free()
+
+
 def lowpass_taps(up: int, down: int, zero_crossings: int = 16, beta: float = 8.6) -> np.ndarray:
     """The default tap bank of ``resample_fir`` for the ratio ``up / down``, designed on the host: a Kaiser-windowed sinc cut at the lower
     of the two Nyquist frequencies, as int16 with unity at ``2**14`` -- ``q = max(up, down)``, ``m = 2 * zero_crossings * q + 1`` taps,

@@ -1096,6 +1096,41 @@ class Sample:
             self._set_host(b"")
         return self
 
+    def limit(self, ceiling: Optional[int] = None, attack: float = 0.005, release: float = 0.2, ceiling_db: Optional[float] = None) -> "Sample":
+        """A look-ahead peak limiter -- a brick wall -- over the sample, in place in HBM and exact in integers:
+        ``mixer.limit(self, ceiling, attack_frames, release_frames)``'s bytes.  No sample of the result exceeds the ceiling in magnitude;
+        the gain comes down on a linear ramp over ``attack`` seconds in front of a peak and back up over ``release`` seconds behind it,
+        one gain for both channels; frames that need no reduction are untouched.  Seconds become frames by
+        ``int(seconds * samplerate + 0.5)``.  Exactly one of ``ceiling`` (an int, in sample steps) and ``ceiling_db`` (at most 0, relative
+        to full scale: ``int(HI * 10 ** (ceiling_db / 20))``) is given.  Widths 1, 2 and 4."""
+        self._check_writable()
+        if self.__samplewidth == 3:
+            raise NotImplementedError("limit: 3-byte samples are not built")
+        if (ceiling is None) == (ceiling_db is None):
+            raise ValueError("limit: exactly one of ceiling and ceiling_db is given")
+        if ceiling is None:
+            if isinstance(ceiling_db, bool) or not isinstance(ceiling_db, (int, float, np.integer, np.floating)) or not ceiling_db <= 0:
+                raise ValueError("limit: ceiling_db is a number of at most 0, not %r" % (ceiling_db,))
+            ceiling = int((2 ** (8 * self.__samplewidth - 1) - 1) * 10.0 ** (float(ceiling_db) / 20.0))
+        frames = []
+        for name, seconds in (("attack", attack), ("release", release)):
+            if isinstance(seconds, bool) or not isinstance(seconds, (int, float, np.integer, np.floating)) or not 0 <= seconds < float("inf"):
+                raise ValueError("limit: %s is a non-negative number of seconds, not %r" % (name, seconds))
+            frames.append(int(seconds * self.__samplerate + 0.5))
+        from .mixer import limit, limit_into, _limit_call       # (lazily: mixer imports this module)
+        _limit_call("limit", self, ceiling, frames[0], frames[1], 0, None)
+        n = self.__nbytes
+        if not n:
+            return self
+        if self._device().nbytes >= n and not self.__dev_shared:
+            # in place: the kernel reads a tile's frames before it writes them and no others (csrc/pcm_limit.hip), and a Sample's
+            # device buffer is its own -- under mix's conditions (one that a mixer streams from takes the copying form below)
+            limit_into(self.__dev, 0, self, ceiling, frames[0], frames[1])
+            self._set_device(self.__dev, n)                     # (drops the host copy: it is stale now)
+        else:
+            self._set_device(limit(self, ceiling, frames[0], frames[1])._device(), n)
+        return self
+
     def peak(self) -> int:
         """Maximum absolute sample value (audioop.max)."""
         self._check_gpu_width("peak")
